@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- keyframes/sec of the RAMP-VO tracking hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): SingleScale encoder, 640x480 synthetic
 event+frame stream, 96 patches/frame, default.yaml windows (lifetime 13, removal
@@ -9,16 +9,25 @@ event+frame stream, 96 patches/frame, default.yaml windows (lifetime 13, removal
 ``Ramp_vo.__call__`` on an initialised tracker = encoder + patchify + reproject +
 corr + update operator + 2 GN iterations + keyframe management.  The tracker is
 first primed (untimed) until its sliding window is full, so the timed steps run at
-the steady-state graph size (E ~ 40k edges), then stepped for >= 0.6 s (untimed,
-``--clock-warm-s``) so that even a 20-step timed region runs at settled clocks.
-Inputs for all steps are generated and resident in HBM before the timed region.
+the steady-state graph size (E ~ 40k edges), then stepped --clock-warm-max times
+(untimed, ~0.45 s) so that even a 20-step timed region runs at settled clocks.
+Inputs for all steps are generated and resident in HBM before the timed region;
+they are the same from run to run for the same arguments (seeded stream, a fixed
+number of untimed steps), so two builds can be compared output for output.
 
 N > 1: one process per GPU (torchrun), every rank tracks its own independent
 sequence (different seed) -- the path shards by sequence only; the single
 collective is an all_gather of per-rank metrics.  value = total steps of all ranks
 / max-over-ranks time.
 
-Prints ONE JSON line on rank 0, including
+A plain run does only what the headline needs: set up, prime, warm up, time the K
+steps, write the outputs (--dump-outputs) and print the result line (metric, value,
+unit, ms_per_step, dtype, config, ...).  --dump-outputs DIR writes what the last
+timed step left for a caller of the tracker as DIR/<name>.npy (float32 / float64,
+~9 MB; see dump_outputs()).
+
+--full adds everything else behind the timed region, and prints ONE JSON line on
+rank 0 that also carries
   roofline     the fused correlation kernel against the HBM roof: COMPULSORY bytes per launch
                (every referenced feature plane / patch read once, every output written once:
                frac <= 1 by construction) / mean launch time (HIP events on the launch stream,
@@ -31,6 +40,9 @@ Prints ONE JSON line on rank 0, including
                against the reference's own run (tests/golden/ramp_vo_traj_ss.npz): ATE + rel
   cpu_baseline the same steady-state step on the host cores through the CPU oracle
                ("port"), a bounded sample from the identical state
+  config       the fp32 leg (fp32_kfps), the non-pipelined / own-stream / converged rates and their legs
+The options of these legs (--cpu-steps, --parity, --fp32-leg, --inst-steps, --np-steps, --live-steps,
+--probe-every, --handback-frames, --no-kernel-timing) only act with --full.
 """
 import argparse
 import gc
@@ -85,9 +97,16 @@ def parse():
                     help="instrumented steps behind the timed region: events around the update operator, bundle adjustment "
                          "and the front end (roofline_update / roofline_ba / roofline_encoder)")
     ap.add_argument("--clock-warm-s", type=float, default=0.6,
-                    help="untimed steady-state steps for at least this long right before the warm-up steps, so that a "
-                         "short timed region (the driver's --steps 20 is ~30 ms) runs at settled clocks")
-    ap.add_argument("--clock-warm-max", type=int, default=480, help="cap of the clock-warm phase in frames")
+                    help="> 0: --clock-warm-max untimed steady-state steps right before the warm-up steps (~0.45 s at the "
+                         "default workload), so that a short timed region (the driver's --steps 20 is ~30 ms) runs at "
+                         "settled clocks; 0: none.  A fixed count, not a time: the timed steps see the same frames and "
+                         "tracker state from run to run")
+    ap.add_argument("--clock-warm-max", type=int, default=480, help="steps of the clock-warm phase")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg behind the timed region: kernel rooflines, parity, CPU baseline, fp32 leg, "
+                         "non-pipelined / own-stream / live-factor legs (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left for a caller of the tracker as DIR/<name>.npy")
     ap.add_argument("--handback-frames", type=int, default=24,
                     help="frames between the state_dict() hand-back and the converged / live legs (reported as "
                          "legs.after_handback)")
@@ -642,7 +661,7 @@ def fp32_leg(args, traj_fp32):
     north_star's 1e-4 (the fp16 headline is default.yaml's autocast policy, a few 1e-3): a short timed run of this script in a
     process of its own, behind everything else of rank 0 (N = 1).  Returns the keys merged into `config`."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--mixed", "0", "--steps", str(args.fp32_leg), "--warmup", "10",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--mixed", "0", "--steps", str(args.fp32_leg), "--warmup", "10",
            "--cpu-steps", "0", "--parity", "0", "--fp32-leg", "0", "--np-steps", "0", "--live-steps", "0", "--inst-steps", "40",
            "--height", str(args.height), "--width", str(args.width), "--patches", str(args.patches), "--mode", args.mode,
            "--preset", args.preset, "--prime", str(args.prime), "--pipeline", str(args.pipeline)]
@@ -758,6 +777,36 @@ def live_factor_fractions(slam, windows=False):
     return out
 
 
+DUMP_NET_ROWS = 4096            # seeded sample of the hidden state's rows (all of them: ~40k x 384 floats, 62 MB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(slam, out_dir):
+    """what the last timed step left for a caller of the tracker, as out_dir/<name>.npy: the poses [n, 7] and patches
+    [n, M, 3, 3, 3] of the n keyframes kept (pixel coordinates + inverse depth), the factor graph (ii, jj, kk) [3, E], the
+    confidence weights of the last update [E', 2] and a fixed, seeded sample of the hidden state's rows [S, 384] (with
+    the sampled row numbers).  Hands a device-resident state back to the host (settle): call it behind the timed region."""
+    slam.settle()
+    n, net = slam.n, slam.net[0]
+    f32 = lambda t: t.detach().float().cpu().numpy()
+    E = int(net.shape[0])
+    rows = np.sort(np.random.default_rng(0).choice(E, size=min(E, DUMP_NET_ROWS), replace=False))
+    arrays = {"poses": f32(slam.poses_[:n]),
+              "patches": f32(slam.patches_[:n]),
+              "factors": np.stack([slam._ii, slam._jj, slam._kk]).astype(np.float64),
+              "net_sample": f32(net[torch.from_numpy(rows).to(net.device)]),
+              "net_sample_rows": rows.astype(np.float64)}
+    weight = getattr(slam, "last_weight", None)
+    if weight is not None:
+        arrays["weight"] = f32(weight.reshape(-1, 2))
+    nbytes = sum(a.nbytes for a in arrays.values())
+    assert nbytes <= DUMP_MAX_BYTES, "bench.py: %d bytes of outputs" % nbytes
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -822,12 +871,17 @@ def main():
     n_os = n_np                                   # the own-stream leg (inputs produced on the caller's stream: evaluate.run's loop)
     total = args.prime + n_warm + args.warmup + args.steps + n_inst + n_os + n_np + n_alone + (2 * n_live + args.handback_frames if n_live else 0)
     n_cpu = args.cpu_steps + 1 if (solo and args.cpu_steps > 0) else 0
+    # (the stream's length sizes its canvas, so it counts the frames of the --full legs in a plain run too: both runs
+    # track the very same frames up to the end of the timed steps)
     stream = SyntheticStream(args.height, args.width, total + n_cpu + 1, seed=1234 + rank, device=dev)
+    if not args.full:
+        n_inst = n_np = n_alone = n_live = n_os = n_cpu = 0
+        total = args.prime + n_warm + args.warmup + args.steps
     frames = [tuple(x.to(dev) if i < 2 else x for i, x in enumerate(stream.frame(t))) for t in range(total)]
 
     ctimer, etimer, btimer, utimer = CorrTimer(), EncoderTimer(), BaTimer(), UpdateTimer()
     dprobe = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         ctimer.install()
         etimer.install(net)
         btimer.install()
@@ -852,10 +906,10 @@ def main():
     # warm phase: a 57 ms idle GPU right in front of a 25 ms timed region (the driver's --steps 20) is a cold start.
     gc.collect()
     gc.freeze()
-    # clock warm: the same steady-state steps, untimed, until the GPU has been busy for clock_warm_s (a fresh
-    # box idles at low clocks; a 20-step region is ~30 ms)
+    # clock warm: the same steady-state steps, untimed, n_warm of them (~0.45 s at the default workload: a fresh box idles
+    # at low clocks; a 20-step region is ~30 ms).  A count, not a time, so that the timed steps start from the same state
     warm_steps, warm_tic = 0, time.perf_counter()
-    while warm_steps < n_warm and time.perf_counter() - warm_tic < args.clock_warm_s:
+    while warm_steps < n_warm:
         step()
         warm_steps += 1
     torch.cuda.synchronize()
@@ -872,7 +926,8 @@ def main():
     # record costs a ~6 us bubble on its stream (five per step were 1.4 % of the rate).  The update operator, bundle
     # adjustment and the front end are timed in the instrumented pass BEHIND the timed region (same stream of frames).
     dv = getattr(slam, "_dev", None)              # (the fp32 path and unsupported configurations stay host driven)
-    device_step = dprobe is not None and dv is not None and bool(getattr(dv, "active", False))
+    resident = dv is not None and bool(getattr(dv, "active", False))
+    device_step = dprobe is not None and resident
     ctimer.enabled = not device_step             # (host-driven path: the Python-level hooks, every step, as before)
     etimer.enabled = btimer.enabled = utimer.enabled = ctimer.enabled and dprobe is not None
     if dprobe is not None:
@@ -880,7 +935,7 @@ def main():
     # (the live factor count of every timed frame from the host's lazy copy of the device-side sizes -- pinned memory, a few
     # frames old, never waited for: a frame's time is proportional to it and it drifts by +-8 % along the stream, which is
     # most of the spread between two short timed regions)
-    e_lazy = dv.dyn_host.numpy() if device_step else None
+    e_lazy = dv.dyn_host.numpy() if resident else None
     e_seen = []
     legs = {}
     leg = LegStats(slam)
@@ -903,7 +958,8 @@ def main():
     legs["timed"] = leg.summary()
     gate_kind = "signal word stored by the gru launch" if getattr(slam, "_gate_by_flag", False) else "event"
     ctimer.enabled = etimer.enabled = btimer.enabled = utimer.enabled = False
-    fp32_dev = device_step and bool(getattr(dv, "fp32", False)) and not bool(getattr(dv, "x3", False))
+    fp32_dev = resident and bool(getattr(dv, "fp32", False)) and not bool(getattr(dv, "x3", False))
+    dumped = dump_outputs(slam, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     if dprobe is not None and device_step:
         dprobe.mode, etimer.enabled, utimer.enabled = "all", True, fp32_dev
         for _ in range(n_inst):
@@ -922,7 +978,7 @@ def main():
         g = gather_metrics([args.steps / dt, float(E_r), float(n_r), float(slam.poses_[:n_r].double().sum())], dev)
         per_rank = [[round(float(v), 4) for v in row] for row in g.tolist()]
     E1 = graph_size(slam)[0]
-    live = live_factor_fractions(slam)
+    live = live_factor_fractions(slam) if args.full else None
 
     # inputs_ready = "stream": what a caller gets that produces every frame's tensors on ITS stream right before the call
     # -- the reference's evaluate.py resizes each frame there; rampvo_amd.evaluate.run tracks in this mode -- : the tracker
@@ -971,7 +1027,7 @@ def main():
 
     # the state the parity block and the CPU baseline start from: taken BEFORE the live-factor leg changes what the
     # tracker correlates (state_dict() hands a device-resident state back to the host; the next frame re-enters)
-    snapshot = slam.state_dict() if (rank == 0 and ((solo and args.cpu_steps > 0) or (solo and args.parity))) else None
+    snapshot = slam.state_dict() if (args.full and rank == 0 and ((solo and args.cpu_steps > 0) or (solo and args.parity))) else None
     live_leg = None
     if n_live and dprobe is not None and device_step:
         from rampvo_amd import track_dev
@@ -1033,7 +1089,7 @@ def main():
                                                ", device-resident steps (the operator's Linear layers: split-fp16 operands on the "
                                                "f16 matrix cores, fp32 accumulate -- csrc/update_x3.hip; correlation: "
                                                "the same split on the target planes, corr_mfma_kernel<CorrX2>)"
-                                               if (not args.mixed and device_step and not fp32_dev) else "",
+                                               if (not args.mixed and resident and not fp32_dev) else "",
                                                ", frame pipelining off" if not args.pipeline else "",
                                                ", host-driven steps (RAMP_DEVICE_STEP=0)"
                                                if os.environ.get("RAMP_DEVICE_STEP", "1") != "1" else ""])),
@@ -1054,8 +1110,11 @@ def main():
                        # per leg: host step times and the tracker's counters (LegStats): a leg with host_frames > 0 fell back
                        # to the host-driven path, one with max >> p50 contains a stall
                        "legs": legs,
-                       "sharding": "independent sequences, 1 per GPU" if world > 1 else "single sequence"},
+                       "sharding": "independent sequences, 1 per GPU" if world > 1 else "single sequence",
+                       "full": bool(args.full)},
         }
+        if dumped:
+            out["config"]["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if per_rank is not None:
             out["config"]["per_rank_kfps_E_n_chk"] = per_rank
             out["config"]["process_group"] = {"backend": dist.get_backend(), "world": dist.get_world_size()}
@@ -1065,7 +1124,7 @@ def main():
         out["config"]["host_threads"] = {"pool": torch.get_num_threads(), "cpu_quota": hostenv.cpu_quota(),
                                          "logical_cpus": os.cpu_count()}
         rl = ctimer.summary(2 if args.mixed else 4, slam)
-        assert rl is not None or args.no_kernel_timing, "no correlation launch was timed: the roofline hook is stale"
+        assert rl is not None or args.no_kernel_timing or not args.full, "no correlation launch was timed: the roofline hook is stale"
         if rl is not None:
             if live is not None:
                 # factors with at least one patch pixel's window inside the target plane, per pyramid level: the others
@@ -1111,13 +1170,13 @@ def main():
                         val["measured_in"] = ("%d sequential steps behind the sequential pass (alone); next to the tail: the "
                                               "%d-step instrumented pass" % (len(etimer.alone), n_inst))
                 out[key] = val
-        if solo and args.parity:
+        if args.full and solo and args.parity:
             # a failing checker fails the run (rc != 0): a headline without its parity block is not a result
             out["parity"] = parity_block(snapshot, args, cfg_kwargs, net, dev)
             tr = out["parity"].get("trajectory", {})
             if "fp32" in tr:
                 out["ate_vs_oracle"] = tr["fp32"]["ate_vs_reference"]
-        if solo and args.mixed and args.fp32_leg > 0 and _which_config(args, world):
+        if args.full and solo and args.mixed and args.fp32_leg > 0 and _which_config(args, world):
             out["config"].update(fp32_leg(args, out.get("parity", {}).get("trajectory", {}).get("fp32")))
         if n_cpu:
             cpu_frames = [stream.frame(total + i) for i in range(n_cpu)]

@@ -842,7 +842,7 @@ def test_bench_runs_the_fp32_path():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--height", "240", "--width", "320", "--patches", "48",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--height", "240", "--width", "320", "--patches", "48",
                           "--prime", "40", "--warmup", "3", "--steps", "8", "--cpu-steps", "0", "--parity", "0", "--mixed", "0",
                           "--np-steps", "4", "--inst-steps", "8"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -859,7 +859,7 @@ def test_bench_json_contract():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--height", "240", "--width", "320",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--height", "240", "--width", "320",
                           "--patches", "48", "--prime", "40", "--warmup", "3", "--steps", "12", "--cpu-steps", "1"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -897,6 +897,47 @@ def test_bench_json_contract():
     assert tr["fp32"]["rel"] <= 1e-4 and tr["fp32"]["ate_vs_reference"] <= 1e-4 and d["ate_vs_oracle"] <= 1e-4, tr
 
 
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """a plain bench.py run prints the headline only (no leg of --full runs) and --dump-outputs writes what its last timed
+    step left for a caller: float32 / float64 arrays, at most 64 MB, the same in a second run with the same arguments --
+    here a --full one, whose timed path tracks the very same frames"""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    args = ["--height", "240", "--width", "320", "--patches", "48", "--prime", "40", "--clock-warm-max", "30", "--warmup", "3",
+            "--steps", "7", "--cpu-steps", "0", "--parity", "0", "--np-steps", "2", "--inst-steps", "4", "--live-steps", "0"]
+    lines, dumps = [], []
+    for extra in ([], ["--full"]):
+        d = str(tmp_path / ("full" if extra else "plain"))
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + extra + ["--dump-outputs", d],
+                             capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-2000:]
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1
+        lines.append(json.loads(js[0]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    plain, full = lines
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert plain.get(k) is not None, k
+    assert plain["steps"] == 7 and plain["warmup"] == 3 and plain["unit"] == "keyframes/s" and plain["higher_is_better"] is True
+    assert abs(plain["value"] * plain["ms_per_step"] - 1e3) <= 2e-3 * 1e3
+    assert not any(k in plain for k in ("roofline", "roofline_update", "roofline_encoder", "roofline_ba", "parity",
+                                        "cpu_baseline"))
+    assert list(plain["config"]["legs"]) == ["timed"] and plain["config"]["non_pipelined_kfps"] is None
+    assert plain["config"]["full"] is False and full["config"]["full"] is True and "roofline" in full
+    assert full["config"]["non_pipelined_kfps"] > 0
+    a, b = dumps
+    assert set(a) == {"poses", "patches", "factors", "weight", "net_sample", "net_sample_rows"}, sorted(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert all(x.dtype in (np.float32, np.float64) and x.size and np.isfinite(x).all() for x in a.values())
+    assert a["factors"].shape[1] == plain["config"]["edges_end"] and a["poses"].shape == (a["patches"].shape[0], 7)
+    assert plain["config"]["edges"] == full["config"]["edges"]
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_bench_under_torchrun_initialises_rccl():
     """the driver's N > 1 launch line on a one-GPU box: `python -m torch.distributed.run --nproc-per-node 1 bench.py
     --gpus 1 ...` with the default backend -- `init_process_group("nccl", device_id=...)` (RCCL), the two barriers
@@ -915,7 +956,7 @@ def test_bench_under_torchrun_initialises_rccl():
     env.pop("RAMP_DIST_BACKEND", None)
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "1", "--height", "240", "--width", "320", "--patches", "48", "--prime", "40",
+                          "--gpus", "1", "--full", "--height", "240", "--width", "320", "--patches", "48", "--prime", "40",
                           "--steps", "5", "--warmup", "2", "--cpu-steps", "0", "--parity", "0", "--np-steps", "4",
                           "--inst-steps", "8", "--live-steps", "0"],
                          capture_output=True, text=True, timeout=900, cwd=root, env=env)
@@ -948,7 +989,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", RAMP_DIST_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"),
-                          "--gpus", "2", "--height", "240", "--width", "320", "--patches", "48", "--prime", "40",
+                          "--gpus", "2", "--full", "--height", "240", "--width", "320", "--patches", "48", "--prime", "40",
                           "--steps", "12", "--warmup", "2", "--cpu-steps", "0", "--parity", "0", "--np-steps", "4",
                           "--inst-steps", "8", "--live-steps", "0"],
                          capture_output=True, text=True, timeout=900, cwd=root, env=env)

@@ -3,11 +3,12 @@
 envs=()
 while [ "$1" != "--" ] && [ $# -gt 0 ]; do envs+=("$1"); shift; done
 shift
+line=$(mktemp)
 for e in "${envs[@]}"; do
-  env $e python bench.py --cpu-steps 0 --parity 0 --fp32-leg 0 --live-steps 0 "$@" 2>/dev/null | grep '^{' > /tmp/ab_line.json
-  python - "$e" <<'PY'
+  env $e python bench.py --full --cpu-steps 0 --parity 0 --fp32-leg 0 --live-steps 0 "$@" 2>/dev/null | grep '^{' > "$line"
+  python - "$e" "$line" <<'PY'
 import json, sys
-d = json.load(open("/tmp/ab_line.json")); c = d["config"]
+d = json.load(open(sys.argv[2])); c = d["config"]
 u, b, en, r = (d.get(k) or {} for k in ("roofline_update", "roofline_ba", "roofline_encoder", "roofline"))
 print("%-36s %7.1f kf/s np %6s | corr %5.1f upd %5.1f (alone %s) ba %5.1f (alone %s) fe %s (tail %s) | E %s..%s live %s" % (
     sys.argv[1], d["value"], c.get("non_pipelined_kfps"), r.get("mean_launch_us", 0), u.get("mean_call_us", 0), u.get("mean_call_us_alone"),
@@ -15,3 +16,4 @@ print("%-36s %7.1f kf/s np %6s | corr %5.1f upd %5.1f (alone %s) ba %5.1f (alone
     c.get("edges"), c.get("edges_end"), r.get("live_factor_fraction_fine_coarse")))
 PY
 done
+rm -f "$line"

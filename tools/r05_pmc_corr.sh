@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 K=${STEPS:-20}; W=${WARMUP:-5}; L=${LIVE:-40}; I=8
-ARGS="--steps $K --warmup $W --cpu-steps 0 --parity 0 --fp32-leg 0 --np-steps 0 --inst-steps $I --live-steps $L --clock-warm-s 0"
+ARGS="--full --steps $K --warmup $W --cpu-steps 0 --parity 0 --fp32-leg 0 --np-steps 0 --inst-steps $I --live-steps $L --clock-warm-s 0"
 # MIXED=0: the fp32 tracker (corr_mfma_kernel<CorrX2>, rows of 896 floats) -> gpurun_out/r05pmc/corr_traffic_fp32.json
 SUF=""; ROWB=1792; KNAME="corr_mfma_kernel<_Float16, true>"
 if [ "${MIXED:-1}" = "0" ]; then ARGS="$ARGS --mixed 0"; SUF="_fp32"; ROWB=3584; KNAME="corr_mfma_kernel<CorrX2, true>"; fi
