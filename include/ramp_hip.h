@@ -735,9 +735,10 @@ typedef struct ramp_track {
   float *coords;                      /* [E_cap][2][P][P] */
   void *corr;                         /* [E_cap][896] fp16 */
   float *net[3];                      /* [E_cap][384] fp32: [0] the hidden state (in: previous, out: new), [1], [2] scratch */
-  void *fg, *ykk, *hkk, *yij, *hij, *relu_t;      /* (relu_t: unused since the heads moved into the gru launch) */
-  float *sagg_frag;                   /* optional [ramp_upd_softagg_frag_rows(E_cap, max(kk_cap, ij_cap))][3][384]: with it the
-                                       * two SoftAggs run as ramp_upd_softagg + _finish (fg / ykk / yij are then unused)  */
+  void *fg, *ykk, *hkk, *yij, *hij, *relu_t;      /* (relu_t: unused since the heads moved into the gru launch; fg / ykk /
+                                                   * yij: fp32 features only, fp16 steps leave them alone)              */
+  float *sagg_frag;                   /* fp16 features: [ramp_upd_softagg_frag_rows(E_cap, max(kk_cap, ij_cap))][3][384], the
+                                       * two SoftAggs run as ramp_upd_softagg + _finish                                   */
   float *target, *weight;             /* [E_cap][2] */
   /* bundle adjustment */
   void *ba_ws;
@@ -758,14 +759,15 @@ typedef struct ramp_track {
   void *probe[5];
   int32_t E_hint;                     /* optional (> 0): the caller's estimate of the live factor count (E_bound is an upper
                                        * bound): picks the gru launch's tile (64 / 80 rows per workgroup)                    */
-  uint32_t gate_seq;                  /* with gate_flag: the value the update operator's last launch (gru) stores into it  */
+  uint32_t gate_seq;                  /* with gate_flag: the value stored into it where the next frame's front end may start:
+                                       * by the first SoftAgg launch (fp16 features), by a one-thread launch in front of the
+                                       * correlation launch (fp32 features)                                               */
   int32_t feat_fp32;                  /* 0: fp16 features (imap / gmap / fmap rows of 2-byte elements, chunked [h][C/32][w][32] pyramid
                                        * planes, corr [E_cap][896] fp16); 2: fp32 features, chunked planes of split fp16 pairs
                                        * (RAMP_CORR_X2: corr_mfma_kernel<CorrX2>; feat_plain must be 0), everything else as 1;
                                        * 1: fp32 features, planes chunked as [h][C/16][w][16]
                                        * (feat_plain = 0) or plain NHWC, corr [E_cap][896] fp32 by corr_mfma_kernel<float>
-                                       * (RAMP_CORR_F32_MFMA=0: corr_kernel<float>, the reference kernel's summation order, plain
-                                       * planes only), operator csrc/update_x3.hip                                          */
+                                       * or corr_kernel<float> (corr_f32_mfma), operator csrc/update_x3.hip               */
   int32_t feat_plain;                 /* 1: the pyramid planes are plain NHWC [h][w][128] rows instead of the
                                        * chunked [h][C/32][w][32] layout -- feature planes whose width is no multiple of 16 or
                                        * whose height is no multiple of 4 (ramp_pyramid_pack's shapes): corr_mfma_kernel<half, false>  */
@@ -779,6 +781,10 @@ typedef struct ramp_track {
                                        * (ramp/Ramp_vo.py:259-271 shifts them); every reader of `fmap1` rows (correlation, frame
                                        * commit, warm-up) goes through the table; the caller undoes the permutation when it takes
                                        * the buffers back.  NULL: rows are slots                                           */
+  int32_t corr_f32_mfma;              /* feat_fp32 == 1: the correlation kernel -- 1 corr_mfma_kernel<float> (the fp32 matrix
+                                       * cores), 0 corr_kernel<float> (the reference kernel's summation order, plain planes
+                                       * only).  The caller sets it from the mode its features were packed in
+                                       * (rampvo_amd: Patchifier.pack_f32, RAMP_CORR_F32_MFMA)                          */
 } ramp_track;
 
 /* cache warm-up for the next step's correlation kernel: reads the planes of the window's frames and the patch features

@@ -26,14 +26,13 @@ MI355X-first differences that do not change results:
 from collections import OrderedDict
 
 import ctypes
-import os
 import warnings
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import altcorr, fastba, hostenv, lietorch, ops, track_dev
+from . import altcorr, fastba, hostenv, lietorch, ops, switches, track_dev
 from . import projective_ops as pops
 from . import _lib
 from ._lib import RAMP_NHWC, RAMP_NHWC32, kplane
@@ -58,33 +57,22 @@ def _gru_tile_rows(E, device):
     return 80 if r5 < r4 else 64
 
 
-_FE_DELAY_US = int(os.environ.get("RAMP_FE_DELAY_US", "35"))     # A/B switch: 0 = the encoder graph right behind the selection
+_FE_DELAY_US = 35          # the encoder graph held back behind the selection (_fe_delay; 0 measured flat)
 _GATE_FLAG_DELAY_US = 0
 _FE_WAIT_PROBE = False      # (diagnostic, set by tools/fe_wait.py before the tracker is built: events around the main queue's wait for the front end)
 # The front end's "done" is a data dependency (the frame commit reads fe_fmap1 / imap / gmap / patches): the wave that waits
 # for its signal word must not give up while the producer can still arrive.  The time-out is a hang guard only -- 20 s, far
 # beyond any profiler slow-down -- and a wait that does give up still raises sticky status bit 128, on which settle() /
-# lazy_state() raise.  Runtimes that serialise kernels never get here (_kernels_are_serialised: events instead).  The gate
+# lazy_state() raise.  Runtimes that serialise kernels never get here (switches.Switches.flag_waits: events instead).  The gate
 # wait (_gate_wait) keeps its 50 ms: it orders nothing but timing (a front end that starts early is slower, not wrong).
 _FE_DONE_TIMEOUT_US = 20000000
 
 
-def _kernels_are_serialised():
-    """a cross-stream wait by a spinning wave needs the two streams to run CONCURRENTLY.  Under counter collection
-    (rocprofv3 --pmc: ROCPROF_COUNTER_COLLECTION), AMD_SERIALIZE_KERNEL or HIP_LAUNCH_BLOCKING the runtime runs one
-    kernel at a time -- the waiting wave would keep its producer off the GPU until it times out -- so the signal words
-    are not used there: events order the streams"""
-    def on(k):
-        return os.environ.get(k, "0") not in ("", "0")
-    return on("ROCPROF_COUNTER_COLLECTION") or on("AMD_SERIALIZE_KERNEL") or on("HIP_LAUNCH_BLOCKING") or on("RAMP_NO_FLAG_WAITS")
 _LIVE = {}        # device index -> trackers alive on it (Ramp_vo._flag_wait_is_safe)
 
 
 def _live_dec(idx):
     _LIVE[idx] = _LIVE.get(idx, 1) - 1
-
-
-_WARM = os.environ.get("RAMP_WARM", "1") != "0"     # A/B switch: the cache warm-up behind the front end
 
 
 class Ramp_vo:
@@ -170,8 +158,12 @@ class Ramp_vo:
         # state_dict() / the n, m, ii ... properties, which join the tracker's stream first.  rampvo_amd.evaluate.run sets it.
         # RAMP_INPUTS_READY=stream|1 sets the default without touching the caller's code (the reference's evaluate.py with
         # its imports redirected: it reads points_ / colors_ / m only behind its closing update() calls, which join).
-        self.inputs_ready = {"stream": "stream", "1": True}.get(os.environ.get("RAMP_INPUTS_READY", ""), False)
-        self.device_steps = os.environ.get("RAMP_DEVICE_STEP", "1") == "1"     # A/B and test switch
+        sw = switches.read()
+        self.inputs_ready = sw.inputs_ready
+        self.device_steps = sw.device_step       # A/B and test switch
+        # cross-stream orders as signal words looked at by a sleeping wave (False: events -- RAMP_NO_FLAG_WAITS, or a
+        # runtime that runs one kernel at a time, where the waiting wave would keep its producer off the GPU: ADVICE r4)
+        self._flag_waits = sw.flag_waits
         self._edge_tmpl = None
         self._shift_plan = None
         self._cur_stream = None
@@ -252,8 +244,8 @@ class Ramp_vo:
         for ev in (self._ev_fe_done, self._ev_gate, self._ev_in):
             ev.record()                      # torch creates the hipEvent lazily; csrc/track.hip records the raw handle
         self._gate_armed = False
-        # the gate as a signal word the gru launch stores a sequence number into (no event packet between the update
-        # operator's launches: tools/mb/stream_signal.hip); RAMP_GATE_FLAG=0: the event (A/B runs)
+        # the gate as a signal word the step stores a sequence number into (no event packet between the update
+        # operator's launches: tools/mb/stream_signal.hip)
         self._gate_sig, self._gate_seq, self._gate_by_flag = None, 0, False
 
     # ------------------------------------------------------------------ weights
@@ -836,25 +828,23 @@ class Ramp_vo:
         return buf
 
     def _gate_signal(self):
-        """the signal word of the gate, or None (RAMP_GATE_FLAG=0, no signal memory, or 2^31 frames behind us: the event
-        then).  Where in the step the word is stored is csrc/track.hip's RAMP_GATE_AT (default: by the first SoftAgg launch)"""
+        """the signal word of the gate, or None (no flag waits, no signal memory, or 2^31 frames behind us: the event
+        then).  Where in the step the word is stored: csrc/track.hip (fp16: by the first SoftAgg launch)"""
         if self._gate_sig is None:
-            use = os.environ.get("RAMP_GATE_FLAG", "1") != "0" and not _kernels_are_serialised()
             with torch.cuda.device(self.device):          # (the word must live on the tracker's GPU, not the caller's current one)
-                self._gate_sig = track_dev.Signal() if use else False
+                self._gate_sig = track_dev.Signal() if self._flag_waits else False
         sig = self._gate_sig
         return sig if (sig and sig.ptr is not None and self._gate_seq < 0x7FFFFFF0) else None
 
     def _fe_done_to(self, fe, cur, dv):
         """the front end's "done" for the main stream: a word in signal memory stored by a one-thread launch behind the
-        encoder graph and looked at by one sleeping wave in front of the frame commit (RAMP_FE_DONE_FLAG=0, or no signal
-        memory, or a runtime that serialises kernels (_kernels_are_serialised): an event record + stream wait, ~10 us of
+        encoder graph and looked at by one sleeping wave in front of the frame commit (no flag waits -- RAMP_NO_FLAG_WAITS,
+        a runtime that serialises kernels -- or no signal memory: an event record + stream wait, ~10 us of
         packets on the serial chain even when the front end is long done).  The commit READS what the front end wrote, so
         this wait's time-out is a hang guard (20 s), not a scheduling choice"""
         if self._fe_done_sig is None:
-            use = os.environ.get("RAMP_FE_DONE_FLAG", "1") != "0" and not _kernels_are_serialised()
             with torch.cuda.device(self.device):
-                self._fe_done_sig = track_dev.Signal() if use else False
+                self._fe_done_sig = track_dev.Signal() if self._flag_waits else False
         sig = self._fe_done_sig
         # A spinning wave needs its producer to run CONCURRENTLY: the runtime maps streams onto a handful of hardware queues,
         # and a waiter that shares one with its producer would sit in front of it until the hang guard fires.  Two streams of
@@ -933,7 +923,7 @@ class Ramp_vo:
                 self.fe_wait_pairs.append((a, b))
             else:
                 self._fe_done_to(fe, cur, dv)
-            if _WARM and not dv.fp32:
+            if not dv.fp32:
                 # (behind the event: the frame does not wait for it) the window's correlation planes back into the
                 # memory-side cache while the previous frame's bundle adjustment is still running
                 with torch.cuda.stream(fe):

@@ -33,15 +33,11 @@ def kplane(dtype):
 
 
 def corr_f32_mode():
-    """how the tracker computes the correlation volume of fp32 features (RAMP_CORR_F32_MFMA): 2 (default) split fp16 pairs on
-    the f16 matrix cores (corr_mfma_kernel<CorrX2>, chunked planes of pairs); 1 the fp32 matrix cores
+    """how the tracker computes the correlation volume of fp32 features (RAMP_CORR_F32_MFMA, switches.read()): 2 (default)
+    split fp16 pairs on the f16 matrix cores (corr_mfma_kernel<CorrX2>, chunked planes of pairs); 1 the fp32 matrix cores
     (corr_mfma_kernel<float>, chunked fp32 planes); 0 corr_kernel<float>, the reference kernel's summation order, plain planes"""
-    import os
-    try:
-        m = int(os.environ.get("RAMP_CORR_F32_MFMA", "2"))
-    except ValueError:
-        m = 2
-    return m if m in (0, 1, 2) else 2
+    from . import switches
+    return switches.read().corr_f32_mfma
 
 _ERR = {-1: "RAMP_EINVAL (bad argument)", -2: "RAMP_ELAUNCH (HIP launch/runtime error)",
         -3: "RAMP_EWORKSPACE (workspace too small)", -4: "RAMP_EUNSUPPORTED (size/shape not supported)"}

@@ -5,7 +5,6 @@ consumer conv's load path (``pre``) or on the residual-block tail kernel.
 """
 import ctypes
 import threading
-import os
 
 import torch
 import torch.nn as nn
@@ -253,9 +252,6 @@ class Pair:
 # post-InstanceNorm / ReLU activations and the random-init plain tower stay well inside; e4m3's relative precision,
 # 2^-4, does not depend on the scale)
 FP8_ACT_SCALE = 8.0
-# fp32 towers: 3x3 / 7x7 layers at fp32 accuracy on the f16 matrix cores (conv_x3_kernel) instead of the f32 MFMA's direct
-# kernel; False: the exact-product f32 MFMA everywhere (tests compare the two)
-X3 = os.environ.get("RAMP_CONV_X3", "1") != "0"      # env: 0 = the fp32 towers on the f32 MFMA (exact products)
 
 
 def _conv_mode(x, half, direct=False):
@@ -271,10 +267,12 @@ def _conv_mode(x, half, direct=False):
 
 
 def conv2d(x, conv, pre=None, res=None, relu=False, want_stats=False, out_scale=1.0, eps=1e-5, half=False,
-           direct=False):
+           direct=False, x3=True):
     """x [H,W,Cin] NHWC (or a Pending: normalise+ReLU on load).  fp32 in/out, or with ``half``:
     half out and half in (fp32 in allowed for the 16-channel first layer).  Returns y [OH,OW,Cout],
-    or Pending(y, scale, shift) when want_stats (InstanceNorm statistics of y, always fp32)."""
+    or Pending(y, scale, shift) when want_stats (InstanceNorm statistics of y, always fp32).  fp32 with ``x3``: the
+    3x3 / 7x7 layers at fp32 accuracy on the f16 matrix cores (conv_x3_kernel); without: the exact-product f32 MFMA
+    kernel everywhere (RAMP_CONV_X3=0, tests compare the two)"""
     if isinstance(x, Tail):
         x = x.tensor()
     if isinstance(x, Pending):
@@ -284,7 +282,7 @@ def conv2d(x, conv, pre=None, res=None, relu=False, want_stats=False, out_scale=
     mode, code, odt = _conv_mode(x, half, direct)
     cout, _, kh, kw = conv.weight.shape
     stride = conv.stride[0]
-    if mode == "f32" and X3 and kh == kw and lib().ramp_conv2d_stats_blocks(H, W, Cin, cout, kh, stride,
+    if mode == "f32" and x3 and kh == kw and lib().ramp_conv2d_stats_blocks(H, W, Cin, cout, kh, stride,
                                                                            RAMP_F32 | _lib.RAMP_CONV_X3) > 0:
         mode, code = "x3", RAMP_F32 | _lib.RAMP_CONV_X3      # the layer shapes conv_x3_kernel covers (the towers' 3x3 / 7x7 layers)
     wpk, bias = pack_conv_weight(conv, mode)
@@ -311,7 +309,7 @@ def conv2d(x, conv, pre=None, res=None, relu=False, want_stats=False, out_scale=
     return Pending(y, scale, shift)
 
 
-def conv2d_towers(jobs, half, fp8=False):
+def conv2d_towers(jobs, half, fp8=False, x3=True):
     """one layer of every tower: ``jobs`` = [dict(x=, conv=, res=None, relu=False, want_stats=False, out_scale=1.0,
     eps=1e-5)] with the same layer shape.  Two fp16 towers go out as ONE launch of the LDS-tiled kernel
     (ramp_conv2d_nhwc_multi) followed by the statistics' finalize launch where a tower has a norm; anything else
@@ -325,7 +323,7 @@ def conv2d_towers(jobs, half, fp8=False):
                 j["res"] = j["res"].tensor()
         return [conv2d(j["x"].cat() if isinstance(j["x"], Pair) else j["x"], j["conv"], res=j.get("res"),
                        relu=j.get("relu", False), want_stats=j.get("want_stats", False),
-                       out_scale=j.get("out_scale", 1.0), eps=j.get("eps", 1e-5), half=half) for j in jobs]
+                       out_scale=j.get("out_scale", 1.0), eps=j.get("eps", 1e-5), half=half, x3=x3) for j in jobs]
     if not half or len(jobs) > 2:
         return single()
     x0 = jobs[0]["x"]
@@ -430,7 +428,7 @@ def conv2d_towers(jobs, half, fp8=False):
         for tl in written:
             tl.out = None
         if use8:
-            return conv2d_towers(jobs, half, fp8=False)      # a layer shape without an fp8 instantiation: f16 MFMA
+            return conv2d_towers(jobs, half, fp8=False, x3=x3)      # a layer shape without an fp8 instantiation: f16 MFMA
         return single()
     check(rc, "ramp_conv2d_nhwc_multi")
     for tl in written:
@@ -483,21 +481,21 @@ def norm_add_relu(y, skip, fuse=True):
 
 
 # --------------------------------------------------------------------------- towers
-def _res_blocks(blks, xs, norms, half, fp8=False):
+def _res_blocks(blks, xs, norms, half, fp8=False, x3=True):
     """reference ResidualBlock.forward (extractor.py:49-57) for the same block of every tower, one launch per
     conv for all of them.  xs[t]: tensor, or (norm towers, first block) the Pending relu(norm(conv1))."""
     job = lambda t, x, conv, **k: dict(x=x, conv=conv, want_stats=norms[t], **k)
     T = range(len(blks))
     skips = list(xs)
     if blks[0].downsample is not None:
-        skips = conv2d_towers([job(t, xs[t], blks[t].downsample[0]) for t in T], half, fp8)
+        skips = conv2d_towers([job(t, xs[t], blks[t].downsample[0]) for t in T], half, fp8, x3)
         for t in T:
             if norms[t]:
                 skips[t].relu = False            # norm3 has no ReLU behind it
-    y = conv2d_towers([job(t, xs[t], blks[t].conv1, relu=not norms[t]) for t in T], half, fp8)
+    y = conv2d_towers([job(t, xs[t], blks[t].conv1, relu=not norms[t]) for t in T], half, fp8, x3)
     # plain towers: relu(skip + relu(conv2(y))) in the conv's epilogue
     y = conv2d_towers([job(t, y[t], blks[t].conv2, relu=not norms[t], res=None if norms[t] else skips[t])
-                       for t in T], half, fp8)
+                       for t in T], half, fp8, x3)
     return [norm_add_relu(y[t], skips[t]) if norms[t] else y[t] for t in T]
 
 
@@ -508,15 +506,15 @@ def _tower_norms(encs):
     return norms
 
 
-def _first_layer(encs, x, norms, half):
+def _first_layer(encs, x, norms, half, x3=True):
     xs = conv2d_towers([dict(x=x, conv=e.conv1, want_stats=n, relu=not n, eps=e.norm1.eps if n else 1e-5)
-                        for e, n in zip(encs, norms)], half)
+                        for e, n in zip(encs, norms)], half, x3=x3)
     if not half:                                  # fp32 tail kernel takes a materialised skip
         xs = [materialize(v) if isinstance(v, Pending) else v for v in xs]
     return xs
 
 
-def basic_encoder4_towers(encs, x, out_scale=1.0, half=False, fp8=False):
+def basic_encoder4_towers(encs, x, out_scale=1.0, half=False, fp8=False, x3=True):
     """BasicEncoder4._forward of every tower in ``encs`` on one NHWC image x [H,W,Cin_padded] -> [H/4,W/4,out] each
     (``half``: fp16 storage + fp16 MFMA after the first layer's fp32 input).  relu(norm1(conv1)) is never
     materialised: layer1's first conv applies it while loading, the block's tail while adding the skip."""
@@ -524,49 +522,50 @@ def basic_encoder4_towers(encs, x, out_scale=1.0, half=False, fp8=False):
     _scope.cur = (_scope.prepared or _AccArena(x.device)) if (half and _IN_ACC and any(norms)) else None
     _scope.prepared = None
     try:
-        xs = _first_layer(encs, x, norms, half)
+        xs = _first_layer(encs, x, norms, half, x3)
         for li in ("layer1", "layer2"):
             for b in range(2):
-                xs = _res_blocks([getattr(e, li)[b] for e in encs], xs, norms, half, fp8)
-        return conv2d_towers([dict(x=xs[t], conv=e.conv2, out_scale=out_scale, keep=False) for t, e in enumerate(encs)], half, fp8)
+                xs = _res_blocks([getattr(e, li)[b] for e in encs], xs, norms, half, fp8, x3)
+        return conv2d_towers([dict(x=xs[t], conv=e.conv2, out_scale=out_scale, keep=False) for t, e in enumerate(encs)], half, fp8,
+                             x3)
     finally:
         _scope.cur = None
 
 
-def basic_encoder4(enc, x, out_scale=1.0, half=False):
-    return basic_encoder4_towers([enc], x, out_scale, half)[0]
+def basic_encoder4(enc, x, out_scale=1.0, half=False, x3=True):
+    return basic_encoder4_towers([enc], x, out_scale, half, x3=x3)[0]
 
 
 _MS_PAIR = True          # (False: torch.cat copies -- round 4's A/B)
 
 
-def multiscale_encoder4_towers(encs, x, x2, x4, out_scale=1.0, half=False, fp8=False):
+def multiscale_encoder4_towers(encs, x, x2, x4, out_scale=1.0, half=False, fp8=False, x3=True):
     """MultiScaleBasicEncoder4.forward (reference extractor.py:288-311) of every tower on NHWC inputs: x [H,W,16],
     x2 [H/2,W/2,32] and x4 [H/4,W/4,64] (the three super-states) -> [H/4,W/4,out].  The channel
     concatenations are the only non-conv steps; layer2/conv2 are unused, as upstream."""
     norms = _tower_norms(encs)
     _scope.cur = _AccArena(x.device) if (half and _IN_ACC and any(norms)) else None
     try:
-        xs = _first_layer(encs, x, norms, half)
+        xs = _first_layer(encs, x, norms, half, x3)
         for b in range(2):
-            xs = _res_blocks([e.layer1[b] for e in encs], xs, norms, half, fp8)
+            xs = _res_blocks([e.layer1[b] for e in encs], xs, norms, half, fp8, x3)
         # the channel concatenations: two-source inputs of the next layer (fp16 towers; ramp_conv_job.x2), else copies
         two = half and _MS_PAIR
         xs = [v.tensor() if isinstance(v, Tail) else v for v in xs]           # (a two-source input takes tensors)
         x2 = x2.to(xs[0].dtype)
         xs = [Pair(v, x2) if two else torch.cat((v, x2), dim=-1) for v in xs]
         for b in range(2):
-            xs = _res_blocks([e.layer3[b] for e in encs], xs, norms, half, fp8)
+            xs = _res_blocks([e.layer3[b] for e in encs], xs, norms, half, fp8, x3)
         xs = [v.tensor() if isinstance(v, Tail) else v for v in xs]
         x4 = x4.to(xs[0].dtype)
         xs = [Pair(v, x4) if two else torch.cat((v, x4), dim=-1) for v in xs]
-        return conv2d_towers([dict(x=xs[t], conv=e.conv3, out_scale=out_scale) for t, e in enumerate(encs)], half, fp8)
+        return conv2d_towers([dict(x=xs[t], conv=e.conv3, out_scale=out_scale) for t, e in enumerate(encs)], half, fp8, x3)
     finally:
         _scope.cur = None
 
 
-def multiscale_encoder4(enc, x, x2, x4, out_scale=1.0, half=False):
-    return multiscale_encoder4_towers([enc], x, x2, x4, out_scale, half)[0]
+def multiscale_encoder4(enc, x, x2, x4, out_scale=1.0, half=False, x3=True):
+    return multiscale_encoder4_towers([enc], x, x2, x4, out_scale, half, x3=x3)[0]
 
 
 # ------------------------------------------------------------------ LSTM / super-state

@@ -549,13 +549,11 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
                                    t->fmap1_slot, 3, nullptr, 0));
   }
   // fp32 features: the correlation launch is corr_mfma_kernel<CorrX2> on planes of split fp16 pairs (feat_fp32 == 2: the
-  // caller packed them so, RAMP_CORR_X2) or corr_mfma_kernel<float> (RAMP_CORR_F32_MFMA=0: corr_kernel<float>, the reference
-  // kernel's summation order) with rows padded to 896 floats, the operator csrc/update_x3.hip's chains; PRE / POST around a
-  // caller-run operator remain (RAMP_X3=0: library GEMMs)
-  static int corr32_fast = -1;
-  if (corr32_fast < 0) { const char *e = getenv("RAMP_CORR_F32_MFMA"); corr32_fast = e ? atoi(e) : 1; }
+  // caller packed them so, RAMP_CORR_X2) or, as t->corr_f32_mfma says, corr_mfma_kernel<float> / corr_kernel<float> (the
+  // reference kernel's summation order) with rows padded to 896 floats, the operator csrc/update_x3.hip's chains; PRE / POST
+  // around a caller-run operator remain (RAMP_X3=0: library GEMMs)
   if (t->feat_fp32 == 2 && t->feat_plain) return RAMP_EINVAL;
-  const int f32_code = RAMP_F32 | (t->feat_fp32 == 2 ? RAMP_CORR_X2 : corr32_fast ? RAMP_CORR_MFMA32 : 0);
+  const int f32_code = RAMP_F32 | (t->feat_fp32 == 2 ? RAMP_CORR_X2 : t->corr_f32_mfma ? RAMP_CORR_MFMA32 : 0);
   if (flags & RAMP_TRACK_UPDATE_PRE) {
     if (!t->coords || !t->corr) return RAMP_EINVAL;
     TRK_DO(ramp_i_transform_dyn(t->poses, t->patches, t->intrinsics, ii, jj, kk, t->coords, Eb, dyn, st));
@@ -590,7 +588,7 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
   if (flags & RAMP_TRACK_UPDATE) {
     const ramp_track_weights &w = t->w;
     if (!t->coords || !t->corr || !t->net[0] || !t->net[1] || !t->net[2] || !t->fg || !t->ykk || !t->hkk || !t->yij ||
-        !t->hij || !t->target || !t->weight || !t->ba_ws)
+        !t->hij || !t->target || !t->weight || !t->ba_ws || (!t->feat_fp32 && !t->sagg_frag))
       return RAMP_EINVAL;
     // Ramp_vo.update(), ramp/Ramp_vo.py:276-310
     // (pops.transform as a launch of its own: riding in the correlation kernel's geometry prologue it was a wash -- the
@@ -603,54 +601,36 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
     lv[0].fmap = t->fmap1; lv[0].H2 = t->feat_h; lv[0].W2 = t->feat_w; lv[0].coord_div = 1.0f;
     lv[1].fmap = t->fmap2; lv[1].H2 = t->feat_h / 4; lv[1].W2 = t->feat_w / 4; lv[1].coord_div = 4.0f;
     TRK_PROBE(0);
-    static int gate_at = -1;
-    if (gate_at < 0) { const char *e = getenv("RAMP_GATE_AT"); gate_at = e ? atoi(e) : 2; if (gate_at < 0 || gate_at > 3) gate_at = 2; }
     if (t->feat_fp32) {
       // ---- fp32 features (MIXED_PRECISION off): the same step with csrc/update_x3.hip's chains (Linear layers on the f16
       // matrix cores from split fp32 operands), fp32 tables, [f | g] rows + segment softmax + h for the two SoftAggs.
-      // The fp32 front end is ~1.1 ms against ~0.9 ms of step behind the second neighbour chain, so it starts at the top of the
-      // step (RAMP_GATE_AT_F32: 5 = before the correlation launch, the default; 4 = before the correlation MLP, 3 = before
-      // c1 / c2, 0 .. 2 as RAMP_GATE_AT).  Measured (bench.py --mixed 0, two runs each): 2 -> 434 kf/s, 3 -> 455, 4 -> 471,
-      // 5 -> 492
-      static int gate32 = -1;
-      if (gate32 < 0) { const char *e = getenv("RAMP_GATE_AT_F32"); gate32 = e ? atoi(e) : 5; if (gate32 < 0 || gate32 > 5) gate32 = 5; }
-      const int gate_at = gate32;
-#define TRK_GATE32(pos)                                                                                   \
-  do {                                                                                                    \
-    if (gate_at == (pos) && !(t->gate_flag && (pos) == 0)) {                                              \
-      if (t->gate_flag) hipLaunchKernelGGL(trk_signal_kernel, dim3(1), dim3(1), 0, st, t->gate_flag, t->gate_seq); \
-      else if (gate_event && hipEventRecord((hipEvent_t)gate_event, st) != hipSuccess) return RAMP_ELAUNCH; \
-    }                                                                                                     \
-  } while (0)
-      TRK_GATE32(5);
+      // The fp32 front end is ~1.1 ms against ~0.9 ms of step behind the second neighbour chain, so the next frame's front
+      // end may start at the top of the step, before the correlation launch: a one-thread launch stores the "go" word
+      // (t->gate_flag), or the caller's event is recorded.  Measured against later gates (bench.py --mixed 0, two runs each):
+      // before the first SoftAgg 434 kf/s, before c1 / c2 455, before the correlation MLP 471, here 492
+      if (t->gate_flag) hipLaunchKernelGGL(trk_signal_kernel, dim3(1), dim3(1), 0, st, t->gate_flag, t->gate_seq);
+      else if (gate_event && hipEventRecord((hipEvent_t)gate_event, st) != hipSuccess) return RAMP_ELAUNCH;
       TRK_DO(ramp_i_corr_fwd(t->gmap, lv, 2, t->coords, kk, jj, t->ij_order, t->corr, 896, (long)t->M * t->mem, t->mem, Eb,
                              t->mem * t->M, t->mem, 128, t->P, 3, f32_code, t->feat_plain ? RAMP_NHWC : RAMP_NHWC32, dyn, st, nullptr, nullptr, nullptr,
                              nullptr, t->fmap1_slot));
       TRK_PROBE(1);
-      TRK_GATE32(4);
       const float *corr32 = (const float *)t->corr;
       float *fg32 = (float *)t->fg, *ykk = (float *)t->ykk, *hkk = (float *)t->hkk, *yij = (float *)t->yij, *hij = (float *)t->hij;
       TRK_DO(ramp_i_x3_corr_mlp(corr32, 896, w.corr_w1, w.corr_b1, w.corr_w2, w.corr_b2, w.corr_w3, w.corr_b3, w.corr_ln_w,
                                 w.corr_ln_b, w.corr_ln_eps, t->net[0], row, (const float *)t->imap, kk, (long)t->M * t->mem,
                                 w.norm_w, w.norm_b, w.norm_eps, t->net[1], Eb, dyn, st));
-      TRK_GATE32(3);
       TRK_DO(ramp_i_x3_nbr(t->net[1], t->ix, w.c1_wa, w.c1_ba, w.c1_wb, w.c1_bb, t->net[2], Eb, dyn, st));
       TRK_DO(ramp_i_x3_nbr(t->net[2], t->jx, w.c2_wa, w.c2_ba, w.c2_wb, w.c2_bb, t->net[1], Eb, dyn, st));
       float *net32 = t->net[1];
-      TRK_GATE32(2);
       TRK_DO(ramp_i_x3_fg(net32, nullptr, nullptr, nullptr, w.kk_wf, w.kk_bf, w.kk_wg, w.kk_bg, fg32, Eb, dyn, st));
       TRK_DO(ramp_x3_segment_softmax(fg32, t->kk_order, t->kk_seg, t->kk_ngroups, ykk, t->kk_cap, stream));
       TRK_DO(ramp_x3_linear(ykk, w.kk_wh, w.kk_bh, hkk, t->kk_cap, t->kk_ngroups, stream));
-      TRK_GATE32(1);
       TRK_DO(ramp_i_x3_fg(net32, hkk, t->kk_gid, nullptr, w.ij_wf, w.ij_bf, w.ij_wg, w.ij_bg, fg32, Eb, dyn, st));
       TRK_DO(ramp_x3_segment_softmax(fg32, t->ij_order, t->ij_seg, t->ij_ngroups, yij, t->ij_cap, stream));
       TRK_DO(ramp_x3_linear(yij, w.ij_wh, w.ij_bh, hij, t->ij_cap, t->ij_ngroups, stream));
-      TRK_GATE32(0);
       TRK_DO(ramp_i_x3_gru(net32, hkk, t->kk_gid, hij, t->ij_gid, w.ln1_w, w.ln1_b, w.ln1_eps, w.gru_w, w.gru_b, w.ln2_w, w.ln2_b,
                            w.ln2_eps, t->net[0], nullptr, Eb, dyn, (const float *)w.heads_w, w.heads_b, t->coords, t->target,
-                           t->weight, t->P, (float)t->feat_w, (float)t->feat_h, gate_at == 0 ? t->gate_flag : nullptr,
-                           t->gate_seq, st));
-#undef TRK_GATE32
+                           t->weight, t->P, (float)t->feat_w, (float)t->feat_h, st));
     } else {
     // (the plan's (jj, ii)-major schedule: worth 1.3 % of the frame against graph order, round 5's A/B)
     TRK_DO(ramp_i_corr_fwd(t->gmap, lv, 2, t->coords, kk, jj, t->ij_order, t->corr, 896, (long)t->M * t->mem, t->mem, Eb,
@@ -661,54 +641,26 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
     TRK_DO(ramp_i_upd_corr_mlp(t->corr, 896, w.corr_w1, w.corr_b1, w.corr_w2, w.corr_b2, w.corr_w3, w.corr_b3, w.corr_ln_w,
                                w.corr_ln_b, w.corr_ln_eps, t->net[0], row, t->imap, kk, (long)t->M * t->mem, w.norm_w,
                                w.norm_b, w.norm_eps, t->net[1], Eb, dyn, st));
-    // where the next frame's front end may start (RAMP_GATE_AT: 2 = before the first SoftAgg, the default -- with the fused
-    // SoftAgg launches next to it the front end costs the operator ~25 us and gives bundle adjustment 12 back, +1.2 % SingleScale,
-    // +2.1 % MultiScale against 0; 0 = before the gru chain (rounds 2-3); 1 = before the second SoftAgg; 3 = before c1 / c2).
-    // The "go" is a word stored by the first workgroup of the launch behind that point (t->gate_flag: gru, SoftAgg), a
-    // one-thread launch where that kernel cannot (the three-launch SoftAgg, c1), or the caller's event.
-    const bool use_sagg = t->sagg_frag != nullptr;
-    const bool flag_in_kernel = t->gate_flag && (gate_at == 0 || ((gate_at == 1 || gate_at == 2) && use_sagg));
-#define TRK_GATE(pos)                                                                                     \
-  do {                                                                                                    \
-    if (gate_at == (pos) && !flag_in_kernel) {                                                            \
-      if (t->gate_flag) hipLaunchKernelGGL(trk_signal_kernel, dim3(1), dim3(1), 0, st, t->gate_flag, t->gate_seq); \
-      else if (gate_event && hipEventRecord((hipEvent_t)gate_event, st) != hipSuccess) return RAMP_ELAUNCH; \
-    }                                                                                                     \
-  } while (0)
-    TRK_GATE(3);
     TRK_DO(ramp_i_upd_nbr(t->net[1], t->ix, w.c1_wa, w.c1_ba, w.c1_wb, w.c1_bb, t->net[2], nullptr, Eb, dyn, st));
     TRK_DO(ramp_i_upd_nbr(t->net[2], t->jx, w.c2_wa, w.c2_ba, w.c2_wb, w.c2_bb, t->net[1], nullptr, Eb, dyn, st));
     float *net = t->net[1];
-    TRK_GATE(2);
-    // SoftAgg x 2 (ramp/net.py:84-85).  With a fragment table: gather-by-group tiles, g and f on the same tile, online
-    // softmax in registers, h on the merged fragments -- 2 launches each, no [E, 768] rows (csrc/update_mlp.hip);
-    // no table: [f | g] rows + segment softmax + h, 3 launches each.
-    const int add2 = 1;                           // (net + hkk[.] is never written back: the gru launch forms the sum itself)
-    if (use_sagg) {
-      TRK_DO(ramp_i_upd_softagg(net, nullptr, nullptr, t->kk_order, t->kk_gid, w.kk_wf, w.kk_bf, w.kk_wg, w.kk_bg, t->sagg_frag,
-                                Eb, dyn, st, gate_at == 2 ? t->gate_flag : nullptr, t->gate_seq));
-      TRK_DO(ramp_upd_softagg_finish(t->sagg_frag, t->kk_seg, t->kk_ngroups, w.kk_wh, w.kk_bh, t->hkk, t->kk_cap, stream));
-      TRK_GATE(1);
-      TRK_DO(ramp_i_upd_softagg(net, t->hkk, t->kk_gid, t->ij_order, t->ij_gid, w.ij_wf, w.ij_bf, w.ij_wg, w.ij_bg, t->sagg_frag,
-                                Eb, dyn, st, gate_at == 1 ? t->gate_flag : nullptr, t->gate_seq));
-      TRK_DO(ramp_upd_softagg_finish(t->sagg_frag, t->ij_seg, t->ij_ngroups, w.ij_wh, w.ij_bh, t->hij, t->ij_cap, stream));
-    } else {
-    TRK_DO(ramp_i_upd_fg(net, nullptr, nullptr, nullptr, w.kk_wf, w.kk_bf, w.kk_wg, w.kk_bg, t->fg, Eb, dyn, st));
-    TRK_DO(ramp_upd_segment_softmax(t->fg, t->kk_order, t->kk_seg, t->kk_ngroups, t->ykk, t->kk_cap, RAMP_F16, stream));
-    TRK_DO(ramp_upd_linear(t->ykk, w.kk_wh, w.kk_bh, t->hkk, t->kk_cap, t->kk_ngroups, stream));
-    TRK_GATE(1);
-    // the pair SoftAgg's [f|g] launch reads net + hkk[patch group] and, by default, does NOT write the sum back: the gru
-    // launch forms (net + hkk[.]) + hij[.] itself, in the same order (61 MB less to write in the serial part of the step;
-    // the extra table rows come from L2).
-    TRK_DO(ramp_i_upd_fg(net, t->hkk, t->kk_gid, add2 ? nullptr : net, w.ij_wf, w.ij_bf, w.ij_wg, w.ij_bg, t->fg, Eb, dyn, st));
-    TRK_DO(ramp_upd_segment_softmax(t->fg, t->ij_order, t->ij_seg, t->ij_ngroups, t->yij, t->ij_cap, RAMP_F16, stream));
-    TRK_DO(ramp_upd_linear(t->yij, w.ij_wh, w.ij_bh, t->hij, t->ij_cap, t->ij_ngroups, stream));
-    }
-    TRK_GATE(0);
+    // the next frame's front end may start here, before the first SoftAgg (against before the gru chain, rounds 2-3: +1.2 %
+    // SingleScale, +2.1 % MultiScale -- the front end costs the operator ~25 us and gives bundle adjustment 12 back).  The
+    // "go" is the word the first SoftAgg launch's first workgroup stores (t->gate_flag), or else the caller's event.
+    if (!t->gate_flag && gate_event && hipEventRecord((hipEvent_t)gate_event, st) != hipSuccess) return RAMP_ELAUNCH;
+    // SoftAgg x 2 (ramp/net.py:84-85): gather-by-group tiles, g and f on the same tile, online softmax in registers, h on
+    // the merged fragments -- 2 launches each, no [E, 768] rows (csrc/update_mlp.hip).  The pair SoftAgg reads net +
+    // hkk[patch group] and does not write the sum back: the gru launch forms (net + hkk[.]) + hij[.] itself
+    TRK_DO(ramp_i_upd_softagg(net, nullptr, nullptr, t->kk_order, t->kk_gid, w.kk_wf, w.kk_bf, w.kk_wg, w.kk_bg, t->sagg_frag,
+                              Eb, dyn, st, t->gate_flag, t->gate_seq));
+    TRK_DO(ramp_upd_softagg_finish(t->sagg_frag, t->kk_seg, t->kk_ngroups, w.kk_wh, w.kk_bh, t->hkk, t->kk_cap, stream));
+    TRK_DO(ramp_i_upd_softagg(net, t->hkk, t->kk_gid, t->ij_order, t->ij_gid, w.ij_wf, w.ij_bf, w.ij_wg, w.ij_bg, t->sagg_frag,
+                              Eb, dyn, st));
+    TRK_DO(ramp_upd_softagg_finish(t->sagg_frag, t->ij_seg, t->ij_ngroups, w.ij_wh, w.ij_bh, t->hij, t->ij_cap, stream));
     // (the heads and target / weight are formed in the gru launch's epilogue: no relu(net) round trip, one launch less)
-    TRK_DO(ramp_i_upd_gru(net, add2 ? t->hkk : nullptr, add2 ? t->kk_gid : nullptr, t->hij, t->ij_gid, w.ln1_w, w.ln1_b, w.ln1_eps, w.gru_w, w.gru_b, w.ln2_w, w.ln2_b,
-                          w.ln2_eps, t->net[0], nullptr, Eb, dyn, w.heads_w, w.heads_b, t->coords, t->target, t->weight, t->P,
-                          (float)t->feat_w, (float)t->feat_h, t->E_hint, gate_at == 0 ? t->gate_flag : nullptr, t->gate_seq, st));
+    TRK_DO(ramp_i_upd_gru(net, t->hkk, t->kk_gid, t->hij, t->ij_gid, w.ln1_w, w.ln1_b, w.ln1_eps, w.gru_w, w.gru_b, w.ln2_w,
+                          w.ln2_b, w.ln2_eps, t->net[0], nullptr, Eb, dyn, w.heads_w, w.heads_b, t->coords, t->target,
+                          t->weight, t->P, (float)t->feat_w, (float)t->feat_h, t->E_hint, st));
     }   // (fp16 features)
     TRK_PROBE(2);
     TRK_PROBE(3);

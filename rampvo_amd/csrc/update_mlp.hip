@@ -234,8 +234,6 @@ struct GruParams {
   // optional prologue: x = LayerNorm_pre(x32 + add_t[add_idx]) -- the last SoftAgg's expand-and-add and gru[0]
   const _Float16 *add_t;       // [groups][384] fp16 or NULL
   const int32_t *add_idx;      // [E]
-  uint32_t *gate_flag;         // optional: workgroup 0 stores gate_seq here when it starts (ramp_track.gate_flag)
-  uint32_t gate_seq;
   const _Float16 *add0_t;      // optional: a FIRST expand-and-add (x32 + add0_t[add0_idx]) + add_t[add_idx] -- the second-last
   const int32_t *add0_idx;     // SoftAgg's, when the launch that consumed it did not write the sum back
   const float *pre_w, *pre_b;  // gru[0] LayerNorm
@@ -388,10 +386,6 @@ __global__ void __launch_bounds__(64 * MWAVES) upd_gru_kernel(const GruParams p)
   float *T1 = reinterpret_cast<float *>(Gs + ROWS * MXS), *T2 = T1 + ROWS * MWAVES;   // LayerNorm partials
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, j = lane & 15;
   const int row0 = blockIdx.x * ROWS;
-  // "the next frame's front end may start": a plain store the other stream's sleeping wave looks for (timing only, no
-  // data rides on it)
-  if (p.gate_flag && blockIdx.x == 0 && tid == 0)
-    __hip_atomic_store(p.gate_flag, p.gate_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   const int pE = p.dyn ? p.dyn[RAMP_DYN_E] : p.E;
   if (row0 >= pE) return;                      // (workgroup-uniform: only with device-side sizes)
   const int col0 = wave * (16 * MNTW);
@@ -1564,18 +1558,13 @@ __global__ void __launch_bounds__(512) upd_linear_kernel(const _Float16 *__restr
   }
 }
 
-// row tiles per workgroup for E edges (0: the 64-row kernels -- small problems, or RAMP_UPD_BIG=0; 4..8 forces a tile
-// for A/B runs); `best`: the measured optimum of the chain at the bench size
-static int big_pick_nmt(int E, int best) {
-  static int mode = -1;
-  if (mode < 0) {
-    const char *e = getenv("RAMP_UPD_BIG");
-    mode = e ? atoi(e) : 1;
-  }
-  if (mode == 0 || E < 16384 || (long)E * MD * 4 >= (1l << 32)) return 0;
-  if (mode >= 4 && mode <= 8) return mode;
-  return best;
-}
+// the wide-tile chain kernels from 16,384 factors on (below, and where E x 384 floats overflow 32-bit offsets: the 64-row
+// kernels); their row tiles per workgroup are the measured optima of each chain at the bench size
+#define NBR_NMT 5
+#ifndef FG_BEST
+#define FG_BEST 6
+#endif
+static bool use_big(int E) { return E >= 16384 && (long)E * MD * 4 < (1l << 32); }
 
 template <typename KernelT, typename ParamsT>
 static int big_launch(KernelT kernel, const ParamsT &p, int E, int nmt, int nw, bool with_red, hipStream_t st) {
@@ -1586,15 +1575,6 @@ static int big_launch(KernelT kernel, const ParamsT &p, int E, int nmt, int nw, 
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;
 }
-
-#define BIG_DISPATCH(KERNEL, NW, P, E, NMT, RED, ST)                                       \
-  switch (NMT) {                                                                             \
-    case 4: return big_launch(KERNEL<4, NW>, P, E, 4, NW, RED, ST);                          \
-    case 5: return big_launch(KERNEL<5, NW>, P, E, 5, NW, RED, ST);                          \
-    case 6: return big_launch(KERNEL<6, NW>, P, E, 6, NW, RED, ST);                          \
-    case 7: return big_launch(KERNEL<7, NW>, P, E, 7, NW, RED, ST);                          \
-    default: return big_launch(KERNEL<8, NW>, P, E, 8, NW, RED, ST);                         \
-  }
 
 extern "C" {
 
@@ -1610,7 +1590,7 @@ int ramp_i_upd_gru(const float *x32, const void *add0_t, const int32_t *add0_idx
                  float pre_eps, const void *const *wp_host, const float *const *bias_host, const float *ln_w,
                  const float *ln_b, float eps, float *out32, void *relu_t, int E, const int32_t *dyn,
                  const void *heads_w, const float *heads_b, const float *coords, float *target, float *weight, int P,
-                 float wd, float ht, int E_hint, uint32_t *gate_flag, uint32_t gate_seq, void *stream) {
+                 float wd, float ht, int E_hint, void *stream) {
   if (E < 0) return RAMP_EINVAL;
   if (E == 0) return RAMP_OK;
   if (!x32 || !wp_host || !bias_host || !ln_w || !ln_b || !out32 || (!relu_t && !heads_w)) return RAMP_EINVAL;
@@ -1619,7 +1599,7 @@ int ramp_i_upd_gru(const float *x32, const void *add0_t, const int32_t *add0_idx
   if (add0_t && (!add0_idx || !add_t)) return RAMP_EINVAL;
   GruParams p;
   p.x32 = x32;
-  p.add0_t = (const _Float16 *)add0_t; p.add0_idx = add0_idx; p.gate_flag = gate_flag; p.gate_seq = gate_seq;
+  p.add0_t = (const _Float16 *)add0_t; p.add0_idx = add0_idx;
   p.add_t = (const _Float16 *)add_t; p.add_idx = add_idx; p.pre_w = pre_w; p.pre_b = pre_b; p.pre_eps = pre_eps;
   for (int i = 0; i < 6; i++) {
     if (!wp_host[i] || !bias_host[i]) return RAMP_EINVAL;
@@ -1672,7 +1652,7 @@ int ramp_i_upd_nbr(const float *net_in, const int64_t *idx, const void *wa, cons
   NbrParams p;
   p.net_in = net_in; p.idx = idx; p.wa = (const _Float16 *)wa; p.wb = (const _Float16 *)wb; p.ba = ba; p.bb = bb;
   p.net_out = net_out; p.out_t = (_Float16 *)out_t; p.E = E; p.dyn = dyn;
-  if (const int nmt = big_pick_nmt(E, 5)) { BIG_DISPATCH(upd_nbr_big_kernel, 8, p, E, nmt, false, (hipStream_t)stream) }
+  if (use_big(E)) return big_launch(upd_nbr_big_kernel<NBR_NMT, 8>, p, E, NBR_NMT, 8, false, (hipStream_t)stream);
   const size_t lds = (size_t)MBM * MXS * 2;          // one tile (see the kernel)
   static bool attr_set = false;
   if (!attr_set) {
@@ -1715,10 +1695,7 @@ int ramp_i_upd_fg(const float *x32, const void *add_t, const int32_t *add_idx, f
   FgParams p;
   p.x32 = x32; p.add_t = (const _Float16 *)add_t; p.add_idx = add_idx; p.x32_out = x32_out;
   p.wf = (const _Float16 *)wf; p.wg = (const _Float16 *)wg; p.bf = bf; p.bg = bg; p.fg = (_Float16 *)fg; p.E = E; p.dyn = dyn;
-  #ifndef FG_BEST
-#define FG_BEST 6
-#endif
-  if (const int nmt = big_pick_nmt(E, FG_BEST)) { BIG_DISPATCH(upd_fg_big_kernel, 8, p, E, nmt, false, (hipStream_t)stream) }
+  if (use_big(E)) return big_launch(upd_fg_big_kernel<FG_BEST, 8>, p, E, FG_BEST, 8, false, (hipStream_t)stream);
   const size_t lds = (size_t)MBM * MXS * 2;
   hipLaunchKernelGGL(upd_fg_kernel, dim3(ramp_cdiv(E, MBM)), dim3(64 * MWAVES), lds, (hipStream_t)stream, p);
   RAMP_CHECK_LAUNCH();
@@ -1731,7 +1708,7 @@ int ramp_upd_gru(const float *x32, const void *add_t, const int32_t *add_idx, co
                  float pre_eps, const void *const *wp_host, const float *const *bias_host, const float *ln_w,
                  const float *ln_b, float eps, float *out32, void *relu_t, int E, void *stream) {
   return ramp_i_upd_gru(x32, nullptr, nullptr, add_t, add_idx, pre_w, pre_b, pre_eps, wp_host, bias_host, ln_w, ln_b, eps, out32, relu_t, E, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, 3, 0.f, 0.f, 0, nullptr, 0u, stream);
+                        nullptr, nullptr, nullptr, nullptr, nullptr, 3, 0.f, 0.f, 0, stream);
 }
 
 int ramp_upd_gru_heads(const float *x32, const void *add_t, const int32_t *add_idx, const float *pre_w, const float *pre_b,
@@ -1740,7 +1717,7 @@ int ramp_upd_gru_heads(const float *x32, const void *add_t, const int32_t *add_i
                        const float *coords, float *target, float *weight, int E, int P, float wd, float ht, void *stream) {
   if (!heads_w) return RAMP_EINVAL;
   return ramp_i_upd_gru(x32, nullptr, nullptr, add_t, add_idx, pre_w, pre_b, pre_eps, wp_host, bias_host, ln_w, ln_b, eps, out32, nullptr, E, nullptr,
-                        heads_w, heads_b, coords, target, weight, P, wd, ht, 0, nullptr, 0u, stream);
+                        heads_w, heads_b, coords, target, weight, P, wd, ht, 0, stream);
 }
 
 int ramp_upd_nbr(const float *net_in, const int64_t *idx, const void *wa, const float *ba, const void *wb,

@@ -597,8 +597,6 @@ struct X3GruParams {
   float *target, *weight;      // [E][2]
   int PP, ctr;
   float wd, ht;
-  uint32_t *gate_flag;         // optional: workgroup 0 stores gate_seq here when it starts
-  uint32_t gate_seq;
   int E;
   const int32_t *dyn;
 };
@@ -613,8 +611,6 @@ __global__ void __launch_bounds__(64 * XWAVES) x3_gru_kernel(const X3GruParams p
   float *T1 = reinterpret_cast<float *>(Xl + ROWS * XS), *T2 = T1 + ROWS * XWAVES;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, q = lane >> 4, j = lane & 15;
   const int row0 = blockIdx.x * ROWS;
-  if (p.gate_flag && blockIdx.x == 0 && tid == 0)
-    __hip_atomic_store(p.gate_flag, p.gate_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   const int pE = p.dyn ? p.dyn[RAMP_DYN_E] : p.E;
   if (row0 >= pE) return;
   const int cq = wave * (16 * XNTW) + 4 * q;
@@ -832,7 +828,7 @@ int ramp_i_x3_gru(const float *x32, const float *add0_t, const int32_t *add0_idx
                   const float *pre_w, const float *pre_b, float pre_eps, const void *const *wp_host,
                   const float *const *bias_host, const float *ln_w, const float *ln_b, float eps, float *out32, float *relu32,
                   int E, const int32_t *dyn, const float *heads_w, const float *heads_b, const float *coords, float *target,
-                  float *weight, int P, float wd, float ht, uint32_t *gate_flag, uint32_t gate_seq, void *stream) {
+                  float *weight, int P, float wd, float ht, void *stream) {
   if (E < 0) return RAMP_EINVAL;
   if (E == 0) return RAMP_OK;
   if (!x32 || !wp_host || !bias_host || !ln_w || !ln_b || !out32) return RAMP_EINVAL;
@@ -849,7 +845,7 @@ int ramp_i_x3_gru(const float *x32, const float *add0_t, const int32_t *add0_idx
   }
   p.ln_w = ln_w; p.ln_b = ln_b; p.eps = eps; p.out32 = out32; p.relu32 = relu32; p.heads_w = heads_w; p.heads_b = heads_b;
   p.coords = coords; p.target = target; p.weight = weight; p.PP = P * P; p.ctr = (P / 2) * P + P / 2; p.wd = wd; p.ht = ht;
-  p.gate_flag = gate_flag; p.gate_seq = gate_seq; p.E = E; p.dyn = dyn;
+  p.E = E; p.dyn = dyn;
   return x3_launch(x3_gru_kernel<X3_GRU_MT>, p, E, X3_GRU_MT, true, (hipStream_t)stream);
 }
 
@@ -874,7 +870,7 @@ int ramp_x3_gru(const float *x32, const float *add0_t, const int32_t *add0_idx, 
                 const float *ln_w, const float *ln_b, float eps, float *out32, float *relu32, int E, const float *heads_w,
                 const float *heads_b, const float *coords, float *target, float *weight, int P, float wd, float ht, void *stream) {
   return ramp_i_x3_gru(x32, add0_t, add0_idx, add_t, add_idx, pre_w, pre_b, pre_eps, wp_host, bias_host, ln_w, ln_b, eps, out32,
-                       relu32, E, nullptr, heads_w, heads_b, coords, target, weight, P, wd, ht, nullptr, 0u, stream);
+                       relu32, E, nullptr, heads_w, heads_b, coords, target, weight, P, wd, ht, stream);
 }
 
 }  // extern "C"

@@ -13,6 +13,8 @@ import warnings
 
 import torch
 
+from . import switches
+
 _fitted = [False]
 
 
@@ -58,15 +60,15 @@ def fit_host_threads(force=False):
     if _fitted[0] and not force:
         return torch.get_num_threads()
     _fitted[0] = True
-    env = os.environ.get("RAMP_HOST_THREADS", "")          # env: the host pool (0: hands off)
-    if env == "0":
+    env = switches.read().host_threads
+    if env == 0:
         return torch.get_num_threads()
     have, quota = torch.get_num_threads(), cpu_quota()
     try:        # one process per GPU on a node (torchrun): the ranks share the container's quota
         quota = max(1, quota // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))
     except ValueError:
         pass
-    want = int(env) if env else max(1, quota // 2)
+    want = env if env else max(1, quota // 2)
     if env or have > quota:
         torch.set_num_threads(want)
         if not env:

@@ -8,7 +8,7 @@ training unroll ``VONet.forward`` is outside the hot path and not provided.
 import torch
 import torch.nn as nn
 
-from . import altcorr, fastba, ops
+from . import altcorr, fastba, ops, switches
 from ._lib import RAMP_NCHW, RAMP_NHWC
 from .blocks import GatedResidual, SoftAgg
 from .extractor import MergerLSTMsceneEncoder, MultiScaleMergerDoubleNet
@@ -137,15 +137,15 @@ class Patchifier(nn.Module):
         else:
             raise ValueError(f"Invalid input mode: {input_mode}")
         self._grid = None
-        import os
-        self.use_graph = os.environ.get("RAMP_NO_GRAPH", "0") != "1"
+        self.use_graph = True          # the front end as one captured hipGraph (False: eager launches, tests compare the two)
         self._graphs = {}
         self._graph_warm = 0
+        sw = switches.read()
         # fp32 features: the tracker's pyramid planes chunked for the MFMA correlation kernels -- 2 (default): split fp16
         # parts [h][4][2][w][32] for corr_mfma_kernel<CorrX2>; 1: [h][8][w][16] fp32 for corr_mfma_kernel<float>; 0
         # (RAMP_CORR_F32_MFMA=0): plain NHWC planes for corr_kernel<float>, the reference kernel's summation order
-        from ._lib import corr_f32_mode
-        self.pack_f32 = corr_f32_mode()
+        self.pack_f32 = sw.corr_f32_mfma
+        self.encoder.conv_x3 = sw.conv_x3
         self._plist = None
         self._extra = None
         self._index = None

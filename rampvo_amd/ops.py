@@ -5,11 +5,9 @@ short fixed pipeline) on torch's current stream.  No CPU fallbacks.
 """
 import ctypes
 
-import os
-
 import torch
 
-from . import _lib
+from . import _lib, switches
 from ._lib import RAMP_CORR_MFMA32 as _LIB_CORR_MFMA32
 from ._lib import RAMP_CORR_X2 as _LIB_CORR_X2
 from ._lib import workspace as _lib_workspace
@@ -66,6 +64,11 @@ def corr(fmap1, fmaps2, coords, ii, jj, radius=3, coord_divs=(1.0,), layout=RAMP
     fmaps2 list of per-level target maps [N2,C,H,W] / [N2,H,W,C]
     coords [E,2,P,P] float32;  ii,jj [E] int64
     -> [E, 2r+1, 2r+1, P, P, nlevels]
+
+    fp32 features: fast_f32 picks the kernel -- False / 0 corr_kernel<float> (the reference's fmaf chain), True / 1
+    corr_mfma_kernel<float>, 2 with RAMP_NHWC32 corr_mfma_kernel<CorrX2> on planes of split fp16 pairs.  None: 1 when
+    RAMP_CORR_F32_MFMA is 1 (switches.read()), else 0 -- the split mode, RAMP_CORR_F32_MFMA's default, is the tracker's
+    packing and is asked for explicitly (the tracker passes fast_f32 itself)
     """
     require_cuda(fmap1, coords, ii, jj, *fmaps2)
     fmap1 = fmap1.contiguous()
@@ -103,7 +106,7 @@ def corr(fmap1, fmaps2, coords, ii, jj, radius=3, coord_divs=(1.0,), layout=RAMP
         assert order.dtype == torch.int32 and order.is_contiguous() and order.shape[0] == E
     code = dtype_code(fmap1)
     if fast_f32 is None:
-        fast_f32 = os.environ.get("RAMP_CORR_F32_MFMA", "0") == "1"
+        fast_f32 = switches.read().corr_f32_mfma == 1
     if fast_f32 and fmap1.dtype == torch.float32 and layout in (RAMP_NHWC, RAMP_NHWC32):
         # opt-in: MFMA accumulation order instead of the reference's fmaf chain.  fast_f32 = 2 with RAMP_NHWC32: the target
         # maps are planes of split fp16 pairs (pyramid_pack(split=True)) -> corr_mfma_kernel<CorrX2>

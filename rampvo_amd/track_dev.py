@@ -8,7 +8,6 @@ reads the device; ``leave()`` is the one synchronisation that hands the state ba
 """
 import collections
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -55,7 +54,8 @@ class Track(ctypes.Structure):
                 + _ptr_fields(["fg", "ykk", "hkk", "yij", "hij", "relu_t", "sagg_frag", "target", "weight", "ba_ws"])
                 + [("ba_ws_bytes", c_sz)]
                 + _ptr_fields(["mm", "median", "dlog", "edit_ws", "dyn_host", "dyn_host_dev"]) + [("probe", c_p * 5), ("E_hint", c_i),
-                   ("gate_seq", ctypes.c_uint32), ("feat_fp32", c_i), ("feat_plain", c_i), ("gate_flag", c_p), ("fmap1_slot", c_p)])
+                   ("gate_seq", ctypes.c_uint32), ("feat_fp32", c_i), ("feat_plain", c_i), ("gate_flag", c_p), ("fmap1_slot", c_p),
+                   ("corr_f32_mfma", c_i)])
 
 
 _E_EST_LAST = 1          # (0: the largest of the last 64 copies, round 3's first rule)
@@ -146,7 +146,7 @@ class DeviceTrack:
         self.corr = e((E_cap, CORR_ROW), f32 if self.fp32 else f16)
         self.net = [z((E_cap, 384), f32) for _ in range(3)]
         tt = f32 if self.fp32 else f16                 # SoftAgg rows / tables
-        self.fg = e((16 if (self.fp32 and not self.x3) else E_cap, 768), tt)
+        self.fg = e((E_cap if self.x3 else 16, 768), tt)             # (fp16: the fused SoftAgg has no [f | g] rows)
         self.ykk, self.hkk = z((kk_cap, 384), tt), z((kk_cap, 384), tt)
         self.yij, self.hij = z((ij_cap, 384), tt), z((ij_cap, 384), tt)
         self.relu_t = e((16 if self.fp32 else E_cap, 384), f16)
@@ -180,6 +180,7 @@ class DeviceTrack:
         t.motion_damping = float(cfg.MOTION_DAMPING)
         t.keyframe_thresh = float(cfg.KEYFRAME_THRESH)
         t.feat_fp32 = (2 if slam._split else 1) if self.fp32 else 0      # (2: planes of split fp16 pairs, RAMP_CORR_X2)
+        t.corr_f32_mfma = int(slam._f32_mode != 0)     # (the patchifier's pack mode; 0: plain planes, the reference order)
         t.feat_plain = 0 if slam._chunked else 1
         P = lambda x: x.data_ptr()
         for name, ten in dict(dyn=self.dyn, poses=slam.poses_, patches=slam.patches_, intrinsics=slam.intrinsics_,
@@ -196,11 +197,9 @@ class DeviceTrack:
             setattr(t, name, P(ten))
         t.plan_ws_bytes, t.ba_ws_bytes = self.plan_ws.numel(), self.ba_ws.numel()
         # level-0 correlation planes by slot table (csrc/track.hip: a dropped keyframe rotates table entries instead of moving
-        # three planes; leave() undoes the permutation).  RAMP_SLOT_TABLE=0: rows are slots, physical shifts
-        self.fmap1_slot = None
-        if os.environ.get("RAMP_SLOT_TABLE", "1") != "0":
-            self.fmap1_slot = torch.arange(slam.mem, dtype=torch.int32, device=dev)
-            t.fmap1_slot = self.fmap1_slot.data_ptr()
+        # three planes; leave() undoes the permutation)
+        self.fmap1_slot = torch.arange(slam.mem, dtype=torch.int32, device=dev)
+        t.fmap1_slot = self.fmap1_slot.data_ptr()
         dp = ctypes.c_void_p()                    # device address of the pinned copy: resolved once, not per frame
         if lib.ramp_host_device_pointer(ctypes.c_void_p(self.dyn_host.data_ptr()), ctypes.byref(dp)) == 0 and dp.value:
             t.dyn_host_dev = dp.value
@@ -286,8 +285,7 @@ class DeviceTrack:
         if (n + 1) * M - d[DYN_KLO] > self.kkey_cap or d[DYN_W] ** 2 > self.pkey_cap:
             return False
         self.dyn.copy_(self.dyn_host, non_blocking=True)
-        if self.fmap1_slot is not None:
-            self.fmap1_slot.copy_(torch.arange(slam.mem, dtype=torch.int32, device=self.fmap1_slot.device))   # (rows are slots on the host side)
+        self.fmap1_slot.copy_(torch.arange(slam.mem, dtype=torch.int32, device=self.fmap1_slot.device))   # (rows are slots on the host side)
         _lib.check(_lib.lib().ramp_track_plan(ctypes.byref(self.t), self.cur, _lib.stream()), "ramp_track_plan")
         self.active = True
         self._frames = 0
@@ -324,8 +322,8 @@ class DeviceTrack:
         return int(min(max(self._e_seen), self.E_cap))
 
     def step(self, counter, flags, k_new=None, gate_event=None, gate_flag=None, gate_seq=0, E_bound=None):
-        """gate_flag / gate_seq: a signal word (Signal) the update operator's last launch stores gate_seq into -- the
-        cheaper form of gate_event (no packet on this stream); the waiting stream uses Signal.wait.  E_bound: the launch
+        """gate_flag / gate_seq: a signal word (Signal) the step stores gate_seq into where the next frame's front end may
+        start -- the cheaper form of gate_event (no packet on this stream); the waiting stream uses Signal.wait.  E_bound: the launch
         bound of this call (default: factor_bound(counter)); the two halves of an fp32 step share one."""
         ev = ctypes.c_void_p(gate_event) if gate_event else None
         self.t.E_hint = self.factor_estimate()
@@ -413,24 +411,23 @@ class DeviceTrack:
         """synchronise and return the host-side view of the state: dict(n, ii, jj, kk, rows (host arrays of the kept
         factors), net (device [EPREV, 384] view), log (list of (t1, t0, dP[7] device tensor)), status)"""
         torch.cuda.current_stream().synchronize()
-        if self.fmap1_slot is not None:
-            # the host-driven path addresses ring row r as slot r: undo the table's permutation of the level-0 planes
-            # (cycle by cycle through ONE scratch plane: a gather of the whole ring would materialise a second copy of
-            # it -- mem x 4.9 MB at 640 x 480 -- on every hand-back behind a dropped keyframe, ADVICE r4)
-            perm = [int(v) for v in self.fmap1_slot.cpu().tolist()]          # row r lives in slot perm[r]
-            if perm != list(range(len(perm))):
-                buf, done = self.slam.fmap1_, [False] * len(perm)
-                for r0 in range(len(perm)):
-                    if done[r0] or perm[r0] == r0:
-                        done[r0] = True
-                        continue
-                    tmp, r = buf[r0].clone(), r0
-                    while perm[r] != r0:
-                        buf[r].copy_(buf[perm[r]])
-                        done[r], r = True, perm[r]
-                    buf[r].copy_(tmp)
-                    done[r] = True
-                self.fmap1_slot.copy_(torch.arange(len(perm), dtype=torch.int32, device=self.fmap1_slot.device))
+        # the host-driven path addresses ring row r as slot r: undo the table's permutation of the level-0 planes
+        # (cycle by cycle through ONE scratch plane: a gather of the whole ring would materialise a second copy of
+        # it -- mem x 4.9 MB at 640 x 480 -- on every hand-back behind a dropped keyframe, ADVICE r4)
+        perm = [int(v) for v in self.fmap1_slot.cpu().tolist()]          # row r lives in slot perm[r]
+        if perm != list(range(len(perm))):
+            buf, done = self.slam.fmap1_, [False] * len(perm)
+            for r0 in range(len(perm)):
+                if done[r0] or perm[r0] == r0:
+                    done[r0] = True
+                    continue
+                tmp, r = buf[r0].clone(), r0
+                while perm[r] != r0:
+                    buf[r].copy_(buf[perm[r]])
+                    done[r], r = True, perm[r]
+                buf[r].copy_(tmp)
+                done[r] = True
+            self.fmap1_slot.copy_(torch.arange(len(perm), dtype=torch.int32, device=self.fmap1_slot.device))
         d = self.dyn.cpu().numpy()
         Ek, n = int(d[DYN_EKEPT]), int(d[DYN_NROW])
         pg = self.pinned_graph()

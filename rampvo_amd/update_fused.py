@@ -6,12 +6,10 @@ two GEMMs is ONE kernel.  The hidden state stays fp32; GEMM inputs/outputs are `
 under MIXED_PRECISION -- what the reference's autocast does -- or float).  Weight copies in
 ``dtype`` (f|g and the two heads stacked) are cached per module.
 """
-import os
-
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, switches
 from ._lib import check, lib, ptr, stream
 
 _code = {torch.float32: _lib.RAMP_F32, torch.float16: _lib.RAMP_F16}
@@ -62,7 +60,7 @@ class FusedUpdate:
         self.use_softagg = True      # SoftAgg without the [f | g] rows
         # fp32: the Linear layers on the f16 matrix cores from split operands (csrc/update_x3.hip), fused chains as on the
         # fp16 path; RAMP_X3=0: library GEMMs + the row kernels of csrc/update.hip (A/B runs)
-        self.use_x3 = dtype == torch.float32 and os.environ.get("RAMP_X3", "1") == "1"
+        self.use_x3 = dtype == torch.float32 and switches.read().x3
         self.before_gru = None                   # optional callable run right before a stage is enqueued
         self.hook_at = "gru"
 

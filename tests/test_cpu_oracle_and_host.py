@@ -31,6 +31,78 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert b"gfx950" in lib.ramp_version()
 
 
+def test_track_descriptor_mirror_matches_the_c_layout(tmp_path):
+    """track_dev.Track / TrackWeights mirror include/ramp_hip.h's ramp_track / ramp_track_weights by hand: the system C
+    compiler's sizeof and offsetof of every field the ctypes mirror names equal the ctypes ones"""
+    import shutil
+    import subprocess
+    from rampvo_amd import track_dev
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    assert cc, "no C compiler on PATH"
+    structs = (("ramp_track", track_dev.Track), ("ramp_track_weights", track_dev.TrackWeights))
+    lines = ['#include "ramp_hip.h"', "#include <stdio.h>", "int main(void) {"]
+    want = []
+    for cname, py in structs:
+        lines.append('  printf("%%zu\\n", sizeof(%s));' % cname)
+        want.append(ctypes.sizeof(py))
+        for name, _ in py._fields_:
+            lines.append('  printf("%%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));' % (cname, name, cname, name))
+            want.append("%d %d" % (getattr(py, name).offset, getattr(py, name).size))
+    lines += ["  return 0;", "}"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines) + "\n")
+    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
+    names = [c for c, py in structs for c in [c] + ["%s.%s" % (c, n) for n, _ in py._fields_]]
+    for name, g, w in zip(names, got, want):
+        assert g == str(w), "%s: C %s, ctypes %s" % (name, g, w)
+    assert len(got) - 1 == len(want)
+
+
+def test_switch_reader_defaults_and_fallbacks():
+    """rampvo_amd.switches.read(): unset variables give the defaults, values that do not parse or are out of range give
+    the same defaults, and kernel-serialising runtimes turn the flag waits off"""
+    from rampvo_amd import _lib, switches
+    d = switches.read({})
+    assert d == switches.Switches()
+    assert (d.device_step, d.inputs_ready, d.flag_waits, d.x3, d.conv_x3, d.corr_f32_mfma, d.host_threads) == \
+        (True, False, True, True, True, 2, None)
+    junk = switches.read(dict(RAMP_DEVICE_STEP="yes", RAMP_INPUTS_READY="maybe", RAMP_NO_FLAG_WAITS="0", RAMP_X3="on",
+                              RAMP_CONV_X3="", RAMP_CORR_F32_MFMA="fast", RAMP_HOST_THREADS="many"))
+    assert junk == switches.Switches(device_step=False, x3=False)      # (only "1" turns these two on)
+    assert switches.read(dict(RAMP_CORR_F32_MFMA="7")).corr_f32_mfma == 2
+    assert switches.read(dict(RAMP_CORR_F32_MFMA="-1")).corr_f32_mfma == 2
+    assert switches.read(dict(RAMP_HOST_THREADS="-3")).host_threads is None
+    assert switches.read(dict(RAMP_HOST_THREADS="")).host_threads is None
+    s = switches.read(dict(RAMP_DEVICE_STEP="0", RAMP_INPUTS_READY="stream", RAMP_X3="0", RAMP_CONV_X3="0",
+                           RAMP_CORR_F32_MFMA="0", RAMP_HOST_THREADS="0"))
+    assert s == switches.Switches(device_step=False, inputs_ready="stream", x3=False, conv_x3=False, corr_f32_mfma=0,
+                                  host_threads=0)
+    assert switches.read(dict(RAMP_INPUTS_READY="1", RAMP_CORR_F32_MFMA="1", RAMP_HOST_THREADS="6")) == \
+        switches.Switches(inputs_ready=True, corr_f32_mfma=1, host_threads=6)
+    for k in ("RAMP_NO_FLAG_WAITS", "ROCPROF_COUNTER_COLLECTION", "AMD_SERIALIZE_KERNEL", "HIP_LAUNCH_BLOCKING"):
+        assert not switches.read({k: "1"}).flag_waits and switches.read({k: "0"}).flag_waits
+    assert _lib.corr_f32_mode() == switches.read().corr_f32_mfma
+
+
+def test_switches_are_read_in_one_place():
+    """the C library reads no environment (every choice is an argument or a ramp_track field), and in the package only
+    the switch reader, _lib.LIB_PATH (RAMP_HIP_LIB) and hostenv's LOCAL_WORLD_SIZE touch os.environ"""
+    csrc = os.path.join(ROOT, "rampvo_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h", ".cpp")):
+            assert "getenv" not in open(os.path.join(csrc, f)).read(), f
+    allowed = {"switches.py": None, "_lib.py": "RAMP_HIP_LIB", "hostenv.py": "LOCAL_WORLD_SIZE"}
+    pkg = os.path.join(ROOT, "rampvo_amd")
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if not f.endswith(".py") or os.path.join(dirpath, f) == os.path.join(pkg, "switches.py"):
+                continue
+            for line in open(os.path.join(dirpath, f)):
+                if "environ" in line or "getenv" in line:
+                    assert dirpath == pkg and allowed.get(f) and allowed[f] in line, (f, line)
+
+
 def test_product_package_never_imports_the_oracle():
     pkg = os.path.join(ROOT, "rampvo_amd")
     for dirpath, _, files in os.walk(pkg):

@@ -80,13 +80,9 @@ def test_conv_x3_against_fp64_and_the_exact_product_kernel(cin, cout, k, stride,
     out = {}
     with torch.no_grad():
         for x3 in (True, False):
-            conv_hip.X3 = x3
-            try:
-                y = conv_hip.conv2d(x, conv, pre=(sc, sh), res=res, relu=True, out_scale=0.25)
-                pend = conv_hip.conv2d(x, conv, want_stats=True)
-                out[x3] = (y, pend.raw, pend.scale, pend.shift)
-            finally:
-                conv_hip.X3 = True
+            y = conv_hip.conv2d(x, conv, pre=(sc, sh), res=res, relu=True, out_scale=0.25, x3=x3)
+            pend = conv_hip.conv2d(x, conv, want_stats=True, x3=x3)
+            out[x3] = (y, pend.raw, pend.scale, pend.shift)
         xd = x.double().permute(2, 0, 1)[None]
         w, b = conv.weight.double(), conv.bias.double()
         raw = F.conv2d(xd, w, b, stride, k // 2)[0].permute(1, 2, 0)

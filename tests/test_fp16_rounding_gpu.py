@@ -68,7 +68,7 @@ def _setup():
 def test_fused_chains_against_the_rounding_emulator(E):
     """every fp16 chain of the update operator against roundref.Chains: single-rounding outputs (fg, the heads' Linear)
     by check_rounded, fp32 outputs and SoftAgg by the elementwise bounds, fp16 copies of fp32 state bit for bit.
-    The instantiations each E reaches on a 256-CU MI355X (update_mlp.hip: ramp_i_upd_gru's row choice, big_pick_nmt):
+    The instantiations each E reaches on a 256-CU MI355X (update_mlp.hip: ramp_i_upd_gru's row choice, use_big):
     E = 1003: upd_gru_kernel<4> (64 rows), the 64-row upd_nbr / upd_fg kernels; E = 20011: upd_gru_kernel<5> (80 rows),
     upd_nbr_big_kernel with NMT = 5 (80 rows), upd_fg_big_kernel with NMT = 6 (96 rows); E = 41003: upd_gru_kernel<4> again and the same
     big kernels, with other partial last tiles.  upd_corr_mlp (64 rows), SoftAgg (80 sorted positions per workgroup)

@@ -834,6 +834,57 @@ def test_event_ordered_streams_equal_signal_word_ordered_streams():
             assert np.array_equal(runs[0][k], b[k]), k
 
 
+def test_fp32_trackers_in_one_process_each_use_their_own_correlation_kernel():
+    """The fp32 correlation kernel of the device-resident step follows the planes the tracker's patchifier packed
+    (ramp_track.corr_f32_mfma), not the first step of the process: two fp32 trackers one after the other in one process --
+    RAMP_CORR_F32_MFMA unset (split fp16 pairs), then 0 (plain planes, the reference order) -- each equal, bit for bit, to
+    the same frames under that setting in a fresh process"""
+    import os
+    import subprocess
+    import sys
+    import tempfile
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import os, sys, numpy as np, torch; sys.path.insert(0, %r)\n"
+            "from rampvo_amd.config import make_cfg; from rampvo_amd.Ramp_vo import Ramp_vo\n"
+            "from rampvo_amd.synthetic import SyntheticStream, make_network\n"
+            "T = 44; stream = SyntheticStream(240, 320, T, seed=77, device='cuda')\n"
+            "frames = [stream.frame(t) for t in range(T)]; torch.cuda.synchronize()\n"
+            "for i, mode in enumerate(sys.argv[2:]):\n"
+            "    os.environ.pop('RAMP_CORR_F32_MFMA', None)\n"
+            "    if mode != 'unset':\n"
+            "        os.environ['RAMP_CORR_F32_MFMA'] = mode\n"
+            "    torch.manual_seed(5)\n"
+            "    slam = Ramp_vo(make_cfg('default', PATCHES_PER_FRAME=48, MIXED_PRECISION=False), make_network('SingleScale'),"
+            " {'event_bias': True}, ht=240, wd=320)\n"
+            "    resident = 0\n"
+            "    with torch.no_grad():\n"
+            "        for t in range(T):\n"
+            "            im, ev, K, mask = frames[t]; slam(t, input_tensor=(ev, im, mask), intrinsics=K)\n"
+            "            resident += int(slam._dev is not None and slam._dev.active)\n"
+            "        slam.update(); traj, ts = slam.terminate()\n"
+            "    n = slam.n\n"
+            "    np.savez(sys.argv[1] + '%%d.npz' %% i, traj=traj, poses=slam.poses_[:n].cpu().numpy(),"
+            " patches=slam.patches_[:n].cpu().numpy(), net=slam.net.float().cpu().numpy(), ii=slam._ii, jj=slam._jj,"
+            " kk=slam._kk, split=np.array([slam._split]), dev=np.array([resident]))\n"
+            "    del slam; torch.cuda.synchronize()\n") % root
+
+    def runs(td, tag, modes):
+        env = {k: v for k, v in os.environ.items() if k != "RAMP_CORR_F32_MFMA"}
+        r = subprocess.run([sys.executable, "-c", code, os.path.join(td, tag)] + list(modes), env=env, capture_output=True,
+                           text=True, timeout=900, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return [dict(np.load(os.path.join(td, "%s%d.npz" % (tag, i)))) for i in range(len(modes))]
+
+    with tempfile.TemporaryDirectory() as td:
+        both = runs(td, "both", ["unset", "0"])
+        fresh = runs(td, "split", ["unset"]) + runs(td, "plain", ["0"])
+    assert bool(both[0]["split"][0]) and not bool(both[1]["split"][0])
+    for a, b in zip(both, fresh):
+        assert int(a["dev"][0]) > 20 and int(b["dev"][0]) > 20, "the run never reached the device-resident step"
+        for k in a:
+            assert np.array_equal(a[k], b[k]), k
+
+
 def test_bench_runs_the_fp32_path():
     """bench.py --mixed 0: the fp32 tracker's steps are device resident too (one C call per frame, the operator's chains are
     csrc/update_x3.hip's) -- correlation / operator / BA legs from the step's probes"""

@@ -9,13 +9,12 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import numpy as np, torch
 import pipeline_checks as pc
 import rampvo_amd.synthetic as syn
-from rampvo_amd import conv_hip
 g = pc.gold("ramp_vo_traj_full.npz")
 orig_frame = syn.SyntheticStream.frame
 res = {}
 for name, x3, eps in (("split", True, 0.0), ("exact", False, 0.0), ("exact, images x (1 + 2^-22 u)", False, 2.0 ** -22),
                       ("split, images x (1 + 2^-22 u)", True, 2.0 ** -22)):
-    conv_hip.X3 = x3
+    os.environ["RAMP_CONV_X3"] = "1" if x3 else "0"      # (read when run_trajectory builds the network)
     def frame(self, t, _eps=eps):
         image, events, K, mask = orig_frame(self, t)
         if _eps:
@@ -34,4 +33,4 @@ for name, x3, eps in (("split", True, 0.0), ("exact", False, 0.0), ("exact, imag
         np.percentile(err, 99.9), err.max(), int((err > 1e-4).sum()), err.size))
     print("   worst (keyframe, patch, reference, here):", [(int(i // d_ref.shape[1]), int(i % d_ref.shape[1]), round(float(d_ref.ravel()[i]), 6), round(float(d_got.ravel()[i]), 6)) for i in idx])
 syn.SyntheticStream.frame = orig_frame
-conv_hip.X3 = True
+os.environ.pop("RAMP_CONV_X3")
