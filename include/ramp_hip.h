@@ -456,6 +456,9 @@ int ramp_conv2d_nhwc_multi(const ramp_conv_job *jobs, int njobs, int H, int W, i
 
 /* number of per-block partials ramp_conv2d_nhwc writes to `stats` for this layer shape / dtype   */
 int ramp_conv2d_stats_blocks(int H, int W, int Cin, int Cout, int KH, int stride, int dtype);
+/* 1 where ramp_conv2d_nhwc runs this layer shape / dtype on the LDS-tiled fp16 kernel (the shapes ramp_conv2d_nhwc_multi
+ * covers; its partials are per 8 x 16 output tile), 0 where on the direct one                                         */
+int ramp_conv2d_tiled(int Cin, int Cout, int KH, int stride, int dtype);
 
 /* InstanceNorm2d statistics (affine=False, biased variance): scale = rsqrt(var+eps),
  * shift = -mean*scale, from the per-block partials of ramp_conv2d_nhwc                         */

@@ -4,6 +4,7 @@ implicit-GEMM MFMA conv towers (csrc/conv.hip).  Activations are NHWC float32 te
 consumer conv's load path (``pre``) or on the residual-block tail kernel.
 """
 import ctypes
+import math
 import threading
 
 import torch
@@ -57,7 +58,6 @@ def pack_conv_weight(conv, mode="f32"):
         # exact-class products on the f16 matrix cores (csrc/conv.hip::conv_x3_kernel): fragments of the THREE fp16 parts of
         # W 2^s -- w0 = fp16(W 2^s), w1 = fp16((W 2^s - w0) 2^11), w2 = fp16((W 2^s - w0 - w1 2^-11) 2^22), s the power of two
         # that puts max |W| 2^s into [2^12, 2^13) -- followed by the exact inverse 2^-s as one float
-        import math
         amax = float(w.detach().abs().max())
         e = (12 - math.floor(math.log2(amax))) if amax > 0 else 0
         ws = t.double() * (2.0 ** e)
@@ -129,7 +129,6 @@ def pack_lstm_mfma(enc):
 
 # ------------------------------------------------------------------------ primitives
 IN_ACC_R = 8             # include/ramp_hip.h::RAMP_IN_ACC_R
-_IN_ACC = True           # (False: per-layer ramp_in_stats_finalize launches -- round 3's A/B)
 
 
 class Pending:
@@ -210,7 +209,7 @@ class ConvJob(ctypes.Structure):
                 ("skip_eps", ctypes.c_float), ("skip_relu", ctypes.c_int32), ("mat", ctypes.c_void_p)]
 
 
-_TAIL_FUSE = True        # (False: a norm_add_relu launch per residual block -- round 4's A/B)
+_TAIL_FUSE = True        # test hook, not a tuning knob (False: a norm_add_relu launch per residual block, which the tests compare with)
 
 
 class Tail:
@@ -266,6 +265,31 @@ def _conv_mode(x, half, direct=False):
     return mode, code, torch.float16
 
 
+def _out_size(H, W, k, stride):
+    return (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
+
+
+def _check_layout(x, conv, wpk, mode, Cin, res, odt):
+    """the packed weights fit the input's (padded) channels, 'same' padding, contiguous operands of the right type"""
+    kc = 32 if mode == "f16" else 16
+    assert Cin == ((conv.weight.shape[1] + 15) // 16 * 16 if mode == "x3" else wpk.shape[1] * kc)
+    assert conv.padding[0] == conv.weight.shape[2] // 2 and x.is_contiguous()
+    assert res is None or (res.is_contiguous() and res.dtype == odt)
+
+
+def _block_stats(y, nblk, eps):
+    """per-block InstanceNorm statistics of the raw conv output y [OH, OW, C]: the buffer the conv launch fills, the
+    Pending it leads to and the finalize launch to run behind the conv (one allocation for all three arrays)"""
+    OH, OW, cout = y.shape
+    ws = torch.empty(cout * 2 * nblk + 2 * cout, dtype=torch.float32, device=y.device)
+    scale, shift, stats = ws[:cout], ws[cout:2 * cout], ws[2 * cout:]
+
+    def finalize():
+        check(lib().ramp_in_stats_finalize(ptr(stats), nblk, cout, float(OH * OW), float(eps), ptr(scale), ptr(shift),
+                                           stream()), "ramp_in_stats_finalize")
+    return stats, Pending(y, scale, shift), finalize
+
+
 def conv2d(x, conv, pre=None, res=None, relu=False, want_stats=False, out_scale=1.0, eps=1e-5, half=False,
            direct=False, x3=True):
     """x [H,W,Cin] NHWC (or a Pending: normalise+ReLU on load).  fp32 in/out, or with ``half``:
@@ -286,27 +310,19 @@ def conv2d(x, conv, pre=None, res=None, relu=False, want_stats=False, out_scale=
                                                                            RAMP_F32 | _lib.RAMP_CONV_X3) > 0:
         mode, code = "x3", RAMP_F32 | _lib.RAMP_CONV_X3      # the layer shapes conv_x3_kernel covers (the towers' 3x3 / 7x7 layers)
     wpk, bias = pack_conv_weight(conv, mode)
-    kc = 32 if mode == "f16" else 16
-    assert (mode == "x3" and Cin == (conv.weight.shape[1] + 15) // 16 * 16) or (mode != "x3" and Cin == wpk.shape[1] * kc)
-    assert conv.padding[0] == kh // 2 and x.is_contiguous()
-    assert res is None or (res.is_contiguous() and res.dtype == odt)
-    OH = (H + 2 * (kh // 2) - kh) // stride + 1
-    OW = (W + 2 * (kw // 2) - kw) // stride + 1
+    _check_layout(x, conv, wpk, mode, Cin, res, odt)
+    OH, OW = _out_size(H, W, kh, stride)
     y = torch.empty(OH, OW, cout, dtype=odt, device=x.device)
     nblk = lib().ramp_conv2d_stats_blocks(H, W, Cin, cout, kh, stride, code)
     assert nblk > 0
-    stats = torch.empty(cout, 2, nblk, dtype=torch.float32, device=x.device) if want_stats else None
+    stats, out, finalize = _block_stats(y, nblk, eps) if want_stats else (None, y, None)
     check(lib().ramp_conv2d_nhwc(ptr(x), ptr(wpk), ptr(bias), ptr(pre[0]) if pre else None,
                                  ptr(pre[1]) if pre else None, ptr(res), ptr(y), ptr(stats), H, W, Cin, cout,
                                  kh, kw, stride, int(relu), float(out_scale), code, stream()),
           "ramp_conv2d_nhwc")
-    if not want_stats:
-        return y
-    scale = torch.empty(cout, dtype=torch.float32, device=x.device)
-    shift = torch.empty(cout, dtype=torch.float32, device=x.device)
-    check(lib().ramp_in_stats_finalize(ptr(stats), nblk, cout, float(OH * OW), float(eps), ptr(scale), ptr(shift),
-                                       stream()), "ramp_in_stats_finalize")
-    return Pending(y, scale, shift)
+    if want_stats:
+        finalize()
+    return out
 
 
 def conv2d_towers(jobs, half, fp8=False, x3=True):
@@ -343,19 +359,15 @@ def conv2d_towers(jobs, half, fp8=False, x3=True):
         code |= _lib.RAMP_CONV_FP8
     c0 = jobs[0]["conv"]
     kh, stride = c0.weight.shape[2], c0.stride[0]
-    OH = (H + 2 * (kh // 2) - kh) // stride + 1
-    OW = (W + 2 * (kh // 2) - kh) // stride + 1
-    nblk = lib().ramp_conv2d_stats_blocks(H, W, Cin, c0.weight.shape[0], kh, stride, code)
-    tiles_y = (OH + 7) // 8
-    if nblk != tiles_y * ((OW + 15) // 16):
+    OH, OW = _out_size(H, W, kh, stride)
+    if not lib().ramp_conv2d_tiled(Cin, c0.weight.shape[0], kh, stride, code):
         return single()                          # not a tiled-kernel layer shape
+    nblk = lib().ramp_conv2d_stats_blocks(H, W, Cin, c0.weight.shape[0], kh, stride, code)
     arr = (ConvJob * len(jobs))()
     outs, finalize, written = [], [], []
     for t, j in enumerate(jobs):
         x, conv = j["x"], j["conv"]
-        pre = acc_in = None
-        x2 = None
-        tail = None
+        pre = acc_in = x2 = tail = None
         if paired:
             x, x2 = x.a, x.b
         if isinstance(x, Tail):
@@ -377,22 +389,18 @@ def conv2d_towers(jobs, half, fp8=False, x3=True):
             wpk, bias = pack_conv_weight(conv, mode)
         cout = conv.weight.shape[0]
         assert tuple(x.shape) == (H, W, Cin - (x2.shape[2] if x2 is not None else 0)) and x.dtype == x0.dtype and x.is_contiguous()
-        assert conv.weight.shape[2] == kh and conv.stride[0] == stride and conv.padding[0] == kh // 2
-        assert Cin == wpk.shape[1] * (32 if mode == "f16" else 16)
+        assert conv.weight.shape[2] == kh and conv.stride[0] == stride
         res = j.get("res")
         if isinstance(res, Tail):
             res = res.tensor()
-        assert res is None or (res.is_contiguous() and res.dtype == odt)
+        _check_layout(x, conv, wpk, mode, Cin, res, odt)
         y = torch.empty(OH, OW, cout, dtype=odt, device=x.device)
         a = arr[t]
         a.x, a.wpk, a.bias = ptr(x), ptr(wpk), ptr(bias)
         a.x2, a.c0 = (ptr(x2), x.shape[2]) if x2 is not None else (None, 0)
         a.pre_scale, a.pre_shift = (ptr(pre[0]), ptr(pre[1])) if pre else (None, None)
         a.acc_in, a.in_count, a.in_eps = (ptr(acc_in.acc), acc_in.count, acc_in.eps) if acc_in else (None, 0.0, 0.0)
-        a.skip = a.acc_skip = a.mat = None
-        a.skip_count = a.skip_eps = 0.0
-        a.skip_relu = 0
-        if tail is not None:
+        if tail is not None:                     # (the fields of a fresh ConvJob are zero: no fused tail, no statistics)
             assert acc_in is not None
             sk = tail.skip
             if isinstance(sk, Tail):
@@ -406,22 +414,19 @@ def conv2d_towers(jobs, half, fp8=False, x3=True):
                 tail.out = torch.empty_like(x)
                 a.mat = ptr(tail.out)
                 written.append(tail)
-        a.acc_out = None
         a.res, a.y = ptr(res), ptr(y)
         a.Cout, a.relu, a.out_scale = cout, int(j.get("relu", False)), float(j.get("out_scale", 1.0))
         a.act_scale, a.w_scale = (FP8_ACT_SCALE, w_scale) if use8 else (0.0, 0.0)
         acc = _scope.cur.slot(cout) if (j.get("want_stats", False) and _scope.cur is not None) else None
         if acc is not None:
-            a.stats, a.acc_out = None, ptr(acc)
+            a.acc_out = ptr(acc)
             outs.append(Pending(y, None, None, acc=acc, count=OH * OW, eps=j.get("eps", 1e-5)))
         elif j.get("want_stats", False):
-            ws = torch.empty(cout * 2 * nblk + 2 * cout, dtype=torch.float32, device=x.device)
-            scale, shift, stats = ws[:cout], ws[cout:2 * cout], ws[2 * cout:]
+            stats, out, fin = _block_stats(y, nblk, j.get("eps", 1e-5))
             a.stats = ptr(stats)
-            finalize.append((stats, cout, scale, shift, float(j.get("eps", 1e-5))))
-            outs.append(Pending(y, scale, shift))
+            finalize.append(fin)
+            outs.append(out)
         else:
-            a.stats = None
             outs.append(y)
     rc = lib().ramp_conv2d_nhwc_multi(arr, len(jobs), H, W, Cin, kh, stride, code, stream())
     if rc == _lib.RAMP_EUNSUPPORTED:
@@ -433,9 +438,8 @@ def conv2d_towers(jobs, half, fp8=False, x3=True):
     check(rc, "ramp_conv2d_nhwc_multi")
     for tl in written:
         tl.written = True
-    for stats, cout, scale, shift, eps in finalize:
-        check(lib().ramp_in_stats_finalize(ptr(stats), nblk, cout, float(OH * OW), eps, ptr(scale), ptr(shift),
-                                           stream()), "ramp_in_stats_finalize")
+    for fin in finalize:
+        fin()
     return outs
 
 
@@ -519,7 +523,7 @@ def basic_encoder4_towers(encs, x, out_scale=1.0, half=False, fp8=False, x3=True
     (``half``: fp16 storage + fp16 MFMA after the first layer's fp32 input).  relu(norm1(conv1)) is never
     materialised: layer1's first conv applies it while loading, the block's tail while adding the skip."""
     norms = _tower_norms(encs)
-    _scope.cur = (_scope.prepared or _AccArena(x.device)) if (half and _IN_ACC and any(norms)) else None
+    _scope.cur = (_scope.prepared or _AccArena(x.device)) if (half and any(norms)) else None
     _scope.prepared = None
     try:
         xs = _first_layer(encs, x, norms, half, x3)
@@ -536,7 +540,7 @@ def basic_encoder4(enc, x, out_scale=1.0, half=False, x3=True):
     return basic_encoder4_towers([enc], x, out_scale, half, x3=x3)[0]
 
 
-_MS_PAIR = True          # (False: torch.cat copies -- round 4's A/B)
+_MS_PAIR = True          # test hook, not a tuning knob (False: torch.cat copies, which the tests compare with)
 
 
 def multiscale_encoder4_towers(encs, x, x2, x4, out_scale=1.0, half=False, fp8=False, x3=True):
@@ -544,7 +548,7 @@ def multiscale_encoder4_towers(encs, x, x2, x4, out_scale=1.0, half=False, fp8=F
     x2 [H/2,W/2,32] and x4 [H/4,W/4,64] (the three super-states) -> [H/4,W/4,out].  The channel
     concatenations are the only non-conv steps; layer2/conv2 are unused, as upstream."""
     norms = _tower_norms(encs)
-    _scope.cur = _AccArena(x.device) if (half and _IN_ACC and any(norms)) else None
+    _scope.cur = _AccArena(x.device) if (half and any(norms)) else None
     try:
         xs = _first_layer(encs, x, norms, half, x3)
         for b in range(2):
@@ -599,7 +603,7 @@ def lstm_superstate_step(enc, ev, im, st, arena_for_towers=False):
     # the presence test is the front end's first launch: it also zeroes the InstanceNorm accumulators of the tower pass
     # that follows (a persistent arena of this state; its memset launch was 4.8 us + a boundary of every front end)
     arena = None
-    if arena_for_towers and _IN_ACC:
+    if arena_for_towers:
         if st.arena is None:
             st.arena = _AccArena(ev.device, zeroed=False)
         arena = st.arena
@@ -631,15 +635,20 @@ class MsState:
         self.fresh = True
 
 
-def pack_ms_scale(enc, k):
-    """the 12 weight arrays of ramp_ms_lstm_superstate for scale index k (see include/ramp_hip.h)"""
+def _ms_modules(enc, k):
+    """scale k's (events encoder, image encoder, events mix, image mix) and the cache key of their 14 parameters"""
     ev, im = enc.ev_encoders[k], enc.im_encoders[k]
     me, mi = enc.super_state_ev_encoder[k].encoder, enc.super_state_im_encoders[k].encoder
     params = [ev.conv_1.weight, ev.conv_1.bias, im.conv_1.weight, im.conv_1.bias,
               ev.convlstm.weight_ih_l0, ev.convlstm.bias_ih_l0, ev.convlstm.bias_hh_l0,
               im.convlstm.weight_ih_l0, im.convlstm.bias_ih_l0, im.convlstm.bias_hh_l0,
               me.weight, me.bias, mi.weight, mi.bias]
-    key = tuple((q.data_ptr(), q._version) for q in params)
+    return ev, im, me, mi, tuple((q.data_ptr(), q._version) for q in params)
+
+
+def pack_ms_scale(enc, k):
+    """the 12 weight arrays of ramp_ms_lstm_superstate for scale index k (see include/ramp_hip.h)"""
+    ev, im, me, mi, key = _ms_modules(enc, k)
     hit = _cache(enc).get(("ms", k))
     if hit is not None and hit[0] == key:
         return hit[1]
@@ -649,7 +658,6 @@ def pack_ms_scale(enc, k):
             f(ev.convlstm.weight_ih_l0), f(ev.convlstm.bias_ih_l0 + ev.convlstm.bias_hh_l0),
             f(im.convlstm.weight_ih_l0), f(im.convlstm.bias_ih_l0 + im.convlstm.bias_hh_l0),
             f(me.weight.view(d, 2 * d).t()), f(me.bias), f(mi.weight.view(d, 2 * d).t()), f(mi.bias)]
-    import ctypes
     ptrs = (ctypes.c_void_p * 12)(*[a.data_ptr() for a in arrs])
     _cache(enc)[("ms", k)] = (key, (arrs, ptrs))
     return arrs, ptrs
@@ -660,13 +668,7 @@ def pack_ms_scale_mfma(enc, k):
     v_mfma_f32_16x16x4_f32 as one float per lane (lane l: row i = l & 15, K column kq = l >> 4), in the order the kernel
     walks them (csrc/conv.hip::ms_lstm_superstate_mfma_kernel: gates ev [t][i,g,o][2 K steps], gates im [t][i,g,o], mix ev
     [n][K step], mix im), and the small arrays (conv_1 weights / biases, gate biases [i,g,o][D] x 2, mix biases x 2)."""
-    ev, im = enc.ev_encoders[k], enc.im_encoders[k]
-    me, mi = enc.super_state_ev_encoder[k].encoder, enc.super_state_im_encoders[k].encoder
-    params = [ev.conv_1.weight, ev.conv_1.bias, im.conv_1.weight, im.conv_1.bias,
-              ev.convlstm.weight_ih_l0, ev.convlstm.bias_ih_l0, ev.convlstm.bias_hh_l0,
-              im.convlstm.weight_ih_l0, im.convlstm.bias_ih_l0, im.convlstm.bias_hh_l0,
-              me.weight, me.bias, mi.weight, mi.bias]
-    key = tuple((q.data_ptr(), q._version) for q in params)
+    ev, im, me, mi, key = _ms_modules(enc, k)
     hit = _cache(enc).get(("ms_mfma", k))
     if hit is not None and hit[0] == key:
         return hit[1]
@@ -702,14 +704,11 @@ def pack_ms_scale_mfma(enc, k):
     return wfrag, wsmall
 
 
-_MS_MFMA = True          # (False: the fp32 VALU kernel -- round 4's A/B)
-
-
 def ms_lstm_superstate_step(enc, k, ev, im, st, use_im, want_half=False):
     """ev [5,H,W], im [3,H,W] contiguous fp32; advances scale k's super-state in place and returns
     it as an NHWC tensor [Hs, Ws, D] (a view of st.s; with want_half the kernel's fp16 copy of it)"""
     H, W = ev.shape[-2:]
-    if _MS_MFMA and (enc.scales[k] == 1 or st.Ws % 16 == 0):
+    if enc.scales[k] == 1 or st.Ws % 16 == 0:        # (else: the fp32 VALU kernel below)
         wfrag, wsmall = pack_ms_scale_mfma(enc, k)
         s16 = None
         if want_half:

@@ -742,26 +742,20 @@ __global__ void __launch_bounds__(256) conv_tile_f16_kernel(const ConvMulti pm) 
 // the reference multiplies exactly and rounds only sums, and so does this kernel.
 // A workgroup owns an 8 x 16 output tile of ALL output channels:
 //   * the fp32 halo tile is loaded once, relu(x scale + shift) applied once per value, the three parts parked in LDS as three
-//     planes (pixel stride CIN 2 + 16 bytes: conflict-free ds_read_b128 A fragments);
+//     planes (pixel stride CIN 2 bytes, unpadded: padding spreads the A-fragment reads over the banks but costs workgroups per
+//     CU -- 7x7 layer 112 instead of 75 KB -- and measured slower);
 //   * weights are packed per layer as fp16 fragments of the three parts of W 2^s (s: max |W| 2^s in [2^12, 2^13)), plus the
 //     exact inverse 2^-s behind the pack (rampvo_amd/conv_hip.py::pack_conv_weight mode "x3");
 //   * a wave owns one 16-channel tile of the output and 8 (COUT = 64) or 4 (COUT = 32) of the tile's rows, so every weight
 //     fragment is fetched from L2 once per workgroup and the A fragments come from LDS;
 //   * bias, InstanceNorm partial sums (sum, sum of squares of the raw output over the tile's valid pixels -> stats[C][2][nblk],
 //     the direct kernel's contract), ReLU, residual + ReLU, out_scale on the accumulators.
-#ifndef CONV_X3_PF
-#define CONV_X3_PF 1      // weight fragments one trip (two steps) ahead
-#endif
-#ifndef CONV_X3_PAD
-#define CONV_X3_PAD 0     // bytes of padding per tile pixel and plane: 16 spreads the A-fragment reads over the banks, 0 lets more
-                          // workgroups share a CU (7x7 layer 112 -> 75 KB) -- front end alone 672 -> 643 us (profiles/r06_convpad_ab.txt)
-#endif
 template <int K, int S, int CIN, int COUT>
 __global__ void __launch_bounds__(256) conv_x3_kernel(const ConvParams p) {
   constexpr int PAD = K / 2, TH = 8, TW = 16;
   constexpr int IH = (TH - 1) * S + K, IW = (TW - 1) * S + K;
   constexpr int KC = CIN >= 32 ? 32 : 16, NCH = CIN / KC, CPL = KC / 4;   // channels per MFMA step, steps per tap, halfs per lane
-  constexpr int PSTR = CIN * 2 + CONV_X3_PAD;                           // LDS bytes per tile pixel and plane
+  constexpr int PSTR = CIN * 2;                                         // LDS bytes per tile pixel and plane
   constexpr int PLANE = IH * IW * PSTR;
   constexpr int NT = COUT / 16, WPN = 4 / NT, MTW = TH / WPN;           // waves per channel tile, rows (m-tiles) per wave
   constexpr int CH4 = CIN / 4, NITEM = IH * IW * CH4;
@@ -830,7 +824,7 @@ __global__ void __launch_bounds__(256) conv_x3_kernel(const ConvParams p) {
   const float descale = *reinterpret_cast<const float *>(wph + 3 * WTOT);
   const int a_off = ((rg * MTW) * S * IW + j * S) * PSTR + q * CPL * 2;
   // One flat loop over (tap, chunk), two steps per trip (fully unrolled the compiler hoists every weight load of the layer --
-  // 256 VGPRs).  The weight fragments of the NEXT trip are requested before this trip's MFMAs are issued (CONV_X3_PF, round 6):
+  // 256 VGPRs).  The weight fragments of the NEXT trip are requested before this trip's MFMAs are issued (round 6):
   // with one wave per SIMD nothing else covers the L2 round trip of a trip's fragments, and a workgroup's life was the sum
   // of its trips' latencies -- 25 trips for the 7x7 layer
   typedef typename std::conditional<KC == 32, f16x8, f16x4>::type wv_t;
@@ -868,7 +862,6 @@ __global__ void __launch_bounds__(256) conv_x3_kernel(const ConvParams p) {
       }
     }
   };
-#if CONV_X3_PF
   WStep wa = ldw(0), wb = ldw(1);
   for (int step = 0; step < nsteps; step += 2) {
     const WStep na = ldw(step + 2), nb = ldw(step + 3);
@@ -876,10 +869,6 @@ __global__ void __launch_bounds__(256) conv_x3_kernel(const ConvParams p) {
     if (step + 1 < nsteps) run(step + 1, wb);
     wa = na; wb = nb;
   }
-#else
-#pragma unroll 2
-  for (int step = 0; step < nsteps; step++) run(step, ldw(step));
-#endif
 
   // ---- 3. epilogue on the accumulators: lane (q, j) holds pixels x = 4q .. 4q+3 of row rg MTW + mt, channel 16 nt + j
   const int c = nt * 16 + j;
@@ -919,7 +908,7 @@ __global__ void __launch_bounds__(256) conv_x3_kernel(const ConvParams p) {
     }
   }
 }
-constexpr int conv_x3_lds_bytes(int K, int S, int CIN) { return 3 * ((8 - 1) * S + K) * ((16 - 1) * S + K) * (CIN * 2 + CONV_X3_PAD); }
+constexpr int conv_x3_lds_bytes(int K, int S, int CIN) { return 3 * ((8 - 1) * S + K) * ((16 - 1) * S + K) * CIN * 2; }
 
 // First layer of BOTH towers in one workgroup (7x7 stride 2, 16 fp32 input channels -> 32 channels per tower): the two
 // towers read the same super-state, so the halo tile is staged once and feeds four 16-channel output tiles.  Unlike
@@ -927,9 +916,7 @@ constexpr int conv_x3_lds_bytes(int K, int S, int CIN) { return 3 * ((8 - 1) * S
 // L2 through a ring of registers CONV7_PF taps deep -- LDS holds the 37 KB input tile only, four workgroups per CU
 // instead of one, and the 600 tiles of a 640x480 frame are one round (the generic kernel ran 2 x 600 workgroups at one
 // per CU: 41 us).  Same tap order and accumulation as conv_tile_f16_kernel<7, 2, true, 16, 2>: identical results.
-#ifndef CONV7_PF
-#define CONV7_PF 4
-#endif
+constexpr int CONV7_PF = 4;
 __global__ void __launch_bounds__(256) conv7_dual_kernel(const ConvMulti pm) {
   constexpr int K = 7, S = 2, PAD = 3, TH = 8, TW = 16, NT = 2;
   constexpr int IH = (TH - 1) * S + K, IW = (TW - 1) * S + K;
@@ -1003,9 +990,7 @@ __global__ void __launch_bounds__(256) conv7_dual_kernel(const ConvMulti pm) {
 #pragma unroll
         for (int nt = 0; nt < NT; nt++) ring[(tap + CONV7_PF) % (CONV7_PF + 1)][t][nt] = wfrag(tap + CONV7_PF, t, nt);
     }
-#ifndef CONV7_NOSB
-    __builtin_amdgcn_sched_barrier(0);
-#endif
+    __builtin_amdgcn_sched_barrier(0);                 // (the ring's loads stay ahead of the tap's MFMAs)
     const int ky = tap / K, kx = tap - ky * K;
     f16x4 a[2];
 #pragma unroll
@@ -1193,8 +1178,6 @@ __global__ void __launch_bounds__(256)
 
 // v_exp_f32 / v_rcp_f32 based (about 1 ulp each): the IEEE expf + division + tanhf sequences were most
 // of this kernel's VALU time; the LSTM gates are insensitive at that level (test tolerance 2e-5)
-__device__ __forceinline__ float lm_sigmoid(float x) { return __frcp_rn(1.0f + __expf(-x)); }
-__device__ __forceinline__ float lm_tanh(float x) { return 2.0f * __frcp_rn(1.0f + __expf(-2.0f * x)) - 1.0f; }
 // h = sigmoid(o) tanh(sigmoid(i) tanh(g)) with 4 exponentials and 2 reciprocals (instead of 4 + 4; both run at a quarter
 // of the VALU rate): sigmoid(a) tanh(b) = sgn(b) (1 - t) / ((1 + e^-a) (1 + t)), t = e^(-2 |b|) <= 1 -- no overflow in the
 // numerator; e^-a = inf gives the right limit 0
@@ -1206,20 +1189,14 @@ __device__ __forceinline__ float ms_sig_tanh(float a, float b) {
 __device__ __forceinline__ float ms_cell(float gi, float gg, float go) { return ms_sig_tanh(go, ms_sig_tanh(gi, gg)); }
 __device__ __forceinline__ float lm_sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
-// LDSW: the 104 weight fragments per lane sit in LDS (26 KB per workgroup) instead of registers: <= 64 VGPRs, so a wave of
+// The 104 weight fragments per lane sit in LDS (26 KB per workgroup), not in registers: <= 64 VGPRs, so a wave of
 // this kernel fits on a SIMD next to the two 222-VGPR waves of the update operator's gru launch -- behind the gate the two
 // launches otherwise TIME-SHARE the chip -- and eight of them fit when it runs alone
 // The recurrent state is read once and written once per frame (120 MB): streamed with the nontemporal hint, so that it
 // does not push the update operator's weights -- which the gru launch on the other stream streams from L2 -- out of the L2
-#ifdef LM_CACHED
-#define LM_LD(p) (*(p))
-#define LM_ST(v, p) (*(p) = (v))
-#else
 #define LM_LD(p) __builtin_nontemporal_load(p)
 #define LM_ST(v, p) __builtin_nontemporal_store((v), (p))
-#endif
-template <bool LDSW>
-__global__ void __launch_bounds__(256, LDSW ? 8 : 1)
+__global__ void __launch_bounds__(256, 8)
     lstm_superstate_mfma_kernel(const float *__restrict__ ev, const float *__restrict__ im,
                                 float *__restrict__ h_ev, float *__restrict__ c_ev,
                                 float *__restrict__ h_im, float *__restrict__ c_im,
@@ -1229,26 +1206,12 @@ __global__ void __launch_bounds__(256, LDSW ? 8 : 1)
   const int lane = threadIdx.x & 63, q = lane >> 4, j = lane & 15;
   const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int ntile = (HW + 15) / 16;
-  // weights: one float per lane per fragment -- in registers for every tile of this wave, or (LDSW) in LDS
-  __shared__ float s_wf[LDSW ? LM_TOTAL * 64 : 1];
-  float a_ev[LDSW ? 1 : 24], a_im[LDSW ? 1 : 20], a_ss[LDSW ? 1 : 8], b_ev[LDSW ? 1 : 16], b_im[LDSW ? 1 : 16], b_ss[LDSW ? 1 : 4];
-  if constexpr (LDSW) {
-    for (int i = threadIdx.x; i < LM_TOTAL * 64 / 4; i += 256)
-      reinterpret_cast<float4 *>(s_wf)[i] = reinterpret_cast<const float4 *>(Wf)[i];
-    __syncthreads();
-  } else {
-#pragma unroll
-    for (int f = 0; f < 24; f++) a_ev[f] = Wf[(LM_EV + f) * 64 + lane];
-#pragma unroll
-    for (int f = 0; f < 20; f++) a_im[f] = Wf[(LM_IM + f) * 64 + lane];
-#pragma unroll
-    for (int f = 0; f < 8; f++) a_ss[f] = Wf[(LM_SS + f) * 64 + lane];
-#pragma unroll
-    for (int f = 0; f < 16; f++) { b_ev[f] = Wf[(LM_BEV + f) * 64 + lane]; b_im[f] = Wf[(LM_BIM + f) * 64 + lane]; }
-#pragma unroll
-    for (int f = 0; f < 4; f++) b_ss[f] = Wf[(LM_BSS + f) * 64 + lane];
-  }
-  auto WA = [&](int base, int f, const float *reg) -> float { if constexpr (LDSW) return s_wf[(base + f) * 64 + lane]; else return reg[f]; };
+  // weights: one float per lane per fragment, in LDS
+  __shared__ float s_wf[LM_TOTAL * 64];
+  for (int i = threadIdx.x; i < LM_TOTAL * 64 / 4; i += 256)
+    reinterpret_cast<float4 *>(s_wf)[i] = reinterpret_cast<const float4 *>(Wf)[i];
+  __syncthreads();
+  auto WA = [&](int base, int f) -> float { return s_wf[(base + f) * 64 + lane]; };
   int f_ev, f_im;
   if (nblk > 0) {
     // per-workgroup results of any_nonzero_kernel ([2][ANY_MAXB], the first nblk of each row): every wave ORs them
@@ -1304,27 +1267,21 @@ __global__ void __launch_bounds__(256, LDSW ? 8 : 1)
       for (int t = 0; t < 4; t++) {
         f32x4 acc;
 #pragma unroll
-        for (int r = 0; r < 4; r++) acc[r] = mod == 0 ? WA(LM_BEV, t * 4 + r, b_ev) : WA(LM_BIM, t * 4 + r, b_im);
+        for (int r = 0; r < 4; r++) acc[r] = mod == 0 ? WA(LM_BEV, t * 4 + r) : WA(LM_BIM, t * 4 + r);
         if (mod == 0) {
 #pragma unroll
           for (int s4 = 0; s4 < 6; s4++)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(WA(LM_EV, t * 6 + s4, a_ev), bk[s4], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(WA(LM_EV, t * 6 + s4), bk[s4], acc, 0, 0, 0);
         } else {
 #pragma unroll
           for (int s4 = 0; s4 < 5; s4++)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(WA(LM_IM, t * 5 + s4, a_im), bk[s4], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(WA(LM_IM, t * 5 + s4), bk[s4], acc, 0, 0, 0);
         }
         // acc = (i, f, g, o) pre-activations of unit 4t+q, pixel j (torch gate order i, f, g, o)
-#ifdef LM_IEEE_CELL                                       // (A/B builds: the round-3 cell, 5 exponentials + 5 IEEE reciprocals)
-        const float ig = lm_sigmoid(acc[0]), fg = lm_sigmoid(acc[1]), gg = lm_tanh(acc[2]), og = lm_sigmoid(acc[3]);
-        const float cn = has_state ? fg * cold[t] + ig * gg : ig * gg;
-        const float hv = og * lm_tanh(cn);
-#else
         // sigmoid(i) tanh(g) and sigmoid(o) tanh(c) with one 1-ulp reciprocal each (ms_sig_tanh): 5 exponentials + 3 reciprocals
         const float igg = ms_sig_tanh(acc[0], acc[2]);
         const float cn = has_state ? __builtin_fmaf(lm_sigmoid_fast(acc[1]), cold[t], igg) : igg;
         const float hv = ms_sig_tanh(acc[3], cn);
-#endif
         const bool unit_ok = 4 * t + q < 15;
         hn[mod][t] = unit_ok ? hv : 0.0f;
         cnew[t] = unit_ok ? cn : 0.0f;
@@ -1338,12 +1295,12 @@ __global__ void __launch_bounds__(256, LDSW ? 8 : 1)
 #pragma unroll
     for (int mod = 0; mod < 2; mod++) {
       if (!(mod == 0 ? f_ev : f_im)) continue;       // uniform
-      f32x4 acc = (f32x4){WA(LM_BSS, 0, b_ss), WA(LM_BSS, 1, b_ss), WA(LM_BSS, 2, b_ss), WA(LM_BSS, 3, b_ss)};
+      f32x4 acc = (f32x4){WA(LM_BSS, 0), WA(LM_BSS, 1), WA(LM_BSS, 2), WA(LM_BSS, 3)};
 #pragma unroll
-      for (int s4 = 0; s4 < 4; s4++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(WA(LM_SS, s4, a_ss), sreg[s4], acc, 0, 0, 0);
+      for (int s4 = 0; s4 < 4; s4++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(WA(LM_SS, s4), sreg[s4], acc, 0, 0, 0);
 #pragma unroll
       for (int t = 0; t < 4; t++)
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(WA(LM_SS, 4 + t, a_ss), hn[mod][t], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(WA(LM_SS, 4 + t), hn[mod][t], acc, 0, 0, 0);
       sreg = acc;
     }
     if (pv) *sp = make_float4(sreg[0], sreg[1], sreg[2], q == 3 ? 0.0f : sreg[3]);
@@ -1485,9 +1442,6 @@ struct MsMfmaParams {
   _Float16 *state16;                    // optional [Hs*Ws][D] fp16 copy of the new state
   int H, W, Hs, Ws, has_state, use_im, tiles_per_wave;
 };
-// (1 ulp reciprocal: the IEEE division sequence of __frcp_rn was a third of the cell's VALU work)
-__device__ __forceinline__ float ms_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float ms_tanh(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
 template <int D, int S, int NWV>
 __global__ void __launch_bounds__(64 * NWV) ms_lstm_superstate_mfma_kernel(const MsMfmaParams p) {
   constexpr int NG = D / 16;                           // 16-unit groups
@@ -1803,13 +1757,8 @@ static int ms_mfma_launch(const MsMfmaParams &p0, hipStream_t st) {
   constexpr int F_N = NG * 3 * 2 + NG * 3 + 16 * NG * NG;
   constexpr int O_N = 25 * KK + 5 + 9 * KK + 3 + 6 * D + 2 * D;
   constexpr int WIN = S > 1 ? 8 * K * (15 * S + K) : 0;
-  const size_t lds = (size_t)(F_N * 64 + ((O_N + 3) & ~3) + NWV * WIN) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void *)ms_lstm_superstate_mfma_kernel<D, S, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return RAMP_ELAUNCH;
-    attr_set = true;
-  }
+  constexpr size_t lds = (size_t)(F_N * 64 + ((O_N + 3) & ~3) + NWV * WIN) * sizeof(float);
+  static_assert(lds <= 64 * 1024, "dynamic LDS within the default limit: the launch needs no hipFuncSetAttribute");
   MsMfmaParams p = p0;
   const int ntile = ramp_cdiv(p.Hs * p.Ws, 16);
   // one tile per wave while that keeps the launch within ~8 waves per SIMD; more tiles per wave beyond (a workgroup's
@@ -1820,6 +1769,117 @@ static int ms_mfma_launch(const MsMfmaParams &p0, hipStream_t st) {
   hipLaunchKernelGGL((ms_lstm_superstate_mfma_kernel<D, S, NWV>), dim3(ramp_cdiv(ntile, NWV * tpw)), dim3(64 * NWV), lds, st, p);
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;
+}
+
+// ------------------------------------------------------------------ conv towers: host side
+// the layer of one conv call: what the (up to two) jobs of ramp_conv2d_nhwc / ramp_conv2d_nhwc_multi share
+struct ConvLayer { int H, W, Cin, K, S, OH, OW; bool in_f32, fp8; };
+static ConvLayer conv_layer(int H, int W, int Cin, int K, int S, bool in_f32, bool fp8) {
+  const int pad = K / 2;
+  return ConvLayer{H, W, Cin, K, S, (H + 2 * pad - K) / S + 1, (W + 2 * pad - K) / S + 1, in_f32, fp8};
+}
+
+// validates one job of layer L and fills its ConvParams: the one place a ConvParams is filled
+static int conv_params_from_job(const ConvLayer &L, const ramp_conv_job &j, ConvParams &p) {
+  if (!j.x || !j.wpk || !j.y || j.Cout <= 0 || j.Cout % 32) return RAMP_EINVAL;
+  p.x = j.x; p.wpk = j.wpk; p.bias = j.bias; p.pre_scale = j.pre_scale; p.pre_shift = j.pre_shift;
+  p.res = j.res; p.y = j.y; p.stats = j.stats;
+  p.x2 = j.x2; p.C0 = j.c0;
+  p.skip = j.skip; p.acc_skip = (const unsigned long long *)j.acc_skip; p.skip_count = j.skip_count; p.skip_eps = j.skip_eps;
+  p.skip_relu = j.skip_relu; p.mat = j.mat;
+  if (p.skip && (L.in_f32 || !j.acc_in || p.x2 || L.Cin > 128 || (p.acc_skip && !(p.skip_count > 0.f)) || (p.skip_relu && !p.acc_skip) ||
+                 (p.mat && (L.S != 1 || (L.K != 1 && L.K != 3)))))
+    return RAMP_EINVAL;
+  if (!p.skip && (p.mat || p.acc_skip)) return RAMP_EINVAL;
+  if (p.skip && (L.fp8 || j.stats)) return RAMP_EUNSUPPORTED;      // (f16 MFMA instances in accumulator mode only)
+  if (p.x2 && (L.in_f32 || p.C0 <= 0 || p.C0 >= L.Cin || (p.C0 & 7) || ((L.Cin - p.C0) & 7) || p.pre_scale || j.acc_in)) return RAMP_EINVAL;
+  p.acc_out = (unsigned long long *)j.acc_out; p.acc_in = (const unsigned long long *)j.acc_in;
+  p.in_count = j.in_count; p.in_eps = j.in_eps;
+  if (p.acc_in && (L.Cin > 128 || p.in_count <= 0.f)) return RAMP_EINVAL;
+  p.H = L.H; p.W = L.W; p.Cin = L.Cin; p.OH = L.OH; p.OW = L.OW; p.Cout = j.Cout;
+  p.relu = j.relu; p.out_scale = j.out_scale;
+  p.act_scale = 1.0f; p.descale = 1.0f;
+  if (L.fp8) {
+    if (!(j.act_scale > 0.0f) || !(j.w_scale > 0.0f)) return RAMP_EINVAL;
+    p.act_scale = j.act_scale; p.descale = 1.0f / (j.act_scale * j.w_scale);
+  }
+  return RAMP_OK;
+}
+
+// The instances of conv_tile_f16_kernel, ONE list: K, S, IN_F32, CIN, NT, TH and what exists for the row beside its plain
+// f16 instance -- T_FP8: an fp8 instance, T_TAIL: a fused-block-tail instance, T_SINGLE / T_PAIRED: ramp_conv2d_nhwc /
+// ramp_conv2d_nhwc_multi may select it.  The first row that fits wins, so among rows of one layer shape the order matters:
+//   * TH = 16 (3x3 / s1 / 32 channels, the half-resolution layers: weight fragments staged once per 256 pixels and a 1.27x
+//     instead of 1.41x halo) only where the 16 x 16 grid still has >= 512 workgroups and no tower wants per-block statistics
+//     (`stats` buffers are sized for the 8 x 16 grid) -- TileQuery::th16;
+//   * NT = 4 for 3x3 / s2 / 64 channels (the MultiScale towers' layer3: the 80 KB halo tile leaves one workgroup per CU either
+//     way; with all 64 output channels in it the tile is staged once instead of twice) only in the paired entry;
+//   * every NT = 4 row wants every Cout a multiple of 64 -- TileQuery::all64;
+//   * the 7x7 first layer (fp32 in) has no fp8 instance: it stays on the f16 MFMA.
+enum { T_FP8 = 1, T_TAIL = 2, T_SINGLE = 4, T_PAIRED = 8 };
+#define CONV_TILE_ROWS(X)                                        \
+  X(7, 2, true, 16, 2, 8, T_SINGLE | T_PAIRED)                   \
+  X(3, 1, false, 32, 2, 16, T_TAIL | T_PAIRED)                   \
+  X(3, 1, false, 32, 2, 8, T_FP8 | T_TAIL | T_SINGLE | T_PAIRED) \
+  X(3, 2, false, 32, 2, 8, T_FP8 | T_TAIL | T_SINGLE | T_PAIRED) \
+  X(3, 2, false, 64, 4, 8, T_PAIRED)                             \
+  X(3, 2, false, 64, 2, 8, T_FP8 | T_SINGLE | T_PAIRED)          \
+  X(3, 1, false, 64, 2, 8, T_FP8 | T_TAIL | T_SINGLE | T_PAIRED) \
+  X(1, 2, false, 32, 4, 8, T_FP8 | T_TAIL | T_SINGLE | T_PAIRED) \
+  X(1, 2, false, 64, 4, 8, T_FP8 | T_SINGLE | T_PAIRED)          \
+  X(1, 1, false, 64, 4, 8, T_FP8 | T_TAIL | T_SINGLE | T_PAIRED) \
+  X(1, 1, false, 128, 4, 8, T_FP8 | T_SINGLE | T_PAIRED)
+struct TileQuery {
+  int K, S, Cin;
+  bool in_f32, all64, th16;
+  int want;             // the T_* bits a row must have: the entry point, T_FP8 / T_TAIL for a launch that needs that instance
+};
+
+template <int K, int S, bool IN_F32, int CIN, int NT, bool FP8, int TH, bool TAIL>
+static int conv_tile_launch(const ConvMulti &pm, int cmax, int njobs, hipStream_t st) {
+  constexpr int lds = conv_tile_lds_bytes(K, S, IN_F32, CIN, NT, FP8, TH);
+  if (conv_tile_attr(conv_tile_f16_kernel<K, S, IN_F32, CIN, NT, FP8, TH, TAIL>, lds) != RAMP_OK) return RAMP_ELAUNCH;
+  hipLaunchKernelGGL((conv_tile_f16_kernel<K, S, IN_F32, CIN, NT, FP8, TH, TAIL>),
+                     dim3(ramp_cdiv(pm.t[0].OH, TH) * ramp_cdiv(pm.t[0].OW, 16), cmax / (NT * 16), njobs), dim3(256), lds, st, pm);
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+// the instance of a row that `want` asks for (a template, so that only the instances a row names are instantiated)
+template <int K, int S, bool IN_F32, int CIN, int NT, int TH, int VARIANTS>
+static int conv_tile_row(int want, const ConvMulti &pm, int cmax, int njobs, hipStream_t st) {
+  if constexpr ((VARIANTS & T_FP8) != 0)
+    if (want & T_FP8) return conv_tile_launch<K, S, IN_F32, CIN, NT, true, TH, false>(pm, cmax, njobs, st);
+  if constexpr ((VARIANTS & T_TAIL) != 0)
+    if (want & T_TAIL) return conv_tile_launch<K, S, IN_F32, CIN, NT, false, TH, true>(pm, cmax, njobs, st);
+  return conv_tile_launch<K, S, IN_F32, CIN, NT, false, TH, false>(pm, cmax, njobs, st);
+}
+// launches the first row that fits q -- or, without pm, only says whether there is one: RAMP_OK / RAMP_EUNSUPPORTED
+static int conv_tile_dispatch(const TileQuery &q, const ConvMulti *pm, int cmax, int njobs, hipStream_t st) {
+#define TILE_ROW(K_, S_, F32_, CIN, NT, TH, VARIANTS)                                                                     \
+  if (q.K == K_ && q.S == S_ && q.in_f32 == F32_ && q.Cin == CIN && (NT == 2 || q.all64) && (TH == 8 || q.th16) &&        \
+      ((VARIANTS) & q.want) == q.want)                                                                                    \
+    return pm ? conv_tile_row<K_, S_, F32_, CIN, NT, TH, (VARIANTS)>(q.want, *pm, cmax, njobs, st) : RAMP_OK;
+  CONV_TILE_ROWS(TILE_ROW)
+#undef TILE_ROW
+  return RAMP_EUNSUPPORTED;
+}
+
+// the layer shapes of conv_x3_kernel, ONE list: K, S, CIN, COUT; p = nullptr only asks, as above
+#define CONV_X3_ROWS(X) X(3, 1, 32, 32) X(3, 1, 64, 64) X(3, 1, 32, 64) X(3, 2, 32, 64) X(3, 1, 64, 32) X(7, 2, 16, 32)
+static int conv_x3_dispatch(int K, int S, int Cin, int Cout, const ConvParams *p, hipStream_t st) {
+#define X3_ROW(K_, S_, CIN, COUT)                                                                                         \
+  if (K == K_ && S == S_ && Cin == CIN && Cout == COUT) {                                                                 \
+    if (!p) return RAMP_OK;                                                                                               \
+    constexpr int lds = conv_x3_lds_bytes(K_, S_, CIN);                                                                   \
+    if (conv_tile_attr(conv_x3_kernel<K_, S_, CIN, COUT>, lds) != RAMP_OK) return RAMP_ELAUNCH;                           \
+    hipLaunchKernelGGL((conv_x3_kernel<K_, S_, CIN, COUT>), dim3(ramp_cdiv(p->OH, 8) * ramp_cdiv(p->OW, 16)), dim3(256),  \
+                       lds, st, *p);                                                                                      \
+    RAMP_CHECK_LAUNCH();                                                                                                  \
+    return RAMP_OK;                                                                                                       \
+  }
+  CONV_X3_ROWS(X3_ROW)
+#undef X3_ROW
+  return RAMP_EUNSUPPORTED;
 }
 
 extern "C" {
@@ -1923,17 +1983,8 @@ int ramp_lstm_superstate_blocks(const float *ev, const float *im, float *h_ev, f
     return RAMP_EINVAL;
   const int ntile = ramp_cdiv(HW, 16);
   const int tpw = ntile >= 8192 ? 4 : 1;           // tiles per wave: amortise the 104 weight fragments
-#ifndef LSTM_LDSW
-#define LSTM_LDSW 1                                // (build-time A/B, tools/ab_build.sh: 0 = weight fragments in registers)
-#endif
-  if (LSTM_LDSW)
-    hipLaunchKernelGGL(lstm_superstate_mfma_kernel<true>, dim3(ramp_cdiv(ntile, 4 * tpw)), dim3(256), 0,
-                       (hipStream_t)stream, ev, im, h_ev, c_ev, h_im, c_im, ss, wfrag, flags, HW, has_state,
-                       has_ss, tpw, nblk);
-  else
-    hipLaunchKernelGGL(lstm_superstate_mfma_kernel<false>, dim3(ramp_cdiv(ntile, 4 * tpw)), dim3(256), 0,
-                       (hipStream_t)stream, ev, im, h_ev, c_ev, h_im, c_im, ss, wfrag, flags, HW, has_state,
-                       has_ss, tpw, nblk);
+  hipLaunchKernelGGL(lstm_superstate_mfma_kernel, dim3(ramp_cdiv(ntile, 4 * tpw)), dim3(256), 0, (hipStream_t)stream, ev, im,
+                     h_ev, c_ev, h_im, c_im, ss, wfrag, flags, HW, has_state, has_ss, tpw, nblk);
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;
 }
@@ -1951,65 +2002,25 @@ int ramp_conv2d_nhwc(const void *x, const void *wpk, const float *bias, const fl
   if (!f16 && dtype != RAMP_F32 && !x3) return RAMP_EINVAL;
   if (f16 && !in_f32 && Cin % 32) return RAMP_EUNSUPPORTED;
   if (in_f32 && Cin != 16) return RAMP_EUNSUPPORTED;
-  ConvParams p;
-  p.x = x; p.wpk = wpk; p.bias = bias; p.pre_scale = pre_scale; p.pre_shift = pre_shift;
-  p.res = res; p.y = y; p.stats = stats; p.x2 = nullptr; p.C0 = 0;
-  p.skip = nullptr; p.acc_skip = nullptr; p.skip_count = 0.f; p.skip_eps = 0.f; p.skip_relu = 0; p.mat = nullptr;
-  p.acc_out = nullptr; p.acc_in = nullptr; p.in_count = 0.f; p.in_eps = 0.f;
-  p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
-  const int pad = KH / 2;
-  p.OH = (H + 2 * pad - KH) / stride + 1;
-  p.OW = (W + 2 * pad - KW) / stride + 1;
-  p.relu = relu; p.out_scale = out_scale;
-  p.act_scale = 1.0f; p.descale = 1.0f;
-  const int M = p.OH * p.OW;
-  dim3 grid(ramp_cdiv(M, 128), Cout / 32), block(256);
+  ramp_conv_job j = {};                               // the arguments as a one-job description
+  j.x = x; j.wpk = wpk; j.bias = bias; j.pre_scale = pre_scale; j.pre_shift = pre_shift;
+  j.res = res; j.y = y; j.stats = stats;
+  j.Cout = Cout; j.relu = relu; j.out_scale = out_scale;
+  ConvMulti pm;
+  const int rc = conv_params_from_job(conv_layer(H, W, Cin, KH, stride, in_f32, false), j, pm.t[0]);
+  if (rc != RAMP_OK) return rc;
+  pm.t[1] = pm.t[0];
+  const ConvParams &p = pm.t[0];
   hipStream_t st = (hipStream_t)stream;
-  if (x3) {
-    // fp32 in / out at fp32 accuracy on the f16 matrix cores (conv_x3_kernel; wpk = pack_conv_weight mode "x3")
-    const dim3 tg(ramp_cdiv(p.OH, 8) * ramp_cdiv(p.OW, 16), 1);
-#define X3_CASE(K, S, CIN, COUT)                                                                      \
-  if (KH == K && stride == S && Cin == CIN && Cout == COUT) {                                         \
-    constexpr int lds_ = conv_x3_lds_bytes(K, S, CIN);                                                \
-    if (conv_tile_attr(conv_x3_kernel<K, S, CIN, COUT>, lds_) != RAMP_OK) return RAMP_ELAUNCH;        \
-    hipLaunchKernelGGL((conv_x3_kernel<K, S, CIN, COUT>), tg, block, lds_, st, p);                    \
-    RAMP_CHECK_LAUNCH();                                                                              \
-    return RAMP_OK;                                                                                   \
-  }
-    X3_CASE(3, 1, 32, 32)
-    X3_CASE(3, 1, 64, 64)
-    X3_CASE(3, 1, 32, 64)
-    X3_CASE(3, 2, 32, 64)
-    X3_CASE(3, 1, 64, 32)
-    X3_CASE(7, 2, 16, 32)
-#undef X3_CASE
-    return RAMP_EUNSUPPORTED;
-  }
+  // fp32 in / out at fp32 accuracy on the f16 matrix cores (conv_x3_kernel; wpk = pack_conv_weight mode "x3")
+  if (x3) return conv_x3_dispatch(KH, stride, Cin, Cout, &p, st);
   // fp16: LDS-tiled kernel for the layer shapes of the towers (RAMP_CONV_DIRECT forces the direct one)
   if (f16 && !(dtype & RAMP_CONV_DIRECT)) {
-    const dim3 tg(ramp_cdiv(p.OH, 8) * ramp_cdiv(p.OW, 16), 1);
-#define TILE_CASE(K, S, INF32, CIN, NT)                                                              \
-  if (KH == K && stride == S && in_f32 == INF32 && Cin == CIN && Cout % (NT * 16) == 0) {             \
-    ConvMulti pm;                                                                                     \
-    pm.t[0] = p; pm.t[1] = p;                                                                         \
-    constexpr int lds_ = conv_tile_lds_bytes(K, S, INF32, CIN, NT, false);                            \
-    if (conv_tile_attr(conv_tile_f16_kernel<K, S, INF32, CIN, NT>, lds_) != RAMP_OK) return RAMP_ELAUNCH; \
-    hipLaunchKernelGGL((conv_tile_f16_kernel<K, S, INF32, CIN, NT>), dim3(tg.x, Cout / (NT * 16), 1),  \
-                       block, lds_, st, pm);                                                          \
-    RAMP_CHECK_LAUNCH();                                                                              \
-    return RAMP_OK;                                                                                   \
+    const TileQuery q = {KH, stride, Cin, in_f32, Cout % 64 == 0, false, T_SINGLE};
+    const int rt = conv_tile_dispatch(q, &pm, Cout, 1, st);
+    if (rt != RAMP_EUNSUPPORTED) return rt;
   }
-    TILE_CASE(7, 2, true, 16, 2)
-    TILE_CASE(3, 1, false, 32, 2)
-    TILE_CASE(3, 2, false, 32, 2)
-    TILE_CASE(3, 2, false, 64, 2)
-    TILE_CASE(3, 1, false, 64, 2)
-    TILE_CASE(1, 2, false, 32, 4)
-    TILE_CASE(1, 2, false, 64, 4)
-    TILE_CASE(1, 1, false, 64, 4)
-    TILE_CASE(1, 1, false, 128, 4)
-#undef TILE_CASE
-  }
+  const dim3 grid(ramp_cdiv(p.OH * p.OW, 128), Cout / 32), block(256);
 #define CONV_CASE(K, S)                                                                              \
   if (KH == K && stride == S) {                                                                      \
     if (!f16) hipLaunchKernelGGL((conv_mfma_f32_kernel<K, K, S>), grid, block, 0, st, p);            \
@@ -2034,148 +2045,47 @@ int ramp_conv2d_nhwc_multi(const ramp_conv_job *jobs, int njobs, int H, int W, i
   if (!f16 || (dtype & RAMP_CONV_DIRECT)) return RAMP_EUNSUPPORTED;
   const bool fp8 = (dtype & RAMP_CONV_FP8) != 0;
   if (fp8 && in_f32) return RAMP_EUNSUPPORTED;
-  const int pad = KH / 2;
-  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
-  if (OH <= 0 || OW <= 0) return RAMP_EINVAL;
+  const ConvLayer L = conv_layer(H, W, Cin, KH, stride, in_f32, fp8);
+  if (L.OH <= 0 || L.OW <= 0) return RAMP_EINVAL;
   ConvMulti pm;
-  int cmax = 0, cgcd_ok64 = 1;
+  int cmax = 0;
+  bool all64 = true, block_stats = false, any_skip = false;
   for (int t = 0; t < 2; t++) {
     const ramp_conv_job &j = jobs[t < njobs ? t : 0];
-    if (!j.x || !j.wpk || !j.y || j.Cout <= 0 || j.Cout % 32) return RAMP_EINVAL;
-    ConvParams &p = pm.t[t];
-    p.x = j.x; p.wpk = j.wpk; p.bias = j.bias; p.pre_scale = j.pre_scale; p.pre_shift = j.pre_shift;
-    p.res = j.res; p.y = j.y; p.stats = j.stats;
-    p.x2 = j.x2; p.C0 = j.c0;
-    p.skip = j.skip; p.acc_skip = (const unsigned long long *)j.acc_skip; p.skip_count = j.skip_count; p.skip_eps = j.skip_eps;
-    p.skip_relu = j.skip_relu; p.mat = j.mat;
-    if (p.skip && (in_f32 || !j.acc_in || p.x2 || Cin > 128 || (p.acc_skip && !(p.skip_count > 0.f)) || (p.skip_relu && !p.acc_skip) ||
-                   (p.mat && (stride != 1 || (KH != 1 && KH != 3)))))
-      return RAMP_EINVAL;
-    if (!p.skip && (p.mat || p.acc_skip)) return RAMP_EINVAL;
-    if (p.skip && (fp8 || j.stats)) return RAMP_EUNSUPPORTED;      // (f16 MFMA instances in accumulator mode only)
-    if (p.x2 && (in_f32 || p.C0 <= 0 || p.C0 >= Cin || (p.C0 & 7) || ((Cin - p.C0) & 7) || p.pre_scale || j.acc_in)) return RAMP_EINVAL;
-    p.acc_out = (unsigned long long *)j.acc_out; p.acc_in = (const unsigned long long *)j.acc_in;
-    p.in_count = j.in_count; p.in_eps = j.in_eps;
-    if (p.acc_in && (Cin > 128 || p.in_count <= 0.f)) return RAMP_EINVAL;
-    p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.Cout = j.Cout;
-    p.relu = j.relu; p.out_scale = j.out_scale;
-    p.act_scale = 1.0f; p.descale = 1.0f;
-    if (fp8) {
-      if (!(j.act_scale > 0.0f) || !(j.w_scale > 0.0f)) return RAMP_EINVAL;
-      p.act_scale = j.act_scale; p.descale = 1.0f / (j.act_scale * j.w_scale);
-    }
+    const int rc = conv_params_from_job(L, j, pm.t[t]);
+    if (rc != RAMP_OK) return rc;
     cmax = j.Cout > cmax ? j.Cout : cmax;
-    if (j.Cout % 64) cgcd_ok64 = 0;
+    all64 &= j.Cout % 64 == 0;
+    block_stats |= j.stats != nullptr;
+    any_skip |= j.skip != nullptr;
   }
-  const dim3 block(256);
-  const int tiles = ramp_cdiv(OH, 8) * ramp_cdiv(OW, 16);
   hipStream_t st = (hipStream_t)stream;
   // the first layer of the two towers: one workgroup per tile computes both (shared input, no prologue)
   if (KH == 7 && stride == 2 && in_f32 && Cin == 16 && njobs == 2 && jobs[0].x == jobs[1].x && jobs[0].Cout == 32 &&
       jobs[1].Cout == 32 && !jobs[0].pre_scale && !jobs[1].pre_scale) {
-    hipLaunchKernelGGL(conv7_dual_kernel, dim3(tiles, 1, 1), block, 0, st, pm);
+    hipLaunchKernelGGL(conv7_dual_kernel, dim3(ramp_cdiv(L.OH, 8) * ramp_cdiv(L.OW, 16), 1, 1), dim3(256), 0, st, pm);
     RAMP_CHECK_LAUNCH();
     return RAMP_OK;
   }
-#define TILE_CASE8(K, S, CIN, NT)                                                                    \
-  if (fp8 && KH == K && stride == S && Cin == CIN && (NT == 2 || cgcd_ok64)) {                        \
-    constexpr int lds_ = conv_tile_lds_bytes(K, S, false, CIN, NT, true);                             \
-    if (conv_tile_attr(conv_tile_f16_kernel<K, S, false, CIN, NT, true>, lds_) != RAMP_OK) return RAMP_ELAUNCH; \
-    hipLaunchKernelGGL((conv_tile_f16_kernel<K, S, false, CIN, NT, true>), dim3(tiles, cmax / (NT * 16), njobs), \
-                       block, lds_, st, pm);                                                          \
-    RAMP_CHECK_LAUNCH();                                                                              \
-    return RAMP_OK;                                                                                   \
-  }
-  TILE_CASE8(3, 1, 32, 2)
-  TILE_CASE8(3, 2, 32, 2)
-  TILE_CASE8(3, 2, 64, 2)
-  TILE_CASE8(3, 1, 64, 2)
-  TILE_CASE8(1, 2, 32, 4)
-  TILE_CASE8(1, 2, 64, 4)
-  TILE_CASE8(1, 1, 64, 4)
-  TILE_CASE8(1, 1, 128, 4)
-#undef TILE_CASE8
-  if (fp8) return RAMP_EUNSUPPORTED;
-#define TILE_CASE(K, S, INF32, CIN, NT)                                                              \
-  if (KH == K && stride == S && in_f32 == INF32 && Cin == CIN && (NT == 2 || cgcd_ok64)) {            \
-    constexpr int lds_ = conv_tile_lds_bytes(K, S, INF32, CIN, NT, false);                            \
-    if (conv_tile_attr(conv_tile_f16_kernel<K, S, INF32, CIN, NT>, lds_) != RAMP_OK) return RAMP_ELAUNCH; \
-    hipLaunchKernelGGL((conv_tile_f16_kernel<K, S, INF32, CIN, NT>), dim3(tiles, cmax / (NT * 16), njobs), \
-                       block, lds_, st, pm);                                                          \
-    RAMP_CHECK_LAUNCH();                                                                              \
-    return RAMP_OK;                                                                                   \
-  }
-  TILE_CASE(7, 2, true, 16, 2)
-  // 16 x 16 output tiles for the 32-channel 3x3 layers at half resolution (600 workgroups of two towers, three per CU: still
-  // one round): weight fragments staged once per 256 pixels and a 1.27x instead of 1.41x halo.  Per-block statistics
-  // (`stats`, the path without accumulators) keep the 8 x 16 grid their buffers are sized for.  (8 x 16 tiles: the A/B of round 4)
-  constexpr bool th16 = true;
-  bool block_stats = false, any_skip = false;
-  for (int t = 0; t < njobs; t++) { block_stats |= jobs[t].stats != nullptr; any_skip |= jobs[t].skip != nullptr; }
-  if (any_skip) {                                     // a tower takes a fused residual-block tail: the TAIL instances
-#define TAIL_CASE(K, S, CIN, NT, TH_)                                                               \
-    if (KH == K && stride == S && !in_f32 && Cin == CIN && (NT == 2 || cgcd_ok64)) {                  \
-      constexpr int lds_ = conv_tile_lds_bytes(K, S, false, CIN, NT, false, TH_);                     \
-      if (conv_tile_attr(conv_tile_f16_kernel<K, S, false, CIN, NT, false, TH_, true>, lds_) != RAMP_OK) return RAMP_ELAUNCH; \
-      hipLaunchKernelGGL((conv_tile_f16_kernel<K, S, false, CIN, NT, false, TH_, true>),              \
-                         dim3(ramp_cdiv(OH, TH_) * ramp_cdiv(OW, 16), cmax / (NT * 16), njobs), block, lds_, st, pm); \
-      RAMP_CHECK_LAUNCH();                                                                          \
-      return RAMP_OK;                                                                               \
-    }
-    if (fp8 || block_stats) return RAMP_EUNSUPPORTED;
-    if (th16 && (long)ramp_cdiv(OH, 16) * ramp_cdiv(OW, 16) * njobs * (cmax / 32) >= 512) { TAIL_CASE(3, 1, 32, 2, 16) }
-    TAIL_CASE(3, 1, 32, 2, 8)
-    TAIL_CASE(3, 2, 32, 2, 8)
-    TAIL_CASE(1, 2, 32, 4, 8)
-    TAIL_CASE(3, 1, 64, 2, 8)
-    TAIL_CASE(1, 1, 64, 4, 8)
-#undef TAIL_CASE
-    return RAMP_EUNSUPPORTED;
-  }
-  if (th16 && !block_stats && KH == 3 && stride == 1 && !in_f32 && Cin == 32 &&
-      (long)ramp_cdiv(OH, 16) * ramp_cdiv(OW, 16) * njobs * (cmax / 32) >= 512) {
-    constexpr int lds_ = conv_tile_lds_bytes(3, 1, false, 32, 2, false, 16);
-    if (conv_tile_attr(conv_tile_f16_kernel<3, 1, false, 32, 2, false, 16>, lds_) != RAMP_OK) return RAMP_ELAUNCH;
-    hipLaunchKernelGGL((conv_tile_f16_kernel<3, 1, false, 32, 2, false, 16>),
-                       dim3(ramp_cdiv(OH, 16) * ramp_cdiv(OW, 16), cmax / 32, njobs), block, lds_, st, pm);
-    RAMP_CHECK_LAUNCH();
-    return RAMP_OK;
-  }
-  TILE_CASE(3, 1, false, 32, 2)
-  TILE_CASE(3, 2, false, 32, 2)
-  // (stride 2 at 64 channels, the MultiScale towers' layer3: the 80 KB halo tile leaves one workgroup per CU either way;
-  // with all 64 output channels in it the tile is staged once instead of twice -- round 4's A/B)
-  constexpr bool s2nt4 = true;
-  if (s2nt4) { TILE_CASE(3, 2, false, 64, 4) }
-  TILE_CASE(3, 2, false, 64, 2)
-  TILE_CASE(3, 1, false, 64, 2)
-  TILE_CASE(1, 2, false, 32, 4)
-  TILE_CASE(1, 2, false, 64, 4)
-  TILE_CASE(1, 1, false, 64, 4)
-  TILE_CASE(1, 1, false, 128, 4)
-#undef TILE_CASE
-  return RAMP_EUNSUPPORTED;
+  if (any_skip && block_stats) return RAMP_EUNSUPPORTED;          // (a fused block tail: accumulator mode in every tower)
+  const bool th16 = !block_stats && (long)ramp_cdiv(L.OH, 16) * ramp_cdiv(L.OW, 16) * njobs * (cmax / 32) >= 512;
+  const TileQuery q = {KH, stride, Cin, in_f32, all64, th16, T_PAIRED | (fp8 ? T_FP8 : 0) | (any_skip ? T_TAIL : 0)};
+  return conv_tile_dispatch(q, &pm, cmax, njobs, st);
+}
+
+int ramp_conv2d_tiled(int Cin, int Cout, int KH, int stride, int dtype) {
+  const bool f16 = (dtype & 0xf) == RAMP_F16, in_f32 = f16 && (dtype & RAMP_IN_F32);
+  if (!f16 || (dtype & RAMP_CONV_DIRECT) || Cout % 32) return 0;
+  const TileQuery q = {KH, stride, Cin, in_f32, Cout % 64 == 0, false, T_SINGLE};
+  return conv_tile_dispatch(q, nullptr, 0, 0, nullptr) == RAMP_OK;
 }
 
 int ramp_conv2d_stats_blocks(int H, int W, int Cin, int Cout, int KH, int stride, int dtype) {
-  const int pad = KH / 2;
-  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
-  if (OH <= 0 || OW <= 0) return RAMP_EINVAL;
-  const bool f16 = (dtype & 0xf) == RAMP_F16, in_f32 = f16 && (dtype & RAMP_IN_F32);
-  if (dtype == (RAMP_F32 | RAMP_CONV_X3)) {
-    const bool ok = (KH == 3 && stride == 1 && ((Cin == 32 && (Cout == 32 || Cout == 64)) || (Cin == 64 && (Cout == 64 || Cout == 32)))) ||
-                    (KH == 3 && stride == 2 && Cin == 32 && Cout == 64) || (KH == 7 && stride == 2 && Cin == 16 && Cout == 32);
-    return ok ? ramp_cdiv(OH, 8) * ramp_cdiv(OW, 16) : RAMP_EUNSUPPORTED;
-  }
-  bool tiled = false;
-  if (f16 && !(dtype & RAMP_CONV_DIRECT)) {
-    tiled = (KH == 7 && stride == 2 && in_f32 && Cin == 16 && Cout % 32 == 0) ||
-            (!in_f32 && KH == 3 && stride == 1 && (Cin == 32 || Cin == 64) && Cout % 32 == 0) ||
-            (!in_f32 && KH == 3 && stride == 2 && (Cin == 32 || Cin == 64) && Cout % 32 == 0) ||
-            (!in_f32 && KH == 1 && stride == 2 && (Cin == 32 || Cin == 64) && Cout % 64 == 0) ||
-            (!in_f32 && KH == 1 && stride == 1 && (Cin == 64 || Cin == 128) && Cout % 64 == 0);
-  }
-  return tiled ? ramp_cdiv(OH, 8) * ramp_cdiv(OW, 16) : ramp_cdiv(OH * OW, 128);
+  const ConvLayer L = conv_layer(H, W, Cin, KH, stride, false, false);
+  if (L.OH <= 0 || L.OW <= 0) return RAMP_EINVAL;
+  const int tiles = ramp_cdiv(L.OH, 8) * ramp_cdiv(L.OW, 16);
+  if (dtype == (RAMP_F32 | RAMP_CONV_X3)) return conv_x3_dispatch(KH, stride, Cin, Cout, nullptr, nullptr) == RAMP_OK ? tiles : RAMP_EUNSUPPORTED;
+  return ramp_conv2d_tiled(Cin, Cout, KH, stride, dtype) ? tiles : ramp_cdiv(L.OH * L.OW, 128);
 }
 
 int ramp_in_stats_finalize(const float *partial, int nblk, int C, float count, float eps, float *scale,
@@ -2212,16 +2122,12 @@ int ramp_ms_lstm_superstate_mfma(const float *ev, const float *im, const float *
   hipStream_t st = (hipStream_t)stream;
   if (scale > 1 && (p.Ws % 16)) return RAMP_EUNSUPPORTED;      // (a tile = 16 neighbours of one row)
   if (scale == 1) return ms_mfma_launch<16, 1, 4>(p, st);
-  constexpr int split = 1;                            // (0: a whole tile per wave at scales 2 / 4 -- measured slower)
+  // scales 2 / 4: one tile per workgroup, one wave per 16-unit group (a whole tile per wave measured slower)
   const int ntile = ramp_cdiv(p.Hs * p.Ws, 16);
-  if (split) {
-    if (scale == 2) hipLaunchKernelGGL((ms_lstm_superstate_split_kernel<32, 2>), dim3(ntile), dim3(128), 0, st, p);
-    else hipLaunchKernelGGL((ms_lstm_superstate_split_kernel<64, 4>), dim3(ntile), dim3(256), 0, st, p);
-    RAMP_CHECK_LAUNCH();
-    return RAMP_OK;
-  }
-  if (scale == 2) return ms_mfma_launch<32, 2, 4>(p, st);
-  return ms_mfma_launch<64, 4, 6>(p, st);
+  if (scale == 2) hipLaunchKernelGGL((ms_lstm_superstate_split_kernel<32, 2>), dim3(ntile), dim3(128), 0, st, p);
+  else hipLaunchKernelGGL((ms_lstm_superstate_split_kernel<64, 4>), dim3(ntile), dim3(256), 0, st, p);
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
 }
 
 int ramp_ms_lstm_superstate(const float *ev, const float *im, const float *const *weights_host,

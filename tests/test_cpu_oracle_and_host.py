@@ -32,14 +32,16 @@ def test_library_loads_and_exports_every_declared_symbol():
 
 
 def test_track_descriptor_mirror_matches_the_c_layout(tmp_path):
-    """track_dev.Track / TrackWeights mirror include/ramp_hip.h's ramp_track / ramp_track_weights by hand: the system C
-    compiler's sizeof and offsetof of every field the ctypes mirror names equal the ctypes ones"""
+    """track_dev.Track / TrackWeights and conv_hip.ConvJob mirror include/ramp_hip.h's ramp_track / ramp_track_weights /
+    ramp_conv_job by hand: the system C compiler's sizeof and offsetof of every field the ctypes mirror names equal the
+    ctypes ones, field by field in the mirror's order"""
     import shutil
     import subprocess
-    from rampvo_amd import track_dev
+    from rampvo_amd import conv_hip, track_dev
     cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
     assert cc, "no C compiler on PATH"
-    structs = (("ramp_track", track_dev.Track), ("ramp_track_weights", track_dev.TrackWeights))
+    structs = (("ramp_track", track_dev.Track), ("ramp_track_weights", track_dev.TrackWeights),
+               ("ramp_conv_job", conv_hip.ConvJob))
     lines = ['#include "ramp_hip.h"', "#include <stdio.h>", "int main(void) {"]
     want = []
     for cname, py in structs:
