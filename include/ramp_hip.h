@@ -677,6 +677,26 @@ int ramp_x3_gru(const float *x32, const float *add0_t, const int32_t *add0_idx, 
 #define RAMP_DYN_FRAME2 31  /* = RAMP_DYN_FRAME, in the other half of the block: the two differ in a torn host copy         */
 #define RAMP_TRACK_LOG 12   /* floats per delta-log entry: t1, t0 (as int32 bit patterns), dP[7], pad             */
 
+/* A pose record (ramp_track_publish): 32 words = two 64-byte halves, written to slot `counter % ring_cap` of a ring in pinned
+ * host memory, one record per accepted frame.  The frame tag sits in both halves (as in `dyn`): the first half is stored,
+ * then a system-scope fence, then the second half -- a host copy whose two tags differ is torn.  Integer words are int32,
+ * POSE / INV are float bit patterns, TSTAMP is a double split into its low and high word.                               */
+#define RAMP_POSE_WORDS 32
+#define RAMP_POSE_FRAME 0       /* `counter` of the frame (the record's tag)                                          */
+#define RAMP_POSE_N 1           /* Ramp_vo.n when the frame's update() ran                                            */
+#define RAMP_POSE_E 2           /* live factors behind the frame's graph edit (Ramp_vo.peek()'s E)                    */
+#define RAMP_POSE_STATUS 3      /* the sticky status word (RAMP_DYN_STATUS) as the frame left it                      */
+#define RAMP_POSE_DROPPED 4     /* 1: this frame's keyframe test dropped a keyframe                                   */
+#define RAMP_POSE_T1 5          /* the delta entry that test wrote: the dropped frame ...                             */
+#define RAMP_POSE_T0 6          /* ... and the frame its pose is chained to (both -1 when DROPPED is 0)               */
+#define RAMP_POSE_KF_TSTAMP 7   /* `counter` of the frame whose pose row is published (the newest keyframe)           */
+#define RAMP_POSE_TSTAMP 8      /* [2] the caller's time stamp of the frame (Ramp_vo.tlist), a double: low, high word  */
+#define RAMP_POSE_POSE 16       /* [7] the newest frame's pose as stored: world -> camera (tx ty tz qx qy qz qw)       */
+#define RAMP_POSE_INV 23        /* [7] its inverse, camera -> world: the convention of Ramp_vo.terminate()            */
+#define RAMP_POSE_FRAME2 31     /* = RAMP_POSE_FRAME, in the other half                                               */
+#define RAMP_TRAJ_UNRESOLVED 1  /* ramp_trajectory_resolve's status bit: a frame is neither a keyframe nor reachable
+                                   through the delta logs (its row is the identity)                                      */
+
 #define RAMP_TRACK_COMMIT 1    /* store the front end's outputs as frame NROW first                               */
 #define RAMP_TRACK_UPDATE 2    /* Ramp_vo.update()                                                                */
 #define RAMP_TRACK_KEYFRAME 4  /* Ramp_vo.keyframe() + the next frame's append_factors + its plan                 */
@@ -830,6 +850,36 @@ int ramp_track_plan(const ramp_track *t, int cur, void *stream);
  * launches; a bound below the live count raises status bit 32 instead of truncating silently.                      */
 int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, int E_bound, const float *k_new,
                     void *gate_event, void *stream);
+
+/* ---------------------------------------------------------------- live poses (csrc/publish.hip)
+ *
+ * ramp_track_publish: one wave that writes the pose record of frame `counter` (layout: RAMP_POSE_*) into slot
+ * counter % ring_cap of `ring_dev`, the DEVICE address (ramp_host_device_pointer) of a ring of ring_cap records in pinned
+ * host memory.  Enqueued on the frame's stream BEHIND the frame's ramp_track_step: the keyframe test's outcome is part of
+ * the record, so the launch follows the graph edit and reads the newest pose from the row the edit left it in
+ * (dyn[RAMP_DYN_NROW] - 1) -- the same seven floats bundle adjustment wrote, a row shift only moves them.
+ *   t != NULL : a device-resident frame; n, the row, the factor count, the status word, the test's outcome and its delta
+ *               entry are read from t->dyn / t->dlog, poses and time stamps from t->poses / t->tstamps; the _imm arguments
+ *               are ignored.
+ *   t == NULL : a host-driven frame; the caller passes the same values as immediates (row_imm: the row of `poses` that
+ *               holds the newest frame's pose, 0 <= row_imm < n_rows; t1_imm / t0_imm: -1 without a delta entry).
+ * tstamp: the caller's time stamp of the frame.                                                                        */
+int ramp_track_publish(const ramp_track *t, int64_t counter, double tstamp, float *ring_dev, int ring_cap,
+                       const float *poses, const int64_t *tstamps, int n_rows, int n_imm, int row_imm, int E_imm,
+                       int status_imm, int dropped_imm, int t1_imm, int t0_imm, void *stream);
+
+/* ramp_trajectory_resolve: what Ramp_vo.terminate() computes (ramp/Ramp_vo.py:113-133), as one launch of one workgroup.
+ * out[t] for t in [0, T): inv(kf_poses[i]) where kf_tstamps[i] == t for a keyframe i < n; otherwise
+ * inv(dP_t * (dP_t0 * ( ... * kf_pose))) along the delta chain (t -> t0 -> ...), entries taken from extra_log [n_extra]
+ * and dlog [nlog], both in the RAMP_TRACK_LOG layout (a frame found in both: the dlog entry; a frame that is a keyframe
+ * and has an entry: the keyframe).  Products are formed innermost first, in rounds of increasing chain depth, with the
+ * device functions of ramp_se3_mul / ramp_se3_inv: the rows equal the host recursion's bit for bit.
+ * dyn != NULL: n = dyn[RAMP_DYN_NROW] and nlog = dyn[RAMP_DYN_NLOG] (a device-resident tracker; the arguments n / nlog are
+ * then the CAPACITIES of kf_poses and dlog, the device values are clamped to them).  ws: int32 [3 * T] scratch.
+ * *status (device int32, written by the launch): 0, or RAMP_TRAJ_UNRESOLVED.                                          */
+int ramp_trajectory_resolve(const float *kf_poses, const int64_t *kf_tstamps, int n, const int32_t *dyn, const float *dlog,
+                            int nlog, const float *extra_log, int n_extra, int T, float *out, int32_t *ws, int32_t *status,
+                            void *stream);
 
 #ifdef __cplusplus
 }

@@ -95,6 +95,10 @@ class Ramp_vo:
         weakref.finalize(self, _live_dec, idx)
 
         self._dev = None                # DeviceTrack while the steady state is device resident
+        self._pose_ring = None          # track_dev.PoseRing once pose_stream() has switched publishing on
+        self._pose_rings_retired = []   # (launches already queued may still write to a ring that was replaced)
+        self._traj_extra = (None, None) # trajectory(): the host's delta entries on the device, re-uploaded when they have grown
+        self._traj_status = None
         self.lmbda = torch.as_tensor([1e-4], device=dev)
         self.load_weights(network)
         self.is_initialized = False
@@ -452,6 +456,90 @@ class Ramp_vo:
         poses = lietorch.stack(poses, dim=0)
         poses = poses.inv().data.cpu().numpy()
         return poses, np.array(self.tlist, dtype=float)
+
+    # ---------------------------------------------------------------- live poses
+    def pose_stream(self, capacity=256):
+        """switch pose publishing on: from the next accepted frame on, every frame -- device resident or host driven --
+        enqueues ONE extra one-wave launch behind its own work that writes a 128-byte record (frame, time stamp, the newest
+        frame's pose and its inverse, sizes, the keyframe test's outcome: track_dev.PoseRecord) into a ring of `capacity`
+        records in pinned host memory.  latest_pose() / poses_since() read the ring with plain loads: no hand-back, no
+        synchronisation, no HIP call.  A frame rejected by its mask publishes nothing.  Returns the ring."""
+        if self._pose_ring is not None:
+            if self._pose_ring.capacity == int(capacity):
+                return self._pose_ring
+            self._pose_rings_retired.append(self._pose_ring)
+        with torch.cuda.device(self.device):
+            self._pose_ring = track_dev.PoseRing(capacity, first=self.counter)
+        return self._pose_ring
+
+    def latest_pose(self):
+        """the newest complete record (track_dev.PoseRecord) or None -- never waits: what the GPU has finished, which may
+        be a few frames behind the last call"""
+        return self._pose_ring.latest() if self._pose_ring is not None else None
+
+    def poses_since(self, frame):
+        """(the complete records of frames above `frame`, in order; how many of those were overwritten before this read --
+        the ring holds the last `capacity` frames)"""
+        return self._pose_ring.since(frame) if self._pose_ring is not None else ([], 0)
+
+    def _publish(self, tstamp, counter, dv=None, n=None, dropped=False, t1=-1, t0=-1):
+        """(behind a frame's work) the record of frame `counter`; dv: the frame ran device resident -- everything is read on
+        the device; else n = the keyframe count the frame's update() saw (default: the current one)"""
+        ring = self._pose_ring
+        if dv is not None:
+            ring.publish(dv.t, counter, tstamp)
+        else:
+            ring.publish(None, counter, tstamp, poses=self.poses_, tstamps=self.tstamps_, n_rows=self.N,
+                         n=self._n if n is None else n, row=max(self._n - 1, 0), E=len(self._hii),
+                         status=self._ba_flags & 3, dropped=dropped, t1=t1, t0=t0)
+
+    def trajectory(self, as_tensor=False):
+        """what terminate() would return now -- (inverse poses [T,7], tstamps) -- as ONE launch (csrc/publish.hip::
+        traj_resolve_kernel) over the keyframe rows and the delta log where they are: a device-resident state stays device
+        resident (no settle(), the next frame is still one C call), a host-driven one works the same.  as_tensor=True:
+        the poses as a device tensor, ordered on the current stream, nothing synchronised (its status word, bit 1 = a
+        frame that neither is a keyframe nor has a delta entry, is left in ``_traj_status`` unread); otherwise numpy, which
+        waits for that one launch.  Does not set ``traj``."""
+        dv = self._dev
+        resident = dv is not None and dv.active
+        T, dev = int(self.counter), self.device
+        tst = np.array(self.tlist, dtype=float)
+        with torch.no_grad():
+            own = getattr(self, "_main_used", False)          # (inputs_ready = "stream": the state is the tracker's own stream's)
+            cur = torch.cuda.current_stream(dev)
+            st = self._main_stream if own else cur
+            with torch.cuda.stream(st):
+                key, extra = self._traj_extra
+                ne = len(self._delta)
+                if key != (id(self._delta), ne):
+                    head = np.zeros((max(ne, 1), track_dev.LOG_WORDS), np.int32)
+                    head[:ne, 0] = list(self._delta.keys())
+                    head[:ne, 1] = [v[0] for v in self._delta.values()]
+                    extra = self._upload(head).view(torch.float32)
+                    if ne:
+                        extra[:ne, 2:9] = torch.stack([v[1].data.reshape(7) for v in self._delta.values()]).to(torch.float32)
+                    self._traj_extra = ((id(self._delta), ne), extra)
+                out = torch.empty((T, 7), dtype=torch.float32, device=dev)
+                ws = torch.empty(3 * max(T, 1), dtype=torch.int32, device=dev)
+                status = torch.zeros(1, dtype=torch.int32, device=dev)
+                _lib.check(_lib.lib().ramp_trajectory_resolve(
+                    _lib.ptr(self.poses_), _lib.ptr(self.tstamps_), self.N if resident else self._n,
+                    _lib.ptr(dv.dyn) if resident else None, _lib.ptr(dv.dlog) if resident else None,
+                    dv.log_cap if resident else 0, _lib.ptr(extra), ne, T, _lib.ptr(out), _lib.ptr(ws), _lib.ptr(status),
+                    _lib.stream()), "ramp_trajectory_resolve")
+            if own:
+                ev = torch.cuda.Event()
+                ev.record(st)
+                cur.wait_event(ev)
+                for x in (out, ws, status, extra):
+                    x.record_stream(cur)
+        self._traj_status = status
+        if as_tensor:
+            return out, tst
+        poses = out.cpu().numpy()
+        if int(status.cpu()) & track_dev.TRAJ_UNRESOLVED:
+            raise RuntimeError("trajectory(): a frame is neither a keyframe nor reachable through the delta chain")
+        return poses, tst
 
     # ------------------------------------------------------------------ kernels
     def corr(self, coords, indicies=None, order=None):
@@ -965,6 +1053,8 @@ class Ramp_vo:
                 self._ev_gate.record(cur)                        # the next frame's front end may start (next to BA)
             dv.step(self.counter, track_dev.UPDATE_POST | track_dev.KEYFRAME, E_bound=E)
             self._gate_armed, self._gate_by_flag = self.inputs_ready, False
+            if self._pose_ring is not None:
+                self._publish(tstamp, self.counter, dv)
             self.counter += 1
             return
         sig = self._gate_signal() if self.inputs_ready else None
@@ -975,6 +1065,8 @@ class Ramp_vo:
                 gate_event=self._ev_gate.cuda_event if (self.inputs_ready and sig is None) else None,
                 gate_flag=sig.ptr if sig is not None else None, gate_seq=self._gate_seq)
         self._gate_armed, self._gate_by_flag = self.inputs_ready, sig is not None
+        if self._pose_ring is not None:
+            self._publish(tstamp, self.counter, dv)  # (behind the step: the record carries the keyframe test's outcome)
         self.counter += 1
 
     def _device_operator_fp32(self, dv, Eb):
@@ -1084,6 +1176,8 @@ class Ramp_vo:
         if n > 0 and not self.is_initialized:
             if self.motion_probe() < 2.0:
                 self.delta[self.counter - 1] = (self.counter - 2, SE3.Identity(1, device=self.device)[0])
+                if self._pose_ring is not None:      # (not kept: the newest pose is still the previous keyframe's)
+                    self._publish(tstamp, self.counter - 1)
                 return
 
         self.n += 1
@@ -1098,8 +1192,20 @@ class Ramp_vo:
                 self.update()
         elif self.is_initialized:
             self.update()
-            self.keyframe()
+            if self._pose_ring is not None:
+                # this frame's record: n as update() saw it, the keyframe test's outcome, the newest pose behind the row shift
+                n_upd, k = self._n, self._n - self.cfg.KEYFRAME_INDEX
+                t1, t0 = self._tstamps[k], self._tstamps[k - 1]
+                self.keyframe()
+                dropped = self._n < n_upd
+                self._publish(tstamp, self.counter - 1, n=n_upd, dropped=dropped, t1=t1 if dropped else -1,
+                              t0=t0 if dropped else -1)
+            else:
+                self.keyframe()
             self._enter_device()
+            return
+        if self._pose_ring is not None:               # (the window is still filling: no keyframe test)
+            self._publish(tstamp, self.counter - 1)
 
     # -------------------------------------------------------- pose prediction
     def _virtual_frame(self, last_keyframe_number):

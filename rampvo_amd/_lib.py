@@ -154,6 +154,9 @@ SIGNATURES = {
     "ramp_stream_signal": (c_i, [c_p, c_p, ctypes.c_uint32]),
     "ramp_stream_wait_flag": (c_i, [c_p, c_p, ctypes.c_uint32, c_i, c_i, c_p]),
     "ramp_host_device_pointer": (c_i, [c_p, c_p]),
+    # live poses (csrc/publish.hip); the record layout is mirrored in track_dev.py
+    "ramp_track_publish": (c_i, [c_p, c_i64, ctypes.c_double, c_p, c_i, c_p, c_p] + [c_i] * 8 + [c_p]),
+    "ramp_trajectory_resolve": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

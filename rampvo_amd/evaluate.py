@@ -40,19 +40,33 @@ class Trajectory:
 
 
 @torch.no_grad()
-def run(cfg_VO, network, eval_cfg, data_list, ht=480, wd=640, device="cuda", inputs_ready="stream"):
+def run(cfg_VO, network, eval_cfg, data_list, ht=480, wd=640, device="cuda", inputs_ready="stream", on_pose=None):
     """reference evaluate.py:232-260 (without the dataset-specific resize): returns poses, tstamps, points, colors.
     The loop hands the tracker tensors that were produced on the current stream right before the call, as the
     reference's loop does; ``inputs_ready = "stream"`` lets the frames pipeline anyway (Ramp_vo.__init__: the tracker
     orders its front end behind the caller's stream with an event and runs on its own stream; results are identical).
-    ``inputs_ready=False``: everything on the caller's stream, frame after frame."""
+    ``inputs_ready=False``: everything on the caller's stream, frame after frame.
+    ``on_pose``: optional callback, called with every frame's pose record (track_dev.PoseRecord) as the loop goes --
+    whatever the GPU has finished by then, never waited for (Ramp_vo.pose_stream); the records still in flight when the
+    loop ends are delivered behind the closing updates.  None (default): the call sequence is the reference's."""
     train_cfg = eval_cfg["data_loader"]["train"]["args"]
     slam = Ramp_vo(cfg=cfg_VO, network=network, train_cfg=train_cfg, ht=ht, wd=wd, device=device)
     slam.inputs_ready = inputs_ready
+    seen = -1
+    if on_pose is not None:
+        slam.pose_stream()
     for t, (image, events, intrinsics, mask) in enumerate(data_list):
         slam(t, input_tensor=(events, image, mask), intrinsics=intrinsics)
+        if on_pose is not None:
+            for rec in slam.poses_since(seen)[0]:
+                on_pose(rec)
+                seen = rec.frame
     for _ in range(12):
         slam.update()
+    if on_pose is not None:
+        torch.cuda.current_stream().synchronize()
+        for rec in slam.poses_since(seen)[0]:
+            on_pose(rec)
     points = slam.points_.cpu().numpy()[:slam.m]
     colors = slam.colors_.view(-1, 3).cpu().numpy()[:slam.m]
     poses, tstamps = slam.terminate()

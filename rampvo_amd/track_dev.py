@@ -23,6 +23,11 @@ LOG_WORDS = 12
 MAX_AHEAD = 6            # frames the host may enqueue ahead of the newest lazy copy of the sizes (Ramp_vo._track_device)
 COMMIT, UPDATE, KEYFRAME, MM_GIVEN, WRAP_COORDS, COMPACT_COORDS, UPDATE_PRE, UPDATE_POST = 1, 2, 4, 8, 16, 32, 64, 128
 CORR_ROW = 896
+# a pose record (include/ramp_hip.h RAMP_POSE_*): 32 words, the frame tag in both 64-byte halves
+POSE_WORDS = 32
+(POSE_FRAME, POSE_N, POSE_E, POSE_STATUS, POSE_DROPPED, POSE_T1, POSE_T0, POSE_KF_TSTAMP, POSE_TSTAMP) = range(9)
+POSE_POSE, POSE_INV, POSE_FRAME2 = 16, 23, 31
+TRAJ_UNRESOLVED = 1
 
 
 def _ptr_fields(names):
@@ -85,6 +90,99 @@ class Signal:
                 _lib.lib().ramp_signal_free(self.ptr)
         except Exception:
             pass
+
+
+PoseRecord = collections.namedtuple("PoseRecord", "frame tstamp pose pose_inv n factors status dropped delta kf_frame")
+PoseRecord.__doc__ = """one frame's published pose: frame (the tracker's counter), tstamp (the caller's), pose (world -> camera as stored,
+numpy [7] tx ty tz qx qy qz qw), pose_inv (camera -> world: terminate()'s convention), n (keyframes when the frame's update
+ran), factors, status (sticky bits of the device step), dropped (this frame's keyframe test dropped a keyframe), delta ((t1,
+t0) of the entry that test wrote, or None), kf_frame (counter of the frame whose pose row this is)"""
+
+
+def pose_read_slot(ring, s):
+    """the record in slot s of ring (int32 [capacity, POSE_WORDS], possibly being written by the GPU), or None while the slot
+    is empty or its two tags differ (a torn copy).  The second tag is read first and the first tag last, around the copy: the
+    device stores the first half, then the second"""
+    for _ in range(2):                            # (a torn copy is re-read once)
+        t2 = int(ring[s, POSE_FRAME2])
+        c = ring[s].copy()
+        t1 = int(ring[s, POSE_FRAME])
+        if t1 == t2 == int(c[POSE_FRAME]) == int(c[POSE_FRAME2]):
+            break
+    else:
+        return None
+    if t1 < 0:
+        return None
+    f = c.view(np.float32)
+    delta = (int(c[POSE_T1]), int(c[POSE_T0])) if c[POSE_DROPPED] and c[POSE_T1] >= 0 else None
+    return PoseRecord(frame=t1, tstamp=float(c[POSE_TSTAMP:POSE_TSTAMP + 2].view(np.float64)[0]),
+                      pose=f[POSE_POSE:POSE_POSE + 7].copy(), pose_inv=f[POSE_INV:POSE_INV + 7].copy(), n=int(c[POSE_N]),
+                      factors=int(c[POSE_E]), status=int(c[POSE_STATUS]), dropped=bool(c[POSE_DROPPED]), delta=delta,
+                      kf_frame=int(c[POSE_KF_TSTAMP]))
+
+
+def pose_records(ring):
+    """every complete record in the ring, ordered by frame tag"""
+    recs = [r for r in (pose_read_slot(ring, s) for s in range(ring.shape[0])) if r is not None]
+    recs.sort(key=lambda r: r.frame)
+    return recs
+
+
+def pose_latest(ring, hint=None):
+    """the complete record with the highest tag, or None.  hint: the tag the newest record may carry (the last frame
+    enqueued): the slots are then tried from that one backwards and the first complete record whose tag is no older than
+    the ring is long wins -- a torn or not yet written slot falls back to the one before it"""
+    cap = ring.shape[0]
+    if hint is not None and hint >= 0:
+        for back in range(min(cap, hint + 1)):
+            r = pose_read_slot(ring, (hint - back) % cap)
+            if r is not None and r.frame == hint - back:
+                return r
+    recs = pose_records(ring)
+    return recs[-1] if recs else None
+
+
+def pose_since(ring, frame, first=0):
+    """(records with a tag above `frame`, in order; how many such frames were published but overwritten before this read).
+    first: the tag of the first frame ever published to this ring (tags are consecutive from there)"""
+    recs = [r for r in pose_records(ring) if r.frame > frame]
+    if not recs:
+        return [], 0
+    lo = max(int(frame) + 1, int(first))
+    return recs, max(recs[-1].frame - lo + 1 - len(recs), 0)
+
+
+class PoseRing:
+    """`capacity` pose records in pinned host memory; the device writes slot counter % capacity (csrc/publish.hip), the
+    host reads with plain loads -- no HIP call, no wait"""
+
+    def __init__(self, capacity, first=0):
+        if int(capacity) < 1:
+            raise ValueError("pose_stream: capacity must be at least 1")
+        self.capacity, self.first = int(capacity), int(first)
+        self.buf = torch.full((self.capacity, POSE_WORDS), -1, dtype=torch.int32).pin_memory()
+        self.np = self.buf.numpy()
+        dp = ctypes.c_void_p()
+        _lib.check(_lib.lib().ramp_host_device_pointer(ctypes.c_void_p(self.buf.data_ptr()), ctypes.byref(dp)),
+                   "ramp_host_device_pointer")
+        self.dev = dp                              # (resolved once, not per frame)
+        self.last = -1                             # the newest tag enqueued
+
+    def publish(self, track, counter, tstamp, poses=None, tstamps=None, n_rows=0, n=0, row=0, E=0, status=0, dropped=0,
+                t1=-1, t0=-1):
+        """enqueue the record of frame `counter` on the current stream; track: the ramp_track descriptor of a device-resident
+        frame (everything is read on the device), or None with the host-driven frame's values"""
+        _lib.check(_lib.lib().ramp_track_publish(ctypes.byref(track) if track is not None else None, int(counter),
+                                                 float(tstamp), self.dev, self.capacity, _lib.ptr(poses), _lib.ptr(tstamps),
+                                                 int(n_rows), int(n), int(row), int(E), int(status), int(dropped), int(t1),
+                                                 int(t0), _lib.stream()), "ramp_track_publish")
+        self.last = int(counter)
+
+    def latest(self):
+        return pose_latest(self.np, self.last)
+
+    def since(self, frame):
+        return pose_since(self.np, frame, self.first)
 
 
 def supported(slam):
