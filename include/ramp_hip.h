@@ -312,6 +312,41 @@ int ramp_ba_forward_planned(float *poses, float *patches, const float *intrinsic
                             const int32_t *ngroups_p, int max_pairs, void *ws, size_t ws_bytes,
                             int32_t *info, void *stream);
 
+/* Uncertainty of the window: the marginal covariance of the free poses and the marginal variance of every patch depth, from
+ * the system ramp_ba_forward builds in ONE iteration, linearised at the state passed in.  No step is taken: poses and
+ * patches are only read.  With the per-factor terms, the validity gate and the fixed poses exactly as in ramp_ba_forward,
+ *   Q = 1 / (C + lambda),  S = B - E Q E',  S_dd += 1e-4 S_dd + 1   (the solver's own diagonal damping: the covariance is
+ *                                                                   that of the system the step is actually solved with)
+ *   cov [6N][6N]        = S^-1, N = t1 - t0, symmetric bit for bit, both triangles written.  Tangent order as the step's:
+ *                         translation 3, rotation 3 per pose; the perturbation is the left one of the retraction
+ *                         T <- Exp(xi) T on the world-to-camera poses
+ *   depth_var [n_patches]: entry kk = Q_k + Q_k^2 |L^-1 e_k|^2 (S = L L'; never below Q_k) for every patch with at least
+ *                         one factor; the other entries are left as the caller filled them
+ *   stats [8] words     : [0] chi2 = sum over valid factors of w0 rx^2 + w1 ry^2 (float, summed in a fixed order), then as
+ *                         int32 bit patterns [1] valid factors, [2] Mu (patches with a factor), [3] N, [4] t0,
+ *                         [5] 1 when the factorisation failed; [6], [7] zero
+ * t1 == t0 (no free pose): cov is not touched, depth_var = Q_k.  E >= 1.
+ *   info: optional device int, zeroed by the call; bit 0 = the factorisation hit a non-positive pivot or the inverse is not
+ *         finite: cov and the depth_var entries the call writes are then NaN (never a plausible number); bit 1 as
+ *         ramp_ba_forward.  The return value stays RAMP_OK: it is an arithmetic outcome.
+ * Deterministic: ordered sums and fma chains only, the same bits from call to call.                                    */
+size_t ramp_ba_covariance_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1);
+int ramp_ba_covariance(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                       const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
+                       const int64_t *kk, int E, int P, int n_poses, int n_patches, int t0, int t1, float *cov,
+                       float *depth_var, float *stats, void *ws, size_t ws_bytes, int32_t *info, void *stream);
+
+/* ramp_ba_covariance with the caller's two edge groupings, as ramp_ba_forward_planned takes them                  */
+size_t ramp_ba_covariance_planned_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1, int max_patches,
+                                                  int max_pairs);
+int ramp_ba_covariance_planned(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                               const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
+                               const int64_t *kk, int E, int P, int n_poses, int n_patches, int t0, int t1,
+                               float *cov, float *depth_var, float *stats, const int32_t *order_k,
+                               const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
+                               const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs,
+                               void *ws, size_t ws_bytes, int32_t *info, void *stream);
+
 /* group-by for a SMALL key range known to the caller: key = a[e]*mul + (b ? b[e] : 0) - sub must lie
  * in [0, K).  Histogram + one-workgroup scan + scatter + per-segment rank sort (5 short kernels vs a
  * radix sort); same outputs and the same (stable) ordering as ramp_group_by.  ukeys = key + sub.  */
@@ -850,6 +885,20 @@ int ramp_track_plan(const ramp_track *t, int cur, void *stream);
  * launches; a bound below the live count raises status bit 32 instead of truncating silently.                      */
 int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, int E_bound, const float *k_new,
                     void *gate_event, void *stream);
+
+/* ramp_ba_covariance for a device-resident tracker BETWEEN two frames, as one call that never reads the device: the window
+ * [max(n - opt_window, 1), n) with n = dyn[RAMP_DYN_NROW] keyframes, the factors the last graph edit kept (the first
+ * dyn[RAMP_DYN_EKEPT] of graph[cur]; the next frame's factors behind them point at a frame that is not stored yet and take
+ * no part), the last update's t->target / t->weight read through the kept factors' hidden-state rows (their index in the
+ * graph that update ran on), at the poses and patches as they are now.  The kept factors are grouped for this call (the
+ * tracker's plan covers the next frame's factors too) into `ws`, with t->plan_ws as scratch; the system is built in
+ * t->ba_ws.  Nothing of the tracker's state is written: not dyn, not its status word, not the plan.
+ *   cov [6 opt_window][6 opt_window] (the leading 6N x 6N block is the window's; a shorter window leaves identity blocks
+ *   behind it), depth_var [n_rows * M] (entries without a kept factor untouched), stats [8] as ramp_ba_covariance: N and
+ *   t0 are read from there.  cur: the half of graph[] that holds the current graph (as ramp_track_step's next call).     */
+size_t ramp_track_uncertainty_workspace_bytes(const ramp_track *t);
+int ramp_track_uncertainty(const ramp_track *t, int cur, float *cov, float *depth_var, float *stats, void *ws,
+                           size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------- live poses (csrc/publish.hip)
  *

@@ -349,6 +349,7 @@ class Ramp_vo:
         self._last_K_row = self._n - 1           # every committed frame copied (or wrote) its intrinsics row
         if self._dev._frames:                    # the last update()'s confidence weights (reference :296; the host-driven
             self.last_weight = st["weight"][None]    # update() sets it; the pose-prediction mode reads it)
+            self.last_target = st["target"][None]    # (uncertainty() after a hand-back)
         self._note_ba_flags(st["status"] & 3)
         if st["status"] & ~3:
             raise RuntimeError("device-resident tracker: status bits %d (4 = factor list full, 8 = group-by key / group "
@@ -540,6 +541,65 @@ class Ramp_vo:
         if int(status.cpu()) & track_dev.TRAJ_UNRESOLVED:
             raise RuntimeError("trajectory(): a frame is neither a keyframe nor reachable through the delta chain")
         return poses, tst
+
+    # --------------------------------------------------------------- uncertainty
+    def uncertainty(self):
+        """How good the window's poses and depths are right now: the marginal covariance of the free poses and the marginal
+        variance of every patch depth (``fastba.covariance``: the damped system the step is solved with), from the LAST
+        update's targets and confidence weights at the poses and patches as they are now, over the factors that survived
+        the keyframe test -- the state between two frames.  Returns a dict:
+
+        ``frames`` (t0 .. t1-1: the keyframe rows the blocks of ``cov`` belong to), ``cov`` [6N, 6N], ``pose_cov`` [N, 6, 6]
+        (its diagonal blocks; translation 3, rotation 3, left perturbation of the world-to-camera pose), ``depth_var`` [n, M]
+        (inf for a patch without a factor), ``chi2``, ``n_valid``, ``dof = 2 n_valid - 6N - Mu``, ``sigma0_sq = chi2 /
+        max(dof, 1)``.  Tensors are on the device.
+
+        A device-resident state stays device resident: ONE C call (csrc/track.hip::ramp_track_uncertainty) that reads the
+        sizes on the device, no settle(), no hand-back; the host synchronises only to read the result.  Nothing of the
+        tracker's state is written, so a queried tracker tracks the same bits as one that is never asked."""
+        dv = self._dev
+        resident = dv is not None and dv.active
+        dev = self.device
+        last_t, last_w = getattr(self, "last_target", None), getattr(self, "last_weight", None)
+        if (last_t is None or last_w is None) and not (resident and dv._frames):
+            raise RuntimeError("uncertainty(): no update has run yet -- there are no targets and weights to form the "
+                               "system from (track at least until the first update())")
+        W = int(self.cfg.OPTIMIZATION_WINDOW)
+        with torch.no_grad():
+            own = getattr(self, "_main_used", False)          # (inputs_ready = "stream": the state is the tracker's own stream's)
+            cur = torch.cuda.current_stream(dev)
+            st = self._main_stream if own else cur
+            with torch.cuda.stream(st):
+                if resident:
+                    if not dv._frames:                        # (handed over, no device step yet: the last update ran host-driven)
+                        k = last_t.shape[1]
+                        dv.target[:k].copy_(last_t[0])
+                        dv.weight[:k].copy_(last_w[0])
+                    cov_c, dvar_c, raw = dv.uncertainty()
+                else:
+                    self._join_main()
+                    n = self._n
+                    rows = self._net_map_dev if self._net_map_dev is not None else self._upload(self._net_rows())
+                    if rows.numel() != self._dii.numel() or rows.numel() == 0:
+                        raise RuntimeError("uncertainty(): the factor graph has changed since the last update()")
+                    t0 = max(n - W, 1) if self.is_initialized else 1
+                    cov_c, dvar_c, raw = ops.ba_covariance(self.poses_, self.patches_, self.intrinsics_, last_t[0][rows],
+                                                           last_w[0][rows], self.lmbda, self._dii, self._djj, self._dkk,
+                                                           t0, n)
+            if own:
+                ev = torch.cuda.Event()
+                ev.record(st)
+                cur.wait_event(ev)
+                for x in (cov_c, dvar_c, raw):
+                    x.record_stream(cur)
+        s = ops.ba_covariance_stats(raw)                      # (the one synchronisation: 32 bytes)
+        N, t0 = s["N"], s["t0"]
+        n = t0 + N
+        cov = cov_c[:6 * N, :6 * N]
+        pose_cov = torch.stack([cov[6 * a:6 * a + 6, 6 * a:6 * a + 6] for a in range(N)]) if N else cov.new_zeros((0, 6, 6))
+        dof = 2 * s["n_valid"] - 6 * N - s["Mu"]
+        return dict(frames=list(range(t0, n)), cov=cov, pose_cov=pose_cov, depth_var=dvar_c[:n * self.M].view(n, self.M),
+                    chi2=s["chi2"], n_valid=s["n_valid"], dof=dof, sigma0_sq=s["chi2"] / max(dof, 1), failed=s["failed"])
 
     # ------------------------------------------------------------------ kernels
     def corr(self, coords, indicies=None, order=None):
@@ -786,6 +846,7 @@ class Ramp_vo:
             else:
                 target, weight, _ = fu.target_weight(fu.heads(relu_t), coords[0], self.wd // 4, self.ht // 4)
             self.last_weight = weight
+            self.last_target = target
         with Timer("BA", enabled=self.enable_timing):
             t0 = self.n - self.cfg.OPTIMIZATION_WINDOW if self.is_initialized else 1
             t0 = max(t0, 1)

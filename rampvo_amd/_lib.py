@@ -96,6 +96,11 @@ SIGNATURES = {
     "ramp_ba_forward": (c_i, [c_p] * 9 + [c_i] * 7 + [c_p, c_sz, c_p, c_p]),
     "ramp_ba_planned_workspace_bytes": (c_sz, [c_i] * 7),
     "ramp_ba_forward_planned": (c_i, [c_p] * 9 + [c_i] * 7 + [c_p] * 4 + [c_i] + [c_p] * 3 + [c_i, c_p, c_sz, c_p, c_p]),
+    "ramp_ba_covariance_workspace_bytes": (c_sz, [c_i] * 5),
+    "ramp_ba_covariance": (c_i, [c_p] * 9 + [c_i] * 6 + [c_p] * 3 + [c_p, c_sz, c_p, c_p]),
+    "ramp_ba_covariance_planned_workspace_bytes": (c_sz, [c_i] * 7),
+    "ramp_ba_covariance_planned": (c_i, [c_p] * 9 + [c_i] * 6 + [c_p] * 3 + [c_p] * 4 + [c_i] + [c_p] * 3
+                                   + [c_i, c_p, c_sz, c_p, c_p]),
     "ramp_group_by_small_workspace_bytes": (c_sz, [c_i, c_i]),
     "ramp_group_by_small": (c_i, [c_p, c_p, c_i64, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "ramp_neighbors_from_groups": (c_i, [c_p] * 7 + [c_i, c_i, c_p]),
@@ -156,6 +161,8 @@ SIGNATURES = {
     "ramp_host_device_pointer": (c_i, [c_p, c_p]),
     # live poses (csrc/publish.hip); the record layout is mirrored in track_dev.py
     "ramp_track_publish": (c_i, [c_p, c_i64, ctypes.c_double, c_p, c_i, c_p, c_p] + [c_i] * 8 + [c_p]),
+    "ramp_track_uncertainty_workspace_bytes": (c_sz, [c_p]),
+    "ramp_track_uncertainty": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
     "ramp_trajectory_resolve": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
 }
 

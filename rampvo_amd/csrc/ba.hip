@@ -15,6 +15,12 @@
 //   K6     single-workgroup LDS Cholesky + triangular solves -> dX
 //   K7     dZ = Q (u - E dX), depth retraction, SE3 pose retraction
 //
+// ramp_ba_covariance (the window's uncertainty) runs K2 .. K5 once at the state passed in, then
+//   C1     single-workgroup LDS Cholesky + in-place triangular inverse -> L^-1
+//   C2     cov = L^-T L^-1 (tiles), depth_var = Q + Q^2 |L^-1 e_k|^2 and the chi2 partials (one wave per patch)
+//   C3     chi2 / valid count from the partials, in group order
+// and never K7: poses and patches are only read.
+//
 // Math restates ramp/fastba/ba_cuda.cu:232-376 (kernel), 433-582 (host loop),
 // 178-229 (retractions).  Everything is fp32 like the reference (mtype=float).
 #include "ramp_device.h"
@@ -38,7 +44,8 @@ struct BaEdgeIn {
   const int64_t *ii, *jj, *kk;
   int PP, c11, t0, N;
 };
-__device__ __forceinline__ void ba_edge_compute(const BaEdgeIn &in, int n, float (&r)[BA_REC]) {
+// (gate: the validity mask on its own, 1 / 0 -- the record only carries it multiplied into the weights)
+__device__ __forceinline__ void ba_edge_compute_gate(const BaEdgeIn &in, int n, float (&r)[BA_REC], float &gate) {
   const float fx = in.intr[0], fy = in.intr[1], cx = in.intr[2], cy = in.intr[3];
   int ix = (int)in.ii[n], jx = (int)in.jj[n];
   const long kx = in.kk[n];
@@ -84,6 +91,11 @@ __device__ __forceinline__ void ba_edge_compute(const BaEdgeIn &in, int n, float
   r[25] = mask * in.weight[2 * (size_t)n + 1];
   r[26] = rx; r[27] = ry; r[28] = Jz0; r[29] = Jz1;
   r[30] = __int_as_float(ix); r[31] = __int_as_float(jx);
+  gate = mask;
+}
+__device__ __forceinline__ void ba_edge_compute(const BaEdgeIn &in, int n, float (&r)[BA_REC]) {
+  float gate;
+  ba_edge_compute_gate(in, n, r, gate);
 }
 // window from the device-side sizes (csrc/track.hip): [max(n - opt_window, 1), n)
 __device__ __forceinline__ void ba_dyn_window(const int32_t *dyn, int opt_window, int &t0, int &N) {
@@ -900,6 +912,280 @@ __global__ void __launch_bounds__(256)
   if (lane < PP) pt[lane] = dd;
 }
 
+// ------------------------------------------------------------------ uncertainty of the window (ramp_ba_covariance)
+// cov = S^-1 and depth_var_k = Q_k + Q_k^2 |L^-1 e_k|^2 from the system K1 .. K5 assemble (S = L L', damping included: the
+// system the step is solved with).  Two kernels of their own:
+//   C1  one workgroup: S in LDS (ld = n6 + 1), the blocked 6-wide Cholesky of K6 (restated without the right-hand side:
+//       ba_cholb_kernel is untouched), then L^-1 IN PLACE, block row by block row from the top: row block I of L^-1 is
+//       -L_II^-1 (L_I,<I  X_<I) with X_<I the rows already inverted above it -- one thread per column keeps the six sums in
+//       registers (the L row block is read as LDS broadcasts, the X column walk is conflict-free with the odd ld), a barrier,
+//       then the rows are overwritten.  n6 (n6 + 1) + 28 n6 / 6 floats: 148 KB at n6 = 192, inside the 160 KB of a CU.
+//   C2  many workgroups: cov = L^-T L^-1 on 16 x 16 tiles of the lower triangle (both triangles written from ONE value: the
+//       matrix is symmetric bit for bit), one wave per patch for v = L^-1 e_k (coalesced rows of the transposed copy) and
+//       the patch's chi2 / valid-factor partial over its edge segment, summed in segment order
+//   C3  one workgroup: chi2 and the valid count from the per-patch partials, in group order
+// No float atomics; every sum is an fma chain or an ordered sum: the outputs are the same bits from call to call.
+template <int TG>
+__global__ void __launch_bounds__(TG * TG)
+    ba_cholinv_kernel(const float *__restrict__ S, float *__restrict__ Linv, float *__restrict__ LinvT,
+                      int32_t *__restrict__ flag, int32_t *__restrict__ info, int n6) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int ld = n6 + 1;                       // odd for every 6N: conflict-free column walks
+  float *A = sm;                               // n6 x ld
+  float *Lk = sm + n6 * ld;                    // nb x 28: the factored diagonal blocks (21 lower entries + 6 inverses)
+  __shared__ int s_bad, s_nf;
+  const int tid = threadIdx.x, nt = TG * TG;
+  const int ty = tid / TG, tx = tid % TG;
+  {
+    int r = tid / n6, c = tid - r * n6;
+    const int dr = nt / n6, dc = nt - dr * n6;
+    for (int q = tid; q < n6 * n6; q += nt) {
+      A[r * ld + c] = S[q];
+      r += dr; c += dc;
+      if (c >= n6) { c -= n6; r++; }
+    }
+  }
+  if (tid == 0) { s_bad = 0; s_nf = 0; }
+  __syncthreads();
+  const int nb = n6 / 6;
+  // ---- S = L L' (K6's factorisation, operation for operation, without the rhs row)
+  for (int kb = 0; kb < nb; kb++) {
+    const int c0 = 6 * kb;
+    const int r0 = c0 + 6, m = n6 - r0;        // m trailing rows / columns
+    if ((tid & ~63) < max(m, 1)) {
+      float l[6][6], li[6];
+#pragma unroll
+      for (int i = 0; i < 6; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++) l[i][j] = A[(c0 + i) * ld + c0 + j];
+      bool bad = false;
+#pragma unroll
+      for (int j = 0; j < 6; j++) {
+        float d = l[j][j];
+#pragma unroll
+        for (int k = 0; k < j; k++) d = __builtin_fmaf(-l[j][k], l[j][k], d);
+        bad |= !(d > 0.0f);
+        li[j] = __builtin_amdgcn_rsqf(d);
+        l[j][j] = d * li[j];
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+          float t = l[i][j];
+#pragma unroll
+          for (int k = 0; k < j; k++) t = __builtin_fmaf(-l[i][k], l[j][k], t);
+          l[i][j] = t * li[j];
+        }
+      }
+      if (tid == 0) {
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+          for (int j = 0; j <= i; j++) Lk[kb * 28 + q++] = l[i][j];
+#pragma unroll
+        for (int j = 0; j < 6; j++) Lk[kb * 28 + 21 + j] = li[j];
+        if (bad) s_bad = 1;
+      }
+      for (int i = r0 + tid; i < n6; i += nt) {
+        float x[6];
+#pragma unroll
+        for (int j = 0; j < 6; j++) x[j] = A[i * ld + c0 + j];
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+#pragma unroll
+          for (int k = 0; k < j; k++) x[j] = __builtin_fmaf(-x[k], l[j][k], x[j]);
+          x[j] *= li[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 6; j++) A[i * ld + c0 + j] = x[j];
+      }
+    }
+    __syncthreads();
+    for (int ii = ty; ii < m; ii += TG) {
+      float ri[6];
+#pragma unroll
+      for (int k = 0; k < 6; k++) ri[k] = A[(r0 + ii) * ld + c0 + k];
+      for (int jj = tx; jj <= ii; jj += TG) {
+        const float *rj = A + (r0 + jj) * ld + c0;
+        float t = A[(r0 + ii) * ld + r0 + jj];
+#pragma unroll
+        for (int k = 0; k < 6; k++) t = __builtin_fmaf(-ri[k], rj[k], t);
+        A[(r0 + ii) * ld + r0 + jj] = t;
+      }
+    }
+    __syncthreads();
+  }
+  // ---- X = L^-1 in place, block row by block row
+  for (int kb = 0; kb < nb; kb++) {
+    const int c0 = 6 * kb;
+    float xd[6][6], x[6];
+    const bool work = (tid & ~63) < c0 + 6;      // whole waves: columns [0, c0) and the diagonal block's writer (tid < 6)
+    if (work) {
+      float lk[21], li[6];
+#pragma unroll
+      for (int q = 0; q < 21; q++) lk[q] = Lk[kb * 28 + q];
+#pragma unroll
+      for (int q = 0; q < 6; q++) li[q] = Lk[kb * 28 + 21 + q];
+      // the 6 x 6 inverse of the diagonal block (every thread: uniform work on broadcast values)
+#pragma unroll
+      for (int c = 0; c < 6; c++) {
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+          if (r < c) { xd[r][c] = 0.0f; continue; }
+          if (r == c) { xd[r][c] = li[r]; continue; }
+          float t = 0.0f;
+#pragma unroll
+          for (int q = c; q < r; q++) t = __builtin_fmaf(lk[r * (r + 1) / 2 + q], xd[q][c], t);
+          xd[r][c] = -t * li[r];
+        }
+      }
+      if (tid < c0) {
+        float t[6] = {0, 0, 0, 0, 0, 0};
+        for (int k = tid & ~63; k < c0; k++) {       // (wave-uniform bounds: the L row block is read as broadcasts)
+          const float xk = k >= tid ? A[k * ld + tid] : 0.0f;
+#pragma unroll
+          for (int r = 0; r < 6; r++) t[r] = __builtin_fmaf(A[(c0 + r) * ld + k], xk, t[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+          float a = 0.0f;
+#pragma unroll
+          for (int q = 0; q <= r; q++) a = __builtin_fmaf(xd[r][q], t[q], a);
+          x[r] = -a;
+        }
+      }
+    }
+    __syncthreads();
+    if (work) {
+      if (tid < c0) {
+#pragma unroll
+        for (int r = 0; r < 6; r++) A[(c0 + r) * ld + tid] = x[r];
+      }
+      if (tid < 6) {
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+          float v = 0.0f;
+#pragma unroll
+          for (int c = 0; c < 6; c++) v = (c == tid) ? xd[r][c] : v;
+          A[(c0 + r) * ld + c0 + tid] = v;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  // ---- out: L^-1 and its transpose, zeros above / below the diagonal; a failed factorisation or an inverse that is not
+  // finite raises the flag (C2 then writes NaN, never a plausible number) and bit 0 of *info, as the solver does
+  for (int q = tid; q < n6 * n6; q += nt) {
+    const int r = q / n6, c = q - r * n6;
+    const float v = c <= r ? A[r * ld + c] : 0.0f;
+    if (!(fabsf(v) <= 3.0e38f)) s_nf = 1;
+    Linv[q] = v;
+    LinvT[(size_t)c * n6 + r] = v;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int bad = (s_bad | s_nf) != 0;
+    *flag = bad;
+    if (bad && info) atomicOr(info, 1);
+  }
+}
+
+#define BA_CT 16      // cov tile
+__global__ void __launch_bounds__(256)
+    ba_cov_expand_kernel(const float *__restrict__ Linv, const float *__restrict__ LinvT, const int32_t *__restrict__ flag,
+                         const float *__restrict__ Erow, const float *__restrict__ Qv, const int64_t *__restrict__ kx,
+                         const int32_t *__restrict__ order_k, const int32_t *__restrict__ seg_k,
+                         const int32_t *__restrict__ ngroups, BaEdgeIn ein, float *__restrict__ cov,
+                         float *__restrict__ depth_var, float *__restrict__ cpart, int32_t *__restrict__ npart, int n6,
+                         int tiles, int max_groups, const int32_t *__restrict__ dyn, int opt_window) {
+  const int tid = threadIdx.x;
+  const bool bad = *flag != 0;
+  const float qnan = __int_as_float(0x7fc00000);
+  if ((int)blockIdx.x < tiles * tiles) {
+    const int bi = blockIdx.x / tiles, bj = blockIdx.x - bi * tiles;
+    if (bj > bi) return;
+    const int i = bi * BA_CT + tid / BA_CT, j = bj * BA_CT + tid % BA_CT;
+    if (i >= n6 || j > i) return;
+    float c = 0.0f;
+    for (int k = i; k < n6; k++) c = __builtin_fmaf(Linv[(size_t)k * n6 + i], Linv[(size_t)k * n6 + j], c);
+    if (bad) c = qnan;
+    cov[(size_t)i * n6 + j] = c;
+    cov[(size_t)j * n6 + i] = c;
+    return;
+  }
+  ba_dyn_window(dyn, opt_window, ein.t0, ein.N);
+  const int wave = tid / 64, lane = tid % 64;
+  const int g = (blockIdx.x - tiles * tiles) * 4 + wave;
+  if (g >= min(*ngroups, max_groups)) return;    // (max_groups: the rows of Erow / cpart the caller's bound gave room for)
+  // v = L^-1 e_k: lane i keeps rows i, i + 64, i + 128 (n6 <= 192); column a of L^-1 is row a of the transposed copy
+  float v[3] = {0, 0, 0};
+  for (int a = 0; a < n6; a++) {
+    const float ea = Erow[(size_t)g * n6 + a];
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+      const int i = lane + 64 * q;
+      if (i < n6) v[q] = __builtin_fmaf(ea, LinvT[(size_t)a * n6 + i], v[q]);
+    }
+  }
+  float s = v[0] * v[0];
+  s = __builtin_fmaf(v[1], v[1], s);
+  s = __builtin_fmaf(v[2], v[2], s);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  s = __shfl(s, 0, 64);
+  // the patch's part of chi2 = sum_valid (w0 rx^2 + w1 ry^2) and of the valid count, in segment order
+  const int s0 = seg_k[g], s1 = seg_k[g + 1];
+  float chi = 0.0f;
+  int cnt = 0;
+  for (int b0 = s0; b0 < s1; b0 += 64) {
+    const int nb = min(64, s1 - b0);
+    float term = 0.0f, gate = 0.0f;
+    if (lane < nb) {
+      float r[BA_REC];
+      ba_edge_compute_gate(ein, order_k[b0 + lane], r, gate);
+      const float tx_ = (r[R_W0] * r[R_R0]) * r[R_R0], ty_ = (r[R_W1] * r[R_R1]) * r[R_R1];
+      term = gate != 0.0f ? tx_ + ty_ : 0.0f;        // (a gated factor's residual may be inf / NaN)
+    }
+    cnt += __popcll(__ballot(gate != 0.0f));
+    for (int l = 0; l < nb; l++) chi += __shfl(term, l, 64);
+  }
+  if (lane == 0) {
+    const float q = Qv[g];
+    cpart[g] = chi;
+    npart[g] = cnt;
+    depth_var[kx[g]] = bad ? qnan : __builtin_fmaf(q * q, s, q);     // Q + Q^2 |L^-1 e|^2: cannot go below Q
+  }
+}
+
+// stats words: [0] chi2 (float), [1] valid factors, [2] Mu, [3] N (free poses), [4] t0, [5] 1 = factorisation failed -- [1] ..
+// [5] int32 bit patterns -- [6], [7] zero
+__global__ void __launch_bounds__(256)
+    ba_cov_stats_kernel(const float *__restrict__ cpart, const int32_t *__restrict__ npart,
+                        const int32_t *__restrict__ ngroups, const int32_t *__restrict__ flag, float *__restrict__ stats,
+                        int t0, int N, int max_groups, const int32_t *__restrict__ dyn, int opt_window) {
+  __shared__ float s_c[256];
+  __shared__ int s_n[256];
+  ba_dyn_window(dyn, opt_window, t0, N);
+  const int tid = threadIdx.x, nk = min(*ngroups, max_groups);
+  const int per = (nk + 255) / 256;
+  float c = 0.0f;
+  int n = 0;
+  for (int g = tid * per; g < min(nk, (tid + 1) * per); g++) { c += cpart[g]; n += npart[g]; }
+  s_c[tid] = c; s_n[tid] = n;
+  __syncthreads();
+  if (tid == 0) {
+    float ct = 0.0f;
+    int nt = 0;
+    for (int q = 0; q < 256; q++) { ct += s_c[q]; nt += s_n[q]; }
+    stats[0] = ct;
+    stats[1] = __int_as_float(nt);
+    stats[2] = __int_as_float(nk);
+    stats[3] = __int_as_float(N > 0 ? N : 0);
+    stats[4] = __int_as_float(t0);
+    stats[5] = __int_as_float(*flag != 0 ? 1 : 0);
+    stats[6] = 0.0f; stats[7] = 0.0f;
+  }
+}
+
 __global__ void ba_pairkey_kernel(const int64_t *__restrict__ ii, const int64_t *__restrict__ jj,
                                   int64_t *__restrict__ keys, int E, long long np) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1053,6 +1339,97 @@ int ramp_i_ba_dyn(float *poses, float *patches, const float *intrinsics, const f
                     opt_window);
 }
 
+// ---- uncertainty: the system of ONE iteration at the state passed in, no step taken (nothing retracts)
+struct BaCovWs { float *Linv, *LinvT, *cpart; int32_t *npart, *flag; };
+static size_t ba_cov_carve(void *ws, int n6, int Mu_b, BaCovWs *c) {
+  size_t off = 0;
+  char *base = (char *)ws;
+  auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += al(bytes); return (void *)p; };
+  c->Linv = (float *)take((size_t)(n6 * n6 + 1) * 4);
+  c->LinvT = (float *)take((size_t)(n6 * n6 + 1) * 4);
+  c->cpart = (float *)take((size_t)Mu_b * 4);
+  c->npart = (int32_t *)take((size_t)Mu_b * 4);
+  c->flag = (int32_t *)take(64);
+  return off;
+}
+static int ba_cov_run(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                      const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk,
+                      int E, int P, int t0, int t1, BaWs &w, BaCovWs &c, const int32_t *order_k, const int32_t *seg_k,
+                      const int32_t *nk, const int64_t *kx, const int32_t *order_p, const int32_t *seg_p, const int32_t *np,
+                      int32_t *info, float *cov, float *depth_var, float *stats, hipStream_t st,
+                      const int32_t *dyn = nullptr, int opt_window = 0) {
+  const int N = t1 - t0, n6 = 6 * N;
+  const size_t lds = (size_t)(n6 * (n6 + 1) + (n6 / 6) * 28) * sizeof(float);
+  if (lds > 160 * 1024) return RAMP_EUNSUPPORTED;
+  const int PP = P * P, c11 = 1 * P + 1;
+  if (N > 0 && lds > 64 * 1024) {
+    if (hipFuncSetAttribute((const void *)ba_cholinv_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return RAMP_ELAUNCH;
+  }
+  const int pthreads = ((n6 + 2 + 63) / 64) * 64;
+  if (pthreads > 256) return RAMP_EUNSUPPORTED;
+  BaEdgeIn ein;
+  ein.poses = poses; ein.patches = patches; ein.intr = intrinsics; ein.target = target; ein.weight = weight;
+  ein.ii = ii; ein.jj = jj; ein.kk = kk; ein.PP = PP; ein.c11 = c11; ein.t0 = t0; ein.N = N;
+  if (hipMemsetAsync(c.flag, 0, sizeof(int32_t), st) != hipSuccess) return RAMP_ELAUNCH;
+  if (N > 0) {
+    // K2 .. K5 exactly as an iteration of ba_iterate launches them
+    hipLaunchKernelGGL(ba_patch_pair_kernel, dim3(w.Mu_b + w.Gp_b), dim3(256), 0, st, w.Mu_b, w.rec, order_k, seg_k, nk,
+                       lmbda, w.Erow, w.Cv, w.uv, w.Qv, n6, order_p, seg_p, np, w.pairs, w.pair_ij, ein, 1, dyn, opt_window);
+    if (w.tiles == 1 && ramp_cdiv(w.Mu_b, w.KS) <= BA_S1_ROWS)
+      hipLaunchKernelGGL(ba_schur1_kernel, dim3(1, 1, w.KS), dim3(256), 0, st, w.Erow, w.Qv, w.uv, nk, w.S_part, w.y_part,
+                         n6, w.KS);
+    else
+      hipLaunchKernelGGL(ba_schur_kernel, dim3(w.tiles, w.tiles, w.KS), dim3(256), 0, st, w.Erow, w.Qv, w.uv, nk,
+                         w.S_part, w.y_part, n6, w.KS);
+    if (N <= 16)
+      hipLaunchKernelGGL(ba_assemble2_kernel, dim3(N, N), dim3(256), 0, st, w.pairs, w.pair_ij, np, w.S_part, w.y_part,
+                         w.S, w.yv, n6, w.KS, info);
+    else
+      hipLaunchKernelGGL(ba_assemble_kernel, dim3(N, ramp_cdiv(6 * n6, 192)), dim3(256), 0, st, w.pairs, w.pair_ij, np,
+                         w.S_part, w.y_part, w.S, w.yv, n6, w.KS, info);
+    hipLaunchKernelGGL(ba_cholinv_kernel<32>, dim3(1), dim3(1024), lds, st, w.S, c.Linv, c.LinvT, c.flag, info, n6);
+  } else {
+    hipLaunchKernelGGL(ba_edge_kernel, dim3(ramp_cdiv(E, 256)), dim3(256), 0, st, ein, w.rec, E, dyn, opt_window);
+    hipLaunchKernelGGL(ba_patch_kernel, dim3(w.Mu_b), dim3(pthreads), 0, st, w.rec, order_k, seg_k, nk, lmbda, w.Erow,
+                       w.Cv, w.uv, w.Qv, n6);
+  }
+  const int tiles = ramp_cdiv(n6, BA_CT);
+  hipLaunchKernelGGL(ba_cov_expand_kernel, dim3(tiles * tiles + ramp_cdiv(w.Mu_b, 4)), dim3(256), 0, st, c.Linv, c.LinvT,
+                     c.flag, w.Erow, w.Qv, kx, order_k, seg_k, nk, ein, cov, depth_var, c.cpart, c.npart, n6, tiles, w.Mu_b,
+                     dyn, opt_window);
+  hipLaunchKernelGGL(ba_cov_stats_kernel, dim3(1), dim3(256), 0, st, c.cpart, c.npart, nk, c.flag, stats, t0, N, w.Mu_b,
+                     dyn, opt_window);
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+
+size_t ramp_i_ba_cov_dyn_ws(int opt_window, int max_patches) {
+  BaCovWs c;
+  return ba_cov_carve(nullptr, 6 * opt_window, max_patches > 0 ? max_patches : 1, &c);
+}
+// the dyn-sized form: the window and the factor segments come from the `dyn` words and the caller's groups; the system has
+// opt_window poses (a shorter window leaves identity blocks behind it), cov is [6 opt_window]^2.  ba_ws: ramp_i_ba_dyn's.
+int ramp_i_ba_cov_dyn(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                      const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk,
+                      int E_cap, int P, int n_poses, int n_patches, int opt_window, const int32_t *order_k,
+                      const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
+                      const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs, void *ba_ws,
+                      size_t ba_ws_bytes, void *cov_ws, size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var,
+                      float *stats, const int32_t *dyn, hipStream_t st) {
+  if (E_cap <= 0 || opt_window <= 0 || !dyn || !ba_ws || !cov_ws || !cov || !depth_var || !stats) return RAMP_EINVAL;
+  int rc = ba_check_args(E_cap, P, n_poses, n_patches, 1, 1 + opt_window, 1);
+  if (rc != RAMP_OK) return rc;
+  BaWs w;
+  BaCovWs c;
+  if (ba_carve(ba_ws, E_cap, n_poses, n_patches, opt_window, 0, max_patches, max_pairs, &w) > ba_ws_bytes)
+    return RAMP_EWORKSPACE;
+  if (ba_cov_carve(cov_ws, 6 * opt_window, w.Mu_b, &c) > cov_ws_bytes) return RAMP_EWORKSPACE;
+  return ba_cov_run(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E_cap, P, 1, 1 + opt_window, w, c,
+                    order_k, seg_k, ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, info, cov, depth_var, stats, st, dyn,
+                    opt_window);
+}
+
 extern "C" {
 
 size_t ramp_ba_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1) {
@@ -1120,6 +1497,78 @@ int ramp_ba_forward_planned(float *poses, float *patches, const float *intrinsic
     return RAMP_EWORKSPACE;
   return ba_iterate(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P, t0, t1, iterations,
                     w, order_k, seg_k, ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, info, st);
+}
+
+size_t ramp_ba_covariance_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1) {
+  BaWs w;
+  BaCovWs c;
+  const int N = t1 - t0 > 0 ? t1 - t0 : 0;
+  const size_t a = ba_carve(nullptr, E, n_poses, n_patches, N, 1, 0, 0, &w);
+  return a + ba_cov_carve(nullptr, 6 * N, w.Mu_b, &c);
+}
+
+int ramp_ba_covariance(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                       const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
+                       const int64_t *kk, int E, int P, int n_poses, int n_patches, int t0, int t1, float *cov,
+                       float *depth_var, float *stats, void *ws, size_t ws_bytes, int32_t *info, void *stream) {
+  int rc = ba_check_args(E, P, n_poses, n_patches, t0, t1, 1);
+  if (rc != RAMP_OK) return rc;
+  if (E == 0) return RAMP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (info) (void)hipMemsetAsync(info, 0, sizeof(int32_t), st);
+  if (!poses || !patches || !intrinsics || !target || !weight || !lmbda || !ii || !jj || !kk || !ws || !depth_var ||
+      !stats || (t1 > t0 && !cov))
+    return RAMP_EINVAL;
+  const int N = t1 - t0;
+  BaWs w;
+  BaCovWs c;
+  const size_t a = ba_carve(ws, E, n_poses, n_patches, N, 1, 0, 0, &w);
+  if (a + ba_cov_carve((char *)ws + a, 6 * N, w.Mu_b, &c) > ws_bytes) return RAMP_EWORKSPACE;
+  int32_t *nk = w.counters, *np = w.counters + 1;
+  rc = ramp_internal_group_by(kk, E, n_patches, w.order_k, nullptr, w.seg_k, w.kx, nk, w.gb, w.gb_bytes, st);
+  if (rc != RAMP_OK) return rc;
+  if (N > 0) {
+    hipLaunchKernelGGL(ba_pairkey_kernel, dim3(ramp_cdiv(E, 256)), dim3(256), 0, st, ii, jj, w.pkeys, E,
+                       (long long)n_poses);
+    rc = ramp_internal_group_by(w.pkeys, E, (int64_t)n_poses * n_poses, w.order_p, nullptr, w.seg_p,
+                                w.pukeys, np, w.gb, w.gb_bytes, st);
+    if (rc != RAMP_OK) return rc;
+  }
+  return ba_cov_run(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P, t0, t1, w, c, w.order_k,
+                    w.seg_k, nk, w.kx, w.order_p, w.seg_p, np, info, cov, depth_var, stats, st);
+}
+
+size_t ramp_ba_covariance_planned_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1, int max_patches,
+                                                  int max_pairs) {
+  BaWs w;
+  BaCovWs c;
+  const int N = t1 - t0 > 0 ? t1 - t0 : 0;
+  const size_t a = ba_carve(nullptr, E, n_poses, n_patches, N, 0, max_patches, max_pairs, &w);
+  return a + ba_cov_carve(nullptr, 6 * N, w.Mu_b, &c);
+}
+
+int ramp_ba_covariance_planned(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                               const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
+                               const int64_t *kk, int E, int P, int n_poses, int n_patches, int t0, int t1,
+                               float *cov, float *depth_var, float *stats, const int32_t *order_k,
+                               const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
+                               const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs,
+                               void *ws, size_t ws_bytes, int32_t *info, void *stream) {
+  int rc = ba_check_args(E, P, n_poses, n_patches, t0, t1, 1);
+  if (rc != RAMP_OK) return rc;
+  if (E == 0) return RAMP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (info) (void)hipMemsetAsync(info, 0, sizeof(int32_t), st);
+  if (!poses || !patches || !intrinsics || !target || !weight || !lmbda || !ii || !jj || !kk || !ws || !order_k ||
+      !seg_k || !ngroups_k || !ukeys_k || !order_p || !seg_p || !ngroups_p || !depth_var || !stats || (t1 > t0 && !cov))
+    return RAMP_EINVAL;
+  if (max_patches <= 0 || max_pairs <= 0) return RAMP_EINVAL;
+  BaWs w;
+  BaCovWs c;
+  const size_t a = ba_carve(ws, E, n_poses, n_patches, t1 - t0, 0, max_patches, max_pairs, &w);
+  if (a + ba_cov_carve((char *)ws + a, 6 * (t1 - t0), w.Mu_b, &c) > ws_bytes) return RAMP_EWORKSPACE;
+  return ba_cov_run(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P, t0, t1, w, c, order_k, seg_k,
+                    ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, info, cov, depth_var, stats, st);
 }
 
 }  // extern "C"

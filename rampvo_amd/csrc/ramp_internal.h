@@ -46,6 +46,14 @@ int ramp_i_ba_dyn(float *poses, float *patches, const float *intrinsics, const f
                   const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
                   const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs, void *ws,
                   size_t ws_bytes, int32_t *info, const int32_t *dyn, hipStream_t st);
+size_t ramp_i_ba_cov_dyn_ws(int opt_window, int max_patches);
+int ramp_i_ba_cov_dyn(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                      const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk,
+                      int E_cap, int P, int n_poses, int n_patches, int opt_window, const int32_t *order_k,
+                      const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
+                      const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs, void *ba_ws,
+                      size_t ba_ws_bytes, void *cov_ws, size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var,
+                      float *stats, const int32_t *dyn, hipStream_t st);
 extern "C" {
 int ramp_i_corr_fwd(const void *fmap1, const ramp_corr_level *levels, int nlevels, const float *coords,
                     const int64_t *ii, const int64_t *jj, const int32_t *order, void *out, int out_row_elems,

@@ -715,3 +715,84 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
 }
 
 }  // extern "C"
+
+// ramp_track_uncertainty: the sizes of the graph the last edit kept, as a dyn block of its own (n = NROW keyframes, the first
+// EKEPT factors), and the last update's target / weight gathered through the kept factors' hidden-state rows
+__global__ void __launch_bounds__(256)
+    trk_unc_prep_kernel(const int32_t *__restrict__ dyn, int32_t *__restrict__ dynp, const int64_t *__restrict__ row,
+                        const float *__restrict__ target, const float *__restrict__ weight, float *__restrict__ tg,
+                        float *__restrict__ wg, int E_cap) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int Ek = min(max(dyn[RAMP_DYN_EKEPT], 0), E_cap);
+  if (e < RAMP_DYN_WORDS) {
+    int v = dyn[e];
+    if (e == RAMP_DYN_N) v = dyn[RAMP_DYN_NROW];
+    if (e == RAMP_DYN_E) v = Ek;
+    if (e == RAMP_DYN_STATUS) v = 0;
+    dynp[e] = v;
+  }
+  if (e >= E_cap) return;
+  const long r = e < Ek ? (long)row[e] : -1;
+  const bool ok = r >= 0 && r < E_cap;
+  tg[2 * (size_t)e + 0] = ok ? target[2 * r + 0] : 0.0f;
+  tg[2 * (size_t)e + 1] = ok ? target[2 * r + 1] : 0.0f;
+  wg[2 * (size_t)e + 0] = ok ? weight[2 * r + 0] : 0.0f;
+  wg[2 * (size_t)e + 1] = ok ? weight[2 * r + 1] : 0.0f;
+}
+struct TrkUncWs {
+  int32_t *dynp, *kk_order, *kk_gid, *kk_seg, *kk_ngroups, *ij_order, *ij_gid, *ij_seg, *ij_ngroups, *kj;
+  int64_t *kk_ukeys, *ij_ukeys, *ix, *jx;
+  float *tg, *wg;
+  void *cov_ws;
+  size_t cov_ws_bytes;
+};
+static size_t trk_unc_carve(const ramp_track *t, void *ws, TrkUncWs *u) {
+  size_t off = 0;
+  char *base = (char *)ws;
+  auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return (void *)p; };
+  const size_t e = (size_t)t->E_cap;
+  u->dynp = (int32_t *)take(RAMP_DYN_WORDS * 4 + 64);
+  u->kk_order = (int32_t *)take(e * 4); u->kk_gid = (int32_t *)take(e * 4);
+  u->ij_order = (int32_t *)take(e * 4); u->ij_gid = (int32_t *)take(e * 4);
+  u->kk_seg = (int32_t *)take((size_t)(t->kk_cap + 2) * 4); u->ij_seg = (int32_t *)take((size_t)(t->ij_cap + 2) * 4);
+  u->kk_ngroups = (int32_t *)take(4); u->ij_ngroups = (int32_t *)take(4);
+  u->kk_ukeys = (int64_t *)take((size_t)(t->kk_cap + 2) * 8); u->ij_ukeys = (int64_t *)take((size_t)(t->ij_cap + 2) * 8);
+  u->ix = (int64_t *)take(e * 8); u->jx = (int64_t *)take(e * 8); u->kj = (int32_t *)take(e * 4);
+  u->tg = (float *)take(e * 8); u->wg = (float *)take(e * 8);
+  u->cov_ws_bytes = ramp_i_ba_cov_dyn_ws(t->opt_window, t->kk_cap);
+  u->cov_ws = take(u->cov_ws_bytes);
+  return off;
+}
+
+extern "C" {
+
+size_t ramp_track_uncertainty_workspace_bytes(const ramp_track *t) {
+  TrkUncWs u;
+  return trk_valid(t) ? trk_unc_carve(t, nullptr, &u) : 0;
+}
+
+int ramp_track_uncertainty(const ramp_track *t, int cur, float *cov, float *depth_var, float *stats, void *ws,
+                           size_t ws_bytes, void *stream) {
+  if (!trk_valid(t) || cur < 0 || cur > 1 || !cov || !depth_var || !stats || !ws || !t->target || !t->weight || !t->ba_ws)
+    return RAMP_EINVAL;
+  TrkUncWs u;
+  if (trk_unc_carve(t, ws, &u) > ws_bytes) return RAMP_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const int Ec = t->E_cap;
+  const int64_t *g = t->graph[cur];
+  const int64_t *ii = g, *jj = g + Ec, *kk = g + 2 * (size_t)Ec, *row = g + 3 * (size_t)Ec;
+  const int nthreads = Ec > RAMP_DYN_WORDS ? Ec : RAMP_DYN_WORDS;
+  hipLaunchKernelGGL(trk_unc_prep_kernel, dim3(ramp_cdiv(nthreads, 256)), dim3(256), 0, st, t->dyn, u.dynp, row, t->target,
+                     t->weight, u.tg, u.wg, Ec);
+  int32_t *status = u.dynp + RAMP_DYN_STATUS;          // (the call's own word: the tracker's sticky status is not touched)
+  const int rc = ramp_i_plan_dyn(g, Ec, Ec, u.dynp, status, t->M, t->kkey_cap, t->pkey_cap, t->kk_cap, t->ij_cap, u.kk_order,
+                                 u.kk_gid, u.kk_seg, u.kk_ngroups, u.kk_ukeys, u.ij_order, u.ij_gid, u.ij_seg, u.ij_ngroups,
+                                 u.ij_ukeys, u.ix, u.jx, u.kj, t->plan_ws, t->plan_ws_bytes, nullptr, st);
+  if (rc != RAMP_OK) return rc;
+  return ramp_i_ba_cov_dyn(t->poses, t->patches, t->intrinsics, u.tg, u.wg, t->lmbda, ii, jj, kk, Ec, t->P, t->n_rows,
+                           t->n_rows * t->M, t->opt_window, u.kk_order, u.kk_seg, u.kk_ngroups, u.kk_ukeys, t->kk_cap,
+                           u.ij_order, u.ij_seg, u.ij_ngroups, t->ij_cap, t->ba_ws, t->ba_ws_bytes, u.cov_ws, u.cov_ws_bytes,
+                           status, cov, depth_var, stats, u.dynp, st);
+}
+
+}  // extern "C"

@@ -26,6 +26,28 @@ def BA(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, M=
     return []
 
 
+def covariance(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, M=0, info=None, plan=None):
+    """Uncertainty of the window: ``(cov [6N, 6N], depth_var [n_patches], stats)`` with N = t1 - t0 free poses.
+
+    The system is the one ``BA`` builds in one iteration, linearised at the state passed in -- same per-factor terms, same
+    validity gate, intrinsics row 0, poses outside [t0, t1) fixed -- and no step is taken: the inputs are untouched.
+    ``Q = 1 / (C + lmbda)``, ``S = B - E Q E'`` INCLUDING the solver's own diagonal damping ``S_dd += 1e-4 S_dd + 1``: the
+    covariance is that of the system the step is actually solved with, not of the undamped normal equations.
+
+    * ``cov = S^-1``, symmetric bit for bit.  Tangent order as the step's (translation 3, rotation 3 per pose); the
+      perturbation is the left one of the retraction ``T <- Exp(xi) T`` on the world-to-camera poses.
+    * ``depth_var[k] = Q_k + Q_k^2 e_k' S^-1 e_k`` at index ``kk`` for every patch with a factor; the others stay ``inf``.
+    * ``stats``: dict(chi2 = sum over valid factors of w0 rx^2 + w1 ry^2, n_valid, Mu, N, t0, failed).  Reading it
+      synchronises; ``cov`` / ``depth_var`` are device tensors ordered on the current stream.
+
+    t1 == t0: ``cov`` is empty and ``depth_var = Q_k``.  A failed factorisation (or an inverse that is not finite) sets bit
+    0 of ``info`` as ``BA`` does and fills ``cov`` and the written ``depth_var`` entries with NaN.  ``M`` is accepted for
+    symmetry with ``BA`` (one storage serves both of the reference's settings).  No autograd."""
+    p = poses.data if hasattr(poses, "data") and not isinstance(poses, torch.Tensor) else poses
+    cov, depth_var, raw = ops.ba_covariance(p, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, info, plan=plan)
+    return cov, depth_var, ops.ba_covariance_stats(raw)
+
+
 def neighbors(ii, jj, ii_bound=0, jj_bound=0):
     """cuda_ba.neighbors(kk, jj) -> (ix, jx), computed on the device."""
     return ops.neighbors(ii, jj, ii_bound, jj_bound)

@@ -570,3 +570,54 @@ def ba(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, it
                                 ptr(_idx(kk)), E, P, n_poses, n_patches, int(t0), int(t1),
                                 int(iterations), ptr(ws), ws.numel(), ptr(info), stream()),
           "ramp_ba_forward")
+
+
+def ba_covariance(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, info=None, plan=None):
+    """marginal covariance of the free poses and marginal depth variances of the window (include/ramp_hip.h
+    ``ramp_ba_covariance``): returns (cov [6N, 6N], depth_var [n_patches] pre-filled with inf, stats [8] raw words).
+    The inputs are only read."""
+    require_cuda(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk)
+    for t in (poses, patches):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("ba_covariance reads poses/patches in place: contiguous float32 required")
+    P = patches.shape[-1]
+    n_poses = poses.numel() // 7
+    n_patches = patches.numel() // (3 * P * P)
+    intrinsics = intrinsics.reshape(-1, 4).contiguous().float()
+    target = target.reshape(-1, 2).contiguous().float()
+    weight = weight.reshape(-1, 2).contiguous().float()
+    lmbda = lmbda.reshape(-1).contiguous().float()
+    E = ii.shape[0]
+    assert target.shape[0] == E and weight.shape[0] == E
+    t0, t1 = int(t0), int(t1)
+    n6 = 6 * max(t1 - t0, 0)
+    dev = poses.device
+    cov = torch.empty((n6, n6), dtype=torch.float32, device=dev)
+    depth_var = torch.full((n_patches,), float("inf"), dtype=torch.float32, device=dev)
+    stats = torch.zeros(8, dtype=torch.float32, device=dev)
+    if plan is not None:
+        gk, gp = plan.g_kk, plan.g_ij
+        mk, mp = max(int(plan.max_kk), 1), max(int(plan.max_ij), 1)
+        nbytes = lib().ramp_ba_covariance_planned_workspace_bytes(E, n_poses, n_patches, t0, t1, mk, mp)
+        ws = _lib.workspace(nbytes, dev, "ba")
+        check(lib().ramp_ba_covariance_planned(ptr(poses), ptr(patches), ptr(intrinsics), ptr(target), ptr(weight),
+                                               ptr(lmbda), ptr(_idx(ii)), ptr(_idx(jj)), ptr(_idx(kk)), E, P, n_poses,
+                                               n_patches, t0, t1, ptr(cov), ptr(depth_var), ptr(stats), ptr(gk.order),
+                                               ptr(gk.seg_start), ptr(gk.ngroups), ptr(gk.ukeys), mk, ptr(gp.order),
+                                               ptr(gp.seg_start), ptr(gp.ngroups), mp, ptr(ws), ws.numel(), ptr(info),
+                                               stream()), "ramp_ba_covariance_planned")
+    else:
+        nbytes = lib().ramp_ba_covariance_workspace_bytes(E, n_poses, n_patches, t0, t1)
+        ws = _lib.workspace(nbytes, dev, "ba")
+        check(lib().ramp_ba_covariance(ptr(poses), ptr(patches), ptr(intrinsics), ptr(target), ptr(weight), ptr(lmbda),
+                                       ptr(_idx(ii)), ptr(_idx(jj)), ptr(_idx(kk)), E, P, n_poses, n_patches, t0, t1,
+                                       ptr(cov), ptr(depth_var), ptr(stats), ptr(ws), ws.numel(), ptr(info), stream()),
+              "ramp_ba_covariance")
+    return cov, depth_var, stats
+
+
+def ba_covariance_stats(stats):
+    """the stats words of ramp_ba_covariance as a dict (synchronises: one 32-byte copy)"""
+    w = stats.detach().cpu()
+    i = w.view(torch.int32)
+    return dict(chi2=float(w[0]), n_valid=int(i[1]), Mu=int(i[2]), N=int(i[3]), t0=int(i[4]), failed=bool(i[5]))

@@ -455,6 +455,24 @@ class DeviceTrack:
         p.max_kk, p.max_ij = self.kk_cap, self.ij_cap
         return p
 
+    def uncertainty(self):
+        """(on the current stream) csrc/track.hip::ramp_track_uncertainty for the state between two frames: returns the
+        capacity-sized device tensors (cov [6 W, 6 W], depth_var [N * M] pre-filled with inf, stats [8] raw words); nothing is
+        synchronised and nothing of the tracker's state is written.  The scratch is allocated on the first call."""
+        lib = _lib.lib()
+        dev = self.dyn.device
+        if getattr(self, "_unc_ws", None) is None:
+            self._unc_ws = torch.empty(lib.ramp_track_uncertainty_workspace_bytes(ctypes.byref(self.t)), dtype=torch.uint8,
+                                       device=dev)
+        n6 = 6 * int(self.t.opt_window)
+        cov = torch.empty((n6, n6), dtype=torch.float32, device=dev)
+        depth_var = torch.full((int(self.t.n_rows) * int(self.t.M),), float("inf"), dtype=torch.float32, device=dev)
+        stats = torch.zeros(8, dtype=torch.float32, device=dev)
+        _lib.check(lib.ramp_track_uncertainty(ctypes.byref(self.t), self.cur, _lib.ptr(cov), _lib.ptr(depth_var),
+                                              _lib.ptr(stats), _lib.ptr(self._unc_ws), self._unc_ws.numel(), _lib.stream()),
+                   "ramp_track_uncertainty")
+        return cov, depth_var, stats
+
     def warm(self):
         """(on the current stream) read the correlation planes of the window once: csrc/track.hip::trk_warm_kernel"""
         _lib.check(_lib.lib().ramp_track_warm(ctypes.byref(self.t), _lib.ptr(self.sink), _lib.stream()), "ramp_track_warm")
@@ -540,4 +558,5 @@ class DeviceTrack:
         self.active = False
         return dict(n=n, ii=np.ascontiguousarray(g[0]), jj=np.ascontiguousarray(g[1]), kk=np.ascontiguousarray(g[2]),
                     rows=np.ascontiguousarray(g[3]), net=self.net[0][:int(d[DYN_EPREV])], log=log,
-                    status=int(d[DYN_STATUS]), weight=self.weight[:int(d[DYN_EPREV])].clone())
+                    status=int(d[DYN_STATUS]), weight=self.weight[:int(d[DYN_EPREV])].clone(),
+                    target=self.target[:int(d[DYN_EPREV])].clone())
