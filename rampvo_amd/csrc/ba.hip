@@ -5,20 +5,26 @@
 // every reduction is an ORDERED SEGMENT SUM (deterministic, no float atomics):
 //
 //   prep   group the edges by patch (kk) and by pose pair (ii,jj)  [graph.hip]
-//   K1     edge kernel: residual, validity, Jacobians -> 128 B record / edge
-//   K2     patch kernel: one workgroup per patch walks its edge segment and
+//   K1     per-edge record: residual, validity, Jacobians (32 floats).  With free poses K2 / K3 recompute it
+//          in registers and nothing is launched; without one ba_edge_kernel writes it to memory
+//   K2     patch role: one workgroup per patch walks its edge segment and
 //          emits the dense E row [6N], C, u, Q = 1/(C+lambda)
-//   K3     pair kernel: one workgroup per (i,j) segment emits the 6x6 blocks
+//   K3     pair role: one workgroup per (i,j) segment emits the 6x6 blocks
 //          w*Ji*Ji', w*Jj*Jj', -w*Ji*Jj', -w*Jj*Ji' and the gradient parts
-//   K4     split-K SYRK: partial  E' diag(Q) E  and  E' diag(Q) u
-//   K5     assemble  S = B - sum(partials),  y = v - ..., damping
-//   K6     single-workgroup LDS Cholesky + triangular solves -> dX
-//   K7     dZ = Q (u - E dX), depth retraction, SE3 pose retraction
+//          (K2 and K3 are ONE launch, ba_patch_pair_kernel; without a free pose ba_patch_kernel alone)
+//   K4     split-K SYRK: partial  E' diag(Q) E  and  E' diag(Q) u  (ba_schur1_kernel for a system of one tile
+//          whose chunk fits the LDS, otherwise ba_schur_kernel)
+//   K5     assemble  S = B - sum(partials),  y = v - ..., damping  (ba_assemble2_kernel up to 16 poses,
+//          ba_assemble_kernel above)
+//   K6     ba_cholb_kernel: single-workgroup LDS Cholesky + triangular solves -> dX
+//   K7     ba_retract_kernel: dZ = Q (u - E dX), depth retraction, SE3 pose retraction
+// K1 .. K5 are ba_build_system(); an iteration of the solver is ba_build_system(), K6, K7 (K4 .. K6 only with free poses).
 //
-// ramp_ba_covariance (the window's uncertainty) runs K2 .. K5 once at the state passed in, then
-//   C1     single-workgroup LDS Cholesky + in-place triangular inverse -> L^-1
-//   C2     cov = L^-T L^-1 (tiles), depth_var = Q + Q^2 |L^-1 e_k|^2 and the chi2 partials (one wave per patch)
-//   C3     chi2 / valid count from the partials, in group order
+// ramp_ba_covariance (the window's uncertainty) runs ba_build_system() once at the state passed in, then
+//   C1     ba_cholinv_kernel: K6's factorisation (ba_chol_factor, without the rhs row) + in-place triangular inverse -> L^-1
+//   C2     ba_cov_expand_kernel: cov = L^-T L^-1 (tiles), depth_var = Q + Q^2 |L^-1 e_k|^2 and the chi2 partials (one
+//          wave per patch)
+//   C3     ba_cov_stats_kernel: chi2 / valid count from the partials, in group order
 // and never K7: poses and patches are only read.
 //
 // Math restates ramp/fastba/ba_cuda.cu:232-376 (kernel), 433-582 (host loop),
@@ -36,7 +42,7 @@ static inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
 
 // ------------------------------------------------------------------ K1
 // The per-edge record: residual, validity, Jacobians (32 floats).  ba_edge_kernel writes it to memory (the path without
-// free poses); the patch / pair kernels of a regular iteration recompute it in registers from the edge's 116 bytes of
+// free poses); the patch / pair roles of a regular iteration recompute it in registers from the edge's 116 bytes of
 // inputs while they stage their segment -- the record never goes through HBM (it was written once and read twice per
 // iteration) and the launch is gone.  Same expressions either way: identical results.
 struct BaEdgeIn {
@@ -138,12 +144,14 @@ __global__ void __launch_bounds__(256)
 #ifndef BA_PBATCH
 #define BA_PBATCH 48    // (128 / 224 measured on MI355X: 126 / 139 us per BA call against 124 -- the pair role is not the long one)
 #endif
+// FUSED: one thread per edge of the chunk recomputes its record (ein); otherwise the records are read from rec
+template <bool FUSED>
 __device__ __forceinline__ void
     ba_patch_body(int g, const float *__restrict__ rec, const int32_t *__restrict__ order,
                   const int32_t *__restrict__ seg, const int32_t *__restrict__ ngroups,
                   const float *__restrict__ lmbda, float *__restrict__ Erow,
                   float *__restrict__ Cv, float *__restrict__ uv, float *__restrict__ Qv,
-                  int n6, const BaEdgeIn &ein, const bool fused, float *__restrict__ s_buf) {
+                  int n6, const BaEdgeIn &ein, float *__restrict__ s_buf) {
   float (*s_rec)[BA_REC + 1] = reinterpret_cast<float (*)[BA_REC + 1]>(s_buf);      // [BA_PCHUNK][BA_REC + 1]
   if (g >= *ngroups) return;
   // The merged launch's workgroups are sized for the pair role (156 sums); a patch needs n6 + 2 threads.  Waves without a
@@ -168,7 +176,7 @@ __device__ __forceinline__ void
   for (int b0 = s0; b0 < s1; b0 += BA_PCHUNK) {
     const int nb = min(BA_PCHUNK, s1 - b0);
     __syncthreads();
-    if (fused) {                                // one thread per edge of the chunk recomputes its record
+    if (FUSED) {
       if (tid < nb) {
         float r[BA_REC];
         ba_edge_compute(ein, order[b0 + tid], r);
@@ -222,17 +230,16 @@ __global__ void __launch_bounds__(256)
                     float *__restrict__ Cv, float *__restrict__ uv, float *__restrict__ Qv,
                     int n6) {
   __shared__ __attribute__((aligned(16))) float s_buf[BA_PCHUNK * (BA_REC + 1)];
-  ba_patch_body(blockIdx.x, rec, order, seg, ngroups, lmbda, Erow, Cv, uv, Qv, n6, BaEdgeIn(), false, s_buf);
+  ba_patch_body<false>(blockIdx.x, rec, order, seg, ngroups, lmbda, Erow, Cv, uv, Qv, n6, BaEdgeIn(), s_buf);
 }
 
 // ------------------------------------------------------------------ K3
 // pair record: [0,36) w Ji Ji', [36,72) w Jj Jj', [72,108) -w Ji Jj',
-// [108,144) -w Jj Ji', [144,150) -w r Ji, [150,156) w r Jj.  Threads >= 192 only take part in the barriers.
+// [108,144) -w Jj Ji', [144,150) -w r Ji, [150,156) w r Jj.  Threads >= 156 only take part in the barriers.
 __device__ __forceinline__ void
-    ba_pair_body(int g, const float *__restrict__ rec, const int32_t *__restrict__ order,
-                 const int32_t *__restrict__ seg, const int32_t *__restrict__ ngroups,
-                 float *__restrict__ pairs, int32_t *__restrict__ pair_ij, const BaEdgeIn &ein, const bool fused,
-                 float *__restrict__ s_rec) {
+    ba_pair_body(int g, const int32_t *__restrict__ order, const int32_t *__restrict__ seg,
+                 const int32_t *__restrict__ ngroups, float *__restrict__ pairs, int32_t *__restrict__ pair_ij,
+                 const BaEdgeIn &ein, float *__restrict__ s_rec) {
   // BA_PBATCH records per batch (any batch size sums the records in the same order: identical values)
   if (g >= *ngroups) return;
   const int tid = threadIdx.x;
@@ -257,20 +264,12 @@ __device__ __forceinline__ void
   for (int b0 = s0; b0 < s1; b0 += BA_PBATCH) {
     const int nb = min(BA_PBATCH, s1 - b0);
     __syncthreads();
-    if (fused) {                                // one thread per edge of the batch recomputes its record
-      if (tid < nb) {
-        float r[BA_REC];
-        ba_edge_compute(ein, order[b0 + tid], r);
+    if (tid < nb) {                             // one thread per edge of the batch recomputes its record
+      float r[BA_REC];
+      ba_edge_compute(ein, order[b0 + tid], r);
 #pragma unroll
-        for (int c = 0; c < BA_REC / 4; c++)
-          reinterpret_cast<float4 *>(s_rec)[tid * (BA_REC / 4) + c] = make_float4(r[4 * c], r[4 * c + 1], r[4 * c + 2], r[4 * c + 3]);
-      }
-    } else {
-      for (int q = tid < 192 ? tid : nb * (BA_REC / 4); q < nb * (BA_REC / 4); q += 192) {      // coalesced 16-byte loads of whole records
-        const int rr = q / (BA_REC / 4), cc = q - rr * (BA_REC / 4);
-        reinterpret_cast<float4 *>(s_rec)[q] =
-            reinterpret_cast<const float4 *>(rec + (size_t)order[b0 + rr] * BA_REC)[cc];
-      }
+      for (int c = 0; c < BA_REC / 4; c++)
+        reinterpret_cast<float4 *>(s_rec)[tid * (BA_REC / 4) + c] = make_float4(r[4 * c], r[4 * c + 1], r[4 * c + 2], r[4 * c + 3]);
     }
     __syncthreads();
     if (tid < 144) {
@@ -294,31 +293,23 @@ __device__ __forceinline__ void
   if (tid < 156) pairs[(size_t)g * BA_PAIR + tid] = acc;
 }
 
-__global__ void __launch_bounds__(192)
-    ba_pair_kernel(const float *__restrict__ rec, const int32_t *__restrict__ order,
-                   const int32_t *__restrict__ seg, const int32_t *__restrict__ ngroups,
-                   float *__restrict__ pairs, int32_t *__restrict__ pair_ij) {
-  __shared__ __attribute__((aligned(16))) float s_buf[BA_PBATCH * BA_REC];
-  ba_pair_body(blockIdx.x, rec, order, seg, ngroups, pairs, pair_ij, BaEdgeIn(), false, s_buf);
-}
-
-// K2 and K3 read the same per-edge records and do not depend on each other: one launch, the first n_patch
-// workgroups take the patch role, the rest the pair role (same arithmetic as the separate kernels)
+// K2 and K3 need the same per-edge records and do not depend on each other: one launch, the first n_patch
+// workgroups take the patch role, the rest the pair role
 __global__ void __launch_bounds__(256)
-    ba_patch_pair_kernel(int n_patch, const float *__restrict__ rec, const int32_t *__restrict__ order_k,
+    ba_patch_pair_kernel(int n_patch, const int32_t *__restrict__ order_k,
                          const int32_t *__restrict__ seg_k, const int32_t *__restrict__ nk,
                          const float *__restrict__ lmbda, float *__restrict__ Erow, float *__restrict__ Cv,
                          float *__restrict__ uv, float *__restrict__ Qv, int n6,
                          const int32_t *__restrict__ order_p, const int32_t *__restrict__ seg_p,
                          const int32_t *__restrict__ np, float *__restrict__ pairs, int32_t *__restrict__ pair_ij,
-                         BaEdgeIn ein, int fused, const int32_t *__restrict__ dyn, int opt_window) {
+                         BaEdgeIn ein, const int32_t *__restrict__ dyn, int opt_window) {
   ba_dyn_window(dyn, opt_window, ein.t0, ein.N);
-  __shared__ __attribute__((aligned(16))) float s_buf[BA_PBATCH * BA_REC];     // one array for both roles (16 KB)
+  __shared__ __attribute__((aligned(16))) float s_buf[BA_PBATCH * BA_REC];     // one array for both roles (6 KB)
   static_assert(BA_PBATCH * BA_REC >= BA_PCHUNK * (BA_REC + 1) && BA_PBATCH <= 256, "role buffers / one thread per record");
   if ((int)blockIdx.x < n_patch)
-    ba_patch_body(blockIdx.x, rec, order_k, seg_k, nk, lmbda, Erow, Cv, uv, Qv, n6, ein, fused != 0, s_buf);
+    ba_patch_body<true>(blockIdx.x, nullptr, order_k, seg_k, nk, lmbda, Erow, Cv, uv, Qv, n6, ein, s_buf);
   else
-    ba_pair_body(blockIdx.x - n_patch, rec, order_p, seg_p, np, pairs, pair_ij, ein, fused != 0, s_buf);
+    ba_pair_body(blockIdx.x - n_patch, order_p, seg_p, np, pairs, pair_ij, ein, s_buf);
 }
 
 // ------------------------------------------------------------------ K4
@@ -687,81 +678,95 @@ __global__ void __launch_bounds__(256)
 // Single workgroup, matrix in LDS, blocked Cholesky (block width 6 = one pose).  Per block column every thread factors the 6 x 6 diagonal block in
 // REGISTERS (21 broadcast LDS reads, then no LDS traffic inside the dependency chain: with the block left in LDS the
 // loads cannot move above the stores and every one of them is an exposed round trip), the row threads solve their
-// panel row against it, and the whole workgroup applies the rank-6 update to the trailing matrix on a TG x TG thread
-// grid -- two barriers per pose instead of one per column.  The right-hand side rides along as row n6 (z = L^-1 y
-// falls out of the panel solves); the back substitution is blocked the same way.
-// the factorisation and the solve on a matrix that is already in LDS (A: (n6 + 1) x ld, lower triangle + the rhs as row n6;
-// every thread of the workgroup calls it)
-template <int TG>
-__device__ __forceinline__ void ba_cholb_body(float *__restrict__ A, float *__restrict__ xv, float *__restrict__ Lk,
-                                              float *__restrict__ dX, int32_t *__restrict__ info, int n6) {
+// panel row against it, and the whole workgroup applies the rank-6 update to the trailing matrix on a BA_TG x BA_TG thread
+// grid -- two barriers per pose instead of one per column.  In the solver the right-hand side rides along as row n6
+// (z = L^-1 y falls out of the panel solves) and the back substitution is blocked the same way; the covariance factors
+// the same matrix without that row and inverts L in place.
+#define BA_TG 32      // the workgroup is BA_TG x BA_TG = 1024 threads
+
+// S ([n6][n6] in memory) into LDS rows of stride ld; every thread of the workgroup calls it
+__device__ __forceinline__ void ba_stage_S(float *__restrict__ A, const float *__restrict__ S, int n6, int ld) {
+  const int tid = threadIdx.x, nt = BA_TG * BA_TG;
+  int r = tid / n6, c = tid - r * n6;          // one division, then stepping
+  const int dr = nt / n6, dc = nt - dr * n6;
+  for (int q = tid; q < n6 * n6; q += nt) {
+    A[r * ld + c] = S[q];
+    r += dr; c += dc;
+    if (c >= n6) { c -= n6; r++; }
+  }
+}
+
+// S = L L' in place on a matrix that is already in LDS (A: (n6 + RHS) x ld, lower triangle; with RHS the right-hand side
+// is row n6 and leaves as z = L^-1 y).  Lk [n6 / 6][28] takes the factored diagonal blocks (21 lower entries + 6 inverse
+// pivots), *s_bad is set where a pivot is not positive.  Every thread of the workgroup calls it; it ends on a barrier.
+template <int RHS>
+__device__ __forceinline__ void ba_chol_factor(float *__restrict__ A, float *__restrict__ Lk, int *s_bad, int n6) {
   const int ld = n6 + 1;
-  __shared__ int s_bad;
-  const int tid = threadIdx.x, nt = TG * TG;
-  const int ty = tid / TG, tx = tid % TG;
-  if (tid == 0) s_bad = 0;
+  const int tid = threadIdx.x, nt = BA_TG * BA_TG;
+  const int ty = tid / BA_TG, tx = tid % BA_TG;
+  if (tid == 0) *s_bad = 0;
   __syncthreads();
   const int nb = n6 / 6;
   for (int kb = 0; kb < nb; kb++) {
     const int c0 = 6 * kb;
-    const int r0 = c0 + 6, m = n6 - r0;        // m trailing columns, m + 1 rows (rhs)
-    // only the waves that own a panel row factor the block (tid 0 is one of them: row n6 always exists)
-    if ((tid & ~63) <= m) {
-    float l[6][6], li[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-      for (int j = 0; j <= i; j++) l[i][j] = A[(c0 + i) * ld + c0 + j];
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-      float d = l[j][j];
-#pragma unroll
-      for (int k = 0; k < j; k++) d = __builtin_fmaf(-l[j][k], l[j][k], d);
-      bad |= !(d > 0.0f);
-      li[j] = __builtin_amdgcn_rsqf(d);          // v_rsq_f32, 1 ulp; d is O(1..1e6) here, no denormal range
-      l[j][j] = d * li[j];
-#pragma unroll
-      for (int i = j + 1; i < 6; i++) {
-        float t = l[i][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) t = __builtin_fmaf(-l[i][k], l[j][k], t);
-        l[i][j] = t * li[j];
-      }
-    }
-    if (tid == 0) {
-      int q = 0;
+    const int r0 = c0 + 6, m = n6 - r0;        // m trailing columns, m + RHS rows
+    // only the waves that own a panel row factor the block (and the wave of tid 0, which writes Lk)
+    if ((tid & ~63) < max(m + RHS, 1)) {
+      float l[6][6], li[6];
 #pragma unroll
       for (int i = 0; i < 6; i++)
 #pragma unroll
-        for (int j = 0; j <= i; j++) Lk[kb * 28 + q++] = l[i][j];
-#pragma unroll
-      for (int j = 0; j < 6; j++) Lk[kb * 28 + 21 + j] = li[j];
-      if (bad) s_bad = 1;
-    }
-    // panel: rows below the block (and the rhs row n6): X L_kk' = A_ik  ->  forward substitution along the row
-    for (int i = c0 + 6 + tid; i <= n6; i += nt) {
-      float x[6];
-#pragma unroll
-      for (int j = 0; j < 6; j++) x[j] = A[i * ld + c0 + j];
+        for (int j = 0; j <= i; j++) l[i][j] = A[(c0 + i) * ld + c0 + j];
+      bool bad = false;
 #pragma unroll
       for (int j = 0; j < 6; j++) {
+        float d = l[j][j];
 #pragma unroll
-        for (int k = 0; k < j; k++) x[j] = __builtin_fmaf(-x[k], l[j][k], x[j]);
-        x[j] *= li[j];
+        for (int k = 0; k < j; k++) d = __builtin_fmaf(-l[j][k], l[j][k], d);
+        bad |= !(d > 0.0f);
+        li[j] = __builtin_amdgcn_rsqf(d);          // v_rsq_f32, 1 ulp; d is O(1..1e6) here, no denormal range
+        l[j][j] = d * li[j];
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+          float t = l[i][j];
+#pragma unroll
+          for (int k = 0; k < j; k++) t = __builtin_fmaf(-l[i][k], l[j][k], t);
+          l[i][j] = t * li[j];
+        }
       }
+      if (tid == 0) {
+        int q = 0;
 #pragma unroll
-      for (int j = 0; j < 6; j++) A[i * ld + c0 + j] = x[j];
-    }
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+          for (int j = 0; j <= i; j++) Lk[kb * 28 + q++] = l[i][j];
+#pragma unroll
+        for (int j = 0; j < 6; j++) Lk[kb * 28 + 21 + j] = li[j];
+        if (bad) *s_bad = 1;
+      }
+      // panel: rows below the block (the rhs row among them): X L_kk' = A_ik  ->  forward substitution along the row
+      for (int i = r0 + tid; i < n6 + RHS; i += nt) {
+        float x[6];
+#pragma unroll
+        for (int j = 0; j < 6; j++) x[j] = A[i * ld + c0 + j];
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+#pragma unroll
+          for (int k = 0; k < j; k++) x[j] = __builtin_fmaf(-x[k], l[j][k], x[j]);
+          x[j] *= li[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 6; j++) A[i * ld + c0 + j] = x[j];
+      }
     }
     __syncthreads();
-    // trailing update: A[i][j] -= sum_k L[i][c0+k] L[j][c0+k],  c0 + 6 <= j <= i <= n6,  j < n6
-    for (int ii = ty; ii <= m; ii += TG) {
+    // trailing update: A[i][j] -= sum_k L[i][c0+k] L[j][c0+k],  r0 <= j <= i < n6 + RHS,  j < n6
+    for (int ii = ty; ii < m + RHS; ii += BA_TG) {
       float ri[6];
 #pragma unroll
       for (int k = 0; k < 6; k++) ri[k] = A[(r0 + ii) * ld + c0 + k];
-      const int jmax = ii < m - 1 ? ii : m - 1;
-      for (int jj = tx; jj <= jmax; jj += TG) {
+      const int jmax = RHS ? min(ii, m - 1) : ii;    // (the rhs row stops in front of its own column)
+      for (int jj = tx; jj <= jmax; jj += BA_TG) {
         const float *rj = A + (r0 + jj) * ld + c0;
         float t = A[(r0 + ii) * ld + r0 + jj];
 #pragma unroll
@@ -771,12 +776,23 @@ __device__ __forceinline__ void ba_cholb_body(float *__restrict__ A, float *__re
     }
     __syncthreads();
   }
+}
+
+// the solve on a matrix that is already in LDS (A: (n6 + 1) x ld, lower triangle + the rhs as row n6; every thread of the
+// workgroup calls it)
+__device__ __forceinline__ void ba_cholb_body(float *__restrict__ A, float *__restrict__ xv, float *__restrict__ Lk,
+                                              float *__restrict__ dX, int32_t *__restrict__ info, int n6) {
+  const int ld = n6 + 1;
+  __shared__ int s_bad;
+  const int tid = threadIdx.x, nt = BA_TG * BA_TG;
+  const int nb = n6 / 6;
+  ba_chol_factor<1>(A, Lk, &s_bad, n6);
   const bool bad = s_bad != 0;
   if (bad && tid == 0 && info) atomicOr(info, 1);
   // L' x = z (z = row n6), block by block from the bottom
   if (n6 <= 64) {
     // one wave, no barriers: lane i keeps z_i; a block's six unknowns are solved by every lane (uniform work on broadcast
-    // values), then lane i < c0 takes them out of its z_i -- the blocked loop below operation for operation
+    // values), then lane i < c0 takes them out of its z_i -- per z_i the fma chain of the blocked loop below
     if (tid < 64) {
       float z = tid < n6 ? A[n6 * ld + tid] : 0.0f;
       for (int kb = nb - 1; kb >= 0; kb--) {
@@ -844,8 +860,7 @@ __device__ __forceinline__ void ba_cholb_body(float *__restrict__ A, float *__re
   if (!bad && s_nf != 0 && tid == 0 && info) atomicOr(info, 1);
   for (int q = tid; q < n6; q += nt) dX[q] = drop ? 0.0f : xv[q];
 }
-template <int TG>
-__global__ void __launch_bounds__(TG * TG)
+__global__ void __launch_bounds__(BA_TG * BA_TG)
     ba_cholb_kernel(const float *__restrict__ S, const float *__restrict__ yv,
                     float *__restrict__ dX, int32_t *__restrict__ info, int n6) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -853,18 +868,9 @@ __global__ void __launch_bounds__(TG * TG)
   float *A = sm;                               // (n6 + 1) x ld: rows 0..n6-1 = S (lower triangle), row n6 = y
   float *xv = sm + (n6 + 1) * ld;              // n6: solution
   float *Lk = xv + n6;                         // nb x 28: the factored diagonal blocks (21 lower entries + 6 inverses)
-  const int tid = threadIdx.x, nt = TG * TG;
-  {
-    int r = tid / n6, c = tid - r * n6;        // one division, then stepping
-    const int dr = nt / n6, dc = nt - dr * n6;
-    for (int q = tid; q < n6 * n6; q += nt) {
-      A[r * ld + c] = S[q];
-      r += dr; c += dc;
-      if (c >= n6) { c -= n6; r++; }
-    }
-  }
-  for (int q = tid; q < n6; q += nt) A[n6 * ld + q] = yv[q];
-  ba_cholb_body<TG>(A, xv, Lk, dX, info, n6);
+  ba_stage_S(A, S, n6, ld);
+  for (int q = threadIdx.x; q < n6; q += BA_TG * BA_TG) A[n6 * ld + q] = yv[q];
+  ba_cholb_body(A, xv, Lk, dX, info, n6);
 }
 
 // ------------------------------------------------------------------ K7
@@ -875,11 +881,7 @@ __global__ void __launch_bounds__(256)
                       const int64_t *__restrict__ kx, const int32_t *__restrict__ ngroups,
                       int n6, int PP, int t0, int N, int depth_blocks, const int32_t *__restrict__ dyn,
                       int opt_window) {
-  if (dyn) {
-    const int t1 = dyn[RAMP_DYN_N];
-    t0 = max(t1 - opt_window, 1);
-    N = min(N, t1 - t0);
-  }
+  ba_dyn_window(dyn, opt_window, t0, N);
   if ((int)blockIdx.x >= depth_blocks) {
     // pose retraction (ba_cuda.cu:178-206)
     const int i = (blockIdx.x - depth_blocks) * blockDim.x + threadIdx.x;
@@ -915,8 +917,8 @@ __global__ void __launch_bounds__(256)
 // ------------------------------------------------------------------ uncertainty of the window (ramp_ba_covariance)
 // cov = S^-1 and depth_var_k = Q_k + Q_k^2 |L^-1 e_k|^2 from the system K1 .. K5 assemble (S = L L', damping included: the
 // system the step is solved with).  Two kernels of their own:
-//   C1  one workgroup: S in LDS (ld = n6 + 1), the blocked 6-wide Cholesky of K6 (restated without the right-hand side:
-//       ba_cholb_kernel is untouched), then L^-1 IN PLACE, block row by block row from the top: row block I of L^-1 is
+//   C1  one workgroup: S in LDS (ld = n6 + 1), K6's factorisation (ba_chol_factor without the right-hand side row: the
+//       same function, so the same L), then L^-1 IN PLACE, block row by block row from the top: row block I of L^-1 is
 //       -L_II^-1 (L_I,<I  X_<I) with X_<I the rows already inverted above it -- one thread per column keeps the six sums in
 //       registers (the L row block is read as LDS broadcasts, the X column walk is conflict-free with the odd ld), a barrier,
 //       then the rows are overwritten.  n6 (n6 + 1) + 28 n6 / 6 floats: 148 KB at n6 = 192, inside the 160 KB of a CU.
@@ -925,8 +927,7 @@ __global__ void __launch_bounds__(256)
 //       the patch's chi2 / valid-factor partial over its edge segment, summed in segment order
 //   C3  one workgroup: chi2 and the valid count from the per-patch partials, in group order
 // No float atomics; every sum is an fma chain or an ordered sum: the outputs are the same bits from call to call.
-template <int TG>
-__global__ void __launch_bounds__(TG * TG)
+__global__ void __launch_bounds__(BA_TG * BA_TG)
     ba_cholinv_kernel(const float *__restrict__ S, float *__restrict__ Linv, float *__restrict__ LinvT,
                       int32_t *__restrict__ flag, int32_t *__restrict__ info, int n6) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -934,86 +935,11 @@ __global__ void __launch_bounds__(TG * TG)
   float *A = sm;                               // n6 x ld
   float *Lk = sm + n6 * ld;                    // nb x 28: the factored diagonal blocks (21 lower entries + 6 inverses)
   __shared__ int s_bad, s_nf;
-  const int tid = threadIdx.x, nt = TG * TG;
-  const int ty = tid / TG, tx = tid % TG;
-  {
-    int r = tid / n6, c = tid - r * n6;
-    const int dr = nt / n6, dc = nt - dr * n6;
-    for (int q = tid; q < n6 * n6; q += nt) {
-      A[r * ld + c] = S[q];
-      r += dr; c += dc;
-      if (c >= n6) { c -= n6; r++; }
-    }
-  }
-  if (tid == 0) { s_bad = 0; s_nf = 0; }
-  __syncthreads();
+  const int tid = threadIdx.x, nt = BA_TG * BA_TG;
   const int nb = n6 / 6;
-  // ---- S = L L' (K6's factorisation, operation for operation, without the rhs row)
-  for (int kb = 0; kb < nb; kb++) {
-    const int c0 = 6 * kb;
-    const int r0 = c0 + 6, m = n6 - r0;        // m trailing rows / columns
-    if ((tid & ~63) < max(m, 1)) {
-      float l[6][6], li[6];
-#pragma unroll
-      for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) l[i][j] = A[(c0 + i) * ld + c0 + j];
-      bool bad = false;
-#pragma unroll
-      for (int j = 0; j < 6; j++) {
-        float d = l[j][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) d = __builtin_fmaf(-l[j][k], l[j][k], d);
-        bad |= !(d > 0.0f);
-        li[j] = __builtin_amdgcn_rsqf(d);
-        l[j][j] = d * li[j];
-#pragma unroll
-        for (int i = j + 1; i < 6; i++) {
-          float t = l[i][j];
-#pragma unroll
-          for (int k = 0; k < j; k++) t = __builtin_fmaf(-l[i][k], l[j][k], t);
-          l[i][j] = t * li[j];
-        }
-      }
-      if (tid == 0) {
-        int q = 0;
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-#pragma unroll
-          for (int j = 0; j <= i; j++) Lk[kb * 28 + q++] = l[i][j];
-#pragma unroll
-        for (int j = 0; j < 6; j++) Lk[kb * 28 + 21 + j] = li[j];
-        if (bad) s_bad = 1;
-      }
-      for (int i = r0 + tid; i < n6; i += nt) {
-        float x[6];
-#pragma unroll
-        for (int j = 0; j < 6; j++) x[j] = A[i * ld + c0 + j];
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-#pragma unroll
-          for (int k = 0; k < j; k++) x[j] = __builtin_fmaf(-x[k], l[j][k], x[j]);
-          x[j] *= li[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 6; j++) A[i * ld + c0 + j] = x[j];
-      }
-    }
-    __syncthreads();
-    for (int ii = ty; ii < m; ii += TG) {
-      float ri[6];
-#pragma unroll
-      for (int k = 0; k < 6; k++) ri[k] = A[(r0 + ii) * ld + c0 + k];
-      for (int jj = tx; jj <= ii; jj += TG) {
-        const float *rj = A + (r0 + jj) * ld + c0;
-        float t = A[(r0 + ii) * ld + r0 + jj];
-#pragma unroll
-        for (int k = 0; k < 6; k++) t = __builtin_fmaf(-ri[k], rj[k], t);
-        A[(r0 + ii) * ld + r0 + jj] = t;
-      }
-    }
-    __syncthreads();
-  }
+  ba_stage_S(A, S, n6, ld);
+  if (tid == 0) s_nf = 0;
+  ba_chol_factor<0>(A, Lk, &s_bad, n6);
   // ---- X = L^-1 in place, block row by block row
   for (int kb = 0; kb < nb; kb++) {
     const int c0 = 6 * kb;
@@ -1250,97 +1176,78 @@ static size_t ba_carve(void *ws, int E, int n_poses, int n_patches, int N, int o
   return off;
 }
 
-// the GN iterations, given the two groupings
-static int ba_iterate(float *poses, float *patches, const float *intrinsics, const float *target,
-                      const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
-                      const int64_t *kk, int E, int P, int t0, int t1, int iterations, BaWs &w,
-                      const int32_t *order_k, const int32_t *seg_k, const int32_t *nk, const int64_t *kx,
-                      const int32_t *order_p, const int32_t *seg_p, const int32_t *np, int32_t *info,
-                      hipStream_t st, const int32_t *dyn = nullptr, int opt_window = 0) {
-  const int N = t1 - t0, n6 = 6 * N;
-  const size_t lds = (size_t)((n6 + 1) * (n6 + 1) + 6 * n6) * sizeof(float);
-  const int PP = P * P, c11 = 1 * P + 1;
-  if (N > 0 && lds > 64 * 1024) {
-    // (per call: the attribute is per device, and a process may drive several)
-    if (hipFuncSetAttribute((const void *)ba_cholb_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return RAMP_ELAUNCH;
-  }
-  const int pthreads = ((n6 + 2 + 63) / 64) * 64;
+static BaEdgeIn ba_edge_in(const BaProblem &p) {
+  BaEdgeIn e;
+  e.poses = p.poses; e.patches = p.patches; e.intr = p.intrinsics; e.target = p.target; e.weight = p.weight;
+  e.ii = p.ii; e.jj = p.jj; e.kk = p.kk; e.PP = p.P * p.P; e.c11 = 1 * p.P + 1; e.t0 = p.t0; e.N = p.t1 - p.t0;
+  return e;
+}
+
+// the single-workgroup kernels keep their matrix in LDS: above 64 KB the kernel has to be told
+// (per call: the attribute is per device, and a process may drive several)
+static int ba_allow_lds(const void *kernel, size_t lds) {
+  if (lds > 160 * 1024) return RAMP_EUNSUPPORTED;
+  if (lds > 64 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return RAMP_ELAUNCH;
+  return RAMP_OK;
+}
+
+// K1 .. K5: the system at the state p.  E row, C, u, Q per patch; with free poses also the pair records, the split-K
+// partials and S, y (w.S, w.yv).  The solver runs it once per iteration, the covariance once.
+static int ba_build_system(const BaProblem &p, const BaGroups &g, BaWs &w, int32_t *info, hipStream_t st) {
+  const int N = p.t1 - p.t0, n6 = 6 * N;
+  const int pthreads = ((n6 + 2 + 63) / 64) * 64;      // a patch's workgroup: one thread per column of its E row, C and u
   if (pthreads > 256) return RAMP_EUNSUPPORTED;
+  const BaEdgeIn ein = ba_edge_in(p);
+  if (N <= 0) {
+    // no free pose: only K2 has anything to do, on records that go through memory
+    hipLaunchKernelGGL(ba_edge_kernel, dim3(ramp_cdiv(p.E, 256)), dim3(256), 0, st, ein, w.rec, p.E, p.dyn, p.opt_window);
+    hipLaunchKernelGGL(ba_patch_kernel, dim3(w.Mu_b), dim3(pthreads), 0, st, w.rec, g.order_k, g.seg_k, g.ngroups_k,
+                       p.lmbda, w.Erow, w.Cv, w.uv, w.Qv, n6);
+    return RAMP_OK;
+  }
+  hipLaunchKernelGGL(ba_patch_pair_kernel, dim3(w.Mu_b + w.Gp_b), dim3(256), 0, st, w.Mu_b, g.order_k, g.seg_k,
+                     g.ngroups_k, p.lmbda, w.Erow, w.Cv, w.uv, w.Qv, n6, g.order_p, g.seg_p, g.ngroups_p, w.pairs,
+                     w.pair_ij, ein, p.dyn, p.opt_window);
+  // (one workgroup per split-K slice where the system is a single tile; N x N assembly workgroups up to 16 poses, one per
+  // pose above -- the interleaved order of the former moves a 180 x 180 solve by 6e-4 of the step)
+  if (w.tiles == 1 && ramp_cdiv(w.Mu_b, w.KS) <= BA_S1_ROWS)
+    hipLaunchKernelGGL(ba_schur1_kernel, dim3(1, 1, w.KS), dim3(256), 0, st, w.Erow, w.Qv, w.uv, g.ngroups_k, w.S_part,
+                       w.y_part, n6, w.KS);
+  else
+    hipLaunchKernelGGL(ba_schur_kernel, dim3(w.tiles, w.tiles, w.KS), dim3(256), 0, st, w.Erow, w.Qv, w.uv, g.ngroups_k,
+                       w.S_part, w.y_part, n6, w.KS);
+  if (N <= 16)
+    hipLaunchKernelGGL(ba_assemble2_kernel, dim3(N, N), dim3(256), 0, st, w.pairs, w.pair_ij, g.ngroups_p, w.S_part,
+                       w.y_part, w.S, w.yv, n6, w.KS, info);
+  else
+    hipLaunchKernelGGL(ba_assemble_kernel, dim3(N, ramp_cdiv(6 * n6, 192)), dim3(256), 0, st, w.pairs, w.pair_ij,
+                       g.ngroups_p, w.S_part, w.y_part, w.S, w.yv, n6, w.KS, info);
+  return RAMP_OK;
+}
+
+// the GN iterations, given the two groupings
+static int ba_iterate(const BaProblem &p, const BaGroups &g, int iterations, BaWs &w, int32_t *info, hipStream_t st) {
+  const int N = p.t1 - p.t0, n6 = 6 * N;
+  const size_t lds = (size_t)((n6 + 1) * (n6 + 1) + 6 * n6) * sizeof(float);
+  int rc = ba_allow_lds((const void *)ba_cholb_kernel, lds);
+  if (rc != RAMP_OK) return rc;
   const int depth_blocks = ramp_cdiv(w.Mu_b, 4);
   const int pose_blocks = N > 0 ? ramp_cdiv(N, 256) : 0;
-  BaEdgeIn ein;
-  ein.poses = poses; ein.patches = patches; ein.intr = intrinsics; ein.target = target; ein.weight = weight;
-  ein.ii = ii; ein.jj = jj; ein.kk = kk; ein.PP = PP; ein.c11 = c11; ein.t0 = t0; ein.N = N;
-  const int fuse_edge = 1;       // the per-factor records are recomputed in registers by the patch / pair kernel (no [E][32] rows through memory)
   for (int itr = 0; itr < iterations; itr++) {
-    if (N <= 0)
-      hipLaunchKernelGGL(ba_edge_kernel, dim3(ramp_cdiv(E, 256)), dim3(256), 0, st, ein, w.rec, E, dyn, opt_window);
-    if (N > 0)
-      hipLaunchKernelGGL(ba_patch_pair_kernel, dim3(w.Mu_b + w.Gp_b), dim3(256), 0, st, w.Mu_b, w.rec, order_k,
-                         seg_k, nk, lmbda, w.Erow, w.Cv, w.uv, w.Qv, n6, order_p, seg_p, np, w.pairs, w.pair_ij, ein,
-                         fuse_edge, dyn, opt_window);
-    else
-      hipLaunchKernelGGL(ba_patch_kernel, dim3(w.Mu_b), dim3(pthreads), 0, st, w.rec, order_k, seg_k, nk,
-                         lmbda, w.Erow, w.Cv, w.uv, w.Qv, n6);
-    if (N > 0) {
-      // (one workgroup per split-K slice where the system is a single tile; N x N assembly workgroups up to 16 poses, one per
-      // pose above -- the interleaved order of the former moves a 180 x 180 solve by 6e-4 of the step)
-      if (w.tiles == 1 && ramp_cdiv(w.Mu_b, w.KS) <= BA_S1_ROWS)
-        hipLaunchKernelGGL(ba_schur1_kernel, dim3(1, 1, w.KS), dim3(256), 0, st, w.Erow, w.Qv, w.uv, nk, w.S_part, w.y_part,
-                           n6, w.KS);
-      else
-        hipLaunchKernelGGL(ba_schur_kernel, dim3(w.tiles, w.tiles, w.KS), dim3(256), 0, st, w.Erow,
-                           w.Qv, w.uv, nk, w.S_part, w.y_part, n6, w.KS);
-      if (N <= 16)
-        hipLaunchKernelGGL(ba_assemble2_kernel, dim3(N, N), dim3(256), 0, st, w.pairs, w.pair_ij, np, w.S_part, w.y_part,
-                           w.S, w.yv, n6, w.KS, info);
-      else
-        hipLaunchKernelGGL(ba_assemble_kernel, dim3(N, ramp_cdiv(6 * n6, 192)), dim3(256), 0, st, w.pairs, w.pair_ij, np,
-                           w.S_part, w.y_part, w.S, w.yv, n6, w.KS, info);
-      hipLaunchKernelGGL(ba_cholb_kernel<32>, dim3(1), dim3(1024), lds, st, w.S, w.yv, w.dX, info, n6);
-    }
-    hipLaunchKernelGGL(ba_retract_kernel, dim3(depth_blocks + pose_blocks), dim3(256), 0, st,
-                       poses, patches, w.Erow, w.Qv, w.uv, w.dX, kx, nk, n6, PP, t0, N, depth_blocks, dyn, opt_window);
+    if ((rc = ba_build_system(p, g, w, info, st)) != RAMP_OK) return rc;
+    if (N > 0) hipLaunchKernelGGL(ba_cholb_kernel, dim3(1), dim3(BA_TG * BA_TG), lds, st, w.S, w.yv, w.dX, info, n6);
+    hipLaunchKernelGGL(ba_retract_kernel, dim3(depth_blocks + pose_blocks), dim3(256), 0, st, p.poses, p.patches, w.Erow,
+                       w.Qv, w.uv, w.dX, g.ukeys_k, g.ngroups_k, n6, p.P * p.P, p.t0, N, depth_blocks, p.dyn, p.opt_window);
     RAMP_CHECK_LAUNCH();
   }
   return RAMP_OK;
 }
 
-static int ba_check_args(int E, int P, int n_poses, int n_patches, int t0, int t1, int iterations) {
-  if (E < 0 || P < 2 || n_poses <= 0 || n_patches <= 0 || iterations < 0) return RAMP_EINVAL;
-  if (t0 < 0 || t1 < t0 || t1 > n_poses) return RAMP_EINVAL;
-  const int n6 = 6 * (t1 - t0);
-  if ((size_t)((n6 + 1) * (n6 + 1) + 2 * n6) * sizeof(float) > 160 * 1024) return RAMP_EUNSUPPORTED;  // > 32 free poses
-  return RAMP_OK;
-}
-
-// ---- device-side sizes (csrc/track.hip): the window [max(n - opt_window, 1), n) with n = dyn[RAMP_DYN_N] and the
-// factor count dyn[RAMP_DYN_E] are read by the kernels; E_cap bounds the launches, the system has opt_window poses.
-// Status bits accumulate in *info (not cleared here).
-size_t ramp_i_ba_dyn_ws(int E_cap, int n_poses, int n_patches, int opt_window, int max_patches, int max_pairs) {
-  BaWs w;
-  return ba_carve(nullptr, E_cap, n_poses, n_patches, opt_window, 0, max_patches, max_pairs, &w);
-}
-int ramp_i_ba_dyn(float *poses, float *patches, const float *intrinsics, const float *target, const float *weight,
-                  const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk, int E_cap, int P,
-                  int n_poses, int n_patches, int opt_window, int iterations, const int32_t *order_k,
-                  const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
-                  const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs, void *ws,
-                  size_t ws_bytes, int32_t *info, const int32_t *dyn, hipStream_t st) {
-  if (E_cap <= 0 || opt_window <= 0 || !dyn || !ws) return RAMP_EINVAL;
-  int rc = ba_check_args(E_cap, P, n_poses, n_patches, 1, 1 + opt_window, iterations);
-  if (rc != RAMP_OK) return rc;
-  BaWs w;
-  if (ba_carve(ws, E_cap, n_poses, n_patches, opt_window, 0, max_patches, max_pairs, &w) > ws_bytes)
-    return RAMP_EWORKSPACE;
-  return ba_iterate(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E_cap, P, 1, 1 + opt_window,
-                    iterations, w, order_k, seg_k, ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, info, st, dyn,
-                    opt_window);
-}
-
 // ---- uncertainty: the system of ONE iteration at the state passed in, no step taken (nothing retracts)
 struct BaCovWs { float *Linv, *LinvT, *cpart; int32_t *npart, *flag; };
+// what a covariance call writes; ws: its own workspace (the dyn form), or nullptr: the buffers follow BA's in the call's
+struct BaCovOut { float *cov, *depth_var, *stats; void *ws; size_t ws_bytes; };
 static size_t ba_cov_carve(void *ws, int n6, int Mu_b, BaCovWs *c) {
   size_t off = 0;
   char *base = (char *)ws;
@@ -1352,199 +1259,173 @@ static size_t ba_cov_carve(void *ws, int n6, int Mu_b, BaCovWs *c) {
   c->flag = (int32_t *)take(64);
   return off;
 }
-static int ba_cov_run(const float *poses, const float *patches, const float *intrinsics, const float *target,
-                      const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk,
-                      int E, int P, int t0, int t1, BaWs &w, BaCovWs &c, const int32_t *order_k, const int32_t *seg_k,
-                      const int32_t *nk, const int64_t *kx, const int32_t *order_p, const int32_t *seg_p, const int32_t *np,
-                      int32_t *info, float *cov, float *depth_var, float *stats, hipStream_t st,
-                      const int32_t *dyn = nullptr, int opt_window = 0) {
-  const int N = t1 - t0, n6 = 6 * N;
+static int ba_cov_run(const BaProblem &p, const BaGroups &g, BaWs &w, BaCovWs &c, const BaCovOut &out, int32_t *info,
+                      hipStream_t st) {
+  const int N = p.t1 - p.t0, n6 = 6 * N;
   const size_t lds = (size_t)(n6 * (n6 + 1) + (n6 / 6) * 28) * sizeof(float);
-  if (lds > 160 * 1024) return RAMP_EUNSUPPORTED;
-  const int PP = P * P, c11 = 1 * P + 1;
-  if (N > 0 && lds > 64 * 1024) {
-    if (hipFuncSetAttribute((const void *)ba_cholinv_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return RAMP_ELAUNCH;
-  }
-  const int pthreads = ((n6 + 2 + 63) / 64) * 64;
-  if (pthreads > 256) return RAMP_EUNSUPPORTED;
-  BaEdgeIn ein;
-  ein.poses = poses; ein.patches = patches; ein.intr = intrinsics; ein.target = target; ein.weight = weight;
-  ein.ii = ii; ein.jj = jj; ein.kk = kk; ein.PP = PP; ein.c11 = c11; ein.t0 = t0; ein.N = N;
+  int rc = ba_allow_lds((const void *)ba_cholinv_kernel, lds);
+  if (rc != RAMP_OK) return rc;
   if (hipMemsetAsync(c.flag, 0, sizeof(int32_t), st) != hipSuccess) return RAMP_ELAUNCH;
-  if (N > 0) {
-    // K2 .. K5 exactly as an iteration of ba_iterate launches them
-    hipLaunchKernelGGL(ba_patch_pair_kernel, dim3(w.Mu_b + w.Gp_b), dim3(256), 0, st, w.Mu_b, w.rec, order_k, seg_k, nk,
-                       lmbda, w.Erow, w.Cv, w.uv, w.Qv, n6, order_p, seg_p, np, w.pairs, w.pair_ij, ein, 1, dyn, opt_window);
-    if (w.tiles == 1 && ramp_cdiv(w.Mu_b, w.KS) <= BA_S1_ROWS)
-      hipLaunchKernelGGL(ba_schur1_kernel, dim3(1, 1, w.KS), dim3(256), 0, st, w.Erow, w.Qv, w.uv, nk, w.S_part, w.y_part,
-                         n6, w.KS);
-    else
-      hipLaunchKernelGGL(ba_schur_kernel, dim3(w.tiles, w.tiles, w.KS), dim3(256), 0, st, w.Erow, w.Qv, w.uv, nk,
-                         w.S_part, w.y_part, n6, w.KS);
-    if (N <= 16)
-      hipLaunchKernelGGL(ba_assemble2_kernel, dim3(N, N), dim3(256), 0, st, w.pairs, w.pair_ij, np, w.S_part, w.y_part,
-                         w.S, w.yv, n6, w.KS, info);
-    else
-      hipLaunchKernelGGL(ba_assemble_kernel, dim3(N, ramp_cdiv(6 * n6, 192)), dim3(256), 0, st, w.pairs, w.pair_ij, np,
-                         w.S_part, w.y_part, w.S, w.yv, n6, w.KS, info);
-    hipLaunchKernelGGL(ba_cholinv_kernel<32>, dim3(1), dim3(1024), lds, st, w.S, c.Linv, c.LinvT, c.flag, info, n6);
-  } else {
-    hipLaunchKernelGGL(ba_edge_kernel, dim3(ramp_cdiv(E, 256)), dim3(256), 0, st, ein, w.rec, E, dyn, opt_window);
-    hipLaunchKernelGGL(ba_patch_kernel, dim3(w.Mu_b), dim3(pthreads), 0, st, w.rec, order_k, seg_k, nk, lmbda, w.Erow,
-                       w.Cv, w.uv, w.Qv, n6);
-  }
+  if ((rc = ba_build_system(p, g, w, info, st)) != RAMP_OK) return rc;
+  if (N > 0)
+    hipLaunchKernelGGL(ba_cholinv_kernel, dim3(1), dim3(BA_TG * BA_TG), lds, st, w.S, c.Linv, c.LinvT, c.flag, info, n6);
   const int tiles = ramp_cdiv(n6, BA_CT);
   hipLaunchKernelGGL(ba_cov_expand_kernel, dim3(tiles * tiles + ramp_cdiv(w.Mu_b, 4)), dim3(256), 0, st, c.Linv, c.LinvT,
-                     c.flag, w.Erow, w.Qv, kx, order_k, seg_k, nk, ein, cov, depth_var, c.cpart, c.npart, n6, tiles, w.Mu_b,
-                     dyn, opt_window);
-  hipLaunchKernelGGL(ba_cov_stats_kernel, dim3(1), dim3(256), 0, st, c.cpart, c.npart, nk, c.flag, stats, t0, N, w.Mu_b,
-                     dyn, opt_window);
+                     c.flag, w.Erow, w.Qv, g.ukeys_k, g.order_k, g.seg_k, g.ngroups_k, ba_edge_in(p), out.cov,
+                     out.depth_var, c.cpart, c.npart, n6, tiles, w.Mu_b, p.dyn, p.opt_window);
+  hipLaunchKernelGGL(ba_cov_stats_kernel, dim3(1), dim3(256), 0, st, c.cpart, c.npart, g.ngroups_k, c.flag, out.stats,
+                     p.t0, N, w.Mu_b, p.dyn, p.opt_window);
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;
 }
 
+// ---- what the entry points share.  plan == nullptr: the call groups its own factors (room for that is carved);
+// otherwise the groups are the caller's and its bounds size Mu_b / Gp_b.  out == nullptr: solve; otherwise the
+// uncertainty (one system, `iterations` is 1).
+// todo = false with RAMP_OK: a valid call that has nothing to do
+static int ba_check(const BaProblem &p, const BaGroups *plan, int iterations, const BaCovOut *out, const void *ws,
+                    int32_t *info, hipStream_t st, bool &todo) {
+  todo = false;
+  if (p.dyn && (p.E <= 0 || p.opt_window <= 0 || !ws || (out && !out->ws))) return RAMP_EINVAL;
+  if (p.E < 0 || p.P < 2 || p.n_poses <= 0 || p.n_patches <= 0 || iterations < 0) return RAMP_EINVAL;
+  if (p.t0 < 0 || p.t1 < p.t0 || p.t1 > p.n_poses) return RAMP_EINVAL;
+  const int n6 = 6 * (p.t1 - p.t0);
+  if ((size_t)((n6 + 1) * (n6 + 1) + 2 * n6) * sizeof(float) > 160 * 1024) return RAMP_EUNSUPPORTED;  // > 32 free poses
+  if (out && p.E == 0) return RAMP_EINVAL;
+  if (info && !p.dyn) (void)hipMemsetAsync(info, 0, sizeof(int32_t), st);     // (the dyn forms accumulate their status bits)
+  if (p.E == 0 || iterations == 0) return RAMP_OK;
+  if (!p.poses || !p.patches || !p.intrinsics || !p.target || !p.weight || !p.lmbda || !p.ii || !p.jj || !p.kk || !ws)
+    return RAMP_EINVAL;
+  if (plan && (!plan->order_k || !plan->seg_k || !plan->ngroups_k || !plan->ukeys_k || !plan->order_p || !plan->seg_p ||
+               !plan->ngroups_p || plan->max_patches <= 0 || plan->max_pairs <= 0))
+    return RAMP_EINVAL;
+  if (out && (!out->depth_var || !out->stats || (p.t1 > p.t0 && !out->cov))) return RAMP_EINVAL;
+  todo = true;
+  return RAMP_OK;
+}
+
+// `ws` carved for the call (the covariance's buffers behind BA's unless the call brings a workspace for them) and checked
+static int ba_carve_checked(void *ws, size_t ws_bytes, const BaProblem &p, const BaGroups *plan, const BaCovOut *out,
+                            BaWs &w, BaCovWs &c) {
+  const int N = p.t1 - p.t0;
+  size_t a = ba_carve(ws, p.E, p.n_poses, p.n_patches, N, !plan, plan ? plan->max_patches : 0, plan ? plan->max_pairs : 0, &w);
+  if (out && out->ws) {
+    if (ba_cov_carve(out->ws, 6 * N, w.Mu_b, &c) > out->ws_bytes) return RAMP_EWORKSPACE;
+  } else if (out) {
+    a += ba_cov_carve((char *)ws + a, 6 * N, w.Mu_b, &c);
+  }
+  return a > ws_bytes ? RAMP_EWORKSPACE : RAMP_OK;
+}
+
+// prep of a call without a plan: group by patch, group by pose pair (the pairs only matter with a free pose)
+static int ba_own_groups(const BaProblem &p, const BaWs &w, BaGroups &g, hipStream_t st) {
+  int32_t *nk = w.counters, *np = w.counters + 1;
+  g = BaGroups{w.order_k, w.seg_k, nk, w.kx, w.order_p, w.seg_p, np, 0, 0};
+  int rc = ramp_internal_group_by(p.kk, p.E, p.n_patches, w.order_k, nullptr, w.seg_k, w.kx, nk, w.gb, w.gb_bytes, st);
+  if (rc != RAMP_OK || p.t1 <= p.t0) return rc;
+  hipLaunchKernelGGL(ba_pairkey_kernel, dim3(ramp_cdiv(p.E, 256)), dim3(256), 0, st, p.ii, p.jj, w.pkeys, p.E,
+                     (long long)p.n_poses);
+  return ramp_internal_group_by(w.pkeys, p.E, (int64_t)p.n_poses * p.n_poses, w.order_p, nullptr, w.seg_p, w.pukeys, np,
+                                w.gb, w.gb_bytes, st);
+}
+
+static int ba_run(const BaProblem &p, const BaGroups *plan, int iterations, const BaCovOut *out, void *ws,
+                  size_t ws_bytes, int32_t *info, hipStream_t st) {
+  bool todo;
+  int rc = ba_check(p, plan, iterations, out, ws, info, st, todo);
+  if (rc != RAMP_OK || !todo) return rc;
+  BaWs w;
+  BaCovWs c;
+  BaGroups own;
+  if ((rc = ba_carve_checked(ws, ws_bytes, p, plan, out, w, c)) != RAMP_OK) return rc;
+  if (!plan && (rc = ba_own_groups(p, w, own, st)) != RAMP_OK) return rc;
+  const BaGroups &g = plan ? *plan : own;
+  return out ? ba_cov_run(p, g, w, c, *out, info, st) : ba_iterate(p, g, iterations, w, info, st);
+}
+static size_t ba_ws_bytes(int E, int n_poses, int n_patches, int N, int own_groups, int max_patches, int max_pairs, bool cov) {
+  BaWs w;
+  BaCovWs c;
+  if (N < 0) N = 0;
+  const size_t a = ba_carve(nullptr, E, n_poses, n_patches, N, own_groups, max_patches, max_pairs, &w);
+  return cov ? a + ba_cov_carve(nullptr, 6 * N, w.Mu_b, &c) : a;
+}
+
+// ---- device-side sizes (csrc/track.hip): the window [max(n - opt_window, 1), n) with n = dyn[RAMP_DYN_N] and the
+// factor count dyn[RAMP_DYN_E] are read by the kernels; p.E bounds the launches, the system has opt_window poses (a
+// shorter window leaves identity blocks behind it; cov is [6 opt_window]^2).  Status bits accumulate in *info (not
+// cleared here).  p.t0 / p.t1 are set here.
+static BaProblem ba_dyn_problem(BaProblem p) {
+  p.t0 = 1; p.t1 = 1 + p.opt_window;
+  return p;
+}
+size_t ramp_i_ba_dyn_ws(int E_cap, int n_poses, int n_patches, int opt_window, int max_patches, int max_pairs) {
+  return ba_ws_bytes(E_cap, n_poses, n_patches, opt_window, 0, max_patches, max_pairs, false);
+}
+int ramp_i_ba_dyn(const BaProblem &p, const BaGroups &g, int iterations, void *ws, size_t ws_bytes, int32_t *info,
+                  hipStream_t st) {
+  if (!p.dyn) return RAMP_EINVAL;
+  return ba_run(ba_dyn_problem(p), &g, iterations, nullptr, ws, ws_bytes, info, st);
+}
 size_t ramp_i_ba_cov_dyn_ws(int opt_window, int max_patches) {
   BaCovWs c;
   return ba_cov_carve(nullptr, 6 * opt_window, max_patches > 0 ? max_patches : 1, &c);
 }
-// the dyn-sized form: the window and the factor segments come from the `dyn` words and the caller's groups; the system has
-// opt_window poses (a shorter window leaves identity blocks behind it), cov is [6 opt_window]^2.  ba_ws: ramp_i_ba_dyn's.
-int ramp_i_ba_cov_dyn(const float *poses, const float *patches, const float *intrinsics, const float *target,
-                      const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk,
-                      int E_cap, int P, int n_poses, int n_patches, int opt_window, const int32_t *order_k,
-                      const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
-                      const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs, void *ba_ws,
-                      size_t ba_ws_bytes, void *cov_ws, size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var,
-                      float *stats, const int32_t *dyn, hipStream_t st) {
-  if (E_cap <= 0 || opt_window <= 0 || !dyn || !ba_ws || !cov_ws || !cov || !depth_var || !stats) return RAMP_EINVAL;
-  int rc = ba_check_args(E_cap, P, n_poses, n_patches, 1, 1 + opt_window, 1);
-  if (rc != RAMP_OK) return rc;
-  BaWs w;
-  BaCovWs c;
-  if (ba_carve(ba_ws, E_cap, n_poses, n_patches, opt_window, 0, max_patches, max_pairs, &w) > ba_ws_bytes)
-    return RAMP_EWORKSPACE;
-  if (ba_cov_carve(cov_ws, 6 * opt_window, w.Mu_b, &c) > cov_ws_bytes) return RAMP_EWORKSPACE;
-  return ba_cov_run(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E_cap, P, 1, 1 + opt_window, w, c,
-                    order_k, seg_k, ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, info, cov, depth_var, stats, st, dyn,
-                    opt_window);
+// ba_ws: ramp_i_ba_dyn's
+int ramp_i_ba_cov_dyn(const BaProblem &p, const BaGroups &g, void *ba_ws, size_t ba_ws_bytes, void *cov_ws,
+                      size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var, float *stats, hipStream_t st) {
+  if (!p.dyn || !cov_ws) return RAMP_EINVAL;
+  const BaCovOut out = {cov, depth_var, stats, cov_ws, cov_ws_bytes};
+  return ba_run(ba_dyn_problem(p), &g, 1, &out, ba_ws, ba_ws_bytes, info, st);
 }
 
 extern "C" {
 
 size_t ramp_ba_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1) {
-  BaWs w;
-  const int N = t1 - t0 > 0 ? t1 - t0 : 0;
-  return ba_carve(nullptr, E, n_poses, n_patches, N, 1, 0, 0, &w);
+  return ba_ws_bytes(E, n_poses, n_patches, t1 - t0, 1, 0, 0, false);
 }
 
-int ramp_ba_forward(float *poses, float *patches, const float *intrinsics, const float *target,
-                    const float *weight, const float *lmbda, const int64_t *ii,
-                    const int64_t *jj, const int64_t *kk, int E, int P, int n_poses,
-                    int n_patches, int t0, int t1, int iterations, void *ws, size_t ws_bytes,
-                    int32_t *info, void *stream) {
-  int rc = ba_check_args(E, P, n_poses, n_patches, t0, t1, iterations);
-  if (rc != RAMP_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (info) (void)hipMemsetAsync(info, 0, sizeof(int32_t), st);
-  if (E == 0 || iterations == 0) return RAMP_OK;
-  if (!poses || !patches || !intrinsics || !target || !weight || !lmbda || !ii || !jj || !kk || !ws)
-    return RAMP_EINVAL;
-  const int N = t1 - t0;
-  BaWs w;
-  if (ba_carve(ws, E, n_poses, n_patches, N, 1, 0, 0, &w) > ws_bytes) return RAMP_EWORKSPACE;
-  int32_t *nk = w.counters, *np = w.counters + 1;
-  // ---- prep: group by patch, group by pose pair
-  rc = ramp_internal_group_by(kk, E, n_patches, w.order_k, nullptr, w.seg_k, w.kx, nk, w.gb, w.gb_bytes, st);
-  if (rc != RAMP_OK) return rc;
-  if (N > 0) {
-    hipLaunchKernelGGL(ba_pairkey_kernel, dim3(ramp_cdiv(E, 256)), dim3(256), 0, st, ii, jj, w.pkeys, E,
-                       (long long)n_poses);
-    rc = ramp_internal_group_by(w.pkeys, E, (int64_t)n_poses * n_poses, w.order_p, nullptr, w.seg_p,
-                                w.pukeys, np, w.gb, w.gb_bytes, st);
-    if (rc != RAMP_OK) return rc;
-  }
-  return ba_iterate(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P, t0, t1, iterations,
-                    w, w.order_k, w.seg_k, nk, w.kx, w.order_p, w.seg_p, np, info, st);
+int ramp_ba_forward(float *poses, float *patches, const float *intrinsics, const float *target, const float *weight,
+                    const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk, int E, int P, int n_poses,
+                    int n_patches, int t0, int t1, int iterations, void *ws, size_t ws_bytes, int32_t *info, void *stream) {
+  const BaProblem p = {poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P, n_poses, n_patches, t0, t1,
+                       nullptr, 0};
+  return ba_run(p, nullptr, iterations, nullptr, ws, ws_bytes, info, (hipStream_t)stream);
 }
 
-size_t ramp_ba_planned_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1,
-                                       int max_patches, int max_pairs) {
-  BaWs w;
-  const int N = t1 - t0 > 0 ? t1 - t0 : 0;
-  return ba_carve(nullptr, E, n_poses, n_patches, N, 0, max_patches, max_pairs, &w);
+size_t ramp_ba_planned_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1, int max_patches, int max_pairs) {
+  return ba_ws_bytes(E, n_poses, n_patches, t1 - t0, 0, max_patches, max_pairs, false);
 }
 
-int ramp_ba_forward_planned(float *poses, float *patches, const float *intrinsics, const float *target,
-                            const float *weight, const float *lmbda, const int64_t *ii,
-                            const int64_t *jj, const int64_t *kk, int E, int P, int n_poses,
-                            int n_patches, int t0, int t1, int iterations, const int32_t *order_k,
-                            const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k,
-                            int max_patches, const int32_t *order_p, const int32_t *seg_p,
-                            const int32_t *ngroups_p, int max_pairs, void *ws, size_t ws_bytes,
-                            int32_t *info, void *stream) {
-  int rc = ba_check_args(E, P, n_poses, n_patches, t0, t1, iterations);
-  if (rc != RAMP_OK) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (info) (void)hipMemsetAsync(info, 0, sizeof(int32_t), st);
-  if (E == 0 || iterations == 0) return RAMP_OK;
-  if (!poses || !patches || !intrinsics || !target || !weight || !lmbda || !ii || !jj || !kk || !ws ||
-      !order_k || !seg_k || !ngroups_k || !ukeys_k || !order_p || !seg_p || !ngroups_p)
-    return RAMP_EINVAL;
-  if (max_patches <= 0 || max_pairs <= 0) return RAMP_EINVAL;
-  BaWs w;
-  if (ba_carve(ws, E, n_poses, n_patches, t1 - t0, 0, max_patches, max_pairs, &w) > ws_bytes)
-    return RAMP_EWORKSPACE;
-  return ba_iterate(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P, t0, t1, iterations,
-                    w, order_k, seg_k, ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, info, st);
+int ramp_ba_forward_planned(float *poses, float *patches, const float *intrinsics, const float *target, const float *weight,
+                            const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk, int E, int P,
+                            int n_poses, int n_patches, int t0, int t1, int iterations, const int32_t *order_k,
+                            const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
+                            const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs,
+                            void *ws, size_t ws_bytes, int32_t *info, void *stream) {
+  const BaProblem p = {poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P, n_poses, n_patches, t0, t1,
+                       nullptr, 0};
+  const BaGroups g = {order_k, seg_k, ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, max_patches, max_pairs};
+  return ba_run(p, &g, iterations, nullptr, ws, ws_bytes, info, (hipStream_t)stream);
 }
 
 size_t ramp_ba_covariance_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1) {
-  BaWs w;
-  BaCovWs c;
-  const int N = t1 - t0 > 0 ? t1 - t0 : 0;
-  const size_t a = ba_carve(nullptr, E, n_poses, n_patches, N, 1, 0, 0, &w);
-  return a + ba_cov_carve(nullptr, 6 * N, w.Mu_b, &c);
+  return ba_ws_bytes(E, n_poses, n_patches, t1 - t0, 1, 0, 0, true);
 }
 
+// (poses and patches are only read: no retraction runs)
 int ramp_ba_covariance(const float *poses, const float *patches, const float *intrinsics, const float *target,
                        const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
                        const int64_t *kk, int E, int P, int n_poses, int n_patches, int t0, int t1, float *cov,
                        float *depth_var, float *stats, void *ws, size_t ws_bytes, int32_t *info, void *stream) {
-  int rc = ba_check_args(E, P, n_poses, n_patches, t0, t1, 1);
-  if (rc != RAMP_OK) return rc;
-  if (E == 0) return RAMP_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (info) (void)hipMemsetAsync(info, 0, sizeof(int32_t), st);
-  if (!poses || !patches || !intrinsics || !target || !weight || !lmbda || !ii || !jj || !kk || !ws || !depth_var ||
-      !stats || (t1 > t0 && !cov))
-    return RAMP_EINVAL;
-  const int N = t1 - t0;
-  BaWs w;
-  BaCovWs c;
-  const size_t a = ba_carve(ws, E, n_poses, n_patches, N, 1, 0, 0, &w);
-  if (a + ba_cov_carve((char *)ws + a, 6 * N, w.Mu_b, &c) > ws_bytes) return RAMP_EWORKSPACE;
-  int32_t *nk = w.counters, *np = w.counters + 1;
-  rc = ramp_internal_group_by(kk, E, n_patches, w.order_k, nullptr, w.seg_k, w.kx, nk, w.gb, w.gb_bytes, st);
-  if (rc != RAMP_OK) return rc;
-  if (N > 0) {
-    hipLaunchKernelGGL(ba_pairkey_kernel, dim3(ramp_cdiv(E, 256)), dim3(256), 0, st, ii, jj, w.pkeys, E,
-                       (long long)n_poses);
-    rc = ramp_internal_group_by(w.pkeys, E, (int64_t)n_poses * n_poses, w.order_p, nullptr, w.seg_p,
-                                w.pukeys, np, w.gb, w.gb_bytes, st);
-    if (rc != RAMP_OK) return rc;
-  }
-  return ba_cov_run(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P, t0, t1, w, c, w.order_k,
-                    w.seg_k, nk, w.kx, w.order_p, w.seg_p, np, info, cov, depth_var, stats, st);
+  const BaProblem p = {const_cast<float *>(poses), const_cast<float *>(patches), intrinsics, target, weight, lmbda, ii, jj,
+                       kk, E, P, n_poses, n_patches, t0, t1, nullptr, 0};
+  const BaCovOut out = {cov, depth_var, stats, nullptr, 0};
+  return ba_run(p, nullptr, 1, &out, ws, ws_bytes, info, (hipStream_t)stream);
 }
 
 size_t ramp_ba_covariance_planned_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1, int max_patches,
                                                   int max_pairs) {
-  BaWs w;
-  BaCovWs c;
-  const int N = t1 - t0 > 0 ? t1 - t0 : 0;
-  const size_t a = ba_carve(nullptr, E, n_poses, n_patches, N, 0, max_patches, max_pairs, &w);
-  return a + ba_cov_carve(nullptr, 6 * N, w.Mu_b, &c);
+  return ba_ws_bytes(E, n_poses, n_patches, t1 - t0, 0, max_patches, max_pairs, true);
 }
 
 int ramp_ba_covariance_planned(const float *poses, const float *patches, const float *intrinsics, const float *target,
@@ -1554,21 +1435,11 @@ int ramp_ba_covariance_planned(const float *poses, const float *patches, const f
                                const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
                                const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs,
                                void *ws, size_t ws_bytes, int32_t *info, void *stream) {
-  int rc = ba_check_args(E, P, n_poses, n_patches, t0, t1, 1);
-  if (rc != RAMP_OK) return rc;
-  if (E == 0) return RAMP_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (info) (void)hipMemsetAsync(info, 0, sizeof(int32_t), st);
-  if (!poses || !patches || !intrinsics || !target || !weight || !lmbda || !ii || !jj || !kk || !ws || !order_k ||
-      !seg_k || !ngroups_k || !ukeys_k || !order_p || !seg_p || !ngroups_p || !depth_var || !stats || (t1 > t0 && !cov))
-    return RAMP_EINVAL;
-  if (max_patches <= 0 || max_pairs <= 0) return RAMP_EINVAL;
-  BaWs w;
-  BaCovWs c;
-  const size_t a = ba_carve(ws, E, n_poses, n_patches, t1 - t0, 0, max_patches, max_pairs, &w);
-  if (a + ba_cov_carve((char *)ws + a, 6 * (t1 - t0), w.Mu_b, &c) > ws_bytes) return RAMP_EWORKSPACE;
-  return ba_cov_run(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, E, P, t0, t1, w, c, order_k, seg_k,
-                    ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, info, cov, depth_var, stats, st);
+  const BaProblem p = {const_cast<float *>(poses), const_cast<float *>(patches), intrinsics, target, weight, lmbda, ii, jj,
+                       kk, E, P, n_poses, n_patches, t0, t1, nullptr, 0};
+  const BaGroups g = {order_k, seg_k, ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, max_patches, max_pairs};
+  const BaCovOut out = {cov, depth_var, stats, nullptr, 0};
+  return ba_run(p, &g, 1, &out, ws, ws_bytes, info, (hipStream_t)stream);
 }
 
 }  // extern "C"

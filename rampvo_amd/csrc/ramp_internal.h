@@ -39,21 +39,29 @@ int ramp_i_plan_dyn(const int64_t *g4, int E_cap, int E_grid, const int32_t *dyn
                     int32_t *kk_ngroups, int64_t *kk_ukeys, int32_t *ij_order, int32_t *ij_gid, int32_t *ij_seg,
                     int32_t *ij_ngroups, int64_t *ij_ukeys, int64_t *ix, int64_t *jx, int32_t *kj, void *ws,
                     size_t ws_bytes, int32_t *mirror, hipStream_t st);
+// bundle adjustment (csrc/ba.hip): the state and the graph of one problem
+struct BaProblem {
+  float *poses, *patches;                                  // [n_poses][7], [n_patches][3][P][P]
+  const float *intrinsics, *target, *weight, *lmbda;       // target / weight [E][2]
+  const int64_t *ii, *jj, *kk;                             // [E]
+  int E, P, n_poses, n_patches;
+  int t0, t1;                                              // the free poses [t0, t1)
+  const int32_t *dyn;                                      // device-side sizes (nullptr: none), the window is then the
+  int opt_window;                                          // last opt_window poses and t0 / t1 are ramp_i_ba_*dyn's to set
+};
+// its factors grouped by patch (kk) and by pose pair (jj * n_poses + ii), and the caller's bounds on the group counts
+struct BaGroups {
+  const int32_t *order_k, *seg_k, *ngroups_k;
+  const int64_t *ukeys_k;
+  const int32_t *order_p, *seg_p, *ngroups_p;
+  int max_patches, max_pairs;
+};
 size_t ramp_i_ba_dyn_ws(int E_cap, int n_poses, int n_patches, int opt_window, int max_patches, int max_pairs);
-int ramp_i_ba_dyn(float *poses, float *patches, const float *intrinsics, const float *target, const float *weight,
-                  const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk, int E_cap, int P,
-                  int n_poses, int n_patches, int opt_window, int iterations, const int32_t *order_k,
-                  const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
-                  const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs, void *ws,
-                  size_t ws_bytes, int32_t *info, const int32_t *dyn, hipStream_t st);
+int ramp_i_ba_dyn(const BaProblem &p, const BaGroups &g, int iterations, void *ws, size_t ws_bytes, int32_t *info,
+                  hipStream_t st);
 size_t ramp_i_ba_cov_dyn_ws(int opt_window, int max_patches);
-int ramp_i_ba_cov_dyn(const float *poses, const float *patches, const float *intrinsics, const float *target,
-                      const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj, const int64_t *kk,
-                      int E_cap, int P, int n_poses, int n_patches, int opt_window, const int32_t *order_k,
-                      const int32_t *seg_k, const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
-                      const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs, void *ba_ws,
-                      size_t ba_ws_bytes, void *cov_ws, size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var,
-                      float *stats, const int32_t *dyn, hipStream_t st);
+int ramp_i_ba_cov_dyn(const BaProblem &p, const BaGroups &g, void *ba_ws, size_t ba_ws_bytes, void *cov_ws,
+                      size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var, float *stats, hipStream_t st);
 extern "C" {
 int ramp_i_corr_fwd(const void *fmap1, const ramp_corr_level *levels, int nlevels, const float *coords,
                     const int64_t *ii, const int64_t *jj, const int32_t *order, void *out, int out_row_elems,

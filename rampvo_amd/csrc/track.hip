@@ -500,6 +500,17 @@ int ramp_track_plan(const ramp_track *t, int cur, void *stream) {
                          nullptr, (hipStream_t)stream);
 }
 
+// the window's bundle adjustment on the tracker's state: a graph (ii, jj, kk) of at most E factors with its targets / weights
+static BaProblem trk_ba_problem(const ramp_track *t, const int64_t *ii, const int64_t *jj, const int64_t *kk,
+                                const float *target, const float *weight, int E, const int32_t *dyn) {
+  return BaProblem{t->poses, t->patches, t->intrinsics, target, weight, t->lmbda, ii, jj, kk, E, t->P, t->n_rows,
+                   t->n_rows * t->M, 0, 0, dyn, t->opt_window};
+}
+static BaGroups trk_ba_groups(const ramp_track *t) {
+  return BaGroups{t->kk_order, t->kk_seg, t->kk_ngroups, t->kk_ukeys, t->ij_order, t->ij_seg, t->ij_ngroups, t->kk_cap,
+                  t->ij_cap};
+}
+
 #define TRK_PROBE(i)                                                                             \
   do {                                                                                           \
     if (t->probe[i] && hipEventRecord((hipEvent_t)t->probe[i], st) != hipSuccess) return RAMP_ELAUNCH; \
@@ -574,10 +585,8 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
   if (flags & RAMP_TRACK_UPDATE_POST) {
     if (!t->target || !t->weight || !t->ba_ws) return RAMP_EINVAL;
     TRK_PROBE(3);
-    TRK_DO(ramp_i_ba_dyn(t->poses, t->patches, t->intrinsics, t->target, t->weight, t->lmbda, ii, jj, kk, Eb, t->P,
-                         t->n_rows, t->n_rows * t->M, t->opt_window, 2, t->kk_order, t->kk_seg, t->kk_ngroups, t->kk_ukeys,
-                         t->kk_cap, t->ij_order, t->ij_seg, t->ij_ngroups, t->ij_cap, t->ba_ws, t->ba_ws_bytes,
-                         t->dyn + RAMP_DYN_STATUS, dyn, st));
+    TRK_DO(ramp_i_ba_dyn(trk_ba_problem(t, ii, jj, kk, t->target, t->weight, Eb, dyn), trk_ba_groups(t), 2, t->ba_ws,
+                         t->ba_ws_bytes, t->dyn + RAMP_DYN_STATUS, st));
     TRK_PROBE(4);
     pc_with_mm = t->points && t->ixm && (flags & RAMP_TRACK_KEYFRAME) && !(flags & RAMP_TRACK_MM_GIVEN) && t->mm;
     if (t->points && t->ixm && !pc_with_mm)
@@ -664,10 +673,8 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
     }   // (fp16 features)
     TRK_PROBE(2);
     TRK_PROBE(3);
-    TRK_DO(ramp_i_ba_dyn(t->poses, t->patches, t->intrinsics, t->target, t->weight, t->lmbda, ii, jj, kk, Eb, t->P,
-                         t->n_rows, t->n_rows * t->M, t->opt_window, 2, t->kk_order, t->kk_seg, t->kk_ngroups, t->kk_ukeys,
-                         t->kk_cap, t->ij_order, t->ij_seg, t->ij_ngroups, t->ij_cap, t->ba_ws, t->ba_ws_bytes,
-                         t->dyn + RAMP_DYN_STATUS, dyn, st));
+    TRK_DO(ramp_i_ba_dyn(trk_ba_problem(t, ii, jj, kk, t->target, t->weight, Eb, dyn), trk_ba_groups(t), 2, t->ba_ws,
+                         t->ba_ws_bytes, t->dyn + RAMP_DYN_STATUS, st));
     TRK_PROBE(4);
     // (with the motion test following, the point cloud rides in its launch)
     pc_with_mm = t->points && t->ixm && (flags & RAMP_TRACK_KEYFRAME) && !(flags & RAMP_TRACK_MM_GIVEN) && t->mm;
@@ -789,10 +796,10 @@ int ramp_track_uncertainty(const ramp_track *t, int cur, float *cov, float *dept
                                  u.kk_gid, u.kk_seg, u.kk_ngroups, u.kk_ukeys, u.ij_order, u.ij_gid, u.ij_seg, u.ij_ngroups,
                                  u.ij_ukeys, u.ix, u.jx, u.kj, t->plan_ws, t->plan_ws_bytes, nullptr, st);
   if (rc != RAMP_OK) return rc;
-  return ramp_i_ba_cov_dyn(t->poses, t->patches, t->intrinsics, u.tg, u.wg, t->lmbda, ii, jj, kk, Ec, t->P, t->n_rows,
-                           t->n_rows * t->M, t->opt_window, u.kk_order, u.kk_seg, u.kk_ngroups, u.kk_ukeys, t->kk_cap,
-                           u.ij_order, u.ij_seg, u.ij_ngroups, t->ij_cap, t->ba_ws, t->ba_ws_bytes, u.cov_ws, u.cov_ws_bytes,
-                           status, cov, depth_var, stats, u.dynp, st);
+  const BaGroups groups = {u.kk_order, u.kk_seg, u.kk_ngroups, u.kk_ukeys, u.ij_order, u.ij_seg, u.ij_ngroups, t->kk_cap,
+                           t->ij_cap};
+  return ramp_i_ba_cov_dyn(trk_ba_problem(t, ii, jj, kk, u.tg, u.wg, Ec, u.dynp), groups, t->ba_ws, t->ba_ws_bytes, u.cov_ws,
+                           u.cov_ws_bytes, status, cov, depth_var, stats, st);
 }
 
 }  // extern "C"

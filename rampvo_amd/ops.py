@@ -533,14 +533,14 @@ def segment_softmax_sum(fx, gx, groups, max_groups):
 
 
 # -------------------------------------------------------------------- fastba
-def ba(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, iterations=2,
-       info=None, plan=None):
-    """in-place bundle adjustment (cuda_ba.forward).  poses [..,7] and patches
-    [..,3,P,P] must be contiguous float32 views of the caller's storage."""
+def _ba_problem(what, poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, plan):
+    """what ba and ba_covariance share: the checks, then ``head`` (every C entry's arguments up to t1), ``sizes`` (the
+    workspace queries' arguments), the plan's ``groups`` (None without one: the planned entries' group arguments, and the
+    two bounds of their workspace queries) and the converted tensors behind the pointers, to be kept until the call"""
     require_cuda(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk)
     for t in (poses, patches):
         if t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("BA mutates poses/patches in place: contiguous float32 required")
+            raise RuntimeError(what + " poses/patches in place: contiguous float32 required")
     P = patches.shape[-1]
     n_poses = poses.numel() // 7
     n_patches = patches.numel() // (3 * P * P)
@@ -550,69 +550,53 @@ def ba(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, it
     lmbda = lmbda.reshape(-1).contiguous().float()
     E = ii.shape[0]
     assert target.shape[0] == E and weight.shape[0] == E
+    keep = (intrinsics, target, weight, lmbda, _idx(ii), _idx(jj), _idx(kk))
+    sizes = (E, n_poses, n_patches, int(t0), int(t1))
+    head = (ptr(poses), ptr(patches), *(ptr(t) for t in keep), E, P, n_poses, n_patches, int(t0), int(t1))
+    groups = None
     if plan is not None:
         # groupings shared with the update operator (GraphPlan): no sort inside BA
         gk, gp = plan.g_kk, plan.g_ij
         mk, mp = max(int(plan.max_kk), 1), max(int(plan.max_ij), 1)
-        nbytes = lib().ramp_ba_planned_workspace_bytes(E, n_poses, n_patches, int(t0), int(t1), mk, mp)
-        ws = _lib.workspace(nbytes, poses.device, "ba")
-        check(lib().ramp_ba_forward_planned(ptr(poses), ptr(patches), ptr(intrinsics), ptr(target), ptr(weight),
-                                            ptr(lmbda), ptr(_idx(ii)), ptr(_idx(jj)), ptr(_idx(kk)), E, P, n_poses,
-                                            n_patches, int(t0), int(t1), int(iterations), ptr(gk.order),
-                                            ptr(gk.seg_start), ptr(gk.ngroups), ptr(gk.ukeys), mk, ptr(gp.order),
-                                            ptr(gp.seg_start), ptr(gp.ngroups), mp, ptr(ws), ws.numel(), ptr(info),
-                                            stream()), "ramp_ba_forward_planned")
+        groups = ((ptr(gk.order), ptr(gk.seg_start), ptr(gk.ngroups), ptr(gk.ukeys), mk, ptr(gp.order), ptr(gp.seg_start),
+                   ptr(gp.ngroups), mp), (mk, mp))
+    return head, sizes, groups, keep
+
+
+def ba(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, iterations=2,
+       info=None, plan=None):
+    """in-place bundle adjustment (cuda_ba.forward).  poses [..,7] and patches
+    [..,3,P,P] must be contiguous float32 views of the caller's storage."""
+    head, sizes, groups, _keep = _ba_problem("BA mutates", poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk,
+                                             t0, t1, plan)
+    if groups is not None:
+        ws = _lib.workspace(lib().ramp_ba_planned_workspace_bytes(*sizes, *groups[1]), poses.device, "ba")
+        check(lib().ramp_ba_forward_planned(*head, int(iterations), *groups[0], ptr(ws), ws.numel(), ptr(info), stream()),
+              "ramp_ba_forward_planned")
         return
-    nbytes = lib().ramp_ba_workspace_bytes(E, n_poses, n_patches, int(t0), int(t1))
-    ws = _lib.workspace(nbytes, poses.device, "ba")
-    check(lib().ramp_ba_forward(ptr(poses), ptr(patches), ptr(intrinsics), ptr(target),
-                                ptr(weight), ptr(lmbda), ptr(_idx(ii)), ptr(_idx(jj)),
-                                ptr(_idx(kk)), E, P, n_poses, n_patches, int(t0), int(t1),
-                                int(iterations), ptr(ws), ws.numel(), ptr(info), stream()),
-          "ramp_ba_forward")
+    ws = _lib.workspace(lib().ramp_ba_workspace_bytes(*sizes), poses.device, "ba")
+    check(lib().ramp_ba_forward(*head, int(iterations), ptr(ws), ws.numel(), ptr(info), stream()), "ramp_ba_forward")
 
 
 def ba_covariance(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, info=None, plan=None):
     """marginal covariance of the free poses and marginal depth variances of the window (include/ramp_hip.h
     ``ramp_ba_covariance``): returns (cov [6N, 6N], depth_var [n_patches] pre-filled with inf, stats [8] raw words).
     The inputs are only read."""
-    require_cuda(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk)
-    for t in (poses, patches):
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError("ba_covariance reads poses/patches in place: contiguous float32 required")
-    P = patches.shape[-1]
-    n_poses = poses.numel() // 7
-    n_patches = patches.numel() // (3 * P * P)
-    intrinsics = intrinsics.reshape(-1, 4).contiguous().float()
-    target = target.reshape(-1, 2).contiguous().float()
-    weight = weight.reshape(-1, 2).contiguous().float()
-    lmbda = lmbda.reshape(-1).contiguous().float()
-    E = ii.shape[0]
-    assert target.shape[0] == E and weight.shape[0] == E
-    t0, t1 = int(t0), int(t1)
-    n6 = 6 * max(t1 - t0, 0)
+    head, sizes, groups, _keep = _ba_problem("ba_covariance reads", poses, patches, intrinsics, target, weight, lmbda, ii,
+                                             jj, kk, t0, t1, plan)
+    n_patches, n6 = sizes[2], 6 * max(sizes[4] - sizes[3], 0)
     dev = poses.device
     cov = torch.empty((n6, n6), dtype=torch.float32, device=dev)
     depth_var = torch.full((n_patches,), float("inf"), dtype=torch.float32, device=dev)
     stats = torch.zeros(8, dtype=torch.float32, device=dev)
-    if plan is not None:
-        gk, gp = plan.g_kk, plan.g_ij
-        mk, mp = max(int(plan.max_kk), 1), max(int(plan.max_ij), 1)
-        nbytes = lib().ramp_ba_covariance_planned_workspace_bytes(E, n_poses, n_patches, t0, t1, mk, mp)
-        ws = _lib.workspace(nbytes, dev, "ba")
-        check(lib().ramp_ba_covariance_planned(ptr(poses), ptr(patches), ptr(intrinsics), ptr(target), ptr(weight),
-                                               ptr(lmbda), ptr(_idx(ii)), ptr(_idx(jj)), ptr(_idx(kk)), E, P, n_poses,
-                                               n_patches, t0, t1, ptr(cov), ptr(depth_var), ptr(stats), ptr(gk.order),
-                                               ptr(gk.seg_start), ptr(gk.ngroups), ptr(gk.ukeys), mk, ptr(gp.order),
-                                               ptr(gp.seg_start), ptr(gp.ngroups), mp, ptr(ws), ws.numel(), ptr(info),
-                                               stream()), "ramp_ba_covariance_planned")
+    outs = (ptr(cov), ptr(depth_var), ptr(stats))
+    if groups is not None:
+        ws = _lib.workspace(lib().ramp_ba_covariance_planned_workspace_bytes(*sizes, *groups[1]), dev, "ba")
+        check(lib().ramp_ba_covariance_planned(*head, *outs, *groups[0], ptr(ws), ws.numel(), ptr(info), stream()),
+              "ramp_ba_covariance_planned")
     else:
-        nbytes = lib().ramp_ba_covariance_workspace_bytes(E, n_poses, n_patches, t0, t1)
-        ws = _lib.workspace(nbytes, dev, "ba")
-        check(lib().ramp_ba_covariance(ptr(poses), ptr(patches), ptr(intrinsics), ptr(target), ptr(weight), ptr(lmbda),
-                                       ptr(_idx(ii)), ptr(_idx(jj)), ptr(_idx(kk)), E, P, n_poses, n_patches, t0, t1,
-                                       ptr(cov), ptr(depth_var), ptr(stats), ptr(ws), ws.numel(), ptr(info), stream()),
-              "ramp_ba_covariance")
+        ws = _lib.workspace(lib().ramp_ba_covariance_workspace_bytes(*sizes), dev, "ba")
+        check(lib().ramp_ba_covariance(*head, *outs, ptr(ws), ws.numel(), ptr(info), stream()), "ramp_ba_covariance")
     return cov, depth_var, stats
 
 

@@ -50,6 +50,24 @@ def ba_scene(seed=0, n_frames=8, M=12, lifetime=5, H=120, W=160, noise=1.5, n_to
                 lmbda=np.array([1e-4], np.float32), n_frames=n_frames, M=M)
 
 
+BA_ORACLE_CASES = ["window", "all_free", "structure_only", "shuffled", "big_window", "full_window"]
+
+
+def ba_oracle_case(case):
+    """the scene and the window (t0, t1) of a test_ba_matches_oracle case (tools/ba_bits.py hashes the same problems)"""
+    kw = dict(seed=11, n_frames=9, M=14, lifetime=4, n_total_frames=16)
+    if case == "shuffled":
+        kw["far"] = True
+    if case == "big_window":
+        kw.update(n_frames=34, M=6, lifetime=33, n_total_frames=40)
+    if case == "full_window":      # 32 free poses, n6 = 192: the solver's whole LDS budget, the factorisation's largest row count
+        kw.update(n_frames=36, M=6, lifetime=35, n_total_frames=42)
+    s = ba_scene(**kw)
+    nf = s["n_frames"]
+    return s, {"window": (nf - 5, nf), "all_free": (1, nf), "structure_only": (nf, nf), "shuffled": (2, nf),
+               "big_window": (nf - 30, nf), "full_window": (nf - 32, nf)}[case]
+
+
 def ba_pin_scene(seed, n_frames, M=8, lifetime=4, H=120, W=160, noise=0.4):
     """float64 problem for the fp64 pin of the bundle-adjustment algebra (tests/golden/ba_f64_pin.npz): ba_scene's graph and
     geometry without anything that makes the two implementations under comparison -- ramp/ba.py::BA and the cuda_ba

@@ -50,19 +50,24 @@ def _f32(s):
     return {k: (v.astype(np.float32) if isinstance(v, np.ndarray) and v.dtype == np.float64 else v) for k, v in s.items()}
 
 
+def scene(tag):
+    """the scene rounded to float32 (what the GPU gets) and its window (t0, t1)"""
+    kw, t0f = CASES[tag]
+    s = _f32(ba_pin_scene(**kw))
+    if tag == "w10_gated":
+        rng = np.random.default_rng(5)
+        far = rng.choice(len(s["ii"]), size=len(s["ii"]) // 20, replace=False)
+        s["target"] = s["target"].copy()
+        s["target"][far] += np.float32(200.0)
+        s["far"] = far
+    n = s["n_frames"]
+    return s, t0f(n), n
+
+
 def _case(tag):
-    """the scene rounded to float32 (what the GPU gets), its float64 result and its float32 envelope -- computed once"""
+    """scene(tag), its float64 result and its float32 envelope -- computed once"""
     if tag not in _cache:
-        kw, t0f = CASES[tag]
-        s = _f32(ba_pin_scene(**kw))
-        if tag == "w10_gated":
-            rng = np.random.default_rng(5)
-            far = rng.choice(len(s["ii"]), size=len(s["ii"]) // 20, replace=False)
-            s["target"] = s["target"].copy()
-            s["target"][far] += np.float32(200.0)
-            s["far"] = far
-        n = s["n_frames"]
-        t0 = t0f(n)
+        s, t0, n = scene(tag)
         _cache[tag] = (s, t0, n, covref.covariance(s, t0, n, np.float64), covref.covariance(s, t0, n, np.float32))
     return _cache[tag]
 

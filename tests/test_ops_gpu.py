@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import oracle as orc
-from scenes import ba_scene, corr_case
+from scenes import BA_ORACLE_CASES, ba_oracle_case, ba_scene, corr_case
 
 pytestmark = pytest.mark.gpu
 
@@ -591,18 +591,10 @@ def test_segment_softmax_sum(dtype):
 
 
 # ---------------------------------------------------------------------------- BA
-@pytest.mark.parametrize("case", ["window", "all_free", "structure_only", "shuffled", "big_window"])
+@pytest.mark.parametrize("case", BA_ORACLE_CASES)
 def test_ba_matches_oracle(case):
     from rampvo_amd import ops
-    kw = dict(seed=11, n_frames=9, M=14, lifetime=4, n_total_frames=16)
-    if case == "shuffled":
-        kw["far"] = True
-    if case == "big_window":
-        kw.update(n_frames=34, M=6, lifetime=33, n_total_frames=40)
-    s = ba_scene(**kw)
-    nf = s["n_frames"]
-    t0, t1 = {"window": (nf - 5, nf), "all_free": (1, nf), "structure_only": (nf, nf),
-              "shuffled": (2, nf), "big_window": (nf - 30, nf)}[case]
+    s, (t0, t1) = ba_oracle_case(case)
     p_ref, pt_ref = s["poses"].copy(), s["patches"].copy()
     st = orc.ba(p_ref, pt_ref, s["intr"], s["target"], s["weight"], s["lmbda"], s["ii"], s["jj"], s["kk"], t0, t1, 2)
     assert st == 0
@@ -625,7 +617,7 @@ def test_ba_matches_oracle(case):
     env_p, env_d = np.abs(p_ref - p64).max(), np.abs(pt_ref - pt64).max()
     tol_p = max(1e-4 * max(1.0, np.abs(p_ref).max()), 4 * env_p)
     tol_d = max(1e-4 * max(1.0, np.abs(pt_ref[:, 2]).max()), 4 * env_d)
-    if case in ("window", "structure_only", "big_window"):
+    if case in ("window", "structure_only", "big_window", "full_window"):
         assert 4 * env_p < 1e-4 and 4 * env_d < 1e-4   # well conditioned: the plain 1e-4 bound applies
     assert np.abs(p - p_ref).max() <= tol_p
     assert np.abs(pt - pt_ref).max() <= tol_d
