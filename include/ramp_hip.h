@@ -347,6 +347,55 @@ int ramp_ba_covariance_planned(const float *poses, const float *patches, const f
                                const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs,
                                void *ws, size_t ws_bytes, int32_t *info, void *stream);
 
+/* The map with its uncertainty: ramp_ba_covariance plus, for every patch with at least one factor, its world point, the 3 x 3
+ * covariance of that point, the pose-depth cross term it is formed with and its valid-factor count.  cov, depth_var, stats and
+ * info are those of ramp_ba_covariance, the same bits (the map stage runs behind the covariance's and only reads them).
+ * From the joint inverse of the damped system, with e_k patch k's E row:  cov(xi, z_k) = -Q_k S^-1 e_k.  The point of patch k
+ * is ramp_point_cloud's: source frame i = the ii of the patch's factors, world-to-camera pose T_i = (t, R), ray
+ * r = ((x - cx) / fx, (y - cy) / fy, 1) at the centre pixel (row 1, column 1: the pixel whose depth the system solves for),
+ * inverse depth d, X_w = R' (r / d - t).  Intrinsics: ROW 0, as the system the covariance comes from uses -- where every row is
+ * equal X_w is ramp_point_cloud's output bit for bit.  Perturbations as the step's: the LEFT one T <- Exp(xi) T with
+ * xi = (translation 3, rotation 3), and d <- d + z:
+ *   J_p = R' [ -I | [r / d]x ]  (3 x 6),   J_d = -R' r / d^2  (3 x 1)
+ *   point_cov = J_p cov_ii J_p' + depth_var_k J_d J_d' + (J_p c) J_d' + J_d (J_p c)',   c = the rows of cov(xi, z_k) of frame i
+ * Outputs, indexed by patch id kk like depth_var; entries of patches without a factor are left as the caller filled them:
+ *   point [n_patches][3]
+ *   point_cov [n_patches][6]      : xx, xy, xz, yy, yz, zz (symmetric by construction: one value per off-diagonal pair)
+ *   pose_depth_cov [n_patches][6] : c; zeros where the source frame is not a free pose (i < t0 or i >= t1, or t1 == t0) --
+ *                                   point_cov is then depth_var_k J_d J_d' (rank one)
+ *   n_obs [n_patches] int32       : the patch's factors that pass the validity gate
+ * Info bit 0 (failed factorisation, as ramp_ba_covariance): point_cov and pose_depth_cov entries the call writes are NaN;
+ * point and n_obs are written as usual (point stays finite).  All four outputs are required.  Deterministic: fma chains and
+ * fixed reduction trees, no atomics.  The workspace may exceed ramp_ba_covariance's.                                      */
+size_t ramp_ba_map_covariance_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1);
+int ramp_ba_map_covariance(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                           const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
+                           const int64_t *kk, int E, int P, int n_poses, int n_patches, int t0, int t1, float *cov,
+                           float *depth_var, float *stats, float *point, float *point_cov, float *pose_depth_cov,
+                           int32_t *n_obs, void *ws, size_t ws_bytes, int32_t *info, void *stream);
+/* ... with the caller's two edge groupings, as ramp_ba_covariance_planned takes them                                */
+size_t ramp_ba_map_covariance_planned_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1, int max_patches,
+                                                      int max_pairs);
+int ramp_ba_map_covariance_planned(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                                   const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
+                                   const int64_t *kk, int E, int P, int n_poses, int n_patches, int t0, int t1,
+                                   float *cov, float *depth_var, float *stats, float *point, float *point_cov,
+                                   float *pose_depth_cov, int32_t *n_obs, const int32_t *order_k, const int32_t *seg_k,
+                                   const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
+                                   const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs,
+                                   void *ws, size_t ws_bytes, int32_t *info, void *stream);
+
+/* Stable stream compaction of the map: index [<= n] receives, ASCENDING, the ids i < n of the points with
+ *   all six point_cov entries finite,  sqrt(xx + yy + zz) <= max_sigma,  sqrt(depth_var_i) / d_i <= max_rel_depth_sigma
+ *   (d_i: the inverse depth of patch i, patches [n][3][P][P] at the centre pixel)  and  n_obs_i >= min_obs,
+ * and *count (device int32) their number; index entries behind *count are not written.  A criterion is switched off by
+ * passing +inf (the two sigmas) or 0 (min_obs); a NaN or a zero depth never passes a criterion that is on.  The order is the
+ * patch order whatever the launch geometry (ballot + ordered prefix, one workgroup).  dyn_rows != NULL: n is clipped to
+ * *dyn_rows * per_row on the device (e.g. &dyn[RAMP_DYN_NROW] and M for a device-resident tracker; n is then the capacity). */
+int ramp_map_select(const float *point_cov, const float *depth_var, const float *patches, const int32_t *n_obs, int n, int P,
+                    const int32_t *dyn_rows, int per_row, float max_sigma, float max_rel_depth_sigma, int min_obs,
+                    int32_t *index, int32_t *count, void *stream);
+
 /* group-by for a SMALL key range known to the caller: key = a[e]*mul + (b ? b[e] : 0) - sub must lie
  * in [0, K).  Histogram + one-workgroup scan + scatter + per-segment rank sort (5 short kernels vs a
  * radix sort); same outputs and the same (stable) ordering as ramp_group_by.  ukeys = key + sub.  */
@@ -899,6 +948,14 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
 size_t ramp_track_uncertainty_workspace_bytes(const ramp_track *t);
 int ramp_track_uncertainty(const ramp_track *t, int cur, float *cov, float *depth_var, float *stats, void *ws,
                            size_t ws_bytes, void *stream);
+
+/* ramp_ba_map_covariance for a device-resident tracker between two frames: ramp_track_uncertainty (same window, same kept
+ * factors, same cov / depth_var / stats bits) plus the map's four outputs, capacity sized: point [n_rows * M][3],
+ * point_cov [n_rows * M][6], pose_depth_cov [n_rows * M][6], n_obs [n_rows * M] (entries without a kept factor untouched).
+ * The sizes are read on the device; nothing of the tracker's state is written.                                         */
+size_t ramp_track_map_workspace_bytes(const ramp_track *t);
+int ramp_track_map(const ramp_track *t, int cur, float *cov, float *depth_var, float *stats, float *point, float *point_cov,
+                   float *pose_depth_cov, int32_t *n_obs, void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------- live poses (csrc/publish.hip)
  *

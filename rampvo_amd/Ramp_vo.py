@@ -543,6 +543,49 @@ class Ramp_vo:
         return poses, tst
 
     # --------------------------------------------------------------- uncertainty
+    def _window_query(self, name, with_map=False, then=None):
+        """what uncertainty() and map() share: the one C call on the stream the state lives on, ordered in front of the
+        current stream.  Returns the call's raw device tensors (cov, depth_var, stats words[, point, point_cov,
+        pose_depth_cov, n_obs]) followed by what ``then(resident, tensors)`` enqueued behind it on the same stream."""
+        dv = self._dev
+        resident = dv is not None and dv.active
+        dev = self.device
+        last_t, last_w = getattr(self, "last_target", None), getattr(self, "last_weight", None)
+        if (last_t is None or last_w is None) and not (resident and dv._frames):
+            raise RuntimeError(name + ": no update has run yet -- there are no targets and weights to form the "
+                               "system from (track at least until the first update())")
+        W = int(self.cfg.OPTIMIZATION_WINDOW)
+        with torch.no_grad():
+            own = getattr(self, "_main_used", False)          # (inputs_ready = "stream": the state is the tracker's own stream's)
+            cur = torch.cuda.current_stream(dev)
+            st = self._main_stream if own else cur
+            with torch.cuda.stream(st):
+                if resident:
+                    if not dv._frames:                        # (handed over, no device step yet: the last update ran host-driven)
+                        k = last_t.shape[1]
+                        dv.target[:k].copy_(last_t[0])
+                        dv.weight[:k].copy_(last_w[0])
+                    out = dv.map() if with_map else dv.uncertainty()
+                else:
+                    self._join_main()
+                    n = self._n
+                    rows = self._net_map_dev if self._net_map_dev is not None else self._upload(self._net_rows())
+                    if rows.numel() != self._dii.numel() or rows.numel() == 0:
+                        raise RuntimeError(name + ": the factor graph has changed since the last update()")
+                    t0 = max(n - W, 1) if self.is_initialized else 1
+                    op = ops.ba_map_covariance if with_map else ops.ba_covariance
+                    out = op(self.poses_, self.patches_, self.intrinsics_, last_t[0][rows], last_w[0][rows], self.lmbda,
+                             self._dii, self._djj, self._dkk, t0, n)
+                if then is not None:
+                    out = tuple(out) + tuple(then(resident, out))
+            if own:
+                ev = torch.cuda.Event()
+                ev.record(st)
+                cur.wait_event(ev)
+                for x in out:
+                    x.record_stream(cur)
+        return out
+
     def uncertainty(self):
         """How good the window's poses and depths are right now: the marginal covariance of the free poses and the marginal
         variance of every patch depth (``fastba.covariance``: the damped system the step is solved with), from the LAST
@@ -557,41 +600,7 @@ class Ramp_vo:
         A device-resident state stays device resident: ONE C call (csrc/track.hip::ramp_track_uncertainty) that reads the
         sizes on the device, no settle(), no hand-back; the host synchronises only to read the result.  Nothing of the
         tracker's state is written, so a queried tracker tracks the same bits as one that is never asked."""
-        dv = self._dev
-        resident = dv is not None and dv.active
-        dev = self.device
-        last_t, last_w = getattr(self, "last_target", None), getattr(self, "last_weight", None)
-        if (last_t is None or last_w is None) and not (resident and dv._frames):
-            raise RuntimeError("uncertainty(): no update has run yet -- there are no targets and weights to form the "
-                               "system from (track at least until the first update())")
-        W = int(self.cfg.OPTIMIZATION_WINDOW)
-        with torch.no_grad():
-            own = getattr(self, "_main_used", False)          # (inputs_ready = "stream": the state is the tracker's own stream's)
-            cur = torch.cuda.current_stream(dev)
-            st = self._main_stream if own else cur
-            with torch.cuda.stream(st):
-                if resident:
-                    if not dv._frames:                        # (handed over, no device step yet: the last update ran host-driven)
-                        k = last_t.shape[1]
-                        dv.target[:k].copy_(last_t[0])
-                        dv.weight[:k].copy_(last_w[0])
-                    cov_c, dvar_c, raw = dv.uncertainty()
-                else:
-                    self._join_main()
-                    n = self._n
-                    rows = self._net_map_dev if self._net_map_dev is not None else self._upload(self._net_rows())
-                    if rows.numel() != self._dii.numel() or rows.numel() == 0:
-                        raise RuntimeError("uncertainty(): the factor graph has changed since the last update()")
-                    t0 = max(n - W, 1) if self.is_initialized else 1
-                    cov_c, dvar_c, raw = ops.ba_covariance(self.poses_, self.patches_, self.intrinsics_, last_t[0][rows],
-                                                           last_w[0][rows], self.lmbda, self._dii, self._djj, self._dkk,
-                                                           t0, n)
-            if own:
-                ev = torch.cuda.Event()
-                ev.record(st)
-                cur.wait_event(ev)
-                for x in (cov_c, dvar_c, raw):
-                    x.record_stream(cur)
+        cov_c, dvar_c, raw = self._window_query("uncertainty()")
         s = ops.ba_covariance_stats(raw)                      # (the one synchronisation: 32 bytes)
         N, t0 = s["N"], s["t0"]
         n = t0 + N
@@ -600,6 +609,44 @@ class Ramp_vo:
         dof = 2 * s["n_valid"] - 6 * N - s["Mu"]
         return dict(frames=list(range(t0, n)), cov=cov, pose_cov=pose_cov, depth_var=dvar_c[:n * self.M].view(n, self.M),
                     chi2=s["chi2"], n_valid=s["n_valid"], dof=dof, sigma0_sq=s["chi2"] / max(dof, 1), failed=s["failed"])
+
+    def map(self, max_sigma=None, max_rel_depth_sigma=None, min_obs=2):
+        """The map with its uncertainty, filtered: the window's patch centres as world points, each with the 3 x 3 covariance
+        ``fastba.map_covariance`` propagates from the system behind ``uncertainty()`` (same factors, same state between two
+        frames), compacted on the device to the K points that pass
+
+        ``sqrt(trace(point_cov)) <= max_sigma`` (world units), ``sqrt(depth_var) / d <= max_rel_depth_sigma`` and
+        ``n_obs >= min_obs`` (valid factors of the patch); ``None`` (or ``min_obs=0``) switches a criterion off.  A point
+        whose covariance is not finite never passes.
+
+        Returns a dict of device tensors in patch order: ``index`` [K] (flat patch id ``frame * M + m``), ``frame`` [K],
+        ``points`` [K, 3], ``point_cov`` [K, 3, 3], ``colors`` [K, 3] uint8, ``depth_sigma_rel`` [K], ``n_obs`` [K]; and
+        ``n_total`` (patches with a factor, before the selection), ``chi2``, ``dof``, ``sigma0_sq``, ``failed`` as
+        ``uncertainty()``.
+
+        As ``uncertainty()``, a device-resident state stays resident and nothing of the tracker's state is written: one C
+        call for the covariance and the map (csrc/track.hip::ramp_track_map), one for the selection (ramp_map_select); the
+        host waits only for the stats words and the count."""
+        M = self.M
+
+        def select(resident, out):
+            _, dvar, _, _, pcov, _, nobs = out
+            if resident:
+                return ops.map_select(pcov, dvar, self.patches_, nobs, max_sigma, max_rel_depth_sigma, min_obs,
+                                      dyn_rows=self._dev.dyn[track_dev.DYN_NROW:], per_row=M)
+            return ops.map_select(pcov, dvar, self.patches_, nobs, max_sigma, max_rel_depth_sigma, min_obs, n=self._n * M)
+
+        _, dvar, raw, point, pcov, _, nobs, index, count = self._window_query("map()", with_map=True, then=select)
+        s = ops.ba_covariance_stats(raw)                      # (the two synchronisations: 32 bytes and 4 bytes)
+        K = int(count.cpu())
+        idx = index[:K].long()
+        P = self.patches_.shape[-1]
+        d = self.patches_.view(-1, 3, P, P)[:, 2, 1, 1]
+        sym = torch.tensor([0, 1, 2, 1, 3, 4, 2, 4, 5], device=idx.device)
+        dof = 2 * s["n_valid"] - 6 * s["N"] - s["Mu"]
+        return dict(index=idx, frame=idx // M, points=point[idx], point_cov=pcov[idx][:, sym].view(K, 3, 3),
+                    colors=self.colors_.view(-1, 3)[idx], depth_sigma_rel=dvar[idx].sqrt() / d[idx], n_obs=nobs[idx],
+                    n_total=s["Mu"], chi2=s["chi2"], dof=dof, sigma0_sq=s["chi2"] / max(dof, 1), failed=s["failed"])
 
     # ------------------------------------------------------------------ kernels
     def corr(self, coords, indicies=None, order=None):

@@ -101,6 +101,12 @@ SIGNATURES = {
     "ramp_ba_covariance_planned_workspace_bytes": (c_sz, [c_i] * 7),
     "ramp_ba_covariance_planned": (c_i, [c_p] * 9 + [c_i] * 6 + [c_p] * 3 + [c_p] * 4 + [c_i] + [c_p] * 3
                                    + [c_i, c_p, c_sz, c_p, c_p]),
+    "ramp_ba_map_covariance_workspace_bytes": (c_sz, [c_i] * 5),
+    "ramp_ba_map_covariance": (c_i, [c_p] * 9 + [c_i] * 6 + [c_p] * 7 + [c_p, c_sz, c_p, c_p]),
+    "ramp_ba_map_covariance_planned_workspace_bytes": (c_sz, [c_i] * 7),
+    "ramp_ba_map_covariance_planned": (c_i, [c_p] * 9 + [c_i] * 6 + [c_p] * 7 + [c_p] * 4 + [c_i] + [c_p] * 3
+                                       + [c_i, c_p, c_sz, c_p, c_p]),
+    "ramp_map_select": (c_i, [c_p] * 4 + [c_i, c_i, c_p, c_i, c_f, c_f, c_i, c_p, c_p, c_p]),
     "ramp_group_by_small_workspace_bytes": (c_sz, [c_i, c_i]),
     "ramp_group_by_small": (c_i, [c_p, c_p, c_i64, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
     "ramp_neighbors_from_groups": (c_i, [c_p] * 7 + [c_i, c_i, c_p]),
@@ -163,6 +169,8 @@ SIGNATURES = {
     "ramp_track_publish": (c_i, [c_p, c_i64, ctypes.c_double, c_p, c_i, c_p, c_p] + [c_i] * 8 + [c_p]),
     "ramp_track_uncertainty_workspace_bytes": (c_sz, [c_p]),
     "ramp_track_uncertainty": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    "ramp_track_map_workspace_bytes": (c_sz, [c_p]),
+    "ramp_track_map": (c_i, [c_p, c_i] + [c_p] * 7 + [c_p, c_sz, c_p]),
     "ramp_trajectory_resolve": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
 }
 

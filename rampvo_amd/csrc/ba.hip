@@ -25,7 +25,10 @@
 //   C2     ba_cov_expand_kernel: cov = L^-T L^-1 (tiles), depth_var = Q + Q^2 |L^-1 e_k|^2 and the chi2 partials (one
 //          wave per patch)
 //   C3     ba_cov_stats_kernel: chi2 / valid count from the partials, in group order
-// and never K7: poses and patches are only read.
+//   C4     ba_map_kernel (ramp_ba_map_covariance only): the pose-depth cross term -Q_k (L^-T L^-1 e_k) of the patch's source
+//          frame, the patch's world point and its 3 x 3 covariance (one wave per patch)
+// and never K7: poses and patches are only read.  ramp_map_select (map_select_kernel) compacts the points that pass the
+// caller's thresholds, in patch order.
 //
 // Math restates ramp/fastba/ba_cuda.cu:232-376 (kernel), 433-582 (host loop),
 // 178-229 (retractions).  Everything is fp32 like the reference (mtype=float).
@@ -1112,6 +1115,192 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// ------------------------------------------------------------------ C4: the map (ramp_ba_map_covariance)
+// One wave per patch group, behind C2 / C3 (it reads what they wrote: cov, depth_var, npart -- their outputs are the same bits
+// with or without this stage).  For patch k with source frame i (the ii of its factors), a = i - t0:
+//   v = L^-1 e_k as C2 forms it; w = (L^-T v)[6a .. 6a+5] from six rows of the transposed copy (lane-strided fma chains, then
+//   the wave's fixed shuffle tree); c = cov(xi_i, z_k) = -Q_k w
+//   the point X_w = R' (r / d - t): csrc/lie.hip::point_cloud_block's expressions with the intrinsics of row 0 (the row the
+//   system is built with), so the same bits wherever every row is equal
+//   J_p = R' [-I | [r / d]x],  J_d = -R' r / d^2  (left perturbation T <- Exp(xi) T, xi = (translation, rotation); d <- d + z)
+//   Sigma = J_p cov_aa J_p' + var(z_k) J_d J_d' + (J_p c) J_d' + J_d (J_p c)'   -- six entries, each from ONE value
+// A source frame outside [t0, t1) is fixed: c = 0 and Sigma = var(z_k) J_d J_d'.  No atomics; fma chains and fixed trees only.
+__global__ void __launch_bounds__(256)
+    ba_map_kernel(const float *__restrict__ LinvT, const int32_t *__restrict__ flag, const float *__restrict__ Erow,
+                  const float *__restrict__ Qv, const int64_t *__restrict__ kx, const int32_t *__restrict__ order_k,
+                  const int32_t *__restrict__ seg_k, const int32_t *__restrict__ ngroups, BaEdgeIn ein,
+                  const float *__restrict__ cov, const float *__restrict__ depth_var, const int32_t *__restrict__ npart,
+                  BaMapOut out, int n6, int max_groups, const int32_t *__restrict__ dyn, int opt_window) {
+  ba_dyn_window(dyn, opt_window, ein.t0, ein.N);
+  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  const int g = blockIdx.x * 4 + wave;
+  if (g >= min(*ngroups, max_groups)) return;
+  const bool bad = *flag != 0;
+  const float qnan = __int_as_float(0x7fc00000);
+  const long k = kx[g];
+  const int src = (int)ein.ii[order_k[seg_k[g]]];
+  const int a = src - ein.t0;
+  const bool is_free = a >= 0 && a < ein.N && 6 * a + 6 <= n6;      // (wave-uniform)
+  float w6[6] = {0, 0, 0, 0, 0, 0};
+  if (is_free) {
+    float v[3] = {0, 0, 0};
+    for (int b = 0; b < n6; b++) {
+      const float eb = Erow[(size_t)g * n6 + b];
+#pragma unroll
+      for (int q = 0; q < 3; q++) {
+        const int i = lane + 64 * q;
+        if (i < n6) v[q] = __builtin_fmaf(eb, LinvT[(size_t)b * n6 + i], v[q]);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+      const float *row = LinvT + (size_t)(6 * a + r) * n6;          // column 6a + r of L^-1 (zero above the diagonal)
+      float s = 0.0f;
+#pragma unroll
+      for (int q = 0; q < 3; q++) {
+        const int i = lane + 64 * q;
+        if (i < n6) s = __builtin_fmaf(row[i], v[q], s);
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+      w6[r] = __shfl(s, 0, 64);
+    }
+  }
+  if (lane != 0) return;
+  // ---- the point (point_cloud_block's statements)
+  float T[7], Tinv[7], t[3], q[4];
+#pragma unroll
+  for (int c = 0; c < 7; c++) T[c] = ein.poses[7 * (size_t)src + c];
+  lt_inv(T, Tinv);
+  lt_load(Tinv, t, q);
+  const float *pt = ein.patches + (size_t)k * 3 * ein.PP;
+  float X0[4], X1[4];
+  X0[0] = (pt[ein.c11] - ein.intr[2]) / ein.intr[0];
+  X0[1] = (pt[ein.PP + ein.c11] - ein.intr[3]) / ein.intr[1];
+  X0[2] = 1.0f;
+  X0[3] = pt[2 * ein.PP + ein.c11];
+  lt_act4_tq(t, q, X0, X1);
+  out.point[3 * (size_t)k + 0] = X1[0] / X1[3];
+  out.point[3 * (size_t)k + 1] = X1[1] / X1[3];
+  out.point[3 * (size_t)k + 2] = X1[2] / X1[3];
+  out.n_obs[k] = npart[g];
+  // ---- Jacobians: Rt = R' (the rotation of the inverse pose), pc = r / d
+  float Rt[9];
+  lt_q2R(q, Rt);
+  const float id = 1.0f / X0[3];
+  const float pc[3] = {X0[0] * id, X0[1] * id, id};
+  float Jp[3][6], Jd[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const float r0 = Rt[3 * i], r1 = Rt[3 * i + 1], r2 = Rt[3 * i + 2];
+    Jp[i][0] = -r0; Jp[i][1] = -r1; Jp[i][2] = -r2;
+    Jp[i][3] = __builtin_fmaf(r1, pc[2], -(r2 * pc[1]));
+    Jp[i][4] = __builtin_fmaf(r2, pc[0], -(r0 * pc[2]));
+    Jp[i][5] = __builtin_fmaf(r0, pc[1], -(r1 * pc[0]));
+    const float rr = __builtin_fmaf(r1, X0[1], __builtin_fmaf(r0, X0[0], r2));      // (R' r)_i with r_z = 1
+    Jd[i] = -rr * (id * id);
+  }
+  const float var = depth_var[k];
+  float P6[6] = {0, 0, 0, 0, 0, 0}, m[3] = {0, 0, 0}, c[6] = {0, 0, 0, 0, 0, 0};
+  if (is_free) {
+    const float qk = Qv[g];
+#pragma unroll
+    for (int r = 0; r < 6; r++) c[r] = -qk * w6[r];
+    float A[3][6];
+#pragma unroll
+    for (int y = 0; y < 6; y++) {
+      float col[6];
+#pragma unroll
+      for (int x = 0; x < 6; x++) col[x] = cov[(size_t)(6 * a + x) * n6 + 6 * a + y];
+#pragma unroll
+      for (int i = 0; i < 3; i++) {
+        float s = 0.0f;
+#pragma unroll
+        for (int x = 0; x < 6; x++) s = __builtin_fmaf(Jp[i][x], col[x], s);
+        A[i][y] = s;
+      }
+    }
+    int e = 0;
+#pragma unroll
+    for (int x = 0; x < 3; x++)
+#pragma unroll
+      for (int y = x; y < 3; y++) {
+        float s = 0.0f;
+#pragma unroll
+        for (int z = 0; z < 6; z++) s = __builtin_fmaf(A[x][z], Jp[y][z], s);
+        P6[e++] = s;
+      }
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      float s = 0.0f;
+#pragma unroll
+      for (int z = 0; z < 6; z++) s = __builtin_fmaf(Jp[i][z], c[z], s);
+      m[i] = s;
+    }
+  }
+  int e = 0;
+#pragma unroll
+  for (int x = 0; x < 3; x++)
+#pragma unroll
+    for (int y = x; y < 3; y++) {
+      float s = var * (Jd[x] * Jd[y]);
+      s = __builtin_fmaf(m[x], Jd[y], s);
+      s = __builtin_fmaf(Jd[x], m[y], s);
+      s += P6[e];
+      out.point_cov[6 * (size_t)k + e] = bad ? qnan : s;
+      e++;
+    }
+#pragma unroll
+  for (int r = 0; r < 6; r++) out.pose_depth_cov[6 * (size_t)k + r] = bad ? qnan : c[r];
+}
+
+// ramp_map_select: stable stream compaction of the points that pass the thresholds -- ONE workgroup walks the patches in
+// chunks of its size; per chunk a ballot per wave, the waves' counts in wave order, the running base: the indices come out
+// ascending whatever the launch geometry, and the count lands in a device word.
+#define BA_SEL_THREADS 1024
+__global__ void __launch_bounds__(BA_SEL_THREADS)
+    map_select_kernel(const float *__restrict__ point_cov, const float *__restrict__ depth_var,
+                      const float *__restrict__ patches, const int32_t *__restrict__ n_obs, int n, int PP, int ctr,
+                      const int32_t *__restrict__ dyn_rows, int per_row, float max_sigma, float max_rel, int min_obs,
+                      int32_t *__restrict__ index, int32_t *__restrict__ count) {
+  __shared__ int s_wcnt[BA_SEL_THREADS / 64];
+  __shared__ int s_base;
+  if (dyn_rows) n = min(n, max(*dyn_rows, 0) * per_row);        // device-side size: the argument is the capacity
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float inf = __int_as_float(0x7f800000);
+  if (tid == 0) s_base = 0;
+  __syncthreads();
+  for (int i0 = 0; i0 < n; i0 += BA_SEL_THREADS) {
+    const int i = i0 + tid;
+    bool hit = false;
+    if (i < n) {
+      const float *pc = point_cov + 6 * (size_t)i;
+      bool fin = true;
+#pragma unroll
+      for (int e = 0; e < 6; e++) fin = fin && (fabsf(pc[e]) < inf);
+      const float sig = sqrtf((pc[0] + pc[3]) + pc[5]);
+      const float rel = sqrtf(depth_var[i]) / patches[((size_t)i * 3 + 2) * PP + ctr];
+      hit = fin && (max_sigma == inf || sig <= max_sigma) && (max_rel == inf || rel <= max_rel) &&
+            (min_obs <= 0 || n_obs[i] >= min_obs);
+    }
+    const unsigned long long mk = __ballot(hit);
+    if (lane == 0) s_wcnt[wave] = __popcll(mk);
+    __syncthreads();
+    int off = s_base;
+    for (int w = 0; w < wave; w++) off += s_wcnt[w];
+    off += __popcll(mk & ((1ull << lane) - 1ull));
+    if (hit) index[off] = i;
+    __syncthreads();
+    if (tid == 0) {
+      int t = s_base;
+      for (int w = 0; w < BA_SEL_THREADS / 64; w++) t += s_wcnt[w];
+      s_base = t;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) *count = s_base;
+}
+
 __global__ void ba_pairkey_kernel(const int64_t *__restrict__ ii, const int64_t *__restrict__ jj,
                                   int64_t *__restrict__ keys, int E, long long np) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1247,7 +1436,8 @@ static int ba_iterate(const BaProblem &p, const BaGroups &g, int iterations, BaW
 // ---- uncertainty: the system of ONE iteration at the state passed in, no step taken (nothing retracts)
 struct BaCovWs { float *Linv, *LinvT, *cpart; int32_t *npart, *flag; };
 // what a covariance call writes; ws: its own workspace (the dyn form), or nullptr: the buffers follow BA's in the call's
-struct BaCovOut { float *cov, *depth_var, *stats; void *ws; size_t ws_bytes; };
+// map.point != nullptr: the map stage C4 runs behind C3
+struct BaCovOut { float *cov, *depth_var, *stats; void *ws; size_t ws_bytes; BaMapOut map; };
 static size_t ba_cov_carve(void *ws, int n6, int Mu_b, BaCovWs *c) {
   size_t off = 0;
   char *base = (char *)ws;
@@ -1275,6 +1465,10 @@ static int ba_cov_run(const BaProblem &p, const BaGroups &g, BaWs &w, BaCovWs &c
                      out.depth_var, c.cpart, c.npart, n6, tiles, w.Mu_b, p.dyn, p.opt_window);
   hipLaunchKernelGGL(ba_cov_stats_kernel, dim3(1), dim3(256), 0, st, c.cpart, c.npart, g.ngroups_k, c.flag, out.stats,
                      p.t0, N, w.Mu_b, p.dyn, p.opt_window);
+  if (out.map.point)
+    hipLaunchKernelGGL(ba_map_kernel, dim3(ramp_cdiv(w.Mu_b, 4)), dim3(256), 0, st, c.LinvT, c.flag, w.Erow, w.Qv, g.ukeys_k,
+                       g.order_k, g.seg_k, g.ngroups_k, ba_edge_in(p), out.cov, out.depth_var, c.npart, out.map, n6, w.Mu_b,
+                       p.dyn, p.opt_window);
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;
 }
@@ -1300,6 +1494,10 @@ static int ba_check(const BaProblem &p, const BaGroups *plan, int iterations, co
                !plan->ngroups_p || plan->max_patches <= 0 || plan->max_pairs <= 0))
     return RAMP_EINVAL;
   if (out && (!out->depth_var || !out->stats || (p.t1 > p.t0 && !out->cov))) return RAMP_EINVAL;
+  const BaMapOut *m = out ? &out->map : nullptr;                  // the map's four outputs: all or none
+  if (m && (m->point || m->point_cov || m->pose_depth_cov || m->n_obs) &&
+      !(m->point && m->point_cov && m->pose_depth_cov && m->n_obs))
+    return RAMP_EINVAL;
   todo = true;
   return RAMP_OK;
 }
@@ -1372,9 +1570,10 @@ size_t ramp_i_ba_cov_dyn_ws(int opt_window, int max_patches) {
 }
 // ba_ws: ramp_i_ba_dyn's
 int ramp_i_ba_cov_dyn(const BaProblem &p, const BaGroups &g, void *ba_ws, size_t ba_ws_bytes, void *cov_ws,
-                      size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var, float *stats, hipStream_t st) {
+                      size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var, float *stats, hipStream_t st,
+                      const BaMapOut *map) {
   if (!p.dyn || !cov_ws) return RAMP_EINVAL;
-  const BaCovOut out = {cov, depth_var, stats, cov_ws, cov_ws_bytes};
+  const BaCovOut out = {cov, depth_var, stats, cov_ws, cov_ws_bytes, map ? *map : BaMapOut{}};
   return ba_run(ba_dyn_problem(p), &g, 1, &out, ba_ws, ba_ws_bytes, info, st);
 }
 
@@ -1419,7 +1618,7 @@ int ramp_ba_covariance(const float *poses, const float *patches, const float *in
                        float *depth_var, float *stats, void *ws, size_t ws_bytes, int32_t *info, void *stream) {
   const BaProblem p = {const_cast<float *>(poses), const_cast<float *>(patches), intrinsics, target, weight, lmbda, ii, jj,
                        kk, E, P, n_poses, n_patches, t0, t1, nullptr, 0};
-  const BaCovOut out = {cov, depth_var, stats, nullptr, 0};
+  const BaCovOut out = {cov, depth_var, stats, nullptr, 0, BaMapOut{}};
   return ba_run(p, nullptr, 1, &out, ws, ws_bytes, info, (hipStream_t)stream);
 }
 
@@ -1438,8 +1637,56 @@ int ramp_ba_covariance_planned(const float *poses, const float *patches, const f
   const BaProblem p = {const_cast<float *>(poses), const_cast<float *>(patches), intrinsics, target, weight, lmbda, ii, jj,
                        kk, E, P, n_poses, n_patches, t0, t1, nullptr, 0};
   const BaGroups g = {order_k, seg_k, ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, max_patches, max_pairs};
-  const BaCovOut out = {cov, depth_var, stats, nullptr, 0};
+  const BaCovOut out = {cov, depth_var, stats, nullptr, 0, BaMapOut{}};
   return ba_run(p, &g, 1, &out, ws, ws_bytes, info, (hipStream_t)stream);
+}
+
+size_t ramp_ba_map_covariance_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1) {
+  return ba_ws_bytes(E, n_poses, n_patches, t1 - t0, 1, 0, 0, true);       // (the map stage reads the covariance's buffers)
+}
+
+int ramp_ba_map_covariance(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                           const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
+                           const int64_t *kk, int E, int P, int n_poses, int n_patches, int t0, int t1, float *cov,
+                           float *depth_var, float *stats, float *point, float *point_cov, float *pose_depth_cov,
+                           int32_t *n_obs, void *ws, size_t ws_bytes, int32_t *info, void *stream) {
+  if (!point || !point_cov || !pose_depth_cov || !n_obs) return RAMP_EINVAL;
+  const BaProblem p = {const_cast<float *>(poses), const_cast<float *>(patches), intrinsics, target, weight, lmbda, ii, jj,
+                       kk, E, P, n_poses, n_patches, t0, t1, nullptr, 0};
+  const BaCovOut out = {cov, depth_var, stats, nullptr, 0, BaMapOut{point, point_cov, pose_depth_cov, n_obs}};
+  return ba_run(p, nullptr, 1, &out, ws, ws_bytes, info, (hipStream_t)stream);
+}
+
+size_t ramp_ba_map_covariance_planned_workspace_bytes(int E, int n_poses, int n_patches, int t0, int t1, int max_patches,
+                                                      int max_pairs) {
+  return ba_ws_bytes(E, n_poses, n_patches, t1 - t0, 0, max_patches, max_pairs, true);
+}
+
+int ramp_ba_map_covariance_planned(const float *poses, const float *patches, const float *intrinsics, const float *target,
+                                   const float *weight, const float *lmbda, const int64_t *ii, const int64_t *jj,
+                                   const int64_t *kk, int E, int P, int n_poses, int n_patches, int t0, int t1,
+                                   float *cov, float *depth_var, float *stats, float *point, float *point_cov,
+                                   float *pose_depth_cov, int32_t *n_obs, const int32_t *order_k, const int32_t *seg_k,
+                                   const int32_t *ngroups_k, const int64_t *ukeys_k, int max_patches,
+                                   const int32_t *order_p, const int32_t *seg_p, const int32_t *ngroups_p, int max_pairs,
+                                   void *ws, size_t ws_bytes, int32_t *info, void *stream) {
+  if (!point || !point_cov || !pose_depth_cov || !n_obs) return RAMP_EINVAL;
+  const BaProblem p = {const_cast<float *>(poses), const_cast<float *>(patches), intrinsics, target, weight, lmbda, ii, jj,
+                       kk, E, P, n_poses, n_patches, t0, t1, nullptr, 0};
+  const BaGroups g = {order_k, seg_k, ngroups_k, ukeys_k, order_p, seg_p, ngroups_p, max_patches, max_pairs};
+  const BaCovOut out = {cov, depth_var, stats, nullptr, 0, BaMapOut{point, point_cov, pose_depth_cov, n_obs}};
+  return ba_run(p, &g, 1, &out, ws, ws_bytes, info, (hipStream_t)stream);
+}
+
+int ramp_map_select(const float *point_cov, const float *depth_var, const float *patches, const int32_t *n_obs, int n, int P,
+                    const int32_t *dyn_rows, int per_row, float max_sigma, float max_rel_depth_sigma, int min_obs,
+                    int32_t *index, int32_t *count, void *stream) {
+  if (n < 0 || P < 2 || !count || (dyn_rows && per_row <= 0)) return RAMP_EINVAL;
+  if (n > 0 && (!point_cov || !depth_var || !patches || !n_obs || !index)) return RAMP_EINVAL;
+  hipLaunchKernelGGL(map_select_kernel, dim3(1), dim3(BA_SEL_THREADS), 0, (hipStream_t)stream, point_cov, depth_var, patches,
+                     n_obs, n, P * P, 1 * P + 1, dyn_rows, per_row, max_sigma, max_rel_depth_sigma, min_obs, index, count);
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
 }
 
 }  // extern "C"

@@ -59,9 +59,16 @@ struct BaGroups {
 size_t ramp_i_ba_dyn_ws(int E_cap, int n_poses, int n_patches, int opt_window, int max_patches, int max_pairs);
 int ramp_i_ba_dyn(const BaProblem &p, const BaGroups &g, int iterations, void *ws, size_t ws_bytes, int32_t *info,
                   hipStream_t st);
+// the map's outputs of a covariance call (include/ramp_hip.h ramp_ba_map_covariance), indexed by patch id; all four or none
+struct BaMapOut {
+  float *point, *point_cov, *pose_depth_cov;               // [n_patches][3], [n_patches][6], [n_patches][6]
+  int32_t *n_obs;                                          // [n_patches]
+};
 size_t ramp_i_ba_cov_dyn_ws(int opt_window, int max_patches);
+// map: nullptr = the covariance alone
 int ramp_i_ba_cov_dyn(const BaProblem &p, const BaGroups &g, void *ba_ws, size_t ba_ws_bytes, void *cov_ws,
-                      size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var, float *stats, hipStream_t st);
+                      size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var, float *stats, hipStream_t st,
+                      const BaMapOut *map = nullptr);
 extern "C" {
 int ramp_i_corr_fwd(const void *fmap1, const ramp_corr_level *levels, int nlevels, const float *coords,
                     const int64_t *ii, const int64_t *jj, const int32_t *order, void *out, int out_row_elems,

@@ -778,8 +778,9 @@ size_t ramp_track_uncertainty_workspace_bytes(const ramp_track *t) {
   return trk_valid(t) ? trk_unc_carve(t, nullptr, &u) : 0;
 }
 
-int ramp_track_uncertainty(const ramp_track *t, int cur, float *cov, float *depth_var, float *stats, void *ws,
-                           size_t ws_bytes, void *stream) {
+// what ramp_track_uncertainty and ramp_track_map share (map: nullptr = the covariance alone)
+static int trk_unc_run(const ramp_track *t, int cur, float *cov, float *depth_var, float *stats, const BaMapOut *map, void *ws,
+                       size_t ws_bytes, void *stream) {
   if (!trk_valid(t) || cur < 0 || cur > 1 || !cov || !depth_var || !stats || !ws || !t->target || !t->weight || !t->ba_ws)
     return RAMP_EINVAL;
   TrkUncWs u;
@@ -799,7 +800,21 @@ int ramp_track_uncertainty(const ramp_track *t, int cur, float *cov, float *dept
   const BaGroups groups = {u.kk_order, u.kk_seg, u.kk_ngroups, u.kk_ukeys, u.ij_order, u.ij_seg, u.ij_ngroups, t->kk_cap,
                            t->ij_cap};
   return ramp_i_ba_cov_dyn(trk_ba_problem(t, ii, jj, kk, u.tg, u.wg, Ec, u.dynp), groups, t->ba_ws, t->ba_ws_bytes, u.cov_ws,
-                           u.cov_ws_bytes, status, cov, depth_var, stats, st);
+                           u.cov_ws_bytes, status, cov, depth_var, stats, st, map);
+}
+
+int ramp_track_uncertainty(const ramp_track *t, int cur, float *cov, float *depth_var, float *stats, void *ws,
+                           size_t ws_bytes, void *stream) {
+  return trk_unc_run(t, cur, cov, depth_var, stats, nullptr, ws, ws_bytes, stream);
+}
+
+size_t ramp_track_map_workspace_bytes(const ramp_track *t) { return ramp_track_uncertainty_workspace_bytes(t); }
+
+int ramp_track_map(const ramp_track *t, int cur, float *cov, float *depth_var, float *stats, float *point, float *point_cov,
+                   float *pose_depth_cov, int32_t *n_obs, void *ws, size_t ws_bytes, void *stream) {
+  if (!point || !point_cov || !pose_depth_cov || !n_obs) return RAMP_EINVAL;
+  const BaMapOut map = {point, point_cov, pose_depth_cov, n_obs};
+  return trk_unc_run(t, cur, cov, depth_var, stats, &map, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -154,3 +154,21 @@ def save_output_for_COLMAP(name, traj, points, colors, fx, fy, cx, cy, H=480, W=
     (colmap_dir / "points3D.txt").write_text(points3D)
     (colmap_dir / "cameras.txt").write_text(f"1 PINHOLE {W} {H} {fx} {fy} {cx} {cy}")
     return colmap_dir
+
+
+def save_map_ply(path, map_dict, scale=1.0):
+    """the dict of ``Ramp_vo.map()`` as a binary little-endian PLY point cloud: x y z (float, times ``scale``), red green
+    blue (uchar) and ``sigma`` (float): the square root of the trace of the point's covariance, in the units of x y z"""
+    cpu = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    xyz = cpu(map_dict["points"]).reshape(-1, 3).astype(np.float64) * scale
+    cov = cpu(map_dict["point_cov"]).reshape(-1, 3, 3).astype(np.float64)
+    rec = np.zeros(len(xyz), np.dtype([("xyz", "<f4", 3), ("rgb", "u1", 3), ("sigma", "<f4")]))
+    rec["xyz"], rec["rgb"] = xyz, cpu(map_dict["colors"]).reshape(-1, 3)
+    rec["sigma"] = scale * np.sqrt(np.trace(cov, axis1=1, axis2=2))
+    Path(path).parent.mkdir(exist_ok=True, parents=True)
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\nproperty float sigma\nend_header\n" % len(rec))
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(rec.tobytes())
+    return path

@@ -48,6 +48,29 @@ def covariance(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0
     return cov, depth_var, ops.ba_covariance_stats(raw)
 
 
+def map_covariance(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, M=0, info=None, plan=None, out=None):
+    """The map with its uncertainty: ``(cov, depth_var, stats, point, point_cov, pose_depth_cov, n_obs)``.
+
+    ``cov``, ``depth_var`` and ``stats`` are ``covariance``'s, the same bits.  For every patch k with a factor (the other
+    entries keep their fill: NaN / 0, or what the caller's ``out`` tensors held):
+
+    * ``point [n_patches, 3]``: the world point of the patch centre, ``projective_ops.point_cloud``'s (intrinsics row 0, as
+      the system uses; the same bits where every row is equal).
+    * ``point_cov [n_patches, 6]``: its 3 x 3 covariance as xx, xy, xz, yy, yz, zz, propagated from the joint inverse of the
+      damped system: the source pose's block of ``cov``, ``depth_var[k]`` and the pose-depth cross term.  Left perturbation
+      ``T <- Exp(xi) T`` of the world-to-camera pose (translation 3, rotation 3), ``d <- d + z``.
+    * ``pose_depth_cov [n_patches, 6]``: ``cov(xi_i, z_k) = -Q_k (S^-1 e_k)`` restricted to the patch's source frame i; zeros
+      where that frame is not a free pose -- ``point_cov`` is then the rank-one ``depth_var[k] J_d J_d'``.
+    * ``n_obs [n_patches]`` int32: the patch's factors that pass the validity gate.
+
+    A failed factorisation (``stats["failed"]``, bit 0 of ``info``) gives NaN ``point_cov`` / ``pose_depth_cov``; ``point``
+    stays finite.  No autograd."""
+    p = poses.data if hasattr(poses, "data") and not isinstance(poses, torch.Tensor) else poses
+    cov, depth_var, raw, point, point_cov, pdc, n_obs = ops.ba_map_covariance(p, patches, intrinsics, target, weight, lmbda,
+                                                                              ii, jj, kk, t0, t1, info, plan=plan, out=out)
+    return cov, depth_var, ops.ba_covariance_stats(raw), point, point_cov, pdc, n_obs
+
+
 def neighbors(ii, jj, ii_bound=0, jj_bound=0):
     """cuda_ba.neighbors(kk, jj) -> (ix, jx), computed on the device."""
     return ops.neighbors(ii, jj, ii_bound, jj_bound)

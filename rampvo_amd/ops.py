@@ -578,26 +578,86 @@ def ba(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, it
     check(lib().ramp_ba_forward(*head, int(iterations), ptr(ws), ws.numel(), ptr(info), stream()), "ramp_ba_forward")
 
 
-def ba_covariance(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, info=None, plan=None):
-    """marginal covariance of the free poses and marginal depth variances of the window (include/ramp_hip.h
-    ``ramp_ba_covariance``): returns (cov [6N, 6N], depth_var [n_patches] pre-filled with inf, stats [8] raw words).
-    The inputs are only read."""
-    head, sizes, groups, _keep = _ba_problem("ba_covariance reads", poses, patches, intrinsics, target, weight, lmbda, ii,
+def _ba_covariance(entry, poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, info, plan, extra=()):
+    """ramp_ba_covariance / ramp_ba_map_covariance (``entry``), self-grouped or planned; ``extra``: the output tensors behind
+    stats"""
+    head, sizes, groups, _keep = _ba_problem(entry[5:] + " reads", poses, patches, intrinsics, target, weight, lmbda, ii,
                                              jj, kk, t0, t1, plan)
     n_patches, n6 = sizes[2], 6 * max(sizes[4] - sizes[3], 0)
     dev = poses.device
     cov = torch.empty((n6, n6), dtype=torch.float32, device=dev)
     depth_var = torch.full((n_patches,), float("inf"), dtype=torch.float32, device=dev)
     stats = torch.zeros(8, dtype=torch.float32, device=dev)
-    outs = (ptr(cov), ptr(depth_var), ptr(stats))
+    outs = (ptr(cov), ptr(depth_var), ptr(stats)) + tuple(ptr(x) for x in extra)
     if groups is not None:
-        ws = _lib.workspace(lib().ramp_ba_covariance_planned_workspace_bytes(*sizes, *groups[1]), dev, "ba")
-        check(lib().ramp_ba_covariance_planned(*head, *outs, *groups[0], ptr(ws), ws.numel(), ptr(info), stream()),
-              "ramp_ba_covariance_planned")
+        ws = _lib.workspace(getattr(lib(), entry + "_planned_workspace_bytes")(*sizes, *groups[1]), dev, "ba")
+        check(getattr(lib(), entry + "_planned")(*head, *outs, *groups[0], ptr(ws), ws.numel(), ptr(info), stream()),
+              entry + "_planned")
     else:
-        ws = _lib.workspace(lib().ramp_ba_covariance_workspace_bytes(*sizes), dev, "ba")
-        check(lib().ramp_ba_covariance(*head, *outs, ptr(ws), ws.numel(), ptr(info), stream()), "ramp_ba_covariance")
+        ws = _lib.workspace(getattr(lib(), entry + "_workspace_bytes")(*sizes), dev, "ba")
+        check(getattr(lib(), entry)(*head, *outs, ptr(ws), ws.numel(), ptr(info), stream()), entry)
     return cov, depth_var, stats
+
+
+def ba_covariance(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, info=None, plan=None):
+    """marginal covariance of the free poses and marginal depth variances of the window (include/ramp_hip.h
+    ``ramp_ba_covariance``): returns (cov [6N, 6N], depth_var [n_patches] pre-filled with inf, stats [8] raw words).
+    The inputs are only read."""
+    return _ba_covariance("ramp_ba_covariance", poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, info,
+                          plan)
+
+
+def map_outputs(n_patches, device):
+    """the four map outputs of ramp_ba_map_covariance / ramp_track_map as the caller fills them: point [n, 3], point_cov
+    [n, 6] and pose_depth_cov [n, 6] NaN (a patch without a factor is never a finite point), n_obs [n] zero"""
+    nan = float("nan")
+    return (torch.full((n_patches, 3), nan, dtype=torch.float32, device=device),
+            torch.full((n_patches, 6), nan, dtype=torch.float32, device=device),
+            torch.full((n_patches, 6), nan, dtype=torch.float32, device=device),
+            torch.zeros(n_patches, dtype=torch.int32, device=device))
+
+
+def ba_map_covariance(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, info=None, plan=None, out=None):
+    """ba_covariance plus the map (include/ramp_hip.h ``ramp_ba_map_covariance``): returns (cov, depth_var, stats, point
+    [n_patches, 3], point_cov [n_patches, 6] (xx, xy, xz, yy, yz, zz), pose_depth_cov [n_patches, 6], n_obs [n_patches]
+    int32).  ``out``: the caller's four map tensors (contiguous; ``map_outputs`` otherwise) -- entries of patches without a
+    factor are left as they are."""
+    P = patches.shape[-1]
+    n_patches = patches.numel() // (3 * P * P)
+    if out is None:
+        out = map_outputs(n_patches, poses.device)
+    point, point_cov, pdc, n_obs = out
+    require_cuda(*out)
+    for x, shape, dt in ((point, (n_patches, 3), torch.float32), (point_cov, (n_patches, 6), torch.float32),
+                         (pdc, (n_patches, 6), torch.float32), (n_obs, (n_patches,), torch.int32)):
+        if tuple(x.shape) != shape or x.dtype != dt or not x.is_contiguous():
+            raise RuntimeError("ba_map_covariance: a map output must be contiguous %s %s" % (dt, shape))
+    cov, depth_var, stats = _ba_covariance("ramp_ba_map_covariance", poses, patches, intrinsics, target, weight, lmbda, ii,
+                                           jj, kk, t0, t1, info, plan, extra=out)
+    return cov, depth_var, stats, point, point_cov, pdc, n_obs
+
+
+def map_select(point_cov, depth_var, patches, n_obs, max_sigma=None, max_rel_depth_sigma=None, min_obs=0, n=None,
+               dyn_rows=None, per_row=0):
+    """stable compaction of the map (include/ramp_hip.h ``ramp_map_select``): returns (index [n] int32 -- the selected patch
+    ids ascending in its first ``count`` entries, -1 behind them -- and count [1] int32), device tensors; nothing is
+    synchronised.  A threshold of None (or +inf / min_obs 0) switches its criterion off.  ``dyn_rows``: a device int32 word
+    that clips n to ``dyn_rows * per_row`` on the device."""
+    require_cuda(point_cov, depth_var, patches, n_obs)
+    P = patches.shape[-1]
+    n = int(point_cov.shape[0] if n is None else n)
+    assert point_cov.dtype == torch.float32 and depth_var.dtype == torch.float32 and n_obs.dtype == torch.int32
+    assert patches.dtype == torch.float32 and patches.is_contiguous() and point_cov.is_contiguous()
+    assert depth_var.is_contiguous() and n_obs.is_contiguous()
+    assert point_cov.numel() >= 6 * n and depth_var.numel() >= n and n_obs.numel() >= n and patches.numel() >= 3 * P * P * n
+    inf = float("inf")
+    index = torch.full((max(n, 1),), -1, dtype=torch.int32, device=point_cov.device)
+    count = torch.zeros(1, dtype=torch.int32, device=point_cov.device)
+    check(lib().ramp_map_select(ptr(point_cov), ptr(depth_var), ptr(patches), ptr(n_obs), n, P, ptr(dyn_rows), int(per_row),
+                                inf if max_sigma is None else float(max_sigma),
+                                inf if max_rel_depth_sigma is None else float(max_rel_depth_sigma), int(min_obs or 0),
+                                ptr(index), ptr(count), stream()), "ramp_map_select")
+    return index[:n], count
 
 
 def ba_covariance_stats(stats):

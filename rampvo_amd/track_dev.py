@@ -473,6 +473,25 @@ class DeviceTrack:
                    "ramp_track_uncertainty")
         return cov, depth_var, stats
 
+    def map(self):
+        """(on the current stream) csrc/track.hip::ramp_track_map: ``uncertainty()``'s three tensors plus the capacity-sized
+        map outputs (point [N * M, 3], point_cov [N * M, 6], pose_depth_cov [N * M, 6] pre-filled with NaN, n_obs [N * M] with
+        0); nothing is synchronised and nothing of the tracker's state is written.  Shares uncertainty()'s scratch."""
+        from . import ops
+        lib = _lib.lib()
+        dev = self.dyn.device
+        if getattr(self, "_unc_ws", None) is None:
+            self._unc_ws = torch.empty(lib.ramp_track_map_workspace_bytes(ctypes.byref(self.t)), dtype=torch.uint8, device=dev)
+        n6, npat = 6 * int(self.t.opt_window), int(self.t.n_rows) * int(self.t.M)
+        cov = torch.empty((n6, n6), dtype=torch.float32, device=dev)
+        depth_var = torch.full((npat,), float("inf"), dtype=torch.float32, device=dev)
+        stats = torch.zeros(8, dtype=torch.float32, device=dev)
+        out = ops.map_outputs(npat, dev)
+        _lib.check(lib.ramp_track_map(ctypes.byref(self.t), self.cur, _lib.ptr(cov), _lib.ptr(depth_var), _lib.ptr(stats),
+                                      *(_lib.ptr(x) for x in out), _lib.ptr(self._unc_ws), self._unc_ws.numel(),
+                                      _lib.stream()), "ramp_track_map")
+        return (cov, depth_var, stats) + out
+
     def warm(self):
         """(on the current stream) read the correlation planes of the window once: csrc/track.hip::trk_warm_kernel"""
         _lib.check(_lib.lib().ramp_track_warm(ctypes.byref(self.t), _lib.ptr(self.sink), _lib.stream()), "ramp_track_warm")
