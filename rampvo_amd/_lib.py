@@ -206,9 +206,9 @@ def lib():
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(l, name)  # AttributeError if a declared symbol is not exported
             fn.restype, fn.argtypes = res, args
-        if l.ramp_corr_kplane() != KPLANE:      # (an A/B build with -DCORR_KPLANE=8: this binding would pack the planes wrong)
+        if l.ramp_corr_kplane() != KPLANE:      # (an older library given through RAMP_HIP_LIB: this binding would pack the planes wrong)
             raise RuntimeError("rampvo_amd: %s packs %d-channel correlation planes, this binding is written for %d "
-                               "(rebuild without -DCORR_KPLANE, or set rampvo_amd._lib.KPLANE)" % (LIB_PATH, l.ramp_corr_kplane(), KPLANE))
+                               "(the library is older than this binding: rebuild it from csrc/)" % (LIB_PATH, l.ramp_corr_kplane(), KPLANE))
         _lib = l
     return _lib
 

@@ -157,17 +157,15 @@ __global__ void __launch_bounds__(256) frame_gather_kernel(const FrameGather p) 
 
 // -------------------------------------------------------------------- corr
 #define CORR_MAXLEV 2
-#ifndef CORR_KPLANE
-#define CORR_KPLANE 32  // channels per plane of the packed target maps: [h][128 / KPLANE][w][KPLANE] (8: round 2/3's layout)
-#endif
-#ifndef CORR_PGB
-#define CORR_PGB 4    // pixel groups (of 16) whose loads are in flight together, MFMA kernel
-#define CORR_WAVES 4  // waves per SIMD the MFMA kernel is register-budgeted for
-#endif
+constexpr int CORR_KPLANE = 32;   // channels per plane of the packed fp16 target maps: [h][128 / 32][w][32] (rounds 2-3 packed
+                                  // [h][16][w][8]; the binding's KPLANE and ramp_corr_kplane() say the same 32)
+constexpr int CORR_PGB = 4;       // pixel groups (of 16) whose loads are in flight together, MFMA kernel
+constexpr int CORR_WAVES = 4;     // waves per SIMD the MFMA kernel is register-budgeted for
+constexpr int CORR_X2_PGB = 2;    // ... of the split-fp32 kernel: 16 sixteen-byte loads per lane, as the fp16 kernel's four
+constexpr int CORR_X2_WAVES = 3;  // ... and its register budget (132 VGPRs)
 #define CORR_T 128  // union pixels handled per group (2 per lane), VALU kernel
-#ifndef CORR_TM
 #define CORR_TM 192 // ... of the MFMA kernel: twelve 16-pixel products.  In the bench's steady state a tenth of the live
-#endif              // factors have a 12 x 11 .. 13 x 13 union window at the fine level (tools/corr_window_stats.py); at 128 they
+                    // factors have a 12 x 11 .. 13 x 13 union window at the fine level (tools/corr_window_stats.py); at 128 they
                     // took the nine-separate-windows path (36 products instead of 9-11)
 
 struct CorrParams {
@@ -232,7 +230,7 @@ template <> struct Vec4<__half> {
 template <typename T, int LAYOUT>
 __global__ void __launch_bounds__(64)
     corr_kernel(const CorrParams prm) {
-  constexpr int C = 128, P = 3, PP = 9, R = 3, D = 8, d = 7;
+  constexpr int C = 128, PP = 9, R = 3, D = 8, d = 7;
   constexpr int NOUT = d * d * PP;  // 441
   __shared__ __attribute__((aligned(16))) float f1s[PP * C];     // [p][c]
   __shared__ __attribute__((aligned(16))) float Cs[PP * CORR_T];  // [p][t]
@@ -431,9 +429,9 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 //
 // Target maps come either as plain NHWC or (CHUNKED) as [H][C/32][W][32] -- one plane per MFMA K step: the 64 lanes of a
 // load (16 neighbouring window pixels x the four 8-channel quarters of the step) read one or two contiguous runs of up
-// to 640 bytes instead of 16 pieces 256 B apart.  (Rounds 2-3: [H][C/8][W][8], four 160-byte runs per quarter-wave;
-// CORR_KPLANE=8 builds it.)  The vector L1 looks up one line per
-// cycle, and with NHWC those lookups (64 per load instruction) were what the kernel waited on.
+// to 640 bytes instead of 16 pieces 256 B apart.  (Rounds 2-3: [H][C/8][W][8], four 160-byte runs per quarter-wave.)
+// The vector L1 looks up one line per cycle, and with NHWC those lookups (64 per load instruction) were what the kernel
+// waited on.
 // element-type traits of the MFMA correlation kernel below: fp16 -> v_mfma_f32_16x16x32_f16 (4 steps of 32 channels,
 // lane (q, .) supplies 8 channels per step); fp32 -> v_mfma_f32_16x16x4_f32 (exact fp32 products; the channel axis is
 // permuted so that ONE 16-byte load per lane feeds 4 MFMA steps on both operands: lane (q, .) of load g holds
@@ -441,9 +439,6 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // The fp32 variant is opt-in (dtype | RAMP_CORR_MFMA32): 2.1x faster than corr_kernel<float> (445 vs 940 us at E = 40k)
 // but its accumulation order is the MFMA's, not the reference kernel's channel-ordered fmaf chain that
 // corr_kernel<float> reproduces bit for bit -- so the exact-parity path stays the default.
-#ifndef CORR_NT
-#define CORR_NT 0     // (measured with csrc/update_mlp.hip's UPD_NT: the hint makes the step slower)
-#endif
 template <typename T> struct CorrMma;
 template <> struct CorrMma<_Float16> {
   typedef f16x8_t frag;
@@ -466,12 +461,9 @@ template <> struct CorrMma<_Float16> {
   static __device__ __forceinline__ void st(_Float16 *p, float v) { *p = (_Float16)v; }
   static __device__ __forceinline__ void st2(_Float16 *p, float a, float b) {
     typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-    // the [E, 896] volume is written once and read once (by the correlation MLP): streamed (CORR_NT=0: plain stores)
-#if CORR_NT
-    __builtin_nontemporal_store((h2v){(_Float16)a, (_Float16)b}, reinterpret_cast<h2v *>(p));
-#else
+    // the [E, 896] volume is written once and read once (by the correlation MLP), yet a plain store: the nontemporal hint
+    // was measured with the update chains' (csrc/update_mlp.hip, the note above mlp_gemm) and makes the step slower
     *reinterpret_cast<h2v *>(p) = (h2v){(_Float16)a, (_Float16)b};
-#endif
   }
 };
 template <> struct CorrMma<float> {
@@ -516,10 +508,6 @@ static __device__ __forceinline__ void corr_split2(const float x, _Float16 &h, _
   h = (_Float16)xh;
   l = (_Float16)((x - xh) * 2048.0f);
 }
-#ifndef CORR_X2_PGB
-#define CORR_X2_PGB 2     // pixel groups in flight (16 sixteen-byte loads per lane, as the fp16 kernel's four)
-#define CORR_X2_WAVES 3   // waves per SIMD of the register budget (132 VGPRs)
-#endif
 struct CorrX2 {};
 template <> struct CorrMma<CorrX2> {
   typedef f16x8_t frag;
@@ -744,8 +732,7 @@ static __device__ __forceinline__ void corr_edge_rows(const CorrParams &prm, con
           const int px = gx0 + tx, py = gy0 + ty;
           inb[u] = (t < Tn) && px >= 0 && px < W2 && py >= 0 && py < H2;
           const int cy = inb[u] ? py : 0, cx = inb[u] ? px : 0;
-          // load s, quarter q <-> channels [4 PER s + PER q, + PER) (fp16: = chunk 4 s + q of the [h][C/8][w][8] layout)
-#if CORR_KPLANE == 32
+          // load s, quarter q <-> channels [4 PER s + PER q, + PER)
           // [h][4][w][32]: K step s of a window row is one run of 64 bytes per pixel (18.8 vs 15.7 TB/s from the vector
           // L1 for the 10-wide windows, tools/mb/gather_patterns.hip P5 / P2).  fp32 features: [h][8][w][16] -- the same 64
           // bytes per pixel and load (load s of quarter q <-> channels 16 s + 4 q .. + 3), eight planes
@@ -757,13 +744,6 @@ static __device__ __forceinline__ void corr_edge_rows(const CorrParams &prm, con
                                  : f2 + ((size_t)cy * W2 + cx) * C + PER * q;
           const size_t sstride = CHUNKED ? (size_t)W2 * (KP * FE) : 4 * PER;
           const size_t part = (size_t)W2 * KP;
-#else
-          static_assert(FE == 1, "CORR_KPLANE=8 builds have no split planes");
-          const PT *pp = CHUNKED ? f2 + (((size_t)cy * (C / 8) + q) * W2 + cx) * 8
-                                 : f2 + ((size_t)cy * W2 + cx) * C + PER * q;
-          const size_t sstride = CHUNKED ? (size_t)4 * W2 * 8 : 4 * PER;
-          const size_t part = 0;
-#endif
 #pragma unroll
           for (int s = 0; s < STEPS; s++) bfr[u][s] = M::load_b(pp + s * sstride, part);
         }
@@ -895,9 +875,6 @@ __global__ void __launch_bounds__(256) pyramid_pack_kernel(const uint4 *__restri
   const int t = threadIdx.x;
   const int x0 = blockIdx.x * 16, y0 = blockIdx.y * 4;
   const int xl = t >> 4, c8 = t & 15;      // read role
-#if CORR_KPLANE != 32
-  const int wc = t >> 4, wx = t & 15;      // write role: chunk wc, pixel wx
-#endif
   float sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int r = 0; r < 4; r++) {
     const int y = y0 + r;
@@ -912,14 +889,8 @@ __global__ void __launch_bounds__(256) pyramid_pack_kernel(const uint4 *__restri
     __syncthreads();
     tile[c8][xl] = v;
     __syncthreads();
-#if CORR_KPLANE == 32
-    {
-      const int ws = t >> 6, px = (t >> 2) & 15, wq = t & 3;     // write role: K step, pixel, quarter -- 1 KB runs
-      out1[(((size_t)y * 4 + ws) * W + x0 + px) * 4 + wq] = tile[4 * ws + wq][px];
-    }
-#else
-    out1[((size_t)y * 16 + wc) * W + x0 + wx] = tile[wc][wx];
-#endif
+    const int ws = t >> 6, px = (t >> 2) & 15, wq = t & 3;     // write role: K step, pixel, quarter -- 1 KB runs
+    out1[(((size_t)y * 4 + ws) * W + x0 + px) * 4 + wq] = tile[4 * ws + wq][px];
   }
   // 4 neighbouring pixels = lanes t, t^16, t^32, t^48 of one wave
 #pragma unroll
@@ -932,11 +903,7 @@ __global__ void __launch_bounds__(256) pyramid_pack_kernel(const uint4 *__restri
     __half2 *h = reinterpret_cast<__half2 *>(&o);
 #pragma unroll
     for (int k = 0; k < 4; k++) h[k] = __floats2half2_rn(sum[2 * k] * 0.0625f, sum[2 * k + 1] * 0.0625f);
-#if CORR_KPLANE == 32
     out4[(((size_t)blockIdx.y * 4 + (c8 >> 2)) * (W / 4) + (x0 + xl) / 4) * 4 + (c8 & 3)] = o;
-#else
-    out4[((size_t)blockIdx.y * 16 + c8) * (W / 4) + (x0 + xl) / 4] = o;
-#endif
   }
 }
 
@@ -1038,7 +1005,7 @@ int ramp_debug_corr_trace(unsigned long long *host, int n_waves) {     // host [
   return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_corr_trace), (size_t)n_waves * 8 * 8) == hipSuccess ? 0 : -1;
 }
 #endif
-int ramp_corr_kplane(void) { return CORR_KPLANE; }
+int ramp_corr_kplane(void) { return CORR_KPLANE; }     // (public ABI: the binding refuses a library that packs another width)
 
 int ramp_pyramid_pack(const void *fmap, void *level1, void *level4, int H, int W, int C, int dtype,
                       void *stream) {

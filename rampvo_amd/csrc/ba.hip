@@ -144,9 +144,7 @@ __global__ void __launch_bounds__(256)
 // with all loads in flight at once (walking them from memory is one dependent round trip per edge);
 // the sums run over the staged records in segment order.
 #define BA_PCHUNK 32
-#ifndef BA_PBATCH
-#define BA_PBATCH 48    // (128 / 224 measured on MI355X: 126 / 139 us per BA call against 124 -- the pair role is not the long one)
-#endif
+constexpr int BA_PBATCH = 48;   // (128 / 224 measured on MI355X: 126 / 139 us per BA call against 124 -- the pair role is not the long one)
 // FUSED: one thread per edge of the chunk recomputes its record (ein); otherwise the records are read from rec
 template <bool FUSED>
 __device__ __forceinline__ void
@@ -160,18 +158,14 @@ __device__ __forceinline__ void
   // The merged launch's workgroups are sized for the pair role (156 sums); a patch needs n6 + 2 threads.  Waves without a
   // column leave at once (the barrier counts live waves only): a CU holds 32 waves, and 2,100 patch workgroups of four
   // live waves each were a second round of workgroups behind 2,048 places -- with one live wave they are all resident.
-#ifndef BA_PATCH_KEEP_WAVES
   // (whole waves leave in front of the barriers below: s_barrier on gfx9 / CDNA counts the waves that are still alive, so the
   // remaining ones synchronise among themselves.  This library is built for gfx950 only; a target whose barrier counts
-  // launched waves would hang here -- hence the check, and -DBA_PATCH_KEEP_WAVES as the portable form)
+  // launched waves would hang here -- hence the check)
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__) && !defined(__gfx90a__)
-#error "ba_patch_body retires whole waves before __syncthreads(): valid on gfx9 / CDNA barriers only (build with -DBA_PATCH_KEEP_WAVES)"
+#error "ba_patch_body retires whole waves before __syncthreads(): valid on gfx9 / CDNA barriers only"
 #endif
   const int nthr = min((int)blockDim.x, ((n6 + 2 + 63) / 64) * 64);
   if ((int)threadIdx.x >= nthr) return;
-#else
-  const int nthr = blockDim.x;
-#endif
   const int tid = threadIdx.x;
   const int s0 = seg[g], s1 = seg[g + 1];
   const int a = tid / 6, c = tid - a * 6;

@@ -16,9 +16,7 @@
 #include <string.h>
 #include <stdlib.h>
 
-#ifndef TRK_EB
-#define TRK_EB 1024        // factors per workgroup of the edit kernels (256 threads x 4 passes)
-#endif
+constexpr int TRK_EB = 1024;   // factors per workgroup of the edit kernels (256 threads x 4 passes)
 #define TRK_MAXBUF 10
 
 struct TrkEdit {

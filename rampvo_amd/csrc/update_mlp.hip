@@ -22,56 +22,22 @@
 #define MKS (MD / 32)          // K steps per 384-wide layer
 #define MNTW 3                 // 16-column tiles per wave
 #define MWAVES 8
-#ifndef MLP_PREFETCH_DEFAULT
-#define MLP_PREFETCH_DEFAULT 0
-#endif
-#ifndef GRU_PF
-#define GRU_PF 2
-#endif
+constexpr int MLP_PREFETCH_DEFAULT = 0;   // weight-fragment ring depth of mlp_gemm where the caller names none (0: loads in the K loop)
+constexpr int GRU_PF = 2;                 // ring depth of the gru kernel's K loops (see upd_gru_kernel)
+#define MLP_UNROLL 2                      // unroll factor of mlp_gemm's K loop without a ring (a pragma argument: a macro)
+constexpr int BIG_PF = 1;                 // ring depth of big_gemm; measured: 2 is 2 % slower on the whole operator (128 / 146 VGPRs),
+                                          // 1 is the round-2 kernel
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
 
-// Nontemporal hints on the operator's state traffic (the [E,384] fp32 residual stream in and out of every chain, the
-// [E,896] correlation rows, the [E,768] [f|g] rows: ~1.3 GB per update) -- VERDICT r3 item 1a -- measured on MI355X
-// (tools/ab_build.sh, alternating builds on one box): with the hint on EVERY such access the step is 12 % SLOWER
-// (899 vs 1020 kf/s; sequential 730 vs 824): a chain's 61 MB output is the next chain's input and is served from the
-// memory-side cache -- the hint takes that away.  UPD_NT = 1 is that build; UPD_NT_DEAD = 1 hints only the loads of rows
-// nobody reads again (the correlation rows, the previous hidden state), see DESIGN.md section 8.
-#ifndef UPD_NT
-#define UPD_NT 0
-#endif
-#ifndef UPD_NT_DEAD
-#define UPD_NT_DEAD 0
-#endif
-template <typename T>
-__device__ __forceinline__ T ld_dead(const T *p) {
-#if UPD_NT || UPD_NT_DEAD
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
-template <typename T>
-__device__ __forceinline__ T ld_st(const T *p) {
-#if UPD_NT
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
-}
-template <typename T>
-__device__ __forceinline__ void st_st(T *p, T v) {
-#if UPD_NT
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
-__device__ __forceinline__ float2 ld_st2(const float *p) { const f2 v = ld_st(reinterpret_cast<const f2 *>(p)); return make_float2(v[0], v[1]); }
-__device__ __forceinline__ void st_st2(float *p, float2 v) { st_st(reinterpret_cast<f2 *>(p), (f2){v.x, v.y}); }
+// The operator's state traffic (the [E,384] fp32 residual stream in and out of every chain, the [E,896] correlation rows,
+// the [E,768] [f|g] rows: ~1.3 GB per update) is plain loads and stores ON PURPOSE.  Nontemporal hints on it -- VERDICT r3
+// item 1a -- were measured on MI355X (tools/ab_build.sh, alternating builds on one box): with the hint on EVERY such access
+// the step is 12 % SLOWER (899 vs 1020 kf/s; sequential 730 vs 824): a chain's 61 MB output is the next chain's input and is
+// served from the memory-side cache -- the hint takes that away.  Hinting only the loads of rows nobody reads again (the
+// correlation rows, the previous hidden state) gained nothing either, see DESIGN.md section 8.
 
 __device__ __forceinline__ float h_round(float v) { return (float)(_Float16)v; }
 // the gate's input was rounded to fp16 one line earlier: the fast exp / reciprocal (~1 ulp) are exact
@@ -91,9 +57,6 @@ __device__ __forceinline__ void mlp_gemm(const _Float16 *Xs, const _Float16 *con
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
       for (int nt = 0; nt < MNTW; nt++) acc[b][mt][nt] = (f4){0.f, 0.f, 0.f, 0.f};
-#ifndef MLP_UNROLL
-#define MLP_UNROLL 2
-#endif
   auto wfrag = [&](int b, int ks, int nt) {
     return *reinterpret_cast<const h8 *>(wp[b] + (((size_t)ks * (MD / 16) + wave * MNTW + nt) * 64 + lane) * 8);
   };
@@ -302,60 +265,6 @@ __device__ __forceinline__ void tile_ln(f4 (&v)[MT][MNTW], const float *__restri
   }
 }
 
-// The same reduction for kernels on a 128-register budget (two workgroups per CU): branch-free -- the four quarter-lanes of
-// a row store the same partial sum -- so that the scheduling barriers bound what is in flight per row tile (the
-// straight-line version above has every table read of the five row tiles live at once: 66 spilled registers).
-// Identical arithmetic and order.
-template <int MT>
-__device__ __forceinline__ void tile_ln_lean(f4 (&v)[MT][MNTW], const float *__restrict__ w, const float *__restrict__ b,
-                                             float eps, float *T1, float *T2, int wave, int q, int j, int col0) {
-  float mean[MT], rstd[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; mt++) {
-    float s = 0.f;
-#pragma unroll
-    for (int nt = 0; nt < MNTW; nt++) s += (v[mt][nt][0] + v[mt][nt][1]) + (v[mt][nt][2] + v[mt][nt][3]);
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    T1[(mt * 16 + j) * MWAVES + wave] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int mt = 0; mt < MT; mt++) {
-    __builtin_amdgcn_sched_barrier(0);
-    const f4 a = *reinterpret_cast<const f4 *>(T1 + (mt * 16 + j) * MWAVES), c = *reinterpret_cast<const f4 *>(T1 + (mt * 16 + j) * MWAVES + 4);
-    mean[mt] = ((((((a[0] + a[1]) + a[2]) + a[3]) + c[0]) + c[1]) + c[2] + c[3]) * (1.0f / MD);
-    float s = 0.f;
-#pragma unroll
-    for (int nt = 0; nt < MNTW; nt++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const float d = v[mt][nt][i] - mean[mt];
-        s += d * d;
-      }
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    T2[(mt * 16 + j) * MWAVES + wave] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int mt = 0; mt < MT; mt++) {
-    __builtin_amdgcn_sched_barrier(0);
-    const f4 a = *reinterpret_cast<const f4 *>(T2 + (mt * 16 + j) * MWAVES), c = *reinterpret_cast<const f4 *>(T2 + (mt * 16 + j) * MWAVES + 4);
-    rstd[mt] = 1.0f / sqrtf(((((((a[0] + a[1]) + a[2]) + a[3]) + c[0]) + c[1]) + c[2] + c[3]) * (1.0f / MD) + eps);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int nt = 0; nt < MNTW; nt++) {
-    const f4 wv = *reinterpret_cast<const f4 *>(w + col0 + nt * 16 + 4 * q), bv = *reinterpret_cast<const f4 *>(b + col0 + nt * 16 + 4 * q);
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) v[mt][nt][i] = (v[mt][nt][i] - mean[mt]) * rstd[mt] * wv[i] + bv[i];
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
 #ifdef GRU_TRACE
 __device__ long long g_gru_trace[32 * 4096];
 #define GT(k) do { if (threadIdx.x == 0) g_gru_trace[blockIdx.x * 32 + (k)] = wall_clock64(); } while (0)
@@ -400,7 +309,7 @@ __global__ void __launch_bounds__(64 * MWAVES) upd_gru_kernel(const GruParams p)
     const int row = row0 + mt * 16 + j;
     roff[mt] = (size_t)(row < pE ? row : pE - 1) * MD;
 #pragma unroll
-    for (int nt = 0; nt < MNTW; nt++) res[mt][nt] = ld_st(reinterpret_cast<const f4 *>(p.x32 + roff[mt] + cq + nt * 16));
+    for (int nt = 0; nt < MNTW; nt++) res[mt][nt] = *reinterpret_cast<const f4 *>(p.x32 + roff[mt] + cq + nt * 16);
   }
   if (p.add0_t) {                               // uniform
 #pragma unroll
@@ -506,7 +415,7 @@ __global__ void __launch_bounds__(64 * MWAVES) upd_gru_kernel(const GruParams p)
 #pragma unroll
         for (int nt = 0; nt < MNTW; nt++) {
           const f4 v = res[mt][nt];
-          st_st(reinterpret_cast<f4 *>(p.out32 + roff[mt] + cq + nt * 16), v);
+          *reinterpret_cast<f4 *>(p.out32 + roff[mt] + cq + nt * 16) = v;
           if (p.relu_t)
             *reinterpret_cast<h4 *>(p.relu_t + roff[mt] + cq + nt * 16) =
                 (h4){(_Float16)fmaxf(v[0], 0.f), (_Float16)fmaxf(v[1], 0.f), (_Float16)fmaxf(v[2], 0.f), (_Float16)fmaxf(v[3], 0.f)};
@@ -735,19 +644,14 @@ __global__ void __launch_bounds__(64 * MWAVES) __attribute__((amdgpu_waves_per_e
     for (int ks0 = 0; ks0 < nks_total; ks0 += MKS) {
       const int nks = min(MKS, nks_total - ks0);
       const int v8 = nks * 4;                                  // 16-byte vectors per row of this chunk
-#ifdef CTAIL_SKIP_STAGE                                        // (diagnostic: what the staging of Linear1's operand costs)
-      if (ks0 == 0)
-#endif
       for (int i = tid; i < MBM * v8; i += 64 * MWAVES) {
         const int r = i / v8, c8 = i - r * v8;
         h8 v = (h8){0, 0, 0, 0, 0, 0, 0, 0};
-        if (row0 + r < pE) v = ld_dead(reinterpret_cast<const h8 *>(p.corr + (size_t)(row0 + r) * p.corr_k + ks0 * 32 + 8 * c8));
+        if (row0 + r < pE) v = *reinterpret_cast<const h8 *>(p.corr + (size_t)(row0 + r) * p.corr_k + ks0 * 32 + 8 * c8);
         *reinterpret_cast<h8 *>(Xs + r * MXS + 8 * c8) = v;
       }
       __syncthreads();
-#ifndef CTAIL_SKIP_L1                                          // (diagnostic: Linear1's products)
       mlp_gemm_chunk(Xs, p.w1, wave, lane, nks, ks0, acc);
-#endif
       __syncthreads();                                         // before the tile is overwritten
     }
 #pragma unroll
@@ -848,8 +752,7 @@ __global__ void __launch_bounds__(64 * MWAVES) __attribute__((amdgpu_waves_per_e
       if (ra >= 0) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-          const f2 a_ = ld_dead(reinterpret_cast<const f2 *>(p.net + (size_t)ra * MD + 2 * lane + 128 * k));
-          const float2 a = make_float2(a_[0], a_[1]);
+          const float2 a = *reinterpret_cast<const float2 *>(p.net + (size_t)ra * MD + 2 * lane + 128 * k);
           v[k][0] = a.x; v[k][1] = a.y;
         }
       }
@@ -869,7 +772,7 @@ __global__ void __launch_bounds__(64 * MWAVES) __attribute__((amdgpu_waves_per_e
       row_ln(v, p.norm_w, p.norm_b, p.norm_eps, lane);
 #pragma unroll
       for (int k = 0; k < 3; k++)
-        st_st2(p.net_out + (size_t)row * MD + 2 * lane + 128 * k, make_float2(v[k][0], v[k][1]));
+        *reinterpret_cast<float2 *>(p.net_out + (size_t)row * MD + 2 * lane + 128 * k) = make_float2(v[k][0], v[k][1]);
     }
     __syncthreads();
   }
@@ -985,9 +888,6 @@ __device__ __forceinline__ void big_zero(f4 (&acc)[NMT][NTW]) {
 // accumulators).  The weight fragments of K step ks + 1 are ISSUED before the matrix work of step ks (the scheduling
 // barrier keeps the compiler from sinking them to their first use, which exposed their full L2 latency every step);
 // the A fragment of row tile mt + 1 is read from LDS while tile mt multiplies.
-#ifndef BIG_PF
-#define BIG_PF 1   // measured: 2 is 2 % slower on the whole operator (128 / 146 VGPRs), 1 is the round-2 kernel
-#endif
 template <int NMT, int NTW, bool SWAP = true>
 __device__ __forceinline__ void big_gemm(const _Float16 *Xs, const _Float16 *wp, int nks, int w_ks0, int wave, int lane,
                                          f4 (&acc)[NMT][NTW]) {
@@ -1046,11 +946,10 @@ __device__ __forceinline__ void big_store_tile(_Float16 *Xs, const f4 (&acc)[NMT
 }
 
 __device__ __forceinline__ float4 ldg4(const float *base, unsigned off, int nt) {
-  const f4 v = ld_st(reinterpret_cast<const f4 *>(reinterpret_cast<const char *>(base) + off + nt * 64));
-  return make_float4(v[0], v[1], v[2], v[3]);
+  return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(base) + off + nt * 64);
 }
 __device__ __forceinline__ void stg4(float *base, unsigned off, int nt, float4 v) {
-  st_st(reinterpret_cast<f4 *>(reinterpret_cast<char *>(base) + off + nt * 64), (f4){v.x, v.y, v.z, v.w});
+  *reinterpret_cast<float4 *>(reinterpret_cast<char *>(base) + off + nt * 64) = v;
 }
 __device__ __forceinline__ void stg4h(_Float16 *base, unsigned off_f32, int nt, float4 v) {   // fp16 row of the same shape
   *reinterpret_cast<hh4 *>(reinterpret_cast<char *>(base) + (off_f32 >> 1) + nt * 32) =
@@ -1098,7 +997,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) upd_nbr_big_kernel(const NbrP
     for (int i = 0; i < RPW; i++) {
       const float *b = p.net_in + (size_t)(src[i] >= 0 ? src[i] : 0) * MD + 2 * lane;
 #pragma unroll
-      for (int k = 0; k < 3; k++) v[i][k] = ld_st2(b + 128 * k);
+      for (int k = 0; k < 3; k++) v[i][k] = *reinterpret_cast<const float2 *>(b + 128 * k);
     }
 #pragma unroll
     for (int i = 0; i < RPW; i++)
@@ -1165,7 +1064,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) upd_fg_big_kernel(const FgPar
       const int row = row0 + wave + i * NW;
       const float *b = p.x32 + (size_t)(row < pE ? row : pE - 1) * MD + 2 * lane;
 #pragma unroll
-      for (int k = 0; k < 3; k++) v[i][k] = ld_st2(b + 128 * k);
+      for (int k = 0; k < 3; k++) v[i][k] = *reinterpret_cast<const float2 *>(b + 128 * k);
     }
     if (p.add_t) {                                       // uniform
       h2 t[RPW][3];
@@ -1187,7 +1086,7 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) upd_fg_big_kernel(const FgPar
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         if (live_row && p.x32_out)
-          st_st2(p.x32_out + (size_t)row * MD + 2 * lane + 128 * k, v[i][k]);
+          *reinterpret_cast<float2 *>(p.x32_out + (size_t)row * MD + 2 * lane + 128 * k) = v[i][k];
         const float2 a = live_row ? v[i][k] : make_float2(0.f, 0.f);
         *reinterpret_cast<h2 *>(Xs + r * MXS + 2 * lane + 128 * k) = (h2){(_Float16)a.x, (_Float16)a.y};
       }
@@ -1210,9 +1109,9 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) upd_fg_big_kernel(const FgPar
 #pragma unroll
       for (int mt = 0; mt < NMT; mt++)
         if ((live >> mt) & 1)
-          st_st(reinterpret_cast<hh4 *>(reinterpret_cast<char *>(dst) + (ro[mt] - cfix) + nt * 32),
-                (hh4){(_Float16)(acc[mt][nt][0] + b.x), (_Float16)(acc[mt][nt][1] + b.y),
-                      (_Float16)(acc[mt][nt][2] + b.z), (_Float16)(acc[mt][nt][3] + b.w)});
+          *reinterpret_cast<hh4 *>(reinterpret_cast<char *>(dst) + (ro[mt] - cfix) + nt * 32) =
+              (hh4){(_Float16)(acc[mt][nt][0] + b.x), (_Float16)(acc[mt][nt][1] + b.y),
+                    (_Float16)(acc[mt][nt][2] + b.z), (_Float16)(acc[mt][nt][3] + b.w)};
     }
   }
 }
@@ -1326,20 +1225,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
   }
   // ---- f = x Wf' + bf on the same tile
   big_zero<NMT, NTW>(acc);
-#ifndef SAGG_SKIP_F                                  // (diagnostic builds: tools/mb_softagg.py)
   big_gemm<NMT, NTW, false>(Xs, p.wf, MKS, 0, wave, lane, acc);
-#endif
-#ifdef SAGG_SKIP_SWEEP
-  {
-    float t = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < NMT; mt++)
-#pragma unroll
-      for (int nt = 0; nt < NTW; nt++) t += acc[mt][nt][0] + acc[mt][nt][1] + acc[mt][nt][2] + acc[mt][nt][3] + (float)gp[mt][nt][0][0] + (float)gp[mt][nt][0][1] + (float)gp[mt][nt][1][0] + (float)gp[mt][nt][1][1];
-    if (t == 123.f) p.frag[tid] = t;
-    return;
-  }
-#endif
   // ---- where this lane block's runs start, and which of its positions exist
   unsigned startm = 0, validm = 0;
   {
@@ -1561,9 +1447,7 @@ __global__ void __launch_bounds__(512) upd_linear_kernel(const _Float16 *__restr
 // the wide-tile chain kernels from 16,384 factors on (below, and where E x 384 floats overflow 32-bit offsets: the 64-row
 // kernels); their row tiles per workgroup are the measured optima of each chain at the bench size
 #define NBR_NMT 5
-#ifndef FG_BEST
-#define FG_BEST 6
-#endif
+constexpr int FG_BEST = 6;
 static bool use_big(int E) { return E >= 16384 && (long)E * MD * 4 < (1l << 32); }
 
 template <typename KernelT, typename ParamsT>

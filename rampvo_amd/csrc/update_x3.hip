@@ -30,6 +30,14 @@
 #define XNTW 3                 // 16-column tiles per wave
 #define XWAVES 8
 #define XFRAG 1024             // halfs per packed fragment pair (two planes x 64 lanes x 8)
+constexpr int X3_PF = 1;       // K steps of weight fragments in flight ahead of the matrix work (0: loaded where used)
+constexpr int X3_GRU_PF = 0;   // (the gru launch holds the residual stream and the gate in registers: no room for a ring)
+// Tiles (measured in the fp32 frame, profiles/r06_f_x3_tiles_ab.txt: 64-row tiles / one workgroup per CU 496 kf/s; 32-row tiles at
+// four waves per SIMD for the three lighter chains + 48 rows for gru 519): the chains are bound by their row traffic at one
+// workgroup per CU, two smaller ones overlap it with the other's matrix work.  Row-local arithmetic: the tile size changes no value.
+constexpr int X3_MT = 2;       // 16-row tiles per workgroup of the three lighter chains
+constexpr int X3_GRU_MT = 3;   // ... of the gru chain
+#define X3_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))   // four waves per SIMD: two workgroups per CU
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -58,12 +66,6 @@ __device__ __forceinline__ float x3_inv_scale(const _Float16 *wp, int nks) {
 // acc[mt][nt] (+)= X[16 MT x 32 nks] W[:, 32 wks0 ..)^T for this wave's 48 columns, transposed accumulators (lane (q, j):
 // row j of row tile mt, columns 4q .. 4q+3 of column tile nt).  One K step = 6 fragment loads (two planes x three column
 // tiles), 2 MT LDS reads, 9 MT matrix instructions.
-#ifndef X3_GRU_PF
-#define X3_GRU_PF 0            // (the gru launch holds the residual stream and the gate in registers: no room for a ring)
-#endif
-#ifndef X3_PF
-#define X3_PF 1                // K steps of weight fragments in flight ahead of the matrix work (0: loaded where used)
-#endif
 template <int MT>
 __device__ __forceinline__ void x3_mma_step(const _Float16 *Xh, const _Float16 *Xl, int ks, int q, int j, const h8 (&wh)[XNTW],
                                             const h8 (&wl)[XNTW], f4 (&acc)[MT][XNTW]) {
@@ -76,14 +78,6 @@ __device__ __forceinline__ void x3_mma_step(const _Float16 *Xh, const _Float16 *
     ah[mt] = *reinterpret_cast<const h8 *>(Xh + off);
     al[mt] = *reinterpret_cast<const h8 *>(Xl + off);
   }
-#if defined(X3_DIAG_NOMMA)                                    // (diagnostic build: operand traffic without the matrix work)
-#pragma unroll
-  for (int nt = 0; nt < XNTW; nt++)
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) acc[mt][nt][i] += (float)wh[nt][i] + (float)wl[nt][i + 4] + (float)ah[mt][i] + (float)al[mt][i + 4];
-#else
 #pragma unroll
   for (int nt = 0; nt < XNTW; nt++) {
     const h8 ws = wh[nt] * s11;
@@ -94,7 +88,6 @@ __device__ __forceinline__ void x3_mma_step(const _Float16 *Xh, const _Float16 *
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[nt], ah[mt], acc[mt][nt], 0, 0, 0);
   }
-#endif
 }
 
 // NKS K steps, fully unrolled, the weight fragments of steps ks+1 .. ks+PF in flight while the matrix cores work on step ks (a
@@ -108,11 +101,7 @@ __device__ __forceinline__ void x3_gemm_static(const _Float16 *Xh, const _Float1
   const _Float16 *wb0 = wp + ((size_t)wks0 * (XD / 16) + wave * XNTW) * XFRAG + lane * 8;
   h8 rh[PF + 1][XNTW], rl[PF + 1][XNTW];
   auto wload = [&](int ks, h8 (&wh)[XNTW], h8 (&wl)[XNTW]) {
-#if defined(X3_DIAG_NOW)                                      // (diagnostic build: every K step reads the first step's fragments)
-    const _Float16 *wb = wb0 + (size_t)(ks & 0) * (XD / 16) * XFRAG;
-#else
     const _Float16 *wb = wb0 + (size_t)ks * (XD / 16) * XFRAG;
-#endif
 #pragma unroll
     for (int nt = 0; nt < XNTW; nt++) {
       wh[nt] = *reinterpret_cast<const h8 *>(wb + nt * XFRAG);
@@ -259,20 +248,6 @@ __device__ __forceinline__ void x3_tile_ln(f4 (&v)[MT][XNTW], const float *__res
   }
 }
 
-// Workgroups that start together run their phases together: every CU gathers rows (HBM saturated, matrix cores idle), then every
-// CU multiplies (HBM idle).  With several workgroups per CU the second one of each CU (dispatch order: 256 workgroups fill the
-// first slot of every CU) starts X3_STAGGER x ~4k cycles late, so that one's row traffic runs beside the other's matrix work.
-#ifndef X3_STAGGER
-#define X3_STAGGER 0
-#endif
-__device__ __forceinline__ void x3_stagger() {
-#if X3_STAGGER > 0
-  if ((blockIdx.x >> 8) & 1) {
-#pragma unroll 1
-    for (int i = 0; i < X3_STAGGER; i++) __builtin_amdgcn_s_sleep(64);
-  }
-#endif
-}
 #define X3_COMMON(MT_)                                                                                      \
   constexpr int ROWS = 16 * (MT_);                                                                          \
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];                                  \
@@ -282,26 +257,8 @@ __device__ __forceinline__ void x3_stagger() {
   const int pE = p.dyn ? p.dyn[RAMP_DYN_E] : p.E;                                                           \
   if (row0 >= pE) return;                                                                                   \
   const int cq = wave * (16 * XNTW) + 4 * q;                                                                \
-  x3_stagger();                                                                                             \
   (void)tid; (void)j; (void)cq
 
-// Tiles (measured in the fp32 frame, profiles/r06_f_x3_tiles_ab.txt: 64-row tiles / one workgroup per CU 496 kf/s; 32-row tiles at
-// four waves per SIMD for the three lighter chains + 48 rows for gru 519): the chains are bound by their row traffic at one
-// workgroup per CU, two smaller ones overlap it with the other's matrix work.  Row-local arithmetic: the tile size changes no value.
-#ifndef X3_MT
-#define X3_MT 2
-#endif
-#ifndef X3_OCC
-#define X3_OCC 4
-#endif
-#ifndef X3_GRU_MT
-#define X3_GRU_MT 3
-#endif
-#if X3_OCC > 0
-#define X3_ATTR __attribute__((amdgpu_waves_per_eu(X3_OCC, X3_OCC)))
-#else
-#define X3_ATTR
-#endif
 static size_t x3_lds_bytes(int mt, bool ln) { return (size_t)2 * 16 * mt * XS * 2 + (ln ? (size_t)2 * 16 * mt * XWAVES * 4 : 0); }
 
 // ------------------------------------------------------------------ c1 / c2 (ramp/net.py:77-82)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """the two BasicEncoder4 towers alone (10 launches per frame behind the LSTM step): HIP events around 50 eager passes and
-around 50 replays of a hipGraph of one pass.  With tools/mb_variants.sh and -DHZ_SKIP_MMA / -DHZ_SKIP_EPI: what the MFMA
-phase and the epilogue of the LDS-tiled conv kernel cost."""
+around 50 replays of a hipGraph of one pass.  (The per-phase costs of the LDS-tiled conv kernel in DESIGN section 8.00 came from
+this script on diagnostic builds that have been retired since.)
+
+usage: mb_towers.py [SingleScale|MultiScale] [H W]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
