@@ -987,6 +987,39 @@ int ramp_trajectory_resolve(const float *kf_poses, const int64_t *kf_tstamps, in
                             int nlog, const float *extra_log, int n_extra, int T, float *out, int32_t *ws, int32_t *status,
                             void *stream);
 
+/* ---------------------------------------------------------------- poses at any time (csrc/interp.hip)
+ *
+ * ramp_se3_interp: the SE(3) geodesic through the knots of a trajectory, evaluated at Q time stamps, as two launches (one
+ * lane per segment, then one lane per query).
+ *   knots [T][7] (t, q) as ramp_se3_*; times [T] float64, non-decreasing; query [Q] float64.  Per query t:
+ *     s     = the largest index with times[s] <= t, clamped to [0, T - 2]
+ *     alpha = (t - times[s]) / (times[s + 1] - times[s]), formed in float64 and rounded to fp32 once; a clamped segment of
+ *             zero length: alpha = 0 for t < times[s], else 1
+ *     xi_s  = Log(knots[s + 1] * knots[s]^-1)   (the left increment, tangent order translation 3, rotation 3)
+ *     out   = Exp(alpha * xi_s) * knots[s]      (the arithmetic of ramp_se3_log / _exp / _mul / _inv)
+ *     twist = xi_s / (times[s + 1] - times[s]) [Q][6], optional (NULL): the segment's constant left twist; zero for a segment
+ *             of zero length and for T == 1
+ *   Outside [times[0], times[T - 1]]: alpha is clamped to [0, 1], or with RAMP_INTERP_EXTRAPOLATE the end segment's screw
+ *   motion is continued.  T == 1: every query returns the knot.
+ *   flags: RAMP_INTERP_EXTRAPOLATE; RAMP_INTERP_ROW_STORES (every lane stores its own 28- / 24-byte row instead of the tile
+ *   leaving through LDS as contiguous full-width stores: the same bits, kept for tools/pose_query_cost.py).
+ *   seg_ws: ramp_se3_interp_workspace_bytes(T) bytes, 16-byte aligned (the segments' increments, twists and lengths).
+ *   status: device int32 [4], written by the call: [0] bits (RAMP_INTERP_BAD_TIMES: a time stamp of `times` decreases or is
+ *   not finite), [1] queries below times[0], [2] queries above times[T - 1], [3] NaN queries.
+ * Failures follow the convention of ramp_ba_covariance (NaN, never a plausible number; the return value stays RAMP_OK, it is
+ * an outcome of the data): RAMP_INTERP_BAD_TIMES makes every row of out and twist NaN; a NaN query makes its own row NaN and
+ * is counted.  T < 1 or Q < 0: RAMP_EINVAL.  Q == 0: RAMP_OK, nothing is launched and nothing written, status included.
+ * A row is a function of its own query alone: its bits depend neither on Q, nor on its position, nor on the queries' order.
+ * ramp_se3_interp_lds_knots(): the largest T whose knot times the query launch stages in LDS; above it the search reads
+ * global memory.                                                                                                       */
+#define RAMP_INTERP_EXTRAPOLATE 1
+#define RAMP_INTERP_ROW_STORES 2
+#define RAMP_INTERP_BAD_TIMES 1 /* status[0] bit 0 */
+size_t ramp_se3_interp_workspace_bytes(int T);
+int ramp_se3_interp_lds_knots(void);
+int ramp_se3_interp(const float *knots, const double *times, int T, const double *query, int Q, int flags, float *out,
+                    float *twist, void *seg_ws, size_t seg_ws_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -98,6 +98,7 @@ class Ramp_vo:
         self._pose_ring = None          # track_dev.PoseRing once pose_stream() has switched publishing on
         self._pose_rings_retired = []   # (launches already queued may still write to a ring that was replaced)
         self._traj_extra = (None, None) # trajectory(): the host's delta entries on the device, re-uploaded when they have grown
+        self._traj_times = (None, None) # poses_at(): the frames' time stamps on the device (float64), re-uploaded per new frame count
         self._traj_status = None
         self.lmbda = torch.as_tensor([1e-4], device=dev)
         self.load_weights(network)
@@ -541,6 +542,41 @@ class Ramp_vo:
         if int(status.cpu()) & track_dev.TRAJ_UNRESOLVED:
             raise RuntimeError("trajectory(): a frame is neither a keyframe nor reachable through the delta chain")
         return poses, tst
+
+    def poses_at(self, times, extrapolate=False, twist=False, as_tensor=False):
+        """The trajectory at ANY time stamps: ``trajectory(as_tensor=True)`` and, behind it on the same stream, the SE(3)
+        geodesic between the frames' poses (ops.se3_interp: ``X(t) = Exp(alpha Log(X[s+1] X[s]^-1)) X[s]`` on the segment
+        [tlist[s], tlist[s+1]] that holds t) -- one pose per event, per IMU sample, per row of a fixed-rate file.  Same
+        convention as ``trajectory()``: inverse poses (interpolating the inverses gives the inverse of the interpolated
+        pose).  ``times``: array or tensor, in the unit of the time stamps the frames were fed with; outside their range
+        the end pose is held, or with ``extrapolate`` the end segment's motion is continued.  ``twist=True`` adds the
+        segment's constant left twist [Q,6] per query.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call); the frames' time
+        stamps are uploaded once per new frame count.  ``as_tensor=True``: device tensors ``(poses [Q,7], twist or None,
+        status int32 [4])``, ordered on the current stream, nothing synchronised (status: ops.se3_interp; trajectory()'s own
+        word stays in ``_traj_status``).  Otherwise numpy ``(poses, twist or None)``, which waits for that one result and
+        raises when the frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
+        knots, _ = self.trajectory(as_tensor=True)
+        dev = self.device
+        with torch.no_grad():
+            key, tdev = self._traj_times
+            if key != (id(self.tlist), len(self.tlist), self.tlist[-1] if self.tlist else None):
+                tdev = self._upload(np.asarray(self.tlist, dtype=np.float64).reshape(-1))
+                self._traj_times = ((id(self.tlist), len(self.tlist), self.tlist[-1] if self.tlist else None), tdev)
+            if isinstance(times, torch.Tensor):
+                q = times.to(device=dev, dtype=torch.float64).reshape(-1)
+            else:
+                q = self._upload(np.asarray(times, dtype=np.float64).reshape(-1))
+            poses, tw, status = ops.se3_interp(knots, tdev, q, extrapolate=extrapolate, twist=twist)
+        if as_tensor:
+            return poses, tw, status
+        words = torch.cat([status, self._traj_status]).cpu()          # (the one wait)
+        if int(words[4]) & track_dev.TRAJ_UNRESOLVED:
+            raise RuntimeError("poses_at(): a frame is neither a keyframe nor reachable through the delta chain")
+        if int(words[0]) & 1:
+            raise RuntimeError("poses_at(): the frames' time stamps decrease or are not finite")
+        return poses.cpu().numpy(), (tw.cpu().numpy() if twist else None)
 
     # --------------------------------------------------------------- uncertainty
     def _window_query(self, name, with_map=False, then=None):

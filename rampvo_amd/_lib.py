@@ -21,6 +21,7 @@ RAMP_CONV_FP8 = 0x40
 RAMP_IN_F32, RAMP_CONV_DIRECT, RAMP_CORR_MFMA32, RAMP_CORR_X2 = 0x10, 0x20, 0x40, 0x80
 RAMP_CONV_X3 = 0x80
 RAMP_NCHW, RAMP_NHWC, RAMP_NHWC32 = 0, 1, 2
+RAMP_INTERP_EXTRAPOLATE, RAMP_INTERP_ROW_STORES, RAMP_INTERP_BAD_TIMES = 1, 2, 1
 KPLANE = 32            # channels per plane of the packed correlation target maps: [h][128 / KPLANE][w][KPLANE]
 
 
@@ -172,6 +173,10 @@ SIGNATURES = {
     "ramp_track_map_workspace_bytes": (c_sz, [c_p]),
     "ramp_track_map": (c_i, [c_p, c_i] + [c_p] * 7 + [c_p, c_sz, c_p]),
     "ramp_trajectory_resolve": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
+    # poses at any time (csrc/interp.hip)
+    "ramp_se3_interp_workspace_bytes": (c_sz, [c_i]),
+    "ramp_se3_interp_lds_knots": (c_i, []),
+    "ramp_se3_interp": (c_i, [c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p]),
 }
 
 _lib = None

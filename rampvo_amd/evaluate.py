@@ -40,7 +40,8 @@ class Trajectory:
 
 
 @torch.no_grad()
-def run(cfg_VO, network, eval_cfg, data_list, ht=480, wd=640, device="cuda", inputs_ready="stream", on_pose=None):
+def run(cfg_VO, network, eval_cfg, data_list, ht=480, wd=640, device="cuda", inputs_ready="stream", on_pose=None,
+        query_times=None):
     """reference evaluate.py:232-260 (without the dataset-specific resize): returns poses, tstamps, points, colors.
     The loop hands the tracker tensors that were produced on the current stream right before the call, as the
     reference's loop does; ``inputs_ready = "stream"`` lets the frames pipeline anyway (Ramp_vo.__init__: the tracker
@@ -48,7 +49,9 @@ def run(cfg_VO, network, eval_cfg, data_list, ht=480, wd=640, device="cuda", inp
     ``inputs_ready=False``: everything on the caller's stream, frame after frame.
     ``on_pose``: optional callback, called with every frame's pose record (track_dev.PoseRecord) as the loop goes --
     whatever the GPU has finished by then, never waited for (Ramp_vo.pose_stream); the records still in flight when the
-    loop ends are delivered behind the closing updates.  None (default): the call sequence is the reference's."""
+    loop ends are delivered behind the closing updates.  None (default): the call sequence is the reference's.
+    ``query_times``: optional time stamps, in the unit of the frame time stamps (the loop feeds the frame index); the
+    poses there (Ramp_vo.poses_at, behind the closing updates) are returned as a fifth value [Q,7]."""
     train_cfg = eval_cfg["data_loader"]["train"]["args"]
     slam = Ramp_vo(cfg=cfg_VO, network=network, train_cfg=train_cfg, ht=ht, wd=wd, device=device)
     slam.inputs_ready = inputs_ready
@@ -69,7 +72,10 @@ def run(cfg_VO, network, eval_cfg, data_list, ht=480, wd=640, device="cuda", inp
             on_pose(rec)
     points = slam.points_.cpu().numpy()[:slam.m]
     colors = slam.colors_.view(-1, 3).cpu().numpy()[:slam.m]
+    at = slam.poses_at(query_times)[0] if query_times is not None else None
     poses, tstamps = slam.terminate()
+    if query_times is not None:
+        return poses, tstamps, points, colors, at
     return poses, tstamps, points, colors
 
 
@@ -134,6 +140,32 @@ def save_results(traj_ref, traj_est, scene, j=0, eval_type="None", root=None):
         time_s = (tr.timestamps * 10 ** -9)[..., np.newaxis]
         np.savetxt(osp.join(save_dir, name), np.concatenate((time_s, tr.positions_xyz, tr.orientations_quat_wxyz), axis=1))
     return save_dir
+
+
+def resample_trajectory(poses, tstamps, rate_hz, device="cuda"):
+    """poses [T,7] at tstamps [T] (seconds; what terminate() / trajectory() return) -> (poses [K,7], times [K]) at the fixed
+    rate ``rate_hz``: times tstamps[0] + k / rate_hz up to tstamps[-1], poses on the SE(3) geodesic between the two frames
+    around each time (ops.se3_interp).  Raises when tstamps decrease or are not finite."""
+    from . import ops
+    tstamps = np.asarray(tstamps, dtype=np.float64).reshape(-1)
+    poses = np.asarray(poses, dtype=np.float32).reshape(-1, 7)
+    assert len(poses) == len(tstamps) >= 1 and rate_hz > 0
+    k = int(np.floor((tstamps[-1] - tstamps[0]) * rate_hz * (1.0 + 1e-12))) + 1 if np.isfinite(tstamps[[0, -1]]).all() else 1
+    times = tstamps[0] + np.arange(max(k, 1), dtype=np.float64) / float(rate_hz)
+    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    out, _, status = ops.se3_interp(cu(poses), cu(tstamps), cu(times))
+    if ops.se3_interp_status(status)["bad_times"]:
+        raise RuntimeError("resample_trajectory: the time stamps decrease or are not finite")
+    return out.cpu().numpy(), times
+
+
+def save_fixed_rate_trajectory(path, poses, tstamps, rate_hz, device="cuda"):
+    """the trajectory resampled at ``rate_hz`` (resample_trajectory) as a text file in the row format of save_results:
+    time[s] x y z qw qx qy qz"""
+    out, times = resample_trajectory(poses, tstamps, rate_hz, device=device)
+    Path(path).parent.mkdir(exist_ok=True, parents=True)
+    np.savetxt(path, np.concatenate((times[:, None], out[:, :3], out[:, [6, 3, 4, 5]]), axis=1))
+    return path
 
 
 def save_output_for_COLMAP(name, traj, points, colors, fx, fy, cx, cy, H=480, W=640):

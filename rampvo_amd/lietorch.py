@@ -119,3 +119,12 @@ def cat(group_list, dim):
 
 def stack(group_list, dim):
     return SE3(torch.stack([X.data for X in group_list], dim=dim))
+
+
+def interpolate(X, times, query, extrapolate=False, twist=False):
+    """the SE(3) geodesic through the knots ``X`` (an SE3 of shape [T]) at ``times`` [T], evaluated at ``query`` [Q] (float64
+    device tensors): an SE3 of shape [Q] -- with ``twist=True`` the pair (SE3, the segments' left twists [Q,6]).  One call of
+    ops.se3_interp on the current stream; time stamps that decrease or are not finite give NaN rows (ops.se3_interp's status
+    word is not read here)."""
+    poses, tw, _ = ops.se3_interp(X.data, times, query, extrapolate=extrapolate, twist=twist)
+    return (SE3(poses), tw) if twist else SE3(poses)

@@ -250,6 +250,41 @@ def se3_binary(name, x, y, dx, dy, dout):
     return out.view(bs + (dout,))
 
 
+# ---------------------------------------------------------------- poses at any time
+def se3_interp(knots, times, query, extrapolate=False, twist=False, row_stores=False):
+    """The SE(3) geodesic through ``knots`` [T,7] at time stamps ``times`` [T] (float64, non-decreasing), evaluated at ``query``
+    [Q] (float64): ``X(t) = Exp(alpha * Log(X[s+1] X[s]^-1)) X[s]`` (include/ramp_hip.h ``ramp_se3_interp``, two launches).
+    Device tensors in and out, ordered on the current stream, nothing synchronised.
+
+    Returns ``(poses [Q,7], twist [Q,6] or None, status int32 [4])``; status: bits (bit 0: ``times`` decreases or is not
+    finite -- every row is NaN then), queries below the range, above it, NaN queries.  Outside the range alpha is clamped,
+    or with ``extrapolate`` the end segment's screw motion is continued.  ``row_stores``: the other store form of the query
+    launch (same bits; tools/pose_query_cost.py)."""
+    require_cuda(knots, times, query)
+    knots = knots.reshape(-1, 7).contiguous().float()
+    times = times.reshape(-1).contiguous().double()
+    query = query.reshape(-1).contiguous().double()
+    T, Q = knots.shape[0], query.shape[0]
+    if times.shape[0] != T:
+        raise RuntimeError("se3_interp: %d knots but %d time stamps" % (T, times.shape[0]))
+    dev = knots.device
+    out = torch.empty((Q, 7), dtype=torch.float32, device=dev)
+    tw = torch.empty((Q, 6), dtype=torch.float32, device=dev) if twist else None
+    status = torch.zeros(4, dtype=torch.int32, device=dev)
+    nbytes = lib().ramp_se3_interp_workspace_bytes(T)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    flags = (_lib.RAMP_INTERP_EXTRAPOLATE if extrapolate else 0) | (_lib.RAMP_INTERP_ROW_STORES if row_stores else 0)
+    check(lib().ramp_se3_interp(ptr(knots), ptr(times), T, ptr(query), Q, flags, ptr(out), ptr(tw), ptr(ws), nbytes,
+                                ptr(status), stream()), "ramp_se3_interp")
+    return out, tw, status
+
+
+def se3_interp_status(status):
+    """the status words of ramp_se3_interp as a dict (synchronises: one 16-byte copy)"""
+    w = status.detach().cpu()
+    return dict(bad_times=bool(int(w[0]) & _lib.RAMP_INTERP_BAD_TIMES), n_below=int(w[1]), n_above=int(w[2]), n_nan=int(w[3]))
+
+
 # ----------------------------------------------------------- projective ops
 def _idx(t):
     assert t.dtype == torch.int64
