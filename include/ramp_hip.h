@@ -142,7 +142,7 @@ int ramp_corr_kplane(void);
  * EventToStack_Numpy; upstream a host-side np.add.at).  Event i goes to bin
  * int32(float32(bins * i) / N); polarities p[i] (+-1) are accumulated per (bin, y, x) and the sum is cast to
  * int8 (wraps).  Integer pixel coordinates only (the reference's uint16 path; its sub-pixel bilinear path is
- * not provided).  out_i8 and/or out_f32 [bins][H][W]; ws: ramp_event_stack_workspace_bytes.          */
+ * ramp_event_warp with RAMP_WARP_IDENTITY).  out_i8 and/or out_f32 [bins][H][W]; ws: ramp_event_stack_workspace_bytes.          */
 size_t ramp_event_stack_workspace_bytes(int bins, int H, int W);
 int ramp_event_stack(const int32_t *x, const int32_t *y, const int8_t *p, int N, int bins, int H, int W,
                      int8_t *out_i8, float *out_f32, void *ws, size_t ws_bytes, void *stream);
@@ -153,6 +153,9 @@ int ramp_event_stack(const int32_t *x, const int32_t *y, const int8_t *p, int N,
 int ramp_depth_median_fill(const float *patches_src, int F, int M, int P, float *patches_dst, void *stream);
 /* the same median into device memory (*out), for a caller that computes it ahead of ramp_frame_commit (median_dev) */
 int ramp_depth_median(const float *patches_src, int F, int M, int P, float *out, void *stream);
+/* the same over rows n - F .. n - 1 of patches_base [rows][M][3][P][P] with n = *n_dev read on the device (a caller that
+ * does not know the row count: the device-resident tracker).  Fewer than F rows: the rows there are; none: *out = 0.  */
+int ramp_depth_median_rows(const float *patches_base, const int32_t *n_dev, int F, int M, int P, float *out, void *stream);
 
 /* Event-biased patch-centre selection: get_coords_from_topk_events + nms_image
  * (ramp/utils.py:186-226, 157-183; upstream ~20 ATen launches) for one frame.
@@ -1019,6 +1022,60 @@ size_t ramp_se3_interp_workspace_bytes(int T);
 int ramp_se3_interp_lds_knots(void);
 int ramp_se3_interp(const float *knots, const double *times, int T, const double *query, int Q, int flags, float *out,
                     float *twist, void *seg_ws, size_t seg_ws_bytes, int32_t *status, void *stream);
+
+/* ---------------------------------------------------------------- motion-compensated events (csrc/warp.hip)
+ *
+ * ramp_event_warp: every event is warped from the camera pose at its own time stamp to the pose at t_ref, and the warped
+ * events are splat bilinearly into an image of warped events and / or a bin stack.  One pass over the events: segment
+ * search, interpolation, warp and scatter; the per-event pose is never written.
+ *   events: x, y [N] fp32 pixel coordinates (fractions allowed), t [N] float64, p [N] int8 polarity (+-1; 0 is read as -1).
+ *   knots [T][7], times [T] float64: a CAMERA-TO-WORLD trajectory, as ramp_trajectory_resolve writes it; C(t) is the geodesic
+ *   of ramp_se3_interp through it (the same s, the same alpha formed in float64, the same segment table), held outside the
+ *   knots' range or continued with RAMP_INTERP_EXTRAPOLATE.  t_ref: float64, finite.  intrinsics: device (fx, fy, cx, cy).
+ *   invdepth: device pointer; RAMP_WARP_DEPTH_SCALAR: one float; RAMP_WARP_DEPTH_MAP: [H][W] floats, sampled at the event's
+ *   rounded pixel (rint: halves to even), clamped to the image.  Inverse depth 0 compensates the rotation alone.
+ *     G  = C(t_ref)^-1 * C(t)                 (C(t_ref)^-1 is formed once, in the segment launch)
+ *     X' = R_G * ((x - cx) / fx, (y - cy) / fy, 1) + t_G * d
+ *     x' = fx * (X' / Z') + cx,   y' = fy * (Y' / Z') + cy
+ *   G is composed so that an event whose C(t) equals C(t_ref) in every bit (T == 1; t == t_ref) gets the exact identity.
+ *   An event is INVALID when x, y or t is not finite, when Z' <= RAMP_WARP_MIN_Z (or Z' is NaN), or when x' or y' is not
+ *   finite: it contributes nothing and its row of xy_out is NaN.  RAMP_WARP_MIN_Z = 0.2 takes the role of
+ *   projective_ops.MIN_DEPTH, in the same units: Z' is the depth at t_ref relative to the depth at t (d scales the
+ *   translation), so the test drops events whose point comes closer than a fifth of its depth or passes behind the camera.
+ *   Scatter: the neighbours floor(x'), floor(x') + 1 with weights 1 - wx, wx (wx = x' - floor(x'), fp32), the same in y;
+ *   neighbours outside the image are dropped.  A neighbour contributes c = llrint(ldexp(wx_i * wy_j, 24)) (one fp32 product,
+ *   no FMA), added with 64-bit INTEGER atomics: the sums do not depend on the events' order and a call repeats its bits.
+ *   |sum| < 2^63 holds up to 2^39 events on one pixel.
+ *   Outputs, each optional (NULL), converted by a finishing launch (float(sum) * 2^-24 rounds once):
+ *     xy_out [N][2] fp32      the warped coordinates
+ *     iwe [2][H][W] fp32      plane 0 the polarity-signed sum, plane 1 the unsigned count
+ *     stack_f32, stack_i8 [bins][H][W]   event i goes to bin int32(float32(bins) * float32(i) / float32(N)) as in
+ *                             ramp_event_stack (capped at bins - 1); int8: the fixed-point sum divided by 2^24 toward zero,
+ *                             then modulo 256.  (stack_f32 is the sum itself, not the value of the wrapped int8.)
+ *   RAMP_WARP_IDENTITY: no trajectory -- x' = x, y' = y; t, knots, times, intrinsics and invdepth are not read (NULL).  This
+ *   is the sub-pixel bilinear path of the event stack.
+ *   status: device int32 [8], written by the call: [0] bits (RAMP_INTERP_BAD_TIMES), [1] / [2] events below / above the
+ *   knots' range, [3] events with a coordinate or time stamp that is not finite ([1], [2] count the others only), [4] events
+ *   rejected by the Z' test or whose projection is not finite, [5] valid events whose four neighbours all lie outside the
+ *   image, [6] events with a neighbour inside it, [7] 0.  [3] + [4] + [5] + [6] = N.  RAMP_INTERP_BAD_TIMES makes every
+ *   output NaN (0 for int8) and [4] - [6] zero; [1] - [3] are still counted.  These are outcomes of the data: RAMP_OK.
+ *   ws: ramp_event_warp_workspace_bytes(T, bins, H, W) bytes, 16-byte aligned (segment table, C(t_ref)^-1, counters, int64
+ *   accumulators); xy_out 8-byte aligned (else RAMP_EINVAL).  Launches: at most three kernels behind one
+ *   hipMemsetAsync, all on `stream`, nothing synchronised.
+ *   N == 0: RAMP_OK, nothing is launched and nothing written.  T < 1, H, W or bins < 1, no output requested, a t_ref that is
+ *   not finite: RAMP_EINVAL (bins is 1 for a caller without a stack).
+ * ramp_event_warp_grid_events(): the number of events one trip of the full event grid covers; above it the workgroups take
+ * a second trip.                                                                                                       */
+#define RAMP_WARP_DEPTH_SCALAR 0
+#define RAMP_WARP_DEPTH_MAP 4
+#define RAMP_WARP_IDENTITY 8
+#define RAMP_WARP_MIN_Z 0.2f
+size_t ramp_event_warp_workspace_bytes(int T, int bins, int H, int W);
+long ramp_event_warp_grid_events(void);
+int ramp_event_warp(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
+                    const double *times, int T, double t_ref, const float *intrinsics, const float *invdepth, int flags,
+                    int bins, int H, int W, float *xy_out, float *iwe, float *stack_f32, int8_t *stack_i8, void *ws,
+                    size_t ws_bytes, int32_t *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -543,6 +543,15 @@ class Ramp_vo:
             raise RuntimeError("trajectory(): a frame is neither a keyframe nor reachable through the delta chain")
         return poses, tst
 
+    def _frame_times_dev(self):
+        """the frames' time stamps on the device (float64), uploaded once per new frame count"""
+        key, tdev = self._traj_times
+        now = (id(self.tlist), len(self.tlist), self.tlist[-1] if self.tlist else None)
+        if key != now:
+            tdev = self._upload(np.asarray(self.tlist, dtype=np.float64).reshape(-1))
+            self._traj_times = (now, tdev)
+        return tdev
+
     def poses_at(self, times, extrapolate=False, twist=False, as_tensor=False):
         """The trajectory at ANY time stamps: ``trajectory(as_tensor=True)`` and, behind it on the same stream, the SE(3)
         geodesic between the frames' poses (ops.se3_interp: ``X(t) = Exp(alpha Log(X[s+1] X[s]^-1)) X[s]`` on the segment
@@ -560,10 +569,7 @@ class Ramp_vo:
         knots, _ = self.trajectory(as_tensor=True)
         dev = self.device
         with torch.no_grad():
-            key, tdev = self._traj_times
-            if key != (id(self.tlist), len(self.tlist), self.tlist[-1] if self.tlist else None):
-                tdev = self._upload(np.asarray(self.tlist, dtype=np.float64).reshape(-1))
-                self._traj_times = ((id(self.tlist), len(self.tlist), self.tlist[-1] if self.tlist else None), tdev)
+            tdev = self._frame_times_dev()
             if isinstance(times, torch.Tensor):
                 q = times.to(device=dev, dtype=torch.float64).reshape(-1)
             else:
@@ -577,6 +583,68 @@ class Ramp_vo:
         if int(words[0]) & 1:
             raise RuntimeError("poses_at(): the frames' time stamps decrease or are not finite")
         return poses.cpu().numpy(), (tw.cpu().numpy() if twist else None)
+
+    def compensate_events(self, x, y, t, p, t_ref=None, invdepth=None, num_bins=0, extrapolate=False, want_xy=False,
+                          want_iwe=True, stack=None, height=None, width=None, as_tensor=False):
+        """Motion compensation with the trajectory as it is now: every event (``x, y`` pixel coordinates of the images the
+        tracker is fed, ``t`` in the unit of the frames' time stamps, ``p`` polarity) is warped from the camera pose at its
+        own time stamp to the pose at ``t_ref`` and splat bilinearly into an image of warped events and / or a bin stack
+        (``ops.event_warp``, one pass over the events; the poses are those of ``poses_at``: ``trajectory(as_tensor=True)``
+        and the cached time stamps, never written per event).
+
+        ``t_ref=None``: the newest frame's time stamp.  ``invdepth=None``: the lower median inverse depth of the last three
+        frames' patches -- the value the next frame's patches start from -- computed into a device word the host never
+        reads; otherwise a float, a one-element device tensor or a [height, width] map.  Intrinsics: row 0 of the tracker's
+        own times the patch stride, i.e. those of the images it was fed.  ``height, width`` default to the tracker's.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
+        the dict of device tensors of ``ops.event_warp`` (``status``, ``xy``, ``iwe``, ``stack`` as requested), ordered on
+        the current stream, nothing synchronised.  Otherwise numpy arrays, which waits for that result and raises when the
+        frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
+        if not self.tlist:
+            raise RuntimeError("compensate_events(): no frame has been tracked yet")
+        knots, _ = self.trajectory(as_tensor=True)
+        dev = self.device
+        dv = self._dev
+        resident = dv is not None and dv.active
+        with torch.no_grad():
+            tdev = self._frame_times_dev()
+            own = getattr(self, "_main_used", False)          # (inputs_ready = "stream": the state is the tracker's own stream's)
+            cur = torch.cuda.current_stream(dev)
+            st = self._main_stream if own else cur
+            with torch.cuda.stream(st):                       # reads of the state, on the stream it lives on
+                K = self.intrinsics_[0] * float(self.RES)
+                if invdepth is None:
+                    invdepth = torch.zeros(1, dtype=torch.float32, device=dev)
+                    if resident:
+                        ops.depth_median_rows(self.patches_, dv.dyn[track_dev.DYN_NROW:], 3, invdepth)
+                    elif self._n > 0:
+                        f = min(3, self._n)
+                        ops.depth_median(self.patches_, self._n, f, invdepth)
+            if own:
+                ev = torch.cuda.Event()
+                ev.record(st)
+                cur.wait_event(ev)
+                for z in (K, invdepth):
+                    if isinstance(z, torch.Tensor):
+                        z.record_stream(cur)
+            as_dev = lambda a, dt: (a.to(device=dev, dtype=dt) if isinstance(a, torch.Tensor)
+                                    else self._upload(np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=dt)))
+            out = ops.event_warp(as_dev(x, torch.float32 if isinstance(x, torch.Tensor) else np.float32),
+                                 as_dev(y, torch.float32 if isinstance(y, torch.Tensor) else np.float32),
+                                 as_dev(t, torch.float64 if isinstance(t, torch.Tensor) else np.float64),
+                                 as_dev(p, torch.int8 if isinstance(p, torch.Tensor) else np.int8), knots, tdev,
+                                 self.tlist[-1] if t_ref is None else float(t_ref), K, invdepth,
+                                 self.ht if height is None else height, self.wd if width is None else width,
+                                 num_bins=num_bins, extrapolate=extrapolate, want_xy=want_xy, want_iwe=want_iwe, stack=stack)
+        if as_tensor:
+            return out
+        words = torch.cat([out["status"], self._traj_status]).cpu()   # (the one wait)
+        if int(words[8]) & track_dev.TRAJ_UNRESOLVED:
+            raise RuntimeError("compensate_events(): a frame is neither a keyframe nor reachable through the delta chain")
+        if int(words[0]) & 1:
+            raise RuntimeError("compensate_events(): the frames' time stamps decrease or are not finite")
+        return {k: v.cpu().numpy() for k, v in out.items()}
 
     # --------------------------------------------------------------- uncertainty
     def _window_query(self, name, with_map=False, then=None):

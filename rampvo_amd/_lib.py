@@ -22,6 +22,7 @@ RAMP_IN_F32, RAMP_CONV_DIRECT, RAMP_CORR_MFMA32, RAMP_CORR_X2 = 0x10, 0x20, 0x40
 RAMP_CONV_X3 = 0x80
 RAMP_NCHW, RAMP_NHWC, RAMP_NHWC32 = 0, 1, 2
 RAMP_INTERP_EXTRAPOLATE, RAMP_INTERP_ROW_STORES, RAMP_INTERP_BAD_TIMES = 1, 2, 1
+RAMP_WARP_DEPTH_SCALAR, RAMP_WARP_DEPTH_MAP, RAMP_WARP_IDENTITY, RAMP_WARP_MIN_Z = 0, 4, 8, 0.2
 KPLANE = 32            # channels per plane of the packed correlation target maps: [h][128 / KPLANE][w][KPLANE]
 
 
@@ -66,6 +67,7 @@ SIGNATURES = {
     "ramp_event_stack": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
     "ramp_depth_median_fill": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
     "ramp_depth_median": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
+    "ramp_depth_median_rows": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
     "ramp_event_topk_workspace_bytes": (c_sz, [c_i, c_i]),
     "ramp_event_topk": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
     "ramp_pyramid_pack": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
@@ -177,6 +179,11 @@ SIGNATURES = {
     "ramp_se3_interp_workspace_bytes": (c_sz, [c_i]),
     "ramp_se3_interp_lds_knots": (c_i, []),
     "ramp_se3_interp": (c_i, [c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p]),
+    # motion-compensated events (csrc/warp.hip)
+    "ramp_event_warp_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "ramp_event_warp_grid_events": (ctypes.c_long, []),
+    "ramp_event_warp": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, ctypes.c_double, c_p, c_p, c_i, c_i, c_i, c_i,
+                              c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
 }
 
 _lib = None

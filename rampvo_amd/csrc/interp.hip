@@ -11,14 +11,7 @@
 // 28-byte row and an optional 24-byte twist).  Every row is a function of its own query alone -- the lt_* device functions
 // of ramp_se3_exp / ramp_se3_mul in program order, no reduction over queries -- and the counters are integers, so a row's
 // bits depend neither on Q, nor on the row's position, nor on the order of the queries, nor on the launch shape.
-#include "ramp_device.h"
-
-#define INTERP_THREADS 256
-#define INTERP_LDS_KNOTS 4096      // knot times staged in LDS up to here (32 KiB of float64); longer: search in global memory
-#define INTERP_MAX_GROUPS 2048     // workgroups per launch; each walks the query tiles with this stride
-#define INTERP_SEG_WORDS 16        // per segment: xi[6], float64 length (words 6, 7), twist[6], 2 spare = one 64-byte row
-
-static __device__ __forceinline__ bool interp_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
+#include "interp_device.h"
 
 __global__ void __launch_bounds__(INTERP_THREADS)
     interp_segment_kernel(const float *__restrict__ knots, const double *__restrict__ times, int T, float *__restrict__ seg,
@@ -26,43 +19,7 @@ __global__ void __launch_bounds__(INTERP_THREADS)
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   const int S = T > 1 ? T - 1 : 1;                 // (T == 1: one segment of zero length and zero motion)
   if (s >= S) return;
-  const double t0 = times[s];
-  bool bad = !interp_finite(t0);
-  float xi[6] = {0, 0, 0, 0, 0, 0}, tw[6] = {0, 0, 0, 0, 0, 0};
-  double dt = 0.0;
-  if (T > 1) {
-    const double t1 = times[s + 1];
-    bad = bad || !interp_finite(t1) || t1 < t0;
-    dt = t1 - t0;
-    float X0[7], X1[7], X0i[7], D[7];
-#pragma unroll
-    for (int c = 0; c < 7; c++) { X0[c] = knots[7 * (size_t)s + c]; X1[c] = knots[7 * (size_t)(s + 1) + c]; }
-    lt_inv(X0, X0i);
-    lt_mul(X1, X0i, D);
-    lt_log(D, xi);
-    if (dt > 0.0) {
-#pragma unroll
-      for (int c = 0; c < 6; c++) tw[c] = (float)((double)xi[c] / dt);
-    }
-  }
-  if (bad) atomicOr(status, RAMP_INTERP_BAD_TIMES);
-  float *row = seg + (size_t)s * INTERP_SEG_WORDS;
-#pragma unroll
-  for (int c = 0; c < 6; c++) { row[c] = xi[c]; row[8 + c] = tw[c]; }
-  *reinterpret_cast<double *>(row + 6) = dt;        // (rows are 64 bytes, the workspace 16-byte aligned: an aligned float64)
-  row[14] = 0.0f;
-  row[15] = 0.0f;
-}
-
-// upper bound: the number of knot times <= t (0 for a NaN)
-template <typename P>
-static __device__ __forceinline__ int interp_upper_bound(P tt, int T, double t) {
-  int lo = 0, hi = T;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (tt[mid] <= t) lo = mid + 1; else hi = mid;
-  }
-  return lo;
+  if (interp_segment_row(knots, times, T, s, seg + (size_t)s * INTERP_SEG_WORDS)) atomicOr(status, RAMP_INTERP_BAD_TIMES);
 }
 
 // LDS_TIMES: the knot times are staged in LDS once per workgroup (T <= INTERP_LDS_KNOTS), else every search step is a global
@@ -117,14 +74,7 @@ __global__ void __launch_bounds__(INTERP_THREADS)
         const float4 r0 = row4[0], r1 = row4[1];      // xi[0..3]; xi[4], xi[5], the length
         const float xi[6] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y};
         const double dt = __hiloint2double(__float_as_int(r1.w), __float_as_int(r1.z));
-        double a;
-        if (dt > 0.0) {
-          a = (t - ts) / dt;
-          if (!extrapolate) a = fmin(fmax(a, 0.0), 1.0);
-        } else {
-          a = t < ts ? 0.0 : 1.0;                   // a segment of zero length (or a failed check of `times`)
-        }
-        const float alpha = (float)a;
+        const float alpha = interp_alpha(t, ts, dt, extrapolate);
         float X[7], axi[6], E[7];
 #pragma unroll
         for (int c = 0; c < 7; c++) X[c] = knots[7 * (size_t)s + c];

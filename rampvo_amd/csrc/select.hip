@@ -228,6 +228,21 @@ __global__ void __launch_bounds__(MED_THREADS)
   if (threadIdx.x == 0) *out = med;
 }
 
+// the same for a caller that does not know the row count: n is read from device memory (the device-resident tracker's
+// dyn word), the frames are rows n - F .. n - 1 of the patch buffer.  Fewer than F rows: those there are; none: 0.
+__global__ void __launch_bounds__(MED_THREADS)
+    depth_median_rows_kernel(const float *__restrict__ base, const int32_t *__restrict__ n_dev, int F, int M, int PP,
+                             float *__restrict__ out) {
+  const int n = *n_dev;                                 // (workgroup uniform)
+  const int f = n < F ? (n > 0 ? n : 0) : F;
+  if (f == 0) {
+    if (threadIdx.x == 0) *out = 0.0f;
+    return;
+  }
+  const float med = depth_median_block(base + (size_t)(n - f) * M * 3 * PP, f, M, PP);
+  if (threadIdx.x == 0) *out = med;
+}
+
 // Everything a steady-state Ramp_vo.__call__ writes before its reprojection (ramp/Ramp_vo.py:345-381) as ONE launch
 // -- these were three dependent tiny launches on the frame's critical path.  Workgroup (0, 0): time stamp, index
 // map, intrinsics row, motion-model pose (ramp_frame_begin), the depth median (ramp_depth_median_fill) and the new
@@ -408,6 +423,15 @@ int ramp_depth_median(const float *patches_src, int F, int M, int P, float *out,
   if (!patches_src || !out || F <= 0 || M <= 0 || P <= 0) return RAMP_EINVAL;
   if ((long)F * M * P * P > MED_THREADS * MED_PER) return RAMP_EUNSUPPORTED;
   hipLaunchKernelGGL(depth_median_kernel, dim3(1), dim3(MED_THREADS), 0, (hipStream_t)stream, patches_src, F, M, P * P, out);
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+
+int ramp_depth_median_rows(const float *patches_base, const int32_t *n_dev, int F, int M, int P, float *out, void *stream) {
+  if (!patches_base || !n_dev || !out || F <= 0 || M <= 0 || P <= 0) return RAMP_EINVAL;
+  if ((long)F * M * P * P > MED_THREADS * MED_PER) return RAMP_EUNSUPPORTED;
+  hipLaunchKernelGGL(depth_median_rows_kernel, dim3(1), dim3(MED_THREADS), 0, (hipStream_t)stream, patches_base, n_dev, F, M,
+                     P * P, out);
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;
 }

@@ -1,0 +1,348 @@
+// Motion-compensated events (include/ramp_hip.h: ramp_event_warp): every event is taken from the camera pose at its own time
+// stamp to the pose at one reference time, and the warped events are splat bilinearly into an image of warped events and / or
+// the encoder's bin stack.  One pass over the events; the per-event pose lives in registers only.
+//
+//   C(t)  = Exp(alpha * xi_s) * knots[s]                  the geodesic of ramp_se3_interp (interp_device.h), camera-to-world
+//   G     = C(t_ref)^-1 * C(t)
+//   X'    = R_G * ((x - cx) / fx, (y - cy) / fy, 1) + t_G * d         d: inverse depth (one float, or a map)
+//   x'    = fx * (X' / Z') + cx,   y' = fy * (Y' / Z') + cy           invalid: Z' <= RAMP_WARP_MIN_Z, anything not finite
+//
+// Three launches behind one memset of the counters and accumulators:
+//   warp_segment_kernel  the segment table of ramp_se3_interp (the same rows) and, in one extra workgroup, C(t_ref)^-1
+//   warp_event_kernel    tiles of WARP_TILE events staged in LDS with 16-byte loads, one event per lane and trip: search,
+//                        interpolation, warp, then up to four integer atomics per requested accumulator plane
+//   warp_finish_kernel   accumulators -> fp32 / int8, counters -> status
+//
+// The splat is FIXED POINT: a neighbour's weight is the fp32 product of its two axis weights, its contribution
+// llrint(weight * 2^24), added with 64-bit integer atomics.  Integer addition commutes, so the sums -- and every output --
+// do not depend on the order in which events arrive, and a call repeats its bits.  |sum| < 2^63 holds up to 2^39 events on
+// one pixel.  G is composed so that C(t) == C(t_ref) bit for bit gives the exact identity (see warp_relative).
+#include "interp_device.h"
+
+#define WARP_TILE (INTERP_THREADS * 4)   // events per workgroup trip: a 16-byte load of x and y per lane
+#define WARP_MAX_GROUPS 1024             // workgroups of the event launch; each walks the tiles with this stride
+#define WARP_FIX_BITS 24
+#define WARP_REF_WORDS 16                // C(t_ref)^-1: translation 3, quaternion 4, 9 spare = one 64-byte row
+#define WARP_CTR_WORDS 16                // int32: the 8 status words, 8 spare
+
+typedef unsigned long long warp_u64;
+
+// G = Cref^-1 * C from ref = (-(qr^-1 . tr), qr^-1) and C = (t, q), without renormalising either factor:
+//   q_G = normalise(qr^-1 * q),  t_G = qr^-1 . t - qr^-1 . tr
+// Both rotations of a translation are the same function of their inputs, so C == Cref in every bit gives t_G = 0 exactly, and
+// the quaternion product of q with its own conjugate has exactly zero imaginary parts: G is then the exact identity.
+static __device__ __forceinline__ void warp_relative(const float *ref, const float *C, float *tG, float *qG) {
+  float q[4], r[3];
+  lt_qmul(ref + 3, C + 3, q);
+  lt_qnorm(q, qG);
+  lt_qrot(ref + 3, C, r);
+  tG[0] = ref[0] + r[0];
+  tG[1] = ref[1] + r[1];
+  tG[2] = ref[2] + r[2];
+}
+
+__global__ void __launch_bounds__(INTERP_THREADS)
+    warp_segment_kernel(const float *__restrict__ knots, const double *__restrict__ times, int T, double t_ref,
+                        int extrapolate, float *__restrict__ seg, float *__restrict__ ref, int32_t *__restrict__ ctr) {
+  const int S = T > 1 ? T - 1 : 1;
+  if (blockIdx.x + 1 < gridDim.x) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < S && interp_segment_row(knots, times, T, s, seg + (size_t)s * INTERP_SEG_WORDS)) atomicOr(ctr, RAMP_INTERP_BAD_TIMES);
+    return;
+  }
+  // the last workgroup: one lane forms C(t_ref) from its own copy of that segment's row (the same function, the same bits)
+  if (threadIdx.x) return;
+  const int s = min(max(interp_upper_bound(times, T, t_ref) - 1, 0), T > 1 ? T - 2 : 0);
+  float xi[6], tw[6], X[7], C[7], r[3];
+  double dt;
+  interp_segment_values(knots, times, T, s, xi, tw, &dt);
+#pragma unroll
+  for (int c = 0; c < 7; c++) X[c] = knots[7 * (size_t)s + c];
+  interp_pose(X, xi, interp_alpha(t_ref, times[s], dt, extrapolate), C);
+  const float qi[4] = {-C[3], -C[4], -C[5], C[6]};
+  lt_qrot(qi, C, r);
+  ref[0] = -r[0]; ref[1] = -r[1]; ref[2] = -r[2];
+  ref[3] = qi[0]; ref[4] = qi[1]; ref[5] = qi[2]; ref[6] = qi[3];
+#pragma unroll
+  for (int c = 7; c < WARP_REF_WORDS; c++) ref[c] = 0.0f;
+}
+
+struct WarpArgs {
+  const float *x, *y;
+  const double *t;
+  const int8_t *p;
+  const float *knots;
+  const double *times;
+  const float *seg, *ref, *intrinsics, *invdepth;
+  float *xy_out;
+  long long *acc_iwe, *acc_stack;
+  int32_t *ctr;
+  int N, T, bins, H, W, extrapolate, depth_map;
+};
+
+// one axis of the splat: the two neighbours floor(v) and floor(v) + 1, their weights 1 - w and w with w = v - floor(v), and
+// whether each lies in [0, n).  The range test is made in float, so a huge coordinate never reaches an integer conversion.
+static __device__ __forceinline__ void warp_axis(float v, int n, int *i0, float *w0, float *w1, bool *in0, bool *in1) {
+  const float fl = floorf(v);
+  const float w = v - fl;
+  *w0 = 1.0f - w;
+  *w1 = w;
+  *in0 = fl >= 0.0f && fl <= (float)(n - 1);
+  *in1 = fl >= -1.0f && fl <= (float)(n - 2);
+  *i0 = (*in0 || *in1) ? (int)fl : 0;
+}
+
+// IDENTITY: no trajectory, x' = x and y' = y (the bilinear path of the event stack).  LDS_TIMES, VEC: the knot times are
+// staged in LDS; full tiles are loaded with 16-byte loads (every event array 16-byte aligned).
+template <bool IDENTITY, bool LDS_TIMES, bool VEC>
+__global__ void __launch_bounds__(INTERP_THREADS) warp_event_kernel(const WarpArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char warp_smem[];
+  __shared__ __attribute__((aligned(16))) double s_t[IDENTITY ? 2 : WARP_TILE];
+  __shared__ __attribute__((aligned(16))) float s_x[WARP_TILE];
+  __shared__ __attribute__((aligned(16))) float s_y[WARP_TILE];
+  __shared__ __attribute__((aligned(16))) int8_t s_p[WARP_TILE];
+  __shared__ float s_uni[12];
+  __shared__ double s_range[2];
+  double *s_times = reinterpret_cast<double *>(warp_smem);
+  const int tid = threadIdx.x;
+  const int N = a.N, T = a.T, H = a.H, W = a.W;
+  if (!IDENTITY && LDS_TIMES)
+    for (int i = tid; i < T; i += INTERP_THREADS) s_times[i] = a.times[i];
+  const bool failed = !IDENTITY && (a.ctr[0] & RAMP_INTERP_BAD_TIMES) != 0;   // (raised by the segment launch in front)
+  if (!IDENTITY) {
+    if (tid == 12) { s_range[0] = a.times[0]; s_range[1] = a.times[T - 1]; }
+    // C(t_ref)^-1 (7), the intrinsics (4) and the scalar inverse depth: read from LDS per event, not held in scalar registers
+    if (tid < 7) s_uni[tid] = a.ref[tid];
+    else if (tid < 11) s_uni[tid] = a.intrinsics[tid - 7];
+    else if (tid == 11) s_uni[tid] = a.depth_map ? 0.0f : a.invdepth[0];
+  }
+  const int s_max = T > 1 ? T - 2 : 0;
+  const float qnan = __int_as_float(0x7fc00000);
+  const size_t HW = (size_t)H * W;
+  const long tiles = ((long)N + WARP_TILE - 1) / WARP_TILE;
+  int n_below = 0, n_above = 0, n_bad = 0, n_z = 0, n_out = 0, n_in = 0;    // wave-uniform: sums of ballots
+  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long base = tile * WARP_TILE;
+    const int live = (int)min((long)WARP_TILE, (long)N - base);
+    __syncthreads();                                 // (the staged knot times; the previous tile has been read)
+    if (VEC && live == WARP_TILE) {
+      reinterpret_cast<float4 *>(s_x)[tid] = reinterpret_cast<const float4 *>(a.x + base)[tid];
+      reinterpret_cast<float4 *>(s_y)[tid] = reinterpret_cast<const float4 *>(a.y + base)[tid];
+      reinterpret_cast<int *>(s_p)[tid] = reinterpret_cast<const int *>(a.p + base)[tid];
+      if (!IDENTITY) {
+        reinterpret_cast<double2 *>(s_t)[tid] = reinterpret_cast<const double2 *>(a.t + base)[tid];
+        reinterpret_cast<double2 *>(s_t)[tid + INTERP_THREADS] = reinterpret_cast<const double2 *>(a.t + base)[tid + INTERP_THREADS];
+      }
+    } else {
+      for (int i = tid; i < live; i += INTERP_THREADS) {
+        s_x[i] = a.x[base + i];
+        s_y[i] = a.y[base + i];
+        s_p[i] = a.p[base + i];
+        if (!IDENTITY) s_t[i] = a.t[base + i];
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int k = 0; k < WARP_TILE / INTERP_THREADS; k++) {
+      const int e = k * INTERP_THREADS + tid;
+      const bool have = e < live;
+      bool below = false, above = false, bad = false, zrej = false, outside = false, inside = false;
+      if (have) {
+        const long i = base + e;
+        const float x = s_x[e], y = s_y[e];
+        const double t = IDENTITY ? 0.0 : s_t[e];
+        float xw = qnan, yw = qnan;
+        bool valid = false;
+        if (!(fabsf(x) <= 3.4028234663852886e38f && fabsf(y) <= 3.4028234663852886e38f && interp_finite(t))) {
+          bad = true;
+        } else if (IDENTITY) {
+          xw = x;
+          yw = y;
+          valid = true;
+        } else {
+          below = t < s_range[0];
+          above = t > s_range[1];
+          int s;
+          double ts;
+          if (LDS_TIMES) {
+            s = min(max(interp_upper_bound(s_times, T, t) - 1, 0), s_max);
+            ts = s_times[s];
+          } else {
+            s = min(max(interp_upper_bound(a.times, T, t) - 1, 0), s_max);
+            ts = a.times[s];
+          }
+          const float4 *row4 = reinterpret_cast<const float4 *>(a.seg + (size_t)s * INTERP_SEG_WORDS);
+          const float4 r0 = row4[0], r1 = row4[1];      // xi[0..3]; xi[4], xi[5], the length
+          const float xi[6] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y};
+          const double dt = __hiloint2double(__float_as_int(r1.w), __float_as_int(r1.z));
+          const float alpha = interp_alpha(t, ts, dt, a.extrapolate);
+          float X[7], C[7], tG[3], qG[4], R[3], ref[7];
+          const float fx = s_uni[7], fy = s_uni[8], cx = s_uni[9], cy = s_uni[10];
+#pragma unroll
+          for (int c = 0; c < 7; c++) ref[c] = s_uni[c];
+#pragma unroll
+          for (int c = 0; c < 7; c++) X[c] = a.knots[7 * (size_t)s + c];
+          interp_pose(X, xi, alpha, C);
+          warp_relative(ref, C, tG, qG);
+          float d = s_uni[11];
+          if (a.depth_map) {                             // the event's rounded pixel (half to even), clamped to the image
+            const int px = (int)fminf(fmaxf(rintf(x), 0.0f), (float)(W - 1));
+            const int py = (int)fminf(fmaxf(rintf(y), 0.0f), (float)(H - 1));
+            d = a.invdepth[(size_t)py * W + px];
+          }
+          const float P[3] = {(x - cx) / fx, (y - cy) / fy, 1.0f};
+          lt_qrot(qG, P, R);
+          const float Xp = R[0] + tG[0] * d, Yp = R[1] + tG[1] * d, Zp = R[2] + tG[2] * d;
+          const float xp = fx * (Xp / Zp) + cx, yp = fy * (Yp / Zp) + cy;
+          valid = Zp > RAMP_WARP_MIN_Z && fabsf(xp) <= 3.4028234663852886e38f && fabsf(yp) <= 3.4028234663852886e38f;
+          zrej = !valid;                                 // (a NaN Z' fails the comparison: rejected, like a NaN projection)
+          if (valid) { xw = xp; yw = yp; }
+        }
+        if (failed) { valid = false; zrej = false; xw = qnan; yw = qnan; }
+        if (a.xy_out) reinterpret_cast<float2 *>(a.xy_out)[i] = make_float2(xw, yw);
+        if (valid) {
+          int ix, iy;
+          float wx[2], wy[2];
+          bool inx[2], iny[2];
+          warp_axis(xw, W, &ix, &wx[0], &wx[1], &inx[0], &inx[1]);
+          warp_axis(yw, H, &iy, &wy[0], &wy[1], &iny[0], &iny[1]);
+          inside = (inx[0] || inx[1]) && (iny[0] || iny[1]);
+          outside = !inside;
+          if (inside) {
+            const long long pol = s_p[e] == 0 ? -1ll : (long long)s_p[e];    // (0 is read as -1, like ops.event_stack)
+            int b = 0;
+            if (a.acc_stack) b = min((int)(((float)a.bins * (float)i) / (float)N), a.bins - 1);
+#pragma unroll
+            for (int jy = 0; jy < 2; jy++)
+#pragma unroll
+              for (int jx = 0; jx < 2; jx++)
+                if (inx[jx] && iny[jy]) {
+                  const long long c = __float2ll_rn(ldexpf(__fmul_rn(wx[jx], wy[jy]), WARP_FIX_BITS));
+                  if (c != 0) {
+                    const size_t at = (size_t)(iy + jy) * W + (size_t)(ix + jx);
+                    if (a.acc_iwe) {
+                      atomicAdd(reinterpret_cast<warp_u64 *>(a.acc_iwe + at), (warp_u64)(pol * c));
+                      atomicAdd(reinterpret_cast<warp_u64 *>(a.acc_iwe + HW + at), (warp_u64)c);
+                    }
+                    if (a.acc_stack) atomicAdd(reinterpret_cast<warp_u64 *>(a.acc_stack + (size_t)b * HW + at), (warp_u64)(pol * c));
+                  }
+                }
+          }
+        }
+      }
+      // the trip count and `have` aside, every lane of the wave is here: one ballot per counter, summed per wave
+      n_below += __popcll(__ballot(below));
+      n_above += __popcll(__ballot(above));
+      n_bad += __popcll(__ballot(bad));
+      n_z += __popcll(__ballot(zrej));
+      n_out += __popcll(__ballot(outside));
+      n_in += __popcll(__ballot(inside));
+    }
+  }
+  if ((tid & (RAMP_WAVE - 1)) == 0) {                  // one integer atomic per wave and counter that is not zero
+    if (n_below) atomicAdd(&a.ctr[1], n_below);
+    if (n_above) atomicAdd(&a.ctr[2], n_above);
+    if (n_bad) atomicAdd(&a.ctr[3], n_bad);
+    if (n_z) atomicAdd(&a.ctr[4], n_z);
+    if (n_out) atomicAdd(&a.ctr[5], n_out);
+    if (n_in) atomicAdd(&a.ctr[6], n_in);
+  }
+}
+
+__global__ void __launch_bounds__(256)
+    warp_finish_kernel(const long long *__restrict__ acc_iwe, const long long *__restrict__ acc_stack, const int32_t *__restrict__ ctr,
+                       float *__restrict__ iwe, float *__restrict__ stack_f32, int8_t *__restrict__ stack_i8, long n_iwe,
+                       long n_stack, int32_t *__restrict__ status) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool failed = (ctr[0] & RAMP_INTERP_BAD_TIMES) != 0;
+  const float qnan = __int_as_float(0x7fc00000), scale = 1.0f / (float)(1 << WARP_FIX_BITS);
+  if (i < 8) status[i] = i < 7 ? ctr[i] : 0;
+  if (i < n_iwe) {
+    iwe[i] = failed ? qnan : (float)acc_iwe[i] * scale;      // int64 -> fp32 rounds once; the power of two is exact
+  } else if (i - n_iwe < n_stack) {
+    const long j = i - n_iwe;
+    const long long v = acc_stack[j];
+    if (stack_f32) stack_f32[j] = failed ? qnan : (float)v * scale;
+    if (stack_i8) stack_i8[j] = failed ? (int8_t)0 : (int8_t)(v / (1ll << WARP_FIX_BITS));   // toward zero, then modulo 256
+  }
+}
+
+static size_t warp_acc_offset(int T) {
+  return ((size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS + WARP_REF_WORDS) * sizeof(float);    // the counters start here
+}
+
+template <bool IDENTITY>
+static int warp_launch_events(const WarpArgs &a, bool lds_times, bool vec, int grid, hipStream_t st) {
+  const size_t lds = (!IDENTITY && lds_times) ? (size_t)a.T * sizeof(double) : 0;
+  static_assert((size_t)INTERP_LDS_KNOTS * sizeof(double) + WARP_TILE * 17 <= 64 * 1024,
+                "LDS within the default limit: the launch needs no hipFuncSetAttribute");
+  if (!IDENTITY && lds_times) {
+    if (vec) hipLaunchKernelGGL((warp_event_kernel<IDENTITY, !IDENTITY, true>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
+    else hipLaunchKernelGGL((warp_event_kernel<IDENTITY, !IDENTITY, false>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
+  } else {
+    if (vec) hipLaunchKernelGGL((warp_event_kernel<IDENTITY, false, true>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
+    else hipLaunchKernelGGL((warp_event_kernel<IDENTITY, false, false>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
+  }
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+
+extern "C" {
+size_t ramp_event_warp_workspace_bytes(int T, int bins, int H, int W) {
+  if (H < 1 || W < 1) return 0;
+  return warp_acc_offset(T) + WARP_CTR_WORDS * sizeof(int32_t) + (size_t)(2 + (bins > 0 ? bins : 0)) * H * W * sizeof(long long);
+}
+long ramp_event_warp_grid_events(void) { return (long)WARP_MAX_GROUPS * WARP_TILE; }
+
+int ramp_event_warp(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
+                    const double *times, int T, double t_ref, const float *intrinsics, const float *invdepth, int flags,
+                    int bins, int H, int W, float *xy_out, float *iwe, float *stack_f32, int8_t *stack_i8, void *ws,
+                    size_t ws_bytes, int32_t *status, void *stream) {
+  const bool identity = (flags & RAMP_WARP_IDENTITY) != 0;
+  if (identity) T = 1;
+  if (N < 0 || T < 1 || H < 1 || W < 1 || bins < 1) return RAMP_EINVAL;
+  if (!xy_out && !iwe && !stack_f32 && !stack_i8) return RAMP_EINVAL;
+  if (flags & ~(RAMP_INTERP_EXTRAPOLATE | RAMP_WARP_DEPTH_MAP | RAMP_WARP_IDENTITY)) return RAMP_EINVAL;
+  if (N == 0) return RAMP_OK;
+  if (!x || !y || !p || !ws || !status) return RAMP_EINVAL;
+  if (!identity && (!t || !knots || !times || !intrinsics || !invdepth || !(fabs(t_ref) <= 1.7976931348623157e308)))
+    return RAMP_EINVAL;
+  if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)xy_out & 7) != 0) return RAMP_EINVAL;    // (xy_out rows are stored as float2)
+  if (ws_bytes < ramp_event_warp_workspace_bytes(T, bins, H, W)) return RAMP_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t HW = (size_t)H * W;
+  const bool stack = stack_f32 || stack_i8;
+  unsigned char *base = (unsigned char *)ws;
+  float *seg = (float *)base, *ref = seg + (size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS;
+  int32_t *ctr = (int32_t *)(base + warp_acc_offset(T));
+  long long *acc = (long long *)(ctr + WARP_CTR_WORDS);
+  long long *acc_iwe = iwe ? acc : nullptr, *acc_stack = stack ? acc + (iwe ? 2 * HW : 0) : nullptr;
+  const long n_iwe = iwe ? (long)(2 * HW) : 0, n_stack = stack ? (long)((size_t)bins * HW) : 0;
+  // the one memset: the counters and, behind them, the accumulators this call uses
+  if (hipMemsetAsync(ctr, 0, WARP_CTR_WORDS * sizeof(int32_t) + (size_t)(n_iwe + n_stack) * sizeof(long long), st) != hipSuccess)
+    return RAMP_ELAUNCH;
+  const int ex = (flags & RAMP_INTERP_EXTRAPOLATE) ? 1 : 0;
+  if (!identity) {
+    const int S = T > 1 ? T - 1 : 1;
+    hipLaunchKernelGGL(warp_segment_kernel, dim3(ramp_cdiv(S, INTERP_THREADS) + 1), dim3(INTERP_THREADS), 0, st, knots, times,
+                       T, t_ref, ex, seg, ref, ctr);
+    RAMP_CHECK_LAUNCH();
+  }
+  WarpArgs a;
+  a.x = x; a.y = y; a.t = t; a.p = p; a.knots = knots; a.times = times; a.seg = seg; a.ref = ref;
+  a.intrinsics = intrinsics; a.invdepth = invdepth; a.xy_out = xy_out; a.acc_iwe = acc_iwe; a.acc_stack = acc_stack;
+  a.ctr = ctr; a.N = N; a.T = T; a.bins = bins; a.H = H; a.W = W; a.extrapolate = ex;
+  a.depth_map = (flags & RAMP_WARP_DEPTH_MAP) ? 1 : 0;
+  const long tiles = ((long)N + WARP_TILE - 1) / WARP_TILE;
+  const int grid = (int)(tiles < WARP_MAX_GROUPS ? tiles : WARP_MAX_GROUPS);
+  const bool vec = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)p | (identity ? 0 : (uintptr_t)t)) & 15) == 0;
+  const int rc = identity ? warp_launch_events<true>(a, false, vec, grid, st)
+                          : warp_launch_events<false>(a, T <= INTERP_LDS_KNOTS, vec, grid, st);
+  if (rc != RAMP_OK) return rc;
+  const long n = n_iwe + n_stack > 8 ? n_iwe + n_stack : 8;
+  hipLaunchKernelGGL(warp_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, acc_iwe, acc_stack, ctr, iwe,
+                     stack_f32, stack_i8, n_iwe, n_stack, status);
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+}  // extern "C"

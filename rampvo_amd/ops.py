@@ -122,14 +122,30 @@ def corr(fmap1, fmaps2, coords, ii, jj, radius=3, coord_divs=(1.0,), layout=RAMP
 
 
 def event_stack(x, y, p, height, width, num_bins=5, as_float=True):
-    """EventToStack_Numpy on the device (reference utils/transformers.py:128-161): integer pixel
-    coordinates x, y [N] and polarities p [N] (int8, +-1; 0 is read as -1 like data/events.py:29) ->
-    the [num_bins, height, width] stack (float32 values of the int8 stack, or int8 with as_float=False)"""
+    """EventToStack_Numpy on the device (reference utils/transformers.py:128-161): pixel coordinates x, y [N] and
+    polarities p [N] (int8, +-1; 0 is read as -1 like data/events.py:29) -> the [num_bins, height, width] stack (float32
+    values of the int8 stack, or int8 with as_float=False).
+
+    Integer coordinate tensors: ramp_event_stack.  Floating-point coordinates take the sub-pixel bilinear path: an identity
+    warp of ramp_event_warp (four fixed-point weights per event, integer atomics, the same bins); the int8 stack is the
+    weighted sum truncated toward zero and wrapped, ``as_float`` its float32 values as above.  Integer-valued float
+    coordinates give the integer path's bits."""
     require_cuda(x, y, p)
     N = x.shape[0]
-    xi, yi = x.to(torch.int32).contiguous(), y.to(torch.int32).contiguous()
     pi = p.to(torch.int8)
     pi = torch.where(pi == 0, torch.full_like(pi, -1), pi).contiguous()
+    if x.is_floating_point() or y.is_floating_point():
+        out = torch.zeros((num_bins, height, width), dtype=torch.int8, device=x.device)
+        if N >= 2:      # fewer than 2 events: an empty grid (transformers.py:151-152)
+            xf, yf = x.to(torch.float32).contiguous(), y.to(torch.float32).contiguous()
+            nbytes = lib().ramp_event_warp_workspace_bytes(1, num_bins, height, width)
+            ws = _lib_workspace(nbytes, x.device, "evwarp")
+            status = torch.empty(8, dtype=torch.int32, device=x.device)
+            check(lib().ramp_event_warp(ptr(xf), ptr(yf), None, ptr(pi), N, None, None, 1, 0.0, None, None,
+                                        _lib.RAMP_WARP_IDENTITY, num_bins, height, width, None, None, None, ptr(out),
+                                        ptr(ws), nbytes, ptr(status), stream()), "ramp_event_warp")
+        return out.float() if as_float else out
+    xi, yi = x.to(torch.int32).contiguous(), y.to(torch.int32).contiguous()
     out = torch.empty((num_bins, height, width), dtype=torch.float32 if as_float else torch.int8, device=x.device)
     nbytes = lib().ramp_event_stack_workspace_bytes(num_bins, height, width)
     ws = _lib_workspace(nbytes, x.device, "evstack")
@@ -137,6 +153,78 @@ def event_stack(x, y, p, height, width, num_bins=5, as_float=True):
                                  None if as_float else ptr(out), ptr(out) if as_float else None, ptr(ws), nbytes,
                                  stream()), "ramp_event_stack")
     return out
+
+
+def event_warp(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, num_bins=0, extrapolate=False,
+               want_xy=False, want_iwe=True, stack=None):
+    """Motion compensation of an event list (include/ramp_hip.h ``ramp_event_warp``): every event is warped from the camera
+    pose at its own time stamp to the pose at ``t_ref`` and splat bilinearly, in one pass over the events.
+
+    ``x, y`` [N] pixel coordinates (fractions allowed), ``t`` [N] float64, ``p`` [N] polarity (+-1; 0 is read as -1);
+    ``knots`` [T,7] CAMERA-TO-WORLD with ``times`` [T] float64, as ``Ramp_vo.trajectory()`` returns them; ``intrinsics`` [4]
+    (fx, fy, cx, cy); ``invdepth`` a float, a 0-d / 1-element device tensor, or an [height, width] map (sampled at the
+    event's rounded pixel); 0 compensates the rotation alone.  Device tensors, ordered on the current stream, nothing
+    synchronised.
+
+    Returns a dict: ``status`` int32 [8] (``event_warp_status``) and, as requested, ``xy`` [N,2] (NaN rows for invalid
+    events), ``iwe`` [2,height,width] (polarity-signed sum, unsigned count), ``stack`` [num_bins,height,width] float32
+    (``stack="f32"``) or int8 (``"i8"``).  The sums are fixed point over integer atomics: the same bits for any order of
+    the events."""
+    require_cuda(x, y, t, p, knots, times)
+    if stack not in (None, "f32", "i8"):
+        raise RuntimeError("event_warp: stack is 'f32', 'i8' or None")
+    if stack is not None and num_bins < 1:
+        raise RuntimeError("event_warp: a stack needs num_bins >= 1")
+    dev = x.device
+    N = x.shape[0]
+    xf, yf = x.reshape(-1).to(torch.float32).contiguous(), y.reshape(-1).to(torch.float32).contiguous()
+    tf = t.reshape(-1).to(torch.float64).contiguous()
+    pi = p.reshape(-1).to(torch.int8)
+    pi = torch.where(pi == 0, torch.full_like(pi, -1), pi).contiguous()
+    knots = knots.reshape(-1, 7).contiguous().float()
+    times = times.reshape(-1).contiguous().double()
+    T = knots.shape[0]
+    if times.shape[0] != T:
+        raise RuntimeError("event_warp: %d knots but %d time stamps" % (T, times.shape[0]))
+    if not (yf.shape[0] == N and tf.shape[0] == N and pi.shape[0] == N):
+        raise RuntimeError("event_warp: x, y, t and p differ in length")
+    K = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(4).contiguous()
+    flags = _lib.RAMP_INTERP_EXTRAPOLATE if extrapolate else 0
+    if isinstance(invdepth, torch.Tensor) and invdepth.numel() != 1:
+        if tuple(invdepth.shape) != (height, width):
+            raise RuntimeError("event_warp: an inverse depth map is [height, width]")
+        require_cuda(invdepth)
+        d = invdepth.to(torch.float32).contiguous()
+        flags |= _lib.RAMP_WARP_DEPTH_MAP
+    elif isinstance(invdepth, torch.Tensor):
+        require_cuda(invdepth)
+        d = invdepth.reshape(1).to(torch.float32).contiguous()
+    else:
+        d = torch.full((1,), float(invdepth), dtype=torch.float32, device=dev)
+    bins = num_bins if stack is not None else 1
+    res = {"status": torch.zeros(8, dtype=torch.int32, device=dev)}
+    if want_xy:
+        res["xy"] = torch.empty((N, 2), dtype=torch.float32, device=dev)
+    if want_iwe:
+        res["iwe"] = torch.zeros((2, height, width), dtype=torch.float32, device=dev)
+    if stack is not None:
+        res["stack"] = torch.zeros((num_bins, height, width), dtype=torch.float32 if stack == "f32" else torch.int8, device=dev)
+    if N == 0:
+        return res
+    nbytes = lib().ramp_event_warp_workspace_bytes(T, bins, height, width)
+    ws = _lib_workspace(nbytes, dev, "evwarp")
+    check(lib().ramp_event_warp(ptr(xf), ptr(yf), ptr(tf), ptr(pi), N, ptr(knots), ptr(times), T, float(t_ref), ptr(K), ptr(d),
+                                flags, bins, height, width, ptr(res.get("xy")), ptr(res.get("iwe")),
+                                ptr(res["stack"]) if stack == "f32" else None, ptr(res["stack"]) if stack == "i8" else None,
+                                ptr(ws), nbytes, ptr(res["status"]), stream()), "ramp_event_warp")
+    return res
+
+
+def event_warp_status(status):
+    """the status words of ramp_event_warp as a dict (synchronises: one 32-byte copy)"""
+    w = status.detach().cpu()
+    return dict(bad_times=bool(int(w[0]) & _lib.RAMP_INTERP_BAD_TIMES), n_below=int(w[1]), n_above=int(w[2]),
+                n_not_finite=int(w[3]), n_rejected=int(w[4]), n_outside=int(w[5]), n_contributed=int(w[6]))
 
 
 def depth_median_fill(patches_state, n, F, patches_new):
@@ -381,6 +469,13 @@ def depth_median(patches_state, n, frames, out):
     _, M, _, P, _ = patches_state.shape
     check(lib().ramp_depth_median(ptr(patches_state[n - frames]), int(frames), M, P, ptr(out), stream()),
           "ramp_depth_median")
+
+
+def depth_median_rows(patches_state, n_dev, frames, out):
+    """the same with the row count read on the device: the median of rows n - frames .. n - 1, n = ``n_dev[0]`` (int32)"""
+    _, M, _, P, _ = patches_state.shape
+    check(lib().ramp_depth_median_rows(ptr(patches_state), ptr(n_dev), int(frames), M, P, ptr(out), stream()),
+          "ramp_depth_median_rows")
 
 
 def frame_commit(poses, n, motion, damping, tstamps, counter, index_map, index_val, intrinsics, copy_k, patches_state,
