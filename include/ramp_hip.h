@@ -1077,6 +1077,61 @@ int ramp_event_warp(const float *x, const float *y, const double *t, const int8_
                     int bins, int H, int W, float *xy_out, float *iwe, float *stack_f32, int8_t *stack_i8, void *ws,
                     size_t ws_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------- inverse-depth map (csrc/depthmap.hip)
+ *
+ * ramp_invdepth_map: the selected patches of the window are projected into one camera pose and regressed to a dense map of
+ * inverse depth -- the [H][W] map ramp_event_warp samples with RAMP_WARP_DEPTH_MAP.
+ *   poses [ceil(n / M)][7] world-to-camera (the tracker's poses); patches [n][3][P][P] (x, y, inverse depth; the centre
+ *   pixel (P / 2, P / 2) is read), patch k belongs to frame k / M; intrinsics: device (fx, fy, cx, cy) at patch resolution;
+ *   scale > 0: image pixel = scale * patch coordinate (the image intrinsics are scale * intrinsics); cam: device float [7], a
+ *   CAMERA-TO-WORLD pose, a row of ramp_trajectory_resolve / ramp_se3_interp.
+ *   Selection: index != NULL: the patch ids index[0 .. *count) as ramp_map_select writes them (K: the capacity of index;
+ *   count == NULL: all K; *count is clamped to [0, K]); index == NULL: all patches below the clipped n, or with
+ *   last_rows > 0 the newest last_rows * per_row of them.  dyn_rows != NULL: n is clipped to *dyn_rows * per_row on the
+ *   device, exactly as ramp_map_select does (n is then the capacity).  An id outside [0, clipped n) is rejected as a patch
+ *   without a depth.  The record capacity Kc is K with an index, else n, or min(n, last_rows * per_row).
+ *   conf [n] (NULL: c = 1): the confidence of patch k, or with RAMP_DEPTHMAP_CONF_IS_VARIANCE its variance, c = 1 / conf[k].
+ *   prior: device float (NULL allowed when prior_weight == 0), pw = prior_weight, or with RAMP_DEPTHMAP_PRIOR_RELATIVE
+ *   pw = prior_weight / prior^2 formed on the device (a prior of relative sigma prior_weight^-1/2, to be weighed against
+ *   1 / variance confidences).  prior_weight == 0: pw = 0 and the prior is not read.  radius R > 0: the support, image pixels.
+ * Stage 1, per selected patch with r = ((x - cx) / fx, (y - cy) / fy, 1) and inverse depth d (fp32, the arithmetic of
+ * ramp_se3_inv / ramp_se3_mul):
+ *     G = cam^-1 * T_i^-1,   X' = R_G r + t_G d,   u = scale * (fx X'/Z' + cx),  v likewise,   d' = d / Z'
+ *   gives the record (u, v, d', c).  A rejected patch is counted in exactly one status word, tested in this order:
+ *     [2] d or c is not finite or <= 0 (an infinite variance included; an id outside the patches)
+ *     [3] Z' <= RAMP_WARP_MIN_Z or NaN, or u, v or d' not finite
+ *     [4] out of reach: u < -R, u > W - 1 + R, or the same in v
+ *   and its record carries weight exactly 0: (NaN, NaN, NaN, 0) for [2] and [3], (u, v, d', 0) for [4].
+ * Stage 2, per integer pixel (x, y), in fp32 without FMA, the sums running over the records in selection order:
+ *     s_k = 1 - ((x - u_k)^2 + (y - v_k)^2) * (1 / R^2),   w_k = c_k * max(s_k, 0)^2        (biweight: compact support)
+ *     S0 = sum w_k,  S1 = sum w_k d'_k,   invdepth = (pw * prior + S1) / (pw + S0),   weight = S0
+ *   A pixel with S0 == 0 gets the prior's own bits when pw > 0 and NaN when pw == 0 -- never a plausible number;
+ *   ramp_event_warp rejects and counts an event that samples NaN.  A pw that is not finite (a relative prior of 0) makes
+ *   every pixel NaN.  A record that is culled for a tile would have contributed w = 0 exactly and all terms are >= 0: a pixel's
+ *   bits do not depend on tiling or culling, and a call repeats its bits (no atomics in the sums).
+ * Outputs, each optional (NULL): invdepth [H][W], weight [H][W], records [Kc][4] (rows behind the live count are zero).
+ * status: device int32 [8], written by the call: [0] bits (RAMP_DEPTHMAP_BAD_CAM: an entry of cam is not finite), [1] patches
+ *   considered, [2] / [3] / [4] rejected as above, [5] contributing, [6] pixels with S0 == 0 (0 when neither map is
+ *   requested), [7] 0.  [2] + [3] + [4] + [5] = [1].  RAMP_DEPTHMAP_BAD_CAM makes every output NaN (the live records
+ *   included); the patches that pass the test of [2] are then counted in [3].  Outcomes of the data: RAMP_OK.
+ * ws: ramp_invdepth_map_workspace_bytes(Kc) bytes, 16-byte aligned (the live count and the records).  Launches: one 32-byte
+ *   hipMemsetAsync (the status words are the counters) and two kernels -- one when only records are requested -- all on
+ *   `stream`, nothing synchronised.  n == 0, an empty selection and a NULL selection on zero capacity are legal and run the
+ *   launches (the sizes live on the device): the prior everywhere, or NaN and weight 0 with pw == 0.
+ * RAMP_EINVAL: H, W < 1; R or scale not finite or <= 0; prior_weight negative or not finite; no output requested; M, P < 1;
+ *   unknown flags; count without index; last_rows > 0 with per_row < 1; a NULL prior with prior_weight > 0.
+ * ramp_invdepth_map_stage_records(): the number of records one LDS chunk of the regression holds.                       */
+#define RAMP_DEPTHMAP_CONF_IS_VARIANCE 1
+#define RAMP_DEPTHMAP_PRIOR_RELATIVE 2
+#define RAMP_DEPTHMAP_BAD_CAM 1 /* status[0] bit 0 */
+size_t ramp_invdepth_map_workspace_bytes(int K);
+int ramp_invdepth_map_stage_records(void);
+int ramp_invdepth_map(const float *poses, const float *patches, const float *intrinsics, const float *cam, int n, int M, int P,
+                      float scale, const int32_t *index, const int32_t *count, int K, const int32_t *dyn_rows, int per_row,
+                      int last_rows, const float *conf, const float *prior, float prior_weight, float radius, int flags, int H,
+                      int W, float *invdepth, float *weight, float *records, void *ws, size_t ws_bytes, int32_t *status,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -585,7 +585,8 @@ class Ramp_vo:
         return poses.cpu().numpy(), (tw.cpu().numpy() if twist else None)
 
     def compensate_events(self, x, y, t, p, t_ref=None, invdepth=None, num_bins=0, extrapolate=False, want_xy=False,
-                          want_iwe=True, stack=None, height=None, width=None, as_tensor=False):
+                          want_iwe=True, stack=None, height=None, width=None, as_tensor=False, radius=None,
+                          weights="variance"):
         """Motion compensation with the trajectory as it is now: every event (``x, y`` pixel coordinates of the images the
         tracker is fed, ``t`` in the unit of the frames' time stamps, ``p`` polarity) is warped from the camera pose at its
         own time stamp to the pose at ``t_ref`` and splat bilinearly into an image of warped events and / or a bin stack
@@ -594,8 +595,11 @@ class Ramp_vo:
 
         ``t_ref=None``: the newest frame's time stamp.  ``invdepth=None``: the lower median inverse depth of the last three
         frames' patches -- the value the next frame's patches start from -- computed into a device word the host never
-        reads; otherwise a float, a one-element device tensor or a [height, width] map.  Intrinsics: row 0 of the tracker's
-        own times the patch stride, i.e. those of the images it was fed.  ``height, width`` default to the tracker's.
+        reads; otherwise a float, a one-element device tensor or a [height, width] map; ``"map"``: the map
+        ``invdepth_map(t_ref, radius, weights)`` renders from the window's patches at the reference pose, so that every event is
+        warped with the depth the tracker has estimated near its pixel (``radius``, ``weights`` are read in this mode only).
+        Intrinsics: row 0 of the tracker's own times the patch stride, i.e. those of the images it was fed.  ``height, width``
+        default to the tracker's.
 
         A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
         the dict of device tensors of ``ops.event_warp`` (``status``, ``xy``, ``iwe``, ``stack`` as requested), ordered on
@@ -603,6 +607,11 @@ class Ramp_vo:
         frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
         if not self.tlist:
             raise RuntimeError("compensate_events(): no frame has been tracked yet")
+        if isinstance(invdepth, str):
+            if invdepth != "map":
+                raise RuntimeError("compensate_events(): invdepth is None, a number, a tensor or 'map'")
+            invdepth = self.invdepth_map(t_ref=t_ref, radius=radius, weights=weights, height=height, width=width,
+                                         as_tensor=True)["invdepth"]
         knots, _ = self.trajectory(as_tensor=True)
         dev = self.device
         dv = self._dev
@@ -615,12 +624,7 @@ class Ramp_vo:
             with torch.cuda.stream(st):                       # reads of the state, on the stream it lives on
                 K = self.intrinsics_[0] * float(self.RES)
                 if invdepth is None:
-                    invdepth = torch.zeros(1, dtype=torch.float32, device=dev)
-                    if resident:
-                        ops.depth_median_rows(self.patches_, dv.dyn[track_dev.DYN_NROW:], 3, invdepth)
-                    elif self._n > 0:
-                        f = min(3, self._n)
-                        ops.depth_median(self.patches_, self._n, f, invdepth)
+                    invdepth = self._depth_median_word(resident)
             if own:
                 ev = torch.cuda.Event()
                 ev.record(st)
@@ -644,6 +648,108 @@ class Ramp_vo:
             raise RuntimeError("compensate_events(): a frame is neither a keyframe nor reachable through the delta chain")
         if int(words[0]) & 1:
             raise RuntimeError("compensate_events(): the frames' time stamps decrease or are not finite")
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def _depth_median_word(self, resident):
+        """(on the stream the state lives on) the lower median inverse depth of the last three frames' patches as a device
+        word the host never reads; 0 without a frame"""
+        word = torch.zeros(1, dtype=torch.float32, device=self.device)
+        if resident:
+            ops.depth_median_rows(self.patches_, self._dev.dyn[track_dev.DYN_NROW:], 3, word)
+        elif self._n > 0:
+            ops.depth_median(self.patches_, self._n, min(3, self._n), word)
+        return word
+
+    def invdepth_map(self, t_ref=None, radius=None, weights="variance", max_rel_depth_sigma=None, min_obs=2,
+                     prior_rel_sigma=1.0, height=None, width=None, as_tensor=False):
+        """A dense inverse-depth map [height, width] of the scene as the tracker has estimated it, at the camera pose of time
+        ``t_ref`` (default: the newest frame): the window's patches are projected into that pose (one row of ``poses_at``)
+        and regressed with a biweight kernel of support ``radius`` image pixels (``ops.invdepth_map``).  The map is what
+        ``compensate_events(invdepth=...)`` and ``ops.event_warp`` sample at an event's pixel.
+
+        ``weights="variance"``: the patches ``map(max_rel_depth_sigma=..., min_obs=...)`` selects (the same query: one C call
+        for the covariance, one for the selection), each weighted by the inverse of its marginal depth variance, against a
+        prior of RELATIVE sigma ``prior_rel_sigma`` -- weight ``prior_rel_sigma**-2 / prior**2``, formed on the device.
+        ``weights="uniform"``: no covariance call; the patches of the newest ``REMOVAL_WINDOW`` frames with weight 1 against a
+        prior of weight ``prior_rel_sigma**-2``.  The prior is the median inverse depth ``compensate_events`` uses by default,
+        so a pixel no patch reaches gets the median and a pixel between patches is drawn to it as the kernel weight falls.
+        ``radius=None``: ``max(height, width) / 10`` -- a default nobody has tuned.  ``height, width`` default to the
+        tracker's.
+
+        A device-resident state stays device resident (no settle(), nothing of the state written; the row count, the selection
+        and the median are read on the device).  ``as_tensor=True``: a dict of device tensors ``invdepth``, ``weight`` (the
+        summed kernel weight per pixel), ``status`` (ops.invdepth_map_status) and ``pose_status`` (ops.se3_interp), ordered on
+        the current stream, nothing synchronised.  Otherwise numpy arrays, which waits for the result and raises when the
+        pose at ``t_ref`` is not finite and on the conditions ``poses_at`` raises on."""
+        if not self.tlist:
+            raise RuntimeError("invdepth_map(): no frame has been tracked yet")
+        if weights not in ("variance", "uniform"):
+            raise RuntimeError("invdepth_map(): weights is 'variance' or 'uniform'")
+        if not prior_rel_sigma > 0:
+            raise RuntimeError("invdepth_map(): prior_rel_sigma is positive")
+        H, W = self.ht if height is None else int(height), self.wd if width is None else int(width)
+        R = max(H, W) / 10.0 if radius is None else float(radius)
+        pw = float(prior_rel_sigma) ** -2
+        cams, _, pose_status = self.poses_at([self.tlist[-1] if t_ref is None else float(t_ref)], as_tensor=True)
+        dev, dv, M = self.device, self._dev, self.M
+        is_resident = dv is not None and dv.active
+        own = getattr(self, "_main_used", False)              # (inputs_ready = "stream": the state is the tracker's own stream's)
+        cur = torch.cuda.current_stream(dev)
+        if own:                                               # the pose is read on the stream the state lives on
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            self._main_stream.wait_event(ev)
+            cams.record_stream(self._main_stream)
+
+        def render(resident, index=None, count=None, dvar=None):
+            dyn = dv.dyn[track_dev.DYN_NROW:] if resident else None
+            prior = self._depth_median_word(resident)
+            if dvar is not None:
+                r = ops.invdepth_map(self.poses_, self.patches_, self.intrinsics_[0], cams[0], H, W, R, scale=self.RES,
+                                     index=index, count=count, conf=dvar, conf_is_variance=True, prior=prior, prior_weight=pw,
+                                     prior_relative=True, dyn_rows=dyn, per_row=M)
+            else:
+                n = self.N if resident else self._n
+                r = ops.invdepth_map(self.poses_[:n], self.patches_[:n], self.intrinsics_[0], cams[0], H, W, R, scale=self.RES,
+                                     prior=prior, prior_weight=pw, dyn_rows=dyn, per_row=M,
+                                     last_rows=int(self.cfg.REMOVAL_WINDOW))
+            return r["invdepth"], r["weight"], r["status"]
+
+        if weights == "variance":
+            def then(resident, out):
+                _, dvar, _, _, pcov, _, nobs = out
+                if resident:
+                    index, count = ops.map_select(pcov, dvar, self.patches_, nobs, None, max_rel_depth_sigma, min_obs,
+                                                  dyn_rows=dv.dyn[track_dev.DYN_NROW:], per_row=M)
+                else:
+                    index, count = ops.map_select(pcov, dvar, self.patches_, nobs, None, max_rel_depth_sigma, min_obs,
+                                                  n=self._n * M)
+                return render(resident, index, count, dvar)
+
+            inv, wgt, status = self._window_query("invdepth_map()", with_map=True, then=then)[-3:]
+        else:
+            with torch.no_grad():
+                st = self._main_stream if own else cur
+                with torch.cuda.stream(st):
+                    if not is_resident:
+                        self._join_main()
+                    inv, wgt, status = render(is_resident)
+                if own:
+                    ev = torch.cuda.Event()
+                    ev.record(st)
+                    cur.wait_event(ev)
+                    for z in (inv, wgt, status):
+                        z.record_stream(cur)
+        out = dict(invdepth=inv, weight=wgt, status=status, pose_status=pose_status)
+        if as_tensor:
+            return out
+        words = torch.cat([status, pose_status, self._traj_status]).cpu()      # (the one wait)
+        if int(words[12]) & track_dev.TRAJ_UNRESOLVED:
+            raise RuntimeError("invdepth_map(): a frame is neither a keyframe nor reachable through the delta chain")
+        if int(words[8]) & 1:
+            raise RuntimeError("invdepth_map(): the frames' time stamps decrease or are not finite")
+        if int(words[0]) & 1:
+            raise RuntimeError("invdepth_map(): the camera pose at t_ref is not finite")
         return {k: v.cpu().numpy() for k, v in out.items()}
 
     # --------------------------------------------------------------- uncertainty

@@ -227,6 +227,78 @@ def event_warp_status(status):
                 n_not_finite=int(w[3]), n_rejected=int(w[4]), n_outside=int(w[5]), n_contributed=int(w[6]))
 
 
+def invdepth_map(poses, patches, intrinsics, cam, height, width, radius, scale=1, index=None, count=None, conf=None,
+                 conf_is_variance=False, prior=None, prior_weight=0.0, prior_relative=False, dyn_rows=None, per_row=0,
+                 last_rows=0, want_weight=True, want_records=False):
+    """Dense inverse-depth map from patches (include/ramp_hip.h ``ramp_invdepth_map``): the selected patches are projected
+    into the pose ``cam`` and regressed with a biweight kernel of support ``radius`` (image pixels) -- the [height, width]
+    map ``event_warp`` takes as ``invdepth``.
+
+    ``poses`` [n,7] world-to-camera, ``patches`` [n*M,3,P,P] (or [n,M,3,P,P]; M = patches per pose row), ``intrinsics`` row 0
+    (fx, fy, cx, cy) at patch resolution, image pixel = ``scale`` x patch coordinate; ``cam`` [7] a device CAMERA-TO-WORLD
+    pose, a row of ``Ramp_vo.trajectory()`` / ``poses_at()``.  ``index`` / ``count``: the selection as ``map_select`` returns
+    it (device int32 list and device count; ``count=None``: the whole list), or None for all patches -- with ``last_rows``
+    the newest ``last_rows * per_row`` of them.  ``dyn_rows``: a device int32 word that clips the patches to ``dyn_rows *
+    per_row`` on the device.  ``conf`` [n*M]: per-patch confidence, or variance with ``conf_is_variance`` (c = 1 / conf).
+    ``prior``: a float or a one-element device tensor, weighted ``prior_weight``, or ``prior_weight / prior**2`` with
+    ``prior_relative``.  Device tensors, ordered on the current stream, nothing synchronised.
+
+    Returns a dict of device tensors: ``invdepth`` [height, width] (NaN where neither a patch nor a prior reaches),
+    ``status`` int32 [8] (``invdepth_map_status``) and, as requested, ``weight`` [height, width] (the summed kernel weight)
+    and ``records`` [K,4] (u, v, d', c per slot of the selection; weight 0: rejected)."""
+    require_cuda(poses, patches, cam, index, count, conf, dyn_rows)
+    dev = cam.device
+    P = patches.shape[-1]
+    poses = poses.reshape(-1, 7)
+    n = patches.numel() // (3 * P * P)
+    if poses.dtype != torch.float32 or patches.dtype != torch.float32 or not (poses.is_contiguous() and patches.is_contiguous()):
+        raise RuntimeError("invdepth_map: poses and patches are contiguous float32")
+    if n and (poses.shape[0] == 0 or n % poses.shape[0]):
+        raise RuntimeError("invdepth_map: %d patches do not divide into %d pose rows" % (n, poses.shape[0]))
+    M = max(n // max(poses.shape[0], 1), 1)
+    K4 = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(-1)[:4].contiguous()
+    camf = cam.reshape(7).to(torch.float32).contiguous()
+    for name, x in (("index", index), ("count", count), ("dyn_rows", dyn_rows)):
+        if x is not None and (x.dtype != torch.int32 or not x.is_contiguous()):
+            raise RuntimeError("invdepth_map: %s is a contiguous int32 tensor" % name)
+    if count is not None and index is None:
+        raise RuntimeError("invdepth_map: a count needs an index")
+    if conf is not None:
+        conf = conf.reshape(-1)
+        if conf.dtype != torch.float32 or not conf.is_contiguous() or conf.numel() < n:
+            raise RuntimeError("invdepth_map: conf is contiguous float32, one entry per patch")
+    if isinstance(prior, torch.Tensor):
+        require_cuda(prior)
+        pr = prior.reshape(-1)[:1].to(torch.float32).contiguous()
+    elif prior is not None:
+        pr = torch.full((1,), float(prior), dtype=torch.float32, device=dev)
+    else:
+        pr = None
+    Ki = int(index.numel()) if index is not None else 0
+    Kc = Ki if index is not None else (min(n, int(last_rows) * int(per_row)) if last_rows > 0 else n)
+    flags = (_lib.RAMP_DEPTHMAP_CONF_IS_VARIANCE if conf_is_variance else 0) | (_lib.RAMP_DEPTHMAP_PRIOR_RELATIVE if prior_relative else 0)
+    res = {"status": torch.zeros(8, dtype=torch.int32, device=dev),
+           "invdepth": torch.empty((height, width), dtype=torch.float32, device=dev)}
+    if want_weight:
+        res["weight"] = torch.empty((height, width), dtype=torch.float32, device=dev)
+    if want_records:
+        res["records"] = torch.empty((Kc, 4), dtype=torch.float32, device=dev)
+    nbytes = lib().ramp_invdepth_map_workspace_bytes(Kc)
+    ws = _lib_workspace(nbytes, dev, "depthmap")
+    check(lib().ramp_invdepth_map(ptr(poses), ptr(patches), ptr(K4), ptr(camf), n, M, P, float(scale), ptr(index), ptr(count),
+                                  Ki, ptr(dyn_rows), int(per_row), int(last_rows), ptr(conf), ptr(pr), float(prior_weight),
+                                  float(radius), flags, int(height), int(width), ptr(res["invdepth"]), ptr(res.get("weight")),
+                                  ptr(res.get("records")), ptr(ws), nbytes, ptr(res["status"]), stream()), "ramp_invdepth_map")
+    return res
+
+
+def invdepth_map_status(status):
+    """the status words of ramp_invdepth_map as a dict (synchronises: one 32-byte copy)"""
+    w = status.detach().cpu()
+    return dict(bad_cam=bool(int(w[0]) & _lib.RAMP_DEPTHMAP_BAD_CAM), n_considered=int(w[1]), n_bad_depth=int(w[2]),
+                n_rejected=int(w[3]), n_out_of_reach=int(w[4]), n_contributing=int(w[5]), n_empty_pixels=int(w[6]))
+
+
 def depth_median_fill(patches_state, n, F, patches_new):
     """patches_new[:, 2] = median of patches_state[n-F:n, :, 2] (reference Ramp_vo.py:370-371), one launch.
     patches_state [N,M,3,P,P], patches_new [M,3,P,P] (both contiguous fp32)"""
