@@ -451,6 +451,13 @@ def _idx(t):
     return t.contiguous()
 
 
+def _geometry(poses, patches, intrinsics):
+    """poses [..,7], patches [..,3,P,P], intrinsics [..,4] as the flat contiguous fp32 tensors the kernels read, and P"""
+    P = patches.shape[-1]
+    return (poses.reshape(-1, 7).contiguous().float(), patches.reshape(-1, 3, P, P).contiguous().float(),
+            intrinsics.reshape(-1, 4).contiguous().float(), P)
+
+
 def transform(poses, patches, intrinsics, ii, jj, kk, tonly=False):
     """Ramp_vo.reproject: poses [..,7], patches [..,3,P,P], intrinsics [..,4] -> [1,E,2,P,P]"""
     require_cuda(poses, patches, intrinsics, ii, jj, kk)
@@ -458,9 +465,7 @@ def transform(poses, patches, intrinsics, ii, jj, kk, tonly=False):
     f32 = torch.float32
     if not (poses.dtype == f32 and patches.dtype == f32 and intrinsics.dtype == f32 and poses.is_contiguous()
             and patches.is_contiguous() and intrinsics.is_contiguous()):        # (the tracker's buffers are)
-        poses = poses.reshape(-1, 7).contiguous().float()
-        patches = patches.reshape(-1, 3, P, P).contiguous().float()
-        intrinsics = intrinsics.reshape(-1, 4).contiguous().float()
+        poses, patches, intrinsics, P = _geometry(poses, patches, intrinsics)
     E = ii.shape[0]
     out = torch.empty((1, E, 2, P, P), dtype=torch.float32, device=poses.device)
     check(lib().ramp_transform(ptr(poses), ptr(patches), ptr(intrinsics), ptr(_idx(ii)),
@@ -472,10 +477,7 @@ def transform(poses, patches, intrinsics, ii, jj, kk, tonly=False):
 def reproject(poses, patches, intrinsics, ii, jj, kk):
     """cuda_ba.reproject -> [1,E,2,P,P]"""
     require_cuda(poses, patches, intrinsics, ii, jj, kk)
-    P = patches.shape[-1]
-    poses = poses.reshape(-1, 7).contiguous().float()
-    patches = patches.reshape(-1, 3, P, P).contiguous().float()
-    intrinsics = intrinsics.reshape(-1, 4).contiguous().float()
+    poses, patches, intrinsics, P = _geometry(poses, patches, intrinsics)
     E = ii.shape[0]
     out = torch.empty((1, E, 2, P, P), dtype=torch.float32, device=poses.device)
     check(lib().ramp_reproject(ptr(poses), ptr(patches), ptr(intrinsics), ptr(_idx(ii)),
@@ -487,10 +489,7 @@ def reproject(poses, patches, intrinsics, ii, jj, kk):
 def point_cloud(poses, patches, intrinsics, ix):
     """3-D point of every patch centre: patches [m,3,P,P] (or [1,m,..]), ix [m] -> [m,3]"""
     require_cuda(poses, patches, intrinsics, ix)
-    P = patches.shape[-1]
-    poses = poses.reshape(-1, 7).contiguous().float()
-    patches = patches.reshape(-1, 3, P, P).contiguous().float()
-    intrinsics = intrinsics.reshape(-1, 4).contiguous().float()
+    poses, patches, intrinsics, P = _geometry(poses, patches, intrinsics)
     m = ix.shape[0]
     assert patches.shape[0] >= m
     out = torch.empty((m, 3), dtype=torch.float32, device=poses.device)
@@ -502,10 +501,7 @@ def point_cloud(poses, patches, intrinsics, ix):
 def motionmag(poses, patches, intrinsics, ii, jj, kk, pair_groups, key_ij, key_ji, beta=0.5):
     """[mean flow i->j, mean flow j->i] (device tensor [2]); pair_groups: the (ii, jj) grouping"""
     require_cuda(poses, patches, intrinsics, ii, jj, kk)
-    P = patches.shape[-1]
-    poses = poses.reshape(-1, 7).contiguous().float()
-    patches = patches.reshape(-1, 3, P, P).contiguous().float()
-    intrinsics = intrinsics.reshape(-1, 4).contiguous().float()
+    poses, patches, intrinsics, P = _geometry(poses, patches, intrinsics)
     out = torch.empty(2, dtype=torch.float32, device=poses.device)
     g = pair_groups
     check(lib().ramp_motionmag(ptr(poses), ptr(patches), ptr(intrinsics), ptr(_idx(ii)), ptr(_idx(jj)),
@@ -525,15 +521,22 @@ def multi_copy(pairs):
     check(lib().ramp_multi_copy(src, dst, nbytes, n, stream()), "ramp_multi_copy")
 
 
-def store_rows(srcs, rows):
-    """one launch: contiguous tensor srcs[i] -> row rows[i][1] of the contiguous buffer rows[i][0] (no view tensors)"""
+def _row_copies(srcs, bufs, rows=None):
+    """descriptor arrays (src, dst, row_bytes) and the row sizes in bytes for: contiguous tensor srcs[i] -> one row of the
+    contiguous buffer bufs[i]; row rows[i], or with rows=None dst is left for the caller to fill"""
     n = len(srcs)
-    rb = [b.stride(0) * b.element_size() for b, _ in rows]
-    for s_, (b, _), nb in zip(srcs, rows, rb):
+    rb = [b.stride(0) * b.element_size() for b in bufs]
+    for s_, b, nb in zip(srcs, bufs, rb):
         assert s_.numel() * s_.element_size() == nb and s_.is_contiguous() and b.is_contiguous()
     src = (ctypes.c_void_p * n)(*[s_.data_ptr() for s_ in srcs])
-    dst = (ctypes.c_void_p * n)(*[b.data_ptr() + int(r) * nb for (b, r), nb in zip(rows, rb)])
-    check(lib().ramp_multi_copy(src, dst, (ctypes.c_long * n)(*rb), n, stream()), "ramp_multi_copy")
+    dst = (ctypes.c_void_p * n)(*([] if rows is None else [b.data_ptr() + int(r) * nb for b, r, nb in zip(bufs, rows, rb)]))
+    return src, dst, (ctypes.c_long * n)(*rb), rb
+
+
+def store_rows(srcs, rows):
+    """one launch: contiguous tensor srcs[i] -> row rows[i][1] of the contiguous buffer rows[i][0] (no view tensors)"""
+    src, dst, rbc, _ = _row_copies(srcs, [b for b, _ in rows], [r for _, r in rows])
+    check(lib().ramp_multi_copy(src, dst, rbc, len(srcs), stream()), "ramp_multi_copy")
 
 
 def depth_median(patches_state, n, frames, out):
@@ -555,17 +558,12 @@ def frame_commit(poses, n, motion, damping, tstamps, counter, index_map, index_v
     """ramp_frame_commit: frame_begin + depth_median_fill + the state stores of one frame in one launch;
     srcs[i] -> row rows[i][1] of buffer rows[i][0] (like store_rows), patches_new -> patches_state[n];
     median_dev: the median of the last ``median_frames`` frames if the caller computed it ahead (depth_median)"""
-    n_copy = len(srcs)
-    rb = [b.stride(0) * b.element_size() for b, _ in rows]
-    for s_, (b, _), nb in zip(srcs, rows, rb):
-        assert s_.numel() * s_.element_size() == nb and s_.is_contiguous() and b.is_contiguous()
-    src = (ctypes.c_void_p * n_copy)(*[s_.data_ptr() for s_ in srcs])
-    dst = (ctypes.c_void_p * n_copy)(*[b.data_ptr() + int(r) * nb for (b, r), nb in zip(rows, rb)])
+    src, dst, rbc, _ = _row_copies(srcs, [b for b, _ in rows], [r for _, r in rows])
     _, M, _, P, _ = patches_state.shape
     check(lib().ramp_frame_commit(ptr(poses), int(n), int(motion), float(damping), ptr(tstamps), int(counter),
                                   ptr(index_map), int(index_val), ptr(intrinsics), int(bool(copy_k)), ptr(patches_state),
-                                  int(median_frames), M, P, ptr(patches_new), n_copy, src, dst,
-                                  (ctypes.c_long * n_copy)(*rb), ptr(median_dev), stream()), "ramp_frame_commit")
+                                  int(median_frames), M, P, ptr(patches_new), len(srcs), src, dst, rbc,
+                                  ptr(median_dev), stream()), "ramp_frame_commit")
 
 
 class FrameCommitPlan:
@@ -574,15 +572,10 @@ class FrameCommitPlan:
     kernel, where the host is the limiter)"""
 
     def __init__(self, srcs, bufs, patches_state):
-        n = self.n_copy = len(srcs)
+        self.n_copy = len(srcs)
         self.keep = (list(srcs), list(bufs), patches_state)
-        self.rb = [b.stride(0) * b.element_size() for b in bufs]
-        for s_, b, nb in zip(srcs, bufs, self.rb):
-            assert s_.numel() * s_.element_size() == nb and s_.is_contiguous() and b.is_contiguous()
-        self.src = (ctypes.c_void_p * n)(*[s_.data_ptr() for s_ in srcs])
-        self.dst = (ctypes.c_void_p * n)()
+        self.src, self.dst, self.rbc, self.rb = _row_copies(srcs, bufs)
         self.base = [b.data_ptr() for b in bufs]
-        self.rbc = (ctypes.c_long * n)(*self.rb)
         _, self.M, _, self.P, _ = patches_state.shape
         self.src_ptrs = tuple(s_.data_ptr() for s_ in srcs)
 
@@ -598,7 +591,8 @@ class FrameCommitPlan:
 
 
 class ShiftPlan:
-    """descriptor arrays of shift_rows for a fixed set of buffers (built once)"""
+    """ramp_shift_rows for a fixed set of buffers -- bufs: list of (tensor [rows, ...], ring_modulus or 0) -- whose
+    descriptor arrays are built once; run(k, nrows): rows k+1..nrows-1 move down by one"""
 
     def __init__(self, bufs):
         n = self.n = len(bufs)
@@ -612,17 +606,6 @@ class ShiftPlan:
     def run(self, k, nrows):
         check(lib().ramp_shift_rows(self.base, self.rb, self.mod, self.n, int(k), int(nrows), stream()),
               "ramp_shift_rows")
-
-
-def shift_rows(bufs, k, nrows):
-    """bufs: list of (tensor [rows, ...], ring_modulus or 0); rows k+1..nrows-1 move down by one"""
-    n = len(bufs)
-    base = (ctypes.c_void_p * n)(*[t.data_ptr() for t, _ in bufs])
-    rb = (ctypes.c_long * n)(*[t[0].numel() * t.element_size() for t, _ in bufs])
-    mod = (ctypes.c_int * n)(*[int(m) for _, m in bufs])
-    for t, _ in bufs:
-        assert t.is_contiguous()
-    check(lib().ramp_shift_rows(base, rb, mod, n, int(k), int(nrows), stream()), "ramp_shift_rows")
 
 
 def motion_model(poses, n, damping):
@@ -648,11 +631,7 @@ class Groups:
     __slots__ = ("order", "gid", "seg_start", "ukeys", "ngroups", "E")
 
 
-def group_by(keys, key_bound=0):
-    require_cuda(keys)
-    keys = _idx(keys)
-    E = keys.shape[0]
-    dev = keys.device
+def _new_groups(E, dev):
     g = Groups()
     g.E = E
     g.order = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
@@ -660,6 +639,15 @@ def group_by(keys, key_bound=0):
     g.seg_start = torch.empty(E + 1, dtype=torch.int32, device=dev)
     g.ukeys = torch.empty(max(E, 1), dtype=torch.int64, device=dev)
     g.ngroups = torch.empty(1, dtype=torch.int32, device=dev)
+    return g
+
+
+def group_by(keys, key_bound=0):
+    require_cuda(keys)
+    keys = _idx(keys)
+    E = keys.shape[0]
+    dev = keys.device
+    g = _new_groups(E, dev)
     nbytes = lib().ramp_group_by_workspace_bytes(E)
     ws = _lib.workspace(nbytes, dev, "graph")
     check(lib().ramp_group_by(ptr(keys), E, int(key_bound), ptr(g.order), ptr(g.gid),
@@ -675,13 +663,7 @@ def group_by_small(a, b, mul, sub, K, max_groups=0):
     b = _idx(b) if b is not None else None
     E = a.shape[0]
     dev = a.device
-    g = Groups()
-    g.E = E
-    g.order = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-    g.gid = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-    g.seg_start = torch.empty(E + 1, dtype=torch.int32, device=dev)
-    g.ukeys = torch.empty(max(E, 1), dtype=torch.int64, device=dev)
-    g.ngroups = torch.empty(1, dtype=torch.int32, device=dev)
+    g = _new_groups(E, dev)
     nbytes = lib().ramp_group_by_small_workspace_bytes(E, int(K))
     ws = _lib.workspace(nbytes, dev, "graph")
     check(lib().ramp_group_by_small(ptr(a), ptr(b), int(mul), int(sub), int(K), E, ptr(g.order), ptr(g.gid),

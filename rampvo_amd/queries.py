@@ -1,0 +1,413 @@
+"""What a caller may ask a tracker between two frames (``Ramp_vo`` inherits ``TrackerQueries``): live poses, the trajectory
+at the frames' and at any time stamps, compensated events, the inverse-depth map, the window's uncertainty and the map.  The
+tracker keeps the state (``_traj_extra``, ``_traj_times``, ``_traj_status``, ``_pose_ring``).  ``StateStream`` is the one place
+that knows on which stream the state is read and how results cross, ``_check_status`` the one that reads status words."""
+import contextlib
+
+import numpy as np
+import torch
+
+from . import _lib, ops, track_dev
+
+
+class StateStream:
+    """``with tracker._state_stream(inputs) as sc:`` -- the body runs under ``torch.no_grad()`` on the stream the tracker's
+    state lives on: the tracker's own while work of an ``inputs_ready = "stream"`` frame is queued there, else the caller's.
+    ``sc.resident`` / ``sc.dv``: whether the steady state is device resident, and its DeviceTrack.  ``inputs``: tensors made on
+    the caller's stream that the body reads -- the state stream is ordered behind the caller's first.  The body names what it
+    hands out with ``sc.leaves(...)``; on exit the caller's stream waits for the state stream once and every tensor named is
+    recorded on it.  Where the two streams are one, entry and exit order nothing."""
+
+    def __init__(self, tracker, inputs=()):
+        self.dv, self._own, self._cur = tracker._dev, tracker._main_used, torch.cuda.current_stream(tracker.device)
+        self.resident = self.dv is not None and self.dv.active
+        self._st = tracker._main_stream if self._own else self._cur
+        self._inputs, self._leaving, self._ctx = inputs, [], contextlib.ExitStack()
+
+    def __enter__(self):
+        self._ctx.enter_context(torch.no_grad())
+        if self._own and self._inputs:
+            self._order(self._st, self._cur, self._inputs)
+        self._ctx.enter_context(torch.cuda.stream(self._st))
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self._ctx.close()
+        if self._own and exc_type is None:
+            self._order(self._cur, self._st, self._leaving)
+
+    @staticmethod
+    def _order(behind, ahead, tensors):
+        """stream ``behind`` waits for what ``ahead`` holds now; ``tensors``, allocated on ``ahead``, are used on ``behind``"""
+        ev = torch.cuda.Event()
+        ev.record(ahead)
+        behind.wait_event(ev)
+        for x in tensors:
+            x.record_stream(behind)
+
+    def leaves(self, *things):
+        """tensors, tuples of tensors or dicts of them that cross to the caller's stream; anything else is ignored"""
+        for x in things if self._own else ():
+            if isinstance(x, torch.Tensor):
+                self._leaving.append(x)
+            elif isinstance(x, (dict, tuple, list)):
+                self.leaves(*(x.values() if isinstance(x, dict) else x))
+
+
+def _check_status(name, traj=None, interp=None, cam=None):
+    """The closing check of a query's numpy form -- its one wait.  Each argument is a device status tensor or None (not part
+    of this query): ``traj`` trajectory()'s word, ``interp`` the words of ops.se3_interp or ops.event_warp (bit 0 of word 0:
+    the frames' time stamps), ``cam`` those of ops.invdepth_map (bit 0 of word 0: the camera pose).  Word 0 of each goes to
+    the host in one copy; raises in this order: unresolved delta chain, bad time stamps, camera pose."""
+    given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam)) if s is not None]
+    if not given:
+        return
+    first = given[0][1] if len(given) == 1 else torch.cat([s for _, s in given])
+    word = dict(zip((k for k, _ in given), first.cpu().tolist()))          # (the one wait)
+    if word.get("traj", 0) & track_dev.TRAJ_UNRESOLVED:
+        raise RuntimeError(name + ": a frame is neither a keyframe nor reachable through the delta chain")
+    if word.get("interp", 0) & 1:
+        raise RuntimeError(name + ": the frames' time stamps decrease or are not finite")
+    if word.get("cam", 0) & 1:
+        raise RuntimeError(name + ": the camera pose at t_ref is not finite")
+
+
+def _dof_sigma0(s):
+    """(dof, sigma0_sq) of ops.ba_covariance_stats' dict: ``dof = 2 n_valid - 6 N - Mu``, ``sigma0_sq = chi2 / max(dof, 1)``"""
+    dof = 2 * s["n_valid"] - 6 * s["N"] - s["Mu"]
+    return dof, s["chi2"] / max(dof, 1)
+
+
+class TrackerQueries:
+    """the query surface of ``Ramp_vo`` (a mixin: it reads the tracker's buffers, streams and host mirror as they are)"""
+
+    _NUMPY = {torch.float32: np.float32, torch.float64: np.float64, torch.int8: np.int8}
+
+    def _state_stream(self, inputs=()):
+        return StateStream(self, inputs)
+
+    def _as_device(self, a, dtype):
+        """tensor -> device tensor of ``dtype``; array-like -> converted on the host, flattened and uploaded"""
+        if isinstance(a, torch.Tensor):
+            return a.to(device=self.device, dtype=dtype)
+        return self._upload(np.asarray(a, dtype=self._NUMPY[dtype]).reshape(-1))
+
+    # ---------------------------------------------------------------- live poses
+    def pose_stream(self, capacity=256):
+        """switch pose publishing on: from the next accepted frame on, every frame -- device resident or host driven --
+        enqueues ONE extra one-wave launch behind its own work that writes a 128-byte record (frame, time stamp, the newest
+        frame's pose and its inverse, sizes, the keyframe test's outcome: track_dev.PoseRecord) into a ring of `capacity`
+        records in pinned host memory.  latest_pose() / poses_since() read the ring with plain loads: no hand-back, no
+        synchronisation, no HIP call.  A frame rejected by its mask publishes nothing.  Returns the ring."""
+        if self._pose_ring is not None:
+            if self._pose_ring.capacity == int(capacity):
+                return self._pose_ring
+            self._pose_rings_retired.append(self._pose_ring)
+        with torch.cuda.device(self.device):
+            self._pose_ring = track_dev.PoseRing(capacity, first=self.counter)
+        return self._pose_ring
+
+    def latest_pose(self):
+        """the newest complete record (track_dev.PoseRecord) or None -- never waits: what the GPU has finished, which may
+        be a few frames behind the last call"""
+        return self._pose_ring.latest() if self._pose_ring is not None else None
+
+    def poses_since(self, frame):
+        """(the complete records of frames above `frame`, in order; how many of those were overwritten before this read --
+        the ring holds the last `capacity` frames)"""
+        return self._pose_ring.since(frame) if self._pose_ring is not None else ([], 0)
+
+    def _publish(self, tstamp, counter, dv=None, n=None, dropped=False, t1=-1, t0=-1):
+        """(behind a frame's work) the record of frame `counter`; dv: the frame ran device resident -- everything is read on
+        the device; else n = the keyframe count the frame's update() saw (default: the current one)"""
+        ring = self._pose_ring
+        if dv is not None:
+            ring.publish(dv.t, counter, tstamp)
+        else:
+            ring.publish(None, counter, tstamp, poses=self.poses_, tstamps=self.tstamps_, n_rows=self.N,
+                         n=self._n if n is None else n, row=max(self._n - 1, 0), E=len(self._hii),
+                         status=self._ba_flags & 3, dropped=dropped, t1=t1, t0=t0)
+
+    def trajectory(self, as_tensor=False):
+        """what terminate() would return now -- (inverse poses [T,7], tstamps) -- as ONE launch (csrc/publish.hip::
+        traj_resolve_kernel) over the keyframe rows and the delta log where they are: a device-resident state stays device
+        resident (no settle(), the next frame is still one C call), a host-driven one works the same.  as_tensor=True:
+        the poses as a device tensor, ordered on the current stream, nothing synchronised (its status word, bit 1 = a
+        frame that neither is a keyframe nor has a delta entry, is left in ``_traj_status`` unread); otherwise numpy, which
+        waits for that one launch.  Does not set ``traj``."""
+        T, dev = int(self.counter), self.device
+        tst = np.array(self.tlist, dtype=float)
+        with self._state_stream() as sc:
+            dv, resident = sc.dv, sc.resident
+            key, extra = self._traj_extra
+            ne = len(self._delta)
+            if key != (id(self._delta), ne):
+                head = np.zeros((max(ne, 1), track_dev.LOG_WORDS), np.int32)
+                head[:ne, 0] = list(self._delta.keys())
+                head[:ne, 1] = [v[0] for v in self._delta.values()]
+                extra = self._upload(head).view(torch.float32)
+                if ne:
+                    extra[:ne, 2:9] = torch.stack([v[1].data.reshape(7) for v in self._delta.values()]).to(torch.float32)
+                self._traj_extra = ((id(self._delta), ne), extra)
+            out = torch.empty((T, 7), dtype=torch.float32, device=dev)
+            ws = torch.empty(3 * max(T, 1), dtype=torch.int32, device=dev)
+            status = torch.zeros(1, dtype=torch.int32, device=dev)
+            _lib.check(_lib.lib().ramp_trajectory_resolve(
+                _lib.ptr(self.poses_), _lib.ptr(self.tstamps_), self.N if resident else self._n,
+                _lib.ptr(dv.dyn) if resident else None, _lib.ptr(dv.dlog) if resident else None,
+                dv.log_cap if resident else 0, _lib.ptr(extra), ne, T, _lib.ptr(out), _lib.ptr(ws), _lib.ptr(status),
+                _lib.stream()), "ramp_trajectory_resolve")
+            sc.leaves(out, ws, status, extra)
+        self._traj_status = status
+        if as_tensor:
+            return out, tst
+        poses = out.cpu().numpy()
+        _check_status("trajectory()", traj=status)
+        return poses, tst
+
+    def _frame_times_dev(self):
+        """the frames' time stamps on the device (float64), uploaded once per new frame count"""
+        key, tdev = self._traj_times
+        now = (id(self.tlist), len(self.tlist), self.tlist[-1] if self.tlist else None)
+        if key != now:
+            tdev = self._upload(np.asarray(self.tlist, dtype=np.float64).reshape(-1))
+            self._traj_times = (now, tdev)
+        return tdev
+
+    def poses_at(self, times, extrapolate=False, twist=False, as_tensor=False):
+        """The trajectory at ANY time stamps: ``trajectory(as_tensor=True)`` and, behind it on the same stream, the SE(3)
+        geodesic between the frames' poses (ops.se3_interp: ``X(t) = Exp(alpha Log(X[s+1] X[s]^-1)) X[s]`` on the segment
+        [tlist[s], tlist[s+1]] that holds t) -- one pose per event, per IMU sample, per row of a fixed-rate file.  Same
+        convention as ``trajectory()``: inverse poses (interpolating the inverses gives the inverse of the interpolated
+        pose).  ``times``: array or tensor, in the unit of the time stamps the frames were fed with; outside their range
+        the end pose is held, or with ``extrapolate`` the end segment's motion is continued.  ``twist=True`` adds the
+        segment's constant left twist [Q,6] per query.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call); the frames' time
+        stamps are uploaded once per new frame count.  ``as_tensor=True``: device tensors ``(poses [Q,7], twist or None,
+        status int32 [4])``, ordered on the current stream, nothing synchronised (status: ops.se3_interp; trajectory()'s own
+        word stays in ``_traj_status``).  Otherwise numpy ``(poses, twist or None)``, which waits for that one result and
+        raises when the frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
+        knots, _ = self.trajectory(as_tensor=True)
+        with torch.no_grad():
+            poses, tw, status = ops.se3_interp(knots, self._frame_times_dev(), self._as_device(times, torch.float64),
+                                               extrapolate=extrapolate, twist=twist)
+        if as_tensor:
+            return poses, tw, status
+        _check_status("poses_at()", traj=self._traj_status, interp=status)
+        return poses.cpu().numpy(), (tw.cpu().numpy() if twist else None)
+
+    def compensate_events(self, x, y, t, p, t_ref=None, invdepth=None, num_bins=0, extrapolate=False, want_xy=False,
+                          want_iwe=True, stack=None, height=None, width=None, as_tensor=False, radius=None,
+                          weights="variance"):
+        """Motion compensation with the trajectory as it is now: every event (``x, y`` pixel coordinates of the images the
+        tracker is fed, ``t`` in the unit of the frames' time stamps, ``p`` polarity) is warped from the camera pose at its
+        own time stamp to the pose at ``t_ref`` and splat bilinearly into an image of warped events and / or a bin stack
+        (``ops.event_warp``, one pass over the events; the poses are those of ``poses_at``: ``trajectory(as_tensor=True)``
+        and the cached time stamps, never written per event).
+
+        ``t_ref=None``: the newest frame's time stamp.  ``invdepth=None``: the lower median inverse depth of the last three
+        frames' patches -- the value the next frame's patches start from -- computed into a device word the host never
+        reads; otherwise a float, a one-element device tensor or a [height, width] map; ``"map"``: the map
+        ``invdepth_map(t_ref, radius, weights)`` renders from the window's patches at the reference pose, so that every event is
+        warped with the depth the tracker has estimated near its pixel (``radius``, ``weights`` are read in this mode only).
+        Intrinsics: row 0 of the tracker's own times the patch stride, i.e. those of the images it was fed.  ``height, width``
+        default to the tracker's.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
+        the dict of device tensors of ``ops.event_warp`` (``status``, ``xy``, ``iwe``, ``stack`` as requested), ordered on
+        the current stream, nothing synchronised.  Otherwise numpy arrays, which waits for that result and raises when the
+        frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
+        if not self.tlist:
+            raise RuntimeError("compensate_events(): no frame has been tracked yet")
+        if isinstance(invdepth, str):
+            if invdepth != "map":
+                raise RuntimeError("compensate_events(): invdepth is None, a number, a tensor or 'map'")
+            invdepth = self.invdepth_map(t_ref=t_ref, radius=radius, weights=weights, height=height, width=width,
+                                         as_tensor=True)["invdepth"]
+        knots, _ = self.trajectory(as_tensor=True)
+        tdev = self._frame_times_dev()
+        with self._state_stream() as sc:                      # reads of the state, on the stream it lives on
+            K = self.intrinsics_[0] * float(self.RES)
+            if invdepth is None:
+                invdepth = self._depth_median_word(sc.resident)
+            sc.leaves(K, invdepth)
+        with torch.no_grad():
+            out = ops.event_warp(self._as_device(x, torch.float32), self._as_device(y, torch.float32),
+                                 self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev,
+                                 self.tlist[-1] if t_ref is None else float(t_ref), K, invdepth,
+                                 self.ht if height is None else height, self.wd if width is None else width,
+                                 num_bins=num_bins, extrapolate=extrapolate, want_xy=want_xy, want_iwe=want_iwe, stack=stack)
+        if as_tensor:
+            return out
+        _check_status("compensate_events()", traj=self._traj_status, interp=out["status"])
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def _depth_median_word(self, resident):
+        """(on the stream the state lives on) the lower median inverse depth of the last three frames' patches as a device
+        word the host never reads; 0 without a frame"""
+        word = torch.zeros(1, dtype=torch.float32, device=self.device)
+        if resident:
+            ops.depth_median_rows(self.patches_, self._dev.dyn[track_dev.DYN_NROW:], 3, word)
+        elif self._n > 0:
+            ops.depth_median(self.patches_, self._n, min(3, self._n), word)
+        return word
+
+    def invdepth_map(self, t_ref=None, radius=None, weights="variance", max_rel_depth_sigma=None, min_obs=2,
+                     prior_rel_sigma=1.0, height=None, width=None, as_tensor=False):
+        """A dense inverse-depth map [height, width] of the scene as the tracker has estimated it, at the camera pose of time
+        ``t_ref`` (default: the newest frame): the window's patches are projected into that pose (one row of ``poses_at``)
+        and regressed with a biweight kernel of support ``radius`` image pixels (``ops.invdepth_map``).  The map is what
+        ``compensate_events(invdepth=...)`` and ``ops.event_warp`` sample at an event's pixel.
+
+        ``weights="variance"``: the patches ``map(max_rel_depth_sigma=..., min_obs=...)`` selects (the same query: one C call
+        for the covariance, one for the selection), each weighted by the inverse of its marginal depth variance, against a
+        prior of RELATIVE sigma ``prior_rel_sigma`` -- weight ``prior_rel_sigma**-2 / prior**2``, formed on the device.
+        ``weights="uniform"``: no covariance call; the patches of the newest ``REMOVAL_WINDOW`` frames with weight 1 against a
+        prior of weight ``prior_rel_sigma**-2``.  The prior is the median inverse depth ``compensate_events`` uses by default,
+        so a pixel no patch reaches gets the median and a pixel between patches is drawn to it as the kernel weight falls.
+        ``radius=None``: ``max(height, width) / 10`` -- a default nobody has tuned.  ``height, width`` default to the
+        tracker's.
+
+        A device-resident state stays device resident (no settle(), nothing of the state written; the row count, the selection
+        and the median are read on the device).  ``as_tensor=True``: a dict of device tensors ``invdepth``, ``weight`` (the
+        summed kernel weight per pixel), ``status`` (ops.invdepth_map_status) and ``pose_status`` (ops.se3_interp), ordered on
+        the current stream, nothing synchronised.  Otherwise numpy arrays, which waits for the result and raises when the
+        pose at ``t_ref`` is not finite and on the conditions ``poses_at`` raises on."""
+        if not self.tlist:
+            raise RuntimeError("invdepth_map(): no frame has been tracked yet")
+        if weights not in ("variance", "uniform"):
+            raise RuntimeError("invdepth_map(): weights is 'variance' or 'uniform'")
+        if not prior_rel_sigma > 0:
+            raise RuntimeError("invdepth_map(): prior_rel_sigma is positive")
+        H, W = self.ht if height is None else int(height), self.wd if width is None else int(width)
+        R = max(H, W) / 10.0 if radius is None else float(radius)
+        pw = float(prior_rel_sigma) ** -2
+        cams, _, pose_status = self.poses_at([self.tlist[-1] if t_ref is None else float(t_ref)], as_tensor=True)
+
+        def render(resident, index=None, count=None, dvar=None):
+            dyn = self._dev.dyn[track_dev.DYN_NROW:] if resident else None
+            prior = self._depth_median_word(resident)
+            if dvar is not None:
+                r = ops.invdepth_map(self.poses_, self.patches_, self.intrinsics_[0], cams[0], H, W, R, scale=self.RES,
+                                     index=index, count=count, conf=dvar, conf_is_variance=True, prior=prior, prior_weight=pw,
+                                     prior_relative=True, dyn_rows=dyn, per_row=self.M)
+            else:
+                n = self.N if resident else self._n
+                r = ops.invdepth_map(self.poses_[:n], self.patches_[:n], self.intrinsics_[0], cams[0], H, W, R, scale=self.RES,
+                                     prior=prior, prior_weight=pw, dyn_rows=dyn, per_row=self.M,
+                                     last_rows=int(self.cfg.REMOVAL_WINDOW))
+            return r["invdepth"], r["weight"], r["status"]
+
+        # inputs=(cams,): the pose was made on the caller's stream and is read on the one the state lives on
+        if weights == "variance":
+            def then(resident, out):
+                index, count = self._select(resident, out, None, max_rel_depth_sigma, min_obs)
+                return render(resident, index, count, out[1])
+
+            inv, wgt, status = self._window_query("invdepth_map()", with_map=True, then=then, inputs=(cams,))[-3:]
+        else:
+            with self._state_stream(inputs=(cams,)) as sc:
+                if not sc.resident:
+                    self._join_main()
+                inv, wgt, status = render(sc.resident)
+                sc.leaves(inv, wgt, status)
+        out = dict(invdepth=inv, weight=wgt, status=status, pose_status=pose_status)
+        if as_tensor:
+            return out
+        _check_status("invdepth_map()", traj=self._traj_status, interp=pose_status, cam=status)
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    # --------------------------------------------------------------- uncertainty
+    def _window_query(self, name, with_map=False, then=None, inputs=()):
+        """what uncertainty() and map() share: the one C call on the stream the state lives on, ordered in front of the
+        current stream.  Returns the call's raw device tensors (cov, depth_var, stats words[, point, point_cov,
+        pose_depth_cov, n_obs]) followed by what ``then(resident, tensors)`` enqueued behind it on the same stream."""
+        dv = self._dev
+        last_t, last_w = getattr(self, "last_target", None), getattr(self, "last_weight", None)
+        if (last_t is None or last_w is None) and not (dv is not None and dv.active and dv._frames):
+            raise RuntimeError(name + ": no update has run yet -- there are no targets and weights to form the "
+                               "system from (track at least until the first update())")
+        W = int(self.cfg.OPTIMIZATION_WINDOW)
+        with self._state_stream(inputs) as sc:
+            if sc.resident:
+                if not dv._frames:                            # (handed over, no device step yet: the last update ran host-driven)
+                    k = last_t.shape[1]
+                    dv.target[:k].copy_(last_t[0])
+                    dv.weight[:k].copy_(last_w[0])
+                out = dv.map() if with_map else dv.uncertainty()
+            else:
+                self._join_main()
+                n = self._n
+                rows = self._net_map_dev if self._net_map_dev is not None else self._upload(self._net_rows())
+                if rows.numel() != self._dii.numel() or rows.numel() == 0:
+                    raise RuntimeError(name + ": the factor graph has changed since the last update()")
+                t0 = max(n - W, 1) if self.is_initialized else 1
+                op = ops.ba_map_covariance if with_map else ops.ba_covariance
+                out = op(self.poses_, self.patches_, self.intrinsics_, last_t[0][rows], last_w[0][rows], self.lmbda,
+                         self._dii, self._djj, self._dkk, t0, n)
+            if then is not None:
+                out = tuple(out) + tuple(then(sc.resident, out))
+            sc.leaves(out)
+        return out
+
+    def _select(self, resident, out, max_sigma, max_rel_depth_sigma, min_obs):
+        """(on the state's stream) ops.map_select over a with_map window query's tensors; resident: the count is read on the device"""
+        _, dvar, _, _, pcov, _, nobs = out
+        rows = dict(dyn_rows=self._dev.dyn[track_dev.DYN_NROW:], per_row=self.M) if resident else dict(n=self._n * self.M)
+        return ops.map_select(pcov, dvar, self.patches_, nobs, max_sigma, max_rel_depth_sigma, min_obs, **rows)
+
+    def uncertainty(self):
+        """How good the window's poses and depths are right now: the marginal covariance of the free poses and the marginal
+        variance of every patch depth (``fastba.covariance``: the damped system the step is solved with), from the LAST
+        update's targets and confidence weights at the poses and patches as they are now, over the factors that survived
+        the keyframe test -- the state between two frames.  Returns a dict:
+
+        ``frames`` (t0 .. t1-1: the keyframe rows the blocks of ``cov`` belong to), ``cov`` [6N, 6N], ``pose_cov`` [N, 6, 6]
+        (its diagonal blocks; translation 3, rotation 3, left perturbation of the world-to-camera pose), ``depth_var`` [n, M]
+        (inf for a patch without a factor), ``chi2``, ``n_valid``, ``dof = 2 n_valid - 6N - Mu``, ``sigma0_sq = chi2 /
+        max(dof, 1)``.  Tensors are on the device.
+
+        A device-resident state stays device resident: ONE C call (csrc/track.hip::ramp_track_uncertainty) that reads the
+        sizes on the device, no settle(), no hand-back; the host synchronises only to read the result.  Nothing of the
+        tracker's state is written, so a queried tracker tracks the same bits as one that is never asked."""
+        cov_c, dvar_c, raw = self._window_query("uncertainty()")
+        s = ops.ba_covariance_stats(raw)                      # (the one synchronisation: 32 bytes)
+        N, t0 = s["N"], s["t0"]
+        n = t0 + N
+        cov = cov_c[:6 * N, :6 * N]
+        pose_cov = torch.stack([cov[6 * a:6 * a + 6, 6 * a:6 * a + 6] for a in range(N)]) if N else cov.new_zeros((0, 6, 6))
+        dof, sigma0_sq = _dof_sigma0(s)
+        return dict(frames=list(range(t0, n)), cov=cov, pose_cov=pose_cov, depth_var=dvar_c[:n * self.M].view(n, self.M),
+                    chi2=s["chi2"], n_valid=s["n_valid"], dof=dof, sigma0_sq=sigma0_sq, failed=s["failed"])
+
+    def map(self, max_sigma=None, max_rel_depth_sigma=None, min_obs=2):
+        """The map with its uncertainty, filtered: the window's patch centres as world points, each with the 3 x 3 covariance
+        ``fastba.map_covariance`` propagates from the system behind ``uncertainty()`` (same factors, same state between two
+        frames), compacted on the device to the K points that pass
+
+        ``sqrt(trace(point_cov)) <= max_sigma`` (world units), ``sqrt(depth_var) / d <= max_rel_depth_sigma`` and
+        ``n_obs >= min_obs`` (valid factors of the patch); ``None`` (or ``min_obs=0``) switches a criterion off.  A point
+        whose covariance is not finite never passes.
+
+        Returns a dict of device tensors in patch order: ``index`` [K] (flat patch id ``frame * M + m``), ``frame`` [K],
+        ``points`` [K, 3], ``point_cov`` [K, 3, 3], ``colors`` [K, 3] uint8, ``depth_sigma_rel`` [K], ``n_obs`` [K]; and
+        ``n_total`` (patches with a factor, before the selection), ``chi2``, ``dof``, ``sigma0_sq``, ``failed`` as
+        ``uncertainty()``.
+
+        As ``uncertainty()``, a device-resident state stays resident and nothing of the tracker's state is written: one C
+        call for the covariance and the map (csrc/track.hip::ramp_track_map), one for the selection (ramp_map_select); the
+        host waits only for the stats words and the count."""
+        M = self.M
+        select = lambda resident, out: self._select(resident, out, max_sigma, max_rel_depth_sigma, min_obs)
+        _, dvar, raw, point, pcov, _, nobs, index, count = self._window_query("map()", with_map=True, then=select)
+        s = ops.ba_covariance_stats(raw)                      # (the two synchronisations: 32 bytes and 4 bytes)
+        K = int(count.cpu())
+        idx = index[:K].long()
+        P = self.patches_.shape[-1]
+        d = self.patches_.view(-1, 3, P, P)[:, 2, 1, 1]
+        sym = torch.tensor([0, 1, 2, 1, 3, 4, 2, 4, 5], device=idx.device)
+        dof, sigma0_sq = _dof_sigma0(s)
+        return dict(index=idx, frame=idx // M, points=point[idx], point_cov=pcov[idx][:, sym].view(K, 3, 3),
+                    colors=self.colors_.view(-1, 3)[idx], depth_sigma_rel=dvar[idx].sqrt() / d[idx], n_obs=nobs[idx],
+                    n_total=s["Mu"], chi2=s["chi2"], dof=dof, sigma0_sq=sigma0_sq, failed=s["failed"])

@@ -15,18 +15,18 @@ behind the tracker.  ONE process, rounds INTERLEAVED over the legs, so that ever
     python tools/depth_map_cost.py [--part kernel|tracker|both] [--weights variance|uniform] [--repeats R] [--json out.json]
 """
 import argparse
-import gc
 import json
 import os
 import statistics
 import sys
-import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+import tracker_legs as tl
 
 TILE_W, TILE_H = 32, 16               # csrc/depthmap.hip: DM_TILE_W, DM_TILE_H (the pair count below models its cull)
 
@@ -121,75 +121,36 @@ def kernel_part(args, dev):
 
 
 def tracker_part(args, dev):
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import SyntheticStream, make_network
-    torch.manual_seed(1234)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=args.patches, MIXED_PRECISION=True), make_network("SingleScale", device=dev),
-                   {"event_bias": True}, ht=args.height, wd=args.width, device=dev)
-    slam.inputs_ready = True
-    total = args.prime + args.clock_warm + args.tracker_repeats * 4 * (args.steps + args.tracker_warmup)
-    stream = SyntheticStream(args.height, args.width, total + 1, seed=1234, device=dev)
-    pos = [0]
-    frames = [stream.frame(t) for t in range(total)]
-    n_ev = args.tracker_events
+    steps, warmup, repeats = args.steps, args.tracker_warmup, args.tracker_repeats
+    t = tl.TrackerLegs(args.patches, args.height, args.width,
+                       tl.frames_needed(args.prime, args.clock_warm, repeats, [steps] * 4, warmup), dev)
+    slam, n_ev = t.slam, args.tracker_events
     g = torch.Generator(device="cpu").manual_seed(9)
     ex = (torch.rand(n_ev, generator=g) * (args.width - 1)).to(dev)
     ey = (torch.rand(n_ev, generator=g) * (args.height - 1)).to(dev)
     ep = (torch.randint(0, 2, (n_ev,), generator=g) * 2 - 1).to(torch.int8).to(dev)
     frac = torch.sort(torch.rand(n_ev, generator=g, dtype=torch.float64)).values.to(dev)      # time-sorted, in the last two frames
-    torch.cuda.synchronize()
-
-    def step():
-        im, ev, K, mask = frames[pos[0]]
-        slam(pos[0], input_tensor=(ev, im, mask), intrinsics=K)
-        pos[0] += 1
-
-    for _ in range(args.prime):
-        step()
-    assert slam.is_initialized and slam._dev is not None and slam._dev.active, "the tracker is not device resident"
-    gc.collect()
-    gc.freeze()
-    for _ in range(args.clock_warm):
-        step()
-    torch.cuda.synchronize()
+    t.prime(args.prime, args.clock_warm)
     what = {"a": "no query", "b": "invdepth_map(weights=%r) per frame" % args.weights,
             "c": "compensate_events(%d events), median" % n_ev, "d": "compensate_events(%d events), invdepth='map'" % n_ev}
-    rates, last = {k: [] for k in what}, {}
+    last = {}
 
-    def leg(name, n):
-        for _ in range(args.tracker_warmup):
-            step()
-        torch.cuda.synchronize()
-        settles = slam.stats["settles"]
-        tic = time.perf_counter()
-        for _ in range(n):
-            step()
-            if name == "b":
-                last["map"] = slam.invdepth_map(weights=args.weights, as_tensor=True)
-            elif name == "c":
-                last["median"] = slam.compensate_events(ex, ey, float(pos[0] - 3) + 2.0 * frac, ep, as_tensor=True)
-            elif name == "d":
-                last["warp"] = slam.compensate_events(ex, ey, float(pos[0] - 3) + 2.0 * frac, ep, invdepth="map",
-                                                      weights=args.weights, as_tensor=True)
-        torch.cuda.synchronize()
-        rates[name].append(n / (time.perf_counter() - tic))
-        assert slam.stats["settles"] == settles and slam._dev.active, "leg %s was handed back" % name
+    def b():
+        last["map"] = slam.invdepth_map(weights=args.weights, as_tensor=True)
 
-    for _ in range(args.tracker_repeats):
-        for name in what:
-            leg(name, args.steps)
-    out = {"workload": "SingleScale %dx%d, %d patches, fp16 features, inputs_ready=True" % (args.width, args.height, args.patches),
-           "weights": args.weights, "events_per_frame": n_ev, "steps": args.steps, "repeats": args.tracker_repeats,
-           "frames_at_end": pos[0], "legs": {}}
-    for name, v in rates.items():
-        out["legs"][name] = {"what": what[name], "kf_per_s_median": round(statistics.median(v), 1), "min": round(min(v), 1),
-                             "max": round(max(v), 1), "rounds": [round(x, 1) for x in v]}
-        print("leg %s  %-52s %8.1f kf/s  (min %.1f, max %.1f; rounds %s)"
-              % (name, what[name], statistics.median(v), min(v), max(v), " ".join("%.1f" % x for x in v)))
-    med = lambda k: out["legs"][k]["kf_per_s_median"]
-    out["b_over_a"], out["d_over_c"] = round(med("b") / med("a"), 4), round(med("d") / med("c"), 4)
-    out["a_spread"] = round((out["legs"]["a"]["max"] - out["legs"]["a"]["min"]) / med("a"), 4)
+    def c():
+        last["median"] = slam.compensate_events(ex, ey, float(t.pos - 3) + 2.0 * frac, ep, as_tensor=True)
+
+    def d():
+        last["warp"] = slam.compensate_events(ex, ey, float(t.pos - 3) + 2.0 * frac, ep, invdepth="map", weights=args.weights,
+                                              as_tensor=True)
+
+    rates, _ = t.run_legs({"a": None, "b": b, "c": c, "d": d}, steps, warmup, repeats)
+    out = {"workload": t.workload, "weights": args.weights, "events_per_frame": n_ev, "steps": steps, "repeats": repeats,
+           "frames_at_end": t.pos}
+    out["legs"] = tl.summary(rates, what)
+    out["b_over_a"], out["d_over_c"] = tl.ratio(out["legs"], "b", "a"), tl.ratio(out["legs"], "d", "c")
+    out["a_spread"] = tl.spread(out["legs"]["a"])
     out["last_map_status"] = last["map"]["status"].cpu().tolist()
     out["last_warp_status"] = {"median": last["median"]["status"].cpu().tolist(), "map": last["warp"]["status"].cpu().tolist()}
     print("b / a = %.4f, d / c = %.4f   (a's own spread, (max - min) / median: %.4f); last map status %s"

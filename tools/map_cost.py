@@ -15,18 +15,17 @@ tracker must stay device resident throughout (no hand-back in any leg).
     python tools/map_cost.py [--steps 200] [--repeats 5] [--json out.json]
 """
 import argparse
-import gc
 import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+import tracker_legs as tl
 
 
 def main():
@@ -41,70 +40,24 @@ def main():
     ap.add_argument("--patches", type=int, default=96)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import SyntheticStream, make_network
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    torch.manual_seed(1234)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=args.patches, MIXED_PRECISION=True), make_network("SingleScale", device=dev),
-                   {"event_bias": True}, ht=args.height, wd=args.width, device=dev)
-    slam.inputs_ready = True
-    total = args.prime + args.clock_warm + args.repeats * 3 * (args.steps + args.warmup)
-    stream = SyntheticStream(args.height, args.width, total + 1, seed=1234, device=dev)
-    pos = [0]
-    frames = [stream.frame(t) for t in range(total)]
-    torch.cuda.synchronize()
-
-    def step():
-        im, ev, K, mask = frames[pos[0]]
-        slam(pos[0], input_tensor=(ev, im, mask), intrinsics=K)
-        pos[0] += 1
-
-    for _ in range(args.prime):
-        step()
-    assert slam.is_initialized and slam._dev is not None and slam._dev.active, "the tracker is not device resident"
-    gc.collect()
-    gc.freeze()
-    for _ in range(args.clock_warm):
-        step()
-    torch.cuda.synchronize()
-    rates = {"a": [], "b": [], "c": []}
+    t = tl.TrackerLegs(args.patches, args.height, args.width,
+                       tl.frames_needed(args.prime, args.clock_warm, args.repeats, [args.steps] * 3, args.warmup), dev)
+    t.prime(args.prime, args.clock_warm)
     last = [None, None]
 
-    def leg(name, n):
-        for _ in range(args.warmup):
-            step()
-        torch.cuda.synchronize()
-        settles = slam.stats["settles"]
-        tic = time.perf_counter()
-        for _ in range(n):
-            step()
-            if name == "b":
-                last[0] = slam.uncertainty()
-            elif name == "c":
-                last[1] = slam.map()
-        torch.cuda.synchronize()
-        rates[name].append(n / (time.perf_counter() - tic))
-        assert slam.stats["settles"] == settles and slam._dev.active, "leg %s was handed back" % name
+    def b():
+        last[0] = t.slam.uncertainty()
 
-    for _ in range(args.repeats):
-        leg("a", args.steps)
-        leg("b", args.steps)
-        leg("c", args.steps)
-    out = {"workload": "SingleScale %dx%d, %d patches, fp16 features, inputs_ready=True" % (args.width, args.height, args.patches),
-           "steps": args.steps, "repeats": args.repeats, "legs": {}}
-    for name, what in (("a", "no query"), ("b", "uncertainty() per call"), ("c", "map() per call")):
-        v = rates[name]
-        out["legs"][name] = {"what": what, "kf_per_s_median": round(statistics.median(v), 1), "min": round(min(v), 1),
-                             "max": round(max(v), 1), "rounds": [round(x, 1) for x in v]}
-        print("leg %s  %-28s %8.1f kf/s  (min %.1f, max %.1f; rounds %s)"
-              % (name, what, statistics.median(v), min(v), max(v), " ".join("%.1f" % x for x in v)))
-    a, b, c = out["legs"]["a"], out["legs"]["b"], out["legs"]["c"]
-    out["b_over_a"] = round(b["kf_per_s_median"] / a["kf_per_s_median"], 4)
-    out["c_over_a"] = round(c["kf_per_s_median"] / a["kf_per_s_median"], 4)
-    out["c_over_b"] = round(c["kf_per_s_median"] / b["kf_per_s_median"], 4)
-    out["a_spread"] = round((a["max"] - a["min"]) / a["kf_per_s_median"], 4)
+    def c():
+        last[1] = t.slam.map()
+
+    rates, _ = t.run_legs({"a": None, "b": b, "c": c}, args.steps, args.warmup, args.repeats)
+    out = {"workload": t.workload, "steps": args.steps, "repeats": args.repeats}
+    out["legs"] = tl.summary(rates, {"a": "no query", "b": "uncertainty() per call", "c": "map() per call"})
+    out["b_over_a"], out["c_over_a"] = tl.ratio(out["legs"], "b", "a"), tl.ratio(out["legs"], "c", "a")
+    out["c_over_b"], out["a_spread"] = tl.ratio(out["legs"], "c", "b"), tl.spread(out["legs"]["a"])
     u = last[0]
     out["last_query"] = {"N": len(u["frames"]), "n_valid": u["n_valid"], "dof": u["dof"], "sigma0_sq": u["sigma0_sq"]}
     m = last[1]

@@ -15,19 +15,18 @@ Ramp_vo.poses_at behind every frame of the flagship workload.  ONE process, so t
     python tools/pose_query_cost.py [--part query|tracker|both] [--json out.json]
 """
 import argparse
-import ctypes
-import gc
 import json
 import os
 import statistics
 import sys
-import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+import tracker_legs as tl
 
 HBM_MEASURED, HBM_SPEC = 6.29e12, 8.0e12
 
@@ -123,64 +122,21 @@ def query_part(args, dev):
 
 
 def tracker_part(args, dev):
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import SyntheticStream, make_network
-    torch.manual_seed(1234)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=args.patches, MIXED_PRECISION=True), make_network("SingleScale", device=dev),
-                   {"event_bias": True}, ht=args.height, wd=args.width, device=dev)
-    slam.inputs_ready = True
-    total = args.prime + args.clock_warm + args.tracker_repeats * 2 * (args.steps + args.tracker_warmup)
-    stream = SyntheticStream(args.height, args.width, total + 1, seed=1234, device=dev)
-    pos = [0]
-    frames = [stream.frame(t) for t in range(total)]
+    steps, warmup, repeats = args.steps, args.tracker_warmup, args.tracker_repeats
+    t = tl.TrackerLegs(args.patches, args.height, args.width,
+                       tl.frames_needed(args.prime, args.clock_warm, repeats, [steps] * 2, warmup), dev)
     frac = torch.sort(torch.rand(args.tracker_queries, dtype=torch.float64, device=dev)).values
-    torch.cuda.synchronize()
+    t.prime(args.prime, args.clock_warm)
+    last = [None]
 
-    def step():
-        im, ev, K, mask = frames[pos[0]]
-        slam(pos[0], input_tensor=(ev, im, mask), intrinsics=K)
-        pos[0] += 1
+    def query():
+        last[0] = t.slam.poses_at(frac * float(t.pos - 1), as_tensor=True)
 
-    for _ in range(args.prime):
-        step()
-    assert slam.is_initialized and slam._dev is not None and slam._dev.active, "the tracker is not device resident"
-    gc.collect()
-    gc.freeze()
-    for _ in range(args.clock_warm):
-        step()
-    torch.cuda.synchronize()
-    rates, last = {"a": [], "b": []}, [None]
-
-    def leg(name, n):
-        for _ in range(args.tracker_warmup):
-            step()
-        torch.cuda.synchronize()
-        settles = slam.stats["settles"]
-        tic = time.perf_counter()
-        for _ in range(n):
-            step()
-            if name == "b":
-                last[0] = slam.poses_at(frac * float(pos[0] - 1), as_tensor=True)
-        torch.cuda.synchronize()
-        rates[name].append(n / (time.perf_counter() - tic))
-        assert slam.stats["settles"] == settles and slam._dev.active, "leg %s was handed back" % name
-
-    for _ in range(args.tracker_repeats):
-        leg("a", args.steps)
-        leg("b", args.steps)
-    out = {"workload": "SingleScale %dx%d, %d patches, fp16 features, inputs_ready=True" % (args.width, args.height, args.patches),
-           "queries_per_frame": args.tracker_queries, "steps": args.steps, "repeats": args.tracker_repeats, "frames_at_end": pos[0],
-           "legs": {}}
-    for name, what in (("a", "no query"), ("b", "poses_at(%d times) per call" % args.tracker_queries)):
-        v = rates[name]
-        out["legs"][name] = {"what": what, "kf_per_s_median": round(statistics.median(v), 1), "min": round(min(v), 1),
-                             "max": round(max(v), 1), "rounds": [round(x, 1) for x in v]}
-        print("leg %s  %-32s %8.1f kf/s  (min %.1f, max %.1f; rounds %s)"
-              % (name, what, statistics.median(v), min(v), max(v), " ".join("%.1f" % x for x in v)))
-    a, b = out["legs"]["a"], out["legs"]["b"]
-    out["b_over_a"] = round(b["kf_per_s_median"] / a["kf_per_s_median"], 4)
-    out["a_spread"] = round((a["max"] - a["min"]) / a["kf_per_s_median"], 4)
+    rates, _ = t.run_legs({"a": None, "b": query}, steps, warmup, repeats)
+    out = {"workload": t.workload, "queries_per_frame": args.tracker_queries, "steps": steps, "repeats": repeats,
+           "frames_at_end": t.pos}
+    out["legs"] = tl.summary(rates, {"a": "no query", "b": "poses_at(%d times) per call" % args.tracker_queries})
+    out["b_over_a"], out["a_spread"] = tl.ratio(out["legs"], "b", "a"), tl.spread(out["legs"]["a"])
     out["last_status"] = last[0][2].cpu().tolist()
     print("b / a = %.4f   (a's own spread, (max - min) / median: %.4f)" % (out["b_over_a"], out["a_spread"]))
     return out
