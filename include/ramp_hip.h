@@ -1132,6 +1132,60 @@ int ramp_invdepth_map(const float *poses, const float *patches, const float *int
                       int W, float *invdepth, float *weight, float *records, void *ws, size_t ws_bytes, int32_t *status,
                       void *stream);
 
+/* ---------------------------------------------------------------- event contrast and its gradient (csrc/contrast.hip)
+ *
+ * ramp_event_contrast: the variance of the image of warped events (contrast maximisation's objective) and its gradient with
+ * respect to a small correction theta = (v[3], w[3], lam) of the warp: translation 3, rotation 3, a log depth scale.
+ * Everything up to X' is ramp_event_warp's, statement for statement: segment search, alpha in float64, C(t),
+ * G = C(t_ref)^-1 C(t), the depth sampled at the event's own rounded pixel, P = ((x - cx) / fx, (y - cy) / fy, 1).  The
+ * arguments are ramp_event_warp's without the stack; RAMP_WARP_IDENTITY is not accepted.  The correction acts in the reference
+ * camera frame, to first order, by definition:
+ *     tau = float32(t - t_ref)            (the difference formed in float64; the unit of the time stamps)
+ *     ds  = d * expf(lam)
+ *     X1  = R_G P + t_G ds
+ *     X2  = X1 + tau * (v * ds + w x X1)
+ *     x'  = fx X2.x / X2.z + cx ,  y' = fy X2.y / X2.z + cy
+ *           invalid exactly as ramp_event_warp, with X2.z in the place of Z'
+ *   correction: device float [7], or NULL for zero (the correction is then not evaluated at all).  A correction of zeros and
+ *   NULL give the accumulators, the image and the status words of ramp_event_warp bit for bit.
+ *   I(u) = sum_k s_k b(u - x'_k) is the bilinear splat of ramp_event_warp (the same fixed point, neighbours outside the image
+ *   dropped); s_k = p_k, or 1 with RAMP_CONTRAST_UNSIGNED (the count plane).  With P_n = H W, mu = mean(I) and
+ *   f = (1 / P_n) sum_u (I(u) - mu)^2 (the population variance), per event over the in-image neighbours (jx, jy) in {0,1}^2:
+ *     df/dx'_k = (2 / P_n) s_k sum (I(ix + jx, iy + jy) - mu) * (jx ? +1 : -1) * wy[jy]
+ *     df/dy'_k = (2 / P_n) s_k sum (I(ix + jx, iy + jy) - mu) * (jy ? +1 : -1) * wx[jx]
+ *   (the mu term cancels only for events with all four neighbours inside, so it stays) and, for r any 3-vector:
+ *     dx'/dX2 = (fx / Z, 0, -fx X / Z^2)         dy'/dX2 = (0, fy / Z, -fy Y / Z^2)
+ *     dX2/dv  = tau ds I_3
+ *     dX2/dw . r = tau (r x X1)                  i.e. the matrix -tau [X1]_x
+ *     dX2/dlam = t_G ds + tau (v ds + w x (t_G ds))
+ *   The correction is linear, so these derivatives are exact at any theta.
+ *   Outputs:
+ *     iwe [2][H][W] fp32 (optional, NULL)   as ramp_event_warp: plane 0 the polarity-signed sum, plane 1 the count
+ *     sums  int64 [2]      the exact sums of the signed and of the count accumulators (units of 2^-24)
+ *     stats float64 [8]    [0] the variance f, [1] the mean mu, [2] sum_u I(u)^2, [3] P_n, the rest 0 -- of the signed image,
+ *                          or of the count image with RAMP_CONTRAST_UNSIGNED
+ *     grad  float64 [7] (optional, NULL)    df/dtheta in the order (v, w, lam)
+ *     status int32 [8]     ramp_event_warp's words; bit 1 of word 0: RAMP_CONTRAST_BAD_CORRECTION
+ *   Determinism: the accumulators and the two sums are integer sums, the squares are centred with mu before they are summed
+ *   over the pixels in a fixed order: stats, sums and iwe do not depend on the order of the events.  grad is a sum of doubles
+ *   in an order fixed by the arguments: it repeats its bits from call to call; another order of the events moves it by the
+ *   rounding of a float64 sum.  No floating-point atomics anywhere.
+ *   Failures, never a plausible number (RAMP_OK: outcomes of the data): RAMP_INTERP_BAD_TIMES, or a correction with an entry
+ *   that is not finite (RAMP_CONTRAST_BAD_CORRECTION), make stats[0 .. 2], grad and iwe NaN and sums 0; status [4] - [6] are
+ *   then zero.  An event that is not finite or rejected is counted and contributes nothing.  No contributing event: variance
+ *   0 and gradient 0, the true values.
+ *   ws: ramp_event_contrast_workspace_bytes(T, H, W) bytes, 16-byte aligned; sums, stats and grad 8-byte aligned.  Launches:
+ *   at most five kernels (four without grad) behind one hipMemsetAsync, all on `stream`, nothing synchronised.
+ *   N == 0: RAMP_OK, nothing is launched and nothing written.  N < 0, T < 1, H or W < 1, unknown flags, a t_ref that is not
+ *   finite, a NULL sums / stats / status: RAMP_EINVAL; a short workspace: RAMP_EWORKSPACE.                                */
+#define RAMP_CONTRAST_UNSIGNED 16
+#define RAMP_CONTRAST_BAD_CORRECTION 2 /* status[0] bit 1 */
+size_t ramp_event_contrast_workspace_bytes(int T, int H, int W);
+int ramp_event_contrast(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
+                        const double *times, int T, double t_ref, const float *intrinsics, const float *invdepth,
+                        const float *correction, int flags, int H, int W, float *iwe, int64_t *sums, double *stats, double *grad,
+                        void *ws, size_t ws_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

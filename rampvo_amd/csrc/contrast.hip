@@ -1,0 +1,395 @@
+// Event contrast and its gradient (include/ramp_hip.h: ramp_event_contrast): the variance of the image of warped events,
+// and its derivative with respect to a small correction theta = (v[3], w[3], lam) of the warp.  Everything up to X' is
+// ramp_event_warp's, statement for statement (warp_device.h); the correction acts in the reference camera frame, to first
+// order, by definition:
+//
+//   tau = float32(t - t_ref)            (the difference formed in float64; the unit of the time stamps)
+//   ds  = d * expf(lam)
+//   X1  = R_G P + t_G ds
+//   X2  = X1 + tau * (v * ds + w x X1)
+//   x'  = fx X2.x / X2.z + cx ,  y' = fy X2.y / X2.z + cy          invalid exactly as the warp, with X2.z in the place of Z'
+//
+// I(u) = sum_k s_k b(u - x'_k), s_k = p_k or 1 (RAMP_CONTRAST_UNSIGNED); f = (1 / P_n) sum_u (I(u) - mu)^2, P_n = H W.
+//
+//   df/dx'_k = (2 / P_n) s_k sum (I(ix + jx, iy + jy) - mu) * (jx ? +1 : -1) * wy[jy]       over the in-image neighbours
+//   df/dy'_k = (2 / P_n) s_k sum (I(ix + jx, iy + jy) - mu) * (jy ? +1 : -1) * wx[jx]
+//   dx'/dX2 = (fx / Z, 0, -fx X / Z^2)        dy'/dX2 = (0, fy / Z, -fy Y / Z^2)
+//   dX2/dv  = tau ds I_3         dX2/dw . r = tau (r x X1)         dX2/dlam = t_G ds + tau (v ds + w x (t_G ds))
+//
+// At most five launches behind one memset of the counters and accumulators:
+//   the segment launch   of the event warp (ramp_i_warp_segments)
+//   contrast_event_kernel<false>  the warp's splat with the correction: the same fixed point, the same staging and counters;
+//                        every wave also adds its events' contributions to two 64-bit integer sums S1 (signed, count)
+//   contrast_finish_kernel        accumulators -> iwe; with mu = S1 / P_n known exactly up to one rounding, per-workgroup
+//                        partials of sum I^2 and sum (I - mu)^2 in double, (double)acc * 2^-24 being exact
+//   contrast_event_kernel<true>   per event, one lane each: warp again, gather the four accumulators, seven terms in double
+//                        from the fp32 geometry; per lane, then per wave by a fixed butterfly, then the waves in wave order:
+//                        one row of 8 doubles per workgroup
+//   contrast_final_kernel         one workgroup: partials and rows summed in index order -> stats, grad, sums, status
+//
+// The accumulators and S1 are integer sums: stats, sums and iwe do not depend on the order of the events.  The squares are
+// centred BEFORE they are summed (that is why S1 is formed by the splat and not by the finish launch), so the variance of a
+// nearly uniform image does not cancel.  grad is a sum of doubles in a fixed order for given arguments: it repeats its bits
+// from call to call; another order of the events moves it by rounding.  No floating-point atomics.
+#include "ramp_internal.h"
+#include "warp_device.h"
+
+#define CON_FIN_MAX_GROUPS 256           // workgroups of the finish launch; each walks the pixels with this stride
+#define CON_ROW_WORDS 8                  // doubles per workgroup of the gradient launch: 7 terms, 1 spare
+#define CON_WAVES (INTERP_THREADS / RAMP_WAVE)
+#define CON_S1_WORD 8                    // the two int64 sums live in the spare counter words 8 .. 11
+
+struct ConArgs {
+  const float *x, *y;
+  const double *t;
+  const int8_t *p;
+  const float *knots;
+  const double *times;
+  const float *seg, *ref, *intrinsics, *invdepth, *correction;
+  long long *acc;                        // [2][H][W]
+  int32_t *ctr;
+  double *rows;                          // [grid][CON_ROW_WORDS]
+  double t_ref;
+  int N, T, H, W, extrapolate, depth_map, plane;
+};
+
+static __device__ __forceinline__ double con_wave_sum(double v) {
+#pragma unroll
+  for (int off = RAMP_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+static __device__ __forceinline__ long long con_wave_sum(long long v) {
+#pragma unroll
+  for (int off = RAMP_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// GRAD = false: the splat.  GRAD = true: the gradient's gather.  LDS_TIMES, VEC: as warp_event_kernel.
+template <bool GRAD, bool LDS_TIMES, bool VEC>
+__global__ void __launch_bounds__(INTERP_THREADS) contrast_event_kernel(const ConArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char con_smem[];
+  __shared__ __attribute__((aligned(16))) double s_t[WARP_TILE];
+  __shared__ __attribute__((aligned(16))) float s_x[WARP_TILE];
+  __shared__ __attribute__((aligned(16))) float s_y[WARP_TILE];
+  __shared__ __attribute__((aligned(16))) int8_t s_p[WARP_TILE];
+  __shared__ float s_uni[WARP_UNI_WORDS];
+  __shared__ float s_cor[8];
+  __shared__ double s_range[2];
+  __shared__ double s_red[GRAD ? CON_WAVES * CON_ROW_WORDS : 1];
+  double *s_times = reinterpret_cast<double *>(con_smem);
+  const int tid = threadIdx.x;
+  const int N = a.N, T = a.T, H = a.H, W = a.W;
+  if (LDS_TIMES)
+    for (int i = tid; i < T; i += INTERP_THREADS) s_times[i] = a.times[i];
+  if (tid == 12) { s_range[0] = a.times[0]; s_range[1] = a.times[T - 1]; }
+  if (tid < 7) s_uni[tid] = a.ref[tid];
+  else if (tid < 11) s_uni[tid] = a.intrinsics[tid - 7];
+  else if (tid == 11) s_uni[tid] = a.depth_map ? 0.0f : a.invdepth[0];
+  const bool has_cor = a.correction != nullptr;
+  if (tid >= 16 && tid < 24) s_cor[tid - 16] = (has_cor && tid < 23) ? a.correction[tid - 16] : 0.0f;
+  __syncthreads();
+  bool cor_bad = false;
+#pragma unroll
+  for (int c = 0; c < 7; c++) cor_bad = cor_bad || !(fabsf(s_cor[c]) <= 3.4028234663852886e38f);
+  if (!GRAD && cor_bad && blockIdx.x == 0 && tid == 0) atomicOr(a.ctr, RAMP_CONTRAST_BAD_CORRECTION);
+  const bool failed = cor_bad || (a.ctr[0] & RAMP_INTERP_BAD_TIMES) != 0;      // (raised by the segment launch in front)
+  const float v0 = s_cor[0], v1 = s_cor[1], v2 = s_cor[2], w0 = s_cor[3], w1 = s_cor[4], w2 = s_cor[5];
+  const float el = has_cor ? expf(s_cor[6]) : 1.0f;
+  const WarpScene sc = {a.knots, a.times, a.seg, a.invdepth, T, H, W, a.extrapolate, a.depth_map};
+  const size_t HW = (size_t)H * W;
+  const double fix = 1.0 / (double)(1 << WARP_FIX_BITS);
+  double mu = 0.0;
+  if (GRAD) {
+    const long long S1 = reinterpret_cast<const long long *>(a.ctr + CON_S1_WORD)[a.plane];
+    mu = ((double)S1 * fix) / (double)HW;
+  }
+  const long long *plane = a.acc + (size_t)a.plane * HW;
+  const long tiles = ((long)N + WARP_TILE - 1) / WARP_TILE;
+  int n_below = 0, n_above = 0, n_bad = 0, n_z = 0, n_out = 0, n_in = 0;    // wave-uniform: sums of ballots
+  long long sum_signed = 0, sum_count = 0;                                  // per lane (the splat)
+  double g[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                       // per lane (the gradient)
+  for (long tile = blockIdx.x; tile < tiles && !(GRAD && failed); tile += gridDim.x) {
+    const long base = tile * WARP_TILE;
+    const int live = (int)min((long)WARP_TILE, (long)N - base);
+    __syncthreads();                                 // (the previous tile has been read)
+    if (VEC && live == WARP_TILE) {
+      reinterpret_cast<float4 *>(s_x)[tid] = reinterpret_cast<const float4 *>(a.x + base)[tid];
+      reinterpret_cast<float4 *>(s_y)[tid] = reinterpret_cast<const float4 *>(a.y + base)[tid];
+      reinterpret_cast<int *>(s_p)[tid] = reinterpret_cast<const int *>(a.p + base)[tid];
+      reinterpret_cast<double2 *>(s_t)[tid] = reinterpret_cast<const double2 *>(a.t + base)[tid];
+      reinterpret_cast<double2 *>(s_t)[tid + INTERP_THREADS] = reinterpret_cast<const double2 *>(a.t + base)[tid + INTERP_THREADS];
+    } else {
+      for (int i = tid; i < live; i += INTERP_THREADS) {
+        s_x[i] = a.x[base + i];
+        s_y[i] = a.y[base + i];
+        s_p[i] = a.p[base + i];
+        s_t[i] = a.t[base + i];
+      }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int k = 0; k < WARP_TILE / INTERP_THREADS; k++) {
+      const int e = k * INTERP_THREADS + tid;
+      const bool have = e < live;
+      bool below = false, above = false, bad = false, zrej = false, outside = false, inside = false;
+      if (have) {
+        const float x = s_x[e], y = s_y[e];
+        const double t = s_t[e];
+        float xw = 0.0f, yw = 0.0f, tau = 0.0f, ds = 0.0f;
+        float X1[3] = {0.0f, 0.0f, 0.0f}, X2[3] = {0.0f, 0.0f, 0.0f}, tG[3] = {0.0f, 0.0f, 0.0f};
+        bool valid = false;
+        if (!warp_event_finite(x, y, t)) {
+          bad = true;
+        } else {
+          float R[3], d;
+          warp_event_geometry<LDS_TIMES>(sc, x, y, t, s_times, s_uni, s_range, &below, &above, R, tG, &d);
+          ds = has_cor ? d * el : d;
+          X1[0] = R[0] + tG[0] * ds; X1[1] = R[1] + tG[1] * ds; X1[2] = R[2] + tG[2] * ds;
+          X2[0] = X1[0]; X2[1] = X1[1]; X2[2] = X1[2];
+          if (GRAD || has_cor) tau = (float)(t - a.t_ref);
+          if (has_cor) {
+            X2[0] = X1[0] + tau * (v0 * ds + (w1 * X1[2] - w2 * X1[1]));
+            X2[1] = X1[1] + tau * (v1 * ds + (w2 * X1[0] - w0 * X1[2]));
+            X2[2] = X1[2] + tau * (v2 * ds + (w0 * X1[1] - w1 * X1[0]));
+          }
+          valid = warp_project(X2[0], X2[1], X2[2], s_uni, &xw, &yw);
+          zrej = !valid;
+        }
+        if (failed) { valid = false; zrej = false; }
+        if (valid) {
+          int ix, iy;
+          float wx[2], wy[2];
+          bool inx[2], iny[2];
+          warp_axis(xw, W, &ix, &wx[0], &wx[1], &inx[0], &inx[1]);
+          warp_axis(yw, H, &iy, &wy[0], &wy[1], &iny[0], &iny[1]);
+          inside = (inx[0] || inx[1]) && (iny[0] || iny[1]);
+          outside = !inside;
+          if (inside) {
+            const long long pol = s_p[e] == 0 ? -1ll : (long long)s_p[e];    // (0 is read as -1, like ops.event_stack)
+            double gx = 0.0, gy = 0.0;
+#pragma unroll
+            for (int jy = 0; jy < 2; jy++)
+#pragma unroll
+              for (int jx = 0; jx < 2; jx++)
+                if (inx[jx] && iny[jy]) {
+                  const size_t at = (size_t)(iy + jy) * W + (size_t)(ix + jx);
+                  if (GRAD) {
+                    const double dI = (double)plane[at] * fix - mu;
+                    gx += dI * (jx ? (double)wy[jy] : -(double)wy[jy]);
+                    gy += dI * (jy ? (double)wx[jx] : -(double)wx[jx]);
+                  } else {
+                    const long long c = warp_fixed_weight(wx[jx], wy[jy]);
+                    if (c != 0) {
+                      atomicAdd(reinterpret_cast<warp_u64 *>(a.acc + at), (warp_u64)(pol * c));
+                      atomicAdd(reinterpret_cast<warp_u64 *>(a.acc + HW + at), (warp_u64)c);
+                      sum_signed += pol * c;
+                      sum_count += c;
+                    }
+                  }
+                }
+            if (GRAD) {
+              const double sk = a.plane == 0 ? (double)pol : 1.0;
+              const double fx = (double)s_uni[7], fy = (double)s_uni[8];
+              const double X = (double)X2[0], Y = (double)X2[1], Z = (double)X2[2];
+              const double ga = sk * gx * fx / Z, gb = sk * gy * fy / Z;          // df/dX2, without the factor 2 / P_n
+              const double gc = -(sk * gx * fx * X + sk * gy * fy * Y) / (Z * Z);
+              const double dtau = (double)tau, dds = (double)ds;
+              const double A[3] = {(double)X1[0], (double)X1[1], (double)X1[2]};
+              const double B[3] = {(double)tG[0] * dds, (double)tG[1] * dds, (double)tG[2] * dds};
+              g[0] += dtau * dds * ga;
+              g[1] += dtau * dds * gb;
+              g[2] += dtau * dds * gc;
+              g[3] += dtau * (A[1] * gc - A[2] * gb);                              // tau (X1 x df/dX2)
+              g[4] += dtau * (A[2] * ga - A[0] * gc);
+              g[5] += dtau * (A[0] * gb - A[1] * ga);
+              const double L0 = B[0] + dtau * ((double)v0 * dds + ((double)w1 * B[2] - (double)w2 * B[1]));
+              const double L1 = B[1] + dtau * ((double)v1 * dds + ((double)w2 * B[0] - (double)w0 * B[2]));
+              const double L2 = B[2] + dtau * ((double)v2 * dds + ((double)w0 * B[1] - (double)w1 * B[0]));
+              g[6] += ga * L0 + gb * L1 + gc * L2;
+            }
+          }
+        }
+      }
+      if (!GRAD) {
+        // the trip count and `have` aside, every lane of the wave is here: one ballot per counter, summed per wave
+        n_below += __popcll(__ballot(below));
+        n_above += __popcll(__ballot(above));
+        n_bad += __popcll(__ballot(bad));
+        n_z += __popcll(__ballot(zrej));
+        n_out += __popcll(__ballot(outside));
+        n_in += __popcll(__ballot(inside));
+      }
+    }
+  }
+  if (!GRAD) {
+    sum_signed = con_wave_sum(sum_signed);
+    sum_count = con_wave_sum(sum_count);
+    if ((tid & (RAMP_WAVE - 1)) == 0) {                // one integer atomic per wave and counter that is not zero
+      if (n_below) atomicAdd(&a.ctr[1], n_below);
+      if (n_above) atomicAdd(&a.ctr[2], n_above);
+      if (n_bad) atomicAdd(&a.ctr[3], n_bad);
+      if (n_z) atomicAdd(&a.ctr[4], n_z);
+      if (n_out) atomicAdd(&a.ctr[5], n_out);
+      if (n_in) atomicAdd(&a.ctr[6], n_in);
+      warp_u64 *S1 = reinterpret_cast<warp_u64 *>(a.ctr + CON_S1_WORD);
+      if (sum_signed) atomicAdd(&S1[0], (warp_u64)sum_signed);
+      if (sum_count) atomicAdd(&S1[1], (warp_u64)sum_count);
+    }
+  } else {
+    // per wave by a fixed butterfly, then the waves in wave order
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < 7; c++) {
+      const double v = con_wave_sum(g[c]);
+      if ((tid & (RAMP_WAVE - 1)) == 0) s_red[(tid / RAMP_WAVE) * CON_ROW_WORDS + c] = v;
+    }
+    __syncthreads();
+    if (tid < CON_ROW_WORDS) {
+      double v = 0.0;
+      if (tid < 7)
+        for (int w = 0; w < CON_WAVES; w++) v += s_red[w * CON_ROW_WORDS + tid];
+      a.rows[(size_t)blockIdx.x * CON_ROW_WORDS + tid] = v;
+    }
+  }
+}
+
+// accumulators -> iwe, and per workgroup the partial sums of I^2 and (I - mu)^2 over the plane the statistics are taken from
+__global__ void __launch_bounds__(256)
+    contrast_finish_kernel(const long long *__restrict__ acc, const int32_t *__restrict__ ctr, float *__restrict__ iwe, long HW,
+                           int plane, double *__restrict__ fin) {
+  __shared__ double s_red[2 * CON_WAVES];
+  const int tid = threadIdx.x;
+  const bool failed = (ctr[0] & (RAMP_INTERP_BAD_TIMES | RAMP_CONTRAST_BAD_CORRECTION)) != 0;
+  const float qnan = __int_as_float(0x7fc00000), scale = 1.0f / (float)(1 << WARP_FIX_BITS);
+  const double fix = 1.0 / (double)(1 << WARP_FIX_BITS);
+  const double mu = ((double)reinterpret_cast<const long long *>(ctr + CON_S1_WORD)[plane] * fix) / (double)HW;
+  double s2 = 0.0, c2 = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + tid; i < HW; i += (long)gridDim.x * blockDim.x) {
+    const long long a0 = acc[i], a1 = acc[HW + i];
+    if (iwe) {
+      iwe[i] = failed ? qnan : (float)a0 * scale;      // int64 -> fp32 rounds once; the power of two is exact
+      iwe[HW + i] = failed ? qnan : (float)a1 * scale;
+    }
+    const double v = (double)(plane ? a1 : a0) * fix;
+    s2 += v * v;
+    c2 += (v - mu) * (v - mu);
+  }
+  s2 = con_wave_sum(s2);
+  c2 = con_wave_sum(c2);
+  if ((tid & (RAMP_WAVE - 1)) == 0) { s_red[2 * (tid / RAMP_WAVE)] = s2; s_red[2 * (tid / RAMP_WAVE) + 1] = c2; }
+  __syncthreads();
+  if (tid < 2) {
+    double v = 0.0;
+    for (int w = 0; w < CON_WAVES; w++) v += s_red[2 * w + tid];
+    fin[2 * (size_t)blockIdx.x + tid] = v;
+  }
+}
+
+// one workgroup: the partials and the rows in index order
+__global__ void __launch_bounds__(RAMP_WAVE)
+    contrast_final_kernel(const int32_t *__restrict__ ctr, const double *__restrict__ fin, int n_fin, const double *__restrict__ rows,
+                          int n_rows, long HW, int plane, long long *__restrict__ sums, double *__restrict__ stats,
+                          double *__restrict__ grad, int32_t *__restrict__ status) {
+  const int tid = threadIdx.x;
+  const int32_t word = ctr[0];
+  const bool failed = (word & (RAMP_INTERP_BAD_TIMES | RAMP_CONTRAST_BAD_CORRECTION)) != 0;
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  const double fix = 1.0 / (double)(1 << WARP_FIX_BITS), Pn = (double)HW;
+  const long long *S1 = reinterpret_cast<const long long *>(ctr + CON_S1_WORD);
+  if (tid < 8) status[tid] = tid < 7 ? ctr[tid] : 0;
+  if (tid < 2) sums[tid] = S1[tid];
+  if (tid < 7 && grad) {
+    double v = 0.0;
+    for (int r = 0; r < n_rows; r++) v += rows[(size_t)r * CON_ROW_WORDS + tid];
+    grad[tid] = failed ? qnan : v * (2.0 / Pn);
+  } else if (tid >= 8 && tid < 10) {
+    double v = 0.0;
+    for (int r = 0; r < n_fin; r++) v += fin[2 * (size_t)r + (tid - 8)];
+    if (tid == 8) stats[2] = failed ? qnan : v;                  // sum of I^2
+    else stats[0] = failed ? qnan : v / Pn;                      // the population variance
+  } else if (tid == 10) {
+    stats[1] = failed ? qnan : ((double)S1[plane] * fix) / Pn;   // the mean: the bits the other launches centred with
+    stats[3] = Pn;
+  } else if (tid >= 12 && tid < 16) {
+    stats[tid - 8] = 0.0;
+  }
+}
+
+static int con_fin_groups(long HW) {
+  const long n = (HW + 255) / 256;
+  return (int)(n < CON_FIN_MAX_GROUPS ? n : CON_FIN_MAX_GROUPS);
+}
+
+template <bool GRAD>
+static int con_launch_events(const ConArgs &a, bool lds_times, bool vec, int grid, hipStream_t st) {
+  const size_t lds = lds_times ? (size_t)a.T * sizeof(double) : 0;
+  static_assert((size_t)INTERP_LDS_KNOTS * sizeof(double) + WARP_TILE * 17 + 512 <= 64 * 1024,
+                "LDS within the default limit: the launch needs no hipFuncSetAttribute");
+  if (lds_times) {
+    if (vec) hipLaunchKernelGGL((contrast_event_kernel<GRAD, true, true>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
+    else hipLaunchKernelGGL((contrast_event_kernel<GRAD, true, false>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
+  } else {
+    if (vec) hipLaunchKernelGGL((contrast_event_kernel<GRAD, false, true>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
+    else hipLaunchKernelGGL((contrast_event_kernel<GRAD, false, false>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
+  }
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+
+extern "C" {
+size_t ramp_event_contrast_workspace_bytes(int T, int H, int W) {
+  if (H < 1 || W < 1) return 0;
+  return warp_acc_offset(T) + WARP_CTR_WORDS * sizeof(int32_t) + (size_t)2 * H * W * sizeof(long long) +
+         (size_t)CON_FIN_MAX_GROUPS * 2 * sizeof(double) + (size_t)WARP_MAX_GROUPS * CON_ROW_WORDS * sizeof(double);
+}
+
+int ramp_event_contrast(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
+                        const double *times, int T, double t_ref, const float *intrinsics, const float *invdepth,
+                        const float *correction, int flags, int H, int W, float *iwe, int64_t *sums, double *stats, double *grad,
+                        void *ws, size_t ws_bytes, int32_t *status, void *stream) {
+  if (N < 0 || T < 1 || H < 1 || W < 1) return RAMP_EINVAL;
+  if (flags & ~(RAMP_INTERP_EXTRAPOLATE | RAMP_WARP_DEPTH_MAP | RAMP_CONTRAST_UNSIGNED)) return RAMP_EINVAL;
+  if (!(fabs(t_ref) <= 1.7976931348623157e308)) return RAMP_EINVAL;
+  if (N == 0) return RAMP_OK;
+  if (!x || !y || !t || !p || !knots || !times || !intrinsics || !invdepth || !sums || !stats || !ws || !status) return RAMP_EINVAL;
+  if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)sums & 7) != 0 || ((uintptr_t)stats & 7) != 0 || ((uintptr_t)grad & 7) != 0)
+    return RAMP_EINVAL;
+  if (ws_bytes < ramp_event_contrast_workspace_bytes(T, H, W)) return RAMP_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t HW = (size_t)H * W;
+  unsigned char *base = (unsigned char *)ws;
+  float *seg = (float *)base, *ref = seg + (size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS;
+  int32_t *ctr = (int32_t *)(base + warp_acc_offset(T));
+  long long *acc = (long long *)(ctr + WARP_CTR_WORDS);
+  double *fin = (double *)(acc + 2 * HW), *rows = fin + (size_t)CON_FIN_MAX_GROUPS * 2;
+  // the one memset: the counters (the two sums among them) and, behind them, the accumulators
+  if (hipMemsetAsync(ctr, 0, WARP_CTR_WORDS * sizeof(int32_t) + 2 * HW * sizeof(long long), st) != hipSuccess) return RAMP_ELAUNCH;
+  const int ex = (flags & RAMP_INTERP_EXTRAPOLATE) ? 1 : 0;
+  int rc = ramp_i_warp_segments(knots, times, T, t_ref, ex, seg, ref, ctr, st);
+  if (rc != RAMP_OK) return rc;
+  ConArgs a;
+  a.x = x; a.y = y; a.t = t; a.p = p; a.knots = knots; a.times = times; a.seg = seg; a.ref = ref;
+  a.intrinsics = intrinsics; a.invdepth = invdepth; a.correction = correction; a.acc = acc; a.ctr = ctr; a.rows = rows;
+  a.t_ref = t_ref; a.N = N; a.T = T; a.H = H; a.W = W; a.extrapolate = ex;
+  a.depth_map = (flags & RAMP_WARP_DEPTH_MAP) ? 1 : 0;
+  a.plane = (flags & RAMP_CONTRAST_UNSIGNED) ? 1 : 0;
+  const long tiles = ((long)N + WARP_TILE - 1) / WARP_TILE;
+  const int grid = (int)(tiles < WARP_MAX_GROUPS ? tiles : WARP_MAX_GROUPS);
+  const bool vec = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)p | (uintptr_t)t) & 15) == 0;
+  const bool lds_times = T <= INTERP_LDS_KNOTS;
+  rc = con_launch_events<false>(a, lds_times, vec, grid, st);
+  if (rc != RAMP_OK) return rc;
+  const int n_fin = con_fin_groups((long)HW);
+  hipLaunchKernelGGL(contrast_finish_kernel, dim3(n_fin), dim3(256), 0, st, acc, ctr, iwe, (long)HW, a.plane, fin);
+  RAMP_CHECK_LAUNCH();
+  if (grad) {
+    rc = con_launch_events<true>(a, lds_times, vec, grid, st);
+    if (rc != RAMP_OK) return rc;
+  }
+  hipLaunchKernelGGL(contrast_final_kernel, dim3(1), dim3(RAMP_WAVE), 0, st, ctr, fin, n_fin, rows, grad ? grid : 0, (long)HW,
+                     a.plane, (long long *)sums, stats, grad, status);
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+}  // extern "C"

@@ -39,6 +39,10 @@ int ramp_i_plan_dyn(const int64_t *g4, int E_cap, int E_grid, const int32_t *dyn
                     int32_t *kk_ngroups, int64_t *kk_ukeys, int32_t *ij_order, int32_t *ij_gid, int32_t *ij_seg,
                     int32_t *ij_ngroups, int64_t *ij_ukeys, int64_t *ix, int64_t *jx, int32_t *kj, void *ws,
                     size_t ws_bytes, int32_t *mirror, hipStream_t st);
+// the segment launch of the event warp (csrc/warp.hip), shared with the event contrast (csrc/contrast.hip): the segment table
+// into seg, C(t_ref)^-1 into ref (WARP_REF_WORDS floats), RAMP_INTERP_BAD_TIMES into ctr[0]
+int ramp_i_warp_segments(const float *knots, const double *times, int T, double t_ref, int extrapolate, float *seg, float *ref,
+                         int32_t *ctr, hipStream_t st);
 // bundle adjustment (csrc/ba.hip): the state and the graph of one problem
 struct BaProblem {
   float *poses, *patches;                                  // [n_poses][7], [n_patches][3][P][P]

@@ -17,29 +17,8 @@
 // llrint(weight * 2^24), added with 64-bit integer atomics.  Integer addition commutes, so the sums -- and every output --
 // do not depend on the order in which events arrive, and a call repeats its bits.  |sum| < 2^63 holds up to 2^39 events on
 // one pixel.  G is composed so that C(t) == C(t_ref) bit for bit gives the exact identity (see warp_relative).
-#include "interp_device.h"
-
-#define WARP_TILE (INTERP_THREADS * 4)   // events per workgroup trip: a 16-byte load of x and y per lane
-#define WARP_MAX_GROUPS 1024             // workgroups of the event launch; each walks the tiles with this stride
-#define WARP_FIX_BITS 24
-#define WARP_REF_WORDS 16                // C(t_ref)^-1: translation 3, quaternion 4, 9 spare = one 64-byte row
-#define WARP_CTR_WORDS 16                // int32: the 8 status words, 8 spare
-
-typedef unsigned long long warp_u64;
-
-// G = Cref^-1 * C from ref = (-(qr^-1 . tr), qr^-1) and C = (t, q), without renormalising either factor:
-//   q_G = normalise(qr^-1 * q),  t_G = qr^-1 . t - qr^-1 . tr
-// Both rotations of a translation are the same function of their inputs, so C == Cref in every bit gives t_G = 0 exactly, and
-// the quaternion product of q with its own conjugate has exactly zero imaginary parts: G is then the exact identity.
-static __device__ __forceinline__ void warp_relative(const float *ref, const float *C, float *tG, float *qG) {
-  float q[4], r[3];
-  lt_qmul(ref + 3, C + 3, q);
-  lt_qnorm(q, qG);
-  lt_qrot(ref + 3, C, r);
-  tG[0] = ref[0] + r[0];
-  tG[1] = ref[1] + r[1];
-  tG[2] = ref[2] + r[2];
-}
+#include "ramp_internal.h"
+#include "warp_device.h"
 
 __global__ void __launch_bounds__(INTERP_THREADS)
     warp_segment_kernel(const float *__restrict__ knots, const double *__restrict__ times, int T, double t_ref,
@@ -80,18 +59,6 @@ struct WarpArgs {
   int N, T, bins, H, W, extrapolate, depth_map;
 };
 
-// one axis of the splat: the two neighbours floor(v) and floor(v) + 1, their weights 1 - w and w with w = v - floor(v), and
-// whether each lies in [0, n).  The range test is made in float, so a huge coordinate never reaches an integer conversion.
-static __device__ __forceinline__ void warp_axis(float v, int n, int *i0, float *w0, float *w1, bool *in0, bool *in1) {
-  const float fl = floorf(v);
-  const float w = v - fl;
-  *w0 = 1.0f - w;
-  *w1 = w;
-  *in0 = fl >= 0.0f && fl <= (float)(n - 1);
-  *in1 = fl >= -1.0f && fl <= (float)(n - 2);
-  *i0 = (*in0 || *in1) ? (int)fl : 0;
-}
-
 // IDENTITY: no trajectory, x' = x and y' = y (the bilinear path of the event stack).  LDS_TIMES, VEC: the knot times are
 // staged in LDS; full tiles are loaded with 16-byte loads (every event array 16-byte aligned).
 template <bool IDENTITY, bool LDS_TIMES, bool VEC>
@@ -101,7 +68,7 @@ __global__ void __launch_bounds__(INTERP_THREADS) warp_event_kernel(const WarpAr
   __shared__ __attribute__((aligned(16))) float s_x[WARP_TILE];
   __shared__ __attribute__((aligned(16))) float s_y[WARP_TILE];
   __shared__ __attribute__((aligned(16))) int8_t s_p[WARP_TILE];
-  __shared__ float s_uni[12];
+  __shared__ float s_uni[WARP_UNI_WORDS];
   __shared__ double s_range[2];
   double *s_times = reinterpret_cast<double *>(warp_smem);
   const int tid = threadIdx.x;
@@ -116,7 +83,6 @@ __global__ void __launch_bounds__(INTERP_THREADS) warp_event_kernel(const WarpAr
     else if (tid < 11) s_uni[tid] = a.intrinsics[tid - 7];
     else if (tid == 11) s_uni[tid] = a.depth_map ? 0.0f : a.invdepth[0];
   }
-  const int s_max = T > 1 ? T - 2 : 0;
   const float qnan = __int_as_float(0x7fc00000);
   const size_t HW = (size_t)H * W;
   const long tiles = ((long)N + WARP_TILE - 1) / WARP_TILE;
@@ -153,48 +119,19 @@ __global__ void __launch_bounds__(INTERP_THREADS) warp_event_kernel(const WarpAr
         const double t = IDENTITY ? 0.0 : s_t[e];
         float xw = qnan, yw = qnan;
         bool valid = false;
-        if (!(fabsf(x) <= 3.4028234663852886e38f && fabsf(y) <= 3.4028234663852886e38f && interp_finite(t))) {
+        if (!warp_event_finite(x, y, t)) {
           bad = true;
         } else if (IDENTITY) {
           xw = x;
           yw = y;
           valid = true;
         } else {
-          below = t < s_range[0];
-          above = t > s_range[1];
-          int s;
-          double ts;
-          if (LDS_TIMES) {
-            s = min(max(interp_upper_bound(s_times, T, t) - 1, 0), s_max);
-            ts = s_times[s];
-          } else {
-            s = min(max(interp_upper_bound(a.times, T, t) - 1, 0), s_max);
-            ts = a.times[s];
-          }
-          const float4 *row4 = reinterpret_cast<const float4 *>(a.seg + (size_t)s * INTERP_SEG_WORDS);
-          const float4 r0 = row4[0], r1 = row4[1];      // xi[0..3]; xi[4], xi[5], the length
-          const float xi[6] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y};
-          const double dt = __hiloint2double(__float_as_int(r1.w), __float_as_int(r1.z));
-          const float alpha = interp_alpha(t, ts, dt, a.extrapolate);
-          float X[7], C[7], tG[3], qG[4], R[3], ref[7];
-          const float fx = s_uni[7], fy = s_uni[8], cx = s_uni[9], cy = s_uni[10];
-#pragma unroll
-          for (int c = 0; c < 7; c++) ref[c] = s_uni[c];
-#pragma unroll
-          for (int c = 0; c < 7; c++) X[c] = a.knots[7 * (size_t)s + c];
-          interp_pose(X, xi, alpha, C);
-          warp_relative(ref, C, tG, qG);
-          float d = s_uni[11];
-          if (a.depth_map) {                             // the event's rounded pixel (half to even), clamped to the image
-            const int px = (int)fminf(fmaxf(rintf(x), 0.0f), (float)(W - 1));
-            const int py = (int)fminf(fmaxf(rintf(y), 0.0f), (float)(H - 1));
-            d = a.invdepth[(size_t)py * W + px];
-          }
-          const float P[3] = {(x - cx) / fx, (y - cy) / fy, 1.0f};
-          lt_qrot(qG, P, R);
+          float R[3], tG[3], d;
+          const WarpScene sc = {a.knots, a.times, a.seg, a.invdepth, T, H, W, a.extrapolate, a.depth_map};
+          warp_event_geometry<LDS_TIMES>(sc, x, y, t, s_times, s_uni, s_range, &below, &above, R, tG, &d);
           const float Xp = R[0] + tG[0] * d, Yp = R[1] + tG[1] * d, Zp = R[2] + tG[2] * d;
-          const float xp = fx * (Xp / Zp) + cx, yp = fy * (Yp / Zp) + cy;
-          valid = Zp > RAMP_WARP_MIN_Z && fabsf(xp) <= 3.4028234663852886e38f && fabsf(yp) <= 3.4028234663852886e38f;
+          float xp, yp;
+          valid = warp_project(Xp, Yp, Zp, s_uni, &xp, &yp);
           zrej = !valid;                                 // (a NaN Z' fails the comparison: rejected, like a NaN projection)
           if (valid) { xw = xp; yw = yp; }
         }
@@ -217,7 +154,7 @@ __global__ void __launch_bounds__(INTERP_THREADS) warp_event_kernel(const WarpAr
 #pragma unroll
               for (int jx = 0; jx < 2; jx++)
                 if (inx[jx] && iny[jy]) {
-                  const long long c = __float2ll_rn(ldexpf(__fmul_rn(wx[jx], wy[jy]), WARP_FIX_BITS));
+                  const long long c = warp_fixed_weight(wx[jx], wy[jy]);
                   if (c != 0) {
                     const size_t at = (size_t)(iy + jy) * W + (size_t)(ix + jx);
                     if (a.acc_iwe) {
@@ -267,10 +204,6 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-static size_t warp_acc_offset(int T) {
-  return ((size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS + WARP_REF_WORDS) * sizeof(float);    // the counters start here
-}
-
 template <bool IDENTITY>
 static int warp_launch_events(const WarpArgs &a, bool lds_times, bool vec, int grid, hipStream_t st) {
   const size_t lds = (!IDENTITY && lds_times) ? (size_t)a.T * sizeof(double) : 0;
@@ -283,6 +216,15 @@ static int warp_launch_events(const WarpArgs &a, bool lds_times, bool vec, int g
     if (vec) hipLaunchKernelGGL((warp_event_kernel<IDENTITY, false, true>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
     else hipLaunchKernelGGL((warp_event_kernel<IDENTITY, false, false>), dim3(grid), dim3(INTERP_THREADS), lds, st, a);
   }
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+
+int ramp_i_warp_segments(const float *knots, const double *times, int T, double t_ref, int extrapolate, float *seg, float *ref,
+                         int32_t *ctr, hipStream_t st) {
+  const int S = T > 1 ? T - 1 : 1;
+  hipLaunchKernelGGL(warp_segment_kernel, dim3(ramp_cdiv(S, INTERP_THREADS) + 1), dim3(INTERP_THREADS), 0, st, knots, times,
+                     T, t_ref, extrapolate, seg, ref, ctr);
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;
 }
@@ -323,10 +265,8 @@ int ramp_event_warp(const float *x, const float *y, const double *t, const int8_
     return RAMP_ELAUNCH;
   const int ex = (flags & RAMP_INTERP_EXTRAPOLATE) ? 1 : 0;
   if (!identity) {
-    const int S = T > 1 ? T - 1 : 1;
-    hipLaunchKernelGGL(warp_segment_kernel, dim3(ramp_cdiv(S, INTERP_THREADS) + 1), dim3(INTERP_THREADS), 0, st, knots, times,
-                       T, t_ref, ex, seg, ref, ctr);
-    RAMP_CHECK_LAUNCH();
+    const int rc = ramp_i_warp_segments(knots, times, T, t_ref, ex, seg, ref, ctr, st);
+    if (rc != RAMP_OK) return rc;
   }
   WarpArgs a;
   a.x = x; a.y = y; a.t = t; a.p = p; a.knots = knots; a.times = times; a.seg = seg; a.ref = ref;

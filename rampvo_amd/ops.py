@@ -155,6 +155,39 @@ def event_stack(x, y, p, height, width, num_bins=5, as_float=True):
     return out
 
 
+def _event_arguments(name, x, y, t, p, knots, times, intrinsics, invdepth, height, width, extrapolate):
+    """the argument handling of ``event_warp``, for the entries that take its arguments -> (xf, yf, tf, pi, knots, times,
+    K, d, flags)"""
+    require_cuda(x, y, t, p, knots, times)
+    dev = x.device
+    N = x.shape[0]
+    xf, yf = x.reshape(-1).to(torch.float32).contiguous(), y.reshape(-1).to(torch.float32).contiguous()
+    tf = t.reshape(-1).to(torch.float64).contiguous()
+    pi = p.reshape(-1).to(torch.int8)
+    pi = torch.where(pi == 0, torch.full_like(pi, -1), pi).contiguous()
+    knots = knots.reshape(-1, 7).contiguous().float()
+    times = times.reshape(-1).contiguous().double()
+    T = knots.shape[0]
+    if times.shape[0] != T:
+        raise RuntimeError("%s: %d knots but %d time stamps" % (name, T, times.shape[0]))
+    if not (yf.shape[0] == N and tf.shape[0] == N and pi.shape[0] == N):
+        raise RuntimeError("%s: x, y, t and p differ in length" % name)
+    K = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(4).contiguous()
+    flags = _lib.RAMP_INTERP_EXTRAPOLATE if extrapolate else 0
+    if isinstance(invdepth, torch.Tensor) and invdepth.numel() != 1:
+        if tuple(invdepth.shape) != (height, width):
+            raise RuntimeError("%s: an inverse depth map is [height, width]" % name)
+        require_cuda(invdepth)
+        d = invdepth.to(torch.float32).contiguous()
+        flags |= _lib.RAMP_WARP_DEPTH_MAP
+    elif isinstance(invdepth, torch.Tensor):
+        require_cuda(invdepth)
+        d = invdepth.reshape(1).to(torch.float32).contiguous()
+    else:
+        d = torch.full((1,), float(invdepth), dtype=torch.float32, device=dev)
+    return xf, yf, tf, pi, knots, times, K, d, flags
+
+
 def event_warp(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, num_bins=0, extrapolate=False,
                want_xy=False, want_iwe=True, stack=None):
     """Motion compensation of an event list (include/ramp_hip.h ``ramp_event_warp``): every event is warped from the camera
@@ -170,37 +203,13 @@ def event_warp(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, wi
     events), ``iwe`` [2,height,width] (polarity-signed sum, unsigned count), ``stack`` [num_bins,height,width] float32
     (``stack="f32"``) or int8 (``"i8"``).  The sums are fixed point over integer atomics: the same bits for any order of
     the events."""
-    require_cuda(x, y, t, p, knots, times)
     if stack not in (None, "f32", "i8"):
         raise RuntimeError("event_warp: stack is 'f32', 'i8' or None")
     if stack is not None and num_bins < 1:
         raise RuntimeError("event_warp: a stack needs num_bins >= 1")
-    dev = x.device
-    N = x.shape[0]
-    xf, yf = x.reshape(-1).to(torch.float32).contiguous(), y.reshape(-1).to(torch.float32).contiguous()
-    tf = t.reshape(-1).to(torch.float64).contiguous()
-    pi = p.reshape(-1).to(torch.int8)
-    pi = torch.where(pi == 0, torch.full_like(pi, -1), pi).contiguous()
-    knots = knots.reshape(-1, 7).contiguous().float()
-    times = times.reshape(-1).contiguous().double()
-    T = knots.shape[0]
-    if times.shape[0] != T:
-        raise RuntimeError("event_warp: %d knots but %d time stamps" % (T, times.shape[0]))
-    if not (yf.shape[0] == N and tf.shape[0] == N and pi.shape[0] == N):
-        raise RuntimeError("event_warp: x, y, t and p differ in length")
-    K = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(4).contiguous()
-    flags = _lib.RAMP_INTERP_EXTRAPOLATE if extrapolate else 0
-    if isinstance(invdepth, torch.Tensor) and invdepth.numel() != 1:
-        if tuple(invdepth.shape) != (height, width):
-            raise RuntimeError("event_warp: an inverse depth map is [height, width]")
-        require_cuda(invdepth)
-        d = invdepth.to(torch.float32).contiguous()
-        flags |= _lib.RAMP_WARP_DEPTH_MAP
-    elif isinstance(invdepth, torch.Tensor):
-        require_cuda(invdepth)
-        d = invdepth.reshape(1).to(torch.float32).contiguous()
-    else:
-        d = torch.full((1,), float(invdepth), dtype=torch.float32, device=dev)
+    xf, yf, tf, pi, knots, times, K, d, flags = _event_arguments("event_warp", x, y, t, p, knots, times, intrinsics, invdepth,
+                                                                 height, width, extrapolate)
+    dev, N, T = xf.device, x.shape[0], knots.shape[0]
     bins = num_bins if stack is not None else 1
     res = {"status": torch.zeros(8, dtype=torch.int32, device=dev)}
     if want_xy:
@@ -225,6 +234,105 @@ def event_warp_status(status):
     w = status.detach().cpu()
     return dict(bad_times=bool(int(w[0]) & _lib.RAMP_INTERP_BAD_TIMES), n_below=int(w[1]), n_above=int(w[2]),
                 n_not_finite=int(w[3]), n_rejected=int(w[4]), n_outside=int(w[5]), n_contributed=int(w[6]))
+
+
+def event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=None, signed=True,
+                   extrapolate=False, want_grad=True, want_iwe=False):
+    """The contrast of a motion-compensated event list and its gradient (include/ramp_hip.h ``ramp_event_contrast``): the
+    population variance of the image of warped events ``event_warp`` would splat, and its derivative with respect to a small
+    correction ``theta = (v[3], w[3], lam)`` -- translation 3, rotation 3, a log depth scale -- that acts in the reference
+    camera frame: ``X2 = X1 + tau (v ds + w x X1)``, ``X1 = R_G P + t_G ds``, ``ds = d exp(lam)``, ``tau = t - t_ref``.
+
+    The arguments up to ``width`` are ``event_warp``'s.  ``correction``: None (zero), a sequence of 7 numbers or a device
+    tensor [7].  ``signed=False`` scores the count image instead of the polarity-signed one.  Device tensors, ordered on the
+    current stream, nothing synchronised.
+
+    Returns a dict of device tensors: ``variance`` (0-d float64 view of ``stats``), ``stats`` float64 [8] (variance, mean,
+    sum of I^2, pixel count), ``sums`` int64 [2] (the exact fixed-point sums of the signed and the count accumulators),
+    ``status`` int32 [8] (``event_warp_status``; bit 1 of word 0: a correction that is not finite) and, as requested, ``grad``
+    float64 [7] and ``iwe`` [2,height,width].  ``stats``, ``sums`` and ``iwe`` are the same bits for any order of the events;
+    ``grad`` repeats its bits from call to call.  Time stamps of the knots that decrease, or a correction that is not finite:
+    NaN in ``stats``, ``grad`` and ``iwe``, never a plausible number."""
+    xf, yf, tf, pi, knots, times, K, d, flags = _event_arguments("event_contrast", x, y, t, p, knots, times, intrinsics,
+                                                                 invdepth, height, width, extrapolate)
+    dev, N, T = xf.device, xf.shape[0], knots.shape[0]
+    if not signed:
+        flags |= _lib.RAMP_CONTRAST_UNSIGNED
+    if correction is None:
+        cor = None
+    else:
+        cor = torch.as_tensor(correction, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+        if cor.numel() != 7:
+            raise RuntimeError("event_contrast: a correction is (v[3], w[3], lam): 7 numbers")
+    res = {"stats": torch.zeros(8, dtype=torch.float64, device=dev), "sums": torch.zeros(2, dtype=torch.int64, device=dev),
+           "status": torch.zeros(8, dtype=torch.int32, device=dev)}
+    res["variance"] = res["stats"][0]
+    if want_grad:
+        res["grad"] = torch.zeros(7, dtype=torch.float64, device=dev)
+    if want_iwe:
+        res["iwe"] = torch.zeros((2, height, width), dtype=torch.float32, device=dev)
+    if N == 0:
+        res["stats"][3] = float(height * width)
+        return res
+    nbytes = lib().ramp_event_contrast_workspace_bytes(T, height, width)
+    ws = _lib_workspace(nbytes, dev, "evcontrast")
+    check(lib().ramp_event_contrast(ptr(xf), ptr(yf), ptr(tf), ptr(pi), N, ptr(knots), ptr(times), T, float(t_ref), ptr(K),
+                                    ptr(d), ptr(cor), flags, height, width, ptr(res.get("iwe")), ptr(res["sums"]),
+                                    ptr(res["stats"]), ptr(res.get("grad")), ptr(ws), nbytes, ptr(res["status"]), stream()),
+          "ramp_event_contrast")
+    return res
+
+
+def align_loop(evaluate, correction, free, step, iters):
+    """the line search of ``event_align`` over ``evaluate(theta) -> (variance, grad)``: normalised gradient ascent with
+    backtracking.  The direction is the gradient masked by ``free``, divided by its norm; the step length starts at ``step``,
+    doubles after an accepted step and halves, up to 8 times, while the contrast does not rise; the loop stops after ``iters``
+    accepted steps, when a step fails 8 halvings, or when the masked gradient is zero or not finite."""
+    theta = [float(c) for c in correction]
+    mask = [1.0 if f else 0.0 for f in free]
+    f, g = evaluate(theta)
+    f0, history, length = f, [], float(step)
+    while len(history) < iters:
+        gm = [gi * mi for gi, mi in zip(g, mask)]
+        norm = sum(gi * gi for gi in gm) ** 0.5
+        if not (norm > 0.0 and norm < float("inf")):
+            break
+        accepted = False
+        for _ in range(9):                                    # the first trial and up to 8 halvings
+            trial = [ti + length * gi / norm for ti, gi in zip(theta, gm)]
+            ft, gt = evaluate(trial)
+            if ft > f:
+                theta, f, g, accepted = trial, ft, gt, True
+                break
+            length *= 0.5
+        if not accepted:
+            break
+        history.append(f)
+        length *= 2.0
+    return dict(correction=theta, variance=f, variance0=f0, history=history)
+
+
+def event_align(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=None,
+                free=(0, 0, 0, 1, 1, 1, 0), step=0.05, iters=20, signed=True, extrapolate=False):
+    """Refine a correction by contrast maximisation: a HOST loop over ``event_contrast`` (``align_loop``: normalised gradient
+    ascent with backtracking over the components ``free`` marks; the default frees the rotation rate).  Every evaluation
+    reads 8 + 7 doubles back (the statistics and the gradient: one synchronisation each), so this is a convenience for a few
+    dozen evaluations, not a hot path.  ``step``: the first step length, in the units of ``theta`` (a rate per unit of the
+    time stamps).
+
+    Returns a dict: ``correction`` (list of 7 floats), ``variance``, ``variance0`` (at the start) and ``history`` (the accepted
+    variances, strictly rising)."""
+    if len(free) != 7:
+        raise RuntimeError("event_align: free marks the 7 components of (v[3], w[3], lam)")
+
+    def evaluate(theta):
+        r = event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=theta,
+                           signed=signed, extrapolate=extrapolate)
+        both = torch.cat([r["stats"], r["grad"]]).cpu().tolist()           # (the 8 + 7 doubles)
+        return both[0], both[8:]
+
+    return align_loop(evaluate, [0.0] * 7 if correction is None else torch.as_tensor(correction).reshape(-1).tolist(), free,
+                      step, iters)
 
 
 def invdepth_map(poses, patches, intrinsics, cam, height, width, radius, scale=1, index=None, count=None, conf=None,

@@ -218,11 +218,27 @@ class TrackerQueries:
         the dict of device tensors of ``ops.event_warp`` (``status``, ``xy``, ``iwe``, ``stack`` as requested), ordered on
         the current stream, nothing synchronised.  Otherwise numpy arrays, which waits for that result and raises when the
         frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
+        knots, tdev, K, invdepth, t_ref, H, W = self._event_query("compensate_events()", t_ref, invdepth, radius, weights,
+                                                                  height, width)
+        with torch.no_grad():
+            out = ops.event_warp(self._as_device(x, torch.float32), self._as_device(y, torch.float32),
+                                 self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
+                                 invdepth, H, W, num_bins=num_bins, extrapolate=extrapolate, want_xy=want_xy,
+                                 want_iwe=want_iwe, stack=stack)
+        if as_tensor:
+            return out
+        _check_status("compensate_events()", traj=self._traj_status, interp=out["status"])
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def _event_query(self, name, t_ref, invdepth, radius, weights, height, width):
+        """what the event queries share: the trajectory as it is now, the cached time stamps, the image intrinsics and the
+        inverse depth (None: the median word; ``"map"``: ``invdepth_map`` at the reference pose), read on the stream the
+        state lives on -> (knots, times, K, invdepth, t_ref, height, width)"""
         if not self.tlist:
-            raise RuntimeError("compensate_events(): no frame has been tracked yet")
+            raise RuntimeError(name + ": no frame has been tracked yet")
         if isinstance(invdepth, str):
             if invdepth != "map":
-                raise RuntimeError("compensate_events(): invdepth is None, a number, a tensor or 'map'")
+                raise RuntimeError(name + ": invdepth is None, a number, a tensor or 'map'")
             invdepth = self.invdepth_map(t_ref=t_ref, radius=radius, weights=weights, height=height, width=width,
                                          as_tensor=True)["invdepth"]
         knots, _ = self.trajectory(as_tensor=True)
@@ -232,16 +248,56 @@ class TrackerQueries:
             if invdepth is None:
                 invdepth = self._depth_median_word(sc.resident)
             sc.leaves(K, invdepth)
+        return (knots, tdev, K, invdepth, self.tlist[-1] if t_ref is None else float(t_ref),
+                self.ht if height is None else height, self.wd if width is None else width)
+
+    def event_contrast(self, x, y, t, p, t_ref=None, invdepth=None, correction=None, signed=True, want_grad=True,
+                       want_iwe=False, extrapolate=False, height=None, width=None, as_tensor=False, radius=None,
+                       weights="variance"):
+        """How sharp the compensated events are with the trajectory as it is now: the variance of the image of warped events
+        ``compensate_events`` would return (the same events, poses, intrinsics and inverse depth -- ``invdepth`` as there,
+        ``"map"`` included) and its gradient with respect to a small correction ``(v[3], w[3], lam)`` of velocity, rotation
+        rate and log depth scale in the reference camera frame (``ops.event_contrast``).  The only figure of quality an
+        event tracker can give about its own trajectory without ground truth.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
+        the dict of device tensors of ``ops.event_contrast`` (``variance``, ``stats``, ``sums``, ``status``, ``grad``, ``iwe``
+        as requested), ordered on the current stream, nothing synchronised.  Otherwise numpy arrays (``variance`` a float),
+        which waits for that result and raises when the frames' time stamps decrease or are not finite, or on trajectory()'s
+        unresolved bit."""
+        knots, tdev, K, invdepth, t_ref, H, W = self._event_query("event_contrast()", t_ref, invdepth, radius, weights,
+                                                                  height, width)
         with torch.no_grad():
-            out = ops.event_warp(self._as_device(x, torch.float32), self._as_device(y, torch.float32),
-                                 self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev,
-                                 self.tlist[-1] if t_ref is None else float(t_ref), K, invdepth,
-                                 self.ht if height is None else height, self.wd if width is None else width,
-                                 num_bins=num_bins, extrapolate=extrapolate, want_xy=want_xy, want_iwe=want_iwe, stack=stack)
+            out = ops.event_contrast(self._as_device(x, torch.float32), self._as_device(y, torch.float32),
+                                     self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
+                                     invdepth, H, W, correction=correction, signed=signed, extrapolate=extrapolate,
+                                     want_grad=want_grad, want_iwe=want_iwe)
         if as_tensor:
             return out
-        _check_status("compensate_events()", traj=self._traj_status, interp=out["status"])
-        return {k: v.cpu().numpy() for k, v in out.items()}
+        _check_status("event_contrast()", traj=self._traj_status, interp=out["status"])
+        res = {k: v.cpu().numpy() for k, v in out.items()}
+        res["variance"] = float(res["stats"][0])
+        return res
+
+    def align_events(self, x, y, t, p, t_ref=None, invdepth=None, correction=None, free=(0, 0, 0, 1, 1, 1, 0), step=0.05,
+                     iters=20, signed=True, extrapolate=False, height=None, width=None, radius=None, weights="variance"):
+        """Refine the compensation by contrast maximisation (``ops.event_align``: a host loop of normalised gradient ascent
+        with backtracking over ``event_contrast``, the components ``free`` marks -- by default the rotation rate).  The
+        trajectory, intrinsics and inverse depth are read ONCE, as ``event_contrast`` reads them; every evaluation then reads
+        8 + 7 doubles back, so this is a convenience between two frames, not a hot path.  A device-resident state stays
+        device resident.  Returns ``ops.event_align``'s dict: ``correction``, ``variance``, ``variance0``, ``history``; raises
+        on the conditions ``event_contrast`` raises on."""
+        knots, tdev, K, invdepth, t_ref, H, W = self._event_query("align_events()", t_ref, invdepth, radius, weights,
+                                                                  height, width)
+        with torch.no_grad():
+            out = ops.event_align(self._as_device(x, torch.float32), self._as_device(y, torch.float32),
+                                  self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
+                                  invdepth, H, W, correction=correction, free=free, step=step, iters=iters, signed=signed,
+                                  extrapolate=extrapolate)
+        _check_status("align_events()", traj=self._traj_status)
+        if out["variance0"] != out["variance0"]:              # (NaN: the kernel's answer to bad time stamps)
+            raise RuntimeError("align_events(): the frames' time stamps decrease or are not finite")
+        return out
 
     def _depth_median_word(self, resident):
         """(on the stream the state lives on) the lower median inverse depth of the last three frames' patches as a device
