@@ -161,7 +161,10 @@ int ramp_depth_median_rows(const float *patches_base, const int32_t *n_dev, int 
  * (ramp/utils.py:186-226, 157-183; upstream ~20 ATen launches) for one frame.
  *   events [bins][H][W] float32 (W % 4 == 0); score = mean over bins of the 4x4 average of |events|,
  *   laid out [W/4][H/4]; local maxima of an nms_kernel_size^2 window kept (0 = no NMS);
- *   the k largest cells in descending order (ties: lowest flat index first)
+ *   the k largest cells in descending order, equal cells by lowest flat index first.  The order is exact for any
+ *   number of ties, zeros included (event stacks are small integers: most cells of a quiet scene are equal):
+ *   the cells above the k-th largest value T are all taken, then the cells equal to T in index order until
+ *   there are k; the same input gives the same bits on every call
  *   coords [k][2] float32 = (flat_index / (H/4) as a TRUE division -- x carries y/h, as upstream --,
  *   flat_index % (H/4));  indices [k] int64 flat indices (optional, may be NULL)
  *   ws: ramp_event_topk_workspace_bytes(H, W);  k <= 512                                          */

@@ -55,14 +55,19 @@ __global__ void __launch_bounds__(NMS_T * NMS_T)
   out[(size_t)X * h + Y] = v * (keep ? 1.0f : 0.0f);
 }
 
-// One workgroup: the k largest cells, sorted by (value desc, index asc).
+// One workgroup: the k largest cells, sorted by (value desc, index asc) -- exactly, for any number of ties.
 //   1. one pass over the map compacts the non-zero cells (after NMS: a few hundred local maxima) into
 //      an LDS candidate list; zeros are only counted;
-//   2. the exact k-th largest value is found by 4 x 8-bit MSB radix passes over the float bit
+//   2. the exact k-th largest value T is found by 4 x 8-bit MSB radix passes over the float bit
 //      patterns of the candidates (values are >= 0, so the patterns order like the values); the bin
-//      search is a wave-wide suffix sum over the 256 counters;
-//   3. everything >= the threshold is gathered and bitonic-sorted; if fewer than k cells are
-//      positive the remaining slots take the zero cells of lowest index.
+//      search is a wave-wide suffix sum over the 256 counters.  The passes also leave how many cells
+//      equal to T the result needs (s_remaining) and how many there are (s_ties);
+//   3. the cells > T (fewer than k) are gathered; when the result needs every cell equal to T -- any
+//      tie-free map -- those are gathered with them.  Otherwise (event stacks are small integers: many
+//      equal cells; T == 0: fewer than k positive cells) the s_remaining cells equal to T of lowest
+//      index are taken by an index-ordered count and scan over the map, so neither the number of ties
+//      nor the order in which atomics hand out slots decides which cells are selected;
+//   4. the k gathered composite keys (value, ~index) are bitonic-sorted.
 // A map with more non-zero cells than the list holds (no NMS, dense events) streams the map from
 // memory in every pass instead.
 #define TOPK_THREADS 1024
@@ -72,14 +77,14 @@ __global__ void __launch_bounds__(TOPK_THREADS)
     topk_coords_kernel(const float *__restrict__ vals, int N, int k, int hh, float *__restrict__ coords,
                        int64_t *__restrict__ idx_out) {
   __shared__ unsigned hist[256];
-  __shared__ unsigned s_prefix, s_remaining, s_count, s_ncand;
+  __shared__ unsigned s_prefix, s_remaining, s_ties, s_count, s_ncand;
   __shared__ unsigned cand_key[TOPK_CAP], cand_idx[TOPK_CAP];
-  __shared__ unsigned long long sel[2 * TOPK_MAXK];
+  __shared__ unsigned long long sel[TOPK_MAXK];
   __shared__ unsigned s_scan[TOPK_THREADS];
   const int tid = threadIdx.x;
   const unsigned *keys = reinterpret_cast<const unsigned *>(vals);
-  if (tid == 0) { s_prefix = 0; s_remaining = (unsigned)k; s_count = 0; s_ncand = 0; }
-  for (int i = tid; i < 2 * TOPK_MAXK; i += TOPK_THREADS) sel[i] = 0ull;
+  if (tid == 0) { s_prefix = 0; s_remaining = (unsigned)k; s_ties = 0; s_count = 0; s_ncand = 0; }
+  for (int i = tid; i < TOPK_MAXK; i += TOPK_THREADS) sel[i] = 0ull;
   __syncthreads();
   for (int i0 = tid; i0 < N; i0 += 4 * TOPK_THREADS) {
     unsigned kv[4];
@@ -126,37 +131,41 @@ __global__ void __launch_bounds__(TOPK_THREADS)
       }
       const unsigned rem = s_remaining, above = suf - tot;
       if (above < rem && suf >= rem) {
-        unsigned rr = rem - above;
+        unsigned rr = rem - above, in_bin = c[0];
         int bin = 4 * tid;
 #pragma unroll
         for (int b = 3; b >= 0; b--) {
-          if (c[b] >= rr) { bin = 4 * tid + b; break; }
+          if (c[b] >= rr) { bin = 4 * tid + b; in_bin = c[b]; break; }
           rr -= c[b];
         }
         s_remaining = rr;
+        s_ties = in_bin;                     // after the last pass: the cells equal to the threshold
         s_prefix = prefix | ((unsigned)bin << shift);
       }
     }
     mask |= 255u << shift;
     __syncthreads();
   }
-  const unsigned T = s_prefix;
-  // gather: T > 0: everything >= T (ties are ordered by the sort); T == 0: every positive cell
+  const unsigned T = s_prefix, need = s_remaining;
+  // the result is the cells > T and `need` of the s_ties cells == T.  All of them (every tie-free map): one gather
+  // takes both, and the slots the atomics hand out do not matter, because the sort orders whatever was gathered
+  const bool all_ties = T != 0 && s_ties == need;
   for (int i = tid; i < M; i += TOPK_THREADS) {
     TOPK_ITEM(i, key, idx)
-    if (key != 0 && key >= T) {
+    if (key > T || (all_ties && key == T)) {
       const unsigned pos = atomicAdd(&s_count, 1u);
-      if (pos < 2u * TOPK_MAXK) sel[pos] = ((unsigned long long)key << 32) | (0xffffffffu - idx);
+      if (pos < (unsigned)TOPK_MAXK) sel[pos] = ((unsigned long long)key << 32) | (0xffffffffu - idx);
     }
   }
   __syncthreads();
-  if (T == 0) {
-    // fewer than k positive cells: the zero cells of lowest index fill up (index-ordered scan of the map)
-    const unsigned ngt = s_count, need = (unsigned)k - min((unsigned)k, ngt);
+  if (!all_ties) {
+    // more cells equal T than the result needs (T == 0: the zero cells fill up): the `need` of lowest index, by an
+    // index-ordered count and scan of the map.  s_count == k - need cells lie above T
+    const unsigned ngt = s_count;
     const int chunk = (N + TOPK_THREADS - 1) / TOPK_THREADS;
     const int i0 = tid * chunk, i1 = min(N, i0 + chunk);
     unsigned cnt = 0;
-    for (int i = i0; i < i1; i++) cnt += (keys[i] == 0);
+    for (int i = i0; i < i1; i++) cnt += (keys[i] == T);
     s_scan[tid] = cnt;
     __syncthreads();
     for (int off = 1; off < TOPK_THREADS; off <<= 1) {
@@ -167,18 +176,17 @@ __global__ void __launch_bounds__(TOPK_THREADS)
     }
     unsigned rank = s_scan[tid] - cnt;
     for (int i = i0; i < i1 && rank < need; i++) {
-      if (keys[i] == 0) {
+      if (keys[i] == T) {
         const unsigned pos = ngt + rank;
-        if (pos < 2u * TOPK_MAXK) sel[pos] = (unsigned long long)(0xffffffffu - (unsigned)i);
+        if (pos < (unsigned)TOPK_MAXK) sel[pos] = ((unsigned long long)T << 32) | (0xffffffffu - (unsigned)i);
         rank++;
       }
     }
     __syncthreads();
   }
-  // bitonic sort, descending, of the gathered composite keys (unused slots are 0 = smallest)
-  const unsigned gathered = T == 0 ? (unsigned)k : min(s_count, 2u * TOPK_MAXK);
+  // bitonic sort, descending, of the k gathered composite keys (unused slots are 0 = smallest)
   int KP = 64;
-  while (KP < (int)gathered) KP <<= 1;
+  while (KP < k) KP <<= 1;
   for (int size = 2; size <= KP; size <<= 1) {
     for (int stride = size >> 1; stride > 0; stride >>= 1) {
       for (int t = tid; t < KP / 2; t += TOPK_THREADS) {
