@@ -1189,6 +1189,62 @@ int ramp_event_contrast(const float *x, const float *y, const double *t, const i
                         const float *correction, int flags, int H, int W, float *iwe, int64_t *sums, double *stats, double *grad,
                         void *ws, size_t ws_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------- event voxel grids (csrc/voxel.hip)
+ *
+ * ramp_event_voxel: the reference's "voxels" event representation (utils/transformers.py:21-125,
+ * EventSequenceToVoxelGrid_Pytorch) for S slices of one event list in one call: every event votes into the two time bins next
+ * to its normalised time stamp with linear weights, and the grid of a slice is standardised over its non-zero cells.
+ *   events: x, y [N] fp32 pixel coordinates, t [N] float64, p [N] int8 polarity (0 is read as -1), as ramp_event_warp.
+ *   offsets: DEVICE int64 [S + 1], never read by the host: slice s is the events [offsets[s], offsets[s + 1]); NULL with
+ *   S == 1: one slice [0, N).  An empty slice gives an all-zero grid and a stats row of zeros.
+ *   Votes, per slice (float64 up to ti, fp32 behind it, no FMA):
+ *     t_first, t_last = the time stamps of the slice's first and last event BY POSITION (not min / max)
+ *     deltaT = t_last - t_first, and 1.0 when that is 0
+ *     tn  = ((bins - 1) * (t - t_first)) / deltaT              in this order
+ *     ti  = floor(tn),   dts = float32(tn - ti)
+ *     pol * (1.0f - dts) -> bin ti       when 0 <= ti < bins
+ *     pol * dts          -> bin ti + 1   when 0 <= ti and ti + 1 < bins          (bins == 1: pol into bin 0)
+ *   Pixels: the coordinate truncated toward zero (the reference's .long()); unlike the reference, which does not check, an
+ *   event whose pixel lies outside the image is dropped and counted.  RAMP_VOXEL_SUBPIXEL: the two neighbours per axis of
+ *   ramp_event_warp's scatter (floor, weights 1 - w and w, neighbours outside the image dropped); a neighbour's share of a
+ *   vote v is (wx * wy) * v, two fp32 products in this order.  A NaN coordinate row -- what ramp_event_warp writes to xy_out
+ *   for an invalid event -- is skipped and counted.  Integer-valued coordinates give the default mode's bits and words (a
+ *   neighbour of weight zero does not make a pixel).
+ *   Accumulation: FIXED POINT, llrint(ldexp(value, 24)) added with 64-bit INTEGER atomics into int64 accumulators
+ *   [slices][bins][H][W]: the sums do not depend on the events' order, a call repeats its bits.  No float atomics.
+ *   grid [S][bins][H][W] fp32: float(sum) * 2^-24 (rounds once), or with RAMP_VOXEL_NORMALIZE, over the n cells with sum != 0:
+ *     mean = (the exact integer sum of those sums) / (n * 2^24)                        float64
+ *     var  = sum((acc * 2^-24 - mean)^2) / (n - 1)     float64, per-workgroup partials in an order fixed by (bins, H, W)
+ *     cell = float32((acc * 2^-24 - mean) / std) where std = sqrt(var) > 0, float32(acc * 2^-24 - mean) otherwise -- n == 1
+ *     included, whose unbiased std is NaN, as in torch.  Cells with sum == 0 stay 0; n == 0 leaves the grid as it is.
+ *   stats float64 [S][4], in every mode: n, mean, std, the sum of the non-zero cells (n == 0: zeros; n == 1: std NaN).
+ *   status: device int32 [8], written by the call, summed over all slices: [0] bits (RAMP_VOXEL_BAD_OFFSETS: an offset is
+ *   negative, exceeds N or decreases; RAMP_VOXEL_BAD_TIMES: the first or last time stamp of a non-empty slice is not
+ *   finite), [1] events seen (those of the slices), [2] events with a coordinate or time stamp that is not finite, [3] finite
+ *   events whose pixel lies outside the image, [4] events inside it without a vote (ti outside [0, bins), every event of a
+ *   slice that fails its time check), [5] events that voted, [6], [7] 0.  [2] + [3] + [4] + [5] = [1].
+ *   Failures, never a plausible number (RAMP_OK: outcomes of the data): RAMP_VOXEL_BAD_OFFSETS makes every grid and stats
+ *   value NaN and no event is read ([1] - [5] are 0); RAMP_VOXEL_BAD_TIMES makes the grid and the stats row of that slice NaN.
+ *   ws: 16-byte aligned.  ramp_event_voxel_workspace_bytes(s, bins, H, W) holds s slices at once; the entry works through the
+ *   slices in chunks of as many as ws_bytes holds (at most 32768) and the result does not depend on the chunking; less than
+ *   one slice's worth: RAMP_EWORKSPACE.  Launches per chunk: one hipMemsetAsync and four kernels (vote, count, spread, finish;
+ *   no vote with N == 0), and once per call the check of the offsets; all on `stream`, nothing synchronised.
+ *   N < 0, S, bins, H or W < 1, unknown flags, NULL offsets with S != 1, a NULL grid / stats / status / ws, NULL events with
+ *   N > 0, stats or offsets not 8-byte aligned: RAMP_EINVAL.  bins * H * W >= 2^31: RAMP_EUNSUPPORTED.
+ * ramp_event_voxel_grid_events(): the number of events one trip of the full vote grid covers; above it the workgroups take a
+ * second trip.  ramp_event_voxel_lds_offsets(): the number of offsets of a chunk the vote launch stages in LDS; a chunk with
+ * more searches them in global memory.                                                                                */
+#define RAMP_VOXEL_NORMALIZE 1
+#define RAMP_VOXEL_SUBPIXEL 2
+#define RAMP_VOXEL_BAD_OFFSETS 1 /* status[0] bit 0 */
+#define RAMP_VOXEL_BAD_TIMES 2   /* status[0] bit 1 */
+size_t ramp_event_voxel_workspace_bytes(int slices, int bins, int H, int W);
+long ramp_event_voxel_grid_events(void);
+int ramp_event_voxel_lds_offsets(void);
+int ramp_event_voxel(const float *x, const float *y, const double *t, const int8_t *p, long N, const int64_t *offsets, int S,
+                     int bins, int H, int W, int flags, float *grid, double *stats, int32_t *status, void *ws, size_t ws_bytes,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

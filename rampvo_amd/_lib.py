@@ -25,6 +25,7 @@ RAMP_INTERP_EXTRAPOLATE, RAMP_INTERP_ROW_STORES, RAMP_INTERP_BAD_TIMES = 1, 2, 1
 RAMP_WARP_DEPTH_SCALAR, RAMP_WARP_DEPTH_MAP, RAMP_WARP_IDENTITY, RAMP_WARP_MIN_Z = 0, 4, 8, 0.2
 RAMP_DEPTHMAP_CONF_IS_VARIANCE, RAMP_DEPTHMAP_PRIOR_RELATIVE, RAMP_DEPTHMAP_BAD_CAM = 1, 2, 1
 RAMP_CONTRAST_UNSIGNED, RAMP_CONTRAST_BAD_CORRECTION = 16, 2
+RAMP_VOXEL_NORMALIZE, RAMP_VOXEL_SUBPIXEL, RAMP_VOXEL_BAD_OFFSETS, RAMP_VOXEL_BAD_TIMES = 1, 2, 1, 2
 KPLANE = 32            # channels per plane of the packed correlation target maps: [h][128 / KPLANE][w][KPLANE]
 
 
@@ -195,6 +196,11 @@ SIGNATURES = {
     "ramp_event_contrast_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "ramp_event_contrast": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, ctypes.c_double, c_p, c_p, c_p, c_i, c_i, c_i,
                                   c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
+    # event voxel grids (csrc/voxel.hip)
+    "ramp_event_voxel_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
+    "ramp_event_voxel_grid_events": (ctypes.c_long, []),
+    "ramp_event_voxel_lds_offsets": (c_i, []),
+    "ramp_event_voxel": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_long, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
 }
 
 _lib = None

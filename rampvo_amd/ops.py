@@ -283,6 +283,73 @@ def event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height
     return res
 
 
+VOXEL_WORKSPACE_CAP = 256 << 20      # bytes: ramp_event_voxel works through more slices than this holds in chunks
+
+
+def event_slices(n_events, count, device="cuda"):
+    """the loader's slicing of an event file (reference evaluate.py:117-135): offsets ``0, count, 2 count, ...`` of the
+    ``n_events // count`` full slices as a device int64 tensor -- the last partial slice is dropped, as upstream drops it"""
+    if count < 1:
+        raise RuntimeError("event_slices: count is positive")
+    return torch.arange(0, (n_events // count) * count + 1, count, dtype=torch.int64, device=device)
+
+
+def event_voxel_grid(x, y, t, p, height, width, num_bins=5, offsets=None, normalize=True, subpixel=False):
+    """EventSequenceToVoxelGrid_Pytorch on the device (reference utils/transformers.py:21-125; include/ramp_hip.h
+    ``ramp_event_voxel``), for many slices of an event list in one call: every event votes into the two time bins next to its
+    normalised time stamp with linear weights, and with ``normalize`` each slice's grid is standardised over its non-zero
+    cells (mean, unbiased std).
+
+    ``x, y`` [N] pixel coordinates, ``t`` [N] float64, ``p`` [N] polarity (+-1; 0 is read as -1).  ``offsets``: None -- one
+    slice, all events -- or a device int64 tensor [S + 1] (``event_slices``): slice s is the events ``[offsets[s],
+    offsets[s + 1])``; the host never reads it.  The pixel is the coordinate truncated toward zero; ``subpixel=True`` splats
+    bilinearly instead and skips NaN rows, so the ``xy`` of ``event_warp(want_xy=True)`` can be passed straight in
+    (``x=xy[:, 0], y=xy[:, 1]``): a motion-compensated voxel grid.  Unlike the reference, an event outside the image is
+    dropped and counted, and an empty slice gives an all-zero grid.
+
+    Returns a dict of device tensors: ``grid`` [S, num_bins, height, width] float32 ([num_bins, height, width] when
+    ``offsets`` is None -- the shape the net takes as ``events[None, None]``), ``stats`` float64 [S, 4] (per slice: the number
+    of non-zero cells, their mean, their std, their sum) and ``status`` int32 [8] (``event_voxel_status``).  Runs on the
+    current stream, nothing is synchronised.  The sums are fixed point over integer atomics: the same bits for any order of
+    the events (the first and last of a slice define its time range) and any chunking.  Bad offsets make everything NaN, a
+    slice whose first or last time stamp is not finite is NaN: never a plausible number."""
+    require_cuda(x, y, t, p, offsets)
+    dev = x.device
+    xf, yf = x.reshape(-1).to(torch.float32).contiguous(), y.reshape(-1).to(torch.float32).contiguous()
+    tf = t.reshape(-1).to(torch.float64).contiguous()
+    pi = p.reshape(-1).to(torch.int8)
+    pi = torch.where(pi == 0, torch.full_like(pi, -1), pi).contiguous()
+    N = xf.shape[0]
+    if not (yf.shape[0] == N and tf.shape[0] == N and pi.shape[0] == N):
+        raise RuntimeError("event_voxel_grid: x, y, t and p differ in length")
+    if num_bins < 1 or height < 1 or width < 1:
+        raise RuntimeError("event_voxel_grid: num_bins, height and width are positive")
+    if offsets is None:
+        S, off = 1, None
+    else:
+        off = offsets.reshape(-1).to(torch.int64).contiguous()
+        S = off.shape[0] - 1
+        if S < 1:
+            raise RuntimeError("event_voxel_grid: offsets holds at least two entries")
+    flags = (_lib.RAMP_VOXEL_NORMALIZE if normalize else 0) | (_lib.RAMP_VOXEL_SUBPIXEL if subpixel else 0)
+    grid = torch.empty((S, num_bins, height, width), dtype=torch.float32, device=dev)
+    res = {"grid": grid if offsets is not None else grid[0], "stats": torch.empty((S, 4), dtype=torch.float64, device=dev),
+           "status": torch.empty(8, dtype=torch.int32, device=dev)}
+    one = lib().ramp_event_voxel_workspace_bytes(1, num_bins, height, width)
+    nbytes = min(lib().ramp_event_voxel_workspace_bytes(S, num_bins, height, width), max(one, VOXEL_WORKSPACE_CAP))
+    ws = _lib_workspace(nbytes, dev, "evvoxel")
+    check(lib().ramp_event_voxel(ptr(xf), ptr(yf), ptr(tf), ptr(pi), N, ptr(off), S, num_bins, height, width, flags, ptr(grid),
+                                 ptr(res["stats"]), ptr(res["status"]), ptr(ws), nbytes, stream()), "ramp_event_voxel")
+    return res
+
+
+def event_voxel_status(status):
+    """the status words of ramp_event_voxel as a dict (synchronises: one 32-byte copy)"""
+    w = status.detach().cpu()
+    return dict(bad_offsets=bool(int(w[0]) & _lib.RAMP_VOXEL_BAD_OFFSETS), bad_times=bool(int(w[0]) & _lib.RAMP_VOXEL_BAD_TIMES),
+                n_events=int(w[1]), n_not_finite=int(w[2]), n_outside=int(w[3]), n_no_bin=int(w[4]), n_contributed=int(w[5]))
+
+
 def align_loop(evaluate, correction, free, step, iters):
     """the line search of ``event_align`` over ``evaluate(theta) -> (variance, grad)``: normalised gradient ascent with
     backtracking.  The direction is the gradient masked by ``free``, divided by its norm; the step length starts at ``step``,

@@ -54,12 +54,14 @@ class StateStream:
                 self.leaves(*(x.values() if isinstance(x, dict) else x))
 
 
-def _check_status(name, traj=None, interp=None, cam=None):
+def _check_status(name, traj=None, interp=None, cam=None, voxel=None):
     """The closing check of a query's numpy form -- its one wait.  Each argument is a device status tensor or None (not part
     of this query): ``traj`` trajectory()'s word, ``interp`` the words of ops.se3_interp or ops.event_warp (bit 0 of word 0:
-    the frames' time stamps), ``cam`` those of ops.invdepth_map (bit 0 of word 0: the camera pose).  Word 0 of each goes to
-    the host in one copy; raises in this order: unresolved delta chain, bad time stamps, camera pose."""
-    given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam)) if s is not None]
+    the frames' time stamps), ``cam`` those of ops.invdepth_map (bit 0 of word 0: the camera pose), ``voxel`` those of
+    ops.event_voxel_grid (bits 0 and 1 of word 0: the offsets, a slice's own time stamps).  Word 0 of each goes to the host
+    in one copy; raises in this order: unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times."""
+    given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam), ("voxel", voxel))
+             if s is not None]
     if not given:
         return
     first = given[0][1] if len(given) == 1 else torch.cat([s for _, s in given])
@@ -70,6 +72,10 @@ def _check_status(name, traj=None, interp=None, cam=None):
         raise RuntimeError(name + ": the frames' time stamps decrease or are not finite")
     if word.get("cam", 0) & 1:
         raise RuntimeError(name + ": the camera pose at t_ref is not finite")
+    if word.get("voxel", 0) & _lib.RAMP_VOXEL_BAD_OFFSETS:
+        raise RuntimeError(name + ": the slice offsets decrease or leave the event list")
+    if word.get("voxel", 0) & _lib.RAMP_VOXEL_BAD_TIMES:
+        raise RuntimeError(name + ": the first or last time stamp of a slice is not finite")
 
 
 def _dof_sigma0(s):
@@ -81,7 +87,7 @@ def _dof_sigma0(s):
 class TrackerQueries:
     """the query surface of ``Ramp_vo`` (a mixin: it reads the tracker's buffers, streams and host mirror as they are)"""
 
-    _NUMPY = {torch.float32: np.float32, torch.float64: np.float64, torch.int8: np.int8}
+    _NUMPY = {torch.float32: np.float32, torch.float64: np.float64, torch.int8: np.int8, torch.int64: np.int64}
 
     def _state_stream(self, inputs=()):
         return StateStream(self, inputs)
@@ -298,6 +304,44 @@ class TrackerQueries:
         if out["variance0"] != out["variance0"]:              # (NaN: the kernel's answer to bad time stamps)
             raise RuntimeError("align_events(): the frames' time stamps decrease or are not finite")
         return out
+
+    def event_voxel_grid(self, x, y, t, p, num_bins=5, offsets=None, normalize=True, compensate=False, t_ref=None,
+                         invdepth=None, as_tensor=False, extrapolate=False, radius=None, weights="variance"):
+        """The reference's voxel-grid event representation at the tracker's image size (``ops.event_voxel_grid``: every event
+        votes into the two time bins next to its normalised time stamp, each slice standardised over its non-zero cells):
+        ``grid`` [S, num_bins, ht, wd] for the slices ``offsets`` (a device int64 tensor [S + 1], ``ops.event_slices``) marks,
+        or [num_bins, ht, wd] for all events as one slice -- the shape the net takes as ``events[None, None]``.
+
+        ``compensate=True``: a MOTION-COMPENSATED voxel grid.  The events are first warped to the camera pose at ``t_ref``
+        with the trajectory as it is now (``compensate_events(want_xy=True, want_iwe=False, as_tensor=True)``; ``t_ref``,
+        ``invdepth``, ``extrapolate``, ``radius`` and ``weights`` are read in this mode only, as there) and their sub-pixel
+        coordinates are splat bilinearly; the events the warp rejects are NaN rows, which the grid skips and counts.  The time
+        bins are those of the events' own time stamps.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
+        the dict of device tensors of ``ops.event_voxel_grid`` (``grid``, ``stats``, ``status``; with ``compensate`` also
+        ``warp_status``, the words of ``ops.event_warp``), ordered on the current stream, nothing synchronised.  Otherwise
+        numpy arrays, which waits for that result and raises on offsets that decrease or leave the event list, on a slice
+        whose first or last time stamp is not finite and, with ``compensate``, on the conditions ``compensate_events`` raises
+        on."""
+        xd, yd = self._as_device(x, torch.float32), self._as_device(y, torch.float32)
+        td, pd = self._as_device(t, torch.float64), self._as_device(p, torch.int8)
+        warp = None
+        if compensate:
+            warp = self.compensate_events(xd, yd, td, pd, t_ref=t_ref, invdepth=invdepth, extrapolate=extrapolate, want_xy=True,
+                                          want_iwe=False, as_tensor=True, radius=radius, weights=weights)
+            xd, yd = warp["xy"][:, 0], warp["xy"][:, 1]
+        with torch.no_grad():
+            out = ops.event_voxel_grid(xd, yd, td, pd, self.ht, self.wd, num_bins=num_bins,
+                                       offsets=None if offsets is None else self._as_device(offsets, torch.int64),
+                                       normalize=normalize, subpixel=compensate)
+        if compensate:
+            out["warp_status"] = warp["status"]
+        if as_tensor:
+            return out
+        _check_status("event_voxel_grid()", traj=self._traj_status if compensate else None, interp=out.get("warp_status"),
+                      voxel=out["status"])
+        return {k: v.cpu().numpy() for k, v in out.items()}
 
     def _depth_median_word(self, resident):
         """(on the stream the state lives on) the lower median inverse depth of the last three frames' patches as a device
