@@ -1245,6 +1245,89 @@ int ramp_event_voxel(const float *x, const float *y, const double *t, const int8
                      int bins, int H, int W, int flags, float *grid, double *stats, int32_t *status, void *ws, size_t ws_bytes,
                      void *stream);
 
+/* ---------------------------------------------------------------- lens distortion (csrc/rectify.hip)
+ *
+ * The event kernels above model the camera as a pinhole (fx, fy, cx, cy).  These two entries stand between a real sensor and
+ * them: ramp_event_rectify takes raw events to sub-pixel coordinates of a rectified pinhole camera (the xy format
+ * ramp_event_voxel's RAMP_VOXEL_SUBPIXEL and ramp_event_warp accept, NaN rows included), ramp_image_rectify resamples a raw
+ * frame into the same camera.
+ *   camera: DEVICE float [RAMP_CAMERA_WORDS], never read by the host, 4-byte aligned:
+ *     [RAMP_CAMERA_RAW .. +3]        the raw intrinsics fx, fy, cx, cy
+ *     [RAMP_CAMERA_MODEL]            RAMP_CAM_PINHOLE, RAMP_CAM_RADTAN or RAMP_CAM_EQUIDISTANT, as a float
+ *     [RAMP_CAMERA_COEFFS .. +4]     radtan: k1, k2, p1, p2, k3 (OpenCV's order); equidistant: k1 .. k4, 0; pinhole: not used
+ *     [RAMP_CAMERA_ROTATION .. +8]   R [3][3] row-major, raw camera -> rectified camera; a caller without one writes the identity
+ *     [RAMP_CAMERA_NEW .. +3]        the rectified intrinsics fx', fy', cx', cy'
+ *     every other word 0.
+ *   Models, (x, y) the normalised raw ray, all arithmetic fp32 without FMA:
+ *     RAMP_CAM_PINHOLE       (xd, yd) = (x, y)
+ *     RAMP_CAM_RADTAN        r2 = x^2 + y^2,  rad = 1 + r2 (k1 + r2 (k2 + r2 k3))
+ *                            xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2),   yd = y rad + p1 (r2 + 2 y^2) + 2 p2 x y
+ *     RAMP_CAM_EQUIDISTANT   (Kalibr "equidistant", OpenCV fisheye)  r = sqrt(x^2 + y^2),  th = atan(r),
+ *                            thd = th (1 + th^2 (k1 + th^2 (k2 + th^2 (k3 + th^2 k4)))),  (xd, yd) = (thd / r)(x, y); r == 0: (x, y)
+ * ramp_event_rectify: x, y [N] fp32 pixels of the raw sensor, or int32 with RAMP_RECTIFY_XY_I32 (converted to fp32; integer-
+ *   valued floats give the same bits).  Per event, one lane:
+ *     (xd, yd) = ((x - cx) / fx, (y - cy) / fy)
+ *     the model is inverted with exactly RAMP_RECTIFY_ITERS Newton steps -- no data-dependent trip count:
+ *       radtan: 2-D Newton with the analytic Jacobian J (symmetric), from (xd, yd): p <- p - J^-1 (distort(p) - (xd, yd))
+ *       equidistant: thd = sqrt(xd^2 + yd^2); 1-D Newton on th from thd; (x, y) = (tan th / thd)(xd, yd), thd == 0: (xd, yd)
+ *     the solution is ACCEPTED only when every iterate is finite, det J (d thd / d th) > 0 at the start and at every iterate
+ *     (a hop across the fold of a strongly distorting polynomial is rejected, never returned), the final residual
+ *     |distort(p) - (xd, yd)| in raw pixels (the components times fx, fy; equidistant: |thd(th) - thd| max(fx, fy)) is
+ *     <= RAMP_RECTIFY_TOL, and for the equidistant model 0 <= th < pi / 2
+ *     X = R (x, y, 1);   x' = fx' X / Z + cx',  y' = fy' Y / Z + cy'
+ *   xy_out [N][2] fp32, 8-byte aligned; valid_out [N] uint8 (optional, NULL).  An event that is not valid gets a NaN row and 0.
+ *   status: device int32 [8], written by the call: [0] bits (RAMP_RECTIFY_BAD_CAMERA: a word of the record is not finite, the
+ *   model is unknown, or fx, fy, fx' or fy' is <= 0), [1] events, [2] x or y not finite, [3] not invertible, [4] behind
+ *   (Z <= 0 or NaN, or a projection that is not finite), [5] valid but outside [0, W - 1] x [0, H - 1] -- the coordinates are
+ *   still written -- [6] valid and inside, [7] 0.  [2] + [3] + [4] + [5] + [6] = [1].  RAMP_RECTIFY_BAD_CAMERA makes every row
+ *   NaN; the finite events are then counted in [3].  Outcomes of the data: RAMP_OK.
+ *   A row is a function of its own event and the record alone: its bits depend neither on N, nor on its position, nor on the
+ *   order of the events, and a call repeats its bits.  One kernel behind one 32-byte hipMemsetAsync on `stream`, nothing
+ *   synchronised.  N == 0: RAMP_OK, nothing is launched and nothing written.  N < 0, H or W < 1, unknown flags, a NULL x / y /
+ *   camera / xy_out / status, xy_out not 8-byte aligned: RAMP_EINVAL.
+ *   ramp_event_rectify_grid_events(): the number of events one trip of the full grid covers; above it the workgroups take a
+ *   second trip.
+ * ramp_image_rectify: the forward direction, closed form.  src [C][Hs][Ws] fp32, or uint8 with RAMP_RECTIFY_SRC_U8; out
+ *   [C][H][W] fp32, the rectified camera's image.  Per output pixel (u, v), one lane for all channels:
+ *     ray = R^T ((u - cx') / fx', (v - cy') / fy', 1);  (x, y) = (X / Z, Y / Z);  (xd, yd) = distort(x, y)
+ *     xs = fx xd + cx,  ys = fy yd + cy
+ *   The pixel is SAMPLED when Z > 0, det J (d thd / d th) > 0 at the ray, xs and ys are finite, and 0 <= xs <= Ws - 1,
+ *   0 <= ys <= Hs - 1; with x0 = floor(xs), wx = xs - x0 (y likewise) and a, b, c, d the source at (x0, y0), (x0 + 1, y0),
+ *   (x0, y0 + 1), (x0 + 1, y0 + 1) -- an index past the last row or column is clamped, its weight is then exactly 0:
+ *     top = (1 - wx) a + wx b,  bot = (1 - wx) c + wx d,  val = (1 - wy) top + wy bot       fp32, every product and sum rounded
+ *   norm: RAMP_RECTIFY_NORM_NONE val; _HALF 2 (val / 255) - 0.5; _UNIT 2 (val / 255) - 1 (the two branches of the reference's
+ *   normalize_image, ramp/utils.py:573-583; a correctly rounded fp32 division).  Any other pixel gets `fill` in every channel.
+ *   map_out [H][W][2] fp32 (optional, 8-byte aligned): (xs, ys), NaN where the pixel is not sampled; mask_out [H][W] uint8
+ *   (optional): 1 where sampled.
+ *   status: device int32 [8]: [0] bits (RAMP_RECTIFY_BAD_CAMERA: every pixel is `fill` and counted in [2]), [1] pixels, [2] not
+ *   sampled by the fold, a ray behind the camera or coordinates that are not finite, [3] outside the source, [4] sampled,
+ *   [5] - [7] 0.  [2] + [3] + [4] = [1].  One kernel behind one 32-byte hipMemsetAsync on `stream`, nothing synchronised; a
+ *   pixel's bits depend on its own coordinates, the record and the source alone.
+ *   C, Hs, Ws, H or W < 1, unknown flags or norm, a NULL src / camera / out / status, a misaligned map_out: RAMP_EINVAL; H W or
+ *   Hs Ws >= 2^31: RAMP_EUNSUPPORTED.                                                                                  */
+#define RAMP_CAMERA_WORDS 32
+#define RAMP_CAMERA_RAW 0
+#define RAMP_CAMERA_MODEL 4
+#define RAMP_CAMERA_COEFFS 5
+#define RAMP_CAMERA_ROTATION 12
+#define RAMP_CAMERA_NEW 24
+#define RAMP_CAM_PINHOLE 0
+#define RAMP_CAM_RADTAN 1
+#define RAMP_CAM_EQUIDISTANT 2
+#define RAMP_RECTIFY_ITERS 8
+#define RAMP_RECTIFY_TOL 0.015625f /* 2^-6 raw pixels */
+#define RAMP_RECTIFY_XY_I32 1
+#define RAMP_RECTIFY_SRC_U8 2
+#define RAMP_RECTIFY_NORM_NONE 0
+#define RAMP_RECTIFY_NORM_HALF 1
+#define RAMP_RECTIFY_NORM_UNIT 2
+#define RAMP_RECTIFY_BAD_CAMERA 1 /* status[0] bit 0 */
+long ramp_event_rectify_grid_events(void);
+int ramp_event_rectify(const void *x, const void *y, long N, const float *camera, int flags, int H, int W, float *xy_out,
+                       uint8_t *valid_out, int32_t *status, void *stream);
+int ramp_image_rectify(const void *src, int C, int Hs, int Ws, const float *camera, int flags, int norm, float fill, int H, int W,
+                       float *out, float *map_out, uint8_t *mask_out, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

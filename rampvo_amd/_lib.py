@@ -26,6 +26,12 @@ RAMP_WARP_DEPTH_SCALAR, RAMP_WARP_DEPTH_MAP, RAMP_WARP_IDENTITY, RAMP_WARP_MIN_Z
 RAMP_DEPTHMAP_CONF_IS_VARIANCE, RAMP_DEPTHMAP_PRIOR_RELATIVE, RAMP_DEPTHMAP_BAD_CAM = 1, 2, 1
 RAMP_CONTRAST_UNSIGNED, RAMP_CONTRAST_BAD_CORRECTION = 16, 2
 RAMP_VOXEL_NORMALIZE, RAMP_VOXEL_SUBPIXEL, RAMP_VOXEL_BAD_OFFSETS, RAMP_VOXEL_BAD_TIMES = 1, 2, 1, 2
+# the camera record of csrc/rectify.hip: word offsets, models, flags, value modes
+RAMP_CAMERA_WORDS, RAMP_CAMERA_RAW, RAMP_CAMERA_MODEL, RAMP_CAMERA_COEFFS, RAMP_CAMERA_ROTATION, RAMP_CAMERA_NEW = 32, 0, 4, 5, 12, 24
+RAMP_CAM_PINHOLE, RAMP_CAM_RADTAN, RAMP_CAM_EQUIDISTANT = 0, 1, 2
+RAMP_RECTIFY_ITERS, RAMP_RECTIFY_TOL = 8, 2.0 ** -6
+RAMP_RECTIFY_XY_I32, RAMP_RECTIFY_SRC_U8, RAMP_RECTIFY_BAD_CAMERA = 1, 2, 1
+RAMP_RECTIFY_NORM_NONE, RAMP_RECTIFY_NORM_HALF, RAMP_RECTIFY_NORM_UNIT = 0, 1, 2
 KPLANE = 32            # channels per plane of the packed correlation target maps: [h][128 / KPLANE][w][KPLANE]
 
 
@@ -201,6 +207,10 @@ SIGNATURES = {
     "ramp_event_voxel_grid_events": (ctypes.c_long, []),
     "ramp_event_voxel_lds_offsets": (c_i, []),
     "ramp_event_voxel": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_long, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
+    # lens distortion (csrc/rectify.hip)
+    "ramp_event_rectify_grid_events": (ctypes.c_long, []),
+    "ramp_event_rectify": (c_i, [c_p, c_p, ctypes.c_long, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "ramp_image_rectify": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
 }
 
 _lib = None

@@ -39,6 +39,35 @@ class Trajectory:
         return len(self.timestamps)
 
 
+KALIBR_MODELS = {"none": "pinhole", "pinhole": "pinhole", "radtan": "radtan", "plumb_bob": "radtan", "equidistant": "equidistant"}
+
+
+def camera_from_kalibr(data, cam="cam0", resize_to=None):
+    """The camera of a Kalibr cam-chain, from the PARSED file (``yaml.safe_load``'s dict; this function imports no yaml): the
+    reference reads ``intrinsics`` and ``resolution`` from it (evaluate.py:44-70) and ignores ``distortion_model`` and
+    ``distortion_coeffs``, which ``Ramp_vo.set_camera`` / ``ops.camera`` take.  ``resize_to`` (width, height): the
+    principal-point shift of the reference's ``set_global_params`` for an image padded or cropped about its centre,
+    ``c += (resize_to - resolution) / 2``.  Returns a dict ``model``, ``raw_intrinsics`` (fx, fy, cx, cy), ``coeffs``,
+    ``resolution`` (width, height) -- ``slam.set_camera(**{k: c[k] for k in ("model", "raw_intrinsics", "coeffs")})``.
+    Raises ``ValueError`` on a distortion model this package has no kernel for."""
+    entry = data[cam]
+    name = str(entry.get("distortion_model", "none")).lower()
+    if name not in KALIBR_MODELS:
+        raise ValueError("camera_from_kalibr: unknown distortion model %r (known: %s)" % (name, ", ".join(sorted(KALIBR_MODELS))))
+    if str(entry.get("camera_model", "pinhole")).lower() != "pinhole":
+        raise ValueError("camera_from_kalibr: unknown camera model %r (known: pinhole)" % entry["camera_model"])
+    fx, fy, cx, cy = (float(v) for v in entry["intrinsics"])
+    resolution = tuple(int(v) for v in entry["resolution"])
+    model = KALIBR_MODELS[name]
+    coeffs = tuple(float(v) for v in entry.get("distortion_coeffs", ())) if model != "pinhole" else ()
+    if model == "radtan" and len(coeffs) not in (4, 5) or model == "equidistant" and len(coeffs) != 4:
+        raise ValueError("camera_from_kalibr: %s with %d coefficients" % (model, len(coeffs)))
+    if resize_to is not None:
+        cx += (float(resize_to[0]) - resolution[0]) / 2
+        cy += (float(resize_to[1]) - resolution[1]) / 2
+    return dict(model=model, raw_intrinsics=(fx, fy, cx, cy), coeffs=coeffs, resolution=resolution)
+
+
 @torch.no_grad()
 def run(cfg_VO, network, eval_cfg, data_list, ht=480, wd=640, device="cuda", inputs_ready="stream", on_pose=None,
         query_times=None):

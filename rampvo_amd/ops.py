@@ -350,6 +350,136 @@ def event_voxel_status(status):
                 n_events=int(w[1]), n_not_finite=int(w[2]), n_outside=int(w[3]), n_no_bin=int(w[4]), n_contributed=int(w[5]))
 
 
+CAMERA_MODELS = {"pinhole": _lib.RAMP_CAM_PINHOLE, "radtan": _lib.RAMP_CAM_RADTAN, "equidistant": _lib.RAMP_CAM_EQUIDISTANT}
+_CAMERA_COEFFS = {_lib.RAMP_CAM_PINHOLE: (0,), _lib.RAMP_CAM_RADTAN: (4, 5), _lib.RAMP_CAM_EQUIDISTANT: (4,)}
+
+
+def camera_words(model, raw_intrinsics, coeffs=(), rotation=None):
+    """the host part of a camera record (include/ramp_hip.h, RAMP_CAMERA_*): a list of RAMP_CAMERA_WORDS floats with the
+    rectified intrinsics left at the raw ones"""
+    code = CAMERA_MODELS.get(model, model)
+    if code not in _CAMERA_COEFFS:
+        raise RuntimeError("camera: the model is 'pinhole', 'radtan' or 'equidistant' (got %r)" % (model,))
+    k = [float(v) for v in coeffs]
+    if code != _lib.RAMP_CAM_PINHOLE and len(k) not in _CAMERA_COEFFS[code]:
+        raise RuntimeError("camera: radtan takes (k1, k2, p1, p2[, k3]), equidistant (k1, k2, k3, k4); got %d coefficients" % len(k))
+    raw = [float(v) for v in raw_intrinsics]
+    if len(raw) != 4:
+        raise RuntimeError("camera: intrinsics are (fx, fy, cx, cy)")
+    R = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+    if rotation is not None:
+        R = [float(v) for v in torch.as_tensor(rotation, dtype=torch.float64).reshape(-1).tolist()]
+        if len(R) != 9:
+            raise RuntimeError("camera: a rotation is 3 x 3")
+    words = [0.0] * _lib.RAMP_CAMERA_WORDS
+    words[_lib.RAMP_CAMERA_RAW:_lib.RAMP_CAMERA_RAW + 4] = raw
+    words[_lib.RAMP_CAMERA_MODEL] = float(code)
+    if code != _lib.RAMP_CAM_PINHOLE:
+        words[_lib.RAMP_CAMERA_COEFFS:_lib.RAMP_CAMERA_COEFFS + len(k)] = k
+    words[_lib.RAMP_CAMERA_ROTATION:_lib.RAMP_CAMERA_ROTATION + 9] = R
+    words[_lib.RAMP_CAMERA_NEW:_lib.RAMP_CAMERA_NEW + 4] = raw
+    return words
+
+
+def camera(model, raw_intrinsics, coeffs=(), new_intrinsics=None, rotation=None, device="cuda"):
+    """The device record of a distorting camera (include/ramp_hip.h, "lens distortion"): ``model`` 'pinhole', 'radtan'
+    (``coeffs`` k1, k2, p1, p2[, k3]) or 'equidistant' (k1 .. k4: Kalibr's name for OpenCV's fisheye); ``raw_intrinsics``
+    (fx, fy, cx, cy) of the sensor; ``rotation`` 3 x 3, raw camera to rectified camera (None: identity); ``new_intrinsics``
+    of the rectified pinhole camera (None: the raw ones), a sequence or a DEVICE tensor [4], which is copied on the current
+    stream and never read by the host.  Returns a float32 tensor [RAMP_CAMERA_WORDS]."""
+    rec = torch.tensor(camera_words(model, raw_intrinsics, coeffs, rotation), dtype=torch.float32, device=device)
+    if new_intrinsics is not None:
+        rec[_lib.RAMP_CAMERA_NEW:_lib.RAMP_CAMERA_NEW + 4] = torch.as_tensor(new_intrinsics, dtype=torch.float32,
+                                                                              device=rec.device).reshape(4)
+    return rec
+
+
+def _camera_record(name, camera, dev):
+    require_cuda(camera)
+    if camera.dtype != torch.float32 or camera.numel() != _lib.RAMP_CAMERA_WORDS or camera.device != dev:
+        raise RuntimeError("%s: the camera is the float32 record ops.camera returns, on the device of the data" % name)
+    return camera.reshape(-1).contiguous()
+
+
+def event_rectify(x, y, camera, height, width, want_valid=False):
+    """Raw sensor events to the rectified pinhole camera (include/ramp_hip.h ``ramp_event_rectify``): every event's pixel is
+    normalised with the raw intrinsics, the distortion model is inverted with a fixed number of Newton steps, the ray is
+    rotated and projected with the rectified intrinsics.  ``x, y`` [N]: integer tensors take the int32 path, floating ones
+    fp32 (integer-valued floats give the same bits); ``camera``: ``ops.camera``; ``height, width``: the rectified image, for
+    the inside / outside count only.  Device tensors on the current stream, nothing synchronised.
+
+    Returns a dict: ``xy`` [N,2] float32 -- a NaN row for an event that is not finite, not invertible (the solution left the
+    branch the model is monotone on, or did not converge to 2^-6 raw pixels) or behind the rectified camera; the format
+    ``event_voxel_grid(subpixel=True)``, ``event_warp`` and ``event_contrast`` take -- ``status`` int32 [8]
+    (``event_rectify_status``) and ``valid`` uint8 [N] (None unless ``want_valid``)."""
+    require_cuda(x, y)
+    dev = x.device
+    cam = _camera_record("event_rectify", camera, dev)
+    if height < 1 or width < 1:
+        raise RuntimeError("event_rectify: height and width are positive")
+    integer = not (x.is_floating_point() or y.is_floating_point())
+    dt = torch.int32 if integer else torch.float32
+    xs, ys = x.reshape(-1).to(dt).contiguous(), y.reshape(-1).to(dt).contiguous()
+    N = xs.shape[0]
+    if ys.shape[0] != N:
+        raise RuntimeError("event_rectify: x and y differ in length")
+    res = {"xy": torch.empty((N, 2), dtype=torch.float32, device=dev), "status": torch.zeros(8, dtype=torch.int32, device=dev),
+           "valid": torch.empty(N, dtype=torch.uint8, device=dev) if want_valid else None}
+    if N == 0:
+        return res
+    check(lib().ramp_event_rectify(ptr(xs), ptr(ys), N, ptr(cam), _lib.RAMP_RECTIFY_XY_I32 if integer else 0, height, width,
+                                   ptr(res["xy"]), ptr(res["valid"]), ptr(res["status"]), stream()), "ramp_event_rectify")
+    return res
+
+
+def event_rectify_status(status):
+    """the status words of ramp_event_rectify as a dict (synchronises: one 32-byte copy)"""
+    w = status.detach().cpu()
+    return dict(bad_camera=bool(int(w[0]) & _lib.RAMP_RECTIFY_BAD_CAMERA), n_events=int(w[1]), n_not_finite=int(w[2]),
+                n_not_invertible=int(w[3]), n_behind=int(w[4]), n_outside=int(w[5]), n_inside=int(w[6]))
+
+
+_RECTIFY_NORM = {None: _lib.RAMP_RECTIFY_NORM_NONE, "half": _lib.RAMP_RECTIFY_NORM_HALF, "unit": _lib.RAMP_RECTIFY_NORM_UNIT}
+
+
+def image_rectify(image, camera, height, width, normalize=None, fill=0.0, want_map=False, want_mask=False):
+    """A raw frame resampled into the rectified pinhole camera (include/ramp_hip.h ``ramp_image_rectify``): per output pixel
+    the ray is rotated back, distorted in closed form and the source sampled bilinearly in fp32.  ``image`` [C,Hs,Ws] or
+    [Hs,Ws], uint8 or float32; ``normalize``: None, ``"half"`` (``2 (v / 255) - 0.5``) or ``"unit"`` (``2 (v / 255) - 1``),
+    the two branches of the reference's ``normalize_image``; a pixel whose ray is behind the camera, beyond the fold of the
+    model or outside the source gets ``fill``.  Device tensors on the current stream, nothing synchronised.
+
+    Returns a dict: ``image`` float32 [C,height,width] ([height,width] for a 2-D source), ``status`` int32 [8]
+    (``image_rectify_status``), ``map`` [height,width,2] the source coordinates with NaN where nothing was sampled, and
+    ``mask`` uint8 [height,width] (None unless requested)."""
+    require_cuda(image)
+    dev = image.device
+    cam = _camera_record("image_rectify", camera, dev)
+    if normalize not in _RECTIFY_NORM:
+        raise RuntimeError("image_rectify: normalize is None, 'half' or 'unit'")
+    if image.dim() not in (2, 3) or image.numel() == 0 or height < 1 or width < 1:
+        raise RuntimeError("image_rectify: an image is [C,Hs,Ws] or [Hs,Ws], not empty; height and width are positive")
+    u8 = image.dtype == torch.uint8
+    src = (image if u8 else image.to(torch.float32)).contiguous()
+    C = 1 if src.dim() == 2 else src.shape[0]
+    Hs, Ws = src.shape[-2], src.shape[-1]
+    out = torch.empty((C, height, width), dtype=torch.float32, device=dev)
+    res = {"image": out if image.dim() == 3 else out[0], "status": torch.zeros(8, dtype=torch.int32, device=dev),
+           "map": torch.empty((height, width, 2), dtype=torch.float32, device=dev) if want_map else None,
+           "mask": torch.empty((height, width), dtype=torch.uint8, device=dev) if want_mask else None}
+    check(lib().ramp_image_rectify(ptr(src), C, Hs, Ws, ptr(cam), _lib.RAMP_RECTIFY_SRC_U8 if u8 else 0, _RECTIFY_NORM[normalize],
+                                   float(fill), height, width, ptr(out), ptr(res["map"]), ptr(res["mask"]), ptr(res["status"]),
+                                   stream()), "ramp_image_rectify")
+    return res
+
+
+def image_rectify_status(status):
+    """the status words of ramp_image_rectify as a dict (synchronises: one 32-byte copy)"""
+    w = status.detach().cpu()
+    return dict(bad_camera=bool(int(w[0]) & _lib.RAMP_RECTIFY_BAD_CAMERA), n_pixels=int(w[1]), n_invalid=int(w[2]),
+                n_outside=int(w[3]), n_sampled=int(w[4]))
+
+
 def align_loop(evaluate, correction, free, step, iters):
     """the line search of ``event_align`` over ``evaluate(theta) -> (variance, grad)``: normalised gradient ascent with
     backtracking.  The direction is the gradient masked by ``free``, divided by its norm; the step length starts at ``step``,

@@ -1,5 +1,5 @@
 """What a caller may ask a tracker between two frames (``Ramp_vo`` inherits ``TrackerQueries``): live poses, the trajectory
-at the frames' and at any time stamps, compensated events, the inverse-depth map, the window's uncertainty and the map.  The
+at the frames' and at any time stamps, compensated events, rectified events and frames, the inverse-depth map, the window's uncertainty and the map.  The
 tracker keeps the state (``_traj_extra``, ``_traj_times``, ``_traj_status``, ``_pose_ring``).  ``StateStream`` is the one place
 that knows on which stream the state is read and how results cross, ``_check_status`` the one that reads status words."""
 import contextlib
@@ -54,18 +54,21 @@ class StateStream:
                 self.leaves(*(x.values() if isinstance(x, dict) else x))
 
 
-def _check_status(name, traj=None, interp=None, cam=None, voxel=None):
+def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None):
     """The closing check of a query's numpy form -- its one wait.  Each argument is a device status tensor or None (not part
     of this query): ``traj`` trajectory()'s word, ``interp`` the words of ops.se3_interp or ops.event_warp (bit 0 of word 0:
     the frames' time stamps), ``cam`` those of ops.invdepth_map (bit 0 of word 0: the camera pose), ``voxel`` those of
-    ops.event_voxel_grid (bits 0 and 1 of word 0: the offsets, a slice's own time stamps).  Word 0 of each goes to the host
-    in one copy; raises in this order: unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times."""
-    given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam), ("voxel", voxel))
-             if s is not None]
+    ops.event_voxel_grid (bits 0 and 1 of word 0: the offsets, a slice's own time stamps), ``rectify`` those of
+    ops.event_rectify / ops.image_rectify (bit 0 of word 0: the camera record).  Word 0 of each goes to the host in one copy;
+    raises in this order: camera record, unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times."""
+    given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam), ("voxel", voxel),
+                                                 ("rectify", rectify)) if s is not None]
     if not given:
         return
     first = given[0][1] if len(given) == 1 else torch.cat([s for _, s in given])
     word = dict(zip((k for k, _ in given), first.cpu().tolist()))          # (the one wait)
+    if word.get("rectify", 0) & _lib.RAMP_RECTIFY_BAD_CAMERA:
+        raise RuntimeError(name + ": the camera record is not finite or a focal length is not positive")
     if word.get("traj", 0) & track_dev.TRAJ_UNRESOLVED:
         raise RuntimeError(name + ": a frame is neither a keyframe nor reachable through the delta chain")
     if word.get("interp", 0) & 1:
@@ -87,7 +90,9 @@ def _dof_sigma0(s):
 class TrackerQueries:
     """the query surface of ``Ramp_vo`` (a mixin: it reads the tracker's buffers, streams and host mirror as they are)"""
 
-    _NUMPY = {torch.float32: np.float32, torch.float64: np.float64, torch.int8: np.int8, torch.int64: np.int64}
+    _NUMPY = {torch.float32: np.float32, torch.float64: np.float64, torch.int8: np.int8, torch.int64: np.int64,
+              torch.int32: np.int32}
+    _camera = None              # set_camera(): the record's host part on the device, without the rectified intrinsics
 
     def _state_stream(self, inputs=()):
         return StateStream(self, inputs)
@@ -203,9 +208,76 @@ class TrackerQueries:
         _check_status("poses_at()", traj=self._traj_status, interp=status)
         return poses.cpu().numpy(), (tw.cpu().numpy() if twist else None)
 
+    # ---------------------------------------------------------------- lens distortion
+    def set_camera(self, model, raw_intrinsics, coeffs=(), rotation=None):
+        """The sensor the raw events and frames come from (``ops.camera``): ``model`` 'pinhole', 'radtan' or 'equidistant',
+        its raw intrinsics (fx, fy, cx, cy), distortion coefficients and an optional rotation raw -> rectified camera --
+        ``evaluate.camera_from_kalibr`` reads them from a Kalibr cam-chain.  The rectified camera is the pinhole the tracker is
+        fed with: row 0 of its own intrinsics times the patch stride, read on the device at every query.  One upload, nothing
+        synchronised."""
+        self._camera = self._upload(np.asarray(ops.camera_words(model, raw_intrinsics, coeffs, rotation), np.float32))
+
+    def _rectified_camera(self, name):
+        """the camera record with the rectified intrinsics ``_event_query`` forms, read on the stream the state lives on"""
+        if self._camera is None:
+            raise RuntimeError(name + ": no camera has been set (set_camera())")
+        if not self.tlist:
+            raise RuntimeError(name + ": no frame has been tracked yet")
+        with self._state_stream(inputs=(self._camera,)) as sc:
+            cam = self._camera.clone()
+            cam[_lib.RAMP_CAMERA_NEW:_lib.RAMP_CAMERA_NEW + 4] = self.intrinsics_[0] * float(self.RES)
+            sc.leaves(cam)
+        return cam
+
+    def _raw_pixels(self, a):
+        """event coordinates as the rectifier takes them: integer input stays integer (the int32 path), anything else fp32"""
+        if isinstance(a, torch.Tensor):
+            return a.to(device=self.device, dtype=torch.float32 if a.is_floating_point() else torch.int32)
+        a = np.asarray(a)
+        return self._as_device(a, torch.int32 if a.dtype.kind in "iu" else torch.float32)
+
+    def rectify_events(self, x, y, as_tensor=False):
+        """Raw sensor events -> sub-pixel coordinates of the images the tracker is fed (``ops.event_rectify`` with the camera of
+        ``set_camera``).  ``xy`` [N,2] is what the event queries take as ``x=xy[:, 0], y=xy[:, 1]``; an event without a
+        solution is a NaN row, which they skip and count.  A device-resident state stays device resident.  ``as_tensor=True``:
+        the dict of device tensors (``xy``, ``status``, ``valid``), ordered on the current stream, nothing synchronised;
+        otherwise numpy arrays, which waits and raises when the camera record is not finite."""
+        cam = self._rectified_camera("rectify_events()")
+        with torch.no_grad():
+            out = ops.event_rectify(self._raw_pixels(x), self._raw_pixels(y), cam, self.ht, self.wd, want_valid=True)
+        if as_tensor:
+            return out
+        _check_status("rectify_events()", rectify=out["status"])
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def rectify_image(self, image, normalize="half", as_tensor=False):
+        """A raw frame [C,Hs,Ws] or [Hs,Ws] (uint8 or float32; a tensor or an array) resampled into the camera the tracker is
+        fed, at its image size, with the reference's normalisation (``ops.image_rectify``; ``normalize`` None, "half" or
+        "unit").  Returns a dict ``image``, ``mask`` (1 where the source was sampled), ``status``: device tensors with
+        ``as_tensor=True``, ordered on the current stream, nothing synchronised; otherwise numpy arrays, which waits and raises
+        when the camera record is not finite."""
+        cam = self._rectified_camera("rectify_image()")
+        if not isinstance(image, torch.Tensor):
+            image = np.asarray(image)
+            image = self._upload(image if image.dtype == np.uint8 else image.astype(np.float32))
+        with torch.no_grad():
+            out = ops.image_rectify(image.to(self.device), cam, self.ht, self.wd, normalize=normalize, want_mask=True)
+        out.pop("map")
+        if as_tensor:
+            return out
+        _check_status("rectify_image()", rectify=out["status"])
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def _undistorted(self, name, x, y):
+        """``distorted=True`` of an event query: (x, y, rectify_status) with the rectified coordinates in the place of the raw"""
+        if self._camera is None:
+            raise RuntimeError(name + ": distorted=True needs the sensor's camera (set_camera())")
+        rect = self.rectify_events(x, y, as_tensor=True)
+        return rect["xy"][:, 0], rect["xy"][:, 1], rect["status"]
+
     def compensate_events(self, x, y, t, p, t_ref=None, invdepth=None, num_bins=0, extrapolate=False, want_xy=False,
                           want_iwe=True, stack=None, height=None, width=None, as_tensor=False, radius=None,
-                          weights="variance"):
+                          weights="variance", distorted=False):
         """Motion compensation with the trajectory as it is now: every event (``x, y`` pixel coordinates of the images the
         tracker is fed, ``t`` in the unit of the frames' time stamps, ``p`` polarity) is warped from the camera pose at its
         own time stamp to the pose at ``t_ref`` and splat bilinearly into an image of warped events and / or a bin stack
@@ -218,12 +290,17 @@ class TrackerQueries:
         ``invdepth_map(t_ref, radius, weights)`` renders from the window's patches at the reference pose, so that every event is
         warped with the depth the tracker has estimated near its pixel (``radius``, ``weights`` are read in this mode only).
         Intrinsics: row 0 of the tracker's own times the patch stride, i.e. those of the images it was fed.  ``height, width``
-        default to the tracker's.
+        default to the tracker's.  ``distorted=True``: ``x, y`` are RAW sensor pixels; they are rectified first
+        (``rectify_events``, the camera of ``set_camera``; raises without one), the events without a solution are skipped and
+        counted like any NaN row, and the result gains ``rectify_status``.
 
         A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
         the dict of device tensors of ``ops.event_warp`` (``status``, ``xy``, ``iwe``, ``stack`` as requested), ordered on
         the current stream, nothing synchronised.  Otherwise numpy arrays, which waits for that result and raises when the
         frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
+        rect = None
+        if distorted:
+            x, y, rect = self._undistorted("compensate_events()", x, y)
         knots, tdev, K, invdepth, t_ref, H, W = self._event_query("compensate_events()", t_ref, invdepth, radius, weights,
                                                                   height, width)
         with torch.no_grad():
@@ -231,9 +308,11 @@ class TrackerQueries:
                                  self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
                                  invdepth, H, W, num_bins=num_bins, extrapolate=extrapolate, want_xy=want_xy,
                                  want_iwe=want_iwe, stack=stack)
+        if rect is not None:
+            out["rectify_status"] = rect
         if as_tensor:
             return out
-        _check_status("compensate_events()", traj=self._traj_status, interp=out["status"])
+        _check_status("compensate_events()", traj=self._traj_status, interp=out["status"], rectify=rect)
         return {k: v.cpu().numpy() for k, v in out.items()}
 
     def _event_query(self, name, t_ref, invdepth, radius, weights, height, width):
@@ -259,18 +338,22 @@ class TrackerQueries:
 
     def event_contrast(self, x, y, t, p, t_ref=None, invdepth=None, correction=None, signed=True, want_grad=True,
                        want_iwe=False, extrapolate=False, height=None, width=None, as_tensor=False, radius=None,
-                       weights="variance"):
+                       weights="variance", distorted=False):
         """How sharp the compensated events are with the trajectory as it is now: the variance of the image of warped events
         ``compensate_events`` would return (the same events, poses, intrinsics and inverse depth -- ``invdepth`` as there,
         ``"map"`` included) and its gradient with respect to a small correction ``(v[3], w[3], lam)`` of velocity, rotation
         rate and log depth scale in the reference camera frame (``ops.event_contrast``).  The only figure of quality an
-        event tracker can give about its own trajectory without ground truth.
+        event tracker can give about its own trajectory without ground truth.  ``distorted=True``: raw sensor pixels, as in
+        ``compensate_events``; the result gains ``rectify_status``.
 
         A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
         the dict of device tensors of ``ops.event_contrast`` (``variance``, ``stats``, ``sums``, ``status``, ``grad``, ``iwe``
         as requested), ordered on the current stream, nothing synchronised.  Otherwise numpy arrays (``variance`` a float),
         which waits for that result and raises when the frames' time stamps decrease or are not finite, or on trajectory()'s
         unresolved bit."""
+        rect = None
+        if distorted:
+            x, y, rect = self._undistorted("event_contrast()", x, y)
         knots, tdev, K, invdepth, t_ref, H, W = self._event_query("event_contrast()", t_ref, invdepth, radius, weights,
                                                                   height, width)
         with torch.no_grad():
@@ -278,21 +361,28 @@ class TrackerQueries:
                                      self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
                                      invdepth, H, W, correction=correction, signed=signed, extrapolate=extrapolate,
                                      want_grad=want_grad, want_iwe=want_iwe)
+        if rect is not None:
+            out["rectify_status"] = rect
         if as_tensor:
             return out
-        _check_status("event_contrast()", traj=self._traj_status, interp=out["status"])
+        _check_status("event_contrast()", traj=self._traj_status, interp=out["status"], rectify=rect)
         res = {k: v.cpu().numpy() for k, v in out.items()}
         res["variance"] = float(res["stats"][0])
         return res
 
     def align_events(self, x, y, t, p, t_ref=None, invdepth=None, correction=None, free=(0, 0, 0, 1, 1, 1, 0), step=0.05,
-                     iters=20, signed=True, extrapolate=False, height=None, width=None, radius=None, weights="variance"):
+                     iters=20, signed=True, extrapolate=False, height=None, width=None, radius=None, weights="variance",
+                     distorted=False):
         """Refine the compensation by contrast maximisation (``ops.event_align``: a host loop of normalised gradient ascent
         with backtracking over ``event_contrast``, the components ``free`` marks -- by default the rotation rate).  The
         trajectory, intrinsics and inverse depth are read ONCE, as ``event_contrast`` reads them; every evaluation then reads
         8 + 7 doubles back, so this is a convenience between two frames, not a hot path.  A device-resident state stays
         device resident.  Returns ``ops.event_align``'s dict: ``correction``, ``variance``, ``variance0``, ``history``; raises
-        on the conditions ``event_contrast`` raises on."""
+        on the conditions ``event_contrast`` raises on.  ``distorted=True``: raw sensor pixels, rectified once in front of the
+        loop; the result gains ``rectify_status`` (the words, on the host)."""
+        rect = None
+        if distorted:
+            x, y, rect = self._undistorted("align_events()", x, y)
         knots, tdev, K, invdepth, t_ref, H, W = self._event_query("align_events()", t_ref, invdepth, radius, weights,
                                                                   height, width)
         with torch.no_grad():
@@ -300,13 +390,15 @@ class TrackerQueries:
                                   self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
                                   invdepth, H, W, correction=correction, free=free, step=step, iters=iters, signed=signed,
                                   extrapolate=extrapolate)
-        _check_status("align_events()", traj=self._traj_status)
+        _check_status("align_events()", traj=self._traj_status, rectify=rect)
+        if rect is not None:
+            out["rectify_status"] = rect.cpu().numpy()
         if out["variance0"] != out["variance0"]:              # (NaN: the kernel's answer to bad time stamps)
             raise RuntimeError("align_events(): the frames' time stamps decrease or are not finite")
         return out
 
     def event_voxel_grid(self, x, y, t, p, num_bins=5, offsets=None, normalize=True, compensate=False, t_ref=None,
-                         invdepth=None, as_tensor=False, extrapolate=False, radius=None, weights="variance"):
+                         invdepth=None, as_tensor=False, extrapolate=False, radius=None, weights="variance", distorted=False):
         """The reference's voxel-grid event representation at the tracker's image size (``ops.event_voxel_grid``: every event
         votes into the two time bins next to its normalised time stamp, each slice standardised over its non-zero cells):
         ``grid`` [S, num_bins, ht, wd] for the slices ``offsets`` (a device int64 tensor [S + 1], ``ops.event_slices``) marks,
@@ -318,15 +410,22 @@ class TrackerQueries:
         coordinates are splat bilinearly; the events the warp rejects are NaN rows, which the grid skips and counts.  The time
         bins are those of the events' own time stamps.
 
+        ``distorted=True``: ``x, y`` are RAW sensor pixels; they are rectified first (``rectify_events``; raises without
+        ``set_camera``) and splat bilinearly at their sub-pixel coordinates, compensated or not; the result gains
+        ``rectify_status``.
+
         A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
         the dict of device tensors of ``ops.event_voxel_grid`` (``grid``, ``stats``, ``status``; with ``compensate`` also
         ``warp_status``, the words of ``ops.event_warp``), ordered on the current stream, nothing synchronised.  Otherwise
         numpy arrays, which waits for that result and raises on offsets that decrease or leave the event list, on a slice
         whose first or last time stamp is not finite and, with ``compensate``, on the conditions ``compensate_events`` raises
         on."""
-        xd, yd = self._as_device(x, torch.float32), self._as_device(y, torch.float32)
+        if not distorted:
+            xd, yd = self._as_device(x, torch.float32), self._as_device(y, torch.float32)
         td, pd = self._as_device(t, torch.float64), self._as_device(p, torch.int8)
-        warp = None
+        warp = rect = None
+        if distorted:
+            xd, yd, rect = self._undistorted("event_voxel_grid()", x, y)
         if compensate:
             warp = self.compensate_events(xd, yd, td, pd, t_ref=t_ref, invdepth=invdepth, extrapolate=extrapolate, want_xy=True,
                                           want_iwe=False, as_tensor=True, radius=radius, weights=weights)
@@ -334,13 +433,15 @@ class TrackerQueries:
         with torch.no_grad():
             out = ops.event_voxel_grid(xd, yd, td, pd, self.ht, self.wd, num_bins=num_bins,
                                        offsets=None if offsets is None else self._as_device(offsets, torch.int64),
-                                       normalize=normalize, subpixel=compensate)
+                                       normalize=normalize, subpixel=compensate or distorted)
         if compensate:
             out["warp_status"] = warp["status"]
+        if rect is not None:
+            out["rectify_status"] = rect
         if as_tensor:
             return out
         _check_status("event_voxel_grid()", traj=self._traj_status if compensate else None, interp=out.get("warp_status"),
-                      voxel=out["status"])
+                      voxel=out["status"], rectify=rect)
         return {k: v.cpu().numpy() for k, v in out.items()}
 
     def _depth_median_word(self, resident):
