@@ -1328,6 +1328,71 @@ int ramp_event_rectify(const void *x, const void *y, long N, const float *camera
 int ramp_image_rectify(const void *src, int C, int Hs, int Ws, const float *camera, int flags, int norm, float fill, int H, int W,
                        float *out, float *map_out, uint8_t *mask_out, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------- event denoising (csrc/filter.hip)
+ *
+ * ramp_event_filter: the first step behind a real sensor -- a hot-pixel mask, a refractory period and the 8-neighbour
+ * background-activity filter over one event list, order-independent and bit-exact.  The xy it writes is the format
+ * ramp_event_rectify (fp32 path), RAMP_VOXEL_SUBPIXEL, ramp_event_warp and ramp_event_contrast take: a NaN row for every event
+ * that is not kept, which they skip and count.
+ *   events: x, y [N] fp32, or int32 with RAMP_FILTER_XY_I32 (converted to fp32; integer-valued floats give the same bits);
+ *   t [N] float64.  The pixel is the coordinate truncated toward zero, as in ramp_event_voxel.  Polarity takes no part.
+ *   Candidates: an event whose x, y or t is not finite is class [2]; a finite event whose pixel is outside the sensor is
+ *   class [3]; the rest are CANDIDATES.
+ *   Order: within a pixel the order of the indices; the time stamps of every pixel's candidates must not decrease in that
+ *   order (a time-sorted stream satisfies this).  Across pixels e' PRECEDES e when (t', index') < (t, index)
+ *   lexicographically -- on a globally time-sorted stream the order of the indices.
+ *   Hot pixels: c[q] = the number of candidates at pixel q, n = the number of pixels with c >= 1, S1 = sum c, S2 = sum c^2
+ *   (exact int64).  In float64, in this order, without FMA:
+ *     mean = S1 / n,   var = max(S2 / n - mean * mean, 0),   thr = mean + hot_sigma * sqrt(var)
+ *   q is hot when hot_count > 0 and c[q] > hot_count, or hot_sigma > 0 and c[q] > thr, or hot_in[q] != 0 (hot_in: optional
+ *   uint8 [H][W]).  Every candidate at a hot pixel is class [4]; it gives no support and does not touch the state.
+ *   State: last_t_in, optional float64 [H][W]: per non-hot pixel the time stamp of the last candidate seen there in earlier
+ *   calls, NaN for none; it acts as one virtual event that precedes every event of the call at that pixel.  NULL: all NaN.
+ *   Refractory period (refractory > 0): t_own = the time stamp of the IMMEDIATE predecessor at the candidate's own pixel --
+ *   the previous candidate there, kept or not, else the state; class [5] when t - t_own < refractory (a float64 subtraction).
+ *   History-free on purpose: an event's outcome is a function of the raw stream (the chained variant is not built).
+ *   Background activity (support_dt >= 0; negative: off): for each of the 8 neighbour pixels -- the own pixel excluded, a
+ *   neighbour outside the sensor or hot skipped -- t_nb = the time stamp of the neighbour's last candidate that precedes the
+ *   event, else the neighbour's state; the event has SUPPORT when some neighbour has t - t_nb <= support_dt.  A candidate
+ *   without support is class [6].  An event dropped by the refractory test still supports its neighbours.
+ *   Every other candidate is KEPT, class [7].  The first class that applies, [2] to [7], is the one counted.
+ *   On a globally time-sorted stream this is, event for event, the textbook sequential filter over a last-time-stamp map
+ *   (test the own entry, test the eight neighbours' entries, write the own entry).
+ *   Outputs (optional ones NULL; keep_out and status are required):
+ *     keep_out [N] uint8: 1 for class [7], else 0.  xy_out [N][2] fp32, 8-byte aligned: the input coordinates for kept events,
+ *     a NaN row for every other.  index_out [N] int32: the K kept indices in ascending order, then -1.  count_out: K as a
+ *     device int64.  hot_out [H][W] uint8: the final mask, hot_in included.  stats_out float64 [4]: n, mean, std, thr (thr NaN
+ *     when hot_sigma <= 0; n == 0: 0 and three NaN).  last_t_out [H][W] float64: per non-hot pixel its last candidate's time
+ *     stamp, else last_t_in's value; written by a launch of its own behind the filter launch, so last_t_out == last_t_in is
+ *     allowed.
+ *   status: device int32 [8], written by the call: [0] bits (RAMP_FILTER_BAD_ORDER: a pixel's candidates decrease in time in
+ *   index order, or a pixel's first candidate lies before its state -- hot pixels included), [1] events, [2] - [7] the class
+ *   counts; [2] + ... + [7] = [1].
+ *   RAMP_FILTER_BAD_ORDER is an outcome of the data (RAMP_OK), never a plausible number: every keep is 0, xy_out NaN, count 0,
+ *   index_out -1, last_t_out and stats_out NaN, [4] - [7] 0 ([1] - [3] are still counted; hot_out is the mask of the counts,
+ *   which do not depend on the order).
+ *   Launches, all on `stream`, nothing synchronised, no floating-point atomics, every loop a binary search or of fixed length:
+ *   one memset; the key kernel; a STABLE radix sort of (pixel, index) over ceil(log2(H W + 1)) bits (hipcub); the segment
+ *   kernel (per-pixel offsets by binary search: counts are differences, not atomics); the hot stage (integer sums and the order
+ *   check, then threshold and mask); the filter kernel, one lane per sorted position (the own predecessor at position - 1,
+ *   eight binary searches over the neighbours' segments); with index_out a scan (hipcub) and the compaction; the state and
+ *   status launch.  The result is a function of the input alone: a call repeats its bits.
+ *   N == 0: RAMP_OK, nothing is launched and nothing written except a copy last_t_in -> last_t_out when both are given and
+ *   differ.  N < 0, H or W < 1, unknown flags, a NULL keep_out / status (N > 0: x / y / t / ws), xy_out, last_t_in, last_t_out,
+ *   stats_out or count_out not 8-byte aligned, ws not 16-byte aligned, refractory < 0, refractory or support_dt not finite:
+ *   RAMP_EINVAL.  N >= 2^31 or H W >= 2^31 - 1: RAMP_EUNSUPPORTED.  ws_bytes below
+ *   ramp_event_filter_workspace_bytes(N, H, W): RAMP_EWORKSPACE.
+ * ramp_event_filter_grid_events(): the number of events one trip of the full grid covers; above it the workgroups take a
+ * second trip.                                                                                                        */
+#define RAMP_FILTER_XY_I32 1
+#define RAMP_FILTER_BAD_ORDER 1 /* status[0] bit 0 */
+size_t ramp_event_filter_workspace_bytes(long N, int H, int W);
+long ramp_event_filter_grid_events(void);
+int ramp_event_filter(const void *x, const void *y, const double *t, long N, int H, int W, int flags, double support_dt,
+                      double refractory, int hot_count, double hot_sigma, const uint8_t *hot_in, const double *last_t_in,
+                      double *last_t_out, uint8_t *keep_out, float *xy_out, int32_t *index_out, int64_t *count_out,
+                      uint8_t *hot_out, double *stats_out, int32_t *status, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,7 @@ RAMP_CAM_PINHOLE, RAMP_CAM_RADTAN, RAMP_CAM_EQUIDISTANT = 0, 1, 2
 RAMP_RECTIFY_ITERS, RAMP_RECTIFY_TOL = 8, 2.0 ** -6
 RAMP_RECTIFY_XY_I32, RAMP_RECTIFY_SRC_U8, RAMP_RECTIFY_BAD_CAMERA = 1, 2, 1
 RAMP_RECTIFY_NORM_NONE, RAMP_RECTIFY_NORM_HALF, RAMP_RECTIFY_NORM_UNIT = 0, 1, 2
+RAMP_FILTER_XY_I32, RAMP_FILTER_BAD_ORDER = 1, 1
 KPLANE = 32            # channels per plane of the packed correlation target maps: [h][128 / KPLANE][w][KPLANE]
 
 
@@ -211,6 +212,11 @@ SIGNATURES = {
     "ramp_event_rectify_grid_events": (ctypes.c_long, []),
     "ramp_event_rectify": (c_i, [c_p, c_p, ctypes.c_long, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "ramp_image_rectify": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    # event denoising (csrc/filter.hip)
+    "ramp_event_filter_workspace_bytes": (c_sz, [ctypes.c_long, c_i, c_i]),
+    "ramp_event_filter_grid_events": (ctypes.c_long, []),
+    "ramp_event_filter": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i,
+                                ctypes.c_double] + [c_p] * 11 + [c_sz, c_p]),
 }
 
 _lib = None

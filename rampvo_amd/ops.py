@@ -480,6 +480,85 @@ def image_rectify_status(status):
                 n_outside=int(w[3]), n_sampled=int(w[4]))
 
 
+def event_filter_state(height, width, device="cuda"):
+    """the state of ``event_filter`` before the first event: float64 [height, width], all NaN"""
+    return torch.full((height, width), float("nan"), dtype=torch.float64, device=device)
+
+
+def event_filter(x, y, t, height, width, support_dt=None, refractory=0.0, hot_count=0, hot_sigma=0.0, hot_mask=None,
+                 last_t=None, want_xy=True, want_index=False):
+    """Event denoising on the device (include/ramp_hip.h ``ramp_event_filter``): a hot-pixel mask, a refractory period and the
+    8-neighbour background-activity filter, order-independent and bit-exact -- on a time-sorted stream, event for event, the
+    textbook sequential filter over a last-time-stamp map.
+
+    ``x, y`` [N]: integer tensors take the int32 path, floating ones fp32 (integer-valued floats give the same bits); ``t`` [N]
+    float64, non-decreasing per pixel.  ``support_dt``: an event is kept only when one of its 8 neighbour pixels saw an event at
+    most this long before it (None: the test is off).  ``refractory``: an event less than this behind the previous event of its
+    own pixel is dropped (0: off).  A pixel is hot with more than ``hot_count`` events (0: off), with more than ``mean +
+    hot_sigma * std`` of the counts of the active pixels (0: off), or where ``hot_mask`` [height, width] is not zero.
+    ``last_t``: the state of the previous call (``event_filter_state``; None: no event yet); it is not written.
+
+    Returns a dict of device tensors: ``keep`` uint8 [N]; ``xy`` float32 [N, 2], the coordinates of the kept events and a NaN
+    row for every other -- the format ``event_rectify`` (as fp32), ``event_voxel_grid(subpixel=True)``, ``event_warp`` and
+    ``event_contrast`` skip and count -- (None unless ``want_xy``); ``index`` int32 [N], the kept indices in ascending order,
+    then -1, and ``count`` int64 [1], their number (None unless ``want_index``); ``hot`` uint8 [height, width], the final mask;
+    ``stats`` float64 [4]: active pixels, mean, std, threshold; ``status`` int32 [8] (``event_filter_status``); ``last_t``, a
+    NEW tensor, the state for the next call.  Runs on the current stream, nothing is synchronised; a call repeats its bits.
+    Time stamps that decrease within a pixel (or against the state) make every output empty or NaN and set bit 0 of
+    ``status[0]``: never a plausible number."""
+    require_cuda(x, y, t, hot_mask, last_t)
+    dev = x.device
+    if height < 1 or width < 1:
+        raise RuntimeError("event_filter: height and width are positive")
+    integer = not (x.is_floating_point() or y.is_floating_point())
+    dt = torch.int32 if integer else torch.float32
+    xs, ys = x.reshape(-1).to(dt).contiguous(), y.reshape(-1).to(dt).contiguous()
+    tf = t.reshape(-1).to(torch.float64).contiguous()
+    N = xs.shape[0]
+    if not (ys.shape[0] == N and tf.shape[0] == N):
+        raise RuntimeError("event_filter: x, y and t differ in length")
+    hot_in = state = None
+    if hot_mask is not None:
+        if tuple(hot_mask.shape) != (height, width):
+            raise RuntimeError("event_filter: hot_mask is [height, width]")
+        hot_in = (hot_mask != 0).to(torch.uint8).contiguous()
+    if last_t is not None:
+        if tuple(last_t.shape) != (height, width) or last_t.dtype != torch.float64:
+            raise RuntimeError("event_filter: last_t is float64 [height, width] (event_filter_state)")
+        state = last_t.contiguous()
+    nan = float("nan")
+    res = {"keep": torch.empty(N, dtype=torch.uint8, device=dev),
+           "xy": torch.empty((N, 2), dtype=torch.float32, device=dev) if want_xy else None,
+           "index": torch.empty(N, dtype=torch.int32, device=dev) if want_index else None,
+           "count": torch.zeros(1, dtype=torch.int64, device=dev) if want_index else None,
+           "status": torch.zeros(8, dtype=torch.int32, device=dev)}
+    if N == 0:                                                # (the entry launches nothing: the empty call's outputs are made here)
+        res["hot"] = hot_in.clone() if hot_in is not None else torch.zeros((height, width), dtype=torch.uint8, device=dev)
+        res["stats"] = torch.tensor([0.0, nan, nan, nan], dtype=torch.float64, device=dev)
+        res["last_t"] = state.clone() if state is not None else event_filter_state(height, width, dev)
+        return res
+    res["hot"] = torch.empty((height, width), dtype=torch.uint8, device=dev)
+    res["stats"] = torch.empty(4, dtype=torch.float64, device=dev)
+    res["last_t"] = torch.empty((height, width), dtype=torch.float64, device=dev)
+    nbytes = lib().ramp_event_filter_workspace_bytes(N, height, width)
+    if nbytes == 0:
+        check(_lib.RAMP_EUNSUPPORTED, "ramp_event_filter")
+    ws = _lib_workspace(nbytes, dev, "evfilter")
+    check(lib().ramp_event_filter(ptr(xs), ptr(ys), ptr(tf), N, height, width, _lib.RAMP_FILTER_XY_I32 if integer else 0,
+                                  -1.0 if support_dt is None else float(support_dt), float(refractory), int(hot_count),
+                                  float(hot_sigma), ptr(hot_in), ptr(state), ptr(res["last_t"]), ptr(res["keep"]), ptr(res["xy"]),
+                                  ptr(res["index"]), ptr(res["count"]), ptr(res["hot"]), ptr(res["stats"]), ptr(res["status"]),
+                                  ptr(ws), nbytes, stream()), "ramp_event_filter")
+    return res
+
+
+def event_filter_status(status):
+    """the status words of ramp_event_filter as a dict (synchronises: one 32-byte copy)"""
+    w = status.detach().cpu()
+    return dict(bad_order=bool(int(w[0]) & _lib.RAMP_FILTER_BAD_ORDER), n_events=int(w[1]), n_not_finite=int(w[2]),
+                n_outside=int(w[3]), n_hot=int(w[4]), n_refractory=int(w[5]), n_no_support=int(w[6]), n_kept=int(w[7]))
+
+
 def align_loop(evaluate, correction, free, step, iters):
     """the line search of ``event_align`` over ``evaluate(theta) -> (variance, grad)``: normalised gradient ascent with
     backtracking.  The direction is the gradient masked by ``free``, divided by its norm; the step length starts at ``step``,

@@ -1,5 +1,5 @@
 """What a caller may ask a tracker between two frames (``Ramp_vo`` inherits ``TrackerQueries``): live poses, the trajectory
-at the frames' and at any time stamps, compensated events, rectified events and frames, the inverse-depth map, the window's uncertainty and the map.  The
+at the frames' and at any time stamps, denoised, compensated and rectified events, rectified frames, the inverse-depth map, the window's uncertainty and the map.  The
 tracker keeps the state (``_traj_extra``, ``_traj_times``, ``_traj_status``, ``_pose_ring``).  ``StateStream`` is the one place
 that knows on which stream the state is read and how results cross, ``_check_status`` the one that reads status words."""
 import contextlib
@@ -54,19 +54,22 @@ class StateStream:
                 self.leaves(*(x.values() if isinstance(x, dict) else x))
 
 
-def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None):
+def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None, filter=None):
     """The closing check of a query's numpy form -- its one wait.  Each argument is a device status tensor or None (not part
     of this query): ``traj`` trajectory()'s word, ``interp`` the words of ops.se3_interp or ops.event_warp (bit 0 of word 0:
     the frames' time stamps), ``cam`` those of ops.invdepth_map (bit 0 of word 0: the camera pose), ``voxel`` those of
     ops.event_voxel_grid (bits 0 and 1 of word 0: the offsets, a slice's own time stamps), ``rectify`` those of
-    ops.event_rectify / ops.image_rectify (bit 0 of word 0: the camera record).  Word 0 of each goes to the host in one copy;
-    raises in this order: camera record, unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times."""
+    ops.event_rectify / ops.image_rectify (bit 0 of word 0: the camera record), ``filter`` those of ops.event_filter (bit 0 of
+    word 0: the events' order).  Word 0 of each goes to the host in one copy; raises in this order: event order, camera record,
+    unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times."""
     given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam), ("voxel", voxel),
-                                                 ("rectify", rectify)) if s is not None]
+                                                 ("rectify", rectify), ("filter", filter)) if s is not None]
     if not given:
         return
     first = given[0][1] if len(given) == 1 else torch.cat([s for _, s in given])
     word = dict(zip((k for k, _ in given), first.cpu().tolist()))          # (the one wait)
+    if word.get("filter", 0) & _lib.RAMP_FILTER_BAD_ORDER:
+        raise RuntimeError(name + ": a pixel's events decrease in time, or lie before the filter's state")
     if word.get("rectify", 0) & _lib.RAMP_RECTIFY_BAD_CAMERA:
         raise RuntimeError(name + ": the camera record is not finite or a focal length is not positive")
     if word.get("traj", 0) & track_dev.TRAJ_UNRESOLVED:
@@ -93,6 +96,8 @@ class TrackerQueries:
     _NUMPY = {torch.float32: np.float32, torch.float64: np.float64, torch.int8: np.int8, torch.int64: np.int64,
               torch.int32: np.int32}
     _camera = None              # set_camera(): the record's host part on the device, without the rectified intrinsics
+    _filter_params = None       # set_event_filter(): the keywords of ops.event_filter
+    _filter_state = None        # the filter's last-time-stamp map, carried by filter_events()
 
     def _state_stream(self, inputs=()):
         return StateStream(self, inputs)
@@ -208,6 +213,71 @@ class TrackerQueries:
         _check_status("poses_at()", traj=self._traj_status, interp=status)
         return poses.cpu().numpy(), (tw.cpu().numpy() if twist else None)
 
+    # ---------------------------------------------------------------- event denoising
+    _FILTER_KEYS = ("support_dt", "refractory", "hot_count", "hot_sigma", "hot_mask")
+
+    def set_event_filter(self, **params):
+        """The parameters of the event filter (``ops.event_filter``: ``support_dt``, ``refractory``, ``hot_count``,
+        ``hot_sigma``, ``hot_mask``) and a fresh state -- no event seen yet -- at the tracker's image size.  ``filter_events``
+        and ``denoise=True`` of the event queries filter with them.  Nothing is synchronised."""
+        unknown = sorted(set(params) - set(self._FILTER_KEYS))
+        if unknown:
+            raise RuntimeError("set_event_filter(): unknown parameter %s (known: %s)" % (unknown[0], ", ".join(self._FILTER_KEYS)))
+        if params.get("hot_mask") is not None:
+            m = params["hot_mask"]
+            m = m.to(self.device) if isinstance(m, torch.Tensor) else self._upload(np.asarray(m))
+            params["hot_mask"] = (m != 0).to(torch.uint8).reshape(self.ht, self.wd)
+        self._filter_params = params
+        self.reset_event_filter()
+
+    def reset_event_filter(self):
+        """forget the events ``filter_events`` has seen: the next call starts from the empty state (the parameters stay)"""
+        self._filter_state = None
+
+    def _filter(self, name, x, y, t, height=None, width=None):
+        """ops.event_filter with the stored parameters and state, on the stream the tracker's state lives on"""
+        if self._filter_params is None:
+            raise RuntimeError(name + ": no event filter has been set (set_event_filter())")
+        H, W = self.ht if height is None else int(height), self.wd if width is None else int(width)
+        xd, yd, td = self._raw_pixels(x), self._raw_pixels(y), self._as_device(t, torch.float64)
+        state = self._filter_state
+        if state is not None and tuple(state.shape) != (H, W):
+            raise RuntimeError(name + ": the filter's state is %d x %d, the call asks for %d x %d (reset_event_filter())"
+                               % (state.shape[0], state.shape[1], H, W))
+        with self._state_stream(inputs=tuple(v for v in (xd, yd, td, state, self._filter_params.get("hot_mask")) if v is not None)) as sc:
+            out = ops.event_filter(xd, yd, td, H, W, last_t=state, want_xy=True, want_index=True, **self._filter_params)
+            sc.leaves(out)
+        return out
+
+    def filter_events(self, x, y, t, as_tensor=False, height=None, width=None):
+        """Denoise the next stretch of the sensor's event stream (``ops.event_filter`` with the parameters of
+        ``set_event_filter``; raises without them): hot pixels, refractory period, 8-neighbour background activity.  The
+        filter's state -- every pixel's last time stamp -- is CARRIED from call to call, so feeding a stream in pieces gives
+        the events of feeding it whole (the hot-pixel statistics are those of each call's own events).  ``x, y``: integer
+        input takes the int32 path; ``height, width`` default to the tracker's.  ``xy`` [N,2] is what the event queries take as
+        ``x=xy[:, 0], y=xy[:, 1]``: a dropped event is a NaN row, which they skip and count.
+
+        A device-resident state stays device resident.  ``as_tensor=True``: the dict of device tensors of
+        ``ops.event_filter`` (``keep``, ``xy``, ``index``, ``count``, ``hot``, ``stats``, ``status``, ``last_t``), ordered on
+        the current stream, nothing synchronised.  Otherwise numpy arrays, which waits and raises when a pixel's events
+        decrease in time or lie before the state (the state is then left as it was)."""
+        out = self._filter("filter_events()", x, y, t, height, width)
+        if as_tensor:
+            self._filter_state = out["last_t"]             # (a bad order leaves NaN: every later call then has no state to hold against)
+            return out
+        _check_status("filter_events()", filter=out["status"])
+        self._filter_state = out["last_t"]
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    def _denoised(self, name, x, y, t):
+        """``denoise=True`` of an event query: (x, y, filter_status) with the filter's xy -- NaN rows for the dropped events --
+        in the place of the coordinates given.  The filter reads the state ``filter_events`` carries and leaves it as it is:
+        a query changes nothing, and several queries may be asked about the same events."""
+        if self._filter_params is None:
+            raise RuntimeError(name + ": denoise=True needs the filter's parameters (set_event_filter())")
+        out = self._filter(name, x, y, t)
+        return out["xy"][:, 0], out["xy"][:, 1], out["status"]
+
     # ---------------------------------------------------------------- lens distortion
     def set_camera(self, model, raw_intrinsics, coeffs=(), rotation=None):
         """The sensor the raw events and frames come from (``ops.camera``): ``model`` 'pinhole', 'radtan' or 'equidistant',
@@ -277,7 +347,7 @@ class TrackerQueries:
 
     def compensate_events(self, x, y, t, p, t_ref=None, invdepth=None, num_bins=0, extrapolate=False, want_xy=False,
                           want_iwe=True, stack=None, height=None, width=None, as_tensor=False, radius=None,
-                          weights="variance", distorted=False):
+                          weights="variance", distorted=False, denoise=False):
         """Motion compensation with the trajectory as it is now: every event (``x, y`` pixel coordinates of the images the
         tracker is fed, ``t`` in the unit of the frames' time stamps, ``p`` polarity) is warped from the camera pose at its
         own time stamp to the pose at ``t_ref`` and splat bilinearly into an image of warped events and / or a bin stack
@@ -292,13 +362,18 @@ class TrackerQueries:
         Intrinsics: row 0 of the tracker's own times the patch stride, i.e. those of the images it was fed.  ``height, width``
         default to the tracker's.  ``distorted=True``: ``x, y`` are RAW sensor pixels; they are rectified first
         (``rectify_events``, the camera of ``set_camera``; raises without one), the events without a solution are skipped and
-        counted like any NaN row, and the result gains ``rectify_status``.
+        counted like any NaN row, and the result gains ``rectify_status``.  ``denoise=True``: the events are filtered first
+        (``set_event_filter``; raises without one), in the coordinates given and ahead of the rectification; the dropped
+        events are NaN rows, skipped and counted, and the result gains ``filter_status``.  The filter's state is read, not
+        advanced (``filter_events`` does that).
 
         A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
         the dict of device tensors of ``ops.event_warp`` (``status``, ``xy``, ``iwe``, ``stack`` as requested), ordered on
         the current stream, nothing synchronised.  Otherwise numpy arrays, which waits for that result and raises when the
         frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
-        rect = None
+        rect = filt = None
+        if denoise:
+            x, y, filt = self._denoised("compensate_events()", x, y, t)
         if distorted:
             x, y, rect = self._undistorted("compensate_events()", x, y)
         knots, tdev, K, invdepth, t_ref, H, W = self._event_query("compensate_events()", t_ref, invdepth, radius, weights,
@@ -310,9 +385,11 @@ class TrackerQueries:
                                  want_iwe=want_iwe, stack=stack)
         if rect is not None:
             out["rectify_status"] = rect
+        if filt is not None:
+            out["filter_status"] = filt
         if as_tensor:
             return out
-        _check_status("compensate_events()", traj=self._traj_status, interp=out["status"], rectify=rect)
+        _check_status("compensate_events()", traj=self._traj_status, interp=out["status"], rectify=rect, filter=filt)
         return {k: v.cpu().numpy() for k, v in out.items()}
 
     def _event_query(self, name, t_ref, invdepth, radius, weights, height, width):
@@ -338,20 +415,23 @@ class TrackerQueries:
 
     def event_contrast(self, x, y, t, p, t_ref=None, invdepth=None, correction=None, signed=True, want_grad=True,
                        want_iwe=False, extrapolate=False, height=None, width=None, as_tensor=False, radius=None,
-                       weights="variance", distorted=False):
+                       weights="variance", distorted=False, denoise=False):
         """How sharp the compensated events are with the trajectory as it is now: the variance of the image of warped events
         ``compensate_events`` would return (the same events, poses, intrinsics and inverse depth -- ``invdepth`` as there,
         ``"map"`` included) and its gradient with respect to a small correction ``(v[3], w[3], lam)`` of velocity, rotation
         rate and log depth scale in the reference camera frame (``ops.event_contrast``).  The only figure of quality an
         event tracker can give about its own trajectory without ground truth.  ``distorted=True``: raw sensor pixels, as in
-        ``compensate_events``; the result gains ``rectify_status``.
+        ``compensate_events``; the result gains ``rectify_status``.  ``denoise=True``: filtered first, as there; the result
+        gains ``filter_status``.
 
         A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
         the dict of device tensors of ``ops.event_contrast`` (``variance``, ``stats``, ``sums``, ``status``, ``grad``, ``iwe``
         as requested), ordered on the current stream, nothing synchronised.  Otherwise numpy arrays (``variance`` a float),
         which waits for that result and raises when the frames' time stamps decrease or are not finite, or on trajectory()'s
         unresolved bit."""
-        rect = None
+        rect = filt = None
+        if denoise:
+            x, y, filt = self._denoised("event_contrast()", x, y, t)
         if distorted:
             x, y, rect = self._undistorted("event_contrast()", x, y)
         knots, tdev, K, invdepth, t_ref, H, W = self._event_query("event_contrast()", t_ref, invdepth, radius, weights,
@@ -363,24 +443,29 @@ class TrackerQueries:
                                      want_grad=want_grad, want_iwe=want_iwe)
         if rect is not None:
             out["rectify_status"] = rect
+        if filt is not None:
+            out["filter_status"] = filt
         if as_tensor:
             return out
-        _check_status("event_contrast()", traj=self._traj_status, interp=out["status"], rectify=rect)
+        _check_status("event_contrast()", traj=self._traj_status, interp=out["status"], rectify=rect, filter=filt)
         res = {k: v.cpu().numpy() for k, v in out.items()}
         res["variance"] = float(res["stats"][0])
         return res
 
     def align_events(self, x, y, t, p, t_ref=None, invdepth=None, correction=None, free=(0, 0, 0, 1, 1, 1, 0), step=0.05,
                      iters=20, signed=True, extrapolate=False, height=None, width=None, radius=None, weights="variance",
-                     distorted=False):
+                     distorted=False, denoise=False):
         """Refine the compensation by contrast maximisation (``ops.event_align``: a host loop of normalised gradient ascent
         with backtracking over ``event_contrast``, the components ``free`` marks -- by default the rotation rate).  The
         trajectory, intrinsics and inverse depth are read ONCE, as ``event_contrast`` reads them; every evaluation then reads
         8 + 7 doubles back, so this is a convenience between two frames, not a hot path.  A device-resident state stays
         device resident.  Returns ``ops.event_align``'s dict: ``correction``, ``variance``, ``variance0``, ``history``; raises
         on the conditions ``event_contrast`` raises on.  ``distorted=True``: raw sensor pixels, rectified once in front of the
-        loop; the result gains ``rectify_status`` (the words, on the host)."""
-        rect = None
+        loop; the result gains ``rectify_status`` (the words, on the host).  ``denoise=True``: filtered once in front of the
+        loop, as in ``compensate_events``; the result gains ``filter_status`` (the words, on the host)."""
+        rect = filt = None
+        if denoise:
+            x, y, filt = self._denoised("align_events()", x, y, t)
         if distorted:
             x, y, rect = self._undistorted("align_events()", x, y)
         knots, tdev, K, invdepth, t_ref, H, W = self._event_query("align_events()", t_ref, invdepth, radius, weights,
@@ -390,15 +475,18 @@ class TrackerQueries:
                                   self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
                                   invdepth, H, W, correction=correction, free=free, step=step, iters=iters, signed=signed,
                                   extrapolate=extrapolate)
-        _check_status("align_events()", traj=self._traj_status, rectify=rect)
+        _check_status("align_events()", traj=self._traj_status, rectify=rect, filter=filt)
         if rect is not None:
             out["rectify_status"] = rect.cpu().numpy()
+        if filt is not None:
+            out["filter_status"] = filt.cpu().numpy()
         if out["variance0"] != out["variance0"]:              # (NaN: the kernel's answer to bad time stamps)
             raise RuntimeError("align_events(): the frames' time stamps decrease or are not finite")
         return out
 
     def event_voxel_grid(self, x, y, t, p, num_bins=5, offsets=None, normalize=True, compensate=False, t_ref=None,
-                         invdepth=None, as_tensor=False, extrapolate=False, radius=None, weights="variance", distorted=False):
+                         invdepth=None, as_tensor=False, extrapolate=False, radius=None, weights="variance", distorted=False,
+                         denoise=False):
         """The reference's voxel-grid event representation at the tracker's image size (``ops.event_voxel_grid``: every event
         votes into the two time bins next to its normalised time stamp, each slice standardised over its non-zero cells):
         ``grid`` [S, num_bins, ht, wd] for the slices ``offsets`` (a device int64 tensor [S + 1], ``ops.event_slices``) marks,
@@ -414,16 +502,22 @@ class TrackerQueries:
         ``set_camera``) and splat bilinearly at their sub-pixel coordinates, compensated or not; the result gains
         ``rectify_status``.
 
+        ``denoise=True``: the events are filtered first (``set_event_filter``; raises without one), in the coordinates given
+        and ahead of the rectification; the dropped events are NaN rows, which the grid skips and counts in every mode; the
+        result gains ``filter_status``.  The filter's state is read, not advanced.
+
         A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
         the dict of device tensors of ``ops.event_voxel_grid`` (``grid``, ``stats``, ``status``; with ``compensate`` also
         ``warp_status``, the words of ``ops.event_warp``), ordered on the current stream, nothing synchronised.  Otherwise
         numpy arrays, which waits for that result and raises on offsets that decrease or leave the event list, on a slice
         whose first or last time stamp is not finite and, with ``compensate``, on the conditions ``compensate_events`` raises
         on."""
+        td, pd = self._as_device(t, torch.float64), self._as_device(p, torch.int8)
+        warp = rect = filt = None
+        if denoise:
+            x, y, filt = self._denoised("event_voxel_grid()", x, y, td)
         if not distorted:
             xd, yd = self._as_device(x, torch.float32), self._as_device(y, torch.float32)
-        td, pd = self._as_device(t, torch.float64), self._as_device(p, torch.int8)
-        warp = rect = None
         if distorted:
             xd, yd, rect = self._undistorted("event_voxel_grid()", x, y)
         if compensate:
@@ -438,10 +532,12 @@ class TrackerQueries:
             out["warp_status"] = warp["status"]
         if rect is not None:
             out["rectify_status"] = rect
+        if filt is not None:
+            out["filter_status"] = filt
         if as_tensor:
             return out
         _check_status("event_voxel_grid()", traj=self._traj_status if compensate else None, interp=out.get("warp_status"),
-                      voxel=out["status"], rectify=rect)
+                      voxel=out["status"], rectify=rect, filter=filt)
         return {k: v.cpu().numpy() for k, v in out.items()}
 
     def _depth_median_word(self, resident):
