@@ -1189,6 +1189,63 @@ int ramp_event_contrast(const float *x, const float *y, const double *t, const i
                         const float *correction, int flags, int H, int W, float *iwe, int64_t *sums, double *stats, double *grad,
                         void *ws, size_t ws_bytes, int32_t *status, void *stream);
 
+/* ramp_event_align: contrast maximisation on the device.  Normalised gradient ascent with backtracking over the evaluations of
+ * ramp_event_contrast (variance and gradient at a correction), the line search itself run by a one-wave kernel behind every
+ * evaluation: one call enqueues the whole alignment, nothing is read back, nothing synchronised.  The arguments up to
+ * `flags, H, W` are ramp_event_contrast's; `correction` is the start (device float [7], or NULL for zero).
+ *   free_mask  bit i frees component i of theta = (v[3], w[3], lam): mask[i] = 1.0 or 0.0
+ *   step       the first step length, in the units of theta;  iters: the accepted steps asked for
+ *   max_evals  the evaluations enqueued (clamped to 1 + 9 * iters, at which the budget can never bind)
+ * The definition is a state machine with one step per evaluation.  All state is float64 unless noted:
+ *     theta[7], f, g[7], f0, length, gm[7], norm, trial[7];  int32 n_accepted, n_evals, halvings, reason, seen;
+ *     history[iters];  the status[8] words of the evaluation at theta
+ *   Set-up: theta = the start, length = step, reason = 0; the evaluation reads float32(theta).
+ *   After evaluation e with its stats[0], grad[7], status[8]:
+ *     reason != 0: nothing.  Otherwise n_evals += 1, seen |= status[0], and
+ *     e == 0:                    f = f0 = stats[0], g = grad, keep status;  iters == 0 ? reason = ITERS : propose(new direction)
+ *     e > 0, ft = stats[0] > f:  theta = trial, f = ft, g = grad, keep status, history[n_accepted++] = f, length *= 2,
+ *                                halvings = 0;  n_accepted == iters ? reason = ITERS : propose(new direction)
+ *     e > 0 otherwise (a NaN ft among them):  length *= 0.5, halvings += 1;
+ *                                halvings == 9 ? reason = STALLED : propose(same direction): gm and norm as they are
+ *   propose(new direction): gm[i] = g[i] * mask[i];  norm = sqrt(((((((0.0 + gm0^2) + gm1^2) + ...) + gm6^2), the products
+ *     and sums rounded one by one in this order, sqrt correctly rounded;  not (norm > 0 && norm < inf): reason = FLAT, stop.
+ *   Both proposals: trial[i] = theta[i] + (length * gm[i]) / norm; the next evaluation reads float32(trial[i]), rounded to
+ *     nearest even, overflow to infinity allowed (RAMP_CONTRAST_BAD_CORRECTION then answers NaN: a rejected trial).
+ *   After the last evaluation a reason still 0 becomes BUDGET: theta is the last accepted point, a valid ascent result.
+ * Evaluations behind the one that set `reason` are enqueued all the same and return at their first statement (a device word
+ * the step kernel sets): empty launches.  The segment launch runs once, in front of evaluation 0, whose word 0 carries its
+ * RAMP_INTERP_BAD_TIMES bit.  That evaluation is then NaN, and NaN stops the machine at once (ITERS with iters == 0, FLAT
+ * otherwise: gm is NaN under any mask), so no later evaluation, whose memset would have cleared the bit, ever runs: `seen`
+ * and `status` carry it to the outputs whatever max_evals is.
+ *   Outputs, all on the device, all written by the step kernel of the last evaluation:
+ *     correction     float64 [7]     theta
+ *     correction_f32 float [7]       the bits the evaluation at theta read: ready for ramp_event_contrast
+ *     result         float64 [4]     f, f0, the final length, 0
+ *     grad           float64 [7]     g, the gradient at theta
+ *     history        float64 [iters] the accepted variances, NaN behind n_accepted (may be NULL when iters == 0)
+ *     status         int32 [8]       the words of the evaluation at theta
+ *     info           int32 [8]       [0] reason [1] n_accepted [2] n_evals [3] halvings [4] seen, the rest 0
+ *   The result is the bits of the same loop run on the host over ramp_event_contrast: the statistics are integer sums, grad
+ *   repeats its bits for equal arguments, and the loop's own arithmetic is the float64 operations written above.
+ *   N == 0: no contrast launches; the step kernel alone answers for the all-zero statistics (FLAT, n_evals = 1, variance 0,
+ *   the start).  ws: ramp_event_align_workspace_bytes(T, H, W) bytes, 16-byte aligned, at least
+ *   ramp_event_contrast_workspace_bytes; the float64 outputs 8-byte, the others 4-byte aligned.  Launches: the segment launch,
+ *   then per evaluation one hipMemsetAsync and five kernels, all on `stream`.
+ *   NULL or misaligned pointers, iters < 0 or > 65536, max_evals < 1, free_mask outside 7 bits, a step or t_ref that is not
+ *   finite, and what ramp_event_contrast refuses: RAMP_EINVAL; a short workspace: RAMP_EWORKSPACE.                        */
+#define RAMP_ALIGN_ITERS 1
+#define RAMP_ALIGN_STALLED 2
+#define RAMP_ALIGN_FLAT 3
+#define RAMP_ALIGN_BUDGET 4
+#define RAMP_ALIGN_MAX_ITERS 65536
+#define RAMP_ALIGN_TRIALS 9 /* the first trial of a direction and up to 8 halvings */
+size_t ramp_event_align_workspace_bytes(int T, int H, int W);
+int ramp_event_align(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
+                     const double *times, int T, double t_ref, const float *intrinsics, const float *invdepth,
+                     const float *correction, int flags, int H, int W, int free_mask, double step, int iters, int max_evals,
+                     double *correction_out, float *correction_f32, double *result, double *grad, double *history,
+                     int32_t *status, int32_t *info, void *ws, size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------- event voxel grids (csrc/voxel.hip)
  *
  * ramp_event_voxel: the reference's "voxels" event representation (utils/transformers.py:21-125,

@@ -25,6 +25,8 @@ RAMP_INTERP_EXTRAPOLATE, RAMP_INTERP_ROW_STORES, RAMP_INTERP_BAD_TIMES = 1, 2, 1
 RAMP_WARP_DEPTH_SCALAR, RAMP_WARP_DEPTH_MAP, RAMP_WARP_IDENTITY, RAMP_WARP_MIN_Z = 0, 4, 8, 0.2
 RAMP_DEPTHMAP_CONF_IS_VARIANCE, RAMP_DEPTHMAP_PRIOR_RELATIVE, RAMP_DEPTHMAP_BAD_CAM = 1, 2, 1
 RAMP_CONTRAST_UNSIGNED, RAMP_CONTRAST_BAD_CORRECTION = 16, 2
+RAMP_ALIGN_ITERS, RAMP_ALIGN_STALLED, RAMP_ALIGN_FLAT, RAMP_ALIGN_BUDGET = 1, 2, 3, 4
+RAMP_ALIGN_MAX_ITERS, RAMP_ALIGN_TRIALS = 65536, 9
 RAMP_VOXEL_NORMALIZE, RAMP_VOXEL_SUBPIXEL, RAMP_VOXEL_BAD_OFFSETS, RAMP_VOXEL_BAD_TIMES = 1, 2, 1, 2
 # the camera record of csrc/rectify.hip: word offsets, models, flags, value modes
 RAMP_CAMERA_WORDS, RAMP_CAMERA_RAW, RAMP_CAMERA_MODEL, RAMP_CAMERA_COEFFS, RAMP_CAMERA_ROTATION, RAMP_CAMERA_NEW = 32, 0, 4, 5, 12, 24
@@ -203,6 +205,9 @@ SIGNATURES = {
     "ramp_event_contrast_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "ramp_event_contrast": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, ctypes.c_double, c_p, c_p, c_p, c_i, c_i, c_i,
                                   c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
+    "ramp_event_align_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "ramp_event_align": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, ctypes.c_double, c_p, c_p, c_p, c_i, c_i, c_i,
+                               c_i, ctypes.c_double, c_i, c_i] + [c_p] * 7 + [c_p, c_sz, c_p]),
     # event voxel grids (csrc/voxel.hip)
     "ramp_event_voxel_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
     "ramp_event_voxel_grid_events": (ctypes.c_long, []),

@@ -16,6 +16,8 @@
 //   dx'/dX2 = (fx / Z, 0, -fx X / Z^2)        dy'/dX2 = (0, fy / Z, -fy Y / Z^2)
 //   dX2/dv  = tau ds I_3         dX2/dw . r = tau (r x X1)         dX2/dlam = t_G ds + tau (v ds + w x (t_G ds))
 //
+// ramp_event_align runs the line search over these evaluations on the device: align_step_kernel behind each of them (below).
+//
 // At most five launches behind one memset of the counters and accumulators:
 //   the segment launch   of the event warp (ramp_i_warp_segments)
 //   contrast_event_kernel<false>  the warp's splat with the correction: the same fixed point, the same staging and counters;
@@ -51,6 +53,7 @@ struct ConArgs {
   double *rows;                          // [grid][CON_ROW_WORDS]
   double t_ref;
   int N, T, H, W, extrapolate, depth_map, plane;
+  const int32_t *done;                   // optional: a device word; not zero: every launch of the evaluation returns at once
 };
 
 static __device__ __forceinline__ double con_wave_sum(double v) {
@@ -77,6 +80,7 @@ __global__ void __launch_bounds__(INTERP_THREADS) contrast_event_kernel(const Co
   __shared__ float s_cor[8];
   __shared__ double s_range[2];
   __shared__ double s_red[GRAD ? CON_WAVES * CON_ROW_WORDS : 1];
+  if (a.done && *a.done) return;                     // (wave-uniform: an alignment that has stopped)
   double *s_times = reinterpret_cast<double *>(con_smem);
   const int tid = threadIdx.x;
   const int N = a.N, T = a.T, H = a.H, W = a.W;
@@ -257,8 +261,9 @@ __global__ void __launch_bounds__(INTERP_THREADS) contrast_event_kernel(const Co
 // accumulators -> iwe, and per workgroup the partial sums of I^2 and (I - mu)^2 over the plane the statistics are taken from
 __global__ void __launch_bounds__(256)
     contrast_finish_kernel(const long long *__restrict__ acc, const int32_t *__restrict__ ctr, float *__restrict__ iwe, long HW,
-                           int plane, double *__restrict__ fin) {
+                           int plane, double *__restrict__ fin, const int32_t *__restrict__ done) {
   __shared__ double s_red[2 * CON_WAVES];
+  if (done && *done) return;
   const int tid = threadIdx.x;
   const bool failed = (ctr[0] & (RAMP_INTERP_BAD_TIMES | RAMP_CONTRAST_BAD_CORRECTION)) != 0;
   const float qnan = __int_as_float(0x7fc00000), scale = 1.0f / (float)(1 << WARP_FIX_BITS);
@@ -290,7 +295,8 @@ __global__ void __launch_bounds__(256)
 __global__ void __launch_bounds__(RAMP_WAVE)
     contrast_final_kernel(const int32_t *__restrict__ ctr, const double *__restrict__ fin, int n_fin, const double *__restrict__ rows,
                           int n_rows, long HW, int plane, long long *__restrict__ sums, double *__restrict__ stats,
-                          double *__restrict__ grad, int32_t *__restrict__ status) {
+                          double *__restrict__ grad, int32_t *__restrict__ status, const int32_t *__restrict__ done) {
+  if (done && *done) return;
   const int tid = threadIdx.x;
   const int32_t word = ctr[0];
   const bool failed = (word & (RAMP_INTERP_BAD_TIMES | RAMP_CONTRAST_BAD_CORRECTION)) != 0;
@@ -337,6 +343,173 @@ static int con_launch_events(const ConArgs &a, bool lds_times, bool vec, int gri
   return RAMP_OK;
 }
 
+// one evaluation: the memset of the counters (the two sums among them) and, behind them, the accumulators; the segment launch
+// when `segments`; the splat, the finish, the gradient when `grad`, the final kernel
+static int con_evaluate(const ConArgs &a, bool segments, float *iwe, long long *sums, double *stats, double *grad, int32_t *status,
+                        hipStream_t st) {
+  const size_t HW = (size_t)a.H * a.W;
+  double *fin = (double *)(a.acc + 2 * HW);
+  if (hipMemsetAsync(a.ctr, 0, WARP_CTR_WORDS * sizeof(int32_t) + 2 * HW * sizeof(long long), st) != hipSuccess) return RAMP_ELAUNCH;
+  int rc = RAMP_OK;
+  if (segments) {
+    rc = ramp_i_warp_segments(a.knots, a.times, a.T, a.t_ref, a.extrapolate, const_cast<float *>(a.seg), const_cast<float *>(a.ref),
+                              a.ctr, st);
+    if (rc != RAMP_OK) return rc;
+  }
+  const long tiles = ((long)a.N + WARP_TILE - 1) / WARP_TILE;
+  const int grid = (int)(tiles < WARP_MAX_GROUPS ? tiles : WARP_MAX_GROUPS);
+  const bool vec = (((uintptr_t)a.x | (uintptr_t)a.y | (uintptr_t)a.p | (uintptr_t)a.t) & 15) == 0;
+  const bool lds_times = a.T <= INTERP_LDS_KNOTS;
+  rc = con_launch_events<false>(a, lds_times, vec, grid, st);
+  if (rc != RAMP_OK) return rc;
+  const int n_fin = con_fin_groups((long)HW);
+  hipLaunchKernelGGL(contrast_finish_kernel, dim3(n_fin), dim3(256), 0, st, a.acc, a.ctr, iwe, (long)HW, a.plane, fin, a.done);
+  RAMP_CHECK_LAUNCH();
+  if (grad) {
+    rc = con_launch_events<true>(a, lds_times, vec, grid, st);
+    if (rc != RAMP_OK) return rc;
+  }
+  hipLaunchKernelGGL(contrast_final_kernel, dim3(1), dim3(RAMP_WAVE), 0, st, a.ctr, fin, n_fin, a.rows, grad ? grid : 0, (long)HW,
+                     a.plane, sums, stats, grad, status, a.done);
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+
+// the arguments both entries share -> ConArgs over the workspace layout: seg, ref | ctr | acc | fin | rows
+static ConArgs con_arguments(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
+                             const double *times, int T, double t_ref, const float *intrinsics, const float *invdepth,
+                             const float *correction, int flags, int H, int W, void *ws) {
+  const size_t HW = (size_t)H * W;
+  unsigned char *base = (unsigned char *)ws;
+  float *seg = (float *)base, *ref = seg + (size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS;
+  int32_t *ctr = (int32_t *)(base + warp_acc_offset(T));
+  long long *acc = (long long *)(ctr + WARP_CTR_WORDS);
+  double *fin = (double *)(acc + 2 * HW), *rows = fin + (size_t)CON_FIN_MAX_GROUPS * 2;
+  ConArgs a;
+  a.x = x; a.y = y; a.t = t; a.p = p; a.knots = knots; a.times = times; a.seg = seg; a.ref = ref;
+  a.intrinsics = intrinsics; a.invdepth = invdepth; a.correction = correction; a.acc = acc; a.ctr = ctr; a.rows = rows;
+  a.t_ref = t_ref; a.N = N; a.T = T; a.H = H; a.W = W; a.extrapolate = (flags & RAMP_INTERP_EXTRAPOLATE) ? 1 : 0;
+  a.depth_map = (flags & RAMP_WARP_DEPTH_MAP) ? 1 : 0;
+  a.plane = (flags & RAMP_CONTRAST_UNSIGNED) ? 1 : 0;
+  a.done = nullptr;
+  return a;
+}
+
+// ---------------------------------------------------------------------------------------------------- the line search
+// The state machine of include/ramp_hip.h (ramp_event_align), one step behind every evaluation.  The block lives behind the
+// contrast's own workspace; the front of the entry zeroes it and copies the start into `cor`.
+struct AlignState {
+  double theta[7], f, g[7], f0, length, gm[7], norm, trial[7];
+  int32_t n_accepted, n_evals, halvings, reason, seen, spare[3];
+  int32_t status[8];                     // the words of the evaluation at theta
+  int32_t done[4];                       // [0]: reason != 0, the word the contrast launches read
+  float cor[8];                          // the correction the next evaluation reads: float32(theta), then float32(trial)
+  float cor_theta[8];                    // the bits the evaluation at theta read
+  double e_stats[8], e_grad[8];          // what one evaluation writes
+  long long e_sums[2];
+  int32_t e_status[8];
+};
+
+struct AlignOut {
+  double *correction;
+  float *correction_f32;
+  double *result, *grad, *history;
+  int32_t *status, *info;
+};
+
+// One wave.  Every lane loads the whole state and takes every decision itself (uniform loads, no shuffles, no LDS): the
+// arithmetic below is the definition's, in its order, once per lane; lane i < 7 then stores component i, lanes < 8 the status
+// words, lane 0 the scalars.  e: the index of the evaluation in front; empty: N == 0, the all-zero statistics.
+__global__ void __launch_bounds__(RAMP_WAVE)
+    align_step_kernel(AlignState *__restrict__ s, int e, int last, int iters, int free_mask, double step, int empty,
+                      const AlignOut out) {
+  const int lane = threadIdx.x;
+  int reason = s->reason;
+  if (reason != 0 && !last) return;
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  double theta[7], g[7], gm[7], trial[7];
+#pragma unroll
+  for (int i = 0; i < 7; i++) { theta[i] = s->theta[i]; g[i] = s->g[i]; gm[i] = s->gm[i]; trial[i] = s->trial[i]; }
+  double f = s->f, f0 = s->f0, length = s->length, norm = s->norm;
+  int n_accepted = s->n_accepted, n_evals = s->n_evals, halvings = s->halvings, seen = s->seen;
+  if (reason == 0) {
+    const double ft = empty ? 0.0 : s->e_stats[0];
+    const int word0 = empty ? 0 : s->e_status[0];
+    n_evals += 1;
+    seen |= word0;
+    bool take;
+    if (e == 0) {
+#pragma unroll
+      for (int i = 0; i < 7; i++) theta[i] = (double)s->cor[i];
+      length = step;
+      f = f0 = ft;
+      take = true;
+      for (int i = lane; i < iters; i += RAMP_WAVE) out.history[i] = qnan;
+      if (iters == 0) reason = RAMP_ALIGN_ITERS;
+    } else if (ft > f) {                               // (a NaN ft is not greater)
+#pragma unroll
+      for (int i = 0; i < 7; i++) theta[i] = trial[i];
+      f = ft;
+      take = true;
+      if (lane == 0) out.history[n_accepted] = f;
+      n_accepted += 1;
+      length *= 2.0;
+      halvings = 0;
+      if (n_accepted == iters) reason = RAMP_ALIGN_ITERS;
+    } else {
+      take = false;
+      length *= 0.5;
+      halvings += 1;
+      if (halvings == RAMP_ALIGN_TRIALS) reason = RAMP_ALIGN_STALLED;
+    }
+    if (take) {
+#pragma unroll
+      for (int i = 0; i < 7; i++) g[i] = empty ? 0.0 : s->e_grad[i];
+      if (lane < 8) {
+        s->status[lane] = empty ? 0 : s->e_status[lane];
+        s->cor_theta[lane] = s->cor[lane];
+      }
+      if (reason == 0) {                               // propose(new direction)
+        double sum = 0.0;
+#pragma unroll
+        for (int i = 0; i < 7; i++) {
+          gm[i] = g[i] * ((free_mask >> i) & 1 ? 1.0 : 0.0);
+          sum = sum + gm[i] * gm[i];
+        }
+        norm = sqrt(sum);
+        if (!(norm > 0.0 && norm < __longlong_as_double(0x7ff0000000000000ll))) reason = RAMP_ALIGN_FLAT;
+      }
+    }
+    if (reason == 0) {
+#pragma unroll
+      for (int i = 0; i < 7; i++) trial[i] = theta[i] + (length * gm[i]) / norm;
+    }
+    if (last && reason == 0) reason = RAMP_ALIGN_BUDGET;
+#pragma unroll
+    for (int i = 0; i < 7; i++)
+      if (lane == i) {
+        s->theta[i] = theta[i]; s->g[i] = g[i]; s->gm[i] = gm[i]; s->trial[i] = trial[i];
+        if (reason == 0) s->cor[i] = (float)trial[i];  // round to nearest even; overflow to infinity is the contrast's to answer
+      }
+    if (lane == 0) {
+      s->f = f; s->f0 = f0; s->length = length; s->norm = norm;
+      s->n_accepted = n_accepted; s->n_evals = n_evals; s->halvings = halvings; s->reason = reason; s->seen = seen;
+      s->done[0] = reason != 0;
+    }
+  }
+  if (!last) return;
+#pragma unroll
+  for (int i = 0; i < 7; i++)
+    if (lane == i) { out.correction[i] = theta[i]; out.grad[i] = g[i]; out.correction_f32[i] = s->cor_theta[i]; }
+  if (lane < 8) {
+    out.status[lane] = s->status[lane];                // (this lane's own stores above, or an earlier launch's)
+    out.info[lane] = lane == 0 ? reason : lane == 1 ? n_accepted : lane == 2 ? n_evals : lane == 3 ? halvings : lane == 4 ? seen : 0;
+  }
+  if (lane < 4) out.result[lane] = lane == 0 ? f : lane == 1 ? f0 : lane == 2 ? length : 0.0;
+}
+
+static size_t align_state_offset(int T, int H, int W) { return (ramp_event_contrast_workspace_bytes(T, H, W) + 15) & ~(size_t)15; }
+
 extern "C" {
 size_t ramp_event_contrast_workspace_bytes(int T, int H, int W) {
   if (H < 1 || W < 1) return 0;
@@ -356,40 +529,50 @@ int ramp_event_contrast(const float *x, const float *y, const double *t, const i
   if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)sums & 7) != 0 || ((uintptr_t)stats & 7) != 0 || ((uintptr_t)grad & 7) != 0)
     return RAMP_EINVAL;
   if (ws_bytes < ramp_event_contrast_workspace_bytes(T, H, W)) return RAMP_EWORKSPACE;
+  const ConArgs a = con_arguments(x, y, t, p, N, knots, times, T, t_ref, intrinsics, invdepth, correction, flags, H, W, ws);
+  return con_evaluate(a, true, iwe, (long long *)sums, stats, grad, status, (hipStream_t)stream);
+}
+
+size_t ramp_event_align_workspace_bytes(int T, int H, int W) {
+  if (T < 1 || H < 1 || W < 1) return 0;
+  return align_state_offset(T, H, W) + sizeof(AlignState);
+}
+
+int ramp_event_align(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
+                     const double *times, int T, double t_ref, const float *intrinsics, const float *invdepth,
+                     const float *correction, int flags, int H, int W, int free_mask, double step, int iters, int max_evals,
+                     double *correction_out, float *correction_f32, double *result, double *grad, double *history,
+                     int32_t *status, int32_t *info, void *ws, size_t ws_bytes, void *stream) {
+  if (N < 0 || T < 1 || H < 1 || W < 1) return RAMP_EINVAL;
+  if (flags & ~(RAMP_INTERP_EXTRAPOLATE | RAMP_WARP_DEPTH_MAP | RAMP_CONTRAST_UNSIGNED)) return RAMP_EINVAL;
+  if (!(fabs(t_ref) <= 1.7976931348623157e308) || !(fabs(step) <= 1.7976931348623157e308)) return RAMP_EINVAL;
+  if (iters < 0 || iters > RAMP_ALIGN_MAX_ITERS || max_evals < 1 || (free_mask & ~127) != 0) return RAMP_EINVAL;
+  if (N > 0 && (!x || !y || !t || !p || !knots || !times || !intrinsics || !invdepth)) return RAMP_EINVAL;
+  if (!correction_out || !correction_f32 || !result || !grad || (!history && iters > 0) || !status || !info || !ws) return RAMP_EINVAL;
+  if (((uintptr_t)ws & 15) != 0 || (((uintptr_t)correction_out | (uintptr_t)result | (uintptr_t)grad | (uintptr_t)history) & 7) != 0 ||
+      (((uintptr_t)correction | (uintptr_t)correction_f32 | (uintptr_t)status | (uintptr_t)info) & 3) != 0)
+    return RAMP_EINVAL;
+  if (ws_bytes < ramp_event_align_workspace_bytes(T, H, W)) return RAMP_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const size_t HW = (size_t)H * W;
-  unsigned char *base = (unsigned char *)ws;
-  float *seg = (float *)base, *ref = seg + (size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS;
-  int32_t *ctr = (int32_t *)(base + warp_acc_offset(T));
-  long long *acc = (long long *)(ctr + WARP_CTR_WORDS);
-  double *fin = (double *)(acc + 2 * HW), *rows = fin + (size_t)CON_FIN_MAX_GROUPS * 2;
-  // the one memset: the counters (the two sums among them) and, behind them, the accumulators
-  if (hipMemsetAsync(ctr, 0, WARP_CTR_WORDS * sizeof(int32_t) + 2 * HW * sizeof(long long), st) != hipSuccess) return RAMP_ELAUNCH;
-  const int ex = (flags & RAMP_INTERP_EXTRAPOLATE) ? 1 : 0;
-  int rc = ramp_i_warp_segments(knots, times, T, t_ref, ex, seg, ref, ctr, st);
-  if (rc != RAMP_OK) return rc;
-  ConArgs a;
-  a.x = x; a.y = y; a.t = t; a.p = p; a.knots = knots; a.times = times; a.seg = seg; a.ref = ref;
-  a.intrinsics = intrinsics; a.invdepth = invdepth; a.correction = correction; a.acc = acc; a.ctr = ctr; a.rows = rows;
-  a.t_ref = t_ref; a.N = N; a.T = T; a.H = H; a.W = W; a.extrapolate = ex;
-  a.depth_map = (flags & RAMP_WARP_DEPTH_MAP) ? 1 : 0;
-  a.plane = (flags & RAMP_CONTRAST_UNSIGNED) ? 1 : 0;
-  const long tiles = ((long)N + WARP_TILE - 1) / WARP_TILE;
-  const int grid = (int)(tiles < WARP_MAX_GROUPS ? tiles : WARP_MAX_GROUPS);
-  const bool vec = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)p | (uintptr_t)t) & 15) == 0;
-  const bool lds_times = T <= INTERP_LDS_KNOTS;
-  rc = con_launch_events<false>(a, lds_times, vec, grid, st);
-  if (rc != RAMP_OK) return rc;
-  const int n_fin = con_fin_groups((long)HW);
-  hipLaunchKernelGGL(contrast_finish_kernel, dim3(n_fin), dim3(256), 0, st, acc, ctr, iwe, (long)HW, a.plane, fin);
-  RAMP_CHECK_LAUNCH();
-  if (grad) {
-    rc = con_launch_events<true>(a, lds_times, vec, grid, st);
-    if (rc != RAMP_OK) return rc;
+  const int need = 1 + RAMP_ALIGN_TRIALS * iters;
+  const int evals = N == 0 ? 1 : (max_evals < need ? max_evals : need);
+  AlignState *s = (AlignState *)((unsigned char *)ws + align_state_offset(T, H, W));
+  // the invariant front: the state zeroed (reason 0, the done word 0), the start in the buffer evaluation 0 reads
+  if (hipMemsetAsync(s, 0, sizeof(AlignState), st) != hipSuccess) return RAMP_ELAUNCH;
+  if (correction && hipMemcpyAsync(s->cor, correction, 7 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return RAMP_ELAUNCH;
+  ConArgs a = con_arguments(x, y, t, p, N, knots, times, T, t_ref, intrinsics, invdepth, s->cor, flags, H, W, ws);
+  a.done = s->done;
+  const AlignOut out = {correction_out, correction_f32, result, grad, history, status, info};
+  for (int e = 0; e < evals; e++) {
+    if (N > 0) {
+      const int rc = con_evaluate(a, e == 0, nullptr, s->e_sums, s->e_stats, s->e_grad, s->e_status, st);
+      if (rc != RAMP_OK) return rc;
+    }
+    hipLaunchKernelGGL(align_step_kernel, dim3(1), dim3(RAMP_WAVE), 0, st, s, e, e == evals - 1 ? 1 : 0, iters, free_mask, step,
+                       N == 0 ? 1 : 0, out);
+    RAMP_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(contrast_final_kernel, dim3(1), dim3(RAMP_WAVE), 0, st, ctr, fin, n_fin, rows, grad ? grid : 0, (long)HW,
-                     a.plane, (long long *)sums, stats, grad, status);
-  RAMP_CHECK_LAUNCH();
   return RAMP_OK;
 }
 }  // extern "C"

@@ -588,27 +588,88 @@ def align_loop(evaluate, correction, free, step, iters):
     return dict(correction=theta, variance=f, variance0=f0, history=history)
 
 
-def event_align(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=None,
-                free=(0, 0, 0, 1, 1, 1, 0), step=0.05, iters=20, signed=True, extrapolate=False):
-    """Refine a correction by contrast maximisation: a HOST loop over ``event_contrast`` (``align_loop``: normalised gradient
-    ascent with backtracking over the components ``free`` marks; the default frees the rotation rate).  Every evaluation
-    reads 8 + 7 doubles back (the statistics and the gradient: one synchronisation each), so this is a convenience for a few
-    dozen evaluations, not a hot path.  ``step``: the first step length, in the units of ``theta`` (a rate per unit of the
-    time stamps).
+ALIGN_REASONS = {0: "running", _lib.RAMP_ALIGN_ITERS: "iters", _lib.RAMP_ALIGN_STALLED: "stalled", _lib.RAMP_ALIGN_FLAT: "flat",
+                 _lib.RAMP_ALIGN_BUDGET: "budget"}
 
-    Returns a dict: ``correction`` (list of 7 floats), ``variance``, ``variance0`` (at the start) and ``history`` (the accepted
-    variances, strictly rising)."""
+
+def event_align(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=None,
+                free=(0, 0, 0, 1, 1, 1, 0), step=0.05, iters=20, signed=True, extrapolate=False, resident=False, max_evals=None):
+    """Refine a correction by contrast maximisation: normalised gradient ascent with backtracking over ``event_contrast``, over
+    the components ``free`` marks (the default frees the rotation rate).  ``step``: the first step length, in the units of
+    ``theta`` (a rate per unit of the time stamps).
+
+    ``resident=False``: a HOST loop (``align_loop``).  Every evaluation reads 8 + 7 doubles back (the statistics and the
+    gradient: one synchronisation each), so this form is a convenience for a few dozen evaluations, not a hot path.  Returns
+    a dict: ``correction`` (list of 7 floats), ``variance``, ``variance0`` (at the start) and ``history`` (the accepted
+    variances, strictly rising).
+
+    ``resident=True``: the same loop on the device (include/ramp_hip.h ``ramp_event_align``): one C call enqueues the whole
+    alignment, ordered on the current stream, nothing is read back and nothing synchronised.  The arguments are checked as
+    ``event_contrast`` checks them; the start is read as float32, as every evaluation reads its correction.  ``max_evals``:
+    the evaluations enqueued; None means ``1 + 9 * iters``, with which the answer is the host loop's bit for bit; a smaller
+    budget ends with reason ``budget`` at the last accepted point.  Nobody has tuned this default: evaluations behind the
+    end of the search are empty launches, which still cost their enqueue.  Returns a dict of device tensors: ``correction``
+    float64 [7], ``correction_f32`` float32 [7] (the bits the evaluation at ``correction`` read: pass it to
+    ``event_contrast(correction=...)``), ``variance`` and ``variance0`` (0-d views of ``result`` float64 [4]: variance,
+    variance0, the final step length, 0), ``grad`` float64 [7] at ``correction``, ``history`` float64 [iters] (NaN behind the
+    accepted steps), ``status`` int32 [8] (the words of the evaluation at ``correction``) and ``info`` int32 [8]
+    (``event_align_info``)."""
     if len(free) != 7:
         raise RuntimeError("event_align: free marks the 7 components of (v[3], w[3], lam)")
+    if not resident:
+        if max_evals is not None:
+            raise RuntimeError("event_align: max_evals belongs to resident=True")
 
-    def evaluate(theta):
-        r = event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=theta,
-                           signed=signed, extrapolate=extrapolate)
-        both = torch.cat([r["stats"], r["grad"]]).cpu().tolist()           # (the 8 + 7 doubles)
-        return both[0], both[8:]
+        def evaluate(theta):
+            r = event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=theta,
+                               signed=signed, extrapolate=extrapolate)
+            both = torch.cat([r["stats"], r["grad"]]).cpu().tolist()           # (the 8 + 7 doubles)
+            return both[0], both[8:]
 
-    return align_loop(evaluate, [0.0] * 7 if correction is None else torch.as_tensor(correction).reshape(-1).tolist(), free,
-                      step, iters)
+        return align_loop(evaluate, [0.0] * 7 if correction is None else torch.as_tensor(correction).reshape(-1).tolist(), free,
+                          step, iters)
+    xf, yf, tf, pi, knots, times, K, d, flags = _event_arguments("event_align", x, y, t, p, knots, times, intrinsics,
+                                                                 invdepth, height, width, extrapolate)
+    dev, N, T = xf.device, xf.shape[0], knots.shape[0]
+    if not signed:
+        flags |= _lib.RAMP_CONTRAST_UNSIGNED
+    if correction is None:
+        cor = None
+    else:
+        cor = torch.as_tensor(correction, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+        if cor.numel() != 7:
+            raise RuntimeError("event_align: a correction is (v[3], w[3], lam): 7 numbers")
+    iters = int(iters)
+    if iters < 0 or iters > _lib.RAMP_ALIGN_MAX_ITERS:
+        raise RuntimeError("event_align: iters is 0 .. %d" % _lib.RAMP_ALIGN_MAX_ITERS)
+    need = 1 + _lib.RAMP_ALIGN_TRIALS * iters
+    max_evals = need if max_evals is None else int(max_evals)
+    if max_evals < 1:
+        raise RuntimeError("event_align: max_evals is at least 1")
+    res = {"correction": torch.zeros(7, dtype=torch.float64, device=dev),
+           "correction_f32": torch.zeros(7, dtype=torch.float32, device=dev),
+           "result": torch.zeros(4, dtype=torch.float64, device=dev), "grad": torch.zeros(7, dtype=torch.float64, device=dev),
+           "history": torch.zeros(iters, dtype=torch.float64, device=dev),
+           "status": torch.zeros(8, dtype=torch.int32, device=dev), "info": torch.zeros(8, dtype=torch.int32, device=dev)}
+    res["variance"], res["variance0"] = res["result"][0], res["result"][1]
+    nbytes = lib().ramp_event_align_workspace_bytes(T, height, width)
+    ws = _lib_workspace(nbytes, dev, "evcontrast")
+    check(lib().ramp_event_align(ptr(xf), ptr(yf), ptr(tf), ptr(pi), N, ptr(knots), ptr(times), T, float(t_ref), ptr(K), ptr(d),
+                                 ptr(cor), flags, height, width, sum(1 << i for i, f in enumerate(free) if f), float(step),
+                                 iters, min(max_evals, need), ptr(res["correction"]), ptr(res["correction_f32"]),
+                                 ptr(res["result"]), ptr(res["grad"]), ptr(res["history"]) if iters else None,
+                                 ptr(res["status"]), ptr(res["info"]), ptr(ws), nbytes, stream()), "ramp_event_align")
+    return res
+
+
+def event_align_info(info):
+    """the info words of ramp_event_align as a dict (synchronises: one 32-byte copy); ``reason``: ``iters`` (the accepted
+    steps asked for), ``stalled`` (a direction failed its 9 trials), ``flat`` (a masked gradient that is zero or not finite)
+    or ``budget`` (``max_evals`` ran out)"""
+    w = info.detach().cpu()
+    return dict(reason=ALIGN_REASONS.get(int(w[0]), "unknown"), n_accepted=int(w[1]), n_evals=int(w[2]), halvings=int(w[3]),
+                seen=int(w[4]), bad_times=bool(int(w[4]) & _lib.RAMP_INTERP_BAD_TIMES),
+                bad_correction=bool(int(w[4]) & _lib.RAMP_CONTRAST_BAD_CORRECTION))
 
 
 def invdepth_map(poses, patches, intrinsics, cam, height, width, radius, scale=1, index=None, count=None, conf=None,

@@ -67,7 +67,11 @@ def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=No
     if not given:
         return
     first = given[0][1] if len(given) == 1 else torch.cat([s for _, s in given])
-    word = dict(zip((k for k, _ in given), first.cpu().tolist()))          # (the one wait)
+    _raise_on_words(name, dict(zip((k for k, _ in given), first.cpu().tolist())))          # (the one wait)
+
+
+def _raise_on_words(name, word):
+    """``_check_status`` behind its copy: ``word`` maps its argument names to word 0 of each, on the host"""
     if word.get("filter", 0) & _lib.RAMP_FILTER_BAD_ORDER:
         raise RuntimeError(name + ": a pixel's events decrease in time, or lie before the filter's state")
     if word.get("rectify", 0) & _lib.RAMP_RECTIFY_BAD_CAMERA:
@@ -454,15 +458,25 @@ class TrackerQueries:
 
     def align_events(self, x, y, t, p, t_ref=None, invdepth=None, correction=None, free=(0, 0, 0, 1, 1, 1, 0), step=0.05,
                      iters=20, signed=True, extrapolate=False, height=None, width=None, radius=None, weights="variance",
-                     distorted=False, denoise=False):
-        """Refine the compensation by contrast maximisation (``ops.event_align``: a host loop of normalised gradient ascent
-        with backtracking over ``event_contrast``, the components ``free`` marks -- by default the rotation rate).  The
-        trajectory, intrinsics and inverse depth are read ONCE, as ``event_contrast`` reads them; every evaluation then reads
-        8 + 7 doubles back, so this is a convenience between two frames, not a hot path.  A device-resident state stays
-        device resident.  Returns ``ops.event_align``'s dict: ``correction``, ``variance``, ``variance0``, ``history``; raises
-        on the conditions ``event_contrast`` raises on.  ``distorted=True``: raw sensor pixels, rectified once in front of the
-        loop; the result gains ``rectify_status`` (the words, on the host).  ``denoise=True``: filtered once in front of the
-        loop, as in ``compensate_events``; the result gains ``filter_status`` (the words, on the host)."""
+                     distorted=False, denoise=False, resident=False, max_evals=None, as_tensor=False):
+        """Refine the compensation by contrast maximisation (``ops.event_align``: normalised gradient ascent with
+        backtracking over ``event_contrast``, the components ``free`` marks -- by default the rotation rate).  The
+        trajectory, intrinsics and inverse depth are read ONCE, as ``event_contrast`` reads them.  A device-resident state
+        stays device resident on every path.  ``distorted=True``: raw sensor pixels, rectified once in front of the loop; the
+        result gains ``rectify_status``.  ``denoise=True``: filtered once in front of the loop, as in ``compensate_events``;
+        the result gains ``filter_status``.
+
+        ``resident=False``: the host loop; every evaluation reads 8 + 7 doubles back, so this form is a convenience between
+        two frames, not a hot path.  Returns ``ops.event_align``'s dict: ``correction``, ``variance``, ``variance0``,
+        ``history`` (the status words on the host); raises on the conditions ``event_contrast`` raises on.
+
+        ``resident=True``: the loop runs on the device (one C call, ``max_evals`` as in ``ops.event_align``) and ONE read at
+        the end gives the same keys plus ``reason`` (``ops.event_align_info``), ``n_evals`` and ``n_accepted``; ``correction``
+        a list of 7 floats, ``history`` a list cut at ``n_accepted``.  Raises on the same conditions.  ``as_tensor=True``
+        (implies ``resident``): the dict of device tensors of ``ops.event_align(resident=True)``, ordered on the current
+        stream; nothing is synchronised and nothing raised, as ``event_contrast(as_tensor=True)``: ``correction_f32`` goes
+        straight into ``event_contrast(correction=...)``."""
+        resident = resident or as_tensor
         rect = filt = None
         if denoise:
             x, y, filt = self._denoised("align_events()", x, y, t)
@@ -474,7 +488,30 @@ class TrackerQueries:
             out = ops.event_align(self._as_device(x, torch.float32), self._as_device(y, torch.float32),
                                   self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
                                   invdepth, H, W, correction=correction, free=free, step=step, iters=iters, signed=signed,
-                                  extrapolate=extrapolate)
+                                  extrapolate=extrapolate, resident=resident, max_evals=max_evals)
+        if as_tensor:
+            if rect is not None:
+                out["rectify_status"] = rect
+            if filt is not None:
+                out["filter_status"] = filt
+            return out
+        if resident:
+            # the one read: every word is an int32 or a double, so one float64 row holds them all exactly
+            extra = [(k, s) for k, s in (("traj", self._traj_status), ("rectify", rect), ("filter", filt)) if s is not None]
+            with torch.no_grad():
+                row = torch.cat([out["correction"], out["result"], out["info"].double(), out["history"]]
+                                + [s.reshape(-1).double() for _, s in extra]).cpu().tolist()
+            info, tail = [int(v) for v in row[11:19]], row[19 + int(iters):]
+            word, res = {"interp": info[4]}, {}
+            for k, s in extra:
+                words, tail = [int(v) for v in tail[:s.numel()]], tail[s.numel():]
+                word[k] = words[0]
+                if k != "traj":
+                    res[k + "_status"] = np.asarray(words, np.int32)
+            _raise_on_words("align_events()", word)
+            res.update(correction=row[:7], variance=row[7], variance0=row[8], history=row[19:19 + info[1]],
+                       reason=ops.ALIGN_REASONS.get(info[0], "unknown"), n_evals=info[2], n_accepted=info[1])
+            return res
         _check_status("align_events()", traj=self._traj_status, rectify=rect, filter=filt)
         if rect is not None:
             out["rectify_status"] = rect.cpu().numpy()
