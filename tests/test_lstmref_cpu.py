@@ -1,0 +1,305 @@
+"""CPU tests of tests/lstmref.py, the float64 restatement that tests/test_frontend_recurrent_gpu.py holds the front end's
+recurrent kernels to: it agrees with torch's own modules in float64 and with the oracle's forwards in float32, its shape
+arithmetic is the product's, and the cases of the GPU test can tell the true statement from plausible wrong ones by more
+than 100 bounds -- so a kernel that passes the GPU test has none of those defects."""
+import contextlib
+import copy
+
+import pytest
+import torch
+import torch.nn as nn
+
+import georef
+import lstmref as lr
+
+ALL_MS_CASES = sorted(set(lr.MS_MFMA_CASES + lr.MS_VALU_CASES))
+SMALL_MS_CASES = [c for c in ALL_MS_CASES if c[1] * c[2] < 10000]
+BITE = 100.0                 # a defect must move the result by more than this many bounds
+
+
+@pytest.fixture(scope="module")
+def nets():
+    ss, ms = lr.make_encoders()
+    return dict(ss=ss, ms=ms, wss=lr.singlescale_weights(ss), wms=lr.multiscale_weights(ms))
+
+
+@pytest.fixture(scope="module")
+def ms_refs(nets):
+    """per MultiScale case: (steps, [(float64 state, envelope)] per step)"""
+    out = {}
+    for S, H, W in ALL_MS_CASES:
+        steps = lr.ms_inputs(S, H, W)
+        out[(S, H, W)] = (steps, lr.ms_reference(nets["wms"], nets["ms"].scales.index(S), steps))
+    return out
+
+
+def _bound(ref, env):
+    return georef.bound(lr.floor_of(ref), env)
+
+
+# ------------------------------------------------------------------------------------------- against torch's own modules
+@torch.no_grad()
+def test_singlescale_step_is_the_modules_in_float64(nets):
+    enc = copy.deepcopy(nets["ss"]).double()
+    H, W = 5, 9
+    g = torch.Generator().manual_seed(3)
+    pres = [(1, 1), (0, 1), (1, 0)]
+    he = hi = None
+    s = torch.zeros(1, 15, H, W, dtype=torch.float64)
+    state = None
+    for pe, pi in pres:
+        ev = torch.randn(5, H, W, generator=g) * pe
+        im = torch.randn(3, H, W, generator=g) * pi
+        xe = ev.double().permute(1, 2, 0).reshape(-1, 1, 5)
+        xi = im.double().permute(1, 2, 0).reshape(-1, 1, 3)
+        oe, he = enc.events_convlstm(xe, he)
+        oi, hi = enc.image_convlstm(xi, hi)
+        for emb, present in ((oe, bool(torch.any(ev != 0))), (oi, bool(torch.any(im != 0)))):
+            if present:
+                s = enc.superstate_encoder(torch.cat((s, emb.reshape(1, H, W, 15).permute(0, 3, 1, 2)), 1))
+        state = lr.singlescale_step(nets["wss"], ev, im, state)
+        assert float((state["ss"] - s[0].permute(1, 2, 0).reshape(-1, 15)).abs().max()) <= 1e-12
+        for name, t in (("h_ev", he[0]), ("c_ev", he[1]), ("h_im", hi[0]), ("c_im", hi[1])):
+            assert float((state[name] - t[0]).abs().max()) <= 1e-12, name
+
+
+@torch.no_grad()
+@pytest.mark.parametrize("S,H,W", [(1, 3, 7), (2, 7, 63), (2, 9, 50), (4, 7, 63), (4, 11, 127), (4, 9, 50)])
+def test_multiscale_step_is_the_modules_in_float64(nets, S, H, W):
+    enc = copy.deepcopy(nets["ms"]).double()
+    k = enc.scales.index(S)
+    s, mine = None, None
+    for (ev, im), (has, use) in zip(lr.ms_inputs(S, H, W), lr.MS_STEPS):
+        hs = []
+        for x, e in ((ev, enc.ev_encoders[k]), (im, enc.im_encoders[k])):
+            y = e.conv_1(x.double()[None])
+            assert tuple(y.shape[-2:]) == lr.scale_shape(H, W, S)
+            hs.append(e.convlstm(y[0].permute(1, 2, 0).reshape(-1, 1, y.shape[1]))[0][:, 0].t().reshape(1, -1, *y.shape[-2:]))
+        if not has:
+            s = torch.zeros_like(hs[0])
+        s = enc.super_state_ev_encoder[k].encoder(torch.cat((s, hs[0]), 1))
+        if use:
+            s = enc.super_state_im_encoders[k].encoder(torch.cat((s, hs[1]), 1))
+        mine = lr.multiscale_step(nets["wms"], k, ev, im, mine, has, use)
+        assert float((mine - s[0].permute(1, 2, 0).reshape(-1, s.shape[1])).abs().max()) <= 1e-12
+
+
+# ---------------------------------------------------------------------------------------------------- against the oracle
+@contextlib.contextmanager
+def _torch_towers():
+    from oracle import host_cpu
+    saved = [(c, a, c.__dict__.get(a)) for c, a, _ in host_cpu.module_patches()]
+    for c, a, f in host_cpu.module_patches():
+        setattr(c, a, f)
+    try:
+        yield
+    finally:
+        for c, a, f in saved:
+            setattr(c, a, f)
+
+
+@torch.no_grad()
+def test_f32_twin_matches_the_oracle_singlescale(nets):
+    from oracle import host_cpu
+    enc = copy.deepcopy(nets["ss"])
+    H, W = 16, 24
+    g = torch.Generator().manual_seed(4)
+    state = None
+    for t, (pe, pi) in enumerate([(1, 1), (0, 1), (1, 0)]):
+        ev, im = torch.randn(5, H, W, generator=g) * pe, torch.randn(3, H, W, generator=g) * pi
+        with _torch_towers():
+            host_cpu.merger_forward(enc, events=ev[None, None], images=im[None, None], reinit_hidden=(t == 0))
+        state = lr.singlescale_step_f32(nets["wss"], ev, im, state)
+        assert float((state["ss"] - enc.super_state).abs().max()) <= 2e-5
+        assert float((state["h_ev"] - enc.states_events[0]).abs().max()) <= 2e-5
+        assert float((state["c_im"] - enc.states_image[1]).abs().max()) <= 2e-5
+
+
+@torch.no_grad()
+def test_f32_twin_matches_the_oracle_multiscale(nets):
+    from oracle import host_cpu
+    enc = copy.deepcopy(nets["ms"])
+    H, W = 16, 24
+    g = torch.Generator().manual_seed(5)
+    mine = [None] * 3
+    for t, use in enumerate([True, False, True]):
+        ev, im = torch.randn(5, H, W, generator=g), torch.randn(3, H, W, generator=g)
+        with _torch_towers():
+            host_cpu.multiscale_forward(enc, events=ev[None, None], images=im[None, None], mask=torch.tensor([use]),
+                                        reinit_hidden=(t == 0))
+        for k in range(3):
+            mine[k] = lr.multiscale_step_f32(nets["wms"], k, ev, im, mine[k], t > 0, use)
+            ref = enc.super_states[k]
+            assert mine[k].shape == ref.shape
+            assert float((mine[k] - ref).abs().max()) <= 2e-5 * max(1.0, float(ref.abs().max()))
+
+
+# -------------------------------------------------------------------------------------------------------- shape arithmetic
+def test_msstate_shapes_are_the_references(ms_refs):
+    from rampvo_amd import conv_hip
+    for (S, H, W), (_, refs) in ms_refs.items():
+        st = conv_hip.MsState(H, W, S, "cpu")
+        assert (st.Hs, st.Ws) == lr.scale_shape(H, W, S) and st.D == 16 * S
+        assert tuple(refs[0][0].shape) == (st.Hs * st.Ws, st.D) == tuple(st.s.shape)
+    # the table of the issue, as written there
+    want = {(2, 7, 63): (4, 32), (2, 8, 64): (4, 32), (2, 7, 64): (4, 32), (2, 8, 63): (4, 32), (4, 7, 63): (2, 16),
+            (4, 8, 64): (2, 16), (4, 11, 127): (3, 32), (2, 9, 50): (5, 25), (4, 9, 50): (2, 12)}
+    for (S, H, W), hw in want.items():
+        assert lr.scale_shape(H, W, S) == hw
+    clip = {(2, 7, 63): (True, True), (2, 8, 64): (False, False), (2, 7, 64): (False, True), (2, 8, 63): (True, False),
+            (4, 7, 63): (True, True), (4, 8, 64): (False, False), (4, 11, 127): (True, True)}
+    for (S, H, W), rb in clip.items():
+        assert lr.clips(H, W, S) == rb
+
+
+# ------------------------------------------------------------------------------------------------------------- sensitivity
+def test_every_reference_output_is_well_away_from_zero(nets, ms_refs):
+    for case, (_, refs) in ms_refs.items():
+        for ref, _ in refs:
+            assert float(ref.abs().max()) >= 0.05, case
+    for HW in lr.SS_HW:
+        for ref, _ in lr.ss_reference(nets["wss"], lr.ss_inputs(HW)):
+            for name in lr.STATE_NAMES:
+                assert float(ref[name].abs().max()) >= 0.05, (HW, name)
+
+
+@pytest.mark.parametrize("S,H,W", [c for c in ALL_MS_CASES if any(lr.clips(c[1], c[2], c[0]))])
+def test_clipping_cases_detect_a_padding_defect(nets, ms_refs, S, H, W):
+    """taps at ix == W / iy == H taken from the nearest pixel instead of zero move the last column / row by > 100 bounds"""
+    k = nets["ms"].scales.index(S)
+    steps, refs = ms_refs[(S, H, W)]
+    Hs, Ws = lr.scale_shape(H, W, S)
+    right, bottom = lr.clips(H, W, S)
+    s = None
+    for (ev, im), (has, use), (ref, env) in zip(steps, lr.MS_STEPS, refs):
+        bad = lr.multiscale_step(nets["wms"], k, ev, im, s, has, use, edge="replicate")
+        s = ref                                       # (the true state goes on: every step's defect is its own)
+        d = (bad - ref).abs().max(dim=1).values.reshape(Hs, Ws)
+        b = _bound(ref, env)
+        if right:
+            assert float(d[:, Ws - 1].max()) > BITE * b, ("right", float(d[:, Ws - 1].max()), b)
+        if bottom:
+            assert float(d[Hs - 1, :].max()) > BITE * b, ("bottom", float(d[Hs - 1, :].max()), b)
+
+
+# -------------------------------------------------------------------------------------------------------- rejected mistakes
+def _swap_go(w):
+    w = dict(w)
+    for n in ("w_ih", "w_hh", "b_ih", "b_hh"):
+        i, f, g, o = w[n].chunk(4, dim=0)
+        w[n] = torch.cat((i, f, o, g), 0)
+    return w
+
+
+def _no_bhh(w):
+    return dict(w, b_hh=torch.zeros_like(w["b_hh"]))
+
+
+def _mix_hs(w):
+    d = w["w"].shape[0]
+    return dict(w, w=torch.cat((w["w"][:, d:], w["w"][:, :d]), 1))
+
+
+def _ms_with(wms, **edit):
+    return [{n: (edit[n.split("_")[0]](v) if n.split("_")[0] in edit else v) for n, v in w.items()} for w in wms]
+
+
+def _ms_rejected(nets, ms_refs, run):
+    """does ``run(k, steps, refs) -> [state per step]`` differ from the reference by > 100 bounds on some case and step"""
+    for (S, H, W) in SMALL_MS_CASES:
+        steps, refs = ms_refs[(S, H, W)]
+        for bad, (ref, env) in zip(run(nets["ms"].scales.index(S), steps, refs), refs):
+            if float((bad - ref).abs().max()) > BITE * _bound(ref, env):
+                return True
+    return False
+
+
+def _ms_run(wms, k, steps, **kw):
+    out, s = [], None
+    for (ev, im), (has, use) in zip(steps, lr.MS_STEPS):
+        s = lr.multiscale_step(wms, k, ev, im, s, has, use, **kw)
+        out.append(s)
+    return out
+
+
+def test_the_unedited_reference_is_not_rejected(nets, ms_refs):
+    assert not _ms_rejected(nets, ms_refs, lambda k, steps, refs: _ms_run(nets["wms"], k, steps))
+
+
+@pytest.mark.parametrize("mistake", ["g and o rows swapped", "b_hh dropped", "mix input [h ; s]"])
+def test_multiscale_weight_mistakes_are_rejected(nets, ms_refs, mistake):
+    edit = {"g and o rows swapped": dict(lstm=_swap_go), "b_hh dropped": dict(lstm=_no_bhh), "mix input [h ; s]": dict(mix=_mix_hs)}[mistake]
+    wbad = _ms_with(nets["wms"], **edit)
+    assert _ms_rejected(nets, ms_refs, lambda k, steps, refs: _ms_run(wbad, k, steps))
+
+
+def test_pad_0_is_rejected(nets, ms_refs):
+    assert _ms_rejected(nets, ms_refs, lambda k, steps, refs: _ms_run(nets["wms"], k, steps, pad=0))
+
+
+def test_mix_im_on_an_events_only_step_is_rejected(nets, ms_refs):
+    def run(k, steps, refs):
+        (ev, im), (has, _) = steps[2], lr.MS_STEPS[2]
+        return [refs[0][0], refs[1][0], lr.multiscale_step(nets["wms"], k, ev, im, refs[1][0], has, 1)]
+    assert lr.MS_STEPS[2] == (1, 0)
+    assert _ms_rejected(nets, ms_refs, run)
+
+
+def test_the_old_state_on_a_first_step_is_rejected(nets, ms_refs):
+    def run(k, steps, refs):
+        ev, im = steps[0]
+        dirty = torch.full_like(refs[0][0], 1e30)
+        return [lr.multiscale_step(nets["wms"], k, ev, im, dirty, 1, 1)]
+    assert lr.MS_STEPS[0] == (0, 1)
+    assert _ms_rejected(nets, ms_refs, run)
+
+
+def _ss_rejected(nets, run, names=lr.STATE_NAMES):
+    for HW in lr.SS_HW[:5]:
+        steps = lr.ss_inputs(HW)
+        refs = lr.ss_reference(nets["wss"], steps)
+        for bad, (ref, env) in zip(run(steps, refs), refs):
+            for n in names:
+                if float((bad[n] - ref[n]).abs().max()) > BITE * georef.bound(lr.floor_of(ref[n]), env[n]):
+                    return True
+    return False
+
+
+def _ss_run(wss, steps, present=None, freeze_absent=False):
+    out, s = [], None
+    for ev, im in steps:
+        new = lr.singlescale_step(wss, ev, im, s, present=present)
+        if freeze_absent and s is not None:
+            pe, pi = lr.any_nonzero(ev, im)
+            if not pe:
+                new["h_ev"], new["c_ev"] = s["h_ev"], s["c_ev"]
+            if not pi:
+                new["h_im"], new["c_im"] = s["h_im"], s["c_im"]
+        s = new
+        out.append(s)
+    return out
+
+
+def test_singlescale_mistakes_are_rejected(nets):
+    wss = nets["wss"]
+    assert not _ss_rejected(nets, lambda steps, refs: _ss_run(wss, steps))
+    # the embedding of an absent modality mixed in anyway: the super-state gives it away
+    assert _ss_rejected(nets, lambda steps, refs: _ss_run(wss, steps, present=(True, True)), names=("ss",))
+    # the cell of an absent modality not advanced: its state, and the next super-state it enters, give it away
+    assert _ss_rejected(nets, lambda steps, refs: _ss_run(wss, steps, freeze_absent=True), names=("h_ev", "c_ev", "h_im", "c_im"))
+    assert _ss_rejected(nets, lambda steps, refs: _ss_run(wss, steps, freeze_absent=True), names=("ss",))
+    for edit in (_swap_go, _no_bhh):
+        wbad = dict(wss, ev=edit(wss["ev"]), im=edit(wss["im"]))
+        assert _ss_rejected(nets, lambda steps, refs: _ss_run(wbad, steps))
+    assert _ss_rejected(nets, lambda steps, refs: _ss_run(dict(wss, ss=_mix_hs(wss["ss"])), steps), names=("ss",))
+
+
+# ------------------------------------------------------------------------------------------------------------ presence test
+def test_any_nonzero_has_torch_any_semantics():
+    z = torch.zeros(7)
+    nz, nan, one = torch.full((7,), -0.0), z.clone(), z.clone()
+    nan[6], one[6] = float("nan"), 1e-45                       # (a subnormal is nonzero)
+    for a in (z, nz, nan, one):
+        for b in (z, nz, nan, one):
+            assert lr.any_nonzero(a, b) == (bool(torch.any(a != 0)), bool(torch.any(b != 0)))
+    assert lr.any_nonzero(z, nz) == (False, False) and lr.any_nonzero(nan, one) == (True, True)
