@@ -56,18 +56,6 @@ struct ConArgs {
   const int32_t *done;                   // optional: a device word; not zero: every launch of the evaluation returns at once
 };
 
-static __device__ __forceinline__ double con_wave_sum(double v) {
-#pragma unroll
-  for (int off = RAMP_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-static __device__ __forceinline__ long long con_wave_sum(long long v) {
-#pragma unroll
-  for (int off = RAMP_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // GRAD = false: the splat.  GRAD = true: the gradient's gather.  LDS_TIMES, VEC: as warp_event_kernel.
 template <bool GRAD, bool LDS_TIMES, bool VEC>
 __global__ void __launch_bounds__(INTERP_THREADS) contrast_event_kernel(const ConArgs a) {
@@ -216,26 +204,21 @@ __global__ void __launch_bounds__(INTERP_THREADS) contrast_event_kernel(const Co
         }
       }
       if (!GRAD) {
-        // the trip count and `have` aside, every lane of the wave is here: one ballot per counter, summed per wave
-        n_below += __popcll(__ballot(below));
-        n_above += __popcll(__ballot(above));
-        n_bad += __popcll(__ballot(bad));
-        n_z += __popcll(__ballot(zrej));
-        n_out += __popcll(__ballot(outside));
-        n_in += __popcll(__ballot(inside));
+        // the trip count and `have` aside, every lane of the wave is here
+        n_below += ramp_wave_count(below);
+        n_above += ramp_wave_count(above);
+        n_bad += ramp_wave_count(bad);
+        n_z += ramp_wave_count(zrej);
+        n_out += ramp_wave_count(outside);
+        n_in += ramp_wave_count(inside);
       }
     }
   }
   if (!GRAD) {
-    sum_signed = con_wave_sum(sum_signed);
-    sum_count = con_wave_sum(sum_count);
-    if ((tid & (RAMP_WAVE - 1)) == 0) {                // one integer atomic per wave and counter that is not zero
-      if (n_below) atomicAdd(&a.ctr[1], n_below);
-      if (n_above) atomicAdd(&a.ctr[2], n_above);
-      if (n_bad) atomicAdd(&a.ctr[3], n_bad);
-      if (n_z) atomicAdd(&a.ctr[4], n_z);
-      if (n_out) atomicAdd(&a.ctr[5], n_out);
-      if (n_in) atomicAdd(&a.ctr[6], n_in);
+    sum_signed = ramp_wave_sum(sum_signed);
+    sum_count = ramp_wave_sum(sum_count);
+    ramp_wave_flush(a.ctr + 1, tid, n_below, n_above, n_bad, n_z, n_out, n_in);
+    if ((tid & (RAMP_WAVE - 1)) == 0) {
       warp_u64 *S1 = reinterpret_cast<warp_u64 *>(a.ctr + CON_S1_WORD);
       if (sum_signed) atomicAdd(&S1[0], (warp_u64)sum_signed);
       if (sum_count) atomicAdd(&S1[1], (warp_u64)sum_count);
@@ -245,7 +228,7 @@ __global__ void __launch_bounds__(INTERP_THREADS) contrast_event_kernel(const Co
     __syncthreads();
 #pragma unroll
     for (int c = 0; c < 7; c++) {
-      const double v = con_wave_sum(g[c]);
+      const double v = ramp_wave_sum(g[c]);
       if ((tid & (RAMP_WAVE - 1)) == 0) s_red[(tid / RAMP_WAVE) * CON_ROW_WORDS + c] = v;
     }
     __syncthreads();
@@ -280,8 +263,8 @@ __global__ void __launch_bounds__(256)
     s2 += v * v;
     c2 += (v - mu) * (v - mu);
   }
-  s2 = con_wave_sum(s2);
-  c2 = con_wave_sum(c2);
+  s2 = ramp_wave_sum(s2);
+  c2 = ramp_wave_sum(c2);
   if ((tid & (RAMP_WAVE - 1)) == 0) { s_red[2 * (tid / RAMP_WAVE)] = s2; s_red[2 * (tid / RAMP_WAVE) + 1] = c2; }
   __syncthreads();
   if (tid < 2) {

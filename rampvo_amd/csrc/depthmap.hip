@@ -116,16 +116,10 @@ __global__ void __launch_bounds__(DM_THREADS) dm_project_kernel(const DmProject 
       o[0] = rec.x; o[1] = rec.y; o[2] = rec.z; o[3] = rec.w;
     }
   }
-  // every lane of the wave is here: one ballot per counter, one integer atomic per wave and counter that is not zero
-  const int n_live = __popcll(__ballot(live)), n_depth = __popcll(__ballot(r_depth)), n_z = __popcll(__ballot(r_z));
-  const int n_reach = __popcll(__ballot(r_reach)), n_in = __popcll(__ballot(r_in));
-  if ((tid & (RAMP_WAVE - 1)) == 0) {
-    if (n_live) atomicAdd(&a.status[1], n_live);
-    if (n_depth) atomicAdd(&a.status[2], n_depth);
-    if (n_z) atomicAdd(&a.status[3], n_z);
-    if (n_reach) atomicAdd(&a.status[4], n_reach);
-    if (n_in) atomicAdd(&a.status[5], n_in);
-  }
+  // every lane of the wave is here: one ballot per counter
+  const int n_live = ramp_wave_count(live), n_depth = ramp_wave_count(r_depth), n_z = ramp_wave_count(r_z);
+  const int n_reach = ramp_wave_count(r_reach), n_in = ramp_wave_count(r_in);
+  ramp_wave_flush(a.status + 1, tid, n_live, n_depth, n_z, n_reach, n_in);
 }
 
 __global__ void __launch_bounds__(DM_THREADS)
@@ -205,8 +199,7 @@ __global__ void __launch_bounds__(DM_THREADS)
       empty += S0[p] == 0.0f ? 1 : 0;
     }
   }
-#pragma unroll
-  for (int o = RAMP_WAVE / 2; o > 0; o >>= 1) empty += __shfl_xor(empty, o);
+  empty = ramp_wave_sum(empty);
   if (lane == 0 && empty) atomicAdd(&status[6], empty);
 }
 

@@ -63,15 +63,11 @@ __global__ void __launch_bounds__(INTERP_THREADS)
       key[i] = k;
       iota[i] = (int32_t)i;
     }
-    n_seen += __popcll(__ballot(have));
-    n_bad += __popcll(__ballot(bad));
-    n_out += __popcll(__ballot(outside));
+    n_seen += ramp_wave_count(have);
+    n_bad += ramp_wave_count(bad);
+    n_out += ramp_wave_count(outside);
   }
-  if ((tid & (RAMP_WAVE - 1)) == 0) {                    // one integer atomic per wave and counter that is not zero
-    if (n_seen) atomicAdd(&ctr[1], n_seen);
-    if (n_bad) atomicAdd(&ctr[2], n_bad);
-    if (n_out) atomicAdd(&ctr[3], n_out);
-  }
+  ramp_wave_flush(ctr + 1, tid, n_seen, n_bad, n_out);
 }
 
 // start[q] = the number of sorted keys below q, for q in [0, H W + 1]: the segment of pixel q is [start[q], start[q + 1])
@@ -120,7 +116,7 @@ __global__ void __launch_bounds__(INTERP_THREADS)
     }
   }
 #pragma unroll
-  for (int off = RAMP_WAVE / 2; off > 0; off >>= 1) {
+  for (int off = RAMP_WAVE / 2; off > 0; off >>= 1) {    // (two sums in one butterfly: ramp_wave_sum, interleaved)
     n += __shfl_xor(n, off);
     s2 += __shfl_xor(s2, off);
   }
@@ -235,7 +231,7 @@ __global__ void __launch_bounds__(INTERP_THREADS) flt_filter_kernel(const FltArg
       }
     }
 #pragma unroll
-    for (int c = 0; c < 4; c++) n_cls[c] += __popcll(__ballot(cls == 4 + c));
+    for (int c = 0; c < 4; c++) n_cls[c] += ramp_wave_count(cls == 4 + c);
   }
   if ((tid & (RAMP_WAVE - 1)) == 0) {
 #pragma unroll

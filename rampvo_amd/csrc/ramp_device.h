@@ -26,6 +26,27 @@ __device__ __forceinline__ int ramp_f2i(float f) {
   return (int)f;
 }
 
+// the sum of v over the wave, in every lane: a fixed xor butterfly, so a floating-point sum repeats its bits
+template <typename V>
+static __device__ __forceinline__ V ramp_wave_sum(V v) {
+#pragma unroll
+  for (int off = RAMP_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// The event counters of a wave are named ints of the kernel, wave-uniform: `n += ramp_wave_count(pred)` where every lane of
+// the wave arrives (the trip count and `have` aside) is one ballot per counter and trip, summed per wave.
+static __device__ __forceinline__ int ramp_wave_count(int pred) { return __popcll(__ballot(pred)); }
+
+// words[k] += the k-th counter: one integer atomic per wave and counter that is not zero, in the order given
+template <typename... C>
+static __device__ __forceinline__ void ramp_wave_flush(int32_t *words, int tid, C... n) {
+  if ((tid & (RAMP_WAVE - 1)) == 0) {
+    int k = 0;
+    ((n ? (void)atomicAdd(&words[k++], n) : (void)k++), ...);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // fastba-flavoured SE3 helpers (quaternions taken as stored, no normalisation)
 // reference: ramp/fastba/ba_cuda.cu:36-174

@@ -205,21 +205,14 @@ __global__ void __launch_bounds__(INTERP_THREADS)
       for (int j = tid; j < live * 2; j += INTERP_THREADS) og[j] = s_rows[j];
     }
     __syncthreads();                                 // (the next tile overwrites the staging rows)
-    n_seen += __popcll(__ballot(have));
-    n_nan += __popcll(__ballot(not_finite));
-    n_inv += __popcll(__ballot(not_inv));
-    n_behind += __popcll(__ballot(behind));
-    n_out += __popcll(__ballot(outside));
-    n_in += __popcll(__ballot(inside));
+    n_seen += ramp_wave_count(have);
+    n_nan += ramp_wave_count(not_finite);
+    n_inv += ramp_wave_count(not_inv);
+    n_behind += ramp_wave_count(behind);
+    n_out += ramp_wave_count(outside);
+    n_in += ramp_wave_count(inside);
   }
-  if ((tid & (RAMP_WAVE - 1)) == 0) {                // one integer atomic per wave and counter that is not zero
-    if (n_seen) atomicAdd(&status[1], n_seen);
-    if (n_nan) atomicAdd(&status[2], n_nan);
-    if (n_inv) atomicAdd(&status[3], n_inv);
-    if (n_behind) atomicAdd(&status[4], n_behind);
-    if (n_out) atomicAdd(&status[5], n_out);
-    if (n_in) atomicAdd(&status[6], n_in);
-  }
+  ramp_wave_flush(status + 1, tid, n_seen, n_nan, n_inv, n_behind, n_out, n_in);
   if (c.bad && blockIdx.x == 0 && tid == 0) atomicOr(&status[0], RAMP_RECTIFY_BAD_CAMERA);
 }
 
@@ -234,7 +227,7 @@ __global__ void __launch_bounds__(INTERP_THREADS)
   const float qnan = __int_as_float(0x7fc00000);
   const long P = (long)H * W, Ps = (long)Hs * Ws;
   const long tiles = (P + INTERP_THREADS - 1) / INTERP_THREADS;
-  int n_seen = 0, n_fold = 0, n_out = 0, n_in = 0;
+  int n_seen = 0, n_fold = 0, n_out = 0, n_in = 0;   // wave-uniform: sums of ballots
   for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const long i = tile * INTERP_THREADS + tid;
     const bool have = i < P;
@@ -290,17 +283,12 @@ __global__ void __launch_bounds__(INTERP_THREADS)
         }
       }
     }
-    n_seen += __popcll(__ballot(have));
-    n_fold += __popcll(__ballot(fold));
-    n_out += __popcll(__ballot(outside));
-    n_in += __popcll(__ballot(sampled));
+    n_seen += ramp_wave_count(have);
+    n_fold += ramp_wave_count(fold);
+    n_out += ramp_wave_count(outside);
+    n_in += ramp_wave_count(sampled);
   }
-  if ((tid & (RAMP_WAVE - 1)) == 0) {
-    if (n_seen) atomicAdd(&status[1], n_seen);
-    if (n_fold) atomicAdd(&status[2], n_fold);
-    if (n_out) atomicAdd(&status[3], n_out);
-    if (n_in) atomicAdd(&status[4], n_in);
-  }
+  ramp_wave_flush(status + 1, tid, n_seen, n_fold, n_out, n_in);
   if (c.bad && blockIdx.x == 0 && tid == 0) atomicOr(&status[0], RAMP_RECTIFY_BAD_CAMERA);
 }
 

@@ -46,18 +46,6 @@ struct VoxArgs {
   int sc, bins, H, W;
 };
 
-static __device__ __forceinline__ long long vox_wave_sum(long long v) {
-#pragma unroll
-  for (int off = RAMP_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-static __device__ __forceinline__ double vox_wave_sum(double v) {
-#pragma unroll
-  for (int off = RAMP_WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
 // the number of offsets <= i among n
 template <typename P>
 static __device__ __forceinline__ int vox_upper_bound(P off, int n, long long i) {
@@ -215,21 +203,15 @@ __global__ void __launch_bounds__(INTERP_THREADS) vox_vote_kernel(const VoxArgs 
           }
         }
       }
-      // the trip count and `have` aside, every lane of the wave is here: one ballot per counter, summed per wave
-      n_seen += __popcll(__ballot(have));
-      n_bad += __popcll(__ballot(bad));
-      n_out += __popcll(__ballot(outside));
-      n_time += __popcll(__ballot(no_bin));
-      n_in += __popcll(__ballot(inside));
+      // the trip count and `have` aside, every lane of the wave is here
+      n_seen += ramp_wave_count(have);
+      n_bad += ramp_wave_count(bad);
+      n_out += ramp_wave_count(outside);
+      n_time += ramp_wave_count(no_bin);
+      n_in += ramp_wave_count(inside);
     }
   }
-  if ((tid & (RAMP_WAVE - 1)) == 0) {                  // one integer atomic per wave and counter that is not zero
-    if (n_seen) atomicAdd(&a.ctr[1], n_seen);
-    if (n_bad) atomicAdd(&a.ctr[2], n_bad);
-    if (n_out) atomicAdd(&a.ctr[3], n_out);
-    if (n_time) atomicAdd(&a.ctr[4], n_time);
-    if (n_in) atomicAdd(&a.ctr[5], n_in);
-  }
+  ramp_wave_flush(a.ctr + 1, tid, n_seen, n_bad, n_out, n_time, n_in);
 }
 
 // workgroup r of the P that share slice s: the number of non-zero cells and their sum, both integers
@@ -245,8 +227,8 @@ __global__ void __launch_bounds__(INTERP_THREADS)
     n += v != 0;
     sum += v;
   }
-  n = vox_wave_sum(n);
-  sum = vox_wave_sum(sum);
+  n = ramp_wave_sum(n);
+  sum = ramp_wave_sum(sum);
   if ((tid & (RAMP_WAVE - 1)) == 0) {
     if (n) atomicAdd(reinterpret_cast<warp_u64 *>(sums + 2 * (size_t)s), (warp_u64)n);
     if (sum) atomicAdd(reinterpret_cast<warp_u64 *>(sums + 2 * (size_t)s + 1), (warp_u64)sum);
@@ -281,7 +263,7 @@ __global__ void __launch_bounds__(INTERP_THREADS)
       c2 += d * d;
     }
   }
-  c2 = vox_wave_sum(c2);
+  c2 = ramp_wave_sum(c2);
   if ((tid & (RAMP_WAVE - 1)) == 0) s_red[tid / RAMP_WAVE] = c2;
   __syncthreads();
   if (tid == 0) {
@@ -311,7 +293,7 @@ __global__ void __launch_bounds__(INTERP_THREADS)
     double v = 0.0;
     if (!failed)
       for (int q = tid; q < P; q += RAMP_WAVE) v += part[(size_t)s * P + q];
-    v = vox_wave_sum(v);
+    v = ramp_wave_sum(v);
     if (tid == 0) s_var = v;
   }
   __syncthreads();

@@ -167,23 +167,16 @@ __global__ void __launch_bounds__(INTERP_THREADS) warp_event_kernel(const WarpAr
           }
         }
       }
-      // the trip count and `have` aside, every lane of the wave is here: one ballot per counter, summed per wave
-      n_below += __popcll(__ballot(below));
-      n_above += __popcll(__ballot(above));
-      n_bad += __popcll(__ballot(bad));
-      n_z += __popcll(__ballot(zrej));
-      n_out += __popcll(__ballot(outside));
-      n_in += __popcll(__ballot(inside));
+      // the trip count and `have` aside, every lane of the wave is here
+      n_below += ramp_wave_count(below);
+      n_above += ramp_wave_count(above);
+      n_bad += ramp_wave_count(bad);
+      n_z += ramp_wave_count(zrej);
+      n_out += ramp_wave_count(outside);
+      n_in += ramp_wave_count(inside);
     }
   }
-  if ((tid & (RAMP_WAVE - 1)) == 0) {                  // one integer atomic per wave and counter that is not zero
-    if (n_below) atomicAdd(&a.ctr[1], n_below);
-    if (n_above) atomicAdd(&a.ctr[2], n_above);
-    if (n_bad) atomicAdd(&a.ctr[3], n_bad);
-    if (n_z) atomicAdd(&a.ctr[4], n_z);
-    if (n_out) atomicAdd(&a.ctr[5], n_out);
-    if (n_in) atomicAdd(&a.ctr[6], n_in);
-  }
+  ramp_wave_flush(a.ctr + 1, tid, n_below, n_above, n_bad, n_z, n_out, n_in);
 }
 
 __global__ void __launch_bounds__(256)

@@ -14,6 +14,32 @@ from ._lib import workspace as _lib_workspace
 from ._lib import KPLANE, RAMP_NHWC32, RAMP_NCHW, RAMP_NHWC, CorrLevel, check, dtype_code, kplane, lib, ptr, require_cuda, stream
 
 
+# ------------------------------------------------------------------- status words
+# per entry point ramp_<key>: the bits of status word 0 with their masks, and the names of words 1 and up
+_STATUS = {
+    "event_warp": ({"bad_times": _lib.RAMP_INTERP_BAD_TIMES},
+                   ("n_below", "n_above", "n_not_finite", "n_rejected", "n_outside", "n_contributed")),
+    "event_voxel": ({"bad_offsets": _lib.RAMP_VOXEL_BAD_OFFSETS, "bad_times": _lib.RAMP_VOXEL_BAD_TIMES},
+                    ("n_events", "n_not_finite", "n_outside", "n_no_bin", "n_contributed")),
+    "event_rectify": ({"bad_camera": _lib.RAMP_RECTIFY_BAD_CAMERA},
+                      ("n_events", "n_not_finite", "n_not_invertible", "n_behind", "n_outside", "n_inside")),
+    "image_rectify": ({"bad_camera": _lib.RAMP_RECTIFY_BAD_CAMERA}, ("n_pixels", "n_invalid", "n_outside", "n_sampled")),
+    "event_filter": ({"bad_order": _lib.RAMP_FILTER_BAD_ORDER},
+                     ("n_events", "n_not_finite", "n_outside", "n_hot", "n_refractory", "n_no_support", "n_kept")),
+    "invdepth_map": ({"bad_cam": _lib.RAMP_DEPTHMAP_BAD_CAM},
+                     ("n_considered", "n_bad_depth", "n_rejected", "n_out_of_reach", "n_contributing", "n_empty_pixels")),
+    "se3_interp": ({"bad_times": _lib.RAMP_INTERP_BAD_TIMES}, ("n_below", "n_above", "n_nan")),
+}
+
+
+def _status(entry, status):
+    """the status words of ramp_<entry> as a dict (synchronises: one copy of the words); ``<entry>_status`` binds it below,
+    beside each wrapper"""
+    bits, names = _STATUS[entry]
+    w = status.detach().cpu().tolist()
+    return {**{k: bool(int(w[0]) & m) for k, m in bits.items()}, **{k: int(w[1 + i]) for i, k in enumerate(names)}}
+
+
 # ------------------------------------------------------------------- altcorr
 def patchify(net, coords, radius, bilinear=True, layout=RAMP_NCHW, out_layout=RAMP_NCHW):
     """net [n,C,H,W] (NCHW) or [n,H,W,C] (NHWC); coords [n,M,2] -> [n,M,C,d,d] (or [n,M,d,d,C])"""
@@ -230,10 +256,8 @@ def event_warp(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, wi
 
 
 def event_warp_status(status):
-    """the status words of ramp_event_warp as a dict (synchronises: one 32-byte copy)"""
-    w = status.detach().cpu()
-    return dict(bad_times=bool(int(w[0]) & _lib.RAMP_INTERP_BAD_TIMES), n_below=int(w[1]), n_above=int(w[2]),
-                n_not_finite=int(w[3]), n_rejected=int(w[4]), n_outside=int(w[5]), n_contributed=int(w[6]))
+    """The status words of ``event_warp`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("event_warp", status)
 
 
 def event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=None, signed=True,
@@ -344,10 +368,8 @@ def event_voxel_grid(x, y, t, p, height, width, num_bins=5, offsets=None, normal
 
 
 def event_voxel_status(status):
-    """the status words of ramp_event_voxel as a dict (synchronises: one 32-byte copy)"""
-    w = status.detach().cpu()
-    return dict(bad_offsets=bool(int(w[0]) & _lib.RAMP_VOXEL_BAD_OFFSETS), bad_times=bool(int(w[0]) & _lib.RAMP_VOXEL_BAD_TIMES),
-                n_events=int(w[1]), n_not_finite=int(w[2]), n_outside=int(w[3]), n_no_bin=int(w[4]), n_contributed=int(w[5]))
+    """The status words of ``event_voxel_grid`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("event_voxel", status)
 
 
 CAMERA_MODELS = {"pinhole": _lib.RAMP_CAM_PINHOLE, "radtan": _lib.RAMP_CAM_RADTAN, "equidistant": _lib.RAMP_CAM_EQUIDISTANT}
@@ -433,10 +455,8 @@ def event_rectify(x, y, camera, height, width, want_valid=False):
 
 
 def event_rectify_status(status):
-    """the status words of ramp_event_rectify as a dict (synchronises: one 32-byte copy)"""
-    w = status.detach().cpu()
-    return dict(bad_camera=bool(int(w[0]) & _lib.RAMP_RECTIFY_BAD_CAMERA), n_events=int(w[1]), n_not_finite=int(w[2]),
-                n_not_invertible=int(w[3]), n_behind=int(w[4]), n_outside=int(w[5]), n_inside=int(w[6]))
+    """The status words of ``event_rectify`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("event_rectify", status)
 
 
 _RECTIFY_NORM = {None: _lib.RAMP_RECTIFY_NORM_NONE, "half": _lib.RAMP_RECTIFY_NORM_HALF, "unit": _lib.RAMP_RECTIFY_NORM_UNIT}
@@ -474,10 +494,8 @@ def image_rectify(image, camera, height, width, normalize=None, fill=0.0, want_m
 
 
 def image_rectify_status(status):
-    """the status words of ramp_image_rectify as a dict (synchronises: one 32-byte copy)"""
-    w = status.detach().cpu()
-    return dict(bad_camera=bool(int(w[0]) & _lib.RAMP_RECTIFY_BAD_CAMERA), n_pixels=int(w[1]), n_invalid=int(w[2]),
-                n_outside=int(w[3]), n_sampled=int(w[4]))
+    """The status words of ``image_rectify`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("image_rectify", status)
 
 
 def event_filter_state(height, width, device="cuda"):
@@ -553,10 +571,8 @@ def event_filter(x, y, t, height, width, support_dt=None, refractory=0.0, hot_co
 
 
 def event_filter_status(status):
-    """the status words of ramp_event_filter as a dict (synchronises: one 32-byte copy)"""
-    w = status.detach().cpu()
-    return dict(bad_order=bool(int(w[0]) & _lib.RAMP_FILTER_BAD_ORDER), n_events=int(w[1]), n_not_finite=int(w[2]),
-                n_outside=int(w[3]), n_hot=int(w[4]), n_refractory=int(w[5]), n_no_support=int(w[6]), n_kept=int(w[7]))
+    """The status words of ``event_filter`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("event_filter", status)
 
 
 def align_loop(evaluate, correction, free, step, iters):
@@ -738,10 +754,8 @@ def invdepth_map(poses, patches, intrinsics, cam, height, width, radius, scale=1
 
 
 def invdepth_map_status(status):
-    """the status words of ramp_invdepth_map as a dict (synchronises: one 32-byte copy)"""
-    w = status.detach().cpu()
-    return dict(bad_cam=bool(int(w[0]) & _lib.RAMP_DEPTHMAP_BAD_CAM), n_considered=int(w[1]), n_bad_depth=int(w[2]),
-                n_rejected=int(w[3]), n_out_of_reach=int(w[4]), n_contributing=int(w[5]), n_empty_pixels=int(w[6]))
+    """The status words of ``invdepth_map`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("invdepth_map", status)
 
 
 def depth_median_fill(patches_state, n, F, patches_new):
@@ -885,9 +899,8 @@ def se3_interp(knots, times, query, extrapolate=False, twist=False, row_stores=F
 
 
 def se3_interp_status(status):
-    """the status words of ramp_se3_interp as a dict (synchronises: one 16-byte copy)"""
-    w = status.detach().cpu()
-    return dict(bad_times=bool(int(w[0]) & _lib.RAMP_INTERP_BAD_TIMES), n_below=int(w[1]), n_above=int(w[2]), n_nan=int(w[3]))
+    """The status words of ``se3_interp`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("se3_interp", status)
 
 
 # ----------------------------------------------------------- projective ops

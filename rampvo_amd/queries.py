@@ -349,6 +349,29 @@ class TrackerQueries:
         rect = self.rectify_events(x, y, as_tensor=True)
         return rect["xy"][:, 0], rect["xy"][:, 1], rect["status"]
 
+    def _event_inputs(self, name, x, y, t, p, denoise, distorted):
+        """The prologue of an event query -> (x, y, t, p, extra): the events as the kernels take them (fp32, fp32, float64, int8
+        on the device) and ``extra``, the ``rectify_status`` / ``filter_status`` the result gains.  ``denoise`` filters first, in
+        the coordinates given (integer raw pixels stay int32), then ``distorted`` rectifies."""
+        td, pd = self._as_device(t, torch.float64), self._as_device(p, torch.int8)
+        rect = filt = None
+        if denoise:
+            x, y, filt = self._denoised(name, x, y, td)
+        if distorted:
+            x, y, rect = self._undistorted(name, x, y)
+        extra = {k: s for k, s in (("rectify_status", rect), ("filter_status", filt)) if s is not None}
+        return self._as_device(x, torch.float32), self._as_device(y, torch.float32), td, pd, extra
+
+    @staticmethod
+    def _answer(name, out, extra, as_tensor, **roles):
+        """The epilogue of an event query: ``out`` gains ``extra``; ``as_tensor``: the device dict as it is, else the one
+        ``_check_status`` call (``roles``: its other arguments) and numpy arrays."""
+        out.update(extra)
+        if as_tensor:
+            return out
+        _check_status(name, rectify=extra.get("rectify_status"), filter=extra.get("filter_status"), **roles)
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
     def compensate_events(self, x, y, t, p, t_ref=None, invdepth=None, num_bins=0, extrapolate=False, want_xy=False,
                           want_iwe=True, stack=None, height=None, width=None, as_tensor=False, radius=None,
                           weights="variance", distorted=False, denoise=False):
@@ -375,26 +398,13 @@ class TrackerQueries:
         the dict of device tensors of ``ops.event_warp`` (``status``, ``xy``, ``iwe``, ``stack`` as requested), ordered on
         the current stream, nothing synchronised.  Otherwise numpy arrays, which waits for that result and raises when the
         frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
-        rect = filt = None
-        if denoise:
-            x, y, filt = self._denoised("compensate_events()", x, y, t)
-        if distorted:
-            x, y, rect = self._undistorted("compensate_events()", x, y)
-        knots, tdev, K, invdepth, t_ref, H, W = self._event_query("compensate_events()", t_ref, invdepth, radius, weights,
-                                                                  height, width)
+        name = "compensate_events()"
+        xd, yd, td, pd, extra = self._event_inputs(name, x, y, t, p, denoise, distorted)
+        knots, tdev, K, invdepth, t_ref, H, W = self._event_query(name, t_ref, invdepth, radius, weights, height, width)
         with torch.no_grad():
-            out = ops.event_warp(self._as_device(x, torch.float32), self._as_device(y, torch.float32),
-                                 self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
-                                 invdepth, H, W, num_bins=num_bins, extrapolate=extrapolate, want_xy=want_xy,
-                                 want_iwe=want_iwe, stack=stack)
-        if rect is not None:
-            out["rectify_status"] = rect
-        if filt is not None:
-            out["filter_status"] = filt
-        if as_tensor:
-            return out
-        _check_status("compensate_events()", traj=self._traj_status, interp=out["status"], rectify=rect, filter=filt)
-        return {k: v.cpu().numpy() for k, v in out.items()}
+            out = ops.event_warp(xd, yd, td, pd, knots, tdev, t_ref, K, invdepth, H, W, num_bins=num_bins,
+                                 extrapolate=extrapolate, want_xy=want_xy, want_iwe=want_iwe, stack=stack)
+        return self._answer(name, out, extra, as_tensor, traj=self._traj_status, interp=out["status"])
 
     def _event_query(self, name, t_ref, invdepth, radius, weights, height, width):
         """what the event queries share: the trajectory as it is now, the cached time stamps, the image intrinsics and the
@@ -433,27 +443,15 @@ class TrackerQueries:
         as requested), ordered on the current stream, nothing synchronised.  Otherwise numpy arrays (``variance`` a float),
         which waits for that result and raises when the frames' time stamps decrease or are not finite, or on trajectory()'s
         unresolved bit."""
-        rect = filt = None
-        if denoise:
-            x, y, filt = self._denoised("event_contrast()", x, y, t)
-        if distorted:
-            x, y, rect = self._undistorted("event_contrast()", x, y)
-        knots, tdev, K, invdepth, t_ref, H, W = self._event_query("event_contrast()", t_ref, invdepth, radius, weights,
-                                                                  height, width)
+        name = "event_contrast()"
+        xd, yd, td, pd, extra = self._event_inputs(name, x, y, t, p, denoise, distorted)
+        knots, tdev, K, invdepth, t_ref, H, W = self._event_query(name, t_ref, invdepth, radius, weights, height, width)
         with torch.no_grad():
-            out = ops.event_contrast(self._as_device(x, torch.float32), self._as_device(y, torch.float32),
-                                     self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
-                                     invdepth, H, W, correction=correction, signed=signed, extrapolate=extrapolate,
-                                     want_grad=want_grad, want_iwe=want_iwe)
-        if rect is not None:
-            out["rectify_status"] = rect
-        if filt is not None:
-            out["filter_status"] = filt
-        if as_tensor:
-            return out
-        _check_status("event_contrast()", traj=self._traj_status, interp=out["status"], rectify=rect, filter=filt)
-        res = {k: v.cpu().numpy() for k, v in out.items()}
-        res["variance"] = float(res["stats"][0])
+            out = ops.event_contrast(xd, yd, td, pd, knots, tdev, t_ref, K, invdepth, H, W, correction=correction,
+                                     signed=signed, extrapolate=extrapolate, want_grad=want_grad, want_iwe=want_iwe)
+        res = self._answer(name, out, extra, as_tensor, traj=self._traj_status, interp=out["status"])
+        if not as_tensor:
+            res["variance"] = float(res["stats"][0])
         return res
 
     def align_events(self, x, y, t, p, t_ref=None, invdepth=None, correction=None, free=(0, 0, 0, 1, 1, 1, 0), step=0.05,
@@ -477,33 +475,25 @@ class TrackerQueries:
         stream; nothing is synchronised and nothing raised, as ``event_contrast(as_tensor=True)``: ``correction_f32`` goes
         straight into ``event_contrast(correction=...)``."""
         resident = resident or as_tensor
-        rect = filt = None
-        if denoise:
-            x, y, filt = self._denoised("align_events()", x, y, t)
-        if distorted:
-            x, y, rect = self._undistorted("align_events()", x, y)
-        knots, tdev, K, invdepth, t_ref, H, W = self._event_query("align_events()", t_ref, invdepth, radius, weights,
-                                                                  height, width)
+        name = "align_events()"
+        xd, yd, td, pd, extra = self._event_inputs(name, x, y, t, p, denoise, distorted)
+        knots, tdev, K, invdepth, t_ref, H, W = self._event_query(name, t_ref, invdepth, radius, weights, height, width)
         with torch.no_grad():
-            out = ops.event_align(self._as_device(x, torch.float32), self._as_device(y, torch.float32),
-                                  self._as_device(t, torch.float64), self._as_device(p, torch.int8), knots, tdev, t_ref, K,
-                                  invdepth, H, W, correction=correction, free=free, step=step, iters=iters, signed=signed,
-                                  extrapolate=extrapolate, resident=resident, max_evals=max_evals)
+            out = ops.event_align(xd, yd, td, pd, knots, tdev, t_ref, K, invdepth, H, W, correction=correction, free=free,
+                                  step=step, iters=iters, signed=signed, extrapolate=extrapolate, resident=resident,
+                                  max_evals=max_evals)
         if as_tensor:
-            if rect is not None:
-                out["rectify_status"] = rect
-            if filt is not None:
-                out["filter_status"] = filt
-            return out
+            return self._answer(name, out, extra, True)
+        rect, filt = extra.get("rectify_status"), extra.get("filter_status")
         if resident:
             # the one read: every word is an int32 or a double, so one float64 row holds them all exactly
-            extra = [(k, s) for k, s in (("traj", self._traj_status), ("rectify", rect), ("filter", filt)) if s is not None]
+            words_of = [(k, s) for k, s in (("traj", self._traj_status), ("rectify", rect), ("filter", filt)) if s is not None]
             with torch.no_grad():
                 row = torch.cat([out["correction"], out["result"], out["info"].double(), out["history"]]
-                                + [s.reshape(-1).double() for _, s in extra]).cpu().tolist()
+                                + [s.reshape(-1).double() for _, s in words_of]).cpu().tolist()
             info, tail = [int(v) for v in row[11:19]], row[19 + int(iters):]
             word, res = {"interp": info[4]}, {}
-            for k, s in extra:
+            for k, s in words_of:
                 words, tail = [int(v) for v in tail[:s.numel()]], tail[s.numel():]
                 word[k] = words[0]
                 if k != "traj":
@@ -512,11 +502,8 @@ class TrackerQueries:
             res.update(correction=row[:7], variance=row[7], variance0=row[8], history=row[19:19 + info[1]],
                        reason=ops.ALIGN_REASONS.get(info[0], "unknown"), n_evals=info[2], n_accepted=info[1])
             return res
-        _check_status("align_events()", traj=self._traj_status, rectify=rect, filter=filt)
-        if rect is not None:
-            out["rectify_status"] = rect.cpu().numpy()
-        if filt is not None:
-            out["filter_status"] = filt.cpu().numpy()
+        _check_status(name, traj=self._traj_status, rectify=rect, filter=filt)
+        out.update({k: s.cpu().numpy() for k, s in extra.items()})
         if out["variance0"] != out["variance0"]:              # (NaN: the kernel's answer to bad time stamps)
             raise RuntimeError("align_events(): the frames' time stamps decrease or are not finite")
         return out
@@ -549,14 +536,8 @@ class TrackerQueries:
         numpy arrays, which waits for that result and raises on offsets that decrease or leave the event list, on a slice
         whose first or last time stamp is not finite and, with ``compensate``, on the conditions ``compensate_events`` raises
         on."""
-        td, pd = self._as_device(t, torch.float64), self._as_device(p, torch.int8)
-        warp = rect = filt = None
-        if denoise:
-            x, y, filt = self._denoised("event_voxel_grid()", x, y, td)
-        if not distorted:
-            xd, yd = self._as_device(x, torch.float32), self._as_device(y, torch.float32)
-        if distorted:
-            xd, yd, rect = self._undistorted("event_voxel_grid()", x, y)
+        name, warp = "event_voxel_grid()", {}
+        xd, yd, td, pd, extra = self._event_inputs(name, x, y, t, p, denoise, distorted)
         if compensate:
             warp = self.compensate_events(xd, yd, td, pd, t_ref=t_ref, invdepth=invdepth, extrapolate=extrapolate, want_xy=True,
                                           want_iwe=False, as_tensor=True, radius=radius, weights=weights)
@@ -566,16 +547,9 @@ class TrackerQueries:
                                        offsets=None if offsets is None else self._as_device(offsets, torch.int64),
                                        normalize=normalize, subpixel=compensate or distorted)
         if compensate:
-            out["warp_status"] = warp["status"]
-        if rect is not None:
-            out["rectify_status"] = rect
-        if filt is not None:
-            out["filter_status"] = filt
-        if as_tensor:
-            return out
-        _check_status("event_voxel_grid()", traj=self._traj_status if compensate else None, interp=out.get("warp_status"),
-                      voxel=out["status"], rectify=rect, filter=filt)
-        return {k: v.cpu().numpy() for k, v in out.items()}
+            extra = {"warp_status": warp["status"], **extra}
+        return self._answer(name, out, extra, as_tensor, traj=self._traj_status if compensate else None,
+                            interp=warp.get("status"), voxel=out["status"])
 
     def _depth_median_word(self, resident):
         """(on the stream the state lives on) the lower median inverse depth of the last three frames' patches as a device
