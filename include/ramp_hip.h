@@ -802,7 +802,11 @@ int ramp_x3_gru(const float *x32, const float *add0_t, const int32_t *add0_idx, 
 #define RAMP_TRACK_COMPACT_COORDS 32 /* (measurement) the same, and every patch with unit pixel spacing around its centre (a
                                      converged tracker's factors: one 10 x 10 union window per level)                  */
 
-typedef struct ramp_track_weights {      /* update operator, fp16 fused formats of ramp_upd_* */
+/* The weights of the update operator in the formats its fused chains read: fp16 features -- Linear weights as fp16 MFMA
+ * fragments (ramp_upd_gru), their biases fp32 [384] holding fp16-rounded values, heads_w [4][384] fp16; fp32 features -- "x3
+ * packs" (ramp_x3_*) with fp32 biases, heads_w [4][384] fp32.  corr_w1 is packed from the weight zero-padded to 896 columns;
+ * LayerNorm parameters are fp32 in both.  rampvo_amd/update_fused.py::FusedUpdate.record() fills it once per set of weights. */
+typedef struct ramp_track_weights {
   const void *corr_w1, *corr_w2, *corr_w3;
   const float *corr_b1, *corr_b2, *corr_b3, *corr_ln_w, *corr_ln_b, *norm_w, *norm_b;
   const void *c1_wa, *c1_wb, *c2_wa, *c2_wb;
@@ -816,6 +820,44 @@ typedef struct ramp_track_weights {      /* update operator, fp16 fused formats 
   const float *heads_b;
   float corr_ln_eps, norm_eps, ln1_eps, ln2_eps;
 } ramp_track_weights;
+
+/* One call of the whole update operator (ramp/net.py:69-90): the launch sequence the device-resident step makes, for a
+ * caller that knows its row count.  fp32 = 0: fp16 features, the ramp_upd_* chains -- corr_mlp, nbr (c1), nbr (c2), softagg +
+ * softagg_finish over the patch groups, the same over the pair groups with hkk[kk_gid] added on the way, gru;  fp32 = 1: the
+ * ramp_x3_* chains, each SoftAgg as fg + segment_softmax + linear.  T is half / float accordingly.
+ *   corr [E][896] T (882 + zero tail);  net_prev [*][384] fp32 or NULL (zeros), row net_map[e] of it per factor (-1: zero
+ *   row; NULL: row e);  inp [*][384] T, row inp_idx[e] % inp_mod (inp_idx NULL: row e);
+ *   state[2]: [E][384] fp32 scratch, distinct, state[0] != net_prev;  net_out [E][384] fp32 (may be state[1] or net_prev);
+ *   relu_out [E][384] T = relu(net_out), the input of the heads -- or, with coords [E][2][P][P] given, target / weight
+ *   [E][2] formed by the gru launch (image size wd x ht) and relu_out optional;
+ *   kk_* / ij_*: the factors grouped by patch / by pose pair (ramp_group_by: order [E], gid [E], seg [groups + 1], ngroups
+ *   [1] on the device, cap >= *ngroups);  ix / jx [E]: the temporal neighbours (-1: none);
+ *   hkk [kk_cap][384], hij [ij_cap][384] T: the SoftAgg tables;  sagg_frag (fp16 features):
+ *   [ramp_upd_softagg_frag_rows(E, max(kk_cap, ij_cap))][3][384];  fg [E][768], ykk [kk_cap][384], yij [ij_cap][384] (fp32
+ *   features; hkk / hij rows >= *ngroups are left alone there);
+ *   E_hint: ramp_track.E_hint's meaning (0: none).
+ * RAMP_EINVAL, before anything is launched, unless every pointer the precision needs is there; E = 0 launches nothing. */
+typedef struct ramp_update_args {
+  const ramp_track_weights *w;
+  const void *corr;
+  const float *net_prev;
+  const int64_t *net_map;
+  const void *inp;
+  const int64_t *inp_idx;
+  long inp_mod;
+  float *state[2];
+  float *net_out;
+  void *relu_out;
+  const float *coords;
+  float *target, *weight;
+  const int32_t *kk_order, *kk_gid, *kk_seg, *kk_ngroups, *ij_order, *ij_gid, *ij_seg, *ij_ngroups;
+  const int64_t *ix, *jx;
+  float *sagg_frag, *fg, *ykk, *yij;
+  void *hkk, *hij;
+  int kk_cap, ij_cap, E, E_hint, P, fp32;
+  float wd, ht;
+} ramp_update_args;
+int ramp_update_forward(const ramp_update_args *args, void *stream);
 
 typedef struct ramp_track {
   /* configuration (cfg: PATCHES_PER_FRAME, PATCH_LIFETIME, REMOVAL_WINDOW, OPTIMIZATION_WINDOW, KEYFRAME_INDEX,
@@ -848,8 +890,8 @@ typedef struct ramp_track {
   float *coords;                      /* [E_cap][2][P][P] */
   void *corr;                         /* [E_cap][896] fp16 */
   float *net[3];                      /* [E_cap][384] fp32: [0] the hidden state (in: previous, out: new), [1], [2] scratch */
-  void *fg, *ykk, *hkk, *yij, *hij, *relu_t;      /* (relu_t: unused since the heads moved into the gru launch; fg / ykk /
-                                                   * yij: fp32 features only, fp16 steps leave them alone)              */
+  void *fg, *ykk, *hkk, *yij, *hij;   /* the SoftAgg tables of ramp_update_args; fg / ykk / yij are read and written by
+                                       * fp32-feature steps only (fp16 steps need hkk / hij and sagg_frag)             */
   float *sagg_frag;                   /* fp16 features: [ramp_upd_softagg_frag_rows(E_cap, max(kk_cap, ij_cap))][3][384], the
                                        * two SoftAggs run as ramp_upd_softagg + _finish                                   */
   float *target, *weight;             /* [E_cap][2] */

@@ -682,7 +682,7 @@ class Ramp_vo(TrackerQueries):
 
     # ------------------------------------------------------------------- update
     def update(self):
-        """reference :276-310 (host-driven form; the device-resident step makes the same launches from C)"""
+        """reference :276-310 (host-driven form; the device-resident step runs the same operator sequence)"""
         if self._cur_stream is None:                 # (a public call, not the tracked frame's own update)
             self._join_main()
         with Timer("other", enabled=self.enable_timing):
@@ -690,8 +690,8 @@ class Ramp_vo(TrackerQueries):
             coords = self.reproject()
             order = plan.g_ij.order
             corr = self.corr(coords, order=order).to(self.dtype)
-            # GEMMs + row-fused glue (csrc/update.hip) / the fused fp16 chains (csrc/update_mlp.hip); the context
-            # gather, the heads' activations, `target = centre + delta` and filter_features are folded in
+            # one C call on the fused chains (csrc/update_op.hip) -- the context gather, the heads, `target = centre + delta`
+            # and filter_features are folded in -- or library GEMMs + row-fused glue (csrc/update.hip) and the heads behind
             fu = self.network.update.fused(self.dtype)
             net_map = None
             if self._net_map is not None:
@@ -700,9 +700,8 @@ class Ramp_vo(TrackerQueries):
                                       corr[0], plan, net_map=net_map,
                                       heads_at=(coords[0].contiguous(), self.wd // 4, self.ht // 4))
             self.net = out32[None]
-            tw = fu.last_tw if relu_t is None else fu.heads_target_weight(relu_t, coords[0], self.wd // 4, self.ht // 4)
-            if tw is not None:
-                target, weight = tw
+            if relu_t is None:
+                target, weight = fu.last_tw
             else:
                 target, weight, _ = fu.target_weight(fu.heads(relu_t), coords[0], self.wd // 4, self.ht // 4)
             self.last_weight = weight

@@ -63,6 +63,30 @@ class CorrLevel(ctypes.Structure):
     _fields_ = [("fmap", c_p), ("H2", c_i), ("W2", c_i), ("coord_div", c_f)]
 
 
+def _ptr_fields(names):
+    return [(n, c_p) for n in names]
+
+
+class TrackWeights(ctypes.Structure):
+    """ramp_track_weights"""
+    _fields_ = (_ptr_fields(["corr_w1", "corr_w2", "corr_w3", "corr_b1", "corr_b2", "corr_b3", "corr_ln_w", "corr_ln_b",
+                             "norm_w", "norm_b", "c1_wa", "c1_wb", "c2_wa", "c2_wb", "c1_ba", "c1_bb", "c2_ba", "c2_bb",
+                             "kk_wf", "kk_wg", "kk_wh", "ij_wf", "ij_wg", "ij_wh", "kk_bf", "kk_bg", "kk_bh", "ij_bf",
+                             "ij_bg", "ij_bh", "ln1_w", "ln1_b", "ln2_w", "ln2_b"])
+                + [("gru_w", c_p * 6), ("gru_b", c_p * 6), ("heads_w", c_p), ("heads_b", c_p)]
+                + [(n, c_f) for n in ("corr_ln_eps", "norm_eps", "ln1_eps", "ln2_eps")])
+
+
+class UpdateArgs(ctypes.Structure):
+    """ramp_update_args"""
+    _fields_ = ([("w", ctypes.POINTER(TrackWeights))]
+                + _ptr_fields(["corr", "net_prev", "net_map", "inp", "inp_idx"]) + [("inp_mod", ctypes.c_long), ("state", c_p * 2)]
+                + _ptr_fields(["net_out", "relu_out", "coords", "target", "weight", "kk_order", "kk_gid", "kk_seg",
+                               "kk_ngroups", "ij_order", "ij_gid", "ij_seg", "ij_ngroups", "ix", "jx", "sagg_frag", "fg",
+                               "ykk", "yij", "hkk", "hij"])
+                + [(n, c_i) for n in ("kk_cap", "ij_cap", "E", "E_hint", "P", "fp32")] + [("wd", c_f), ("ht", c_f)])
+
+
 # name -> (restype, argtypes); also the list the CPU test checks for export
 SIGNATURES = {
     "ramp_version": (ctypes.c_char_p, []),
@@ -167,6 +191,8 @@ SIGNATURES = {
     "ramp_x3_linear": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     "ramp_x3_gru": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_p, c_p, c_f,
                           c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_p]),
+    # the whole operator as one call (csrc/update_op.hip)
+    "ramp_update_forward": (c_i, [ctypes.POINTER(UpdateArgs), c_p]),
     # device-resident tracking step (csrc/track.hip); the ramp_track descriptor is mirrored in track_dev.py
     "ramp_track_sizeof": (c_sz, []),
     "ramp_track_plan_workspace_bytes": (c_sz, [c_i, c_i, c_i]),

@@ -73,6 +73,16 @@ size_t ramp_i_ba_cov_dyn_ws(int opt_window, int max_patches);
 int ramp_i_ba_cov_dyn(const BaProblem &p, const BaGroups &g, void *ba_ws, size_t ba_ws_bytes, void *cov_ws,
                       size_t cov_ws_bytes, int32_t *info, float *cov, float *depth_var, float *stats, hipStream_t st,
                       const BaMapOut *map = nullptr);
+// one call of the update operator (csrc/update_op.hip): ramp_update_args plus what only the device-resident step has
+struct UpdOp {
+  ramp_update_args a;
+  const int32_t *dyn;          // device-side sizes (nullptr: a.E rows are live), a.E is then the launch bound
+  void *gate_event;            // fp16 features: "the next frame's front end may start", in front of the first SoftAgg -- an
+  uint32_t *gate_flag;         // event recorded there, or (gate_flag) the word gate_seq that launch's first workgroup stores
+  uint32_t gate_seq;
+};
+int ramp_i_update_check(const UpdOp &op);                      // RAMP_EINVAL unless every pointer the precision needs is there
+int ramp_i_update_operator(const UpdOp &op, hipStream_t st);   // (a checked op)
 extern "C" {
 int ramp_i_corr_fwd(const void *fmap1, const ramp_corr_level *levels, int nlevels, const float *coords,
                     const int64_t *ii, const int64_t *jj, const int32_t *order, void *out, int out_row_elems,

@@ -524,6 +524,55 @@ __global__ void trk_bound_check_kernel(int32_t *dyn, int E_bound) {
   if (dyn[RAMP_DYN_E] > E_bound) atomicOr(dyn + RAMP_DYN_STATUS, 32);
 }
 
+// Ramp_vo.update()'s reprojection and correlation volume (ramp/Ramp_vo.py:276-284) of the graph g on launch bound Eb, into
+// t->coords / t->corr.  dtype: the correlation launch's code (RAMP_F16, or RAMP_F32 with its kernel bits); wrap: the
+// measurement flags RAMP_TRACK_WRAP_COORDS / _COMPACT_COORDS or 0; go: store / record the fp32 step's gate (below)
+// (pops.transform as a launch of its own: riding in the correlation kernel's geometry prologue it was a wash -- the
+// nine-lane Lie algebra adds to every wave what the 7.8 us launch took, corr 158 -> 166 us)
+static int trk_reproject_correlate(const ramp_track *t, const int64_t *g, int Eb, int dtype, int wrap, bool go, void *gate_event,
+                                   hipStream_t st) {
+  const int64_t *ii = g, *jj = g + t->E_cap, *kk = g + 2 * (size_t)t->E_cap;
+  TRK_DO(ramp_i_transform_dyn(t->poses, t->patches, t->intrinsics, ii, jj, kk, t->coords, Eb, t->dyn, st));
+  if (wrap)
+    hipLaunchKernelGGL(trk_wrap_coords_kernel, dim3(ramp_cdiv(Eb, 256)), dim3(256), 0, st, t->coords, t->dyn, t->P,
+                       (float)t->feat_w, (float)t->feat_h, (wrap & RAMP_TRACK_COMPACT_COORDS) ? 1 : 0);
+  ramp_corr_level lv[2];
+  lv[0].fmap = t->fmap1; lv[0].H2 = t->feat_h; lv[0].W2 = t->feat_w; lv[0].coord_div = 1.0f;
+  lv[1].fmap = t->fmap2; lv[1].H2 = t->feat_h / 4; lv[1].W2 = t->feat_w / 4; lv[1].coord_div = 4.0f;
+  TRK_PROBE(0);
+  if (go) {
+    // The fp32 front end is ~1.1 ms against ~0.9 ms of step behind the second neighbour chain, so the next frame's front
+    // end may start at the top of the step, before the correlation launch: a one-thread launch stores the "go" word
+    // (t->gate_flag), or the caller's event is recorded.  Measured against later gates (bench.py --mixed 0, two runs each):
+    // before the first SoftAgg 434 kf/s, before c1 / c2 455, before the correlation MLP 471, here 492
+    if (t->gate_flag) hipLaunchKernelGGL(trk_signal_kernel, dim3(1), dim3(1), 0, st, t->gate_flag, t->gate_seq);
+    else if (gate_event && hipEventRecord((hipEvent_t)gate_event, st) != hipSuccess) return RAMP_ELAUNCH;
+  }
+  // (the plan's (jj, ii)-major schedule: worth 1.3 % of the frame against graph order, round 5's A/B)
+  TRK_DO(ramp_i_corr_fwd(t->gmap, lv, 2, t->coords, kk, jj, t->ij_order, t->corr, 896, (long)t->M * t->mem, t->mem, Eb,
+                         t->mem * t->M, t->mem, 128, t->P, 3, dtype, t->feat_plain ? RAMP_NHWC : RAMP_NHWC32, t->dyn, st, nullptr,
+                         nullptr, nullptr, nullptr, t->fmap1_slot));
+  TRK_PROBE(1);
+  return RAMP_OK;
+}
+
+// the tail of Ramp_vo.update() (ramp/Ramp_vo.py:298-310) from t->target / t->weight: two bundle-adjustment iterations, the
+// point cloud (with the motion test following, it rides in that launch: *pc_with_mm) and, without a graph edit behind it,
+// the identity row map -- the new hidden state is indexed by the factors themselves from there on
+static int trk_solve(const ramp_track *t, int64_t *g, int Eb, int flags, bool *pc_with_mm, hipStream_t st) {
+  const int64_t *ii = g, *jj = g + t->E_cap, *kk = g + 2 * (size_t)t->E_cap;
+  TRK_PROBE(3);
+  TRK_DO(ramp_i_ba_dyn(trk_ba_problem(t, ii, jj, kk, t->target, t->weight, Eb, t->dyn), trk_ba_groups(t), 2, t->ba_ws,
+                       t->ba_ws_bytes, t->dyn + RAMP_DYN_STATUS, st));
+  TRK_PROBE(4);
+  *pc_with_mm = t->points && t->ixm && (flags & RAMP_TRACK_KEYFRAME) && !(flags & RAMP_TRACK_MM_GIVEN) && t->mm;
+  if (t->points && t->ixm && !*pc_with_mm)
+    TRK_DO(ramp_i_point_cloud_dyn(t->poses, t->patches, t->intrinsics, t->ixm, t->points, t->m_cap, t->dyn, t->M, st));
+  if (!(flags & RAMP_TRACK_KEYFRAME))
+    hipLaunchKernelGGL(trk_iota_kernel, dim3(ramp_cdiv(Eb, 256)), dim3(256), 0, st, g + 3 * (size_t)t->E_cap, t->dyn);
+  return RAMP_OK;
+}
+
 int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, int E_bound, const float *k_new,
                     void *gate_event, void *stream) {
   if (!trk_valid(t) || cur < 0 || cur > 1 || E_bound < 0) return RAMP_EINVAL;
@@ -533,10 +582,9 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
   const int Eb = (E_bound > 0 && E_bound < Ec) ? E_bound : Ec;
   const int new_cap = (2 * t->patch_lifetime - 1) * t->M;          // factors one frame adds
   // (the bound check rides in the frame commit's launch when there is one)
-  const int fold = 1;
-  const bool folded = fold && (flags & RAMP_TRACK_COMMIT);
+  const bool folded = flags & RAMP_TRACK_COMMIT;
   if (Eb < Ec && !folded) hipLaunchKernelGGL(trk_bound_check_kernel, dim3(1), dim3(1), 0, st, t->dyn, Eb);
-  const int64_t *g = t->graph[cur];
+  int64_t *g = t->graph[cur];
   const int64_t *ii = g, *jj = g + Ec, *kk = g + 2 * (size_t)Ec, *row = g + 3 * (size_t)Ec;
   const int32_t *dyn = t->dyn;
   bool pc_with_mm = false;
@@ -557,131 +605,41 @@ int ramp_track_step(const ramp_track *t, int cur, int64_t counter, int flags, in
                                    mod, dyn, (t->median && t->keyframe_index >= 4) ? t->median : nullptr, t->dyn + RAMP_DYN_STATUS, (Eb < Ec && folded) ? Eb : 0, t->n_rows, st,
                                    t->fmap1_slot, 3, nullptr, 0));
   }
-  // fp32 features: the correlation launch is corr_mfma_kernel<CorrX2> on planes of split fp16 pairs (feat_fp32 == 2: the
-  // caller packed them so, RAMP_CORR_X2) or, as t->corr_f32_mfma says, corr_mfma_kernel<float> / corr_kernel<float> (the
-  // reference kernel's summation order) with rows padded to 896 floats, the operator csrc/update_x3.hip's chains; PRE / POST
-  // around a caller-run operator remain (RAMP_X3=0: library GEMMs)
+  // the correlation launch.  fp16 features: corr_mfma_kernel<half>.  fp32 features: corr_mfma_kernel<CorrX2> on planes of
+  // split fp16 pairs (feat_fp32 == 2: the caller packed them so, RAMP_CORR_X2) or, as t->corr_f32_mfma says,
+  // corr_mfma_kernel<float> / corr_kernel<float> (the reference kernel's summation order); rows padded to 896 elements
   if (t->feat_fp32 == 2 && t->feat_plain) return RAMP_EINVAL;
-  const int f32_code = RAMP_F32 | (t->feat_fp32 == 2 ? RAMP_CORR_X2 : t->corr_f32_mfma ? RAMP_CORR_MFMA32 : 0);
+  const int corr_code = !t->feat_fp32 ? RAMP_F16
+                                      : RAMP_F32 | (t->feat_fp32 == 2 ? RAMP_CORR_X2 : t->corr_f32_mfma ? RAMP_CORR_MFMA32 : 0);
+  // PRE / POST: update() around an operator the caller runs in between (RAMP_X3=0: library GEMMs)
   if (flags & RAMP_TRACK_UPDATE_PRE) {
     if (!t->coords || !t->corr) return RAMP_EINVAL;
-    TRK_DO(ramp_i_transform_dyn(t->poses, t->patches, t->intrinsics, ii, jj, kk, t->coords, Eb, dyn, st));
-    ramp_corr_level lv[2];
-    lv[0].fmap = t->fmap1; lv[0].H2 = t->feat_h; lv[0].W2 = t->feat_w; lv[0].coord_div = 1.0f;
-    lv[1].fmap = t->fmap2; lv[1].H2 = t->feat_h / 4; lv[1].W2 = t->feat_w / 4; lv[1].coord_div = 4.0f;
-    TRK_PROBE(0);
-    if (t->feat_fp32)
-      TRK_DO(ramp_i_corr_fwd(t->gmap, lv, 2, t->coords, kk, jj, t->ij_order, t->corr, 896, (long)t->M * t->mem, t->mem, Eb,
-                             t->mem * t->M, t->mem, 128, t->P, 3, f32_code, t->feat_plain ? RAMP_NHWC : RAMP_NHWC32, dyn, st, nullptr, nullptr, nullptr, nullptr,
-                             t->fmap1_slot));
-    else
-      TRK_DO(ramp_i_corr_fwd(t->gmap, lv, 2, t->coords, kk, jj, t->ij_order, t->corr, 896, (long)t->M * t->mem, t->mem, Eb,
-                             t->mem * t->M, t->mem, 128, t->P, 3, RAMP_F16, t->feat_plain ? RAMP_NHWC : RAMP_NHWC32, dyn, st, nullptr, nullptr, nullptr, nullptr,
-                             t->fmap1_slot));
-    TRK_PROBE(1);
+    TRK_DO(trk_reproject_correlate(t, g, Eb, corr_code, 0, false, nullptr, st));
   }
   if (flags & RAMP_TRACK_UPDATE_POST) {
     if (!t->target || !t->weight || !t->ba_ws) return RAMP_EINVAL;
-    TRK_PROBE(3);
-    TRK_DO(ramp_i_ba_dyn(trk_ba_problem(t, ii, jj, kk, t->target, t->weight, Eb, dyn), trk_ba_groups(t), 2, t->ba_ws,
-                         t->ba_ws_bytes, t->dyn + RAMP_DYN_STATUS, st));
-    TRK_PROBE(4);
-    pc_with_mm = t->points && t->ixm && (flags & RAMP_TRACK_KEYFRAME) && !(flags & RAMP_TRACK_MM_GIVEN) && t->mm;
-    if (t->points && t->ixm && !pc_with_mm)
-      TRK_DO(ramp_i_point_cloud_dyn(t->poses, t->patches, t->intrinsics, t->ixm, t->points, t->m_cap, dyn, t->M, st));
-    if (!(flags & RAMP_TRACK_KEYFRAME))
-      hipLaunchKernelGGL(trk_iota_kernel, dim3(ramp_cdiv(Eb, 256)), dim3(256), 0, st, t->graph[cur] + 3 * (size_t)Ec, t->dyn);
+    TRK_DO(trk_solve(t, g, Eb, flags, &pc_with_mm, st));
   }
   if (flags & RAMP_TRACK_UPDATE) {
-    const ramp_track_weights &w = t->w;
-    if (!t->coords || !t->corr || !t->net[0] || !t->net[1] || !t->net[2] || !t->fg || !t->ykk || !t->hkk || !t->yij ||
-        !t->hij || !t->target || !t->weight || !t->ba_ws || (!t->feat_fp32 && !t->sagg_frag))
-      return RAMP_EINVAL;
-    // Ramp_vo.update(), ramp/Ramp_vo.py:276-310
-    // (pops.transform as a launch of its own: riding in the correlation kernel's geometry prologue it was a wash -- the
-    // nine-lane Lie algebra adds to every wave what the 7.8 us launch took, corr 158 -> 166 us)
-    TRK_DO(ramp_i_transform_dyn(t->poses, t->patches, t->intrinsics, ii, jj, kk, t->coords, Eb, dyn, st));
-    if (flags & (RAMP_TRACK_WRAP_COORDS | RAMP_TRACK_COMPACT_COORDS))
-      hipLaunchKernelGGL(trk_wrap_coords_kernel, dim3(ramp_cdiv(Eb, 256)), dim3(256), 0, st, t->coords, dyn, t->P,
-                         (float)t->feat_w, (float)t->feat_h, (flags & RAMP_TRACK_COMPACT_COORDS) ? 1 : 0);
-    ramp_corr_level lv[2];
-    lv[0].fmap = t->fmap1; lv[0].H2 = t->feat_h; lv[0].W2 = t->feat_w; lv[0].coord_div = 1.0f;
-    lv[1].fmap = t->fmap2; lv[1].H2 = t->feat_h / 4; lv[1].W2 = t->feat_w / 4; lv[1].coord_div = 4.0f;
-    TRK_PROBE(0);
-    if (t->feat_fp32) {
-      // ---- fp32 features (MIXED_PRECISION off): the same step with csrc/update_x3.hip's chains (Linear layers on the f16
-      // matrix cores from split fp32 operands), fp32 tables, [f | g] rows + segment softmax + h for the two SoftAggs.
-      // The fp32 front end is ~1.1 ms against ~0.9 ms of step behind the second neighbour chain, so the next frame's front
-      // end may start at the top of the step, before the correlation launch: a one-thread launch stores the "go" word
-      // (t->gate_flag), or the caller's event is recorded.  Measured against later gates (bench.py --mixed 0, two runs each):
-      // before the first SoftAgg 434 kf/s, before c1 / c2 455, before the correlation MLP 471, here 492
-      if (t->gate_flag) hipLaunchKernelGGL(trk_signal_kernel, dim3(1), dim3(1), 0, st, t->gate_flag, t->gate_seq);
-      else if (gate_event && hipEventRecord((hipEvent_t)gate_event, st) != hipSuccess) return RAMP_ELAUNCH;
-      TRK_DO(ramp_i_corr_fwd(t->gmap, lv, 2, t->coords, kk, jj, t->ij_order, t->corr, 896, (long)t->M * t->mem, t->mem, Eb,
-                             t->mem * t->M, t->mem, 128, t->P, 3, f32_code, t->feat_plain ? RAMP_NHWC : RAMP_NHWC32, dyn, st, nullptr, nullptr, nullptr,
-                             nullptr, t->fmap1_slot));
-      TRK_PROBE(1);
-      const float *corr32 = (const float *)t->corr;
-      float *fg32 = (float *)t->fg, *ykk = (float *)t->ykk, *hkk = (float *)t->hkk, *yij = (float *)t->yij, *hij = (float *)t->hij;
-      TRK_DO(ramp_i_x3_corr_mlp(corr32, 896, w.corr_w1, w.corr_b1, w.corr_w2, w.corr_b2, w.corr_w3, w.corr_b3, w.corr_ln_w,
-                                w.corr_ln_b, w.corr_ln_eps, t->net[0], row, (const float *)t->imap, kk, (long)t->M * t->mem,
-                                w.norm_w, w.norm_b, w.norm_eps, t->net[1], Eb, dyn, st));
-      TRK_DO(ramp_i_x3_nbr(t->net[1], t->ix, w.c1_wa, w.c1_ba, w.c1_wb, w.c1_bb, t->net[2], Eb, dyn, st));
-      TRK_DO(ramp_i_x3_nbr(t->net[2], t->jx, w.c2_wa, w.c2_ba, w.c2_wb, w.c2_bb, t->net[1], Eb, dyn, st));
-      float *net32 = t->net[1];
-      TRK_DO(ramp_i_x3_fg(net32, nullptr, nullptr, nullptr, w.kk_wf, w.kk_bf, w.kk_wg, w.kk_bg, fg32, Eb, dyn, st));
-      TRK_DO(ramp_x3_segment_softmax(fg32, t->kk_order, t->kk_seg, t->kk_ngroups, ykk, t->kk_cap, stream));
-      TRK_DO(ramp_x3_linear(ykk, w.kk_wh, w.kk_bh, hkk, t->kk_cap, t->kk_ngroups, stream));
-      TRK_DO(ramp_i_x3_fg(net32, hkk, t->kk_gid, nullptr, w.ij_wf, w.ij_bf, w.ij_wg, w.ij_bg, fg32, Eb, dyn, st));
-      TRK_DO(ramp_x3_segment_softmax(fg32, t->ij_order, t->ij_seg, t->ij_ngroups, yij, t->ij_cap, stream));
-      TRK_DO(ramp_x3_linear(yij, w.ij_wh, w.ij_bh, hij, t->ij_cap, t->ij_ngroups, stream));
-      TRK_DO(ramp_i_x3_gru(net32, hkk, t->kk_gid, hij, t->ij_gid, w.ln1_w, w.ln1_b, w.ln1_eps, w.gru_w, w.gru_b, w.ln2_w, w.ln2_b,
-                           w.ln2_eps, t->net[0], nullptr, Eb, dyn, (const float *)w.heads_w, w.heads_b, t->coords, t->target,
-                           t->weight, t->P, (float)t->feat_w, (float)t->feat_h, st));
-    } else {
-    // (the plan's (jj, ii)-major schedule: worth 1.3 % of the frame against graph order, round 5's A/B)
-    TRK_DO(ramp_i_corr_fwd(t->gmap, lv, 2, t->coords, kk, jj, t->ij_order, t->corr, 896, (long)t->M * t->mem, t->mem, Eb,
-                           t->mem * t->M, t->mem, 128, t->P, 3, RAMP_F16, t->feat_plain ? RAMP_NHWC : RAMP_NHWC32, dyn, st,
-                           nullptr, nullptr, nullptr, nullptr, t->fmap1_slot));
-    TRK_PROBE(1);
-    // the update operator, ramp/net.py:69-90 (the fp16 fused chains of csrc/update_mlp.hip)
-    TRK_DO(ramp_i_upd_corr_mlp(t->corr, 896, w.corr_w1, w.corr_b1, w.corr_w2, w.corr_b2, w.corr_w3, w.corr_b3, w.corr_ln_w,
-                               w.corr_ln_b, w.corr_ln_eps, t->net[0], row, t->imap, kk, (long)t->M * t->mem, w.norm_w,
-                               w.norm_b, w.norm_eps, t->net[1], Eb, dyn, st));
-    TRK_DO(ramp_i_upd_nbr(t->net[1], t->ix, w.c1_wa, w.c1_ba, w.c1_wb, w.c1_bb, t->net[2], nullptr, Eb, dyn, st));
-    TRK_DO(ramp_i_upd_nbr(t->net[2], t->jx, w.c2_wa, w.c2_ba, w.c2_wb, w.c2_bb, t->net[1], nullptr, Eb, dyn, st));
-    float *net = t->net[1];
-    // the next frame's front end may start here, before the first SoftAgg (against before the gru chain, rounds 2-3: +1.2 %
-    // SingleScale, +2.1 % MultiScale -- the front end costs the operator ~25 us and gives bundle adjustment 12 back).  The
-    // "go" is the word the first SoftAgg launch's first workgroup stores (t->gate_flag), or else the caller's event.
-    if (!t->gate_flag && gate_event && hipEventRecord((hipEvent_t)gate_event, st) != hipSuccess) return RAMP_ELAUNCH;
-    // SoftAgg x 2 (ramp/net.py:84-85): gather-by-group tiles, g and f on the same tile, online softmax in registers, h on
-    // the merged fragments -- 2 launches each, no [E, 768] rows (csrc/update_mlp.hip).  The pair SoftAgg reads net +
-    // hkk[patch group] and does not write the sum back: the gru launch forms (net + hkk[.]) + hij[.] itself
-    TRK_DO(ramp_i_upd_softagg(net, nullptr, nullptr, t->kk_order, t->kk_gid, w.kk_wf, w.kk_bf, w.kk_wg, w.kk_bg, t->sagg_frag,
-                              Eb, dyn, st, t->gate_flag, t->gate_seq));
-    TRK_DO(ramp_upd_softagg_finish(t->sagg_frag, t->kk_seg, t->kk_ngroups, w.kk_wh, w.kk_bh, t->hkk, t->kk_cap, stream));
-    TRK_DO(ramp_i_upd_softagg(net, t->hkk, t->kk_gid, t->ij_order, t->ij_gid, w.ij_wf, w.ij_bf, w.ij_wg, w.ij_bg, t->sagg_frag,
-                              Eb, dyn, st));
-    TRK_DO(ramp_upd_softagg_finish(t->sagg_frag, t->ij_seg, t->ij_ngroups, w.ij_wh, w.ij_bh, t->hij, t->ij_cap, stream));
-    // (the heads and target / weight are formed in the gru launch's epilogue: no relu(net) round trip, one launch less)
-    TRK_DO(ramp_i_upd_gru(net, t->hkk, t->kk_gid, t->hij, t->ij_gid, w.ln1_w, w.ln1_b, w.ln1_eps, w.gru_w, w.gru_b, w.ln2_w,
-                          w.ln2_b, w.ln2_eps, t->net[0], nullptr, Eb, dyn, w.heads_w, w.heads_b, t->coords, t->target,
-                          t->weight, t->P, (float)t->feat_w, (float)t->feat_h, t->E_hint, st));
-    }   // (fp16 features)
+    // Ramp_vo.update(), ramp/Ramp_vo.py:276-310: reproject and correlate, the update operator (ramp/net.py:69-90; the new
+    // hidden state replaces the previous one in net[0]), solve
+    UpdOp op = {};
+    ramp_update_args &a = op.a;
+    a.w = &t->w; a.corr = t->corr; a.net_prev = t->net[0]; a.net_map = row; a.inp = t->imap; a.inp_idx = kk;
+    a.inp_mod = (long)t->M * t->mem; a.state[0] = t->net[1]; a.state[1] = t->net[2]; a.net_out = t->net[0];
+    a.coords = t->coords; a.target = t->target; a.weight = t->weight;
+    a.kk_order = t->kk_order; a.kk_gid = t->kk_gid; a.kk_seg = t->kk_seg; a.kk_ngroups = t->kk_ngroups; a.kk_cap = t->kk_cap;
+    a.ij_order = t->ij_order; a.ij_gid = t->ij_gid; a.ij_seg = t->ij_seg; a.ij_ngroups = t->ij_ngroups; a.ij_cap = t->ij_cap;
+    a.ix = t->ix; a.jx = t->jx; a.sagg_frag = t->sagg_frag; a.fg = (float *)t->fg; a.ykk = (float *)t->ykk;
+    a.yij = (float *)t->yij; a.hkk = t->hkk; a.hij = t->hij; a.E = Eb; a.E_hint = t->E_hint; a.P = t->P;
+    a.fp32 = t->feat_fp32 != 0; a.wd = (float)t->feat_w; a.ht = (float)t->feat_h;
+    op.dyn = dyn; op.gate_event = gate_event; op.gate_flag = t->gate_flag; op.gate_seq = t->gate_seq;
+    if (!t->coords || !t->ba_ws || ramp_i_update_check(op) != RAMP_OK) return RAMP_EINVAL;
+    TRK_DO(trk_reproject_correlate(t, g, Eb, corr_code, flags & (RAMP_TRACK_WRAP_COORDS | RAMP_TRACK_COMPACT_COORDS),
+                                   a.fp32 != 0, gate_event, st));
+    TRK_DO(ramp_i_update_operator(op, st));
     TRK_PROBE(2);
-    TRK_PROBE(3);
-    TRK_DO(ramp_i_ba_dyn(trk_ba_problem(t, ii, jj, kk, t->target, t->weight, Eb, dyn), trk_ba_groups(t), 2, t->ba_ws,
-                         t->ba_ws_bytes, t->dyn + RAMP_DYN_STATUS, st));
-    TRK_PROBE(4);
-    // (with the motion test following, the point cloud rides in its launch)
-    pc_with_mm = t->points && t->ixm && (flags & RAMP_TRACK_KEYFRAME) && !(flags & RAMP_TRACK_MM_GIVEN) && t->mm;
-    if (t->points && t->ixm && !pc_with_mm)
-      TRK_DO(ramp_i_point_cloud_dyn(t->poses, t->patches, t->intrinsics, t->ixm, t->points, t->m_cap, dyn, t->M, st));
-    if (!(flags & RAMP_TRACK_KEYFRAME)) {
-      // the new hidden state is indexed by the factors themselves from here on
-      hipLaunchKernelGGL(trk_iota_kernel, dim3(ramp_cdiv(Eb, 256)), dim3(256), 0, st, t->graph[cur] + 3 * (size_t)Ec, t->dyn);
-    }
+    TRK_DO(trk_solve(t, g, Eb, flags, &pc_with_mm, st));
   }
   if (flags & RAMP_TRACK_KEYFRAME) {
     if (!t->mm || !t->dlog) return RAMP_EINVAL;

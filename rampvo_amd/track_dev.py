@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import c_i, c_p, c_sz
+from ._lib import TrackWeights, _ptr_fields, c_i, c_p, c_sz
 
 DYN_WORDS = 32
 (DYN_N, DYN_NROW, DYN_E, DYN_KLO, DYN_FLO, DYN_W, DYN_REMOVED, DYN_K, DYN_NPREV, DYN_EPREV, DYN_EKEPT, DYN_STATUS,
@@ -30,19 +30,6 @@ POSE_POSE, POSE_INV, POSE_FRAME2 = 16, 23, 31
 TRAJ_UNRESOLVED = 1
 
 
-def _ptr_fields(names):
-    return [(n, c_p) for n in names]
-
-
-class TrackWeights(ctypes.Structure):
-    _fields_ = (_ptr_fields(["corr_w1", "corr_w2", "corr_w3", "corr_b1", "corr_b2", "corr_b3", "corr_ln_w", "corr_ln_b",
-                             "norm_w", "norm_b", "c1_wa", "c1_wb", "c2_wa", "c2_wb", "c1_ba", "c1_bb", "c2_ba", "c2_bb",
-                             "kk_wf", "kk_wg", "kk_wh", "ij_wf", "ij_wg", "ij_wh", "kk_bf", "kk_bg", "kk_bh", "ij_bf",
-                             "ij_bg", "ij_bh", "ln1_w", "ln1_b", "ln2_w", "ln2_b"])
-                + [("gru_w", c_p * 6), ("gru_b", c_p * 6), ("heads_w", c_p), ("heads_b", c_p)]
-                + [(n, ctypes.c_float) for n in ("corr_ln_eps", "norm_eps", "ln1_eps", "ln2_eps")])
-
-
 class Track(ctypes.Structure):
     _fields_ = ([(n, c_i) for n in ("M", "P", "mem", "n_rows", "patch_lifetime", "removal_window", "opt_window",
                                     "keyframe_index", "motion_model", "feat_h", "feat_w", "E_cap", "kk_cap", "ij_cap",
@@ -56,7 +43,7 @@ class Track(ctypes.Structure):
                                "kk_ukeys", "ij_ukeys", "ix", "jx", "kj", "plan_ws"])
                 + [("plan_ws_bytes", c_sz), ("w", TrackWeights)]
                 + _ptr_fields(["coords", "corr"]) + [("net", c_p * 3)]
-                + _ptr_fields(["fg", "ykk", "hkk", "yij", "hij", "relu_t", "sagg_frag", "target", "weight", "ba_ws"])
+                + _ptr_fields(["fg", "ykk", "hkk", "yij", "hij", "sagg_frag", "target", "weight", "ba_ws"])
                 + [("ba_ws_bytes", c_sz)]
                 + _ptr_fields(["mm", "median", "dlog", "edit_ws", "dyn_host", "dyn_host_dev"]) + [("probe", c_p * 5), ("E_hint", c_i),
                    ("gate_seq", ctypes.c_uint32), ("feat_fp32", c_i), ("feat_plain", c_i), ("gate_flag", c_p), ("fmap1_slot", c_p),
@@ -247,7 +234,6 @@ class DeviceTrack:
         self.fg = e((E_cap if self.x3 else 16, 768), tt)             # (fp16: the fused SoftAgg has no [f | g] rows)
         self.ykk, self.hkk = z((kk_cap, 384), tt), z((kk_cap, 384), tt)
         self.yij, self.hij = z((ij_cap, 384), tt), z((ij_cap, 384), tt)
-        self.relu_t = e((16 if self.fp32 else E_cap, 384), f16)
         # fragment table of the fused SoftAgg (csrc/update_mlp.hip::upd_softagg_kernel): (m, z, a)[384] per run
         self.sagg_frag = e((16 if self.fp32 else lib.ramp_upd_softagg_frag_rows(E_cap, max(kk_cap, ij_cap)), 3, 384), f32)
         self.target, self.weight = z((E_cap, 2), f32), z((E_cap, 2), f32)
@@ -289,7 +275,7 @@ class DeviceTrack:
                               ij_gid=self.ij["gid"], ij_seg=self.ij["seg"], ij_ngroups=self.ij["ngroups"],
                               ij_ukeys=self.ij["ukeys"], ix=self.ix, jx=self.jx, kj=self.kj, plan_ws=self.plan_ws,
                               coords=self.coords, corr=self.corr, fg=self.fg, ykk=self.ykk, hkk=self.hkk, yij=self.yij,
-                              hij=self.hij, relu_t=self.relu_t, sagg_frag=self.sagg_frag, target=self.target, weight=self.weight,
+                              hij=self.hij, sagg_frag=self.sagg_frag, target=self.target, weight=self.weight,
                               ba_ws=self.ba_ws, mm=self.mm, dlog=self.dlog, edit_ws=self.edit_ws,
                               dyn_host=self.dyn_host).items():
             setattr(t, name, P(ten))
@@ -309,28 +295,11 @@ class DeviceTrack:
 
     # ------------------------------------------------------------------ weights / front-end outputs
     def bind_weights(self, fu):
-        w = fu.weights()
-        if self._wkey == fu._key:
-            return
-        tw = self.t.w
-        P = lambda x: x.data_ptr()
-        tw.corr_w1, tw.corr_b1 = map(P, w["corr1_pack"])
-        tw.corr_w2, tw.corr_b2, tw.corr_w3, tw.corr_b3 = map(P, w["tail_pack"])
-        tw.corr_ln_w, tw.corr_ln_b, tw.corr_ln_eps = P(w["corr_ln"][0]), P(w["corr_ln"][1]), float(w["corr_ln"][2])
-        tw.norm_w, tw.norm_b, tw.norm_eps = P(w["norm"][0]), P(w["norm"][1]), float(w["norm"][2])
-        tw.c1_wa, tw.c1_ba, tw.c1_wb, tw.c1_bb = map(P, w["c1_pack"])
-        tw.c2_wa, tw.c2_ba, tw.c2_wb, tw.c2_bb = map(P, w["c2_pack"])
-        tw.kk_wf, tw.kk_bf, tw.kk_wg, tw.kk_bg = map(P, w["kk_fg_pack"])
-        tw.ij_wf, tw.ij_bf, tw.ij_wg, tw.ij_bg = map(P, w["ij_fg_pack"])
-        tw.kk_wh, tw.kk_bh = map(P, w["kk_h_pack"])
-        tw.ij_wh, tw.ij_bh = map(P, w["ij_h_pack"])
-        tw.ln1_w, tw.ln1_b, tw.ln1_eps = P(w["ln1"][0]), P(w["ln1"][1]), float(w["ln1"][2])
-        tw.ln2_w, tw.ln2_b, tw.ln2_eps = P(w["ln2"][0]), P(w["ln2"][1]), float(w["ln2"][2])
-        wp, bs = w["gru_pack"][0], w["gru_pack"][1]
-        for i in range(6):
-            tw.gru_w[i], tw.gru_b[i] = P(wp[i]), P(bs[i])
-        tw.heads_w, tw.heads_b = map(P, w["heads_pack"])
-        self._wkey = fu._key
+        """the operator's weight record is FusedUpdate's (one table for the host-driven call and for the step)"""
+        rec = fu.record()
+        if self._wkey != fu._key:
+            ctypes.memmove(ctypes.byref(self.t.w), ctypes.byref(rec), ctypes.sizeof(TrackWeights))
+            self._wkey = fu._key
 
     def bind_front_end(self, ex, patches):
         """the static output buffers of the front-end graph (the same objects every frame)"""

@@ -1,16 +1,17 @@
-"""Fused forward of the update operator (reference: ramp/net.py:69-90).
+"""Forward of the update operator (reference: ramp/net.py:69-90).
 
-~19 GEMMs (hipBLASLt through torch, bias / bias+ReLU epilogues) stitched by the row-fused HIP
-kernels of csrc/update.hip: every gather, residual add, LayerNorm, gate and dtype cast between
-two GEMMs is ONE kernel.  The hidden state stays fp32; GEMM inputs/outputs are ``dtype`` (half
-under MIXED_PRECISION -- what the reference's autocast does -- or float).  Weight copies in
-``dtype`` (f|g and the two heads stacked) are cached per module.
+The hidden state stays fp32; the Linear layers' inputs / outputs are ``dtype`` (half under MIXED_PRECISION -- what the
+reference's autocast does -- or float).  ``FusedUpdate.hidden`` is one C call on the fused GEMM chains (the device-resident
+step's launch sequence, csrc/update_op.hip), or, as an A/B and test reference, library GEMMs stitched by the row kernels
+of csrc/update.hip.  Weight copies in the formats both read are cached per module.
 """
+import ctypes
+
 import torch
 import torch.nn.functional as F
 
 from . import _lib, switches
-from ._lib import check, lib, ptr, stream
+from ._lib import TrackWeights, UpdateArgs, check, lib, ptr, stream
 
 _code = {torch.float32: _lib.RAMP_F32, torch.float16: _lib.RAMP_F16}
 
@@ -48,21 +49,20 @@ def pack_linear_x3(weight):
 
 
 class FusedUpdate:
+    """Two paths.  The default one is a single C call, ``ramp_update_forward`` (csrc/update_op.hip): the launch sequence the
+    device-resident step makes, on the fused chains of csrc/update_mlp.hip (fp16) / csrc/update_x3.hip (fp32).  The
+    library-GEMM path -- ``use_mlp = False`` (fp16, tests) or RAMP_X3=0 (fp32, A/B runs) -- stitches hipBLASLt GEMMs with the
+    row kernels of csrc/update.hip."""
+
     def __init__(self, update, dtype):
         self.m = update
         self.dtype = dtype
-        self._w = None
-        self._key = None
+        self._w = self._key = self._rec = None
         self._params = list(update.parameters())     # module structure is fixed; values are tracked by key
         self._act_ok = True
-        self.use_mlp = True          # fp16: the fused GEMM-chain kernels of csrc/update_mlp.hip (instance switches, for tests:
-        self.use_corr_mlp = True     # False falls back to library GEMMs + the row kernels of csrc/update.hip stage by stage)
-        self.use_softagg = True      # SoftAgg without the [f | g] rows
-        # fp32: the Linear layers on the f16 matrix cores from split operands (csrc/update_x3.hip), fused chains as on the
-        # fp16 path; RAMP_X3=0: library GEMMs + the row kernels of csrc/update.hip (A/B runs)
+        self.use_mlp = True
         self.use_x3 = dtype == torch.float32 and switches.read().x3
-        self.before_gru = None                   # optional callable run right before a stage is enqueued
-        self.hook_at = "gru"
+        self.last_tw = None                      # (target, weight) of the last hidden(..., heads_at=...) on the default path
 
     # ------------------------------------------------------------------ weights
     def weights(self):
@@ -97,48 +97,100 @@ class FusedUpdate:
             g2_r2=(c(m.gru[3].res[2].weight), c(m.gru[3].res[2].bias)),
             heads=(c(torch.cat([m.d[1].weight, m.w[1].weight], 0)), c(torch.cat([m.d[1].bias, m.w[1].bias], 0))),
         )
-        if T == torch.float16:
-            # fused GEMM chains (csrc/update_mlp.hip): weights in MFMA fragment order, biases as the fp32
-            # values of their fp16 roundings (they are half tensors under the reference's autocast)
-            import ctypes
-            gru = [m.gru[1].gate[0], m.gru[1].res[0], m.gru[1].res[2], m.gru[3].gate[0], m.gru[3].res[0], m.gru[3].res[2]]
-            wp = [pack_linear_f16(l.weight) for l in gru]
-            bs = [l.bias.detach().half().float().contiguous() for l in gru]
+        self._rec = None
+        if T == torch.float16 or self.use_x3:
+            # the fused chains: weights in MFMA fragment order (fp16) / as split-fp16 packs (fp32); biases fp32 -- on the fp16
+            # path the values of their fp16 roundings (they are half tensors under the reference's autocast)
+            pack = pack_linear_x3 if self.use_x3 else pack_linear_f16
+            px = lambda l, pad=0: (pack(F.pad(l.weight, (0, pad)) if pad else l.weight), f(c(l.bias)))
+            gru = [px(l) for l in (m.gru[1].gate[0], m.gru[1].res[0], m.gru[1].res[2], m.gru[3].gate[0], m.gru[3].res[0],
+                                   m.gru[3].res[2])]
+            wp, bs = [g[0] for g in gru], [g[1] for g in gru]
             w["gru_pack"] = (wp, bs, (ctypes.c_void_p * 6)(*[t.data_ptr() for t in wp]),
                              (ctypes.c_void_p * 6)(*[t.data_ptr() for t in bs]))
-            hb = lambda l: l.bias.detach().half().float().contiguous()
-            w["c1_pack"] = (pack_linear_f16(m.c1[0].weight), hb(m.c1[0]), pack_linear_f16(m.c1[2].weight), hb(m.c1[2]))
-            w["c2_pack"] = (pack_linear_f16(m.c2[0].weight), hb(m.c2[0]), pack_linear_f16(m.c2[2].weight), hb(m.c2[2]))
-            for name, agg in (("kk_fg_pack", m.agg_kk), ("ij_fg_pack", m.agg_ij)):
-                w[name] = (pack_linear_f16(agg.f.weight), hb(agg.f), pack_linear_f16(agg.g.weight), hb(agg.g))
-            w["kk_h_pack"] = (pack_linear_f16(m.agg_kk.h.weight), hb(m.agg_kk.h))
-            w["ij_h_pack"] = (pack_linear_f16(m.agg_ij.h.weight), hb(m.agg_ij.h))
-            w["corr1_pack"] = (pack_linear_f16(F.pad(m.corr[0].weight, (0, CORR_ROW - m.corr[0].weight.shape[1]))),
-                               hb(m.corr[0]))
-            w["heads_pack"] = (w["heads"][0], w["heads"][1].float().contiguous())
-            w["tail_pack"] = (pack_linear_f16(m.corr[2].weight), hb(m.corr[2]), pack_linear_f16(m.corr[5].weight),
-                              hb(m.corr[5]))
-        if self.use_x3:
-            import ctypes
-            f32 = lambda t: t.detach().float().contiguous()
-            px = lambda l, pad=0: (pack_linear_x3(F.pad(l.weight, (0, pad)) if pad else l.weight), f32(l.bias))
-            gru = [m.gru[1].gate[0], m.gru[1].res[0], m.gru[1].res[2], m.gru[3].gate[0], m.gru[3].res[0], m.gru[3].res[2]]
-            wp = [pack_linear_x3(l.weight) for l in gru]
-            bs = [f32(l.bias) for l in gru]
-            w["gru_pack"] = (wp, bs, (ctypes.c_void_p * 6)(*[t.data_ptr() for t in wp]),
-                             (ctypes.c_void_p * 6)(*[t.data_ptr() for t in bs]))
-            w["c1_pack"] = px(m.c1[0]) + px(m.c1[2])
-            w["c2_pack"] = px(m.c2[0]) + px(m.c2[2])
-            w["kk_fg_pack"] = px(m.agg_kk.f) + px(m.agg_kk.g)
-            w["ij_fg_pack"] = px(m.agg_ij.f) + px(m.agg_ij.g)
+            w["c1_pack"], w["c2_pack"] = px(m.c1[0]) + px(m.c1[2]), px(m.c2[0]) + px(m.c2[2])
+            w["kk_fg_pack"], w["ij_fg_pack"] = px(m.agg_kk.f) + px(m.agg_kk.g), px(m.agg_ij.f) + px(m.agg_ij.g)
             w["kk_h_pack"], w["ij_h_pack"] = px(m.agg_kk.h), px(m.agg_ij.h)
             w["corr1_pack"] = px(m.corr[0], CORR_ROW - m.corr[0].weight.shape[1])
             w["tail_pack"] = px(m.corr[2]) + px(m.corr[5])
-            w["heads_pack"] = (f32(torch.cat([m.d[1].weight, m.w[1].weight], 0)), f32(torch.cat([m.d[1].bias, m.w[1].bias], 0)))
+            w["heads_pack"] = (w["heads"][0], f(w["heads"][1]))
+            self._rec = self._record(w)
         self._w, self._key = w, key
         return w
 
-    # --------------------------------------------------------------- primitives
+    @staticmethod
+    def _record(w):
+        """the packs as a ramp_track_weights record (the tensors stay alive in w)"""
+        r = TrackWeights()
+        P = lambda x: x.data_ptr()
+        r.corr_w1, r.corr_b1 = map(P, w["corr1_pack"])
+        r.corr_w2, r.corr_b2, r.corr_w3, r.corr_b3 = map(P, w["tail_pack"])
+        r.c1_wa, r.c1_ba, r.c1_wb, r.c1_bb = map(P, w["c1_pack"])
+        r.c2_wa, r.c2_ba, r.c2_wb, r.c2_bb = map(P, w["c2_pack"])
+        r.kk_wf, r.kk_bf, r.kk_wg, r.kk_bg = map(P, w["kk_fg_pack"])
+        r.ij_wf, r.ij_bf, r.ij_wg, r.ij_bg = map(P, w["ij_fg_pack"])
+        r.kk_wh, r.kk_bh = map(P, w["kk_h_pack"])
+        r.ij_wh, r.ij_bh = map(P, w["ij_h_pack"])
+        for ln in ("corr_ln", "norm", "ln1", "ln2"):
+            setattr(r, ln + "_w", P(w[ln][0]))
+            setattr(r, ln + "_b", P(w[ln][1]))
+            setattr(r, ln + "_eps", float(w[ln][2]))
+        for i in range(6):
+            r.gru_w[i], r.gru_b[i] = P(w["gru_pack"][0][i]), P(w["gru_pack"][1][i])
+        r.heads_w, r.heads_b = map(P, w["heads_pack"])
+        return r
+
+    def record(self):
+        """the ramp_track_weights record of the current weights: built once per weights key, read by ramp_update_forward
+        and copied by DeviceTrack.bind_weights"""
+        self.weights()
+        if self._rec is None:
+            raise RuntimeError("FusedUpdate: the library-GEMM path (RAMP_X3=0) has no fused-chain weights")
+        return self._rec
+
+    # ------------------------------------------------------------------ forward
+    def hidden(self, net, inp_table, inp_idx, inp_mod, corr, plan, net_map=None, heads_at=None, net32_buf=None, out32_buf=None):
+        """net [*,384] fp32 or None (zeros), row net_map[e] of it per edge when net_map is given (-1: zero
+        row); inp = inp_table[inp_idx % inp_mod] (or inp_table rows when inp_idx is None); corr [E,896] (or dense [E,882]) in
+        self.dtype.  Returns (net_out fp32 [E,384], relu copy in self.dtype).  heads_at = (coords [E,2,P,P], wd, ht), default
+        path: the gru launch also forms the heads and target / weight (left in self.last_tw; the relu copy is then None).
+        net32_buf / out32_buf: the library-GEMM path only (_hidden_gemm)."""
+        self.last_tw = None
+        x3 = self.use_x3
+        if not (x3 or (self.dtype == torch.float16 and self.use_mlp)):
+            return self._hidden_gemm(net, inp_table, inp_idx, inp_mod, corr, plan, net_map, net32_buf, out32_buf)
+        E, dev, T, f32 = corr.shape[0], corr.device, self.dtype, torch.float32
+        if corr.shape[1] != CORR_ROW:          # (a caller with dense [E, 882] rows: zero tail for the 16-byte row loads)
+            corr = F.pad(corr, (0, CORR_ROW - corr.shape[1]))
+        new = lambda *shape, dtype=f32, zero=False: (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=dev)
+        g_kk, g_ij, Gkk, Gij = plan.g_kk, plan.g_ij, max(int(plan.max_kk), 1), max(int(plan.max_ij), 1)
+        state = new(E, 384), new(E, 384)
+        t = dict(corr=corr.contiguous(), net_prev=net, net_map=net_map, inp=inp_table.to(T), inp_idx=inp_idx,
+                 net_out=state[1], kk_order=g_kk.order, kk_gid=g_kk.gid, kk_seg=g_kk.seg_start, kk_ngroups=g_kk.ngroups,
+                 ij_order=g_ij.order, ij_gid=g_ij.gid, ij_seg=g_ij.seg_start, ij_ngroups=g_ij.ngroups, ix=plan.ix_raw,
+                 jx=plan.jx_raw,
+                 # the SoftAgg tables h(y); fp32: the h launch writes the rows below the group count only
+                 hkk=new(Gkk, 384, dtype=T, zero=x3), hij=new(Gij, 384, dtype=T, zero=x3))
+        if x3:
+            t.update(fg=new(E, 768), ykk=new(Gkk, 384), yij=new(Gij, 384))
+        else:
+            t["sagg_frag"] = new(lib().ramp_upd_softagg_frag_rows(E, max(Gkk, Gij)), 3, 384)
+        a = UpdateArgs(E=E, kk_cap=Gkk, ij_cap=Gij, inp_mod=int(inp_mod or 0), fp32=int(x3), P=3)
+        if heads_at is not None:
+            coords, wd, ht = heads_at
+            a.P, a.wd, a.ht = coords.shape[-1], float(wd), float(ht)
+            t.update(coords=coords, target=new(1, E, 2), weight=new(1, E, 2))
+            self.last_tw = (t["target"], t["weight"])
+        else:
+            t["relu_out"] = new(E, 384, dtype=T)
+        a.w = ctypes.pointer(self.record())
+        a.state[0], a.state[1] = state[0].data_ptr(), state[1].data_ptr()
+        for name, ten in t.items():
+            setattr(a, name, ten.data_ptr() if ten is not None else None)
+        check(lib().ramp_update_forward(ctypes.byref(a), stream()), "ramp_update_forward")
+        return state[1], t.get("relu_out")
+
+    # --------------------------------------------------------------- the library-GEMM path
     def lin(self, x, wb):
         return F.linear(x, wb[0], wb[1])
 
@@ -179,6 +231,15 @@ class FusedUpdate:
                                    stream()), "ramp_upd_gated")
         return o32, ot, orl
 
+    def seg(self, fg, groups, max_groups):
+        y = torch.empty(max(max_groups, 1), 384, dtype=self.dtype, device=fg.device)     # the kernel writes every row
+        check(lib().ramp_upd_segment_softmax(ptr(fg), ptr(groups.order), ptr(groups.seg_start), ptr(groups.ngroups),
+                                             ptr(y), int(max_groups), _code[self.dtype], stream()),
+              "ramp_upd_segment_softmax")
+        return y
+
+    # (single stages of the fp16 chains: tests/test_ops_gpu.py, tests/test_fp16_rounding_gpu.py and tools/mb_softagg.py hold
+    # them against their references through these three; hidden() does not use them)
     def fg(self, net32, add_t, add_idx, pack, E):
         """[f(x) | g(x)] of x = net32 (+ add_t[add_idx], written back to net32): csrc/update_mlp.hip::upd_fg_kernel"""
         out = torch.empty(E, 768, dtype=self.dtype, device=net32.device)
@@ -187,16 +248,9 @@ class FusedUpdate:
                                 ptr(wf), ptr(bf), ptr(wg), ptr(bg), ptr(out), E, stream()), "ramp_upd_fg")
         return out
 
-    def seg(self, fg, groups, max_groups):
-        y = torch.empty(max(max_groups, 1), 384, dtype=self.dtype, device=fg.device)     # the kernel writes every row
-        check(lib().ramp_upd_segment_softmax(ptr(fg), ptr(groups.order), ptr(groups.seg_start), ptr(groups.ngroups),
-                                             ptr(y), int(max_groups), _code[self.dtype], stream()),
-              "ramp_upd_segment_softmax")
-        return y
-
     def softagg(self, net32, add_t, add_idx, fg_pack, h_pack, groups, max_groups, E):
         """h(segment softmax-sum of f(x), g(x)) for x = net32 (+ add_t[add_idx]) without the [E, 768] rows:
-        csrc/update_mlp.hip::upd_softagg_kernel + upd_softagg_finish_kernel (the device-resident step runs the same two)"""
+        csrc/update_mlp.hip::upd_softagg_kernel + upd_softagg_finish_kernel"""
         G = max(int(max_groups), 1)
         rows = lib().ramp_upd_softagg_frag_rows(E, G)
         frag = torch.empty(rows, 3, 384, dtype=torch.float32, device=net32.device)
@@ -210,217 +264,45 @@ class FusedUpdate:
 
     def h_lin(self, y, pack, groups):
         """SoftAgg's `h` Linear on the group table, rows below the device-side group count only
-        (csrc/update_mlp.hip::upd_linear_kernel; the device-resident step runs the same kernel)"""
+        (csrc/update_mlp.hip::upd_linear_kernel)"""
         out = torch.empty_like(y)
         check(lib().ramp_upd_linear(ptr(y), ptr(pack[0]), ptr(pack[1]), ptr(out), y.shape[0], ptr(groups.ngroups),
                                     stream()), "ramp_upd_linear")
         return out
 
-    # ------------------------------------------------------------------ forward
-    def hidden(self, net, inp_table, inp_idx, inp_mod, corr, plan, net_map=None, heads_at=None, net32_buf=None, out32_buf=None):
-        """net [*,384] fp32 or None (zeros), row net_map[e] of it per edge when net_map is given (-1: zero
-        row); inp = inp_table[inp_idx % inp_mod] (or inp_table rows when inp_idx is None); corr [E,882] in
-        self.dtype.  Returns (net_out fp32 [E,384], relu copy T).  heads_at = (coords [E,2,P,P], wd, ht): the fused gru
-        launch also forms the heads and target / weight (left in self.last_tw; the relu copy is then None)."""
-        self.last_tw, self._heads_at = None, heads_at
-        # (net32_buf / out32_buf: capacity-sized [>= E, 384] fp32 buffers for the state after the first LayerNorm and for the
-        # result -- the device-resident fp32 step gathers through index rows beyond the live factor count, which must stay
-        # inside an allocation; the non-fused path only)
-        self._bufs = (net32_buf, out32_buf)
+    def _hidden_gemm(self, net, inp_table, inp_idx, inp_mod, corr, plan, net_map, net32_buf=None, out32_buf=None):
+        """hidden() from library GEMMs (hipBLASLt through torch, bias / bias+ReLU epilogues) and the row kernels of
+        csrc/update.hip: every gather, residual add, LayerNorm, gate and dtype cast between two GEMMs is one kernel.  Returns
+        (net_out, relu copy); the caller forms the heads.  net32_buf / out32_buf: capacity-sized [>= E, 384] fp32 buffers for
+        the state after the first LayerNorm and for the result -- the device-resident fp32 step gathers through index rows
+        beyond the live factor count, which must stay inside an allocation."""
         w = self.weights()
         E = corr.shape[0]
-        if self.use_x3:
-            return self._hidden_x3(w, net, inp_table, inp_idx, inp_mod, corr, plan, net_map, heads_at)
-        if "tail_pack" in w and self.use_mlp and corr.shape[1] == CORR_ROW and self.use_corr_mlp:
-            # the whole correlation MLP (3 Linear, LayerNorm, ReLUs) + net + inp + c + LayerNorm: one launch
-            w1, b1 = w["corr1_pack"]
-            w2, b2, w3, b3 = w["tail_pack"]
-            ln, nm = w["corr_ln"], w["norm"]
-            net32 = torch.empty(E, 384, dtype=torch.float32, device=corr.device)
-            check(lib().ramp_upd_corr_mlp(ptr(corr), CORR_ROW, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3),
-                                          ptr(ln[0]), ptr(ln[1]), float(ln[2]), ptr(net), ptr(net_map), ptr(inp_table),
-                                          ptr(inp_idx), int(inp_mod or 0), ptr(nm[0]), ptr(nm[1]), float(nm[2]),
-                                          ptr(net32), E, stream()), "ramp_upd_corr_mlp")
-            c = None
-        else:
-            c = self.lin_relu(corr, w["corr0_pad"] if corr.shape[1] == CORR_ROW else w["corr0"])
-        if c is None:
-            pass
-        else:
-            c = self.lin(c, w["corr2"])
-            _, c = self.row_fuse(E, B=c, ln=w["corr_ln"], relu=True, want_t=True)
-            c = self.lin(c, w["corr5"])
-            net32, _ = self.row_fuse(E, A=net, idxA=net_map, B=inp_table, idxB=inp_idx, modB=inp_mod, C=c,
-                                     ln=w["norm"], want_f32=True, out_f32=net32_buf[:E] if net32_buf is not None else None)
+        lin, lin_relu, fuse = self.lin, self.lin_relu, self.row_fuse
+        # correlation MLP, net + inp + c, LayerNorm (net.py:71-74)
+        c = lin(lin_relu(corr, w["corr0_pad"] if corr.shape[1] == CORR_ROW else w["corr0"]), w["corr2"])
+        _, c = fuse(E, B=c, ln=w["corr_ln"], relu=True, want_t=True)
+        net32, _ = fuse(E, A=net, idxA=net_map, B=inp_table, idxB=inp_idx, modB=inp_mod, C=lin(c, w["corr5"]), ln=w["norm"],
+                        want_f32=True, out_f32=net32_buf[:E] if net32_buf is not None else None)
         # temporal neighbours (net.py:77-82); plan.ix_raw / jx_raw keep the -1 markers
-        if "c1_pack" in w and self.use_mlp:
-            # gather + 2 Linear + residual add per launch; ping-pong between two state buffers
-            tmp = torch.empty_like(net32)
-            net_t = torch.empty(E, 384, dtype=self.dtype, device=net32.device)
-            if self.before_gru is not None and self.hook_at == "nbr":
-                self.before_gru()
-            wa, ba, wb, bb = w["c1_pack"]
-            wa2, ba2, wb2, bb2 = w["c2_pack"]
-            check(lib().ramp_upd_nbr(ptr(net32), ptr(plan.ix_raw), ptr(wa), ptr(ba), ptr(wb), ptr(bb), ptr(tmp), None,
-                                     E, stream()), "ramp_upd_nbr")
-            check(lib().ramp_upd_nbr(ptr(tmp), ptr(plan.jx_raw), ptr(wa2), ptr(ba2), ptr(wb2), ptr(bb2), ptr(net32),
-                                     None, E, stream()), "ramp_upd_nbr")
-            return self._tail(w, E, net32, None, plan)
-        g = self.gather_mask(net32, plan.ix_raw, E)
-        y = self.lin(self.lin_relu(g, w["c1a"]), w["c1b"])
-        self.row_fuse(E, A=net32, B=y, out_f32=net32)
-        g = self.gather_mask(net32, plan.jx_raw, E)
-        y = self.lin(self.lin_relu(g, w["c2a"]), w["c2b"])
-        _, net_t = self.row_fuse(E, A=net32, B=y, out_f32=net32, want_t=True)
-        return self._tail(w, E, net32, net_t, plan)
-
-    def _hidden_x3(self, w, net, inp_table, inp_idx, inp_mod, corr, plan, net_map, heads_at):
-        """the fp32 operator as six fused launches + the two SoftAgg tables (csrc/update_x3.hip); the device-resident step
-        (csrc/track.hip) makes the same launches"""
-        E, dev = corr.shape[0], corr.device
-        f32 = torch.float32
-        if E == 0:
-            z = torch.zeros(0, 384, dtype=f32, device=dev)
-            self.last_tw = (torch.zeros(1, 0, 2, dtype=f32, device=dev), torch.zeros(1, 0, 2, dtype=f32, device=dev))
-            return z, None
-        if corr.shape[1] != CORR_ROW:          # (a caller with dense [E, 882] rows: zero tail for the 16-byte row loads)
-            corr = F.pad(corr, (0, CORR_ROW - corr.shape[1]))
-        corr = corr.contiguous()
-        inp_table = inp_table.float() if inp_table.dtype != f32 else inp_table
-        w1, b1 = w["corr1_pack"]
-        w2, b2, w3, b3 = w["tail_pack"]
-        ln, nm = w["corr_ln"], w["norm"]
-        a = torch.empty(E, 384, dtype=f32, device=dev)
-        b = torch.empty(E, 384, dtype=f32, device=dev)
-        check(lib().ramp_x3_corr_mlp(ptr(corr), CORR_ROW, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(ln[0]),
-                                     ptr(ln[1]), float(ln[2]), ptr(net), ptr(net_map), ptr(inp_table), ptr(inp_idx),
-                                     int(inp_mod or 0), ptr(nm[0]), ptr(nm[1]), float(nm[2]), ptr(a), E, stream()),
-              "ramp_x3_corr_mlp")
-        if self.before_gru is not None and self.hook_at == "nbr":
-            self.before_gru()
-        wa, ba, wb, bb = w["c1_pack"]
-        check(lib().ramp_x3_nbr(ptr(a), ptr(plan.ix_raw), ptr(wa), ptr(ba), ptr(wb), ptr(bb), ptr(b), E, stream()), "ramp_x3_nbr")
-        wa, ba, wb, bb = w["c2_pack"]
-        check(lib().ramp_x3_nbr(ptr(b), ptr(plan.jx_raw), ptr(wa), ptr(ba), ptr(wb), ptr(bb), ptr(a), E, stream()), "ramp_x3_nbr")
-        if self.before_gru is not None and self.hook_at == "softagg":
-            self.before_gru()
-        fg = torch.empty(E, 768, dtype=f32, device=dev)
-
-        def softagg(add_t, add_idx, fg_pack, h_pack, groups, max_groups):
-            G = max(int(max_groups), 1)
-            wf, bf, wg, bg = fg_pack
-            check(lib().ramp_x3_fg(ptr(a), ptr(add_t), ptr(add_idx), None, ptr(wf), ptr(bf), ptr(wg), ptr(bg), ptr(fg), E,
-                                   stream()), "ramp_x3_fg")
-            y = torch.empty(G, 384, dtype=f32, device=dev)
-            check(lib().ramp_x3_segment_softmax(ptr(fg), ptr(groups.order), ptr(groups.seg_start), ptr(groups.ngroups), ptr(y),
-                                                G, stream()), "ramp_x3_segment_softmax")
-            hy = torch.zeros(G, 384, dtype=f32, device=dev)
-            check(lib().ramp_x3_linear(ptr(y), ptr(h_pack[0]), ptr(h_pack[1]), ptr(hy), G, ptr(groups.ngroups), stream()),
-                  "ramp_x3_linear")
-            return hy
-        # (the pair SoftAgg reads net + hkk[patch group] without writing the sum back; the gru launch forms
-        # (net + hkk[.]) + hij[.] itself: the same fp32 additions in the same order)
-        hkk = softagg(None, None, w["kk_fg_pack"], w["kk_h_pack"], plan.g_kk, plan.max_kk)
-        hij = softagg(hkk, plan.g_kk.gid, w["ij_fg_pack"], w["ij_h_pack"], plan.g_ij, plan.max_ij)
-        if self.before_gru is not None and self.hook_at == "gru":
-            self.before_gru()
-        _, _, wptr, bptr = w["gru_pack"]
-        ln1, ln2 = w["ln1"], w["ln2"]
-        out32 = b
-        target = weight = relu32 = None
-        hw = hb = coords = None
-        wd = ht = 0.0
-        P = 3
-        if heads_at is not None:
-            coords, wd, ht = heads_at
-            P = coords.shape[-1]
-            hw, hb = w["heads_pack"]
-            target = torch.empty(1, E, 2, dtype=f32, device=dev)
-            weight = torch.empty(1, E, 2, dtype=f32, device=dev)
-        else:
-            relu32 = torch.empty(E, 384, dtype=f32, device=dev)
-        check(lib().ramp_x3_gru(ptr(a), ptr(hkk), ptr(plan.g_kk.gid), ptr(hij), ptr(plan.g_ij.gid), ptr(ln1[0]), ptr(ln1[1]),
-                                float(ln1[2]), wptr, bptr, ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out32), ptr(relu32), E,
-                                ptr(hw), ptr(hb), ptr(coords), ptr(target), ptr(weight), int(P), float(wd), float(ht), stream()),
-              "ramp_x3_gru")
-        if heads_at is not None:
-            self.last_tw = (target, weight)
-            return out32, None
-        return out32, relu32
-
-    def _tail(self, w, E, net32, net_t, plan):
-        """SoftAgg x2 and the gru block, from the state after c1 / c2"""
+        fuse(E, A=net32, B=lin(lin_relu(self.gather_mask(net32, plan.ix_raw, E), w["c1a"]), w["c1b"]), out_f32=net32)
+        _, net_t = fuse(E, A=net32, B=lin(lin_relu(self.gather_mask(net32, plan.jx_raw, E), w["c2a"]), w["c2b"]),
+                        out_f32=net32, want_t=True)
         # SoftAgg over patches, then over (i, j) pairs (net.py:84-85)
-        if self.before_gru is not None and self.hook_at == "softagg":
-            self.before_gru()
-        if net_t is None and self.use_softagg and E > 0:
-            hy0 = self.softagg(net32, None, None, w["kk_fg_pack"], w["kk_h_pack"], plan.g_kk, plan.max_kk, E)
-            # (the device-resident step adds hy0[.] inside the next two launches instead of writing the sum back: the
-            # same fp32 additions in the same order)
-            self.row_fuse(E, A=net32, B=hy0, idxB32=plan.g_kk.gid, out_f32=net32)
-            hy = self.softagg(net32, None, None, w["ij_fg_pack"], w["ij_h_pack"], plan.g_ij, plan.max_ij, E)
-        elif net_t is None:
-            # fused path: the [f | g] GEMM forms its own fp16 input tile from the fp32 state (and applies the
-            # previous SoftAgg's expand-and-add on the way): no fp16 state copy, no separate row pass
-            hy = self.h_lin(self.seg(self.fg(net32, None, None, w["kk_fg_pack"], E), plan.g_kk, plan.max_kk),
-                            w["kk_h_pack"], plan.g_kk)
-            hy = self.h_lin(self.seg(self.fg(net32, hy, plan.g_kk.gid, w["ij_fg_pack"], E), plan.g_ij, plan.max_ij),
-                            w["ij_h_pack"], plan.g_ij)
-        else:
-            hy = self.lin(self.seg(self.lin(net_t, w["kk_fg"]), plan.g_kk, plan.max_kk), w["kk_h"])
-            _, net_t = self.row_fuse(E, A=net32, B=hy, idxB32=plan.g_kk.gid, out_f32=net32, want_t=True)
-            hy = self.lin(self.seg(self.lin(net_t, w["ij_fg"]), plan.g_ij, plan.max_ij), w["ij_h"])
+        hy = lin(self.seg(lin(net_t, w["kk_fg"]), plan.g_kk, plan.max_kk), w["kk_h"])
+        _, net_t = fuse(E, A=net32, B=hy, idxB32=plan.g_kk.gid, out_f32=net32, want_t=True)
+        hy = lin(self.seg(lin(net_t, w["ij_fg"]), plan.g_ij, plan.max_ij), w["ij_h"])
         # gru = LN, GatedResidual, LN, GatedResidual (net.py:49-54)
-        if "gru_pack" in w and self.use_mlp:
-            # the chain kernel forms LN(net + hy[gid]) itself while it stages its tile: no separate row pass
-            _, _, wptr, bptr = w["gru_pack"]
-            out32 = torch.empty(E, 384, dtype=torch.float32, device=net32.device)
-            relu_t = torch.empty(E, 384, dtype=self.dtype, device=net32.device)
-            ln1 = w["ln1"]
-            if self.before_gru is not None and self.hook_at == "gru":
-                self.before_gru()
-            heads_at = getattr(self, "_heads_at", None)
-            if heads_at is not None and "heads_pack" in w and self.dtype == torch.float16:
-                coords, wd, ht = heads_at
-                hwt, hb = w["heads_pack"]
-                target = torch.empty(1, E, 2, dtype=torch.float32, device=net32.device)
-                weight = torch.empty(1, E, 2, dtype=torch.float32, device=net32.device)
-                check(lib().ramp_upd_gru_heads(ptr(net32), ptr(hy), ptr(plan.g_ij.gid), ptr(ln1[0]), ptr(ln1[1]),
-                                               float(ln1[2]), wptr, bptr, ptr(w["ln2"][0]), ptr(w["ln2"][1]),
-                                               float(w["ln2"][2]), ptr(out32), ptr(hwt), ptr(hb), ptr(coords), ptr(target),
-                                               ptr(weight), E, coords.shape[-1], float(wd), float(ht), stream()),
-                      "ramp_upd_gru_heads")
-                self.last_tw = (target, weight)
-                return out32, None
-            check(lib().ramp_upd_gru(ptr(net32), ptr(hy), ptr(plan.g_ij.gid), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2]),
-                                     wptr, bptr, ptr(w["ln2"][0]), ptr(w["ln2"][1]), float(w["ln2"][2]),
-                                     ptr(out32), ptr(relu_t), E, stream()), "ramp_upd_gru")
-            return out32, relu_t
-        x32, x_t = self.row_fuse(E, A=net32, B=hy, idxB32=plan.g_ij.gid, ln=w["ln1"], out_f32=net32, want_t=True)
-        gate = self.lin(x_t, w["g1_gate"])
-        r = self.lin(self.lin_relu(x_t, w["g1_r1"]), w["g1_r2"])
-        x32, x_t, _ = self.gated(x32, gate, r, E, ln=w["ln2"], want_t=True)
-        gate = self.lin(x_t, w["g2_gate"])
-        r = self.lin(self.lin_relu(x_t, w["g2_r1"]), w["g2_r2"])
-        ob = getattr(self, "_bufs", (None, None))[1]
-        out32, _, relu_t = self.gated(x32, gate, r, E, want_relu=True, out=ob[:E] if ob is not None else None)
+        x32, x_t = fuse(E, A=net32, B=hy, idxB32=plan.g_ij.gid, ln=w["ln1"], out_f32=net32, want_t=True)
+        x32, x_t, _ = self.gated(x32, lin(x_t, w["g1_gate"]), lin(lin_relu(x_t, w["g1_r1"]), w["g1_r2"]), E, ln=w["ln2"],
+                                 want_t=True)
+        out32, _, relu_t = self.gated(x32, lin(x_t, w["g2_gate"]), lin(lin_relu(x_t, w["g2_r1"]), w["g2_r2"]), E,
+                                      want_relu=True, out=out32_buf[:E] if out32_buf is not None else None)
         return out32, relu_t
 
+    # ------------------------------------------------------------------ heads
     def heads(self, relu_t):
         return self.lin(relu_t, self.weights()["heads"])          # [E,4]
-
-    def heads_target_weight(self, relu_t, coords, wd, ht):
-        """heads(relu_t) followed by target_weight, one launch (fp16 path); None when not available"""
-        w = self.weights()
-        if "heads_pack" not in w or not self.use_mlp or relu_t.dtype != torch.float16:
-            return None
-        E, P, dev = relu_t.shape[0], coords.shape[-1], relu_t.device
-        target = torch.empty(1, E, 2, dtype=torch.float32, device=dev)
-        weight = torch.empty(1, E, 2, dtype=torch.float32, device=dev)
-        hwt, hb = w["heads_pack"]
-        check(lib().ramp_upd_heads_linear(ptr(relu_t), ptr(hwt), ptr(hb), ptr(coords), ptr(target), ptr(weight), E, P,
-                                          float(wd), float(ht), stream()), "ramp_upd_heads_linear")
-        return target, weight
 
     def target_weight(self, hw, coords, wd, ht, want_delta=False):
         E = hw.shape[0]

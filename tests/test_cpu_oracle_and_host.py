@@ -31,17 +31,13 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert b"gfx950" in lib.ramp_version()
 
 
-def test_track_descriptor_mirror_matches_the_c_layout(tmp_path):
-    """track_dev.Track / TrackWeights and conv_hip.ConvJob mirror include/ramp_hip.h's ramp_track / ramp_track_weights /
-    ramp_conv_job by hand: the system C compiler's sizeof and offsetof of every field the ctypes mirror names equal the
-    ctypes ones, field by field in the mirror's order"""
+def _layout_mismatches(structs, tmp_path):
+    """[(field, C's "offset size", ctypes')] where the system C compiler's sizeof / offsetof of a field the ctypes mirror
+    names differs from the mirror's, field by field in the mirror's order; structs: (C name, ctypes.Structure) pairs"""
     import shutil
     import subprocess
-    from rampvo_amd import conv_hip, track_dev
     cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
     assert cc, "no C compiler on PATH"
-    structs = (("ramp_track", track_dev.Track), ("ramp_track_weights", track_dev.TrackWeights),
-               ("ramp_conv_job", conv_hip.ConvJob))
     lines = ['#include "ramp_hip.h"', "#include <stdio.h>", "int main(void) {"]
     want = []
     for cname, py in structs:
@@ -56,9 +52,34 @@ def test_track_descriptor_mirror_matches_the_c_layout(tmp_path):
     subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
     got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
     names = [c for c, py in structs for c in [c] + ["%s.%s" % (c, n) for n, _ in py._fields_]]
-    for name, g, w in zip(names, got, want):
-        assert g == str(w), "%s: C %s, ctypes %s" % (name, g, w)
     assert len(got) - 1 == len(want)
+    return [(name, g, str(w)) for name, g, w in zip(names, got, want) if g != str(w)]
+
+
+def test_track_descriptor_mirror_matches_the_c_layout(tmp_path):
+    """track_dev.Track, _lib.TrackWeights / UpdateArgs and conv_hip.ConvJob mirror include/ramp_hip.h's ramp_track /
+    ramp_track_weights / ramp_update_args / ramp_conv_job by hand: the system C compiler's sizeof and offsetof of every field
+    the ctypes mirror names equal the ctypes ones, field by field in the mirror's order"""
+    from rampvo_amd import _lib, conv_hip, track_dev
+    assert track_dev.TrackWeights is _lib.TrackWeights
+    assert "relu_t" not in [n for n, _ in track_dev.Track._fields_]
+    structs = (("ramp_track", track_dev.Track), ("ramp_track_weights", _lib.TrackWeights),
+               ("ramp_update_args", _lib.UpdateArgs), ("ramp_conv_job", conv_hip.ConvJob))
+    for name, g, w in _layout_mismatches(structs, tmp_path):
+        assert g == w, "%s: C %s, ctypes %s" % (name, g, w)
+
+
+def test_update_args_layout_check_sees_a_swapped_field_pair(tmp_path):
+    """the layout check above is not vacuous for ramp_update_args: a mirror with two neighbouring fields swapped (the
+    last pointer, hij, and the first int, kk_cap) is reported for both"""
+    from rampvo_amd import _lib
+    fields = list(_lib.UpdateArgs._fields_)
+    i, j = [n for n, _ in fields].index("hij"), [n for n, _ in fields].index("kk_cap")
+    assert j == i + 1
+    fields[i], fields[j] = fields[j], fields[i]
+    swapped = type("SwappedUpdateArgs", (ctypes.Structure,), {"_fields_": fields})
+    bad = _layout_mismatches((("ramp_update_args", swapped),), tmp_path)
+    assert {"ramp_update_args.hij", "ramp_update_args.kk_cap"} <= {name for name, _, _ in bad}
 
 
 def test_switch_reader_defaults_and_fallbacks():

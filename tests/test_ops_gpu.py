@@ -782,20 +782,25 @@ def test_fused_gru_chain_matches_gemm_path():
     scale = float(outs[False][0].abs().max())
     assert float((outs[False][0] - outs[True][0]).abs().max()) <= 4e-3 * scale
     assert float((outs[False][1] - outs[True][1]).abs().max()) <= 4e-3 * scale
-    # padded correlation rows (the tracker's layout): the whole correlation MLP in one launch vs library GEMM + tail
+    # padded correlation rows (the tracker's layout): the default path against the library path on the same padded rows
     corr_pad = torch.nn.functional.pad(corr, (0, 896 - 882)).contiguous()
     res = {}
     with torch.no_grad():
-        for one in (False, True):
-            fu.use_corr_mlp = one
+        for mlp in (False, True):
+            fu.use_mlp = mlp
             o32, rt = fu.hidden(netst[:700].contiguous(), table, inp_idx, 300, corr_pad, plan, net_map=net_map)
-            res[one] = (o32.clone(), rt.float().clone())
-    fu.use_corr_mlp = True
+            res[mlp] = (o32.clone(), rt.float().clone())
+    fu.use_mlp = True
     # heads: row-wise dot-product kernel (+ target / weight epilogue) vs the [E,384]x[384,4] GEMM + upd_heads
+    from rampvo_amd._lib import check, lib, ptr, stream
     coords = (torch.rand(E, 2, 3, 3, generator=g) * 60).cuda()
+    relu_t = res[True][1].half()
     with torch.no_grad():
-        t_ref, w_ref, _ = fu.target_weight(fu.heads(res[True][1].half()), coords, 40.0, 30.0)
-        t_new, w_new = fu.heads_target_weight(res[True][1].half(), coords, 40.0, 30.0)
+        t_ref, w_ref, _ = fu.target_weight(fu.heads(relu_t), coords, 40.0, 30.0)
+        t_new, w_new = torch.empty(1, E, 2, device="cuda"), torch.empty(1, E, 2, device="cuda")
+        hwt, hb = fu.weights()["heads_pack"]
+        check(lib().ramp_upd_heads_linear(ptr(relu_t), ptr(hwt), ptr(hb), ptr(coords), ptr(t_new), ptr(w_new), E, 3, 40.0,
+                                          30.0, stream()), "ramp_upd_heads_linear")
     assert float((t_ref - t_new).abs().max()) <= 2e-3 * max(1.0, float(t_ref.abs().max()))
     near_edge = ((t_ref - torch.tensor([40.0, 30.0], device="cuda")).abs().min(-1).values < 0.1) | (t_ref.abs().min(-1).values < 0.1)
     assert float(((w_ref - w_new).abs().max(-1).values * (~near_edge)).max()) <= 2e-3
