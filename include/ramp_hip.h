@@ -1492,6 +1492,98 @@ int ramp_event_filter(const void *x, const void *y, const double *t, long N, int
                       double *last_t_out, uint8_t *keep_out, float *xy_out, int32_t *index_out, int64_t *count_out,
                       uint8_t *hot_out, double *stats_out, int32_t *status, void *ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------- IMU: preintegration and alignment (csrc/imu.hip)
+ *
+ * A monocular trajectory has an arbitrary unit and no notion of down.  These entries take raw IMU samples and the trajectory as
+ * it is (a ramp_trajectory_resolve / ramp_se3_interp row per knot) and return the gyro bias, the metric scale, gravity in the
+ * tracker's world frame and a velocity per knot.  The tracker's step, its bundle adjustment and every other kernel are untouched.
+ *   Inputs.  tau [N] float64 sample times; gyro, accel [N][3] float, or float64 with RAMP_IMU_F64 (rad/s, m/s^2: the
+ *   accelerometer measures R^T (a - g)).  knots [T][7] fp32 camera-to-world (tx ty tz qx qy qz qw); the quaternion is taken to
+ *   float64 and normalised there.  times [T] float64, in the unit of tau.  stride >= 1: the knots used are 0, stride,
+ *   2 stride, ..., K = (T - 1) / stride + 1 of them.  extrinsics: HOST float64 [12], R_bc [3][3] row-major then p_bc [3], the
+ *   camera in the IMU (body) frame; NULL: identity.  R_bc has to be a rotation -- every word of R R^T - I within
+ *   RAMP_IMU_ROTATION_TOL and det R > 0, else RAMP_EINVAL, never a plausible answer from a matrix that is none -- and is
+ *   converted to a unit quaternion on the host.  bias_g, bias_a: HOST float64 [3] or NULL for zero.  max_gap: seconds, > 0, infinity allowed.  gravity_norm: 0 = free, else the known norm G.
+ *   One interval [T_k, T_k+1] of consecutive used knots.  Its breakpoints u_0 .. u_m are T_k, the samples with
+ *   T_k < tau_i < T_k+1, then T_k+1: a sample equal to an end is not repeated, duplicated tau give sub-intervals of length 0,
+ *   which are identities.  The measurement is piecewise linear between samples (at a sample's own time: that sample).  On a
+ *   sub-interval of length dt, w = 1/2 (gyro(u_j) + gyro(u_j+1)) - bias_g, a likewise with bias_a, and its element is
+ *     e = (E, dv, dp, dt, J) = (Exp(w dt), a dt, (a dt)(dt / 2), dt, -Jr(w dt) dt)
+ *   with Exp as a unit quaternion and Jr = I - b [phi]x + c [phi]x^2, b = (1 - cos th) / th^2 = 2 sin^2(th / 2) / th^2,
+ *   c = (th - sin th) / th^3; below th^2 = 1e-4 all four coefficients are their Taylor series to th^8 (no cancellation, no
+ *   sin / cos call).  Elements compose in order with the associative law
+ *     (R1,v1,p1,t1,J1) o (R2,v2,p2,t2,J2) = (R1 R2,  v1 + R1 v2,  (p1 + v1 t2) + R1 p2,  t1 + t2,  R2^T J1 + J2)
+ *   and the product over the interval is (dR, dv, dp, dt, J_Rg): Forster's on-manifold preintegral with d dR / d bias_g.  All
+ *   of it is float64 without FMA contraction.  The quaternion product is not renormalised on the way; the record's is
+ *   normalised once and given qw >= 0.
+ *   preint [K - 1][RAMP_IMU_PREINT_WORDS] float64: [0] dt (the composed sum), [1] the sub-interval count m, [2..5] dR as
+ *   qx qy qz qw, [6..8] dv, [9..11] dp, [12..20] J_Rg row-major, [21..23] 0.
+ *   Covered.  An interval is covered when tau_0 <= T_k and T_k+1 <= tau_N-1, every sample it touches (from the last one at or
+ *   before T_k to the first one at or after T_k+1) is finite, no two consecutive touched samples are further apart than
+ *   max_gap, and T_k+1 > T_k.  Anything else is counted and its record is NaN in all 24 words.
+ *   Kernel.  One wave per interval: two binary searches in tau, then the sub-intervals in chunks of 64, one per lane; a chunk is
+ *   reduced by an ORDERED shuffle tree (offsets 1, 2, 4, ...: lane i takes own o lane(i + off); lanes beyond the tail hold the
+ *   identity, which is neutral to the bit on either side) and chunks chain left to right in lane 0.  A record's bits are a
+ *   function of its own interval's samples and the biases alone -- not of K, stride or its position -- and a call repeats its
+ *   bits.  An interval with 10^6 samples costs one wave's walk: accepted, a VO interval holds tens of samples.
+ *   status: device int32 [8]: [0] bits, [1] samples, [2] intervals, [3] intervals not covered (range, gap, not finite),
+ *   [4] intervals with T_k+1 <= T_k, [5] intervals in the (first) gyro step, [6] triples used, [7] 0.  [3] + [4] + covered = [2].
+ *   RAMP_IMU_BAD_ORDER: tau or times (all T) decrease or are not finite; no interval is walked, all count in [3], every output
+ *   is NaN.  A gyro bias that is not finite -- what a failed gyro step leaves -- is treated alike: the integration behind it
+ *   walks nothing, every interval counts in [3] and every record is NaN, so [6] is 0 and the scale stage ends in
+ *   RAMP_IMU_FEW_TRIPLES.
+ * ramp_imu_preintegrate: one 32-byte hipMemsetAsync of status, the check kernel, the integration.  [5], [6] stay 0.
+ * ramp_imu_align: with R_wb = R_wc R_bc^T, c_k = R_wc,k (-R_bc^T p_bc), pbar the knots' translations, p_wb = s pbar + c:
+ *   Gyro bias, gyro_steps (1 .. RAMP_IMU_MAX_GYRO_STEPS) Gauss-Newton steps, re-integrating in front of each: over the covered
+ *     intervals r_k = Log(dR_k^T R_wb,k^T R_wb,k+1), H = sum J^T J, b = sum J^T r, delta = H^-1 b (3 x 3 Cholesky),
+ *     bias_g += delta.  Fewer than one covered interval, a pivot that is not positive and finite or a result that is not
+ *     finite: RAMP_IMU_GYRO_FAILED, the bias NaN (and with it everything behind).
+ *   Scale and gravity: the integration is run AGAIN with the corrected bias -- the records carry no Jacobians of dv and dp with
+ *     respect to the biases, a deliberate simplification: the integration is cheap here.  Every pair of consecutive covered
+ *     intervals 1 = (k, k+1), 2 = (k+1, k+2) gives three rows in x = (s, g), the velocities eliminated:
+ *       s [(p3 - p2) / dt2 - (p2 - p1) / dt1] - 1/2 (dt1 + dt2) g
+ *           = (((R2 dp2 / dt2 - R1 dp1 / dt1) + R1 dv1) - (c3 - c2) / dt2) + (c2 - c1) / dt1          (p = pbar, R = R_wb)
+ *     N = sum A^T A [4][4], y = sum A^T rhs [4]: per-workgroup partials of 256 triples (wave butterflies, the four waves in
+ *     order), then one wave over the partials in index order: an order fixed by K alone.  One lane solves by Cholesky.
+ *     RAMP_IMU_SCALE_FAILED with RAMP_IMU_FEW_TRIPLES (fewer than two triples), RAMP_IMU_SINGULAR (a pivot that is not positive
+ *     and finite, sums or a solution that are not finite) or RAMP_IMU_BAD_SCALE (s <= 0); bias_g1 stays valid.
+ *   Known norm G > 0: exactly four tangent refinements from N and y alone, no second pass over the data: with gh = g / |g|,
+ *     b1 = normalise(gh x e), e the axis of the smallest |gh| component (the first on ties), b2 = gh x b1, x0 = (0, G gh),
+ *     P = [e_s, (0, b1), (0, b2)]:  (P^T N P) z = P^T (y - N x0),  g = G gh + z1 b1 + z2 b2,  gh = g / |g|,  x = (z0, G gh).
+ *   Velocities [K][3]: v_k = (((p_k+1 - p_k) - 1/2 g dt^2) - R_k dp) / dt with p = s pbar + c; the last knot takes
+ *     v + g dt + R dv of the last interval; NaN beside an interval that is not covered.
+ *   residual [K - 2]: |A x - rhs| per triple (NaN for a triple not used);  rms = sqrt(sum residual^2 / triples).
+ *   The accelerometer bias is an input and is not estimated.
+ *   Outputs, all on the device:  result float64 [16]: [0] s, [1..3] g, [4..6] bias_g1, [7] rms, [8] the largest over the
+ *   smallest pivot d_j = L_jj^2 of the 4 x 4 factorisation (a cheap estimate of the condition number), [9..15] 0;
+ *   normal float64 [32]: N [16], y [4], the last gyro step's H [9], b [3];  velocity, residual;  preint (optional, NULL): the
+ *   records of the final integration;  status.  With RAMP_IMU_SCALE_FAILED s, g, rms, [8], velocity and residual are NaN.
+ *   Launches, all on `stream`, nothing read back, nothing synchronised, no floating-point atomics: one hipMemsetAsync, the check,
+ *   (integrate, gyro partials, gyro final) x gyro_steps, integrate, scale partials (K > 2), scale final, and one workgroup for
+ *   velocities, residuals, rms and the status words.  ws: ramp_imu_workspace_bytes(N, K) bytes, 16-byte aligned.
+ *   Outcomes of the data return RAMP_OK.  NULL inputs or outputs (residual may be NULL with K == 2), N < 1 or >= 2^31, T < 2,
+ *   stride < 1 or K < 2, unknown flags, max_gap not > 0, gravity_norm negative or not finite, a bias or extrinsic that is not
+ *   finite, an R_bc that is no rotation, gyro_steps outside its range, float64 arrays not 8-byte (fp32 samples: 4-byte) aligned, ws not 16-byte aligned:
+ *   RAMP_EINVAL; a short workspace: RAMP_EWORKSPACE.                                                                   */
+#define RAMP_IMU_F64 1
+#define RAMP_IMU_PREINT_WORDS 24
+#define RAMP_IMU_MAX_GYRO_STEPS 16
+#define RAMP_IMU_ROTATION_TOL 1e-6
+#define RAMP_IMU_BAD_ORDER 1    /* status[0] bit 0 */
+#define RAMP_IMU_GYRO_FAILED 2  /* bit 1 */
+#define RAMP_IMU_SCALE_FAILED 4 /* bit 2, with one of the three below */
+#define RAMP_IMU_FEW_TRIPLES 8
+#define RAMP_IMU_SINGULAR 16
+#define RAMP_IMU_BAD_SCALE 32
+size_t ramp_imu_workspace_bytes(long N, int K);
+int ramp_imu_preintegrate(const double *tau, const void *gyro, const void *accel, long N, const double *times, int T, int stride,
+                          const double *bias_g, const double *bias_a, double max_gap, int flags, double *preint,
+                          int32_t *status, void *stream);
+int ramp_imu_align(const double *tau, const void *gyro, const void *accel, long N, const float *knots, const double *times, int T,
+                   int stride, const double *extrinsics, const double *bias_g, const double *bias_a, double max_gap,
+                   double gravity_norm, int gyro_steps, int flags, double *result, double *normal, double *velocity,
+                   double *residual, double *preint, int32_t *status, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

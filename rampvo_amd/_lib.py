@@ -35,6 +35,9 @@ RAMP_RECTIFY_ITERS, RAMP_RECTIFY_TOL = 8, 2.0 ** -6
 RAMP_RECTIFY_XY_I32, RAMP_RECTIFY_SRC_U8, RAMP_RECTIFY_BAD_CAMERA = 1, 2, 1
 RAMP_RECTIFY_NORM_NONE, RAMP_RECTIFY_NORM_HALF, RAMP_RECTIFY_NORM_UNIT = 0, 1, 2
 RAMP_FILTER_XY_I32, RAMP_FILTER_BAD_ORDER = 1, 1
+RAMP_IMU_F64, RAMP_IMU_PREINT_WORDS, RAMP_IMU_MAX_GYRO_STEPS = 1, 24, 16
+RAMP_IMU_BAD_ORDER, RAMP_IMU_GYRO_FAILED, RAMP_IMU_SCALE_FAILED = 1, 2, 4
+RAMP_IMU_FEW_TRIPLES, RAMP_IMU_SINGULAR, RAMP_IMU_BAD_SCALE = 8, 16, 32
 KPLANE = 32            # channels per plane of the packed correlation target maps: [h][128 / KPLANE][w][KPLANE]
 
 
@@ -248,6 +251,11 @@ SIGNATURES = {
     "ramp_event_filter_grid_events": (ctypes.c_long, []),
     "ramp_event_filter": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i,
                                 ctypes.c_double] + [c_p] * 11 + [c_sz, c_p]),
+    # IMU preintegration and alignment (csrc/imu.hip)
+    "ramp_imu_workspace_bytes": (c_sz, [ctypes.c_long, c_i]),
+    "ramp_imu_preintegrate": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_p, c_i, c_i, c_p, c_p, ctypes.c_double, c_i, c_p, c_p, c_p]),
+    "ramp_imu_align": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_p, c_p, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, ctypes.c_double,
+                             c_i, c_i] + [c_p] * 7 + [c_sz, c_p]),
 }
 
 _lib = None

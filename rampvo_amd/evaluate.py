@@ -188,6 +188,39 @@ def resample_trajectory(poses, tstamps, rate_hz, device="cuda"):
     return out.cpu().numpy(), times
 
 
+def metric_trajectory(poses, align, down=(0.0, 0.0, -1.0)):
+    """A trajectory in metres with gravity along ``down``: poses [T,7] camera-to-world (tx ty tz qx qy qz qw; what
+    trajectory() returns) and ``align``, the dict of ``align_imu`` (or anything with ``scale`` and ``gravity``) ->
+    poses [T,7] float64 whose translations are scaled by s and whose world frame is turned by the smallest rotation R that
+    takes g / |g| to ``down``: t' = R (s t), q' = q_R q.  Host numpy, a convenience.  Raises when the scale or gravity is not
+    finite (a failed alignment is NaN)."""
+    to_np = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64).reshape(-1)
+    s, g, d = float(to_np(align["scale"])[0]), to_np(align["gravity"]), to_np(down)
+    if not (np.isfinite(s) and s > 0 and np.isfinite(g).all() and np.linalg.norm(g) > 0 and np.linalg.norm(d) > 0):
+        raise RuntimeError("metric_trajectory: the alignment holds no finite positive scale and gravity")
+    g, d = g / np.linalg.norm(g), d / np.linalg.norm(d)
+    axis, c = np.cross(g, d), float(g @ d)
+    n = np.linalg.norm(axis)
+    half = 0.5 * np.arctan2(n, c)
+    if n < 1e-12:                                              # parallel: nothing to turn; opposite: half a turn about any normal
+        axis = np.cross(g, np.eye(3)[int(np.argmin(np.abs(g)))])
+        n, half = np.linalg.norm(axis), (0.0 if c > 0 else 0.5 * np.pi)
+    qr = np.concatenate([np.sin(half) * axis / n, [np.cos(half)]])
+    x, y, z, w = qr
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 7)
+    out = np.empty_like(poses)
+    out[:, :3] = (s * poses[:, :3]) @ R.T
+    qx, qy, qz, qw = poses[:, 3], poses[:, 4], poses[:, 5], poses[:, 6]
+    out[:, 3] = w * qx + x * qw + y * qz - z * qy
+    out[:, 4] = w * qy + y * qw + z * qx - x * qz
+    out[:, 5] = w * qz + z * qw + x * qy - y * qx
+    out[:, 6] = w * qw - x * qx - y * qy - z * qz
+    return out
+
+
 def save_fixed_rate_trajectory(path, poses, tstamps, rate_hz, device="cuda"):
     """the trajectory resampled at ``rate_hz`` (resample_trajectory) as a text file in the row format of save_results:
     time[s] x y z qw qx qy qz"""

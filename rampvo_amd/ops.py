@@ -29,6 +29,10 @@ _STATUS = {
     "invdepth_map": ({"bad_cam": _lib.RAMP_DEPTHMAP_BAD_CAM},
                      ("n_considered", "n_bad_depth", "n_rejected", "n_out_of_reach", "n_contributing", "n_empty_pixels")),
     "se3_interp": ({"bad_times": _lib.RAMP_INTERP_BAD_TIMES}, ("n_below", "n_above", "n_nan")),
+    "imu": ({"bad_order": _lib.RAMP_IMU_BAD_ORDER, "gyro_failed": _lib.RAMP_IMU_GYRO_FAILED,
+             "scale_failed": _lib.RAMP_IMU_SCALE_FAILED, "few_triples": _lib.RAMP_IMU_FEW_TRIPLES,
+             "singular": _lib.RAMP_IMU_SINGULAR, "bad_scale": _lib.RAMP_IMU_BAD_SCALE},
+            ("n_samples", "n_intervals", "n_uncovered", "n_dt_not_positive", "n_gyro_intervals", "n_triples")),
 }
 
 
@@ -573,6 +577,119 @@ def event_filter(x, y, t, height, width, support_dt=None, refractory=0.0, hot_co
 def event_filter_status(status):
     """The status words of ``event_filter`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
     return _status("event_filter", status)
+
+
+# ------------------------------------------------------------------- IMU
+def _host_value(name, v):
+    """``v`` as nested lists; a device tensor is refused: reading it back would synchronise, which these wrappers never do"""
+    if isinstance(v, torch.Tensor):
+        if v.is_cuda:
+            raise RuntimeError(name + " is a host value (a list, an array, a CPU tensor): a device tensor would have to be "
+                               "read back, and this call synchronises nothing")
+        return v.detach().tolist()
+    return v
+
+
+def _host3(name, v, n=3):
+    """a host float64 array of n words for a C entry that reads it before it returns (None: NULL)"""
+    if v is None:
+        return None, None
+    v = _host_value(name, v)
+    flat = [float(c) for row in v for c in (row if hasattr(row, "__len__") else [row])]
+    if len(flat) != n:
+        raise RuntimeError("%s holds %d numbers" % (name, n))
+    arr = (ctypes.c_double * n)(*flat)
+    return arr, ctypes.cast(arr, ctypes.c_void_p)
+
+
+def _imu_samples(name, tau, gyro, accel, times):
+    require_cuda(tau, gyro, accel, times)
+    tf, tt = tau.reshape(-1).to(torch.float64).contiguous(), times.reshape(-1).to(torch.float64).contiguous()
+    f64 = gyro.dtype == torch.float64 or accel.dtype == torch.float64
+    dt = torch.float64 if f64 else torch.float32
+    g, a = gyro.to(dt).reshape(-1, 3).contiguous(), accel.to(dt).reshape(-1, 3).contiguous()
+    N = tf.shape[0]
+    if N < 1 or g.shape[0] != N or a.shape[0] != N:
+        raise RuntimeError(name + ": tau [N], gyro [N,3] and accel [N,3] hold the same N >= 1 samples")
+    return tf, g, a, tt, N, (_lib.RAMP_IMU_F64 if f64 else 0)
+
+
+def imu_preintegrate(tau, gyro, accel, times, bias_g=None, bias_a=None, stride=1, max_gap=float("inf")):
+    """Forster's on-manifold IMU preintegrals between consecutive time stamps ``times[0], times[stride], ...`` (include/
+    ramp_hip.h ``ramp_imu_preintegrate``; one wave per interval, float64): ``tau`` [N] float64 sample times, ``gyro``, ``accel``
+    [N,3] float32 or float64 device tensors, the biases HOST triples (lists, arrays, CPU tensors; a device tensor is refused, it
+    would have to be read back).  Returns ``(preint, status)``: ``preint`` float64
+    [K - 1, 24] -- dt, the sub-interval count, dR as qx qy qz qw, dv, dp, d dR / d bias_g row-major, three zeros; NaN for an
+    interval the samples do not cover -- and ``status`` int32 [8] (``imu_status``).  Runs on the current stream, nothing is
+    synchronised.  A record's bits depend on its own interval's samples and the biases alone."""
+    tf, g, a, tt, N, flags = _imu_samples("imu_preintegrate", tau, gyro, accel, times)
+    T = tt.shape[0]
+    K = (T - 1) // max(int(stride), 1) + 1
+    if T < 2 or stride < 1 or K < 2:
+        raise RuntimeError("imu_preintegrate: at least two of the time stamps are used (stride >= 1)")
+    (_, bg), (_, ba) = keep = _host3("imu_preintegrate: bias_g", bias_g), _host3("imu_preintegrate: bias_a", bias_a)
+    preint = torch.empty((K - 1, _lib.RAMP_IMU_PREINT_WORDS), dtype=torch.float64, device=tf.device)
+    status = torch.empty(8, dtype=torch.int32, device=tf.device)
+    check(lib().ramp_imu_preintegrate(ptr(tf), ptr(g), ptr(a), N, ptr(tt), T, int(stride), bg, ba, float(max_gap), flags,
+                                      ptr(preint), ptr(status), stream()), "ramp_imu_preintegrate")
+    del keep
+    return preint, status
+
+
+def imu_align(tau, gyro, accel, knots, times, R_bc=None, p_bc=None, bias_g=None, bias_a=None, stride=1, max_gap=float("inf"),
+              gravity_norm=None, gyro_steps=1, want_preint=False):
+    """Metric scale, gravity and gyro bias of a monocular trajectory from raw IMU samples, on the device (include/ramp_hip.h
+    ``ramp_imu_align``): ONE C call enqueues the preintegration between the knots used (``0, stride, ...``), ``gyro_steps``
+    Gauss-Newton steps of the gyro bias, the integration again with the corrected bias, the linear solve for ``(s, g)`` over
+    all triples of knots, and the velocities.  Nothing is read back, nothing synchronised.
+
+    ``knots`` [T,7] camera-to-world rows (``trajectory(as_tensor=True)``), ``times`` [T] float64.  ``R_bc`` [3,3], ``p_bc`` [3]:
+    the camera in the IMU frame (None: identity, zero); ``R_bc`` has to be a rotation.  ``bias_g``, ``bias_a``: the start gyro
+    bias and the accelerometer bias (not estimated).  These four are HOST values (lists, arrays, CPU tensors); a device tensor
+    is refused, since reading it back would synchronise.  ``gravity_norm``: None or 0 leaves the norm free; a value fixes ``|g|``.
+
+    Returns a dict of device tensors: ``result`` float64 [16] with the views ``scale`` [1], ``gravity`` [3], ``bias_g`` [3],
+    ``rms`` [1], ``cond`` [1]; ``normal`` float64 [32] (N, y, H, b); ``velocity`` [K,3]; ``residual`` [K-2]; ``status`` int32
+    [8] (``imu_status``); with ``want_preint`` the records of the final integration.  A stage that fails sets its status bit
+    and leaves NaN, never a plausible number."""
+    tf, g, a, tt, N, flags = _imu_samples("imu_align", tau, gyro, accel, times)
+    require_cuda(knots)
+    kn = knots.reshape(-1, 7).to(torch.float32).contiguous()
+    T = tt.shape[0]
+    K = (T - 1) // max(int(stride), 1) + 1
+    if kn.shape[0] != T:
+        raise RuntimeError("imu_align: knots [T,7] and times [T] differ in length")
+    if T < 2 or stride < 1 or K < 2:
+        raise RuntimeError("imu_align: at least two of the knots are used (stride >= 1)")
+    ext = None
+    if R_bc is not None or p_bc is not None:
+        R = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]] if R_bc is None else R_bc
+        R = [list(r) for r in _host_value("imu_align: R_bc", R)]
+        p = [0.0, 0.0, 0.0] if p_bc is None else list(_host_value("imu_align: p_bc", p_bc))
+        ext = list(R) + [p]
+    (_, ex), (_, bg), (_, ba) = keep = (_host3("imu_align: R_bc and p_bc", ext, 12), _host3("imu_align: bias_g", bias_g),
+                                        _host3("imu_align: bias_a", bias_a))
+    dev = tf.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    res = {"result": torch.empty(16, **f64), "normal": torch.empty(32, **f64), "velocity": torch.empty((K, 3), **f64),
+           "residual": torch.empty(max(K - 2, 0), **f64), "status": torch.empty(8, dtype=torch.int32, device=dev)}
+    if want_preint:
+        res["preint"] = torch.empty((K - 1, _lib.RAMP_IMU_PREINT_WORDS), **f64)
+    nbytes = lib().ramp_imu_workspace_bytes(N, K)
+    ws = _lib_workspace(nbytes, dev, "imu")
+    check(lib().ramp_imu_align(ptr(tf), ptr(g), ptr(a), N, ptr(kn), ptr(tt), T, int(stride), ex, bg, ba, float(max_gap),
+                               float(gravity_norm or 0.0), int(gyro_steps), flags, ptr(res["result"]), ptr(res["normal"]),
+                               ptr(res["velocity"]), ptr(res["residual"]) if K > 2 else None, ptr(res.get("preint")),
+                               ptr(res["status"]), ptr(ws), nbytes, stream()), "ramp_imu_align")
+    del keep
+    r = res["result"]
+    res.update(scale=r[0:1], gravity=r[1:4], bias_g=r[4:7], rms=r[7:8], cond=r[8:9])
+    return res
+
+
+def imu_status(status):
+    """The status words of ``imu_preintegrate`` / ``imu_align`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("imu", status)
 
 
 def align_loop(evaluate, correction, free, step, iters):

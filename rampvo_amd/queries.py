@@ -54,16 +54,18 @@ class StateStream:
                 self.leaves(*(x.values() if isinstance(x, dict) else x))
 
 
-def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None, filter=None):
+def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None, filter=None, imu=None):
     """The closing check of a query's numpy form -- its one wait.  Each argument is a device status tensor or None (not part
     of this query): ``traj`` trajectory()'s word, ``interp`` the words of ops.se3_interp or ops.event_warp (bit 0 of word 0:
     the frames' time stamps), ``cam`` those of ops.invdepth_map (bit 0 of word 0: the camera pose), ``voxel`` those of
     ops.event_voxel_grid (bits 0 and 1 of word 0: the offsets, a slice's own time stamps), ``rectify`` those of
     ops.event_rectify / ops.image_rectify (bit 0 of word 0: the camera record), ``filter`` those of ops.event_filter (bit 0 of
-    word 0: the events' order).  Word 0 of each goes to the host in one copy; raises in this order: event order, camera record,
-    unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times."""
+    word 0: the events' order), ``imu`` those of ops.imu_align (bit 0: the order of the samples or of the frames' time stamps;
+    bits 1 and 2: the gyro stage, the scale stage).  Word 0 of each goes to the host in one copy; raises in this order: event
+    order, camera record, unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times, IMU order, gyro
+    stage, scale stage."""
     given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam), ("voxel", voxel),
-                                                 ("rectify", rectify), ("filter", filter)) if s is not None]
+                                                 ("rectify", rectify), ("filter", filter), ("imu", imu)) if s is not None]
     if not given:
         return
     first = given[0][1] if len(given) == 1 else torch.cat([s for _, s in given])
@@ -86,6 +88,15 @@ def _raise_on_words(name, word):
         raise RuntimeError(name + ": the slice offsets decrease or leave the event list")
     if word.get("voxel", 0) & _lib.RAMP_VOXEL_BAD_TIMES:
         raise RuntimeError(name + ": the first or last time stamp of a slice is not finite")
+    imu = word.get("imu", 0)
+    if imu & _lib.RAMP_IMU_BAD_ORDER:
+        raise RuntimeError(name + ": the IMU samples' or the frames' time stamps decrease or are not finite")
+    if imu & _lib.RAMP_IMU_GYRO_FAILED:
+        raise RuntimeError(name + ": the gyro bias step failed (no interval between two frames is covered by the samples, or its system is not finite)")
+    if imu & _lib.RAMP_IMU_SCALE_FAILED:
+        why = ("fewer than two triples of frames are covered by the samples" if imu & _lib.RAMP_IMU_FEW_TRIPLES else
+               "the scale is not positive" if imu & _lib.RAMP_IMU_BAD_SCALE else "the system is singular")
+        raise RuntimeError(name + ": the scale and gravity solve failed: " + why)
 
 
 def _dof_sigma0(s):
@@ -102,6 +113,7 @@ class TrackerQueries:
     _camera = None              # set_camera(): the record's host part on the device, without the rectified intrinsics
     _filter_params = None       # set_event_filter(): the keywords of ops.event_filter
     _filter_state = None        # the filter's last-time-stamp map, carried by filter_events()
+    _imu = None                 # set_imu(): the keywords of ops.imu_align that describe the sensor
 
     def _state_stream(self, inputs=()):
         return StateStream(self, inputs)
@@ -216,6 +228,47 @@ class TrackerQueries:
             return poses, tw, status
         _check_status("poses_at()", traj=self._traj_status, interp=status)
         return poses.cpu().numpy(), (tw.cpu().numpy() if twist else None)
+
+    # ---------------------------------------------------------------- IMU
+    def set_imu(self, R_bc=None, p_bc=None, bias_g=None, bias_a=None):
+        """The IMU the samples of ``align_imu`` come from: the camera in the IMU (body) frame -- ``R_bc`` [3,3], ``p_bc`` [3], as
+        Kalibr's ``T_cam_imu`` inverted; None: identity, zero -- the gyro bias the alignment starts from and the accelerometer
+        bias it uses as it is (None: zero).  All four are HOST values (lists, arrays, CPU tensors; a device tensor is refused, as in
+        ``ops.imu_align``).  Nothing is uploaded, nothing synchronised."""
+        as_list = lambda k, v: None if v is None else np.asarray(ops._host_value("set_imu(): " + k, v), np.float64).tolist()
+        self._imu = dict(R_bc=as_list("R_bc", R_bc), p_bc=as_list("p_bc", p_bc), bias_g=as_list("bias_g", bias_g),
+                         bias_a=as_list("bias_a", bias_a))
+
+    def align_imu(self, tau, gyro, accel, stride=1, gravity_norm=9.80665, max_gap=float("inf"), gyro_steps=1,
+                  want_preint=False, as_tensor=False):
+        """Metric scale, gravity direction and gyro bias of the trajectory as it is now, from raw IMU samples (``ops.imu_align``
+        over ``trajectory(as_tensor=True)`` and the cached time stamps, with the sensor of ``set_imu``; raises without one):
+        ``tau`` [N] in the unit of the frames' time stamps, ``gyro``, ``accel`` [N,3] in the IMU frame (arrays or tensors;
+        float64 input stays float64).  ``stride``: every stride-th frame is a knot.  ``gravity_norm``: the known norm, or None
+        to leave it free.  ``evaluate.metric_trajectory`` applies the result to a trajectory.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
+        the dict of device tensors of ``ops.imu_align``, ordered on the current stream, nothing synchronised, nothing raised.
+        Otherwise numpy arrays (``scale`` a float), which reads once at the end and raises on the status bits: the order of
+        the time stamps, a failed gyro step, a failed scale solve, and trajectory()'s unresolved bit."""
+        if self._imu is None:
+            raise RuntimeError("align_imu(): no IMU has been set (set_imu())")
+        if len(self.tlist) < 2:
+            raise RuntimeError("align_imu(): fewer than two frames have been tracked")
+        fl = lambda v: torch.float64 if (v.dtype == torch.float64 if isinstance(v, torch.Tensor) else np.asarray(v).dtype == np.float64) else torch.float32
+        td = self._as_device(tau, torch.float64)
+        gd, ad = self._as_device(gyro, fl(gyro)).reshape(-1, 3), self._as_device(accel, fl(accel)).reshape(-1, 3)
+        knots, _ = self.trajectory(as_tensor=True)
+        tdev = self._frame_times_dev()
+        with torch.no_grad():                                  # (on the caller's stream, behind trajectory()'s launch: as poses_at)
+            out = ops.imu_align(td, gd, ad, knots, tdev, stride=stride, max_gap=max_gap, gravity_norm=gravity_norm,
+                                gyro_steps=gyro_steps, want_preint=want_preint, **self._imu)
+        if as_tensor:
+            return out
+        _check_status("align_imu()", traj=self._traj_status, imu=out["status"])
+        res = {k: v.cpu().numpy() for k, v in out.items()}
+        res["scale"] = float(res["scale"][0])
+        return res
 
     # ---------------------------------------------------------------- event denoising
     _FILTER_KEYS = ("support_dt", "refractory", "hot_count", "hot_sigma", "hot_mask")
