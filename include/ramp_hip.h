@@ -549,6 +549,24 @@ int ramp_conv2d_stats_blocks(int H, int W, int Cin, int Cout, int KH, int stride
 /* 1 where ramp_conv2d_nhwc runs this layer shape / dtype on the LDS-tiled fp16 kernel (the shapes ramp_conv2d_nhwc_multi
  * covers; its partials are per 8 x 16 output tile), 0 where on the direct one                                         */
 int ramp_conv2d_tiled(int Cin, int Cout, int KH, int stride, int dtype);
+/* The instances of the LDS-tiled fp16 kernel, as its one table lists them (csrc/conv.hip::CONV_TILE_ROWS; for tests that
+ * take the table as their parameter list).  ramp_conv2d_tile_rows: the number of rows.  ramp_conv2d_tile_row: row i
+ * (0 <= i < rows, else RAMP_EINVAL) -- filter size K, stride S, in_f32 (1: the fp32-input first layer), input channels
+ * Cin, NT (16-channel tiles per workgroup: NT = 4 rows want every Cout % 64 == 0), tile height TH (8 or 16 output rows
+ * of 16 pixels) and `variants`, the RAMP_TILE_* bits: the instances the row has beside its plain one and the entry
+ * points that may select it.  The first row that fits a launch wins.                                                  */
+#define RAMP_TILE_FP8 1      /* an fp8 instance (RAMP_CONV_FP8)                              */
+#define RAMP_TILE_TAIL 2     /* a fused-block-tail instance (ramp_conv_job.skip)             */
+#define RAMP_TILE_SINGLE 4   /* ramp_conv2d_nhwc may select the row                          */
+#define RAMP_TILE_PAIRED 8   /* ramp_conv2d_nhwc_multi may select the row                    */
+int ramp_conv2d_tile_rows(void);
+int ramp_conv2d_tile_row(int i, int *K, int *S, int *in_f32, int *Cin, int *NT, int *TH, int *variants);
+/* the row ramp_conv2d_nhwc_multi would launch for these arguments, without launching (the same validation and the same
+ * selection, tile height included: the code the launch itself runs): its index >= 0; -1 - row where the two towers' 7x7
+ * first layer goes to the dual kernel instead of that row (row 0, so -1: the same number as RAMP_EINVAL -- the launch's
+ * own return code tells the two apart); or the launch's error code (RAMP_EINVAL, RAMP_EUNSUPPORTED).  The instance of
+ * the row is the fp8 one with RAMP_CONV_FP8, the tail one where a job has `skip`, else the plain one.                  */
+int ramp_conv2d_multi_row(const ramp_conv_job *jobs, int njobs, int H, int W, int Cin, int KH, int stride, int dtype);
 
 /* InstanceNorm2d statistics (affine=False, biased variance): scale = rsqrt(var+eps),
  * shift = -mean*scale, from the per-block partials of ramp_conv2d_nhwc                         */

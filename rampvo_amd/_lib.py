@@ -20,6 +20,7 @@ RAMP_EUNSUPPORTED = -4
 RAMP_CONV_FP8 = 0x40
 RAMP_IN_F32, RAMP_CONV_DIRECT, RAMP_CORR_MFMA32, RAMP_CORR_X2 = 0x10, 0x20, 0x40, 0x80
 RAMP_CONV_X3 = 0x80
+RAMP_TILE_FP8, RAMP_TILE_TAIL, RAMP_TILE_SINGLE, RAMP_TILE_PAIRED = 1, 2, 4, 8
 RAMP_NCHW, RAMP_NHWC, RAMP_NHWC32 = 0, 1, 2
 RAMP_INTERP_EXTRAPOLATE, RAMP_INTERP_ROW_STORES, RAMP_INTERP_BAD_TIMES = 1, 2, 1
 RAMP_WARP_DEPTH_SCALAR, RAMP_WARP_DEPTH_MAP, RAMP_WARP_IDENTITY, RAMP_WARP_MIN_Z = 0, 4, 8, 0.2
@@ -101,6 +102,9 @@ SIGNATURES = {
     "ramp_ms_lstm_superstate_mfma": (c_i, [c_p] * 6 + [c_i] * 5 + [c_p]),
     "ramp_conv2d_stats_blocks": (c_i, [c_i] * 7),
     "ramp_conv2d_tiled": (c_i, [c_i] * 5),
+    "ramp_conv2d_tile_rows": (c_i, []),
+    "ramp_conv2d_tile_row": (c_i, [c_i] + [ctypes.POINTER(c_i)] * 7),
+    "ramp_conv2d_multi_row": (c_i, [c_p] + [c_i] * 7),
     "ramp_graph_edit_host": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
     "ramp_event_stack_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "ramp_event_stack": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),

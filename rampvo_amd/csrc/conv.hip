@@ -1794,7 +1794,7 @@ static int conv_params_from_job(const ConvLayer &L, const ramp_conv_job &j, Conv
 //     way; with all 64 output channels in it the tile is staged once instead of twice) only in the paired entry;
 //   * every NT = 4 row wants every Cout a multiple of 64 -- TileQuery::all64;
 //   * the 7x7 first layer (fp32 in) has no fp8 instance: it stays on the f16 MFMA.
-enum { T_FP8 = 1, T_TAIL = 2, T_SINGLE = 4, T_PAIRED = 8 };
+enum { T_FP8 = RAMP_TILE_FP8, T_TAIL = RAMP_TILE_TAIL, T_SINGLE = RAMP_TILE_SINGLE, T_PAIRED = RAMP_TILE_PAIRED };
 #define CONV_TILE_ROWS(X)                                        \
   X(7, 2, true, 16, 2, 8, T_SINGLE | T_PAIRED)                   \
   X(3, 1, false, 32, 2, 16, T_TAIL | T_PAIRED)                   \
@@ -1831,15 +1831,60 @@ static int conv_tile_row(int want, const ConvMulti &pm, int cmax, int njobs, hip
     if (want & T_TAIL) return conv_tile_launch<K, S, IN_F32, CIN, NT, false, TH, true>(pm, cmax, njobs, st);
   return conv_tile_launch<K, S, IN_F32, CIN, NT, false, TH, false>(pm, cmax, njobs, st);
 }
-// launches the first row that fits q -- or, without pm, only says whether there is one: RAMP_OK / RAMP_EUNSUPPORTED
-static int conv_tile_dispatch(const TileQuery &q, const ConvMulti *pm, int cmax, int njobs, hipStream_t st) {
+// launches the first row that fits q -- or, without pm, only says whether there is one: RAMP_OK / RAMP_EUNSUPPORTED; `row`
+// (optional) receives that row's index in CONV_TILE_ROWS
+static int conv_tile_dispatch(const TileQuery &q, const ConvMulti *pm, int cmax, int njobs, hipStream_t st, int *row = nullptr) {
+  int r = -1;
 #define TILE_ROW(K_, S_, F32_, CIN, NT, TH, VARIANTS)                                                                     \
+  r++;                                                                                                                    \
   if (q.K == K_ && q.S == S_ && q.in_f32 == F32_ && q.Cin == CIN && (NT == 2 || q.all64) && (TH == 8 || q.th16) &&        \
-      ((VARIANTS) & q.want) == q.want)                                                                                    \
-    return pm ? conv_tile_row<K_, S_, F32_, CIN, NT, TH, (VARIANTS)>(q.want, *pm, cmax, njobs, st) : RAMP_OK;
+      ((VARIANTS) & q.want) == q.want) {                                                                                  \
+    if (row) *row = r;                                                                                                    \
+    return pm ? conv_tile_row<K_, S_, F32_, CIN, NT, TH, (VARIANTS)>(q.want, *pm, cmax, njobs, st) : RAMP_OK;             \
+  }
   CONV_TILE_ROWS(TILE_ROW)
 #undef TILE_ROW
   return RAMP_EUNSUPPORTED;
+}
+
+// what ramp_conv2d_nhwc_multi decides before it launches: the validated jobs, the first layer's dual kernel or the
+// query its row is found with (the one place the th16 rule lives) -- shared with ramp_conv2d_multi_row, which only asks
+struct ConvMultiPlan {
+  ConvLayer L;
+  ConvMulti pm;
+  TileQuery q;
+  int cmax;
+  bool dual7;
+};
+static int conv_multi_plan(const ramp_conv_job *jobs, int njobs, int H, int W, int Cin, int KH, int stride, int dtype,
+                           ConvMultiPlan &pl) {
+  if (!jobs || njobs < 1 || njobs > 2 || H <= 0 || W <= 0) return RAMP_EINVAL;
+  const bool f16 = (dtype & 0xf) == RAMP_F16, in_f32 = f16 && (dtype & RAMP_IN_F32);
+  if (!f16 || (dtype & RAMP_CONV_DIRECT)) return RAMP_EUNSUPPORTED;
+  const bool fp8 = (dtype & RAMP_CONV_FP8) != 0;
+  if (fp8 && in_f32) return RAMP_EUNSUPPORTED;
+  pl.L = conv_layer(H, W, Cin, KH, stride, in_f32, fp8);
+  const ConvLayer &L = pl.L;
+  if (L.OH <= 0 || L.OW <= 0) return RAMP_EINVAL;
+  int cmax = 0;
+  bool all64 = true, block_stats = false, any_skip = false;
+  for (int t = 0; t < 2; t++) {
+    const ramp_conv_job &j = jobs[t < njobs ? t : 0];
+    const int rc = conv_params_from_job(L, j, pl.pm.t[t]);
+    if (rc != RAMP_OK) return rc;
+    cmax = j.Cout > cmax ? j.Cout : cmax;
+    all64 &= j.Cout % 64 == 0;
+    block_stats |= j.stats != nullptr;
+    any_skip |= j.skip != nullptr;
+  }
+  pl.cmax = cmax;
+  // the first layer of the two towers: one workgroup per tile computes both (shared input, no prologue)
+  pl.dual7 = KH == 7 && stride == 2 && in_f32 && Cin == 16 && njobs == 2 && jobs[0].x == jobs[1].x && jobs[0].Cout == 32 &&
+             jobs[1].Cout == 32 && !jobs[0].pre_scale && !jobs[1].pre_scale;
+  if (!pl.dual7 && any_skip && block_stats) return RAMP_EUNSUPPORTED;          // (a fused block tail: accumulator mode in every tower)
+  const bool th16 = !block_stats && (long)ramp_cdiv(L.OH, 16) * ramp_cdiv(L.OW, 16) * njobs * (cmax / 32) >= 512;
+  pl.q = TileQuery{KH, stride, Cin, in_f32, all64, th16, T_PAIRED | (fp8 ? T_FP8 : 0) | (any_skip ? T_TAIL : 0)};
+  return RAMP_OK;
 }
 
 // the layer shapes of conv_x3_kernel, ONE list: K, S, CIN, COUT; p = nullptr only asks, as above
@@ -2018,37 +2063,48 @@ int ramp_conv2d_nhwc(const void *x, const void *wpk, const float *bias, const fl
 
 int ramp_conv2d_nhwc_multi(const ramp_conv_job *jobs, int njobs, int H, int W, int Cin, int KH, int stride,
                            int dtype, void *stream) {
-  if (!jobs || njobs < 1 || njobs > 2 || H <= 0 || W <= 0) return RAMP_EINVAL;
-  const bool f16 = (dtype & 0xf) == RAMP_F16, in_f32 = f16 && (dtype & RAMP_IN_F32);
-  if (!f16 || (dtype & RAMP_CONV_DIRECT)) return RAMP_EUNSUPPORTED;
-  const bool fp8 = (dtype & RAMP_CONV_FP8) != 0;
-  if (fp8 && in_f32) return RAMP_EUNSUPPORTED;
-  const ConvLayer L = conv_layer(H, W, Cin, KH, stride, in_f32, fp8);
-  if (L.OH <= 0 || L.OW <= 0) return RAMP_EINVAL;
-  ConvMulti pm;
-  int cmax = 0;
-  bool all64 = true, block_stats = false, any_skip = false;
-  for (int t = 0; t < 2; t++) {
-    const ramp_conv_job &j = jobs[t < njobs ? t : 0];
-    const int rc = conv_params_from_job(L, j, pm.t[t]);
-    if (rc != RAMP_OK) return rc;
-    cmax = j.Cout > cmax ? j.Cout : cmax;
-    all64 &= j.Cout % 64 == 0;
-    block_stats |= j.stats != nullptr;
-    any_skip |= j.skip != nullptr;
-  }
+  ConvMultiPlan pl;
+  const int rc = conv_multi_plan(jobs, njobs, H, W, Cin, KH, stride, dtype, pl);
+  if (rc != RAMP_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // the first layer of the two towers: one workgroup per tile computes both (shared input, no prologue)
-  if (KH == 7 && stride == 2 && in_f32 && Cin == 16 && njobs == 2 && jobs[0].x == jobs[1].x && jobs[0].Cout == 32 &&
-      jobs[1].Cout == 32 && !jobs[0].pre_scale && !jobs[1].pre_scale) {
-    hipLaunchKernelGGL(conv7_dual_kernel, dim3(ramp_cdiv(L.OH, 8) * ramp_cdiv(L.OW, 16), 1, 1), dim3(256), 0, st, pm);
+  if (pl.dual7) {
+    hipLaunchKernelGGL(conv7_dual_kernel, dim3(ramp_cdiv(pl.L.OH, 8) * ramp_cdiv(pl.L.OW, 16), 1, 1), dim3(256), 0, st, pl.pm);
     RAMP_CHECK_LAUNCH();
     return RAMP_OK;
   }
-  if (any_skip && block_stats) return RAMP_EUNSUPPORTED;          // (a fused block tail: accumulator mode in every tower)
-  const bool th16 = !block_stats && (long)ramp_cdiv(L.OH, 16) * ramp_cdiv(L.OW, 16) * njobs * (cmax / 32) >= 512;
-  const TileQuery q = {KH, stride, Cin, in_f32, all64, th16, T_PAIRED | (fp8 ? T_FP8 : 0) | (any_skip ? T_TAIL : 0)};
-  return conv_tile_dispatch(q, &pm, cmax, njobs, st);
+  return conv_tile_dispatch(pl.q, &pl.pm, pl.cmax, njobs, st);
+}
+
+int ramp_conv2d_multi_row(const ramp_conv_job *jobs, int njobs, int H, int W, int Cin, int KH, int stride, int dtype) {
+  ConvMultiPlan pl;
+  int rc = conv_multi_plan(jobs, njobs, H, W, Cin, KH, stride, dtype, pl), row = 0;
+  if (rc != RAMP_OK) return rc;
+  if (pl.dual7) {                                     // (the row of its layer shape, as a single 8 x 16 launch would take it)
+    pl.q.th16 = false;
+    pl.q.want = T_PAIRED;
+  }
+  rc = conv_tile_dispatch(pl.q, nullptr, 0, 0, nullptr, &row);
+  if (rc != RAMP_OK) return rc;
+  return pl.dual7 ? -1 - row : row;
+}
+
+int ramp_conv2d_tile_rows(void) {
+#define TILE_ROW(K_, S_, F32_, CIN, NT, TH, VARIANTS) +1
+  return 0 CONV_TILE_ROWS(TILE_ROW);
+#undef TILE_ROW
+}
+
+int ramp_conv2d_tile_row(int i, int *K, int *S, int *in_f32, int *Cin, int *NT, int *TH, int *variants) {
+  if (!K || !S || !in_f32 || !Cin || !NT || !TH || !variants) return RAMP_EINVAL;
+  int r = -1;
+#define TILE_ROW(K_, S_, F32_, CIN, NT_, TH_, VARIANTS)                                                        \
+  if (++r == i) {                                                                                              \
+    *K = K_; *S = S_; *in_f32 = F32_; *Cin = CIN; *NT = NT_; *TH = TH_; *variants = (VARIANTS);               \
+    return RAMP_OK;                                                                                            \
+  }
+  CONV_TILE_ROWS(TILE_ROW)
+#undef TILE_ROW
+  return RAMP_EINVAL;
 }
 
 int ramp_conv2d_tiled(int Cin, int Cout, int KH, int stride, int dtype) {

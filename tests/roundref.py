@@ -139,6 +139,48 @@ def conv_ref(x_nhwc, w, b, stride, pad):
     return y, m
 
 
+# the small biases of the conv-layer cases (test_conv_instances_gpu.py::make_conv): a dropped one must show
+TINY_BIASES = (2e-3, -1e-3, 3e-3, -2.5e-3)
+IN_ACC_ONE = 2.0 ** 20       # csrc/conv.hip::IN_ACC_ONE: the accumulators' fixed point
+# the fp32 steps between the float64 tail pixel and the kernels' (scale, shift as floats, product, sum: four for y, four
+# for a normalised skip, one for the last sum), each within 2^-24 of a partial magnitude <= m: 9 2^-24 m < GAMMA(TAIL_K) m
+TAIL_K = 8
+NORM_K = 2                   # fp16(relu(x scale + shift)): scale, shift, product, sum -- 4 2^-24 m <= GAMMA(2) m
+
+
+def acc_stats(acc, C, count, eps):
+    """InstanceNorm statistics from the accumulator integers (csrc/conv.hip::in_acc_finalize; acc [R][C][2] int64:
+    replicated 2^-20 fixed-point sums of x and x^2): (mean, biased variance, scale = rsqrt(var + eps), shift =
+    -mean scale) in float64.  The integer sum is exact; eps is the float the kernel is handed."""
+    s = acc.view(-1, C, 2).sum(0)
+    eps = float(torch.tensor(eps, dtype=torch.float32))
+    mean = s[:, 0].double() / IN_ACC_ONE / float(count)
+    var = (s[:, 1].double() / IN_ACC_ONE / float(count) - mean * mean).clamp(min=0.0)
+    scale = 1.0 / torch.sqrt(var + eps)
+    return mean, var, scale, -mean * scale
+
+
+def norm_relu_ref(x, scale, shift):
+    """relu(x scale + shift) in float64 and its magnitude |x scale| + |shift| (the prologue's operand before rounding)"""
+    a = x.double() * scale.double()
+    return torch.relu(a + shift.double()), a.abs() + shift.double().abs()
+
+
+def tail_ref(y, scale, shift, skip, skip_scale=None, skip_shift=None, skip_relu=False):
+    """the residual block's tail pixel relu(relu(y scale + shift) + skip') in float64 and its magnitude; skip' = skip,
+    or skip skip_scale + skip_shift (the downsample path's norm), or fp16(relu(that)) (`skip_relu`: a normalised map
+    that was never materialised, rounded as the materialised one would be); y, skip [H, W, C]"""
+    a, ma = norm_relu_ref(y, scale, shift)
+    b = skip.double()
+    mb = b.abs()
+    if skip_scale is not None:
+        t = b * skip_scale.double()
+        b, mb = t + skip_shift.double(), t.abs() + skip_shift.double().abs()
+    if skip_relu:
+        b = round_to(torch.relu(b), "fp16")
+    return torch.relu(a + b), ma + mb
+
+
 def corr_ref(fmap1, fmap2, coords, ii, jj, R):
     """the correlation (oracle/ramp_oracle.c orc_corr: dot products over C at the integer window, then the bilinear
     blend) in float64, with its magnitude; fmap1 [N1, C, P, P], fmap2 [N2, C, H, W], coords [E, 2, P, P] ->

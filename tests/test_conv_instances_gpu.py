@@ -1,0 +1,607 @@
+"""Every instance of the LDS-tiled fp16 conv kernel (csrc/conv.hip::conv_tile_f16_kernel) against float64, at its edges.
+
+The kernel's layer-shape table (CONV_TILE_ROWS, read through ramp_conv2d_tile_rows / ramp_conv2d_tile_row) is this file's
+parameter list: every row, each of its variants (plain, fp8, fused residual-block tail) and both entry points
+(ramp_conv2d_nhwc, ramp_conv2d_nhwc_multi) has a case below, and `test_every_table_entry_has_a_case` fails for a row that
+has none.  Before a launch the driver asks the library which row the launch takes (ramp_conv2d_multi_row; for the single
+launch ramp_conv2d_tiled and the table's first-fit rule) and asserts that it is the row the case is labelled with -- the
+tile height is part of the row, so a TH = 16 case is known to have run TH = 16.
+
+What a case checks (tests/roundref.py; tests/test_roundref_cpu.py shows what these checks can tell apart):
+  * every output element is fp16(exact) of the float64 value on the same rounded operands, or the neighbour an fp32
+    accumulation error of GAMMA(K) m explains: zero unexplained elements (`check_rounded`);
+  * the operand of a layer behind a normalisation (pre_scale / pre_shift, the accumulators `acc_in`, the fused tail) is
+    taken from the kernel that writes the same value out (ramp_affine_relu_f16, ramp_norm_add_relu_f16_acc, the tail's own
+    `mat`), so that a flipped fp16 rounding of the operand does not compound; that operand is checked against float64 on its
+    own, the scale and shift formed in float64 from the accumulators' integers;
+  * the InstanceNorm statistics (per-block partials of the single launch, accumulators of the paired one) against the
+    float64 mean and variance of the exact raw output; accumulators bit-identical over three launches;
+  * every output buffer (y, mat, acc_out, stats) is a view between canary rows, intact after every launch.
+
+Shapes: the smallest that reach each path -- the TH = 16 row needs 512 workgroups of 16 x 16 pixels x 32 channels (113 x 250,
+121 x 241, 128 x 256 for two 64-channel towers: one live row, 9 live rows and one live column, exact; 250 x 249 for two
+32-channel towers; 112 x 250 stays on TH = 8), the TH = 8 rows one ragged map (OH % 8 and OW % 16 nonzero), and every row
+maps smaller than a tile, than the filter, with one output row or column.  conv_layer rejects none of these (padding
+K / 2 leaves at least one output pixel for every H, W >= 1), so none is skipped; the TH = 16 row cannot be reached by a
+map that small.
+
+The per-pixel accumulation order of conv_tile_f16_kernel does not depend on TH (the same ky, kx, channel-chunk loop feeds
+one MFMA per 16-pixel row segment; TH only changes which wave owns the row), so the TH = 16 outputs are also compared bit
+for bit with the single launches (TH = 8) and with the direct kernel.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+import roundref as rr
+from guarded import Guarded
+
+pytestmark = pytest.mark.gpu
+
+PLAIN, FP8, TAIL, SINGLE, PAIRED = 0, 1, 2, 4, 8      # include/ramp_hip.h::RAMP_TILE_*
+MAT_CANARY = -3.0            # a tail pixel is a ReLU's output: never negative
+ACC_CANARY = 0x5A5A5A5A5A5A5A
+# |mean - mean64| / rms and |var - var64| / mean square of the raw output (test_fp16_rounding_gpu.py::IN_STATS_TOL's
+# metric and value).  Measured on MI355X against float64 over the TH = 16, the ragged, the prologue, the tail and the
+# two-source cases of this file (f16 instances): accumulators mean <= 4.8e-8, var <= 7.0e-8; per-block partials mean
+# <= 2.7e-8, var <= 5.4e-8 -- inside the older bound, which is kept.  (The fp8 instances and the degenerate maps: see
+# test_fp8_instance and test_degenerate_maps.)
+IN_STATS_TOL = 6e-7
+# the fp8 instances' accumulators (test_fp8_instance): measured over the eight fp8 rows mean <= 8.7e-6, var <= 4.5e-6;
+# bounds about 2x
+FP8_STATS_TOL = (2e-5, 1e-5)
+# the single launch's fp32 partials on the degenerate maps (test_degenerate_maps): measured mean <= 6.6e-5 (the one-pixel
+# map of the 1x1 128-channel row; the next 9.2e-6), var <= 6.5e-7; bounds about 2x.  The accumulators of those maps stay on
+# IN_STATS_TOL behind the fixed point's allowance (measured there: mean <= 1.7e-7, var <= 1.8e-7)
+SMALL_MAP_PARTIALS_TOL = (1.3e-4, 1.3e-6)
+
+# rows of the table by what they are: (K, S, in_f32, Cin, NT, TH)
+R7x7 = (7, 2, 1, 16, 2, 8)
+R3_32_TH16 = (3, 1, 0, 32, 2, 16)
+R3_32 = (3, 1, 0, 32, 2, 8)
+R3S2_32 = (3, 2, 0, 32, 2, 8)
+R3S2_64_NT4 = (3, 2, 0, 64, 4, 8)
+R3S2_64 = (3, 2, 0, 64, 2, 8)
+R3_64 = (3, 1, 0, 64, 2, 8)
+R1S2_32 = (1, 2, 0, 32, 4, 8)
+R1S2_64 = (1, 2, 0, 64, 4, 8)
+R1_64 = (1, 1, 0, 64, 4, 8)
+R1_128 = (1, 1, 0, 128, 4, 8)
+S1_RAGGED, S2_RAGGED = (37, 53), (61, 83)              # OH x OW = 37 x 53 and 31 x 42: OH % 8 = 5 / 7, OW % 16 = 5 / 10
+
+# (row, Cout of the two towers, H x W): the TH = 16 shapes, the same layer just under the threshold, every TH = 8 row ragged
+# (the 7x7 layer through its own row and, with two 32-channel towers on one input, through the dual kernel), and one map
+# whose OW is a multiple of 16 while OH is not
+TH16_LAYERS = [(R3_32_TH16, (64, 64), (113, 250)), (R3_32_TH16, (64, 64), (121, 241)), (R3_32_TH16, (64, 64), (128, 256)),
+               (R3_32_TH16, (32, 32), (250, 249))]
+LAYERS = TH16_LAYERS + [
+    (R3_32, (64, 64), (112, 250)),
+    (R7x7, (32, 64), S2_RAGGED), (R7x7, (32, 32), S2_RAGGED),
+    (R3_32, (32, 64), S1_RAGGED), (R3_32, (32, 64), (37, 48)), (R3S2_32, (64, 32), S2_RAGGED),
+    (R3S2_64_NT4, (64, 64), S2_RAGGED), (R3S2_64, (64, 32), S2_RAGGED), (R3_64, (64, 64), S1_RAGGED),
+    (R1S2_32, (64, 64), S2_RAGGED), (R1S2_64, (64, 128), S2_RAGGED), (R1_64, (64, 128), S1_RAGGED),
+    (R1_128, (128, 64), S1_RAGGED)]
+TAIL_LAYERS = [(R3_32_TH16, (64, 64), (113, 250)), (R3_32, (32, 64), S1_RAGGED), (R3_64, (64, 64), S1_RAGGED),
+               (R3S2_32, (64, 32), S2_RAGGED), (R1S2_32, (64, 64), S2_RAGGED), (R1_64, (64, 128), S1_RAGGED)]
+SKIP_FORMS = ["tensor", "norm", "norm_relu"]           # a plain fp16 tensor, Pending(relu=False), Pending(relu=True)
+# the MultiScale towers' two-source layers (conv_hip.multiscale_encoder4_towers): layer3's 3x3 / s2 conv1 and 1x1 / s2
+# downsample read cat(layer1's 32 channels, the 1/2 super-state's 32), conv3 (1x1) cat(layer3's 64, the 1/4 super-state's 64)
+PAIR_LAYERS = [(R3S2_64_NT4, (64, 64), S2_RAGGED, 32), (R3S2_64, (64, 32), S2_RAGGED, 32),
+               (R1S2_64, (64, 64), S2_RAGGED, 32), (R1_128, (128, 384), S1_RAGGED, 64)]
+FP8_LAYERS = [(R3_32, (32, 64), S1_RAGGED), (R3S2_32, (64, 32), S2_RAGGED), (R3S2_64, (64, 64), S2_RAGGED),
+              (R3_64, (64, 64), S1_RAGGED), (R1S2_32, (64, 64), S2_RAGGED), (R1S2_64, (64, 128), S2_RAGGED),
+              (R1_64, (64, 128), S1_RAGGED), (R1_128, (128, 384), S1_RAGGED)]
+SMALL_ROWS = [(R7x7, (32, 64)), (R3_32, (32, 64)), (R3S2_32, (64, 32)), (R3S2_64_NT4, (64, 64)), (R3S2_64, (64, 32)),
+              (R3_64, (64, 64)), (R1S2_32, (64, 64)), (R1S2_64, (64, 128)), (R1_64, (64, 128)), (R1_128, (128, 64))]
+SMALL_MAPS = [(1, 1), (1, 17), (2, 2), (3, 2), (7, 5), (9, 16)]
+
+_table = []
+
+
+def table():
+    """the kernel's rows as the library reports them: [(K, S, in_f32, Cin, NT, TH, variants)]"""
+    if not _table:
+        from rampvo_amd._lib import lib
+        v = [ctypes.c_int() for _ in range(7)]
+        for i in range(lib().ramp_conv2d_tile_rows()):
+            assert lib().ramp_conv2d_tile_row(i, *[ctypes.byref(c) for c in v]) == 0
+            _table.append(tuple(c.value for c in v))
+        assert lib().ramp_conv2d_tile_row(len(_table), *[ctypes.byref(c) for c in v]) == -1      # RAMP_EINVAL past the end
+    return _table
+
+
+def row_of(key):
+    return [r[:6] for r in table()].index(key)
+
+
+def single_row(K, S, in_f32, Cin, cout):
+    """the table's first-fit rule for ramp_conv2d_nhwc: the first SINGLE row of this shape (NT = 4: Cout % 64 == 0).  This
+    restates the TileQuery that csrc/conv.hip::ramp_conv2d_nhwc (and ramp_conv2d_tiled) builds -- all64 = Cout % 64 == 0,
+    th16 = false, want = T_SINGLE -- against conv_tile_dispatch's row condition; the library has no row query for the
+    single launch, so a change to that query has to be made here as well"""
+    for i, (k, s, f, c, nt, th, var) in enumerate(table()):
+        if (k, s, f, c) == (K, S, in_f32, Cin) and (nt == 2 or cout % 64 == 0) and th == 8 and var & SINGLE:
+            return i
+    return None
+
+
+def _name(key, couts, hw):
+    return "%dx%d s%d %d->%s TH%d %dx%d" % (key[0], key[0], key[1], key[3], "/".join(map(str, couts)), key[5], hw[0], hw[1])
+
+
+def _ids(cases):
+    return [_name(*c[:3]).replace(" ", "_") for c in cases]
+
+
+# ----------------------------------------------------------------------------------------------------- inputs
+def make_conv(cin, cout, k, stride, rounded=True):
+    """fp16-valued weights and biases; the first four biases are TINY_BIASES, small against the others and still above
+    GAMMA(K) m of these layers' small-magnitude outputs, so that dropping one of them shows
+    (test_roundref_cpu.py::test_conv_reference_rejects_the_tiled_kernels_defects drops one of exactly these).  The first
+    layer has 15 real input channels: the pack pads the 16th with zeros"""
+    conv = nn.Conv2d(15 if cin == 16 else cin, cout, k, stride=stride, padding=k // 2).cuda()
+    with torch.no_grad():
+        if rounded:
+            conv.weight.copy_(conv.weight.half().float())
+        conv.bias.copy_(conv.bias.half().float())
+        conv.bias[:4] = torch.tensor(rr.TINY_BIASES, device="cuda").half().float()
+    return conv
+
+
+def make_x(H, W, cin, first=False, gain=1.0):
+    """the layer's input: fp16 values with every fourth row scaled by 1e-2 (fp32, unrounded, for the first layer)"""
+    x = torch.randn(H, W, cin, device="cuda") * gain
+    x[::4] *= 1e-2
+    if cin == 16:
+        x[..., 15] = 0
+    return x if first else x.half()
+
+
+def out_size(H, W, k, s):
+    return (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
+
+
+# ----------------------------------------------------------------------------------------------------- driver
+def _codes(x, fp8):
+    from rampvo_amd import _lib
+    first = x.dtype == torch.float32
+    code = _lib.RAMP_F16 | (_lib.RAMP_IN_F32 if first else 0) | (_lib.RAMP_CONV_FP8 if fp8 else 0)
+    return code, "f8" if fp8 else "f16_first" if first else "f16"
+
+
+def launch(jobs, k, stride, fp8=False, label=None, expect=0):
+    """ONE ramp_conv2d_nhwc_multi launch of `jobs` (dicts: x = tensor | Pending with accumulators | Tail, conv, and
+    optionally x2, pre = (scale, shift), res, relu, out_scale, stats = "acc" | "block", mat = False), filled as
+    conv_hip.conv2d_towers fills them, every output inside a canary-filled allocation.  label = (row key, variant, dual):
+    what ramp_conv2d_multi_row must say first.  expect: the launch's return code.  -> [dict(y=, mat=, acc=, stats=)] views"""
+    from rampvo_amd import conv_hip
+    from rampvo_amd._lib import lib, ptr, stream
+    raw0 = jobs[0]["x"]
+    raw0 = raw0.y.raw if isinstance(raw0, conv_hip.Tail) else raw0.raw if isinstance(raw0, conv_hip.Pending) else raw0
+    code, mode = _codes(raw0, fp8)
+    H, W = raw0.shape[:2]
+    Cin = raw0.shape[2] + (jobs[0]["x2"].shape[2] if jobs[0].get("x2") is not None else 0)
+    OH, OW = out_size(H, W, k, stride)
+    arr = (conv_hip.ConvJob * len(jobs))()
+    guards, outs, alive = [], [], []
+    for a, j in zip(arr, jobs):
+        x, conv, tail = j["x"], j["conv"], None
+        cout = conv.weight.shape[0]
+        if isinstance(x, conv_hip.Tail):
+            tail, x = x, x.y
+        if isinstance(x, conv_hip.Pending):
+            assert x.acc is not None and x.relu
+            a.acc_in, a.in_count, a.in_eps = ptr(x.acc), x.count, x.eps
+            x = x.raw
+        pk = conv_hip.pack_conv_weight(conv, mode)
+        alive.append(pk)
+        a.x, a.wpk, a.bias = ptr(x), ptr(pk[0]), ptr(pk[1])
+        assert x.is_contiguous() and x.shape[:2] == (H, W)
+        if j.get("x2") is not None:
+            assert j["x2"].is_contiguous() and x.shape[2] + j["x2"].shape[2] == Cin
+            a.x2, a.c0 = ptr(j["x2"]), x.shape[2]
+        if j.get("pre"):
+            a.pre_scale, a.pre_shift = ptr(j["pre"][0]), ptr(j["pre"][1])
+        g = dict(y=Guarded(OH * OW, cout, torch.float16, fill=float("inf")))
+        if tail is not None:
+            sk = tail.skip
+            if isinstance(sk, conv_hip.Pending):
+                a.skip, a.acc_skip, a.skip_count, a.skip_eps, a.skip_relu = ptr(sk.raw), ptr(sk.acc), sk.count, sk.eps, int(sk.relu)
+            else:
+                assert sk.is_contiguous() and sk.dtype == x.dtype and sk.shape == x.shape
+                a.skip = ptr(sk)
+            if stride == 1 and j.get("mat", True):
+                g["mat"] = Guarded(H * W, Cin, torch.float16, fill=MAT_CANARY)
+                a.mat = ptr(g["mat"].t)
+        a.res, a.y = ptr(j.get("res")), ptr(g["y"].t)
+        a.Cout, a.relu, a.out_scale = cout, int(j.get("relu", False)), float(j.get("out_scale", 1.0))
+        a.act_scale, a.w_scale = (conv_hip.FP8_ACT_SCALE, pk[2]) if fp8 else (0.0, 0.0)
+        if j.get("stats") == "acc":
+            g["acc"] = Guarded(conv_hip.IN_ACC_R, cout * 2, torch.int64, fill=0, canary=ACC_CANARY)
+            a.acc_out = ptr(g["acc"].t)
+        elif j.get("stats") == "block":
+            nblk = lib().ramp_conv2d_stats_blocks(H, W, Cin, cout, k, stride, code)
+            g["stats"] = Guarded(cout * 2, nblk, torch.float32)
+            a.stats = ptr(g["stats"].t)
+        guards.append(g)
+    row = lib().ramp_conv2d_multi_row(arr, len(jobs), H, W, Cin, k, stride, code)
+    if label is not None:
+        key, variant, dual = label
+        want = FP8 if fp8 else TAIL if any(isinstance(j["x"], conv_hip.Tail) for j in jobs) else PLAIN
+        assert variant == want, "the case is labelled with another instance than its arguments select"
+        assert variant == PLAIN or table()[row_of(key)][6] & variant, "the row has no such instance"
+        assert row == (-1 - row_of(key) if dual else row_of(key)), (row, key, table())
+        assert key[5] == (table()[row][5] if row >= 0 else 8)
+    rc = lib().ramp_conv2d_nhwc_multi(arr, len(jobs), H, W, Cin, k, stride, code, stream())
+    torch.cuda.synchronize()
+    assert rc == expect, (rc, expect)
+    if expect != 0:
+        assert row == expect, (row, expect)
+    for g in guards:
+        for n, b in g.items():
+            assert b.intact(), "a write outside " + n
+        outs.append({n: b.t for n, b in g.items()})
+        if expect != 0:
+            assert bool(torch.isinf(g["y"].t).all()), "a refused launch wrote"
+    for o, j in zip(outs, jobs):
+        o["y"] = o["y"].view(OH, OW, -1)
+        if "mat" in o:
+            o["mat"] = o["mat"].view(H, W, Cin)
+    return outs
+
+
+def launch_single(x, conv, key):
+    """ramp_conv2d_nhwc (plain output, per-block statistics) on guarded buffers; key: the row the table's first-fit rule
+    must give for it -> (y, stats [Cout][2][blocks])"""
+    from rampvo_amd import conv_hip
+    from rampvo_amd._lib import lib, ptr, stream
+    code, mode = _codes(x, False)
+    H, W, Cin = x.shape
+    cout, _, k, _ = conv.weight.shape
+    stride = conv.stride[0]
+    OH, OW = out_size(H, W, k, stride)
+    assert lib().ramp_conv2d_tiled(Cin, cout, k, stride, code) == 1
+    assert single_row(k, stride, int(x.dtype == torch.float32), Cin, cout) == row_of(key)
+    wpk, bias = conv_hip.pack_conv_weight(conv, mode)
+    y = Guarded(OH * OW, cout, torch.float16, fill=float("inf"))
+    nblk = lib().ramp_conv2d_stats_blocks(H, W, Cin, cout, k, stride, code)
+    assert nblk == -(-OH // 8) * -(-OW // 16)
+    st = Guarded(cout * 2, nblk, torch.float32)
+    rc = lib().ramp_conv2d_nhwc(ptr(x), ptr(wpk), ptr(bias), None, None, None, ptr(y.t), ptr(st.t), H, W, Cin, cout, k, k,
+                                stride, 0, 1.0, code, stream())
+    torch.cuda.synchronize()
+    assert rc == 0, rc
+    assert y.intact() and st.intact()
+    return y.t.view(OH, OW, cout), st.t.view(cout, 2, nblk)
+
+
+def producer(H, W, C):
+    """a raw fp16 map [H, W, C] with its InstanceNorm accumulators, as a real layer leaves them: the output of a 3x3
+    32 -> C layer of the tiled kernel in accumulator mode -> Pending(relu=True)"""
+    from rampvo_amd import conv_hip
+    u, conv = make_x(H, W, 32), make_conv(32, C, 3, 1)
+    o = launch([dict(x=u, conv=conv, stats="acc")], 3, 1)[0]
+    return conv_hip.Pending(o["y"], None, None, acc=o["acc"], count=H * W, eps=1e-5)
+
+
+def fresh(p, relu=True):
+    """the same raw map and accumulators as a Pending nobody has finalised"""
+    from rampvo_amd import conv_hip
+    return conv_hip.Pending(p.raw, None, None, relu=relu, acc=p.acc, count=p.count, eps=p.eps)
+
+
+def normalised(p, name):
+    """fp16(relu(norm(p.raw))) as ramp_affine_relu_f16 writes it from the accumulators' scale and shift, checked against
+    float64 with the scale and shift formed in float64 from the accumulators' integers"""
+    from rampvo_amd import conv_hip
+    op = conv_hip.materialize(fresh(p))
+    _, _, sc, sh = rr.acc_stats(p.acc, p.raw.shape[-1], p.count, p.eps)
+    e, m = rr.norm_relu_ref(p.raw, sc, sh)
+    rr.check_rounded(op, e, m, "fp16", rr.NORM_K, name + " operand")
+    return op
+
+
+# ----------------------------------------------------------------------------------------------------- checks
+def fixed_point_allowance(ex, tiles):
+    """what the accumulators' 2^-20 fixed point may add to the statistics' error on a map of n pixels in `tiles` tiles, per
+    channel and in IN_STATS_TOL's units: every tile's two sums are rounded to a multiple of 2^-20 (2^-21 each), so the
+    mean and the mean square err by d = tiles 2^-21 / n -- d / rms for the mean, and for the variance (mean square minus
+    mean^2, |mean| <= rms) d / ms + 2 d / rms.  On the ragged and the TH = 16 maps that is below 1e-8 (n / tiles ~ 100
+    pixels, rms ~ 0.5) and not granted; on a map of one or a few pixels a channel's rms can be 1e-3 and d / rms 1e-3"""
+    n, ms = ex.shape[0] * ex.shape[1], (ex * ex).mean((0, 1))
+    d = tiles * 2.0 ** -21 / n
+    return d / ms.sqrt(), d / (ms + 1e-5) + 2 * d / ms.sqrt()
+
+
+def check_stats(name, kind, mean_k, var_k, ex, tol=(IN_STATS_TOL, IN_STATS_TOL), allow=None):
+    """the statistics' error over the rms / the mean square, per channel, less `allow` (fixed_point_allowance), within tol"""
+    mean, ms, var = ex.mean((0, 1)), (ex * ex).mean((0, 1)), ex.var((0, 1), unbiased=False)
+    em, ev = (mean_k - mean).abs() / ms.sqrt(), (var_k - var).abs() / (ms + 1e-5)
+    raw = float(em.max()), float(ev.max())
+    if allow is not None:
+        em, ev = em - allow[0], ev - allow[1]
+    em, ev = float(em.max()), float(ev.max())
+    print("%-44s IN stats (%s): mean %.2e, var %.2e (bounds %.1e, %.1e)%s" % (
+        name, kind, em, ev, tol[0], tol[1], "" if allow is None else "; before the fixed-point allowance %.2e, %.2e" % raw))
+    assert em <= tol[0] and ev <= tol[1], (name, kind, em, ev, tol)
+
+
+def check_towers(name, key, outs, operand, convs, res, K=None, fixed_point=False):
+    """tower 0 (raw output + accumulators) and tower 1 (ReLU, residual, out_scale 0.25) against float64 on `operand`
+    ([H, W, Cin]; a pair: one per tower) -> the exact raw output of tower 0 and its magnitude.  fixed_point: the degenerate
+    maps' allowance for the accumulators' resolution (fixed_point_allowance)"""
+    k, stride = key[0], key[1]
+    K = K or (15 if key[3] == 16 else key[3]) * k * k
+    ops = operand if isinstance(operand, (tuple, list)) else (operand, operand)
+    ex0, m0 = rr.conv_ref(ops[0].float(), convs[0].weight, convs[0].bias, stride, k // 2)
+    ex1, m1 = rr.conv_ref(ops[1].float(), convs[1].weight, convs[1].bias, stride, k // 2)
+    rr.check_rounded(outs[0]["y"], ex0, m0, "fp16", K, name + " t0")
+    rr.check_rounded(outs[1]["y"], torch.relu(torch.relu(ex1) + res.double()) * 0.25, (m1 + res.double().abs()) * 0.25,
+                     "fp16", K + 2, name + " t1")
+    if "acc" in outs[0]:
+        mean, var, _, _ = rr.acc_stats(outs[0]["acc"], convs[0].weight.shape[0], ex0.shape[0] * ex0.shape[1], 1e-5)
+        if fixed_point:
+            tiles = -(-ex0.shape[0] // 8) * -(-ex0.shape[1] // 16)
+            check_stats(name, "accumulators", mean, var, ex0, allow=fixed_point_allowance(ex0, tiles))
+        else:
+            check_stats(name, "accumulators", mean, var, ex0)
+    return ex0, m0
+
+
+def tower_jobs(x0, x1, convs, res, stats="acc", **extra):
+    return [dict(x=x0, conv=convs[0], stats=stats, **extra), dict(x=x1, conv=convs[1], relu=True, res=res, out_scale=0.25, **extra)]
+
+
+def layer(key, couts, hw):
+    k, stride, first, cin = key[:4]
+    convs = [make_conv(cin, c, k, stride) for c in couts]
+    x = make_x(hw[0], hw[1], cin, bool(first))
+    res = torch.randn(*out_size(hw[0], hw[1], k, stride), couts[1], device="cuda").half()
+    return convs, x, res
+
+
+# ----------------------------------------------------------------------------------------------------- the table
+def test_every_table_entry_has_a_case():
+    """every (row, instance, entry point) the table declares is named by a case list of this file.  The instances of a row
+    for the paired entry: plain, fp8 (RAMP_TILE_FP8), tail (RAMP_TILE_TAIL); the single entry has no fp8 flag and no skip
+    argument, so it reaches a row's plain instance only.  (The drivers assert that a case reaches what it names.)"""
+    t = table()
+    declared = set()
+    for i, r in enumerate(t):
+        if r[6] & PAIRED:
+            declared |= {(i, PLAIN, PAIRED)} | {(i, v, PAIRED) for v in (FP8, TAIL) if r[6] & v}
+        if r[6] & SINGLE:
+            declared.add((i, PLAIN, SINGLE))
+    named = set()
+    for cases, variant in ((LAYERS, PLAIN), (TAIL_LAYERS, TAIL), (FP8_LAYERS, FP8), (PAIR_LAYERS, PLAIN)):
+        for c in cases:
+            i = row_of(c[0])
+            named.add((i, variant, PAIRED))
+            if variant == PLAIN and cases is LAYERS and t[i][6] & SINGLE:
+                named.add((i, PLAIN, SINGLE))                # test_plain_output_and_statistics runs the single launch too
+    small = {row_of(k) for k, _ in SMALL_ROWS}
+    print("table: %d rows, %d declared (row, instance, entry point), %d named" % (len(t), len(declared), len(named)))
+    assert declared <= named, sorted(declared - named)
+    assert {i for i, r in enumerate(t) if r[5] == 8} <= small, "a TH = 8 row without its degenerate maps"
+
+
+@torch.no_grad()
+def test_refusals_say_so_before_the_launch():
+    """what ramp_conv2d_nhwc_multi refuses, ramp_conv2d_multi_row refuses with the same code, and nothing is written"""
+    from rampvo_amd import _lib, conv_hip
+    torch.manual_seed(11)
+    convs, x, res = layer(R1S2_32, (32, 64), (9, 16))
+    launch(tower_jobs(x, x, convs, res), 1, 2, expect=_lib.RAMP_EUNSUPPORTED)      # the NT = 4 rows want Cout % 64 == 0
+    convs, x, res = layer(R3_32, (32, 64), (9, 16))
+    t = conv_hip.Tail(producer(9, 16, 32), make_x(9, 16, 32))
+    launch([dict(x=t, conv=convs[0], stats="block")], 3, 1, expect=_lib.RAMP_EUNSUPPORTED)   # a tail wants accumulators
+    convs, x, res = layer((5, 1, 0, 32, 2, 8), (32, 64), (9, 16))
+    launch(tower_jobs(x, x, convs, res), 5, 1, expect=_lib.RAMP_EUNSUPPORTED)      # no 5x5 row
+
+
+# ----------------------------------------------------------------------------------------------------- the layers
+@pytest.mark.parametrize("key,couts,hw", LAYERS, ids=_ids(LAYERS))
+@torch.no_grad()
+def test_plain_output_and_statistics(key, couts, hw):
+    """both towers of the paired launch per element against float64; accumulators against the float64 statistics and
+    bit-identical over three launches; where the row serves the single launch, that launch per element and its per-block
+    partials; on TH = 16 bit equality with the single launches (TH = 8) and the direct kernel"""
+    from rampvo_amd import conv_hip
+    torch.manual_seed(2)
+    k, stride, _, cin = key[:4]
+    name = _name(key, couts, hw)
+    convs, x, res = layer(key, couts, hw)
+    dual = key == R7x7 and couts == (32, 32)
+    outs = launch(tower_jobs(x, x, convs, res), k, stride, label=(key, PLAIN, dual))
+    ex0, m0 = check_towers(name, key, outs, x.half(), convs, res)
+    for _ in range(2):
+        again = launch(tower_jobs(x, x, convs, res), k, stride)
+        assert torch.equal(again[0]["acc"], outs[0]["acc"]) and torch.equal(again[0]["y"], outs[0]["y"])
+        assert torch.equal(again[1]["y"], outs[1]["y"])
+    if table()[row_of(key)][6] & SINGLE:
+        y, st = launch_single(x, convs[0], key)
+        rr.check_rounded(y, ex0, m0, "fp16", (15 if cin == 16 else cin) * k * k, name + " single")
+        s = st.double().sum(-1) / (ex0.shape[0] * ex0.shape[1])
+        check_stats(name, "per-block partials", s[:, 0], s[:, 1] - s[:, 0] ** 2, ex0)
+        assert torch.equal(y, outs[0]["y"])                  # one accumulation order in both entry points
+    if key[5] == 16:
+        for direct in (False, True):
+            assert torch.equal(outs[0]["y"], conv_hip.conv2d(x, convs[0], half=True, direct=direct))
+            assert torch.equal(outs[1]["y"], conv_hip.conv2d(x, convs[1], res=res, relu=True, out_scale=0.25, half=True,
+                                                              direct=direct))
+
+
+@pytest.mark.parametrize("key,couts,hw", LAYERS, ids=_ids(LAYERS))
+@torch.no_grad()
+def test_prologues(key, couts, hw):
+    """relu(x scale + shift) on the load path: through pre_scale / pre_shift (operand: the same fp32 expression, rounded
+    to fp16) and through the producer's accumulators `acc_in` (operand: ramp_affine_relu_f16 on the same accumulators,
+    itself checked against float64 from the accumulators' integers)"""
+    torch.manual_seed(3)
+    k, stride, first, cin = key[:4]
+    name = _name(key, couts, hw)
+    convs, x, res = layer(key, couts, hw)
+    sc, sh = torch.rand(cin, device="cuda") + 0.5, torch.randn(cin, device="cuda") * 0.1
+    xq = torch.relu(x.float() * sc + sh).half()
+    if cin == 16:
+        xq[..., 15] = 0
+    # (the dual kernel takes no prologue: two 32-channel first layers with one go to the 7x7 row)
+    outs = launch(tower_jobs(x, x, convs, res, pre=(sc, sh)), k, stride, label=(key, PLAIN, False))
+    check_towers(name + " pre", key, outs, xq, convs, res)
+    if not first:
+        p0, p1 = producer(hw[0], hw[1], cin), producer(hw[0], hw[1], cin)
+        ops = normalised(p0, name + " t0"), normalised(p1, name + " t1")
+        outs = launch(tower_jobs(p0, p1, convs, res), k, stride, label=(key, PLAIN, False))
+        check_towers(name + " acc_in", key, outs, ops, convs, res)
+
+
+@pytest.mark.parametrize("form", SKIP_FORMS)
+@pytest.mark.parametrize("key,couts,hw", TAIL_LAYERS, ids=_ids(TAIL_LAYERS))
+@torch.no_grad()
+def test_fused_tail(key, couts, hw, form):
+    """tower 0 reads a fused residual-block tail fp16(relu(relu(norm(y)) + skip')), tower 1 of the same (TAIL) instance a
+    plain accumulator-mode input.  The tail pixel -- `mat` for stride 1, where it must also equal
+    ramp_norm_add_relu_f16_acc's output bit for bit and leave no pixel unwritten; that unfused launch for stride 2, which
+    writes no `mat` -- against float64; the conv output against float64 on that pixel"""
+    from rampvo_amd import conv_hip
+    torch.manual_seed(4)
+    k, stride, _, cin = key[:4]
+    H, W = hw
+    name = _name(key, couts, hw) + " skip=" + form
+    convs, _, res = layer(key, couts, hw)
+    y, other = producer(H, W, cin), producer(H, W, cin)
+    _, _, sc, sh = rr.acc_stats(y.acc, cin, y.count, y.eps)
+    if form == "tensor":
+        skip = make_x(H, W, cin)
+        e, m = rr.tail_ref(y.raw, sc, sh, skip)
+    else:
+        skip = fresh(producer(H, W, cin), relu=form == "norm_relu")
+        _, _, s2, h2 = rr.acc_stats(skip.acc, cin, skip.count, skip.eps)
+        if form == "norm":
+            e, m = rr.tail_ref(y.raw, sc, sh, skip.raw, s2, h2)
+        else:       # the inner fp16 rounding of the skip taken from the kernel that writes it out (checked on its own)
+            e, m = rr.tail_ref(y.raw, sc, sh, normalised(skip, name + " skip"))
+    unfused = conv_hip.norm_add_relu(fresh(y), skip, fuse=False)
+    rr.check_rounded(unfused, e, m, "fp16", rr.TAIL_K, name + " unfused pixel")
+    jobs = tower_jobs(conv_hip.Tail(fresh(y), skip), other, convs, res)
+    outs = launch(jobs, k, stride, label=(key, TAIL, False))
+    if stride == 1:
+        mat = outs[0]["mat"]
+        assert not bool((mat == MAT_CANARY).any()), "a pixel of mat was not written"
+        assert torch.equal(mat, unfused)
+        rr.check_rounded(mat, e, m, "fp16", rr.TAIL_K, name + " mat")
+        assert "mat" not in outs[1]
+    else:
+        assert "mat" not in outs[0]
+        mat = unfused
+    check_towers(name, key, outs, (mat, normalised(other, name + " t1")), convs, res)
+    if stride == 1:                                           # keep = False: the same output without the write
+        again = launch([dict(jobs[0], mat=False), jobs[1]], k, stride, label=(key, TAIL, False))
+        assert "mat" not in again[0] and torch.equal(again[0]["y"], outs[0]["y"]) and torch.equal(again[0]["acc"], outs[0]["acc"])
+
+
+@pytest.mark.parametrize("key,couts,hw,c0", PAIR_LAYERS, ids=_ids(PAIR_LAYERS))
+@torch.no_grad()
+def test_two_source_input(key, couts, hw, c0):
+    """channels [0, c0) from x, [c0, Cin) from x2: float64 of the concatenation"""
+    torch.manual_seed(5)
+    k, stride, _, cin = key[:4]
+    convs, _, res = layer(key, couts, hw)
+    a, b = make_x(hw[0], hw[1], c0), make_x(hw[0], hw[1], cin - c0, gain=0.5)
+    outs = launch(tower_jobs(a, a, convs, res, x2=b), k, stride, label=(key, PLAIN, False))
+    check_towers(_name(key, couts, hw) + " two-source", key, outs, torch.cat((a, b), dim=-1), convs, res)
+
+
+@pytest.mark.parametrize("key,couts,hw", FP8_LAYERS, ids=_ids(FP8_LAYERS))
+@torch.no_grad()
+def test_fp8_instance(key, couts, hw):
+    """test_conv_fp8_layer_is_fp16_of_the_exact_sum's reference (e4m3 operands, products exact in fp32, roundref.fp8_K) on
+    every row with an fp8 instance: prologue + accumulators for tower 0, ReLU + residual + scale for tower 1.
+
+    Statistics: the accumulators hold the statistics of the kernel's own fp32 values, each within GAMMA(K) m of the exact
+    one (K = roundref.fp8_K, the bound the elements are held to).  On the f16 instances those errors average out over the
+    map (IN_STATS_TOL); on the fp8 instances the statistics sit further from float64: measured on MI355X mean 4.5e-6 ..
+    8.7e-6 and variance 1.3e-6 .. 4.5e-6 of the rms / mean square over the eight rows.  A supposition, not established:
+    the fp8 matrix-core accumulation errs to one side (roundref.py notes that its adder is not documented as
+    round-to-nearest and that fp8 layers went past GAMMA(K) m for a cause not found), so the elements' errors add up
+    where random ones would cancel; the worst case of that, GAMMA(K) mean(m) / rms, would be 9e-5 .. 9e-4.  The bound
+    asserted is FP8_STATS_TOL, about twice the measurement."""
+    from rampvo_amd import conv_hip
+    torch.manual_seed(7)
+    k, stride, _, cin = key[:4]
+    name = _name(key, couts, hw) + " fp8"
+    convs = [make_conv(cin, c, k, stride, rounded=False) for c in couts]
+    x = (torch.randn(hw[0], hw[1], cin, device="cuda") * 1.5).half()
+    x[::4] *= 1e-2
+    sc, sh = torch.rand(cin, device="cuda") + 0.5, torch.randn(cin, device="cuda") * 0.1
+    res = torch.randn(*out_size(hw[0], hw[1], k, stride), couts[1], device="cuda").half()
+    jobs = [dict(x=x, conv=convs[0], pre=(sc, sh), stats="acc"), dict(x=x, conv=convs[1], relu=True, res=res, out_scale=0.25)]
+    outs = launch(jobs, k, stride, fp8=True, label=(key, FP8, False))
+    K = rr.fp8_K(cin * k * k)
+
+    def ref(xin, conv):
+        a = rr.FP8_ACT_SCALE
+        xq = rr.e4m3(xin, a)                                  # scaled e4m3 values
+        ws = float(np.float32(448.0 / float(conv.weight.abs().max())))
+        wq = (conv.weight.float() * ws).clamp(-448, 448).to(torch.float8_e4m3fn).double()   # conv_hip.pack_conv_weight
+        ex, m = rr.conv_ref(xq, wq, None, conv.stride, conv.padding)
+        d, b = 1.0 / (a * ws), conv.bias.double()
+        return ex * d + b, m * d + b.abs()
+    e0, m0 = ref(torch.relu(x.float() * sc + sh), convs[0])
+    e1, m1 = ref(x.float(), convs[1])
+    rr.check_rounded(outs[0]["y"], e0, m0, "fp16", K, name + " t0")
+    rr.check_rounded(outs[1]["y"], torch.relu(torch.relu(e1) + res.double()) * 0.25, (m1 + res.double().abs()) * 0.25,
+                     "fp16", K + 2, name + " t1")
+    mean, var, _, _ = rr.acc_stats(outs[0]["acc"], couts[0], e0.shape[0] * e0.shape[1], 1e-5)
+    check_stats(name, "accumulators", mean, var, e0, FP8_STATS_TOL)
+    assert conv_hip.FP8_ACT_SCALE == rr.FP8_ACT_SCALE
+
+
+@pytest.mark.parametrize("hw", SMALL_MAPS, ids=["%dx%d" % s for s in SMALL_MAPS])
+@pytest.mark.parametrize("key,couts", SMALL_ROWS, ids=[_name(k, c, (0, 0)).rsplit(" ", 1)[0].replace(" ", "_") for k, c in SMALL_ROWS])
+@torch.no_grad()
+def test_degenerate_maps(key, couts, hw):
+    """maps smaller than a tile, than the filter, with one output row or column: the halo is mostly padding and most of
+    the workgroup is masked.  Plain paired launch (both towers, accumulators), the single launch where the row serves it,
+    the accumulator prologue, and the fused tail (normalised skip) where the row has one.  conv_layer rejects no map with
+    H, W >= 1; the size it does reject is asserted.
+
+    Statistics: a channel of a map this small can have an rms of 1e-5 (row 0 is one of the rows scaled by 1e-2), and the
+    accumulators resolve 2^-20, so their error in IN_STATS_TOL's units goes far past it (measured on MI355X: mean up to
+    3.3e-2, variance up to 4.1e-2).  What the fixed point allows is derived in fixed_point_allowance and granted per
+    channel; behind it the accumulators are held to IN_STATS_TOL itself (measured: mean <= 1.7e-7, variance <= 1.8e-7).
+    The single launch's fp32 partials have no fixed point; on a map with one or a few output pixels nothing averages out,
+    and where a pixel's value nearly cancels its own fp32 accumulation error is the statistic's: SMALL_MAP_PARTIALS_TOL,
+    about twice the measurement"""
+    from rampvo_amd import _lib, conv_hip
+    torch.manual_seed(6)
+    k, stride, first, cin = key[:4]
+    H, W = hw
+    name = _name(key, couts, hw)
+    convs, x, res = layer(key, couts, hw)
+    outs = launch(tower_jobs(x, x, convs, res), k, stride, label=(key, PLAIN, False))
+    ex0, _ = check_towers(name, key, outs, x.half(), convs, res, fixed_point=True)
+    if table()[row_of(key)][6] & SINGLE:
+        y, st = launch_single(x, convs[0], key)
+        assert torch.equal(y, outs[0]["y"])
+        s = st.double().sum(-1) / (ex0.shape[0] * ex0.shape[1])
+        check_stats(name, "per-block partials", s[:, 0], s[:, 1] - s[:, 0] ** 2, ex0, SMALL_MAP_PARTIALS_TOL)
+    if not first:
+        p0, p1 = producer(H, W, cin), producer(H, W, cin)
+        ops = normalised(p0, name + " t0"), normalised(p1, name + " t1")
+        outs = launch(tower_jobs(p0, p1, convs, res), k, stride, label=(key, PLAIN, False))
+        check_towers(name + " acc_in", key, outs, ops, convs, res, fixed_point=True)
+        if table()[row_of(key)][6] & TAIL:
+            skip = fresh(producer(H, W, cin), relu=False)
+            unfused = conv_hip.norm_add_relu(fresh(p0), skip, fuse=False)
+            outs = launch(tower_jobs(conv_hip.Tail(fresh(p0), skip), p1, convs, res), k, stride, label=(key, TAIL, False))
+            if stride == 1:
+                assert torch.equal(outs[0]["mat"], unfused)
+            check_towers(name + " tail", key, outs, (unfused, ops[1]), convs, res, fixed_point=True)
+    # the one size conv_layer's callers reject: no rows or no columns
+    arr = (conv_hip.ConvJob * 1)()
+    assert _lib.lib().ramp_conv2d_multi_row(arr, 1, 0, W, cin, k, stride, _lib.RAMP_F16) == -1            # RAMP_EINVAL
+    assert _lib.lib().ramp_conv2d_nhwc_multi(arr, 1, H, 0, cin, k, stride, _lib.RAMP_F16, None) == -1

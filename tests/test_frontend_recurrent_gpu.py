@@ -15,12 +15,10 @@ import torch
 
 import georef
 import lstmref as lr
+from guarded import DIRTY, Guarded
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-CANARY = 12345.0
-DIRTY = 1e30
 _nets, _refs = {}, {}
 
 
@@ -50,20 +48,6 @@ def ss_case(gain, HW):
         steps = lr.ss_inputs(HW)
         _refs[key] = (steps, lr.ss_reference(nets(gain)["wss"], steps))
     return _refs[key]
-
-
-class Guarded:
-    """``rows`` x ``cols`` between GUARD canary rows on either side"""
-
-    def __init__(self, rows, cols, dtype=torch.float32, fill=DIRTY, canary=CANARY):
-        self.buf = torch.full((rows + 2 * GUARD, cols), canary, dtype=dtype, device="cuda")
-        self.t = self.buf[GUARD:GUARD + rows]
-        self.t.fill_(fill)
-        self.rows, self.canary = rows, canary
-
-    def intact(self):
-        c = torch.full_like(self.buf[:GUARD], self.canary)
-        return torch.equal(self.buf[:GUARD], c) and torch.equal(self.buf[GUARD + self.rows:], c)
 
 
 def _lib():

@@ -104,6 +104,136 @@ def test_check_rounded_accepts_a_correct_conv_and_rejects_mutations():
     assert _old_ok(mutants["rounded toward zero"], ex) and _old_ok(mutants["small biases dropped"], ex)
 
 
+# ------------------------------------------------------------------- the conv towers' tiled kernel (test_conv_instances_gpu.py)
+def _acc_of(x, tile_rows=8, tile_cols=16, R=8):
+    """the accumulators a layer leaves for its raw output x [H, W, C] (csrc/conv.hip::conv_tile_epilogue): per 8 x 16 tile
+    the fp32 sums of x and x^2, as 2^-20 fixed-point integers, added to replica (tile index % R) -> [R][C][2] int64"""
+    H, W, C = x.shape
+    acc = torch.zeros(R, C, 2, dtype=torch.int64)
+    t = 0
+    for y0 in range(0, H, tile_rows):
+        for x0 in range(0, W, tile_cols):
+            v = x[y0:y0 + tile_rows, x0:x0 + tile_cols].float().reshape(-1, C)
+            s = torch.stack([v.sum(0), (v * v).sum(0)], dim=1)
+            acc[t % R] += torch.round(s.double() * rr.IN_ACC_ONE).to(torch.int64)
+            t += 1
+    return acc
+
+
+def _tail_case():
+    g = torch.Generator().manual_seed(5)
+    H, W, C = 11, 19, 32                                     # two tile rows, two tile columns, both ragged
+    y = (torch.randn(H, W, C, generator=g) * 0.6 + 0.2).half()
+    skip = (torch.randn(H, W, C, generator=g) * 0.8 - 0.1).half()
+    return y, skip, _acc_of(y), _acc_of(skip), float(H * W)
+
+
+def test_accumulator_statistics_and_tail_pixel_match_a_plain_torch_evaluation():
+    """roundref.acc_stats / tail_ref on a tiny map against F.instance_norm and the written-out expression in float64: the
+    statistics agree to the accumulators' resolution (2^-21 per tile and sum, 4 tiles over 209 pixels), the tail pixel
+    formed with torch's own statistics to that resolution times the scale"""
+    y, skip, acc_y, acc_s, n = _tail_case()
+    C = y.shape[-1]
+    mean, var, sc, sh = rr.acc_stats(acc_y, C, n, 1e-5)
+    yd = y.double()
+    res = 4 * 2.0 ** -21 / n
+    assert float((mean - yd.mean((0, 1))).abs().max()) <= res + 1e-7 * float(yd.abs().max())     # (+ the tiles' fp32 sums)
+    assert float((var - yd.var((0, 1), unbiased=False)).abs().max()) <= 4 * res + 1e-6
+    assert torch.equal(sh, -mean * sc) and float((sc - 1.0 / torch.sqrt(var + float(torch.tensor(1e-5)))).abs().max()) == 0.0
+    norm = lambda t: F.instance_norm(t.double().permute(2, 0, 1)[None], eps=1e-5)[0].permute(1, 2, 0)
+    _, _, s2, h2 = rr.acc_stats(acc_s, C, n, 1e-5)
+    forms = {
+        "tensor": (rr.tail_ref(y, sc, sh, skip), torch.relu(torch.relu(norm(y)) + skip.double())),
+        "norm": (rr.tail_ref(y, sc, sh, skip, s2, h2), torch.relu(torch.relu(norm(y)) + norm(skip))),
+        "norm_relu": (rr.tail_ref(y, sc, sh, skip, s2, h2, skip_relu=True),
+                      torch.relu(torch.relu(norm(y)) + torch.relu(norm(skip)))),
+    }
+    for name, ((e, m), plain) in forms.items():
+        tol = 2e-5 if name != "norm_relu" else 2e-5 + 2.0 ** -11 * float(plain.max())     # (the inner fp16 rounding)
+        assert float((e - plain).abs().max()) <= tol, name
+        assert bool((m >= e.abs() - 1e-12).all()), name
+    # the prologue's operand
+    e, m = rr.norm_relu_ref(y, sc, sh)
+    assert float((e - torch.relu(norm(y))).abs().max()) <= 2e-5 and bool((m >= e).all())
+
+
+def test_tail_reference_accepts_the_fp32_evaluation_and_rejects_its_defects():
+    """the tail pixel as the kernels form it (fp32 scale and shift from the accumulators, fp32 arithmetic, one rounding to
+    fp16; the normalised-and-ReLU'd skip rounded once more) is accepted with zero unexplained elements by the float64
+    reference alone; without the inner ReLU, or with the skip's normalisation dropped, it is rejected -- by check_rounded
+    and by the bit equality with the unfused kernel's output that the GPU test also asserts"""
+    y, skip, acc_y, acc_s, n = _tail_case()
+    C = y.shape[-1]
+    _, _, sc, sh = rr.acc_stats(acc_y, C, n, 1e-5)
+    _, _, s2, h2 = rr.acc_stats(acc_s, C, n, 1e-5)
+    f = lambda t: t.float()
+
+    def kernel(inner_relu=True, skip_norm=True, skip_relu=False):
+        a = f(y) * f(sc) + f(sh)
+        if inner_relu:
+            a = torch.relu(a)
+        b = f(skip) * f(s2) + f(h2) if skip_norm else f(skip)
+        if skip_relu:
+            b = torch.relu(b).half().float()
+        return torch.relu(a + b).half()
+    for relu in (False, True):
+        e, m = rr.tail_ref(y, sc, sh, skip, s2, h2, skip_relu=relu)
+        good = kernel(skip_relu=relu)
+        assert _bad(good, e, m, rr.TAIL_K) == 0
+        for name, kw in (("inner ReLU skipped", dict(inner_relu=False)), ("skip's normalisation dropped", dict(skip_norm=False))):
+            bad = kernel(skip_relu=relu, **kw)
+            rep = rr.rounding_report(bad, e, m, "fp16", rr.TAIL_K)
+            print("tail mutant %-30s (skip relu %d) unexplained %5d of %d" % (name, relu, rep["bad"], rep["n"]))
+            assert rep["bad"] > 0 and not torch.equal(bad, good), name
+    e, m = rr.tail_ref(y, sc, sh, skip)
+    assert _bad(kernel(skip_norm=False), e, m, rr.TAIL_K) == 0          # a plain tensor skip: that IS the expression
+    e, m = rr.norm_relu_ref(y, sc, sh)
+    assert _bad(torch.relu(f(y) * f(sc) + f(sh)).half(), e, m, rr.NORM_K) == 0
+    assert _bad((f(y) * f(sc) + f(sh)).half(), e, m, rr.NORM_K) > 0
+
+
+@pytest.mark.parametrize("k,stride,hw", [(3, 1, (11, 19)), (3, 2, (21, 37)), (1, 2, (21, 37)), (7, 2, (21, 37))])
+def test_conv_reference_rejects_the_tiled_kernels_defects(k, stride, hw):
+    """a tiled layer emulated in fp32 on a ragged map (two tile rows, two tile columns of 8 x 16 output pixels), one defect
+    at a time: the last live row of the ragged bottom tile zeroed; the halo column left of the image taken from the
+    neighbouring pixel where it should be padding; one of the tiny biases (roundref.TINY_BIASES,
+    the smallest) dropped.  check_rounded rejects
+    each and accepts the undamaged emulation with zero unexplained elements"""
+    g = torch.Generator().manual_seed(8)
+    cin, cout = (15, 32) if k == 7 else (32, 32)
+    conv = nn.Conv2d(cin, cout, k, stride=stride, padding=k // 2)
+    with torch.no_grad():
+        conv.weight.copy_(conv.weight.half().float())
+        conv.bias.copy_(conv.bias.half().float())
+        conv.bias[:4] = torch.tensor(rr.TINY_BIASES).half().float()      # test_conv_instances_gpu.py::make_conv's
+    w, b = conv.weight.detach(), conv.bias.detach()
+    x = torch.randn(hw[0], hw[1], cin, generator=g)
+    x[::4] *= 1e-2
+    x = x.half().float()
+    ex, m = rr.conv_ref(x, w, b, stride, k // 2)
+    K = cin * k * k
+    nchw = x.permute(2, 0, 1)[None]
+    run = lambda inp, pad, bias: F.conv2d(inp, w, bias, stride, pad)[0].permute(1, 2, 0)
+    good = run(nchw, k // 2, b).half()
+    assert 8 < good.shape[0] < 16 and 16 < good.shape[1] < 32 and good.shape[0] % 8 and good.shape[1] % 16
+    assert _bad(good, ex, m, K) == 0
+    mutants = {}
+    row = good.clone()
+    row[-1] = 0
+    mutants["last live row of the ragged tile zeroed"] = row
+    bdrop = b.clone()
+    bdrop[1] = 0                                             # the smallest of the tiny biases
+    mutants["smallest tiny bias dropped"] = run(nchw, k // 2, bdrop).half()
+    if k > 1:
+        p = k // 2
+        halo = F.pad(F.pad(nchw, (p, 0, 0, 0), mode="replicate"), (0, p, p, p))
+        mutants["halo column from the neighbouring pixel"] = run(halo, 0, b).half()
+    for name, y in mutants.items():
+        rep = rr.rounding_report(y, ex, m, "fp16", K)
+        print("conv %dx%d s%d mutant %-42s unexplained %5d of %d" % (k, k, stride, name, rep["bad"], rep["n"]))
+        assert y.shape == good.shape and rep["bad"] > 0, name
+
+
 @pytest.fixture(scope="module")
 def gru_case():
     from rampvo_amd.synthetic import make_network
