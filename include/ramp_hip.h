@@ -662,6 +662,11 @@ int ramp_upd_gru_heads(const float *x32, const void *add_t, const int32_t *add_i
                        float pre_eps, const void *const *wp_host, const float *const *bias_host, const float *ln_w,
                        const float *ln_b, float eps, float *out32, const void *heads_w, const float *heads_b,
                        const float *coords, float *target, float *weight, int E, int P, float wd, float ht, void *stream);
+/* Rows per workgroup (64 or 80) of the gru launch for E factors, the rule the launch itself applies: the tile that needs fewer
+ * rounds of one workgroup per CU (ties: 64; CU count of the current device, 256 without one).  E_hint: the caller's estimate
+ * of the live count where E is only a launch bound (the device-resident step) -- it replaces E when 0 < E_hint < E.  The
+ * frame pipeline asks this to place the next frame's front end around the launch (rampvo_amd/frame_pipeline.py).         */
+int ramp_upd_gru_tile_rows(int E, int E_hint);
 size_t ramp_upd_mlp_lds_bytes(void);
 
 /* net_out[e] = net_in[e] + Lb(relu(La(idx[e] >= 0 ? net_in[idx[e]] : 0)))  -- the temporal-neighbour MLPs

@@ -256,13 +256,6 @@ class RampVoCPU(Ramp_vo):
     def _layout_flags(self, h, w):
         return False, False            # plain NHWC ring slots; the hidden state is compacted eagerly like the reference's
 
-    def _init_streams(self, dev):
-        self._fe_stream = self._ev_fe_done = self._ev_gate = self._ev_in = None
-        self._gate_armed = False
-
-    def _current_stream(self):
-        return None
-
     def corr(self, coords, indicies=None, order=None):
         ii, jj = indicies if indicies is not None else (self.kk, self.jj)
         ii1 = ii % (self.M * self.mem)                      # reference Ramp_vo.py:178-179

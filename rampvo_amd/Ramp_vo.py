@@ -25,7 +25,6 @@ MI355X-first differences that do not change results:
 """
 from collections import OrderedDict
 
-import ctypes
 import warnings
 
 import numpy as np
@@ -38,46 +37,13 @@ from . import _lib
 from ._lib import RAMP_NHWC, RAMP_NHWC32, kplane
 from .update_fused import CORR_ROW
 from .lietorch import SE3
+from .frame_pipeline import FramePipeline, NoPipeline
 from .net import GraphPlan, VONet
 from .queries import TrackerQueries
 from .utils import Timer, preprocess_input
 
 
-_CUS = {}
-
-
-def _gru_tile_rows(E, device):
-    """rows per workgroup ramp_upd_gru picks for E factors (csrc/update_mlp.hip: the tile that needs fewer rounds of one
-    workgroup per CU)"""
-    key = str(device)
-    if key not in _CUS:
-        _CUS[key] = torch.cuda.get_device_properties(device).multi_processor_count
-    cus = _CUS[key]
-    r4 = -(-(-(-E // 64)) // cus) * 4
-    r5 = -(-(-(-E // 80)) // cus) * 5
-    return 80 if r5 < r4 else 64
-
-
-_FE_DELAY_US = 35          # the encoder graph held back behind the selection (_fe_delay; 0 measured flat, DESIGN.md)
-_GATE_FLAG_DELAY_US = 0
-_FE_WAIT_PROBE = False      # (diagnostic, set by tools/fe_wait.py before the tracker is built: events around the main queue's wait for the front end)
-# The front end's "done" is a data dependency (the frame commit reads fe_fmap1 / imap / gmap / patches): the wave that waits
-# for its signal word must not give up while the producer can still arrive.  The time-out is a hang guard only -- 20 s, far
-# beyond any profiler slow-down -- and a wait that does give up still raises sticky status bit 128, on which settle() /
-# lazy_state() raise.  Runtimes that serialise kernels never get here (switches.Switches.flag_waits: events instead).  The gate
-# wait (_gate_wait) keeps its 50 ms: it orders nothing but timing (a front end that starts early is slower, not wrong).
-_FE_DONE_TIMEOUT_US = 20000000
-
-
-_LIVE = {}        # device index -> trackers alive on it (Ramp_vo._flag_wait_is_safe)
-
-
-def _live_dec(idx):
-    _LIVE[idx] = _LIVE.get(idx, 1) - 1
-
-
 class Ramp_vo(TrackerQueries):
-    _main_used = False      # work queued on the tracker's own stream (_init_streams; a subclass without streams never has any)
     def __init__(self, cfg, network, train_cfg, ht=480, wd=640, device="cuda"):
         self.cfg = cfg
         self.event_bias = train_cfg["event_bias"]
@@ -90,11 +56,6 @@ class Ramp_vo(TrackerQueries):
         # driven, hand-backs to the host (settle), waits of the host for the GPU (track_dev.DeviceTrack.throttle)
         self.stats = dict(device_frames=0, host_frames=0, settles=0, throttle_waits=0, throttle_s=0.0)
         hostenv.fit_host_threads()          # (once per process) a host thread pool larger than the container's CPU quota: see there
-        import weakref
-        idx = dev.index if dev.index is not None else (torch.cuda.current_device() if dev.type == "cuda" else -1)
-        self._live_idx = idx
-        _LIVE[idx] = _LIVE.get(idx, 0) + 1
-        weakref.finalize(self, _live_dec, idx)
 
         self._dev = None                # DeviceTrack while the steady state is device resident
         self._pose_ring = None          # track_dev.PoseRing once pose_stream() has switched publishing on
@@ -151,35 +112,18 @@ class Ramp_vo(TrackerQueries):
         self._net_map = None                     # host int64 [E]: row of _net_buf per current edge (-1: zeros)
         self._net_map_dev = None
         self._ixm = None
-        # Frame pipelining (opt-in): the caller guarantees that the tensors it hands to __call__ are complete (not
-        # still being produced on the current stream).  In the device-resident steady state the next frame's front
-        # end is then launched on a side stream, gated by an event recorded before the last kernel of the previous
-        # frame's update operator: it runs next to the gru chain and BA (a few small blocks on a 256-CU chip).
-        # inputs_ready = "stream" (round 5): the same pipelining for callers whose tensors ARE still being produced on the
-        # current stream when they call (the reference's evaluate.py resizes each frame right before slam(...)): the tracker
-        # records an event on the caller's stream, its front end waits for THAT, and everything else of the tracker runs on
-        # the tracker's own stream (_main_stream) -- so the caller's stream carries the caller's work only and the next
-        # frame's inputs are not queued behind this frame's bundle adjustment.  The caller's stream in turn waits until the
-        # front end has taken its copy of the inputs (they may be overwritten or freed right after the call, as on one
-        # stream).  Same contract for reading state as with True: through settle() / update() / terminate() / peek() /
-        # state_dict() / the n, m, ii ... properties, which join the tracker's stream first.  rampvo_amd.evaluate.run sets it.
-        # RAMP_INPUTS_READY=stream|1 sets the default without touching the caller's code (the reference's evaluate.py with
-        # its imports redirected: it reads points_ / colors_ / m only behind its closing update() calls, which join).
+        # frame pipelining (opt-in; the contract: frame_pipeline.py): False, True or "stream"
         sw = switches.read()
         self.inputs_ready = sw.inputs_ready
         self.device_steps = sw.device_step       # A/B and test switch
-        # cross-stream orders as signal words looked at by a sleeping wave (False: events -- RAMP_NO_FLAG_WAITS, or a
-        # runtime that runs one kernel at a time, where the waiting wave would keep its producer off the GPU: ADVICE r4)
-        self._flag_waits = sw.flag_waits
+        self._pipe = self._make_pipeline(dev, sw.flag_waits)     # streams, events and signal words of the frames: who waits for whom
         self._edge_tmpl = None
         self._shift_plan = None
-        self._cur_stream = None
         self._corr_levels = None
         self._fc_plan = None           # (front-end outputs, patches, FrameCommitPlan or None)
         self._warned_slow = False
         self._extra_step_flags = 0     # (measurement: track_dev.WRAP_COORDS, bench.py's live-factor leg)
         self._ba_flags = 0             # bits of fastba's info seen so far (1: a pose step was dropped, 2: pair list overflow)
-        self._init_streams(dev)
         self._net_buf = torch.zeros(1, 0, DIM, dtype=torch.float, device=dev)   # hidden state is fp32 (as under autocast)
         self._dii = torch.zeros(0, dtype=torch.long, device=dev)
         self._djj = torch.zeros(0, dtype=torch.long, device=dev)
@@ -240,20 +184,14 @@ class Ramp_vo(TrackerQueries):
                           "1/4 resolution): plain NHWC slots and the slower correlation kernel" % (w, h))
         return chunked, True
 
-    def _init_streams(self, dev):
-        self._fe_stream = torch.cuda.Stream(device=dev)
-        self._main_stream = torch.cuda.Stream(device=dev)     # inputs_ready = "stream": the tracker's own main stream
-        self._main_used, self._user_dirty = False, True
-        self._ev_taken = torch.cuda.Event()
-        # events are re-recorded every frame (creating one costs a hipEventCreate/Destroy pair per use)
-        self._fe_done_sig, self._fe_done_seq = None, 0
-        self._ev_fe_done, self._ev_gate, self._ev_in = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
-        for ev in (self._ev_fe_done, self._ev_gate, self._ev_in):
-            ev.record()                      # torch creates the hipEvent lazily; csrc/track.hip records the raw handle
-        self._gate_armed = False
-        # the gate as a signal word the step stores a sequence number into (no event packet between the update
-        # operator's launches: tools/mb/stream_signal.hip)
-        self._gate_sig, self._gate_seq, self._gate_by_flag = None, 0, False
+    def _make_pipeline(self, dev, flag_waits):
+        return FramePipeline(dev, flag_waits) if dev.type == "cuda" else NoPipeline()    # (no streams: the tests' CPU twin)
+
+    # (names that queries.py, bench.py and the tests read on the tracker)
+    _main_used = property(lambda self: self._pipe.main_used)
+    _main_stream = property(lambda self: self._pipe.main_stream)
+    _gate_by_flag = property(lambda self: self._pipe.gate_by_flag)
+    _join_main = property(lambda self: self._pipe.join_main)
 
     # ------------------------------------------------------------------ weights
     def load_weights(self, network):
@@ -329,7 +267,7 @@ class Ramp_vo(TrackerQueries):
         """bring the host mirror up to date: if the steady state is device resident, synchronise and take the
         keyframe count, the factor graph, the hidden-state row map and the delta chain back (the next tracked frame
         runs host-driven and hands the state over again)"""
-        self._join_main()
+        self._pipe.join_main()
         dv = self._dev
         if dv is None or not dv.active:
             return
@@ -363,7 +301,7 @@ class Ramp_vo(TrackerQueries):
     def peek(self):
         """(keyframes, factors) right now -- synchronises, but leaves a device-resident state where it is (tests and
         benchmarks read these per frame; ``n`` / ``_ii`` would hand the state back to the host every time)"""
-        self._join_main()
+        self._pipe.join_main()
         dv = self._dev
         if dv is not None and dv.active:
             torch.cuda.current_stream().synchronize()
@@ -683,8 +621,8 @@ class Ramp_vo(TrackerQueries):
     # ------------------------------------------------------------------- update
     def update(self):
         """reference :276-310 (host-driven form; the device-resident step runs the same operator sequence)"""
-        if self._cur_stream is None:                 # (a public call, not the tracked frame's own update)
-            self._join_main()
+        if self._pipe.cur_stream is None:            # (a public call, not the tracked frame's own update)
+            self._pipe.join_main()
         with Timer("other", enabled=self.enable_timing):
             plan = self._graph_plan()
             coords = self.reproject()
@@ -724,71 +662,22 @@ class Ramp_vo(TrackerQueries):
     def __call__(self, tstamp, input_tensor, intrinsics):
         """track a new frame"""
         input_ = preprocess_input(input_tensor=input_tensor)
+        frame = lambda: self._frame(tstamp, input_, intrinsics)
         with torch.no_grad():
             if self.inputs_ready == "stream" and self.device.type == "cuda":
-                return self._call_on_own_stream(tstamp, input_, intrinsics)
-            self._join_main()
-            self._cur_stream = self._current_stream()
-            try:
-                if self._dev is not None and self._dev.active:
-                    self.stats["device_frames"] += 1
-                    return self._track_device(tstamp, input_, intrinsics)
-                self.stats["host_frames"] += 1
-                return self._track(tstamp, input_, intrinsics)
-            finally:
-                self._cur_stream = None
+                return self._pipe.on_own_stream(input_, self._dev is not None and self._dev.active, frame)
+            return self._pipe.on_caller_stream(frame)
 
-    def _call_on_own_stream(self, tstamp, input_, intrinsics):
-        """inputs_ready = "stream": see __init__.  The caller's stream gets one event record and one event wait per frame."""
-        user, main, fe = torch.cuda.current_stream(self.device), self._main_stream, self._fe_stream
-        self._ev_in.record(user)                        # the inputs (and whatever else the caller enqueued) up to here
-        for t in input_[:2]:
-            if torch.is_tensor(t) and t.is_cuda:        # allocated on the caller's stream, read on the tracker's
-                t.record_stream(main)
-                t.record_stream(fe)
-        # the main stream itself waits for the caller's stream only when it has to: after a public call ran tracker work
-        # there (update(), settle() ...: _join_main marks it), or when this frame's front end runs on the main stream (no
-        # gate armed: host-driven frames, the first device-resident one) -- in the steady state the front-end stream's wait
-        # is the only one, and the main stream keeps no event packet between two frames
-        gated = self._dev is not None and self._dev.active and self._gate_armed
-        if self._user_dirty or not gated:
-            main.wait_event(self._ev_in)
-            self._user_dirty = False
-        self._in_event_pending, self._taken_recorded = True, False
-        self._cur_stream = main
-        try:
-            with torch.cuda.stream(main):
-                if self._dev is not None and self._dev.active:
-                    self.stats["device_frames"] += 1
-                    out = self._track_device(tstamp, input_, intrinsics)
-                else:
-                    self.stats["host_frames"] += 1
-                    out = self._track(tstamp, input_, intrinsics)
-        finally:
-            self._cur_stream = None
-            self._in_event_pending = False
-            self._main_used = True                      # (a settle() inside the call may have joined: there is new work now)
-        # the caller may overwrite / free its tensors once the front end has run on them (a frame whose front end ran on the
-        # tracker's main stream -- host-driven frames -- : once that frame is through)
-        if not self._taken_recorded:
-            self._ev_taken.record(main)
-        user.wait_event(self._ev_taken)
-        return out
+    def _frame(self, tstamp, input_, intrinsics):
+        if self._dev is not None and self._dev.active:
+            self.stats["device_frames"] += 1
+            return self._track_device(tstamp, input_, intrinsics)
+        self.stats["host_frames"] += 1
+        return self._track(tstamp, input_, intrinsics)
 
-    def _join_main(self):
-        """(public entry points that run on the caller's stream) everything the tracker enqueued on its own stream first"""
-        self._user_dirty = True                       # (whatever follows runs tracker work on the caller's stream)
-        if self._main_used:
-            self._main_stream.synchronize()
-            self._fe_stream.synchronize()
-            self._main_used = False
-
-    def _current_stream(self):
-        return torch.cuda.current_stream()
-
-    def _cur(self):
-        """the caller's stream; looked up once per __call__ (torch.cuda.current_stream() costs ~4 us)"""
-        return self._cur_stream if self._cur_stream is not None else torch.cuda.current_stream()
+    def _patchify(self, input_, reinit_hidden=False, **kw):
+        return self.network.patchify(input_=input_, patches_per_image=self.cfg.PATCHES_PER_FRAME, event_bias=self.event_bias,
+                                     reinit_hidden=reinit_hidden, **kw)
 
     def _intrinsics_row(self, intrinsics, accepts):
         """intrinsics at feature resolution.  Returns (kq, k_dev): k_dev is a device [4] tensor when row n needs new
@@ -824,65 +713,16 @@ class Ramp_vo(TrackerQueries):
             return self._k_cuda[self.counter & 1]
         if self._k_cuda is None:
             self._k_cuda = [torch.zeros(4, dtype=torch.float32, device=self.device) for _ in range(2)]
-        cur = self._cur()
-        st = stream if stream is not None else cur
-        if stream is None and getattr(self, "_in_event_pending", False):
-            cur.wait_event(self._ev_in)                 # (a host-driven frame behind a front end that ran on its own stream)
+        st = stream
+        if st is None:
+            st = self._pipe.cur()
+            self._pipe.wait_input()                     # (a host-driven frame behind a front end that ran on its own stream)
         buf = self._k_cuda[self.counter & 1]
         with torch.cuda.stream(st):
             torch.div(intrinsics.detach().reshape(4).to(torch.float32), float(self.RES), out=buf)
         intrinsics.record_stream(st)
         self._k_cuda_for = self.counter
         return buf
-
-    def _gate_signal(self):
-        """the signal word of the gate, or None (no flag waits, no signal memory, or 2^31 frames behind us: the event
-        then).  Where in the step the word is stored: csrc/track.hip (fp16: by the first SoftAgg launch)"""
-        if self._gate_sig is None:
-            with torch.cuda.device(self.device):          # (the word must live on the tracker's GPU, not the caller's current one)
-                self._gate_sig = track_dev.Signal() if self._flag_waits else False
-        sig = self._gate_sig
-        return sig if (sig and sig.ptr is not None and self._gate_seq < 0x7FFFFFF0) else None
-
-    def _fe_done_to(self, fe, cur, dv):
-        """the front end's "done" for the main stream: a word in signal memory stored by a one-thread launch behind the
-        encoder graph and looked at by one sleeping wave in front of the frame commit (no flag waits -- RAMP_NO_FLAG_WAITS,
-        a runtime that serialises kernels -- or no signal memory: an event record + stream wait, ~10 us of
-        packets on the serial chain even when the front end is long done).  The commit READS what the front end wrote, so
-        this wait's time-out is a hang guard (20 s), not a scheduling choice"""
-        if self._fe_done_sig is None:
-            with torch.cuda.device(self.device):
-                self._fe_done_sig = track_dev.Signal() if self._flag_waits else False
-        sig = self._fe_done_sig
-        # A spinning wave needs its producer to run CONCURRENTLY: the runtime maps streams onto a handful of hardware queues,
-        # and a waiter that shares one with its producer would sit in front of it until the hang guard fires.  Two streams of
-        # one tracker (the caller's + the front end's: inputs_ready = True) have been measured safe on every box; with a third
-        # tracker stream (inputs_ready = "stream": _main_stream), or a second tracker in the process, the DATA dependency goes
-        # through an event -- the gate (_gate_wait), which orders timing only, keeps its word (ADVICE r5)
-        if sig and self._flag_wait_is_safe() and sig.ptr is not None and self._fe_done_seq < 0x7FFFFFF0:
-            self._fe_done_seq += 1
-            _lib.check(_lib.lib().ramp_stream_signal(ctypes.c_void_p(fe.cuda_stream), sig.ptr, self._fe_done_seq), "ramp_stream_signal")
-            sig.wait(cur, self._fe_done_seq, timeout_us=_FE_DONE_TIMEOUT_US, status=dv.status_ptr)
-        else:
-            self._ev_fe_done.record(fe)
-            cur.wait_event(self._ev_fe_done)
-
-    def _flag_wait_is_safe(self):
-        return self.inputs_ready is True and _LIVE.get(self._live_idx, 0) <= 1
-
-    def _gate_wait(self, fe):
-        """(front-end stream) wait for the previous frame's gate: the signal word if that step stored one, else the event"""
-        if self._gate_by_flag:
-            self._gate_sig.wait(fe, self._gate_seq, then_delay_us=_GATE_FLAG_DELAY_US,
-                                status=self._dev.status_ptr if self._dev is not None else None)
-        else:
-            fe.wait_event(self._ev_gate)
-
-    def _fe_delay(self):
-        """(on the front-end stream, behind the selection) hold the encoder graph back a little: its LSTM launch should not
-        arrive while the gru launch is still filling the chip (csrc/track.hip::trk_delay_kernel)"""
-        if _FE_DELAY_US > 0:
-            _lib.check(_lib.lib().ramp_stream_delay(_FE_DELAY_US, _lib.stream()), "ramp_stream_delay")
 
     # ----------------------------------------------------- device-resident steady state
     def _track_device(self, tstamp, input_, intrinsics):
@@ -897,48 +737,13 @@ class Ramp_vo(TrackerQueries):
                          or lazy[track_dev.DYN_STATUS] & ~3)):
             self.settle()                           # buffer / log nearly full, or a capacity flag: back to the host
             return self._track(tstamp, input_, intrinsics)
-        cur = self._cur()
-        if self.inputs_ready and self._gate_armed:
-            # the caller's tensors are complete: the front end runs on its own stream, next to what is left of the
-            # previous frame from the gru chain on (the event is recorded inside ramp_track_step)
-            # (the staging copies and the patch selection go out ahead of the gate: they depend on the input alone)
-            fe = self._fe_stream
-            # Where the encoder graph starts relative to the gru launch depends on that launch's tile (csrc/update_mlp.hip
-            # picks 64 or 80 rows per workgroup by the factor count, tools/corun_gru_lstm.py): with 80-row tiles (two full
-            # rounds of one workgroup per CU, 254 VGPRs) the front end's LSTM launch cannot take a CU from it, so the
-            # selection goes out AHEAD of the gate and the graph right behind it; with 64-row tiles an LSTM launch that
-            # arrives within ~40 us costs gru 45 us, so the selection runs behind the gate and the graph is held back
-            # another 35 us (_fe_delay).
-            ahead = _gru_tile_rows(dv.factor_estimate(), self.device) == 80
-            if getattr(self, "_in_event_pending", False):
-                fe.wait_event(self._ev_in)              # inputs_ready = "stream": the caller's stream up to the call
-            if accepts and torch.is_tensor(intrinsics) and intrinsics.is_cuda:
-                self._cuda_intrinsics(intrinsics, stream=fe)   # (behind the caller's stream, ahead of this frame's "done")
-            if not ahead:
-                self._gate_wait(fe)
-            with torch.cuda.stream(fe):
-                out = self.network.patchify(input_=input_, patches_per_image=self.cfg.PATCHES_PER_FRAME,
-                                            event_bias=self.event_bias, reinit_hidden=False,
-                                            pre_replay=(lambda: self._gate_wait(fe)) if ahead else self._fe_delay)
-            if getattr(self, "_in_event_pending", False):
-                self._ev_taken.record(fe)
-                self._taken_recorded = True
-            if _FE_WAIT_PROBE:                      # (diagnostic: how long the main queue waits for the front end)
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record(cur)
-                self._fe_done_to(fe, cur, dv)
-                b.record(cur)
-                self.fe_wait_pairs.append((a, b))
-            else:
-                self._fe_done_to(fe, cur, dv)
-            if not dv.fp32:
-                # (behind the event: the frame does not wait for it) the window's correlation planes back into the
-                # memory-side cache while the previous frame's bundle adjustment is still running
-                with torch.cuda.stream(fe):
-                    dv.warm()
+        pipe, ready = self._pipe, self.inputs_ready
+        if ready and pipe.gate_armed:
+            k_cuda = accepts and torch.is_tensor(intrinsics) and intrinsics.is_cuda     # (converted on that stream too, ahead of the gate)
+            out = pipe.front_end(dv, ready, lambda **kw: self._patchify(input_, **kw),
+                                 (lambda fe: self._cuda_intrinsics(intrinsics, stream=fe)) if k_cuda else None)
         else:
-            out = self.network.patchify(input_=input_, patches_per_image=self.cfg.PATCHES_PER_FRAME,
-                                        event_bias=self.event_bias, reinit_hidden=False)
+            out = self._patchify(input_)
         if not accepts:
             return      # events only: the encoder state has advanced, the VO has not
         patches = out[3]
@@ -969,22 +774,18 @@ class Ramp_vo(TrackerQueries):
             # previous frame's plan wrote -- the GPU is busy with the correlation launch enqueued above meanwhile
             E = int(dv.wait_frame(self.counter - 1)[track_dev.DYN_E])
             self._device_operator_fp32(dv, E)
-            if self.inputs_ready:
-                self._ev_gate.record(cur)                        # the next frame's front end may start (next to BA)
+            if ready:
+                pipe.ev_gate.record(pipe.cur())                  # the next frame's front end may start (next to BA)
             dv.step(self.counter, track_dev.UPDATE_POST | track_dev.KEYFRAME, E_bound=E)
-            self._gate_armed, self._gate_by_flag = self.inputs_ready, False
+            pipe.arm(ready, False)
             if self._pose_ring is not None:
                 self._publish(tstamp, self.counter, dv)
             self.counter += 1
             return
-        sig = self._gate_signal() if self.inputs_ready else None
-        if sig is not None:
-            self._gate_seq += 1
+        gate = pipe.step_gate(ready)
         dv.step(self.counter, track_dev.COMMIT | track_dev.UPDATE | track_dev.KEYFRAME | self._extra_step_flags,
-                k_new=k_new,
-                gate_event=self._ev_gate.cuda_event if (self.inputs_ready and sig is None) else None,
-                gate_flag=sig.ptr if sig is not None else None, gate_seq=self._gate_seq)
-        self._gate_armed, self._gate_by_flag = self.inputs_ready, sig is not None
+                k_new=k_new, **gate)
+        pipe.arm(ready, gate["gate_flag"] is not None)
         if self._pose_ring is not None:
             self._publish(tstamp, self.counter, dv)  # (behind the step: the record carries the keyframe test's outcome)
         self.counter += 1
@@ -1038,17 +839,14 @@ class Ramp_vo(TrackerQueries):
         ok = self._dev.enter(self._hii, self._hjj, self._hkk, self._net_rows(), self._new_edges(n1),
                              self._net_buf[0], self._n)
         if ok:
-            self._gate_armed = False
+            self._pipe.gate_armed = False
             # the device owns these now (their public names settle() first)
             self._plan = None
 
     # ----------------------------------------------------------- host-driven frame
     def _track(self, tstamp, input_, intrinsics):
-        if getattr(self, "_in_event_pending", False):
-            self._cur().wait_event(self._ev_in)     # inputs_ready = "stream": this frame's front end runs on the main stream
-        out = self.network.patchify(
-            input_=input_, patches_per_image=self.cfg.PATCHES_PER_FRAME, event_bias=self.event_bias,
-            reinit_hidden=True if tstamp == 0 else False)
+        self._pipe.wait_input()                     # inputs_ready = "stream": this frame's front end runs on the main stream
+        out = self._patchify(input_, reinit_hidden=True if tstamp == 0 else False)
         mask = input_[2]
         if mask is not None and not mask:
             return      # events only: the encoder state has advanced, the VO has not

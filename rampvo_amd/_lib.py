@@ -183,6 +183,7 @@ SIGNATURES = {
                            c_p, c_i, c_p]),
     "ramp_upd_gru_heads": (c_i, [c_p, c_p, c_p, c_p, c_p, c_f, ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_p, c_p, c_f, c_p,
                                  c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_p]),
+    "ramp_upd_gru_tile_rows": (c_i, [c_i, c_i]),
     "ramp_upd_mlp_lds_bytes": (c_sz, []),
     "ramp_upd_nbr": (c_i, [c_p] * 8 + [c_i, c_p]),
     "ramp_upd_linear": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p]),

@@ -1460,6 +1460,21 @@ static int big_launch(KernelT kernel, const ParamsT &p, int E, int nmt, int nw, 
   return RAMP_OK;
 }
 
+// 16-row tiles per workgroup of the gru launch (4 or 5: 64 or 80 rows): whichever needs fewer rounds of one-workgroup-per-CU
+// (ties: fewer row-rounds, 64).  With device-side sizes E is the launch bound and the live count a little below it: E_hint, the
+// caller's estimate, stands in for it when it is positive and below E
+static int gru_tiles(int E, int E_hint) {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+  }
+  const int El = (E_hint > 0 && E_hint < E) ? E_hint : E;
+  const long r4 = (long)ramp_cdiv(ramp_cdiv(El, 64), cus) * 4, r5 = (long)ramp_cdiv(ramp_cdiv(El, 80), cus) * 5;
+  return r5 < r4 ? 5 : 4;
+}
+
 extern "C" {
 
 #ifdef GRU_TRACE
@@ -1493,23 +1508,7 @@ int ramp_i_upd_gru(const float *x32, const void *add0_t, const int32_t *add0_idx
   p.ln_w = ln_w; p.ln_b = ln_b; p.eps = eps; p.out32 = out32; p.relu_t = (_Float16 *)relu_t; p.E = E; p.dyn = dyn;
   p.heads_w = (const _Float16 *)heads_w; p.heads_b = heads_b; p.coords = coords; p.target = target; p.weight = weight;
   p.PP = P * P; p.ctr = (P / 2) * P + P / 2; p.wd = wd; p.ht = ht;
-  // rows per workgroup: whichever of 64 / 80 needs fewer rounds of one-workgroup-per-CU (ties: fewer row-rounds); with
-  // device-side sizes E is the launch bound, the live count is a little below it
-  static int cus = 0;
-  const int mt_force = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-  }
-  int mt = 4;
-  if (mt_force == 4 || mt_force == 5) mt = mt_force;
-  else {
-    const int El = (E_hint > 0 && E_hint < E) ? E_hint : E;      // (device-side sizes: E is the launch bound, the hint the caller's estimate)
-    const long r4 = (long)ramp_cdiv(ramp_cdiv(El, 64), cus) * 4, r5 = (long)ramp_cdiv(ramp_cdiv(El, 80), cus) * 5;
-    mt = r5 < r4 ? 5 : 4;
-  }
-  const int rows = 16 * mt;
+  const int mt = gru_tiles(E, E_hint), rows = 16 * mt;
   const size_t lds = (size_t)2 * rows * MXS * 2 + 2 * rows * MWAVES * sizeof(float);   // x / h and sigmoid(gate) tiles + the LayerNorm tables
   static bool attr_set = false;
   if (!attr_set) {
@@ -1586,6 +1585,8 @@ int ramp_i_upd_fg(const float *x32, const void *add_t, const int32_t *add_idx, f
   return RAMP_OK;
 }
 
+
+int ramp_upd_gru_tile_rows(int E, int E_hint) { return 16 * gru_tiles(E, E_hint); }
 
 // ---- public entry points: host-side sizes (dyn = NULL)
 int ramp_upd_gru(const float *x32, const void *add_t, const int32_t *add_idx, const float *pre_w, const float *pre_b,

@@ -82,6 +82,34 @@ def test_update_args_layout_check_sees_a_swapped_field_pair(tmp_path):
     assert {"ramp_update_args.hij", "ramp_update_args.kk_cap"} <= {name for name, _, _ in bad}
 
 
+def test_gru_tile_rows_follow_the_round_rule_at_its_edges():
+    """ramp_upd_gru_tile_rows is the rule ramp_upd_gru's launch applies (one function in csrc/update_mlp.hip) and the one
+    the frame pipeline asks when it places the next front end around that launch.  Restated here in integers: 64- or 80-row
+    tiles, whichever needs fewer rounds of one workgroup per CU counted in 16-row units (4 or 5 per round), a tie gives 64;
+    a positive E_hint below E stands in for E.  CU count: the device's, 256 without one (the launcher's fallback)."""
+    from rampvo_amd import _lib
+    rows = _lib.lib().ramp_upd_gru_tile_rows
+    cus = torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count if torch.cuda.is_available() else 256
+    cdiv = lambda a, b: (a + b - 1) // b
+
+    def want(E, hint=0):
+        live = hint if 0 < hint < E else E
+        return 80 if cdiv(cdiv(live, 80), cus) * 5 < cdiv(cdiv(live, 64), cus) * 4 else 64
+
+    edges = sorted({1, 63, 64, 65, 80, 81} | {t * cus * k + d for t in (64, 80) for k in (1, 2, 3, 4, 5) for d in (-1, 0, 1)})
+    for E in edges:
+        assert rows(E, 0) == want(E), (E, cus)
+        for hint in (0, -5, 1, E - 1, E, E + 1, 64 * cus, 64 * cus + 1, 80 * cus, 80 * cus + 1):
+            assert rows(E, hint) == want(E, hint), (E, hint, cus)
+    assert want(320 * cus) == 64 and rows(320 * cus, 0) == 64           # five rounds of 64 rows = four of 80: the tie
+    assert rows(80 * cus + 1, 80 * cus) == 80 and rows(80 * cus + 1, 0) == 64 and rows(80 * cus, 80 * cus + 1) == 80
+    if cus == 256:
+        table = {1: 64, 16384: 64, 16385: 80, 20480: 80, 20481: 64, 32768: 64, 32769: 80, 40960: 80, 40961: 64}
+        assert {E: rows(E, 0) for E in table} == table
+        assert rows(81920, 0) == 64                                     # 20 = 20
+        assert rows(46000, 40960) == 80 and rows(46000, 0) == 64 and rows(46000, 46000) == 64 and rows(40960, 46000) == 80
+
+
 def test_switch_reader_defaults_and_fallbacks():
     """rampvo_amd.switches.read(): unset variables give the defaults, values that do not parse or are out of range give
     the same defaults, and kernel-serialising runtimes turn the flag waits off"""

@@ -804,6 +804,9 @@ def _tracker_runs_under(envs, ready="False"):
             "    for t in range(T):\n"
             "        im, ev, K, mask = frames[t]; slam(t, input_tensor=(ev, im, mask), intrinsics=K)\n"
             "        resident += int(slam._dev is not None and slam._dev.active); E.append(slam.peek()['E'])\n"
+            # (the name bench.py reports the gate's kind from: a bool, True exactly where signal words order the streams)
+            "    from rampvo_amd import switches\n"
+            "    assert slam._gate_by_flag is (bool(slam.inputs_ready) and switches.read().flag_waits), slam._gate_by_flag\n"
             "    slam.update(); traj, ts = slam.terminate()\n"
             "n = slam.n\n"
             "np.savez(sys.argv[1], traj=traj, ts=ts, poses=slam.poses_[:n].cpu().numpy(), patches=slam.patches_[:n].cpu().numpy(),"

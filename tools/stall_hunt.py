@@ -33,6 +33,7 @@ def step():
     pos[0] += 1
 # where a slow frame spends its host time: wall time inside the calls of Ramp_vo._track_device, per frame
 import rampvo_amd.Ramp_vo as rv
+from rampvo_amd.frame_pipeline import FramePipeline
 acc = {}
 def timed(obj, name, key):
     inner = getattr(obj, name)
@@ -46,8 +47,8 @@ def timed(obj, name, key):
 timed(track_dev.DeviceTrack, "throttle", "throttle")
 timed(track_dev.DeviceTrack, "step", "dv.step")
 timed(track_dev.DeviceTrack, "lazy_state", "lazy_state")
-timed(rv.Ramp_vo, "_fe_done_to", "fe_done_to")
-timed(rv.Ramp_vo, "_gate_wait", "gate_wait")
+timed(FramePipeline, "fe_done_to", "fe_done_to")
+timed(FramePipeline, "gate_wait", "gate_wait")
 timed(rv.Ramp_vo, "_intrinsics_row", "intrinsics_row")
 timed(type(slam.network.patchify), "forward", "patchify")
 # STALL_SPY=1: a watchdog thread that, when the main thread has been inside one frame for more than 8 ms, prints for every

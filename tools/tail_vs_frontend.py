@@ -24,7 +24,7 @@ def step(dv, counter, flags, k_new=None, gate_event=None, **kw):
     g.record(); e.record()            # create the handles
     dv.t.probe[2] = None
     inner(dv, counter, flags, k_new=k_new, gate_event=g.cuda_event)     # our own (timing) event as the gate
-    slam._ev_gate = g
+    slam._pipe.ev_gate = g
     e.record()
     rec.append([g, e, None])
 track_dev.DeviceTrack.step = step
