@@ -1607,6 +1607,56 @@ int ramp_imu_align(const double *tau, const void *gyro, const void *accel, long 
                    double gravity_norm, int gyro_steps, int flags, double *result, double *normal, double *velocity,
                    double *residual, double *preint, int32_t *status, void *ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------- IMU propagation (csrc/imu_propagate.hip)
+ *
+ * Poses at the sample rate ahead of a knot: from an anchor -- a knot's pose and what ramp_imu_align found for it -- forward
+ * through every sample behind it, one row per sample.  Nothing of the entries above changes.
+ *   Inputs.  tau, gyro, accel, N, flags (RAMP_IMU_F64), extrinsics (HOST [12], NULL: identity; the rotation test), bias_a (HOST
+ *   [3] or NULL) and max_gap as in ramp_imu_align.  horizon: seconds, > 0, infinity allowed.  anchor: DEVICE float64
+ *   [RAMP_IMU_ANCHOR_WORDS]; the host never reads it:  [0] t0;  [1..3] pbar0, the knot's translation in the tracker's unit;
+ *   [4..7] the knot's quaternion xyzw, camera to world, normalised here in float64;  [8..10] v0, metric, world frame (the
+ *   knot's row of `velocity`);  [11] s;  [12..14] g;  [15..17] bias_g;  [18..23] 0.
+ *   Definition, float64 without FMA contraction, the element and the law of the section above word for word (J is not carried:
+ *   11 words).  u_i = max(tau_i, t0).  The measurement is piecewise linear between samples; at t0 it is interpolated between
+ *   the last sample at or before t0 and the next, exactly as an interval's first sub-interval is formed above (a sample on t0
+ *   is used as it is).  e_i (i >= 1) is the element on [u_i-1, u_i] with w = 1/2 (gyro(u_i-1) + gyro(u_i)) - bias_g, a likewise
+ *   with bias_a; a sub-interval of length 0 is the identity.  P_0 is the identity, P_i = e_1 o ... o e_i = (dR, dv, dp, dt).
+ *   With R0 = R_wc0 R_bc^T and p0 = s pbar0 - R0 p_bc, row i is
+ *     R_wb = R0 dR        v = (v0 + g dt) + R0 dv        p_wb = ((p0 + v0 dt) + 1/2 g dt^2) + R0 dp
+ *   Outputs, all on the device; times_out and state may be NULL.
+ *   state [N][16] float64: [0] dt, [1..4] q_wb (normalised once, its sign as it comes), [5..7] v, [8..10] p_wb, [11..15] 0.
+ *   poses [N][7] fp32, camera to world in the tracker's unit, a ramp_trajectory_resolve row in every respect: translation
+ *   (p_wb + R_wb p_bc) / s, rotation q_wb (x) q_bc normalised in float64, each rounded to fp32 once.
+ *   times_out [N] = u_i: with poses the `knots, times` of ramp_se3_interp / ramp_event_warp.  Rows at or before the anchor hold
+ *   the anchor's pose at time t0; equal time stamps do not decrease, which those entries accept.
+ *   status: device int32 [8]: [0] bits, [1] samples, [2] rows held (tau_i <= t0), [3] rows propagated, [4] rows cut off,
+ *   [5] rows beyond the horizon, [6], [7] 0;  [2] + [3] + [4] + [5] = [1] whenever no bit is set.
+ *   Bits: RAMP_IMU_BAD_ORDER (tau decreases or is not finite), RAMP_IMU_BAD_ANCHOR (a word of anchor[0..17] is not finite, or
+ *   s <= 0), RAMP_IMU_NO_START (tau[0] > t0).  Any bit: every word of poses, state and times_out is NaN, nothing is walked.
+ *   Dead reckoning does not bridge a break: with b the first index with u_b > t0 at which sample b or sample b - 1 is not finite
+ *   or tau_b - tau_b-1 > max_gap, every row >= b is NaN in poses and state and counts in [4]; its times_out stays u_i.  Samples
+ *   that are not finite strictly before the last one at or before t0 are never touched.  A row with dt > horizon is NaN and
+ *   counts in [5] (behind [4]).  These are outcomes of the data and return RAMP_OK.
+ *   Kernel: a three-level ORDERED scan of the non-commutative product, aligned to sample 0.  A chunk is 64 samples, one per
+ *   lane: lane i takes lane(i - off) o own for off = 1, 2, 4, ..., 32, the lanes before the head supplying the identity, which
+ *   is neutral to the bit.  A tile is 64 chunks (4,096 samples, one workgroup); its chunk totals are scanned the same way.  The
+ *   tile totals chain left to right in one wave.  Row i = (chain[tile - 1] o chunks of its tile before its own) o its chunk's
+ *   scan: its bits are a function of samples 0 .. i and the arguments -- not of N, the grid or the samples behind it -- and a
+ *   call repeats its bits.  The elements are recomputed in the output pass, not stored.  No floating-point atomics: b is an
+ *   integer atomicMin, the counters are ballots.  One 64-byte hipMemsetAsync and five launches (check, tiles, chain, rows,
+ *   status) on `stream`; nothing read back, nothing synchronised.  ws: ramp_imu_propagate_workspace_bytes(N) bytes (64 and 11
+ *   doubles per chunk and per tile; 0 for N < 1), 16-byte aligned.
+ *   NULL tau, gyro, accel, anchor, poses, status or ws, N < 1 or >= 2^31, unknown flags, max_gap or horizon not > 0, a bias or
+ *   extrinsic that is not finite, an R_bc that is no rotation, misaligned arrays: RAMP_EINVAL; a short workspace:
+ *   RAMP_EWORKSPACE.  A refusal touches nothing.                                                                          */
+#define RAMP_IMU_ANCHOR_WORDS 24
+#define RAMP_IMU_BAD_ANCHOR 64  /* status[0] bit 6 */
+#define RAMP_IMU_NO_START 128   /* bit 7 */
+size_t ramp_imu_propagate_workspace_bytes(long N);
+int ramp_imu_propagate(const double *tau, const void *gyro, const void *accel, long N, const double *anchor,
+                       const double *extrinsics, const double *bias_a, double max_gap, double horizon, int flags, float *poses,
+                       double *times_out, double *state, int32_t *status, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ RAMP_FILTER_XY_I32, RAMP_FILTER_BAD_ORDER = 1, 1
 RAMP_IMU_F64, RAMP_IMU_PREINT_WORDS, RAMP_IMU_MAX_GYRO_STEPS = 1, 24, 16
 RAMP_IMU_BAD_ORDER, RAMP_IMU_GYRO_FAILED, RAMP_IMU_SCALE_FAILED = 1, 2, 4
 RAMP_IMU_FEW_TRIPLES, RAMP_IMU_SINGULAR, RAMP_IMU_BAD_SCALE = 8, 16, 32
+RAMP_IMU_ANCHOR_WORDS, RAMP_IMU_BAD_ANCHOR, RAMP_IMU_NO_START = 24, 64, 128
 KPLANE = 32            # channels per plane of the packed correlation target maps: [h][128 / KPLANE][w][KPLANE]
 
 
@@ -261,6 +262,10 @@ SIGNATURES = {
     "ramp_imu_preintegrate": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_p, c_i, c_i, c_p, c_p, ctypes.c_double, c_i, c_p, c_p, c_p]),
     "ramp_imu_align": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_p, c_p, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, ctypes.c_double,
                              c_i, c_i] + [c_p] * 7 + [c_sz, c_p]),
+    # IMU propagation (csrc/imu_propagate.hip)
+    "ramp_imu_propagate_workspace_bytes": (c_sz, [ctypes.c_long]),
+    "ramp_imu_propagate": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_p, c_p, c_p, ctypes.c_double, ctypes.c_double, c_i] + [c_p] * 5
+                           + [c_sz, c_p]),
 }
 
 _lib = None

@@ -33,6 +33,9 @@ _STATUS = {
              "scale_failed": _lib.RAMP_IMU_SCALE_FAILED, "few_triples": _lib.RAMP_IMU_FEW_TRIPLES,
              "singular": _lib.RAMP_IMU_SINGULAR, "bad_scale": _lib.RAMP_IMU_BAD_SCALE},
             ("n_samples", "n_intervals", "n_uncovered", "n_dt_not_positive", "n_gyro_intervals", "n_triples")),
+    "imu_propagate": ({"bad_order": _lib.RAMP_IMU_BAD_ORDER, "bad_anchor": _lib.RAMP_IMU_BAD_ANCHOR,
+                       "no_start": _lib.RAMP_IMU_NO_START},
+                      ("n_samples", "n_held", "n_propagated", "n_cut_off", "n_beyond_horizon")),
 }
 
 
@@ -661,12 +664,7 @@ def imu_align(tau, gyro, accel, knots, times, R_bc=None, p_bc=None, bias_g=None,
         raise RuntimeError("imu_align: knots [T,7] and times [T] differ in length")
     if T < 2 or stride < 1 or K < 2:
         raise RuntimeError("imu_align: at least two of the knots are used (stride >= 1)")
-    ext = None
-    if R_bc is not None or p_bc is not None:
-        R = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]] if R_bc is None else R_bc
-        R = [list(r) for r in _host_value("imu_align: R_bc", R)]
-        p = [0.0, 0.0, 0.0] if p_bc is None else list(_host_value("imu_align: p_bc", p_bc))
-        ext = list(R) + [p]
+    ext = _imu_extrinsics("imu_align", R_bc, p_bc)
     (_, ex), (_, bg), (_, ba) = keep = (_host3("imu_align: R_bc and p_bc", ext, 12), _host3("imu_align: bias_g", bias_g),
                                         _host3("imu_align: bias_a", bias_a))
     dev = tf.device
@@ -690,6 +688,69 @@ def imu_align(tau, gyro, accel, knots, times, R_bc=None, p_bc=None, bias_g=None,
 def imu_status(status):
     """The status words of ``imu_preintegrate`` / ``imu_align`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
     return _status("imu", status)
+
+
+def _imu_extrinsics(name, R_bc, p_bc):
+    """R_bc [3,3] and p_bc [3] (host values; None: identity, zero) as the 12 host words the C entries take, or None for both"""
+    if R_bc is None and p_bc is None:
+        return None
+    R = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]] if R_bc is None else R_bc
+    R = [list(r) for r in _host_value(name + ": R_bc", R)]
+    p = [0.0, 0.0, 0.0] if p_bc is None else list(_host_value(name + ": p_bc", p_bc))
+    return list(R) + [p]
+
+
+def imu_anchor(align, knots, times, stride=1):
+    """The anchor of ``imu_propagate`` from the dict of ``imu_align`` and the last knot it used (``knots`` [T,7], ``times`` [T],
+    ``stride`` as given there): device float64 [24] -- t0, the knot's translation, its quaternion, the knot's velocity, ``s``,
+    ``g``, ``bias_g``, six zeros (include/ramp_hip.h ``ramp_imu_propagate``).  Torch ops on the current stream: nothing is read
+    back, nothing synchronised; a failed alignment's NaNs simply arrive in it, and the propagation answers ``bad_anchor``."""
+    require_cuda(knots, times, align["result"], align["velocity"])
+    kn, tt = knots.reshape(-1, 7), times.reshape(-1)
+    T = kn.shape[0]
+    K = (T - 1) // max(int(stride), 1) + 1
+    if stride < 1 or tt.shape[0] != T or align["velocity"].shape[0] != K:
+        raise RuntimeError("imu_anchor: the alignment holds %d knots, knots [T,7] / times [T] at this stride hold %d"
+                           % (align["velocity"].shape[0], K))
+    last = (K - 1) * int(stride)
+    r = align["result"]
+    return torch.cat([tt[last:last + 1].to(torch.float64), kn[last].to(torch.float64), align["velocity"][K - 1], r[0:7],
+                      torch.zeros(6, dtype=torch.float64, device=r.device)])
+
+
+def imu_propagate(tau, gyro, accel, anchor, R_bc=None, p_bc=None, bias_a=None, max_gap=float("inf"), horizon=float("inf"),
+                  want_state=False):
+    """Poses at the IMU's rate ahead of a knot (include/ramp_hip.h ``ramp_imu_propagate``): from ``anchor`` (``imu_anchor``)
+    forward through every sample behind it -- a device-wide ordered float64 scan of the preintegration elements.  ``tau`` [N],
+    ``gyro``, ``accel`` [N,3], ``R_bc``, ``p_bc``, ``bias_a``, ``max_gap`` as in ``imu_align``; ``horizon``: rows further than this
+    many seconds from the anchor are NaN.  Returns a dict of device tensors: ``poses`` [N,7] fp32 camera-to-world rows in the
+    tracker's unit and ``times`` [N] float64 ``max(tau, t0)`` -- together the ``knots, times`` of ``se3_interp`` /
+    ``event_warp`` --, ``status`` int32 [8] (``imu_propagate_status``), with ``want_state`` ``state`` [N,16] float64 (dt, q_wb,
+    v, p_wb, zeros).  Rows at or before the anchor hold its pose; rows behind a sample that is not finite or a gap above
+    ``max_gap`` are NaN; a status bit makes everything NaN, never a plausible number.  One C call on the current stream,
+    nothing read back, nothing synchronised.  Row i's bits depend on samples 0 .. i and the arguments alone."""
+    tf, g, a, an, N, flags = _imu_samples("imu_propagate", tau, gyro, accel, anchor)
+    if an.shape[0] != _lib.RAMP_IMU_ANCHOR_WORDS:
+        raise RuntimeError("imu_propagate: anchor holds %d float64 words (imu_anchor)" % _lib.RAMP_IMU_ANCHOR_WORDS)
+    (_, ex), (_, ba) = keep = (_host3("imu_propagate: R_bc and p_bc", _imu_extrinsics("imu_propagate", R_bc, p_bc), 12),
+                               _host3("imu_propagate: bias_a", bias_a))
+    dev = tf.device
+    res = {"poses": torch.empty((N, 7), dtype=torch.float32, device=dev), "times": torch.empty(N, dtype=torch.float64, device=dev),
+           "status": torch.empty(8, dtype=torch.int32, device=dev)}
+    if want_state:
+        res["state"] = torch.empty((N, 16), dtype=torch.float64, device=dev)
+    nbytes = lib().ramp_imu_propagate_workspace_bytes(N)
+    ws = _lib_workspace(nbytes, dev, "imu_propagate")
+    check(lib().ramp_imu_propagate(ptr(tf), ptr(g), ptr(a), N, ptr(an), ex, ba, float(max_gap), float(horizon), flags,
+                                   ptr(res["poses"]), ptr(res["times"]), ptr(res.get("state")), ptr(res["status"]), ptr(ws),
+                                   nbytes, stream()), "ramp_imu_propagate")
+    del keep
+    return res
+
+
+def imu_propagate_status(status):
+    """The status words of ``imu_propagate`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("imu_propagate", status)
 
 
 def align_loop(evaluate, correction, free, step, iters):

@@ -54,18 +54,20 @@ class StateStream:
                 self.leaves(*(x.values() if isinstance(x, dict) else x))
 
 
-def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None, filter=None, imu=None):
+def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None, filter=None, imu=None, propagate=None):
     """The closing check of a query's numpy form -- its one wait.  Each argument is a device status tensor or None (not part
     of this query): ``traj`` trajectory()'s word, ``interp`` the words of ops.se3_interp or ops.event_warp (bit 0 of word 0:
     the frames' time stamps), ``cam`` those of ops.invdepth_map (bit 0 of word 0: the camera pose), ``voxel`` those of
     ops.event_voxel_grid (bits 0 and 1 of word 0: the offsets, a slice's own time stamps), ``rectify`` those of
     ops.event_rectify / ops.image_rectify (bit 0 of word 0: the camera record), ``filter`` those of ops.event_filter (bit 0 of
     word 0: the events' order), ``imu`` those of ops.imu_align (bit 0: the order of the samples or of the frames' time stamps;
-    bits 1 and 2: the gyro stage, the scale stage).  Word 0 of each goes to the host in one copy; raises in this order: event
+    bits 1 and 2: the gyro stage, the scale stage), ``propagate`` those of ops.imu_propagate (bit 0: the samples' order; bits
+    6 and 7: the anchor, no sample at or before it).  Word 0 of each goes to the host in one copy; raises in this order: event
     order, camera record, unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times, IMU order, gyro
-    stage, scale stage."""
+    stage, scale stage, the propagation's order, anchor and start."""
     given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam), ("voxel", voxel),
-                                                 ("rectify", rectify), ("filter", filter), ("imu", imu)) if s is not None]
+                                                 ("rectify", rectify), ("filter", filter), ("imu", imu),
+                                                 ("propagate", propagate)) if s is not None]
     if not given:
         return
     first = given[0][1] if len(given) == 1 else torch.cat([s for _, s in given])
@@ -97,6 +99,13 @@ def _raise_on_words(name, word):
         why = ("fewer than two triples of frames are covered by the samples" if imu & _lib.RAMP_IMU_FEW_TRIPLES else
                "the scale is not positive" if imu & _lib.RAMP_IMU_BAD_SCALE else "the system is singular")
         raise RuntimeError(name + ": the scale and gravity solve failed: " + why)
+    prop = word.get("propagate", 0)
+    if prop & _lib.RAMP_IMU_BAD_ORDER:
+        raise RuntimeError(name + ": the IMU samples' time stamps decrease or are not finite")
+    if prop & _lib.RAMP_IMU_BAD_ANCHOR:
+        raise RuntimeError(name + ": the anchor is not finite or its scale is not positive (a failed alignment leaves NaN)")
+    if prop & _lib.RAMP_IMU_NO_START:
+        raise RuntimeError(name + ": no IMU sample lies at or before the anchor's time stamp")
 
 
 def _dof_sigma0(s):
@@ -269,6 +278,47 @@ class TrackerQueries:
         res = {k: v.cpu().numpy() for k, v in out.items()}
         res["scale"] = float(res["scale"][0])
         return res
+
+    def propagate_imu(self, tau, gyro, accel, align=None, stride=1, gravity_norm=9.80665, max_gap=float("inf"),
+                      horizon=float("inf"), gyro_steps=1, want_state=False, as_tensor=False):
+        """Poses at the IMU's rate ahead of the newest frame: the alignment (``align=None``: ``ops.imu_align`` exactly as
+        ``align_imu`` runs it; else the device dict of ``align_imu(as_tensor=True)``, reused; raises when its knot count is not
+        the current one), the anchor on the last knot used (``ops.imu_anchor``) and the propagation through every sample behind
+        it (``ops.imu_propagate``), all on one stream with the sensor of ``set_imu`` (raises without one).  ``horizon``: rows
+        further than this many seconds from the anchor are NaN.  The result holds ``poses`` [N,7] camera-to-world rows in the
+        tracker's unit, ``times`` [N], ``status``, ``state`` on request, and ``align``.  ``poses, times`` are knots and time
+        stamps for ``ops.se3_interp`` / ``ops.event_warp``: appended behind ``trajectory(as_tensor=True)`` and the frames' time
+        stamps from the first row with a time above the newest frame's, they warp the events newer than that frame.
+
+        A device-resident state stays device resident.  ``as_tensor=True``: device tensors, ordered on the current stream,
+        nothing synchronised, nothing raised.  Otherwise numpy arrays, which reads once at the end and raises on the status
+        bits of the alignment and of the propagation, and on trajectory()'s unresolved bit."""
+        if self._imu is None:
+            raise RuntimeError("propagate_imu(): no IMU has been set (set_imu())")
+        if len(self.tlist) < 2:
+            raise RuntimeError("propagate_imu(): fewer than two frames have been tracked")
+        K = (len(self.tlist) - 1) // max(int(stride), 1) + 1
+        if align is not None and (not isinstance(align.get("velocity"), torch.Tensor) or align["velocity"].shape[0] != K):
+            raise RuntimeError("propagate_imu(): align= is the device dict of align_imu(as_tensor=True) at this stride and "
+                               "frame count (%d knots)" % K)
+        fl = lambda v: torch.float64 if (v.dtype == torch.float64 if isinstance(v, torch.Tensor) else np.asarray(v).dtype == np.float64) else torch.float32
+        td = self._as_device(tau, torch.float64)
+        gd, ad = self._as_device(gyro, fl(gyro)).reshape(-1, 3), self._as_device(accel, fl(accel)).reshape(-1, 3)
+        knots, _ = self.trajectory(as_tensor=True)
+        tdev = self._frame_times_dev()
+        with torch.no_grad():                                  # (on the caller's stream, behind trajectory()'s launch: as align_imu)
+            if align is None:
+                align = ops.imu_align(td, gd, ad, knots, tdev, stride=stride, max_gap=max_gap, gravity_norm=gravity_norm,
+                                      gyro_steps=gyro_steps, **self._imu)
+            anchor = ops.imu_anchor(align, knots, tdev, stride=stride)
+            out = ops.imu_propagate(td, gd, ad, anchor, R_bc=self._imu["R_bc"], p_bc=self._imu["p_bc"],
+                                    bias_a=self._imu["bias_a"], max_gap=max_gap, horizon=horizon, want_state=want_state)
+        out["align"] = align
+        if as_tensor:
+            return out
+        _check_status("propagate_imu()", traj=self._traj_status, imu=align["status"], propagate=out["status"])
+        host = lambda d: {k: (host(v) if isinstance(v, dict) else v.cpu().numpy()) for k, v in d.items()}
+        return host(out)
 
     # ---------------------------------------------------------------- event denoising
     _FILTER_KEYS = ("support_dt", "refractory", "hot_count", "hot_sigma", "hot_mask")
