@@ -19,6 +19,12 @@
  *   - feature maps come in two layouts: RAMP_NCHW (the reference's) and
  *     RAMP_NHWC (channels-last, this library's native layout: one pixel's
  *     channels are contiguous so a wavefront reads whole 512 B rows)
+ *   - the Python binding (rampvo_amd/_lib.py) keeps no copy of the numbers or
+ *     signatures below: it reads this file when it is imported.  So a value
+ *     macro is `#define RAMP_<NAME> <integer or float literal>`, a scalar
+ *     parameter is an int, long, size_t, float, double or <stdint.h> type, and
+ *     everything with a `*` is passed as a void pointer.  The structs are still
+ *     mirrored by hand there (a test holds them to the C compiler's layout)
  */
 #ifndef RAMP_HIP_H
 #define RAMP_HIP_H
@@ -779,16 +785,22 @@ int ramp_x3_gru(const float *x32, const float *add0_t, const int32_t *add0_idx, 
 #define RAMP_DYN_NPREV 8    /* Ramp_vo.n when the test ran                                                        */
 #define RAMP_DYN_EPREV 9    /* factors before the edit                                                            */
 #define RAMP_DYN_EKEPT 10   /* factors the edit kept (next graph = kept ++ new)                                   */
-#define RAMP_DYN_STATUS 11  /* sticky bits: 1 BA pose step dropped, 2 BA pair list overflow (ramp_ba_forward's
-                               info), 4 factor capacity exceeded, 8 group-by key out of range, 16 delta log full,
-                               32 a step's E_bound was below the live factor count, 64 frame buffers full (n_rows),
-                               128 a gate wait (ramp_stream_wait_flag) timed out: the front end ran unordered       */
+#define RAMP_DYN_STATUS 11  /* sticky bits, RAMP_STATUS_* below                                                   */
 #define RAMP_DYN_NLOG 12    /* entries written to the delta log                                                   */
 #define RAMP_DYN_FRAME 13   /* `counter` of the last frame stepped (tags the host's lazy copy)                    */
 #define RAMP_DYN_MEDOK 14   /* 1: ramp_track.median holds the depth median of the three newest frames (set beside the
                              * motion test, cleared by an update-only step; 0 when the host hands the state over)     */
 #define RAMP_DYN_FRAME2 31  /* = RAMP_DYN_FRAME, in the other half of the block: the two differ in a torn host copy         */
 #define RAMP_TRACK_LOG 12   /* floats per delta-log entry: t1, t0 (as int32 bit patterns), dP[7], pad             */
+/* the bits of the RAMP_DYN_STATUS word: set by the kernel that meets the condition, never cleared by a step */
+#define RAMP_STATUS_BA_STEP_DROPPED 1    /* BA dropped a pose step (ramp_ba_forward's info bit 0)                    */
+#define RAMP_STATUS_BA_PAIR_OVERFLOW 2   /* BA's pair list overflowed (ramp_ba_forward's info bit 1)                 */
+#define RAMP_STATUS_FACTORS_FULL 4       /* factor capacity exceeded                                                 */
+#define RAMP_STATUS_KEY_RANGE 8          /* group-by key out of range                                                */
+#define RAMP_STATUS_LOG_FULL 16          /* delta log full                                                           */
+#define RAMP_STATUS_E_BOUND 32           /* a step's E_bound was below the live factor count                         */
+#define RAMP_STATUS_FRAMES_FULL 64       /* frame buffers full (n_rows)                                              */
+#define RAMP_STATUS_GATE_TIMEOUT 128     /* a gate wait (ramp_stream_wait_flag) timed out: the front end ran unordered */
 
 /* A pose record (ramp_track_publish): 32 words = two 64-byte halves, written to slot `counter % ring_cap` of a ring in pinned
  * host memory, one record per accepted frame.  The frame tag sits in both halves (as in `dyn`): the first half is stored,

@@ -291,8 +291,8 @@ class Ramp_vo(TrackerQueries):
         if self._dev._frames:                    # the last update()'s confidence weights (reference :296; the host-driven
             self.last_weight = st["weight"][None]    # update() sets it; the pose-prediction mode reads it)
             self.last_target = st["target"][None]    # (uncertainty() after a hand-back)
-        self._note_ba_flags(st["status"] & 3)
-        if st["status"] & ~3:
+        self._note_ba_flags(st["status"] & track_dev.STATUS_BA)
+        if st["status"] & ~track_dev.STATUS_BA:
             raise RuntimeError("device-resident tracker: status bits %d (4 = factor list full, 8 = group-by key / group "
                                "capacity, 16 = delta log full, 32 = launch bound below the factor count, 64 = frame "
                                "buffers full (BUFFER_SIZE), 128 = a gate wait timed out: a front end ran unordered)"
@@ -734,7 +734,7 @@ class Ramp_vo(TrackerQueries):
         dv.throttle(self.counter)                   # at most MAX_AHEAD frames ahead of the newest lazy copy (the margins below)
         lazy = dv.lazy_state()                      # whatever copy of the device-side sizes has arrived: never waited for
         if (accepts and (lazy[track_dev.DYN_N] + 8 >= self.N or lazy[track_dev.DYN_NLOG] + 8 >= dv.log_cap
-                         or lazy[track_dev.DYN_STATUS] & ~3)):
+                         or lazy[track_dev.DYN_STATUS] & ~track_dev.STATUS_BA)):
             self.settle()                           # buffer / log nearly full, or a capacity flag: back to the host
             return self._track(tstamp, input_, intrinsics)
         pipe, ready = self._pipe, self.inputs_ready

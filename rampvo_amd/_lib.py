@@ -7,6 +7,7 @@ built (``python -c "import __graft_entry__ as g; g.build()"`` or
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -15,31 +16,61 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("RAMP_HIP_LIB") or os.path.join(CSRC, "libramp_hip.so")   # env: kernel A/B builds
 
-RAMP_F32, RAMP_F16 = 0, 1
-RAMP_EUNSUPPORTED = -4
-RAMP_CONV_FP8 = 0x40
-RAMP_IN_F32, RAMP_CONV_DIRECT, RAMP_CORR_MFMA32, RAMP_CORR_X2 = 0x10, 0x20, 0x40, 0x80
-RAMP_CONV_X3 = 0x80
-RAMP_TILE_FP8, RAMP_TILE_TAIL, RAMP_TILE_SINGLE, RAMP_TILE_PAIRED = 1, 2, 4, 8
-RAMP_NCHW, RAMP_NHWC, RAMP_NHWC32 = 0, 1, 2
-RAMP_INTERP_EXTRAPOLATE, RAMP_INTERP_ROW_STORES, RAMP_INTERP_BAD_TIMES = 1, 2, 1
-RAMP_WARP_DEPTH_SCALAR, RAMP_WARP_DEPTH_MAP, RAMP_WARP_IDENTITY, RAMP_WARP_MIN_Z = 0, 4, 8, 0.2
-RAMP_DEPTHMAP_CONF_IS_VARIANCE, RAMP_DEPTHMAP_PRIOR_RELATIVE, RAMP_DEPTHMAP_BAD_CAM = 1, 2, 1
-RAMP_CONTRAST_UNSIGNED, RAMP_CONTRAST_BAD_CORRECTION = 16, 2
-RAMP_ALIGN_ITERS, RAMP_ALIGN_STALLED, RAMP_ALIGN_FLAT, RAMP_ALIGN_BUDGET = 1, 2, 3, 4
-RAMP_ALIGN_MAX_ITERS, RAMP_ALIGN_TRIALS = 65536, 9
-RAMP_VOXEL_NORMALIZE, RAMP_VOXEL_SUBPIXEL, RAMP_VOXEL_BAD_OFFSETS, RAMP_VOXEL_BAD_TIMES = 1, 2, 1, 2
-# the camera record of csrc/rectify.hip: word offsets, models, flags, value modes
-RAMP_CAMERA_WORDS, RAMP_CAMERA_RAW, RAMP_CAMERA_MODEL, RAMP_CAMERA_COEFFS, RAMP_CAMERA_ROTATION, RAMP_CAMERA_NEW = 32, 0, 4, 5, 12, 24
-RAMP_CAM_PINHOLE, RAMP_CAM_RADTAN, RAMP_CAM_EQUIDISTANT = 0, 1, 2
-RAMP_RECTIFY_ITERS, RAMP_RECTIFY_TOL = 8, 2.0 ** -6
-RAMP_RECTIFY_XY_I32, RAMP_RECTIFY_SRC_U8, RAMP_RECTIFY_BAD_CAMERA = 1, 2, 1
-RAMP_RECTIFY_NORM_NONE, RAMP_RECTIFY_NORM_HALF, RAMP_RECTIFY_NORM_UNIT = 0, 1, 2
-RAMP_FILTER_XY_I32, RAMP_FILTER_BAD_ORDER = 1, 1
-RAMP_IMU_F64, RAMP_IMU_PREINT_WORDS, RAMP_IMU_MAX_GYRO_STEPS = 1, 24, 16
-RAMP_IMU_BAD_ORDER, RAMP_IMU_GYRO_FAILED, RAMP_IMU_SCALE_FAILED = 1, 2, 4
-RAMP_IMU_FEW_TRIPLES, RAMP_IMU_SINGULAR, RAMP_IMU_BAD_SCALE = 8, 16, 32
-RAMP_IMU_ANCHOR_WORDS, RAMP_IMU_BAD_ANCHOR, RAMP_IMU_NO_START = 24, 64, 128
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "ramp_hip.h")
+
+_C_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "long": ctypes.c_long, "const char *": ctypes.c_char_p}
+_C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "long": ctypes.c_long,
+              "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def parse_header(text):
+    """(constants, signatures) of a C header written like include/ramp_hip.h: every ``#define RAMP_<NAME> <literal>`` (decimal
+    or hex integer, float with an optional f suffix) as name -> value, and every ``ramp_*`` prototype as name -> (restype,
+    argtypes).  A parameter with ``*`` or ``[`` is a c_void_p (it takes byref(), arrays, pointer(), c_void_p and None); a
+    scalar maps by its type name.  A literal or a type this reader does not know raises: nothing defaults to int."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(RAMP_\w+)(.*)$", text, re.M):
+        value = value.strip()
+        if not value:                               # (the include guard)
+            continue
+        try:
+            constants[name] = int(value, 0)
+        except ValueError:
+            try:
+                constants[name] = float(value[:-1] if value[-1] in "fF" else value)
+            except ValueError:
+                raise RuntimeError("%s: the value %r is not an integer or float literal" % (name, value)) from None
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"\btypedef\s+struct\b[^{;]*\{[^{}]*\}[^;]*;", " ", text)
+    signatures = {}
+    for ret, name, params in re.findall(r"([^;{}()\"]*?)\b(ramp_\w+)\s*\(([^()]*)\)\s*;", text):
+        ret, params = " ".join(ret.split()), [" ".join(p.split()) for p in params.split(",")]
+        if ret not in _C_RETURNS:
+            raise RuntimeError("%s: return type %r is not one this binding maps" % (name, ret))
+        argtypes = []
+        for p in [] if params == ["void"] else params:
+            ctype = " ".join([w for w in p.split() if w != "const"][:-1])       # (the last word is the parameter's name)
+            if "*" not in p and "[" not in p and ctype not in _C_SCALARS:
+                raise RuntimeError("%s: parameter %r has a type this binding does not map" % (name, p))
+            argtypes.append(ctypes.c_void_p if "*" in p or "[" in p else _C_SCALARS[ctype])
+        signatures[name] = (_C_RETURNS[ret], argtypes)
+    return constants, signatures
+
+
+def _read_header():
+    try:
+        with open(HEADER) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise RuntimeError("rampvo_amd: cannot read the C header %s (%s): its constants and signatures are taken from it"
+                           % (HEADER, e)) from None
+
+
+# every RAMP_* value macro of the header as a global of this module, under its own name; SIGNATURES: name -> (restype,
+# argtypes) of every entry point it declares
+CONSTANTS, SIGNATURES = _read_header()
+globals().update(CONSTANTS)
 KPLANE = 32            # channels per plane of the packed correlation target maps: [h][128 / KPLANE][w][KPLANE]
 
 
@@ -58,8 +89,9 @@ def corr_f32_mode():
     from . import switches
     return switches.read().corr_f32_mfma
 
-_ERR = {-1: "RAMP_EINVAL (bad argument)", -2: "RAMP_ELAUNCH (HIP launch/runtime error)",
-        -3: "RAMP_EWORKSPACE (workspace too small)", -4: "RAMP_EUNSUPPORTED (size/shape not supported)"}
+_ERR = {CONSTANTS[name]: "%s (%s)" % (name, why) for name, why in (
+    ("RAMP_EINVAL", "bad argument"), ("RAMP_ELAUNCH", "HIP launch/runtime error"),
+    ("RAMP_EWORKSPACE", "workspace too small"), ("RAMP_EUNSUPPORTED", "size/shape not supported"))}
 
 c_p, c_i, c_i64, c_sz, c_f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 
@@ -92,182 +124,6 @@ class UpdateArgs(ctypes.Structure):
                 + [(n, c_i) for n in ("kk_cap", "ij_cap", "E", "E_hint", "P", "fp32")] + [("wd", c_f), ("ht", c_f)])
 
 
-# name -> (restype, argtypes); also the list the CPU test checks for export
-SIGNATURES = {
-    "ramp_version": (ctypes.c_char_p, []),
-    "ramp_corr_kplane": (c_i, []),
-    "ramp_patchify_fwd": (c_i, [c_p, c_p, c_p] + [c_i] * 10 + [c_p]),
-    "ramp_frame_gather": (c_i, [c_p] * 9 + [c_i] * 8 + [c_p]),
-    "ramp_corr_fwd": (c_i, [c_p, ctypes.POINTER(CorrLevel), c_i, c_p, c_p, c_p, c_p] + [c_i] * 8 + [c_p]),
-    "ramp_ms_lstm_superstate": (c_i, [c_p, c_p, ctypes.POINTER(c_p), c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "ramp_ms_lstm_superstate_mfma": (c_i, [c_p] * 6 + [c_i] * 5 + [c_p]),
-    "ramp_conv2d_stats_blocks": (c_i, [c_i] * 7),
-    "ramp_conv2d_tiled": (c_i, [c_i] * 5),
-    "ramp_conv2d_tile_rows": (c_i, []),
-    "ramp_conv2d_tile_row": (c_i, [c_i] + [ctypes.POINTER(c_i)] * 7),
-    "ramp_conv2d_multi_row": (c_i, [c_p] + [c_i] * 7),
-    "ramp_graph_edit_host": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
-    "ramp_event_stack_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
-    "ramp_event_stack": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "ramp_depth_median_fill": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
-    "ramp_depth_median": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
-    "ramp_depth_median_rows": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
-    "ramp_event_topk_workspace_bytes": (c_sz, [c_i, c_i]),
-    "ramp_event_topk": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_sz, c_p]),
-    "ramp_pyramid_pack": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
-    "ramp_corr_fwd_ordered": (c_i, [c_p, ctypes.POINTER(CorrLevel), c_i, c_p, c_p, c_p, c_p, c_p, c_i, ctypes.c_long,
-                                    ctypes.c_long] + [c_i] * 8 + [c_p]),
-    "ramp_se3_exp": (c_i, [c_p, c_p, c_i, c_p]),
-    "ramp_se3_log": (c_i, [c_p, c_p, c_i, c_p]),
-    "ramp_se3_inv": (c_i, [c_p, c_p, c_i, c_p]),
-    "ramp_se3_mul": (c_i, [c_p, c_p, c_p, c_i, c_p]),
-    "ramp_se3_act4": (c_i, [c_p, c_p, c_p, c_i, c_p]),
-    "ramp_se3_adj": (c_i, [c_p, c_p, c_p, c_i, c_p]),
-    "ramp_se3_adjT": (c_i, [c_p, c_p, c_p, c_i, c_p]),
-    "ramp_transform": (c_i, [c_p] * 7 + [c_i, c_i, c_i, c_p]),
-    "ramp_reproject": (c_i, [c_p] * 7 + [c_i, c_i, c_p]),
-    "ramp_point_cloud": (c_i, [c_p] * 5 + [c_i, c_i, c_p]),
-    "ramp_multi_copy": (c_i, [c_p, c_p, c_p, c_i, c_p]),
-    "ramp_shift_rows": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
-    "ramp_motionmag": (c_i, [c_p] * 10 + [c_i64, c_i64, c_f, c_p, c_i, c_p]),
-    "ramp_motion_model": (c_i, [c_p, c_i, c_f, c_p]),
-    "ramp_frame_commit": (c_i, [c_p, c_i, c_i, c_f, c_p, c_i64, c_p, c_i64, c_p, c_i, c_p, c_i, c_i, c_i, c_p, c_i,
-                                ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(ctypes.c_long), c_p, c_p]),
-    "ramp_frame_begin": (c_i, [c_p, c_i, c_i, c_f, c_p, c_i64, c_p, c_i64, c_p, c_i, c_p]),
-    "ramp_group_by_workspace_bytes": (c_sz, [c_i]),
-    "ramp_group_by": (c_i, [c_p, c_i, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "ramp_neighbors_workspace_bytes": (c_sz, [c_i]),
-    "ramp_neighbors": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i64, c_i64, c_p, c_sz, c_p]),
-    "ramp_segment_softmax_sum": (c_i, [c_p] * 6 + [c_i, c_i, c_i, c_i, c_p]),
-    "ramp_ba_workspace_bytes": (c_sz, [c_i] * 5),
-    "ramp_ba_forward": (c_i, [c_p] * 9 + [c_i] * 7 + [c_p, c_sz, c_p, c_p]),
-    "ramp_ba_planned_workspace_bytes": (c_sz, [c_i] * 7),
-    "ramp_ba_forward_planned": (c_i, [c_p] * 9 + [c_i] * 7 + [c_p] * 4 + [c_i] + [c_p] * 3 + [c_i, c_p, c_sz, c_p, c_p]),
-    "ramp_ba_covariance_workspace_bytes": (c_sz, [c_i] * 5),
-    "ramp_ba_covariance": (c_i, [c_p] * 9 + [c_i] * 6 + [c_p] * 3 + [c_p, c_sz, c_p, c_p]),
-    "ramp_ba_covariance_planned_workspace_bytes": (c_sz, [c_i] * 7),
-    "ramp_ba_covariance_planned": (c_i, [c_p] * 9 + [c_i] * 6 + [c_p] * 3 + [c_p] * 4 + [c_i] + [c_p] * 3
-                                   + [c_i, c_p, c_sz, c_p, c_p]),
-    "ramp_ba_map_covariance_workspace_bytes": (c_sz, [c_i] * 5),
-    "ramp_ba_map_covariance": (c_i, [c_p] * 9 + [c_i] * 6 + [c_p] * 7 + [c_p, c_sz, c_p, c_p]),
-    "ramp_ba_map_covariance_planned_workspace_bytes": (c_sz, [c_i] * 7),
-    "ramp_ba_map_covariance_planned": (c_i, [c_p] * 9 + [c_i] * 6 + [c_p] * 7 + [c_p] * 4 + [c_i] + [c_p] * 3
-                                       + [c_i, c_p, c_sz, c_p, c_p]),
-    "ramp_map_select": (c_i, [c_p] * 4 + [c_i, c_i, c_p, c_i, c_f, c_f, c_i, c_p, c_p, c_p]),
-    "ramp_group_by_small_workspace_bytes": (c_sz, [c_i, c_i]),
-    "ramp_group_by_small": (c_i, [c_p, c_p, c_i64, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
-    "ramp_neighbors_from_groups": (c_i, [c_p] * 7 + [c_i, c_i, c_p]),
-    "ramp_any_nonzero": (c_i, [c_p, ctypes.c_long, c_p, ctypes.c_long, c_p, c_p]),
-    "ramp_lstm_superstate_tiled": (c_i, [c_p] * 9 + [c_i, c_i, c_i, c_p]),
-    "ramp_lstm_superstate_blocks": (c_i, [c_p] * 9 + [c_i, c_i, c_i, c_i, c_p]),
-    "ramp_any_nonzero_blocks": (c_i, [c_p, ctypes.c_long, c_p, ctypes.c_long, c_p, c_p]),
-    "ramp_any_nonzero_blocks_clear": (c_i, [c_p, ctypes.c_long, c_p, ctypes.c_long, c_p, c_p, ctypes.c_long, c_p]),
-    "ramp_conv2d_nhwc": (c_i, [c_p] * 8 + [c_i] * 8 + [c_f, c_i, c_p]),
-    "ramp_in_stats_finalize": (c_i, [c_p, c_i, c_i, c_f, c_f, c_p, c_p, c_p]),
-    "ramp_affine_relu": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_long, c_i, c_p]),
-    "ramp_norm_add_relu": (c_i, [c_p] * 7 + [ctypes.c_long, c_i, c_p]),
-    "ramp_affine_relu_f16": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_long, c_i, c_p]),
-    "ramp_norm_add_relu_f16": (c_i, [c_p] * 7 + [ctypes.c_long, c_i, c_i, c_p]),
-    "ramp_norm_add_relu_f16_acc": (c_i, [c_p, c_p, c_f, c_f, c_p, c_p, c_f, c_f, c_p, ctypes.c_long, c_i, c_i, c_p]),
-    "ramp_in_acc_finalize": (c_i, [c_p, c_i, c_f, c_f, c_p, c_p, c_p]),
-    "ramp_conv2d_nhwc_multi": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "ramp_upd_row_fuse": (c_i, [c_p] * 6 + [ctypes.c_long, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_i, c_i, c_p]),
-    "ramp_upd_gather_mask": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p]),
-    "ramp_upd_gated": (c_i, [c_p] * 5 + [c_f, c_p, c_p, c_p, c_i, c_i, c_p]),
-    "ramp_upd_heads": (c_i, [c_p] * 5 + [c_i, c_i, c_f, c_f, c_i, c_p]),
-    "ramp_upd_segment_softmax": (c_i, [c_p] * 5 + [c_i, c_i, c_p]),
-    "ramp_upd_corr_mlp": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, ctypes.c_long,
-                                c_p, c_p, c_f, c_p, c_i, c_p]),
-    "ramp_upd_heads_linear": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_p]),
-    "ramp_upd_fg": (c_i, [c_p] * 9 + [c_i, c_p]),
-    "ramp_upd_gru": (c_i, [c_p, c_p, c_p, c_p, c_p, c_f, ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_p, c_p, c_f, c_p,
-                           c_p, c_i, c_p]),
-    "ramp_upd_gru_heads": (c_i, [c_p, c_p, c_p, c_p, c_p, c_f, ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_p, c_p, c_f, c_p,
-                                 c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_p]),
-    "ramp_upd_gru_tile_rows": (c_i, [c_i, c_i]),
-    "ramp_upd_mlp_lds_bytes": (c_sz, []),
-    "ramp_upd_nbr": (c_i, [c_p] * 8 + [c_i, c_p]),
-    "ramp_upd_linear": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
-    "ramp_upd_softagg_frag_rows": (c_sz, [c_i, c_i]),
-    "ramp_upd_softagg": (c_i, [c_p] * 10 + [c_i, c_p]),
-    "ramp_upd_softagg_finish": (c_i, [c_p] * 6 + [c_i, c_p]),
-    # the update operator at fp32 accuracy on the f16 matrix cores (csrc/update_x3.hip)
-    "ramp_x3_corr_mlp": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_p, ctypes.c_long,
-                               c_p, c_p, c_f, c_p, c_i, c_p]),
-    "ramp_x3_nbr": (c_i, [c_p] * 7 + [c_i, c_p]),
-    "ramp_x3_fg": (c_i, [c_p] * 9 + [c_i, c_p]),
-    "ramp_x3_segment_softmax": (c_i, [c_p] * 5 + [c_i, c_p]),
-    "ramp_x3_linear": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
-    "ramp_x3_gru": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, ctypes.POINTER(c_p), ctypes.POINTER(c_p), c_p, c_p, c_f,
-                          c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_p]),
-    # the whole operator as one call (csrc/update_op.hip)
-    "ramp_update_forward": (c_i, [ctypes.POINTER(UpdateArgs), c_p]),
-    # device-resident tracking step (csrc/track.hip); the ramp_track descriptor is mirrored in track_dev.py
-    "ramp_track_sizeof": (c_sz, []),
-    "ramp_track_plan_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
-    "ramp_track_ba_workspace_bytes": (c_sz, [c_i] * 6),
-    "ramp_track_plan": (c_i, [c_p, c_i, c_p]),
-    "ramp_track_step": (c_i, [c_p, c_i, c_i64, c_i, c_i, c_p, c_p, c_p]),
-    "ramp_track_warm": (c_i, [c_p, c_p, c_p]),
-    "ramp_stream_delay": (c_i, [c_i, c_p]),
-    "ramp_signal_alloc": (c_i, [c_p]),
-    "ramp_signal_free": (c_i, [c_p]),
-    "ramp_stream_signal": (c_i, [c_p, c_p, ctypes.c_uint32]),
-    "ramp_stream_wait_flag": (c_i, [c_p, c_p, ctypes.c_uint32, c_i, c_i, c_p]),
-    "ramp_host_device_pointer": (c_i, [c_p, c_p]),
-    # live poses (csrc/publish.hip); the record layout is mirrored in track_dev.py
-    "ramp_track_publish": (c_i, [c_p, c_i64, ctypes.c_double, c_p, c_i, c_p, c_p] + [c_i] * 8 + [c_p]),
-    "ramp_track_uncertainty_workspace_bytes": (c_sz, [c_p]),
-    "ramp_track_uncertainty": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    "ramp_track_map_workspace_bytes": (c_sz, [c_p]),
-    "ramp_track_map": (c_i, [c_p, c_i] + [c_p] * 7 + [c_p, c_sz, c_p]),
-    "ramp_trajectory_resolve": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
-    # poses at any time (csrc/interp.hip)
-    "ramp_se3_interp_workspace_bytes": (c_sz, [c_i]),
-    "ramp_se3_interp_lds_knots": (c_i, []),
-    "ramp_se3_interp": (c_i, [c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_sz, c_p, c_p]),
-    # motion-compensated events (csrc/warp.hip)
-    "ramp_event_warp_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "ramp_event_warp_grid_events": (ctypes.c_long, []),
-    "ramp_event_warp": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, ctypes.c_double, c_p, c_p, c_i, c_i, c_i, c_i,
-                              c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
-    # inverse-depth map from the window's patches (csrc/depthmap.hip)
-    "ramp_invdepth_map_workspace_bytes": (c_sz, [c_i]),
-    "ramp_invdepth_map_stage_records": (c_i, []),
-    "ramp_invdepth_map": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_f, c_f,
-                                c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
-    # event contrast and its gradient (csrc/contrast.hip)
-    "ramp_event_contrast_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
-    "ramp_event_contrast": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, ctypes.c_double, c_p, c_p, c_p, c_i, c_i, c_i,
-                                  c_p, c_p, c_p, c_p, c_p, c_sz, c_p, c_p]),
-    "ramp_event_align_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
-    "ramp_event_align": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, ctypes.c_double, c_p, c_p, c_p, c_i, c_i, c_i,
-                               c_i, ctypes.c_double, c_i, c_i] + [c_p] * 7 + [c_p, c_sz, c_p]),
-    # event voxel grids (csrc/voxel.hip)
-    "ramp_event_voxel_workspace_bytes": (c_sz, [c_i, c_i, c_i, c_i]),
-    "ramp_event_voxel_grid_events": (ctypes.c_long, []),
-    "ramp_event_voxel_lds_offsets": (c_i, []),
-    "ramp_event_voxel": (c_i, [c_p, c_p, c_p, c_p, ctypes.c_long, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_sz, c_p]),
-    # lens distortion (csrc/rectify.hip)
-    "ramp_event_rectify_grid_events": (ctypes.c_long, []),
-    "ramp_event_rectify": (c_i, [c_p, c_p, ctypes.c_long, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
-    "ramp_image_rectify": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
-    # event denoising (csrc/filter.hip)
-    "ramp_event_filter_workspace_bytes": (c_sz, [ctypes.c_long, c_i, c_i]),
-    "ramp_event_filter_grid_events": (ctypes.c_long, []),
-    "ramp_event_filter": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_i, c_i, c_i, ctypes.c_double, ctypes.c_double, c_i,
-                                ctypes.c_double] + [c_p] * 11 + [c_sz, c_p]),
-    # IMU preintegration and alignment (csrc/imu.hip)
-    "ramp_imu_workspace_bytes": (c_sz, [ctypes.c_long, c_i]),
-    "ramp_imu_preintegrate": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_p, c_i, c_i, c_p, c_p, ctypes.c_double, c_i, c_p, c_p, c_p]),
-    "ramp_imu_align": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_p, c_p, c_i, c_i, c_p, c_p, c_p, ctypes.c_double, ctypes.c_double,
-                             c_i, c_i] + [c_p] * 7 + [c_sz, c_p]),
-    # IMU propagation (csrc/imu_propagate.hip)
-    "ramp_imu_propagate_workspace_bytes": (c_sz, [ctypes.c_long]),
-    "ramp_imu_propagate": (c_i, [c_p, c_p, c_p, ctypes.c_long, c_p, c_p, c_p, ctypes.c_double, ctypes.c_double, c_i] + [c_p] * 5
-                           + [c_sz, c_p]),
-}
-
 _lib = None
 
 
@@ -278,15 +134,6 @@ def build(force=False, jobs=8):
         cmd.append("-B")
     subprocess.check_call(cmd + ["libramp_hip.so"])
     return LIB_PATH
-
-
-def register_optional(extra):
-    """late registration of signatures for optional translation units"""
-    SIGNATURES.update(extra)
-    if _lib is not None:
-        for name, (res, args) in extra.items():
-            fn = getattr(_lib, name)
-            fn.restype, fn.argtypes = res, args
 
 
 def lib():

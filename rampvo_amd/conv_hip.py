@@ -128,7 +128,7 @@ def pack_lstm_mfma(enc):
 
 
 # ------------------------------------------------------------------------ primitives
-IN_ACC_R = 8             # include/ramp_hip.h::RAMP_IN_ACC_R
+IN_ACC_R = _lib.RAMP_IN_ACC_R
 
 
 class Pending:

@@ -167,7 +167,7 @@ class TrackerQueries:
         else:
             ring.publish(None, counter, tstamp, poses=self.poses_, tstamps=self.tstamps_, n_rows=self.N,
                          n=self._n if n is None else n, row=max(self._n - 1, 0), E=len(self._hii),
-                         status=self._ba_flags & 3, dropped=dropped, t1=t1, t0=t0)
+                         status=self._ba_flags & track_dev.STATUS_BA, dropped=dropped, t1=t1, t0=t0)
 
     def trajectory(self, as_tensor=False):
         """what terminate() would return now -- (inverse poses [T,7], tstamps) -- as ONE launch (csrc/publish.hip::

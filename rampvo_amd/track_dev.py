@@ -15,19 +15,18 @@ import torch
 from . import _lib
 from ._lib import TrackWeights, _ptr_fields, c_i, c_p, c_sz
 
-DYN_WORDS = 32
-(DYN_N, DYN_NROW, DYN_E, DYN_KLO, DYN_FLO, DYN_W, DYN_REMOVED, DYN_K, DYN_NPREV, DYN_EPREV, DYN_EKEPT, DYN_STATUS,
- DYN_NLOG, DYN_FRAME) = range(14)
-DYN_FRAME2 = 31          # repeats DYN_FRAME in the other 64-byte half of the block (a torn lazy copy shows)
-LOG_WORDS = 12
+# include/ramp_hip.h's words of `dyn` and of a pose record, and the step flags, as _lib reads them from the header, under the names
+# this package uses: RAMP_DYN_N -> DYN_N, RAMP_POSE_FRAME -> POSE_FRAME, RAMP_TRAJ_UNRESOLVED -> TRAJ_UNRESOLVED, and
+# RAMP_TRACK_COMMIT ... RAMP_TRACK_UPDATE_POST -> COMMIT ... UPDATE_POST
+for _name, _value in _lib.CONSTANTS.items():
+    if _name.startswith(("RAMP_DYN_", "RAMP_POSE_", "RAMP_TRAJ_")):
+        globals()[_name[len("RAMP_"):]] = _value
+    elif _name.startswith("RAMP_TRACK_") and _name != "RAMP_TRACK_LOG":
+        globals()[_name[len("RAMP_TRACK_"):]] = _value
+LOG_WORDS = _lib.RAMP_TRACK_LOG     # floats per delta-log entry
+STATUS_BA = _lib.RAMP_STATUS_BA_STEP_DROPPED | _lib.RAMP_STATUS_BA_PAIR_OVERFLOW   # the DYN_STATUS bits a tracker goes on with
 MAX_AHEAD = 6            # frames the host may enqueue ahead of the newest lazy copy of the sizes (Ramp_vo._track_device)
-COMMIT, UPDATE, KEYFRAME, MM_GIVEN, WRAP_COORDS, COMPACT_COORDS, UPDATE_PRE, UPDATE_POST = 1, 2, 4, 8, 16, 32, 64, 128
 CORR_ROW = 896
-# a pose record (include/ramp_hip.h RAMP_POSE_*): 32 words, the frame tag in both 64-byte halves
-POSE_WORDS = 32
-(POSE_FRAME, POSE_N, POSE_E, POSE_STATUS, POSE_DROPPED, POSE_T1, POSE_T0, POSE_KF_TSTAMP, POSE_TSTAMP) = range(9)
-POSE_POSE, POSE_INV, POSE_FRAME2 = 16, 23, 31
-TRAJ_UNRESOLVED = 1
 
 
 class Track(ctypes.Structure):

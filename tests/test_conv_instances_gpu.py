@@ -38,10 +38,12 @@ import torch.nn as nn
 
 import roundref as rr
 from guarded import Guarded
+from rampvo_amd._lib import (RAMP_TILE_FP8 as FP8, RAMP_TILE_PAIRED as PAIRED, RAMP_TILE_SINGLE as SINGLE,
+                             RAMP_TILE_TAIL as TAIL)
 
 pytestmark = pytest.mark.gpu
 
-PLAIN, FP8, TAIL, SINGLE, PAIRED = 0, 1, 2, 4, 8      # include/ramp_hip.h::RAMP_TILE_*
+PLAIN = 0                    # a row's instance without a RAMP_TILE_* bit
 MAT_CANARY = -3.0            # a tail pixel is a ReLU's output: never negative
 ACC_CANARY = 0x5A5A5A5A5A5A5A
 # |mean - mean64| / rms and |var - var64| / mean square of the raw output (test_fp16_rounding_gpu.py::IN_STATS_TOL's

@@ -57,14 +57,15 @@ def _layout_mismatches(structs, tmp_path):
 
 
 def test_track_descriptor_mirror_matches_the_c_layout(tmp_path):
-    """track_dev.Track, _lib.TrackWeights / UpdateArgs and conv_hip.ConvJob mirror include/ramp_hip.h's ramp_track /
-    ramp_track_weights / ramp_update_args / ramp_conv_job by hand: the system C compiler's sizeof and offsetof of every field
+    """track_dev.Track, _lib.TrackWeights / UpdateArgs / CorrLevel and conv_hip.ConvJob mirror include/ramp_hip.h's ramp_track /
+    ramp_track_weights / ramp_update_args / ramp_corr_level / ramp_conv_job by hand: the system C compiler's sizeof and offsetof of every field
     the ctypes mirror names equal the ctypes ones, field by field in the mirror's order"""
     from rampvo_amd import _lib, conv_hip, track_dev
     assert track_dev.TrackWeights is _lib.TrackWeights
     assert "relu_t" not in [n for n, _ in track_dev.Track._fields_]
     structs = (("ramp_track", track_dev.Track), ("ramp_track_weights", _lib.TrackWeights),
-               ("ramp_update_args", _lib.UpdateArgs), ("ramp_conv_job", conv_hip.ConvJob))
+               ("ramp_update_args", _lib.UpdateArgs), ("ramp_conv_job", conv_hip.ConvJob),
+               ("ramp_corr_level", _lib.CorrLevel))
     for name, g, w in _layout_mismatches(structs, tmp_path):
         assert g == w, "%s: C %s, ctypes %s" % (name, g, w)
 
@@ -80,6 +81,106 @@ def test_update_args_layout_check_sees_a_swapped_field_pair(tmp_path):
     swapped = type("SwappedUpdateArgs", (ctypes.Structure,), {"_fields_": fields})
     bad = _layout_mismatches((("ramp_update_args", swapped),), tmp_path)
     assert {"ramp_update_args.hij", "ramp_update_args.kk_cap"} <= {name for name, _, _ in bad}
+
+
+def test_header_constants_equal_the_c_compilers_values(tmp_path):
+    """every RAMP_* value macro _lib reads from include/ramp_hip.h has the value the system C compiler gives it (an f-suffixed
+    literal: as a float32 on both sides), and the reader saw every `#define RAMP_` line that carries a value"""
+    import shutil
+    import subprocess
+    from rampvo_amd import _lib
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    assert cc, "no C compiler on PATH"
+    lines = [l.split() for l in open(_lib.HEADER) if l.startswith("#define RAMP_")]
+    literal = {t[1]: t[2] for t in lines if len(t) > 2 and not t[2].startswith("/*")}
+    assert sorted(literal) == sorted(_lib.CONSTANTS) and len(literal) > 100
+    names = sorted(literal)
+    src, exe = tmp_path / "constants.c", tmp_path / "constants"
+    src.write_text('#include "ramp_hip.h"\n#include <stdio.h>\nint main(void) {\n' + "".join(
+        '  printf("%%.17g\\n", (double)(%s));\n' % n for n in names) + "  return 0;\n}\n")
+    subprocess.run([cc, "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
+    assert len(got) == len(names)
+    for n, g in zip(names, got):
+        mine = _lib.CONSTANTS[n]
+        assert getattr(_lib, n) is mine
+        if isinstance(mine, int):
+            assert float(g) == mine and float(g).is_integer(), (n, g, mine)
+        elif literal[n][-1] in "fF":
+            assert np.float32(float(g)) == np.float32(mine), (n, g, mine)
+        else:
+            assert float(g) == mine, (n, g, mine)
+    assert _lib.RAMP_WARP_MIN_Z == 0.2 and _lib.RAMP_RECTIFY_TOL == 2.0 ** -6 and _lib.RAMP_CORR_X2 == 128
+    assert {rc: text.split()[0] for rc, text in _lib._ERR.items()} == {
+        _lib.RAMP_EINVAL: "RAMP_EINVAL", _lib.RAMP_ELAUNCH: "RAMP_ELAUNCH", _lib.RAMP_EWORKSPACE: "RAMP_EWORKSPACE",
+        _lib.RAMP_EUNSUPPORTED: "RAMP_EUNSUPPORTED"}
+
+
+_SYNTHETIC_HEADER = """
+#define RAMP_SYN_H
+#define RAMP_SYN_A 3
+#define RAMP_SYN_B -0x10  /* a comment that runs
+                             over two lines */
+#define RAMP_SYN_C 0.25f
+/* int ramp_syn_commented(int a); */
+typedef struct ramp_syn_thing {
+  int a;          /* ramp_syn_field(int x); */
+  const void *p;
+} ramp_syn_thing;
+const char *ramp_syn_name(void);
+size_t ramp_syn_bytes(const float *x, void *y, const ramp_syn_thing *const *t, int a, int32_t b, int64_t c);
+long ramp_syn_many(long a, size_t b,
+                   uint32_t c, float d, /* optional */
+                   double e, const int v[3]);
+"""
+
+
+def test_header_reader_on_a_synthetic_header():
+    """_lib.parse_header on a header with one parameter of every kind: exactly the expected constants and signatures, nothing
+    from a comment or a struct body, and a type or a literal it does not know raises (nothing defaults to int)"""
+    from rampvo_amd import _lib
+    c = ctypes
+    constants, signatures = _lib.parse_header(_SYNTHETIC_HEADER)
+    assert constants == {"RAMP_SYN_A": 3, "RAMP_SYN_B": -16, "RAMP_SYN_C": 0.25}
+    assert [type(constants[k]) for k in ("RAMP_SYN_A", "RAMP_SYN_B", "RAMP_SYN_C")] == [int, int, float]
+    assert signatures == {
+        "ramp_syn_name": (c.c_char_p, []),
+        "ramp_syn_bytes": (c.c_size_t, [c.c_void_p, c.c_void_p, c.c_void_p, c.c_int, c.c_int32, c.c_int64]),
+        "ramp_syn_many": (c.c_long, [c.c_long, c.c_size_t, c.c_uint32, c.c_float, c.c_double, c.c_void_p])}
+    for bad in ("int ramp_syn_bad(short a);", "int ramp_syn_bad(int);", "short ramp_syn_bad(int a);",
+                "void *ramp_syn_bad(int a);", "#define RAMP_SYN_BAD (1 << 3)\n", "#define RAMP_SYN_BAD(x) 3\n"):
+        with pytest.raises(RuntimeError):
+            _lib.parse_header(bad)
+
+
+def test_header_reader_on_the_whole_header():
+    """every ramp_* declaration the export test finds has a signature and there is no other; four of the longest argument
+    lists, written out here by hand from the header text (p pointer, i int, l long, z size_t, f float, d double)"""
+    from rampvo_amd import _lib
+    header = open(_lib.HEADER).read()
+    declared = set(re.findall(r"\b(ramp_[a-z0-9_]+)\s*\(", header)) - {"ramp_corr_level"}
+    assert len(declared) > 100 and declared <= set(_lib.SIGNATURES)
+    assert set(re.findall(r"\b(ramp_\w+)\s*\(", header)) == set(_lib.SIGNATURES)       # (\w: ramp_se3_adjT has a capital)
+    letter = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "z": ctypes.c_size_t, "f": ctypes.c_float,
+              "d": ctypes.c_double}
+    for name, args in (("ramp_event_warp", "pppp i pp i d pp iiii ppppp z pp"),
+                       ("ramp_invdepth_map", "pppp iii f pp i p ii pp ff iii pppp z pp"),
+                       ("ramp_event_filter", "ppp l iii dd i d ppppppppppp z p"),
+                       ("ramp_imu_propagate", "ppp l ppp dd i ppppp z p")):
+        res, argtypes = _lib.SIGNATURES[name]
+        assert res is ctypes.c_int and argtypes == [letter[a] for a in args.replace(" ", "")], name
+    assert len(_lib.SIGNATURES["ramp_event_warp"][1]) == 23 and _lib.SIGNATURES["ramp_event_warp"][1][8] is ctypes.c_double
+    assert len(_lib.SIGNATURES["ramp_invdepth_map"][1]) == 28
+    assert _lib.SIGNATURES["ramp_version"] == (ctypes.c_char_p, [])
+    assert _lib.SIGNATURES["ramp_event_warp_grid_events"] == (ctypes.c_long, [])
+    assert _lib.SIGNATURES["ramp_stream_signal"][1] == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]
+
+
+def test_a_missing_header_is_named(monkeypatch, tmp_path):
+    from rampvo_amd import _lib
+    monkeypatch.setattr(_lib, "HEADER", str(tmp_path / "nowhere" / "ramp_hip.h"))
+    with pytest.raises(RuntimeError, match="nowhere"):
+        _lib._read_header()
 
 
 def test_gru_tile_rows_follow_the_round_rule_at_its_edges():

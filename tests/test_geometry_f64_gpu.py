@@ -23,10 +23,10 @@ import torch
 
 import georef as gr
 import oracle as orc
+from rampvo_amd._lib import RAMP_EINVAL as EINVAL, RAMP_EUNSUPPORTED as EUNSUPPORTED
 
 pytestmark = pytest.mark.gpu
 
-EINVAL, EUNSUPPORTED = -1, -4
 CANARY = 0x7fc0beef                      # a NaN pattern: a write of any float shows, and so does a read that propagates
 
 

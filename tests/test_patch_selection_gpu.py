@@ -11,11 +11,11 @@ import pytest
 import torch
 
 import selectref as sr
+from rampvo_amd._lib import RAMP_EUNSUPPORTED, RAMP_EWORKSPACE
 
 pytestmark = pytest.mark.gpu
 
 CANARY = -777.25
-RAMP_EWORKSPACE, RAMP_EUNSUPPORTED = -3, -4          # include/ramp_hip.h
 _ref = {}
 
 

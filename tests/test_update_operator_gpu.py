@@ -8,9 +8,10 @@ import ctypes
 import pytest
 import torch
 
+from rampvo_amd._lib import RAMP_EINVAL
+
 pytestmark = pytest.mark.gpu
 
-RAMP_EINVAL = -1
 SIZES = [1, 63, 64, 65, 1003]          # one row, both sides of the 64-row tile, a ragged tail
 WD, HT = 40.0, 30.0
 
