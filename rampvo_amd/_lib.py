@@ -217,3 +217,10 @@ def workspace(nbytes, device, tag="ws"):
         buf = torch.empty(max(int(nbytes * 1.25), 1 << 20), dtype=torch.uint8, device=device)
         _ws_cache[key] = buf
     return buf
+
+
+def sized_workspace(query, dims, device, tag="ws"):
+    """(buffer, nbytes): the scratch buffer of ``workspace`` for an entry point whose size query ``lib().<query>(*dims)``
+    returns ``nbytes`` -- the bytes the entry point is told it has (the buffer may be larger)"""
+    nbytes = getattr(lib(), query)(*dims)
+    return workspace(nbytes, device, tag), nbytes

@@ -41,7 +41,6 @@
 #define BA_TS 64      // SYRK tile
 #define BA_KB 8       // SYRK k batch
 
-static inline size_t al(size_t x) { return (x + 255) / 256 * 256; }
 
 // ------------------------------------------------------------------ K1
 // The per-edge record: residual, validity, Jacobians (32 floats).  ba_edge_kernel writes it to memory (the path without
@@ -1315,9 +1314,7 @@ static size_t ba_carve(void *ws, int E, int n_poses, int n_patches, int N, int o
                        int max_patches, int max_pairs, BaWs *w) {
   const size_t e = (size_t)(E > 0 ? E : 1);
   const int n6 = 6 * N;
-  size_t off = 0;
-  char *base = (char *)ws;
-  auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += al(bytes); return (void *)p; };
+  WsCarver c(ws);
   w->Mu_b = (int)((size_t)n_patches < e ? (size_t)n_patches : e);
   if (max_patches > 0 && max_patches < w->Mu_b) w->Mu_b = max_patches;
   if (w->Mu_b < 1) w->Mu_b = 1;
@@ -1334,29 +1331,29 @@ static size_t ba_carve(void *ws, int E, int n_poses, int n_patches, int N, int o
   w->order_k = w->seg_k = w->order_p = w->seg_p = nullptr;
   if (own_groups) {
     w->gb_bytes = ramp_internal_group_by_ws(E);
-    w->gb = take(w->gb_bytes);
-    w->pkeys = (int64_t *)take(e * 8);
-    w->kx = (int64_t *)take(e * 8);
-    w->pukeys = (int64_t *)take(e * 8);
-    w->order_k = (int32_t *)take(e * 4);
-    w->seg_k = (int32_t *)take((e + 1) * 4);
-    w->order_p = (int32_t *)take(e * 4);
-    w->seg_p = (int32_t *)take((e + 1) * 4);
+    w->gb = c.take<char>(w->gb_bytes, 256);
+    w->pkeys = c.take<int64_t>(e, 256);
+    w->kx = c.take<int64_t>(e, 256);
+    w->pukeys = c.take<int64_t>(e, 256);
+    w->order_k = c.take<int32_t>(e, 256);
+    w->seg_k = c.take<int32_t>(e + 1, 256);
+    w->order_p = c.take<int32_t>(e, 256);
+    w->seg_p = c.take<int32_t>(e + 1, 256);
   }
-  w->pair_ij = (int32_t *)take((size_t)w->Gp_b * 8);
-  w->counters = (int32_t *)take(64);
-  w->rec = (float *)take(e * BA_REC * 4);
-  w->Erow = (float *)take((size_t)w->Mu_b * (n6 > 0 ? n6 : 1) * 4);
-  w->Cv = (float *)take((size_t)w->Mu_b * 4);
-  w->uv = (float *)take((size_t)w->Mu_b * 4);
-  w->Qv = (float *)take((size_t)w->Mu_b * 4);
-  w->pairs = (float *)take((size_t)w->Gp_b * BA_PAIR * 4);
-  w->S_part = (float *)take((size_t)w->KS * (n6 * n6 + 1) * 4);
-  w->y_part = (float *)take((size_t)w->KS * (n6 + 1) * 4);
-  w->S = (float *)take((size_t)(n6 * n6 + 1) * 4);
-  w->yv = (float *)take((size_t)(n6 + 1) * 4);
-  w->dX = (float *)take((size_t)(n6 + 1) * 4);
-  return off;
+  w->pair_ij = c.take<int32_t>((size_t)w->Gp_b * 2, 256);
+  w->counters = c.take<int32_t>(16, 256);
+  w->rec = c.take<float>(e * BA_REC, 256);
+  w->Erow = c.take<float>((size_t)w->Mu_b * (n6 > 0 ? n6 : 1), 256);
+  w->Cv = c.take<float>((size_t)w->Mu_b, 256);
+  w->uv = c.take<float>((size_t)w->Mu_b, 256);
+  w->Qv = c.take<float>((size_t)w->Mu_b, 256);
+  w->pairs = c.take<float>((size_t)w->Gp_b * BA_PAIR, 256);
+  w->S_part = c.take<float>((size_t)w->KS * (n6 * n6 + 1), 256);
+  w->y_part = c.take<float>((size_t)w->KS * (n6 + 1), 256);
+  w->S = c.take<float>((size_t)(n6 * n6 + 1), 256);
+  w->yv = c.take<float>((size_t)(n6 + 1), 256);
+  w->dX = c.take<float>((size_t)(n6 + 1), 256);
+  return c.bytes();
 }
 
 static BaEdgeIn ba_edge_in(const BaProblem &p) {
@@ -1432,16 +1429,15 @@ struct BaCovWs { float *Linv, *LinvT, *cpart; int32_t *npart, *flag; };
 // what a covariance call writes; ws: its own workspace (the dyn form), or nullptr: the buffers follow BA's in the call's
 // map.point != nullptr: the map stage C4 runs behind C3
 struct BaCovOut { float *cov, *depth_var, *stats; void *ws; size_t ws_bytes; BaMapOut map; };
-static size_t ba_cov_carve(void *ws, int n6, int Mu_b, BaCovWs *c) {
-  size_t off = 0;
-  char *base = (char *)ws;
-  auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += al(bytes); return (void *)p; };
-  c->Linv = (float *)take((size_t)(n6 * n6 + 1) * 4);
-  c->LinvT = (float *)take((size_t)(n6 * n6 + 1) * 4);
-  c->cpart = (float *)take((size_t)Mu_b * 4);
-  c->npart = (int32_t *)take((size_t)Mu_b * 4);
-  c->flag = (int32_t *)take(64);
-  return off;
+// at: where the blocks start in ws -- 0 in a workspace of their own, BA's bytes behind BA's; returns where they end
+static size_t ba_cov_carve(void *ws, size_t at, int n6, int Mu_b, BaCovWs *w) {
+  WsCarver c(ws, at);
+  w->Linv = c.take<float>((size_t)(n6 * n6 + 1), 256);
+  w->LinvT = c.take<float>((size_t)(n6 * n6 + 1), 256);
+  w->cpart = c.take<float>((size_t)Mu_b, 256);
+  w->npart = c.take<int32_t>((size_t)Mu_b, 256);
+  w->flag = c.take<int32_t>(16, 256);
+  return c.bytes();
 }
 static int ba_cov_run(const BaProblem &p, const BaGroups &g, BaWs &w, BaCovWs &c, const BaCovOut &out, int32_t *info,
                       hipStream_t st) {
@@ -1502,9 +1498,9 @@ static int ba_carve_checked(void *ws, size_t ws_bytes, const BaProblem &p, const
   const int N = p.t1 - p.t0;
   size_t a = ba_carve(ws, p.E, p.n_poses, p.n_patches, N, !plan, plan ? plan->max_patches : 0, plan ? plan->max_pairs : 0, &w);
   if (out && out->ws) {
-    if (ba_cov_carve(out->ws, 6 * N, w.Mu_b, &c) > out->ws_bytes) return RAMP_EWORKSPACE;
+    if (ba_cov_carve(out->ws, 0, 6 * N, w.Mu_b, &c) > out->ws_bytes) return RAMP_EWORKSPACE;
   } else if (out) {
-    a += ba_cov_carve((char *)ws + a, 6 * N, w.Mu_b, &c);
+    a = ba_cov_carve(ws, a, 6 * N, w.Mu_b, &c);
   }
   return a > ws_bytes ? RAMP_EWORKSPACE : RAMP_OK;
 }
@@ -1539,7 +1535,7 @@ static size_t ba_ws_bytes(int E, int n_poses, int n_patches, int N, int own_grou
   BaCovWs c;
   if (N < 0) N = 0;
   const size_t a = ba_carve(nullptr, E, n_poses, n_patches, N, own_groups, max_patches, max_pairs, &w);
-  return cov ? a + ba_cov_carve(nullptr, 6 * N, w.Mu_b, &c) : a;
+  return cov ? ba_cov_carve(nullptr, a, 6 * N, w.Mu_b, &c) : a;
 }
 
 // ---- device-side sizes (csrc/track.hip): the window [max(n - opt_window, 1), n) with n = dyn[RAMP_DYN_N] and the
@@ -1560,7 +1556,7 @@ int ramp_i_ba_dyn(const BaProblem &p, const BaGroups &g, int iterations, void *w
 }
 size_t ramp_i_ba_cov_dyn_ws(int opt_window, int max_patches) {
   BaCovWs c;
-  return ba_cov_carve(nullptr, 6 * opt_window, max_patches > 0 ? max_patches : 1, &c);
+  return ba_cov_carve(nullptr, 0, 6 * opt_window, max_patches > 0 ? max_patches : 1, &c);
 }
 // ba_ws: ramp_i_ba_dyn's
 int ramp_i_ba_cov_dyn(const BaProblem &p, const BaGroups &g, void *ba_ws, size_t ba_ws_bytes, void *cov_ws,

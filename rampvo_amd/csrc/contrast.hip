@@ -328,11 +328,10 @@ static int con_launch_events(const ConArgs &a, bool lds_times, bool vec, int gri
 
 // one evaluation: the memset of the counters (the two sums among them) and, behind them, the accumulators; the segment launch
 // when `segments`; the splat, the finish, the gradient when `grad`, the final kernel
-static int con_evaluate(const ConArgs &a, bool segments, float *iwe, long long *sums, double *stats, double *grad, int32_t *status,
-                        hipStream_t st) {
+static int con_evaluate(const ConArgs &a, double *fin, bool segments, float *iwe, long long *sums, double *stats, double *grad,
+                        int32_t *status, hipStream_t st) {
   const size_t HW = (size_t)a.H * a.W;
-  double *fin = (double *)(a.acc + 2 * HW);
-  if (hipMemsetAsync(a.ctr, 0, WARP_CTR_WORDS * sizeof(int32_t) + 2 * HW * sizeof(long long), st) != hipSuccess) return RAMP_ELAUNCH;
+  if (hipMemsetAsync(a.ctr, 0, ws_span(a.ctr, fin), st) != hipSuccess) return RAMP_ELAUNCH;      // (fin: the block behind acc)
   int rc = RAMP_OK;
   if (segments) {
     rc = ramp_i_warp_segments(a.knots, a.times, a.T, a.t_ref, a.extrapolate, const_cast<float *>(a.seg), const_cast<float *>(a.ref),
@@ -358,19 +357,26 @@ static int con_evaluate(const ConArgs &a, bool segments, float *iwe, long long *
   return RAMP_OK;
 }
 
-// the arguments both entries share -> ConArgs over the workspace layout: seg, ref | ctr | acc | fin | rows
+// the contrast's workspace: the warp's with the image accumulator alone (seg, ref | ctr | acc), then, packed, fin | rows
+struct ConWs {
+  WarpWs warp;
+  double *fin, *rows;
+};
+static size_t con_carve(void *ws, int T, int H, int W, ConWs *w) {
+  WsCarver c(ws, warp_carve(ws, T, (size_t)2 * H * W, 0, &w->warp));
+  w->fin = c.take<double>((size_t)CON_FIN_MAX_GROUPS * 2, 1);
+  w->rows = c.take<double>((size_t)WARP_MAX_GROUPS * CON_ROW_WORDS, 1);
+  return c.bytes();
+}
+
+// the arguments both entries share -> ConArgs over the carved workspace
 static ConArgs con_arguments(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
                              const double *times, int T, double t_ref, const float *intrinsics, const float *invdepth,
-                             const float *correction, int flags, int H, int W, void *ws) {
-  const size_t HW = (size_t)H * W;
-  unsigned char *base = (unsigned char *)ws;
-  float *seg = (float *)base, *ref = seg + (size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS;
-  int32_t *ctr = (int32_t *)(base + warp_acc_offset(T));
-  long long *acc = (long long *)(ctr + WARP_CTR_WORDS);
-  double *fin = (double *)(acc + 2 * HW), *rows = fin + (size_t)CON_FIN_MAX_GROUPS * 2;
+                             const float *correction, int flags, int H, int W, const ConWs &w) {
   ConArgs a;
-  a.x = x; a.y = y; a.t = t; a.p = p; a.knots = knots; a.times = times; a.seg = seg; a.ref = ref;
-  a.intrinsics = intrinsics; a.invdepth = invdepth; a.correction = correction; a.acc = acc; a.ctr = ctr; a.rows = rows;
+  a.x = x; a.y = y; a.t = t; a.p = p; a.knots = knots; a.times = times; a.seg = w.warp.seg; a.ref = w.warp.ref;
+  a.intrinsics = intrinsics; a.invdepth = invdepth; a.correction = correction; a.acc = w.warp.acc_iwe; a.ctr = w.warp.ctr;
+  a.rows = w.rows;
   a.t_ref = t_ref; a.N = N; a.T = T; a.H = H; a.W = W; a.extrapolate = (flags & RAMP_INTERP_EXTRAPOLATE) ? 1 : 0;
   a.depth_map = (flags & RAMP_WARP_DEPTH_MAP) ? 1 : 0;
   a.plane = (flags & RAMP_CONTRAST_UNSIGNED) ? 1 : 0;
@@ -491,13 +497,22 @@ __global__ void __launch_bounds__(RAMP_WAVE)
   if (lane < 4) out.result[lane] = lane == 0 ? f : lane == 1 ? f0 : lane == 2 ? length : 0.0;
 }
 
-static size_t align_state_offset(int T, int H, int W) { return (ramp_event_contrast_workspace_bytes(T, H, W) + 15) & ~(size_t)15; }
+// the alignment's workspace: the contrast's, then the state on the next multiple of 16
+struct AlignWs {
+  ConWs con;
+  AlignState *state;
+};
+static size_t align_carve(void *ws, int T, int H, int W, AlignWs *w) {
+  WsCarver c(ws, round_up(con_carve(ws, T, H, W, &w->con), 16));
+  w->state = c.take<AlignState>(1, 1);
+  return c.bytes();
+}
 
 extern "C" {
 size_t ramp_event_contrast_workspace_bytes(int T, int H, int W) {
   if (H < 1 || W < 1) return 0;
-  return warp_acc_offset(T) + WARP_CTR_WORDS * sizeof(int32_t) + (size_t)2 * H * W * sizeof(long long) +
-         (size_t)CON_FIN_MAX_GROUPS * 2 * sizeof(double) + (size_t)WARP_MAX_GROUPS * CON_ROW_WORDS * sizeof(double);
+  ConWs w;
+  return con_carve(nullptr, T, H, W, &w);
 }
 
 int ramp_event_contrast(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
@@ -511,14 +526,16 @@ int ramp_event_contrast(const float *x, const float *y, const double *t, const i
   if (!x || !y || !t || !p || !knots || !times || !intrinsics || !invdepth || !sums || !stats || !ws || !status) return RAMP_EINVAL;
   if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)sums & 7) != 0 || ((uintptr_t)stats & 7) != 0 || ((uintptr_t)grad & 7) != 0)
     return RAMP_EINVAL;
-  if (ws_bytes < ramp_event_contrast_workspace_bytes(T, H, W)) return RAMP_EWORKSPACE;
-  const ConArgs a = con_arguments(x, y, t, p, N, knots, times, T, t_ref, intrinsics, invdepth, correction, flags, H, W, ws);
-  return con_evaluate(a, true, iwe, (long long *)sums, stats, grad, status, (hipStream_t)stream);
+  ConWs w;
+  if (ws_bytes < con_carve(ws, T, H, W, &w)) return RAMP_EWORKSPACE;
+  const ConArgs a = con_arguments(x, y, t, p, N, knots, times, T, t_ref, intrinsics, invdepth, correction, flags, H, W, w);
+  return con_evaluate(a, w.fin, true, iwe, (long long *)sums, stats, grad, status, (hipStream_t)stream);
 }
 
 size_t ramp_event_align_workspace_bytes(int T, int H, int W) {
   if (T < 1 || H < 1 || W < 1) return 0;
-  return align_state_offset(T, H, W) + sizeof(AlignState);
+  AlignWs w;
+  return align_carve(nullptr, T, H, W, &w);
 }
 
 int ramp_event_align(const float *x, const float *y, const double *t, const int8_t *p, int N, const float *knots,
@@ -535,21 +552,22 @@ int ramp_event_align(const float *x, const float *y, const double *t, const int8
   if (((uintptr_t)ws & 15) != 0 || (((uintptr_t)correction_out | (uintptr_t)result | (uintptr_t)grad | (uintptr_t)history) & 7) != 0 ||
       (((uintptr_t)correction | (uintptr_t)correction_f32 | (uintptr_t)status | (uintptr_t)info) & 3) != 0)
     return RAMP_EINVAL;
-  if (ws_bytes < ramp_event_align_workspace_bytes(T, H, W)) return RAMP_EWORKSPACE;
+  AlignWs w;
+  if (ws_bytes < align_carve(ws, T, H, W, &w)) return RAMP_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   const int need = 1 + RAMP_ALIGN_TRIALS * iters;
   const int evals = N == 0 ? 1 : (max_evals < need ? max_evals : need);
-  AlignState *s = (AlignState *)((unsigned char *)ws + align_state_offset(T, H, W));
+  AlignState *s = w.state;
   // the invariant front: the state zeroed (reason 0, the done word 0), the start in the buffer evaluation 0 reads
   if (hipMemsetAsync(s, 0, sizeof(AlignState), st) != hipSuccess) return RAMP_ELAUNCH;
   if (correction && hipMemcpyAsync(s->cor, correction, 7 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
     return RAMP_ELAUNCH;
-  ConArgs a = con_arguments(x, y, t, p, N, knots, times, T, t_ref, intrinsics, invdepth, s->cor, flags, H, W, ws);
+  ConArgs a = con_arguments(x, y, t, p, N, knots, times, T, t_ref, intrinsics, invdepth, s->cor, flags, H, W, w.con);
   a.done = s->done;
   const AlignOut out = {correction_out, correction_f32, result, grad, history, status, info};
   for (int e = 0; e < evals; e++) {
     if (N > 0) {
-      const int rc = con_evaluate(a, e == 0, nullptr, s->e_sums, s->e_stats, s->e_grad, s->e_status, st);
+      const int rc = con_evaluate(a, w.con.fin, e == 0, nullptr, s->e_sums, s->e_stats, s->e_grad, s->e_status, st);
       if (rc != RAMP_OK) return rc;
     }
     hipLaunchKernelGGL(align_step_kernel, dim3(1), dim3(RAMP_WAVE), 0, st, s, e, e == evals - 1 ? 1 : 0, iters, free_mask, step,

@@ -13,6 +13,7 @@
 // contributed w = 0 exactly (see dm_cull_margin) and every term is >= 0, so leaving it out changes no bit: a pixel's value
 // depends neither on the tile shape nor on the chunking, and a call repeats its bits.
 #include "ramp_device.h"
+#include "workspace.h"
 
 #define DM_THREADS 256
 #define DM_TILE_W 32
@@ -209,11 +210,24 @@ static int dm_record_capacity(int n, int K, bool has_index, int per_row, int las
   return n;
 }
 
+// the workspace for K records, packed: the header words | the records
+struct DmWs {
+  int32_t *hdr;
+  float4 *rec;
+};
+static size_t dm_carve(void *ws, int K, DmWs *w) {
+  WsCarver c(ws);
+  w->hdr = c.take<int32_t>(DM_HDR_WORDS, 1);
+  w->rec = c.take<float4>((size_t)(K > 0 ? K : 0), 1);
+  return c.bytes();
+}
+
 extern "C" {
 int ramp_invdepth_map_stage_records(void) { return DM_STAGE; }
 
 size_t ramp_invdepth_map_workspace_bytes(int K) {
-  return DM_HDR_WORDS * sizeof(int32_t) + (size_t)(K > 0 ? K : 0) * sizeof(float4);
+  DmWs w;
+  return dm_carve(nullptr, K, &w);
 }
 
 int ramp_invdepth_map(const float *poses, const float *patches, const float *intrinsics, const float *cam, int n, int M, int P,
@@ -233,14 +247,15 @@ int ramp_invdepth_map(const float *poses, const float *patches, const float *int
   if (((uintptr_t)ws & 15) != 0) return RAMP_EINVAL;
   if (ramp_cdiv(H, DM_TILE_H) > 65535) return RAMP_EUNSUPPORTED;           // (the tile rows are the grid's y)
   const int Kc = dm_record_capacity(n, K, index != nullptr, per_row, last_rows);
-  if (ws_bytes < ramp_invdepth_map_workspace_bytes(Kc)) return RAMP_EWORKSPACE;
+  DmWs w;
+  if (ws_bytes < dm_carve(ws, Kc, &w)) return RAMP_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   // the one memset: the status words are the counters
   if (hipMemsetAsync(status, 0, 8 * sizeof(int32_t), st) != hipSuccess) return RAMP_ELAUNCH;
   DmProject a;
   a.poses = poses; a.patches = patches; a.intrinsics = intrinsics; a.cam = cam; a.conf = conf;
   a.index = index; a.count = count; a.dyn_rows = dyn_rows;
-  a.hdr = (int32_t *)ws; a.rec = (float4 *)((int32_t *)ws + DM_HDR_WORDS); a.status = status; a.records = records;
+  a.hdr = w.hdr; a.rec = w.rec; a.status = status; a.records = records;
   a.scale = scale; a.R = radius; a.n = n; a.K = Kc; a.M = M; a.PP = P * P; a.ctr = (P / 2) * P + P / 2;
   a.per_row = per_row; a.last_rows = last_rows; a.conf_is_variance = (flags & RAMP_DEPTHMAP_CONF_IS_VARIANCE) ? 1 : 0;
   a.H = H; a.W = W;

@@ -5,6 +5,7 @@
 // Integer pixel coordinates only (the reference's uint16 path): the accumulation is an integer
 // atomic add, so the result does not depend on the order the events arrive in.
 #include "ramp_device.h"
+#include "workspace.h"
 
 __global__ void __launch_bounds__(256)
     event_scatter_kernel(const int32_t *__restrict__ x, const int32_t *__restrict__ y, const int8_t *__restrict__ p,
@@ -26,22 +27,33 @@ __global__ void __launch_bounds__(256)
   if (outf) outf[i] = (float)v;
 }
 
+// the workspace: the int32 grid
+static size_t stack_carve(void *ws, int bins, int H, int W, int32_t **grid) {
+  WsCarver c(ws);
+  *grid = c.take<int32_t>((size_t)bins * H * W, 1);
+  return c.bytes();
+}
+
 extern "C" {
 
-size_t ramp_event_stack_workspace_bytes(int bins, int H, int W) { return (size_t)bins * H * W * sizeof(int32_t); }
+size_t ramp_event_stack_workspace_bytes(int bins, int H, int W) {
+  int32_t *grid;
+  return stack_carve(nullptr, bins, H, W, &grid);
+}
 
 int ramp_event_stack(const int32_t *x, const int32_t *y, const int8_t *p, int N, int bins, int H, int W,
                      int8_t *out_i8, float *out_f32, void *ws, size_t ws_bytes, void *stream) {
   if (N < 0 || bins <= 0 || H <= 0 || W <= 0 || (!out_i8 && !out_f32) || !ws) return RAMP_EINVAL;
-  if (ws_bytes < ramp_event_stack_workspace_bytes(bins, H, W)) return RAMP_EWORKSPACE;
+  int32_t *grid;
+  const size_t need = stack_carve(ws, bins, H, W, &grid);
+  if (ws_bytes < need) return RAMP_EWORKSPACE;
   if (N > 0 && (!x || !y || !p)) return RAMP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   const long n = (long)bins * H * W;
-  if (hipMemsetAsync(ws, 0, (size_t)n * sizeof(int32_t), st) != hipSuccess) return RAMP_ELAUNCH;
+  if (hipMemsetAsync(grid, 0, need, st) != hipSuccess) return RAMP_ELAUNCH;
   if (N >= 2)     // fewer than 2 events: an empty grid (transformers.py:151-152)
-    hipLaunchKernelGGL(event_scatter_kernel, dim3(ramp_cdiv(N, 256)), dim3(256), 0, st, x, y, p, (int32_t *)ws, N,
-                       bins, H, W);
-  hipLaunchKernelGGL(event_cast_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int32_t *)ws,
+    hipLaunchKernelGGL(event_scatter_kernel, dim3(ramp_cdiv(N, 256)), dim3(256), 0, st, x, y, p, grid, N, bins, H, W);
+  hipLaunchKernelGGL(event_cast_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int32_t *)grid,
                      out_i8, out_f32, n);
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;

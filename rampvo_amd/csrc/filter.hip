@@ -20,7 +20,7 @@
 // No floating-point atomics; every loop is a binary search or has a fixed trip count.  Within a segment the index rises and the
 // time stamp does not fall (the order check), so (t, index) rises lexicographically and "the last entry that precedes the
 // event" is a partition point.
-#include <hipcub/hipcub.hpp>
+#include "workspace_cub.h"
 #include "ramp_internal.h"
 #include "interp_device.h"
 
@@ -28,8 +28,6 @@
 #define FLT_WAVES (INTERP_THREADS / RAMP_WAVE)
 #define FLT_CTR_WORDS 16                 // int32: the 8 status words, 8 spare; behind them two int64: n, S2
 #define FLT_FLT_MAX 3.4028234663852886e38f
-
-static size_t flt_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static __device__ __forceinline__ double flt_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
@@ -289,16 +287,8 @@ static int flt_sort_bits(uint32_t HW) {                    // ceil(log2(H W + 1)
   return bits;
 }
 
-static size_t flt_cub_bytes(long N) {
-  size_t a = 0, b = 0;
-  uint32_t *k = nullptr;
-  int32_t *v = nullptr;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, k, k, v, v, (int)N, 0, 32, (hipStream_t)0);
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, v, v, (int)N, (hipStream_t)0);
-  return flt_align((a > b ? a : b) + 256);
-}
-
-// the workspace: counters, the two key and the two index arrays, ts, start, hot, the library's own
+// the workspace: counters and, adjacent, the two sums (one memset clears both); the two key and the two index arrays, ts, start,
+// hot, the library's own
 struct FltWs {
   int32_t *ctr;
   unsigned long long *sums;
@@ -311,22 +301,20 @@ struct FltWs {
 };
 
 static size_t flt_carve(void *ws, long N, long HW, FltWs *w) {
-  size_t off = 0;
-  char *base = (char *)ws;
-  auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += flt_align(bytes); return p; };
+  WsCarver c(ws);
   const size_t n = (size_t)(N > 0 ? N : 1);
-  w->ctr = (int32_t *)take(FLT_CTR_WORDS * sizeof(int32_t) + 2 * sizeof(unsigned long long));
-  w->sums = (unsigned long long *)(w->ctr + FLT_CTR_WORDS);
-  w->key = (uint32_t *)take(n * 4);
-  w->skey = (uint32_t *)take(n * 4);
-  w->iota = (int32_t *)take(n * 4);
-  w->sidx = (int32_t *)take(n * 4);
-  w->ts = (double *)take(n * 8);
-  w->start = (int32_t *)take(((size_t)HW + 2) * 4);
-  w->hot = (uint8_t *)take((size_t)HW);
-  w->cub_bytes = flt_cub_bytes(N > 0 ? N : 1);
-  w->cub = take(w->cub_bytes);
-  return off;
+  w->ctr = c.take<int32_t>(FLT_CTR_WORDS, 1);
+  w->sums = c.take<unsigned long long>(2, 256);
+  w->key = c.take<uint32_t>(n, 256);
+  w->skey = c.take<uint32_t>(n, 256);
+  w->iota = c.take<int32_t>(n, 256);
+  w->sidx = c.take<int32_t>(n, 256);
+  w->ts = c.take<double>(n, 256);
+  w->start = c.take<int32_t>((size_t)HW + 2, 256);
+  w->hot = c.take<uint8_t>((size_t)HW, 256);
+  w->cub_bytes = ws_cub_bytes<uint32_t>((int)n, 32);
+  w->cub = c.take<char>(w->cub_bytes, 256);
+  return c.bytes();
 }
 
 static int flt_grid(long lanes) {
@@ -371,8 +359,7 @@ int ramp_event_filter(const void *x, const void *y, const double *t, long N, int
   const uint32_t HW = (uint32_t)HWl;
   const int n = (int)N;
   const bool i32 = (flags & RAMP_FILTER_XY_I32) != 0;
-  if (hipMemsetAsync(w.ctr, 0, FLT_CTR_WORDS * sizeof(int32_t) + 2 * sizeof(unsigned long long), st) != hipSuccess)
-    return RAMP_ELAUNCH;
+  if (hipMemsetAsync(w.ctr, 0, ws_span(w.ctr, w.sums + 2), st) != hipSuccess) return RAMP_ELAUNCH;
   if (i32) hipLaunchKernelGGL((flt_key_kernel<true>), dim3(flt_grid(N)), dim3(INTERP_THREADS), 0, st, x, y, t, N, H, W, w.key, w.iota, w.ctr);
   else hipLaunchKernelGGL((flt_key_kernel<false>), dim3(flt_grid(N)), dim3(INTERP_THREADS), 0, st, x, y, t, N, H, W, w.key, w.iota, w.ctr);
   RAMP_CHECK_LAUNCH();

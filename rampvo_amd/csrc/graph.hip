@@ -3,8 +3,8 @@
 // replacements of the reference's torch.unique syncs and its host std::stable_sort.
 #include "ramp_device.h"
 #include "ramp_internal.h"
+#include "workspace_cub.h"
 #include <cstdint>
-#include <hipcub/hipcub.hpp>
 
 #define GR_THREADS 256
 
@@ -14,8 +14,6 @@ static inline int key_bits(int64_t bound) {
   while (b < 63 && ((int64_t)1 << b) < bound) b++;
   return b;
 }
-
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 __global__ void __launch_bounds__(GR_THREADS)
     gb_init_kernel(const int64_t *__restrict__ keys, unsigned long long *__restrict__ k64,
@@ -57,27 +55,29 @@ struct GbWs {
   void *cub;
   size_t cub_bytes;
 };
-static size_t gb_cub_bytes(int E) {
-  size_t a = 0, b = 0;
-  unsigned long long *k = nullptr;
-  int32_t *v = nullptr;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, k, k, v, v, E > 0 ? E : 1, 0, 64, (hipStream_t)0);
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, v, v, E > 0 ? E : 1, (hipStream_t)0);
-  return align_up((a > b ? a : b) + 256, 256);
-}
 static size_t gb_carve(void *ws, int E, GbWs *w) {
   const size_t n = (size_t)(E > 0 ? E : 1);
-  size_t off = 0;
-  char *base = (char *)ws;
-  auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
-  w->k_in = (unsigned long long *)take(n * 8);
-  w->k_out = (unsigned long long *)take(n * 8);
-  w->iota = (int32_t *)take(n * 4);
-  w->heads = (int32_t *)take(n * 4);
-  w->incl = (int32_t *)take(n * 4);
-  w->cub_bytes = gb_cub_bytes(E);
-  w->cub = take(w->cub_bytes);
-  return off;
+  WsCarver c(ws);
+  w->k_in = c.take<unsigned long long>(n, 256);
+  w->k_out = c.take<unsigned long long>(n, 256);
+  w->iota = c.take<int32_t>(n, 256);
+  w->heads = c.take<int32_t>(n, 256);
+  w->incl = c.take<int32_t>(n, 256);
+  w->cub_bytes = ws_cub_bytes<unsigned long long>((int)n, 64);
+  w->cub = c.take<char>(w->cub_bytes, 256);
+  return c.bytes();
+}
+// ramp_neighbors: the group-by's layout, then the two orders of its sorts
+struct NbWs {
+  GbWs gb;
+  int32_t *order1, *order2;
+};
+static size_t nb_carve(void *ws, int E, NbWs *w) {
+  const size_t n = (size_t)(E > 0 ? E : 1);
+  WsCarver c(ws, gb_carve(ws, E, &w->gb));
+  w->order1 = c.take<int32_t>(n, 256);
+  w->order2 = c.take<int32_t>(n, 256);
+  return c.bytes();
 }
 
 // keys already prepared in w.k_in / w.iota
@@ -582,9 +582,24 @@ __global__ void __launch_bounds__(256) plan_segsort_kernel(const PlanPair pp, in
   }
 }
 
-size_t ramp_i_plan_dyn_ws(int E_cap, int kkey_cap, int pkey_cap) {
+// the plan's workspace: the histograms of the two groupings in one block (the plan's last launch clears them together), their
+// group-id maps in a second, one scatter buffer each, a spare row
+struct PlanWs { int32_t *hist[2], *gidmap[2], *tmp[2]; };
+static size_t plan_carve(void *ws, int E_cap, int kkey_cap, int pkey_cap, PlanWs *w) {
   const size_t e = (size_t)(E_cap > 0 ? E_cap : 1);
-  return align_up((size_t)(kkey_cap + pkey_cap + 4) * 4, 256) * 2 + 2 * align_up(e * 4, 256) + 256;
+  WsCarver c(ws);
+  w->hist[0] = c.take<int32_t>((size_t)(kkey_cap + 2), 1);
+  w->hist[1] = c.take<int32_t>((size_t)(pkey_cap + 2), 256);
+  w->gidmap[0] = c.take<int32_t>((size_t)(kkey_cap + 2), 1);
+  w->gidmap[1] = c.take<int32_t>((size_t)(pkey_cap + 2), 256);
+  w->tmp[0] = c.take<int32_t>(e, 256);
+  w->tmp[1] = c.take<int32_t>(e, 256);
+  c.take<char>(256, 256);
+  return c.bytes();
+}
+size_t ramp_i_plan_dyn_ws(int E_cap, int kkey_cap, int pkey_cap) {
+  PlanWs w;
+  return plan_carve(nullptr, E_cap, kkey_cap, pkey_cap, &w);
 }
 
 // the graph plan (two groupings + temporal neighbours) of the factor list g4 = [4][E_cap] int64 (ii, jj, kk, row)
@@ -593,14 +608,11 @@ static int plan_fill(PlanPair &pp, int z, const int64_t *g4, int E_cap, int E_gr
                      int32_t *kk_ngroups, int64_t *kk_ukeys, int32_t *ij_order, int32_t *ij_gid, int32_t *ij_seg,
                      int32_t *ij_ngroups, int64_t *ij_ukeys, int64_t *ix, int64_t *jx, int32_t *kj, void *ws, size_t ws_bytes) {
   if (!g4 || !dyn || !status || !ws || E_cap <= 0 || kkey_cap <= 0 || pkey_cap <= 0) return RAMP_EINVAL;
-  if (ws_bytes < ramp_i_plan_dyn_ws(E_cap, kkey_cap, pkey_cap)) return RAMP_EWORKSPACE;
+  PlanWs w;
+  if (ws_bytes < plan_carve(ws, E_cap, kkey_cap, pkey_cap, &w)) return RAMP_EWORKSPACE;
   PlanDyn &p = pp.s[z];
   p.ii = g4; p.jj = g4 + E_cap; p.kk = g4 + 2 * (size_t)E_cap; p.dyn = dyn; p.M = M;
-  char *base = (char *)ws;
-  const size_t hb = align_up((size_t)(kkey_cap + pkey_cap + 4) * 4, 256);
-  p.hist[0] = (int32_t *)base; p.hist[1] = p.hist[0] + kkey_cap + 2;
-  p.gidmap[0] = (int32_t *)(base + hb); p.gidmap[1] = p.gidmap[0] + kkey_cap + 2;
-  p.tmp[0] = (int32_t *)(base + 2 * hb); p.tmp[1] = (int32_t *)(base + 2 * hb + align_up((size_t)E_cap * 4, 256));
+  for (int s = 0; s < 2; s++) { p.hist[s] = w.hist[s]; p.gidmap[s] = w.gidmap[s]; p.tmp[s] = w.tmp[s]; }
   p.order[0] = kk_order; p.gid[0] = kk_gid; p.seg[0] = kk_seg; p.ngroups[0] = kk_ngroups; p.ukeys[0] = kk_ukeys;
   p.order[1] = ij_order; p.gid[1] = ij_gid; p.seg[1] = ij_seg; p.ngroups[1] = ij_ngroups; p.ukeys[1] = ij_ukeys;
   p.Kcap[0] = kkey_cap; p.Kcap[1] = pkey_cap;
@@ -638,10 +650,24 @@ int ramp_i_plan_dyn(const int64_t *g4, int E_cap, int E_grid, const int32_t *dyn
   pp.s[1] = pp.s[0]; pp.ix[1] = ix; pp.jx[1] = jx; pp.kj[1] = kj;
   return plan_launch(pp, 1, E_cap, E_grid, kkey_cap, pkey_cap, kk_cap, ij_cap, mirror, st);
 }
+// ramp_group_by_small: [K + 1] counts and, adjacent, the out-of-range flag (one memset clears both); the group-id map; the
+// scatter buffer; a spare row
+struct GbcWs { int32_t *hist, *bad, *gidmap, *tmp; };
+static size_t gbc_carve(void *ws, int E, int K, GbcWs *w) {
+  WsCarver c(ws);
+  w->hist = c.take<int32_t>((size_t)(K + 1), 1);
+  w->bad = c.take<int32_t>(1, 256);
+  w->gidmap = c.take<int32_t>((size_t)(K + 2), 256);
+  w->tmp = c.take<int32_t>((size_t)(E > 0 ? E : 1), 256);
+  c.take<char>(256, 256);
+  return c.bytes();
+}
+
 extern "C" {
 
 size_t ramp_group_by_small_workspace_bytes(int E, int K) {
-  return align_up((size_t)(K + 2) * 4, 256) * 2 + align_up((size_t)(E > 0 ? E : 1) * 4, 256) + 256;
+  GbcWs w;
+  return gbc_carve(nullptr, E, K, &w);
 }
 
 int ramp_group_by_small(const int64_t *a, const int64_t *b, int64_t mul, int64_t sub, int K, int E,
@@ -655,13 +681,10 @@ int ramp_group_by_small(const int64_t *a, const int64_t *b, int64_t mul, int64_t
     return RAMP_OK;
   }
   if (!a || !order || !ws) return RAMP_EINVAL;
-  if (ws_bytes < ramp_group_by_small_workspace_bytes(E, K)) return RAMP_EWORKSPACE;
-  char *base = (char *)ws;
-  int32_t *hist = (int32_t *)base;                 // [K + 1] counts, then the out-of-range flag: one memset for both
-  int32_t *bad = hist + (K + 1);
-  int32_t *gidmap = (int32_t *)(base + align_up((size_t)(K + 2) * 4, 256));
-  int32_t *tmp = (int32_t *)(base + 2 * align_up((size_t)(K + 2) * 4, 256));
-  (void)hipMemsetAsync(hist, 0, (size_t)(K + 2) * 4, st);
+  GbcWs w;
+  if (ws_bytes < gbc_carve(ws, E, K, &w)) return RAMP_EWORKSPACE;
+  int32_t *hist = w.hist, *bad = w.bad, *gidmap = w.gidmap, *tmp = w.tmp;
+  (void)hipMemsetAsync(hist, 0, ws_span(hist, bad + 1), st);
   const int nb = ramp_cdiv(E, 256);
   const bool lds = K <= GBC_LDS_K;
   if (lds)
@@ -704,8 +727,8 @@ int ramp_group_by(const int64_t *keys, int E, int64_t key_bound, int32_t *order,
 }
 
 size_t ramp_neighbors_workspace_bytes(int E) {
-  const size_t n = (size_t)(E > 0 ? E : 1);
-  return ramp_internal_group_by_ws(E) + 2 * align_up(n * 4, 256);
+  NbWs w;
+  return nb_carve(nullptr, E, &w);
 }
 
 int ramp_neighbors(const int64_t *kk, const int64_t *jj, int64_t *ix, int64_t *jx, int E,
@@ -714,12 +737,11 @@ int ramp_neighbors(const int64_t *kk, const int64_t *jj, int64_t *ix, int64_t *j
   if (E < 0) return RAMP_EINVAL;
   if (E == 0) return RAMP_OK;
   if (!kk || !jj || !ix || !jx || !ws) return RAMP_EINVAL;
-  if (ws_bytes < ramp_neighbors_workspace_bytes(E)) return RAMP_EWORKSPACE;
+  NbWs nw;
+  if (ws_bytes < nb_carve(ws, E, &nw)) return RAMP_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  GbWs w;
-  const size_t used = gb_carve(ws, E, &w);
-  int32_t *order1 = (int32_t *)((char *)ws + used);
-  int32_t *order2 = (int32_t *)((char *)ws + used + align_up((size_t)E * 4, 256));
+  GbWs &w = nw.gb;
+  int32_t *order1 = nw.order1, *order2 = nw.order2;
   const int nb = ramp_cdiv(E, GR_THREADS);
   size_t cb;
   const int bk = key_bits(kk_bound), bj = key_bits(jj_bound);

@@ -590,11 +590,26 @@ static ImuArgs imu_args(const double *tau, const void *gyro, const void *accel, 
   return a;
 }
 
+// ramp_imu_align's workspace for K knots, packed: ctr | state | part | records.  The counters and the state are adjacent because
+// one memset clears them.
+struct ImuWs {
+  int32_t *ctr;
+  double *state, *part, *records;
+};
+static size_t imu_carve(void *ws, int K, ImuWs *w) {
+  WsCarver c(ws);
+  w->ctr = c.take<int32_t>(IMU_CTR_WORDS, 1);
+  w->state = c.take<double>(IMU_STATE_WORDS, 1);
+  w->part = c.take<double>((size_t)imu_groups(K - 1) * IMU_PART_WORDS, 1);
+  w->records = c.take<double>((size_t)(K - 1) * IMU_REC, 1);
+  return c.bytes();
+}
+
 extern "C" {
 size_t ramp_imu_workspace_bytes(long N, int K) {
   if (N < 1 || K < 2) return 0;
-  return IMU_CTR_WORDS * sizeof(int32_t) + IMU_STATE_WORDS * sizeof(double) +
-         (size_t)imu_groups(K - 1) * IMU_PART_WORDS * sizeof(double) + (size_t)(K - 1) * IMU_REC * sizeof(double);
+  ImuWs w;
+  return imu_carve(nullptr, K, &w);
 }
 
 int ramp_imu_preintegrate(const double *tau, const void *gyro, const void *accel, long N, const double *times, int T, int stride,
@@ -632,13 +647,12 @@ int ramp_imu_align(const double *tau, const void *gyro, const void *accel, long 
     return RAMP_EINVAL;
   ImuAlign al;
   if (!imu_extrinsics(extrinsics, al.q_bc, al.lever, nullptr)) return RAMP_EINVAL;
-  if (ws_bytes < ramp_imu_workspace_bytes(N, K)) return RAMP_EWORKSPACE;
+  ImuWs w;
+  if (ws_bytes < imu_carve(ws, K, &w)) return RAMP_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  unsigned char *base = (unsigned char *)ws;
-  int32_t *ctr = (int32_t *)base;
-  double *state = (double *)(base + IMU_CTR_WORDS * sizeof(int32_t));
-  double *part = state + IMU_STATE_WORDS;
-  double *records = preint ? preint : part + (size_t)imu_groups(K - 1) * IMU_PART_WORDS;
+  int32_t *ctr = w.ctr;
+  double *state = w.state, *part = w.part;
+  double *records = preint ? preint : w.records;
   const bool f64 = (flags & RAMP_IMU_F64) != 0;
 
   ImuArgs ia = imu_args(tau, gyro, accel, N, times, K, stride, bias_g, bias_a, max_gap);
@@ -650,8 +664,7 @@ int ramp_imu_align(const double *tau, const void *gyro, const void *accel, long 
   al.stride = stride; al.first = 1;
 
   // the one memset: the counters and the state
-  if (hipMemsetAsync(base, 0, IMU_CTR_WORDS * sizeof(int32_t) + IMU_STATE_WORDS * sizeof(double), st) != hipSuccess)
-    return RAMP_ELAUNCH;
+  if (hipMemsetAsync(ctr, 0, ws_span(ctr, part), st) != hipSuccess) return RAMP_ELAUNCH;
   hipLaunchKernelGGL(imu_check_kernel, dim3(imu_check_grid(N, T)), dim3(IMU_THREADS), 0, st, tau, N, times, T, ctr, state,
                      ia.bias_g[0], ia.bias_g[1], ia.bias_g[2]);
   RAMP_CHECK_LAUNCH();

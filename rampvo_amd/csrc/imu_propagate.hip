@@ -328,11 +328,27 @@ __global__ void __launch_bounds__(RAMP_WAVE) prop_status_kernel(const int32_t *_
   if (tid < 8) status[tid] = tid < 6 ? ctr[tid] : 0;
 }
 
+// the workspace for N samples, packed: ctr | chunk_tot | tile_tot; `tiles` is also the grid of the tile launches
+struct PropWs {
+  int32_t *ctr;
+  double *chunk_tot, *tile_tot;
+  long tiles;
+};
+static size_t prop_carve(void *ws, long N, PropWs *w) {
+  const long chunks = (N + PROP_CHUNK - 1) / PROP_CHUNK;
+  w->tiles = (N + PROP_TILE - 1) / PROP_TILE;
+  WsCarver c(ws);
+  w->ctr = c.take<int32_t>(PROP_CTR_WORDS, 1);
+  w->chunk_tot = c.take<double>((size_t)chunks * PROP_W, 1);
+  w->tile_tot = c.take<double>((size_t)w->tiles * PROP_W, 1);
+  return c.bytes();
+}
+
 extern "C" {
 size_t ramp_imu_propagate_workspace_bytes(long N) {
   if (N < 1) return 0;
-  const size_t chunks = (size_t)((N + PROP_CHUNK - 1) / PROP_CHUNK), tiles = (size_t)((N + PROP_TILE - 1) / PROP_TILE);
-  return PROP_CTR_WORDS * sizeof(int32_t) + (chunks + tiles) * PROP_W * sizeof(double);
+  PropWs w;
+  return prop_carve(nullptr, N, &w);
 }
 
 int ramp_imu_propagate(const double *tau, const void *gyro, const void *accel, long N, const double *anchor,
@@ -348,14 +364,12 @@ int ramp_imu_propagate(const double *tau, const void *gyro, const void *accel, l
     if (bias_a && !imu_host_finite(bias_a[c])) return RAMP_EINVAL;
   PropArgs a;
   if (!imu_extrinsics(extrinsics, a.q_bc, a.lever, a.p_bc)) return RAMP_EINVAL;
-  if (ws_bytes < ramp_imu_propagate_workspace_bytes(N)) return RAMP_EWORKSPACE;
+  PropWs w;
+  if (ws_bytes < prop_carve(ws, N, &w)) return RAMP_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const long chunks = (N + PROP_CHUNK - 1) / PROP_CHUNK, tiles = (N + PROP_TILE - 1) / PROP_TILE;
-  unsigned char *base = (unsigned char *)ws;
+  const long tiles = w.tiles;
   a.tau = tau; a.gyro = gyro; a.accel = accel; a.anchor = anchor;
-  a.ctr = (int32_t *)base;
-  a.chunk_tot = (double *)(base + PROP_CTR_WORDS * sizeof(int32_t));
-  a.tile_tot = a.chunk_tot + (size_t)chunks * PROP_W;
+  a.ctr = w.ctr; a.chunk_tot = w.chunk_tot; a.tile_tot = w.tile_tot;
   a.poses = poses; a.times_out = times_out; a.state = state;
   for (int c = 0; c < 3; c++) a.bias_a[c] = bias_a ? bias_a[c] : 0.0;
   a.max_gap = max_gap; a.horizon = horizon; a.N = N;
@@ -364,7 +378,7 @@ int ramp_imu_propagate(const double *tau, const void *gyro, const void *accel, l
   const dim3 grid((unsigned)tiles), block(PROP_THREADS);
 
   // the one memset: the counters (the break word reads "none" at zero)
-  if (hipMemsetAsync(base, 0, PROP_CTR_WORDS * sizeof(int32_t), st) != hipSuccess) return RAMP_ELAUNCH;
+  if (hipMemsetAsync(a.ctr, 0, ws_span(a.ctr, a.chunk_tot), st) != hipSuccess) return RAMP_ELAUNCH;
   if (f64) hipLaunchKernelGGL(prop_check_kernel<double>, dim3(check_grid), block, 0, st, a);
   else hipLaunchKernelGGL(prop_check_kernel<float>, dim3(check_grid), block, 0, st, a);
   RAMP_CHECK_LAUNCH();

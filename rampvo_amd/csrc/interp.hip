@@ -145,7 +145,8 @@ static int interp_launch_query(const float *knots, const double *times, int T, c
 
 extern "C" {
 size_t ramp_se3_interp_workspace_bytes(int T) {
-  return (size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS * sizeof(float);
+  float *seg;
+  return interp_carve(nullptr, T, &seg);
 }
 int ramp_se3_interp_lds_knots(void) { return INTERP_LDS_KNOTS; }
 
@@ -156,16 +157,16 @@ int ramp_se3_interp(const float *knots, const double *times, int T, const double
   if (!knots || !times || !query || !out || !seg_ws || !status) return RAMP_EINVAL;
   if (flags & ~(RAMP_INTERP_EXTRAPOLATE | RAMP_INTERP_ROW_STORES)) return RAMP_EINVAL;
   if (((uintptr_t)seg_ws & 15) != 0) return RAMP_EINVAL;
-  if (seg_ws_bytes < ramp_se3_interp_workspace_bytes(T)) return RAMP_EWORKSPACE;
+  float *seg;
+  if (seg_ws_bytes < interp_carve(seg_ws, T, &seg)) return RAMP_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(status, 0, 4 * sizeof(int32_t), st) != hipSuccess) return RAMP_ELAUNCH;
   const int S = T > 1 ? T - 1 : 1;
   hipLaunchKernelGGL(interp_segment_kernel, dim3(ramp_cdiv(S, INTERP_THREADS)), dim3(INTERP_THREADS), 0, st, knots, times,
-                     T, (float *)seg_ws, status);
+                     T, seg, status);
   RAMP_CHECK_LAUNCH();
   const int ex = (flags & RAMP_INTERP_EXTRAPOLATE) ? 1 : 0;
   const bool lds_times = T <= INTERP_LDS_KNOTS, lds_rows = !(flags & RAMP_INTERP_ROW_STORES);
-  const float *seg = (const float *)seg_ws;
   if (lds_times)
     return lds_rows ? interp_launch_query<true, true>(knots, times, T, query, Q, ex, seg, out, twist, status, st)
                     : interp_launch_query<true, false>(knots, times, T, query, Q, ex, seg, out, twist, status, st);

@@ -7,11 +7,19 @@
 //   X(t)  = Exp(alpha * xi_s) * X[s]
 #pragma once
 #include "ramp_device.h"
+#include "workspace.h"
 
 #define INTERP_THREADS 256
 #define INTERP_LDS_KNOTS 4096      // knot times staged in LDS up to here (32 KiB of float64); longer: search in global memory
 #define INTERP_MAX_GROUPS 2048     // workgroups per launch; each walks the query tiles with this stride
 #define INTERP_SEG_WORDS 16        // per segment: xi[6], float64 length (words 6, 7), twist[6], 2 spare = one 64-byte row
+
+// the segment table of T knots (one row for a single knot): ramp_se3_interp's whole workspace, the head of the warp's
+static inline size_t interp_carve(void *ws, int T, float **seg) {
+  WsCarver c(ws);
+  *seg = c.take<float>((size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS, 1);
+  return c.bytes();
+}
 
 static __device__ __forceinline__ bool interp_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }
 

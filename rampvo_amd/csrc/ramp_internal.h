@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/ramp_hip.h"
+#include "workspace.h"
 
 size_t ramp_internal_group_by_ws(int E);
 int ramp_internal_group_by(const int64_t *keys, int E, int64_t key_bound, int32_t *order,

@@ -389,6 +389,15 @@ int ramp_i_frame_commit_dyn(float *poses, int motion, float damping, int64_t *ts
   return RAMP_OK;
 }
 
+// ramp_event_topk's workspace, packed: the score map at quarter resolution | what the suppression keeps of it
+static size_t topk_carve(void *ws, int H, int W, float **score, float **kept) {
+  const size_t n = (size_t)(H / 4) * (W / 4);
+  WsCarver c(ws);
+  *score = c.take<float>(n, 1);
+  *kept = c.take<float>(n, 1);
+  return c.bytes();
+}
+
 extern "C" {
 
 int ramp_depth_median_fill(const float *patches_src, int F, int M, int P, float *patches_dst, void *stream) {
@@ -401,7 +410,8 @@ int ramp_depth_median_fill(const float *patches_src, int F, int M, int P, float 
 }
 
 size_t ramp_event_topk_workspace_bytes(int H, int W) {
-  return (size_t)2 * (H / 4) * (W / 4) * sizeof(float);
+  float *score, *kept;
+  return topk_carve(nullptr, H, W, &score, &kept);
 }
 
 int ramp_event_topk(const float *events, int bins, int H, int W, int k, int nms_kernel_size, float *coords,
@@ -411,8 +421,8 @@ int ramp_event_topk(const float *events, int bins, int H, int W, int k, int nms_
   if (k > TOPK_MAXK || k > N || (W % 4) || nms_kernel_size < 0 || (nms_kernel_size && !(nms_kernel_size & 1)) ||
       nms_kernel_size > 2 * NMS_RMAX + 1)
     return RAMP_EUNSUPPORTED;
-  if (ws_bytes < ramp_event_topk_workspace_bytes(H, W)) return RAMP_EWORKSPACE;
-  float *score = (float *)ws, *kept = score + N;
+  float *score, *kept;
+  if (ws_bytes < topk_carve(ws, H, W, &score, &kept)) return RAMP_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(event_score_kernel, dim3(ramp_cdiv(N, 256)), dim3(256), 0, st, events, score, bins, H, W, h,
                      w);

@@ -710,21 +710,19 @@ struct TrkUncWs {
   size_t cov_ws_bytes;
 };
 static size_t trk_unc_carve(const ramp_track *t, void *ws, TrkUncWs *u) {
-  size_t off = 0;
-  char *base = (char *)ws;
-  auto take = [&](size_t bytes) { char *p = base ? base + off : nullptr; off += (bytes + 255) / 256 * 256; return (void *)p; };
-  const size_t e = (size_t)t->E_cap;
-  u->dynp = (int32_t *)take(RAMP_DYN_WORDS * 4 + 64);
-  u->kk_order = (int32_t *)take(e * 4); u->kk_gid = (int32_t *)take(e * 4);
-  u->ij_order = (int32_t *)take(e * 4); u->ij_gid = (int32_t *)take(e * 4);
-  u->kk_seg = (int32_t *)take((size_t)(t->kk_cap + 2) * 4); u->ij_seg = (int32_t *)take((size_t)(t->ij_cap + 2) * 4);
-  u->kk_ngroups = (int32_t *)take(4); u->ij_ngroups = (int32_t *)take(4);
-  u->kk_ukeys = (int64_t *)take((size_t)(t->kk_cap + 2) * 8); u->ij_ukeys = (int64_t *)take((size_t)(t->ij_cap + 2) * 8);
-  u->ix = (int64_t *)take(e * 8); u->jx = (int64_t *)take(e * 8); u->kj = (int32_t *)take(e * 4);
-  u->tg = (float *)take(e * 8); u->wg = (float *)take(e * 8);
+  WsCarver c(ws);
+  const size_t e = (size_t)t->E_cap, kc = (size_t)(t->kk_cap + 2), ic = (size_t)(t->ij_cap + 2);
+  u->dynp = c.take<int32_t>(RAMP_DYN_WORDS + 16, 256);
+  u->kk_order = c.take<int32_t>(e, 256); u->kk_gid = c.take<int32_t>(e, 256);
+  u->ij_order = c.take<int32_t>(e, 256); u->ij_gid = c.take<int32_t>(e, 256);
+  u->kk_seg = c.take<int32_t>(kc, 256); u->ij_seg = c.take<int32_t>(ic, 256);
+  u->kk_ngroups = c.take<int32_t>(1, 256); u->ij_ngroups = c.take<int32_t>(1, 256);
+  u->kk_ukeys = c.take<int64_t>(kc, 256); u->ij_ukeys = c.take<int64_t>(ic, 256);
+  u->ix = c.take<int64_t>(e, 256); u->jx = c.take<int64_t>(e, 256); u->kj = c.take<int32_t>(e, 256);
+  u->tg = c.take<float>(2 * e, 256); u->wg = c.take<float>(2 * e, 256);
   u->cov_ws_bytes = ramp_i_ba_cov_dyn_ws(t->opt_window, t->kk_cap);
-  u->cov_ws = take(u->cov_ws_bytes);
-  return off;
+  u->cov_ws = c.take<char>(u->cov_ws_bytes, 256);
+  return c.bytes();
 }
 
 extern "C" {

@@ -341,13 +341,28 @@ static int vox_stat_groups(long C) {
   return (int)(n < VOX_STAT_GROUPS ? n : VOX_STAT_GROUPS);
 }
 
-// bytes per slice behind the counters: n and sum, the accumulators, the partials
-static size_t vox_slice_bytes(long C) { return 2 * sizeof(long long) + (size_t)C * sizeof(long long) + (size_t)vox_stat_groups(C) * sizeof(double); }
+// The workspace of a chunk of sc slices of C cells, packed: ctr | sums (n and sum per slice) | acc | part (the partials).  The
+// counters, the sums and the accumulators are adjacent because one memset clears them.  Every block behind the counters is
+// linear in sc: vox_carve(sc) - vox_carve(0) is sc times the bytes of one slice.
+struct VoxWs {
+  int32_t *ctr;
+  long long *sums, *acc;
+  double *part;
+};
+static size_t vox_carve(void *ws, int sc, long C, VoxWs *w) {
+  WsCarver c(ws);
+  w->ctr = c.take<int32_t>(VOX_CTR_WORDS, 1);
+  w->sums = c.take<long long>(2 * (size_t)sc, 1);
+  w->acc = c.take<long long>((size_t)sc * C, 1);
+  w->part = c.take<double>((size_t)sc * vox_stat_groups(C), 1);
+  return c.bytes();
+}
 
 extern "C" {
 size_t ramp_event_voxel_workspace_bytes(int slices, int bins, int H, int W) {
   if (slices < 1 || bins < 1 || H < 1 || W < 1) return 0;
-  return VOX_CTR_WORDS * sizeof(int32_t) + (size_t)slices * vox_slice_bytes((long)bins * H * W);
+  VoxWs w;
+  return vox_carve(nullptr, slices, (long)bins * H * W, &w);
 }
 long ramp_event_voxel_grid_events(void) { return (long)WARP_MAX_GROUPS * WARP_TILE; }
 int ramp_event_voxel_lds_offsets(void) { return VOX_LDS_OFFSETS; }
@@ -364,26 +379,27 @@ int ramp_event_voxel(const float *x, const float *y, const double *t, const int8
   if ((double)bins * (double)H * (double)W > 2147483647.0) return RAMP_EUNSUPPORTED;
   const long C = (long)bins * H * W;
   const int P = vox_stat_groups(C);
-  const size_t head = VOX_CTR_WORDS * sizeof(int32_t), per = vox_slice_bytes(C);
-  if (ws_bytes < head + per) return RAMP_EWORKSPACE;
+  VoxWs w;
+  const size_t head = vox_carve(nullptr, 0, C, &w), one = vox_carve(nullptr, 1, C, &w);
+  if (ws_bytes < one) return RAMP_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  size_t fit = (ws_bytes - head) / per;
+  size_t fit = (ws_bytes - head) / (one - head);
   if (fit > VOX_MAX_CHUNK) fit = VOX_MAX_CHUNK;
   const int chunk = (int)(fit < (size_t)S ? fit : (size_t)S);
-  unsigned char *base = (unsigned char *)ws;
-  int32_t *ctr = (int32_t *)base;
   const long tiles = (N + WARP_TILE - 1) / WARP_TILE;
   const int vote_grid = (int)(tiles < WARP_MAX_GROUPS ? tiles : WARP_MAX_GROUPS);
   const bool vec = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)p | (uintptr_t)t) & 15) == 0;
   const bool sub = (flags & RAMP_VOXEL_SUBPIXEL) != 0;
   for (int c0 = 0; c0 < S; c0 += chunk) {
     const int sc = S - c0 < chunk ? S - c0 : chunk;
-    long long *sums = (long long *)(base + head), *acc = sums + 2 * (size_t)sc;
-    double *part = (double *)(acc + (size_t)sc * C);
+    vox_carve(ws, sc, C, &w);
+    int32_t *ctr = w.ctr;
+    long long *sums = w.sums, *acc = w.acc;
+    double *part = w.part;
     const long long *off = offsets ? (const long long *)offsets + c0 : nullptr;
     // the one memset of the chunk: n and sum and the accumulators; in front of the first chunk the counters as well
-    const size_t zero = (2 * (size_t)sc + (size_t)sc * C) * sizeof(long long);
-    if (hipMemsetAsync(c0 ? base + head : base, 0, c0 ? zero : head + zero, st) != hipSuccess) return RAMP_ELAUNCH;
+    void *first = c0 ? (void *)sums : (void *)ctr;
+    if (hipMemsetAsync(first, 0, ws_span(first, part), st) != hipSuccess) return RAMP_ELAUNCH;
     if (c0 == 0 && offsets) {
       hipLaunchKernelGGL(vox_offsets_kernel, dim3(ramp_cdiv((long)S + 1, INTERP_THREADS)), dim3(INTERP_THREADS), 0, st,
                          (const long long *)offsets, S, N, ctr);

@@ -225,7 +225,8 @@ int ramp_i_warp_segments(const float *knots, const double *times, int T, double 
 extern "C" {
 size_t ramp_event_warp_workspace_bytes(int T, int bins, int H, int W) {
   if (H < 1 || W < 1) return 0;
-  return warp_acc_offset(T) + WARP_CTR_WORDS * sizeof(int32_t) + (size_t)(2 + (bins > 0 ? bins : 0)) * H * W * sizeof(long long);
+  WarpWs w;                              // (room for both accumulators, whichever a call uses)
+  return warp_carve(nullptr, T, (size_t)2 * H * W, (size_t)(bins > 0 ? bins : 0) * H * W, &w);
 }
 long ramp_event_warp_grid_events(void) { return (long)WARP_MAX_GROUPS * WARP_TILE; }
 
@@ -243,19 +244,18 @@ int ramp_event_warp(const float *x, const float *y, const double *t, const int8_
   if (!identity && (!t || !knots || !times || !intrinsics || !invdepth || !(fabs(t_ref) <= 1.7976931348623157e308)))
     return RAMP_EINVAL;
   if (((uintptr_t)ws & 15) != 0 || ((uintptr_t)xy_out & 7) != 0) return RAMP_EINVAL;    // (xy_out rows are stored as float2)
-  if (ws_bytes < ramp_event_warp_workspace_bytes(T, bins, H, W)) return RAMP_EWORKSPACE;
+  if (ws_bytes < ramp_event_warp_workspace_bytes(T, bins, H, W)) return RAMP_EWORKSPACE;    // (never less than this call's own carve)
   hipStream_t st = (hipStream_t)stream;
   const size_t HW = (size_t)H * W;
   const bool stack = stack_f32 || stack_i8;
-  unsigned char *base = (unsigned char *)ws;
-  float *seg = (float *)base, *ref = seg + (size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS;
-  int32_t *ctr = (int32_t *)(base + warp_acc_offset(T));
-  long long *acc = (long long *)(ctr + WARP_CTR_WORDS);
-  long long *acc_iwe = iwe ? acc : nullptr, *acc_stack = stack ? acc + (iwe ? 2 * HW : 0) : nullptr;
   const long n_iwe = iwe ? (long)(2 * HW) : 0, n_stack = stack ? (long)((size_t)bins * HW) : 0;
+  WarpWs w;
+  warp_carve(ws, T, (size_t)n_iwe, (size_t)n_stack, &w);
+  float *seg = w.seg, *ref = w.ref;
+  int32_t *ctr = w.ctr;
+  long long *acc_iwe = iwe ? w.acc_iwe : nullptr, *acc_stack = stack ? w.acc_stack : nullptr;
   // the one memset: the counters and, behind them, the accumulators this call uses
-  if (hipMemsetAsync(ctr, 0, WARP_CTR_WORDS * sizeof(int32_t) + (size_t)(n_iwe + n_stack) * sizeof(long long), st) != hipSuccess)
-    return RAMP_ELAUNCH;
+  if (hipMemsetAsync(ctr, 0, ws_span(ctr, w.end), st) != hipSuccess) return RAMP_ELAUNCH;
   const int ex = (flags & RAMP_INTERP_EXTRAPOLATE) ? 1 : 0;
   if (!identity) {
     const int rc = ramp_i_warp_segments(knots, times, T, t_ref, ex, seg, ref, ctr, st);

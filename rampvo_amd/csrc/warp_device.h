@@ -18,8 +18,24 @@
 
 typedef unsigned long long warp_u64;
 
-static inline size_t warp_acc_offset(int T) {
-  return ((size_t)(T > 1 ? T - 1 : 1) * INTERP_SEG_WORDS + WARP_REF_WORDS) * sizeof(float);    // the counters start here
+// The warp's workspace, packed: seg, ref | ctr | acc_iwe | acc_stack | end.  The counters and the accumulators are adjacent
+// because one memset clears them (from ctr up to the next block the call does not clear).  n_iwe, n_stack: the int64 words of
+// the two accumulators; a call that leaves one out carves it with 0 words and the other moves up.  The contrast extends the
+// layout at `end` (contrast.hip).
+struct WarpWs {
+  float *seg, *ref;
+  int32_t *ctr;
+  long long *acc_iwe, *acc_stack;
+  char *end;
+};
+static inline size_t warp_carve(void *ws, int T, size_t n_iwe, size_t n_stack, WarpWs *w) {
+  WsCarver c(ws, interp_carve(ws, T, &w->seg));
+  w->ref = c.take<float>(WARP_REF_WORDS, 1);
+  w->ctr = c.take<int32_t>(WARP_CTR_WORDS, 1);
+  w->acc_iwe = c.take<long long>(n_iwe, 1);
+  w->acc_stack = c.take<long long>(n_stack, 1);
+  w->end = c.take<char>(0, 1);
+  return c.bytes();
 }
 
 // G = Cref^-1 * C from ref = (-(qr^-1 . tr), qr^-1) and C = (t, q), without renormalising either factor:

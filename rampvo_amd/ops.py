@@ -10,7 +10,7 @@ import torch
 from . import _lib, switches
 from ._lib import RAMP_CORR_MFMA32 as _LIB_CORR_MFMA32
 from ._lib import RAMP_CORR_X2 as _LIB_CORR_X2
-from ._lib import workspace as _lib_workspace
+from ._lib import sized_workspace, workspace as _lib_workspace
 from ._lib import KPLANE, RAMP_NHWC32, RAMP_NCHW, RAMP_NHWC, CorrLevel, check, dtype_code, kplane, lib, ptr, require_cuda, stream
 
 
@@ -171,8 +171,7 @@ def event_stack(x, y, p, height, width, num_bins=5, as_float=True):
         out = torch.zeros((num_bins, height, width), dtype=torch.int8, device=x.device)
         if N >= 2:      # fewer than 2 events: an empty grid (transformers.py:151-152)
             xf, yf = x.to(torch.float32).contiguous(), y.to(torch.float32).contiguous()
-            nbytes = lib().ramp_event_warp_workspace_bytes(1, num_bins, height, width)
-            ws = _lib_workspace(nbytes, x.device, "evwarp")
+            ws, nbytes = sized_workspace("ramp_event_warp_workspace_bytes", (1, num_bins, height, width), x.device, "evwarp")
             status = torch.empty(8, dtype=torch.int32, device=x.device)
             check(lib().ramp_event_warp(ptr(xf), ptr(yf), None, ptr(pi), N, None, None, 1, 0.0, None, None,
                                         _lib.RAMP_WARP_IDENTITY, num_bins, height, width, None, None, None, ptr(out),
@@ -180,8 +179,7 @@ def event_stack(x, y, p, height, width, num_bins=5, as_float=True):
         return out.float() if as_float else out
     xi, yi = x.to(torch.int32).contiguous(), y.to(torch.int32).contiguous()
     out = torch.empty((num_bins, height, width), dtype=torch.float32 if as_float else torch.int8, device=x.device)
-    nbytes = lib().ramp_event_stack_workspace_bytes(num_bins, height, width)
-    ws = _lib_workspace(nbytes, x.device, "evstack")
+    ws, nbytes = sized_workspace("ramp_event_stack_workspace_bytes", (num_bins, height, width), x.device, "evstack")
     check(lib().ramp_event_stack(ptr(xi), ptr(yi), ptr(pi), N, num_bins, height, width,
                                  None if as_float else ptr(out), ptr(out) if as_float else None, ptr(ws), nbytes,
                                  stream()), "ramp_event_stack")
@@ -253,8 +251,7 @@ def event_warp(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, wi
         res["stack"] = torch.zeros((num_bins, height, width), dtype=torch.float32 if stack == "f32" else torch.int8, device=dev)
     if N == 0:
         return res
-    nbytes = lib().ramp_event_warp_workspace_bytes(T, bins, height, width)
-    ws = _lib_workspace(nbytes, dev, "evwarp")
+    ws, nbytes = sized_workspace("ramp_event_warp_workspace_bytes", (T, bins, height, width), dev, "evwarp")
     check(lib().ramp_event_warp(ptr(xf), ptr(yf), ptr(tf), ptr(pi), N, ptr(knots), ptr(times), T, float(t_ref), ptr(K), ptr(d),
                                 flags, bins, height, width, ptr(res.get("xy")), ptr(res.get("iwe")),
                                 ptr(res["stack"]) if stack == "f32" else None, ptr(res["stack"]) if stack == "i8" else None,
@@ -305,8 +302,7 @@ def event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height
     if N == 0:
         res["stats"][3] = float(height * width)
         return res
-    nbytes = lib().ramp_event_contrast_workspace_bytes(T, height, width)
-    ws = _lib_workspace(nbytes, dev, "evcontrast")
+    ws, nbytes = sized_workspace("ramp_event_contrast_workspace_bytes", (T, height, width), dev, "evcontrast")
     check(lib().ramp_event_contrast(ptr(xf), ptr(yf), ptr(tf), ptr(pi), N, ptr(knots), ptr(times), T, float(t_ref), ptr(K),
                                     ptr(d), ptr(cor), flags, height, width, ptr(res.get("iwe")), ptr(res["sums"]),
                                     ptr(res["stats"]), ptr(res.get("grad")), ptr(ws), nbytes, ptr(res["status"]), stream()),
@@ -673,8 +669,7 @@ def imu_align(tau, gyro, accel, knots, times, R_bc=None, p_bc=None, bias_g=None,
            "residual": torch.empty(max(K - 2, 0), **f64), "status": torch.empty(8, dtype=torch.int32, device=dev)}
     if want_preint:
         res["preint"] = torch.empty((K - 1, _lib.RAMP_IMU_PREINT_WORDS), **f64)
-    nbytes = lib().ramp_imu_workspace_bytes(N, K)
-    ws = _lib_workspace(nbytes, dev, "imu")
+    ws, nbytes = sized_workspace("ramp_imu_workspace_bytes", (N, K), dev, "imu")
     check(lib().ramp_imu_align(ptr(tf), ptr(g), ptr(a), N, ptr(kn), ptr(tt), T, int(stride), ex, bg, ba, float(max_gap),
                                float(gravity_norm or 0.0), int(gyro_steps), flags, ptr(res["result"]), ptr(res["normal"]),
                                ptr(res["velocity"]), ptr(res["residual"]) if K > 2 else None, ptr(res.get("preint")),
@@ -739,8 +734,7 @@ def imu_propagate(tau, gyro, accel, anchor, R_bc=None, p_bc=None, bias_a=None, m
            "status": torch.empty(8, dtype=torch.int32, device=dev)}
     if want_state:
         res["state"] = torch.empty((N, 16), dtype=torch.float64, device=dev)
-    nbytes = lib().ramp_imu_propagate_workspace_bytes(N)
-    ws = _lib_workspace(nbytes, dev, "imu_propagate")
+    ws, nbytes = sized_workspace("ramp_imu_propagate_workspace_bytes", (N,), dev, "imu_propagate")
     check(lib().ramp_imu_propagate(ptr(tf), ptr(g), ptr(a), N, ptr(an), ex, ba, float(max_gap), float(horizon), flags,
                                    ptr(res["poses"]), ptr(res["times"]), ptr(res.get("state")), ptr(res["status"]), ptr(ws),
                                    nbytes, stream()), "ramp_imu_propagate")
@@ -846,8 +840,7 @@ def event_align(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, w
            "history": torch.zeros(iters, dtype=torch.float64, device=dev),
            "status": torch.zeros(8, dtype=torch.int32, device=dev), "info": torch.zeros(8, dtype=torch.int32, device=dev)}
     res["variance"], res["variance0"] = res["result"][0], res["result"][1]
-    nbytes = lib().ramp_event_align_workspace_bytes(T, height, width)
-    ws = _lib_workspace(nbytes, dev, "evcontrast")
+    ws, nbytes = sized_workspace("ramp_event_align_workspace_bytes", (T, height, width), dev, "evcontrast")
     check(lib().ramp_event_align(ptr(xf), ptr(yf), ptr(tf), ptr(pi), N, ptr(knots), ptr(times), T, float(t_ref), ptr(K), ptr(d),
                                  ptr(cor), flags, height, width, sum(1 << i for i, f in enumerate(free) if f), float(step),
                                  iters, min(max_evals, need), ptr(res["correction"]), ptr(res["correction_f32"]),
@@ -922,8 +915,7 @@ def invdepth_map(poses, patches, intrinsics, cam, height, width, radius, scale=1
         res["weight"] = torch.empty((height, width), dtype=torch.float32, device=dev)
     if want_records:
         res["records"] = torch.empty((Kc, 4), dtype=torch.float32, device=dev)
-    nbytes = lib().ramp_invdepth_map_workspace_bytes(Kc)
-    ws = _lib_workspace(nbytes, dev, "depthmap")
+    ws, nbytes = sized_workspace("ramp_invdepth_map_workspace_bytes", (Kc,), dev, "depthmap")
     check(lib().ramp_invdepth_map(ptr(poses), ptr(patches), ptr(K4), ptr(camf), n, M, P, float(scale), ptr(index), ptr(count),
                                   Ki, ptr(dyn_rows), int(per_row), int(last_rows), ptr(conf), ptr(pr), float(prior_weight),
                                   float(radius), flags, int(height), int(width), ptr(res["invdepth"]), ptr(res.get("weight")),
@@ -960,8 +952,7 @@ def event_topk(events, k, nms_kernel_size=11, want_indices=False, out=None):
     coords = out if out is not None else torch.empty((k, 2), dtype=torch.float32, device=events.device)
     assert coords.shape == (k, 2) and coords.dtype == torch.float32 and coords.is_contiguous()
     idx = torch.empty(k, dtype=torch.int64, device=events.device) if want_indices else None
-    nbytes = lib().ramp_event_topk_workspace_bytes(H, W)
-    ws = _lib_workspace(nbytes, events.device, "topk")
+    ws, nbytes = sized_workspace("ramp_event_topk_workspace_bytes", (H, W), events.device, "topk")
     check(lib().ramp_event_topk(ptr(events), bins, H, W, int(k), int(nms_kernel_size), ptr(coords),
                                 ptr(idx) if idx is not None else None, ptr(ws), nbytes, stream()),
           "ramp_event_topk")
@@ -1284,8 +1275,7 @@ def group_by(keys, key_bound=0):
     E = keys.shape[0]
     dev = keys.device
     g = _new_groups(E, dev)
-    nbytes = lib().ramp_group_by_workspace_bytes(E)
-    ws = _lib.workspace(nbytes, dev, "graph")
+    ws, nbytes = sized_workspace("ramp_group_by_workspace_bytes", (E,), dev, "graph")
     check(lib().ramp_group_by(ptr(keys), E, int(key_bound), ptr(g.order), ptr(g.gid),
                               ptr(g.seg_start), ptr(g.ukeys), ptr(g.ngroups), ptr(ws),
                               ws.numel(), stream()), "ramp_group_by")
@@ -1300,8 +1290,7 @@ def group_by_small(a, b, mul, sub, K, max_groups=0):
     E = a.shape[0]
     dev = a.device
     g = _new_groups(E, dev)
-    nbytes = lib().ramp_group_by_small_workspace_bytes(E, int(K))
-    ws = _lib.workspace(nbytes, dev, "graph")
+    ws, nbytes = sized_workspace("ramp_group_by_small_workspace_bytes", (E, int(K)), dev, "graph")
     check(lib().ramp_group_by_small(ptr(a), ptr(b), int(mul), int(sub), int(K), E, ptr(g.order), ptr(g.gid),
                                     ptr(g.seg_start), ptr(g.ukeys), ptr(g.ngroups), int(max_groups), ptr(ws),
                                     ws.numel(), stream()), "ramp_group_by_small")
@@ -1330,8 +1319,7 @@ def neighbors(kk, jj, kk_bound=0, jj_bound=0):
     jx = torch.empty(E, dtype=torch.int64, device=kk.device)
     if E == 0:
         return ix, jx
-    nbytes = lib().ramp_neighbors_workspace_bytes(E)
-    ws = _lib.workspace(nbytes, kk.device, "graph")
+    ws, nbytes = sized_workspace("ramp_neighbors_workspace_bytes", (E,), kk.device, "graph")
     check(lib().ramp_neighbors(ptr(kk), ptr(jj), ptr(ix), ptr(jx), E, int(kk_bound),
                                int(jj_bound), ptr(ws), ws.numel(), stream()), "ramp_neighbors")
     return ix, jx
