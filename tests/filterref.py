@@ -179,3 +179,14 @@ def stream(N, seed=3, H=13, W=17, hot_pixels=3, tick=STREAM_TICK):
     ts = np.round(ts / tick) * tick
     order = np.argsort(ts, kind="stable")
     return xs[order].astype(np.float32), ys[order].astype(np.float32), ts[order]
+
+
+def shuffle_keeping_pixels(x, y, rng):
+    """a permutation of the events that keeps every pixel's own events in their order"""
+    pix = np.trunc(y).astype(int) * 1000 + np.trunc(x).astype(int)
+    slots = rng.permutation(len(x))
+    perm = np.empty(len(x), int)
+    for q in np.unique(pix):
+        at = np.nonzero(pix == q)[0]
+        perm[np.sort(slots[at])] = at
+    return perm

@@ -15,7 +15,6 @@ w32 0.16, w10_m7 0.10, w10_t4 0.37, w10_gated 0.60; chi2 at most 8e-7 from float
 
 chi2 is held to E 2^-23 relative (the ordered-sum bound for positive terms), n_valid and Mu exactly.  Every case prints its
 measured errors and the ratio to its bound before it asserts."""
-import gc
 import os
 import sys
 
@@ -28,6 +27,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import covref  # noqa: E402
+import trackerkit as kit  # noqa: E402
 from oracle.make_golden_params import BA_PIN  # noqa: E402
 from scenes import ba_pin_scene  # noqa: E402
 
@@ -157,26 +157,6 @@ def test_a_system_that_is_not_finite_gives_nan_and_the_info_bit():
 T_FRAMES = 30
 
 
-def _frames():
-    if "frames" not in _cache:
-        from rampvo_amd.synthetic import SyntheticStream
-        stream = SyntheticStream(192, 256, T_FRAMES, seed=11, device="cuda")
-        _cache["frames"] = [stream.frame(t) for t in range(T_FRAMES)]
-        torch.cuda.synchronize()
-    return _cache["frames"]
-
-
-def _tracker(device_steps):
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import make_network
-    torch.manual_seed(5)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=16, MIXED_PRECISION=True), make_network("SingleScale"),
-                   {"event_bias": True}, ht=192, wd=256)
-    slam.device_steps, slam.inputs_ready = device_steps, device_steps
-    return slam
-
-
 def _snap(u):
     return dict(frames=list(u["frames"]), cov=u["cov"].cpu().numpy().copy(), depth_var=u["depth_var"].cpu().numpy().copy(),
                 pose_cov=u["pose_cov"].cpu().numpy().copy(), chi2=u["chi2"], n_valid=u["n_valid"], dof=u["dof"],
@@ -187,13 +167,13 @@ def _snap(u):
 def _tracked(device_steps, query):
     key = ("trk", device_steps, query)
     if key not in _cache:
-        slam = _tracker(device_steps)
+        slam = kit.tracker(device_steps, device_steps, **kit.COV_TRACKER)
         out = dict(dicts={}, resident={}, first_error=None)
         try:
             slam.uncertainty()
         except RuntimeError as e:
             out["first_error"] = str(e)
-        for t, (im, ev, K, mask) in enumerate(_frames()):
+        for t, (im, ev, K, mask) in enumerate(kit.frames(*kit.COV_STREAM)):
             slam(float(t), input_tensor=(ev, im, mask), intrinsics=K)
             res = slam._dev is not None and slam._dev.active
             out["resident"][t] = bool(res)
@@ -218,8 +198,7 @@ def _tracked(device_steps, query):
         traj, _ = slam.terminate()
         out["traj"], out["patches"] = traj, slam.patches_[:slam.n].cpu().numpy()
         del slam
-        torch.cuda.synchronize()
-        gc.collect()
+        kit.quiesce()
         _cache[key] = out
     return _cache[key]
 

@@ -8,6 +8,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from lstmref import ENC_HIP_VS_ATEN_TOL, torch_towers
+
 pytestmark = pytest.mark.gpu
 
 
@@ -240,7 +242,6 @@ def test_instance_norm_accumulators_match_the_finalize_launch(cin, cout, k, stri
             assert torch.equal(rb.raw, ab.raw) and torch.equal(rout, aout)
 
 
-ENC_HIP_VS_ATEN_TOL = 4e-5  # fp32 HIP encoder against the ATen forward of the same modules, x the map's largest entry (measured 4.9e-6 / 9.4e-6)
 FP8_LAYER_TOL = 2e-3        # x the output scale: what is left after both sides use the SAME e4m3-rounded operands
 FP8_ENCODER_TOL = 0.2       # max abs error of fmap / imap against the f16-MFMA towers, x the map's largest entry (measured: 0.07-0.125)
 
@@ -383,7 +384,7 @@ def test_singlescale_encoder_hip_vs_aten():
             for t in range(3):
                 im, ev, _, _ = stream.frame(t)
                 if backend == "torch":
-                    with _torch_towers():
+                    with torch_towers():
                         f, i, _ = fwd(events=ev.cuda(), images=im.cuda(), reinit_hidden=(t == 0), out_scale=0.25)
                 else:
                     f, i, _ = fwd(events=ev.cuda(), images=im.cuda(), reinit_hidden=(t == 0), out_scale=0.25)
@@ -397,24 +398,6 @@ def test_singlescale_encoder_hip_vs_aten():
         worst = max(worst, ef, ei)
         assert ef <= ENC_HIP_VS_ATEN_TOL and ei <= ENC_HIP_VS_ATEN_TOL, (ef, ei)
     print("HIP fp32 encoder vs ATen, worst max-abs / max:", worst)
-
-
-def _torch_towers():
-    """bind the torch forwards of the tower modules (ResidualBlock ...) for the duration of the reference run"""
-    import contextlib
-    from oracle import host_cpu
-
-    @contextlib.contextmanager
-    def ctx():
-        saved = [(c, a, c.__dict__.get(a)) for c, a, _ in host_cpu.module_patches()]
-        for c, a, f in host_cpu.module_patches():
-            setattr(c, a, f)
-        try:
-            yield
-        finally:
-            for c, a, f in saved:
-                setattr(c, a, f)
-    return ctx()
 
 
 def test_multiscale_encoder_hip_vs_aten():
@@ -434,7 +417,7 @@ def test_multiscale_encoder_hip_vs_aten():
                 kw = dict(events=ev.cuda(), images=im.cuda(), mask=torch.tensor([masks[t]]), reinit_hidden=(t == 0),
                           out_scale=0.25)
                 if backend == "torch":
-                    with _torch_towers():
+                    with torch_towers():
                         f, i = host_cpu.multiscale_forward(enc, **kw)
                 else:
                     f, i = enc(**kw)

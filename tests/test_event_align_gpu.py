@@ -15,15 +15,15 @@ import alignref
 import contrastref
 import georef
 import interpref
+import trackerkit as kit
+from guarded import Flat
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
 
 _memo = {}
 OUTPUTS = ("correction", "correction_f32", "result", "grad", "history", "status", "info")
 
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def dots():
@@ -249,46 +249,42 @@ def test_refusals_canaries_and_repeated_bits():
     """the C entry with guard words on both sides of every output and of the workspace; three calls repeat every bit"""
     from rampvo_amd import _lib
     L = _lib.lib()
-    G, iters = 64, 5
+    iters = 5
     dx, dy, dt, dp, dk, dtm, t_ref, dK, dd, H, W = dev("walk")
     T, N = dk.shape[0], dx.shape[0]
     nbytes = L.ramp_event_align_workspace_bytes(T, H, W)
     assert nbytes >= L.ramp_event_contrast_workspace_bytes(T, H, W) + 400 and nbytes % 8 == 0
 
-    def guarded(n, dtype, fill):
-        buf = torch.full((n + 2 * G,), fill, dtype=dtype, device="cuda")
-        return buf, buf[G:G + n]
-
-    bufs = dict(correction=guarded(7, torch.float64, -7.0), correction_f32=guarded(7, torch.float32, -7.0),
-                result=guarded(4, torch.float64, -7.0), grad=guarded(7, torch.float64, -7.0), history=guarded(iters, torch.float64, -7.0),
-                status=guarded(8, torch.int32, -7), info=guarded(8, torch.int32, -7), ws=guarded(nbytes, torch.uint8, 0xA5))
-    assert bufs["ws"][1].data_ptr() % 16 == 0
+    bufs = dict(correction=Flat(7, torch.float64, -7.0), correction_f32=Flat(7, torch.float32, -7.0),
+                result=Flat(4, torch.float64, -7.0), grad=Flat(7, torch.float64, -7.0), history=Flat(iters, torch.float64, -7.0),
+                status=Flat(8, torch.int32, -7), info=Flat(8, torch.int32, -7), ws=Flat(nbytes, torch.uint8, 0xA5))
+    assert bufs["ws"].t.data_ptr() % 16 == 0
     P = _lib.ptr
 
     def call(N=N, ws_bytes=nbytes, flags=_lib.RAMP_WARP_DEPTH_MAP, free_mask=127, step=0.02, iters=iters, max_evals=1000, t_ref=t_ref,
              skip=None, cor=None):
-        o = lambda k: None if k == skip else P(bufs[k][1])
+        o = lambda k: None if k == skip else P(bufs[k].t)
         rc = L.ramp_event_align(P(dx), P(dy), P(dt), P(dp), N, P(dk), P(dtm), T, t_ref, P(dK), P(dd), cor, flags, H, W, free_mask,
                                 step, iters, max_evals, o("correction"), o("correction_f32"), o("result"), o("grad"), o("history"),
                                 o("status"), o("info"), o("ws"), ws_bytes, _lib.stream())
         torch.cuda.synchronize()
         return rc
 
-    before = {k: v[0].clone() for k, v in bufs.items()}
+    before = {k: v.snapshot() for k, v in bufs.items()}
     for kw in (dict(N=-1), dict(flags=_lib.RAMP_WARP_IDENTITY), dict(free_mask=128), dict(step=float("inf")), dict(step=float("nan")),
                dict(t_ref=float("nan")), dict(iters=-1), dict(iters=65537), dict(max_evals=0)) + tuple(dict(skip=k) for k in bufs):
         assert call(**kw) == -1, kw
     assert call(ws_bytes=nbytes - 8) == -3 and call(N=0, ws_bytes=nbytes - 8) == -3
-    assert all(torch.equal(before[k], bufs[k][0]) for k in bufs)                 # nothing written by a refused call
+    assert all(bufs[k].unchanged(before[k]) for k in bufs)                 # nothing written by a refused call
     ref = expected(dev("walk"), **WALK_CALL)
     runs = []
     for _ in range(3):
         for k in OUTPUTS:
-            bufs[k][1].fill_(-7)
+            bufs[k].t.fill_(-7)
         assert call() == 0                                                       # (max_evals = 1000 is clamped to 1 + 9 * iters)
-        for k, (buf, mid) in bufs.items():
-            assert torch.equal(buf[:G], before[k][:G]) and torch.equal(buf[-G:], before[k][-G:]), k
-        runs.append({k: bufs[k][1].cpu().numpy().copy() for k in OUTPUTS})
+        for k, b in bufs.items():
+            assert b.intact(), k
+        runs.append({k: bufs[k].t.cpu().numpy().copy() for k in OUTPUTS})
         runs[-1]["variance"], runs[-1]["variance0"] = runs[-1]["result"][0], runs[-1]["result"][1]
         check(runs[-1], ref, "the C entry")
     same_outputs(runs[0], runs[1], "second call")
@@ -313,12 +309,6 @@ FILTER = dict(support_dt=0.02, refractory=1e-4, hot_count=20)
 HOST_KEYS = ["correction", "history", "n_accepted", "n_evals", "reason", "variance", "variance0"]
 
 
-def _events_for(f, n_ev=5000):
-    rng = np.random.default_rng(21)
-    return (cu(rng.uniform(0, 319, n_ev).astype(np.float32)), cu(rng.uniform(0, 239, n_ev).astype(np.float32)),
-            cu(rng.uniform(100.0 + 0.5 * (f - 2), 100.0 + 0.5 * f, n_ev)), cu(rng.choice([-1, 1], n_ev).astype(np.int8)))
-
-
 def _raw_events(f, n_ev=4000):
     rng = np.random.default_rng(31)
     return (cu(rng.integers(100, 160, n_ev).astype(np.int32)), cu(rng.integers(100, 140, n_ev).astype(np.int32)),
@@ -334,39 +324,25 @@ def _same_as_host_form(res, h, what):
     assert georef.same_bits(np.float64(res["variance0"]), np.float64(h["variance0"])), what
 
 
-@torch.no_grad()
-def _run_resident(query):
-    import test_queries_own_stream_gpu as own
+def _ask(slam, f, frame):
     from rampvo_amd import ops
-    slam = own._tracker(True, True)
+    x, y, t, p = kit.query_events(f)
     res = {}
-    for f, frame in enumerate(own._frames()):
-        own._feed(slam, f, frame)
-        if f == own.T_QUERY and query:
-            x, y, t, p = _events_for(f)
-            res["resident_before"] = own._resident(slam)
-            out = slam.align_events(x, y, t, p, iters=2, as_tensor=True)
-            res["read"] = slam.align_events(x, y, t, p, iters=2, resident=True)
-            res["host"] = slam.align_events(x, y, t, p, iters=2)
-            knots, ts = slam.trajectory(as_tensor=True)
-            n = slam.peek()["n"]
-            med = torch.median(slam.patches_[n - 3:n, :, 2])
-            ref = ops.event_align(x, y, t, p, knots, cu(np.asarray(ts, np.float64)), float(ts[-1]), frame[2].cuda().float(), med, 240, 320,
-                                  iters=2, resident=True)
-            res["out"], res["ref"] = own._host(out), own._host(ref)
-            xr, yr, tr, pr = _raw_events(f)
-            slam.set_camera(**SENSOR)
-            slam.set_event_filter(**FILTER)
-            res["passed"] = slam.align_events(xr, yr, tr, pr, iters=1, distorted=True, denoise=True, resident=True)
-            res["passed_host"] = slam.align_events(xr, yr, tr, pr, iters=1, distorted=True, denoise=True)
-            res["passed_dev"] = own._host(slam.align_events(xr, yr, tr, pr, iters=1, distorted=True, denoise=True, as_tensor=True))
-            res["resident_after"] = own._resident(slam)
-        if f > own.T_QUERY:
-            n = slam.peek()["n"]
-            res["state", f] = dict(n=n, poses=slam.poses_[:n].cpu().numpy())
-    res["resident_at_end"] = own._resident(slam)
-    del slam
-    own._quiesce()
+    out = slam.align_events(x, y, t, p, iters=2, as_tensor=True)
+    res["read"] = slam.align_events(x, y, t, p, iters=2, resident=True)
+    res["host"] = slam.align_events(x, y, t, p, iters=2)
+    knots, ts = slam.trajectory(as_tensor=True)
+    n = slam.peek()["n"]
+    med = torch.median(slam.patches_[n - 3:n, :, 2])
+    ref = ops.event_align(x, y, t, p, knots, cu(np.asarray(ts, np.float64)), float(ts[-1]), frame[2].cuda().float(), med, 240, 320,
+                          iters=2, resident=True)
+    res["out"], res["ref"] = kit.host(out), kit.host(ref)
+    xr, yr, tr, pr = _raw_events(f)
+    slam.set_camera(**SENSOR)
+    slam.set_event_filter(**FILTER)
+    res["passed"] = slam.align_events(xr, yr, tr, pr, iters=1, distorted=True, denoise=True, resident=True)
+    res["passed_host"] = slam.align_events(xr, yr, tr, pr, iters=1, distorted=True, denoise=True)
+    res["passed_dev"] = kit.host(slam.align_events(xr, yr, tr, pr, iters=1, distorted=True, denoise=True, as_tensor=True))
     return res
 
 
@@ -374,10 +350,9 @@ def test_tracker_align_events_device_resident():
     """slam.align_events(resident=True) equals ops.event_align(resident=True) on trajectory(as_tensor=True), the fed intrinsics
     and the tracker's depth median, and the host form; the tracker stays device resident and ends with the pose bits of one never
     asked; distorted=True and denoise=True pass through"""
-    import test_queries_own_stream_gpu as own
-    a, c = _run_resident(True), _run_resident(False)
+    a, c = kit.run_resident(True, _ask), kit.run_resident(True, None)
     assert a["resident_before"] and a["resident_after"] and a["resident_at_end"] and c["resident_at_end"]
-    own._same(a["out"], a["ref"], "against ops.event_align")
+    kit.same(a["out"], a["ref"], "against ops.event_align")
     assert sorted(a["out"]) == sorted(OUTPUTS + ("variance", "variance0"))
     _same_as_host_form(a["read"], a["host"], "one read")
     assert georef.same_bits(np.asarray(a["read"]["correction"]), a["out"]["correction"]) and a["read"]["n_evals"] == a["out"]["info"][2]
@@ -386,32 +361,31 @@ def test_tracker_align_events_device_resident():
     for k in ("rectify_status", "filter_status"):
         assert np.array_equal(a["passed"][k], a["passed_host"][k]) and np.array_equal(a["passed"][k], a["passed_dev"][k]), k
     assert a["passed"]["filter_status"][7] > 500 and a["passed"]["rectify_status"][0] == 0
-    for f in (own.T_QUERY + 1, own.T_QUERY + 2):
-        own._same(a["state", f], c["state", f], "state of a tracker that is never asked, frame %d" % f)
+    for f in (kit.T_QUERY + 1, kit.T_QUERY + 2):
+        kit.same(a["state", f], c["state", f], "state of a tracker that is never asked, frame %d" % f)
 
 
 @torch.no_grad()
 def test_tracker_align_events_host_driven():
-    import test_queries_own_stream_gpu as own
     from rampvo_amd import ops
-    slam = own._tracker(False, False)
-    for f, frame in enumerate(own._frames()):
-        own._feed(slam, f, frame)
+    slam = kit.tracker(False, False)
+    for f, frame in enumerate(kit.frames()):
+        kit.feed(slam, f, frame)
         if slam.is_initialized and slam._n >= 4:
             break
     assert slam.is_initialized and slam._dev is None
-    x, y, t, p = (v.cpu().numpy() for v in _events_for(f, 1000))
+    x, y, t, p = (v.cpu().numpy() for v in kit.query_events(f, 1000))
     res = slam.align_events(x, y, t, p, iters=2, resident=True)                       # numpy in, one read
     _same_as_host_form(res, slam.align_events(x, y, t, p, iters=2), "host driven")
     knots, ts = slam.trajectory(as_tensor=True)
     med = torch.median(slam.patches_[slam._n - 3:slam._n, :, 2])
     ref = ops.event_align(cu(x), cu(y), cu(t), cu(p), knots, cu(np.asarray(ts, np.float64)), float(ts[-1]), frame[2].cuda().float(), med,
                           240, 320, iters=2, resident=True)
-    own._same(own._host(slam.align_events(x, y, t, p, iters=2, as_tensor=True)), own._host(ref), "against ops.event_align")
+    kit.same(kit.host(slam.align_events(x, y, t, p, iters=2, as_tensor=True)), kit.host(ref), "against ops.event_align")
     slam.tlist = slam.tlist[::-1]
     with pytest.raises(RuntimeError, match="time stamps decrease"):
         slam.align_events(x, y, t, p, iters=1, resident=True)
     quiet = slam.align_events(x, y, t, p, iters=1, as_tensor=True)                    # nothing raised: the words say it
     assert int(quiet["info"][4]) & 1 and int(quiet["info"][0]) == alignref.FLAT and bool(torch.isnan(quiet["variance"]))
     del slam
-    own._quiesce()
+    kit.quiesce()

@@ -8,9 +8,7 @@ gradient: per component ``|grad - float64| <= georef.bound(floor, env)``, env = 
 against float64 on the same inputs, floor = 1e-5 x the sum of the absolute per-event terms of that component.
 
 Images are 24 x 32 and 37 x 53 (not square, not multiples of a wave).  The tracker tests run the small synthetic tracker of
-test_event_warp_gpu.py through the helpers of test_queries_own_stream_gpu.py."""
-import contextlib
-import ctypes
+tests/trackerkit.py."""
 from fractions import Fraction
 
 import numpy as np
@@ -20,7 +18,10 @@ import torch
 import contrastref
 import georef
 import interpref
+import trackerkit as kit
 import warpref
+from guarded import Flat
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
 
@@ -29,9 +30,6 @@ SIZES = {"24x32": (24, 32, np.array([30.0, 28.0, 15.5, 11.25], np.float32)),
 THETA = np.array([0.3, -0.2, 0.15, 0.25, -0.3, 0.5, 0.2], np.float32)
 _tab = {}
 
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _scene(seed, n, size="24x32", T=5, margin=1.5, depth="scalar", step=None):
@@ -244,43 +242,39 @@ def test_arguments_and_canaries():
     """the C entry with guard words on both sides of every output and of the workspace; N == 0 launches and writes nothing"""
     from rampvo_amd import _lib
     L = _lib.lib()
-    N, T, G = 300, 5, 64
+    N, T = 300, 5
     args = _scene(19, N)
     dx, dy, dt, dp, dk, dtm, t_ref, dK, _, H, W = _dev(args)
     dd = torch.full((1,), 0.5, device="cuda")
     dth = cu(THETA)
     nbytes = L.ramp_event_contrast_workspace_bytes(T, H, W)
 
-    def guarded(n, dtype, fill):
-        buf = torch.full((n + 2 * G,), fill, dtype=dtype, device="cuda")
-        return buf, buf[G:G + n]
-
-    bufs = dict(iwe=guarded(2 * H * W, torch.float32, -7.0), sums=guarded(2, torch.int64, -7), stats=guarded(8, torch.float64, -7.0),
-                grad=guarded(7, torch.float64, -7.0), status=guarded(8, torch.int32, -7), ws=guarded(nbytes, torch.uint8, 0xA5))
-    assert bufs["ws"][1].data_ptr() % 16 == 0
+    bufs = dict(iwe=Flat(2 * H * W, torch.float32, -7.0), sums=Flat(2, torch.int64, -7), stats=Flat(8, torch.float64, -7.0),
+                grad=Flat(7, torch.float64, -7.0), status=Flat(8, torch.int32, -7), ws=Flat(nbytes, torch.uint8, 0xA5))
+    assert bufs["ws"].t.data_ptr() % 16 == 0
 
     def call(N=N, ws_bytes=nbytes, flags=0, outs=("iwe", "grad")):
-        o = lambda k: _lib.ptr(bufs[k][1]) if k in outs else None
+        o = lambda k: _lib.ptr(bufs[k].t) if k in outs else None
         rc = L.ramp_event_contrast(_lib.ptr(dx), _lib.ptr(dy), _lib.ptr(dt), _lib.ptr(dp), N, _lib.ptr(dk), _lib.ptr(dtm), T, t_ref,
-                                   _lib.ptr(dK), _lib.ptr(dd), _lib.ptr(dth), flags, H, W, o("iwe"), _lib.ptr(bufs["sums"][1]),
-                                   _lib.ptr(bufs["stats"][1]), o("grad"), _lib.ptr(bufs["ws"][1]), ws_bytes,
-                                   _lib.ptr(bufs["status"][1]), _lib.stream())
+                                   _lib.ptr(dK), _lib.ptr(dd), _lib.ptr(dth), flags, H, W, o("iwe"), _lib.ptr(bufs["sums"].t),
+                                   _lib.ptr(bufs["stats"].t), o("grad"), _lib.ptr(bufs["ws"].t), ws_bytes,
+                                   _lib.ptr(bufs["status"].t), _lib.stream())
         torch.cuda.synchronize()
         return rc
 
-    before = {k: v[0].clone() for k, v in bufs.items()}
+    before = {k: v.snapshot() for k, v in bufs.items()}
     assert call(N=0) == 0 and call(flags=_lib.RAMP_WARP_IDENTITY) == -1 and call(ws_bytes=nbytes - 8) == -3
-    assert all(torch.equal(before[k], bufs[k][0]) for k in bufs)                 # nothing written, status included
+    assert all(bufs[k].unchanged(before[k]) for k in bufs)                 # nothing written, status included
     assert call(outs=()) == 0                                                    # neither optional output
-    assert torch.equal(before["iwe"], bufs["iwe"][0]) and torch.equal(before["grad"], bufs["grad"][0])
-    stats_only = bufs["stats"][1].cpu().numpy().copy()
+    assert bufs["iwe"].unchanged(before["iwe"]) and bufs["grad"].unchanged(before["grad"])
+    stats_only = bufs["stats"].t.cpu().numpy().copy()
     assert call() == 0
-    for k, (buf, mid) in bufs.items():
-        assert torch.equal(buf[:G], before[k][:G]) and torch.equal(buf[-G:], before[k][-G:]), k
+    for k, b in bufs.items():
+        assert b.intact(), k
     ref = _contrast(args, correction=THETA, want_iwe=True)
-    assert georef.same_bits(bufs["stats"][1].cpu().numpy(), ref["stats"]) and georef.same_bits(stats_only, ref["stats"])
-    assert georef.same_bits(bufs["grad"][1].cpu().numpy(), ref["grad"]) and georef.same_bits(bufs["iwe"][1].view(2, H, W).cpu().numpy(), ref["iwe"])
-    assert np.array_equal(bufs["sums"][1].cpu().numpy(), ref["sums"]) and np.array_equal(bufs["status"][1].cpu().numpy(), ref["status"])
+    assert georef.same_bits(bufs["stats"].t.cpu().numpy(), ref["stats"]) and georef.same_bits(stats_only, ref["stats"])
+    assert georef.same_bits(bufs["grad"].t.cpu().numpy(), ref["grad"]) and georef.same_bits(bufs["iwe"].t.view(2, H, W).cpu().numpy(), ref["iwe"])
+    assert np.array_equal(bufs["sums"].t.cpu().numpy(), ref["sums"]) and np.array_equal(bufs["status"].t.cpu().numpy(), ref["status"])
 
 
 # ------------------------------------------------------------------------------------------------ 5. the line search
@@ -301,44 +295,22 @@ def test_event_align_on_the_dot_scene():
 
 
 # ------------------------------------------------------------------------------------------------ 6. tracker
-def _events_for(f, n_ev=5000):
-    rng = np.random.default_rng(21)
-    return (cu(rng.uniform(0, 319, n_ev).astype(np.float32)), cu(rng.uniform(0, 239, n_ev).astype(np.float32)),
-            cu(rng.uniform(100.0 + 0.5 * (f - 2), 100.0 + 0.5 * f, n_ev)), cu(rng.choice([-1, 1], n_ev).astype(np.int8)))
-
-
-@torch.no_grad()
-def _run_resident(ready, query):
-    import test_queries_own_stream_gpu as own
+def _ask(slam, f, frame):
     from rampvo_amd import ops
-    slam = own._tracker(True, ready)
-    side = torch.cuda.Stream() if ready == "stream" else None
+    x, y, t, p = kit.query_events(f)
     res = {}
-    with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-        for f, frame in enumerate(own._frames()):
-            own._feed(slam, f, frame)
-            if f == own.T_QUERY and query:
-                x, y, t, p = _events_for(f)
-                res["resident_before"] = own._resident(slam)
-                out = slam.event_contrast(x, y, t, p, correction=THETA * 0.1, want_iwe=True, as_tensor=True)
-                res["numpy"] = slam.event_contrast(x, y, t, p, correction=THETA * 0.1, want_iwe=True)
-                res["map"] = own._host(slam.event_contrast(x, y, t, p, invdepth="map", radius=own.RADIUS, signed=False, as_tensor=True))
-                res["align"] = slam.align_events(x, y, t, p, iters=2)
-                res["resident_after"] = own._resident(slam)
-                knots, ts = slam.trajectory(as_tensor=True)
-                n = slam.peek()["n"]
-                med = torch.median(slam.patches_[n - 3:n, :, 2])
-                K = frame[2].cuda().float()
-                tdev = cu(np.asarray(ts, np.float64))
-                ref = ops.event_contrast(x, y, t, p, knots, tdev, float(ts[-1]), K, med, 240, 320, correction=THETA * 0.1, want_iwe=True)
-                res["align_ref"] = ops.event_align(x, y, t, p, knots, tdev, float(ts[-1]), K, med, 240, 320, iters=2)
-                res["out"], res["ref"] = own._host(out), own._host(ref)
-            if f > own.T_QUERY:
-                n = slam.peek()["n"]
-                res["state", f] = dict(n=n, poses=slam.poses_[:n].cpu().numpy())
-        res["resident_at_end"] = own._resident(slam)
-    del slam
-    own._quiesce()
+    out = slam.event_contrast(x, y, t, p, correction=THETA * 0.1, want_iwe=True, as_tensor=True)
+    res["numpy"] = slam.event_contrast(x, y, t, p, correction=THETA * 0.1, want_iwe=True)
+    res["map"] = kit.host(slam.event_contrast(x, y, t, p, invdepth="map", radius=kit.RADIUS, signed=False, as_tensor=True))
+    res["align"] = slam.align_events(x, y, t, p, iters=2)
+    knots, ts = slam.trajectory(as_tensor=True)
+    n = slam.peek()["n"]
+    med = torch.median(slam.patches_[n - 3:n, :, 2])
+    K = frame[2].cuda().float()
+    tdev = cu(np.asarray(ts, np.float64))
+    ref = ops.event_contrast(x, y, t, p, knots, tdev, float(ts[-1]), K, med, 240, 320, correction=THETA * 0.1, want_iwe=True)
+    res["align_ref"] = ops.event_align(x, y, t, p, knots, tdev, float(ts[-1]), K, med, 240, 320, iters=2)
+    res["out"], res["ref"] = kit.host(out), kit.host(ref)
     return res
 
 
@@ -346,38 +318,36 @@ def test_tracker_event_contrast_and_align():
     """slam.event_contrast / align_events equal ops.event_contrast / event_align on trajectory(as_tensor=True), the fed
     intrinsics and the tracker's depth median, bit for bit; the same from a tracker on its own stream; the tracker stays device
     resident and ends with the pose bits of one never asked"""
-    import test_queries_own_stream_gpu as own
-    a, b, c = _run_resident(True, True), _run_resident("stream", True), _run_resident(True, False)
+    a, b, c = kit.run_resident(True, _ask), kit.run_resident("stream", _ask), kit.run_resident(True, None)
     for r in (a, b):
         assert r["resident_before"] and r["resident_after"] and r["resident_at_end"]
-        own._same(r["out"], r["ref"], "against ops.event_contrast")
+        kit.same(r["out"], r["ref"], "against ops.event_contrast")
         assert isinstance(r["numpy"]["variance"], float)
-        own._same({k: v for k, v in r["numpy"].items() if k != "variance"}, {k: v for k, v in r["out"].items() if k != "variance"},
-                  "numpy form")
-        own._same(r["align"], r["align_ref"], "against ops.event_align")
+        kit.same({k: v for k, v in r["numpy"].items() if k != "variance"}, {k: v for k, v in r["out"].items() if k != "variance"},
+                 "numpy form")
+        kit.same(r["align"], r["align_ref"], "against ops.event_align")
         st = r["out"]["status"]
         assert st[0] == 0 and st[3:7].sum() == 5000 and r["out"]["stats"][0] > 0 and np.isfinite(r["out"]["grad"]).all()
         assert r["map"]["status"][0] == 0 and r["map"]["stats"][0] > 0
         assert r["align"]["variance"] >= r["align"]["variance0"]
     for k in ("out", "map", "align"):
-        own._same(b[k], a[k], "own stream: " + k)
+        kit.same(b[k], a[k], "own stream: " + k)
     assert c["resident_at_end"]
-    for f in (own.T_QUERY + 1, own.T_QUERY + 2):
-        own._same(a["state", f], c["state", f], "state of a tracker that is never asked, frame %d" % f)
-        own._same(b["state", f], c["state", f], "own stream, frame %d" % f)
+    for f in (kit.T_QUERY + 1, kit.T_QUERY + 2):
+        kit.same(a["state", f], c["state", f], "state of a tracker that is never asked, frame %d" % f)
+        kit.same(b["state", f], c["state", f], "own stream, frame %d" % f)
 
 
 @torch.no_grad()
 def test_tracker_event_contrast_host_driven():
-    import test_queries_own_stream_gpu as own
     from rampvo_amd import ops
-    slam = own._tracker(False, False)
-    for f, frame in enumerate(own._frames()):
-        own._feed(slam, f, frame)
+    slam = kit.tracker(False, False)
+    for f, frame in enumerate(kit.frames()):
+        kit.feed(slam, f, frame)
         if slam.is_initialized and slam._n >= 4:
             break
     assert slam.is_initialized and slam._dev is None
-    x, y, t, p = (v.cpu().numpy() for v in _events_for(f, 1000))
+    x, y, t, p = (v.cpu().numpy() for v in kit.query_events(f, 1000))
     out = slam.event_contrast(x, y, t, p, correction=THETA * 0.1)                     # numpy in, numpy out
     al = slam.align_events(x, y, t, p, iters=2)
     knots, ts = slam.trajectory(as_tensor=True)
@@ -387,11 +357,11 @@ def test_tracker_event_contrast_host_driven():
     assert sorted(out) == ["grad", "stats", "status", "sums", "variance"] and out["variance"] == out["stats"][0] > 0
     for k in ("grad", "stats", "status", "sums"):
         assert isinstance(out[k], np.ndarray) and np.array_equal(out[k], ref[k].cpu().numpy()), k
-    own._same(al, ops.event_align(cu(x), cu(y), cu(t), cu(p), knots, tdev, float(ts[-1]), K, med, 240, 320, iters=2), "align")
+    kit.same(al, ops.event_align(cu(x), cu(y), cu(t), cu(p), knots, tdev, float(ts[-1]), K, med, 240, 320, iters=2), "align")
     slam.tlist = slam.tlist[::-1]
     with pytest.raises(RuntimeError, match="time stamps decrease"):
         slam.event_contrast(x, y, t, p)
     with pytest.raises(RuntimeError, match="time stamps decrease"):
         slam.align_events(x, y, t, p, iters=1)
     del slam
-    own._quiesce()
+    kit.quiesce()

@@ -11,35 +11,21 @@ import torch
 
 import filterref as fr
 import georef
+import trackerkit as kit
+from guarded import Flat
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
 
 H, W = 13, 17
-PAD = 16
-GUARD = {torch.uint8: 0xA5, torch.float32: 12345.0, torch.float64: 12345.0, torch.int32: -77, torch.int64: -77}
 ALL = dict(fr.STREAM_PARAMS)
 _cache = {}
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def stream(N, seed=3):
     if (N, seed) not in _cache:
         _cache[N, seed] = fr.stream(N, seed=seed)
     return _cache[N, seed]
-
-
-def guarded(shape, dtype):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * PAD,), GUARD[dtype], dtype=dtype, device="cuda")
-    return buf, buf[PAD:PAD + n]
-
-
-def guards_intact(buf):
-    g = torch.cat([buf[:PAD], buf[-PAD:]]).cpu()
-    return bool((g == GUARD[buf.dtype]).all())
 
 
 def entry(x, y, t, N, h, w, flags, support_dt, refractory, hot_count, hot_sigma, hot_in, last_in, last_out, keep, xy, index,
@@ -62,12 +48,11 @@ def call(x, y, t, h=H, w=W, support_dt=None, refractory=0.0, hot_count=0, hot_si
     td = cu(np.asarray(t, np.float64))
     N = len(td)
     hot_in = None if hot_mask is None else cu((np.asarray(hot_mask) != 0).astype(np.uint8))
-    bufs = {k: guarded(s, d) for k, (s, d) in dict(keep=((N,), torch.uint8), xy=((N, 2), torch.float32), index=((N,), torch.int32),
-                                                     count=((1,), torch.int64), hot=((h, w), torch.uint8),
-                                                     stats=((4,), torch.float64), status=((8,), torch.int32),
-                                                     last_t=((h, w), torch.float64)).items()}
-    o = {k: v[1] for k, v in bufs.items()}
-    at = {k: ctypes.c_void_p(b.data_ptr() + PAD * b.element_size()) for k, (b, _) in bufs.items()}   # (an empty view has no pointer)
+    bufs = {k: Flat(n, d) for k, (n, d) in dict(keep=(N, torch.uint8), xy=(N * 2, torch.float32), index=(N, torch.int32),
+                                                count=(1, torch.int64), hot=(h * w, torch.uint8), stats=(4, torch.float64),
+                                                status=(8, torch.int32), last_t=(h * w, torch.float64)).items()}
+    o = {k: v.t for k, v in bufs.items()}
+    at = {k: ctypes.c_void_p(b.address()) for k, b in bufs.items()}          # (an empty view has no pointer)
     last_in = None
     if last_t is not None:
         if inplace:
@@ -82,12 +67,12 @@ def call(x, y, t, h=H, w=W, support_dt=None, refractory=0.0, hot_count=0, hot_si
                at["hot"], at["stats"], at["status"], ws, nbytes)
     assert rc == 0, rc
     torch.cuda.synchronize()
-    for k, (buf, _) in bufs.items():
-        assert guards_intact(buf), "guard band of " + k
+    for k, b in bufs.items():
+        assert b.intact(), "guard band of " + k
     res = {k: v.cpu().numpy() for k, v in o.items()}
     if N == 0:                                                     # nothing launched: status, count, hot and stats are untouched
         for k in ("status", "count", "hot", "stats") + (() if last_t is not None else ("last_t",)):
-            assert (res[k] == GUARD[o[k].dtype]).all(), k
+            assert (res[k] == bufs[k].canary).all(), k
         res["status"][:], res["count"][:] = 0, 0
         res["hot"] = np.zeros(h * w, np.uint8) if hot_mask is None else (np.asarray(hot_mask) != 0).astype(np.uint8).reshape(-1)
         res["stats"] = np.array([0.0, np.nan, np.nan, np.nan])
@@ -242,9 +227,8 @@ def test_state_in_place_and_with_hot_pixels():
 
 
 def test_per_pixel_sorted_globally_shuffled():
-    import test_filterref_cpu as cpu
     x, y, t = stream(4099)
-    perm = cpu.shuffle_keeping_pixels(x, y, np.random.default_rng(2))
+    perm = fr.shuffle_keeping_pixels(x, y, np.random.default_rng(2))
     assert (np.diff(t[perm]) < 0).sum() > 1000
     g = check(x[perm], y[perm], t[perm], **ALL)
     assert g["status"][0] == 0 and (g["status"][4:] > 100).all()
@@ -406,14 +390,14 @@ def _events(f, n_ev=4000):
     return x, y, t, rng.choice([-1, 1], n_ev).astype(np.int8)
 
 
-def _tracker_queries(slam, own, f):
+def _tracker_queries(slam, f):
     """everything the tracker tests assert, asked between two frames"""
     from rampvo_amd import ops
     xh, yh, th, ph = _events(f)
     x, y, t, p = cu(xh), cu(yh), cu(th), cu(ph)
     xf, yf = x.float(), y.float()
-    before = own._host(dict(v=slam.event_voxel_grid(xf, yf, t, p, num_bins=3, as_tensor=True),
-                            c=slam.compensate_events(xf, yf, t, p, want_xy=True, as_tensor=True)))
+    before = kit.host(dict(v=slam.event_voxel_grid(xf, yf, t, p, num_bins=3, as_tensor=True),
+                           c=slam.compensate_events(xf, yf, t, p, want_xy=True, as_tensor=True)))
     for ask in (lambda: slam.event_voxel_grid(x, y, t, p, denoise=True), lambda: slam.compensate_events(x, y, t, p, denoise=True),
                 lambda: slam.event_contrast(x, y, t, p, denoise=True), lambda: slam.align_events(x, y, t, p, iters=1, denoise=True),
                 lambda: slam.filter_events(x, y, t)):
@@ -422,19 +406,19 @@ def _tracker_queries(slam, own, f):
     with pytest.raises(RuntimeError, match="unknown parameter"):
         slam.set_event_filter(support=1.0)
     slam.set_event_filter(**PARAMS)
-    after = own._host(dict(v=slam.event_voxel_grid(xf, yf, t, p, num_bins=3, as_tensor=True),
-                           c=slam.compensate_events(xf, yf, t, p, want_xy=True, as_tensor=True)))
-    own._same(after, before, "denoise=False after set_event_filter")
+    after = kit.host(dict(v=slam.event_voxel_grid(xf, yf, t, p, num_bins=3, as_tensor=True),
+                          c=slam.compensate_events(xf, yf, t, p, want_xy=True, as_tensor=True)))
+    kit.same(after, before, "denoise=False after set_event_filter")
     # filter_events carries the state across two calls
     cut = 1500
     ref = fr.event_filter(xh, yh, th, 240, 320, **PARAMS)
     a = slam.filter_events(xh[:cut], yh[:cut], th[:cut])                       # numpy in (int32: the integer path), numpy out
-    b = own._host(slam.filter_events(x[cut:], y[cut:], t[cut:], as_tensor=True))
+    b = kit.host(slam.filter_events(x[cut:], y[cut:], t[cut:], as_tensor=True))
     assert np.array_equal(np.concatenate([a["keep"], b["keep"]]), ref["keep"]) and ref["status"][4] == 200 and ref["status"][7] > 500
-    assert georef.same_bits(b["last_t"], ref["last_t"]) and georef.same_bits(own._host(slam._filter_state), ref["last_t"])
+    assert georef.same_bits(b["last_t"], ref["last_t"]) and georef.same_bits(kit.host(slam._filter_state), ref["last_t"])
     with pytest.raises(RuntimeError, match="decrease in time"):
         slam.filter_events(xh, yh, th)                                         # the same events again: they lie before the state
-    assert georef.same_bits(own._host(slam._filter_state), ref["last_t"])      # ... which is left as it was
+    assert georef.same_bits(kit.host(slam._filter_state), ref["last_t"])       # ... which is left as it was
     slam.reset_event_filter()
     assert slam._filter_state is None
     # denoise=True: filtering by hand, then the query
@@ -442,14 +426,14 @@ def _tracker_queries(slam, own, f):
     hx, hy = hand["xy"][:, 0], hand["xy"][:, 1]
     want = slam.event_voxel_grid(hx, hy, t, p, num_bins=3, as_tensor=True)
     want["filter_status"] = hand["status"]
-    own._same(own._host(slam.event_voxel_grid(x, y, t, p, num_bins=3, as_tensor=True, denoise=True)), own._host(want), "voxel")
+    kit.same(kit.host(slam.event_voxel_grid(x, y, t, p, num_bins=3, as_tensor=True, denoise=True)), kit.host(want), "voxel")
     want = slam.compensate_events(hx, hy, t, p, want_xy=True, as_tensor=True)
     want["filter_status"] = hand["status"]
-    got = own._host(slam.compensate_events(x, y, t, p, want_xy=True, as_tensor=True, denoise=True))
-    own._same(got, own._host(want), "compensate")
+    got = kit.host(slam.compensate_events(x, y, t, p, want_xy=True, as_tensor=True, denoise=True))
+    kit.same(got, kit.host(want), "compensate")
     assert got["status"][3] == 4000 - ref["status"][7]                         # the dropped events: the warp's NaN count
     host = slam.compensate_events(xh, yh, th, ph, want_xy=True, denoise=True)
-    own._same(host, got, "numpy form")
+    kit.same(host, got, "numpy form")
     c = slam.event_contrast(x, y, t, p, denoise=True)
     assert np.array_equal(c["filter_status"], ref["status"]) and np.isfinite(c["variance"])
     al = slam.align_events(x, y, t, p, iters=1, denoise=True)
@@ -458,58 +442,37 @@ def _tracker_queries(slam, own, f):
     return dict(filter=b, compensate=got, contrast=c, host=host)
 
 
-@torch.no_grad()
-def _run_resident(query):
-    import test_queries_own_stream_gpu as own
-    slam = own._tracker(True, True)
-    state = None
-    for f, frame in enumerate(own._frames()[:own.T_QUERY + 2]):
-        own._feed(slam, f, frame)
-        if f == own.T_QUERY and query:
-            assert own._resident(slam)
-            _tracker_queries(slam, own, f)
-            assert own._resident(slam)
-        if f == own.T_QUERY + 1:
-            n = slam.peek()["n"]
-            state = dict(n=n, poses=slam.poses_[:n].cpu().numpy(), patches=slam.patches_[:n].cpu().numpy())
-    assert own._resident(slam)
-    del slam
-    own._quiesce()
-    return state
-
-
 def test_tracker_device_resident():
-    import test_queries_own_stream_gpu as own
-    own._same(_run_resident(True), _run_resident(False), "the frame behind the queries")
+    a, c = kit.run_resident(True, lambda slam, f, frame: _tracker_queries(slam, f)), kit.run_resident(True, None)
+    assert a["resident_before"] and a["resident_after"] and a["resident_at_end"] and c["resident_at_end"]
+    kit.same(a["state", kit.T_QUERY + 1], c["state", kit.T_QUERY + 1], "the frame behind the queries")
 
 
 @torch.no_grad()
 def _run_host_driven(query, ready):
     import contextlib
-    import test_queries_own_stream_gpu as own
-    slam = own._tracker(False, ready)
+    slam = kit.tracker(False, ready)
     side = torch.cuda.Stream() if ready == "stream" else None
-    frames, res = own._frames(), None
+    frames, res = kit.frames(), None
     with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
         for f, frame in enumerate(frames):
-            own._feed(slam, f, frame)
+            kit.feed(slam, f, frame)
             if slam.is_initialized and slam._n >= 4:
                 break
         assert slam.is_initialized and slam._dev is None
         if query:
-            res = _tracker_queries(slam, own, f)
-        own._feed(slam, f + 1, frames[f + 1])
+            res = _tracker_queries(slam, f)
+        kit.feed(slam, f + 1, frames[f + 1])
         n = slam._n
         state = dict(n=n, poses=slam.poses_[:n].cpu().numpy(), patches=slam.patches_[:n].cpu().numpy())
         assert slam._dev is None
     del slam
-    own._quiesce()
+    kit.quiesce()
     return state, res
 
 
 def test_tracker_host_driven_and_on_its_own_stream():
-    import test_queries_own_stream_gpu as own
     (a, ra), (b, _), (c, rc) = _run_host_driven(True, False), _run_host_driven(False, False), _run_host_driven(True, "stream")
-    own._same(a, b, "the frame behind the queries")
-    own._same(c, a, "own stream: the frame behind the queries")
-    own._same(rc, ra, "own stream: the queries")
+    kit.same(a, b, "the frame behind the queries")
+    kit.same(c, a, "own stream: the frame behind the queries")
+    kit.same(rc, ra, "own stream: the queries")

@@ -7,13 +7,16 @@ env the float32 restatement's own error.  Validity agrees with float64's except 
 (``rectifyref.excused``): none excused on the ordinary cameras, at most 2 % on the strong one.  Pixel values are compared BIT FOR
 BIT with the exact emulator (``rectifyref.sample``) fed the kernel's own map.  The sensor is 64 x 48.
 
-The tracker tests run the small synthetic tracker of test_queries_own_stream_gpu.py (240 x 320, 48 patches per frame)."""
+The tracker tests run the small synthetic tracker of tests/trackerkit.py."""
 import numpy as np
 import pytest
 import torch
 
 import georef
 import rectifyref as rr
+import trackerkit as kit
+from guarded import Flat
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
 
@@ -22,9 +25,6 @@ NAMES = {rr.PINHOLE: "pinhole", rr.RADTAN: "radtan", rr.EQUIDISTANT: "equidistan
 EVENT_CAMERAS = tuple(n for n in rr.CAMERAS if n != "strong_wide")
 _cache = {}
 
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _camera(name):
@@ -174,11 +174,6 @@ def test_a_camera_record_that_cannot_be_used(word, value):
     assert img["status"].tolist() == [1, 47 * 61, 47 * 61, 0, 0, 0, 0, 0] and ops.image_rectify_status(img["status"])["bad_camera"]
 
 
-def _guarded(n, dtype, fill, G=64, shift=0):
-    buf = torch.full((n + 2 * G + shift,), fill, dtype=dtype, device="cuda")
-    return buf, buf[G + shift:G + shift + n]
-
-
 def test_event_canaries_and_the_unaligned_store_path():
     """the C entry with guard words around xy_out and valid_out; an xy_out that is 8- but not 16-byte aligned takes the other
     store path and gives the same bits"""
@@ -188,18 +183,15 @@ def test_event_canaries_and_the_unaligned_store_path():
     dx, dy, cam = cu(x), cu(y), _camera("strong")
     for N in (len(x), 256, 255, 1):
         for shift in (0, 2):
-            xy, xy_mid = _guarded(2 * N, torch.float32, -7.0, shift=shift)
-            va, va_mid = _guarded(N, torch.uint8, 0xA5)
-            st, st_mid = _guarded(8, torch.int32, -7)
-            assert xy_mid.data_ptr() % 16 == 4 * shift and xy_mid.data_ptr() % 8 == 0
-            rc = L.ramp_event_rectify(_lib.ptr(dx), _lib.ptr(dy), N, _lib.ptr(cam), 0, H, W, _lib.ptr(xy_mid), _lib.ptr(va_mid),
-                                      _lib.ptr(st_mid), _lib.stream())
+            xy, va, st = Flat(2 * N, torch.float32, -7.0, shift=shift), Flat(N, torch.uint8, 0xA5), Flat(8, torch.int32, -7)
+            assert xy.t.data_ptr() % 16 == 4 * shift and xy.t.data_ptr() % 8 == 0
+            rc = L.ramp_event_rectify(_lib.ptr(dx), _lib.ptr(dy), N, _lib.ptr(cam), 0, H, W, _lib.ptr(xy.t), _lib.ptr(va.t),
+                                      _lib.ptr(st.t), _lib.stream())
             torch.cuda.synchronize()
             assert rc == 0
-            assert (xy[:64 + shift] == -7.0).all() and (xy[64 + shift + 2 * N:] == -7.0).all()
-            assert (va[:64] == 0xA5).all() and (va[64 + N:] == 0xA5).all() and (st[:64] == -7).all() and (st[72:] == -7).all()
-            assert georef.same_bits(xy_mid.cpu().numpy().reshape(N, 2), r["xy"][:N])
-            assert np.array_equal(va_mid.cpu().numpy(), r["valid"][:N]) and int(st_mid[1]) == N
+            assert xy.intact() and va.intact() and st.intact()
+            assert georef.same_bits(xy.t.cpu().numpy().reshape(N, 2), r["xy"][:N])
+            assert np.array_equal(va.t.cpu().numpy(), r["valid"][:N]) and int(st.t[1]) == N
 
 
 def test_invalid_arguments():
@@ -283,17 +275,14 @@ def test_image_canaries():
     from rampvo_amd import _lib
     L = _lib.lib()
     src, cam, h, w = cu(_source(3, np.uint8)), _camera("strong_wide"), 61, 77
-    out, out_mid = _guarded(3 * h * w, torch.float32, -7.0)
-    m, m_mid = _guarded(2 * h * w, torch.float32, -7.0)
-    k, k_mid = _guarded(h * w, torch.uint8, 0xA5)
-    st, st_mid = _guarded(8, torch.int32, -7)
-    rc = L.ramp_image_rectify(_lib.ptr(src), 3, H, W, _lib.ptr(cam), _lib.RAMP_RECTIFY_SRC_U8, 1, 0.0, h, w, _lib.ptr(out_mid),
-                              _lib.ptr(m_mid), _lib.ptr(k_mid), _lib.ptr(st_mid), _lib.stream())
+    out, m = Flat(3 * h * w, torch.float32, -7.0), Flat(2 * h * w, torch.float32, -7.0)
+    k, st = Flat(h * w, torch.uint8, 0xA5), Flat(8, torch.int32, -7)
+    rc = L.ramp_image_rectify(_lib.ptr(src), 3, H, W, _lib.ptr(cam), _lib.RAMP_RECTIFY_SRC_U8, 1, 0.0, h, w, _lib.ptr(out.t),
+                              _lib.ptr(m.t), _lib.ptr(k.t), _lib.ptr(st.t), _lib.stream())
     torch.cuda.synchronize()
     assert rc == 0
-    for buf, n, fill in ((out, 3 * h * w, -7.0), (m, 2 * h * w, -7.0), (k, h * w, 0xA5), (st, 8, -7)):
-        assert (buf[:64] == fill).all() and (buf[64 + n:] == fill).all()
-    assert not (out_mid == -7.0).any() and int(st_mid[1]) == h * w
+    assert out.intact() and m.intact() and k.intact() and st.intact()
+    assert not (out.t == -7.0).any() and int(st.t[1]) == h * w
 
 
 # ------------------------------------------------------------------------------------------------ 3. round trip, consumers
@@ -342,13 +331,13 @@ SENSOR = dict(model="radtan", raw_intrinsics=(205.0, 204.0, 158.5, 121.5), coeff
 
 
 def _raw_events(f, n_ev=5000):
-    """raw integer pixels of a 320 x 240 sensor, as a sensor gives them"""
+    """raw integer pixels of a 320 x 240 sensor, as a sensor gives them (not trackerkit.query_events: integer coordinates)"""
     rng = np.random.default_rng(21)
     return (cu(rng.integers(0, 320, n_ev).astype(np.int32)), cu(rng.integers(0, 240, n_ev).astype(np.int32)),
             cu(np.sort(rng.uniform(100.0 + 0.5 * (f - 2), 100.0 + 0.5 * f, n_ev))), cu(rng.choice([-1, 1], n_ev).astype(np.int8)))
 
 
-def _queries(slam, own, x, y, t, p):
+def _queries(slam, x, y, t, p):
     """the distorted=True forms against the parts they are made of -> dict of (got, want) pairs on the host"""
     from rampvo_amd import ops
     cam = ops.camera(new_intrinsics=slam.intrinsics_[0] * float(slam.RES), **SENSOR)
@@ -369,64 +358,62 @@ def _queries(slam, own, x, y, t, p):
     want = ops.image_rectify(img, cam, 240, 320, normalize="half", want_mask=True)
     want.pop("map")
     res["image"] = (slam.rectify_image(img, as_tensor=True), want)
-    return {k: (own._host(a), own._host(b)) for k, (a, b) in res.items()}
+    return {k: (kit.host(a), kit.host(b)) for k, (a, b) in res.items()}
 
 
 @torch.no_grad()
 def test_tracker_distorted_queries_device_resident():
-    import test_queries_own_stream_gpu as own
-    slam = own._tracker(True, True)
+    slam = kit.tracker(True, True)
     res = {}
-    for f, frame in enumerate(own._frames()):
-        own._feed(slam, f, frame)
-        if f == own.T_QUERY:
+    for f, frame in enumerate(kit.frames()):
+        kit.feed(slam, f, frame)
+        if f == kit.T_QUERY:
             x, y, t, p = _raw_events(f)
-            assert own._resident(slam)
-            before = own._host(slam.compensate_events(x.float(), y.float(), t, p, want_xy=True, as_tensor=True))
+            assert kit.resident(slam)
+            before = kit.host(slam.compensate_events(x.float(), y.float(), t, p, want_xy=True, as_tensor=True))
             with pytest.raises(RuntimeError, match="set_camera"):
                 slam.compensate_events(x, y, t, p, distorted=True)
             with pytest.raises(RuntimeError, match="set_camera"):
                 slam.rectify_events(x, y)
             slam.set_camera(**SENSOR)
-            after = own._host(slam.compensate_events(x.float(), y.float(), t, p, want_xy=True, as_tensor=True))
-            res = _queries(slam, own, x, y, t, p)
+            after = kit.host(slam.compensate_events(x.float(), y.float(), t, p, want_xy=True, as_tensor=True))
+            res = _queries(slam, x, y, t, p)
             aligned = slam.align_events(x, y, t, p, iters=1, distorted=True)
-            assert own._resident(slam)
-    assert own._resident(slam)
-    own._same(after, before, "distorted=False after set_camera")               # today's code path, untouched
+            assert kit.resident(slam)
+    assert kit.resident(slam)
+    kit.same(after, before, "distorted=False after set_camera")               # today's code path, untouched
     for k, (got, want) in res.items():
-        own._same(got, want, k)
+        kit.same(got, want, k)
     s = res["compensate"][0]
     assert s["rectify_status"][0] == 0 and s["rectify_status"][1] == 5000 and s["rectify_status"][6] > 1000
     assert s["status"][3] == s["rectify_status"][2:5].sum()                    # the rows without a solution: the warp's NaN count
     assert np.array_equal(aligned["rectify_status"], s["rectify_status"]) and np.isfinite(aligned["variance"])
     assert res["image"][0]["image"].shape == (3, 240, 320) and res["image"][0]["mask"].sum() > 10000
     del slam
-    own._quiesce()
+    kit.quiesce()
 
 
 @torch.no_grad()
 def test_tracker_distorted_queries_host_driven():
     """a host-driven tracker: numpy in, numpy out, the same bits as the parts; a record that is not finite makes the numpy
     form raise"""
-    import test_queries_own_stream_gpu as own
-    slam = own._tracker(False, False)
-    for f, frame in enumerate(own._frames()):
-        own._feed(slam, f, frame)
+    slam = kit.tracker(False, False)
+    for f, frame in enumerate(kit.frames()):
+        kit.feed(slam, f, frame)
         if slam.is_initialized and slam._n >= 4:
             break
     assert slam.is_initialized and slam._dev is None
     x, y, t, p = _raw_events(f, 1000)
-    before = own._host(slam.compensate_events(x.float(), y.float(), t, p, want_xy=True, as_tensor=True))
+    before = kit.host(slam.compensate_events(x.float(), y.float(), t, p, want_xy=True, as_tensor=True))
     with pytest.raises(RuntimeError, match="set_camera"):
         slam.event_voxel_grid(x, y, t, p, distorted=True)
     slam.set_camera(**SENSOR)
-    own._same(own._host(slam.compensate_events(x.float(), y.float(), t, p, want_xy=True, as_tensor=True)), before, "distorted=False")
-    for k, (got, want) in _queries(slam, own, x, y, t, p).items():
-        own._same(got, want, k)
+    kit.same(kit.host(slam.compensate_events(x.float(), y.float(), t, p, want_xy=True, as_tensor=True)), before, "distorted=False")
+    for k, (got, want) in _queries(slam, x, y, t, p).items():
+        kit.same(got, want, k)
     xh, yh, th, ph = (v.cpu().numpy() for v in (x, y, t, p))
     host = slam.compensate_events(xh, yh, th, ph, want_xy=True, distorted=True)      # numpy in (int32: the integer path), numpy out
-    own._same(host, own._host(slam.compensate_events(x, y, t, p, want_xy=True, as_tensor=True, distorted=True)), "numpy form")
+    kit.same(host, kit.host(slam.compensate_events(x, y, t, p, want_xy=True, as_tensor=True, distorted=True)), "numpy form")
     assert sorted(slam.rectify_events(xh, yh)) == ["status", "valid", "xy"]
     slam.set_camera("radtan", (float("nan"), 204.0, 158.5, 121.5), SENSOR["coeffs"])
     with pytest.raises(RuntimeError, match="camera record"):
@@ -434,4 +421,4 @@ def test_tracker_distorted_queries_host_driven():
     with pytest.raises(RuntimeError, match="camera record"):
         slam.rectify_image(np.zeros((240, 320), np.uint8))
     del slam
-    own._quiesce()
+    kit.quiesce()

@@ -6,22 +6,22 @@ The accumulators, the raw grid, n, the sum and the mean are compared BIT FOR BIT
 normalised cell within one fp32 ulp.  Against the reference class's recorded output (tests/golden/event_voxel.npz) the
 tolerance is the envelope rule of ``voxelref.compare``.  Images are 13 x 17 and 4 x 5.
 
-The tracker tests run the small synthetic tracker of test_queries_own_stream_gpu.py (240 x 320, 48 patches per frame)."""
+The tracker tests run the small synthetic tracker of tests/trackerkit.py."""
 
 import numpy as np
 import pytest
 import torch
 
 import georef
+import trackerkit as kit
 import voxelref
+from guarded import Flat
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
 
 H, W = 13, 17
 
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _events(seed, n, h=H, w=W, margin=1.0):
@@ -284,34 +284,29 @@ def test_chunking_canaries_and_the_accumulators():
     one that holds all three give the same bits; the int64 accumulators in the workspace are the emulator's"""
     from rampvo_amd import _lib
     L = _lib.lib()
-    N, S, bins, G = 900, 3, 5, 64
+    N, S, bins = 900, 3, 5
     x, y, t, p = _events(15, N)
     off = np.array([0, 250, 250, 900], np.int64)
     dx, dy, dt, dp, doff = cu(x), cu(y), cu(t), cu(p), cu(off)
     one, three = (L.ramp_event_voxel_workspace_bytes(s, bins, H, W) for s in (1, 3))
     C = bins * H * W
 
-    def guarded(n, dtype, fill):
-        buf = torch.full((n + 2 * G,), fill, dtype=dtype, device="cuda")
-        return buf, buf[G:G + n]
-
     res = {}
     for nbytes in (one, three, three + 4096):
-        bufs = dict(grid=guarded(S * C, torch.float32, -7.0), stats=guarded(4 * S, torch.float64, -7.0),
-                    status=guarded(8, torch.int32, -7), ws=guarded(nbytes, torch.uint8, 0xA5))
-        assert bufs["ws"][1].data_ptr() % 16 == 0
-        before = {k: v[0].clone() for k, v in bufs.items()}
+        bufs = dict(grid=Flat(S * C, torch.float32, -7.0), stats=Flat(4 * S, torch.float64, -7.0),
+                    status=Flat(8, torch.int32, -7), ws=Flat(nbytes, torch.uint8, 0xA5))
+        assert bufs["ws"].t.data_ptr() % 16 == 0
         for flags in (0, _lib.RAMP_VOXEL_NORMALIZE | _lib.RAMP_VOXEL_SUBPIXEL):
             rc = L.ramp_event_voxel(_lib.ptr(dx), _lib.ptr(dy), _lib.ptr(dt), _lib.ptr(dp), N, _lib.ptr(doff), S, bins, H, W, flags,
-                                    _lib.ptr(bufs["grid"][1]), _lib.ptr(bufs["stats"][1]), _lib.ptr(bufs["status"][1]),
-                                    _lib.ptr(bufs["ws"][1]), nbytes, _lib.stream())
+                                    _lib.ptr(bufs["grid"].t), _lib.ptr(bufs["stats"].t), _lib.ptr(bufs["status"].t),
+                                    _lib.ptr(bufs["ws"].t), nbytes, _lib.stream())
             torch.cuda.synchronize()
             assert rc == 0
-            for k, (buf, mid) in bufs.items():
-                assert torch.equal(buf[:G], before[k][:G]) and torch.equal(buf[-G:], before[k][-G:]), k
-            res[nbytes, flags] = {k: bufs[k][1].cpu().numpy().copy() for k in ("grid", "stats", "status")}
+            for k, b in bufs.items():
+                assert b.intact(), k
+            res[nbytes, flags] = {k: bufs[k].t.cpu().numpy().copy() for k in ("grid", "stats", "status")}
         if nbytes == three:                                                  # all slices at once: counters, n and sum, accumulators
-            words = bufs["ws"][1].cpu().numpy()
+            words = bufs["ws"].t.cpu().numpy()
             acc = words[64 + 16 * S:64 + 16 * S + 8 * S * C].view(np.int64).reshape(S, bins, H, W)
             ref = voxelref.accumulate(x, y, t, p, H, W, bins, offsets=off, subpixel=True)
             assert np.array_equal(acc, ref["acc"])
@@ -328,38 +323,23 @@ def test_chunking_canaries_and_the_accumulators():
 
 # ------------------------------------------------------------------------------------------------ 7. tracker
 def _tracker_events(f, n_ev=5000):
-    rng = np.random.default_rng(21)
-    return (cu(rng.uniform(0, 319, n_ev).astype(np.float32)), cu(rng.uniform(0, 239, n_ev).astype(np.float32)),
-            cu(np.sort(rng.uniform(100.0 + 0.5 * (f - 2), 100.0 + 0.5 * f, n_ev))), cu(rng.choice([-1, 1], n_ev).astype(np.int8)))
+    x, y, t, p = kit.query_events(f, n_ev)
+    return x, y, torch.sort(t).values, p
 
 
-@torch.no_grad()
-def _run_resident(query):
-    import test_queries_own_stream_gpu as own
+def _ask(slam, f, frame):
     from rampvo_amd import ops
-    slam = own._tracker(True, True)
+    x, y, t, p = _tracker_events(f)
+    off = ops.event_slices(5000, 2000)
     res = {}
-    for f, frame in enumerate(own._frames()):
-        own._feed(slam, f, frame)
-        if f == own.T_QUERY and query:
-            x, y, t, p = _tracker_events(f)
-            off = ops.event_slices(5000, 2000)
-            res["resident_before"] = own._resident(slam)
-            plain = slam.event_voxel_grid(x, y, t, p, offsets=off, as_tensor=True)
-            comp = slam.event_voxel_grid(x, y, t, p, num_bins=3, compensate=True, as_tensor=True)
-            res["numpy"] = slam.event_voxel_grid(x, y, t, p, num_bins=3, compensate=True)
-            res["resident_after"] = own._resident(slam)
-            warp = slam.compensate_events(x, y, t, p, want_xy=True, want_iwe=False, as_tensor=True)
-            ref = ops.event_voxel_grid(warp["xy"][:, 0], warp["xy"][:, 1], t, p, 240, 320, num_bins=3, subpixel=True)
-            ref["warp_status"] = warp["status"]
-            res["plain"], res["plain_ref"] = own._host(plain), own._host(ops.event_voxel_grid(x, y, t, p, 240, 320, offsets=off))
-            res["comp"], res["comp_ref"] = own._host(comp), own._host(ref)
-        if f > own.T_QUERY:
-            n = slam.peek()["n"]
-            res["state", f] = dict(n=n, poses=slam.poses_[:n].cpu().numpy())
-    res["resident_at_end"] = own._resident(slam)
-    del slam
-    own._quiesce()
+    plain = slam.event_voxel_grid(x, y, t, p, offsets=off, as_tensor=True)
+    comp = slam.event_voxel_grid(x, y, t, p, num_bins=3, compensate=True, as_tensor=True)
+    res["numpy"] = slam.event_voxel_grid(x, y, t, p, num_bins=3, compensate=True)
+    warp = slam.compensate_events(x, y, t, p, want_xy=True, want_iwe=False, as_tensor=True)
+    ref = ops.event_voxel_grid(warp["xy"][:, 0], warp["xy"][:, 1], t, p, 240, 320, num_bins=3, subpixel=True)
+    ref["warp_status"] = warp["status"]
+    res["plain"], res["plain_ref"] = kit.host(plain), kit.host(ops.event_voxel_grid(x, y, t, p, 240, 320, offsets=off))
+    res["comp"], res["comp_ref"] = kit.host(comp), kit.host(ref)
     return res
 
 
@@ -367,27 +347,25 @@ def test_tracker_event_voxel_grid():
     """slam.event_voxel_grid equals ops.event_voxel_grid at the tracker's image size; compensate=True equals
     compensate_events(want_xy) followed by the sub-pixel grid; the tracker stays device resident and ends with the pose bits
     of one never asked"""
-    import test_queries_own_stream_gpu as own
-    a, c = _run_resident(True), _run_resident(False)
+    a, c = kit.run_resident(True, _ask), kit.run_resident(True, None)
     assert a["resident_before"] and a["resident_after"] and a["resident_at_end"] and c["resident_at_end"]
-    own._same(a["plain"], a["plain_ref"], "against ops.event_voxel_grid")
-    own._same(a["comp"], a["comp_ref"], "against compensate_events + the sub-pixel grid")
-    own._same(a["numpy"], a["comp"], "numpy form")
+    kit.same(a["plain"], a["plain_ref"], "against ops.event_voxel_grid")
+    kit.same(a["comp"], a["comp_ref"], "against compensate_events + the sub-pixel grid")
+    kit.same(a["numpy"], a["comp"], "numpy form")
     assert a["plain"]["grid"].shape == (2, 5, 240, 320) and a["comp"]["grid"].shape == (3, 240, 320)
     assert a["plain"]["status"].tolist()[:2] == [0, 4000] and a["comp"]["status"][0] == 0 and a["comp"]["status"][5] > 2500
     assert a["comp"]["warp_status"][0] == 0 and a["comp"]["stats"][0, 0] > 1000 and np.isfinite(a["comp"]["grid"]).all()
-    for f in (own.T_QUERY + 1, own.T_QUERY + 2):
-        own._same(a["state", f], c["state", f], "state of a tracker that is never asked, frame %d" % f)
+    for f in (kit.T_QUERY + 1, kit.T_QUERY + 2):
+        kit.same(a["state", f], c["state", f], "state of a tracker that is never asked, frame %d" % f)
 
 
 @torch.no_grad()
 def test_tracker_event_voxel_grid_host_driven():
     """a host-driven tracker: numpy in, numpy out, the same bits as the parts; bad offsets make the numpy form raise"""
-    import test_queries_own_stream_gpu as own
     from rampvo_amd import ops
-    slam = own._tracker(False, False)
-    for f, frame in enumerate(own._frames()):
-        own._feed(slam, f, frame)
+    slam = kit.tracker(False, False)
+    for f, frame in enumerate(kit.frames()):
+        kit.feed(slam, f, frame)
         if slam.is_initialized and slam._n >= 4:
             break
     assert slam.is_initialized and slam._dev is None
@@ -395,10 +373,10 @@ def test_tracker_event_voxel_grid_host_driven():
     plain = slam.event_voxel_grid(x, y, t, p, normalize=False)
     comp = slam.event_voxel_grid(x, y, t, p, compensate=True)
     assert sorted(plain) == ["grid", "stats", "status"] and sorted(comp) == ["grid", "stats", "status", "warp_status"]
-    own._same(plain, own._host(ops.event_voxel_grid(cu(x), cu(y), cu(t), cu(p), 240, 320, normalize=False)), "plain")
+    kit.same(plain, kit.host(ops.event_voxel_grid(cu(x), cu(y), cu(t), cu(p), 240, 320, normalize=False)), "plain")
     warp = slam.compensate_events(cu(x), cu(y), cu(t), cu(p), want_xy=True, want_iwe=False, as_tensor=True)
     ref = ops.event_voxel_grid(warp["xy"][:, 0], warp["xy"][:, 1], cu(t), cu(p), 240, 320, subpixel=True)
-    own._same({k: comp[k] for k in ref}, own._host(ref), "compensated")
+    kit.same({k: comp[k] for k in ref}, kit.host(ref), "compensated")
     assert comp["status"][0] == 0 and comp["status"][5] > 500
     with pytest.raises(RuntimeError, match="slice offsets"):
         slam.event_voxel_grid(x, y, t, p, offsets=np.array([0, 600, 500]))
@@ -406,4 +384,4 @@ def test_tracker_event_voxel_grid_host_driven():
     with pytest.raises(RuntimeError, match="time stamps decrease"):
         slam.event_voxel_grid(x, y, t, p, compensate=True)
     del slam
-    own._quiesce()
+    kit.quiesce()

@@ -6,10 +6,8 @@ Coordinates are compared per event with the float64 restatement (tests/warpref.p
 the same inputs.  The splat is compared BIT FOR BIT with the exact emulator (``warpref.scatter``) applied to the kernel's
 own ``xy``.  Images are 12 x 20 (not square), intrinsics (16, 12, 9.5, 6.25).
 
-The tracker test runs the small synthetic tracker of test_pose_query_gpu.py (240 x 320, 48 patches per frame, seed 77, the
-`wide` weights with d_gain = 14.5, fp16 features), device resident."""
+The tracker test runs the small synthetic tracker of tests/trackerkit.py, device resident and publishing pose records."""
 import ctypes
-import gc
 
 import numpy as np
 import pytest
@@ -17,17 +15,15 @@ import torch
 
 import georef
 import interpref
+import trackerkit as kit
 import warpref
+from guarded import Flat
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
 
 H, W = 12, 20
 K = np.array([16.0, 12.0, 9.5, 6.25], np.float32)
-_cache = {}
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _events(seed, n, t_lo, t_hi, margin=0.0):
@@ -239,7 +235,7 @@ def test_arguments_and_canaries():
     T < 1, H / W / bins < 1, no output, a t_ref that is not finite: RAMP_EINVAL; a short workspace: RAMP_EWORKSPACE"""
     from rampvo_amd import _lib
     L = _lib.lib()
-    N, T, bins, G = 300, 5, 5, 64
+    N, T, bins = 300, 5, 5
     knots, times = interpref.walk_scene(19, T)
     x, y, t, p = _events(20, N, -1.0, 5.0, margin=2.0)
     dx, dy, dt, dp, dk, dtm, dK = cu(x), cu(y), cu(t), cu(p), cu(knots), cu(times), cu(K)
@@ -247,88 +243,62 @@ def test_arguments_and_canaries():
     nbytes = L.ramp_event_warp_workspace_bytes(T, bins, H, W)
     assert nbytes % 8 == 0
 
-    def guarded(n, dtype, fill):
-        buf = torch.full((n + 2 * G,), fill, dtype=dtype, device="cuda")
-        return buf, buf[G:G + n]
-
-    bufs = dict(xy=guarded(2 * N, torch.float32, -7.0), iwe=guarded(2 * H * W, torch.float32, -7.0),
-                sf=guarded(bins * H * W, torch.float32, -7.0), s8=guarded(bins * H * W, torch.int8, 99),
-                status=guarded(8, torch.int32, -7), ws=guarded(nbytes, torch.uint8, 0xA5))
-    assert bufs["ws"][1].data_ptr() % 16 == 0
+    bufs = dict(xy=Flat(2 * N, torch.float32, -7.0), iwe=Flat(2 * H * W, torch.float32, -7.0),
+                sf=Flat(bins * H * W, torch.float32, -7.0), s8=Flat(bins * H * W, torch.int8, 99),
+                status=Flat(8, torch.int32, -7), ws=Flat(nbytes, torch.uint8, 0xA5))
+    assert bufs["ws"].t.data_ptr() % 16 == 0
 
     def call(N=N, T=T, bins=bins, H_=H, W_=W, t_ref=2.0, outs=("xy", "iwe", "sf", "s8"), ws_bytes=nbytes, pol=dp, xy_off=0):
-        o = lambda k: _lib.ptr(bufs[k][1]) if k in outs else None
-        xy_p = ctypes.c_void_p(bufs["xy"][1].data_ptr() + xy_off) if "xy" in outs else None
+        o = lambda k: _lib.ptr(bufs[k].t) if k in outs else None
+        xy_p = ctypes.c_void_p(bufs["xy"].t.data_ptr() + xy_off) if "xy" in outs else None
         rc = L.ramp_event_warp(_lib.ptr(dx), _lib.ptr(dy), _lib.ptr(dt), _lib.ptr(pol), N, _lib.ptr(dk), _lib.ptr(dtm), T, t_ref,
                                _lib.ptr(dK), _lib.ptr(dd), 0, bins, H_, W_, xy_p, o("iwe"), o("sf"), o("s8"),
-                               _lib.ptr(bufs["ws"][1]), ws_bytes, _lib.ptr(bufs["status"][1]), _lib.stream())
+                               _lib.ptr(bufs["ws"].t), ws_bytes, _lib.ptr(bufs["status"].t), _lib.stream())
         torch.cuda.synchronize()
         return rc
 
-    before = {k: v[0].clone() for k, v in bufs.items()}
+    before = {k: v.snapshot() for k, v in bufs.items()}
     assert call(N=0) == 0
-    assert all(torch.equal(before[k], bufs[k][0]) for k in bufs)             # nothing written, status included
+    assert all(bufs[k].unchanged(before[k]) for k in bufs)                 # nothing written, status included
     for kw in (dict(T=0), dict(H_=0), dict(W_=0), dict(bins=0), dict(outs=()), dict(t_ref=float("nan")), dict(N=-1),
                dict(xy_off=4)):                                              # (xy_out rows are stored as float2)
         assert call(**kw) == -1, kw
     assert call(ws_bytes=nbytes - 8) == -3
-    assert all(torch.equal(before[k], bufs[k][0]) for k in bufs)
+    assert all(bufs[k].unchanged(before[k]) for k in bufs)
     assert call() == 0
-    for k, (buf, mid) in bufs.items():
-        assert torch.equal(buf[:G], before[k][:G]) and torch.equal(buf[-G:], before[k][-G:]), k
-    r = dict(xy=bufs["xy"][1].view(N, 2).cpu().numpy(), iwe=bufs["iwe"][1].view(2, H, W).cpu().numpy(),
-             stack=bufs["sf"][1].view(bins, H, W).cpu().numpy(), status=bufs["status"][1].cpu().numpy())
+    for k, b in bufs.items():
+        assert b.intact(), k
+    r = dict(xy=bufs["xy"].t.view(N, 2).cpu().numpy(), iwe=bufs["iwe"].t.view(2, H, W).cpu().numpy(),
+             stack=bufs["sf"].t.view(bins, H, W).cpu().numpy(), status=bufs["status"].t.cpu().numpy())
     _check_splat(r, p, bins, "f32")
-    r["stack"] = bufs["s8"][1].view(bins, H, W).cpu().numpy()
+    r["stack"] = bufs["s8"].t.view(bins, H, W).cpu().numpy()
     _check_splat(r, p, bins, "i8")
     assert warpref.compare(r["xy"], x, y, t, knots, times, 2.0, K, 0.4, H, W)["ok"]
     # a polarity of 0 is read as -1 by the C entry itself
     p0 = p.copy()
     p0[p == -1] = 0
     assert (p0 == 0).sum() > 50 and call(pol=cu(p0)) == 0
-    assert georef.same_bits(bufs["iwe"][1].view(2, H, W).cpu().numpy(), r["iwe"])
-    assert np.array_equal(bufs["s8"][1].view(bins, H, W).cpu().numpy(), r["stack"])
+    assert georef.same_bits(bufs["iwe"].t.view(2, H, W).cpu().numpy(), r["iwe"])
+    assert np.array_equal(bufs["s8"].t.view(bins, H, W).cpu().numpy(), r["stack"])
 
 
 # ------------------------------------------------------------------------------------------------ 5. tracker
-T_STREAM, T_FRAMES, T_QUERY = 46, 44, 41           # the stream, the frames and the query frame of test_pose_query_gpu.py
-
-
-def _frames():
-    if "frames" not in _cache:
-        from rampvo_amd.synthetic import SyntheticStream
-        stream = SyntheticStream(240, 320, T_STREAM, seed=77, device="cuda")   # (the canvas depends on the stream's length)
-        _cache["frames"] = [stream.frame(t) for t in range(T_FRAMES)]
-        torch.cuda.synchronize()
-    return _cache["frames"]
-
-
 @torch.no_grad()
 def _run(query):
     from rampvo_amd import ops
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import make_network
-    torch.manual_seed(5)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=48, MIXED_PRECISION=True), make_network("SingleScale", d_gain=14.5),
-                   {"event_bias": True}, ht=240, wd=320)
-    slam.device_steps, slam.inputs_ready = True, True
+    slam = kit.tracker(True, True)
     slam.pose_stream()
     res = {}
-    for f, (im, ev, Kf, mask) in enumerate(_frames()):
-        slam(100.0 + 0.5 * f, input_tensor=(ev, im, mask), intrinsics=Kf)
-        if f == T_QUERY and query:
-            assert slam._dev is not None and slam._dev.active and slam.stats["settles"] == 0
-            rng = np.random.default_rng(21)
-            n_ev = 5000
-            x, y = cu(rng.uniform(0, 319, n_ev).astype(np.float32)), cu(rng.uniform(0, 239, n_ev).astype(np.float32))
-            tn = rng.uniform(100.0 + 0.5 * (f - 2), 100.0 + 0.5 * f, n_ev)       # behind the two newest frames
-            tn[:100] = 100.0 + 0.5 * f                                           # at the reference time: G is the identity
-            t = cu(tn)
-            p = cu(rng.choice([-1, 1], n_ev).astype(np.int8))
+    for f, frame in enumerate(kit.frames()):
+        kit.feed(slam, f, frame)
+        Kf = frame[2]
+        if f == kit.T_QUERY and query:
+            assert kit.resident(slam)
+            x, y, t, p = kit.query_events(f)
+            t[:100] = kit.tstamp(f)                                              # at the reference time: G is the identity
             out = slam.compensate_events(x, y, t, p, num_bins=3, stack="i8", want_xy=True, as_tensor=True)
             res["numpy"] = slam.compensate_events(x, y, t, p, num_bins=3, stack="i8", want_xy=True)
-            res["resident_after"] = slam._dev.active and slam.stats["settles"] == 0
+            res["resident_after"] = kit.resident(slam)
             # the same from the parts: poses_at's knots, the fed intrinsics, the median the next frame's patches start from
             knots, ts = slam.trajectory(as_tensor=True)
             n = slam.peek()["n"]
@@ -339,13 +309,12 @@ def _run(query):
             res["xy_in"] = np.stack([x.cpu().numpy(), y.cpu().numpy()], -1)
             res["ref"] = {k: v.cpu().numpy() for k, v in ref.items()}
             res["med"] = float(med)
-            res["still_resident"] = slam._dev.active and slam.stats["settles"] == 0
+            res["still_resident"] = kit.resident(slam)
     n = slam.peek()["n"]
-    res["final_resident"] = slam._dev.active and slam.stats["settles"] == 0
+    res["final_resident"] = kit.resident(slam)
     res["poses"] = slam.poses_[:n].cpu().numpy()
     del slam
-    torch.cuda.synchronize()
-    gc.collect()
+    kit.quiesce()
     return res
 
 
@@ -370,18 +339,13 @@ def test_tracker_compensate_events_host_driven():
     trajectory()'s knots and the median of the last three keyframes' patches (ops.depth_median with the host's row count);
     frame time stamps that decrease make it raise"""
     from rampvo_amd import ops
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import make_network
-    torch.manual_seed(5)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=48, MIXED_PRECISION=True), make_network("SingleScale", d_gain=14.5),
-                   {"event_bias": True}, ht=240, wd=320)
-    slam.device_steps, slam.inputs_ready = False, False
-    for f, (im, ev, Kf, mask) in enumerate(_frames()):
-        slam(100.0 + 0.5 * f, input_tensor=(ev, im, mask), intrinsics=Kf)
+    slam = kit.tracker(False, False)
+    for f, frame in enumerate(kit.frames()):
+        kit.feed(slam, f, frame)
         if slam.is_initialized and slam._n >= 4:
             break
-    assert slam.is_initialized and slam._dev is None and f < T_FRAMES - 1
+    Kf = frame[2]
+    assert slam.is_initialized and slam._dev is None and f < kit.T_FRAMES - 1
     rng = np.random.default_rng(22)
     n_ev = 1000
     x, y = rng.uniform(0, 319, n_ev).astype(np.float32), rng.uniform(0, 239, n_ev).astype(np.float32)
@@ -401,8 +365,7 @@ def test_tracker_compensate_events_host_driven():
     with pytest.raises(RuntimeError, match="time stamps decrease"):
         slam.compensate_events(x, y, t, p)
     del slam
-    torch.cuda.synchronize()
-    gc.collect()
+    kit.quiesce()
 
 
 # ------------------------------------------------------------------------------------------------ 6. the small entries

@@ -114,23 +114,12 @@ def test_bad_order():
 def test_a_shuffled_stream_gives_the_sorted_streams_classes():
     x, y, t = fr.stream(1500, seed=9)
     want = fr.event_filter(x, y, t, H, W, **fr.STREAM_PARAMS)
-    perm = shuffle_keeping_pixels(x, y, np.random.default_rng(2))
+    perm = fr.shuffle_keeping_pixels(x, y, np.random.default_rng(2))
     got = fr.event_filter(x[perm], y[perm], t[perm], H, W, **fr.STREAM_PARAMS)
     assert got["status"][0] == 0
     # ties across pixels are ordered by index, which the shuffle changes: compare away from them
     clear = ~np.isin(t, t[1:][np.diff(t) == 0])
     assert clear.sum() > 1000 and np.array_equal(got["cls"][np.argsort(perm)][clear], want["cls"][clear])
-
-
-def shuffle_keeping_pixels(x, y, rng):
-    """a permutation of the events that keeps every pixel's own events in their order"""
-    pix = np.trunc(y).astype(int) * 1000 + np.trunc(x).astype(int)
-    slots = rng.permutation(len(x))
-    perm = np.empty(len(x), int)
-    for q in np.unique(pix):
-        at = np.nonzero(pix == q)[0]
-        perm[np.sort(slots[at])] = at
-    return perm
 
 
 # ------------------------------------------------------------------------------------------------ the streams

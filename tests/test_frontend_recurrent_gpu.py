@@ -390,7 +390,6 @@ def test_multiscale_encoder_at_a_plane_the_mfma_kernels_refuse():
     hand the fp16 towers an fp32 state.  fp32 against the ATen forward of the same modules, mixed precision against fp32"""
     from oracle import host_cpu
     from rampvo_amd.synthetic import SyntheticStream, make_network
-    from test_encoder_gpu import ENC_HIP_VS_ATEN_TOL, _torch_towers
     H, W = 96, 136
     stream = SyntheticStream(H, W, 3, seed=6)
     masks = [True, False, True]
@@ -404,7 +403,7 @@ def test_multiscale_encoder_at_a_plane_the_mfma_kernels_refuse():
                 im, ev, _, _ = stream.frame(t)
                 kw = dict(events=ev.cuda(), images=im.cuda(), mask=torch.tensor([masks[t]]), reinit_hidden=(t == 0), out_scale=0.25)
                 if backend == "torch":
-                    with _torch_towers():
+                    with lr.torch_towers():
                         f, i = host_cpu.multiscale_forward(enc, **kw)
                 else:
                     f, i = enc(**kw)
@@ -426,5 +425,5 @@ def test_multiscale_encoder_at_a_plane_the_mfma_kernels_refuse():
         assert f0.shape == f1.shape == f2.shape == (1, 1, 128, H // 4, W // 4) and i0.shape == i1.shape == i2.shape
         print("96x136 fp32 vs ATen: fmap %.2e imap %.2e; mixed vs fp32: fmap %.2e imap %.2e"
               % (rel(f0, f1), rel(i0, i1), rel(f1, f2), rel(i1, i2)))
-        assert rel(f0, f1) <= ENC_HIP_VS_ATEN_TOL and rel(i0, i1) <= ENC_HIP_VS_ATEN_TOL
+        assert rel(f0, f1) <= lr.ENC_HIP_VS_ATEN_TOL and rel(i0, i1) <= lr.ENC_HIP_VS_ATEN_TOL
         assert rel(f1, f2) <= 3e-2 and rel(i1, i2) <= 3e-2

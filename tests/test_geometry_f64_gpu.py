@@ -23,15 +23,12 @@ import torch
 
 import georef as gr
 import oracle as orc
+from trackerkit import cu
 from rampvo_amd._lib import RAMP_EINVAL as EINVAL, RAMP_EUNSUPPORTED as EUNSUPPORTED
 
 pytestmark = pytest.mark.gpu
 
 CANARY = 0x7fc0beef                      # a NaN pattern: a write of any float shows, and so does a read that propagates
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _api():

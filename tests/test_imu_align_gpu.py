@@ -20,29 +20,15 @@ import torch
 
 import georef
 import imuref as ir
+import trackerkit as kit
+from guarded import Flat
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -53
-PAD = 64                                    # canary rows in front of and behind every buffer
-GUARD = {torch.float64: 12345.0, torch.int32: -77}
 FIELDS = dict(dt=(0, 1), m=(1, 2), q=(2, 6), dv=(6, 9), dp=(9, 12), J=(12, 21), pad=(21, 24))
 _cache = {}
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def guarded(shape, dtype, rows=1):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * PAD * rows,), GUARD[dtype], dtype=dtype, device="cuda")
-    return buf, buf[PAD * rows:PAD * rows + n].view(*shape) if n else buf[:0]
-
-
-def intact(buf, rows=1):
-    g = torch.cat([buf[:PAD * rows], buf[buf.numel() - PAD * rows:]]).cpu()
-    return bool((g == GUARD[buf.dtype]).all())
 
 
 def host_triple(v, n=3):
@@ -58,19 +44,18 @@ def c_preintegrate(tau, gyro, accel, times, bias_g=None, bias_a=None, stride=1, 
     td, gd, ad, tt = cu(np.asarray(tau, np.float64)), cu(np.asarray(gyro)), cu(np.asarray(accel)), cu(np.asarray(times, np.float64))
     T = len(tt)
     K = (T - 1) // stride + 1
-    pb, pre = guarded((max(K - 1, 1), 24), torch.float64, 24)
-    sb, st = guarded((8,), torch.int32)
+    pre, st = Flat((max(K - 1, 1), 24), torch.float64, rows=24), Flat(8, torch.int32)
     bg, ba = host_triple(bias_g), host_triple(bias_a)
     args = dict(tau=_lib.ptr(td), gyro=_lib.ptr(gd), accel=_lib.ptr(ad), N=len(td), times=_lib.ptr(tt), T=T, stride=stride, bg=bg,
-                ba=ba, max_gap=float(max_gap), flags=_lib.RAMP_IMU_F64 if f64 else 0, preint=_lib.ptr(pre), status=_lib.ptr(st))
+                ba=ba, max_gap=float(max_gap), flags=_lib.RAMP_IMU_F64 if f64 else 0, preint=_lib.ptr(pre.t), status=_lib.ptr(st.t))
     args.update(over or {})
     rc = _lib.lib().ramp_imu_preintegrate(*[args[k] for k in ("tau", "gyro", "accel", "N", "times", "T", "stride", "bg", "ba",
                                                               "max_gap", "flags", "preint", "status")], _lib.stream())
     if rc_only:
         return rc
     assert rc == 0
-    out = pre.cpu().numpy(), st.cpu().numpy()
-    assert intact(pb, 24) and intact(sb)
+    out = pre.t.cpu().numpy(), st.t.cpu().numpy()
+    assert pre.intact() and st.intact()
     return out
 
 
@@ -84,9 +69,9 @@ def c_align(tau, gyro, accel, knots, times, R_bc=None, p_bc=None, bias_g=None, b
     T = len(tt)
     K = (T - 1) // stride + 1
     shapes = dict(result=((16,), 1), normal=((32,), 1), velocity=((K, 3), 3), residual=((max(K - 2, 0),), 1), preint=((K - 1, 24), 24))
-    bufs = {k: guarded(s, torch.float64, r) for k, (s, r) in shapes.items()}
-    bufs["status"] = guarded((8,), torch.int32)
-    at = {k: ctypes.c_void_p(b.data_ptr() + PAD * shapes.get(k, (0, 1))[1] * b.element_size()) for k, (b, _) in bufs.items()}
+    bufs = {k: Flat(s, torch.float64, rows=r) for k, (s, r) in shapes.items()}
+    bufs["status"] = Flat(8, torch.int32)
+    at = {k: ctypes.c_void_p(b.address()) for k, b in bufs.items()}
     ext = None if R_bc is None and p_bc is None else host_triple(np.concatenate([np.asarray(R_bc, np.float64).reshape(-1),
                                                                                 np.asarray(p_bc, np.float64).reshape(-1)]), 12)
     nbytes = _lib.lib().ramp_imu_workspace_bytes(len(td), K)
@@ -103,9 +88,9 @@ def c_align(tau, gyro, accel, knots, times, R_bc=None, p_bc=None, bias_g=None, b
     if rc_only:
         return rc
     assert rc == 0
-    out = {k: v.cpu().numpy() for k, (_, v) in bufs.items()}
-    for k, (b, _) in bufs.items():
-        assert intact(b, shapes.get(k, (0, 1))[1]), k
+    out = {k: b.t.cpu().numpy() for k, b in bufs.items()}
+    for k, b in bufs.items():
+        assert b.intact(), k
     return out
 
 
@@ -363,23 +348,17 @@ def test_side_stream_and_the_wrappers():
 
 
 # ------------------------------------------------------------------------------------------------ 3. tracker
-def _imu_for(f):
-    rng = np.random.default_rng(41)
-    tau = 99.0 + np.arange(int((0.5 * f + 2.0) * 200)) / 200.0 + 0.00123
-    return tau, (0.2 * rng.normal(size=(len(tau), 3))).astype(np.float32), (rng.normal(size=(len(tau), 3)) + [0, 0, 9.8]).astype(np.float32)
-
-
-def _tracker_query(slam, own, f):
+def _tracker_query(slam, f):
     from rampvo_amd import ops
-    tau, gyro, accel = _imu_for(f)
+    tau, gyro, accel = kit.imu_samples(f)
     with pytest.raises(RuntimeError, match="set_imu"):
         slam.align_imu(tau, gyro, accel)
     slam.set_imu(R_bc=ir.R_BC, p_bc=ir.P_BC, bias_g=[0.01, 0.0, -0.01])
-    got = own._host(slam.align_imu(cu(tau), cu(gyro), cu(accel), as_tensor=True, want_preint=True))
+    got = kit.host(slam.align_imu(cu(tau), cu(gyro), cu(accel), as_tensor=True, want_preint=True))
     knots, tst = slam.trajectory(as_tensor=True)
-    want = own._host(ops.imu_align(cu(tau), cu(gyro), cu(accel), knots, cu(np.asarray(tst, np.float64)), R_bc=ir.R_BC, p_bc=ir.P_BC,
-                                   bias_g=[0.01, 0.0, -0.01], gravity_norm=9.80665, want_preint=True))
-    own._same(got, want, "align_imu")
+    want = kit.host(ops.imu_align(cu(tau), cu(gyro), cu(accel), knots, cu(np.asarray(tst, np.float64)), R_bc=ir.R_BC, p_bc=ir.P_BC,
+                                  bias_g=[0.01, 0.0, -0.01], gravity_norm=9.80665, want_preint=True))
+    kit.same(got, want, "align_imu")
     n = len(tst) - 1
     assert n >= 3 and list(got["status"][2:6]) == [n, 0, 0, n]              # every interval between two frames is covered
     if got["status"][0]:
@@ -393,31 +372,29 @@ def _tracker_query(slam, own, f):
 
 @torch.no_grad()
 def test_tracker_device_resident():
-    import test_queries_own_stream_gpu as own
-    slam = own._tracker(True, True)
-    for f, frame in enumerate(own._frames()[:own.T_QUERY + 2]):
-        own._feed(slam, f, frame)
-        if f == own.T_QUERY:
-            assert own._resident(slam)
-            _tracker_query(slam, own, f)
-            assert own._resident(slam)                                      # the device-resident tracker is still resident
-    assert own._resident(slam)
+    slam = kit.tracker(True, True)
+    for f, frame in enumerate(kit.frames()[:kit.T_QUERY + 2]):
+        kit.feed(slam, f, frame)
+        if f == kit.T_QUERY:
+            assert kit.resident(slam)
+            _tracker_query(slam, f)
+            assert kit.resident(slam)                                      # the device-resident tracker is still resident
+    assert kit.resident(slam)
     del slam
-    own._quiesce()
+    kit.quiesce()
 
 
 @torch.no_grad()
 def test_tracker_host_driven():
-    import test_queries_own_stream_gpu as own
-    slam = own._tracker(False, False)
-    frames = own._frames()
+    slam = kit.tracker(False, False)
+    frames = kit.frames()
     for f, frame in enumerate(frames):
-        own._feed(slam, f, frame)
+        kit.feed(slam, f, frame)
         if slam.is_initialized and slam._n >= 4:
             break
     assert slam.is_initialized and slam._dev is None
-    _tracker_query(slam, own, f)
-    own._feed(slam, f + 1, frames[f + 1])
+    _tracker_query(slam, f)
+    kit.feed(slam, f + 1, frames[f + 1])
     assert slam._dev is None
     del slam
-    own._quiesce()
+    kit.quiesce()

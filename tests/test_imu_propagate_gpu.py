@@ -19,31 +19,17 @@ import torch
 import georef
 import imuref as ir
 import propref as pr
+import trackerkit as kit
+from guarded import Flat
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -53
-PAD = 64                                    # canary rows in front of and behind every buffer
-GUARD = {torch.float64: 12345.0, torch.float32: 4321.0, torch.int32: -77}
 FIELDS = dict(dt=(0, 1), q=(1, 5), v=(5, 8), p=(8, 11))
 SIZES = (1, 2, 63, 64, 65, 4095, 4096, 4097, 4099, 8193)      # around the chunk and the tile; 2 tiles + 1: the chain runs
 N_BIG = max(SIZES)
 _cache = {}
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def guarded(shape, dtype, rows=1):
-    n = int(np.prod(shape))
-    buf = torch.full((n + 2 * PAD * rows,), GUARD[dtype], dtype=dtype, device="cuda")
-    return buf, buf[PAD * rows:PAD * rows + n].view(*shape)
-
-
-def intact(buf, rows=1):
-    g = torch.cat([buf[:PAD * rows], buf[buf.numel() - PAD * rows:]]).cpu()
-    return bool((g == GUARD[buf.dtype]).all())
 
 
 def host_array(v, n):
@@ -61,28 +47,28 @@ def c_propagate(tau, gyro, accel, anchor, R_bc=None, p_bc=None, bias_a=None, max
     N = len(td)
     shapes = dict(poses=((N, 7), torch.float32, 7), times=((N,), torch.float64, 1), state=((N, 16), torch.float64, 16),
                   status=((8,), torch.int32, 1))
-    bufs = {k: guarded(s, d, r) for k, (s, d, r) in shapes.items()}
+    bufs = {k: Flat(s, d, rows=r) for k, (s, d, r) in shapes.items()}
     ext = None if R_bc is None and p_bc is None else host_array(np.concatenate([np.asarray(R_bc, np.float64).reshape(-1),
                                                                               np.asarray(p_bc, np.float64).reshape(-1)]), 12)
     nbytes = _lib.lib().ramp_imu_propagate_workspace_bytes(N)
-    wb, ws = guarded((max(nbytes, 16) // 8,), torch.float64, 2)
+    bufs["ws"] = Flat(max(nbytes, 16) // 8, torch.float64, rows=2)
+    fresh = {k: b.snapshot() for k, b in bufs.items()}
     args = dict(tau=_lib.ptr(td), gyro=_lib.ptr(gd), accel=_lib.ptr(ad), N=N, anchor=_lib.ptr(an), ext=ext, ba=host_array(bias_a, 3),
-                max_gap=float(max_gap), horizon=float(horizon), flags=_lib.RAMP_IMU_F64 if f64 else 0, poses=_lib.ptr(bufs["poses"][1]),
-                times=_lib.ptr(bufs["times"][1]) if want_times else None, state=_lib.ptr(bufs["state"][1]) if want_state else None,
-                status=_lib.ptr(bufs["status"][1]), ws=_lib.ptr(ws), nbytes=nbytes)
+                max_gap=float(max_gap), horizon=float(horizon), flags=_lib.RAMP_IMU_F64 if f64 else 0, poses=_lib.ptr(bufs["poses"].t),
+                times=_lib.ptr(bufs["times"].t) if want_times else None, state=_lib.ptr(bufs["state"].t) if want_state else None,
+                status=_lib.ptr(bufs["status"].t), ws=_lib.ptr(bufs["ws"].t), nbytes=nbytes)
     args.update(over or {})
     order = ("tau", "gyro", "accel", "N", "anchor", "ext", "ba", "max_gap", "horizon", "flags", "poses", "times", "state", "status",
              "ws", "nbytes")
     rc = _lib.lib().ramp_imu_propagate(*[args[k] for k in order], _lib.stream())
     torch.cuda.synchronize()
-    whole = lambda k: bool((bufs[k][0].cpu() == GUARD[shapes[k][1]]).all())
+    whole = lambda k: bufs[k].unchanged(fresh[k])
     if rc_only:
-        return rc, all(whole(k) for k in bufs)
+        return rc, all(whole(k) for k in shapes)
     assert rc == 0
-    out = {k: v.cpu().numpy() for k, (_, v) in bufs.items()}
-    for k, (b, _) in bufs.items():
-        assert intact(b, shapes[k][2]), k
-    assert intact(wb, 2)
+    out = {k: bufs[k].t.cpu().numpy() for k in shapes}
+    for k, b in bufs.items():
+        assert b.intact(), k
     if not want_times:
         assert whole("times")
     if not want_state:
@@ -300,14 +286,13 @@ def test_alignment_anchor_propagation_on_the_scene():
 
 
 # ------------------------------------------------------------------------------------------------ 5. tracker
-def _tracker_query(slam, own, f):
+def _tracker_query(slam, f):
     from rampvo_amd import ops
-    import test_imu_align_gpu as ta
-    tau, gyro, accel = ta._imu_for(f)
+    tau, gyro, accel = kit.imu_samples(f)
     with pytest.raises(RuntimeError, match="set_imu"):
         slam.propagate_imu(tau, gyro, accel)
     slam.set_imu(R_bc=ir.R_BC, p_bc=ir.P_BC, bias_g=[0.01, 0.0, -0.01], bias_a=[0.1, 0.0, 0.0])
-    got = own._host(slam.propagate_imu(cu(tau), cu(gyro), cu(accel), as_tensor=True, want_state=True))
+    got = kit.host(slam.propagate_imu(cu(tau), cu(gyro), cu(accel), as_tensor=True, want_state=True))
     knots, tst = slam.trajectory(as_tensor=True)
     tdev = cu(np.asarray(tst, np.float64))
     al = ops.imu_align(cu(tau), cu(gyro), cu(accel), knots, tdev, R_bc=ir.R_BC, p_bc=ir.P_BC, bias_g=[0.01, 0.0, -0.01],
@@ -315,7 +300,7 @@ def _tracker_query(slam, own, f):
     want = ops.imu_propagate(cu(tau), cu(gyro), cu(accel), ops.imu_anchor(al, knots, tdev), R_bc=ir.R_BC, p_bc=ir.P_BC,
                              bias_a=[0.1, 0.0, 0.0], want_state=True)
     want["align"] = al
-    own._same(got, own._host(want), "propagate_imu")
+    kit.same(got, kit.host(want), "propagate_imu")
     n_held = int((tau <= tst[-1]).sum())
     assert got["status"][1] == len(tau) and (got["status"][0] != 0 or got["status"][2] == n_held)
     # align= reuse: the device dict of align_imu(as_tensor=True)
@@ -335,31 +320,29 @@ def _tracker_query(slam, own, f):
 
 @torch.no_grad()
 def test_tracker_device_resident():
-    import test_queries_own_stream_gpu as own
-    slam = own._tracker(True, True)
-    for f, frame in enumerate(own._frames()[:own.T_QUERY + 2]):
-        own._feed(slam, f, frame)
-        if f == own.T_QUERY:
-            assert own._resident(slam)
-            _tracker_query(slam, own, f)
-            assert own._resident(slam)                                      # the device-resident tracker is still resident
-    assert own._resident(slam)
+    slam = kit.tracker(True, True)
+    for f, frame in enumerate(kit.frames()[:kit.T_QUERY + 2]):
+        kit.feed(slam, f, frame)
+        if f == kit.T_QUERY:
+            assert kit.resident(slam)
+            _tracker_query(slam, f)
+            assert kit.resident(slam)                                      # the device-resident tracker is still resident
+    assert kit.resident(slam)
     del slam
-    own._quiesce()
+    kit.quiesce()
 
 
 @torch.no_grad()
 def test_tracker_host_driven():
-    import test_queries_own_stream_gpu as own
-    slam = own._tracker(False, False)
-    frames = own._frames()
+    slam = kit.tracker(False, False)
+    frames = kit.frames()
     for f, frame in enumerate(frames):
-        own._feed(slam, f, frame)
+        kit.feed(slam, f, frame)
         if slam.is_initialized and slam._n >= 4:
             break
     assert slam.is_initialized and slam._dev is None
-    _tracker_query(slam, own, f)
-    own._feed(slam, f + 1, frames[f + 1])
+    _tracker_query(slam, f)
+    kit.feed(slam, f + 1, frames[f + 1])
     assert slam._dev is None
     del slam
-    own._quiesce()
+    kit.quiesce()

@@ -11,6 +11,8 @@ import types
 import numpy as np
 import pytest
 
+from trackerkit import cu
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM_NAMES = ("cuda_corr", "cuda_ba", "lietorch_backends")
 
@@ -61,11 +63,6 @@ def shims():
             sys.modules.pop(n, None)
         else:
             sys.modules[n] = m
-
-
-def cu(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 @pytest.mark.gpu

@@ -7,10 +7,7 @@ Maps are compared with the float64 regression of the call's OWN records (``compa
 Shapes: 120 x 160 and 37 x 53 (no tile and no vector width divides it); projections from ``georef.geo_scene``, regressions
 from points drawn uniformly over the reach box and seen from their own camera.
 
-The tracker tests run the small synthetic tracker of test_event_warp_gpu.py (240 x 320, 48 patches per frame, seed 77, the
-`wide` weights with d_gain = 14.5, fp16 features)."""
-import gc
-
+The tracker tests run the small synthetic tracker of tests/trackerkit.py."""
 import numpy as np
 import pytest
 import torch
@@ -18,6 +15,9 @@ import torch
 import depthref
 import georef
 import oracle as orc
+import trackerkit as kit
+from guarded import Flat
+from trackerkit import RADIUS, cu
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +26,6 @@ K4 = np.array([30.0, 20.0, 19.5, 11.25], np.float32)
 IDENT = np.array([0, 0, 0, 0, 0, 0, 1], np.float32)
 PRIOR, PW = 0.4, 0.7
 _cache = {}
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _np(r):
@@ -287,83 +283,55 @@ def test_arguments_and_canaries():
     from rampvo_amd import _lib
     L = _lib.lib()
     H, W = SHAPES[1]
-    K, G, R = 300, 64, 12.0
+    K, R = 300, 12.0
     poses, patches, conf = _points(15, K, H, W, R)
     dpo, dpa, dco, dK, dcam = cu(poses), cu(patches), cu(conf), cu(K4), cu(IDENT)
     dprior = torch.full((1,), PRIOR, device="cuda")
     nbytes = L.ramp_invdepth_map_workspace_bytes(K)
 
-    def guarded(n, dtype, fill):
-        buf = torch.full((n + 2 * G,), fill, dtype=dtype, device="cuda")
-        return buf, buf[G:G + n]
-
-    bufs = dict(inv=guarded(H * W, torch.float32, -7.0), wgt=guarded(H * W, torch.float32, -7.0),
-                rec=guarded(4 * K, torch.float32, -7.0), status=guarded(8, torch.int32, -7), ws=guarded(nbytes, torch.uint8, 0xA5))
-    assert bufs["ws"][1].data_ptr() % 16 == 0
+    bufs = dict(inv=Flat(H * W, torch.float32, -7.0), wgt=Flat(H * W, torch.float32, -7.0),
+                rec=Flat(4 * K, torch.float32, -7.0), status=Flat(8, torch.int32, -7), ws=Flat(nbytes, torch.uint8, 0xA5))
+    assert bufs["ws"].t.data_ptr() % 16 == 0
 
     def call(n=K, M=1, P=3, scale=1.0, H_=H, W_=W, R_=R, pw=PW, flags=0, outs=("inv", "wgt", "rec"), ws_bytes=nbytes,
              prior=dprior, count=None, last_rows=0, per_row=0):
-        o = lambda k: _lib.ptr(bufs[k][1]) if k in outs else None
+        o = lambda k: _lib.ptr(bufs[k].t) if k in outs else None
         rc = L.ramp_invdepth_map(_lib.ptr(dpo), _lib.ptr(dpa), _lib.ptr(dK), _lib.ptr(dcam), n, M, P, scale, None,
                                  _lib.ptr(count), 0, None, per_row, last_rows, _lib.ptr(dco), _lib.ptr(prior), pw, R_, flags, H_,
-                                 W_, o("inv"), o("wgt"), o("rec"), _lib.ptr(bufs["ws"][1]), ws_bytes,
-                                 _lib.ptr(bufs["status"][1]), _lib.stream())
+                                 W_, o("inv"), o("wgt"), o("rec"), _lib.ptr(bufs["ws"].t), ws_bytes,
+                                 _lib.ptr(bufs["status"].t), _lib.stream())
         torch.cuda.synchronize()
         return rc
 
-    before = {k: v[0].clone() for k, v in bufs.items()}
+    before = {k: v.snapshot() for k, v in bufs.items()}
     inf, nan = float("inf"), float("nan")
     for kw in (dict(H_=0), dict(W_=0), dict(R_=0.0), dict(R_=-1.0), dict(R_=nan), dict(R_=inf), dict(pw=-0.5), dict(pw=nan),
                dict(pw=inf), dict(outs=()), dict(M=0), dict(P=0), dict(n=-1), dict(scale=0.0), dict(scale=nan), dict(flags=4),
                dict(prior=None), dict(count=dprior), dict(last_rows=2, per_row=0)):
         assert call(**kw) == -1, kw
     assert call(ws_bytes=nbytes - 16) == -3
-    assert all(torch.equal(before[k], bufs[k][0]) for k in bufs)                 # nothing written, status included
+    assert all(bufs[k].unchanged(before[k]) for k in bufs)                 # nothing written, status included
     assert call() == 0
-    for k, (buf, mid) in bufs.items():
-        assert torch.equal(buf[:G], before[k][:G]) and torch.equal(buf[-G:], before[k][-G:]), k
+    for k, b in bufs.items():
+        assert b.intact(), k
     ref = _regress(poses, patches, conf, H, W, R)
-    got = dict(invdepth=bufs["inv"][1].view(H, W), weight=bufs["wgt"][1].view(H, W), records=bufs["rec"][1].view(K, 4),
-               status=bufs["status"][1])
+    got = dict(invdepth=bufs["inv"].t.view(H, W), weight=bufs["wgt"].t.view(H, W), records=bufs["rec"].t.view(K, 4),
+               status=bufs["status"].t)
     for k, v in got.items():
         assert georef.same_bits(v.cpu().numpy(), ref[k]), k
     # records alone: one launch less, [6] stays 0; a prior of weight 0 may be NULL
     assert call(outs=("rec",), prior=None, pw=0.0) == 0
-    assert georef.same_bits(bufs["rec"][1].view(K, 4).cpu().numpy(), ref["records"])
-    assert bufs["status"][1].cpu().tolist() == ref["status"].tolist()[:6] + [0, 0]
+    assert georef.same_bits(bufs["rec"].t.view(K, 4).cpu().numpy(), ref["records"])
+    assert bufs["status"].t.cpu().tolist() == ref["status"].tolist()[:6] + [0, 0]
     # zero capacity: the launches run, the prior everywhere
     assert call(n=0) == 0
-    assert (bufs["inv"][1] == PRIOR).all() and not bufs["wgt"][1].any()
-    assert bufs["status"][1].cpu().tolist() == [0, 0, 0, 0, 0, 0, H * W, 0]
-    for k, (buf, mid) in bufs.items():
-        assert torch.equal(buf[:G], before[k][:G]) and torch.equal(buf[-G:], before[k][-G:]), k
+    assert (bufs["inv"].t == PRIOR).all() and not bufs["wgt"].t.any()
+    assert bufs["status"].t.cpu().tolist() == [0, 0, 0, 0, 0, 0, H * W, 0]
+    for k, b in bufs.items():
+        assert b.intact(), k
 
 
 # ------------------------------------------------------------------------------------------------ 7. tracker
-T_STREAM, T_FRAMES, T_QUERY = 46, 44, 41           # the stream, the frames and the query frame of test_event_warp_gpu.py
-RADIUS = 24.0
-
-
-def _frames():
-    if "frames" not in _cache:
-        from rampvo_amd.synthetic import SyntheticStream
-        stream = SyntheticStream(240, 320, T_STREAM, seed=77, device="cuda")   # (the canvas depends on the stream's length)
-        _cache["frames"] = [stream.frame(t) for t in range(T_FRAMES)]
-        torch.cuda.synchronize()
-    return _cache["frames"]
-
-
-def _tracker(device_steps):
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import make_network
-    torch.manual_seed(5)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=48, MIXED_PRECISION=True), make_network("SingleScale", d_gain=14.5),
-                   {"event_bias": True}, ht=240, wd=320)
-    slam.device_steps, slam.inputs_ready = device_steps, device_steps
-    return slam
-
-
 def _from_parts(slam, n, t_now, want_records=True):
     """the two maps from the parts: the pose of poses_at, map()'s selection with the depth variance of the same query, the
     newest REMOVAL_WINDOW rows, the median of the last three frames' patches"""
@@ -384,36 +352,30 @@ def _from_parts(slam, n, t_now, want_records=True):
 @torch.no_grad()
 def _run(query):
     from rampvo_amd import ops
-    slam = _tracker(True)
+    slam = kit.tracker(True, True)
     slam.pose_stream()
     res = {}
-    for f, (im, ev, Kf, mask) in enumerate(_frames()):
-        slam(100.0 + 0.5 * f, input_tensor=(ev, im, mask), intrinsics=Kf)
-        if f == T_QUERY and query:
-            resident = lambda: bool(slam._dev is not None and slam._dev.active and slam.stats["settles"] == 0)
-            res["resident_before"] = resident()
+    for f, frame in enumerate(kit.frames()):
+        kit.feed(slam, f, frame)
+        if f == kit.T_QUERY and query:
+            res["resident_before"] = kit.resident(slam)
             var = slam.invdepth_map(radius=RADIUS, as_tensor=True)
             uni = slam.invdepth_map(radius=RADIUS, weights="uniform", prior_rel_sigma=0.5, as_tensor=True)
             res["numpy"] = slam.invdepth_map(radius=RADIUS)
-            rng = np.random.default_rng(21)
-            n_ev = 5000
-            x, y = cu(rng.uniform(0, 319, n_ev).astype(np.float32)), cu(rng.uniform(0, 239, n_ev).astype(np.float32))
-            t = cu(rng.uniform(100.0 + 0.5 * (f - 2), 100.0 + 0.5 * f, n_ev))
-            p = cu(rng.choice([-1, 1], n_ev).astype(np.int8))
+            x, y, t, p = kit.query_events(f)
             comp = slam.compensate_events(x, y, t, p, invdepth="map", radius=RADIUS, want_xy=True, as_tensor=True)
-            res["resident_after"] = resident()
+            res["resident_after"] = kit.resident(slam)
             knots, ts = slam.trajectory(as_tensor=True)
-            ref = ops.event_warp(x, y, t, p, knots, cu(np.asarray(ts, np.float64)), float(ts[-1]), Kf.cuda().float(),
+            ref = ops.event_warp(x, y, t, p, knots, cu(np.asarray(ts, np.float64)), float(ts[-1]), frame[2].cuda().float(),
                                  var["invdepth"], 240, 320, want_xy=True)
             res.update(var=_np(var), uni=_np(uni), comp=_np(comp), ref=_np(ref), n_query=slam.peek()["n"])
-            res["parts_var"], res["parts_uni"], res["med"] = _from_parts(slam, slam.peek()["n"], 100.0 + 0.5 * f)
-            res["still_resident"] = resident()
+            res["parts_var"], res["parts_uni"], res["med"] = _from_parts(slam, slam.peek()["n"], kit.tstamp(f))
+            res["still_resident"] = kit.resident(slam)
     n = slam.peek()["n"]
-    res["final_resident"] = bool(slam._dev.active and slam.stats["settles"] == 0)
+    res["final_resident"] = kit.resident(slam)
     res["poses"] = slam.poses_[:n].cpu().numpy()
     del slam
-    torch.cuda.synchronize()
-    gc.collect()
+    kit.quiesce()
     return res
 
 
@@ -448,15 +410,15 @@ def test_tracker_invdepth_map():
 def test_tracker_invdepth_map_host_driven():
     """a host-driven tracker (no device-resident step): the numpy form of invdepth_map equals ops.invdepth_map fed from the
     parts in both weight modes; frame time stamps that decrease make it raise"""
-    slam = _tracker(False)
-    for f, (im, ev, Kf, mask) in enumerate(_frames()):
-        slam(100.0 + 0.5 * f, input_tensor=(ev, im, mask), intrinsics=Kf)
+    slam = kit.tracker(False, False)
+    for f, frame in enumerate(kit.frames()):
+        kit.feed(slam, f, frame)
         if slam.is_initialized and slam._n >= 4:
             break
-    assert slam.is_initialized and slam._dev is None and f < T_FRAMES - 1
+    assert slam.is_initialized and slam._dev is None and f < kit.T_FRAMES - 1
     var = slam.invdepth_map(radius=RADIUS)
     uni = slam.invdepth_map(radius=RADIUS, weights="uniform", prior_rel_sigma=0.5)
-    parts_var, parts_uni, med = _from_parts(slam, slam._n, 100.0 + 0.5 * f, want_records=False)
+    parts_var, parts_uni, med = _from_parts(slam, slam._n, kit.tstamp(f), want_records=False)
     assert med > 0 and sorted(var) == ["invdepth", "pose_status", "status", "weight"]
     for got, parts in ((var, parts_var), (uni, parts_uni)):
         for k in ("invdepth", "weight", "status"):
@@ -472,5 +434,4 @@ def test_tracker_invdepth_map_host_driven():
     with pytest.raises(RuntimeError, match="time stamps decrease"):
         slam.invdepth_map(radius=RADIUS, weights="uniform")
     del slam
-    torch.cuda.synchronize()
-    gc.collect()
+    kit.quiesce()

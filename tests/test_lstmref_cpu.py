@@ -2,7 +2,6 @@
 recurrent kernels to: it agrees with torch's own modules in float64 and with the oracle's forwards in float32, its shape
 arithmetic is the product's, and the cases of the GPU test can tell the true statement from plausible wrong ones by more
 than 100 bounds -- so a kernel that passes the GPU test has none of those defects."""
-import contextlib
 import copy
 
 import pytest
@@ -85,19 +84,6 @@ def test_multiscale_step_is_the_modules_in_float64(nets, S, H, W):
 
 
 # ---------------------------------------------------------------------------------------------------- against the oracle
-@contextlib.contextmanager
-def _torch_towers():
-    from oracle import host_cpu
-    saved = [(c, a, c.__dict__.get(a)) for c, a, _ in host_cpu.module_patches()]
-    for c, a, f in host_cpu.module_patches():
-        setattr(c, a, f)
-    try:
-        yield
-    finally:
-        for c, a, f in saved:
-            setattr(c, a, f)
-
-
 @torch.no_grad()
 def test_f32_twin_matches_the_oracle_singlescale(nets):
     from oracle import host_cpu
@@ -107,7 +93,7 @@ def test_f32_twin_matches_the_oracle_singlescale(nets):
     state = None
     for t, (pe, pi) in enumerate([(1, 1), (0, 1), (1, 0)]):
         ev, im = torch.randn(5, H, W, generator=g) * pe, torch.randn(3, H, W, generator=g) * pi
-        with _torch_towers():
+        with lr.torch_towers():
             host_cpu.merger_forward(enc, events=ev[None, None], images=im[None, None], reinit_hidden=(t == 0))
         state = lr.singlescale_step_f32(nets["wss"], ev, im, state)
         assert float((state["ss"] - enc.super_state).abs().max()) <= 2e-5
@@ -124,7 +110,7 @@ def test_f32_twin_matches_the_oracle_multiscale(nets):
     mine = [None] * 3
     for t, use in enumerate([True, False, True]):
         ev, im = torch.randn(5, H, W, generator=g), torch.randn(3, H, W, generator=g)
-        with _torch_towers():
+        with lr.torch_towers():
             host_cpu.multiscale_forward(enc, events=ev[None, None], images=im[None, None], mask=torch.tensor([use]),
                                         reinit_hidden=(t == 0))
         for k in range(3):

@@ -23,7 +23,6 @@ What each case is the smallest instance of:
 The measured error / bound ratios on MI355X are not recorded here yet: every case prints them.  n_obs is exact, ``point``
 equals ``ramp_point_cloud``'s output bit for bit, and cov / depth_var / stats equal ``fastba.covariance``'s bit for bit.  Every
 case prints its measured errors and the ratio to its bound before it asserts."""
-import gc
 import os
 import sys
 
@@ -37,6 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import covref  # noqa: E402
 import mapref  # noqa: E402
+import trackerkit as kit  # noqa: E402
 from oracle.make_golden_params import BA_PIN  # noqa: E402
 from scenes import ba_pin_scene  # noqa: E402
 
@@ -259,26 +259,6 @@ def test_map_select_equals_numpy_exactly(n):
 T_FRAMES = 30
 
 
-def _frames():
-    if "frames" not in _cache:
-        from rampvo_amd.synthetic import SyntheticStream
-        stream = SyntheticStream(192, 256, T_FRAMES, seed=11, device="cuda")
-        _cache["frames"] = [stream.frame(t) for t in range(T_FRAMES)]
-        torch.cuda.synchronize()
-    return _cache["frames"]
-
-
-def _tracker(device_steps):
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import make_network
-    torch.manual_seed(5)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=16, MIXED_PRECISION=True), make_network("SingleScale"),
-                   {"event_bias": True}, ht=192, wd=256)
-    slam.device_steps, slam.inputs_ready = device_steps, device_steps
-    return slam
-
-
 TENSORS = ("index", "frame", "points", "point_cov", "colors", "depth_sigma_rel", "n_obs")
 SCALARS = ("n_total", "chi2", "dof", "sigma0_sq", "failed")
 
@@ -291,13 +271,13 @@ def _snap(m):
 def _tracked(device_steps, query):
     key = ("trk", device_steps, query)
     if key not in _cache:
-        slam = _tracker(device_steps)
+        slam = kit.tracker(device_steps, device_steps, **kit.COV_TRACKER)
         out = dict(dicts={}, resident={}, first_error=None)
         try:
             slam.map()
         except RuntimeError as e:
             out["first_error"] = str(e)
-        for t, (im, ev, K, mask) in enumerate(_frames()):
+        for t, (im, ev, K, mask) in enumerate(kit.frames(*kit.COV_STREAM)):
             slam(float(t), input_tensor=(ev, im, mask), intrinsics=K)
             res = slam._dev is not None and slam._dev.active
             out["resident"][t] = bool(res)
@@ -332,8 +312,7 @@ def _tracked(device_steps, query):
         traj, _ = slam.terminate()
         out["traj"], out["patches"] = traj, slam.patches_[:slam.n].cpu().numpy()
         del slam
-        torch.cuda.synchronize()
-        gc.collect()
+        kit.quiesce()
         _cache[key] = out
     return _cache[key]
 

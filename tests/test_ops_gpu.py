@@ -8,12 +8,9 @@ import torch
 
 import oracle as orc
 from scenes import BA_ORACLE_CASES, ba_oracle_case, ba_scene, corr_case
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def rel_err(a, b):

@@ -3,11 +3,9 @@
 (tests/interpref.py), every comparison by ``interpref.compare``: the bound is ``georef.bound(floor, env)`` with floor =
 georef.FLOOR["log"] x max(1, largest |translation|) and env = the fp32 restatement's own error against float64.
 
-The tracker tests run the small synthetic tracker test_pose_stream_gpu.py drives for trajectory() (240 x 320, 48 patches per
-frame, SyntheticStream(240, 320, 46, seed=77), the `wide` weights with d_gain = 14.5, fp16 features: keyframes are dropped
-while it is device resident from frame 21 on, and the initialisation leaves delta chains of depth 6), device resident."""
+The tracker tests run the small synthetic tracker of tests/trackerkit.py (keyframes are dropped while it is device resident
+from frame 21 on, and the initialisation leaves delta chains of depth 6), device resident."""
 import ctypes
-import gc
 
 import numpy as np
 import pytest
@@ -15,14 +13,12 @@ import torch
 
 import georef
 import interpref
+import trackerkit as kit
+from trackerkit import T_FRAMES, T_QUERY, cu
 
 pytestmark = pytest.mark.gpu
 
 _cache = {}
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _interp(knots, times, query, extrapolate=False, twist=True, **kw):
@@ -241,40 +237,6 @@ def test_order_independence():
 
 
 # ------------------------------------------------------------------------------------------------ 8. tracker
-T_STREAM, T_FRAMES, T_QUERY = 46, 44, 41            # frames 0 .. 41 are tracked before the queries, 42 and 43 behind them
-
-
-def _frames():
-    if "frames" not in _cache:
-        from rampvo_amd.synthetic import SyntheticStream
-        stream = SyntheticStream(240, 320, T_STREAM, seed=77, device="cuda")
-        _cache["frames"] = [stream.frame(t) for t in range(T_FRAMES)]
-        torch.cuda.synchronize()
-    return _cache["frames"]
-
-
-def _tracker(device_steps=True, ready=True):
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import make_network
-    torch.manual_seed(5)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=48, MIXED_PRECISION=True), make_network("SingleScale", d_gain=14.5),
-                   {"event_bias": True}, ht=240, wd=320)
-    slam.device_steps, slam.inputs_ready = device_steps, ready
-    return slam
-
-
-def _tstamp(t):
-    return 100.0 + 0.5 * t
-
-
-def _drop(slam):
-    del slam
-    torch.cuda.synchronize()
-    gc.collect()
-    torch.cuda.synchronize()
-
-
 def _midpoints(ts):
     return 0.5 * (ts[:-1] + ts[1:])
 
@@ -286,12 +248,12 @@ def _run(kind):
     if kind in _cache:
         return _cache[kind]
     resident = kind != "host"
-    slam = _tracker(device_steps=resident, ready=resident)
+    slam = kit.tracker(resident, resident)
     if resident:
         slam.pose_stream()
     res = {}
-    for t, (im, ev, K, mask) in enumerate(_frames()):
-        slam(_tstamp(t), input_tensor=(ev, im, mask), intrinsics=K)
+    for t, frame in enumerate(kit.frames()):
+        kit.feed(slam, t, frame)
         if t == T_QUERY and kind != "plain":
             if resident:
                 assert slam._dev is not None and slam._dev.active and slam.stats["settles"] == 0
@@ -314,7 +276,7 @@ def _run(kind):
         recs, lost = slam.poses_since(-1)
         res.update(n=n, recs=recs, lost=lost, poses=slam.poses_[:n].cpu().numpy(), patches=slam.patches_[:n].cpu().numpy())
     _cache[kind] = res
-    _drop(slam)
+    kit.drop(slam)
     return res
 
 
@@ -325,7 +287,7 @@ def test_tracker_poses_at_the_frame_times_and_between():
     assert a["resident_after"] and a["still_resident"] and a["resident_frames"] >= 10
     assert any(r.dropped for r in a["recs"][:T_QUERY + 1]), "no keyframe was dropped before the query"
     traj, ts = a["traj"], a["ts"]
-    assert traj.shape == (T_QUERY + 1, 7) and np.array_equal(ts, [_tstamp(t) for t in range(T_QUERY + 1)])
+    assert traj.shape == (T_QUERY + 1, 7) and np.array_equal(ts, [kit.tstamp(t) for t in range(T_QUERY + 1)])
     floor = interpref.floor_of(traj)
     assert georef.pose_err(a["at_knots"], traj) <= floor
     mid = _midpoints(ts)

@@ -3,12 +3,14 @@ trk_publish_kernel, Ramp_vo.pose_stream / latest_pose / poses_since) and the tra
 (traj_resolve_kernel, Ramp_vo.trajectory) -- bit for bit against the host-driven tracker and terminate().
 
 Trackers run at 240 x 320 with 48 patches per frame (the size test_pipeline_gpu.py's device-resident test uses) on
-SyntheticStream(240, 320, 44, seed=77) with the synthetic `wide` weights, fp16 features."""
-import gc
-
+SyntheticStream(240, 320, 44, seed=77) with the synthetic `wide` weights, fp16 features (tests/trackerkit.py's tracker with
+the default d_gain; the trajectory test runs the kit's own stream and d_gain = 14.5)."""
 import numpy as np
 import pytest
 import torch
+
+import trackerkit as kit
+from trackerkit import drop as _drop, tstamp as _tstamp
 
 pytestmark = pytest.mark.gpu
 
@@ -17,34 +19,11 @@ _cache = {}
 
 
 def _frames():
-    if "frames" not in _cache:
-        from rampvo_amd.synthetic import SyntheticStream
-        stream = SyntheticStream(240, 320, T_FRAMES, seed=77, device="cuda")
-        _cache["frames"] = [stream.frame(t) for t in range(T_FRAMES)]
-        torch.cuda.synchronize()
-    return _cache["frames"]
+    return kit.frames(240, 320, T_FRAMES, 77, T_FRAMES)
 
 
 def _tracker(device_steps=True, ready=True):
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import make_network
-    torch.manual_seed(5)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=48, MIXED_PRECISION=True), make_network("SingleScale"),
-                   {"event_bias": True}, ht=240, wd=320)
-    slam.device_steps, slam.inputs_ready = device_steps, ready
-    return slam
-
-
-def _tstamp(t):
-    return 100.0 + 0.5 * t              # (the caller's time stamps: not the frame counter)
-
-
-def _drop(slam):
-    del slam
-    torch.cuda.synchronize()
-    gc.collect()
-    torch.cuda.synchronize()
+    return kit.tracker(device_steps, ready, d_gain=None)
 
 
 def _final_state(slam):
@@ -142,17 +121,6 @@ def _chain_depths(log):
     return {t: depth(t) for t in log}
 
 
-def _slow_start_tracker():
-    from rampvo_amd.config import make_cfg
-    from rampvo_amd.Ramp_vo import Ramp_vo
-    from rampvo_amd.synthetic import make_network
-    torch.manual_seed(5)
-    slam = Ramp_vo(make_cfg("default", PATCHES_PER_FRAME=48, MIXED_PRECISION=True), make_network("SingleScale", d_gain=14.5),
-                   {"event_bias": True}, ht=240, wd=320)
-    slam.device_steps, slam.inputs_ready = True, True
-    return slam
-
-
 @torch.no_grad()
 def test_trajectory_equals_terminate_without_a_hand_back():
     """Ramp_vo.trajectory() mid-run, device resident (frame 37: no settle, the next frame still resident) and at the end,
@@ -170,12 +138,9 @@ def test_trajectory_equals_terminate_without_a_hand_back():
     6) and 8, 9, 10 (depth 3), initialises at frame 16, has its window full at frame 19 and drops 15 keyframes behind that
     (21 -> 20, 23 -> 22, 24 -> 22, ... 41 -> 38), 25 entries in all over the 46 frames."""
     from rampvo_amd import track_dev
-    from rampvo_amd.synthetic import SyntheticStream
     MID, SETTLE = 37, 40
-    stream = SyntheticStream(240, 320, 46, seed=77, device="cuda")
-    frames = [stream.frame(t) for t in range(46)]
-    torch.cuda.synchronize()
-    slam = _slow_start_tracker()
+    frames = kit.frames(240, 320, 46, 77, 46)
+    slam = kit.tracker()
     mid = None
     for t, (im, ev, K, mask) in enumerate(frames):
         slam(_tstamp(t), input_tensor=(ev, im, mask), intrinsics=K)
@@ -210,7 +175,7 @@ def test_trajectory_equals_terminate_without_a_hand_back():
     assert np.array_equal(host_poses, traj)
     _drop(slam)
     # what terminate() returns at frame MID: a second tracker on the same frames, stopped there
-    ref = _slow_start_tracker()
+    ref = kit.tracker()
     for t, (im, ev, K, mask) in enumerate(frames[:MID + 1]):
         ref(_tstamp(t), input_tensor=(ev, im, mask), intrinsics=K)
     traj_m, ts_m = ref.terminate()
@@ -227,7 +192,8 @@ def test_trajectory_equals_terminate_without_a_hand_back():
 def _resolve(kf_poses, kf_ts, extra, dlog, T):
     import ctypes
     from rampvo_amd import _lib, track_dev
-    cu = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    cu = kit.cu
+
     def pack(entries):
         a = np.zeros((max(len(entries), 1), track_dev.LOG_WORDS), np.float32)
         for r, (t1, t0, dP) in enumerate(entries):

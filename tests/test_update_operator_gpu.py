@@ -202,14 +202,14 @@ def test_update_forward_without_rows_and_with_missing_pointers_launches_nothing(
     c = _case(65, x3)
     canary = 1234.0                      # (exact in fp16)
 
-    def intact(b):
+    def untouched(b):
         torch.cuda.synchronize()
         return all(bool((t == canary).all()) for t in b.values())
 
     for heads in (False, True):
         b = _buffers(c, x3, heads, fill=canary)
         assert lib().ramp_update_forward(ctypes.byref(_args(fu, c, x3, heads, b, E=0)), stream()) == 0
-        assert intact(b)
+        assert untouched(b)
         needed = ["w", "corr", "inp", "net_out", "kk_order", "kk_gid", "kk_seg", "kk_ngroups", "ij_order", "ij_gid", "ij_seg",
                   "ij_ngroups", "ix", "jx", "hkk", "hij"]
         needed += ["fg", "ykk", "yij"] if x3 else ["sagg_frag"]
@@ -229,4 +229,4 @@ def test_update_forward_without_rows_and_with_missing_pointers_launches_nothing(
                 setattr(a, name, None)
             assert lib().ramp_update_forward(ctypes.byref(a), stream()) == RAMP_EINVAL, name
         assert lib().ramp_update_forward(None, stream()) == RAMP_EINVAL
-        assert intact(b)
+        assert untouched(b)

@@ -11,15 +11,12 @@ import torch
 
 import imuref as ir
 import propref as pr
+from trackerkit import cu
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 4096
 CANARY = 0xA5
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 class Arena:
