@@ -1157,6 +1157,59 @@ int ramp_event_warp(const float *x, const float *y, const double *t, const int8_
                     int bins, int H, int W, float *xy_out, float *iwe, float *stack_f32, int8_t *stack_i8, void *ws,
                     size_t ws_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------- event multi-view stereo (csrc/emvs.hip)
+ *
+ * ramp_event_dsi: depth from a plane sweep of the events (the space-sweep "disparity space image" of EMVS, Rebecq et al., IJCV
+ * 2018).  Every event is back-projected from the camera pose at its own time stamp and swept through D planes of constant
+ * inverse depth of the camera at t_ref; each plane takes the bilinear splat of ramp_event_warp.  Votes pile up where the
+ * scene's edges are: per pixel, the plane with the most votes, refined by a parabola, is a semi-dense inverse depth.
+ *   events: x, y [N] fp32, t [N] float64 (the polarity takes no part); knots, times, t_ref, intrinsics and
+ *   RAMP_INTERP_EXTRAPOLATE (the only flag) as ramp_event_warp.  range: device float [2] = (d_lo, d_hi), inverse depths in the
+ *   unit of the knots' translations; the host never reads it.  The planes are uniform in inverse depth:
+ *     step = (double(d_hi) - double(d_lo)) / (D - 1)   (0 for D == 1),     d_k = float32(double(d_lo) + k * step)
+ * Vote.  The statements of ramp_event_warp up to R = R_G ((x - cx) / fx, (y - cy) / fy, 1) and t_G (the same segment table,
+ *   alpha, C(t), G), once per event; then per plane X'_k = R + t_G * d_k and the projection of ramp_event_warp.  A plane whose
+ *   Z' <= RAMP_WARP_MIN_Z (or NaN) or whose projection is not finite gets NO VOTE from this event; every other plane gets the
+ *   splat of ramp_event_warp at (x'_k, y'_k): the neighbours floor and floor + 1, c = llrint(ldexp(wx_i * wy_j, 24)), neighbours
+ *   outside the image dropped (a vote may so add nothing), added with 64-bit INTEGER atomics into
+ *     dsi int64 [D][H][W]       caller-owned, 8-byte aligned, zeroed by the call
+ *   The sums do not depend on the events' order and a call repeats its bits.
+ *     coords fp32 [N][D][2]     optional (NULL), 8-byte aligned: (x'_k, y'_k), NaN where the plane got no vote.  For tests and
+ *                               small calls: it is N * D * 8 bytes.
+ * Detect, per pixel, in integers:  best = max_k dsi[k],  plane = the LOWEST k that attains it.  The pixel is detected when
+ *     best >= min_fixed   and, with adaptive_radius r > 0,   best >= (box // n_in) + offset_fixed
+ *   box: the int64 sum of `best` over the (2r + 1)^2 window clipped to the image, n_in: the pixels of that window inside the
+ *   image, //: floor division; min_fixed = llrint(min_votes * 2^24), offset_fixed = llrint(adaptive_offset * 2^24) (it may be
+ *   negative).  Refinement, in float64 without FMA: with (a, b, c) = dsi[plane - 1, plane, plane + 1],
+ *     delta = (a - c) / (2 den)  for 0 < plane < D - 1 and den = a - 2 b + c != 0 (integers),  else 0
+ *     invdepth = float32(double(d_lo) + (plane + delta) * step)
+ * Outputs, each optional (NULL): invdepth [H][W] fp32; confidence [H][W] fp32 = float(best) * 2^-24, detected or not; plane
+ *   [H][W] int32, -1 where not detected.  A pixel that is not detected gets *fill (a device float) in invdepth, NaN when fill is
+ *   NULL.
+ * status: device int32 [8], written by the call: [0] bits (bit 0 RAMP_INTERP_BAD_TIMES; RAMP_DSI_BAD_RANGE: a word of range is
+ *   not finite, d_lo < 0, or d_hi <= d_lo with D > 1), [1] / [2] events below / above the knots' range ([3] not among them), [3]
+ *   events with a coordinate or time stamp that is not finite, [4] finite events that voted in no plane, [5] events that voted in
+ *   at least one plane, [6] detected pixels, [7] 0.  [3] + [4] + [5] = N.
+ * Failures, never a plausible number: either bit makes invdepth, confidence and coords NaN, plane -1, dsi zero and [5], [6]
+ *   zero (the finite events are then counted in [4]).  Outcomes of the data: RAMP_OK.
+ * ws: ramp_event_dsi_ws_bytes(T, H, W) bytes, 16-byte aligned (segment table, C(t_ref)^-1, counters, per pixel the best
+ *   votes, plane and refined inverse depth).  Launches: one hipMemsetAsync (the DSI) and four kernels (segment table and
+ *   C(t_ref)^-1, vote, detect, threshold and status), all on `stream`, nothing read back, nothing synchronised, no
+ *   floating-point atomics.  N == 0 runs them all: the DSI is zero, nothing is detected, invdepth is the fill everywhere.
+ * RAMP_EINVAL: NULL events with N > 0, N < 0, T < 1, H, W or D < 1, adaptive_radius outside [0, 15], unknown flags, a t_ref,
+ *   min_votes or adaptive_offset that is not finite, a NULL knots / times / intrinsics / range / dsi / ws / status, a dsi or
+ *   coords that is not 8-byte aligned.  RAMP_EUNSUPPORTED: D * H * W >= 2^31, or N * D >= 2^38 (below it every box sum stays
+ *   below 2^62).  RAMP_EWORKSPACE: a workspace too small.  A refused call touches nothing.
+ * ramp_event_dsi_grid_events(): the number of events one trip of the full event grid covers.                            */
+#define RAMP_DSI_BAD_RANGE 2 /* status[0] bit 1 */
+size_t ramp_event_dsi_ws_bytes(int T, int H, int W);
+long ramp_event_dsi_grid_events(void);
+int ramp_event_dsi(const float *x, const float *y, const double *t, int N, const float *knots, const double *times, int T,
+                   double t_ref, const float *intrinsics, const float *range, int flags, int D, int H, int W, double min_votes,
+                   int adaptive_radius, double adaptive_offset, const float *fill, int64_t *dsi, float *coords,
+                   float *invdepth, float *confidence, int32_t *plane, void *ws, size_t ws_bytes, int32_t *status,
+                   void *stream);
+
 /* ---------------------------------------------------------------- inverse-depth map (csrc/depthmap.hip)
  *
  * ramp_invdepth_map: the selected patches of the window are projected into one camera pose and regressed to a dense map of

@@ -29,21 +29,9 @@ __global__ void __launch_bounds__(INTERP_THREADS)
     if (s < S && interp_segment_row(knots, times, T, s, seg + (size_t)s * INTERP_SEG_WORDS)) atomicOr(ctr, RAMP_INTERP_BAD_TIMES);
     return;
   }
-  // the last workgroup: one lane forms C(t_ref) from its own copy of that segment's row (the same function, the same bits)
+  // the last workgroup: one lane forms C(t_ref)^-1 (warp_reference_row)
   if (threadIdx.x) return;
-  const int s = min(max(interp_upper_bound(times, T, t_ref) - 1, 0), T > 1 ? T - 2 : 0);
-  float xi[6], tw[6], X[7], C[7], r[3];
-  double dt;
-  interp_segment_values(knots, times, T, s, xi, tw, &dt);
-#pragma unroll
-  for (int c = 0; c < 7; c++) X[c] = knots[7 * (size_t)s + c];
-  interp_pose(X, xi, interp_alpha(t_ref, times[s], dt, extrapolate), C);
-  const float qi[4] = {-C[3], -C[4], -C[5], C[6]};
-  lt_qrot(qi, C, r);
-  ref[0] = -r[0]; ref[1] = -r[1]; ref[2] = -r[2];
-  ref[3] = qi[0]; ref[4] = qi[1]; ref[5] = qi[2]; ref[6] = qi[3];
-#pragma unroll
-  for (int c = 7; c < WARP_REF_WORDS; c++) ref[c] = 0.0f;
+  warp_reference_row(knots, times, T, t_ref, extrapolate, ref);
 }
 
 struct WarpArgs {

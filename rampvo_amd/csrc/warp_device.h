@@ -52,6 +52,25 @@ static __device__ __forceinline__ void warp_relative(const float *ref, const flo
   tG[2] = ref[2] + r[2];
 }
 
+// ref (WARP_REF_WORDS floats) = C(t_ref)^-1 as (-(qr^-1 . tr), qr^-1), zero padded: one lane forms C(t_ref) from its own copy of
+// that segment's row (the same function as the table's, the same bits)
+static __device__ __forceinline__ void warp_reference_row(const float *__restrict__ knots, const double *__restrict__ times, int T,
+                                                          double t_ref, int extrapolate, float *__restrict__ ref) {
+  const int s = min(max(interp_upper_bound(times, T, t_ref) - 1, 0), T > 1 ? T - 2 : 0);
+  float xi[6], tw[6], X[7], C[7], r[3];
+  double dt;
+  interp_segment_values(knots, times, T, s, xi, tw, &dt);
+#pragma unroll
+  for (int c = 0; c < 7; c++) X[c] = knots[7 * (size_t)s + c];
+  interp_pose(X, xi, interp_alpha(t_ref, times[s], dt, extrapolate), C);
+  const float qi[4] = {-C[3], -C[4], -C[5], C[6]};
+  lt_qrot(qi, C, r);
+  ref[0] = -r[0]; ref[1] = -r[1]; ref[2] = -r[2];
+  ref[3] = qi[0]; ref[4] = qi[1]; ref[5] = qi[2]; ref[6] = qi[3];
+#pragma unroll
+  for (int c = 7; c < WARP_REF_WORDS; c++) ref[c] = 0.0f;
+}
+
 // one axis of the splat: the two neighbours floor(v) and floor(v) + 1, their weights 1 - w and w with w = v - floor(v), and
 // whether each lies in [0, n).  The range test is made in float, so a huge coordinate never reaches an integer conversion.
 static __device__ __forceinline__ void warp_axis(float v, int n, int *i0, float *w0, float *w1, bool *in0, bool *in1) {

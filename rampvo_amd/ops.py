@@ -19,6 +19,8 @@ from ._lib import KPLANE, RAMP_NHWC32, RAMP_NCHW, RAMP_NHWC, CorrLevel, check, d
 _STATUS = {
     "event_warp": ({"bad_times": _lib.RAMP_INTERP_BAD_TIMES},
                    ("n_below", "n_above", "n_not_finite", "n_rejected", "n_outside", "n_contributed")),
+    "event_dsi": ({"bad_times": _lib.RAMP_INTERP_BAD_TIMES, "bad_range": _lib.RAMP_DSI_BAD_RANGE},
+                  ("n_below", "n_above", "n_not_finite", "n_no_vote", "n_voted", "n_detected")),
     "event_voxel": ({"bad_offsets": _lib.RAMP_VOXEL_BAD_OFFSETS, "bad_times": _lib.RAMP_VOXEL_BAD_TIMES},
                     ("n_events", "n_not_finite", "n_outside", "n_no_bin", "n_contributed")),
     "event_rectify": ({"bad_camera": _lib.RAMP_RECTIFY_BAD_CAMERA},
@@ -262,6 +264,78 @@ def event_warp(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, wi
 def event_warp_status(status):
     """The status words of ``event_warp`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
     return _status("event_warp", status)
+
+
+def event_dsi(x, y, t, knots, times, t_ref, intrinsics, height, width, planes=64, range=(0.05, 2.0), min_votes=4.0,
+              adaptive_radius=0, adaptive_offset=0.0, fill=None, extrapolate=False, want_coords=False):
+    """Depth from a plane sweep of an event list (include/ramp_hip.h ``ramp_event_dsi``; EMVS, Rebecq et al. 2018): every
+    event is back-projected from the camera pose at its own time stamp and swept through ``planes`` planes of constant inverse
+    depth of the camera at ``t_ref``, each plane taking ``event_warp``'s bilinear splat; per pixel the plane with the most
+    votes (the lowest on a tie), refined by a parabola, is the inverse depth -- at the pixels where events fire.
+
+    ``x, y, t, knots, times, t_ref, intrinsics`` as ``event_warp`` (no polarity).  ``range``: ``(d_lo, d_hi)`` inverse depths,
+    a pair of numbers or a device tensor [2] the host never reads; the planes are uniform in inverse depth.  A pixel is
+    detected when its best plane holds ``min_votes`` votes and, with ``adaptive_radius`` r in 1 .. 15, at least the mean of
+    the best votes over its (2r + 1)^2 window (clipped to the image) plus ``adaptive_offset``.  ``fill``: what an undetected
+    pixel's ``invdepth`` gets -- None (NaN), a number or a one-element device tensor.  The defaults of ``planes``, ``range`` and
+    ``min_votes`` are defaults nobody has tuned.  Device tensors, ordered on the current stream, nothing synchronised.
+
+    Returns a dict of device tensors: ``dsi`` int64 [planes, height, width] (votes in fixed point, 2^24 per event and plane),
+    ``invdepth`` and ``confidence`` (= best votes) [height, width] float32, ``plane`` int32 (-1: not detected), ``status``
+    int32 [8] (``event_dsi_status``) and, with ``want_coords``, ``coords`` [N, planes, 2] (NaN where a plane got no vote;
+    N x planes x 8 bytes: for tests and small calls).  ``invdepth`` goes straight into ``event_warp(invdepth=...)``.  The
+    votes are integers: the same bits for any order of the events.  Time stamps of the knots that decrease, or a range that is
+    not finite, negative or empty: NaN / -1 / zero outputs, never a plausible number."""
+    dev, N = x.device, x.numel()
+    T, D, H, W = knots.numel() // 7, int(planes), int(height), int(width)
+    if times.numel() != T:
+        raise RuntimeError("event_dsi: %d knots but %d time stamps" % (T, times.numel()))
+    if not (y.numel() == N and t.numel() == N):
+        raise RuntimeError("event_dsi: x, y and t differ in length")
+    if T < 1 or D < 1 or H < 1 or W < 1:
+        raise RuntimeError("event_dsi: at least one knot, one plane and one pixel")
+    if not 0 <= int(adaptive_radius) <= 15:
+        raise RuntimeError("event_dsi: adaptive_radius is 0 .. 15")
+    if D * H * W >= 1 << 31 or N * D >= 1 << 38:
+        raise RuntimeError("event_dsi: planes x height x width is below 2^31 and events x planes below 2^38")
+    require_cuda(x, y, t, knots, times)
+    xf, yf = x.reshape(-1).to(torch.float32).contiguous(), y.reshape(-1).to(torch.float32).contiguous()
+    tf = t.reshape(-1).to(torch.float64).contiguous()
+    knots = knots.reshape(-1, 7).contiguous().float()
+    times = times.reshape(-1).contiguous().double()
+
+    def word(name, v, n):
+        if isinstance(v, torch.Tensor):
+            require_cuda(v)
+            v = v.reshape(-1).to(torch.float32).contiguous()
+        else:
+            v = torch.tensor([float(u) for u in (v if n > 1 else [v])], dtype=torch.float32, device=dev)
+        if v.numel() != n:
+            raise RuntimeError("event_dsi: %s holds %d number%s" % (name, n, "s" if n > 1 else ""))
+        return v
+
+    rng = word("range", range, 2)
+    fl = None if fill is None else word("fill", fill, 1)
+    K = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(4).contiguous()
+    res = {"status": torch.empty(8, dtype=torch.int32, device=dev),
+           "dsi": torch.empty((D, H, W), dtype=torch.int64, device=dev),
+           "invdepth": torch.empty((H, W), dtype=torch.float32, device=dev),
+           "confidence": torch.empty((H, W), dtype=torch.float32, device=dev),
+           "plane": torch.empty((H, W), dtype=torch.int32, device=dev)}
+    if want_coords:
+        res["coords"] = torch.empty((N, D, 2), dtype=torch.float32, device=dev)
+    ws, nbytes = sized_workspace("ramp_event_dsi_ws_bytes", (T, H, W), dev, "evdsi")
+    check(lib().ramp_event_dsi(ptr(xf), ptr(yf), ptr(tf), N, ptr(knots), ptr(times), T, float(t_ref), ptr(K), ptr(rng),
+                               _lib.RAMP_INTERP_EXTRAPOLATE if extrapolate else 0, D, H, W, float(min_votes),
+                               int(adaptive_radius), float(adaptive_offset), ptr(fl), ptr(res["dsi"]), ptr(res.get("coords")),
+                               ptr(res["invdepth"]), ptr(res["confidence"]), ptr(res["plane"]), ptr(ws), nbytes,
+                               ptr(res["status"]), stream()), "ramp_event_dsi")
+    return res
+
+
+def event_dsi_status(status):
+    """The status words of ``event_dsi`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("event_dsi", status)
 
 
 def event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=None, signed=True,

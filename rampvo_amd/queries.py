@@ -54,7 +54,8 @@ class StateStream:
                 self.leaves(*(x.values() if isinstance(x, dict) else x))
 
 
-def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None, filter=None, imu=None, propagate=None):
+def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None, filter=None, imu=None, propagate=None,
+                  dsi=None):
     """The closing check of a query's numpy form -- its one wait.  Each argument is a device status tensor or None (not part
     of this query): ``traj`` trajectory()'s word, ``interp`` the words of ops.se3_interp or ops.event_warp (bit 0 of word 0:
     the frames' time stamps), ``cam`` those of ops.invdepth_map (bit 0 of word 0: the camera pose), ``voxel`` those of
@@ -62,12 +63,13 @@ def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=No
     ops.event_rectify / ops.image_rectify (bit 0 of word 0: the camera record), ``filter`` those of ops.event_filter (bit 0 of
     word 0: the events' order), ``imu`` those of ops.imu_align (bit 0: the order of the samples or of the frames' time stamps;
     bits 1 and 2: the gyro stage, the scale stage), ``propagate`` those of ops.imu_propagate (bit 0: the samples' order; bits
-    6 and 7: the anchor, no sample at or before it).  Word 0 of each goes to the host in one copy; raises in this order: event
+    6 and 7: the anchor, no sample at or before it), ``dsi`` those of ops.event_dsi (bit 0: the frames' time stamps, bit 1: the
+    range of inverse depths).  Word 0 of each goes to the host in one copy; raises in this order: event
     order, camera record, unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times, IMU order, gyro
-    stage, scale stage, the propagation's order, anchor and start."""
+    stage, scale stage, the propagation's order, anchor and start, the sweep's time stamps and range."""
     given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam), ("voxel", voxel),
                                                  ("rectify", rectify), ("filter", filter), ("imu", imu),
-                                                 ("propagate", propagate)) if s is not None]
+                                                 ("propagate", propagate), ("dsi", dsi)) if s is not None]
     if not given:
         return
     first = given[0][1] if len(given) == 1 else torch.cat([s for _, s in given])
@@ -106,6 +108,10 @@ def _raise_on_words(name, word):
         raise RuntimeError(name + ": the anchor is not finite or its scale is not positive (a failed alignment leaves NaN)")
     if prop & _lib.RAMP_IMU_NO_START:
         raise RuntimeError(name + ": no IMU sample lies at or before the anchor's time stamp")
+    if word.get("dsi", 0) & _lib.RAMP_INTERP_BAD_TIMES:
+        raise RuntimeError(name + ": the frames' time stamps decrease or are not finite")
+    if word.get("dsi", 0) & _lib.RAMP_DSI_BAD_RANGE:
+        raise RuntimeError(name + ": the range of inverse depths is not finite, negative or empty (no depth median yet?)")
 
 
 def _dof_sigma0(s):
@@ -454,9 +460,9 @@ class TrackerQueries:
 
     def _event_inputs(self, name, x, y, t, p, denoise, distorted):
         """The prologue of an event query -> (x, y, t, p, extra): the events as the kernels take them (fp32, fp32, float64, int8
-        on the device) and ``extra``, the ``rectify_status`` / ``filter_status`` the result gains.  ``denoise`` filters first, in
+        on the device; ``p=None``: a query without polarity) and ``extra``, the ``rectify_status`` / ``filter_status`` the result gains.  ``denoise`` filters first, in
         the coordinates given (integer raw pixels stay int32), then ``distorted`` rectifies."""
-        td, pd = self._as_device(t, torch.float64), self._as_device(p, torch.int8)
+        td, pd = self._as_device(t, torch.float64), None if p is None else self._as_device(p, torch.int8)
         rect = filt = None
         if denoise:
             x, y, filt = self._denoised(name, x, y, td)
@@ -488,7 +494,9 @@ class TrackerQueries:
         frames' patches -- the value the next frame's patches start from -- computed into a device word the host never
         reads; otherwise a float, a one-element device tensor or a [height, width] map; ``"map"``: the map
         ``invdepth_map(t_ref, radius, weights)`` renders from the window's patches at the reference pose, so that every event is
-        warped with the depth the tracker has estimated near its pixel (``radius``, ``weights`` are read in this mode only).
+        warped with the depth the tracker has estimated near its pixel (``radius``, ``weights`` are read in this mode only);
+        ``"events"``: the map ``event_depth(x, y, t, t_ref, fill="median")`` sweeps from these very events (at the tracker's
+        image size), so that the events are warped with the depth they vote for themselves and with the median elsewhere.
         Intrinsics: row 0 of the tracker's own times the patch stride, i.e. those of the images it was fed.  ``height, width``
         default to the tracker's.  ``distorted=True``: ``x, y`` are RAW sensor pixels; they are rectified first
         (``rectify_events``, the camera of ``set_camera``; raises without one), the events without a solution are skipped and
@@ -503,23 +511,28 @@ class TrackerQueries:
         frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit."""
         name = "compensate_events()"
         xd, yd, td, pd, extra = self._event_inputs(name, x, y, t, p, denoise, distorted)
-        knots, tdev, K, invdepth, t_ref, H, W = self._event_query(name, t_ref, invdepth, radius, weights, height, width)
+        knots, tdev, K, invdepth, t_ref, H, W = self._event_query(name, t_ref, invdepth, radius, weights, height, width,
+                                                                  events=(xd, yd, td))
         with torch.no_grad():
             out = ops.event_warp(xd, yd, td, pd, knots, tdev, t_ref, K, invdepth, H, W, num_bins=num_bins,
                                  extrapolate=extrapolate, want_xy=want_xy, want_iwe=want_iwe, stack=stack)
         return self._answer(name, out, extra, as_tensor, traj=self._traj_status, interp=out["status"])
 
-    def _event_query(self, name, t_ref, invdepth, radius, weights, height, width):
+    def _event_query(self, name, t_ref, invdepth, radius, weights, height, width, events=None):
         """what the event queries share: the trajectory as it is now, the cached time stamps, the image intrinsics and the
-        inverse depth (None: the median word; ``"map"``: ``invdepth_map`` at the reference pose), read on the stream the
-        state lives on -> (knots, times, K, invdepth, t_ref, height, width)"""
+        inverse depth (None: the median word; ``"map"``: ``invdepth_map`` at the reference pose; ``"events"``: ``event_depth``
+        of the query's own ``events`` = (x, y, t) at the reference time, the median where nothing is detected), read on the
+        stream the state lives on -> (knots, times, K, invdepth, t_ref, height, width)"""
         if not self.tlist:
             raise RuntimeError(name + ": no frame has been tracked yet")
         if isinstance(invdepth, str):
-            if invdepth != "map":
-                raise RuntimeError(name + ": invdepth is None, a number, a tensor or 'map'")
-            invdepth = self.invdepth_map(t_ref=t_ref, radius=radius, weights=weights, height=height, width=width,
-                                         as_tensor=True)["invdepth"]
+            if invdepth == "map":
+                invdepth = self.invdepth_map(t_ref=t_ref, radius=radius, weights=weights, height=height, width=width,
+                                             as_tensor=True)["invdepth"]
+            elif invdepth == "events" and events is not None:
+                invdepth = self.event_depth(*events, t_ref=t_ref, fill="median", as_tensor=True)["invdepth"]
+            else:
+                raise RuntimeError(name + ": invdepth is None, a number, a tensor, 'map' or 'events'")
         knots, _ = self.trajectory(as_tensor=True)
         tdev = self._frame_times_dev()
         with self._state_stream() as sc:                      # reads of the state, on the stream it lives on
@@ -535,7 +548,7 @@ class TrackerQueries:
                        weights="variance", distorted=False, denoise=False):
         """How sharp the compensated events are with the trajectory as it is now: the variance of the image of warped events
         ``compensate_events`` would return (the same events, poses, intrinsics and inverse depth -- ``invdepth`` as there,
-        ``"map"`` included) and its gradient with respect to a small correction ``(v[3], w[3], lam)`` of velocity, rotation
+        ``"map"`` and ``"events"`` included) and its gradient with respect to a small correction ``(v[3], w[3], lam)`` of velocity, rotation
         rate and log depth scale in the reference camera frame (``ops.event_contrast``).  The only figure of quality an
         event tracker can give about its own trajectory without ground truth.  ``distorted=True``: raw sensor pixels, as in
         ``compensate_events``; the result gains ``rectify_status``.  ``denoise=True``: filtered first, as there; the result
@@ -548,7 +561,8 @@ class TrackerQueries:
         unresolved bit."""
         name = "event_contrast()"
         xd, yd, td, pd, extra = self._event_inputs(name, x, y, t, p, denoise, distorted)
-        knots, tdev, K, invdepth, t_ref, H, W = self._event_query(name, t_ref, invdepth, radius, weights, height, width)
+        knots, tdev, K, invdepth, t_ref, H, W = self._event_query(name, t_ref, invdepth, radius, weights, height, width,
+                                                                  events=(xd, yd, td))
         with torch.no_grad():
             out = ops.event_contrast(xd, yd, td, pd, knots, tdev, t_ref, K, invdepth, H, W, correction=correction,
                                      signed=signed, extrapolate=extrapolate, want_grad=want_grad, want_iwe=want_iwe)
@@ -580,7 +594,8 @@ class TrackerQueries:
         resident = resident or as_tensor
         name = "align_events()"
         xd, yd, td, pd, extra = self._event_inputs(name, x, y, t, p, denoise, distorted)
-        knots, tdev, K, invdepth, t_ref, H, W = self._event_query(name, t_ref, invdepth, radius, weights, height, width)
+        knots, tdev, K, invdepth, t_ref, H, W = self._event_query(name, t_ref, invdepth, radius, weights, height, width,
+                                                                  events=(xd, yd, td))
         with torch.no_grad():
             out = ops.event_align(xd, yd, td, pd, knots, tdev, t_ref, K, invdepth, H, W, correction=correction, free=free,
                                   step=step, iters=iters, signed=signed, extrapolate=extrapolate, resident=resident,
@@ -653,6 +668,39 @@ class TrackerQueries:
             extra = {"warp_status": warp["status"], **extra}
         return self._answer(name, out, extra, as_tensor, traj=self._traj_status if compensate else None,
                             interp=warp.get("status"), voxel=out["status"])
+
+    def event_depth(self, x, y, t, t_ref=None, planes=64, range=None, rel_range=4.0, min_votes=4.0, adaptive_radius=0,
+                    adaptive_offset=0.0, fill=None, distorted=False, denoise=False, as_tensor=False):
+        """Semi-dense inverse depth from the events themselves (``ops.event_dsi``: a plane sweep of the events' rays through
+        ``planes`` planes of inverse depth of the camera at ``t_ref``, with the trajectory as it is now -- event multi-view
+        stereo), at the tracker's image size and intrinsics: depth at the pixels where events fire, depth edges included,
+        which ``invdepth_map``'s regression of the patches cannot know.  Events, ``t_ref``, ``distorted`` and ``denoise`` as
+        ``compensate_events`` (no polarity).
+
+        ``range=None``: ``(median / rel_range, median * rel_range)`` around the median inverse depth ``compensate_events``
+        uses by default, formed on the device; else ``(d_lo, d_hi)`` as numbers or a device tensor [2].  ``min_votes``,
+        ``adaptive_radius``, ``adaptive_offset``: the detection of ``ops.event_dsi``.  ``fill``: what an undetected pixel
+        gets -- None (NaN), a number, a one-element device tensor, or ``"median"`` (that median word).  ``planes``,
+        ``rel_range`` and ``min_votes`` are defaults nobody has tuned.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call).  ``as_tensor=True``:
+        the dict of device tensors of ``ops.event_dsi`` (``dsi``, ``invdepth``, ``confidence``, ``plane``, ``status``) and
+        ``range``, ordered on the current stream, nothing synchronised.  Otherwise numpy arrays, which reads once and raises
+        when the frames' time stamps decrease or are not finite, when the range is not finite, negative or empty (a median
+        of 0: no frame's patches yet), or on trajectory()'s unresolved bit."""
+        name = "event_depth()"
+        if not rel_range > 1:
+            raise RuntimeError(name + ": rel_range is above 1")
+        xd, yd, td, _, extra = self._event_inputs(name, x, y, t, None, denoise, distorted)
+        knots, tdev, K, median, t_ref, H, W = self._event_query(name, t_ref, None, None, None, None, None)
+        with torch.no_grad():
+            if range is None:
+                range = torch.cat([median / float(rel_range), median * float(rel_range)])
+            out = ops.event_dsi(xd, yd, td, knots, tdev, t_ref, K, H, W, planes=planes, range=range, min_votes=min_votes,
+                                adaptive_radius=adaptive_radius, adaptive_offset=adaptive_offset,
+                                fill=median if isinstance(fill, str) and fill == "median" else fill)
+            out["range"] = range if isinstance(range, torch.Tensor) else torch.tensor([float(v) for v in range], device=self.device)
+        return self._answer(name, out, extra, as_tensor, traj=self._traj_status, dsi=out["status"])
 
     def _depth_median_word(self, resident):
         """(on the stream the state lives on) the lower median inverse depth of the last three frames' patches as a device
