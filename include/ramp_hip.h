@@ -1210,6 +1210,80 @@ int ramp_event_dsi(const float *x, const float *y, const double *t, int N, const
                    float *invdepth, float *confidence, int32_t *plane, void *ws, size_t ws_bytes, int32_t *status,
                    void *stream);
 
+/* ---------------------------------------------------------------- event map (csrc/evmap.hip)
+ *
+ * What EMVS does behind its detection: the semi-dense inverse depths of one reference view (ramp_event_dsi's invdepth / plane /
+ * confidence, or any map) are median-filtered over the detected pixels, isolated detections are dropped, the rest is lifted to
+ * world points (ramp_depth_points); the clouds of successive views are merged in a voxel hash table (ramp_point_map_*).
+ *
+ * ramp_depth_points.  invdepth [H][W] fp32; plane [H][W] int32, optional: a pixel is DETECTED when plane >= 0, with plane ==
+ *   NULL when invdepth is finite and > 0; confidence [H][W] fp32, optional (NULL: 1); cam: device float [7], CAMERA-TO-WORLD
+ *   (t, q as stored, not normalised: a row of the trajectory / of ramp_se3_interp); intrinsics: device (fx, fy, cx, cy) at the
+ *   image's resolution; median_radius r in 0 .. 3; min_support s >= 1; min_invdepth >= 0, finite.
+ * Filter, per detected pixel: the inverse depths of the detected pixels of the (2r + 1)^2 window clipped to the image, the
+ *   pixel itself among them, n in number.  n < s: the pixel is ISOLATED.  Else the filtered value is the LOWER median, the
+ *   element of index (n - 1) / 2 in ascending order -- the order of the project's median (csrc/median.h): that of the floats'
+ *   bits mapped to unsigned words, -0 below +0, a NaN with a clear sign bit above +inf.  r = 0: the pixel's own value.
+ * Lift, fp32 without FMA, (u, v) the integer pixel coordinates:   z = 1.0f / d,
+ *     Xc = (((u - cx) / fx) * z, ((v - cy) / fy) * z, z),    Xw = q Xc q^-1 + t   (lt_qrot of csrc/ramp_device.h)
+ *   DEPTH REJECTED: d not finite, d <= 0, d < min_invdepth, or a world point that is not finite.
+ * Outputs, compacted in ascending pixel index (a scan gives the positions: no atomics): points [K][3] fp32, conf [K] fp32,
+ *   pixel [K] int32 (v * W + u), each with room for H * W rows; count: device int32 = K; invdepth_filtered [H][W] fp32,
+ *   optional (NULL): the filtered value of a lifted pixel, NaN elsewhere.
+ * status: device int32 [8], written by the call: [0] bits (bit 0 RAMP_DEPTH_POINTS_BAD_CAMERA: a word of cam or intrinsics is
+ *   not finite, or fx / fy is 0: nothing is detected, count = 0, invdepth_filtered NaN everywhere, [1] .. [4] zero), [1]
+ *   detected, [2] isolated, [3] depth rejected, [4] lifted = count, [5] .. [7] 0.  [2] + [3] + [4] = [1].
+ * ws: ramp_depth_points_ws_bytes(H, W) bytes, 256-byte aligned.  One hipMemsetAsync (status), two kernels and one hipcub
+ *   scan, all on `stream`, nothing read back, nothing synchronised, no floating-point atomics; a call repeats its bits.
+ * RAMP_EINVAL: H or W < 1, r outside [0, 3], s < 1, a min_invdepth that is negative or not finite, a NULL invdepth / cam /
+ *   intrinsics / points / conf / pixel / count / ws / status, a ws that is not 256-byte aligned.  RAMP_EUNSUPPORTED: H * W >=
+ *   2^31.  RAMP_EWORKSPACE: a workspace too small.  A refused call touches nothing.
+ *
+ * The voxel hash.  map: a caller-owned device buffer of ramp_point_map_bytes(capacity) bytes, 64-byte aligned; capacity: a
+ *   power of two, 2^3 .. 2^30 (else the size is 0 and every call RAMP_EINVAL).  A 64-byte header (word 0: the occupied slots,
+ *   int64) and one 64-byte slot per voxel: key int64 (-1: empty; no voxel's key has bit 63 set), n int64, sq[3] int64, sc int64,
+ *   views uint64, one spare word.  ramp_point_map_clear: one launch; a buffer has to be cleared before its first insert.
+ * ramp_point_map_insert.  points [n_points][3] fp32, conf [n_points] fp32 (NULL: 1); count: optional device int32, the live
+ *   rows are then min(max(*count, 0), n_points), and n_points is the launch bound; voxel: the edge, a double, finite, > 0;
+ *   view >= 0: the id of the reference view.  One lane per point, float64 without FMA, per axis a:
+ *     g = double(p[a]) / voxel,  i = floor(g),  q = llrint((g - i) * 2^20) in 0 .. 2^20;   |i| >= 2^20: OUT OF RANGE
+ *     key = (ix + 2^20) << 42 | (iy + 2^20) << 21 | (iz + 2^20),      c = llrint(min(double(conf), 2^20) * 2^16)
+ *   A coordinate or confidence that is not finite, or a confidence below 0: NOT FINITE.  Both kinds are counted and dropped.
+ *   Slot: the finaliser of splitmix64 on the key (z ^= z >> 30, z *= 0xbf58476d1ce4e5b9, z ^= z >> 27, z *= 0x94d049bb133111eb,
+ *   z ^= z >> 31) masked to the capacity, then linear probing with a 64-bit atomicCAS on the key word.  On a claim or a match:
+ *   n += 1, sq[a] += q[a], sc += c (atomicAdd), views |= 1 << (view & 63) (atomicOr): VIEW IDS WRAP AT 64.  The probe loop is
+ *   bounded by `capacity` iterations; a point that ends it without a slot is DROPPED-FULL.  No lane waits for another lane.
+ *   status: device int32 [8], written by the call: [0] 0, [1] seen (the live rows), [2] not finite, [3] out of range, [4]
+ *   dropped-full, [5] accumulated, [6] occupied slots after the call, [7] 0.  [2] + [3] + [4] + [5] = [1].  All sums are
+ *   integers: while nothing is dropped-full the table does not depend on the points' order or on how they are split over calls.
+ *   One hipMemsetAsync (status) and two kernels (one with n_points == 0).
+ * ramp_point_map_export.  The occupied slots with n >= min_points and popcount(views) >= min_views, sorted by key ascending
+ *   (hipcub radix sort over the whole table), the first max_out of them, K in number:
+ *     points [K][3] fp32: float32((double(i_a) + (double(sq_a) / double(n)) * 2^-20) * voxel)     (voxel: as at the inserts)
+ *     n [K] int32 (saturating), conf [K] fp32 = float32(double(sc) * 2^-16), n_views [K] int32, key [K] int64, count: device
+ *     int32 = K.  Each array has room for min(max_out, capacity) rows.
+ *   status: device int32 [8]: [0] 0, [1] slots that pass, [2] of those, cut off by max_out (the highest keys), [3] occupied
+ *   slots, [4] .. [7] 0.  ws: ramp_point_map_export_ws_bytes(capacity) bytes (24 bytes per slot and hipcub's own),
+ *   256-byte aligned.  One hipMemsetAsync (status), two kernels around the sort.  The map is not written.
+ * All on `stream`, nothing read back, nothing synchronised, no floating-point atomics.  RAMP_EINVAL: a NULL or misaligned map,
+ *   a capacity that is not a power of two in 2^3 .. 2^30, a voxel that is not finite or not > 0, n_points < 0, NULL points with
+ *   n_points > 0, view < 0, min_points / min_views / max_out < 0, a NULL output with max_out > 0, a NULL count / ws / status, a
+ *   misaligned ws or key.  RAMP_EWORKSPACE: a workspace too small.  A refused call touches nothing.                        */
+#define RAMP_DEPTH_POINTS_BAD_CAMERA 1 /* status[0] bit 0 */
+size_t ramp_depth_points_ws_bytes(int H, int W);
+int ramp_depth_points(const float *invdepth, const int32_t *plane, const float *confidence, const float *cam,
+                      const float *intrinsics, int H, int W, int median_radius, int min_support, float min_invdepth,
+                      float *points, float *conf, int32_t *pixel, float *invdepth_filtered, int32_t *count, void *ws,
+                      size_t ws_bytes, int32_t *status, void *stream);
+size_t ramp_point_map_bytes(long capacity);
+int ramp_point_map_clear(void *map, long capacity, void *stream);
+int ramp_point_map_insert(void *map, long capacity, const float *points, const float *conf, int n_points, const int32_t *count,
+                          double voxel, int view, int32_t *status, void *stream);
+size_t ramp_point_map_export_ws_bytes(long capacity);
+int ramp_point_map_export(const void *map, long capacity, double voxel, long min_points, int min_views, int max_out,
+                          float *points, int32_t *n, float *conf, int32_t *n_views, int64_t *key, int32_t *count, void *ws,
+                          size_t ws_bytes, int32_t *status, void *stream);
+
 /* ---------------------------------------------------------------- inverse-depth map (csrc/depthmap.hip)
  *
  * ramp_invdepth_map: the selected patches of the window are projected into one camera pose and regressed to a dense map of

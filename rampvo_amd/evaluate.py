@@ -266,3 +266,25 @@ def save_map_ply(path, map_dict, scale=1.0):
         f.write(head.encode("ascii"))
         f.write(rec.tobytes())
     return path
+
+
+def save_points_ply(path, points, scalar=None, name="scalar"):
+    """points [K, 3] (``Ramp_vo.event_map_points()["points"]``, ``ops.PointMap.export``) as a binary little-endian PLY point
+    cloud: x y z (float) and, with ``scalar`` [K] (a confidence, a count), one more float property called ``name``"""
+    cpu = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    xyz = cpu(points).reshape(-1, 3)
+    fields = [("xyz", "<f4", 3)] + ([] if scalar is None else [("s", "<f4")])
+    rec = np.zeros(len(xyz), np.dtype(fields))
+    rec["xyz"] = xyz
+    if scalar is not None:
+        s = cpu(scalar).reshape(-1)
+        if len(s) != len(xyz):
+            raise RuntimeError("save_points_ply: scalar holds one number per point")
+        rec["s"] = s
+    Path(path).parent.mkdir(exist_ok=True, parents=True)
+    head = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % len(rec)
+            + ("" if scalar is None else "property float %s\n" % name) + "end_header\n")
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(rec.tobytes())
+    return path

@@ -21,6 +21,9 @@ _STATUS = {
                    ("n_below", "n_above", "n_not_finite", "n_rejected", "n_outside", "n_contributed")),
     "event_dsi": ({"bad_times": _lib.RAMP_INTERP_BAD_TIMES, "bad_range": _lib.RAMP_DSI_BAD_RANGE},
                   ("n_below", "n_above", "n_not_finite", "n_no_vote", "n_voted", "n_detected")),
+    "depth_points": ({"bad_camera": _lib.RAMP_DEPTH_POINTS_BAD_CAMERA}, ("n_detected", "n_isolated", "n_depth_rejected", "n_lifted")),
+    "point_map": ({}, ("n_seen", "n_not_finite", "n_out_of_range", "n_dropped_full", "n_accumulated", "n_occupied")),
+    "point_map_export": ({}, ("n_passing", "n_cut_off", "n_occupied")),
     "event_voxel": ({"bad_offsets": _lib.RAMP_VOXEL_BAD_OFFSETS, "bad_times": _lib.RAMP_VOXEL_BAD_TIMES},
                     ("n_events", "n_not_finite", "n_outside", "n_no_bin", "n_contributed")),
     "event_rectify": ({"bad_camera": _lib.RAMP_RECTIFY_BAD_CAMERA},
@@ -336,6 +339,146 @@ def event_dsi(x, y, t, knots, times, t_ref, intrinsics, height, width, planes=64
 def event_dsi_status(status):
     """The status words of ``event_dsi`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
     return _status("event_dsi", status)
+
+
+def depth_points(invdepth, cam, intrinsics, plane=None, confidence=None, median_radius=2, min_support=3, min_invdepth=0.0,
+                 want_filtered=False):
+    """A semi-dense inverse depth map, cleaned and lifted to world points (include/ramp_hip.h ``ramp_depth_points``; what EMVS
+    does behind its detection).  ``invdepth`` [H, W]; ``plane`` [H, W] int32: a pixel is detected when ``plane >= 0`` (None:
+    when ``invdepth`` is finite and positive); ``confidence`` [H, W] (None: 1) -- the ``invdepth``, ``plane`` and ``confidence``
+    of ``event_dsi`` as they are.  ``cam`` [7]: the CAMERA-TO-WORLD pose of the view, a row of ``trajectory()`` / ``poses_at()``;
+    ``intrinsics`` (fx, fy, cx, cy) at the map's resolution.
+
+    Per detected pixel: the LOWER median of the detected inverse depths of the (2 ``median_radius`` + 1)^2 window clipped to
+    the image (``median_radius`` 0 .. 3; 0: the pixel's own value); fewer than ``min_support`` detected pixels in the window
+    (the pixel itself counts): dropped as isolated.  A filtered value that is not finite, not positive or below
+    ``min_invdepth``, or a world point that is not finite, is dropped as well.  The defaults are defaults nobody has tuned.
+
+    Returns a dict of device tensors, nothing synchronised: ``points`` [H*W, 3], ``conf`` [H*W] and ``pixel`` [H*W] int32 (v * W
+    + u) of which the first ``count`` rows (int32 [1], ascending pixel index) are written, ``status`` int32 [8]
+    (``depth_points_status``) and, with ``want_filtered``, ``invdepth_filtered`` [H, W] (NaN where nothing was lifted).  A
+    ``cam`` or intrinsics that are not finite: ``count`` 0 and bit 0 of the status, never a plausible point."""
+    if invdepth.dim() != 2:
+        raise RuntimeError("depth_points: invdepth is [height, width]")
+    H, W = (int(v) for v in invdepth.shape)
+    if H < 1 or W < 1 or H * W >= 1 << 31:
+        raise RuntimeError("depth_points: at least one pixel and fewer than 2^31")
+    for name, m in (("plane", plane), ("confidence", confidence)):
+        if m is not None and tuple(m.shape) != (H, W):
+            raise RuntimeError("depth_points: %s has the shape of invdepth" % name)
+    if not 0 <= int(median_radius) <= 3:
+        raise RuntimeError("depth_points: median_radius is 0 .. 3")
+    if int(min_support) < 1:
+        raise RuntimeError("depth_points: min_support is at least 1")
+    if not 0.0 <= float(min_invdepth) < float("inf"):
+        raise RuntimeError("depth_points: min_invdepth is finite and not negative")
+    if cam.numel() != 7:
+        raise RuntimeError("depth_points: cam holds 7 numbers (t, q), camera to world")
+    require_cuda(invdepth, cam, plane, confidence)
+    dev = invdepth.device
+    inv = invdepth.to(torch.float32).contiguous()
+    pl = None if plane is None else plane.to(torch.int32).contiguous()
+    cf = None if confidence is None else confidence.to(torch.float32).contiguous()
+    camf = cam.reshape(7).to(torch.float32).contiguous()
+    K = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(4).contiguous()
+    res = {"points": torch.empty((H * W, 3), dtype=torch.float32, device=dev),
+           "conf": torch.empty(H * W, dtype=torch.float32, device=dev),
+           "pixel": torch.empty(H * W, dtype=torch.int32, device=dev),
+           "count": torch.empty(1, dtype=torch.int32, device=dev),
+           "status": torch.empty(8, dtype=torch.int32, device=dev)}
+    if want_filtered:
+        res["invdepth_filtered"] = torch.empty((H, W), dtype=torch.float32, device=dev)
+    ws, nbytes = sized_workspace("ramp_depth_points_ws_bytes", (H, W), dev, "evpts")
+    check(lib().ramp_depth_points(ptr(inv), ptr(pl), ptr(cf), ptr(camf), ptr(K), H, W, int(median_radius), int(min_support),
+                                  float(min_invdepth), ptr(res["points"]), ptr(res["conf"]), ptr(res["pixel"]),
+                                  ptr(res.get("invdepth_filtered")), ptr(res["count"]), ptr(ws), nbytes, ptr(res["status"]),
+                                  stream()), "ramp_depth_points")
+    return res
+
+
+def depth_points_status(status):
+    """The status words of ``depth_points`` as a dict: the bit of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("depth_points", status)
+
+
+class PointMap:
+    """A persistent map of world points: a voxel hash table on the device (include/ramp_hip.h ``ramp_point_map_*``).  Every
+    voxel of edge ``voxel`` that has received a point holds the number of its points, the sum of their positions inside the
+    voxel in fixed point (2^-20 voxel), the sum of their confidences (2^-16) and a mask of the views that saw it; ``export``
+    returns the mean point of every voxel, sorted by voxel.  All sums are 64-bit integers: the map does not depend on the
+    order of the points or on how they are split over calls, and repeats its bits.
+
+    ``capacity``: the slots, a power of two in 2^3 .. 2^30 (64 bytes each).  The table never grows: points whose voxel finds
+    no slot are counted (``n_dropped_full``) and dropped -- keep it at most half full.  Coordinates reach +-2^20 voxels from
+    the origin; points beyond are counted and dropped."""
+
+    def __init__(self, voxel, capacity=2 ** 20, device="cuda"):
+        voxel, capacity = float(voxel), int(capacity)
+        if not 0.0 < voxel < float("inf"):
+            raise RuntimeError("PointMap: voxel is finite and positive")
+        if not (8 <= capacity <= 1 << 30 and capacity & (capacity - 1) == 0):
+            raise RuntimeError("PointMap: capacity is a power of two in 2^3 .. 2^30")
+        self.voxel, self.capacity, self.device = voxel, capacity, torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("rampvo_amd operators run on the GPU only (got device %s); there is no CPU fallback" % self.device)
+        self.buf = torch.empty(lib().ramp_point_map_bytes(capacity), dtype=torch.uint8, device=self.device)
+        self.clear()
+
+    def clear(self):
+        """empty the map (one launch on the current stream)"""
+        check(lib().ramp_point_map_clear(ptr(self.buf), self.capacity, stream()), "ramp_point_map_clear")
+
+    def insert(self, points, conf=None, count=None, view=0):
+        """``points`` [N, 3] (``conf`` [N], None: 1) into the map; ``count``: a device int32 word, the rows that are live
+        (``depth_points``' ``count``), read on the device; ``view`` >= 0: the id of the reference view the points come from
+        (ids wrap at 64 in the mask of views).  Returns the device status words (``point_map_status``); nothing synchronised."""
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise RuntimeError("PointMap.insert: points is [N, 3]")
+        N = int(points.shape[0])
+        if conf is not None and conf.numel() != N:
+            raise RuntimeError("PointMap.insert: conf holds one number per point")
+        if count is not None and (count.dtype != torch.int32 or count.numel() != 1):
+            raise RuntimeError("PointMap.insert: count is one int32 word on the device")
+        if int(view) < 0:
+            raise RuntimeError("PointMap.insert: view is not negative")
+        require_cuda(points, conf, count)
+        pts = points.to(torch.float32).contiguous()
+        cf = None if conf is None else conf.reshape(-1).to(torch.float32).contiguous()
+        status = torch.empty(8, dtype=torch.int32, device=self.device)
+        check(lib().ramp_point_map_insert(ptr(self.buf), self.capacity, ptr(pts) if N else None, ptr(cf), N, ptr(count),
+                                          self.voxel, int(view), ptr(status), stream()), "ramp_point_map_insert")
+        return status
+
+    def export(self, min_points=1, min_views=1, max_out=None):
+        """The voxels with at least ``min_points`` points seen from at least ``min_views`` views (of 64: view ids wrap), sorted
+        by key, at most ``max_out`` of them (None: all).  Returns a dict of device tensors, nothing synchronised: ``points``
+        [R, 3], ``n`` [R] int32, ``conf`` [R] (the summed confidence), ``n_views`` [R] int32, ``key`` [R] int64 with R =
+        min(max_out, capacity) rows of which the first ``count`` (int32 [1]) are written, and ``status`` int32 [8]
+        (``point_map_export_status``)."""
+        if int(min_points) < 0 or int(min_views) < 0 or (max_out is not None and int(max_out) < 0):
+            raise RuntimeError("PointMap.export: min_points, min_views and max_out are not negative")
+        R = self.capacity if max_out is None else min(int(max_out), self.capacity)
+        dev = self.device
+        res = {"points": torch.empty((R, 3), dtype=torch.float32, device=dev), "n": torch.empty(R, dtype=torch.int32, device=dev),
+               "conf": torch.empty(R, dtype=torch.float32, device=dev), "n_views": torch.empty(R, dtype=torch.int32, device=dev),
+               "key": torch.empty(R, dtype=torch.int64, device=dev), "count": torch.empty(1, dtype=torch.int32, device=dev),
+               "status": torch.empty(8, dtype=torch.int32, device=dev)}
+        ws, nbytes = sized_workspace("ramp_point_map_export_ws_bytes", (self.capacity,), dev, "evmap")
+        p = lambda k: ptr(res[k]) if R else None
+        check(lib().ramp_point_map_export(ptr(self.buf), self.capacity, self.voxel, int(min_points), int(min_views), R,
+                                          p("points"), p("n"), p("conf"), p("n_views"), p("key"), ptr(res["count"]), ptr(ws),
+                                          nbytes, ptr(res["status"]), stream()), "ramp_point_map_export")
+        return res
+
+
+def point_map_status(status):
+    """The status words of ``PointMap.insert`` as a dict (synchronises: one small copy)."""
+    return _status("point_map", status)
+
+
+def point_map_export_status(status):
+    """The status words of ``PointMap.export`` as a dict (synchronises: one small copy)."""
+    return _status("point_map_export", status)
 
 
 def event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=None, signed=True,

@@ -702,6 +702,87 @@ class TrackerQueries:
             out["range"] = range if isinstance(range, torch.Tensor) else torch.tensor([float(v) for v in range], device=self.device)
         return self._answer(name, out, extra, as_tensor, traj=self._traj_status, dsi=out["status"])
 
+    # ---------------------------------------------------------------- event map
+    _event_map = None           # event_map(): the ops.PointMap the event queries merge their clouds in
+
+    def event_map(self, voxel=None, capacity=2 ** 20):
+        """The persistent semi-dense map of the scene: an ``ops.PointMap`` (a voxel hash table on the device) that
+        ``event_map_insert`` merges the cleaned clouds of successive reference views in.  Created at the first call, returned
+        by every later one (``voxel`` and ``capacity`` are then not read); it lives as long as the tracker.
+
+        ``voxel=None``: ``0.01 / median``, one hundredth of the median depth -- the median inverse depth ``compensate_events``
+        uses by default, read ONCE, here (the one wait of this call; raises while it is 0: no frame's patches yet).  A default
+        nobody has tuned.  A device-resident state stays device resident."""
+        if self._event_map is None:
+            if voxel is None:
+                with self._state_stream() as sc:
+                    word = self._depth_median_word(sc.resident)
+                    sc.leaves(word)
+                median = float(word.cpu())
+                if not (median > 0.0 and median < float("inf")):
+                    raise RuntimeError("event_map(): no depth median yet to size the voxels from (track a frame, or give voxel)")
+                voxel = 0.01 / median
+            with torch.cuda.device(self.device):
+                self._event_map = ops.PointMap(voxel, capacity=capacity, device=self.device)
+        return self._event_map
+
+    def event_map_insert(self, x, y, t, t_ref=None, median_radius=2, min_support=3, min_invdepth=None, as_tensor=False,
+                         **event_depth_arguments):
+        """One reference view into the event map: ``event_depth(x, y, t, t_ref, **event_depth_arguments)`` (the plane sweep of
+        these events), ``ops.depth_points`` of its ``invdepth`` / ``plane`` / ``confidence`` at the camera pose
+        ``poses_at([t_ref])`` (median filter of radius ``median_radius`` over the detected pixels, detections with fewer than
+        ``min_support`` detected pixels in their window dropped, lift to world points), and ``event_map().insert`` of the
+        cloud with the frame counter as the view id (the map's mask of views wraps at 64).  ``min_invdepth=None``: 0, every
+        positive inverse depth of the sweep's range is lifted.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call); nothing of the
+        tracker's state is written.  ``as_tensor=True``: a dict of device tensors, ordered on the current stream, nothing
+        synchronised: ``depth_status`` (ops.event_dsi), ``points_status`` (ops.depth_points), ``map_status``
+        (PointMap.insert), ``pose_status`` (ops.se3_interp), ``count`` (the points inserted from).  Otherwise the three status
+        words as dicts (``ops.event_dsi_status``, ``ops.depth_points_status``, ``ops.point_map_status``) and ``count`` as an
+        int, which reads once and raises on the conditions ``event_depth`` raises on and when the pose at ``t_ref`` is not
+        finite."""
+        name = "event_map_insert()"
+        if event_depth_arguments.get("fill") is not None:
+            raise RuntimeError(name + ": fill stays None (an undetected pixel has no depth to lift)")
+        pm = self.event_map()
+        out = self.event_depth(x, y, t, t_ref=t_ref, as_tensor=True, **event_depth_arguments)
+        cams, _, pose_status = self.poses_at([self.tlist[-1] if t_ref is None else float(t_ref)], as_tensor=True)
+        with self._state_stream() as sc:
+            K = self.intrinsics_[0] * float(self.RES)
+            sc.leaves(K)
+        with torch.no_grad():
+            pts = ops.depth_points(out["invdepth"], cams[0], K, plane=out["plane"], confidence=out["confidence"],
+                                   median_radius=median_radius, min_support=min_support,
+                                   min_invdepth=0.0 if min_invdepth is None else float(min_invdepth))
+            map_status = pm.insert(pts["points"], conf=pts["conf"], count=pts["count"], view=int(self.counter))
+        res = dict(depth_status=out["status"], points_status=pts["status"], map_status=map_status, pose_status=pose_status,
+                   count=pts["count"])
+        if as_tensor:
+            return res
+        _check_status(name, traj=self._traj_status, interp=pose_status, dsi=out["status"])
+        st = ops.depth_points_status(pts["status"])
+        if st["bad_camera"]:
+            raise RuntimeError(name + ": the camera pose at t_ref is not finite")
+        return dict(depth_status=ops.event_dsi_status(out["status"]), points_status=st,
+                    map_status=ops.point_map_status(map_status), count=st["n_lifted"])
+
+    def event_map_points(self, min_points=2, min_views=1, as_tensor=False):
+        """The event map as it is now (``event_map().export``): the mean point of every voxel that holds at least ``min_points``
+        points from at least ``min_views`` views (of 64: view ids wrap), sorted by voxel key.  ``as_tensor=True``: the dict of
+        device tensors of ``PointMap.export`` (``points``, ``n``, ``conf``, ``n_views``, ``key`` over the table's capacity, the
+        first ``count`` rows written; ``status``), nothing synchronised.  Otherwise numpy arrays cut to the count (one wait),
+        ready for ``evaluate.save_points_ply(path, points, conf)``.  Raises before the first ``event_map()``."""
+        if self._event_map is None:
+            raise RuntimeError("event_map_points(): there is no event map yet (event_map() or event_map_insert())")
+        with torch.no_grad():
+            out = self._event_map.export(min_points=min_points, min_views=min_views)
+        if as_tensor:
+            return out
+        k = int(out["count"].cpu())
+        return {**{key: out[key][:k].cpu().numpy() for key in ("points", "n", "conf", "n_views", "key")},
+                "count": k, "status": out["status"].cpu().numpy()}
+
     def _depth_median_word(self, resident):
         """(on the stream the state lives on) the lower median inverse depth of the last three frames' patches as a device
         word the host never reads; 0 without a frame"""
