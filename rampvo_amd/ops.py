@@ -7,7 +7,7 @@ import ctypes
 
 import torch
 
-from . import _lib, switches
+from . import _lib, switches, track_dev
 from ._lib import RAMP_CORR_MFMA32 as _LIB_CORR_MFMA32
 from ._lib import RAMP_CORR_X2 as _LIB_CORR_X2
 from ._lib import sized_workspace, workspace as _lib_workspace
@@ -15,33 +15,62 @@ from ._lib import KPLANE, RAMP_NHWC32, RAMP_NCHW, RAMP_NHWC, CorrLevel, check, d
 
 
 # ------------------------------------------------------------------- status words
-# per entry point ramp_<key>: the bits of status word 0 with their masks, and the names of words 1 and up
+# The one table of status words.  Per entry point ramp_<key>: the bits of status word 0 as name -> (mask, message), and the names
+# of words 1 and up.  The message is what the numpy form of a query raises with when the bit is set (queries._check_status):
+# a text, None for a bit that is decoded but never raises, or (head, ((refining mask, text), ...), default text) for a bit
+# whose text the word's other bits refine.  Entries whose words share a bit share its row.
+_BAD_TIMES = (_lib.RAMP_INTERP_BAD_TIMES, "the frames' time stamps decrease or are not finite")
+_BAD_CAMERA = (_lib.RAMP_RECTIFY_BAD_CAMERA, "the camera record is not finite or a focal length is not positive")
 _STATUS = {
-    "event_warp": ({"bad_times": _lib.RAMP_INTERP_BAD_TIMES},
-                   ("n_below", "n_above", "n_not_finite", "n_rejected", "n_outside", "n_contributed")),
-    "event_dsi": ({"bad_times": _lib.RAMP_INTERP_BAD_TIMES, "bad_range": _lib.RAMP_DSI_BAD_RANGE},
+    "trajectory": ({"unresolved": (track_dev.TRAJ_UNRESOLVED,
+                                   "a frame is neither a keyframe nor reachable through the delta chain")}, ()),
+    "event_warp": ({"bad_times": _BAD_TIMES}, ("n_below", "n_above", "n_not_finite", "n_rejected", "n_outside", "n_contributed")),
+    "event_dsi": ({"bad_times": _BAD_TIMES,
+                   "bad_range": (_lib.RAMP_DSI_BAD_RANGE,
+                                 "the range of inverse depths is not finite, negative or empty (no depth median yet?)")},
                   ("n_below", "n_above", "n_not_finite", "n_no_vote", "n_voted", "n_detected")),
-    "depth_points": ({"bad_camera": _lib.RAMP_DEPTH_POINTS_BAD_CAMERA}, ("n_detected", "n_isolated", "n_depth_rejected", "n_lifted")),
+    "depth_points": ({"bad_camera": (_lib.RAMP_DEPTH_POINTS_BAD_CAMERA, "the camera pose at t_ref is not finite")},
+                     ("n_detected", "n_isolated", "n_depth_rejected", "n_lifted")),
     "point_map": ({}, ("n_seen", "n_not_finite", "n_out_of_range", "n_dropped_full", "n_accumulated", "n_occupied")),
     "point_map_export": ({}, ("n_passing", "n_cut_off", "n_occupied")),
-    "event_voxel": ({"bad_offsets": _lib.RAMP_VOXEL_BAD_OFFSETS, "bad_times": _lib.RAMP_VOXEL_BAD_TIMES},
+    "event_voxel": ({"bad_offsets": (_lib.RAMP_VOXEL_BAD_OFFSETS, "the slice offsets decrease or leave the event list"),
+                     "bad_times": (_lib.RAMP_VOXEL_BAD_TIMES, "the first or last time stamp of a slice is not finite")},
                     ("n_events", "n_not_finite", "n_outside", "n_no_bin", "n_contributed")),
-    "event_rectify": ({"bad_camera": _lib.RAMP_RECTIFY_BAD_CAMERA},
+    "event_rectify": ({"bad_camera": _BAD_CAMERA},
                       ("n_events", "n_not_finite", "n_not_invertible", "n_behind", "n_outside", "n_inside")),
-    "image_rectify": ({"bad_camera": _lib.RAMP_RECTIFY_BAD_CAMERA}, ("n_pixels", "n_invalid", "n_outside", "n_sampled")),
-    "event_filter": ({"bad_order": _lib.RAMP_FILTER_BAD_ORDER},
+    "image_rectify": ({"bad_camera": _BAD_CAMERA}, ("n_pixels", "n_invalid", "n_outside", "n_sampled")),
+    "event_filter": ({"bad_order": (_lib.RAMP_FILTER_BAD_ORDER,
+                                    "a pixel's events decrease in time, or lie before the filter's state")},
                      ("n_events", "n_not_finite", "n_outside", "n_hot", "n_refractory", "n_no_support", "n_kept")),
-    "invdepth_map": ({"bad_cam": _lib.RAMP_DEPTHMAP_BAD_CAM},
+    "invdepth_map": ({"bad_cam": (_lib.RAMP_DEPTHMAP_BAD_CAM, "the camera pose at t_ref is not finite")},
                      ("n_considered", "n_bad_depth", "n_rejected", "n_out_of_reach", "n_contributing", "n_empty_pixels")),
-    "se3_interp": ({"bad_times": _lib.RAMP_INTERP_BAD_TIMES}, ("n_below", "n_above", "n_nan")),
-    "imu": ({"bad_order": _lib.RAMP_IMU_BAD_ORDER, "gyro_failed": _lib.RAMP_IMU_GYRO_FAILED,
-             "scale_failed": _lib.RAMP_IMU_SCALE_FAILED, "few_triples": _lib.RAMP_IMU_FEW_TRIPLES,
-             "singular": _lib.RAMP_IMU_SINGULAR, "bad_scale": _lib.RAMP_IMU_BAD_SCALE},
+    "se3_interp": ({"bad_times": _BAD_TIMES}, ("n_below", "n_above", "n_nan")),
+    "imu": ({"bad_order": (_lib.RAMP_IMU_BAD_ORDER, "the IMU samples' or the frames' time stamps decrease or are not finite"),
+             "gyro_failed": (_lib.RAMP_IMU_GYRO_FAILED, "the gyro bias step failed (no interval between two frames is covered "
+                                                        "by the samples, or its system is not finite)"),
+             "scale_failed": (_lib.RAMP_IMU_SCALE_FAILED,
+                              ("the scale and gravity solve failed: ",
+                               ((_lib.RAMP_IMU_FEW_TRIPLES, "fewer than two triples of frames are covered by the samples"),
+                                (_lib.RAMP_IMU_BAD_SCALE, "the scale is not positive")), "the system is singular")),
+             "few_triples": (_lib.RAMP_IMU_FEW_TRIPLES, None), "singular": (_lib.RAMP_IMU_SINGULAR, None),
+             "bad_scale": (_lib.RAMP_IMU_BAD_SCALE, None)},
             ("n_samples", "n_intervals", "n_uncovered", "n_dt_not_positive", "n_gyro_intervals", "n_triples")),
-    "imu_propagate": ({"bad_order": _lib.RAMP_IMU_BAD_ORDER, "bad_anchor": _lib.RAMP_IMU_BAD_ANCHOR,
-                       "no_start": _lib.RAMP_IMU_NO_START},
+    "imu_propagate": ({"bad_order": (_lib.RAMP_IMU_BAD_ORDER, "the IMU samples' time stamps decrease or are not finite"),
+                       "bad_anchor": (_lib.RAMP_IMU_BAD_ANCHOR, "the anchor is not finite or its scale is not positive "
+                                                                "(a failed alignment leaves NaN)"),
+                       "no_start": (_lib.RAMP_IMU_NO_START, "no IMU sample lies at or before the anchor's time stamp")},
                       ("n_samples", "n_held", "n_propagated", "n_cut_off", "n_beyond_horizon")),
 }
+# the roles of queries._check_status (its keywords): the entry whose word 0 each one carries -- ``interp`` also the words of
+# ops.event_warp and word 4 of ops.event_align's info, ``rectify`` also those of ops.image_rectify
+STATUS_ROLES = {"traj": "trajectory", "interp": "se3_interp", "cam": "invdepth_map", "voxel": "event_voxel",
+                "rectify": "event_rectify", "filter": "event_filter", "imu": "imu", "propagate": "imu_propagate",
+                "dsi": "event_dsi", "depth_points": "depth_points"}
+# the order in which the bits that raise are looked at, as (role, bit): the first one set gives the message
+STATUS_ORDER = (("filter", "bad_order"), ("rectify", "bad_camera"), ("traj", "unresolved"), ("interp", "bad_times"),
+                ("cam", "bad_cam"), ("voxel", "bad_offsets"), ("voxel", "bad_times"), ("imu", "bad_order"),
+                ("imu", "gyro_failed"), ("imu", "scale_failed"), ("propagate", "bad_order"), ("propagate", "bad_anchor"),
+                ("propagate", "no_start"), ("dsi", "bad_times"), ("dsi", "bad_range"), ("depth_points", "bad_camera"))
 
 
 def _status(entry, status):
@@ -49,7 +78,18 @@ def _status(entry, status):
     beside each wrapper"""
     bits, names = _STATUS[entry]
     w = status.detach().cpu().tolist()
-    return {**{k: bool(int(w[0]) & m) for k, m in bits.items()}, **{k: int(w[1 + i]) for i, k in enumerate(names)}}
+    return {**{k: bool(int(w[0]) & m) for k, (m, _) in bits.items()}, **{k: int(w[1 + i]) for i, k in enumerate(names)}}
+
+
+def status_message(role, bit, word):
+    """what a query raises with for ``bit`` of a role's word 0 = ``word``, or None while the bit is clear or never raises"""
+    mask, message = _STATUS[STATUS_ROLES[role]][0][bit]
+    if message is None or not word & mask:
+        return None
+    if isinstance(message, str):
+        return message
+    head, refined, default = message
+    return head + next((text for m, text in refined if word & m), default)
 
 
 # ------------------------------------------------------------------- altcorr
@@ -191,26 +231,40 @@ def event_stack(x, y, p, height, width, num_bins=5, as_float=True):
     return out
 
 
-def _event_arguments(name, x, y, t, p, knots, times, intrinsics, invdepth, height, width, extrapolate):
-    """the argument handling of ``event_warp``, for the entries that take its arguments -> (xf, yf, tf, pi, knots, times,
-    K, d, flags)"""
-    require_cuda(x, y, t, p, knots, times)
-    dev = x.device
-    N = x.shape[0]
+def _events(x, y, t, p):
+    """an event list as the kernels take it -> (xf, yf, tf, pi): fp32, fp32, float64, int8 with 0 read as -1 (``p=None``: no
+    polarity, ``pi`` None)"""
     xf, yf = x.reshape(-1).to(torch.float32).contiguous(), y.reshape(-1).to(torch.float32).contiguous()
     tf = t.reshape(-1).to(torch.float64).contiguous()
+    if p is None:
+        return xf, yf, tf, None
     pi = p.reshape(-1).to(torch.int8)
-    pi = torch.where(pi == 0, torch.full_like(pi, -1), pi).contiguous()
+    return xf, yf, tf, torch.where(pi == 0, torch.full_like(pi, -1), pi).contiguous()
+
+
+def _same_length(name, which, N, *lists):
+    """raises in the entry's own words (``which``: the lists it names) unless every list given holds N events"""
+    if any(v is not None and v.shape[0] != N for v in lists):
+        raise RuntimeError("%s: %s differ in length" % (name, which))
+
+
+def _event_arguments(name, x, y, t, p, knots, times, intrinsics, invdepth, height, width, extrapolate, which="x, y, t and p"):
+    """the argument handling of ``event_warp``, for the entries that take its arguments -> (xf, yf, tf, pi, knots, times,
+    K, d, flags); ``p=None``: no polarity, ``invdepth=None``: no inverse depth (``pi``, ``d`` None)"""
+    require_cuda(x, y, t, p, knots, times)
+    dev = x.device
+    xf, yf, tf, pi = _events(x, y, t, p)
     knots = knots.reshape(-1, 7).contiguous().float()
     times = times.reshape(-1).contiguous().double()
     T = knots.shape[0]
     if times.shape[0] != T:
         raise RuntimeError("%s: %d knots but %d time stamps" % (name, T, times.shape[0]))
-    if not (yf.shape[0] == N and tf.shape[0] == N and pi.shape[0] == N):
-        raise RuntimeError("%s: x, y, t and p differ in length" % name)
+    _same_length(name, which, x.shape[0], yf, tf, pi)
     K = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(4).contiguous()
     flags = _lib.RAMP_INTERP_EXTRAPOLATE if extrapolate else 0
-    if isinstance(invdepth, torch.Tensor) and invdepth.numel() != 1:
+    if invdepth is None:
+        d = None
+    elif isinstance(invdepth, torch.Tensor) and invdepth.numel() != 1:
         if tuple(invdepth.shape) != (height, width):
             raise RuntimeError("%s: an inverse depth map is [height, width]" % name)
         require_cuda(invdepth)
@@ -222,6 +276,16 @@ def _event_arguments(name, x, y, t, p, knots, times, intrinsics, invdepth, heigh
     else:
         d = torch.full((1,), float(invdepth), dtype=torch.float32, device=dev)
     return xf, yf, tf, pi, knots, times, K, d, flags
+
+
+def _correction(name, correction, dev):
+    """``correction`` of ``event_contrast`` / ``event_align`` as the kernels read it: None, or float32 [7] on the device"""
+    if correction is None:
+        return None
+    cor = torch.as_tensor(correction, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+    if cor.numel() != 7:
+        raise RuntimeError("%s: a correction is (v[3], w[3], lam): 7 numbers" % name)
+    return cor
 
 
 def event_warp(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, num_bins=0, extrapolate=False,
@@ -301,11 +365,8 @@ def event_dsi(x, y, t, knots, times, t_ref, intrinsics, height, width, planes=64
         raise RuntimeError("event_dsi: adaptive_radius is 0 .. 15")
     if D * H * W >= 1 << 31 or N * D >= 1 << 38:
         raise RuntimeError("event_dsi: planes x height x width is below 2^31 and events x planes below 2^38")
-    require_cuda(x, y, t, knots, times)
-    xf, yf = x.reshape(-1).to(torch.float32).contiguous(), y.reshape(-1).to(torch.float32).contiguous()
-    tf = t.reshape(-1).to(torch.float64).contiguous()
-    knots = knots.reshape(-1, 7).contiguous().float()
-    times = times.reshape(-1).contiguous().double()
+    xf, yf, tf, _, knots, times, K, _, flags = _event_arguments("event_dsi", x, y, t, None, knots, times, intrinsics, None, H, W,
+                                                                extrapolate, which="x, y and t")
 
     def word(name, v, n):
         if isinstance(v, torch.Tensor):
@@ -319,7 +380,6 @@ def event_dsi(x, y, t, knots, times, t_ref, intrinsics, height, width, planes=64
 
     rng = word("range", range, 2)
     fl = None if fill is None else word("fill", fill, 1)
-    K = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(4).contiguous()
     res = {"status": torch.empty(8, dtype=torch.int32, device=dev),
            "dsi": torch.empty((D, H, W), dtype=torch.int64, device=dev),
            "invdepth": torch.empty((H, W), dtype=torch.float32, device=dev),
@@ -329,7 +389,7 @@ def event_dsi(x, y, t, knots, times, t_ref, intrinsics, height, width, planes=64
         res["coords"] = torch.empty((N, D, 2), dtype=torch.float32, device=dev)
     ws, nbytes = sized_workspace("ramp_event_dsi_ws_bytes", (T, H, W), dev, "evdsi")
     check(lib().ramp_event_dsi(ptr(xf), ptr(yf), ptr(tf), N, ptr(knots), ptr(times), T, float(t_ref), ptr(K), ptr(rng),
-                               _lib.RAMP_INTERP_EXTRAPOLATE if extrapolate else 0, D, H, W, float(min_votes),
+                               flags, D, H, W, float(min_votes),
                                int(adaptive_radius), float(adaptive_offset), ptr(fl), ptr(res["dsi"]), ptr(res.get("coords")),
                                ptr(res["invdepth"]), ptr(res["confidence"]), ptr(res["plane"]), ptr(ws), nbytes,
                                ptr(res["status"]), stream()), "ramp_event_dsi")
@@ -503,12 +563,7 @@ def event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height
     dev, N, T = xf.device, xf.shape[0], knots.shape[0]
     if not signed:
         flags |= _lib.RAMP_CONTRAST_UNSIGNED
-    if correction is None:
-        cor = None
-    else:
-        cor = torch.as_tensor(correction, dtype=torch.float32, device=dev).reshape(-1).contiguous()
-        if cor.numel() != 7:
-            raise RuntimeError("event_contrast: a correction is (v[3], w[3], lam): 7 numbers")
+    cor = _correction("event_contrast", correction, dev)
     res = {"stats": torch.zeros(8, dtype=torch.float64, device=dev), "sums": torch.zeros(2, dtype=torch.int64, device=dev),
            "status": torch.zeros(8, dtype=torch.int32, device=dev)}
     res["variance"] = res["stats"][0]
@@ -559,13 +614,9 @@ def event_voxel_grid(x, y, t, p, height, width, num_bins=5, offsets=None, normal
     slice whose first or last time stamp is not finite is NaN: never a plausible number."""
     require_cuda(x, y, t, p, offsets)
     dev = x.device
-    xf, yf = x.reshape(-1).to(torch.float32).contiguous(), y.reshape(-1).to(torch.float32).contiguous()
-    tf = t.reshape(-1).to(torch.float64).contiguous()
-    pi = p.reshape(-1).to(torch.int8)
-    pi = torch.where(pi == 0, torch.full_like(pi, -1), pi).contiguous()
+    xf, yf, tf, pi = _events(x, y, t, p)
     N = xf.shape[0]
-    if not (yf.shape[0] == N and tf.shape[0] == N and pi.shape[0] == N):
-        raise RuntimeError("event_voxel_grid: x, y, t and p differ in length")
+    _same_length("event_voxel_grid", "x, y, t and p", N, yf, tf, pi)
     if num_bins < 1 or height < 1 or width < 1:
         raise RuntimeError("event_voxel_grid: num_bins, height and width are positive")
     if offsets is None:
@@ -1038,12 +1089,7 @@ def event_align(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, w
     dev, N, T = xf.device, xf.shape[0], knots.shape[0]
     if not signed:
         flags |= _lib.RAMP_CONTRAST_UNSIGNED
-    if correction is None:
-        cor = None
-    else:
-        cor = torch.as_tensor(correction, dtype=torch.float32, device=dev).reshape(-1).contiguous()
-        if cor.numel() != 7:
-            raise RuntimeError("event_align: a correction is (v[3], w[3], lam): 7 numbers")
+    cor = _correction("event_align", correction, dev)
     iters = int(iters)
     if iters < 0 or iters > _lib.RAMP_ALIGN_MAX_ITERS:
         raise RuntimeError("event_align: iters is 0 .. %d" % _lib.RAMP_ALIGN_MAX_ITERS)

@@ -54,22 +54,15 @@ class StateStream:
                 self.leaves(*(x.values() if isinstance(x, dict) else x))
 
 
-def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=None, filter=None, imu=None, propagate=None,
-                  dsi=None):
-    """The closing check of a query's numpy form -- its one wait.  Each argument is a device status tensor or None (not part
-    of this query): ``traj`` trajectory()'s word, ``interp`` the words of ops.se3_interp or ops.event_warp (bit 0 of word 0:
-    the frames' time stamps), ``cam`` those of ops.invdepth_map (bit 0 of word 0: the camera pose), ``voxel`` those of
-    ops.event_voxel_grid (bits 0 and 1 of word 0: the offsets, a slice's own time stamps), ``rectify`` those of
-    ops.event_rectify / ops.image_rectify (bit 0 of word 0: the camera record), ``filter`` those of ops.event_filter (bit 0 of
-    word 0: the events' order), ``imu`` those of ops.imu_align (bit 0: the order of the samples or of the frames' time stamps;
-    bits 1 and 2: the gyro stage, the scale stage), ``propagate`` those of ops.imu_propagate (bit 0: the samples' order; bits
-    6 and 7: the anchor, no sample at or before it), ``dsi`` those of ops.event_dsi (bit 0: the frames' time stamps, bit 1: the
-    range of inverse depths).  Word 0 of each goes to the host in one copy; raises in this order: event
-    order, camera record, unresolved delta chain, bad time stamps, camera pose, slice offsets, slice times, IMU order, gyro
-    stage, scale stage, the propagation's order, anchor and start, the sweep's time stamps and range."""
-    given = [(k, s.reshape(-1)[:1]) for k, s in (("traj", traj), ("interp", interp), ("cam", cam), ("voxel", voxel),
-                                                 ("rectify", rectify), ("filter", filter), ("imu", imu),
-                                                 ("propagate", propagate), ("dsi", dsi)) if s is not None]
+def _check_status(name, **roles):
+    """The closing check of a query's numpy form -- its one wait.  Each keyword is a role of ``ops.STATUS_ROLES`` (anything else
+    is a TypeError) with the device status tensor of that role's entry, or None (not part of this query).  Word 0 of each
+    goes to the host in one copy; raises on the first bit set in the order of ``ops.STATUS_ORDER``, with the text the
+    table ``ops._STATUS`` holds for it."""
+    for k in roles:
+        if k not in ops.STATUS_ROLES:
+            raise TypeError("_check_status() got an unexpected keyword argument %r" % k)
+    given = [(k, s.reshape(-1)[:1]) for k, s in roles.items() if s is not None]
     if not given:
         return
     first = given[0][1] if len(given) == 1 else torch.cat([s for _, s in given])
@@ -77,41 +70,11 @@ def _check_status(name, traj=None, interp=None, cam=None, voxel=None, rectify=No
 
 
 def _raise_on_words(name, word):
-    """``_check_status`` behind its copy: ``word`` maps its argument names to word 0 of each, on the host"""
-    if word.get("filter", 0) & _lib.RAMP_FILTER_BAD_ORDER:
-        raise RuntimeError(name + ": a pixel's events decrease in time, or lie before the filter's state")
-    if word.get("rectify", 0) & _lib.RAMP_RECTIFY_BAD_CAMERA:
-        raise RuntimeError(name + ": the camera record is not finite or a focal length is not positive")
-    if word.get("traj", 0) & track_dev.TRAJ_UNRESOLVED:
-        raise RuntimeError(name + ": a frame is neither a keyframe nor reachable through the delta chain")
-    if word.get("interp", 0) & 1:
-        raise RuntimeError(name + ": the frames' time stamps decrease or are not finite")
-    if word.get("cam", 0) & 1:
-        raise RuntimeError(name + ": the camera pose at t_ref is not finite")
-    if word.get("voxel", 0) & _lib.RAMP_VOXEL_BAD_OFFSETS:
-        raise RuntimeError(name + ": the slice offsets decrease or leave the event list")
-    if word.get("voxel", 0) & _lib.RAMP_VOXEL_BAD_TIMES:
-        raise RuntimeError(name + ": the first or last time stamp of a slice is not finite")
-    imu = word.get("imu", 0)
-    if imu & _lib.RAMP_IMU_BAD_ORDER:
-        raise RuntimeError(name + ": the IMU samples' or the frames' time stamps decrease or are not finite")
-    if imu & _lib.RAMP_IMU_GYRO_FAILED:
-        raise RuntimeError(name + ": the gyro bias step failed (no interval between two frames is covered by the samples, or its system is not finite)")
-    if imu & _lib.RAMP_IMU_SCALE_FAILED:
-        why = ("fewer than two triples of frames are covered by the samples" if imu & _lib.RAMP_IMU_FEW_TRIPLES else
-               "the scale is not positive" if imu & _lib.RAMP_IMU_BAD_SCALE else "the system is singular")
-        raise RuntimeError(name + ": the scale and gravity solve failed: " + why)
-    prop = word.get("propagate", 0)
-    if prop & _lib.RAMP_IMU_BAD_ORDER:
-        raise RuntimeError(name + ": the IMU samples' time stamps decrease or are not finite")
-    if prop & _lib.RAMP_IMU_BAD_ANCHOR:
-        raise RuntimeError(name + ": the anchor is not finite or its scale is not positive (a failed alignment leaves NaN)")
-    if prop & _lib.RAMP_IMU_NO_START:
-        raise RuntimeError(name + ": no IMU sample lies at or before the anchor's time stamp")
-    if word.get("dsi", 0) & _lib.RAMP_INTERP_BAD_TIMES:
-        raise RuntimeError(name + ": the frames' time stamps decrease or are not finite")
-    if word.get("dsi", 0) & _lib.RAMP_DSI_BAD_RANGE:
-        raise RuntimeError(name + ": the range of inverse depths is not finite, negative or empty (no depth median yet?)")
+    """``_check_status`` behind its copy: ``word`` maps roles to word 0 of each, on the host"""
+    for role, bit in ops.STATUS_ORDER:
+        message = role in word and ops.status_message(role, bit, word[role])
+        if message:
+            raise RuntimeError(name + ": " + message)
 
 
 def _dof_sigma0(s):
@@ -254,6 +217,20 @@ class TrackerQueries:
         self._imu = dict(R_bc=as_list("R_bc", R_bc), p_bc=as_list("p_bc", p_bc), bias_g=as_list("bias_g", bias_g),
                          bias_a=as_list("bias_a", bias_a))
 
+    def _imu_inputs(self, name, tau, gyro, accel):
+        """The prologue of the IMU queries -> (td, gd, ad, knots, tdev): the samples on the device (``tau`` float64; ``gyro``,
+        ``accel`` [N,3], float64 input stays float64), the trajectory as it is now and the cached time stamps.  Raises without a
+        sensor and below two frames."""
+        if self._imu is None:
+            raise RuntimeError(name + ": no IMU has been set (set_imu())")
+        if len(self.tlist) < 2:
+            raise RuntimeError(name + ": fewer than two frames have been tracked")
+        fl = lambda v: torch.float64 if (v.dtype == torch.float64 if isinstance(v, torch.Tensor) else np.asarray(v).dtype == np.float64) else torch.float32
+        td = self._as_device(tau, torch.float64)
+        gd, ad = self._as_device(gyro, fl(gyro)).reshape(-1, 3), self._as_device(accel, fl(accel)).reshape(-1, 3)
+        knots, _ = self.trajectory(as_tensor=True)
+        return td, gd, ad, knots, self._frame_times_dev()
+
     def align_imu(self, tau, gyro, accel, stride=1, gravity_norm=9.80665, max_gap=float("inf"), gyro_steps=1,
                   want_preint=False, as_tensor=False):
         """Metric scale, gravity direction and gyro bias of the trajectory as it is now, from raw IMU samples (``ops.imu_align``
@@ -266,23 +243,13 @@ class TrackerQueries:
         the dict of device tensors of ``ops.imu_align``, ordered on the current stream, nothing synchronised, nothing raised.
         Otherwise numpy arrays (``scale`` a float), which reads once at the end and raises on the status bits: the order of
         the time stamps, a failed gyro step, a failed scale solve, and trajectory()'s unresolved bit."""
-        if self._imu is None:
-            raise RuntimeError("align_imu(): no IMU has been set (set_imu())")
-        if len(self.tlist) < 2:
-            raise RuntimeError("align_imu(): fewer than two frames have been tracked")
-        fl = lambda v: torch.float64 if (v.dtype == torch.float64 if isinstance(v, torch.Tensor) else np.asarray(v).dtype == np.float64) else torch.float32
-        td = self._as_device(tau, torch.float64)
-        gd, ad = self._as_device(gyro, fl(gyro)).reshape(-1, 3), self._as_device(accel, fl(accel)).reshape(-1, 3)
-        knots, _ = self.trajectory(as_tensor=True)
-        tdev = self._frame_times_dev()
+        td, gd, ad, knots, tdev = self._imu_inputs("align_imu()", tau, gyro, accel)
         with torch.no_grad():                                  # (on the caller's stream, behind trajectory()'s launch: as poses_at)
             out = ops.imu_align(td, gd, ad, knots, tdev, stride=stride, max_gap=max_gap, gravity_norm=gravity_norm,
                                 gyro_steps=gyro_steps, want_preint=want_preint, **self._imu)
-        if as_tensor:
-            return out
-        _check_status("align_imu()", traj=self._traj_status, imu=out["status"])
-        res = {k: v.cpu().numpy() for k, v in out.items()}
-        res["scale"] = float(res["scale"][0])
+        res = self._answer("align_imu()", out, {}, as_tensor, traj=self._traj_status, imu=out["status"])
+        if not as_tensor:
+            res["scale"] = float(res["scale"][0])
         return res
 
     def propagate_imu(self, tau, gyro, accel, align=None, stride=1, gravity_norm=9.80665, max_gap=float("inf"),
@@ -299,19 +266,11 @@ class TrackerQueries:
         A device-resident state stays device resident.  ``as_tensor=True``: device tensors, ordered on the current stream,
         nothing synchronised, nothing raised.  Otherwise numpy arrays, which reads once at the end and raises on the status
         bits of the alignment and of the propagation, and on trajectory()'s unresolved bit."""
-        if self._imu is None:
-            raise RuntimeError("propagate_imu(): no IMU has been set (set_imu())")
-        if len(self.tlist) < 2:
-            raise RuntimeError("propagate_imu(): fewer than two frames have been tracked")
+        td, gd, ad, knots, tdev = self._imu_inputs("propagate_imu()", tau, gyro, accel)
         K = (len(self.tlist) - 1) // max(int(stride), 1) + 1
         if align is not None and (not isinstance(align.get("velocity"), torch.Tensor) or align["velocity"].shape[0] != K):
             raise RuntimeError("propagate_imu(): align= is the device dict of align_imu(as_tensor=True) at this stride and "
                                "frame count (%d knots)" % K)
-        fl = lambda v: torch.float64 if (v.dtype == torch.float64 if isinstance(v, torch.Tensor) else np.asarray(v).dtype == np.float64) else torch.float32
-        td = self._as_device(tau, torch.float64)
-        gd, ad = self._as_device(gyro, fl(gyro)).reshape(-1, 3), self._as_device(accel, fl(accel)).reshape(-1, 3)
-        knots, _ = self.trajectory(as_tensor=True)
-        tdev = self._frame_times_dev()
         with torch.no_grad():                                  # (on the caller's stream, behind trajectory()'s launch: as align_imu)
             if align is None:
                 align = ops.imu_align(td, gd, ad, knots, tdev, stride=stride, max_gap=max_gap, gravity_norm=gravity_norm,
@@ -319,12 +278,10 @@ class TrackerQueries:
             anchor = ops.imu_anchor(align, knots, tdev, stride=stride)
             out = ops.imu_propagate(td, gd, ad, anchor, R_bc=self._imu["R_bc"], p_bc=self._imu["p_bc"],
                                     bias_a=self._imu["bias_a"], max_gap=max_gap, horizon=horizon, want_state=want_state)
-        out["align"] = align
-        if as_tensor:
-            return out
-        _check_status("propagate_imu()", traj=self._traj_status, imu=align["status"], propagate=out["status"])
-        host = lambda d: {k: (host(v) if isinstance(v, dict) else v.cpu().numpy()) for k, v in d.items()}
-        return host(out)
+        res = self._answer("propagate_imu()", out, {}, as_tensor, traj=self._traj_status, imu=align["status"],
+                           propagate=out["status"])
+        res["align"] = align if as_tensor else {k: v.cpu().numpy() for k, v in align.items()}
+        return res
 
     # ---------------------------------------------------------------- event denoising
     _FILTER_KEYS = ("support_dt", "refractory", "hot_count", "hot_sigma", "hot_mask")
@@ -375,12 +332,9 @@ class TrackerQueries:
         the current stream, nothing synchronised.  Otherwise numpy arrays, which waits and raises when a pixel's events
         decrease in time or lie before the state (the state is then left as it was)."""
         out = self._filter("filter_events()", x, y, t, height, width)
-        if as_tensor:
-            self._filter_state = out["last_t"]             # (a bad order leaves NaN: every later call then has no state to hold against)
-            return out
-        _check_status("filter_events()", filter=out["status"])
-        self._filter_state = out["last_t"]
-        return {k: v.cpu().numpy() for k, v in out.items()}
+        res = self._answer("filter_events()", out, {}, as_tensor, filter=out["status"])
+        self._filter_state = out["last_t"]                 # (behind a clean check; as_tensor: a bad order leaves NaN, every later call then has no state to hold against)
+        return res
 
     def _denoised(self, name, x, y, t):
         """``denoise=True`` of an event query: (x, y, filter_status) with the filter's xy -- NaN rows for the dropped events --
@@ -428,10 +382,7 @@ class TrackerQueries:
         cam = self._rectified_camera("rectify_events()")
         with torch.no_grad():
             out = ops.event_rectify(self._raw_pixels(x), self._raw_pixels(y), cam, self.ht, self.wd, want_valid=True)
-        if as_tensor:
-            return out
-        _check_status("rectify_events()", rectify=out["status"])
-        return {k: v.cpu().numpy() for k, v in out.items()}
+        return self._answer("rectify_events()", out, {}, as_tensor, rectify=out["status"])
 
     def rectify_image(self, image, normalize="half", as_tensor=False):
         """A raw frame [C,Hs,Ws] or [Hs,Ws] (uint8 or float32; a tensor or an array) resampled into the camera the tracker is
@@ -446,10 +397,7 @@ class TrackerQueries:
         with torch.no_grad():
             out = ops.image_rectify(image.to(self.device), cam, self.ht, self.wd, normalize=normalize, want_mask=True)
         out.pop("map")
-        if as_tensor:
-            return out
-        _check_status("rectify_image()", rectify=out["status"])
-        return {k: v.cpu().numpy() for k, v in out.items()}
+        return self._answer("rectify_image()", out, {}, as_tensor, rectify=out["status"])
 
     def _undistorted(self, name, x, y):
         """``distorted=True`` of an event query: (x, y, rectify_status) with the rectified coordinates in the place of the raw"""
@@ -473,12 +421,13 @@ class TrackerQueries:
 
     @staticmethod
     def _answer(name, out, extra, as_tensor, **roles):
-        """The epilogue of an event query: ``out`` gains ``extra``; ``as_tensor``: the device dict as it is, else the one
-        ``_check_status`` call (``roles``: its other arguments) and numpy arrays."""
+        """The epilogue of a query with a numpy form: ``out`` gains ``extra`` (an event query's ``rectify_status`` /
+        ``filter_status``; else empty); ``as_tensor``: the device dict as it is, else the one ``_check_status`` call
+        (``roles``: its arguments, beside those two words) and numpy arrays."""
         out.update(extra)
         if as_tensor:
             return out
-        _check_status(name, rectify=extra.get("rectify_status"), filter=extra.get("filter_status"), **roles)
+        _check_status(name, **{"rectify": extra.get("rectify_status"), "filter": extra.get("filter_status"), **roles})
         return {k: v.cpu().numpy() for k, v in out.items()}
 
     def compensate_events(self, x, y, t, p, t_ref=None, invdepth=None, num_bins=0, extrapolate=False, want_xy=False,
@@ -760,10 +709,8 @@ class TrackerQueries:
                    count=pts["count"])
         if as_tensor:
             return res
-        _check_status(name, traj=self._traj_status, interp=pose_status, dsi=out["status"])
+        _check_status(name, traj=self._traj_status, interp=pose_status, dsi=out["status"], depth_points=pts["status"])
         st = ops.depth_points_status(pts["status"])
-        if st["bad_camera"]:
-            raise RuntimeError(name + ": the camera pose at t_ref is not finite")
         return dict(depth_status=ops.event_dsi_status(out["status"]), points_status=st,
                     map_status=ops.point_map_status(map_status), count=st["n_lifted"])
 
@@ -853,10 +800,7 @@ class TrackerQueries:
                 inv, wgt, status = render(sc.resident)
                 sc.leaves(inv, wgt, status)
         out = dict(invdepth=inv, weight=wgt, status=status, pose_status=pose_status)
-        if as_tensor:
-            return out
-        _check_status("invdepth_map()", traj=self._traj_status, interp=pose_status, cam=status)
-        return {k: v.cpu().numpy() for k, v in out.items()}
+        return self._answer("invdepth_map()", out, {}, as_tensor, traj=self._traj_status, interp=pose_status, cam=status)
 
     # --------------------------------------------------------------- uncertainty
     def _window_query(self, name, with_map=False, then=None, inputs=()):
