@@ -1284,6 +1284,55 @@ int ramp_point_map_export(const void *map, long capacity, double voxel, long min
                           float *points, int32_t *n, float *conf, int32_t *n_views, int64_t *key, int32_t *count, void *ws,
                           size_t ws_bytes, int32_t *status, void *stream);
 
+/* ---------------------------------------------------------------- event map rendering (csrc/maprender.hip)
+ *
+ * ramp_point_map_render: the voxel hash seen from any camera -- a z-buffered [H][W] map of inverse depth, the map
+ * ramp_event_warp samples with RAMP_WARP_DEPTH_MAP.  map, capacity, voxel: as at the inserts; the map is not written.
+ * Which slots take part.  One lane per slot reads the table where it is (no sort, no export).  A slot takes part when key !=
+ *   -1, n >= min_points and popcount(views) >= min_views: the export's conditions.  Every other occupied slot is FILTERED.
+ * World point.  The export's mean point, fp32: float32((double(i_a) + (double(sq_a) / double(n)) * 2^-20) * voxel) (one device
+ *   function, csrc/evmap_device.h, which the export calls as well).
+ * Camera.  cam: device float [7], CAMERA-TO-WORLD (t, q as stored, not normalised: a row of the trajectory / of
+ *   ramp_se3_interp, as in ramp_depth_points); intrinsics: device (fx, fy, cx, cy) at the image's resolution.
+ * Projection, fp32 without FMA:   Xc = q^-1 (Xw - t) q   (lt_qrot of csrc/ramp_device.h with (-qx, -qy, -qz, qw)),
+ *     z = Xc.z,   d' = 1.0f / z,   u = fx * (Xc.x * d') + cx,   v = fy * (Xc.y * d') + cy
+ *   REJECTED: z <= RAMP_WARP_MIN_Z (or NaN), a word of Xc that is not finite, or u or v not finite.
+ * Footprint.  The centre pixel is (rintf(u), rintf(v)) -- half to even, the rounding with which ramp_event_warp samples an
+ *   [H][W] map, so a rendered map and its consumer agree on what a pixel is.  footprint == 0: r_p = radius.  Else r_p is half
+ *   the voxel's projected edge, float64 without FMA:
+ *     rho = ((0.5 * voxel) * double(max(|fx|, |fy|))) * double(d'),    r_p = min(radius, max(0, (int)ceil(rho - 0.5)))
+ *   (the comparison with radius is made on the double: a huge rho never reaches an integer).  The slot covers the square
+ *   [px - r_p, px + r_p] x [py - r_p, py + r_p] clipped to the image.  A square without a pixel inside the image: the slot is
+ *   OUTSIDE (tested in floating point before any conversion to an integer: a huge u does not overflow).  Else it is RENDERED.
+ * Visibility.  Per pixel the winner is the covering slot with the largest d' -- the floats' bits compared as unsigned words,
+ *   d' > 0 -- and among equal bits the one with the LOWEST key (keys are unique): the image depends neither on the order of
+ *   the slots nor on the order of the inserts that built the table.
+ * Outputs.  invdepth [H][W] fp32: the winner's d'; a pixel no slot covers gets *fill (fill: optional device float word, as in
+ *   ramp_event_dsi) or NaN with fill == NULL.  key [H][W] int64, optional: the winner's key, -1 where nothing rendered.  n [H][W]
+ *   int32, optional: the winner's n, saturating as the export's, 0 where nothing rendered.  conf [H][W] fp32, optional: the
+ *   winner's float32(double(sc) * 2^-16), 0 where nothing rendered.  records [capacity][4] fp32, optional: (u, v, d',
+ *   float(r_p)) of every slot that is rendered or outside, a NaN row for every other slot.
+ * status: device int32 [8], written by the call: [0] bits (bit 0 RAMP_MAP_RENDER_BAD_CAMERA, raised exactly as
+ *   RAMP_DEPTH_POINTS_BAD_CAMERA: a word of cam or intrinsics is not finite, or fx / fy is 0: invdepth and conf are NaN
+ *   everywhere, fill or not, key -1, n 0, records NaN, [1] .. [6] zero -- never a plausible number), [1] occupied slots, [2]
+ *   filtered, [3] rejected, [4] outside, [5] rendered (covers at least one pixel, whether or not it wins one), [6] pixels with
+ *   a winner, [7] 0.  [2] + [3] + [4] + [5] = [1].
+ * ws: ramp_point_map_render_ws_bytes(H, W) bytes (12 bytes per pixel), 256-byte aligned.  One hipMemsetAsync (status) and FOUR
+ *   launches on `stream`: the clear of the workspace; per slot a return-less 32-bit atomicMax of the bits of d'; per slot a
+ *   return-less 64-bit atomicMin of the key where the slot's bits are the pixel's; per pixel, one writer, the outputs, the
+ *   winner's slot found by a read-only probe of the hash bounded by `capacity`.  The table is read twice.  Nothing is read
+ *   back, nothing synchronised, no floating-point atomics, no lane waits for another one; a call repeats its bits.
+ * RAMP_EINVAL: H or W < 1, radius outside 0 .. 7, a capacity that is not a power of two in 2^3 .. 2^30, a voxel that is not
+ *   finite or not > 0, min_points or min_views < 0, a NULL map / cam / intrinsics / invdepth / ws / status, a map that is not
+ *   64-byte, a ws that is not 256-byte or a key that is not 8-byte aligned.  RAMP_EUNSUPPORTED: H * W >= 2^31.
+ *   RAMP_EWORKSPACE: a workspace too small.  A refused call touches nothing.                                            */
+#define RAMP_MAP_RENDER_BAD_CAMERA 1 /* status[0] bit 0 */
+size_t ramp_point_map_render_ws_bytes(int H, int W);
+int ramp_point_map_render(const void *map, long capacity, double voxel, long min_points, int min_views, const float *cam,
+                          const float *intrinsics, int H, int W, int radius, int footprint, const float *fill, float *invdepth,
+                          int64_t *key, int32_t *n, float *conf, float *records, void *ws, size_t ws_bytes, int32_t *status,
+                          void *stream);
+
 /* ---------------------------------------------------------------- inverse-depth map (csrc/depthmap.hip)
  *
  * ramp_invdepth_map: the selected patches of the window are projected into one camera pose and regressed to a dense map of

@@ -19,28 +19,13 @@
 // pass get the key ~0, which no voxel has (bit 63 of a voxel's key is clear), and sort behind the rest.
 #include <hipcub/hipcub.hpp>
 
-#include "ramp_internal.h"
-#include "ramp_device.h"
+#include "evmap_device.h"
 
-#define EVM_THREADS 256
 #define EVM_TW 32
 #define EVM_TH 8
 #define EVM_RMAX 3                         // the largest median_radius: the halo of a tile in LDS
-#define EVM_AXIS (1ll << 20)               // voxel indices lie in (-2^20, 2^20); the fractions are in units of 2^-20 voxel
-#define EVM_CONF_BITS 16
-#define EVM_EMPTY (-1ll)                   // no voxel's key: bit 63 of a key is clear
-#define EVM_HEADER 64                      // bytes in front of the slots
 static_assert(EVM_TW * EVM_TH == EVM_THREADS, "one pixel per lane");
 
-struct __attribute__((aligned(64))) EvmSlot {
-  long long key, n, sq[3], sc;
-  unsigned long long views;
-  long long spare;
-};
-static_assert(sizeof(EvmSlot) == 64, "one slot, one 64-byte line");
-typedef unsigned long long evm_u64;
-
-static __device__ __forceinline__ bool evm_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }
 // median.h's order-preserving map of a float's bits to an unsigned word, and back
 static __device__ __forceinline__ unsigned evm_key(float v) {
   const unsigned b = __float_as_uint(v);
@@ -48,17 +33,6 @@ static __device__ __forceinline__ unsigned evm_key(float v) {
 }
 static __device__ __forceinline__ float evm_unkey(unsigned b) {
   return __uint_as_float(b ^ ((b >> 31) ? 0x80000000u : 0xffffffffu));
-}
-
-// c[0..6] = cam, c[7..10] = (fx, fy, cx, cy); true: a word is not finite or fx / fy is 0
-static __device__ __forceinline__ bool evm_load_camera(const float *cam, const float *intrinsics, float *c) {
-  bool bad = false;
-#pragma unroll
-  for (int k = 0; k < 11; k++) {
-    c[k] = k < 7 ? cam[k] : intrinsics[k - 7];
-    bad = bad || !evm_finite(c[k]);
-  }
-  return bad || c[7] == 0.0f || c[8] == 0.0f;
 }
 
 // the lift of pixel (u, v) with inverse depth d; false: rejected by its depth or a world point that is not finite
@@ -172,12 +146,6 @@ __global__ void __launch_bounds__(EVM_THREADS)
 }
 
 // ---------------------------------------------------------------------------------------------------------- the voxel hash
-static __device__ __forceinline__ evm_u64 evm_hash(evm_u64 z) {          // the finaliser of splitmix64
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
 __global__ void __launch_bounds__(EVM_THREADS) evm_clear_kernel(EvmSlot *__restrict__ slots, evm_u64 *__restrict__ header,
                                                                 long capacity) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -259,7 +227,7 @@ __global__ void __launch_bounds__(EVM_THREADS)
   if (i < capacity) {
     const EvmSlot *s = slots + i;
     const long long key = s->key;
-    pass = key != EVM_EMPTY && s->n >= min_points && __popcll(s->views) >= min_views;
+    pass = key != EVM_EMPTY && s->n >= min_points && __popcll(s->views) >= min_views;      // (evm_slot_passes, loads on demand)
     keys[i] = pass ? (evm_u64)key : ~(evm_u64)0;
     vals[i] = (int32_t)i;
   }
@@ -284,12 +252,10 @@ __global__ void __launch_bounds__(EVM_THREADS)
   if (i >= K) return;
   const EvmSlot *s = slots + order[i];
   const long long key = s->key, n = s->n;
-  const long long idx[3] = {(key >> 42) - EVM_AXIS, ((key >> 21) & (2 * EVM_AXIS - 1)) - EVM_AXIS, (key & (2 * EVM_AXIS - 1)) - EVM_AXIS};
 #pragma unroll
-  for (int a = 0; a < 3; a++)
-    points[3 * i + a] = (float)(((double)idx[a] + ((double)s->sq[a] / (double)n) * (1.0 / (double)EVM_AXIS)) * voxel);
-  n_out[i] = (int32_t)(n < 2147483647ll ? n : 2147483647ll);
-  conf[i] = (float)((double)s->sc * (1.0 / (double)(1 << EVM_CONF_BITS)));
+  for (int a = 0; a < 3; a++) points[3 * i + a] = evm_mean_axis(key, s->sq[a], n, a, voxel);
+  n_out[i] = evm_count_word(n);
+  conf[i] = evm_conf_word(s->sc);
   n_views[i] = __popcll(s->views);
   key_out[i] = key;
 }
@@ -334,11 +300,6 @@ static size_t evm_export_carve(void *ws, size_t capacity, EvmExportWs *w) {
   w->cub = c.take<char>(w->cub_bytes, 256);
   return c.bytes();
 }
-
-static bool evm_capacity_ok(long capacity) {
-  return capacity >= 8 && capacity <= (1l << 30) && (capacity & (capacity - 1)) == 0;
-}
-static EvmSlot *evm_slots(void *map) { return reinterpret_cast<EvmSlot *>((char *)map + EVM_HEADER); }
 
 extern "C" {
 size_t ramp_depth_points_ws_bytes(int H, int W) {

@@ -21,6 +21,9 @@ from ._lib import KPLANE, RAMP_NHWC32, RAMP_NCHW, RAMP_NHWC, CorrLevel, check, d
 # whose text the word's other bits refine.  Entries whose words share a bit share its row.
 _BAD_TIMES = (_lib.RAMP_INTERP_BAD_TIMES, "the frames' time stamps decrease or are not finite")
 _BAD_CAMERA = (_lib.RAMP_RECTIFY_BAD_CAMERA, "the camera record is not finite or a focal length is not positive")
+# (RAMP_MAP_RENDER_BAD_CAMERA is the same bit, raised on the same condition: the two entries share the row and the role)
+_BAD_POSE = (_lib.RAMP_DEPTH_POINTS_BAD_CAMERA, "the camera pose at t_ref is not finite")
+assert _lib.RAMP_MAP_RENDER_BAD_CAMERA == _lib.RAMP_DEPTH_POINTS_BAD_CAMERA
 _STATUS = {
     "trajectory": ({"unresolved": (track_dev.TRAJ_UNRESOLVED,
                                    "a frame is neither a keyframe nor reachable through the delta chain")}, ()),
@@ -29,10 +32,11 @@ _STATUS = {
                    "bad_range": (_lib.RAMP_DSI_BAD_RANGE,
                                  "the range of inverse depths is not finite, negative or empty (no depth median yet?)")},
                   ("n_below", "n_above", "n_not_finite", "n_no_vote", "n_voted", "n_detected")),
-    "depth_points": ({"bad_camera": (_lib.RAMP_DEPTH_POINTS_BAD_CAMERA, "the camera pose at t_ref is not finite")},
-                     ("n_detected", "n_isolated", "n_depth_rejected", "n_lifted")),
+    "depth_points": ({"bad_camera": _BAD_POSE}, ("n_detected", "n_isolated", "n_depth_rejected", "n_lifted")),
     "point_map": ({}, ("n_seen", "n_not_finite", "n_out_of_range", "n_dropped_full", "n_accumulated", "n_occupied")),
     "point_map_export": ({}, ("n_passing", "n_cut_off", "n_occupied")),
+    "point_map_render": ({"bad_camera": _BAD_POSE},
+                         ("n_occupied", "n_filtered", "n_rejected", "n_outside", "n_rendered", "n_pixels")),
     "event_voxel": ({"bad_offsets": (_lib.RAMP_VOXEL_BAD_OFFSETS, "the slice offsets decrease or leave the event list"),
                      "bad_times": (_lib.RAMP_VOXEL_BAD_TIMES, "the first or last time stamp of a slice is not finite")},
                     ("n_events", "n_not_finite", "n_outside", "n_no_bin", "n_contributed")),
@@ -62,7 +66,8 @@ _STATUS = {
                       ("n_samples", "n_held", "n_propagated", "n_cut_off", "n_beyond_horizon")),
 }
 # the roles of queries._check_status (its keywords): the entry whose word 0 each one carries -- ``interp`` also the words of
-# ops.event_warp and word 4 of ops.event_align's info, ``rectify`` also those of ops.image_rectify
+# ops.event_warp and word 4 of ops.event_align's info, ``rectify`` also those of ops.image_rectify, ``depth_points`` also
+# those of PointMap.render
 STATUS_ROLES = {"traj": "trajectory", "interp": "se3_interp", "cam": "invdepth_map", "voxel": "event_voxel",
                 "rectify": "event_rectify", "filter": "event_filter", "imu": "imu", "propagate": "imu_propagate",
                 "dsi": "event_dsi", "depth_points": "depth_points"}
@@ -530,6 +535,53 @@ class PointMap:
                                           nbytes, ptr(res["status"]), stream()), "ramp_point_map_export")
         return res
 
+    def render(self, cam, intrinsics, height, width, radius=2, footprint=True, min_points=1, min_views=1, fill=None,
+               want_key=True, want_n=True, want_conf=True, want_records=False):
+        """The map as a camera sees it: a z-buffered [height, width] map of inverse depth (include/ramp_hip.h
+        ``ramp_point_map_render``), the map ``event_warp`` samples at an event's pixel.  ``cam`` [7]: the CAMERA-TO-WORLD pose, a
+        row of ``trajectory()`` / ``poses_at()``; ``intrinsics`` (fx, fy, cx, cy) at the image's resolution.  Every voxel with at
+        least ``min_points`` points from at least ``min_views`` views (``export``'s conditions) is projected with ``export``'s
+        mean point and covers the square of radius r_p around its pixel: ``radius`` (0 .. 7) with ``footprint=False``, else half
+        the voxel's projected edge, at most ``radius``.  Per pixel the largest inverse depth wins, among equal ones the lowest
+        key.  ``fill``: what a pixel no voxel covers gets -- None (NaN), a number, or a one-element device tensor the host never
+        reads.  ``radius`` and the footprint rule are defaults nobody has tuned.
+
+        Returns a dict of device tensors, nothing synchronised: ``invdepth`` [H, W], ``status`` int32 [8]
+        (``point_map_render_status``) and, as requested, ``key`` [H, W] int64 (-1: nothing rendered), ``n`` [H, W] int32,
+        ``conf`` [H, W], ``records`` [capacity, 4] (u, v, inverse depth, r_p per slot that is rendered or outside the image, NaN
+        rows else).  A ``cam`` or intrinsics that are not finite: NaN everywhere and bit 0 of the status, never a plausible
+        depth."""
+        H, W = int(height), int(width)
+        if H < 1 or W < 1 or H * W >= 1 << 31:
+            raise RuntimeError("PointMap.render: at least one pixel and fewer than 2^31")
+        if not 0 <= int(radius) <= 7:
+            raise RuntimeError("PointMap.render: radius is 0 .. 7")
+        if int(min_points) < 0 or int(min_views) < 0:
+            raise RuntimeError("PointMap.render: min_points and min_views are not negative")
+        if not isinstance(cam, torch.Tensor) or cam.numel() != 7:
+            raise RuntimeError("PointMap.render: cam is a tensor of 7 numbers (t, q), camera to world")
+        if isinstance(fill, torch.Tensor) and fill.numel() != 1:
+            raise RuntimeError("PointMap.render: fill is None, a number or a one-element device tensor")
+        require_cuda(cam, fill if isinstance(fill, torch.Tensor) else None)
+        dev = self.device
+        camf = cam.reshape(7).to(torch.float32).contiguous()
+        K = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(4).contiguous()
+        if fill is not None:
+            fill = (fill.reshape(1).to(torch.float32) if isinstance(fill, torch.Tensor)
+                    else torch.full((1,), float(fill), dtype=torch.float32, device=dev))
+        res = {"invdepth": torch.empty((H, W), dtype=torch.float32, device=dev), "status": torch.empty(8, dtype=torch.int32, device=dev)}
+        for name, want, shape, dtype in (("key", want_key, (H, W), torch.int64), ("n", want_n, (H, W), torch.int32),
+                                         ("conf", want_conf, (H, W), torch.float32),
+                                         ("records", want_records, (self.capacity, 4), torch.float32)):
+            if want:
+                res[name] = torch.empty(shape, dtype=dtype, device=dev)
+        ws, nbytes = sized_workspace("ramp_point_map_render_ws_bytes", (H, W), dev, "evrender")
+        check(lib().ramp_point_map_render(ptr(self.buf), self.capacity, self.voxel, int(min_points), int(min_views), ptr(camf), ptr(K),
+                                          H, W, int(radius), 1 if footprint else 0, ptr(fill), ptr(res["invdepth"]), ptr(res.get("key")),
+                                          ptr(res.get("n")), ptr(res.get("conf")), ptr(res.get("records")), ptr(ws), nbytes,
+                                          ptr(res["status"]), stream()), "ramp_point_map_render")
+        return res
+
 
 def point_map_status(status):
     """The status words of ``PointMap.insert`` as a dict (synchronises: one small copy)."""
@@ -539,6 +591,11 @@ def point_map_status(status):
 def point_map_export_status(status):
     """The status words of ``PointMap.export`` as a dict (synchronises: one small copy)."""
     return _status("point_map_export", status)
+
+
+def point_map_render_status(status):
+    """The status words of ``PointMap.render`` as a dict: the bit of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("point_map_render", status)
 
 
 def event_contrast(x, y, t, p, knots, times, t_ref, intrinsics, invdepth, height, width, correction=None, signed=True,

@@ -445,7 +445,10 @@ class TrackerQueries:
         ``invdepth_map(t_ref, radius, weights)`` renders from the window's patches at the reference pose, so that every event is
         warped with the depth the tracker has estimated near its pixel (``radius``, ``weights`` are read in this mode only);
         ``"events"``: the map ``event_depth(x, y, t, t_ref, fill="median")`` sweeps from these very events (at the tracker's
-        image size), so that the events are warped with the depth they vote for themselves and with the median elsewhere.
+        image size), so that the events are warped with the depth they vote for themselves and with the median elsewhere;
+        ``"event_map"``: the map ``event_map_depth(t_ref, fill="median")`` renders from the persistent event map at the
+        reference pose (raises before the first ``event_map()``): the depth of every view inserted so far, at the cost of a
+        table read instead of a sweep, and the median where the map renders nothing.
         Intrinsics: row 0 of the tracker's own times the patch stride, i.e. those of the images it was fed.  ``height, width``
         default to the tracker's.  ``distorted=True``: ``x, y`` are RAW sensor pixels; they are rectified first
         (``rectify_events``, the camera of ``set_camera``; raises without one), the events without a solution are skipped and
@@ -470,7 +473,8 @@ class TrackerQueries:
     def _event_query(self, name, t_ref, invdepth, radius, weights, height, width, events=None):
         """what the event queries share: the trajectory as it is now, the cached time stamps, the image intrinsics and the
         inverse depth (None: the median word; ``"map"``: ``invdepth_map`` at the reference pose; ``"events"``: ``event_depth``
-        of the query's own ``events`` = (x, y, t) at the reference time, the median where nothing is detected), read on the
+        of the query's own ``events`` = (x, y, t) at the reference time, the median where nothing is detected;
+        ``"event_map"``: ``event_map_depth`` at the reference pose, the median where the map renders nothing), read on the
         stream the state lives on -> (knots, times, K, invdepth, t_ref, height, width)"""
         if not self.tlist:
             raise RuntimeError(name + ": no frame has been tracked yet")
@@ -480,8 +484,10 @@ class TrackerQueries:
                                              as_tensor=True)["invdepth"]
             elif invdepth == "events" and events is not None:
                 invdepth = self.event_depth(*events, t_ref=t_ref, fill="median", as_tensor=True)["invdepth"]
+            elif invdepth == "event_map":
+                invdepth = self.event_map_depth(t_ref=t_ref, fill="median", height=height, width=width, as_tensor=True)["invdepth"]
             else:
-                raise RuntimeError(name + ": invdepth is None, a number, a tensor, 'map' or 'events'")
+                raise RuntimeError(name + ": invdepth is None, a number, a tensor, 'map' or 'events', or 'event_map'")
         knots, _ = self.trajectory(as_tensor=True)
         tdev = self._frame_times_dev()
         with self._state_stream() as sc:                      # reads of the state, on the stream it lives on
@@ -497,7 +503,7 @@ class TrackerQueries:
                        weights="variance", distorted=False, denoise=False):
         """How sharp the compensated events are with the trajectory as it is now: the variance of the image of warped events
         ``compensate_events`` would return (the same events, poses, intrinsics and inverse depth -- ``invdepth`` as there,
-        ``"map"`` and ``"events"`` included) and its gradient with respect to a small correction ``(v[3], w[3], lam)`` of velocity, rotation
+        ``"map"``, ``"events"`` and ``"event_map"`` included) and its gradient with respect to a small correction ``(v[3], w[3], lam)`` of velocity, rotation
         rate and log depth scale in the reference camera frame (``ops.event_contrast``).  The only figure of quality an
         event tracker can give about its own trajectory without ground truth.  ``distorted=True``: raw sensor pixels, as in
         ``compensate_events``; the result gains ``rectify_status``.  ``denoise=True``: filtered first, as there; the result
@@ -525,7 +531,8 @@ class TrackerQueries:
                      distorted=False, denoise=False, resident=False, max_evals=None, as_tensor=False):
         """Refine the compensation by contrast maximisation (``ops.event_align``: normalised gradient ascent with
         backtracking over ``event_contrast``, the components ``free`` marks -- by default the rotation rate).  The
-        trajectory, intrinsics and inverse depth are read ONCE, as ``event_contrast`` reads them.  A device-resident state
+        trajectory, intrinsics and inverse depth (``invdepth`` as in ``compensate_events``, ``"event_map"`` included) are read
+        ONCE, as ``event_contrast`` reads them.  A device-resident state
         stays device resident on every path.  ``distorted=True``: raw sensor pixels, rectified once in front of the loop; the
         result gains ``rectify_status``.  ``denoise=True``: filtered once in front of the loop, as in ``compensate_events``;
         the result gains ``filter_status``.
@@ -585,7 +592,8 @@ class TrackerQueries:
 
         ``compensate=True``: a MOTION-COMPENSATED voxel grid.  The events are first warped to the camera pose at ``t_ref``
         with the trajectory as it is now (``compensate_events(want_xy=True, want_iwe=False, as_tensor=True)``; ``t_ref``,
-        ``invdepth``, ``extrapolate``, ``radius`` and ``weights`` are read in this mode only, as there) and their sub-pixel
+        ``invdepth`` -- ``"event_map"`` included --, ``extrapolate``, ``radius`` and ``weights`` are read in this mode only, as
+        there) and their sub-pixel
         coordinates are splat bilinearly; the events the warp rejects are NaN rows, which the grid skips and counts.  The time
         bins are those of the events' own time stamps.
 
@@ -729,6 +737,43 @@ class TrackerQueries:
         k = int(out["count"].cpu())
         return {**{key: out[key][:k].cpu().numpy() for key in ("points", "n", "conf", "n_views", "key")},
                 "count": k, "status": out["status"].cpu().numpy()}
+
+    def event_map_depth(self, t_ref=None, radius=2, footprint=True, min_points=2, min_views=1, fill=None, height=None,
+                        width=None, as_tensor=False):
+        """What the event map looks like from the camera pose at ``t_ref`` (default: the newest frame): a z-buffered inverse
+        depth map [height, width] (``event_map().render`` at ``poses_at([t_ref])`` with the image intrinsics, row 0 of the
+        tracker's own times the patch stride).  It carries the evidence of every view inserted so far and can be asked at a
+        pose the map has never been swept at; it is what ``compensate_events(invdepth="event_map")`` and its siblings sample.
+        ``radius``, ``footprint``, ``min_points``, ``min_views``: as ``ops.PointMap.render``; ``fill``: what a pixel no voxel
+        covers gets -- None (NaN), a number, a one-element device tensor, or ``"median"`` (the median inverse depth
+        ``compensate_events`` uses by default, a device word the host never reads).  ``radius=2``, ``min_points=2`` and the
+        footprint rule are defaults nobody has tuned.  ``height, width`` default to the tracker's.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call); neither the map nor
+        the tracker's state is written.  ``as_tensor=True``: the dict of device tensors of ``PointMap.render`` (``invdepth``,
+        ``key``, ``n``, ``conf``, ``status``) and ``pose_status`` (ops.se3_interp), ordered on the current stream, nothing
+        synchronised.  Otherwise numpy arrays, which reads once and raises when the pose at ``t_ref`` is not finite, when the
+        frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit.  Raises before the first
+        ``event_map()``."""
+        name = "event_map_depth()"
+        if self._event_map is None:
+            raise RuntimeError(name + ": there is no event map yet (event_map() or event_map_insert())")
+        if not self.tlist:
+            raise RuntimeError(name + ": no frame has been tracked yet")
+        if isinstance(fill, str) and fill != "median":
+            raise RuntimeError(name + ": fill is None, a number, a one-element device tensor or 'median'")
+        cams, _, pose_status = self.poses_at([self.tlist[-1] if t_ref is None else float(t_ref)], as_tensor=True)
+        with self._state_stream() as sc:                      # reads of the state, on the stream it lives on
+            K = self.intrinsics_[0] * float(self.RES)
+            if isinstance(fill, str):
+                fill = self._depth_median_word(sc.resident)
+            sc.leaves(K, fill)
+        with torch.no_grad():
+            out = self._event_map.render(cams[0], K, self.ht if height is None else int(height),
+                                         self.wd if width is None else int(width), radius=radius, footprint=footprint,
+                                         min_points=min_points, min_views=min_views, fill=fill)
+        out["pose_status"] = pose_status
+        return self._answer(name, out, {}, as_tensor, traj=self._traj_status, interp=pose_status, depth_points=out["status"])
 
     def _depth_median_word(self, resident):
         """(on the stream the state lives on) the lower median inverse depth of the last three frames' patches as a device
