@@ -1333,6 +1333,120 @@ int ramp_point_map_render(const void *map, long capacity, double voxel, long min
                           int64_t *key, int32_t *n, float *conf, float *records, void *ws, size_t ws_bytes, int32_t *status,
                           void *stream);
 
+/* ---------------------------------------------------------------- time surface (csrc/timesurface.hip)
+ *
+ * ramp_time_surface: per pixel the newest time stamp at or before t_ref, decayed and smoothed -- negated, the distance-like
+ * field ramp_point_map_localize samples: near 0 where events fired just before t_ref, 1 where none did.
+ * Last time stamps.  x, y: device fp32 [N]; t: device float64 [N], in any order.  The pixel of an event is (rintf(x),
+ *   rintf(y)) -- half to even, the rounding with which ramp_event_warp samples a map.  Per pixel the largest finite t <= t_ref
+ *   over the events and, if given, last_t_in (device float64 [H][W], ramp_event_filter's convention: NaN means no event yet; a
+ *   word that is not finite or lies behind t_ref counts as none).  One return-less 64-bit atomicMax per used event on the
+ *   double's bits mapped to an unsigned word of the same order (the word 0: no event), behind a relaxed load that skips an
+ *   atomic which cannot change the word.  The integer max does not depend on the events' order: a call repeats its bits.
+ * Surface, fp32.  raw(u) = expf(float32((last(u) - t_ref) / tau)), the quotient formed in float64; raw(u) = 0 where there is no
+ *   time stamp.  With RAMP_TIME_SURFACE_NEGATE raw becomes 1.0f - raw.
+ * Smoothing.  `smooth` passes (0 .. 8) of the separable 5-tap binomial (1, 4, 6, 4, 1) / 16, rows then columns, edges
+ *   replicated, fp32 without FMA: ((((1 a + 4 b) + 6 c) + 4 d) + 1 e) * 0.0625f.  Tiles go through LDS; the passes ping-pong
+ *   between `surface` and the workspace.  An fp32 emulator reproduces `surface` bit for bit from `raw`.
+ * Outputs.  surface [H][W] fp32.  raw [H][W] fp32, optional: the surface in front of the smoothing.  last_t_out [H][W] float64,
+ *   optional: the time stamps, NaN where there is none -- last_t_in of a later call.
+ * status: device int32 [8], written by the call: [0] bits (bit 0 RAMP_TIME_SURFACE_BAD_ARGS: t_ref or tau is not finite or tau
+ *   <= 0: surface and raw are NaN everywhere, last_t_out is still written), [1] events seen, [2] not finite (x, y or t), [3]
+ *   outside the image, [4] later than t_ref, [5] used, [6] pixels with a time stamp, [7] 0.  [2] + [3] + [4] + [5] = [1] = N.
+ * ws: ramp_time_surface_ws_bytes(H, W) bytes (12 bytes per pixel), 256-byte aligned.  One hipMemsetAsync (status) and 3 + 2 *
+ *   smooth launches on `stream` (2 + 2 * smooth with N == 0, which is valid: the surface of last_t_in, or all "no event").
+ *   Nothing is read back, nothing synchronised, no floating-point atomics, no lane waits for another one.
+ * RAMP_EINVAL: N < 0, H or W < 1, smooth outside 0 .. 8, an unknown flag, a NULL surface / status / ws, NULL events with N > 0,
+ *   a ws that is not 256-byte, a float64 buffer that is not 8-byte or another one that is not 4-byte aligned.
+ *   RAMP_EUNSUPPORTED: H * W >= 2^31.  RAMP_EWORKSPACE: a workspace too small.  A refused call touches nothing.        */
+#define RAMP_TIME_SURFACE_BAD_ARGS 1 /* status[0] bit 0 */
+#define RAMP_TIME_SURFACE_NEGATE 1   /* flags */
+size_t ramp_time_surface_ws_bytes(int H, int W);
+int ramp_time_surface(const float *x, const float *y, const double *t, long N, const double *last_t_in, double t_ref, double tau,
+                      int H, int W, int smooth, int flags, float *surface, float *raw, double *last_t_out, void *ws,
+                      size_t ws_bytes, int32_t *status, void *stream);
+
+/* ---------------------------------------------------------------- event map localisation (csrc/maplocalize.hip)
+ *
+ * ramp_point_map_localize_eval: one evaluation of the alignment of the voxel hash with a time surface at a camera pose.
+ * map, capacity, voxel, min_points, min_views, cam (CAMERA-TO-WORLD), intrinsics: as in ramp_point_map_render; which slots take
+ * part (the export's conditions), their mean point and their projection (Xc, u, v, REJECTED) are the renderer's, one device
+ * function (csrc/evmap_device.h): both entries give a voxel the same u, v in every bit.  The map is not written.
+ * surface: device fp32 [H][W] (ramp_time_surface with RAMP_TIME_SURFACE_NEGATE).
+ * Reach.  (u, v) is IN REACH when its four bilinear neighbours lie inside the image: 0 <= floorf(u) < W - 1 and 0 <= floorf(v) <
+ *   H - 1, tested in floating point before any conversion.
+ * Residual, fp32 without FMA, x0 = floorf(u), y0 = floorf(v), ax = u - x0, ay = v - y0, bx = 1.0f - ax, by = 1.0f - ay, s00 =
+ *   surface[y0][x0], s10 = surface[y0][x0 + 1], s01 = surface[y0 + 1][x0], s11 = surface[y0 + 1][x0 + 1]:
+ *     r  = by * (bx * s00 + ax * s10) + ay * (bx * s01 + ax * s11)
+ *     gu = by * (s10 - s00) + ay * (s11 - s01),    gv = bx * (s01 - s00) + ax * (s11 - s10)     (the interpolant's own derivative)
+ * Row, float64 without FMA from those fp32 words, (X, Y, z) = Xc, gx = double(gu) * double(fx), gy = double(gv) * double(fy):
+ *     J0 = gx / z,  J1 = gy / z,  J2 = -(gx * X + gy * Y) / (z * z),  J3 = Y * J2 - z * J1,  J4 = z * J0 - X * J2,  J5 = X * J1 - Y * J0
+ *   the derivative of r for the LEFT perturbation T <- Exp(xi) T of the world-to-camera pose T = cam^-1, xi = (translation 3,
+ *   rotation 3).  Huber threshold k = huber (<= 0: off): |r| <= k: w = 1, rho = r * r; else w = k / |r|, rho = (2 k) |r| - k k.
+ *   A slot that takes part but is REJECTED or out of reach contributes rho of r = 1, the surface's "no event" value, and no J:
+ *   the cost is a sum over the same slots at every pose, and a step cannot lower it by pushing points out of the image.
+ * sums: device float64 [32]: [0..20] sum (w J_p) J_q over p <= q, row-major; [21..26] sum (w J_p) r; [27] sum rho, the cost;
+ *   [28] the slots in reach; [29] the slots that take part; [30], [31] 0.  Per lane over its slots in ascending order (a
+ *   grid-stride loop, the grid capped: ramp_point_map_localize_grid_slots() slots per trip), then a fixed butterfly per wave,
+ *   the waves in wave order, the workgroups' rows in index order by one workgroup: no floating-point atomics, and for a given
+ *   table and arguments a call repeats its bits.  (Another insert order can move a slot, and with it the sums' rounding.)
+ * records [capacity][8] fp32, optional: (u, v, r, gu, gv, Xc.x, Xc.y, Xc.z); a slot that does not take part gets a NaN row, a
+ *   rejected one NaN in u .. gv, one out of reach NaN in r .. gv.
+ * status: device int32 [8], written by the call: [0] bits (bit 0 RAMP_MAP_LOCALIZE_BAD_CAMERA, raised exactly as
+ *   RAMP_MAP_RENDER_BAD_CAMERA: sums and records are then NaN, [1] .. [5] zero), [1] occupied slots, [2] filtered, [3] rejected,
+ *   [4] out of reach, [5] in reach, [6], [7] 0.  [2] + [3] + [4] + [5] = [1].  A surface pixel that is NaN makes r and the cost NaN.
+ * ws: ramp_point_map_localize_ws_bytes(capacity, iters) bytes, 256-byte aligned: ONE size for every valid capacity and iters
+ *   (the workgroups' rows under the grid's cap and the loop's state; the arguments are only checked, 0 for an invalid one), so
+ *   a caller queries it once.  One hipMemsetAsync (status), two launches.
+ * RAMP_EINVAL: the renderer's list with H or W < 2, a NULL surface or sums, a NaN huber, sums not 8-byte aligned.
+ *   RAMP_EUNSUPPORTED: H * W >= 2^31.  RAMP_EWORKSPACE.  A refused call touches nothing.
+ *
+ * ramp_point_map_localize: Levenberg-Marquardt over those evaluations, on the device: one call enqueues the whole solve, nothing
+ * is read back.  A state machine, one step (a one-wave launch) behind every evaluation; all state float64, only + - * / and
+ * sqrt in the order written, no FMA: a float64 restatement gives the same bits.
+ *   state: C = (c[3], q[4]) camera-to-world (cam0 widened), lambda = lambda0, f, (H, b) = (sums[0..20], sums[21..26]) kept
+ *   e == 0:     f = f0 = cost, keep (H, b);  in reach < 6 ? FEW : iters == 0 ? ITERS : propose
+ *   cost < f:   C = trial, f = cost, keep (H, b), history[n_accepted++] = f, lambda = max(lambda / 10, 1e-12), rejects = 0;
+ *               n_accepted == iters ? ITERS : in reach < 6 ? FEW : propose
+ *   otherwise:  lambda = lambda * 10, rejects += 1;  rejects == RAMP_LOCALIZE_REJECTS ? STALLED : propose      (a NaN cost lands here)
+ *   propose:    A = H, A_jj = H_jj + lambda * H_jj;  A = L L' by columns j = 0 .. 5, every sum started from A's word and reduced
+ *               term by term in ascending k; a pivot that is not > 0 and finite: SINGULAR.  L y = -b forward, L' delta = y
+ *               backward (terms in ascending k).  sqrt(sum delta_i^2) < min_step ? CONVERGED : trial = retract(C, delta); the
+ *               next evaluation reads float32(trial).  The last evaluation enqueued ends a machine still running: BUDGET.
+ *   retract:    delta = (v, w);  s = sqrt(1 + (w.w) / 4);  conj(dq) = (-(w / 2) / s, 1 / s)      (the Cayley map: Exp to first
+ *               order, rational);  q' = q * conj(dq) (Hamilton, xyzw), divided by its norm;  c' = c - rot(q', v)    (lt_qrot's
+ *               statements in float64): C' = C D^-1 for T' = D T, D = (R(dq), v).
+ *   iters accepted steps at most (0 .. RAMP_LOCALIZE_MAX_ITERS); max_evals <= 0: 1 + 9 * iters evaluations, else the smaller of
+ *   the two.  lambda0, the factors 10, the 8 rejections and min_step are values nobody has tuned.
+ * Outputs (device).  pose_out float64 [7]: C; pose_f32 fp32 [7]: the bits the evaluation at C read; result float64 [4]: cost,
+ *   cost0, lambda, the slots in reach at C; hessian float64 [36], gradient float64 [6]: the kept H (full, symmetric) and b;
+ *   history float64 [iters]: the accepted costs, NaN behind them; status int32 [8]: the words of the evaluation at C; info int32
+ *   [8]: reason (RAMP_LOCALIZE_*), n_accepted, n_evals, rejects, the OR of every evaluation's status[0], 0, 0, 0.  After FEW or
+ *   SINGULAR with nothing accepted, or with the bad-camera bit in info[4], pose_out and pose_f32 are NaN in every word: never a
+ *   plausible number.
+ * RAMP_EINVAL as the evaluation, and: iters outside its range, lambda0 or min_step negative or not finite, a NULL output (history
+ *   with iters > 0), a float64 output that is not 8-byte aligned.  3 launches per evaluation enqueued, behind one hipMemsetAsync
+ *   and one copy of cam0; the launches behind a stop return at their first statement.                                    */
+#define RAMP_MAP_LOCALIZE_BAD_CAMERA 1 /* status[0] bit 0 */
+#define RAMP_LOCALIZE_ITERS 1
+#define RAMP_LOCALIZE_CONVERGED 2
+#define RAMP_LOCALIZE_STALLED 3
+#define RAMP_LOCALIZE_SINGULAR 4
+#define RAMP_LOCALIZE_FEW 5
+#define RAMP_LOCALIZE_BUDGET 6
+#define RAMP_LOCALIZE_MAX_ITERS 4096
+#define RAMP_LOCALIZE_REJECTS 8 /* a step is given up after this many rejections in a row */
+size_t ramp_point_map_localize_ws_bytes(long capacity, int iters);
+long ramp_point_map_localize_grid_slots(void);
+int ramp_point_map_localize_eval(const void *map, long capacity, double voxel, long min_points, int min_views, const float *cam,
+                                 const float *intrinsics, const float *surface, int H, int W, double huber, double *sums,
+                                 float *records, void *ws, size_t ws_bytes, int32_t *status, void *stream);
+int ramp_point_map_localize(const void *map, long capacity, double voxel, long min_points, int min_views, const float *cam0,
+                            const float *intrinsics, const float *surface, int H, int W, double huber, double lambda0,
+                            double min_step, int iters, int max_evals, double *pose_out, float *pose_f32, double *result,
+                            double *hessian, double *gradient, double *history, int32_t *status, int32_t *info, void *ws,
+                            size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------- inverse-depth map (csrc/depthmap.hip)
  *
  * ramp_invdepth_map: the selected patches of the window are projected into one camera pose and regressed to a dense map of

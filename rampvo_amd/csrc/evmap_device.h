@@ -1,6 +1,8 @@
-// What the event map (evmap.hip) and its renderer (maprender.hip) share: the voxel hash's slot and constants, its hash, the
-// voxel indices of a key, the mean point of a slot -- one definition, so that the export and the renderer give a voxel the
-// same point in every bit -- and the camera words with their test (RAMP_DEPTH_POINTS_BAD_CAMERA, RAMP_MAP_RENDER_BAD_CAMERA).
+// What the event map (evmap.hip), its renderer (maprender.hip) and the localiser (maplocalize.hip) share: the voxel hash's slot
+// and constants, its hash, the voxel indices of a key, the mean point of a slot -- one definition, so that the export and the
+// renderer give a voxel the same point in every bit --, the projection of that point -- one definition again, so that the
+// renderer and the localiser give a voxel the same u, v in every bit -- and the camera words with their test
+// (RAMP_DEPTH_POINTS_BAD_CAMERA, RAMP_MAP_RENDER_BAD_CAMERA, RAMP_MAP_LOCALIZE_BAD_CAMERA).
 #pragma once
 #include "ramp_internal.h"
 #include "ramp_device.h"
@@ -46,6 +48,22 @@ static __device__ __forceinline__ long long evm_key_index(long long key, int a) 
 // the mean point of a slot along axis a: float32((double(i_a) + (double(sq_a) / double(n)) * 2^-20) * voxel)
 static __device__ __forceinline__ float evm_mean_axis(long long key, long long sq, long long n, int a, double voxel) {
   return (float)(((double)evm_key_index(key, a) + ((double)sq / (double)n) * (1.0 / (double)EVM_AXIS)) * voxel);
+}
+// The projection of a slot's mean point into the camera c (evm_load_camera's words; cam is CAMERA-TO-WORLD), fp32 without FMA --
+// one definition, so that the renderer (maprender.hip) and the localiser (maplocalize.hip) give a voxel the same u, v in every
+// bit.  False: REJECTED (z <= RAMP_WARP_MIN_Z or NaN, a word of Xc, u or v not finite); the outputs are then not to be used.
+static __device__ __forceinline__ bool evm_project(long long key, const long long *sq, long long n, const float *c, double voxel,
+                                                   float *Xc, float *d_out, float *u_out, float *v_out) {
+  float dX[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) dX[a] = evm_mean_axis(key, sq[a], n, a, voxel) - c[a];
+  const float qi[4] = {-c[3], -c[4], -c[5], c[6]};
+  lt_qrot(qi, dX, Xc);
+  const float z = Xc[2];
+  const float d = 1.0f / z;
+  const float u = c[7] * (Xc[0] * d) + c[9], v = c[8] * (Xc[1] * d) + c[10];
+  *d_out = d; *u_out = u; *v_out = v;
+  return !(!(z > RAMP_WARP_MIN_Z) || !evm_finite(Xc[0]) || !evm_finite(Xc[1]) || !evm_finite(z) || !evm_finite(u) || !evm_finite(v));
 }
 // what the export writes beside the point: n saturating, the summed confidence
 static __device__ __forceinline__ int32_t evm_count_word(long long n) { return (int32_t)(n < 2147483647ll ? n : 2147483647ll); }

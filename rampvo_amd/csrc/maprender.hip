@@ -52,15 +52,8 @@ static __device__ __forceinline__ MrdSplat mrd_splat(const EvmSlot *__restrict__
   if (key == EVM_EMPTY) return o;
   const long long n = s->n;
   if (!evm_slot_passes(key, n, s->views, min_points, min_views)) { o.kind = MRD_FILTERED; return o; }
-  float dX[3], Xc[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) dX[a] = evm_mean_axis(key, s->sq[a], n, a, voxel) - c[a];
-  const float qi[4] = {-c[3], -c[4], -c[5], c[6]};
-  lt_qrot(qi, dX, Xc);
-  const float z = Xc[2];
-  const float d = 1.0f / z;
-  const float u = c[7] * (Xc[0] * d) + c[9], v = c[8] * (Xc[1] * d) + c[10];
-  if (!(z > RAMP_WARP_MIN_Z) || !evm_finite(Xc[0]) || !evm_finite(Xc[1]) || !evm_finite(z) || !evm_finite(u) || !evm_finite(v)) {
+  float Xc[3], d, u, v;
+  if (!evm_project(key, s->sq, n, c, voxel, Xc, &d, &u, &v)) {
     o.kind = MRD_REJECTED;
     return o;
   }

@@ -23,7 +23,7 @@ _BAD_TIMES = (_lib.RAMP_INTERP_BAD_TIMES, "the frames' time stamps decrease or a
 _BAD_CAMERA = (_lib.RAMP_RECTIFY_BAD_CAMERA, "the camera record is not finite or a focal length is not positive")
 # (RAMP_MAP_RENDER_BAD_CAMERA is the same bit, raised on the same condition: the two entries share the row and the role)
 _BAD_POSE = (_lib.RAMP_DEPTH_POINTS_BAD_CAMERA, "the camera pose at t_ref is not finite")
-assert _lib.RAMP_MAP_RENDER_BAD_CAMERA == _lib.RAMP_DEPTH_POINTS_BAD_CAMERA
+assert _lib.RAMP_MAP_RENDER_BAD_CAMERA == _lib.RAMP_DEPTH_POINTS_BAD_CAMERA == _lib.RAMP_MAP_LOCALIZE_BAD_CAMERA
 _STATUS = {
     "trajectory": ({"unresolved": (track_dev.TRAJ_UNRESOLVED,
                                    "a frame is neither a keyframe nor reachable through the delta chain")}, ()),
@@ -37,6 +37,9 @@ _STATUS = {
     "point_map_export": ({}, ("n_passing", "n_cut_off", "n_occupied")),
     "point_map_render": ({"bad_camera": _BAD_POSE},
                          ("n_occupied", "n_filtered", "n_rejected", "n_outside", "n_rendered", "n_pixels")),
+    "point_map_localize": ({"bad_camera": _BAD_POSE}, ("n_occupied", "n_filtered", "n_rejected", "n_out_of_reach", "n_in_reach")),
+    "time_surface": ({"bad_args": (_lib.RAMP_TIME_SURFACE_BAD_ARGS, None)},
+                     ("n_events", "n_not_finite", "n_outside", "n_late", "n_used", "n_pixels")),
     "event_voxel": ({"bad_offsets": (_lib.RAMP_VOXEL_BAD_OFFSETS, "the slice offsets decrease or leave the event list"),
                      "bad_times": (_lib.RAMP_VOXEL_BAD_TIMES, "the first or last time stamp of a slice is not finite")},
                     ("n_events", "n_not_finite", "n_outside", "n_no_bin", "n_contributed")),
@@ -581,6 +584,152 @@ class PointMap:
                                           ptr(res.get("n")), ptr(res.get("conf")), ptr(res.get("records")), ptr(ws), nbytes,
                                           ptr(res["status"]), stream()), "ramp_point_map_render")
         return res
+
+    def _localize_arguments(self, name, surface, cam, intrinsics, min_points, min_views, huber):
+        """the checks both localisation entries share -> (surface, cam, intrinsics, H, W) as the kernels take them"""
+        if not isinstance(surface, torch.Tensor) or surface.dim() != 2 or surface.shape[0] < 2 or surface.shape[1] < 2:
+            raise RuntimeError("PointMap.%s: surface is a tensor [H, W] of at least 2 x 2 pixels (ops.time_surface)" % name)
+        H, W = int(surface.shape[0]), int(surface.shape[1])
+        if H * W >= 1 << 31:
+            raise RuntimeError("PointMap.%s: fewer than 2^31 pixels" % name)
+        if int(min_points) < 0 or int(min_views) < 0:
+            raise RuntimeError("PointMap.%s: min_points and min_views are not negative" % name)
+        if not isinstance(cam, torch.Tensor) or cam.numel() != 7:
+            raise RuntimeError("PointMap.%s: cam is a tensor of 7 numbers (t, q), camera to world" % name)
+        if huber != huber:
+            raise RuntimeError("PointMap.%s: huber is a number (<= 0: off)" % name)
+        require_cuda(surface, cam)
+        return (surface.to(torch.float32).contiguous(), cam.reshape(7).to(torch.float32).contiguous(),
+                torch.as_tensor(intrinsics, dtype=torch.float32, device=self.device).reshape(4).contiguous(), H, W)
+
+    def localize_eval(self, surface, cam, intrinsics, min_points=1, min_views=1, huber=0.0, want_records=False):
+        """One evaluation of the alignment of the map with a negative time surface (include/ramp_hip.h
+        ``ramp_point_map_localize_eval``): every voxel ``render`` would project -- the same conditions, the same u, v in every bit
+        -- samples ``surface`` [H, W] (``time_surface``) bilinearly at the CAMERA-TO-WORLD pose ``cam`` [7]; the sample is its
+        residual, and a voxel that leaves the image keeps the residual 1.  ``huber``: the threshold of the robust weight (<= 0: off).
+
+        Returns a dict of device tensors, nothing synchronised: ``sums`` float64 [32] and its views ``cost`` (0-d), ``hessian``
+        [6, 6] (the Gauss-Newton matrix, symmetric), ``gradient`` [6] -- for the left perturbation of the world-to-camera pose,
+        translation then rotation -- and ``in_reach`` (0-d); ``status`` int32 [8] (``point_map_localize_status``); ``records``
+        [capacity, 8] (u, v, r, gu, gv, Xc per slot; None unless ``want_records``).  A ``cam`` or intrinsics that are not
+        finite: NaN everywhere and bit 0 of the status."""
+        S, camf, K, H, W = self._localize_arguments("localize_eval", surface, cam, intrinsics, min_points, min_views, huber)
+        dev = self.device
+        res = {"sums": torch.empty(32, dtype=torch.float64, device=dev), "status": torch.empty(8, dtype=torch.int32, device=dev),
+               "records": torch.empty((self.capacity, 8), dtype=torch.float32, device=dev) if want_records else None}
+        ws, nbytes = sized_workspace("ramp_point_map_localize_ws_bytes", (self.capacity, 0), dev, "evlocalize")
+        check(lib().ramp_point_map_localize_eval(ptr(self.buf), self.capacity, self.voxel, int(min_points), int(min_views), ptr(camf),
+                                                 ptr(K), ptr(S), H, W, float(huber), ptr(res["sums"]), ptr(res["records"]), ptr(ws),
+                                                 nbytes, ptr(res["status"]), stream()), "ramp_point_map_localize_eval")
+        iu = torch.triu_indices(6, 6, device=dev)
+        hess = torch.zeros((6, 6), dtype=torch.float64, device=dev)
+        hess[iu[0], iu[1]] = res["sums"][:21]
+        hess[iu[1], iu[0]] = res["sums"][:21]
+        res.update(cost=res["sums"][27], hessian=hess, gradient=res["sums"][21:27], in_reach=res["sums"][28])
+        return res
+
+    def localize(self, surface, cam, intrinsics, min_points=1, min_views=1, huber=0.0, lambda0=1e-3, min_step=1e-6, iters=10,
+                 max_evals=None):
+        """Where is the camera in this map?  Levenberg-Marquardt over ``localize_eval`` from the start ``cam``, entirely on the
+        device (include/ramp_hip.h ``ramp_point_map_localize``: the state machine is written out there): one C call enqueues the
+        whole solve, ordered on the current stream, nothing is read back and nothing synchronised.  At most ``iters`` accepted
+        steps and ``max_evals`` evaluations (None: ``1 + 9 * iters``); evaluations behind the end of the solve are empty
+        launches, which still cost their enqueue.  ``lambda0`` (the first damping), its factors of 10, the 8 rejections that give
+        a step up and ``min_step`` (the length of a step that counts as converged) are values nobody has tuned.
+
+        Returns a dict of device tensors: ``pose`` float64 [7] (camera to world), ``pose_f32`` float32 [7] (the bits the
+        evaluation at ``pose`` read: pass it to ``localize_eval`` / ``render``), ``cost`` and ``cost0`` (0-d views of ``result``
+        float64 [4]: cost, cost0, the final lambda, the voxels in reach), ``hessian`` [6, 6] and ``gradient`` [6] at ``pose``,
+        ``history`` float64 [iters] (the accepted costs, NaN behind them), ``status`` int32 [8] (the words of the evaluation
+        at ``pose``) and ``info`` int32 [8] (``point_map_localize_info``).  The pose is NaN in every word when fewer than 6
+        voxels are in reach at the start, when the first system is singular, or when a camera was not finite."""
+        S, camf, K, H, W = self._localize_arguments("localize", surface, cam, intrinsics, min_points, min_views, huber)
+        iters = int(iters)
+        if iters < 0 or iters > _lib.RAMP_LOCALIZE_MAX_ITERS:
+            raise RuntimeError("PointMap.localize: iters is 0 .. %d" % _lib.RAMP_LOCALIZE_MAX_ITERS)
+        if not (0.0 <= float(lambda0) < float("inf") and 0.0 <= float(min_step) < float("inf")):
+            raise RuntimeError("PointMap.localize: lambda0 and min_step are finite and not negative")
+        if max_evals is not None and int(max_evals) < 1:
+            raise RuntimeError("PointMap.localize: max_evals is at least 1")
+        dev = self.device
+        res = {"pose": torch.zeros(7, dtype=torch.float64, device=dev), "pose_f32": torch.zeros(7, dtype=torch.float32, device=dev),
+               "result": torch.zeros(4, dtype=torch.float64, device=dev), "hessian": torch.zeros((6, 6), dtype=torch.float64, device=dev),
+               "gradient": torch.zeros(6, dtype=torch.float64, device=dev), "history": torch.zeros(iters, dtype=torch.float64, device=dev),
+               "status": torch.zeros(8, dtype=torch.int32, device=dev), "info": torch.zeros(8, dtype=torch.int32, device=dev)}
+        res["cost"], res["cost0"] = res["result"][0], res["result"][1]
+        ws, nbytes = sized_workspace("ramp_point_map_localize_ws_bytes", (self.capacity, iters), dev, "evlocalize")
+        check(lib().ramp_point_map_localize(ptr(self.buf), self.capacity, self.voxel, int(min_points), int(min_views), ptr(camf), ptr(K),
+                                            ptr(S), H, W, float(huber), float(lambda0), float(min_step), iters,
+                                            0 if max_evals is None else int(max_evals), ptr(res["pose"]), ptr(res["pose_f32"]),
+                                            ptr(res["result"]), ptr(res["hessian"]), ptr(res["gradient"]),
+                                            ptr(res["history"]) if iters else None, ptr(res["status"]), ptr(res["info"]), ptr(ws), nbytes,
+                                            stream()), "ramp_point_map_localize")
+        return res
+
+
+LOCALIZE_REASONS = {0: "running", _lib.RAMP_LOCALIZE_ITERS: "iters", _lib.RAMP_LOCALIZE_CONVERGED: "converged",
+                    _lib.RAMP_LOCALIZE_STALLED: "stalled", _lib.RAMP_LOCALIZE_SINGULAR: "singular", _lib.RAMP_LOCALIZE_FEW: "few",
+                    _lib.RAMP_LOCALIZE_BUDGET: "budget"}
+
+
+def point_map_localize_status(status):
+    """The status words of ``PointMap.localize_eval`` / ``localize`` as a dict: the bit of word 0 by name, then the counters
+    (synchronises: one small copy)."""
+    return _status("point_map_localize", status)
+
+
+def point_map_localize_info(info):
+    """the info words of ``PointMap.localize`` as a dict (synchronises: one 32-byte copy); ``reason``: ``iters`` (the accepted
+    steps asked for), ``converged`` (a step shorter than ``min_step``), ``stalled`` (8 rejections in a row), ``singular`` (the
+    damped system has no Cholesky factor), ``few`` (fewer than 6 voxels in reach) or ``budget`` (``max_evals`` ran out)"""
+    w = info.detach().cpu()
+    return dict(reason=LOCALIZE_REASONS.get(int(w[0]), "unknown"), n_accepted=int(w[1]), n_evals=int(w[2]), rejects=int(w[3]),
+                seen=int(w[4]), bad_camera=bool(int(w[4]) & _lib.RAMP_MAP_LOCALIZE_BAD_CAMERA))
+
+
+def time_surface(x, y, t, t_ref, tau, height, width, smooth=2, last_t=None, negate=True, want_raw=False, want_last_t=False):
+    """The time surface of an event list (include/ramp_hip.h ``ramp_time_surface``): per pixel ``exp((last - t_ref) / tau)`` of
+    the newest time stamp at or before ``t_ref`` (0 without one), ``negate``: one minus it -- near 0 where events fired just
+    before ``t_ref``, 1 where none did, the field ``PointMap.localize`` samples --, smoothed by ``smooth`` (0 .. 8) passes of
+    the 5-tap binomial.  ``x, y`` [N] (the pixel is the rounded coordinate), ``t`` [N] float64 in any order; ``last_t``: float64
+    [height, width], time stamps from before these events (``event_filter``'s ``last_t`` as it is; NaN: none).  ``smooth=2`` is
+    a default nobody has tuned.
+
+    Returns a dict of device tensors, nothing synchronised: ``surface`` [H, W] float32, ``status`` int32 [8]
+    (``time_surface_status``), ``raw`` (the surface in front of the smoothing; None unless ``want_raw``) and ``last_t`` (float64
+    [H, W], NaN where no event; None unless ``want_last_t``).  A ``t_ref`` or ``tau`` that is not finite, or ``tau <= 0``: NaN
+    everywhere and bit 0 of the status."""
+    H, W = int(height), int(width)
+    if H < 1 or W < 1 or H * W >= 1 << 31:
+        raise RuntimeError("time_surface: at least one pixel and fewer than 2^31")
+    if not 0 <= int(smooth) <= 8:
+        raise RuntimeError("time_surface: smooth is 0 .. 8")
+    require_cuda(x, y, t, last_t)
+    dev = x.device
+    xs, ys = x.reshape(-1).to(torch.float32).contiguous(), y.reshape(-1).to(torch.float32).contiguous()
+    tf = t.reshape(-1).to(torch.float64).contiguous()
+    N = xs.shape[0]
+    if not (ys.shape[0] == N and tf.shape[0] == N):
+        raise RuntimeError("time_surface: x, y and t differ in length")
+    state = None
+    if last_t is not None:
+        if tuple(last_t.shape) != (H, W) or last_t.dtype != torch.float64:
+            raise RuntimeError("time_surface: last_t is float64 [height, width] (event_filter's last_t)")
+        state = last_t.contiguous()
+    res = {"surface": torch.empty((H, W), dtype=torch.float32, device=dev), "status": torch.empty(8, dtype=torch.int32, device=dev),
+           "raw": torch.empty((H, W), dtype=torch.float32, device=dev) if want_raw else None,
+           "last_t": torch.empty((H, W), dtype=torch.float64, device=dev) if want_last_t else None}
+    ws, nbytes = sized_workspace("ramp_time_surface_ws_bytes", (H, W), dev, "timesurface")
+    check(lib().ramp_time_surface(ptr(xs) if N else None, ptr(ys) if N else None, ptr(tf) if N else None, N, ptr(state), float(t_ref),
+                                  float(tau), H, W, int(smooth), _lib.RAMP_TIME_SURFACE_NEGATE if negate else 0, ptr(res["surface"]),
+                                  ptr(res["raw"]), ptr(res["last_t"]), ptr(ws), nbytes, ptr(res["status"]), stream()),
+          "ramp_time_surface")
+    return res
+
+
+def time_surface_status(status):
+    """The status words of ``time_surface`` as a dict: the bit of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("time_surface", status)
 
 
 def point_map_status(status):

@@ -77,6 +77,35 @@ def _raise_on_words(name, word):
             raise RuntimeError(name + ": " + message)
 
 
+def _se3_log_between(a, b):
+    """Log(a^-1 b) of two poses (t, q) on the host, float64 -> (translation 3, rotation 3); NaN where a pose is.  Through the
+    relative quaternion: the angle is 2 atan2(|v|, w) (no loss near 0 or pi), with the series of the two coefficients below
+    1e-4 rad"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    if not (np.isfinite(a).all() and np.isfinite(b).all()):
+        return np.full(6, np.nan)
+
+    def mul(p, q):                                            # Hamilton, xyzw
+        return np.array([p[3] * q[0] + p[0] * q[3] + p[1] * q[2] - p[2] * q[1], p[3] * q[1] - p[0] * q[2] + p[1] * q[3] + p[2] * q[0],
+                         p[3] * q[2] + p[0] * q[1] - p[1] * q[0] + p[2] * q[3], p[3] * q[3] - p[0] * q[0] - p[1] * q[1] - p[2] * q[2]])
+
+    def rot(q, v):
+        return mul(mul(q, np.r_[v, 0.0]), q * [-1, -1, -1, 1])[:3]
+
+    qa, qb = a[3:] / np.linalg.norm(a[3:]), b[3:] / np.linalg.norm(b[3:])
+    qi = qa * [-1, -1, -1, 1]
+    q, t = mul(qi, qb), rot(qi, b[:3] - a[:3])
+    if q[3] < 0:
+        q = -q                                                # (the shorter way round)
+    n = np.linalg.norm(q[:3])
+    angle = 2.0 * np.arctan2(n, q[3])
+    w = q[:3] * ((2.0 + angle * angle / 12.0) if angle < 1e-4 else angle / n)
+    # V^-1 = I - W / 2 + c W^2,  c = (1 - (angle / 2) cot(angle / 2)) / angle^2
+    c = (1.0 / 12.0 + angle * angle / 720.0) if angle < 1e-4 else (1.0 - 0.5 * angle * q[3] / n) / (angle * angle)
+    wt = np.cross(w, t)
+    return np.concatenate([t - 0.5 * wt + c * np.cross(w, wt), w])
+
+
 def _dof_sigma0(s):
     """(dof, sigma0_sq) of ops.ba_covariance_stats' dict: ``dof = 2 n_valid - 6 N - Mu``, ``sigma0_sq = chi2 / max(dof, 1)``"""
     dof = 2 * s["n_valid"] - 6 * s["N"] - s["Mu"]
@@ -774,6 +803,69 @@ class TrackerQueries:
                                          min_points=min_points, min_views=min_views, fill=fill)
         out["pose_status"] = pose_status
         return self._answer(name, out, {}, as_tensor, traj=self._traj_status, interp=pose_status, depth_points=out["status"])
+
+    def event_map_localize(self, x, y, t, t_ref=None, tau=None, cam=None, smooth=2, min_points=2, min_views=1, huber=0.0,
+                           iters=10, max_evals=None, distorted=False, denoise=False, as_tensor=False):
+        """Where is the camera in the event map at ``t_ref`` (default: the newest frame)?  The events become a smoothed negative
+        time surface at the tracker's image size (``ops.time_surface``: decay ``tau``, ``smooth`` passes), and
+        ``event_map().localize`` moves the start pose ``cam`` [7] (camera to world; None: ``poses_at([t_ref])``) until the map's
+        voxels, projected with the image intrinsics (row 0 of the tracker's own times the patch stride), sample small values of
+        that surface -- Levenberg-Marquardt on the device, the tracking half of EVO / ESVO.  Events, ``distorted`` and ``denoise``
+        as ``compensate_events`` (no polarity).  ``tau=None``: the time between the last two frames; it, ``smooth``,
+        ``min_points=2`` and ``iters`` are defaults nobody has tuned.  ``min_points``, ``min_views``, ``huber``, ``iters``,
+        ``max_evals``: as ``ops.PointMap.localize``.
+
+        A device-resident state stays device resident (no settle(), the next frame is still one C call); NOTHING of the tracker
+        or of the map is written: the pose is an answer, not fed back into the window.  ``as_tensor=True``: the dict of device
+        tensors of ``PointMap.localize`` with ``pose_prior`` (the start, float32 [7]), ``surface_status`` (ops.time_surface) and
+        ``pose_status`` (ops.se3_interp; None with a ``cam`` given), ordered on the current stream, nothing synchronised.
+        Otherwise numpy arrays and numbers (a few small copies): ``pose``, ``pose_prior``, ``delta`` (the 6-vector Log(pose^-1
+        pose_prior), translation then rotation), ``cost``, ``cost0``, ``hessian``, ``reason`` (``ops.LOCALIZE_REASONS``: ``few``,
+        ``singular``, ``stalled`` and ``budget`` are reported, not raised), ``n_accepted``, ``n_evals`` and ``counts``
+        (``ops.point_map_localize_status`` of the evaluation at ``pose``); raises when the start pose is not finite, when the
+        frames' time stamps decrease or are not finite, or on trajectory()'s unresolved bit.  Raises before the first
+        ``event_map()``."""
+        name = "event_map_localize()"
+        if self._event_map is None:
+            raise RuntimeError(name + ": there is no event map yet (event_map() or event_map_insert())")
+        if not self.tlist:
+            raise RuntimeError(name + ": no frame has been tracked yet")
+        t_ref = float(self.tlist[-1] if t_ref is None else t_ref)
+        if tau is None:
+            if len(self.tlist) < 2:
+                raise RuntimeError(name + ": tau=None needs two frames (the time between the last two)")
+            tau = float(self.tlist[-1]) - float(self.tlist[-2])
+        if not (0.0 < float(tau) < float("inf")) or t_ref != t_ref or abs(t_ref) == float("inf"):
+            raise RuntimeError(name + ": tau is finite and positive, t_ref finite")
+        xd, yd, td, _, extra = self._event_inputs(name, x, y, t, None, denoise, distorted)
+        pose_status = None
+        if cam is None:
+            cams, _, pose_status = self.poses_at([t_ref], as_tensor=True)
+            cam = cams[0]
+        else:
+            cam = self._as_device(cam, torch.float32).reshape(-1)
+        with self._state_stream() as sc:                      # reads of the state, on the stream it lives on
+            K = self.intrinsics_[0] * float(self.RES)
+            sc.leaves(K)
+        with torch.no_grad():
+            ts = ops.time_surface(xd, yd, td, t_ref, float(tau), self.ht, self.wd, smooth=smooth)
+            out = self._event_map.localize(ts["surface"], cam, K, min_points=min_points, min_views=min_views, huber=huber,
+                                           iters=iters, max_evals=max_evals)
+            out["pose_prior"] = cam.reshape(7).to(torch.float32)
+        out["surface_status"], out["pose_status"] = ts["status"], pose_status
+        out.update(extra)
+        if as_tensor:
+            return out
+        info = torch.zeros(8, dtype=torch.int32, device=self.device)
+        info[0] = out["info"][4]                              # (every evaluation's word 0: the bad-camera bit rides on the one copy)
+        _check_status(name, rectify=extra.get("rectify_status"), filter=extra.get("filter_status"),
+                      traj=self._traj_status if pose_status is not None else None, interp=pose_status, depth_points=info)
+        pose, prior = out["pose"].cpu().numpy(), out["pose_prior"].cpu().numpy()
+        words = ops.point_map_localize_info(out["info"])
+        return dict(pose=pose, pose_prior=prior, delta=_se3_log_between(pose, prior), cost=float(out["cost"].cpu()),
+                    cost0=float(out["cost0"].cpu()), hessian=out["hessian"].cpu().numpy(), reason=words["reason"],
+                    n_accepted=words["n_accepted"], n_evals=words["n_evals"], counts=ops.point_map_localize_status(out["status"]),
+                    surface_counts=ops.time_surface_status(out["surface_status"]))
 
     def _depth_median_word(self, resident):
         """(on the stream the state lives on) the lower median inverse depth of the last three frames' patches as a device
