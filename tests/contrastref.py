@@ -19,8 +19,8 @@ purpose (every one of them has to be rejected by ``compare``).
 import numpy as np
 
 import georef
-import interpref
-import oracle as orc
+import poseref
+import splatref
 import warpref
 
 MISTAKES = ("nomean", "rotsign", "tausign", "nopol", "nolam", "unbiased")
@@ -34,36 +34,21 @@ def _theta(theta, dtype):
 
 def geometry(x, y, t, knots, times, t_ref, K, invdepth, H, W, theta=None, extrapolate=False, dtype=np.float64, mistake=None):
     """-> dict(xy [N,2] with NaN rows for invalid events, X1, X2, B = t_G ds [N,3], ds, tau [N]) in ``dtype``"""
-    x32, y32 = np.asarray(x, np.float32).reshape(-1), np.asarray(y, np.float32).reshape(-1)
-    t = np.asarray(t, np.float64).reshape(-1)
-    N = len(x32)
-    times = np.asarray(times, np.float64).reshape(-1)
-    nan3 = np.full((N, 3), np.nan, dtype)
-    if not np.isfinite(times).all() or (np.diff(times) < 0).any():
+    rays = warpref.event_rays(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate, dtype)
+    if rays is None:
+        N = np.asarray(x).size
+        nan3 = np.full((N, 3), np.nan, dtype)
         return dict(xy=np.full((N, 2), np.nan, dtype), X1=nan3, X2=nan3, B=nan3, ds=nan3[:, 0], tau=nan3[:, 0])
-    fin = np.isfinite(x32) & np.isfinite(y32) & np.isfinite(t)
-    tq = np.where(fin, t, times[0])
-    C, _ = interpref.interpolate(knots, times, tq, extrapolate, dtype)
-    Cr, _ = interpref.interpolate(knots, times, np.array([t_ref]), extrapolate, dtype)
-    if dtype == np.float64:
-        inv, mul = orc.se3_inv_f64, orc.se3_mul_f64
-    else:
-        f = lambda fn: (lambda *a: fn(*[np.ascontiguousarray(v, np.float32) for v in a]))
-        inv, mul = f(orc.se3_inv), f(orc.se3_mul)
-    G = np.asarray(mul(inv(np.repeat(np.asarray(Cr, dtype), N, 0)), np.asarray(C, dtype)), dtype)
-    fx, fy, cx, cy = (dtype(v) for v in np.asarray(K, np.float32).reshape(4))
-    xs, ys = np.where(fin, x32, 0).astype(dtype), np.where(fin, y32, 0).astype(dtype)
-    d = warpref.sample_depth(invdepth, x32, y32, H, W).astype(dtype)
+    fin, tq, G, P, d, (fx, fy, cx, cy) = rays
     th = _theta(theta, dtype)
     v, w, lam = th[:3], th[3:6], th[6]
     tau = (tq - float(t_ref)).astype(np.float32).astype(dtype)
     if mistake == "tausign":
         tau = -tau
-    P = np.stack([(xs - cx) / fx, (ys - cy) / fy, np.ones(N, dtype)], -1)
     with np.errstate(all="ignore"):
         ds = (d * np.exp(lam)).astype(dtype)
         B = (G[:, :3] * ds[:, None]).astype(dtype)
-        X1 = (warpref._qrot(G[:, 3:], P) + B).astype(dtype)
+        X1 = (poseref.qrot(G[:, 3:], P) + B).astype(dtype)
         X2 = (X1 + tau[:, None] * (v[None, :] * ds[:, None] + np.cross(w[None, :], X1))).astype(dtype)
         Z = X2[:, 2]
         xy = np.stack([fx * (X2[:, 0] / Z) + cx, fy * (X2[:, 1] / Z) + cy], -1).astype(dtype)
@@ -72,22 +57,12 @@ def geometry(x, y, t, knots, times, t_ref, K, invdepth, H, W, theta=None, extrap
     return dict(xy=xy, X1=X1, X2=X2, B=B, ds=ds, tau=tau)
 
 
-def _axis(v, n):
-    """one axis of the bilinear splat in the dtype of ``v``: floor, the two weights, which neighbours lie in [0, n)"""
-    fl = np.floor(v)
-    w = (v - fl).astype(v.dtype)
-    w0 = (v.dtype.type(1) - w).astype(v.dtype)
-    in0 = (fl >= 0) & (fl <= n - 1)
-    in1 = (fl >= -1) & (fl <= n - 2)
-    return np.where(in0 | in1, fl, 0).astype(np.int64), (w0, w), (in0, in1)
-
-
 def _splat(xy, s, H, W):
     """the image in float64 from coordinates in their own dtype -> (I [H,W], per-event neighbour data)"""
     valid = ~np.isnan(xy).any(-1)
     xv, yv = np.where(valid, xy[:, 0], 0).astype(xy.dtype), np.where(valid, xy[:, 1], 0).astype(xy.dtype)
-    ix, wx, inx = _axis(xv, W)
-    iy, wy, iny = _axis(yv, H)
+    ix, wx, inx = splatref.axis(xv, W, dtype=None)
+    iy, wy, iny = splatref.axis(yv, H, dtype=None)
     img = np.zeros((H, W), np.float64)
     for jy in range(2):
         for jx in range(2):

@@ -25,27 +25,13 @@ The ``mistake`` keywords break the restatement on purpose (tests/test_depthref_c
 import numpy as np
 
 import georef
-import oracle as orc
+import poseref
 
 MIN_Z = 0.2                  # RAMP_WARP_MIN_Z
 MAP_FLOOR = 1e-5             # x the largest d' (the map) / the largest weight
 Z_MARGIN = 1e-4              # rejected sets may differ where float64's Z' is this close to MIN_Z
 PROJECT_MISTAKES = ("fxfy", "inverse", "dz", "noscale")
 REGRESS_MISTAKES = ("unsquared", "noprior_den")
-
-
-def _qrot(q, v):
-    """lietorch's rotation of v by the unit quaternion q (x, y, z, w), in the dtype of the inputs"""
-    two = q.dtype.type(2)
-    uv = two * np.cross(q[..., :3], v)
-    return v + q[..., 3:4] * uv + np.cross(q[..., :3], uv)
-
-
-def _se3(dtype):
-    if dtype == np.float64:
-        return orc.se3_inv_f64, orc.se3_mul_f64
-    f = lambda fn: (lambda *a: fn(*[np.ascontiguousarray(v, np.float32) for v in a]))
-    return f(orc.se3_inv), f(orc.se3_mul)
 
 
 def project(poses, patches, intr, cam, ids, M, H, W, R, scale=1.0, conf=None, conf_is_variance=False, dtype=np.float64,
@@ -69,7 +55,7 @@ def project(poses, patches, intr, cam, ids, M, H, W, R, scale=1.0, conf=None, co
         cf = np.asarray(conf, np.float32).reshape(-1)[ids]
         with np.errstate(all="ignore"):
             c = ((np.float32(1.0) / cf) if conf_is_variance else cf).astype(dtype)      # (1 / conf is formed in float32)
-    inv, mul = _se3(dtype)
+    _, _, inv, mul = poseref.se3_ops(dtype)
     T = poses[ids // M].astype(dtype)
     C = np.repeat(cam.astype(dtype), K, 0)
     with np.errstate(all="ignore"):
@@ -78,7 +64,7 @@ def project(poses, patches, intr, cam, ids, M, H, W, R, scale=1.0, conf=None, co
         ux, uy = (fy, fx) if mistake == "fxfy" else (fx, fy)
         sc = dtype(1.0 if mistake == "noscale" else np.float32(scale))
         r = np.stack([(x - cx) / ux, (y - cy) / uy, np.ones(K, dtype)], -1)
-        X = _qrot(G[:, 3:], r) + G[:, :3] * d[:, None]
+        X = poseref.qrot(G[:, 3:], r) + G[:, :3] * d[:, None]
         Z = X[:, 2]
         u = sc * (fx * (X[:, 0] / Z) + cx)
         v = sc * (fy * (X[:, 1] / Z) + cy)

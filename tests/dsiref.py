@@ -12,7 +12,7 @@
 """
 import numpy as np
 
-import georef
+import splatref
 import warpref
 
 FIX_BITS = warpref.FIX_BITS
@@ -48,22 +48,10 @@ def coordinates(x, y, t, knots, times, t_ref, K, rng, D, H, W, extrapolate=False
 
 
 def compare(coords_gpu, x, y, t, knots, times, t_ref, K, rng, D, H, W, extrapolate=False, z_margin=1e-4, mistake=None):
-    """``warpref.compare`` over events x planes: err against float64 where both are valid, env the float32 restatement's own,
-    bound = georef.bound(PIXEL_FLOOR x largest |coordinate|, env); the NaN entries have to agree except where float64's Z' is
-    within ``z_margin`` of MIN_Z"""
+    """``warpref.compare`` over events x planes: ``warpref.compare_coords`` against this restatement"""
     r64, z64 = coordinates(x, y, t, knots, times, t_ref, K, rng, D, H, W, extrapolate, np.float64)
     r32, _ = coordinates(x, y, t, knots, times, t_ref, K, rng, D, H, W, extrapolate, np.float32)
-    out = np.asarray(coords_gpu, np.float64)
-    v64, v32, vg = ~np.isnan(r64).any(-1), ~np.isnan(r32).any(-1), ~np.isnan(out).any(-1)
-    edge = np.abs(z64 - MIN_Z) < z_margin
-    nan_ok = bool(((vg == v64) | edge).all())
-    keep = v64 & vg
-    err = float(np.abs(out[keep] - r64[keep]).max()) if keep.any() else 0.0
-    k32 = v64 & v32
-    env = float(np.abs(r32[k32].astype(np.float64) - r64[k32]).max()) if k32.any() else 0.0
-    floor = georef.PIXEL_FLOOR * max(1.0, float(np.abs(r64[v64]).max()) if v64.any() else 1.0)
-    b = georef.bound(floor, env)
-    return dict(err=err, env=env, floor=floor, bound=b, nan_ok=nan_ok, n_valid=int(keep.sum()), ok=nan_ok and err <= b)
+    return warpref.compare_coords(coords_gpu, r64, z64, r32, z_margin)
 
 
 # ------------------------------------------------------------------------------------------------------- the exact emulator
@@ -78,11 +66,11 @@ def votes(coords, H, W, mistake=None):
     for k in range(D):
         m0 = valid[:, k]
         xv, yv = np.where(m0, c[:, k, 0], 0).astype(np.float32), np.where(m0, c[:, k, 1], 0).astype(np.float32)
-        ix, wx, inx = warpref._axis(xv, W, mistake)
-        iy, wy, iny = warpref._axis(yv, H, mistake)
+        ix, wx, inx = splatref.axis(xv, W, mistake=mistake)
+        iy, wy, iny = splatref.axis(yv, H, mistake=mistake)
         for jy in range(2):
             for jx in range(2):
-                w = np.rint(np.ldexp((wx[jx] * wy[jy]).astype(np.float32), FIX_BITS)).astype(np.int64)
+                w = splatref.fixed_weight(wx[jx], wy[jy], FIX_BITS)
                 m = m0 & inx[jx] & iny[jy]
                 np.add.at(dsi[k], ((iy + jy)[m], (ix + jx)[m]), w[m])
     any_vote = valid.any(1) if D else np.zeros(N, bool)

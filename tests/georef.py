@@ -11,6 +11,7 @@ The checks: ``bound(floor, env)`` is the one tolerance rule of tests/test_geomet
 import numpy as np
 
 import oracle as orc
+import poseref
 
 ENV_FACTOR = 4.0             # as test_ba_matches_oracle: a device cosf / sinf / atanf a few ulp from the host's
 # unit-scale floors of test_se3_ops_match_oracle, per operator
@@ -56,12 +57,6 @@ def transform(poses, patches, intr, ii, jj, kk, tonly=False, want_z=False):
     return (out, X1[..., 2].reshape(E, P, P)) if want_z else out
 
 
-def _qrot_raw(q, v):
-    """v + w * uv + q x uv, uv = 2 q x v: the rotation formula of fastba, the quaternion taken as stored"""
-    uv = 2.0 * np.cross(q[..., :3], v)
-    return v + q[..., 3:4] * uv + np.cross(q[..., :3], uv)
-
-
 def reproject(poses, patches, intr, ii, jj, kk, want_z=False):
     """fastba's reproject (ramp/fastba/ba_cuda.cu:379-429) -> [1,E,2,P,P]: intrinsics row 0 for every frame, no clamp,
     quaternions as stored (not normalised)"""
@@ -75,10 +70,10 @@ def reproject(poses, patches, intr, ii, jj, kk, want_z=False):
     a, b = qj, qi * np.array([-1.0, -1.0, -1.0, 1.0])                       # q_ij = q_j q_i^-1
     qij = np.concatenate([a[:, 3:] * b[:, :3] + b[:, 3:] * a[:, :3] + np.cross(a[:, :3], b[:, :3]),
                           a[:, 3:] * b[:, 3:] - (a[:, :3] * b[:, :3]).sum(-1, keepdims=True)], -1)
-    tij = tj - _qrot_raw(qij, ti)
+    tij = tj - poseref.qrot(qij, ti)
     K0 = np.broadcast_to(intr[0], (E, 4))
     X0 = _unproject(patches[kk], K0)
-    X1 = _qrot_raw(qij[:, None, :], X0[..., :3]) + tij[:, None, :] * X0[..., 3:]
+    X1 = poseref.qrot(qij[:, None, :], X0[..., :3]) + tij[:, None, :] * X0[..., 3:]
     out = _project(X1, K0, clamp=False).reshape(1, E, 2, P, P)
     return (out, X1[..., 2].reshape(E, P, P)) if want_z else out
 

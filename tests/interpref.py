@@ -17,15 +17,9 @@ import numpy as np
 
 import georef
 import oracle as orc
+import poseref
 
 MISTAKES = ("right", "lower", "alpha32", "nlerp", "tlerp", "noclamp")
-
-
-def _ops(dtype):
-    if dtype == np.float64:
-        return orc.se3_exp_f64, orc.se3_log_f64, orc.se3_inv_f64, orc.se3_mul_f64
-    f = lambda fn: (lambda *a: fn(*[np.ascontiguousarray(x, np.float32) for x in a]))
-    return f(orc.se3_exp), f(orc.se3_log), f(orc.se3_inv), f(orc.se3_mul)
 
 
 def segment_of(times, query, side="right"):
@@ -58,7 +52,7 @@ def interpolate(knots, times, query, extrapolate=False, dtype=np.float64, mistak
         return np.full((Q, 7), np.nan, dtype), np.full((Q, 6), np.nan, dtype)
     nanq = np.isnan(query)
     q = np.where(nanq, times[0], query)
-    exp, log, inv, mul = _ops(dtype)
+    exp, log, inv, mul = poseref.se3_ops(dtype)
     s = segment_of(times, q, side="left" if mistake == "lower" else "right")
     a, dt = alpha_of(times, q, s, extrapolate, clamp=mistake != "noclamp")
     if mistake == "alpha32" and T > 1:              # alpha formed in fp32 from the absolute times

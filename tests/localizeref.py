@@ -16,7 +16,9 @@ import math
 
 import numpy as np
 
+import alignref
 import pointmapref as pm
+import poseref
 import renderref as rr
 
 H, W, K, CAM, VOXEL = rr.H, rr.W, rr.K, rr.CAM, rr.VOXEL
@@ -199,8 +201,8 @@ def _right_terms(r, gu, gv, Xc, cam, Kc, k):
     q = np.asarray(cam, f32).astype(np.float64)[3:]
     qi = q * np.array([-1.0, -1, -1, 1])
     c = np.asarray(cam, f32).astype(np.float64)[:3]
-    Xw = pm._qrot(q, Xc.astype(np.float64)) + c
-    jw = pm._qrot(q, J[:, :3])                                # dr/dXw
+    Xw = poseref.qrot(q, Xc.astype(np.float64)) + c
+    jw = poseref.qrot(q, J[:, :3])                                # dr/dXw
     Jr = np.concatenate([jw, np.cross(Xw, jw)], 1)
     rd = np.asarray(r, f32).astype(np.float64)
     rho, w = huber(rd, k)
@@ -266,11 +268,6 @@ def retract(C, delta, mistake=None):
             c2 - ((v2 + qw * u2) + (qx * u1 - qy * u0)), qx, qy, qz, qw]
 
 
-def to_f32(values):
-    with np.errstate(over="ignore", invalid="ignore"):
-        return np.asarray(values, np.float64).astype(f32)
-
-
 def _tri(i, j):
     return i * 6 - (i * (i - 1)) // 2 + (j - i)
 
@@ -325,7 +322,7 @@ class Machine:
             self.reason = CONVERGED
             return
         self.trial = retract(self.C, delta)
-        self.cam = to_f32(self.trial)
+        self.cam = alignref.f32(self.trial)
 
     def step(self, e, cost, H21, b, in_reach, status):
         if self.reason != 0:
@@ -394,18 +391,11 @@ def ref_evaluator(tab, voxel, Kc, surface, k=0.0, mistake=None, **kw):
 
 
 # -------------------------------------------------------------------------------------------------------------- inputs
-def q_mul(a, b):
-    ax, ay, az, aw = a
-    bx, by, bz, bw = b
-    return np.array([aw * bx + ax * bw + ay * bz - az * by, aw * by - ax * bz + ay * bw + az * bx,
-                     aw * bz + ax * by - ay * bx + az * bw, aw * bw - ax * bx - ay * by - az * bz])
-
-
 def pose_distance(a, b):
     """(translation distance, rotation angle) between two camera-to-world poses, float64"""
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     qa, qb = a[3:] / np.linalg.norm(a[3:]), b[3:] / np.linalg.norm(b[3:])
-    dq = q_mul(qa * [-1, -1, -1, 1], qb)
+    dq = poseref.qmul(qa * [-1, -1, -1, 1], qb)
     return float(np.linalg.norm(a[:3] - b[:3])), float(2 * math.atan2(np.linalg.norm(dq[:3]), abs(dq[3])))
 
 
@@ -514,7 +504,7 @@ def convergence_scene():
     x, y = u[ok].astype(f32), v[ok].astype(f32)
     t = s["t_ref"] - rng.uniform(0, s["tau"] / 5, len(x))
     surf = time_surface(x, y, t, s["t_ref"], s["tau"], s["h"], s["w"], s["smooth"])["surface"]
-    start = to_f32(retract(list(true32.astype(np.float64)), s["perturb"]))
+    start = alignref.f32(retract(list(true32.astype(np.float64)), s["perturb"]))
     _conv.update(inserts=ins, tab=tab, voxel=s["voxel"], K=s["K"], h=s["h"], w=s["w"], events=(x, y, t), t_ref=s["t_ref"], tau=s["tau"],
                  smooth=s["smooth"], surface=surf, true=true32, start=start, iters=s["iters"], huber=s["huber"])
     return _conv

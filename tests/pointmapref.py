@@ -13,6 +13,8 @@
 """
 import numpy as np
 
+import poseref
+
 AXIS = 1 << 20
 CONF_BITS = 16
 H, W = 13, 17
@@ -63,33 +65,17 @@ def masked_median(inv, det, r, s, mistake=None):
     return out, iso
 
 
-def _qrot(q, p):
-    """lt_qrot of csrc/ramp_device.h, in the dtype of its arguments"""
-    uv = np.stack([q[1] * p[..., 2] - q[2] * p[..., 1], q[2] * p[..., 0] - q[0] * p[..., 2], q[0] * p[..., 1] - q[1] * p[..., 0]], -1)
-    uv = uv + uv
-    return np.stack([p[..., 0] + q[3] * uv[..., 0] + (q[1] * uv[..., 2] - q[2] * uv[..., 1]),
-                     p[..., 1] + q[3] * uv[..., 1] + (q[2] * uv[..., 0] - q[0] * uv[..., 2]),
-                     p[..., 2] + q[3] * uv[..., 2] + (q[0] * uv[..., 1] - q[1] * uv[..., 0])], -1)
-
-
-def invert_pose(cam):
-    """the inverse of (t, q), float64, unit q"""
-    cam = np.asarray(cam, np.float64)
-    qi = cam[3:] * np.array([-1.0, -1.0, -1.0, 1.0])
-    return np.concatenate([-_qrot(qi, cam[None, :3])[0], qi])
-
-
 def lift(u, v, d, cam, Kc, dtype=np.float64, mistake=None):
     """world points [n,3] of pixels (u, v) with inverse depth d, in ``dtype`` (the inputs are the float32 words either way)"""
     assert mistake is None or mistake in LIFT_MISTAKES
     cam = np.asarray(cam, np.float32)
     if mistake == "w2c":
-        cam = invert_pose(cam).astype(np.float32)
+        cam = poseref.invert_pose(cam).astype(np.float32)
     c, k = cam.astype(dtype), np.asarray(Kc, np.float32).astype(dtype)
     with np.errstate(all="ignore"):
         z = dtype(1.0) / np.asarray(d, np.float32).astype(dtype)
         Xc = np.stack([((np.asarray(u).astype(dtype) - k[2]) / k[0]) * z, ((np.asarray(v).astype(dtype) - k[3]) / k[1]) * z, z], -1)
-        return (_qrot(c[3:], Xc) + c[:3]).astype(dtype)
+        return (poseref.qrot(c[3:], Xc) + c[:3]).astype(dtype)
 
 
 def depth_points(inv, cam, Kc, plane=None, confidence=None, r=2, s=3, min_invdepth=0.0, mistake=None):

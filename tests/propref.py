@@ -20,7 +20,7 @@ def make_anchor(t0, pbar0, q_wc0, v0, s, g, bias_g):
 
 
 def quat_mul(a, b):
-    """xyzw"""
+    """xyzw.  Not poseref.qmul: y and z are summed in another order here (last-bit differences), and this module needs no oracle"""
     return np.array([a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1], a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2],
                      a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0], a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2]])
 

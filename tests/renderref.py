@@ -13,6 +13,7 @@
 import numpy as np
 
 import pointmapref as pm
+import poseref
 
 MIN_Z = np.float32(0.2)                       # RAMP_WARP_MIN_Z
 H, W = pm.H, pm.W                             # 13 x 17
@@ -72,9 +73,9 @@ def project(points, cam, Kc, dtype=np.float32, mistake=None):
     X = np.asarray(points, np.float32).astype(dtype).reshape(-1, 3)
     with np.errstate(all="ignore"):
         if mistake == "w2c":                                 # the pose taken as world-to-camera
-            Xc = pm._qrot(cam[3:], X) + cam[:3]
+            Xc = poseref.qrot(cam[3:], X) + cam[:3]
         else:
-            Xc = pm._qrot(cam[3:] * np.array([-1, -1, -1, 1], dtype), X - cam[:3])
+            Xc = poseref.qrot(cam[3:] * np.array([-1, -1, -1, 1], dtype), X - cam[:3])
         d = dtype(1.0) / Xc[:, 2]
         u, v = k[0] * (Xc[:, 0] * d) + k[2], k[1] * (Xc[:, 1] * d) + k[3]
     return u.astype(dtype), v.astype(dtype), d.astype(dtype), Xc.astype(dtype)

@@ -10,6 +10,7 @@ import torch
 
 import localizeref as lr
 import pointmapref as pm
+import poseref
 import renderref as rr
 import scenes
 
@@ -60,7 +61,7 @@ def _cost64(tab, voxel, cam64, Kc, surface, k):
 
 def _project64(X, cam, Kc):
     k = np.asarray(Kc, np.float64)
-    Xc = pm._qrot(cam[3:] * np.array([-1.0, -1, -1, 1]), X.astype(np.float64) - cam[:3])
+    Xc = poseref.qrot(cam[3:] * np.array([-1.0, -1, -1, 1]), X.astype(np.float64) - cam[:3])
     d = 1.0 / Xc[:, 2]
     return k[0] * (Xc[:, 0] * d) + k[2], k[1] * (Xc[:, 1] * d) + k[3], d, Xc
 
@@ -94,7 +95,7 @@ def test_the_cayley_retraction_is_the_exponential_to_second_order_and_the_identi
     errs = []
     for s in (1e-1, 1e-2):
         D = scenes.se3_exp_np(s * xi).astype(np.float64)      # (t, q) of Exp(xi)
-        Di = pm.invert_pose(D)
+        Di = poseref.invert_pose(D)
         got = np.asarray(lr.retract([0, 0, 0, 0, 0, 0, 1.0], s * xi))   # I D^-1
         errs.append(np.abs(got - Di * np.sign(Di[6]) * np.sign(got[6])).max())
     assert errs[0] < 2e-3 and errs[1] < errs[0] / 50, errs    # the difference is of third order in the step (float32 oracle floor)
@@ -337,7 +338,7 @@ def test_the_host_log_inverts_the_exponential():
 
     def compose(a, b):                                        # a b as (t, q)
         qa, qb = a[3:], b[3:]
-        return np.r_[a[:3] + pm._qrot(qa, b[None, :3])[0], lr.q_mul(qa, qb)]
+        return np.r_[a[:3] + poseref.qrot(qa, b[None, :3])[0], poseref.qmul(qa, qb)]
 
     a = np.array([0.3, -0.2, 0.5, 0.18257419, -0.36514837, 0.54772256, 0.73029674])
     a[3:] /= np.linalg.norm(a[3:])

@@ -114,14 +114,14 @@ def _one_update_vs_cpu_oracle(mode, preset, H, W, sd, cfgk, legs=(False,), w_bia
                                   kk=kk.numpy().copy(), t0=int(t0), t1=int(t1), iterations=int(iterations)))
                 return _ba(poses, patches, intrinsics, target, weight, lmbda, ii, jj, kk, t0, t1, iterations, info, **kw)
             _ops.ba = spy
-        ref = cpu_tracker(make_cfg(preset, **dict(cfgk, MIXED_PRECISION=False)),
-                          make_network(mode, device="cpu", w_bias=w_bias), {"event_bias": True}, ht=H, wd=W)
-        ref.load_state_dict(f32)
-        ref.update()
-        r_poses = ref.poses_[:n].numpy().copy()
-        r_depth = ref.patches_[:n, :, 2, 1, 1].numpy().copy()
-        r_net = ref.net[0].float().numpy().copy()
-        r_w = ref.last_weight.numpy().copy()
+        host = cpu_tracker(make_cfg(preset, **dict(cfgk, MIXED_PRECISION=False)),
+                           make_network(mode, device="cpu", w_bias=w_bias), {"event_bias": True}, ht=H, wd=W)
+        host.load_state_dict(f32)
+        host.update()
+        r_poses = host.poses_[:n].numpy().copy()
+        r_depth = host.patches_[:n, :, 2, 1, 1].numpy().copy()
+        r_net = host.net[0].float().numpy().copy()
+        r_w = host.last_weight.numpy().copy()
     pol = None
     if policy:
         # the same step on the CPU oracle WITH the shipped precision policy's rounding points (oracle/host_cpu.py::
@@ -152,7 +152,7 @@ def _one_update_vs_cpu_oracle(mode, preset, H, W, sd, cfgk, legs=(False,), w_bia
     for mixed in legs:
         slam = Ramp_vo(make_cfg(preset, **dict(cfgk, MIXED_PRECISION=mixed)), net, {"event_bias": True}, ht=H, wd=W)
         slam.load_state_dict(sd)
-        assert np.array_equal(slam._ii, ref._ii) and np.array_equal(slam._kk, ref._kk)
+        assert np.array_equal(slam._ii, host._ii) and np.array_equal(slam._kk, host._kk)
         slam.update()
         g_poses = slam.poses_[:n].cpu().numpy()
         g_depth = slam.patches_[:n, :, 2, 1, 1].cpu().numpy()

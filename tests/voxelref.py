@@ -17,6 +17,8 @@ import os
 
 import numpy as np
 
+import splatref
+
 FIX_BITS = 24
 FIX = float(1 << FIX_BITS)
 MISTAKES = ("minmax", "swap", "biased", "round", "allcells", "rightedge")
@@ -24,16 +26,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "eve
 CASES = ("random", "three", "onebin", "equal_times", "cancel")
 BAD_OFFSETS, BAD_TIMES = 1, 2
 f32 = np.float32
-
-
-def _axis(v, n):
-    """warp_axis of csrc/warp_device.h: floor, the weights 1 - w and w in fp32, whether each neighbour lies in [0, n)"""
-    fl = np.floor(v).astype(f32)
-    w = (v - fl).astype(f32)
-    w0 = (f32(1.0) - w).astype(f32)
-    in0 = (fl >= 0) & (fl <= n - 1)
-    in1 = (fl >= -1) & (fl <= n - 2)
-    return np.where(in0 | in1, fl, 0).astype(np.int64), (w0, w), (in0, in1)
 
 
 def votes(x, y, t, p, H, W, bins, subpixel=False, mistake=None):
@@ -58,8 +50,8 @@ def votes(x, y, t, p, H, W, bins, subpixel=False, mistake=None):
     fin = np.isfinite(x) & np.isfinite(y) & np.isfinite(t)
     xs, ys = np.where(fin, x, 0).astype(f32), np.where(fin, y, 0).astype(f32)
     if subpixel:
-        ix, wx, inx = _axis(xs, W)
-        iy, wy, iny = _axis(ys, H)
+        ix, wx, inx = splatref.axis(xs, W)
+        iy, wy, iny = splatref.axis(ys, H)
         inside = ((inx[0] & (wx[0] != 0)) | (inx[1] & (wx[1] != 0))) & ((iny[0] & (wy[0] != 0)) | (iny[1] & (wy[1] != 0)))
     else:
         xt, yt = (np.rint(xs), np.rint(ys)) if mistake == "round" else (np.trunc(xs), np.trunc(ys))

@@ -20,19 +20,13 @@ import numpy as np
 
 import georef
 import interpref
-import oracle as orc
+import poseref
+import splatref
 
 MIN_Z = 0.2                  # RAMP_WARP_MIN_Z
 FIX_BITS = 24
 WARP_MISTAKES = ("fxfy", "inverse")
 SCATTER_MISTAKES = ("trunc", "bin")
-
-
-def _qrot(q, v):
-    """lietorch's rotation of v by the unit quaternion q (x, y, z, w), in the dtype of the inputs"""
-    two = q.dtype.type(2)
-    uv = two * np.cross(q[..., :3], v)
-    return v + q[..., 3:4] * uv + np.cross(q[..., :3], uv)
 
 
 def sample_depth(invdepth, x, y, H, W):
@@ -46,24 +40,21 @@ def sample_depth(invdepth, x, y, H, W):
     return d.reshape(H, W)[py, px]
 
 
-def warp(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate=False, dtype=np.float64, mistake=None):
-    """-> (xy [N,2] in ``dtype`` with NaN rows for invalid events, Z' [N])"""
-    assert mistake is None or mistake in WARP_MISTAKES
+def event_rays(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate, dtype, mistake=None):
+    """what the warp and the contrast share, in ``dtype``: x, y read as float32 and t as float64 -> (fin: the events that are
+    finite; tq: their time stamps, times[0] for the others; G [N,7] = C(t_ref)^-1 C(tq); the rays P [N,3]; the inverse depths
+    d [N]; (fx, fy, cx, cy)).  None: time stamps that decrease or are not finite"""
     x32, y32 = np.asarray(x, np.float32).reshape(-1), np.asarray(y, np.float32).reshape(-1)
     t = np.asarray(t, np.float64).reshape(-1)
     N = len(x32)
     times = np.asarray(times, np.float64).reshape(-1)
     if not np.isfinite(times).all() or (np.diff(times) < 0).any():
-        return np.full((N, 2), np.nan, dtype), np.full(N, np.nan, dtype)
+        return None
     fin = np.isfinite(x32) & np.isfinite(y32) & np.isfinite(t)
     tq = np.where(fin, t, times[0])
     C, _ = interpref.interpolate(knots, times, tq, extrapolate, dtype)
     Cr, _ = interpref.interpolate(knots, times, np.array([t_ref]), extrapolate, dtype)
-    if dtype == np.float64:
-        inv, mul = orc.se3_inv_f64, orc.se3_mul_f64
-    else:
-        f = lambda fn: (lambda *a: fn(*[np.ascontiguousarray(v, np.float32) for v in a]))
-        inv, mul = f(orc.se3_inv), f(orc.se3_mul)
+    _, _, inv, mul = poseref.se3_ops(dtype)
     Crn = np.repeat(np.asarray(Cr, dtype), N, 0)
     C = np.asarray(C, dtype)
     G = np.asarray(mul(inv(C), Crn) if mistake == "inverse" else mul(inv(Crn), C), dtype)
@@ -72,8 +63,19 @@ def warp(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate=False, dty
     xs, ys = np.where(fin, x32, 0).astype(dtype), np.where(fin, y32, 0).astype(dtype)
     d = sample_depth(invdepth, x32, y32, H, W).astype(dtype)
     P = np.stack([(xs - cx) / ux, (ys - cy) / uy, np.ones(N, dtype)], -1)
+    return fin, tq, G, P, d, (fx, fy, cx, cy)
+
+
+def warp(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate=False, dtype=np.float64, mistake=None):
+    """-> (xy [N,2] in ``dtype`` with NaN rows for invalid events, Z' [N])"""
+    assert mistake is None or mistake in WARP_MISTAKES
+    rays = event_rays(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate, dtype, mistake)
+    if rays is None:
+        N = np.asarray(x).size
+        return np.full((N, 2), np.nan, dtype), np.full(N, np.nan, dtype)
+    fin, _, G, P, d, (fx, fy, cx, cy) = rays
     with np.errstate(all="ignore"):
-        X = _qrot(G[:, 3:], P) + G[:, :3] * d[:, None]
+        X = poseref.qrot(G[:, 3:], P) + G[:, :3] * d[:, None]
         Z = X[:, 2]
         xy = np.stack([fx * (X[:, 0] / Z) + cx, fy * (X[:, 1] / Z) + cy], -1)
         bad = ~fin | ~(Z > dtype(MIN_Z)) | ~np.isfinite(xy).all(-1)
@@ -82,13 +84,12 @@ def warp(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate=False, dty
     return xy.astype(dtype), Z.astype(dtype)
 
 
-def compare(xy_gpu, x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate=False, z_margin=1e-4):
-    """the GPU test's check of one launch.  err: largest coordinate difference from the float64 restatement over the rows
-    both call valid; env: the float32 restatement's own; bound = georef.bound(PIXEL_FLOOR x largest |coordinate|, env).  The
-    NaN rows have to agree except where float64's Z' is within ``z_margin`` of MIN_Z."""
-    r64, z64 = warp(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate, np.float64)
-    r32, _ = warp(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate, np.float32)
-    out = np.asarray(xy_gpu, np.float64)
+def compare_coords(out, r64, z64, r32, z_margin):
+    """the check of coordinates [..., 2] (NaN: invalid) against the float64 restatement ``r64`` with its ``z64``.  err: largest
+    coordinate difference over the entries both call valid; env: the float32 restatement's own (``r32``); bound =
+    georef.bound(PIXEL_FLOOR x largest |coordinate|, env).  The NaN entries have to agree except where float64's Z' is within
+    ``z_margin`` of MIN_Z."""
+    out = np.asarray(out, np.float64)
     v64, v32, vg = ~np.isnan(r64).any(-1), ~np.isnan(r32).any(-1), ~np.isnan(out).any(-1)
     edge = np.abs(z64 - MIN_Z) < z_margin
     nan_ok = bool(((vg == v64) | edge).all())
@@ -101,17 +102,14 @@ def compare(xy_gpu, x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate
     return dict(err=err, env=env, floor=floor, bound=b, nan_ok=nan_ok, n_valid=int(keep.sum()), ok=nan_ok and err <= b)
 
 
+def compare(xy_gpu, x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate=False, z_margin=1e-4):
+    """the GPU test's check of one launch: ``compare_coords`` against this restatement"""
+    r64, z64 = warp(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate, np.float64)
+    r32, _ = warp(x, y, t, knots, times, t_ref, K, invdepth, H, W, extrapolate, np.float32)
+    return compare_coords(xy_gpu, r64, z64, r32, z_margin)
+
+
 # ------------------------------------------------------------------------------------------------------------ the splat
-def _axis(v, n, mistake=None):
-    fl = (np.trunc(v) if mistake == "trunc" else np.floor(v)).astype(np.float32)
-    w = (v - fl).astype(np.float32)
-    w0 = (np.float32(1.0) - w).astype(np.float32)
-    in0 = (fl >= 0) & (fl <= n - 1)
-    in1 = (fl >= -1) & (fl <= n - 2)
-    i0 = np.where(in0 | in1, fl, 0).astype(np.int64)
-    return i0, (w0, w), (in0, in1)
-
-
 def bins_of(index, N, bins):
     """event i -> int32(float32(bins) * float32(i) / float32(N)), capped at bins - 1"""
     b = ((np.float32(bins) * np.asarray(index).astype(np.float32)) / np.float32(N)).astype(np.int32)
@@ -129,8 +127,8 @@ def scatter(xy, p, H, W, bins=0, index=None, mistake=None):
     valid = ~np.isnan(xy).any(-1)
     xv = np.where(valid, xy[:, 0], 0).astype(np.float32)
     yv = np.where(valid, xy[:, 1], 0).astype(np.float32)
-    ix, wx, inx = _axis(xv, W, mistake)
-    iy, wy, iny = _axis(yv, H, mistake)
+    ix, wx, inx = splatref.axis(xv, W, mistake=mistake)
+    iy, wy, iny = splatref.axis(yv, H, mistake=mistake)
     iwe = np.zeros((2, H, W), np.int64)
     stack = np.zeros((bins, H, W), np.int64) if bins else None
     b = bins_of(np.arange(N) if index is None else index, N, bins) if bins else None
@@ -140,7 +138,7 @@ def scatter(xy, p, H, W, bins=0, index=None, mistake=None):
     wsum = np.zeros(N, np.int64)
     for jy in range(2):
         for jx in range(2):
-            c = np.rint(np.ldexp((wx[jx] * wy[jy]).astype(np.float32), FIX_BITS)).astype(np.int64)
+            c = splatref.fixed_weight(wx[jx], wy[jy], FIX_BITS)
             wsum += np.where(valid, c, 0)
             m = valid & inx[jx] & iny[jy]
             yy, xx = (iy + jy)[m], (ix + jx)[m]
