@@ -259,6 +259,8 @@ int ramp_shift_rows(void *const *base_host, const long *row_bytes_host, const in
 /* group the E edges by an int64 key (device-side replacement of the
  * torch.unique / torch::_unique / std::stable_sort host round trips at
  * ramp/blocks.py:43, ramp/fastba/ba_cuda.cu:447, ramp/fastba/ba.cpp:59-97).
+ *   keys      : 0 <= key < 2^63 (the sort ignores bit 63: a negative key is a contract violation, and so is a
+ *               key at or above a given key_bound)
  *   key_bound : exclusive upper bound of the keys (0 = unknown: full 63 bits)
  *   order[E]      edge indices sorted by (key, edge index)  (stable)
  *   gid[E]        dense rank of the edge's key among the sorted unique keys
@@ -410,16 +412,19 @@ int ramp_map_select(const float *point_cov, const float *depth_var, const float 
 
 /* group-by for a SMALL key range known to the caller: key = a[e]*mul + (b ? b[e] : 0) - sub must lie
  * in [0, K).  Histogram + one-workgroup scan + scatter + per-segment rank sort (5 short kernels vs a
- * radix sort); same outputs and the same (stable) ordering as ramp_group_by.  ukeys = key + sub.  */
+ * radix sort); same outputs and the same (stable) ordering as ramp_group_by.  ukeys = key + sub.
+ * max_groups is an upper bound on G (fewer is a contract violation), and 0 means min(K, E).
+ * A key outside [0, K) makes the call yield the empty grouping: *ngroups == 0 and seg_start[0] == 0, so every
+ * consumer launches over no group; the other outputs then hold anything, inside their extents.  */
 size_t ramp_group_by_small_workspace_bytes(int E, int K);
 int ramp_group_by_small(const int64_t *a, const int64_t *b, int64_t mul, int64_t sub, int K, int E,
                         int32_t *order, int32_t *gid, int32_t *seg_start, int64_t *ukeys,
                         int32_t *ngroups, int max_groups, void *ws, size_t ws_bytes, void *stream);
 
 /* cuda_ba.neighbors derived from the per-kk groups (no second sort): every group's edges are
- * ranked by (jj, edge index).  Groups longer than 1024 edges are left untouched (use
- * ramp_neighbors for such graphs).  kj_order (optional, int32 [E]): the factors in that (kk, jj) order -- a
- * factor's temporal neighbours are its neighbours in this list.                                    */
+ * ranked by (jj, edge index), whatever the group's length.  max_groups: an upper bound on *ngroups.
+ * kj_order (optional, int32 [E]): the factors in that (kk, jj) order -- a factor's temporal neighbours are its
+ * neighbours in this list.                                                                          */
 int ramp_neighbors_from_groups(const int32_t *order, const int32_t *seg_start, const int32_t *ngroups,
                                const int64_t *jj, int64_t *ix, int64_t *jx, int32_t *kj_order, int E,
                                int max_groups, void *stream);

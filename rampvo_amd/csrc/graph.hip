@@ -185,6 +185,7 @@ __global__ void __launch_bounds__(128)
 // key = a[e]*mul + (b ? b[e] : 0) - sub in [0, K).  histogram -> single-workgroup scan ->
 // scatter -> per-group rank sort by edge index (restores the stable order).  5 short kernels
 // instead of a radix sort's ~12; used when the caller knows a tight key range (the tracker does).
+// A key outside [0, K) raises `bad` in the histogram; the scan then publishes the empty grouping.
 __device__ __forceinline__ long gbc_key(const int64_t *a, const int64_t *b, long mul, long sub, int e) {
   return a[e] * mul + (b ? b[e] : 0) - sub;
 }
@@ -220,9 +221,12 @@ __global__ void __launch_bounds__(256)
 __global__ void __launch_bounds__(1024)
     gbc_scan_kernel(int32_t *__restrict__ hist, int32_t *__restrict__ gidmap, int32_t *__restrict__ seg_start,
                     int64_t *__restrict__ ukeys, int32_t *__restrict__ ngroups, int K, int E, long sub,
-                    long mul_is_pair) {
+                    const int32_t *__restrict__ bad) {
   __shared__ int s_cnt[1024], s_grp[1024];
   const int tid = threadIdx.x;
+  // a key outside [0, K) (the histogram finished writing the flag on this stream): the empty grouping.  The cursors and the
+  // group-id map are still written, so the scatter stays inside tmp_order and gid; the consumers launch over no group.
+  const bool refuse = *bad != 0;
   const int per = (K + 1023) / 1024;
   const int k0 = tid * per, k1 = min(K, k0 + per);
   int c = 0, g = 0;
@@ -242,15 +246,21 @@ __global__ void __launch_bounds__(1024)
     hist[k] = oc;               // becomes the scatter cursor
     if (h > 0) {
       gidmap[k] = og;
-      seg_start[og] = oc;
-      if (ukeys) ukeys[og] = (int64_t)k + sub;
+      if (!refuse) {
+        seg_start[og] = oc;
+        if (ukeys) ukeys[og] = (int64_t)k + sub;
+      }
       og++;
     } else {
       gidmap[k] = -1;
     }
     oc += h;
   }
-  if (tid == 1023) { *ngroups = s_grp[1023]; seg_start[s_grp[1023]] = E; }
+  if (tid == 1023) {
+    const int ng = refuse ? 0 : s_grp[1023];
+    *ngroups = ng;
+    seg_start[ng] = refuse ? 0 : E;
+  }
 }
 // (the order inside a segment is arbitrary here either way; gbc_segsort_kernel restores it)
 template <bool LDS>
@@ -302,6 +312,7 @@ __global__ void __launch_bounds__(64)
   }
 }
 // temporal neighbours from the per-patch groups: rank each edge of a group by (jj, edge index)
+__device__ __forceinline__ bool nb_before(long jf, int f, long j, int e) { return (jf < j) || (jf == j && f < e); }
 __global__ void __launch_bounds__(64)
     nb_from_groups_kernel(const int32_t *__restrict__ order, const int32_t *__restrict__ seg_start,
                           const int32_t *__restrict__ ngroups, const int64_t *__restrict__ jj,
@@ -310,15 +321,37 @@ __global__ void __launch_bounds__(64)
   const int g = blockIdx.x;
   if (g >= *ngroups) return;
   const int s0 = seg_start[g], n = seg_start[g + 1] - s0;
-  if (n > 1024) return;   // host falls back to the sort-based path for such graphs
+  if (n > 1024) {
+    // longer than the staging: the one pass over the group that ranks an edge also finds the closest edge before it and the
+    // closest after it under the same order
+    for (int p = threadIdx.x; p < n; p += 64) {
+      const int e = order[s0 + p];
+      const long j = jj[e];
+      int r = 0, prev = -1, next = -1;
+      long jprev = 0, jnext = 0;
+      for (int q = 0; q < n; q++) {
+        const int f = order[s0 + q];
+        const long jf = jj[f];
+        if (nb_before(jf, f, j, e)) {
+          r++;
+          if (prev < 0 || nb_before(jprev, prev, jf, f)) { prev = f; jprev = jf; }
+        } else if (f != e) {
+          if (next < 0 || nb_before(jf, f, jnext, next)) { next = f; jnext = jf; }
+        }
+      }
+      ix[e] = prev;
+      jx[e] = next;
+      if (kj) kj[s0 + r] = e;
+    }
+    return;
+  }
   for (int p = threadIdx.x; p < n; p += 64) {
     const int e = order[s0 + p];
     const long j = jj[e];
     int r = 0;
     for (int q = 0; q < n; q++) {
       const int f = order[s0 + q];
-      const long jf = jj[f];
-      r += (jf < j) || (jf == j && f < e);
+      r += nb_before(jj[f], f, j, e);
     }
     s_sorted[r] = e;
   }
@@ -692,7 +725,7 @@ int ramp_group_by_small(const int64_t *a, const int64_t *b, int64_t mul, int64_t
   else
     hipLaunchKernelGGL(gbc_hist_kernel<false>, dim3(nb), dim3(256), 0, st, a, b, (long)mul, (long)sub, hist, E, K, bad);
   hipLaunchKernelGGL(gbc_scan_kernel, dim3(1), dim3(1024), 0, st, hist, gidmap, seg_start, ukeys, ngroups, K, E,
-                     (long)sub, 0L);
+                     (long)sub, bad);
   if (lds)
     hipLaunchKernelGGL(gbc_scatter_kernel<true>, dim3(nb), dim3(256), 0, st, a, b, (long)mul, (long)sub, hist, gidmap,
                        tmp, gid, E, K);

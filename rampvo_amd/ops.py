@@ -1752,7 +1752,8 @@ def group_by(keys, key_bound=0):
 
 
 def group_by_small(a, b, mul, sub, K, max_groups=0):
-    """group_by for keys a*mul + b - sub known to lie in [0, K) (counting sort, 5 short kernels)"""
+    """group_by for keys a*mul + b - sub known to lie in [0, K) (counting sort, 5 short kernels); a key outside the
+    range gives the empty grouping (ngroups 0).  max_groups: an upper bound on the number of groups, 0 = min(K, E)"""
     require_cuda(a)
     a = _idx(a)
     b = _idx(b) if b is not None else None
