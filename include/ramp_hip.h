@@ -1822,6 +1822,76 @@ int ramp_event_filter(const void *x, const void *y, const double *t, long N, int
                       double *last_t_out, uint8_t *keep_out, float *xy_out, int32_t *index_out, int64_t *count_out,
                       uint8_t *hot_out, double *stats_out, int32_t *status, void *ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------- event optical flow (csrc/flow.hip)
+ *
+ * ramp_event_flow: how the image moves at each event, without a trajectory and without a depth -- per event a plane fitted to
+ * the surface of active events around it at its own time (Benosman et al., "Event-based visual flow", TNNLS 2014).  The result
+ * is the NORMAL flow.  Order-independent and bit-exact: every rounding below is fixed.
+ *   Events: x, y [N] fp32, or int32 with RAMP_FLOW_XY_I32; t [N] float64; p [N] int8, optional (NULL).  The pixel is the
+ *   coordinate truncated toward zero, and the finiteness and range tests are ramp_event_filter's: class [2] is an event that is
+ *   not finite, class [3] an event outside the sensor, the rest are CANDIDATES.
+ *   Surfaces: without p one; with p two (p > 0 is plane 1, else plane 0), and an event sees only its own plane.  With S the
+ *   number of planes a CELL is (plane, pixel), its key plane * H * W + pixel.
+ *   Order: within a cell the order of the indices; every cell's time stamps must not decrease in that order.  Across cells e'
+ *   PRECEDES e when (t', i') < (t, i) lexicographically (ramp_event_filter's rule).
+ *   State: last_t_in, optional float64 [S][H][W], NaN meaning none: one virtual event per cell that precedes the call's.
+ *   last_t_out: per cell the last candidate's time stamp, else the input's value; written by a launch of its own, so
+ *   last_t_out == last_t_in is allowed.  With S = 1 it is the array of ramp_event_filter's and ramp_time_surface's last_t.
+ *   Points: for a candidate at (qx, qy) with (t, i), every offset j = (dy + r) * (2r + 1) + (dx + r), dx, dy in -r .. r, r in
+ *   1 .. 3, in ascending j.  The centre is always a point with s = 0 (the event overwrites its own surface entry: its own
+ *   predecessor takes no part).  A neighbour outside the sensor is skipped.  Otherwise t_nb = the time stamp of the last
+ *   candidate of cell (own plane, neighbour pixel) that precedes the event, else that cell's state, else none; with
+ *   delta = t - t_nb (one float64 subtraction) the neighbour is a point with s = -delta when delta <= window_dt (a NaN
+ *   compares false).
+ *   Fit: n, Sx, Sy, Sxx, Sxy, Syy are exact integers over the points; Sxs = sum (double)dx * s, Sys = sum (double)dy * s,
+ *   Ss = sum s in float64, without FMA, added in ascending j from +0 (a skipped offset adds nothing).  The int64 cofactors
+ *     C00 = Syy n - Sy Sy    C01 = Sx Sy - Sxy n    C02 = Sxy Sy - Syy Sx
+ *     C11 = Sxx n - Sx Sx    C12 = Sxy Sx - Sxx Sy   C22 = Sxx Syy - Sxy Sxy        D = Sxx C00 + Sxy C01 + Sx C02
+ *   Class [4] when n < min_points, class [5] when D == 0.  Otherwise, each integer converted exactly,
+ *     a = ((C00 Sxs + C01 Sys) + C02 Ss) / D    b = ((C01 Sxs + C11 Sys) + C12 Ss) / D    c = ((C02 Sxs + C12 Sys) + C22 Ss) / D
+ *   Refinement (refine in 0 .. 2 passes): a non-centre point is dropped when fabs(s - ((a * dx + b * dy) + c)) > outlier_dt,
+ *   all points tested against the same fit.  Nothing dropped: the passes end.  Otherwise the sums and the fit are recomputed
+ *   over the remaining points, with the same two class tests.
+ *   Flow: g2 = a * a + b * b, vx = a / g2, vy = b / g2.  Class [6] ("flat") when g2 is not positive, when vx or vy is not
+ *   finite, or when vx * vx + vy * vy > max_speed * max_speed (max_speed = +inf is allowed).  Everything else is valid, class
+ *   [7].  The first class that applies, [2] to [7], is the one counted.
+ *   Outputs (optional ones NULL; flow and status are required):
+ *     flow [N][2] fp32, 8-byte aligned: (float)vx, (float)vy in pixels per unit of t; every row that is not class [7] is NaN.
+ *     cls [N] uint8: the class.  n_used [N] uint8: the final n, 0 for classes [2] and [3].  fit [N][3] float64: a, b, c, NaN
+ *     where the final fit was not formed (classes [2] to [5]).
+ *     flow_map [2][H][W] fp32 and map_index [H][W] int32 (both or neither): per pixel the flow and the index of the valid event
+ *     with the LARGEST INDEX at that pixel, over both planes; NaN and -1 without one.  An int32 atomicMax of the index, then a
+ *     resolve pass with one writer per pixel.
+ *     last_t_out.  status: device int32 [8]: [0] bit 0 RAMP_FLOW_BAD_ORDER, [1] events, [2] .. [7] the class counts;
+ *     [2] + ... + [7] = [1].
+ *   RAMP_FLOW_BAD_ORDER (a cell's candidates decrease in time in index order, or its first candidate lies before its state) is
+ *   an outcome of the data (RAMP_OK), never a plausible number: flow, fit, flow_map and last_t_out are NaN, map_index is -1,
+ *   every cls and n_used is 0, [4] .. [7] are 0 ([1] .. [3] are still counted).
+ *   Launches, all on `stream`, nothing synchronised, no floating-point atomics, every loop a binary search or of fixed length:
+ *   memsets; the key kernel; a STABLE radix sort of (cell, index) over ceil(log2(S H W + 1)) bits (hipcub); the segment kernel;
+ *   the time-stamp gather with the order check; the fit kernel, one lane per sorted position, templated on r ((2r + 1)^2 - 1
+ *   binary searches, the points' s in an LDS slab [j][lane], the used set a 64-bit mask; 256 lanes per workgroup, 128 at
+ *   r = 3); the state, map and status launch.  The result is a function of the input alone: a call repeats its bits.
+ *   N == 0: RAMP_OK, no kernel is launched: status is zeroed, flow_map is NaN and map_index -1, last_t_in is copied to
+ *   last_t_out when both are given and differ -- S planes, S = 2 when p is not NULL -- (last_t_out without last_t_in is left
+ *   as it is).
+ *   RAMP_EINVAL: r outside 1 .. 3, min_points outside 3 .. (2r + 1)^2, refine outside 0 .. 2, window_dt or outlier_dt negative
+ *   or NaN, max_speed NaN or <= 0, N < 0, H or W < 1, unknown flags, a NULL status (N > 0: flow / x / y / t / ws), one of
+ *   flow_map / map_index without the other, flow, fit, last_t_in or last_t_out not 8-byte aligned, status, flow_map or map_index
+ *   not 4-byte aligned, ws not 16-byte aligned.  RAMP_EUNSUPPORTED: N >= 2^31 or 2 H W >= 2^31 - 1.  RAMP_EWORKSPACE: ws_bytes
+ *   below ramp_event_flow_ws_bytes(N, H, W, planes) (planes: 1 without p, 2 with; 0 for sizes that are refused).  A refused call
+ *   touches nothing.
+ * ramp_event_flow_grid_events(): the number of events one trip of the full grid covers at r <= 2 (half of it at r = 3); above
+ * it the workgroups take a second trip.                                                                                 */
+#define RAMP_FLOW_XY_I32 1
+#define RAMP_FLOW_BAD_ORDER 1 /* status[0] bit 0: the value of RAMP_FILTER_BAD_ORDER */
+size_t ramp_event_flow_ws_bytes(long N, int H, int W, int planes);
+long ramp_event_flow_grid_events(void);
+int ramp_event_flow(const void *x, const void *y, const double *t, const int8_t *p, long N, int H, int W, int flags, int r,
+                    double window_dt, int min_points, int refine, double outlier_dt, double max_speed, const double *last_t_in,
+                    double *last_t_out, float *flow, uint8_t *cls, uint8_t *n_used, double *fit, float *flow_map,
+                    int32_t *map_index, int32_t *status, void *ws, size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------- IMU: preintegration and alignment (csrc/imu.hip)
  *
  * A monocular trajectory has an arbitrary unit and no notion of down.  These entries take raw IMU samples and the trajectory as

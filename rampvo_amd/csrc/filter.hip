@@ -6,7 +6,7 @@
 //   flt_key_kernel        one lane per event and trip: classes [2], [3]; the key is the pixel index of a candidate, H W otherwise
 //   hipcub SortPairs      stable radix sort of (key, event index) over ceil(log2(H W + 1)) bits: every pixel's candidates become
 //                         one segment, in index order
-//   flt_segment_kernel    one lane per pixel: the segment's start, a binary search over the sorted keys (counts are differences)
+//   ord_segment_kernel    one lane per pixel: the segment's start, a binary search over the sorted keys (counts are differences)
 //   flt_hot_sums_kernel   per sorted position the time stamp (gathered once into ts[]) and the order check -- the neighbour in
 //                         the segment, the segment's first entry against the state --; per pixel n and S2 as integer sums
 //   flt_hot_mask_kernel   the threshold in float64 (no FMA), the mask, the stats row
@@ -22,19 +22,10 @@
 // event" is a partition point.
 #include "workspace_cub.h"
 #include "ramp_internal.h"
-#include "interp_device.h"
+#include "order_device.h"                // the order stage shared with flow.hip: candidate test, segments, the search
 
-#define FLT_MAX_GROUPS 2048              // workgroups per launch; each walks the tiles of INTERP_THREADS with this stride
 #define FLT_WAVES (INTERP_THREADS / RAMP_WAVE)
 #define FLT_CTR_WORDS 16                 // int32: the 8 status words, 8 spare; behind them two int64: n, S2
-#define FLT_FLT_MAX 3.4028234663852886e38f
-
-static __device__ __forceinline__ double flt_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-template <bool I32>
-static __device__ __forceinline__ float flt_coord(const void *__restrict__ v, long i) {
-  return I32 ? (float)static_cast<const int32_t *>(v)[i] : static_cast<const float *>(v)[i];
-}
 
 template <bool I32>
 __global__ void __launch_bounds__(INTERP_THREADS)
@@ -49,15 +40,11 @@ __global__ void __launch_bounds__(INTERP_THREADS)
     const bool have = i < N;
     bool bad = false, outside = false;
     if (have) {
-      const float x = flt_coord<I32>(xv, i), y = flt_coord<I32>(yv, i);
+      const float x = ord_coord<I32>(xv, i), y = ord_coord<I32>(yv, i);
       uint32_t k = HW;
-      if (!(fabsf(x) <= FLT_FLT_MAX && fabsf(y) <= FLT_FLT_MAX && interp_finite(t[i]))) {
-        bad = true;
-      } else {
-        const float xt = truncf(x), yt = truncf(y);      // (the range test is made in float, as ramp_event_voxel makes it)
-        if (xt >= 0.0f && xt <= (float)(W - 1) && yt >= 0.0f && yt <= (float)(H - 1)) k = (uint32_t)(int)yt * (uint32_t)W + (uint32_t)(int)xt;
-        else outside = true;
-      }
+      const int c = ord_pixel(x, y, t[i], H, W, &k);
+      bad = c == 2;
+      outside = c == 3;
       key[i] = k;
       iota[i] = (int32_t)i;
     }
@@ -66,22 +53,6 @@ __global__ void __launch_bounds__(INTERP_THREADS)
     n_out += ramp_wave_count(outside);
   }
   ramp_wave_flush(ctr + 1, tid, n_seen, n_bad, n_out);
-}
-
-// start[q] = the number of sorted keys below q, for q in [0, H W + 1]: the segment of pixel q is [start[q], start[q + 1])
-__global__ void __launch_bounds__(INTERP_THREADS)
-    flt_segment_kernel(const uint32_t *__restrict__ skey, int N, uint32_t HW, int32_t *__restrict__ start) {
-  const long tiles = ((long)HW + 2 + INTERP_THREADS - 1) / INTERP_THREADS;
-  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const long q = tile * INTERP_THREADS + threadIdx.x;
-    if (q > (long)HW + 1) continue;
-    int lo = 0, hi = N;
-    while (lo < hi) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if ((long)skey[mid] < q) lo = mid + 1; else hi = mid;
-    }
-    start[q] = lo;
-  }
 }
 
 // lanes [0, N): sorted positions -- ts[] and the order check; lanes [0, H W): pixels -- n and S2
@@ -101,7 +72,7 @@ __global__ void __launch_bounds__(INTERP_THREADS)
       const double ti = t[sidx[i]];
       ts[i] = ti;
       if (k < HW) {
-        double before = flt_nan();                         // (NaN: nothing in front, the comparison is false)
+        double before = ord_nan();                         // (NaN: nothing in front, the comparison is false)
         if (i > 0 && skey[i - 1] == k) before = t[sidx[i - 1]];
         else if (last_in) before = last_in[k];
         bad = bad || ti < before;
@@ -131,7 +102,7 @@ __global__ void __launch_bounds__(INTERP_THREADS)
                         uint8_t *__restrict__ hot, uint8_t *__restrict__ hot_out, double *__restrict__ stats_out) {
   const long long n = (long long)sums[0], S2 = (long long)sums[1], S1 = (long long)start[HW];
   const bool sigma = hot_sigma > 0.0;
-  double mean = flt_nan(), sd = flt_nan(), thr = flt_nan();
+  double mean = ord_nan(), sd = ord_nan(), thr = ord_nan();
   if (n > 0) {                                             // float64, in this order, no FMA (the unit is built without contraction)
     mean = (double)S1 / (double)n;
     const double v = (double)S2 / (double)n - mean * mean;
@@ -149,10 +120,10 @@ __global__ void __launch_bounds__(INTERP_THREADS)
   }
   if (stats_out && blockIdx.x == 0 && threadIdx.x == 0) {
     const bool failed = (ctr[0] & RAMP_FILTER_BAD_ORDER) != 0;
-    stats_out[0] = failed ? flt_nan() : (double)n;
-    stats_out[1] = failed ? flt_nan() : mean;
-    stats_out[2] = failed ? flt_nan() : sd;
-    stats_out[3] = failed ? flt_nan() : thr;
+    stats_out[0] = failed ? ord_nan() : (double)n;
+    stats_out[1] = failed ? ord_nan() : mean;
+    stats_out[2] = failed ? ord_nan() : sd;
+    stats_out[3] = failed ? ord_nan() : thr;
   }
 }
 
@@ -191,7 +162,7 @@ __global__ void __launch_bounds__(INTERP_THREADS) flt_filter_kernel(const FltArg
         if (a.hot[k]) {
           cls = 4;
         } else {
-          const double t_own = pos > (long)a.start[k] ? a.ts[pos - 1] : (a.last_in ? a.last_in[k] : flt_nan());
+          const double t_own = pos > (long)a.start[k] ? a.ts[pos - 1] : (a.last_in ? a.last_in[k] : ord_nan());
           if (refr && ti - t_own < a.refractory) {
             cls = 5;
           } else if (activity) {
@@ -203,15 +174,7 @@ __global__ void __launch_bounds__(INTERP_THREADS) flt_filter_kernel(const FltArg
               if (j == 4 || sup || ny < 0 || ny >= H || nx < 0 || nx >= W) continue;
               const uint32_t nb = (uint32_t)ny * (uint32_t)W + (uint32_t)nx;
               if (a.hot[nb]) continue;
-              const int lo = a.start[nb];
-              int p0 = lo, p1 = a.start[nb + 1];             // the first entry of the segment that does not precede (ti, i)
-              while (p0 < p1) {
-                const int mid = p0 + ((p1 - p0) >> 1);
-                const double tm = a.ts[mid];
-                const bool less = tm < ti || (tm == ti && a.sidx[mid] < i);
-                if (less) p0 = mid + 1; else p1 = mid;
-              }
-              const double t_nb = p0 > lo ? a.ts[p0 - 1] : (a.last_in ? a.last_in[nb] : flt_nan());
+              const double t_nb = ord_last_before(a.ts, a.sidx, a.start, a.last_in, nb, ti, i);
               sup = ti - t_nb <= a.support_dt;
             }
             cls = sup ? 7 : 6;
@@ -224,7 +187,7 @@ __global__ void __launch_bounds__(INTERP_THREADS) flt_filter_kernel(const FltArg
       a.keep_out[i] = keep ? 1 : 0;
       if (a.keep32) a.keep32[i] = keep ? 1 : 0;
       if (a.xy_out) {
-        const float2 row = keep ? make_float2(flt_coord<I32>(a.x, i), flt_coord<I32>(a.y, i)) : make_float2(qnan, qnan);
+        const float2 row = keep ? make_float2(ord_coord<I32>(a.x, i), ord_coord<I32>(a.y, i)) : make_float2(qnan, qnan);
         reinterpret_cast<float2 *>(a.xy_out)[i] = row;
       }
     }
@@ -269,9 +232,9 @@ __global__ void __launch_bounds__(INTERP_THREADS)
       const long q = tile * INTERP_THREADS + threadIdx.x;
       if (q >= (long)HW) continue;
       const int s0 = start[q], s1 = start[q + 1];
-      double v = last_in ? last_in[q] : flt_nan();         // (in place: a lane reads and writes its own pixel alone)
+      double v = last_in ? last_in[q] : ord_nan();         // (in place: a lane reads and writes its own pixel alone)
       if (s1 > s0 && !hot[q]) v = ts[s1 - 1];
-      last_out[q] = failed ? flt_nan() : v;
+      last_out[q] = failed ? ord_nan() : v;
     }
   }
   if (blockIdx.x == 0 && threadIdx.x < 8) {
@@ -279,12 +242,6 @@ __global__ void __launch_bounds__(INTERP_THREADS)
     status[w] = (failed && w >= 4) ? 0 : ctr[w];
   }
   if (count_out && blockIdx.x == 0 && threadIdx.x == 0) *count_out = failed ? 0 : (int64_t)ctr[7];
-}
-
-static int flt_sort_bits(uint32_t HW) {                    // ceil(log2(H W + 1)): the keys are 0 .. H W
-  int bits = 0;
-  while (bits < 32 && (HW >> bits) != 0) bits++;
-  return bits;
 }
 
 // the workspace: counters and, adjacent, the two sums (one memset clears both); the two key and the two index arrays, ts, start,
@@ -317,11 +274,6 @@ static size_t flt_carve(void *ws, long N, long HW, FltWs *w) {
   return c.bytes();
 }
 
-static int flt_grid(long lanes) {
-  const long tiles = (lanes + INTERP_THREADS - 1) / INTERP_THREADS;
-  return (int)(tiles < 1 ? 1 : (tiles < FLT_MAX_GROUPS ? tiles : FLT_MAX_GROUPS));
-}
-
 extern "C" {
 size_t ramp_event_filter_workspace_bytes(long N, int H, int W) {
   if (N < 0 || N > 2147483647L || H < 1 || W < 1 || (double)H * (double)W >= 2147483647.0) return 0;
@@ -329,7 +281,7 @@ size_t ramp_event_filter_workspace_bytes(long N, int H, int W) {
   return flt_carve(nullptr, N, (long)H * W, &w);
 }
 
-long ramp_event_filter_grid_events(void) { return (long)FLT_MAX_GROUPS * INTERP_THREADS; }
+long ramp_event_filter_grid_events(void) { return (long)ORD_MAX_GROUPS * INTERP_THREADS; }
 
 int ramp_event_filter(const void *x, const void *y, const double *t, long N, int H, int W, int flags, double support_dt,
                       double refractory, int hot_count, double hot_sigma, const uint8_t *hot_in, const double *last_t_in,
@@ -360,18 +312,18 @@ int ramp_event_filter(const void *x, const void *y, const double *t, long N, int
   const int n = (int)N;
   const bool i32 = (flags & RAMP_FILTER_XY_I32) != 0;
   if (hipMemsetAsync(w.ctr, 0, ws_span(w.ctr, w.sums + 2), st) != hipSuccess) return RAMP_ELAUNCH;
-  if (i32) hipLaunchKernelGGL((flt_key_kernel<true>), dim3(flt_grid(N)), dim3(INTERP_THREADS), 0, st, x, y, t, N, H, W, w.key, w.iota, w.ctr);
-  else hipLaunchKernelGGL((flt_key_kernel<false>), dim3(flt_grid(N)), dim3(INTERP_THREADS), 0, st, x, y, t, N, H, W, w.key, w.iota, w.ctr);
+  if (i32) hipLaunchKernelGGL((flt_key_kernel<true>), dim3(ord_grid(N)), dim3(INTERP_THREADS), 0, st, x, y, t, N, H, W, w.key, w.iota, w.ctr);
+  else hipLaunchKernelGGL((flt_key_kernel<false>), dim3(ord_grid(N)), dim3(INTERP_THREADS), 0, st, x, y, t, N, H, W, w.key, w.iota, w.ctr);
   RAMP_CHECK_LAUNCH();
   size_t cb = w.cub_bytes;
-  if (hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.key, w.skey, w.iota, w.sidx, n, 0, flt_sort_bits(HW), st) != hipSuccess)
+  if (hipcub::DeviceRadixSort::SortPairs(w.cub, cb, w.key, w.skey, w.iota, w.sidx, n, 0, ord_sort_bits(HW), st) != hipSuccess)
     return RAMP_ELAUNCH;
-  hipLaunchKernelGGL(flt_segment_kernel, dim3(flt_grid(HWl + 2)), dim3(INTERP_THREADS), 0, st, w.skey, n, HW, w.start);
+  hipLaunchKernelGGL(ord_segment_kernel, dim3(ord_grid(HWl + 2)), dim3(INTERP_THREADS), 0, st, w.skey, n, HW, w.start);
   RAMP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(flt_hot_sums_kernel, dim3(flt_grid(N > HWl ? N : HWl)), dim3(INTERP_THREADS), 0, st, w.skey, w.sidx, t, n, HW,
+  hipLaunchKernelGGL(flt_hot_sums_kernel, dim3(ord_grid(N > HWl ? N : HWl)), dim3(INTERP_THREADS), 0, st, w.skey, w.sidx, t, n, HW,
                      w.start, last_t_in, w.ts, w.ctr, w.sums);
   RAMP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(flt_hot_mask_kernel, dim3(flt_grid(HWl)), dim3(INTERP_THREADS), 0, st, w.start, HW, w.sums, w.ctr, hot_count,
+  hipLaunchKernelGGL(flt_hot_mask_kernel, dim3(ord_grid(HWl)), dim3(INTERP_THREADS), 0, st, w.start, HW, w.sums, w.ctr, hot_count,
                      hot_sigma, hot_in, w.hot, hot_out, stats_out);
   RAMP_CHECK_LAUNCH();
   // the sort's inputs are dead behind it: the keep flags and their sums take their place
@@ -380,16 +332,16 @@ int ramp_event_filter(const void *x, const void *y, const double *t, long N, int
   a.x = x; a.y = y; a.skey = w.skey; a.sidx = w.sidx; a.start = w.start; a.ts = w.ts; a.last_in = last_t_in; a.hot = w.hot;
   a.keep_out = keep_out; a.xy_out = xy_out; a.keep32 = keep32; a.ctr = w.ctr; a.support_dt = support_dt;
   a.refractory = refractory; a.N = n; a.H = H; a.W = W;
-  if (i32) hipLaunchKernelGGL((flt_filter_kernel<true>), dim3(flt_grid(N)), dim3(INTERP_THREADS), 0, st, a);
-  else hipLaunchKernelGGL((flt_filter_kernel<false>), dim3(flt_grid(N)), dim3(INTERP_THREADS), 0, st, a);
+  if (i32) hipLaunchKernelGGL((flt_filter_kernel<true>), dim3(ord_grid(N)), dim3(INTERP_THREADS), 0, st, a);
+  else hipLaunchKernelGGL((flt_filter_kernel<false>), dim3(ord_grid(N)), dim3(INTERP_THREADS), 0, st, a);
   RAMP_CHECK_LAUNCH();
   if (index_out) {
     cb = w.cub_bytes;
     if (hipcub::DeviceScan::InclusiveSum(w.cub, cb, keep32, incl, n, st) != hipSuccess) return RAMP_ELAUNCH;
-    hipLaunchKernelGGL(flt_compact_kernel, dim3(flt_grid(N)), dim3(INTERP_THREADS), 0, st, keep32, incl, n, index_out);
+    hipLaunchKernelGGL(flt_compact_kernel, dim3(ord_grid(N)), dim3(INTERP_THREADS), 0, st, keep32, incl, n, index_out);
     RAMP_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(flt_finish_kernel, dim3(last_t_out ? flt_grid(HWl) : 1), dim3(INTERP_THREADS), 0, st, w.start, w.ts, w.hot, HW,
+  hipLaunchKernelGGL(flt_finish_kernel, dim3(last_t_out ? ord_grid(HWl) : 1), dim3(INTERP_THREADS), 0, st, w.start, w.ts, w.hot, HW,
                      last_t_in, last_t_out, w.ctr, count_out, status);
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;

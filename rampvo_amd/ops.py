@@ -24,6 +24,9 @@ _BAD_CAMERA = (_lib.RAMP_RECTIFY_BAD_CAMERA, "the camera record is not finite or
 # (RAMP_MAP_RENDER_BAD_CAMERA is the same bit, raised on the same condition: the two entries share the row and the role)
 _BAD_POSE = (_lib.RAMP_DEPTH_POINTS_BAD_CAMERA, "the camera pose at t_ref is not finite")
 assert _lib.RAMP_MAP_RENDER_BAD_CAMERA == _lib.RAMP_DEPTH_POINTS_BAD_CAMERA == _lib.RAMP_MAP_LOCALIZE_BAD_CAMERA
+# (RAMP_FLOW_BAD_ORDER is the same bit, raised on the same condition: event_flow shares the row and the ``filter`` role)
+_BAD_ORDER = (_lib.RAMP_FILTER_BAD_ORDER, "a pixel's events decrease in time, or lie before the filter's state")
+assert _lib.RAMP_FLOW_BAD_ORDER == _lib.RAMP_FILTER_BAD_ORDER
 _STATUS = {
     "trajectory": ({"unresolved": (track_dev.TRAJ_UNRESOLVED,
                                    "a frame is neither a keyframe nor reachable through the delta chain")}, ()),
@@ -46,9 +49,10 @@ _STATUS = {
     "event_rectify": ({"bad_camera": _BAD_CAMERA},
                       ("n_events", "n_not_finite", "n_not_invertible", "n_behind", "n_outside", "n_inside")),
     "image_rectify": ({"bad_camera": _BAD_CAMERA}, ("n_pixels", "n_invalid", "n_outside", "n_sampled")),
-    "event_filter": ({"bad_order": (_lib.RAMP_FILTER_BAD_ORDER,
-                                    "a pixel's events decrease in time, or lie before the filter's state")},
+    "event_filter": ({"bad_order": _BAD_ORDER},
                      ("n_events", "n_not_finite", "n_outside", "n_hot", "n_refractory", "n_no_support", "n_kept")),
+    "event_flow": ({"bad_order": _BAD_ORDER},
+                   ("n_events", "n_not_finite", "n_outside", "n_few_points", "n_collinear", "n_flat", "n_valid")),
     "invdepth_map": ({"bad_cam": (_lib.RAMP_DEPTHMAP_BAD_CAM, "the camera pose at t_ref is not finite")},
                      ("n_considered", "n_bad_depth", "n_rejected", "n_out_of_reach", "n_contributing", "n_empty_pixels")),
     "se3_interp": ({"bad_times": _BAD_TIMES}, ("n_below", "n_above", "n_nan")),
@@ -1050,6 +1054,90 @@ def event_filter(x, y, t, height, width, support_dt=None, refractory=0.0, hot_co
 def event_filter_status(status):
     """The status words of ``event_filter`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
     return _status("event_filter", status)
+
+
+def event_flow(x, y, t, height, width, p=None, radius=2, window_dt=None, min_points=5, refine=1, outlier_dt=None,
+               max_speed=float("inf"), last_t=None, want_map=False, want_fit=False):
+    """Per-event optical flow on the device (include/ramp_hip.h ``ramp_event_flow``): at every event a plane is fitted to the
+    surface of active events -- the last time stamp of each pixel of a ``(2 radius + 1)^2`` window that precedes the event and
+    is at most ``window_dt`` older -- and the plane's slope gives the NORMAL flow in pixels per unit of ``t``.  No trajectory,
+    no depth.  Order-independent and bit-exact, every rounding fixed by the header.
+
+    ``x, y`` [N]: integer tensors take the int32 path, floating ones fp32; ``t`` [N] float64, non-decreasing per pixel (and
+    plane); ``p`` [N]: with it the two polarities have a surface each (``p > 0`` and the rest).  ``radius`` 1 .. 3;
+    ``min_points`` 3 .. ``(2 radius + 1)^2`` points a fit needs; ``refine`` 0 .. 2 passes that drop points further than
+    ``outlier_dt`` (None: ``window_dt / 4``) from the plane and fit again; flows faster than ``max_speed`` are flat.
+    ``last_t``: the state of the previous call, float64 [height, width] without ``p`` (``event_filter``'s ``last_t`` as it
+    is), [2, height, width] with it; None: no event yet.  It is not written.
+
+    Returns a dict of device tensors: ``flow`` float32 [N, 2] (NaN rows for every event without a valid flow), ``cls`` uint8
+    [N] (2 not finite, 3 outside, 4 too few points, 5 collinear, 6 flat, 7 valid), ``n_used`` uint8 [N], ``status`` int32 [8]
+    (``event_flow_status``), ``last_t``, a NEW tensor, the state for the next call; with ``want_fit`` ``fit`` float64 [N, 3]
+    (the plane a, b, c); with ``want_map`` ``flow_map`` float32 [2, height, width] and ``map_index`` int32 [height, width]: per
+    pixel the valid event with the largest index.  Runs on the current stream, nothing is synchronised; a call repeats its
+    bits.  Time stamps that decrease within a pixel (or against the state) make every output NaN, -1 or 0 and set bit 0 of
+    ``status[0]``: never a plausible number."""
+    dev = x.device
+    if height < 1 or width < 1:
+        raise RuntimeError("event_flow: height and width are positive")
+    if window_dt is None:
+        raise RuntimeError("event_flow: window_dt is required (the age, in the unit of t, up to which a neighbour is a point)")
+    radius, min_points, refine = int(radius), int(min_points), int(refine)
+    window_dt, max_speed = float(window_dt), float(max_speed)
+    outlier_dt = window_dt / 4 if outlier_dt is None else float(outlier_dt)
+    if not 1 <= radius <= 3:
+        raise RuntimeError("event_flow: radius is 1, 2 or 3")
+    if not 3 <= min_points <= (2 * radius + 1) ** 2:
+        raise RuntimeError("event_flow: min_points is between 3 and (2 radius + 1)^2 = %d" % (2 * radius + 1) ** 2)
+    if not 0 <= refine <= 2:
+        raise RuntimeError("event_flow: refine is 0, 1 or 2")
+    if not window_dt >= 0 or not outlier_dt >= 0:
+        raise RuntimeError("event_flow: window_dt and outlier_dt are not negative (and not NaN)")
+    if not max_speed > 0:
+        raise RuntimeError("event_flow: max_speed is positive (inf: no limit)")
+    integer = not (x.is_floating_point() or y.is_floating_point())
+    dt = torch.int32 if integer else torch.float32
+    xs, ys = x.reshape(-1).to(dt).contiguous(), y.reshape(-1).to(dt).contiguous()
+    tf = t.reshape(-1).to(torch.float64).contiguous()
+    N = xs.shape[0]
+    pd = None if p is None else p.reshape(-1).to(torch.int8).contiguous()
+    if not (ys.shape[0] == N and tf.shape[0] == N and (pd is None or pd.shape[0] == N)):
+        raise RuntimeError("event_flow: x, y, t and p differ in length")
+    planes = 1 if pd is None else 2
+    shape = (height, width) if planes == 1 else (2, height, width)
+    state = None
+    if last_t is not None:
+        if tuple(last_t.shape) != shape or last_t.dtype != torch.float64:
+            raise RuntimeError("event_flow: last_t is float64 [height, width], or [2, height, width] with p")
+        state = last_t.contiguous()
+    require_cuda(x, y, t, p, last_t)
+    nbytes = lib().ramp_event_flow_ws_bytes(N, height, width, planes)
+    if nbytes == 0:
+        check(_lib.RAMP_EUNSUPPORTED, "ramp_event_flow")
+    res = {"flow": torch.empty((N, 2), dtype=torch.float32, device=dev), "cls": torch.empty(N, dtype=torch.uint8, device=dev),
+           "n_used": torch.empty(N, dtype=torch.uint8, device=dev), "status": torch.zeros(8, dtype=torch.int32, device=dev)}
+    if want_fit:
+        res["fit"] = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    if want_map:
+        res["flow_map"] = torch.empty((2, height, width), dtype=torch.float32, device=dev)
+        res["map_index"] = torch.empty((height, width), dtype=torch.int32, device=dev)
+    if N == 0:                                                # (an empty p has no pointer to tell the entry of two planes: the state is made here)
+        res["last_t"] = state.clone() if state is not None else torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+        state = None
+    else:
+        res["last_t"] = torch.empty(shape, dtype=torch.float64, device=dev)
+    ws = _lib_workspace(nbytes, dev, "evflow")
+    check(lib().ramp_event_flow(ptr(xs), ptr(ys), ptr(tf), ptr(pd), N, height, width, _lib.RAMP_FLOW_XY_I32 if integer else 0,
+                                radius, window_dt, min_points, refine, outlier_dt, max_speed, ptr(state), ptr(res["last_t"]) if N else None,
+                                ptr(res["flow"]), ptr(res["cls"]), ptr(res["n_used"]), ptr(res.get("fit")),
+                                ptr(res.get("flow_map")), ptr(res.get("map_index")), ptr(res["status"]), ptr(ws), nbytes,
+                                stream()), "ramp_event_flow")
+    return res
+
+
+def event_flow_status(status):
+    """The status words of ``event_flow`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("event_flow", status)
 
 
 # ------------------------------------------------------------------- IMU

@@ -120,6 +120,7 @@ class TrackerQueries:
     _camera = None              # set_camera(): the record's host part on the device, without the rectified intrinsics
     _filter_params = None       # set_event_filter(): the keywords of ops.event_filter
     _filter_state = None        # the filter's last-time-stamp map, carried by filter_events()
+    _flow_state = None          # the surface of active events, carried by event_flow()
     _imu = None                 # set_imu(): the keywords of ops.imu_align that describe the sensor
 
     def _state_stream(self, inputs=()):
@@ -373,6 +374,61 @@ class TrackerQueries:
             raise RuntimeError(name + ": denoise=True needs the filter's parameters (set_event_filter())")
         out = self._filter(name, x, y, t)
         return out["xy"][:, 0], out["xy"][:, 1], out["status"]
+
+    # ---------------------------------------------------------------- event optical flow
+    _FLOW_KEYS = ("radius", "window_dt", "min_points", "refine", "outlier_dt", "max_speed", "want_map", "want_fit")
+
+    def reset_event_flow(self):
+        """forget the events ``event_flow`` has seen: the next call starts from the empty surface"""
+        self._flow_state = None
+
+    def event_flow(self, x, y, t, p=None, as_tensor=False, denoise=False, carry=True, **params):
+        """How the image moves at each event of the next stretch of the sensor's stream, without a trajectory and without a
+        depth (``ops.event_flow``; ``params``: its ``radius``, ``window_dt``, ``min_points``, ``refine``, ``outlier_dt``,
+        ``max_speed``, ``want_map``, ``want_fit``): the normal flow of a plane fitted to the surface of active events around
+        the event, in pixels per unit of ``t``, at the tracker's image size.  ``x, y`` are RAW SENSOR PIXELS -- the fit lives on
+        the integer lattice, so it sits where the filter sits, ahead of any rectification; integer input takes the int32
+        path.  ``p``: with it each polarity has its own surface.  The surface -- every cell's last time stamp -- is CARRIED
+        from call to call, so feeding a stream in pieces gives the flows of feeding it whole (``reset_event_flow`` forgets it;
+        ``carry=False``: these events alone, the carried surface neither read nor advanced).  ``denoise=True``: filtered first
+        (``set_event_filter``; raises without one; the filter's state is read, not advanced); a dropped event is a NaN row and
+        falls in class 2, and the result gains ``filter_status``.
+
+        A device-resident state stays device resident.  ``as_tensor=True``: the dict of device tensors of ``ops.event_flow``,
+        ordered on the current stream, nothing synchronised.  Otherwise numpy arrays, which waits and raises when a pixel's
+        events decrease in time or lie before the carried surface (which is then left as it was) -- with ``denoise`` the
+        denoiser's word is looked at first, the flow's second."""
+        name = "event_flow()"
+        unknown = sorted(set(params) - set(self._FLOW_KEYS))
+        if unknown:
+            raise RuntimeError(name + ": unknown parameter %s (known: %s)" % (unknown[0], ", ".join(self._FLOW_KEYS)))
+        td = self._as_device(t, torch.float64)
+        pd = None if p is None else self._as_device(p, torch.int8)
+        filt = None
+        if denoise:
+            xd, yd, filt = self._denoised(name, x, y, td)
+        else:
+            xd, yd = self._raw_pixels(x), self._raw_pixels(y)
+        state = self._flow_state if carry else None
+        shape = (self.ht, self.wd) if pd is None else (2, self.ht, self.wd)
+        if state is not None and tuple(state.shape) != shape:
+            raise RuntimeError(name + ": the carried surface is %s, the call asks for %s -- with and without p do not mix "
+                               "(reset_event_flow())" % (" x ".join(map(str, state.shape)), " x ".join(map(str, shape))))
+        with self._state_stream(inputs=tuple(v for v in (xd, yd, td, pd, state) if v is not None)) as sc:
+            out = ops.event_flow(xd, yd, td, self.ht, self.wd, p=pd, last_t=state, **params)
+            sc.leaves(out)
+        if filt is not None:
+            out["filter_status"] = filt
+        if not as_tensor:
+            words = [s.reshape(-1)[:1] for s in (filt, out["status"]) if s is not None]
+            for word in (words[0] if len(words) == 1 else torch.cat(words)).cpu().tolist():      # (the one wait)
+                _raise_on_words(name, {"filter": word})
+            res = {k: v.cpu().numpy() for k, v in out.items()}
+        else:
+            res = out
+        if carry:
+            self._flow_state = out["last_t"]               # (behind a clean check; as_tensor: a bad order leaves NaN)
+        return res
 
     # ---------------------------------------------------------------- lens distortion
     def set_camera(self, model, raw_intrinsics, coeffs=(), rotation=None):
