@@ -1363,14 +1363,8 @@ static BaEdgeIn ba_edge_in(const BaProblem &p) {
   return e;
 }
 
-// the single-workgroup kernels keep their matrix in LDS: above 64 KB the kernel has to be told
-// (per call: the attribute is per device, and a process may drive several)
-static int ba_allow_lds(const void *kernel, size_t lds) {
-  if (lds > 160 * 1024) return RAMP_EUNSUPPORTED;
-  if (lds > 64 * 1024 && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return RAMP_ELAUNCH;
-  return RAMP_OK;
-}
+// the single-workgroup kernels keep their matrix in LDS (ramp_launch_lds); a window whose matrix exceeds a CU's 160 KB is refused
+constexpr size_t BA_LDS_MAX = 160 * 1024;
 
 // K1 .. K5: the system at the state p.  E row, C, u, Q per patch; with free poses also the pair records, the split-K
 // partials and S, y (w.S, w.yv).  The solver runs it once per iteration, the covariance once.
@@ -1410,13 +1404,14 @@ static int ba_build_system(const BaProblem &p, const BaGroups &g, BaWs &w, int32
 static int ba_iterate(const BaProblem &p, const BaGroups &g, int iterations, BaWs &w, int32_t *info, hipStream_t st) {
   const int N = p.t1 - p.t0, n6 = 6 * N;
   const size_t lds = (size_t)((n6 + 1) * (n6 + 1) + 6 * n6) * sizeof(float);
-  int rc = ba_allow_lds((const void *)ba_cholb_kernel, lds);
-  if (rc != RAMP_OK) return rc;
+  if (lds > BA_LDS_MAX) return RAMP_EUNSUPPORTED;
+  int rc;
   const int depth_blocks = ramp_cdiv(w.Mu_b, 4);
   const int pose_blocks = N > 0 ? ramp_cdiv(N, 256) : 0;
   for (int itr = 0; itr < iterations; itr++) {
     if ((rc = ba_build_system(p, g, w, info, st)) != RAMP_OK) return rc;
-    if (N > 0) hipLaunchKernelGGL(ba_cholb_kernel, dim3(1), dim3(BA_TG * BA_TG), lds, st, w.S, w.yv, w.dX, info, n6);
+    if (N > 0 && (rc = ramp_launch_lds(ba_cholb_kernel, dim3(1), dim3(BA_TG * BA_TG), lds, st, w.S, w.yv, w.dX, info, n6)) != RAMP_OK)
+      return rc;
     hipLaunchKernelGGL(ba_retract_kernel, dim3(depth_blocks + pose_blocks), dim3(256), 0, st, p.poses, p.patches, w.Erow,
                        w.Qv, w.uv, w.dX, g.ukeys_k, g.ngroups_k, n6, p.P * p.P, p.t0, N, depth_blocks, p.dyn, p.opt_window);
     RAMP_CHECK_LAUNCH();
@@ -1443,12 +1438,13 @@ static int ba_cov_run(const BaProblem &p, const BaGroups &g, BaWs &w, BaCovWs &c
                       hipStream_t st) {
   const int N = p.t1 - p.t0, n6 = 6 * N;
   const size_t lds = (size_t)(n6 * (n6 + 1) + (n6 / 6) * 28) * sizeof(float);
-  int rc = ba_allow_lds((const void *)ba_cholinv_kernel, lds);
-  if (rc != RAMP_OK) return rc;
+  if (lds > BA_LDS_MAX) return RAMP_EUNSUPPORTED;
+  int rc;
   if (hipMemsetAsync(c.flag, 0, sizeof(int32_t), st) != hipSuccess) return RAMP_ELAUNCH;
   if ((rc = ba_build_system(p, g, w, info, st)) != RAMP_OK) return rc;
-  if (N > 0)
-    hipLaunchKernelGGL(ba_cholinv_kernel, dim3(1), dim3(BA_TG * BA_TG), lds, st, w.S, c.Linv, c.LinvT, c.flag, info, n6);
+  if (N > 0 &&
+      (rc = ramp_launch_lds(ba_cholinv_kernel, dim3(1), dim3(BA_TG * BA_TG), lds, st, w.S, c.Linv, c.LinvT, c.flag, info, n6)) != RAMP_OK)
+    return rc;
   const int tiles = ramp_cdiv(n6, BA_CT);
   hipLaunchKernelGGL(ba_cov_expand_kernel, dim3(tiles * tiles + ramp_cdiv(w.Mu_b, 4)), dim3(256), 0, st, c.Linv, c.LinvT,
                      c.flag, w.Erow, w.Qv, g.ukeys_k, g.order_k, g.seg_k, g.ngroups_k, ba_edge_in(p), out.cov,

@@ -473,11 +473,6 @@ constexpr int conv_tile_lds_bytes(int K, int S, bool IN_F32, int CIN, int NT, bo
   const int OBYTES = TH * TW * (NT * 16 + 4) * 4;
   return (WBYTES + IBYTES) > OBYTES ? (WBYTES + IBYTES) : OBYTES;
 }
-template <typename KernelT>
-static int conv_tile_attr(KernelT kernel, int lds) {
-  if (lds <= 64 * 1024) return RAMP_OK;
-  return hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess ? RAMP_OK : RAMP_ELAUNCH;
-}
 
 // LDS-tiled fp16 variant: the layers of these towers are tiny (32/64 channels, <= 77k pixels), so
 // the direct kernel above spends its time on one global round trip per tap and on re-applying
@@ -1816,11 +1811,8 @@ struct TileQuery {
 template <int K, int S, bool IN_F32, int CIN, int NT, bool FP8, int TH, bool TAIL>
 static int conv_tile_launch(const ConvMulti &pm, int cmax, int njobs, hipStream_t st) {
   constexpr int lds = conv_tile_lds_bytes(K, S, IN_F32, CIN, NT, FP8, TH);
-  if (conv_tile_attr(conv_tile_f16_kernel<K, S, IN_F32, CIN, NT, FP8, TH, TAIL>, lds) != RAMP_OK) return RAMP_ELAUNCH;
-  hipLaunchKernelGGL((conv_tile_f16_kernel<K, S, IN_F32, CIN, NT, FP8, TH, TAIL>),
-                     dim3(ramp_cdiv(pm.t[0].OH, TH) * ramp_cdiv(pm.t[0].OW, 16), cmax / (NT * 16), njobs), dim3(256), lds, st, pm);
-  RAMP_CHECK_LAUNCH();
-  return RAMP_OK;
+  return ramp_launch_lds(conv_tile_f16_kernel<K, S, IN_F32, CIN, NT, FP8, TH, TAIL>,
+                         dim3(ramp_cdiv(pm.t[0].OH, TH) * ramp_cdiv(pm.t[0].OW, 16), cmax / (NT * 16), njobs), dim3(256), lds, st, pm);
 }
 // the instance of a row that `want` asks for (a template, so that only the instances a row names are instantiated)
 template <int K, int S, bool IN_F32, int CIN, int NT, int TH, int VARIANTS>
@@ -1894,11 +1886,8 @@ static int conv_x3_dispatch(int K, int S, int Cin, int Cout, const ConvParams *p
   if (K == K_ && S == S_ && Cin == CIN && Cout == COUT) {                                                                 \
     if (!p) return RAMP_OK;                                                                                               \
     constexpr int lds = conv_x3_lds_bytes(K_, S_, CIN);                                                                   \
-    if (conv_tile_attr(conv_x3_kernel<K_, S_, CIN, COUT>, lds) != RAMP_OK) return RAMP_ELAUNCH;                           \
-    hipLaunchKernelGGL((conv_x3_kernel<K_, S_, CIN, COUT>), dim3(ramp_cdiv(p->OH, 8) * ramp_cdiv(p->OW, 16)), dim3(256),  \
-                       lds, st, *p);                                                                                      \
-    RAMP_CHECK_LAUNCH();                                                                                                  \
-    return RAMP_OK;                                                                                                       \
+    return ramp_launch_lds(conv_x3_kernel<K_, S_, CIN, COUT>, dim3(ramp_cdiv(p->OH, 8) * ramp_cdiv(p->OW, 16)), dim3(256), \
+                           lds, st, *p);                                                                                  \
   }
   CONV_X3_ROWS(X3_ROW)
 #undef X3_ROW

@@ -18,6 +18,20 @@
 
 static inline int ramp_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// The one rule for a launch with dynamic LDS.  A kernel gets up to 64 KiB unasked; above that it has to be allowed the size
+// (hipFuncAttributeMaxDynamicSharedMemorySize) -- on EVERY such call, not once per process: the attribute is per device, and
+// a process may drive several.  A launch that stays below says so beside it (a static_assert or the arithmetic).
+constexpr size_t RAMP_LDS_DEFAULT_MAX = 64 * 1024;
+template <class KernelT, class... ArgT>
+static inline int ramp_launch_lds(KernelT kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, const ArgT &...args) {
+  if (lds > RAMP_LDS_DEFAULT_MAX &&
+      hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return RAMP_ELAUNCH;
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  RAMP_CHECK_LAUNCH();
+  return RAMP_OK;
+}
+
 // float -> int, saturating (v_cvt_i32_f32 semantics; NaN -> 0)
 __device__ __forceinline__ int ramp_f2i(float f) {
   if (f != f) return 0;

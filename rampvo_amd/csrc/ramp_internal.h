@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include "../../include/ramp_hip.h"
+#include "update_params.h"
 #include "workspace.h"
 
 size_t ramp_internal_group_by_ws(int E);
@@ -84,44 +85,20 @@ struct UpdOp {
 };
 int ramp_i_update_check(const UpdOp &op);                      // RAMP_EINVAL unless every pointer the precision needs is there
 int ramp_i_update_operator(const UpdOp &op, hipStream_t st);   // (a checked op)
+// its stages (csrc/update_mlp.hip, csrc/update_x3.hip): one operand record each (update_params.h), which the launcher
+// validates -- RAMP_EINVAL for E < 0, RAMP_OK for E = 0 before any pointer is looked at.  E_hint: ramp_track.E_hint
+int ramp_i_upd_corr_mlp(const CorrTailParams &p, hipStream_t st);
+int ramp_i_upd_nbr(const NbrParams &p, hipStream_t st);
+int ramp_i_upd_softagg(const SoftAggParams &p, hipStream_t st);
+int ramp_i_upd_gru(const GruParams &p, int E_hint, hipStream_t st);
+int ramp_i_x3_corr_mlp(const X3CorrMlpParams &p, hipStream_t st);
+int ramp_i_x3_nbr(const X3NbrParams &p, hipStream_t st);
+int ramp_i_x3_fg(const X3FgParams &p, hipStream_t st);
+int ramp_i_x3_gru(const X3GruParams &p, hipStream_t st);
 extern "C" {
 int ramp_i_corr_fwd(const void *fmap1, const ramp_corr_level *levels, int nlevels, const float *coords,
                     const int64_t *ii, const int64_t *jj, const int32_t *order, void *out, int out_row_elems,
                     long mod_ii, long mod_jj, int E, int N1, int N2, int C, int P, int radius, int dtype, int layout,
                     const int32_t *dyn, void *stream, const float *tf_poses = nullptr, const float *tf_patches = nullptr,
                     const float *tf_intr = nullptr, const int64_t *tf_src = nullptr, const int32_t *slot0 = nullptr);
-int ramp_i_upd_gru(const float *x32, const void *add0_t, const int32_t *add0_idx, const void *add_t, const int32_t *add_idx,
-                 const float *pre_w, const float *pre_b,
-                   float pre_eps, const void *const *wp_host, const float *const *bias_host, const float *ln_w,
-                   const float *ln_b, float eps, float *out32, void *relu_t, int E, const int32_t *dyn,
-                   const void *heads_w, const float *heads_b, const float *coords, float *target, float *weight, int P,
-                   float wd, float ht, int E_hint, void *stream);
-int ramp_i_upd_nbr(const float *net_in, const int64_t *idx, const void *wa, const float *ba, const void *wb,
-                   const float *bb, float *net_out, void *out_t, int E, const int32_t *dyn, void *stream);
-int ramp_i_upd_corr_mlp(const void *corr, int corr_k, const void *w1, const float *b1, const void *w2, const float *b2,
-                        const void *w3, const float *b3, const float *ln_w, const float *ln_b, float ln_eps,
-                        const float *net, const int64_t *net_map, const void *inp, const int64_t *inp_idx, long inp_mod,
-                        const float *norm_w, const float *norm_b, float norm_eps, float *net_out, int E,
-                        const int32_t *dyn, void *stream);
-int ramp_i_upd_softagg(const float *x32, const void *add_t, const int32_t *add_idx, const int32_t *order, const int32_t *gid,
-                       const void *wf, const float *bf, const void *wg, const float *bg, float *frag, int E,
-                       const int32_t *dyn, void *stream, uint32_t *gate_flag = nullptr, uint32_t gate_seq = 0);
-int ramp_i_upd_fg(const float *x32, const void *add_t, const int32_t *add_idx, float *x32_out, const void *wf,
-                  const float *bf, const void *wg, const float *bg, void *fg, int E, const int32_t *dyn, void *stream);
-int ramp_i_upd_heads_linear(const void *relu_t, const void *heads_w, const float *heads_b, const float *coords,
-                            float *target, float *weight, int E, int P, float wd, float ht, const int32_t *dyn,
-                            void *stream);
-int ramp_i_x3_nbr(const float *net_in, const int64_t *idx, const void *wa, const float *ba, const void *wb, const float *bb,
-                  float *net_out, int E, const int32_t *dyn, void *stream);
-int ramp_i_x3_corr_mlp(const float *corr, int corr_k, const void *w1, const float *b1, const void *w2, const float *b2,
-                       const void *w3, const float *b3, const float *ln_w, const float *ln_b, float ln_eps, const float *net,
-                       const int64_t *net_map, const float *inp, const int64_t *inp_idx, long inp_mod, const float *norm_w,
-                       const float *norm_b, float norm_eps, float *net_out, int E, const int32_t *dyn, void *stream);
-int ramp_i_x3_fg(const float *x32, const float *add_t, const int32_t *add_idx, float *x32_out, const void *wf, const float *bf,
-                 const void *wg, const float *bg, float *fg, int E, const int32_t *dyn, void *stream);
-int ramp_i_x3_gru(const float *x32, const float *add0_t, const int32_t *add0_idx, const float *add_t, const int32_t *add_idx,
-                  const float *pre_w, const float *pre_b, float pre_eps, const void *const *wp_host,
-                  const float *const *bias_host, const float *ln_w, const float *ln_b, float eps, float *out32, float *relu32,
-                  int E, const int32_t *dyn, const float *heads_w, const float *heads_b, const float *coords, float *target,
-                  float *weight, int P, float wd, float ht, void *stream);
 }

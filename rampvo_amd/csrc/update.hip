@@ -497,22 +497,17 @@ int ramp_upd_heads(const void *hw, const float *coords, float *target, float *we
   return RAMP_OK;
 }
 
-int ramp_i_upd_heads_linear(const void *relu_t, const void *heads_w, const float *heads_b, const float *coords,
-                            float *target, float *weight, int E, int P, float wd, float ht, const int32_t *dyn,
-                            void *stream) {
+int ramp_upd_heads_linear(const void *relu_t, const void *heads_w, const float *heads_b, const float *coords,
+                          float *target, float *weight, int E, int P, float wd, float ht, void *stream) {
   if (E < 0 || P < 1) return RAMP_EINVAL;
   if (E == 0) return RAMP_OK;
   if (!relu_t || !heads_w || !heads_b || !coords || !target || !weight) return RAMP_EINVAL;
   const int PP = P * P, ctr = (P / 2) * P + P / 2;
   hipLaunchKernelGGL(upd_heads_linear_f16_kernel, dim3(ramp_cdiv(E, 4)), dim3(256), 0, (hipStream_t)stream,
                      (const _Float16 *)relu_t, (const _Float16 *)heads_w, heads_b, coords, target, weight, E, PP, ctr,
-                     wd, ht, dyn);
+                     wd, ht, (const int32_t *)nullptr);   // (no device-side sizes: the step forms the heads in its gru launch)
   RAMP_CHECK_LAUNCH();
   return RAMP_OK;
-}
-int ramp_upd_heads_linear(const void *relu_t, const void *heads_w, const float *heads_b, const float *coords,
-                          float *target, float *weight, int E, int P, float wd, float ht, void *stream) {
-  return ramp_i_upd_heads_linear(relu_t, heads_w, heads_b, coords, target, weight, E, P, wd, ht, nullptr, stream);
 }
 
 int ramp_upd_segment_softmax(const void *fg, const int32_t *order, const int32_t *seg_start,

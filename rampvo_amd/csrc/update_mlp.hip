@@ -14,6 +14,7 @@
 //     next layer's fp16 input goes back to LDS.  Linear outputs are rounded to fp16 where the
 //     reference's autocast would (they are half tensors there).
 #include "ramp_device.h"
+#include "ramp_internal.h"
 #include <stdlib.h>
 
 #define MD 384                 // feature width
@@ -185,33 +186,6 @@ __device__ __forceinline__ void park_half(float *P, const float (&val)[4][MNTW][
 #pragma unroll
       for (int r = 0; r < 4; r++) P[(m * 16 + 4 * q + r) * MPS + col0 + nt * 16 + j] = val[2 * half + m][nt][r];
 }
-
-struct GruParams {
-  const float *x32;            // [E][384] fp32: the LayerNorm'ed residual stream entering gru[1]
-  const _Float16 *wp[6];       // packed weights: g1_gate, g1_r1, g1_r2, g2_gate, g2_r1, g2_r2
-  const float *bias[6];        // biases (fp16-rounded values as fp32)
-  const float *ln_w, *ln_b;    // gru[2] LayerNorm
-  float eps;
-  float *out32;                // [E][384] fp32 result of gru[3]
-  _Float16 *relu_t;            // [E][384] relu(result) in fp16 (input of the heads)
-  // optional prologue: x = LayerNorm_pre(x32 + add_t[add_idx]) -- the last SoftAgg's expand-and-add and gru[0]
-  const _Float16 *add_t;       // [groups][384] fp16 or NULL
-  const int32_t *add_idx;      // [E]
-  const _Float16 *add0_t;      // optional: a FIRST expand-and-add (x32 + add0_t[add0_idx]) + add_t[add_idx] -- the second-last
-  const int32_t *add0_idx;     // SoftAgg's, when the launch that consumed it did not write the sum back
-  const float *pre_w, *pre_b;  // gru[0] LayerNorm
-  float pre_eps;
-  int E;
-  const int32_t *dyn;          // optional device-side sizes (RAMP_DYN_*): E is then the launch bound
-  // optional epilogue: the two heads and target / weight (ramp/net.py:87-90, ramp/Ramp_vo.py:291-297) from the
-  // result tile while it is in registers -- relu_t is then not written (may be NULL)
-  const _Float16 *heads_w;     // [4][384] fp16: d.weight rows 0..1, w.weight rows 0..1
-  const float *heads_b;        // [4]
-  const float *coords;         // [E][2][PP]
-  float *target, *weight;      // [E][2]
-  int PP, ctr;
-  float wd, ht;
-};
 
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
@@ -488,16 +462,6 @@ __global__ void __launch_bounds__(64 * MWAVES) upd_gru_kernel(const GruParams p)
 // net[e] += Lb(relu(La(mask * net[idx[e]])))   (ramp/net.py:77-82: the temporal-neighbour MLPs; idx = -1
 // marks a missing neighbour).  The gathered rows are staged straight into the LDS tile; the result is
 // written to a SECOND state buffer (other workgroups still gather from the input one).
-struct NbrParams {
-  const float *net_in;         // [E][384] fp32
-  const int64_t *idx;          // [E] neighbour row or -1
-  const _Float16 *wa, *wb;     // packed weights of the two Linear layers
-  const float *ba, *bb;        // biases (fp16-rounded values as fp32)
-  float *net_out;              // [E][384] fp32
-  _Float16 *out_t;             // optional [E][384] fp16 copy of net_out
-  int E;
-  const int32_t *dyn;          // optional device-side sizes (RAMP_DYN_*): E is then the launch bound
-};
 
 // waves_per_eu 6: 80 VGPRs -> three workgroups per CU (3 x 50 KB LDS): all ~625 workgroups of an update are
 // resident at once (768 slots) instead of 1.2 rounds of 512
@@ -581,28 +545,6 @@ __global__ void __launch_bounds__(64 * MWAVES) __attribute__((amdgpu_waves_per_e
 //   c = Linear3(relu(LayerNorm(Linear2(c1))));  net = LayerNorm(net_prev + inp + c)
 // c1 = relu(Linear1(corr)) comes from the library GEMM (K = 896).  One 50 KB LDS tile (input, hidden, fp32
 // parking) -> two workgroups per CU.  Linear outputs are rounded to fp16 where autocast makes them half tensors.
-struct CorrTailParams {
-  // FULL variant: the first Linear (+ReLU) of the MLP on the correlation rows as well
-  const _Float16 *corr;        // [E][corr_k] fp16 (corr_k a multiple of 32, e.g. 896 = 882 + zero padding)
-  const _Float16 *w1;          // packed [corr_k/32][24][64][8]
-  const float *b1;
-  int corr_k;
-  const _Float16 *c1;          // [E][384] fp16 (tail-only variant: relu(Linear1(corr)) from a library GEMM)
-  const _Float16 *w2, *w3;     // packed weights of corr[2], corr[5]
-  const float *b2, *b3;        // biases (fp16-rounded values as fp32)
-  const float *ln_w, *ln_b;    // corr[3] LayerNorm
-  float ln_eps;
-  const float *net;            // [*][384] fp32 previous hidden state or NULL (zeros)
-  const int64_t *net_map;      // [E] row of `net` per edge (-1: zero row) or NULL (identity)
-  const _Float16 *inp;         // context table [*][384] fp16
-  const int64_t *inp_idx;      // [E] row of `inp` (taken modulo inp_mod when inp_mod > 0) or NULL (identity)
-  long inp_mod;
-  const float *norm_w, *norm_b;
-  float norm_eps;
-  float *net_out;              // [E][384] fp32
-  int E;
-  const int32_t *dyn;          // optional device-side sizes (RAMP_DYN_*): E is then the launch bound
-};
 
 #ifdef GRU_TRACE
 #define CT(k) do { if (threadIdx.x == 0) g_gru_trace[blockIdx.x * 32 + (k)] = wall_clock64(); } while (0)
@@ -783,18 +725,6 @@ __global__ void __launch_bounds__(64 * MWAVES) __attribute__((amdgpu_waves_per_e
 // SoftAgg's expand-and-add, written back to x32_out) -- the row pass that formed x and the [E,384]x[384,768] GEMM in
 // one launch.  Transposed accumulators: every lane stores four consecutive fp16 outputs, no parking pass, the
 // input tile stays valid for the second matrix.  One 50 KB tile, three workgroups per CU.
-struct FgParams {
-  const float *x32;            // [E][384] fp32
-  const _Float16 *add_t;       // optional [groups][384] fp16
-  const int32_t *add_idx;      // [E]
-  float *x32_out;              // optional [E][384] fp32 (may be x32): x after the add
-  const _Float16 *wf, *wg;     // packed weights of f and g
-  const float *bf, *bg;        // biases (fp16-rounded values as fp32)
-  _Float16 *fg;                // [E][768] fp16
-  int E;
-  const int32_t *dyn;          // optional device-side sizes (RAMP_DYN_*): E is then the launch bound
-};
-
 __global__ void __launch_bounds__(64 * MWAVES) __attribute__((amdgpu_waves_per_eu(6, 6))) upd_fg_kernel(const FgParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   _Float16 *Xs = reinterpret_cast<_Float16 *>(smem_raw);
@@ -1116,7 +1046,6 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) upd_fg_big_kernel(const FgPar
   }
 }
 
-
 // ------------------------------------------------------------------ SoftAgg without the [f | g] rows
 // y[group][c] = sum_e softmax_e(g(x_e)[c]) f(x_e)[c] over the factors e of a group, hy = h(y)  (ramp/blocks.py:42-47).
 // upd_fg (+ upd_segment_softmax) write the [E, 768] fp16 rows of [f | g] and read them back through the grouping's
@@ -1138,20 +1067,6 @@ __global__ void __launch_bounds__(64 * NW, NW / 4) upd_fg_big_kernel(const FgPar
 #define SAGG_NMT 5
 #define SAGG_ROWS (16 * SAGG_NMT)   // 80 positions per workgroup
 #define SAGG_BLK (4 * SAGG_NMT)     // 20 positions per lane block
-struct SoftAggParams {
-  const float *x32;            // [E][384] fp32
-  const _Float16 *add_t;       // optional [groups'][384] fp16: x = x32 + add_t[add_idx] (the previous SoftAgg's expand-and-add)
-  const int32_t *add_idx;      // [E]
-  const int32_t *order;        // [E] sorted position -> factor
-  const int32_t *gid;          // [E] factor -> group
-  const _Float16 *wf, *wg;     // packed weights of f and g
-  const float *bf, *bg;        // biases (fp16-rounded values as fp32)
-  float *frag;                 // [slots][3][384] fp32: (m, z, a) per run
-  int E;
-  const int32_t *dyn;          // optional device-side sizes (RAMP_DYN_*): E is then the launch bound
-  uint32_t *gate_flag;         // optional: workgroup 0 stores gate_seq here when it starts (ramp_track.gate_flag)
-  uint32_t gate_seq;
-};
 
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) upd_softagg_kernel(const SoftAggParams p) {
   constexpr int NMT = SAGG_NMT, NTW = 3, NW = 8, ROWS = SAGG_ROWS, BLK = SAGG_BLK;
@@ -1450,31 +1365,87 @@ __global__ void __launch_bounds__(512) upd_linear_kernel(const _Float16 *__restr
 constexpr int FG_BEST = 6;
 static bool use_big(int E) { return E >= 16384 && (long)E * MD * 4 < (1l << 32); }
 
-template <typename KernelT, typename ParamsT>
-static int big_launch(KernelT kernel, const ParamsT &p, int E, int nmt, int nw, bool with_red, hipStream_t st) {
-  const size_t lds = (size_t)16 * nmt * MXS * 2 + (with_red ? (size_t)2 * 16 * nmt * nw * 4 : 0);
-  if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return RAMP_ELAUNCH;
-  hipLaunchKernelGGL(kernel, dim3(ramp_cdiv(E, 16 * nmt)), dim3(64 * nw), lds, st, p);
-  RAMP_CHECK_LAUNCH();
-  return RAMP_OK;
-}
+// dynamic LDS of the launches below, against the 64 KiB a kernel gets unasked (ramp_launch_lds): one 64-row tile, the
+// wide-tile kernels' 16 nmt rows, the SoftAgg tile with its group ids.  The gru launch (100 KiB and up) and the wide fg
+// launch are the ones that need the attribute.
+constexpr size_t TILE_LDS = (size_t)MBM * MXS * 2;                                 // 64 x 392 x 2 = 50,176 B
+constexpr size_t big_lds(int nmt) { return (size_t)16 * nmt * MXS * 2; }
+constexpr size_t SAGG_LDS = (size_t)SAGG_ROWS * MXS * 2 + SAGG_ROWS * sizeof(int);   // 80 x 392 x 2 + 320 = 63,040 B
+static_assert(TILE_LDS == 50176 && TILE_LDS <= RAMP_LDS_DEFAULT_MAX, "c1 / c2, corr MLP, fg: no attribute needed");
+static_assert(big_lds(NBR_NMT) == 62720 && big_lds(NBR_NMT) <= RAMP_LDS_DEFAULT_MAX, "wide c1 / c2: no attribute needed");
+static_assert(SAGG_LDS == 63040 && SAGG_LDS <= RAMP_LDS_DEFAULT_MAX, "SoftAgg: no attribute needed");
 
 // 16-row tiles per workgroup of the gru launch (4 or 5: 64 or 80 rows): whichever needs fewer rounds of one-workgroup-per-CU
-// (ties: fewer row-rounds, 64).  With device-side sizes E is the launch bound and the live count a little below it: E_hint, the
-// caller's estimate, stands in for it when it is positive and below E
+// (ties: fewer row-rounds, 64) on the CURRENT device (256 CUs where there is none).  With device-side sizes E is the launch
+// bound and the live count a little below it: E_hint, the caller's estimate, stands in for it when it is positive and below E
 static int gru_tiles(int E, int E_hint) {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
+  // (the count is kept per device id, in a fixed table: asking the runtime on every launch showed in the host cost of a step)
+  constexpr int NDEV = 64;
+  static int cus_of[NDEV];
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) cus = 256;
+  else if (dev < NDEV && cus_of[dev] > 0) cus = cus_of[dev];
+  else {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    if (dev < NDEV) cus_of[dev] = cus;
   }
   const int El = (E_hint > 0 && E_hint < E) ? E_hint : E;
   const long r4 = (long)ramp_cdiv(ramp_cdiv(El, 64), cus) * 4, r5 = (long)ramp_cdiv(ramp_cdiv(El, 80), cus) * 5;
   return r5 < r4 ? 5 : 4;
 }
 
+// ---- the launchers (csrc/ramp_internal.h): validate the record, choose tile and instance, launch
+int ramp_i_upd_gru(const GruParams &p, int E_hint, hipStream_t st) {
+  if (p.E < 0) return RAMP_EINVAL;
+  if (p.E == 0) return RAMP_OK;
+  if (!p.x32 || !p.ln_w || !p.ln_b || !p.out32 || (!p.relu_t && !p.heads_w)) return RAMP_EINVAL;
+  for (int i = 0; i < 6; i++)
+    if (!p.wp[i] || !p.bias[i]) return RAMP_EINVAL;
+  if (p.heads_w && (!p.heads_b || !p.coords || !p.target || !p.weight || p.PP < 1)) return RAMP_EINVAL;
+  if (p.add_t && (!p.add_idx || !p.pre_w || !p.pre_b)) return RAMP_EINVAL;
+  if (p.add0_t && (!p.add0_idx || !p.add_t)) return RAMP_EINVAL;
+  const int mt = gru_tiles(p.E, E_hint), rows = 16 * mt;
+  const size_t lds = (size_t)2 * rows * MXS * 2 + 2 * rows * MWAVES * sizeof(float);   // x / h and sigmoid(gate) tiles + the LayerNorm tables
+  const dim3 grid(ramp_cdiv(p.E, rows)), block(64 * MWAVES);
+  return mt == 4 ? ramp_launch_lds(upd_gru_kernel<4>, grid, block, lds, st, p)
+                 : ramp_launch_lds(upd_gru_kernel<5>, grid, block, lds, st, p);
+}
+
+int ramp_i_upd_nbr(const NbrParams &p, hipStream_t st) {
+  if (p.E < 0) return RAMP_EINVAL;
+  if (p.E == 0) return RAMP_OK;
+  if (!p.net_in || !p.idx || !p.wa || !p.ba || !p.wb || !p.bb || !p.net_out || p.net_in == p.net_out) return RAMP_EINVAL;
+  if (use_big(p.E))
+    return ramp_launch_lds(upd_nbr_big_kernel<NBR_NMT, 8>, dim3(ramp_cdiv(p.E, 16 * NBR_NMT)), dim3(64 * 8), big_lds(NBR_NMT), st, p);
+  return ramp_launch_lds(upd_nbr_kernel, dim3(ramp_cdiv(p.E, MBM)), dim3(64 * MWAVES), TILE_LDS, st, p);
+}
+
+int ramp_i_upd_corr_mlp(const CorrTailParams &p, hipStream_t st) {
+  if (p.E < 0) return RAMP_EINVAL;
+  if (p.E == 0) return RAMP_OK;
+  if (!p.corr || p.corr_k <= 0 || (p.corr_k & 31) || !p.w1 || !p.b1 || !p.w2 || !p.b2 || !p.w3 || !p.b3 || !p.ln_w || !p.ln_b ||
+      !p.inp || !p.norm_w || !p.norm_b || !p.net_out || p.net == p.net_out)
+    return RAMP_EINVAL;
+  return ramp_launch_lds(upd_corr_tail_kernel<true>, dim3(ramp_cdiv(p.E, MBM)), dim3(64 * MWAVES), TILE_LDS, st, p);
+}
+
+static int ramp_i_upd_fg(const FgParams &p, hipStream_t st) {
+  if (p.E < 0) return RAMP_EINVAL;
+  if (p.E == 0) return RAMP_OK;
+  if (!p.x32 || !p.wf || !p.bf || !p.wg || !p.bg || !p.fg || (p.add_t && !p.add_idx)) return RAMP_EINVAL;
+  if (use_big(p.E))
+    return ramp_launch_lds(upd_fg_big_kernel<FG_BEST, 8>, dim3(ramp_cdiv(p.E, 16 * FG_BEST)), dim3(64 * 8), big_lds(FG_BEST), st, p);
+  return ramp_launch_lds(upd_fg_kernel, dim3(ramp_cdiv(p.E, MBM)), dim3(64 * MWAVES), TILE_LDS, st, p);
+}
+
+int ramp_i_upd_softagg(const SoftAggParams &p, hipStream_t st) {
+  if (p.E < 0) return RAMP_EINVAL;
+  if (p.E == 0) return RAMP_OK;
+  if (!p.x32 || !p.order || !p.gid || !p.wf || !p.bf || !p.wg || !p.bg || !p.frag || (p.add_t && !p.add_idx)) return RAMP_EINVAL;
+  return ramp_launch_lds(upd_softagg_kernel, dim3(ramp_cdiv(p.E, SAGG_ROWS)), dim3(512), SAGG_LDS, st, p);
+}
+
+// ---- the exported entry points (include/ramp_hip.h): host-side sizes (dyn = NULL).  The one place where position meets name
 extern "C" {
 
 #ifdef GRU_TRACE
@@ -1484,142 +1455,65 @@ int ramp_debug_gru_trace(long long *host, int n) {
 #endif
 size_t ramp_upd_mlp_lds_bytes(void) { return (size_t)2 * MBM * MXS * 2; }
 
-int ramp_i_upd_gru(const float *x32, const void *add0_t, const int32_t *add0_idx, const void *add_t, const int32_t *add_idx,
-                 const float *pre_w, const float *pre_b,
-                 float pre_eps, const void *const *wp_host, const float *const *bias_host, const float *ln_w,
-                 const float *ln_b, float eps, float *out32, void *relu_t, int E, const int32_t *dyn,
-                 const void *heads_w, const float *heads_b, const float *coords, float *target, float *weight, int P,
-                 float wd, float ht, int E_hint, void *stream) {
-  if (E < 0) return RAMP_EINVAL;
-  if (E == 0) return RAMP_OK;
-  if (!x32 || !wp_host || !bias_host || !ln_w || !ln_b || !out32 || (!relu_t && !heads_w)) return RAMP_EINVAL;
-  if (heads_w && (!heads_b || !coords || !target || !weight || P < 1)) return RAMP_EINVAL;
-  if (add_t && (!add_idx || !pre_w || !pre_b)) return RAMP_EINVAL;
-  if (add0_t && (!add0_idx || !add_t)) return RAMP_EINVAL;
-  GruParams p;
-  p.x32 = x32;
-  p.add0_t = (const _Float16 *)add0_t; p.add0_idx = add0_idx;
-  p.add_t = (const _Float16 *)add_t; p.add_idx = add_idx; p.pre_w = pre_w; p.pre_b = pre_b; p.pre_eps = pre_eps;
-  for (int i = 0; i < 6; i++) {
-    if (!wp_host[i] || !bias_host[i]) return RAMP_EINVAL;
-    p.wp[i] = (const _Float16 *)wp_host[i];
-    p.bias[i] = bias_host[i];
-  }
-  p.ln_w = ln_w; p.ln_b = ln_b; p.eps = eps; p.out32 = out32; p.relu_t = (_Float16 *)relu_t; p.E = E; p.dyn = dyn;
-  p.heads_w = (const _Float16 *)heads_w; p.heads_b = heads_b; p.coords = coords; p.target = target; p.weight = weight;
-  p.PP = P * P; p.ctr = (P / 2) * P + P / 2; p.wd = wd; p.ht = ht;
-  const int mt = gru_tiles(E, E_hint), rows = 16 * mt;
-  const size_t lds = (size_t)2 * rows * MXS * 2 + 2 * rows * MWAVES * sizeof(float);   // x / h and sigmoid(gate) tiles + the LayerNorm tables
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void *)upd_gru_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)((size_t)2 * 64 * MXS * 2 + 2 * 64 * MWAVES * sizeof(float))) != hipSuccess ||
-        hipFuncSetAttribute((const void *)upd_gru_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)((size_t)2 * 80 * MXS * 2 + 2 * 80 * MWAVES * sizeof(float))) != hipSuccess)
-      return RAMP_ELAUNCH;
-    attr_set = true;
-  }
-  if (mt == 5)
-    hipLaunchKernelGGL(upd_gru_kernel<5>, dim3(ramp_cdiv(E, rows)), dim3(64 * MWAVES), lds, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL(upd_gru_kernel<4>, dim3(ramp_cdiv(E, rows)), dim3(64 * MWAVES), lds, (hipStream_t)stream, p);
-  RAMP_CHECK_LAUNCH();
-  return RAMP_OK;
-}
-
-int ramp_i_upd_nbr(const float *net_in, const int64_t *idx, const void *wa, const float *ba, const void *wb,
-                 const float *bb, float *net_out, void *out_t, int E, const int32_t *dyn, void *stream) {
-  if (E < 0) return RAMP_EINVAL;
-  if (E == 0) return RAMP_OK;
-  if (!net_in || !idx || !wa || !ba || !wb || !bb || !net_out || net_in == net_out) return RAMP_EINVAL;
-  NbrParams p;
-  p.net_in = net_in; p.idx = idx; p.wa = (const _Float16 *)wa; p.wb = (const _Float16 *)wb; p.ba = ba; p.bb = bb;
-  p.net_out = net_out; p.out_t = (_Float16 *)out_t; p.E = E; p.dyn = dyn;
-  if (use_big(E)) return big_launch(upd_nbr_big_kernel<NBR_NMT, 8>, p, E, NBR_NMT, 8, false, (hipStream_t)stream);
-  const size_t lds = (size_t)MBM * MXS * 2;          // one tile (see the kernel)
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void *)upd_nbr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess)
-      return RAMP_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(upd_nbr_kernel, dim3(ramp_cdiv(E, MBM)), dim3(64 * MWAVES), lds, (hipStream_t)stream, p);
-  RAMP_CHECK_LAUNCH();
-  return RAMP_OK;
-}
-
-int ramp_i_upd_corr_mlp(const void *corr, int corr_k, const void *w1, const float *b1, const void *w2, const float *b2,
-                      const void *w3, const float *b3, const float *ln_w, const float *ln_b, float ln_eps,
-                      const float *net, const int64_t *net_map, const void *inp, const int64_t *inp_idx, long inp_mod,
-                      const float *norm_w, const float *norm_b, float norm_eps, float *net_out, int E, const int32_t *dyn, void *stream) {
-  if (E < 0) return RAMP_EINVAL;
-  if (E == 0) return RAMP_OK;
-  if (!corr || corr_k <= 0 || (corr_k & 31) || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !ln_w || !ln_b || !inp ||
-      !norm_w || !norm_b || !net_out || net == net_out)
-    return RAMP_EINVAL;
-  CorrTailParams p;
-  p.corr = (const _Float16 *)corr; p.w1 = (const _Float16 *)w1; p.b1 = b1; p.corr_k = corr_k; p.c1 = nullptr;
-  p.w2 = (const _Float16 *)w2; p.w3 = (const _Float16 *)w3; p.b2 = b2; p.b3 = b3;
-  p.ln_w = ln_w; p.ln_b = ln_b; p.ln_eps = ln_eps; p.net = net; p.net_map = net_map; p.inp = (const _Float16 *)inp;
-  p.inp_idx = inp_idx; p.inp_mod = inp_mod; p.norm_w = norm_w; p.norm_b = norm_b; p.norm_eps = norm_eps;
-  p.net_out = net_out; p.E = E; p.dyn = dyn;
-  const size_t lds = (size_t)MBM * MXS * 2;
-  hipLaunchKernelGGL(upd_corr_tail_kernel<true>, dim3(ramp_cdiv(E, MBM)), dim3(64 * MWAVES), lds, (hipStream_t)stream, p);
-  RAMP_CHECK_LAUNCH();
-  return RAMP_OK;
-}
-
-int ramp_i_upd_fg(const float *x32, const void *add_t, const int32_t *add_idx, float *x32_out, const void *wf,
-                const float *bf, const void *wg, const float *bg, void *fg, int E, const int32_t *dyn, void *stream) {
-  if (E < 0) return RAMP_EINVAL;
-  if (E == 0) return RAMP_OK;
-  if (!x32 || !wf || !bf || !wg || !bg || !fg || (add_t && !add_idx)) return RAMP_EINVAL;
-  FgParams p;
-  p.x32 = x32; p.add_t = (const _Float16 *)add_t; p.add_idx = add_idx; p.x32_out = x32_out;
-  p.wf = (const _Float16 *)wf; p.wg = (const _Float16 *)wg; p.bf = bf; p.bg = bg; p.fg = (_Float16 *)fg; p.E = E; p.dyn = dyn;
-  if (use_big(E)) return big_launch(upd_fg_big_kernel<FG_BEST, 8>, p, E, FG_BEST, 8, false, (hipStream_t)stream);
-  const size_t lds = (size_t)MBM * MXS * 2;
-  hipLaunchKernelGGL(upd_fg_kernel, dim3(ramp_cdiv(E, MBM)), dim3(64 * MWAVES), lds, (hipStream_t)stream, p);
-  RAMP_CHECK_LAUNCH();
-  return RAMP_OK;
-}
-
-
 int ramp_upd_gru_tile_rows(int E, int E_hint) { return 16 * gru_tiles(E, E_hint); }
-
-// ---- public entry points: host-side sizes (dyn = NULL)
-int ramp_upd_gru(const float *x32, const void *add_t, const int32_t *add_idx, const float *pre_w, const float *pre_b,
-                 float pre_eps, const void *const *wp_host, const float *const *bias_host, const float *ln_w,
-                 const float *ln_b, float eps, float *out32, void *relu_t, int E, void *stream) {
-  return ramp_i_upd_gru(x32, nullptr, nullptr, add_t, add_idx, pre_w, pre_b, pre_eps, wp_host, bias_host, ln_w, ln_b, eps, out32, relu_t, E, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr, 3, 0.f, 0.f, 0, stream);
-}
 
 int ramp_upd_gru_heads(const float *x32, const void *add_t, const int32_t *add_idx, const float *pre_w, const float *pre_b,
                        float pre_eps, const void *const *wp_host, const float *const *bias_host, const float *ln_w,
                        const float *ln_b, float eps, float *out32, const void *heads_w, const float *heads_b,
                        const float *coords, float *target, float *weight, int E, int P, float wd, float ht, void *stream) {
   if (!heads_w) return RAMP_EINVAL;
-  return ramp_i_upd_gru(x32, nullptr, nullptr, add_t, add_idx, pre_w, pre_b, pre_eps, wp_host, bias_host, ln_w, ln_b, eps, out32, nullptr, E, nullptr,
-                        heads_w, heads_b, coords, target, weight, P, wd, ht, 0, stream);
+  GruParams p = {};
+  p.E = E;
+  p.x32 = x32; p.add_t = (const _Float16 *)add_t; p.add_idx = add_idx;
+  p.pre_w = pre_w; p.pre_b = pre_b; p.pre_eps = pre_eps;
+  upd_gru_layers(p, wp_host, bias_host);
+  p.ln_w = ln_w; p.ln_b = ln_b; p.eps = eps; p.out32 = out32;
+  p.heads_w = (const _Float16 *)heads_w; p.heads_b = heads_b; p.coords = coords; p.target = target; p.weight = weight;
+  upd_patch_side(p, P);
+  p.wd = wd; p.ht = ht;
+  return ramp_i_upd_gru(p, 0, (hipStream_t)stream);
+}
+
+int ramp_upd_gru(const float *x32, const void *add_t, const int32_t *add_idx, const float *pre_w, const float *pre_b,
+                 float pre_eps, const void *const *wp_host, const float *const *bias_host, const float *ln_w,
+                 const float *ln_b, float eps, float *out32, void *relu_t, int E, void *stream) {
+  GruParams p = {};
+  p.E = E;
+  p.x32 = x32; p.add_t = (const _Float16 *)add_t; p.add_idx = add_idx;
+  p.pre_w = pre_w; p.pre_b = pre_b; p.pre_eps = pre_eps;
+  upd_gru_layers(p, wp_host, bias_host);
+  p.ln_w = ln_w; p.ln_b = ln_b; p.eps = eps; p.out32 = out32; p.relu_t = (_Float16 *)relu_t;
+  upd_patch_side(p, 3);
+  return ramp_i_upd_gru(p, 0, (hipStream_t)stream);
 }
 
 int ramp_upd_nbr(const float *net_in, const int64_t *idx, const void *wa, const float *ba, const void *wb,
                  const float *bb, float *net_out, void *out_t, int E, void *stream) {
-  return ramp_i_upd_nbr(net_in, idx, wa, ba, wb, bb, net_out, out_t, E, nullptr, stream);
+  NbrParams p = {};
+  p.net_in = net_in; p.idx = idx; p.wa = (const _Float16 *)wa; p.ba = ba; p.wb = (const _Float16 *)wb; p.bb = bb;
+  p.net_out = net_out; p.out_t = (_Float16 *)out_t; p.E = E;
+  return ramp_i_upd_nbr(p, (hipStream_t)stream);
 }
 
 int ramp_upd_corr_mlp(const void *corr, int corr_k, const void *w1, const float *b1, const void *w2, const float *b2,
                       const void *w3, const float *b3, const float *ln_w, const float *ln_b, float ln_eps,
                       const float *net, const int64_t *net_map, const void *inp, const int64_t *inp_idx, long inp_mod,
                       const float *norm_w, const float *norm_b, float norm_eps, float *net_out, int E, void *stream) {
-  return ramp_i_upd_corr_mlp(corr, corr_k, w1, b1, w2, b2, w3, b3, ln_w, ln_b, ln_eps, net, net_map, inp, inp_idx, inp_mod, norm_w, norm_b, norm_eps, net_out, E, nullptr, stream);
+  CorrTailParams p = {};
+  p.corr = (const _Float16 *)corr; p.corr_k = corr_k; p.w1 = (const _Float16 *)w1; p.b1 = b1;
+  p.w2 = (const _Float16 *)w2; p.b2 = b2; p.w3 = (const _Float16 *)w3; p.b3 = b3;
+  p.ln_w = ln_w; p.ln_b = ln_b; p.ln_eps = ln_eps; p.net = net; p.net_map = net_map; p.inp = (const _Float16 *)inp;
+  p.inp_idx = inp_idx; p.inp_mod = inp_mod; p.norm_w = norm_w; p.norm_b = norm_b; p.norm_eps = norm_eps;
+  p.net_out = net_out; p.E = E;
+  return ramp_i_upd_corr_mlp(p, (hipStream_t)stream);
 }
 
 int ramp_upd_fg(const float *x32, const void *add_t, const int32_t *add_idx, float *x32_out, const void *wf,
                 const float *bf, const void *wg, const float *bg, void *fg, int E, void *stream) {
-  return ramp_i_upd_fg(x32, add_t, add_idx, x32_out, wf, bf, wg, bg, fg, E, nullptr, stream);
+  FgParams p = {};
+  p.x32 = x32; p.add_t = (const _Float16 *)add_t; p.add_idx = add_idx; p.x32_out = x32_out;
+  p.wf = (const _Float16 *)wf; p.bf = bf; p.wg = (const _Float16 *)wg; p.bg = bg; p.fg = (_Float16 *)fg; p.E = E;
+  return ramp_i_upd_fg(p, (hipStream_t)stream);
 }
 
 int ramp_upd_linear(const void *x, const void *w_packed, const float *bias, void *y, int rows, const int32_t *rows_dev,
@@ -1633,35 +1527,16 @@ int ramp_upd_linear(const void *x, const void *w_packed, const float *bias, void
   return RAMP_OK;
 }
 
-
 size_t ramp_upd_softagg_frag_rows(int E, int max_groups) {
   return (size_t)(max_groups > 0 ? max_groups : 0) + (size_t)((E > 0 ? E : 0) + SAGG_BLK - 1) / SAGG_BLK + 1;
 }
 
-int ramp_i_upd_softagg(const float *x32, const void *add_t, const int32_t *add_idx, const int32_t *order, const int32_t *gid,
-                       const void *wf, const float *bf, const void *wg, const float *bg, float *frag, int E,
-                       const int32_t *dyn, void *stream, uint32_t *gate_flag, uint32_t gate_seq) {
-  if (E < 0) return RAMP_EINVAL;
-  if (E == 0) return RAMP_OK;
-  if (!x32 || !order || !gid || !wf || !bf || !wg || !bg || !frag || (add_t && !add_idx)) return RAMP_EINVAL;
-  SoftAggParams p;
-  p.gate_flag = gate_flag; p.gate_seq = gate_seq;
-  p.x32 = x32; p.add_t = (const _Float16 *)add_t; p.add_idx = add_idx; p.order = order; p.gid = gid;
-  p.wf = (const _Float16 *)wf; p.wg = (const _Float16 *)wg; p.bf = bf; p.bg = bg; p.frag = frag; p.E = E; p.dyn = dyn;
-  const size_t lds = (size_t)SAGG_ROWS * MXS * 2 + SAGG_ROWS * sizeof(int);
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void *)upd_softagg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return RAMP_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(upd_softagg_kernel, dim3(ramp_cdiv(E, SAGG_ROWS)), dim3(512), lds, (hipStream_t)stream, p);
-  RAMP_CHECK_LAUNCH();
-  return RAMP_OK;
-}
 int ramp_upd_softagg(const float *x32, const void *add_t, const int32_t *add_idx, const int32_t *order, const int32_t *gid,
                      const void *wf, const float *bf, const void *wg, const float *bg, float *frag, int E, void *stream) {
-  return ramp_i_upd_softagg(x32, add_t, add_idx, order, gid, wf, bf, wg, bg, frag, E, nullptr, stream, nullptr, 0);
+  SoftAggParams p = {};
+  p.x32 = x32; p.add_t = (const _Float16 *)add_t; p.add_idx = add_idx; p.order = order; p.gid = gid;
+  p.wf = (const _Float16 *)wf; p.bf = bf; p.wg = (const _Float16 *)wg; p.bg = bg; p.frag = frag; p.E = E;
+  return ramp_i_upd_softagg(p, (hipStream_t)stream);
 }
 int ramp_upd_softagg_finish(const float *frag, const int32_t *seg_start, const int32_t *ngroups, const void *wh,
                             const float *bh, void *hy, int max_groups, void *stream) {

@@ -22,6 +22,7 @@
 //     [K/32][24][2][64 lanes][8] fp16 -- plane 0: fp16(W 2^s), plane 1: fp16(W 2^s - plane 0); lane (q, j) of fragment
 //     (ks, nt) holds W[16 nt + j][32 ks + 8 q .. + 8]; followed by one float, 2^-s.
 #include "ramp_device.h"
+#include "ramp_internal.h"
 #include <stdlib.h>
 
 #define XD 384
@@ -158,7 +159,6 @@ __device__ __forceinline__ void x3_to_lds(_Float16 *Xh, _Float16 *Xl, const f4 (
     }
 }
 
-
 // Stage ROWS x (4 NV4) floats into the two LDS planes: ALL global loads of a thread are issued before the first conversion (a loop
 // that loads, converts and stores element by element waits for one memory round trip per iteration: twelve in a row per tile)
 template <int ROWS, int NV4, typename LoadT>
@@ -262,16 +262,6 @@ __device__ __forceinline__ void x3_tile_ln(f4 (&v)[MT][XNTW], const float *__res
 static size_t x3_lds_bytes(int mt, bool ln) { return (size_t)2 * 16 * mt * XS * 2 + (ln ? (size_t)2 * 16 * mt * XWAVES * 4 : 0); }
 
 // ------------------------------------------------------------------ c1 / c2 (ramp/net.py:77-82)
-struct X3NbrParams {
-  const float *net_in;         // [E][384]
-  const int64_t *idx;          // [E] neighbour row or -1
-  const _Float16 *wa, *wb;     // packed (x3)
-  const float *ba, *bb;        // fp32 biases
-  float *net_out;              // [E][384], must not alias net_in
-  int E;
-  const int32_t *dyn;
-};
-
 template <int MT>
 __global__ void __launch_bounds__(64 * XWAVES) X3_ATTR x3_nbr_kernel(const X3NbrParams p) {
   X3_COMMON(MT);
@@ -306,25 +296,6 @@ __global__ void __launch_bounds__(64 * XWAVES) X3_ATTR x3_nbr_kernel(const X3Nbr
 
 // ------------------------------------------------------------------ correlation MLP + Update.norm (ramp/net.py:57-62, 71-74)
 //   c = Linear3(relu(LayerNorm(Linear2(relu(Linear1(corr))))));  net = LayerNorm((net_prev + inp) + c)
-struct X3CorrMlpParams {
-  const float *corr;           // [E][corr_k] fp32 (corr_k a multiple of 32: 896 = 882 + zero tail)
-  int corr_k;
-  const _Float16 *w1, *w2, *w3;
-  const float *b1, *b2, *b3;
-  const float *ln_w, *ln_b;    // corr[3]
-  float ln_eps;
-  const float *net;            // [*][384] previous hidden state or NULL (zeros)
-  const int64_t *net_map;      // [E] row of `net` per factor (-1: zero row) or NULL (identity)
-  const float *inp;            // context table [*][384] fp32
-  const int64_t *inp_idx;      // [E] row of `inp` (modulo inp_mod when > 0) or NULL (identity)
-  long inp_mod;
-  const float *norm_w, *norm_b;
-  float norm_eps;
-  float *net_out;              // [E][384]
-  int E;
-  const int32_t *dyn;
-};
-
 template <int MT>
 __global__ void __launch_bounds__(64 * XWAVES) X3_ATTR x3_corr_mlp_kernel(const X3CorrMlpParams p) {
   X3_COMMON(MT);
@@ -401,18 +372,6 @@ __global__ void __launch_bounds__(64 * XWAVES) X3_ATTR x3_corr_mlp_kernel(const 
 }
 
 // ------------------------------------------------------------------ SoftAgg front half: [f(x) | g(x)] rows (ramp/blocks.py:42-46)
-struct X3FgParams {
-  const float *x32;            // [E][384]
-  const float *add_t;          // optional [groups][384] fp32: x = x32 + add_t[add_idx]
-  const int32_t *add_idx;
-  float *x32_out;              // optional: x written back (may be x32)
-  const _Float16 *wf, *wg;
-  const float *bf, *bg;
-  float *fg;                   // [E][768] fp32
-  int E;
-  const int32_t *dyn;
-};
-
 template <int MT>
 __global__ void __launch_bounds__(64 * XWAVES) X3_ATTR x3_fg_kernel(const X3FgParams p) {
   X3_COMMON(MT);
@@ -493,16 +452,6 @@ __global__ void __launch_bounds__(X3SEG_R *X3SEG_T) x3_segment_softmax_kernel(co
 }
 
 // ------------------------------------------------------------------ one Linear 384 -> 384 on a table of rows (SoftAgg's h)
-struct X3LinParams {
-  const float *x;              // [rows][384]
-  const _Float16 *w;
-  const float *b;
-  float *y;                    // [rows][384]
-  int E;                       // rows (launch bound)
-  const int32_t *rows_dev;     // optional device-side row count
-  const int32_t *dyn;          // unused (X3_COMMON)
-};
-
 __global__ void __launch_bounds__(64 * XWAVES) x3_linear_kernel(const X3LinParams p) {
   constexpr int MT = 1;
   constexpr int ROWS = 16;
@@ -534,29 +483,6 @@ __global__ void __launch_bounds__(64 * XWAVES) x3_linear_kernel(const X3LinParam
 }
 
 // ------------------------------------------------------------------ gru (+ heads) (ramp/net.py:49-54, 64-66, 87-90; ramp/blocks.py:15-31)
-struct X3GruParams {
-  const float *x32;            // [E][384]: the residual stream entering gru[0]
-  const float *add0_t;         // optional first expand-and-add table (fp32) -- (x32 + add0_t[add0_idx]) + add_t[add_idx]
-  const int32_t *add0_idx;
-  const float *add_t;          // optional: with it x = LayerNorm_pre(x32 (+ add0) + add_t[add_idx]) (gru[0]); without: x = x32
-  const int32_t *add_idx;
-  const float *pre_w, *pre_b;
-  float pre_eps;
-  const _Float16 *wp[6];       // g1_gate, g1_r1, g1_r2, g2_gate, g2_r1, g2_r2 (x3 packs)
-  const float *bias[6];
-  const float *ln_w, *ln_b;    // gru[2]
-  float eps;
-  float *out32;                // [E][384]
-  float *relu32;               // optional [E][384]: relu(result)
-  const float *heads_w;        // optional [4][384] fp32 (d rows 0..1, w rows 0..1) -> target / weight
-  const float *heads_b;        // [4]
-  const float *coords;         // [E][2][PP]
-  float *target, *weight;      // [E][2]
-  int PP, ctr;
-  float wd, ht;
-  int E;
-  const int32_t *dyn;
-};
 
 __device__ __forceinline__ float x3_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
@@ -708,56 +634,74 @@ __global__ void __launch_bounds__(64 * XWAVES) x3_gru_kernel(const X3GruParams p
 }
 
 // ------------------------------------------------------------------ launchers
+// (csrc/ramp_internal.h): validate the record, launch on tiles of 16 mt rows.  Dynamic LDS: x3_lds_bytes -- 50,176 / 52,224 B
+// for the three lighter chains, 25,088 B for the Linear, 78,336 B for gru, the one launch that needs the attribute
+static dim3 x3_grid(int rows, int mt) { return dim3(ramp_cdiv(rows, 16 * mt)); }
 
-template <typename KernelT, typename ParamsT>
-static int x3_launch(KernelT kernel, const ParamsT &p, int rows, int mt, bool ln, hipStream_t st) {
-  const size_t lds = x3_lds_bytes(mt, ln);
-  // (per call: the attribute is per device, and a process may drive several)
-  if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return RAMP_ELAUNCH;
-  hipLaunchKernelGGL(kernel, dim3(ramp_cdiv(rows, 16 * mt)), dim3(64 * XWAVES), lds, st, p);
-  RAMP_CHECK_LAUNCH();
-  return RAMP_OK;
+int ramp_i_x3_nbr(const X3NbrParams &p, hipStream_t st) {
+  if (p.E < 0) return RAMP_EINVAL;
+  if (p.E == 0) return RAMP_OK;
+  if (!p.net_in || !p.idx || !p.wa || !p.ba || !p.wb || !p.bb || !p.net_out || p.net_in == p.net_out) return RAMP_EINVAL;
+  return ramp_launch_lds(x3_nbr_kernel<X3_MT>, x3_grid(p.E, X3_MT), dim3(64 * XWAVES), x3_lds_bytes(X3_MT, false), st, p);
 }
 
+int ramp_i_x3_corr_mlp(const X3CorrMlpParams &p, hipStream_t st) {
+  if (p.E < 0) return RAMP_EINVAL;
+  if (p.E == 0) return RAMP_OK;
+  if (!p.corr || p.corr_k <= 0 || (p.corr_k & 31) || !p.w1 || !p.b1 || !p.w2 || !p.b2 || !p.w3 || !p.b3 || !p.ln_w || !p.ln_b ||
+      !p.inp || !p.norm_w || !p.norm_b || !p.net_out || p.net == p.net_out)
+    return RAMP_EINVAL;
+  return ramp_launch_lds(x3_corr_mlp_kernel<X3_MT>, x3_grid(p.E, X3_MT), dim3(64 * XWAVES), x3_lds_bytes(X3_MT, true), st, p);
+}
+
+int ramp_i_x3_fg(const X3FgParams &p, hipStream_t st) {
+  if (p.E < 0) return RAMP_EINVAL;
+  if (p.E == 0) return RAMP_OK;
+  if (!p.x32 || !p.wf || !p.bf || !p.wg || !p.bg || !p.fg || (p.add_t && !p.add_idx)) return RAMP_EINVAL;
+  return ramp_launch_lds(x3_fg_kernel<X3_MT>, x3_grid(p.E, X3_MT), dim3(64 * XWAVES), x3_lds_bytes(X3_MT, false), st, p);
+}
+
+int ramp_i_x3_gru(const X3GruParams &p, hipStream_t st) {
+  if (p.E < 0) return RAMP_EINVAL;
+  if (p.E == 0) return RAMP_OK;
+  if (!p.x32 || !p.ln_w || !p.ln_b || !p.out32) return RAMP_EINVAL;
+  for (int i = 0; i < 6; i++)
+    if (!p.wp[i] || !p.bias[i]) return RAMP_EINVAL;
+  if (p.heads_w && (!p.heads_b || !p.coords || !p.target || !p.weight || p.PP < 1)) return RAMP_EINVAL;
+  if (p.add_t && (!p.add_idx || !p.pre_w || !p.pre_b)) return RAMP_EINVAL;
+  if (p.add0_t && (!p.add0_idx || !p.add_t)) return RAMP_EINVAL;
+  return ramp_launch_lds(x3_gru_kernel<X3_GRU_MT>, x3_grid(p.E, X3_GRU_MT), dim3(64 * XWAVES), x3_lds_bytes(X3_GRU_MT, true), st, p);
+}
+
+// ---- the exported entry points (include/ramp_hip.h): host-side sizes (dyn = NULL).  The one place where position meets name
 extern "C" {
 
-int ramp_i_x3_nbr(const float *net_in, const int64_t *idx, const void *wa, const float *ba, const void *wb, const float *bb,
-                  float *net_out, int E, const int32_t *dyn, void *stream) {
-  if (E < 0) return RAMP_EINVAL;
-  if (E == 0) return RAMP_OK;
-  if (!net_in || !idx || !wa || !ba || !wb || !bb || !net_out || net_in == net_out) return RAMP_EINVAL;
-  X3NbrParams p;
-  p.net_in = net_in; p.idx = idx; p.wa = (const _Float16 *)wa; p.wb = (const _Float16 *)wb; p.ba = ba; p.bb = bb;
-  p.net_out = net_out; p.E = E; p.dyn = dyn;
-  return x3_launch(x3_nbr_kernel<X3_MT>, p, E, X3_MT, false, (hipStream_t)stream);
+int ramp_x3_nbr(const float *net_in, const int64_t *idx, const void *wa, const float *ba, const void *wb, const float *bb,
+                float *net_out, int E, void *stream) {
+  X3NbrParams p = {};
+  p.net_in = net_in; p.idx = idx; p.wa = (const _Float16 *)wa; p.ba = ba; p.wb = (const _Float16 *)wb; p.bb = bb;
+  p.net_out = net_out; p.E = E;
+  return ramp_i_x3_nbr(p, (hipStream_t)stream);
 }
 
-int ramp_i_x3_corr_mlp(const float *corr, int corr_k, const void *w1, const float *b1, const void *w2, const float *b2,
-                       const void *w3, const float *b3, const float *ln_w, const float *ln_b, float ln_eps, const float *net,
-                       const int64_t *net_map, const float *inp, const int64_t *inp_idx, long inp_mod, const float *norm_w,
-                       const float *norm_b, float norm_eps, float *net_out, int E, const int32_t *dyn, void *stream) {
-  if (E < 0) return RAMP_EINVAL;
-  if (E == 0) return RAMP_OK;
-  if (!corr || corr_k <= 0 || (corr_k & 31) || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !ln_w || !ln_b || !inp || !norm_w ||
-      !norm_b || !net_out || net == net_out)
-    return RAMP_EINVAL;
-  X3CorrMlpParams p;
-  p.corr = corr; p.corr_k = corr_k; p.w1 = (const _Float16 *)w1; p.w2 = (const _Float16 *)w2; p.w3 = (const _Float16 *)w3;
-  p.b1 = b1; p.b2 = b2; p.b3 = b3; p.ln_w = ln_w; p.ln_b = ln_b; p.ln_eps = ln_eps; p.net = net; p.net_map = net_map;
+int ramp_x3_corr_mlp(const float *corr, int corr_k, const void *w1, const float *b1, const void *w2, const float *b2,
+                     const void *w3, const float *b3, const float *ln_w, const float *ln_b, float ln_eps, const float *net,
+                     const int64_t *net_map, const float *inp, const int64_t *inp_idx, long inp_mod, const float *norm_w,
+                     const float *norm_b, float norm_eps, float *net_out, int E, void *stream) {
+  X3CorrMlpParams p = {};
+  p.corr = corr; p.corr_k = corr_k; p.w1 = (const _Float16 *)w1; p.b1 = b1; p.w2 = (const _Float16 *)w2; p.b2 = b2;
+  p.w3 = (const _Float16 *)w3; p.b3 = b3; p.ln_w = ln_w; p.ln_b = ln_b; p.ln_eps = ln_eps; p.net = net; p.net_map = net_map;
   p.inp = inp; p.inp_idx = inp_idx; p.inp_mod = inp_mod; p.norm_w = norm_w; p.norm_b = norm_b; p.norm_eps = norm_eps;
-  p.net_out = net_out; p.E = E; p.dyn = dyn;
-  return x3_launch(x3_corr_mlp_kernel<X3_MT>, p, E, X3_MT, true, (hipStream_t)stream);
+  p.net_out = net_out; p.E = E;
+  return ramp_i_x3_corr_mlp(p, (hipStream_t)stream);
 }
 
-int ramp_i_x3_fg(const float *x32, const float *add_t, const int32_t *add_idx, float *x32_out, const void *wf, const float *bf,
-                 const void *wg, const float *bg, float *fg, int E, const int32_t *dyn, void *stream) {
-  if (E < 0) return RAMP_EINVAL;
-  if (E == 0) return RAMP_OK;
-  if (!x32 || !wf || !bf || !wg || !bg || !fg || (add_t && !add_idx)) return RAMP_EINVAL;
-  X3FgParams p;
-  p.x32 = x32; p.add_t = add_t; p.add_idx = add_idx; p.x32_out = x32_out; p.wf = (const _Float16 *)wf;
-  p.wg = (const _Float16 *)wg; p.bf = bf; p.bg = bg; p.fg = fg; p.E = E; p.dyn = dyn;
-  return x3_launch(x3_fg_kernel<X3_MT>, p, E, X3_MT, false, (hipStream_t)stream);
+int ramp_x3_fg(const float *x32, const float *add_t, const int32_t *add_idx, float *x32_out, const void *wf, const float *bf,
+               const void *wg, const float *bg, float *fg, int E, void *stream) {
+  X3FgParams p = {};
+  p.x32 = x32; p.add_t = add_t; p.add_idx = add_idx; p.x32_out = x32_out; p.wf = (const _Float16 *)wf; p.bf = bf;
+  p.wg = (const _Float16 *)wg; p.bg = bg; p.fg = fg; p.E = E;
+  return ramp_i_x3_fg(p, (hipStream_t)stream);
 }
 
 int ramp_x3_segment_softmax(const float *fg, const int32_t *order, const int32_t *seg_start, const int32_t *ngroups, float *y,
@@ -776,58 +720,25 @@ int ramp_x3_linear(const float *x, const void *w_packed, const float *bias, floa
   if (rows < 0) return RAMP_EINVAL;
   if (rows == 0) return RAMP_OK;
   if (!x || !w_packed || !bias || !y) return RAMP_EINVAL;
-  X3LinParams p;
-  p.x = x; p.w = (const _Float16 *)w_packed; p.b = bias; p.y = y; p.E = rows; p.rows_dev = rows_dev; p.dyn = nullptr;
-  return x3_launch(x3_linear_kernel, p, rows, 1, false, (hipStream_t)stream);
+  X3LinParams p = {};
+  p.x = x; p.w = (const _Float16 *)w_packed; p.b = bias; p.y = y; p.E = rows; p.rows_dev = rows_dev;
+  return ramp_launch_lds(x3_linear_kernel, x3_grid(rows, 1), dim3(64 * XWAVES), x3_lds_bytes(1, false), (hipStream_t)stream, p);
 }
 
-int ramp_i_x3_gru(const float *x32, const float *add0_t, const int32_t *add0_idx, const float *add_t, const int32_t *add_idx,
-                  const float *pre_w, const float *pre_b, float pre_eps, const void *const *wp_host,
-                  const float *const *bias_host, const float *ln_w, const float *ln_b, float eps, float *out32, float *relu32,
-                  int E, const int32_t *dyn, const float *heads_w, const float *heads_b, const float *coords, float *target,
-                  float *weight, int P, float wd, float ht, void *stream) {
-  if (E < 0) return RAMP_EINVAL;
-  if (E == 0) return RAMP_OK;
-  if (!x32 || !wp_host || !bias_host || !ln_w || !ln_b || !out32) return RAMP_EINVAL;
-  if (heads_w && (!heads_b || !coords || !target || !weight || P < 1)) return RAMP_EINVAL;
-  if (add_t && (!add_idx || !pre_w || !pre_b)) return RAMP_EINVAL;
-  if (add0_t && (!add0_idx || !add_t)) return RAMP_EINVAL;
-  X3GruParams p;
-  p.x32 = x32; p.add0_t = add0_t; p.add0_idx = add0_idx; p.add_t = add_t; p.add_idx = add_idx;
-  p.pre_w = pre_w; p.pre_b = pre_b; p.pre_eps = pre_eps;
-  for (int i = 0; i < 6; i++) {
-    if (!wp_host[i] || !bias_host[i]) return RAMP_EINVAL;
-    p.wp[i] = (const _Float16 *)wp_host[i];
-    p.bias[i] = bias_host[i];
-  }
-  p.ln_w = ln_w; p.ln_b = ln_b; p.eps = eps; p.out32 = out32; p.relu32 = relu32; p.heads_w = heads_w; p.heads_b = heads_b;
-  p.coords = coords; p.target = target; p.weight = weight; p.PP = P * P; p.ctr = (P / 2) * P + P / 2; p.wd = wd; p.ht = ht;
-  p.E = E; p.dyn = dyn;
-  return x3_launch(x3_gru_kernel<X3_GRU_MT>, p, E, X3_GRU_MT, true, (hipStream_t)stream);
-}
-
-// ---- public entry points: host-side sizes
-int ramp_x3_nbr(const float *net_in, const int64_t *idx, const void *wa, const float *ba, const void *wb, const float *bb,
-                float *net_out, int E, void *stream) {
-  return ramp_i_x3_nbr(net_in, idx, wa, ba, wb, bb, net_out, E, nullptr, stream);
-}
-int ramp_x3_corr_mlp(const float *corr, int corr_k, const void *w1, const float *b1, const void *w2, const float *b2,
-                     const void *w3, const float *b3, const float *ln_w, const float *ln_b, float ln_eps, const float *net,
-                     const int64_t *net_map, const float *inp, const int64_t *inp_idx, long inp_mod, const float *norm_w,
-                     const float *norm_b, float norm_eps, float *net_out, int E, void *stream) {
-  return ramp_i_x3_corr_mlp(corr, corr_k, w1, b1, w2, b2, w3, b3, ln_w, ln_b, ln_eps, net, net_map, inp, inp_idx, inp_mod, norm_w,
-                            norm_b, norm_eps, net_out, E, nullptr, stream);
-}
-int ramp_x3_fg(const float *x32, const float *add_t, const int32_t *add_idx, float *x32_out, const void *wf, const float *bf,
-               const void *wg, const float *bg, float *fg, int E, void *stream) {
-  return ramp_i_x3_fg(x32, add_t, add_idx, x32_out, wf, bf, wg, bg, fg, E, nullptr, stream);
-}
 int ramp_x3_gru(const float *x32, const float *add0_t, const int32_t *add0_idx, const float *add_t, const int32_t *add_idx,
                 const float *pre_w, const float *pre_b, float pre_eps, const void *const *wp_host, const float *const *bias_host,
                 const float *ln_w, const float *ln_b, float eps, float *out32, float *relu32, int E, const float *heads_w,
                 const float *heads_b, const float *coords, float *target, float *weight, int P, float wd, float ht, void *stream) {
-  return ramp_i_x3_gru(x32, add0_t, add0_idx, add_t, add_idx, pre_w, pre_b, pre_eps, wp_host, bias_host, ln_w, ln_b, eps, out32,
-                       relu32, E, nullptr, heads_w, heads_b, coords, target, weight, P, wd, ht, stream);
+  X3GruParams p = {};
+  p.E = E;
+  p.x32 = x32; p.add0_t = add0_t; p.add0_idx = add0_idx; p.add_t = add_t; p.add_idx = add_idx;
+  p.pre_w = pre_w; p.pre_b = pre_b; p.pre_eps = pre_eps;
+  upd_gru_layers(p, wp_host, bias_host);
+  p.ln_w = ln_w; p.ln_b = ln_b; p.eps = eps; p.out32 = out32; p.relu32 = relu32;
+  p.heads_w = heads_w; p.heads_b = heads_b; p.coords = coords; p.target = target; p.weight = weight;
+  upd_patch_side(p, P);
+  p.wd = wd; p.ht = ht;
+  return ramp_i_x3_gru(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -233,42 +233,103 @@ class FusedUpdate:
 
     def seg(self, fg, groups, max_groups):
         y = torch.empty(max(max_groups, 1), 384, dtype=self.dtype, device=fg.device)     # the kernel writes every row
-        check(lib().ramp_upd_segment_softmax(ptr(fg), ptr(groups.order), ptr(groups.seg_start), ptr(groups.ngroups),
-                                             ptr(y), int(max_groups), _code[self.dtype], stream()),
-              "ramp_upd_segment_softmax")
+        grp = (ptr(groups.order), ptr(groups.seg_start), ptr(groups.ngroups))
+        if self.use_x3:
+            check(lib().ramp_x3_segment_softmax(ptr(fg), *grp, ptr(y), int(max_groups), stream()), "ramp_x3_segment_softmax")
+        else:
+            check(lib().ramp_upd_segment_softmax(ptr(fg), *grp, ptr(y), int(max_groups), _code[self.dtype], stream()),
+                  "ramp_upd_segment_softmax")
         return y
 
-    # (single stages of the fp16 chains: tests/test_ops_gpu.py, tests/test_fp16_rounding_gpu.py and tools/mb_softagg.py hold
-    # them against their references through these three; hidden() does not use them)
-    def fg(self, net32, add_t, add_idx, pack, E):
-        """[f(x) | g(x)] of x = net32 (+ add_t[add_idx], written back to net32): csrc/update_mlp.hip::upd_fg_kernel"""
+    # ------------------------------------------------------------------ single stages of the fused chains
+    # One wrapper per exported stage, on the module's own packs (fg, softagg and h_lin are handed theirs, as they always were):
+    # ramp_upd_* (fp16 features) or ramp_x3_* (fp32 features) by the instance's precision, outputs allocated here.  The tests and the tools under tools/ hold each stage against its reference
+    # through these; hidden() does not use them (it is one call, ramp_update_forward).  add / add0 = (table, idx): the rows
+    # table[idx] of a SoftAgg table, added to the state on the way in.
+    def _stage(self, name):
+        name = ("ramp_x3_" if self.use_x3 else "ramp_upd_") + name
+        fn = getattr(lib(), name)
+        return lambda *args: check(fn(*args, stream()), name)
+
+    def corr_mlp(self, corr, net, net_map, inp, inp_idx, inp_mod):
+        """LayerNorm((net[net_map] + inp[inp_idx % inp_mod]) + corr-MLP(corr)) for corr [E, 896]; net None: zeros, net_map /
+        inp_idx None: row e"""
+        w, E = self.weights(), corr.shape[0]
+        ln, nm = w["corr_ln"], w["norm"]
+        out = torch.empty(E, 384, dtype=torch.float32, device=corr.device)
+        self._stage("corr_mlp")(ptr(corr), CORR_ROW, *map(ptr, w["corr1_pack"] + w["tail_pack"]), ptr(ln[0]), ptr(ln[1]),
+                                float(ln[2]), ptr(net), ptr(net_map), ptr(inp), ptr(inp_idx), int(inp_mod), ptr(nm[0]),
+                                ptr(nm[1]), float(nm[2]), ptr(out), E)
+        return out
+
+    def nbr(self, net_in, idx, which, want_t=False):
+        """net_in + Lb(relu(La(mask * net_in[idx]))) for the temporal-neighbour MLP `which` = "c1" / "c2" (idx -1: none).
+        want_t (fp16 features): also the result's fp16 copy, (out, out_t)"""
+        E = net_in.shape[0]
+        out = torch.empty_like(net_in)
+        out_t = torch.empty(E, 384, dtype=self.dtype, device=net_in.device) if want_t else None
+        self._stage("nbr")(ptr(net_in), ptr(idx), *map(ptr, self.weights()[which + "_pack"]), ptr(out),
+                           *(() if self.use_x3 else (ptr(out_t),)), E)
+        return (out, out_t) if want_t else out
+
+    def fg(self, net32, add_t, add_idx, pack, E, write_back=True):
+        """[f(x) | g(x)] [E, 768] for x = net32 (+ add_t[add_idx], written back to net32 unless write_back is off); pack: the
+        module's kk_fg_pack / ij_fg_pack"""
         out = torch.empty(E, 768, dtype=self.dtype, device=net32.device)
-        wf, bf, wg, bg = pack
-        check(lib().ramp_upd_fg(ptr(net32), ptr(add_t), ptr(add_idx), ptr(net32) if add_t is not None else None,
-                                ptr(wf), ptr(bf), ptr(wg), ptr(bg), ptr(out), E, stream()), "ramp_upd_fg")
+        self._stage("fg")(ptr(net32), ptr(add_t), ptr(add_idx), ptr(net32) if add_t is not None and write_back else None,
+                          *map(ptr, pack), ptr(out), E)
         return out
 
     def softagg(self, net32, add_t, add_idx, fg_pack, h_pack, groups, max_groups, E):
-        """h(segment softmax-sum of f(x), g(x)) for x = net32 (+ add_t[add_idx]) without the [E, 768] rows:
+        """fp16 features: h(segment softmax-sum of f(x), g(x)) for x = net32 (+ add_t[add_idx]) without the [E, 768] rows:
         csrc/update_mlp.hip::upd_softagg_kernel + upd_softagg_finish_kernel"""
         G = max(int(max_groups), 1)
-        rows = lib().ramp_upd_softagg_frag_rows(E, G)
-        frag = torch.empty(rows, 3, 384, dtype=torch.float32, device=net32.device)
-        wf, bf, wg, bg = fg_pack
-        check(lib().ramp_upd_softagg(ptr(net32), ptr(add_t), ptr(add_idx), ptr(groups.order), ptr(groups.gid), ptr(wf), ptr(bf),
-                                     ptr(wg), ptr(bg), ptr(frag), E, stream()), "ramp_upd_softagg")
+        frag = torch.empty(lib().ramp_upd_softagg_frag_rows(E, G), 3, 384, dtype=torch.float32, device=net32.device)
+        self._stage("softagg")(ptr(net32), ptr(add_t), ptr(add_idx), ptr(groups.order), ptr(groups.gid), *map(ptr, fg_pack),
+                               ptr(frag), E)
         hy = torch.empty(G, 384, dtype=self.dtype, device=net32.device)
-        check(lib().ramp_upd_softagg_finish(ptr(frag), ptr(groups.seg_start), ptr(groups.ngroups), ptr(h_pack[0]),
-                                            ptr(h_pack[1]), ptr(hy), G, stream()), "ramp_upd_softagg_finish")
+        self._stage("softagg_finish")(ptr(frag), ptr(groups.seg_start), ptr(groups.ngroups), *map(ptr, h_pack), ptr(hy), G)
         return hy
 
     def h_lin(self, y, pack, groups):
-        """SoftAgg's `h` Linear on the group table, rows below the device-side group count only
-        (csrc/update_mlp.hip::upd_linear_kernel)"""
-        out = torch.empty_like(y)
-        check(lib().ramp_upd_linear(ptr(y), ptr(pack[0]), ptr(pack[1]), ptr(out), y.shape[0], ptr(groups.ngroups),
-                                    stream()), "ramp_upd_linear")
+        """SoftAgg's `h` Linear on the group table y, rows below the device-side group count only (fp32 features: the other
+        rows are zero); pack: the module's kk_h_pack / ij_h_pack"""
+        out = torch.zeros_like(y) if self.use_x3 else torch.empty_like(y)
+        self._stage("linear")(ptr(y), *map(ptr, pack), ptr(out), y.shape[0], ptr(groups.ngroups))
         return out
+
+    def gru(self, x32, add=None, add0=None, heads_at=None):
+        """gru (LayerNorm, GatedResidual, LayerNorm, GatedResidual) on x = LayerNorm_pre((x32 (+ add0)) + add); without add x32
+        is gru[0]'s output already.  add0: fp32 features only (ramp_upd_gru takes one table).  Returns (out32, relu copy in
+        self.dtype) -- or, with heads_at = (coords [E,2,P,P], wd, ht), (out32, target, weight) from the launch's epilogue"""
+        if add0 is not None and not self.use_x3:
+            raise ValueError("FusedUpdate.gru: add0 is the fp32 chains'; the fp16 export takes one table")
+        w, E, x3 = self.weights(), x32.shape[0], self.use_x3
+        new = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=x32.device)
+        ln1, ln2 = w["ln1"], w["ln2"]
+        out32 = new(E, 384)
+        args = [ptr(x32)] + ([ptr(t) for t in add0 or (None, None)] if x3 else [])
+        args += [ptr(add[0]), ptr(add[1]), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2])] if add else [None, None, None, None, 0.0]
+        args += [*w["gru_pack"][2:], ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out32)]
+        if heads_at is None:
+            relu = new(E, 384, dtype=self.dtype)
+            self._stage("gru")(*args, ptr(relu), E, *((None,) * 5 + (3, 0.0, 0.0) if x3 else ()))
+            return out32, relu
+        coords, wd, ht = heads_at
+        target, weight = new(1, E, 2), new(1, E, 2)
+        heads = [*map(ptr, w["heads_pack"]), ptr(coords), ptr(target), ptr(weight)]
+        size = [coords.shape[-1], float(wd), float(ht)]
+        self._stage("gru" if x3 else "gru_heads")(*args, *([None, E] + heads if x3 else heads + [E]), *size)
+        return out32, target, weight
+
+    def heads_linear(self, relu_t, coords, wd, ht):
+        """fp16 features: (target, weight) from the relu copy -- the two heads' Linear layers and ramp_upd_heads's epilogue in one
+        launch (csrc/update.hip::upd_heads_linear_f16_kernel)"""
+        E = relu_t.shape[0]
+        target, weight = (torch.empty(1, E, 2, dtype=torch.float32, device=relu_t.device) for _ in range(2))
+        self._stage("heads_linear")(ptr(relu_t), *map(ptr, self.weights()["heads_pack"]), ptr(coords), ptr(target), ptr(weight),
+                                    E, coords.shape[-1], float(wd), float(ht))
+        return target, weight
 
     def _hidden_gemm(self, net, inp_table, inp_idx, inp_mod, corr, plan, net_map, net32_buf=None, out32_buf=None):
         """hidden() from library GEMMs (hipBLASLt through torch, bias / bias+ReLU epilogues) and the row kernels of

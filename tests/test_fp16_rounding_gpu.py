@@ -48,6 +48,7 @@ def test_upd_linear_is_fp16_of_the_exact_sum():
         w, b = lin.weight.half().float(), lin.bias.half().float()
         y = torch.full((rows, 384), 7.0, device="cuda").half()
         nd = torch.tensor([live], dtype=torch.int32, device="cuda")
+        # (a direct call: a freshly packed Linear and a poisoned output, not the module's operands)
         check(lib().ramp_upd_linear(ptr(x), ptr(pack_linear_f16(lin.weight)), ptr(b.contiguous()), ptr(y), rows, ptr(nd),
                                     stream()), "ramp_upd_linear")
         ex, m = rr.linear_ref(x[:live], w, b)
@@ -73,7 +74,6 @@ def test_fused_chains_against_the_rounding_emulator(E):
     upd_nbr_big_kernel with NMT = 5 (80 rows), upd_fg_big_kernel with NMT = 6 (96 rows); E = 41003: upd_gru_kernel<4> again and the same
     big kernels, with other partial last tiles.  upd_corr_mlp (64 rows), SoftAgg (80 sorted positions per workgroup)
     and the heads have one instantiation each; none of the E is a multiple of a tile."""
-    check, lib, ptr, stream = _ptr()
     fu, w, emu, upd = _setup()
     g = torch.Generator().manual_seed(17)
     rnd = lambda *s, sc=0.5: (torch.randn(*s, generator=g) * sc).cuda()
@@ -86,12 +86,7 @@ def test_fused_chains_against_the_rounding_emulator(E):
     # --- upd_gru (with the prologue, then without), relu copy, heads in the epilogue
     x32, hy = rnd(E, 384), rnd(G, 384).half()
     gid = torch.randint(0, G, (E,), generator=g).int().cuda()
-    out32 = torch.empty(E, 384, device="cuda")
-    relu_t = torch.empty(E, 384, dtype=torch.half, device="cuda")
-    _, _, wptr, bptr = w["gru_pack"]
-    ln1, ln2 = w["ln1"], w["ln2"]
-    check(lib().ramp_upd_gru(ptr(x32), ptr(hy), ptr(gid), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2]), wptr, bptr,
-                             ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out32), ptr(relu_t), E, stream()), "gru")
+    out32, relu_t = fu.gru(x32, add=(hy, gid))
     o, mag, _ = emu.gru(x32, hy.float()[gid.long()])
     fp32("gru", out32, (o, mag))
     assert torch.equal(relu_t, torch.relu(out32).half())
@@ -99,20 +94,14 @@ def test_fused_chains_against_the_rounding_emulator(E):
         strict = rr.Chains(upd, strict_autocast=True).gru(x32, hy.float()[gid.long()])
         print("  (gru against autocast's rounded gate * res product, for the record: worst %.2e, frac %.4f)"
               % rr.fp32_report(out32, strict[0], strict[1]))
-    htarget, hweight = torch.empty(1, E, 2, device="cuda"), torch.empty(1, E, 2, device="cuda")
-    hwt, hb = w["heads_pack"]
-    out32_h = torch.empty(E, 384, device="cuda")
     coords0 = torch.zeros(E, 2, 3, 3, device="cuda")
-    check(lib().ramp_upd_gru_heads(ptr(x32), ptr(hy), ptr(gid), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2]), wptr, bptr,
-                                   ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out32_h), ptr(hwt), ptr(hb),
-                                   ptr(coords0), ptr(htarget), ptr(hweight), E, 3,
-                                   1e9, 1e9, stream()), "gru_heads")
+    out32_h, htarget, hweight = fu.gru(x32, add=(hy, gid), heads_at=(coords0, 1e9, 1e9))
     assert torch.equal(out32_h, out32)
     _heads_check("gru_heads E=%d" % E, relu_t, htarget[0], hweight[0], upd)
 
+    ln1 = w["ln1"]
     xin = torch.nn.functional.layer_norm(x32 + hy.float()[gid.long()], (384,), ln1[0], ln1[1], float(ln1[2]))
-    check(lib().ramp_upd_gru(ptr(xin), None, None, None, None, 0.0, wptr, bptr, ptr(ln2[0]), ptr(ln2[1]),
-                             float(ln2[2]), ptr(out32), ptr(relu_t), E, stream()), "gru")
+    out32, relu_t = fu.gru(xin)
     o, mag, _ = emu.gru(xin, prologue=False)
     fp32("gru_noprologue", out32, (o, mag))
     assert torch.equal(relu_t, torch.relu(out32).half())
@@ -122,11 +111,7 @@ def test_fused_chains_against_the_rounding_emulator(E):
     idx = torch.randint(-1, E, (E,), generator=g).cuda()
     idx[::5] = -1
     for name, seq in (("c1_pack", upd.c1), ("c2_pack", upd.c2)):
-        wa, ba, wb, bb = w[name]
-        on = torch.empty_like(net_in)
-        ot = torch.empty(E, 384, dtype=torch.half, device="cuda")
-        check(lib().ramp_upd_nbr(ptr(net_in), ptr(idx), ptr(wa), ptr(ba), ptr(wb), ptr(bb), ptr(on), ptr(ot), E, stream()),
-              "nbr")
+        on, ot = fu.nbr(net_in, idx, name[:2], want_t=True)
         fp32("nbr_" + name[:2], on, emu.nbr(net_in, idx, seq))
         assert torch.equal(ot, on.half())
 
@@ -137,27 +122,16 @@ def test_fused_chains_against_the_rounding_emulator(E):
     net_map[-3:] = 699
     table = rnd(300, 384).half()
     inp_idx = torch.randint(0, 5000, (E,), generator=g).cuda()
-    w1, b1 = w["corr1_pack"]
-    w2, b2, w3, b3 = w["tail_pack"]
-    ln, nm = w["corr_ln"], w["norm"]
-    oc = torch.empty(E, 384, device="cuda")
-    check(lib().ramp_upd_corr_mlp(ptr(corr), 896, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(ln[0]),
-                                  ptr(ln[1]), float(ln[2]), ptr(state), ptr(net_map), ptr(table), ptr(inp_idx), 300,
-                                  ptr(nm[0]), ptr(nm[1]), float(nm[2]), ptr(oc), E, stream()), "corr_mlp")
+    oc = fu.corr_mlp(corr, state, net_map, table, inp_idx, 300)
     fp32("corr_mlp", oc, emu.corr_mlp(corr[:, :882].float(), state, net_map, table.float(), inp_idx, 300))
     ctx = rnd(E, 384).half()
-    check(lib().ramp_upd_corr_mlp(ptr(corr), 896, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(ln[0]),
-                                  ptr(ln[1]), float(ln[2]), None, None, ptr(ctx), None, 0,
-                                  ptr(nm[0]), ptr(nm[1]), float(nm[2]), ptr(oc), E, stream()), "corr_mlp")
+    oc = fu.corr_mlp(corr, None, None, ctx, None, 0)
     fp32("corr_mlp_zero_state", oc, emu.corr_mlp(corr[:, :882].float(), None, None, ctx.float(), None, 0))
 
     # --- upd_fg: x written back bit for bit, [f | g] = one Linear each, rounded once (K = 384)
     for name, agg in (("kk_fg_pack", upd.agg_kk), ("ij_fg_pack", upd.agg_ij)):
-        wf, bf, wg, bg = w[name]
         xs = x32.clone()
-        fg = torch.empty(E, 768, dtype=torch.half, device="cuda")
-        check(lib().ramp_upd_fg(ptr(xs), ptr(hy), ptr(gid), ptr(xs), ptr(wf), ptr(bf), ptr(wg), ptr(bg), ptr(fg), E,
-                                stream()), "fg")
+        fg = fu.fg(xs, hy, gid, w[name], E)
         xe = x32 + hy.float()[gid.long()]
         assert torch.equal(xs, xe)
         for part, lin in ((0, agg.f), (1, agg.g)):
@@ -181,10 +155,7 @@ def test_fused_chains_against_the_rounding_emulator(E):
 
     # --- ramp_upd_heads_linear on a relu'd fp16 input
     relu_in = torch.relu(rnd(E, 384)).half()
-    target, weight = torch.empty(1, E, 2, device="cuda"), torch.empty(1, E, 2, device="cuda")
-    coords0 = torch.zeros(E, 2, 3, 3, device="cuda")
-    check(lib().ramp_upd_heads_linear(ptr(relu_in), ptr(hwt), ptr(hb), ptr(coords0),
-                                      ptr(target), ptr(weight), E, 3, 1e9, 1e9, stream()), "heads")
+    target, weight = fu.heads_linear(relu_in, coords0, 1e9, 1e9)
     _heads_check("heads_linear E=%d" % E, relu_in, target[0], weight[0], upd)
     print("E=%d measured:" % E, measured)
 

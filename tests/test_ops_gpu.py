@@ -789,15 +789,11 @@ def test_fused_gru_chain_matches_gemm_path():
             res[mlp] = (o32.clone(), rt.float().clone())
     fu.use_mlp = True
     # heads: row-wise dot-product kernel (+ target / weight epilogue) vs the [E,384]x[384,4] GEMM + upd_heads
-    from rampvo_amd._lib import check, lib, ptr, stream
     coords = (torch.rand(E, 2, 3, 3, generator=g) * 60).cuda()
     relu_t = res[True][1].half()
     with torch.no_grad():
         t_ref, w_ref, _ = fu.target_weight(fu.heads(relu_t), coords, 40.0, 30.0)
-        t_new, w_new = torch.empty(1, E, 2, device="cuda"), torch.empty(1, E, 2, device="cuda")
-        hwt, hb = fu.weights()["heads_pack"]
-        check(lib().ramp_upd_heads_linear(ptr(relu_t), ptr(hwt), ptr(hb), ptr(coords), ptr(t_new), ptr(w_new), E, 3, 40.0,
-                                          30.0, stream()), "ramp_upd_heads_linear")
+        t_new, w_new = fu.heads_linear(relu_t, coords, 40.0, 30.0)
     assert float((t_ref - t_new).abs().max()) <= 2e-3 * max(1.0, float(t_ref.abs().max()))
     near_edge = ((t_ref - torch.tensor([40.0, 30.0], device="cuda")).abs().min(-1).values < 0.1) | (t_ref.abs().min(-1).values < 0.1)
     assert float(((w_ref - w_new).abs().max(-1).values * (~near_edge)).max()) <= 2e-3
@@ -818,7 +814,6 @@ def test_softagg_fused_against_fp32_torch(E, mode):
     one and a fifth tiles), `ones` = every factor its own group."""
     import torch.nn.functional as F
     from rampvo_amd import ops
-    from rampvo_amd._lib import check, lib, ptr, stream
     from rampvo_amd.synthetic import make_network
     net = make_network("SingleScale")
     fu = net.update.fused(torch.float16)
@@ -876,7 +871,6 @@ def test_fused_update_chains_against_fp32_torch(E):
     this repo's own GEMM path.  E = 1003: the 64-row kernels; 20011 / 41003: the big-tile kernels (96 / 176 rows per
     workgroup); none a multiple of its tile."""
     import torch.nn.functional as F
-    from rampvo_amd._lib import check, lib, ptr, stream
     from rampvo_amd.synthetic import make_network
     net = make_network("SingleScale")
     fu = net.update.fused(torch.float16)
@@ -901,24 +895,14 @@ def test_fused_update_chains_against_fp32_torch(E):
     # --- upd_gru: LN(x + hy[gid]) -> GatedResidual -> LN -> GatedResidual (+ relu copy)
     x32, hy = rnd(E, 384), rnd(G, 384).half()
     gid = torch.randint(0, G, (E,), generator=g).int().cuda()
-    out32 = torch.empty(E, 384, device="cuda")
-    relu_t = torch.empty(E, 384, dtype=torch.half, device="cuda")
-    _, _, wptr, bptr = w["gru_pack"]
-    ln1, ln2 = w["ln1"], w["ln2"]
-    check(lib().ramp_upd_gru(ptr(x32), ptr(hy), ptr(gid), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2]), wptr, bptr,
-                             ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out32), ptr(relu_t), E, stream()), "gru")
+    out32, relu_t = fu.gru(x32, add=(hy, gid))
     exp = ref.gru(x32 + hy.float()[gid.long()])
     cmp("gru", out32, exp)
     cmp("gru_relu", relu_t, torch.relu(exp))
     # the same launch with the heads in its epilogue (ramp_upd_gru_heads): out32 bit-equal, target / weight against fp32
     # torch on the launch's own relu copy (the heads' half input)
-    out32_h = torch.empty(E, 384, device="cuda")
     hcoords = (torch.rand(E, 2, 3, 3, generator=g) * 60).cuda()
-    htarget, hweight = torch.empty(1, E, 2, device="cuda"), torch.empty(1, E, 2, device="cuda")
-    hwt, hb = w["heads_pack"]
-    check(lib().ramp_upd_gru_heads(ptr(x32), ptr(hy), ptr(gid), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2]), wptr, bptr,
-                                   ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out32_h), ptr(hwt), ptr(hb), ptr(hcoords),
-                                   ptr(htarget), ptr(hweight), E, 3, 40.0, 30.0, stream()), "gru_heads")
+    out32_h, htarget, hweight = fu.gru(x32, add=(hy, gid), heads_at=(hcoords, 40.0, 30.0))
     assert torch.equal(out32_h, out32)
     t_exp = hcoords[:, :, 1, 1] + ref.d[1](relu_t.float())
     w_exp = torch.sigmoid(ref.w[1](relu_t.float()))
@@ -928,20 +912,14 @@ def test_fused_update_chains_against_fp32_torch(E):
     assert float(((hweight[0] - w_exp * inside[:, None].float()).abs().max(-1).values * far.float()).max()) <= 2e-3
     # without the prologue: x32 is already gru[0]'s output
     xin = ref.gru[0](x32)
-    check(lib().ramp_upd_gru(ptr(xin), None, None, None, None, 0.0, wptr, bptr, ptr(ln2[0]), ptr(ln2[1]),
-                             float(ln2[2]), ptr(out32), ptr(relu_t), E, stream()), "gru")
-    cmp("gru_noprologue", out32, ref.gru[3](ref.gru[2](ref.gru[1](xin))))
+    cmp("gru_noprologue", fu.gru(xin)[0], ref.gru[3](ref.gru[2](ref.gru[1](xin))))
 
     # --- upd_nbr: net + Lb(relu(La(mask * net[idx])))
     net_in = rnd(E, 384)
     idx = torch.randint(-1, E, (E,), generator=g).cuda()
     idx[::5] = -1
     for name, seq in (("c1_pack", ref.c1), ("c2_pack", ref.c2)):
-        wa, ba, wb, bb = w[name]
-        o = torch.empty_like(net_in)
-        ot = torch.empty(E, 384, dtype=torch.half, device="cuda")
-        check(lib().ramp_upd_nbr(ptr(net_in), ptr(idx), ptr(wa), ptr(ba), ptr(wb), ptr(bb), ptr(o), ptr(ot), E, stream()),
-              "nbr")
+        o, ot = fu.nbr(net_in, idx, name[:2], want_t=True)
         gathered = net_in[idx.clamp(min=0)] * (idx >= 0).float()[:, None]
         exp = net_in + seq(gathered)
         cmp("nbr_" + name, o, exp)
@@ -954,29 +932,18 @@ def test_fused_update_chains_against_fp32_torch(E):
     net_map[-3:] = 699
     table = rnd(300, 384).half()
     inp_idx = torch.randint(0, 5000, (E,), generator=g).cuda()
-    w1, b1 = w["corr1_pack"]
-    w2, b2, w3, b3 = w["tail_pack"]
-    ln, nm = w["corr_ln"], w["norm"]
-    o = torch.empty(E, 384, device="cuda")
-    check(lib().ramp_upd_corr_mlp(ptr(corr), 896, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(ln[0]),
-                                  ptr(ln[1]), float(ln[2]), ptr(state), ptr(net_map), ptr(table), ptr(inp_idx), 300,
-                                  ptr(nm[0]), ptr(nm[1]), float(nm[2]), ptr(o), E, stream()), "corr_mlp")
+    o = fu.corr_mlp(corr, state, net_map, table, inp_idx, 300)
     st = state[net_map.clamp(min=0)] * (net_map >= 0).float()[:, None]
     exp = ref.norm(st + table.float()[inp_idx % 300] + ref.corr(corr[:, :882].float()))
     cmp("corr_mlp", o, exp)
     # zero state / identity context (the motion probe's form)
-    check(lib().ramp_upd_corr_mlp(ptr(corr), 896, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(ln[0]),
-                                  ptr(ln[1]), float(ln[2]), None, None, ptr(rnd(E, 384).half()), None, 0,
-                                  ptr(nm[0]), ptr(nm[1]), float(nm[2]), ptr(o), E, stream()), "corr_mlp")
+    o = fu.corr_mlp(corr, None, None, rnd(E, 384).half(), None, 0)
     assert torch.isfinite(o).all()
 
     # --- upd_fg: x = x32 (+ add[gid], written back); fg = [f(x) | g(x)]; then the segment softmax + h: SoftAgg
     for name, agg in (("kk_fg_pack", ref.agg_kk), ("ij_fg_pack", ref.agg_ij)):
-        wf, bf, wg, bg = w[name]
         xs = x32.clone()
-        fg = torch.empty(E, 768, dtype=torch.half, device="cuda")
-        check(lib().ramp_upd_fg(ptr(xs), ptr(hy), ptr(gid), ptr(xs), ptr(wf), ptr(bf), ptr(wg), ptr(bg), ptr(fg), E,
-                                stream()), "fg")
+        fg = fu.fg(xs, hy, gid, w[name], E)
         xe = x32 + hy.float()[gid.long()]
         cmp("fg_x_" + name, xs, xe, tol=1e-6)
         cmp("fg_" + name, fg, torch.cat([agg.f(xe), agg.g(xe)], 1))
@@ -984,11 +951,7 @@ def test_fused_update_chains_against_fp32_torch(E):
     # --- heads: Linear(384 -> 2) x 2 on relu(net), target = centre + delta, weight = sigmoid(.) inside the image
     relu_in = torch.relu(rnd(E, 384)).half()
     coords = (torch.rand(E, 2, 3, 3, generator=g) * 60).cuda()
-    target = torch.empty(1, E, 2, device="cuda")
-    weight = torch.empty(1, E, 2, device="cuda")
-    hwt, hb = w["heads_pack"]
-    check(lib().ramp_upd_heads_linear(ptr(relu_in), ptr(hwt), ptr(hb), ptr(coords), ptr(target), ptr(weight), E, 3,
-                                      40.0, 30.0, stream()), "heads")
+    target, weight = fu.heads_linear(relu_in, coords, 40.0, 30.0)
     delta = ref.d[1](relu_in.float())
     t_exp = coords[:, :, 1, 1] + delta
     w_exp = torch.sigmoid(ref.w[1](relu_in.float()))
@@ -1260,6 +1223,7 @@ def test_upd_linear_matches_fp32_torch():
     lin = torch.nn.Linear(384, 384).cuda()
     y = torch.full((rows, 384), 7.0, device="cuda").half()
     nd = torch.tensor([live], dtype=torch.int32, device="cuda")
+    # (a direct call: a freshly packed Linear and a poisoned output, not the module's operands)
     _lib.check(_lib.lib().ramp_upd_linear(_lib.ptr(x), _lib.ptr(pack_linear_f16(lin.weight)),
                                           _lib.ptr(lin.bias.detach().half().float().contiguous()), _lib.ptr(y), rows,
                                           _lib.ptr(nd), _lib.stream()), "ramp_upd_linear")

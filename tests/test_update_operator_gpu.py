@@ -64,7 +64,7 @@ def _buffers(c, x3, heads, fill=None):
     if x3:
         b.update(fg=new(E, 768), ykk=new(Gkk, 384), yij=new(Gij, 384))
     else:
-        b["sagg_frag"] = new(lib().ramp_upd_softagg_frag_rows(E, max(Gkk, Gij)), 3, 384)
+        b["sagg_frag"] = new(lib().ramp_upd_softagg_frag_rows(E, max(Gkk, Gij)), 3, 384)     # (a size query, no stage)
     if heads:
         b.update(target=new(1, E, 2), weight=new(1, E, 2))
     else:
@@ -96,18 +96,10 @@ def _forward(fu, c, x3, heads):
     return (b["net_out"], b["target"], b["weight"]) if heads else (b["net_out"], b["relu_out"])
 
 
-def _softagg_x3(x32, add_t, add_idx, fg_pack, h_pack, groups, max_groups):
+def _softagg_x3(fu, x32, add_t, add_idx, fg_pack, h_pack, groups, max_groups):
     """one fp32 SoftAgg from its three exports (fg, segment_softmax, linear); h's rows at and above the group count zero"""
-    from rampvo_amd._lib import check, lib, ptr, stream
-    E, G, L = x32.shape[0], max(int(max_groups), 1), lib()
-    wf, bf, wg, bg = fg_pack
-    fg, y, hy = (torch.empty(E, 768, device="cuda"), torch.empty(G, 384, device="cuda"), torch.zeros(G, 384, device="cuda"))
-    check(L.ramp_x3_fg(ptr(x32), ptr(add_t), ptr(add_idx), None, ptr(wf), ptr(bf), ptr(wg), ptr(bg), ptr(fg), E, stream()),
-          "ramp_x3_fg")
-    check(L.ramp_x3_segment_softmax(ptr(fg), ptr(groups.order), ptr(groups.seg_start), ptr(groups.ngroups), ptr(y), G,
-                                    stream()), "ramp_x3_segment_softmax")
-    check(L.ramp_x3_linear(ptr(y), ptr(h_pack[0]), ptr(h_pack[1]), ptr(hy), G, ptr(groups.ngroups), stream()), "ramp_x3_linear")
-    return hy
+    fg = fu.fg(x32, add_t, add_idx, fg_pack, x32.shape[0], write_back=False)
+    return fu.h_lin(fu.seg(fg, groups, max(int(max_groups), 1)), h_pack, groups)
 
 
 def _chained(fu, w, c, x3, heads, write_back=False):
@@ -116,52 +108,28 @@ def _chained(fu, w, c, x3, heads, write_back=False):
     sum it starts from is written by ramp_upd_row_fuse -- write_back=True: before the pair SoftAgg already, which then adds
     nothing (the host-driven path's form before the two shared one sequence)"""
     from rampvo_amd._lib import check, lib, ptr, stream
-    L, E, T, p = lib(), c["E"], c["T"], c["plan"]
-    pre = "ramp_x3_" if x3 else "ramp_upd_"
-    new = lambda *s, dtype=torch.float32: torch.empty(*s, dtype=dtype, device="cuda")
-    s0, s1, out = new(E, 384), new(E, 384), new(E, 384)
-    (w1, b1), (w2, b2, w3, b3), ln, nm = w["corr1_pack"], w["tail_pack"], w["corr_ln"], w["norm"]
-    check(getattr(L, pre + "corr_mlp")(ptr(c["corr"]), 896, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(ln[0]),
-                                       ptr(ln[1]), float(ln[2]), ptr(c["net"]), ptr(c["net_map"]), ptr(c["inp"]),
-                                       ptr(c["inp_idx"]), 300, ptr(nm[0]), ptr(nm[1]), float(nm[2]), ptr(s0), E, stream()),
-          "corr_mlp")
-    for src, dst, idx, pack in ((s0, s1, p.ix_raw, "c1_pack"), (s1, s0, p.jx_raw, "c2_pack")):
-        wa, ba, wb, bb = w[pack]
-        tail = (E, stream()) if x3 else (None, E, stream())
-        check(getattr(L, pre + "nbr")(ptr(src), ptr(idx), ptr(wa), ptr(ba), ptr(wb), ptr(bb), ptr(dst), *tail), "nbr")
-    _, _, wptr, bptr = w["gru_pack"]
-    ln1, ln2 = w["ln1"], w["ln2"]
-    hw, hb = w["heads_pack"] if heads else (None, None)
-    target, weight = (new(1, E, 2), new(1, E, 2)) if heads else (None, None)
-    relu = None if heads else new(E, 384, dtype=T)
-    coords = c["coords"] if heads else None
+    E, p = c["E"], c["plan"]
+    s0 = fu.corr_mlp(c["corr"], c["net"], c["net_map"], c["inp"], c["inp_idx"], 300)
+    s0 = fu.nbr(fu.nbr(s0, p.ix_raw, "c1"), p.jx_raw, "c2")
+    heads_at = (c["coords"], WD, HT) if heads else None
     if x3:
-        hkk = _softagg_x3(s0, None, None, w["kk_fg_pack"], w["kk_h_pack"], p.g_kk, p.max_kk)
-        hij = _softagg_x3(s0, hkk, p.g_kk.gid, w["ij_fg_pack"], w["ij_h_pack"], p.g_ij, p.max_ij)
-        check(L.ramp_x3_gru(ptr(s0), ptr(hkk), ptr(p.g_kk.gid), ptr(hij), ptr(p.g_ij.gid), ptr(ln1[0]), ptr(ln1[1]),
-                            float(ln1[2]), wptr, bptr, ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out), ptr(relu), E, ptr(hw),
-                            ptr(hb), ptr(coords), ptr(target), ptr(weight), 3, WD, HT, stream()), "ramp_x3_gru")
-    else:
-        hkk = fu.softagg(s0, None, None, w["kk_fg_pack"], w["kk_h_pack"], p.g_kk, p.max_kk, E)
-        summed = new(E, 384)
+        hkk = _softagg_x3(fu, s0, None, None, w["kk_fg_pack"], w["kk_h_pack"], p.g_kk, p.max_kk)
+        hij = _softagg_x3(fu, s0, hkk, p.g_kk.gid, w["ij_fg_pack"], w["ij_h_pack"], p.g_ij, p.max_ij)
+        return fu.gru(s0, add=(hij, p.g_ij.gid), add0=(hkk, p.g_kk.gid), heads_at=heads_at)
+    hkk = fu.softagg(s0, None, None, w["kk_fg_pack"], w["kk_h_pack"], p.g_kk, p.max_kk, E)
+    summed = torch.empty(E, 384, device="cuda")
 
-        def write_sum():
-            check(L.ramp_upd_row_fuse(ptr(s0), None, ptr(hkk), None, None, ptr(p.g_kk.gid), 0, None, None, None, None, 0.0, 0,
+    def write_sum():
+        # (a direct call: a row kernel of the library-GEMM path, no stage of the fused chains)
+        check(lib().ramp_upd_row_fuse(ptr(s0), None, ptr(hkk), None, None, ptr(p.g_kk.gid), 0, None, None, None, None, 0.0, 0,
                                       ptr(summed), None, E, 1, stream()), "ramp_upd_row_fuse")
-        if write_back:
-            write_sum()
-            hij = fu.softagg(summed, None, None, w["ij_fg_pack"], w["ij_h_pack"], p.g_ij, p.max_ij, E)
-        else:
-            hij = fu.softagg(s0, hkk, p.g_kk.gid, w["ij_fg_pack"], w["ij_h_pack"], p.g_ij, p.max_ij, E)
-            write_sum()
-        common = (ptr(summed), ptr(hij), ptr(p.g_ij.gid), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2]), wptr, bptr, ptr(ln2[0]),
-                  ptr(ln2[1]), float(ln2[2]), ptr(out))
-        if heads:
-            check(L.ramp_upd_gru_heads(*common, ptr(hw), ptr(hb), ptr(coords), ptr(target), ptr(weight), E, 3, WD, HT,
-                                       stream()), "ramp_upd_gru_heads")
-        else:
-            check(L.ramp_upd_gru(*common, ptr(relu), E, stream()), "ramp_upd_gru")
-    return (out, target, weight) if heads else (out, relu)
+    if write_back:
+        write_sum()
+        hij = fu.softagg(summed, None, None, w["ij_fg_pack"], w["ij_h_pack"], p.g_ij, p.max_ij, E)
+    else:
+        hij = fu.softagg(s0, hkk, p.g_kk.gid, w["ij_fg_pack"], w["ij_h_pack"], p.g_ij, p.max_ij, E)
+        write_sum()
+    return fu.gru(summed, add=(hij, p.g_ij.gid), heads_at=heads_at)
 
 
 def _assert_equal(got, ref, what):

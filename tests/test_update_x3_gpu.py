@@ -39,6 +39,7 @@ def test_x3_linear_against_fp64_over_operand_ranges():
     pack = pack_linear_x3(W.cuda())
     y = torch.zeros(rows, 384, device="cuda")
     nrows = torch.tensor([rows - 7], dtype=torch.int32, device="cuda")
+    # (a direct call: a freshly packed random matrix, not the module's operands)
     check(lib().ramp_x3_linear(ptr(xc), ptr(pack), ptr(bc), ptr(y), rows, ptr(nrows), stream()), "ramp_x3_linear")
     assert float(y[rows - 7:].abs().max()) == 0.0                            # rows >= *rows_dev are not computed
     n = rows - 7
@@ -66,7 +67,7 @@ def test_x3_linear_against_fp64_over_operand_ranges():
 def test_x3_update_chains_against_fp64_torch(E):
     """every fused chain of the fp32 operator on its own, at sizes that are no multiple of the 64-row tile, against the
     fp64 evaluation of the reference module (same seeded weights)"""
-    from rampvo_amd._lib import check, lib, ptr, stream
+    from types import SimpleNamespace
     from rampvo_amd.synthetic import make_network
     net = make_network("SingleScale")
     fu = net.update.fused(torch.float32)
@@ -88,23 +89,12 @@ def test_x3_update_chains_against_fp64_torch(E):
     x32, h0, h1 = rnd(E, 384), rnd(G, 384), rnd(G + 3, 384)
     gid0 = torch.randint(0, G, (E,), generator=g).int().cuda()
     gid1 = torch.randint(0, G + 3, (E,), generator=g).int().cuda()
-    out32 = torch.empty(E, 384, device="cuda")
-    relu32 = torch.empty(E, 384, device="cuda")
-    _, _, wptr, bptr = w["gru_pack"]
-    ln1, ln2 = w["ln1"], w["ln2"]
-    check(lib().ramp_x3_gru(ptr(x32), ptr(h0), ptr(gid0), ptr(h1), ptr(gid1), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2]), wptr,
-                            bptr, ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out32), ptr(relu32), E, None, None, None, None,
-                            None, 3, 0.0, 0.0, stream()), "ramp_x3_gru")
+    out32, relu32 = fu.gru(x32, add=(h1, gid1), add0=(h0, gid0))
     exp = ref.gru((x32.double() + h0.double()[gid0.long()]) + h1.double()[gid1.long()])
     cmp("gru", out32, exp)
     cmp("gru_relu", relu32, torch.relu(exp))
-    hw, hb = w["heads_pack"]
     coords = (torch.rand(E, 2, 3, 3, generator=g) * 60).cuda()
-    target, weight = torch.empty(1, E, 2, device="cuda"), torch.empty(1, E, 2, device="cuda")
-    out_h = torch.empty(E, 384, device="cuda")
-    check(lib().ramp_x3_gru(ptr(x32), ptr(h0), ptr(gid0), ptr(h1), ptr(gid1), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2]), wptr,
-                            bptr, ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out_h), None, E, ptr(hw), ptr(hb), ptr(coords),
-                            ptr(target), ptr(weight), 3, 40.0, 30.0, stream()), "ramp_x3_gru")
+    out_h, target, weight = fu.gru(x32, add=(h1, gid1), add0=(h0, gid0), heads_at=(coords, 40.0, 30.0))
     assert torch.equal(out_h, out32)
     t_exp = coords[:, :, 1, 1].double() + ref.d[1](torch.relu(exp))
     w_exp = torch.sigmoid(ref.w[1](torch.relu(exp)))
@@ -114,19 +104,14 @@ def test_x3_update_chains_against_fp64_torch(E):
     assert float(((weight[0].double() - w_exp * inside[:, None].double()).abs().max(-1).values * far.double()).max()) <= 2e-6
     # without the prologue: x32 is already gru[0]'s output
     xin = ref.gru[0](x32.double()).float()
-    check(lib().ramp_x3_gru(ptr(xin), None, None, None, None, None, None, 0.0, wptr, bptr, ptr(ln2[0]), ptr(ln2[1]),
-                            float(ln2[2]), ptr(out32), ptr(relu32), E, None, None, None, None, None, 3, 0.0, 0.0, stream()),
-          "ramp_x3_gru")
-    cmp("gru_noprologue", out32, ref.gru[3](ref.gru[2](ref.gru[1](xin.double()))))
+    cmp("gru_noprologue", fu.gru(xin)[0], ref.gru[3](ref.gru[2](ref.gru[1](xin.double()))))
 
     # --- c1 / c2: net + Lb(relu(La(mask * net[idx])))
     net_in = rnd(E, 384)
     idx = torch.randint(-1, E, (E,), generator=g).cuda()
     idx[::5] = -1
     for name, seq in (("c1_pack", ref.c1), ("c2_pack", ref.c2)):
-        wa, ba, wb, bb = w[name]
-        o = torch.empty_like(net_in)
-        check(lib().ramp_x3_nbr(ptr(net_in), ptr(idx), ptr(wa), ptr(ba), ptr(wb), ptr(bb), ptr(o), E, stream()), "ramp_x3_nbr")
+        o = fu.nbr(net_in, idx, name[:2])
         gathered = net_in.double()[idx.clamp(min=0)] * (idx >= 0).double()[:, None]
         cmp("nbr_" + name, o, net_in.double() + seq(gathered))
 
@@ -137,20 +122,12 @@ def test_x3_update_chains_against_fp64_torch(E):
     net_map[-3:] = 699
     table = rnd(300, 384)
     inp_idx = torch.randint(0, 5000, (E,), generator=g).cuda()
-    w1, b1 = w["corr1_pack"]
-    w2, b2, w3, b3 = w["tail_pack"]
-    ln, nm = w["corr_ln"], w["norm"]
-    o = torch.empty(E, 384, device="cuda")
-    check(lib().ramp_x3_corr_mlp(ptr(corr), 896, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(ln[0]), ptr(ln[1]),
-                                 float(ln[2]), ptr(state), ptr(net_map), ptr(table), ptr(inp_idx), 300, ptr(nm[0]), ptr(nm[1]),
-                                 float(nm[2]), ptr(o), E, stream()), "ramp_x3_corr_mlp")
+    o = fu.corr_mlp(corr, state, net_map, table, inp_idx, 300)
     st = state.double()[net_map.clamp(min=0)] * (net_map >= 0).double()[:, None]
     cmp("corr_mlp", o, ref.norm(st + table.double()[inp_idx % 300] + ref.corr(corr[:, :882].double())))
     # zero state / identity context (the motion probe's form)
     tab2 = rnd(E, 384)
-    check(lib().ramp_x3_corr_mlp(ptr(corr), 896, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), ptr(ln[0]), ptr(ln[1]),
-                                 float(ln[2]), None, None, ptr(tab2), None, 0, ptr(nm[0]), ptr(nm[1]), float(nm[2]), ptr(o), E,
-                                 stream()), "ramp_x3_corr_mlp")
+    o = fu.corr_mlp(corr, None, None, tab2, None, 0)
     cmp("corr_mlp_zero_state", o, ref.norm(tab2.double() + ref.corr(corr[:, :882].double())))
 
     # --- SoftAgg: [f | g] rows (+ the expand-and-add of the previous one), segment softmax, h
@@ -158,19 +135,15 @@ def test_x3_update_chains_against_fp64_torch(E):
     counts = torch.bincount(gid0.long(), minlength=G)
     seg = torch.zeros(G + 1, dtype=torch.int32, device="cuda")
     seg[1:] = torch.cumsum(counts, 0).int()
-    ngroups = torch.tensor([G], dtype=torch.int32, device="cuda")
+    grp = SimpleNamespace(order=order, seg_start=seg, ngroups=torch.tensor([G], dtype=torch.int32, device="cuda"))
     for name, hname, agg, add in (("kk_fg_pack", "kk_h_pack", ref.agg_kk, False), ("ij_fg_pack", "ij_h_pack", ref.agg_ij, True)):
-        wf, bf, wg, bg = w[name]
         xs = x32.clone()
-        fg = torch.empty(E, 768, device="cuda")
-        check(lib().ramp_x3_fg(ptr(xs), ptr(h1) if add else None, ptr(gid1) if add else None, ptr(xs) if add else None, ptr(wf),
-                               ptr(bf), ptr(wg), ptr(bg), ptr(fg), E, stream()), "ramp_x3_fg")
+        fg = fu.fg(xs, h1 if add else None, gid1 if add else None, w[name], E)
         xe = x32.double() + (h1.double()[gid1.long()] if add else 0)
         if add:
             cmp("fg_x_" + name, xs, xe, tol=1e-7)
         cmp("fg_" + name, fg, torch.cat([agg.f(xe), agg.g(xe)], 1))
-        y = torch.empty(G + 4, 384, device="cuda")
-        check(lib().ramp_x3_segment_softmax(ptr(fg), ptr(order), ptr(seg), ptr(ngroups), ptr(y), G + 4, stream()), "seg")
+        y = fu.seg(fg, grp, G + 4)
         assert float(y[G:].abs().max()) == 0.0
         fgd = fg.double()
         ye = torch.zeros(G, 384, dtype=torch.float64, device="cuda")
@@ -179,9 +152,7 @@ def test_x3_update_chains_against_fp64_torch(E):
             if m.any():
                 ye[k] = (torch.softmax(fgd[m, 384:], 0) * fgd[m, :384]).sum(0)
         cmp("seg_" + name, y[:G], ye, tol=2e-6)
-        hy = torch.zeros(G + 4, 384, device="cuda")
-        hp = w[hname]
-        check(lib().ramp_x3_linear(ptr(y), ptr(hp[0]), ptr(hp[1]), ptr(hy), G + 4, ptr(ngroups), stream()), "ramp_x3_linear")
+        hy = fu.h_lin(y, w[hname], grp)
         cmp("h_" + name, hy[:G], agg.h(y[:G].double()))
     print("x3 update chains vs fp64 torch, max err / output scale:", {k: float("%.2e" % v) for k, v in worst.items()})
 

@@ -50,6 +50,7 @@ def corr_rows(r0, n):
 
 
 def mlp_rows(r0, n):
+    # (a direct call: row chunks of the caller's buffers at byte offsets, the result compared in place -- not a whole-tensor stage)
     check(lib().ramp_upd_corr_mlp(corr.data_ptr() + r0 * CORR_ROW * 2, 896, ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3),
                                   ptr(ln[0]), ptr(ln[1]), float(ln[2]), ptr(x32), net_map.data_ptr() + r0 * 8, ptr(table),
                                   inp_idx.data_ptr() + r0 * 8, 3072, ptr(nm[0]), ptr(nm[1]), float(nm[2]),

@@ -4,22 +4,16 @@ step alone, and both started together on two streams (HIP events on the gru stre
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from rampvo_amd._lib import check, lib, ptr, stream
 from rampvo_amd.synthetic import make_network
 from rampvo_amd import conv_hip
 E = 40000
 net = make_network("SingleScale")
 fu = net.update.fused(torch.float16)
-w = fu.weights()
 g = torch.Generator().manual_seed(1)
 rnd = lambda *s: (torch.randn(*s, generator=g) * 0.5).cuda()
 x32, hy = rnd(E, 384), rnd(2200, 384).half()
 gid = torch.randint(0, 2200, (E,), generator=g).int().cuda()
-out32 = torch.empty(E, 384, device="cuda"); relu_t = torch.empty(E, 384, dtype=torch.half, device="cuda")
-_, _, wptr, bptr = w["gru_pack"]; ln1, ln2 = w["ln1"], w["ln2"]
-def gru():
-    check(lib().ramp_upd_gru(ptr(x32), ptr(hy), ptr(gid), ptr(ln1[0]), ptr(ln1[1]), float(ln1[2]), wptr, bptr,
-                             ptr(ln2[0]), ptr(ln2[1]), float(ln2[2]), ptr(out32), ptr(relu_t), E, stream()), "gru")
+gru = lambda: fu.gru(x32, add=(hy, gid))
 enc = net.patchify.encoder
 H, W = 480, 640
 ev, im = rnd(5, H, W), rnd(3, H, W)

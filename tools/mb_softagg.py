@@ -31,18 +31,11 @@ def timed(fn, n=40):
 for name, keys in (("patch-like", (torch.arange(E) // 19)[torch.randperm(E, generator=g)]), ("pair-like", torch.arange(E) // 96)):
     grp = ops.group_by(keys.cuda())
     G = int(grp.ngroups.item())
-    from rampvo_amd._lib import check, lib, ptr, stream
-    rows = lib().ramp_upd_softagg_frag_rows(E, G)
-    frag = torch.empty(rows, 3, 384, device="cuda")
-    hy = torch.empty(G, 384, dtype=torch.half, device="cuda")
-    wf, bf, wg, bg = w["kk_fg_pack"]; wh, bh = w["kk_h_pack"]
-    main = lambda: check(lib().ramp_upd_softagg(ptr(x32), ptr(hy0), ptr(gid0), ptr(grp.order), ptr(grp.gid), ptr(wf), ptr(bf), ptr(wg), ptr(bg), ptr(frag), E, stream()), "softagg")
-    fin = lambda: check(lib().ramp_upd_softagg_finish(ptr(frag), ptr(grp.seg_start), ptr(grp.ngroups), ptr(wh), ptr(bh), ptr(hy), G, stream()), "finish")
-    fg = torch.empty(E, 768, dtype=torch.half, device="cuda")
+    fused = lambda: fu.softagg(x32, hy0, gid0, w["kk_fg_pack"], w["kk_h_pack"], grp, G, E)
     old_fg = lambda: fu.fg(x32, hy0, gid0, w["kk_fg_pack"], E)
     fgv = old_fg()
     old_seg = lambda: fu.seg(fgv, grp, G)
     yv = old_seg()
     old_lin = lambda: fu.h_lin(yv, w["kk_h_pack"], grp)
-    print("E=%d %-10s G=%5d | softagg %.1f + finish %.1f us | fg %.1f + softmax %.1f + linear %.1f us" %
-          (E, name, G, timed(main), timed(fin), timed(old_fg), timed(old_seg), timed(old_lin)), flush=True)
+    print("E=%d %-10s G=%5d | softagg + finish %.1f us | fg %.1f + softmax %.1f + linear %.1f us" %
+          (E, name, G, timed(fused), timed(old_fg), timed(old_seg), timed(old_lin)), flush=True)

@@ -22,6 +22,7 @@ for name, ng in (("patch grouping", 2112), ("pair grouping", 420)):
     order, seg, n = grouping(ng)
     cap = ng + 96
     y = torch.empty(cap, 384, dtype=torch.half, device="cuda")
+    # (a direct call: synthetic [f | g] rows and groupings, no module and no weights)
     fn = lambda: check(lib().ramp_upd_segment_softmax(ptr(fg), ptr(order), ptr(seg), ptr(n), ptr(y), cap, F16, stream()), "seg")
     for _ in range(5):
         fn()
