@@ -1892,6 +1892,71 @@ int ramp_event_flow(const void *x, const void *y, const double *t, const int8_t 
                     double *last_t_out, float *flow, uint8_t *cls, uint8_t *n_used, double *fit, float *flow_map,
                     int32_t *map_index, int32_t *status, void *ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------- event corner detection (csrc/corner.hip)
+ *
+ * ramp_event_corners: which events are corners -- FAST-style arcs of newest events on the surface of active events around each
+ * event at its own time (Mueggler, Bartolozzi and Scaramuzza, "Fast Event-based Corner Detection", BMVC 2017; with
+ * RAMP_CORNER_WIDE the Arc* acceptance of Alzugaray and Chli, RA-L 2018).  Order-independent and bit-exact: time stamps are
+ * only compared, there is no floating-point arithmetic and no tolerance anywhere.
+ *   Shared with ramp_event_flow, word for word: events (x, y [N] fp32, or int32 with RAMP_CORNER_XY_I32; t [N] float64; p [N]
+ *   int8, optional), pixels (the coordinate truncated toward zero), candidates, class [2] (not finite) and class [3] (outside
+ *   the sensor); the planes S (1 without p, 2 with; p > 0 is plane 1) and the rule that an event sees only its own plane; cells
+ *   (plane, pixel), the order within a cell (the indices; time stamps must not decrease) and across cells (e' PRECEDES e when
+ *   (t', i') < (t, i) lexicographically); the state last_t_in / last_t_out (float64 [S][H][W], NaN = none, one virtual event per
+ *   cell that precedes the call's, in place allowed), and RAMP_CORNER_BAD_ORDER with its emptying behaviour.  With S = 1 the
+ *   state is the very array of ramp_event_filter, ramp_time_surface and ramp_event_flow.
+ *   Circles: the order of each list is part of the definition; k ascends along each list, each entry is (dx, dy).
+ *     inner, n = 16: (0,3) (1,3) (2,2) (3,1) (3,0) (3,-1) (2,-2) (1,-3) (0,-3) (-1,-3) (-2,-2) (-3,-1) (-3,0) (-3,1) (-2,2) (-1,3)
+ *     outer, n = 20: (0,4) (1,4) (2,3) (3,2) (4,1) (4,0) (4,-1) (3,-2) (2,-3) (1,-4) (0,-4) (-1,-4) (-2,-3) (-3,-2) (-4,-1)
+ *                    (-4,0) (-4,1) (-3,2) (-2,3) (-1,4)
+ *   Class [4], border: a candidate with qx < 4, qy < 4, qx > W - 5 or qy > H - 5 (its outer circle is not wholly on the sensor).
+ *   A sensor with H < 9 or W < 9 has only border pixels: valid, not refused.
+ *   Per circle: v[k] = the time stamp of the last candidate of cell (own plane, circle pixel k) that precedes the event (t, i),
+ *   else that cell's state, else NaN, which counts as below every number.  The event's own pixel and its own predecessor take
+ *   no part.  An ARC (start, L) is the cyclic run k = start, start + 1, .., start + L - 1 (mod n).  It PASSES when every v on it
+ *   is strictly greater than every v off it: equal values across the boundary fail, an arc that holds a NaN fails.  The lengths
+ *   allowed are lo .. hi (the published values: inner 3 .. 6, outer 4 .. 8; parameters, 1 <= lo <= hi <= n - 1); with
+ *   RAMP_CORNER_WIDE an arc also passes when n - L is in lo .. hi (the complement of a wide arc of oldest events).  Several
+ *   lengths can pass (the sets above a threshold are nested): the arc REPORTED is the one with the smallest L; its start is the
+ *   one index whose predecessor is off the arc.  L = n cannot pass.  Equivalently: for an element e with a number let
+ *   m_e = {k : v[k] >= v[e]}; the circle passes exactly when some m_e is a cyclic run of an allowed size.
+ *   Classes: [5] the inner circle has no passing arc; [6] the inner circle passes, the outer does not; [7] both pass: a corner.
+ *   The first class that applies, [2] to [7], is the one counted.
+ *   Outputs (optional ones NULL; cls and status are required):
+ *     cls [N] uint8: the class.  arc [N][4] uint8, 4-byte aligned: inner start, inner L, outer start, outer L; zeros for a
+ *     circle that was not evaluated or did not pass.
+ *     index [N] int32 and count [1] int32 (both or neither): the corner events' indices ascending, -1 beyond the count.
+ *     corner_count [H][W] int32: corner events per pixel over both planes (int32 atomic adds).
+ *     last_t_out.  status: device int32 [8]: [0] bit 0 RAMP_CORNER_BAD_ORDER, [1] events, [2] .. [7] the class counts;
+ *     [2] + ... + [7] = [1].
+ *   RAMP_CORNER_BAD_ORDER (a cell's candidates decrease in time in index order, or its first candidate lies before its state)
+ *   is an outcome of the data (RAMP_OK), never a plausible answer: every cls and arc is 0, index is -1, count 0, corner_count 0,
+ *   last_t_out NaN, [4] .. [7] are 0 ([1] .. [3] are still counted).
+ *   Launches, all on `stream`, nothing synchronised, no floating-point atomics, every loop a binary search or of fixed length:
+ *   memsets; the key kernel; a STABLE radix sort of (cell, index) over ceil(log2(S H W + 1)) bits (hipcub); the segment kernel;
+ *   the time-stamp gather with the order check; the corner kernel, one lane per sorted position (16 binary searches into
+ *   registers and the inner test; for the lanes that passed 20 more and the outer test); with index, a running count of the
+ *   corner flags (hipcub); the state, index and status launch.  The result is a function of the input alone: a call repeats
+ *   its bits.
+ *   N == 0: RAMP_OK, no kernel is launched: status, count and corner_count are zeroed, last_t_in is copied to last_t_out when
+ *   both are given and differ -- S planes, S = 2 when p is not NULL -- (last_t_out without last_t_in is left as it is).
+ *   RAMP_EINVAL: an arc range outside 1 <= lo <= hi <= n - 1, N < 0, H or W < 1, unknown flags, a NULL status (N > 0: cls / x /
+ *   y / t / ws), one of index / count without the other, last_t_in or last_t_out not 8-byte aligned, status, arc, index, count
+ *   or corner_count not 4-byte aligned, ws not 16-byte aligned.  RAMP_EUNSUPPORTED: N >= 2^31 or 2 H W >= 2^31 - 1.
+ *   RAMP_EWORKSPACE: ws_bytes below ramp_event_corners_ws_bytes(N, H, W, planes) (planes: 1 without p, 2 with; 0 for sizes that
+ *   are refused).  A refused call touches nothing.
+ * ramp_event_corners_grid_events(): the number of events one trip of the full grid covers; above it the workgroups take a
+ * second trip.                                                                                                           */
+#define RAMP_CORNER_XY_I32 1
+#define RAMP_CORNER_WIDE 2
+#define RAMP_CORNER_BAD_ORDER 1 /* status[0] bit 0: the value of RAMP_FILTER_BAD_ORDER */
+size_t ramp_event_corners_ws_bytes(long N, int H, int W, int planes);
+long ramp_event_corners_grid_events(void);
+int ramp_event_corners(const void *x, const void *y, const double *t, const int8_t *p, long N, int H, int W, int flags,
+                       int inner_lo, int inner_hi, int outer_lo, int outer_hi, const double *last_t_in, double *last_t_out,
+                       uint8_t *cls, uint8_t *arc, int32_t *index, int32_t *count, int32_t *corner_count, int32_t *status,
+                       void *ws, size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------- IMU: preintegration and alignment (csrc/imu.hip)
  *
  * A monocular trajectory has an arbitrary unit and no notion of down.  These entries take raw IMU samples and the trajectory as

@@ -24,9 +24,10 @@ _BAD_CAMERA = (_lib.RAMP_RECTIFY_BAD_CAMERA, "the camera record is not finite or
 # (RAMP_MAP_RENDER_BAD_CAMERA is the same bit, raised on the same condition: the two entries share the row and the role)
 _BAD_POSE = (_lib.RAMP_DEPTH_POINTS_BAD_CAMERA, "the camera pose at t_ref is not finite")
 assert _lib.RAMP_MAP_RENDER_BAD_CAMERA == _lib.RAMP_DEPTH_POINTS_BAD_CAMERA == _lib.RAMP_MAP_LOCALIZE_BAD_CAMERA
-# (RAMP_FLOW_BAD_ORDER is the same bit, raised on the same condition: event_flow shares the row and the ``filter`` role)
+# (RAMP_FLOW_BAD_ORDER and RAMP_CORNER_BAD_ORDER are the same bit, raised on the same condition: event_flow and event_corners
+# share the row and the ``filter`` role)
 _BAD_ORDER = (_lib.RAMP_FILTER_BAD_ORDER, "a pixel's events decrease in time, or lie before the filter's state")
-assert _lib.RAMP_FLOW_BAD_ORDER == _lib.RAMP_FILTER_BAD_ORDER
+assert _lib.RAMP_FLOW_BAD_ORDER == _lib.RAMP_CORNER_BAD_ORDER == _lib.RAMP_FILTER_BAD_ORDER
 _STATUS = {
     "trajectory": ({"unresolved": (track_dev.TRAJ_UNRESOLVED,
                                    "a frame is neither a keyframe nor reachable through the delta chain")}, ()),
@@ -53,6 +54,8 @@ _STATUS = {
                      ("n_events", "n_not_finite", "n_outside", "n_hot", "n_refractory", "n_no_support", "n_kept")),
     "event_flow": ({"bad_order": _BAD_ORDER},
                    ("n_events", "n_not_finite", "n_outside", "n_few_points", "n_collinear", "n_flat", "n_valid")),
+    "event_corners": ({"bad_order": _BAD_ORDER},
+                      ("n_events", "n_not_finite", "n_outside", "n_border", "n_no_inner_arc", "n_no_outer_arc", "n_corners")),
     "invdepth_map": ({"bad_cam": (_lib.RAMP_DEPTHMAP_BAD_CAM, "the camera pose at t_ref is not finite")},
                      ("n_considered", "n_bad_depth", "n_rejected", "n_out_of_reach", "n_contributing", "n_empty_pixels")),
     "se3_interp": ({"bad_times": _BAD_TIMES}, ("n_below", "n_above", "n_nan")),
@@ -1138,6 +1141,86 @@ def event_flow(x, y, t, height, width, p=None, radius=2, window_dt=None, min_poi
 def event_flow_status(status):
     """The status words of ``event_flow`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
     return _status("event_flow", status)
+
+
+def event_corners(x, y, t, height, width, p=None, inner=(3, 6), outer=(4, 8), wide=False, last_t=None, want_arc=False,
+                  want_index=True, want_map=False):
+    """Event corner detection on the device (include/ramp_hip.h ``ramp_event_corners``): an event is a corner when, on the
+    surface of active events at its own time, both a circle of 16 pixels (radius 3) and one of 20 (radius 4) around it hold a
+    contiguous arc of pixels that are all newer than all the rest (Mueggler et al. 2017) -- arcs of ``inner`` = (lo, hi) and
+    ``outer`` = (lo, hi) pixels, with ``wide`` also the arcs whose complement has such a length (Arc*, Alzugaray and Chli
+    2018).  Time stamps are only compared: order-independent and bit-exact, no tolerance anywhere.
+
+    ``x, y`` [N]: integer tensors take the int32 path, floating ones fp32; ``t`` [N] float64, non-decreasing per pixel (and
+    plane); ``p`` [N]: with it the two polarities have a surface each (``p > 0`` and the rest).  ``last_t``: the state of the
+    previous call, float64 [height, width] without ``p`` (``event_filter``'s and ``event_flow``'s ``last_t`` as it is),
+    [2, height, width] with it; None: no event yet.  It is not written.
+
+    Returns a dict of device tensors: ``cls`` uint8 [N] (2 not finite, 3 outside, 4 border, 5 no inner arc, 6 no outer arc, 7
+    corner), ``corner`` bool [N] (``cls == 7``), ``status`` int32 [8] (``event_corners_status``), ``last_t``, a NEW tensor,
+    the state for the next call; with ``want_arc`` ``arc`` uint8 [N, 4] (inner start, inner length, outer start, outer length
+    of the shortest passing arcs); with ``want_index`` ``index`` int32 [N] (the corners' indices ascending, then -1) and
+    ``count`` int32 [1]; with ``want_map`` ``corner_count`` int32 [height, width], the corners per pixel.  Runs on the current
+    stream, nothing is synchronised; a call repeats its bits.  Time stamps that decrease within a pixel (or against the state)
+    make every output 0, -1 or NaN and set bit 0 of ``status[0]``: never a plausible answer."""
+    dev = x.device
+    if height < 1 or width < 1:
+        raise RuntimeError("event_corners: height and width are positive")
+    ranges = []
+    for name, n, r in (("inner", 16, inner), ("outer", 20, outer)):
+        try:
+            lo, hi = (int(v) for v in r)
+        except (TypeError, ValueError):
+            raise RuntimeError("event_corners: %s is a pair (lo, hi) of arc lengths" % name) from None
+        if not 1 <= lo <= hi <= n - 1:
+            raise RuntimeError("event_corners: %s is (lo, hi) with 1 <= lo <= hi <= %d" % (name, n - 1))
+        ranges += [lo, hi]
+    integer = not (x.is_floating_point() or y.is_floating_point())
+    dt = torch.int32 if integer else torch.float32
+    xs, ys = x.reshape(-1).to(dt).contiguous(), y.reshape(-1).to(dt).contiguous()
+    tf = t.reshape(-1).to(torch.float64).contiguous()
+    N = xs.shape[0]
+    pd = None if p is None else p.reshape(-1).to(torch.int8).contiguous()
+    if not (ys.shape[0] == N and tf.shape[0] == N and (pd is None or pd.shape[0] == N)):
+        raise RuntimeError("event_corners: x, y, t and p differ in length")
+    planes = 1 if pd is None else 2
+    shape = (height, width) if planes == 1 else (2, height, width)
+    state = None
+    if last_t is not None:
+        if tuple(last_t.shape) != shape or last_t.dtype != torch.float64:
+            raise RuntimeError("event_corners: last_t is float64 [height, width], or [2, height, width] with p")
+        state = last_t.contiguous()
+    require_cuda(x, y, t, p, last_t)
+    nbytes = lib().ramp_event_corners_ws_bytes(N, height, width, planes)
+    if nbytes == 0:
+        check(_lib.RAMP_EUNSUPPORTED, "ramp_event_corners")
+    res = {"cls": torch.empty(N, dtype=torch.uint8, device=dev), "status": torch.zeros(8, dtype=torch.int32, device=dev)}
+    if want_arc:
+        res["arc"] = torch.empty((N, 4), dtype=torch.uint8, device=dev)
+    if want_index:
+        res["index"] = torch.empty(N, dtype=torch.int32, device=dev)
+        res["count"] = torch.zeros(1, dtype=torch.int32, device=dev)
+    if want_map:
+        res["corner_count"] = torch.empty((height, width), dtype=torch.int32, device=dev)
+    if N == 0:                                                # (an empty p has no pointer to tell the entry of two planes: the state is made here;
+        # an empty index has none to pair with count: count, zeroed above, stays here too)
+        res["last_t"] = state.clone() if state is not None else torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
+        state = None
+    else:
+        res["last_t"] = torch.empty(shape, dtype=torch.float64, device=dev)
+    ws = _lib_workspace(nbytes, dev, "evcorners")
+    flags = (_lib.RAMP_CORNER_XY_I32 if integer else 0) | (_lib.RAMP_CORNER_WIDE if wide else 0)
+    check(lib().ramp_event_corners(ptr(xs), ptr(ys), ptr(tf), ptr(pd), N, height, width, flags, *ranges, ptr(state),
+                                   ptr(res["last_t"]) if N else None, ptr(res["cls"]), ptr(res.get("arc")), ptr(res.get("index")),
+                                   ptr(res.get("count")) if N else None, ptr(res.get("corner_count")), ptr(res["status"]), ptr(ws), nbytes,
+                                   stream()), "ramp_event_corners")
+    res["corner"] = res["cls"] == 7
+    return res
+
+
+def event_corners_status(status):
+    """The status words of ``event_corners`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("event_corners", status)
 
 
 # ------------------------------------------------------------------- IMU

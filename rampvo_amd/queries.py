@@ -121,6 +121,7 @@ class TrackerQueries:
     _filter_params = None       # set_event_filter(): the keywords of ops.event_filter
     _filter_state = None        # the filter's last-time-stamp map, carried by filter_events()
     _flow_state = None          # the surface of active events, carried by event_flow()
+    _corner_state = None        # the surface of active events, carried by event_corners(): its own, not the flow's
     _imu = None                 # set_imu(): the keywords of ops.imu_align that describe the sensor
 
     def _state_stream(self, inputs=()):
@@ -398,10 +399,17 @@ class TrackerQueries:
         ordered on the current stream, nothing synchronised.  Otherwise numpy arrays, which waits and raises when a pixel's
         events decrease in time or lie before the carried surface (which is then left as it was) -- with ``denoise`` the
         denoiser's word is looked at first, the flow's second."""
-        name = "event_flow()"
-        unknown = sorted(set(params) - set(self._FLOW_KEYS))
+        return self._surface_query("event_flow", "_flow_state", self._FLOW_KEYS, x, y, t, p, as_tensor, denoise, carry, params)
+
+    def _surface_query(self, entry, attr, keys, x, y, t, p, as_tensor, denoise, carry, params):
+        """The body of a query on a carried surface of active events (``event_flow``, ``event_corners``): ``ops.<entry>`` on
+        raw sensor pixels at the tracker's image size with the surface held in ``self.<attr>``.  Not ``_event_inputs`` /
+        ``_answer``: integer pixels keep the int32 path, and with ``denoise`` two words of the ``filter`` role are looked at,
+        the denoiser's first."""
+        name = entry + "()"
+        unknown = sorted(set(params) - set(keys))
         if unknown:
-            raise RuntimeError(name + ": unknown parameter %s (known: %s)" % (unknown[0], ", ".join(self._FLOW_KEYS)))
+            raise RuntimeError(name + ": unknown parameter %s (known: %s)" % (unknown[0], ", ".join(keys)))
         td = self._as_device(t, torch.float64)
         pd = None if p is None else self._as_device(p, torch.int8)
         filt = None
@@ -409,13 +417,13 @@ class TrackerQueries:
             xd, yd, filt = self._denoised(name, x, y, td)
         else:
             xd, yd = self._raw_pixels(x), self._raw_pixels(y)
-        state = self._flow_state if carry else None
+        state = getattr(self, attr) if carry else None
         shape = (self.ht, self.wd) if pd is None else (2, self.ht, self.wd)
         if state is not None and tuple(state.shape) != shape:
             raise RuntimeError(name + ": the carried surface is %s, the call asks for %s -- with and without p do not mix "
-                               "(reset_event_flow())" % (" x ".join(map(str, state.shape)), " x ".join(map(str, shape))))
+                               "(reset_%s())" % (" x ".join(map(str, state.shape)), " x ".join(map(str, shape)), entry))
         with self._state_stream(inputs=tuple(v for v in (xd, yd, td, pd, state) if v is not None)) as sc:
-            out = ops.event_flow(xd, yd, td, self.ht, self.wd, p=pd, last_t=state, **params)
+            out = getattr(ops, entry)(xd, yd, td, self.ht, self.wd, p=pd, last_t=state, **params)
             sc.leaves(out)
         if filt is not None:
             out["filter_status"] = filt
@@ -427,8 +435,33 @@ class TrackerQueries:
         else:
             res = out
         if carry:
-            self._flow_state = out["last_t"]               # (behind a clean check; as_tensor: a bad order leaves NaN)
+            setattr(self, attr, out["last_t"])             # (behind a clean check; as_tensor: a bad order leaves NaN)
         return res
+
+    # ---------------------------------------------------------------- event corner detection
+    _CORNER_KEYS = ("inner", "outer", "wide", "want_arc", "want_index", "want_map")
+
+    def reset_event_corners(self):
+        """forget the events ``event_corners`` has seen: the next call starts from the empty surface"""
+        self._corner_state = None
+
+    def event_corners(self, x, y, t, p=None, as_tensor=False, denoise=False, carry=True, **params):
+        """Which events of the next stretch of the sensor's stream are corners (``ops.event_corners``; ``params``: its
+        ``inner``, ``outer``, ``wide``, ``want_arc``, ``want_index``, ``want_map``): arcs of newest events on two circles of
+        the surface of active events around each event, at the tracker's image size.  ``x, y`` are RAW SENSOR PIXELS -- the
+        circles live on the integer lattice, so the detector sits where the filter and the flow sit, ahead of any
+        rectification; integer input takes the int32 path.  ``p``: with it each polarity has its own surface.  The surface --
+        every cell's last time stamp -- is CARRIED from call to call, so feeding a stream in pieces gives the corners of
+        feeding it whole (``reset_event_corners`` forgets it; ``carry=False``: these events alone, the carried surface neither
+        read nor advanced).  It is this query's own surface, not ``event_flow``'s: each query advances only its own.
+        ``denoise=True``: filtered first (``set_event_filter``; raises without one; the filter's state is read, not
+        advanced); a dropped event is a NaN row and falls in class 2, and the result gains ``filter_status``.
+
+        A device-resident state stays device resident.  ``as_tensor=True``: the dict of device tensors of
+        ``ops.event_corners``, ordered on the current stream, nothing synchronised.  Otherwise numpy arrays, which waits and
+        raises when a pixel's events decrease in time or lie before the carried surface (which is then left as it was) -- with
+        ``denoise`` the denoiser's word is looked at first, the detector's second."""
+        return self._surface_query("event_corners", "_corner_state", self._CORNER_KEYS, x, y, t, p, as_tensor, denoise, carry, params)
 
     # ---------------------------------------------------------------- lens distortion
     def set_camera(self, model, raw_intrinsics, coeffs=(), rotation=None):
