@@ -1957,6 +1957,82 @@ int ramp_event_corners(const void *x, const void *y, const double *t, const int8
                        uint8_t *cls, uint8_t *arc, int32_t *index, int32_t *count, int32_t *corner_count, int32_t *status,
                        void *ws, size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------- event corner tracks (csrc/cornertrack.hip)
+ *
+ * ramp_event_corner_tracks: links corner events in space and time into feature tracks -- each with an identity, a birth and a
+ * length -- and gives the full two-component image velocity at each of them, the mean since the track's birth.  Every
+ * CANDIDATE is linked to the newest candidate around it that precedes it by at most max_dt; without one a track is born.
+ * Order-independent and bit-exact: time stamps are compared, subtracted once and divided once, every rounding below is fixed.
+ *   Shared with ramp_event_corners, word for word: events (x, y [N] fp32, or int32 with RAMP_CORNER_TRACK_XY_I32; t [N]
+ *   float64; p [N] int8, optional), pixels (the coordinate truncated toward zero), class [2] (not finite) and class [3]
+ *   (outside the sensor); the planes S (1 without p, 2 with; p > 0 is plane 1) and the rule that an event sees only its own
+ *   plane; cells (plane, pixel), the order within a cell (the indices; time stamps must not decrease) and across cells (e'
+ *   PRECEDES e when (t', i') < (t, i) lexicographically), and RAMP_CORNER_TRACK_BAD_ORDER with its emptying behaviour.
+ *   Candidates: corner, uint8 [N], nonzero = the event is a candidate (ramp_event_corners' cls == 7, or any mask); NULL: every
+ *   valid event is one.  A valid event that is not a candidate is class [4]: it takes no part and leaves the state alone.
+ *   State: state_in, optional int64 [S][H][W][4], one record per cell: word 0 the bits of t (NaN = none), word 1 the track
+ *   id, word 2 the bits of t0, word 3 the birth pixel index y0 * W + x0 in the low 32 bits and the length in the high 32 bits.
+ *   A record with a number in word 0 is one virtual candidate of its cell that precedes the call's.  next_id_in, a device
+ *   int64 word, goes with it (both or neither; neither: empty state, ids from 0).  The state is also the live-track map: a
+ *   cell with t >= now - max_dt holds a live track's newest corner.  Nothing is pruned by age.
+ *   Parent of a candidate e at pixel (qx, qy) with (t, i): walk the (2 rho + 1)^2 window clipped to the sensor, the own pixel
+ *   included, in ascending j = (dy + rho) * (2 rho + 1) + (dx + rho).  In each cell take the last candidate of e's own plane
+ *   that precedes e; if there is none, the cell's state record.  The cell is ELIGIBLE when that time stamp t' is a number
+ *   (not NaN) and t - t' <= max_dt (one float64 subtraction, no FMA).  The parent is the eligible cell with the greatest t';
+ *   ties go to the smallest dx^2 + dy^2, then to the lowest j.  No index takes part in the choice: a state record and an event
+ *   of this call compete on equal terms.
+ *   Classes: [5] no eligible cell, a track is born; [6] the parent is a state record; [7] the parent is an event of this
+ *   call.  The first class that applies, [2] to [7], is the one counted.
+ *   Tracks: a parent strictly precedes its child, so the parent relation is a forest.  A ROOT is an event of class [5] or [6].
+ *   A root of class [5] with index r: track = next_id_in + r, birth = (t_r, qx_r, qy_r), length = 1.  A root of class [6]:
+ *   track and birth are the record's, length = the record's + 1.  Every other event takes track and birth from its root and
+ *   length = length(parent) + 1.  length saturates at 2^31 - 1.  next_id_out = next_id_in + N: ids are global event numbers,
+ *   so a stream fed in pieces gets the ids of the stream fed whole.
+ *   velocity = ((float)((qx - x0) / (t - t0)), (float)((qy - y0) / (t - t0))): exact integer differences converted to
+ *   float64, one float64 subtraction, one float64 division each, no FMA; NaN when t == t0, which includes every birth.  It is
+ *   the MEAN velocity since birth; parent lets a consumer walk back for anything more local.
+ *   state_out: per cell the record (t, track, t0, birth pixel | length << 32) of its last candidate in this call, else the
+ *   record of state_in (else NaN, 0, 0, 0); the state is read by the link launch alone and written by the last one, so
+ *   state_out == state_in and next_id_out == next_id_in are allowed.
+ *   Outputs (optional ones NULL; cls, status and, with N > 0, state_out and next_id_out are required):
+ *     cls [N] uint8: the class.  parent [N] int32: the parent's event index, -1 for a birth or a non-candidate, -2 for a state
+ *     record.  track [N] int64: -1 for non-candidates.  length [N] int32: 0 for non-candidates.  birth [N][3] float64: t0, x0,
+ *     y0, NaN for non-candidates.  velocity [N][2] fp32, NaN for non-candidates.
+ *     status: device int32 [8]: [0] bit 0 RAMP_CORNER_TRACK_BAD_ORDER, [1] events, [2] .. [7] the class counts;
+ *     [2] + ... + [7] = [1].
+ *   RAMP_CORNER_TRACK_BAD_ORDER (a cell's candidates decrease in time in index order, or its first candidate lies before its
+ *   state's t) is an outcome of the data (RAMP_OK), never a plausible answer: every cls and length is 0, parent and track are
+ *   -1, birth and velocity NaN, every cell of state_out has word 0 = NaN and the rest 0, next_id_out = next_id_in + N,
+ *   [4] .. [7] are 0 ([1] .. [3] are still counted).
+ *   Launches, all on `stream`, nothing synchronised, no LDS, no atomics on results, no floating-point atomics, every loop a
+ *   binary search or of fixed length: a memset; the key kernel (a non-candidate takes the sentinel key, as an invalid event
+ *   does); a STABLE radix sort of (cell, index) over ceil(log2(S H W + 1)) bits (hipcub); the segment kernel; the time-stamp
+ *   gather with the order check; the link kernel, one lane per sorted position ((2 rho + 1)^2 binary searches, the running
+ *   best (t', d^2) and its source -- a sorted position or a state cell -- in registers); ceil(log2(max(N, 2))) rounds of
+ *   pointer jumping over sorted positions between two buffers of (ancestor, links to it), launched unconditionally -- the
+ *   host never learns the candidate count -- and never in place; the resolve launch (track, birth, length, velocity and parent
+ *   from the roots, the state, next_id_out, the status words).  The result is a function of the input alone: a call repeats
+ *   its bits.
+ *   N == 0: RAMP_OK, no kernel is launched: status is zeroed, state_in is copied to state_out and next_id_in to next_id_out
+ *   where both are given and differ -- S planes, S = 2 when p is not NULL -- (an output without its input is left as it is).
+ *   RAMP_EINVAL: rho outside 0 .. 5, max_dt NaN or negative (+inf is allowed), N < 0, H or W < 1, unknown flags, a NULL
+ *   status (N > 0: cls / state_out / next_id_out / x / y / t / ws), one of state_in / next_id_in without the other, state_in,
+ *   state_out, next_id_in, next_id_out, track or birth not 8-byte aligned, status, parent, length or velocity not 4-byte
+ *   aligned, ws not 16-byte aligned.  RAMP_EUNSUPPORTED: N >= 2^31 or 2 H W >= 2^31 - 1.  RAMP_EWORKSPACE: ws_bytes below
+ *   ramp_event_corner_tracks_ws_bytes(N, H, W, planes) (planes: 1 without p, 2 with; 0 for sizes that are refused).  A
+ *   refused call touches nothing.
+ * ramp_event_corner_tracks_grid_events(): the number of events one trip of the full grid covers; above it the workgroups take
+ * a second trip.                                                                                                         */
+#define RAMP_CORNER_TRACK_XY_I32 1
+#define RAMP_CORNER_TRACK_BAD_ORDER 1 /* status[0] bit 0: the value of RAMP_FILTER_BAD_ORDER */
+size_t ramp_event_corner_tracks_ws_bytes(long N, int H, int W, int planes);
+long ramp_event_corner_tracks_grid_events(void);
+int ramp_event_corner_tracks(const void *x, const void *y, const double *t, const int8_t *p, const uint8_t *corner, long N, int H,
+                             int W, int flags, int rho, double max_dt, const int64_t *state_in, const int64_t *next_id_in,
+                             int64_t *state_out, int64_t *next_id_out, uint8_t *cls, int32_t *parent, int64_t *track,
+                             int32_t *length, double *birth, float *velocity, int32_t *status, void *ws, size_t ws_bytes,
+                             void *stream);
+
 /* ---------------------------------------------------------------- IMU: preintegration and alignment (csrc/imu.hip)
  *
  * A monocular trajectory has an arbitrary unit and no notion of down.  These entries take raw IMU samples and the trajectory as

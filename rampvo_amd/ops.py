@@ -24,10 +24,10 @@ _BAD_CAMERA = (_lib.RAMP_RECTIFY_BAD_CAMERA, "the camera record is not finite or
 # (RAMP_MAP_RENDER_BAD_CAMERA is the same bit, raised on the same condition: the two entries share the row and the role)
 _BAD_POSE = (_lib.RAMP_DEPTH_POINTS_BAD_CAMERA, "the camera pose at t_ref is not finite")
 assert _lib.RAMP_MAP_RENDER_BAD_CAMERA == _lib.RAMP_DEPTH_POINTS_BAD_CAMERA == _lib.RAMP_MAP_LOCALIZE_BAD_CAMERA
-# (RAMP_FLOW_BAD_ORDER and RAMP_CORNER_BAD_ORDER are the same bit, raised on the same condition: event_flow and event_corners
-# share the row and the ``filter`` role)
+# (RAMP_FLOW_BAD_ORDER, RAMP_CORNER_BAD_ORDER and RAMP_CORNER_TRACK_BAD_ORDER are the same bit, raised on the same condition:
+# event_flow, event_corners and event_corner_tracks share the row and the ``filter`` role)
 _BAD_ORDER = (_lib.RAMP_FILTER_BAD_ORDER, "a pixel's events decrease in time, or lie before the filter's state")
-assert _lib.RAMP_FLOW_BAD_ORDER == _lib.RAMP_CORNER_BAD_ORDER == _lib.RAMP_FILTER_BAD_ORDER
+assert _lib.RAMP_FLOW_BAD_ORDER == _lib.RAMP_CORNER_BAD_ORDER == _lib.RAMP_CORNER_TRACK_BAD_ORDER == _lib.RAMP_FILTER_BAD_ORDER
 _STATUS = {
     "trajectory": ({"unresolved": (track_dev.TRAJ_UNRESOLVED,
                                    "a frame is neither a keyframe nor reachable through the delta chain")}, ()),
@@ -56,6 +56,8 @@ _STATUS = {
                    ("n_events", "n_not_finite", "n_outside", "n_few_points", "n_collinear", "n_flat", "n_valid")),
     "event_corners": ({"bad_order": _BAD_ORDER},
                       ("n_events", "n_not_finite", "n_outside", "n_border", "n_no_inner_arc", "n_no_outer_arc", "n_corners")),
+    "event_corner_tracks": ({"bad_order": _BAD_ORDER},
+                            ("n_events", "n_not_finite", "n_outside", "n_not_corner", "n_born", "n_carried", "n_linked")),
     "invdepth_map": ({"bad_cam": (_lib.RAMP_DEPTHMAP_BAD_CAM, "the camera pose at t_ref is not finite")},
                      ("n_considered", "n_bad_depth", "n_rejected", "n_out_of_reach", "n_contributing", "n_empty_pixels")),
     "se3_interp": ({"bad_times": _BAD_TIMES}, ("n_below", "n_above", "n_nan")),
@@ -1221,6 +1223,114 @@ def event_corners(x, y, t, height, width, p=None, inner=(3, 6), outer=(4, 8), wi
 def event_corners_status(status):
     """The status words of ``event_corners`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
     return _status("event_corners", status)
+
+
+def event_corner_tracks(x, y, t, height, width, corner=None, p=None, radius=3, max_dt=None, state=None, next_id=None,
+                        want_parent=True, want_birth=False, want_velocity=True):
+    """Event corner tracks on the device (include/ramp_hip.h ``ramp_event_corner_tracks``): every candidate event is linked to
+    the newest candidate in the (2 ``radius`` + 1)^2 window around it -- its own pixel included -- that precedes it by at most
+    ``max_dt`` (required, in the unit of ``t``; ``float("inf")`` is allowed); without one a track is born.  A track has an id
+    (the global number of the event it was born with), a birth (t0, x0, y0) and a length, and each of its events the mean
+    image velocity since the birth, both components.  Order-independent and bit-exact.  ``radius`` = 3 is a default nobody
+    has tuned.
+
+    ``x, y`` [N]: integer tensors take the int32 path, floating ones fp32; ``t`` [N] float64, non-decreasing per pixel (and
+    plane); ``corner`` [N]: nonzero marks the candidates (``event_corners``' ``corner`` as it is), None: every valid event is
+    one; ``p`` [N]: with it the two polarities are linked apart.  ``state`` and ``next_id``: those of the previous call (both or
+    neither; None: no track yet, ids from 0), int64 [height, width, 4] without ``p``, [2, height, width, 4] with it
+    (``corner_track_state`` unpacks it), and int64 [1].  Neither is written.
+
+    Returns a dict of device tensors: ``cls`` uint8 [N] (2 not finite, 3 outside, 4 not a candidate, 5 born, 6 carried on from
+    the state, 7 linked to an event of this call), ``track`` int64 [N] (-1 for an event that is no candidate), ``length`` int32
+    [N] (the events of the track so far, 0), ``status`` int32 [8] (``event_corner_tracks_status``), ``state`` and ``next_id``,
+    NEW tensors, for the next call: a stream fed in pieces gets the tracks and ids of the stream fed whole; with
+    ``want_parent`` ``parent`` int32 [N] (the event linked to, -1 a birth or no candidate, -2 the state); with ``want_birth``
+    ``birth`` float64 [N, 3] (t0, x0, y0; NaN); with ``want_velocity`` ``velocity`` float32 [N, 2] in pixels per unit of ``t``
+    (NaN at a birth and for an event that is no candidate).  Runs on the current stream, nothing is synchronised; a call
+    repeats its bits.  Time stamps that decrease within a pixel (or against the state) make every output 0, -1 or NaN, empty
+    the state and set bit 0 of ``status[0]``: never a plausible answer."""
+    dev = x.device
+    if height < 1 or width < 1:
+        raise RuntimeError("event_corner_tracks: height and width are positive")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= 5:
+        raise RuntimeError("event_corner_tracks: radius is an integer in 0 .. 5")
+    if max_dt is None:
+        raise RuntimeError("event_corner_tracks: max_dt is required (the longest gap a link may span, in the unit of t)")
+    max_dt = float(max_dt)
+    if not max_dt >= 0.0:
+        raise RuntimeError("event_corner_tracks: max_dt is not negative and not NaN")
+    integer = not (x.is_floating_point() or y.is_floating_point())
+    dt = torch.int32 if integer else torch.float32
+    xs, ys = x.reshape(-1).to(dt).contiguous(), y.reshape(-1).to(dt).contiguous()
+    tf = t.reshape(-1).to(torch.float64).contiguous()
+    N = xs.shape[0]
+    pd = None if p is None else p.reshape(-1).to(torch.int8).contiguous()
+    cd = None if corner is None else (corner.reshape(-1) != 0).to(torch.uint8).contiguous()
+    if not (ys.shape[0] == N and tf.shape[0] == N and (pd is None or pd.shape[0] == N) and (cd is None or cd.shape[0] == N)):
+        raise RuntimeError("event_corner_tracks: x, y, t, corner and p differ in length")
+    planes = 1 if pd is None else 2
+    shape = (height, width, 4) if planes == 1 else (2, height, width, 4)
+    if (state is None) != (next_id is None):
+        raise RuntimeError("event_corner_tracks: state and next_id go together (both of the previous call, or neither)")
+    if state is not None:
+        if tuple(state.shape) != shape or state.dtype != torch.int64:
+            raise RuntimeError("event_corner_tracks: state is int64 [height, width, 4], or [2, height, width, 4] with p")
+        if next_id.numel() != 1 or next_id.dtype != torch.int64:
+            raise RuntimeError("event_corner_tracks: next_id is int64 [1]")
+        state, next_id = state.contiguous(), next_id.reshape(1)
+    require_cuda(x, y, t, corner, p, state, next_id)
+    nbytes = lib().ramp_event_corner_tracks_ws_bytes(N, height, width, planes)
+    if nbytes == 0:
+        check(_lib.RAMP_EUNSUPPORTED, "ramp_event_corner_tracks")
+    res = {"cls": torch.empty(N, dtype=torch.uint8, device=dev), "track": torch.empty(N, dtype=torch.int64, device=dev),
+           "length": torch.empty(N, dtype=torch.int32, device=dev), "status": torch.zeros(8, dtype=torch.int32, device=dev)}
+    if want_parent:
+        res["parent"] = torch.empty(N, dtype=torch.int32, device=dev)
+    if want_birth:
+        res["birth"] = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    if want_velocity:
+        res["velocity"] = torch.empty((N, 2), dtype=torch.float32, device=dev)
+    if N == 0:                                                # (an empty p has no pointer to tell the entry of two planes: the state is made here)
+        res["state"] = state.clone() if state is not None else _empty_track_state(shape, dev)
+        res["next_id"] = next_id.clone() if next_id is not None else torch.zeros(1, dtype=torch.int64, device=dev)
+        state = next_id = None
+    else:
+        res["state"] = torch.empty(shape, dtype=torch.int64, device=dev)
+        res["next_id"] = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = _lib_workspace(nbytes, dev, "evtracks")
+    check(lib().ramp_event_corner_tracks(ptr(xs), ptr(ys), ptr(tf), ptr(pd), ptr(cd), N, height, width,
+                                         _lib.RAMP_CORNER_TRACK_XY_I32 if integer else 0, radius, max_dt, ptr(state), ptr(next_id),
+                                         ptr(res["state"]) if N else None, ptr(res["next_id"]) if N else None, ptr(res["cls"]),
+                                         ptr(res.get("parent")), ptr(res["track"]), ptr(res["length"]), ptr(res.get("birth")),
+                                         ptr(res.get("velocity")), ptr(res["status"]), ptr(ws), nbytes, stream()),
+          "ramp_event_corner_tracks")
+    return res
+
+
+def _empty_track_state(shape, dev):
+    """no track yet: every cell's t is NaN, its other words 0"""
+    s = torch.zeros(shape, dtype=torch.int64, device=dev)
+    s[..., 0] = torch.tensor(float("nan"), dtype=torch.float64).view(torch.int64).item()
+    return s
+
+
+def event_corner_tracks_status(status):
+    """The status words of ``event_corner_tracks`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("event_corner_tracks", status)
+
+
+def corner_track_state(state):
+    """The state of ``event_corner_tracks`` (int64 [..., height, width, 4]) unpacked with plain torch, on the state's device: a
+    dict ``t`` float64 (NaN: the cell holds no corner), ``track`` int64, ``t0`` float64, ``x0``, ``y0`` int64 (the birth) and
+    ``length`` int32, each [..., height, width].  The state is also the live-track map: ``t >= now - max_dt`` marks the cells
+    that hold a live track's newest corner."""
+    if state.dtype != torch.int64 or state.dim() < 3 or state.shape[-1] != 4:
+        raise RuntimeError("corner_track_state: state is int64 [..., height, width, 4]")
+    width = state.shape[-2]
+    pix = state[..., 3] & 0xFFFFFFFF
+    return {"t": state[..., 0].contiguous().view(torch.float64), "track": state[..., 1].clone(),
+            "t0": state[..., 2].contiguous().view(torch.float64), "x0": pix % width, "y0": torch.div(pix, width, rounding_mode="floor"),
+            "length": (state[..., 3] >> 32).to(torch.int32)}
 
 
 # ------------------------------------------------------------------- IMU

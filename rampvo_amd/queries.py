@@ -122,6 +122,7 @@ class TrackerQueries:
     _filter_state = None        # the filter's last-time-stamp map, carried by filter_events()
     _flow_state = None          # the surface of active events, carried by event_flow()
     _corner_state = None        # the surface of active events, carried by event_corners(): its own, not the flow's
+    _track_state = None         # (surface, track state, next id), carried by event_corner_tracks(): its own surface too
     _imu = None                 # set_imu(): the keywords of ops.imu_align that describe the sensor
 
     def _state_stream(self, inputs=()):
@@ -462,6 +463,69 @@ class TrackerQueries:
         raises when a pixel's events decrease in time or lie before the carried surface (which is then left as it was) -- with
         ``denoise`` the denoiser's word is looked at first, the detector's second."""
         return self._surface_query("event_corners", "_corner_state", self._CORNER_KEYS, x, y, t, p, as_tensor, denoise, carry, params)
+
+    # ---------------------------------------------------------------- event corner tracks
+    _TRACK_KEYS = ("radius", "max_dt", "want_parent", "want_birth", "want_velocity")
+
+    def reset_event_corner_tracks(self):
+        """forget the events ``event_corner_tracks`` has seen: the next call starts without a surface and without a track"""
+        self._track_state = None
+
+    def event_corner_tracks(self, x, y, t, p=None, as_tensor=False, denoise=False, carry=True, **params):
+        """Feature tracks over the next stretch of the sensor's stream, without a trajectory and without a depth:
+        ``ops.event_corners`` says which events are corners, ``ops.event_corner_tracks`` links them in space and time
+        (``params``: the detector's ``inner``, ``outer``, ``wide``, ``want_arc``, ``want_index``, ``want_map`` and the linker's
+        ``radius``, ``max_dt`` -- required --, ``want_parent``, ``want_birth``, ``want_velocity``).  ``x, y`` are RAW SENSOR
+        PIXELS at the tracker's image size; integer input takes the int32 path.  ``p``: with it each polarity has its own
+        surface and its own tracks.  The detector's surface, the track state and the next id are CARRIED from call to call,
+        so feeding a stream in pieces gives the tracks and ids of feeding it whole (``reset_event_corner_tracks`` forgets
+        them; ``carry=False``: these events alone, nothing read and nothing advanced).  The surface is this query's own, not
+        the one ``event_corners`` carries.  ``denoise=True``: filtered first (``set_event_filter``; raises without one; the
+        filter's state is read, not advanced); a dropped event is a NaN row and falls in class 2, and the result gains
+        ``filter_status``.
+
+        Returns the union of both operators' dicts: the linker's under its own names (``cls``, ``status``, ``track``,
+        ``length``, ``state``, ``next_id``, ...), the detector's too (``corner``, ``last_t``, ``index``, ...) except its ``cls``
+        and ``status``, which are ``corner_cls`` and ``corner_status``.  A device-resident state stays device resident.
+        ``as_tensor=True``: device tensors, ordered on the current stream, nothing synchronised.  Otherwise numpy arrays,
+        which waits and raises when a pixel's events decrease in time or lie before what is carried (all of which is then
+        left as it was) -- the denoiser's word is looked at first, the detector's second, the linker's third."""
+        name = "event_corner_tracks()"
+        keys = self._CORNER_KEYS + self._TRACK_KEYS
+        unknown = sorted(set(params) - set(keys))
+        if unknown:
+            raise RuntimeError(name + ": unknown parameter %s (known: %s)" % (unknown[0], ", ".join(keys)))
+        td = self._as_device(t, torch.float64)
+        pd = None if p is None else self._as_device(p, torch.int8)
+        filt = None
+        if denoise:
+            xd, yd, filt = self._denoised(name, x, y, td)
+        else:
+            xd, yd = self._raw_pixels(x), self._raw_pixels(y)
+        surface, state, next_id = (self._track_state if carry else None) or (None, None, None)
+        shape = (self.ht, self.wd) if pd is None else (2, self.ht, self.wd)
+        if surface is not None and tuple(surface.shape) != shape:
+            raise RuntimeError(name + ": the carried surface is %s, the call asks for %s -- with and without p do not mix "
+                               "(reset_event_corner_tracks())" % (" x ".join(map(str, surface.shape)), " x ".join(map(str, shape))))
+        with self._state_stream(inputs=tuple(v for v in (xd, yd, td, pd, surface, state, next_id) if v is not None)) as sc:
+            det = ops.event_corners(xd, yd, td, self.ht, self.wd, p=pd, last_t=surface,
+                                    **{k: v for k, v in params.items() if k in self._CORNER_KEYS})
+            trk = ops.event_corner_tracks(xd, yd, td, self.ht, self.wd, corner=det["corner"], p=pd, state=state, next_id=next_id,
+                                          **{k: v for k, v in params.items() if k in self._TRACK_KEYS})
+            out = {**det, **trk, "corner_cls": det["cls"], "corner_status": det["status"]}
+            sc.leaves(out)
+        if filt is not None:
+            out["filter_status"] = filt
+        if not as_tensor:
+            words = [s.reshape(-1)[:1] for s in (filt, out["corner_status"], out["status"]) if s is not None]
+            for word in torch.cat(words).cpu().tolist():           # (the one wait)
+                _raise_on_words(name, {"filter": word})
+            res = {k: v.cpu().numpy() for k, v in out.items()}
+        else:
+            res = out
+        if carry:
+            self._track_state = (out["last_t"], out["state"], out["next_id"])      # (behind a clean check; as_tensor: a bad order leaves them empty)
+        return res
 
     # ---------------------------------------------------------------- lens distortion
     def set_camera(self, model, raw_intrinsics, coeffs=(), rotation=None):
