@@ -2033,6 +2033,79 @@ int ramp_event_corner_tracks(const void *x, const void *y, const double *t, cons
                              int32_t *length, double *birth, float *velocity, int32_t *status, void *ws, size_t ws_bytes,
                              void *stream);
 
+/* ---------------------------------------------------------------- event landmarks (csrc/landmark.hip)
+ *
+ * ramp_event_landmarks: one corner track, seen from the camera poses at its own events' time stamps, is one 3-D point.  Every
+ * track of ramp_event_corner_tracks is triangulated along the trajectory: a midpoint solve, a fixed number of Gauss-Newton steps
+ * on the reprojection error, a covariance in the convention of ramp_ba_map_covariance and a class that says why a landmark is
+ * not valid.
+ *   Inputs: x, y [N] fp32 pixel coordinates of the pinhole camera `intrinsics` (device fx, fy, cx, cy) -- what ramp_event_warp
+ *   takes; raw pixels are rectified first.  t [N] float64.  track [N] int64: ramp_event_corner_tracks' output, negative = the
+ *   event observes nothing.  knots [T][7], times [T]: a CAMERA-TO-WORLD trajectory as for ramp_event_warp.  flags:
+ *   RAMP_INTERP_EXTRAPOLATE alone.
+ *   An event is an OBSERVATION when track >= 0, x, y and t are finite, and times[0] <= t <= times[T - 1] (with
+ *   RAMP_INTERP_EXTRAPOLATE: any finite t).  The first test that fails counts the event: no track [1], not finite [2], outside
+ *   the knots' range [3].  Its pose C_i = (c_i, q_i) is ramp_se3_interp's at t_i (the same s, the same alpha formed in float64
+ *   and rounded once, the same statements: the same bits).  The camera ray is f_i = ((x - cx) / fx, (y - cy) / fy, 1) in fp32,
+ *   its world direction d_i = q_i f_i (the rotation of ramp_event_warp, fp32), and ev_ray[i] = (c_i, d_i), six fp32 words: the
+ *   call's own record.  EVERYTHING BEHIND THIS POINT IS FLOAT64 computed from fp32 words -- c_i, d_i, q_i, x_i, y_i, the
+ *   intrinsics -- each converted exactly: u_i = d_i / |d_i|, R_i the rotation of q_i / |q_i|.
+ *   Landmarks: the set of observations with one id, numbered in ascending id; lm_track[l] is the id.  Within a landmark the
+ *   observations are ordered by (t, index) (-0.0 is 0.0).  count[0] = min(tracks seen, max_landmarks): the highest ids are cut
+ *   off and counted, as ramp_point_map_export cuts at max_out; rows from count[0] on are not written.  ev_landmark[i]: the
+ *   landmark number of observation i, -1 for an event that is no observation and for an observation whose landmark was cut
+ *   off.
+ *   Per landmark with n observations, c0 the centre of its first:
+ *     1. A = sum (I - u_i u_i^T), b = sum (I - u_i u_i^T)(c_i - c0), X = c0 + A^-1 b by a 3x3 Cholesky (l00 = sqrt(a00),
+ *        l10 = a01 / l00, l20 = a02 / l00, p1 = a11 - l10^2, l11 = sqrt(p1), l21 = (a12 - l20 l10) / l11, p2 = (a22 - l20^2) -
+ *        l21^2, l22 = sqrt(p2); forward, then back substitution).  It FAILS when a pivot a00, p1, p2 is <= 0 or not finite.
+ *     2. exactly `refine` (0 .. 4) Gauss-Newton steps, no trip count depends on the data: Y_i = R_i^T (X - c_i),
+ *        r_i = (fx (Y.x / Y.z) + cx - x_i, fy (Y.y / Y.z) + cy - y_i), J_i = dr_i / dX, H = sum J^T J, g = sum J^T r,
+ *        X <- X - H^-1 g (the same Cholesky).  A step whose factorisation fails or whose result is not finite keeps X.
+ *     3. a last pass at the final X: H, rms = sqrt(sum |r_i|^2 / n), ev_residual[i] = r_i, cov = sigma_px^2 H^-1 stored xx, xy,
+ *        xz, yy, yz, zz (the order of ramp_ba_map_covariance's point_cov).
+ *     4. parallax = max_i acos(clamp((u_i.x u_1.x + u_i.y u_1.y) + u_i.z u_1.z, -1, 1)) in radians, u_1 the first observation's.
+ *     5. span = (t_first, t_last).
+ *   cls is the first that applies: 1 n < min_obs; 2 parallax < min_parallax; 3 the Cholesky of step 1 failed; 4 some Y_i.z <=
+ *   RAMP_WARP_MIN_Z (or NaN) at the final X; 5 rms > max_rms; 6 a word of point or cov, as stored, is not finite; 7 valid.
+ *   point [.][3] and cov [.][6] fp32 are NaN unless cls is 7 -- never a plausible number, so ramp_point_map_insert(point, count)
+ *   drops every landmark that is not valid by itself.  n_obs int32, parallax fp32 and span [.][2] float64 are written for every
+ *   landmark; rms fp32 and the landmark's rows of ev_residual are NaN when step 1 failed, else what step 3 gives whatever the
+ *   class.  ev_residual [N][2] is NaN for every event that is not an observation of a landmark kept, ev_ray [N][6] for every
+ *   event that is not an observation.  ev_landmark, ev_residual, ev_ray: optional, NULL.
+ *   status: device int32 [8]: [0] bit 0 RAMP_INTERP_BAD_TIMES (the knots' time stamps decrease or are not finite), [1] events
+ *   without a track, [2] not finite, [3] outside the knots' range, [4] observations, [5] tracks seen, [6] tracks cut off,
+ *   [7] valid landmarks; [1] + [2] + [3] + [4] = N.  RAMP_INTERP_BAD_TIMES is an outcome of the data (RAMP_OK), never a
+ *   plausible answer: count = 0, every ev_landmark is -1, ev_residual and ev_ray are NaN, [4] .. [7] are 0 ([1] .. [3] are
+ *   still counted by the tests above, so the sum is then short of N).
+ *   Launches, all on `stream`, nothing synchronised; the host never learns the observation count or the landmark count, every
+ *   loop is a bounded search, of fixed length or strided over a device count: a memset; the key kernel ((ordered bits of t,
+ *   index) and the segment table of ramp_se3_interp; an event that is no observation takes the all-ones key); a STABLE 64-bit
+ *   radix sort by time (hipcub); the id gather; a stable 64-bit radix sort by id; head flags; one exclusive sum (landmark
+ *   numbers, the landmarks' first positions, count); the ray kernel, one lane per SORTED position (segment search over the
+ *   knot times, in LDS up to 4096 knots, else in global memory; the pose; (c, d, q, x, y) written contiguously per landmark);
+ *   the solve kernel, one wave per landmark striding over count, lanes striding over the landmark's observations, every sum
+ *   through a fixed butterfly, refine + 2 passes over the rays.  No floating-point atomics anywhere.  A call repeats its bits,
+ *   and its landmarks -- every per-landmark output -- do not depend on the order of the events as long as no track holds two
+ *   equal time stamps (the index then decides their order, and with it the order of the sums and which observation is first).
+ *   Only the observations of this call are triangulated; nothing is carried from call to call.
+ *   N == 0: RAMP_OK, no kernel is launched: count and status are zeroed.
+ *   RAMP_EINVAL, touching nothing: N < 0, T < 1, unknown flags, min_obs < 2, refine outside 0 .. 4, min_parallax, max_rms or
+ *   sigma_px negative or not finite, max_landmarks < 1, a NULL lm_track, point, cov, n_obs, cls, rms, parallax, span, count or
+ *   status (N > 0: x, y, t, track, knots, times, intrinsics, ws), lm_track, span, t, track or times not 8-byte aligned, any
+ *   other array not 4-byte aligned, ws not 16-byte aligned.  RAMP_EUNSUPPORTED: N >= 2^31.  RAMP_EWORKSPACE: ws_bytes below
+ *   ramp_event_landmarks_ws_bytes(N, T, max_landmarks) (0 for sizes that are refused).
+ * ramp_event_landmarks_grid_events(): the number of events one trip of the full grid covers; above it the workgroups take a
+ * second trip.                                                                                                            */
+size_t ramp_event_landmarks_ws_bytes(long N, int T, long max_landmarks);
+long ramp_event_landmarks_grid_events(void);
+int ramp_event_landmarks(const float *x, const float *y, const double *t, const int64_t *track, long N, const float *knots,
+                         const double *times, int T, const float *intrinsics, int flags, int min_obs, int refine,
+                         float min_parallax, float max_rms, float sigma_px, long max_landmarks, int64_t *lm_track, float *point,
+                         float *cov, int32_t *n_obs, uint8_t *cls, float *rms, float *parallax, double *span, int32_t *count,
+                         int32_t *ev_landmark, float *ev_residual, float *ev_ray, int32_t *status, void *ws, size_t ws_bytes,
+                         void *stream);
+
 /* ---------------------------------------------------------------- IMU: preintegration and alignment (csrc/imu.hip)
  *
  * A monocular trajectory has an arbitrary unit and no notion of down.  These entries take raw IMU samples and the trajectory as

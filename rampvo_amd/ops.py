@@ -58,6 +58,8 @@ _STATUS = {
                       ("n_events", "n_not_finite", "n_outside", "n_border", "n_no_inner_arc", "n_no_outer_arc", "n_corners")),
     "event_corner_tracks": ({"bad_order": _BAD_ORDER},
                             ("n_events", "n_not_finite", "n_outside", "n_not_corner", "n_born", "n_carried", "n_linked")),
+    "event_landmarks": ({"bad_times": _BAD_TIMES},
+                        ("n_no_track", "n_not_finite", "n_out_of_range", "n_observations", "n_tracks", "n_cut_off", "n_valid")),
     "invdepth_map": ({"bad_cam": (_lib.RAMP_DEPTHMAP_BAD_CAM, "the camera pose at t_ref is not finite")},
                      ("n_considered", "n_bad_depth", "n_rejected", "n_out_of_reach", "n_contributing", "n_empty_pixels")),
     "se3_interp": ({"bad_times": _BAD_TIMES}, ("n_below", "n_above", "n_nan")),
@@ -1331,6 +1333,82 @@ def corner_track_state(state):
     return {"t": state[..., 0].contiguous().view(torch.float64), "track": state[..., 1].clone(),
             "t0": state[..., 2].contiguous().view(torch.float64), "x0": pix % width, "y0": torch.div(pix, width, rounding_mode="floor"),
             "length": (state[..., 3] >> 32).to(torch.int32)}
+
+
+def event_landmarks(x, y, t, track, knots, times, intrinsics, min_obs=3, refine=2, min_parallax=0.02, max_rms=2.0, sigma_px=1.0,
+                    max_landmarks=None, extrapolate=False, want_index=False, want_residual=False, want_rays=False):
+    """Event landmarks on the device (include/ramp_hip.h ``ramp_event_landmarks``): every corner track, seen from the camera
+    poses at its own events' time stamps, is triangulated into one 3-D point -- a midpoint solve, ``refine`` (0 .. 4)
+    Gauss-Newton steps on the reprojection error in pixels, the covariance ``sigma_px``^2 H^-1 and a class.
+
+    ``x, y`` [N] pixel coordinates of the pinhole camera ``intrinsics`` (fx, fy, cx, cy) -- rectify raw pixels first; ``t`` [N]
+    float64; ``track`` [N] int64, ``event_corner_tracks``' ``track`` (negative: the event observes nothing); ``knots`` [T,7]
+    CAMERA-TO-WORLD with ``times`` [T] float64, as ``Ramp_vo.trajectory()`` returns them.  An event outside the knots' range
+    observes nothing unless ``extrapolate``.  ``max_landmarks=None``: min(N, 2**20), at least 1; the tracks with the highest
+    ids are cut off and counted.  ``min_obs`` = 3, ``refine`` = 2, ``min_parallax`` = 0.02 rad, ``max_rms`` = 2 pixels and
+    ``sigma_px`` = 1 are defaults nobody has tuned.
+
+    Returns a dict of device tensors, nothing synchronised: ``count`` int32 [1] and, over ``max_landmarks`` rows of which the
+    first ``count`` are written, in ascending id: ``track`` int64, ``point`` [.,3] and ``cov`` [.,6] (xx, xy, xz, yy, yz, zz;
+    both NaN unless ``cls`` is 7, so ``PointMap.insert(point, count=count)`` drops the rest by itself), ``n_obs`` int32, ``cls``
+    uint8 (1 fewer than ``min_obs`` observations, 2 parallax below ``min_parallax``, 3 the midpoint system is singular, 4 the
+    point lies behind or too near a camera, 5 rms above ``max_rms``, 6 not finite, 7 valid), ``rms`` in pixels, ``parallax`` in
+    radians, ``span`` float64 [.,2] (first and last time stamp); ``status`` int32 [8] (``event_landmarks_status``); with
+    ``want_index`` ``index`` int32 [N] (the event's landmark number, -1), with ``want_residual`` ``residual`` [N,2] (pixels;
+    NaN), with ``want_rays`` ``rays`` [N,6] (camera centre and world direction; NaN).  Only the observations of this call are
+    triangulated.  A call repeats its bits; time stamps of the knots that decrease or are not finite give ``count`` = 0 and
+    set bit 0 of ``status[0]``: never a plausible answer."""
+    name = "event_landmarks"
+    if isinstance(min_obs, bool) or not isinstance(min_obs, int) or min_obs < 2:
+        raise RuntimeError(name + ": min_obs is an integer, at least 2")
+    if isinstance(refine, bool) or not isinstance(refine, int) or not 0 <= refine <= 4:
+        raise RuntimeError(name + ": refine is an integer in 0 .. 4")
+    for k, v in (("min_parallax", min_parallax), ("max_rms", max_rms), ("sigma_px", sigma_px)):
+        if not 0.0 <= float(v) <= 3.4028234663852886e38:
+            raise RuntimeError(name + ": %s is finite and not negative" % k)
+    if max_landmarks is not None and (isinstance(max_landmarks, bool) or not isinstance(max_landmarks, int) or max_landmarks < 1):
+        raise RuntimeError(name + ": max_landmarks is a positive integer or None")
+    xf, yf, tf, _ = _events(x, y, t, None)
+    N = xf.shape[0]
+    if track.dtype != torch.int64:
+        raise RuntimeError(name + ": track is int64 (event_corner_tracks' track)")
+    tr = track.reshape(-1).contiguous()
+    _same_length(name, "x, y, t and track", N, yf, tf, tr)
+    knots = knots.reshape(-1, 7).contiguous().float()
+    times = times.reshape(-1).contiguous().double()
+    T = knots.shape[0]
+    if T < 1 or times.shape[0] != T:
+        raise RuntimeError("%s: %d knots but %d time stamps (at least one knot)" % (name, T, times.shape[0]))
+    if N >= 2 ** 31:
+        check(_lib.RAMP_EUNSUPPORTED, "ramp_event_landmarks")
+    require_cuda(x, y, t, track, knots, times)
+    dev = xf.device
+    K = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev).reshape(4).contiguous()
+    L = max(1, min(N, 2 ** 20)) if max_landmarks is None else max_landmarks
+    e = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    res = {"track": e(L, torch.int64), "point": e((L, 3), torch.float32), "cov": e((L, 6), torch.float32), "n_obs": e(L, torch.int32),
+           "cls": e(L, torch.uint8), "rms": e(L, torch.float32), "parallax": e(L, torch.float32), "span": e((L, 2), torch.float64),
+           "count": e(1, torch.int32), "status": e(8, torch.int32)}
+    if want_index:
+        res["index"] = e(N, torch.int32)
+    if want_residual:
+        res["residual"] = e((N, 2), torch.float32)
+    if want_rays:
+        res["rays"] = e((N, 6), torch.float32)
+    ws, nbytes = sized_workspace("ramp_event_landmarks_ws_bytes", (N, T, L), dev, "evlandmarks")
+    opt = lambda k: ptr(res[k]) if k in res and N else None
+    check(lib().ramp_event_landmarks(ptr(xf), ptr(yf), ptr(tf), ptr(tr), N, ptr(knots), ptr(times), T, ptr(K),
+                                     _lib.RAMP_INTERP_EXTRAPOLATE if extrapolate else 0, min_obs, refine, float(min_parallax),
+                                     float(max_rms), float(sigma_px), L, ptr(res["track"]), ptr(res["point"]), ptr(res["cov"]),
+                                     ptr(res["n_obs"]), ptr(res["cls"]), ptr(res["rms"]), ptr(res["parallax"]), ptr(res["span"]),
+                                     ptr(res["count"]), opt("index"), opt("residual"), opt("rays"), ptr(res["status"]), ptr(ws),
+                                     nbytes, stream()), "ramp_event_landmarks")
+    return res
+
+
+def event_landmarks_status(status):
+    """The status words of ``event_landmarks`` as a dict: the bits of word 0 by name, then the counters (synchronises: one small copy)."""
+    return _status("event_landmarks", status)
 
 
 # ------------------------------------------------------------------- IMU

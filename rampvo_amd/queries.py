@@ -904,6 +904,85 @@ class TrackerQueries:
         return dict(depth_status=ops.event_dsi_status(out["status"]), points_status=st,
                     map_status=ops.point_map_status(map_status), count=st["n_lifted"])
 
+    # ---------------------------------------------------------------- event landmarks
+    _LANDMARK_KEYS = ("min_obs", "refine", "min_parallax", "max_rms", "sigma_px", "max_landmarks", "extrapolate", "want_index",
+                      "want_residual", "want_rays")
+
+    def event_landmarks(self, x, y, t, p=None, distorted=False, denoise=False, carry=True, insert=False, as_tensor=False, **params):
+        """The sparse landmark map of the next stretch of the sensor's stream: ``event_corner_tracks`` links the corners of
+        these events into tracks, ``ops.event_landmarks`` triangulates every track from the camera poses at its own events'
+        time stamps, with the trajectory as it is now (``params``: the detector's and the linker's -- ``max_dt`` is required --
+        and the triangulation's ``min_obs``, ``refine``, ``min_parallax``, ``max_rms``, ``sigma_px``, ``max_landmarks``,
+        ``extrapolate``, ``want_index``, ``want_residual``, ``want_rays``; its defaults are numbers nobody has tuned).
+
+        ``x, y`` are RAW SENSOR PIXELS at the tracker's image size: the tracks are linked on them, with ``p``, ``denoise`` and
+        ``carry`` exactly as ``event_corner_tracks`` takes them.  The rays take the coordinates of the images the tracker is
+        fed: the same pixels, or with ``distorted=True`` those of ``rectify_events`` (the camera of ``set_camera``; raises
+        without one) -- an event without a solution is a NaN row and is counted in word [2].  Trajectory, time stamps and
+        intrinsics are those of ``compensate_events``.  ONLY THE OBSERVATIONS OF THIS CALL are triangulated: the track ids
+        carry on from call to call, partial sums of a track do not.  ``insert=True``: the points go into ``event_map()`` with
+        the confidence 1 / trace(cov) and the frame counter as the view; a landmark that is not valid is a NaN row, which
+        the map drops and counts; the result gains ``map_status``.
+
+        Returns the union of ``event_corner_tracks``' dict and ``ops.event_landmarks``' -- per event ``track`` and the
+        linker's other outputs, per landmark ``lm_track`` (the id), ``point``, ``cov``, ``n_obs``, ``lm_cls``, ``rms``,
+        ``parallax``, ``span``, ``count``, ``status`` (the triangulation's; the linker's ``cls`` and ``status`` stay ``cls``
+        and ``track_status``).  A device-resident state stays device resident.  ``as_tensor=True``: device tensors, ordered on
+        the current stream, nothing synchronised.  Otherwise numpy arrays, the per-landmark ones cut to ``count`` (an int),
+        which waits and raises on what ``event_corner_tracks`` raises on, when the frames' time stamps decrease or are not
+        finite, and on trajectory()'s unresolved bit."""
+        name = "event_landmarks()"
+        keys = self._CORNER_KEYS + self._TRACK_KEYS + self._LANDMARK_KEYS
+        unknown = sorted(set(params) - set(keys))
+        if unknown:
+            raise RuntimeError(name + ": unknown parameter %s (known: %s)" % (unknown[0], ", ".join(keys)))
+        if not self.tlist:
+            raise RuntimeError(name + ": no frame has been tracked yet")
+        if insert:
+            pm = self.event_map()
+        td = self._as_device(t, torch.float64)
+        rect = None
+        if distorted:
+            xr, yr, rect = self._undistorted(name, x, y)
+        else:
+            xr, yr = self._as_device(x, torch.float32), self._as_device(y, torch.float32)
+        carried = self._track_state
+        trk = self.event_corner_tracks(x, y, td, p=p, as_tensor=True, denoise=denoise, carry=carry,
+                                       **{k: v for k, v in params.items() if k not in self._LANDMARK_KEYS})
+        knots, _ = self.trajectory(as_tensor=True)
+        tdev = self._frame_times_dev()
+        with self._state_stream() as sc:                      # reads of the state, on the stream it lives on
+            K = self.intrinsics_[0] * float(self.RES)
+            sc.leaves(K)
+        with torch.no_grad():
+            lm = ops.event_landmarks(xr, yr, td, trk["track"], knots, tdev, K,
+                                     **{k: v for k, v in params.items() if k in self._LANDMARK_KEYS})
+            out = {**trk, **lm, "track": trk["track"], "lm_track": lm["track"], "cls": trk["cls"], "lm_cls": lm["cls"],
+                   "track_status": trk["status"]}
+            if insert:
+                c = lm["cov"]
+                out["map_status"] = pm.insert(lm["point"], conf=1.0 / (c[:, 0] + c[:, 3] + c[:, 5]), count=lm["count"],
+                                              view=int(self.counter))
+        if rect is not None:
+            out["rectify_status"] = rect
+        if as_tensor:
+            return out
+        # (the one wait: the linker's words were not looked at by its as_tensor form)
+        words = [s.reshape(-1)[:1] for s in (out.get("filter_status"), out["corner_status"], out["track_status"]) if s is not None]
+        try:
+            for word in torch.cat(words).cpu().tolist():
+                _raise_on_words(name, {"filter": word})
+        except RuntimeError:
+            if carry:
+                self._track_state = carried                    # (a bad order leaves what is carried as it was)
+            raise
+        _check_status(name, rectify=rect, traj=self._traj_status, interp=lm["status"])
+        k = int(out["count"].cpu())
+        per_landmark = ("lm_track", "point", "cov", "n_obs", "lm_cls", "rms", "parallax", "span")
+        res = {key: (v[:k] if key in per_landmark else v).cpu().numpy() for key, v in out.items()}
+        res["count"] = k
+        return res
+
     def event_map_points(self, min_points=2, min_views=1, as_tensor=False):
         """The event map as it is now (``event_map().export``): the mean point of every voxel that holds at least ``min_points``
         points from at least ``min_views`` views (of 64: view ids wrap), sorted by voxel key.  ``as_tensor=True``: the dict of
